@@ -62,6 +62,58 @@ def _trace(what):
             fh.write("%s %s %.6f\n" % (os.environ.get("RANK", "0"), what, time.time()))
 
 
+DUMP_BYTES = 64 << 20          # --dump-outputs: at most this much array data in all (every rank's files together)
+DUMP_SEED = 20240611           # the fixed seed of the sample of an output larger than its share
+
+
+def dump_outputs(dirname, rank, world, arrays):
+    """--dump-outputs DIR: what the timed path handed its caller in the last timed step, as DIR/<name>.npy (rank r > 0 of a
+    multi-GPU run: <name>_rank<r>.npy).  arrays = {name: tensor or ndarray}; a complex array gets a trailing axis of 2 (real,
+    imaginary) in float64 (complex128) or float32 (complex64).  A 2-D output larger than this rank's share of DUMP_BYTES is
+    written as a fixed sample: every row and a seeded, sorted set of columns (and of rows when there are too many of them), the
+    indices beside it as <name>_rows.npy / <name>_cols.npy -- the same positions on every run with the same arguments."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    sfx = "_rank%d" % rank if rank > 0 else ""
+    small = {k: v for k, v in arrays.items() if getattr(v, "ndim", 0) < 2}
+    budget = (DUMP_BYTES // max(1, world)) - sum(np.asarray(v).nbytes for v in small.values()) - (1 << 20)
+    big = [k for k in arrays if k not in small]
+    out = {}
+    for name, a in arrays.items():
+        if name in big:
+            rows, cols, esize = a.shape[0], a.shape[1], a.element_size()
+            share = budget // len(big)
+            if rows * cols * esize > share:
+                rng = np.random.default_rng(DUMP_SEED)           # (a kept row or column costs its indices' 8 bytes too)
+                nr = max(1, min(rows, share // (min(cols, 4096) * esize + 8)))
+                nc = max(1, min(cols, (share - 8 * nr) // (nr * esize + 8)))
+                r_idx = np.arange(rows) if nr == rows else np.sort(rng.choice(rows, nr, replace=False))
+                c_idx = np.sort(rng.choice(cols, nc, replace=False))
+                dev = a.device
+                import torch
+                a = a.index_select(0, torch.as_tensor(r_idx, device=dev)).index_select(1, torch.as_tensor(c_idx, device=dev))
+                out[name + "_rows"] = r_idx.astype(np.float64)
+                out[name + "_cols"] = c_idx.astype(np.float64)
+            a = a.cpu().numpy()
+        a = np.asarray(a)
+        if np.iscomplexobj(a):
+            a = np.ascontiguousarray(a).view(np.float64 if a.dtype == np.complex128 else np.float32).reshape(a.shape + (2,))
+        out[name] = a.astype(np.float32 if a.dtype == np.float32 else np.float64, copy=False)
+    for name, a in out.items():
+        np.save(os.path.join(dirname, name + sfx + ".npy"), a)
+    return sorted(out)
+
+
+def _barrier(dist, dry):
+    """dist.barrier(), but in a --dry-run a 1-element all_reduce over the CPU (gloo) ranks: torch's barrier first looks up the machine's
+    accelerator (torch._C._get_accelerator), which on a GPU box starts the HIP runtime and opens the GPU in every CPU-only rank."""
+    if dry:
+        import torch
+        dist.all_reduce(torch.zeros(1))
+    else:
+        dist.barrier()
+
+
 class DryEngine:
     """--dry-run only (tests/test_bench_plumbing.py): stands where RxaEngine stands so that the argument / rank / channel
     split / barrier / max-over-ranks / JSON plumbing of this file can run in CPU processes.  It does no DSP; a line made
@@ -350,6 +402,7 @@ def sharded_config(args, torch, dist, shard, rank, world, local_rank, dev, dry, 
             step = leg.step
         else:
             n = 1 << (args.log2_samples if args.log2_samples != LOG2_SAMPLES else 26)       # 2^26 samples of the one stream per step
+            torch.manual_seed(5 + rank)     # the stream's input (torch.randn in setup_config5): the same on every run
             leg = bc.setup_config5(torch, qh, dev, n=n, unfused=False)
             samples_rank = float(n)
             step = leg.step_fused
@@ -361,21 +414,25 @@ def sharded_config(args, torch, dist, shard, rank, world, local_rank, dev, dry, 
         sync()
         _trace("warm_done")
         if world > 1:
-            dist.barrier()
+            _barrier(dist, dry)
         sync()
         _trace("timed_start")
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            step()
+            last[0] = step()
         sync()
         _trace("steps_done")
         if world > 1:
-            dist.barrier()
+            _barrier(dist, dry)
         sync()
         _trace("timed_end")
         return shard.max_over_ranks(time.perf_counter() - t0, dev if not dry else None)
 
+    last = [None]
     dt = timed_run()
+    if args.dump_outputs:               # config 4: every channel's audio; config 5: the valid part of the bandpass output
+        dump_outputs(args.dump_outputs, rank, world,
+                     {"y": torch.zeros((nch, 8), dtype=torch.complex128) if dry else leg.y if cfg == 4 else leg.yo[:, :last[0]]})
     # the dominant kernel's own time on this rank, HIP events on the stream it is launched on
     if dry:
         kname, kms, algo = "dry", 1.0, 20.0
@@ -426,7 +483,7 @@ def sharded_config(args, torch, dist, shard, rank, world, local_rank, dev, dry, 
             line["dry"] = {"rank0_channels": [first, first + nch], "steps_run": leg.calls}
         print(json.dumps(line), flush=True)
     if world > 1:
-        dist.barrier()
+        _barrier(dist, dry)
         dist.destroy_process_group()
 
 
@@ -498,7 +555,12 @@ def main():
     ap.add_argument("--ingest", choices=["f64", "le24"], default="f64",
                     help="f64: complex double input resident in HBM (the BASELINE workload); le24: the same signal as "
                          "24-bit little-endian IQ bytes (quisk_read_rx_udp wire format), decoded in the front kernel's load")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (float64 / float32; "
+                         "an output above 64 MB in all as a fixed, seeded sample, its indices beside it)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
     if args.channels is None:
         args.channels = 1 if args.config == 5 else NCH
 
@@ -536,7 +598,7 @@ def main():
             dist.init_process_group("nccl", rank=rank, world_size=world, device_id=dev)
         else:
             dist.init_process_group(backend, rank=rank, world_size=world)
-        dist.barrier()
+        _barrier(dist, dry)
 
     if args.config != 2:
         return sharded_config(args, torch, dist, shard, rank, world, local_rank, dev, dry, sync)
@@ -612,7 +674,7 @@ def main():
         sync()
         _trace("warm_done")
         if world > 1:
-            dist.barrier()
+            _barrier(dist, dry)
         sync()
         _trace("timed_start")
         t0 = time.perf_counter()
@@ -621,13 +683,18 @@ def main():
         sync()
         _trace("steps_done")
         if world > 1:
-            dist.barrier()
+            _barrier(dist, dry)
         sync()
         _trace("timed_end")
         return shard.max_over_ranks(time.perf_counter() - t0, dev if not dry else None)
 
     dt = timed_run()                    # the measurement `value` reports
     meter_db = [eng.GetRXAMeter(0, mt) for mt in (1, 3, 6)] if args.meters == "on" else None
+    if args.dump_outputs:               # the last timed step's output (before the meters-off run below writes y again) and meters
+        outs = {"y": y}
+        if args.meters == "on":
+            outs["meters_dB"] = [[eng.GetRXAMeter(c, mt) for mt in (1, 3, 6)] for c in range(nch)]
+        dump_outputs(args.dump_outputs, rank, world, outs)
     dt_off = None
     if args.meters == "on":             # the same steps once more with the meters off, reported beside it
         eng.enable_meters(False)
@@ -832,7 +899,7 @@ def main():
                                         "sample": "failed: %r" % (exc,)}
         print(json.dumps(line), flush=True)
     if world > 1:
-        dist.barrier()
+        _barrier(dist, dry)
         dist.destroy_process_group()
 
 

@@ -159,3 +159,37 @@ def test_config_2_line_carries_every_ranks_roofline():
     j = _launch(2, ["--channels", "8"])
     assert all({"achieved", "peak", "unit", "kernel"} <= set(p["roofline"]) for p in j["per_rank"])
     assert j["roofline"]["bound"] in ("hbm", "valu", "latency") and "bound_evidence" in j["roofline"]
+
+
+def test_dump_outputs_of_two_ranks(tmp_path):
+    """--dump-outputs DIR: every rank writes what its timed path computed in its last step (rank 0 under the plain names, rank r > 0 with
+    _rank<r>), as float64 arrays: the audio as [channels, samples, 2] and, with the meters on, each channel's three meter readings."""
+    import numpy as np
+    d = tmp_path / "dump"
+    j = _launch(2, ["--channels", "8", "--dump-outputs", str(d)])
+    assert j["steps"] == 4 and j["ms_per_step"] > 0
+    for sfx in ("", "_rank1"):
+        y, m = np.load(d / ("y%s.npy" % sfx)), np.load(d / ("meters_dB%s.npy" % sfx))
+        assert y.dtype == np.float64 and y.shape == (8, 8, 2)
+        assert m.dtype == np.float64 and m.shape == (8, 3)
+    assert sum(f.stat().st_size for f in d.iterdir()) <= 64 << 20
+
+
+def test_dump_outputs_samples_a_large_output(tmp_path):
+    """An output above the 64 MB budget goes out as a seeded sample: every row, a fixed sorted set of columns, the indices beside it."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    y = torch.randn((16, 1 << 19), dtype=torch.complex128, generator=torch.Generator().manual_seed(1))       # 128 MiB
+    names = bench.dump_outputs(str(tmp_path / "a"), 0, 1, {"y": y})
+    bench.dump_outputs(str(tmp_path / "b"), 0, 1, {"y": y})
+    assert names == ["y", "y_cols", "y_rows"]
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= 64 << 20
+    for n in names:
+        assert np.array_equal(np.load(tmp_path / "a" / (n + ".npy")), np.load(tmp_path / "b" / (n + ".npy")))
+    got = np.load(tmp_path / "a" / "y.npy")
+    rows, cols = (np.load(tmp_path / "a" / (n + ".npy")).astype(int) for n in ("y_rows", "y_cols"))
+    assert rows.tolist() == list(range(16)) and cols.size > 100000 and np.all(np.diff(cols) > 0)
+    want = y.numpy()[np.ix_(rows, cols)]
+    assert np.array_equal(got[..., 0], want.real) and np.array_equal(got[..., 1], want.imag)

@@ -1,12 +1,13 @@
 """The EMNR tables compiled into the library (quisk_amd/build.py: _emnr_tables_source -> qh_emnr_tables_gen.cpp) are WDSP's own compiled-in
 fall-backs: wdsp/calculus.c (GG, GGS) and wdsp/zetahat.c, which emnr.c:207-225, 322-326 takes when `calculus` / `zetaHat.bin` are not in the
 working directory."""
+import hashlib
+import json
 import os
 import re
 import struct
 
 import numpy as np
-import pytest
 
 
 def _generated(tmp_path):
@@ -34,17 +35,13 @@ def test_generated_tables_are_the_shipped_data(tmp_path):
     assert np.array_equal(g["kEmnrDefaultZeta"][~none], z["zeta_hat"][~none]) and not np.any(g["kEmnrDefaultZeta"][none]) and not np.any(ok & none)
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/wdsp/zetahat.c"), reason="the reference tree is not mounted here")
 def test_generated_tables_are_the_references_compiled_in_ones(tmp_path):
+    """Pinned by tests/golden/emnr_tables_pin.json: the SHA-256 of the numbers of wdsp/calculus.c and wdsp/zetahat.c (little-endian float64,
+    int32 for the valid flags) and the four range constants, read out of the reference files by tests/golden/make_emnr_tables_pin.py."""
     g = _generated(tmp_path)
-    cal = open("/root/reference/wdsp/calculus.c").read()
-    nums = np.array([float(x) for x in re.findall(r"[-+]?\d+\.\d+(?:[eE][-+]?\d+)?", cal)])
-    assert nums.size == 2 * 241 * 241
-    assert np.array_equal(nums[:241 * 241], g["kEmnrDefaultGG"]) and np.array_equal(nums[241 * 241:], g["kEmnrDefaultGGS"])
-    zh = open("/root/reference/wdsp/zetahat.c").read()
-    data = re.search(r"zetaHatDefaultData\s*\[[^\]]*\]\s*=\s*\{(.*?)\};", zh, re.S).group(1)
-    valid = re.search(r"zetaHatDefaultValid\s*\[[^\]]*\]\s*=\s*\{(.*?)\};", zh, re.S).group(1)
-    assert np.array_equal(np.array([float(t) for t in data.replace("\n", " ").split(",")]), g["kEmnrDefaultZeta"])
-    assert np.array_equal(np.array([int(t) for t in valid.replace("\n", " ").split(",")]), g["kEmnrDefaultValid"])
-    rng = [float(re.search(r"zetaHatDefault%s\s*=\s*([^;]+);" % k, zh).group(1)) for k in ("Gmin", "Gmax", "Ximin", "Ximax")]
-    assert rng == list(g["kEmnrDefaultRange"])
+    pin = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "emnr_tables_pin.json")))
+    for key, name, dt in (("GG", "kEmnrDefaultGG", "<f8"), ("GGS", "kEmnrDefaultGGS", "<f8"), ("zeta", "kEmnrDefaultZeta", "<f8"),
+                          ("valid", "kEmnrDefaultValid", "<i4")):
+        a = np.ascontiguousarray(g[name], dtype=dt)
+        assert a.size == pin[key]["count"] and hashlib.sha256(a.tobytes()).hexdigest() == pin[key]["sha256"], key
+    assert list(g["kEmnrDefaultRange"]) == pin["range"]

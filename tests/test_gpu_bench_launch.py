@@ -68,3 +68,23 @@ def test_plain_python_launch():
     assert live and "failed" not in live, live
     assert r["traffic"] is not None and 0.9 < r["traffic"] / r["algorithmic_bytes_per_launch"] < 1.3, (r["traffic"], r["algorithmic_bytes_per_launch"])
     assert 15.0 < live["front"] < 26.0 and 6.0 < live["band"] < 12.0
+
+
+def test_dump_outputs_are_the_same_from_run_to_run(tmp_path):
+    """--dump-outputs: two runs with the same arguments write the same bits (the inputs are seeded, the chain is deterministic), and what
+    is written is the timed path's audio -- the in-band tone at the panel gain of 4 -- and its meters."""
+    import numpy as np
+    args = ARGS + ["--no-le24", "--no-host-fed", "--no-live-traffic", "--no-other-configs"]
+    for d in ("a", "b"):
+        _check(_line([sys.executable, "bench.py"] + args + ["--dump-outputs", str(tmp_path / d)]))
+    names = sorted(f.name for f in (tmp_path / "a").iterdir())
+    assert names == sorted(f.name for f in (tmp_path / "b").iterdir()) == ["meters_dB.npy", "y.npy", "y_cols.npy", "y_rows.npy"]
+    for n in names:
+        assert np.array_equal(np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)), n
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= 64 << 20
+    # 256 x 2^16 audio samples are 256 MiB: every channel, a seeded set of sample positions
+    y, rows, cols = (np.load(tmp_path / "a" / n) for n in ("y.npy", "y_rows.npy", "y_cols.npy"))
+    assert y.dtype == np.float64 and rows.tolist() == list(range(256)) and y.shape == (256, cols.size, 2)
+    assert 10000 < cols.size < (1 << 16) and np.all(np.diff(cols) > 0) and cols[-1] < (1 << 16)
+    assert abs(np.abs(y[0, :, 0] + 1j * y[0, :, 1]).mean() / 0.1 - 4.0) < 1e-2
+    assert np.load(tmp_path / "a" / "meters_dB.npy").shape == (256, 3)

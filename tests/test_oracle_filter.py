@@ -1,5 +1,5 @@
 """The filter.c restatement (oracle/quisk_oracle.c) against golden vectors generated from the reference's
-own filter.c, and -- when oracle/_ref is present -- bit-exact against that build on fresh random input."""
+own filter.c, and bit-exact against that build's outputs on seeded random input (tests/golden/ref_build_golden.npz)."""
 import os
 
 import numpy as np
@@ -77,21 +77,31 @@ def test_golden_cascade_config5(oracle, gold):
     assert np.array_equal(out, gold["cascade_8hb45_d5"])
 
 
-def test_bit_exact_against_reference_build(oracle):
-    po = oracle
-    if po.ref_filter_lib() is None:
-        pytest.skip("oracle/_ref not built (the reference tree is not mounted here)")
+REF_GOLD = os.path.join(os.path.dirname(__file__), "golden", "ref_build_golden.npz")
+BIT_EXACT_CUTS = ((0, 13), (13, 14), (14, 2500), (2500, 4000))
+
+
+def bit_exact_cases():
+    """(ntaps, decim), taps, input of test_bit_exact_against_reference_build -- tests/golden/make_ref_build_golden.py replays the same
+    cases on the reference build."""
     rng = np.random.default_rng(77)
     for ntaps, d in ((5, 1), (50, 2), (147, 3), (1023, 32), (64, 7)):
         taps = rng.standard_normal(ntaps)
-        x = stream(rng.integers(1 << 30), 4000)
-        a, b = po.OracleFir(taps), po.RefFir(taps)
-        for lo, hi in ((0, 13), (13, 14), (14, 2500), (2500, 4000)):
-            assert np.array_equal(a.cDecimate(x[lo:hi], d), b.cDecimate(x[lo:hi], d))
-    a, b = po.OracleHB45(), po.RefHB45()
+        yield (ntaps, d), taps, stream(rng.integers(1 << 30), 4000)
+
+
+def test_bit_exact_against_reference_build(oracle):
+    """Every call's output, bit for bit, as the reference's own filter.c (oracle/_ref) put it out: tests/golden/ref_build_golden.npz."""
+    po = oracle
+    ref = np.load(REF_GOLD)
+    for (ntaps, d), taps, x in bit_exact_cases():
+        a = po.OracleFir(taps)
+        for lo, hi in BIT_EXACT_CUTS:
+            assert np.array_equal(a.cDecimate(x[lo:hi], d), ref["fir_%d_%d_%d" % (ntaps, d, lo)]), (ntaps, d, lo)
+    a = po.OracleHB45()
     x = stream(5, 3001)
-    assert np.array_equal(a.cDecim2(x[:1001]), b.cDecim2(x[:1001]))
-    assert np.array_equal(a.cDecim2(x[1001:]), b.cDecim2(x[1001:]))
+    assert np.array_equal(a.cDecim2(x[:1001]), ref["hb45_0"])
+    assert np.array_equal(a.cDecim2(x[1001:]), ref["hb45_1001"])
 
 
 def test_decimator_is_plain_convolution(oracle):
