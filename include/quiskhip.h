@@ -175,7 +175,7 @@ int qh_rxa_SetRXACTCSSRun(qh_rxa *e, int ch, int run);
  * the extent of the rows themselves (first sample of the first row to last sample of the last), not by where the matrices lie. */
 int qh_rxa_process(qh_rxa *e, const double *d_in, long long in_stride, double *d_out, long long out_stride, int nblk);
 
-/* Same with host buffers (synchronous; pageable memory; includes the PCIe copies). */
+/* Same with host buffers (synchronous; pageable memory; includes the PCIe copies).  h_out == h_in is allowed (rows of its own on the device). */
 int qh_rxa_process_host(qh_rxa *e, const double *h_in, long long in_stride, double *h_out, long long out_stride, int nblk);
 
 /* Tiles of the time-tiled FM loop that had to be re-run sequentially so far (diagnostics; 0 on carriers, a fraction of a
@@ -342,7 +342,8 @@ int qh_fir_reset(qh_fir *f);                                   /* history and ph
 int qh_fir_set_state(qh_fir *f, const void *hist, int phase);
 int qh_fir_out_count(const qh_fir *f, int n_in);               /* outputs the next call with n_in samples produces */
 /* d_in [nch][in_stride], d_out [nch][out_stride] device pointers (strides in complex samples); *n_out = outputs
- * per channel (may be 0).  Asynchronous on the filter's stream.  In-place (d_out == d_in) is not supported. */
+ * per channel (may be 0).  Asynchronous on the filter's stream.  Output rows that share any byte with the input rows are refused
+ * (QH_ERR_INVALID, nothing enqueued, no state moved); the _host form stages through device rows of its own and takes h_out == h_in. */
 int qh_fir_process(qh_fir *f, const void *d_in, long long in_stride, int n_in, void *d_out, long long out_stride, int *n_out);
 int qh_fir_process_host(qh_fir *f, const void *h_in, long long in_stride, int n_in, void *h_out, long long out_stride, int *n_out);
 int qh_fir_synchronize(qh_fir *f);
@@ -353,9 +354,9 @@ void qh_hb45_taps(double *taps43);
 /* `nstage` (1..8) consecutive quisk_cDecim2HB45 stages (filter.c:377-417; chained at quisk.c:1772-1796) over
  * `nch` complex streams in ONE pass over HBM: decimation 2^nstage, state (the input history) carried between
  * calls.  n_in must be a multiple of 2^nstage; n_in / 2^nstage outputs per channel.  dtype QH_F64 / QH_F32.
- * Results equal nstage calls of quisk_cDecim2HB45 to rounding (time-domain sums, not FFT).  In-place (d_out over d_in) is not
- * supported: the time segments of a call run side by side (the drop-in quisk_cDecim2HB45, which works in place like the reference's, goes
- * through rows of its own). */
+ * Results equal nstage calls of quisk_cDecim2HB45 to rounding (time-domain sums, not FFT).  Output rows that share any byte with the
+ * input rows are refused (QH_ERR_INVALID, before anything runs): the time segments of a call run side by side (the drop-in
+ * quisk_cDecim2HB45, which works in place like the reference's, goes through rows of its own; so does qh_hbc_process_host, h_out == h_in). */
 typedef struct qh_hbc qh_hbc;
 qh_hbc *qh_hbc_create(int device, int nch, int nstage, int dtype, void *stream);
 void qh_hbc_destroy(qh_hbc *h);
@@ -377,6 +378,7 @@ int qh_rat_reset(qh_rat *h);
 int qh_rat_set_state(qh_rat *h, const void *hist, int phase);
 int qh_rat_phase(const qh_rat *h);
 int qh_rat_out_count(const qh_rat *h, int n_in);
+/* Output rows that share any byte with the input rows are refused (QH_ERR_INVALID, state untouched); _host takes h_out == h_in. */
 int qh_rat_process(qh_rat *h, const void *d_in, long long in_stride, int n_in, void *d_out, long long out_stride, int *n_out);
 int qh_rat_process_host(qh_rat *h, const void *h_in, long long in_stride, int n_in, void *h_out, long long out_stride, int *n_out);
 int qh_rat_synchronize(qh_rat *h);
@@ -405,7 +407,8 @@ int qh_pan_count(const qh_pan *p);          /* FFTs averaged since the last qh_p
  * panadapter's own transform serves both (panfir16k_kernel, qh_pan.hip) and the stream is read once.  qh_pan_feed_decimate
  * takes whole blocks (n a multiple of fft_size, the panadapter at a block boundary) and writes n / decim samples per channel
  * exactly as quisk_cDecimate(cSamples, n, filter, decim) leaves them, state carried between calls; other shapes are refused
- * (QH_ERR_UNSUPPORTED): qh_fir beside qh_pan_feed does those. */
+ * (QH_ERR_UNSUPPORTED): qh_fir beside qh_pan_feed does those.  Output rows that share any byte with the input rows are refused
+ * (QH_ERR_INVALID, before the block count or the delay line moves). */
 int qh_pan_attach_fir(qh_pan *p, const double *taps, int ntaps, int decim);
 int qh_pan_feed_decimate(qh_pan *p, const double *d_in, long long in_stride, int n, double *d_out, long long out_stride, int *n_out);
 /* The refresh branch of get_graph: h_pixels [nch][data_width] dB, h_smeter [nch] dB (either may be NULL),
@@ -468,7 +471,8 @@ typedef struct qh_qrx_tables {
 } qh_qrx_tables;
 qh_qrx *qh_qrx_create_ex(int device, int nch, int sample_rate, int mode, int bandwidth, const qh_qrx_tables *tables, void *stream);
 int qh_qrx_decim_rate(const qh_qrx *r);
-/* d_in [nch][in_stride] complex double at sample_rate, d_out [nch][out_stride] at 48 ksps; any n_in. */
+/* d_in [nch][in_stride] complex double at sample_rate, d_out [nch][out_stride] at 48 ksps; any n_in.  Output rows that share any byte
+ * with the input rows are refused (QH_ERR_INVALID, state untouched); the _host form takes h_out == h_in. */
 int qh_qrx_process(qh_qrx *r, const double *d_in, long long in_stride, int n_in, double *d_out, long long out_stride, int *n_out);
 int qh_qrx_process_host(qh_qrx *r, const double *h_in, long long in_stride, int n_in, double *h_out, long long out_stride, int *n_out);
 int qh_qrx_synchronize(qh_qrx *r);
@@ -491,11 +495,13 @@ typedef struct qh_iq_format {
 } qh_iq_format;
 void qh_iq_format_le24(qh_iq_format *f, double gain);               /* quisk_read_rx_udp, quisk.c:3378-3392 */
 void qh_iq_format_hermes(qh_iq_format *f, int nrx, double gain);    /* read_rx_udp10 frames, quisk.c:3745-3760; channel r: chan_stride 6 */
-/* d_src: packed bytes on the device; d_dst [nch][dst_stride] complex of `dtype`. */
+/* d_src: packed bytes on the device; d_dst [nch][dst_stride] complex of `dtype`.  Output rows that share any byte with the
+ * src_bytes of d_src are refused (QH_ERR_INVALID). */
 int qh_unpack_iq(int device, void *stream, const void *d_src, long long src_bytes, const qh_iq_format *fmt, int nch,
                  long long chan_stride, int n, void *d_dst, long long dst_stride, int dtype);
 /* qh_rxa_process with the decode fused into the first kernel's load: 6 bytes per sample cross HBM instead of 16
- * and no complex-double copy of the input exists.  nblk blocks of dsp_insize samples per channel. */
+ * and no complex-double copy of the input exists.  nblk blocks of dsp_insize samples per channel.  Output rows that share any byte
+ * with the src_bytes of d_src are refused (QH_ERR_INVALID, state untouched). */
 int qh_rxa_process_packed(qh_rxa *e, const void *d_src, long long src_bytes, const qh_iq_format *fmt, long long chan_stride,
                           double *d_out, long long out_stride, int nblk);
 /* The same two from host memory (upload, run, download, synchronize). */
@@ -512,7 +518,8 @@ int qh_rxa_process_packed_host(qh_rxa *e, const void *h_src, long long src_bytes
  * stay in the sample values, as in the reference.  d_counts[4] = samples on channel 0, on channel 1, marks, packets with
  * the overrange bit; d_dc_sum[2] = sum of the channel-1 samples ahead of the DC removal: the caller keeps the estimate (the
  * reference renews it from that sum once a second of wall time, quisk.c:3947-3952).  Buffers: npackets * (packet_bytes - 2) / 6
- * entries each.  Bit-exact with the reference's loop. */
+ * entries each.  Bit-exact with the reference's loop.  Any byte shared by two of the six buffers (the source and each output) is
+ * refused (QH_ERR_INVALID). */
 int qh_unpack_udp17(int device, void *stream, const void *d_src, int npackets, int packet_bytes, double gain, int invert_spectrum,
                     double dc_re, double dc_im, void *d_ch0, void *d_ch1, int *d_marks, long long *d_counts, double *d_dc_sum);
 int qh_unpack_udp17_host(int device, const void *h_src, int npackets, int packet_bytes, double gain, int invert_spectrum, double dc_re,
@@ -534,10 +541,12 @@ typedef struct qh_audio_format {
     int kind, num_channels, channel_I, channel_Q;
     double volume, prescale;
 } qh_audio_format;
-/* qh_rxa_process with audio frames as output: d_out [nch][out_stride_bytes], nblk * dsp_outsize frames per channel. */
+/* qh_rxa_process with audio frames as output: d_out [nch][out_stride_bytes], nblk * dsp_outsize frames per channel.  Output rows
+ * that share any byte with the input rows are refused (QH_ERR_INVALID, state untouched). */
 int qh_rxa_process_audio(qh_rxa *e, const double *d_in, long long in_stride, void *d_out, long long out_stride_bytes, int nblk,
                          const qh_audio_format *fmt);
-/* Stand-alone: d_src [nch][src_stride] complex double on the device -> frames. */
+/* Stand-alone: d_src [nch][src_stride] complex double on the device -> frames.  Frames that share any byte with the source rows
+ * are refused (QH_ERR_INVALID). */
 int qh_audio_pack(int device, void *stream, const double *d_src, long long src_stride, int nch, int n, const qh_audio_format *fmt,
                   void *d_dst, long long dst_stride_bytes);
 
@@ -554,7 +563,8 @@ int qh_qagc_set_gain(qh_qagc *a, int ch, double release_gain);          /* set_a
 int qh_qagc_set_cpx(qh_qagc *a, int is_cpx);                            /* process_agc's is_cpx argument for the calls to come */
 int qh_qagc_reset(qh_qagc *a);
 int qh_qagc_process(qh_qagc *a, void *d_buf, long long stride, int n);
-/* the same from one device buffer into another */
+/* the same from one device buffer into another: d_src == d_dst with src_stride == dst_stride is qh_qagc_process (in place); any
+ * other overlap of the two sets of rows is refused (QH_ERR_INVALID, AGC state untouched) */
 int qh_qagc_process2(qh_qagc *a, const void *d_src, long long src_stride, void *d_dst, long long dst_stride, int n);
 /* diagnostics: 0 = the two regimes of the state machine as instruction chains (default), 1 = the whole machine sample by sample
    (bit-identical, ~9 times slower) */
@@ -577,8 +587,8 @@ int qh_qrx_set_ssb_squelch(qh_qrx *r, int enabled, int level);
  * where quisk_process_samples runs it (quisk.c:2448-2449: before the panadapter ring and the tune).  While on, the
  * output lags the input by qh_nb_delay() = 3 * (int)(sample_rate * 500e-6 + 0.5) samples (the reference's delay
  * line); level 0 passes samples through undelayed and freezes the delay line, as the reference does.  Levels 1..3 =
- * threshold 6.0 / 4.0 / 2.5 times the mean magnitude (set_noise_blanker, quisk.c:4605).  d_in and d_out must be
- * different buffers.  Sample rates up to about 3.5 MHz (the 500 us window has to fit one LDS tile). */
+ * threshold 6.0 / 4.0 / 2.5 times the mean magnitude (set_noise_blanker, quisk.c:4605).  Output rows that share any byte
+ * with the input rows are refused (QH_ERR_INVALID, delay line untouched); the _host form takes h_out == h_in.  Sample rates up to about 3.5 MHz (the 500 us window has to fit one LDS tile). */
 typedef struct qh_nb qh_nb;
 qh_nb *qh_nb_create(int device, int nch, int sample_rate, void *stream);
 void qh_nb_destroy(qh_nb *b);
@@ -759,7 +769,8 @@ int qh_qps_set_pipelined(qh_qps *h, int on);                               /* st
 int qh_qps_filter_rate(qh_qps *h);                                         /* get_filter_rate, quisk.c:2787 */
 int qh_qps_decim_rate(qh_qps *h);
 int qh_qps_out_capacity(qh_qps *h, int n_in);                              /* the most playback samples a call of n_in returns: out_stride >= this */
-/* device rows [nch][stride] of complex doubles; *n_out = playback samples per receiver; asynchronous on the bank's stream */
+/* device rows [nch][stride] of complex doubles; *n_out = playback samples per receiver; asynchronous on the bank's stream.  Output rows
+ * (qh_qps_out_capacity long) that share any byte with the input rows are refused (QH_ERR_INVALID, state untouched); _host takes h_out == h_in. */
 int qh_qps_process(qh_qps *h, const double *d_in, long long in_stride, int n, double *d_out, long long out_stride, int *n_out);
 int qh_qps_process_host(qh_qps *h, const double *h_in, long long in_stride, int n, double *h_out, long long out_stride, int *n_out);
 int qh_qps_synchronize(qh_qps *h);

@@ -3207,6 +3207,11 @@ int qh_rxa_process(qh_rxa *h, const double *d_in, long long in_stride, double *d
 }
 
 // ---- audio egress ---------------------------------------------------------------------------------------------------
+static long long egress_frame_bytes(const qh_audio_format *fmt)        // (a format make_egress has accepted)
+{
+    return (long long)fmt->num_channels * (fmt->kind == QH_AUDIO_I16 ? 2 : fmt->kind == QH_AUDIO_I24 ? 3 : 4);
+}
+
 static int make_egress(const qh_audio_format *fmt, void *d_out, long long out_stride_bytes, long long frames, EgressFmt *f)
 {
     if (!fmt || !d_out) return set_error(QH_ERR_INVALID, "null audio format or buffer");
@@ -3214,7 +3219,7 @@ static int make_egress(const qh_audio_format *fmt, void *d_out, long long out_st
     if (fmt->num_channels < 1 || fmt->channel_I < 0 || fmt->channel_Q < 0 || fmt->channel_I >= fmt->num_channels ||
         fmt->channel_Q >= fmt->num_channels)
         return set_error(QH_ERR_INVALID, "audio channel slots outside the frame");
-    const int bytes = fmt->kind == QH_AUDIO_I16 ? 2 : fmt->kind == QH_AUDIO_I24 ? 3 : 4;
+    const int bytes = egress_frame_bytes(fmt) / fmt->num_channels;
     if (out_stride_bytes < frames * fmt->num_channels * bytes) return set_error(QH_ERR_INVALID, "audio row stride shorter than the frames");
     if (fmt->kind != QH_AUDIO_I24 && out_stride_bytes % bytes) return set_error(QH_ERR_INVALID, "audio row stride not a multiple of the sample size");
     f->kind = fmt->kind; f->nchan = fmt->num_channels; f->ch_i = fmt->channel_I; f->ch_q = fmt->channel_Q;
@@ -3232,6 +3237,9 @@ int qh_rxa_process_audio(qh_rxa *h, const double *d_in, long long in_stride, voi
     if (in_stride < (long long)nblk * h->e.dsp_insize) return set_error(QH_ERR_INVALID, "stride shorter than nblk blocks");
     EgressFmt f{};
     if (int rc = make_egress(fmt, d_out, out_stride_bytes, (long long)nblk * h->e.dsp_outsize, &f)) return rc;
+    if (rows_overlap(d_in, in_stride * 16, (long long)nblk * h->e.dsp_insize * 16, d_out, out_stride_bytes,
+                     (long long)nblk * h->e.dsp_outsize * egress_frame_bytes(fmt), h->e.nch))
+        return set_error(QH_ERR_INVALID, "qh_rxa_process_audio: the output rows overlap the input rows (in place is not supported)");
     h->e.eg = f;
     const int rc = h->e.process(d_in, in_stride, nullptr, 0, nblk);
     h->e.eg = EgressFmt{};
@@ -3246,6 +3254,8 @@ int qh_audio_pack(int device, void *stream, const double *d_src, long long src_s
     EgressFmt f{};
     if (int rc = make_egress(fmt, d_dst, dst_stride_bytes, n, &f)) return rc;
     if (n == 0) return QH_OK;
+    if (rows_overlap(d_src, src_stride * 16, (long long)n * 16, d_dst, dst_stride_bytes, (long long)n * egress_frame_bytes(fmt), nch))
+        return set_error(QH_ERR_INVALID, "qh_audio_pack: the output rows overlap the input rows (in place is not supported)");
     QH_HIP(hipSetDevice(device));
     const long long per = ((long long)n + 255) / 256;
     hipLaunchKernelGGL(egress_pack_kernel, dim3((unsigned)(per < 1024 ? per : 1024), (unsigned)nch), dim3(256), 0, (hipStream_t)stream,
@@ -3333,6 +3343,8 @@ int qh_rxa_process_packed(qh_rxa *h, const void *d_src, long long src_bytes, con
     if (out_stride < (long long)nblk * h->e.dsp_outsize) return set_error(QH_ERR_INVALID, "stride shorter than nblk blocks");
     PackedFmt pk;
     if (int rc = qh::make_packed_fmt(fmt, chan_stride, src_bytes, (long long)nblk * h->e.dsp_insize, h->e.nch, &pk)) return rc;
+    if (rows_overlap(d_src, 0, src_bytes, d_out, out_stride * 16, (long long)nblk * h->e.dsp_outsize * 16, h->e.nch))
+        return set_error(QH_ERR_INVALID, "qh_rxa_process_packed: the output rows overlap the packed source (in place is not supported)");
     h->e.pk_src = static_cast<const unsigned char *>(d_src);
     h->e.pk = pk;
     // process() wants an input pointer; the packed kernels never touch it

@@ -97,6 +97,9 @@ int qh_fir_process(qh_fir *h, const void *d_in, long long in_stride, int n_in, v
     if (n_in <= 0) return QH_OK;                // quisk_cDecimate with count <= 0 produces nothing
     if (!d_in || !d_out) return set_error(QH_ERR_INVALID, "null buffer");
     if (in_stride < n_in || out_stride < h->b.out_count(n_in)) return set_error(QH_ERR_INVALID, "stride shorter than the data");
+    const long long es = h->b.esize;
+    if (rows_overlap(d_in, in_stride * es, n_in * es, d_out, out_stride * es, h->b.out_count(n_in) * es, h->b.nch))
+        return set_error(QH_ERR_INVALID, "qh_fir_process: the output rows overlap the input rows (in place is not supported)");
     return h->b.process(d_in, in_stride, n_in, d_out, out_stride, n_out);
 }
 

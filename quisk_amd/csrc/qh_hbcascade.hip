@@ -178,6 +178,9 @@ int qh_hbc_process(qh_hbc *h, const void *d_in, long long in_stride, int n_in, v
     if (n_in % (1 << h->nstage)) return set_error(QH_ERR_INVALID, "qh_hbc_process: n_in must be a multiple of 2^nstage = %d", 1 << h->nstage);
     if (in_stride < n_in || out_stride < (n_in >> h->nstage)) return set_error(QH_ERR_INVALID, "qh_hbc_process: stride shorter than the data");
     if (n_in == 0) return QH_OK;
+    const long long es = (long long)h->esize;
+    if (rows_overlap(d_in, in_stride * es, n_in * es, d_out, out_stride * es, (long long)(n_in >> h->nstage) * es, h->nch))
+        return set_error(QH_ERR_INVALID, "qh_hbc_process: the output rows overlap the input rows (in place is not supported)");
     QH_HIP(hipSetDevice(h->device));
     if (h->tail) {
         const long long n_mid = n_in >> h->head;

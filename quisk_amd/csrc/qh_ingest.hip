@@ -141,6 +141,9 @@ int qh_unpack_iq(int device, void *stream, const void *d_src, long long src_byte
     PackedFmt pk;
     if (int rc = make_packed_fmt(fmt, chan_stride, src_bytes, n, nch, &pk)) return rc;
     if (n == 0) return QH_OK;
+    const long long es = dtype == QH_F64 ? 16 : 8;
+    if (rows_overlap(d_src, 0, src_bytes, d_dst, dst_stride * es, (long long)n * es, nch))
+        return set_error(QH_ERR_INVALID, "qh_unpack_iq: the output rows overlap the packed source (in place is not supported)");
     QH_HIP(hipSetDevice(device));
     long long blocks = ((long long)n + NT - 1) / NT;
     if (blocks > 65535) blocks = 65535;
@@ -191,6 +194,17 @@ int qh_unpack_udp17(int device, void *stream, const void *d_src, int npackets, i
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
         return set_error(QH_ERR_NO_DEVICE, "no HIP device %d (libquiskhip has no CPU fallback)", device);
+    {
+        // the source and the five outputs: no two of them may share a byte
+        const long long nrec = (long long)npackets * ((packet_bytes - 2) / 6);
+        const void *buf[6] = { d_src, d_ch0, d_ch1, d_marks, d_counts, d_dc_sum };
+        const long long len[6] = { (long long)npackets * packet_bytes, nrec * 16, nrec * 16, nrec * 4, 32, 16 };
+        static const char *const name[6] = { "source", "d_ch0", "d_ch1", "d_marks", "d_counts", "d_dc_sum" };
+        for (int i = 0; i < 6; i++)
+            for (int j = i + 1; j < 6; j++)
+                if (rows_overlap(buf[i], 0, len[i], buf[j], 0, len[j], 1))
+                    return set_error(QH_ERR_INVALID, "qh_unpack_udp17: %s and %s overlap", name[i], name[j]);
+    }
     QH_HIP(hipSetDevice(device));
     hipLaunchKernelGGL(udp17_kernel, dim3(1), dim3(kUdp17Threads), 0, (hipStream_t)stream, (const unsigned char *)d_src, npackets, packet_bytes,
                        gain, invert_spectrum ? 1 : 0, dc_re, dc_im, (double2 *)d_ch0, (double2 *)d_ch1, d_marks, d_counts, d_dc_sum);

@@ -1,5 +1,6 @@
 // qh_internal.hpp -- declarations shared by the translation units of libquiskhip.so.
 #pragma once
+#include <cstdint>
 #include <cstdlib>
 #include <hip/hip_runtime.h>
 #include <string>
@@ -36,6 +37,27 @@ static inline hipError_t dev_zero(void *p, size_t bytes)
     hipError_t e = hipMemset(p, 0, bytes);
     if (e == hipSuccess) e = hipDeviceSynchronize();
     return e;
+}
+
+// Whether two matrices of rows share a byte: row c of A is [a + c sa, a + c sa + la), row c of B [b + c sb, b + c sb + lb), c < nrows (all
+// in bytes).  Exact: rows of one matrix that sit in the gaps between the rows of the other are disjoint from it, whatever the extents of the
+// two matrices do.  Both lists of rows ascend by start and by end, so one merge walk over them finds the first pair that meets -- O(nrows).
+// A stride of 0 makes a matrix one buffer of la (lb) bytes; empty rows overlap nothing.
+static inline bool rows_overlap(const void *a, long long a_stride_bytes, long long a_len_bytes, const void *b, long long b_stride_bytes,
+                                long long b_len_bytes, long long nrows)
+{
+    if (!a || !b || a_len_bytes <= 0 || b_len_bytes <= 0 || nrows <= 0) return false;
+    long long pa = (long long)reinterpret_cast<uintptr_t>(a), pb = (long long)reinterpret_cast<uintptr_t>(b);
+    long long sa = a_stride_bytes, sb = b_stride_bytes;
+    if (sa < 0) { pa += (nrows - 1) * sa; sa = -sa; }
+    if (sb < 0) { pb += (nrows - 1) * sb; sb = -sb; }
+    for (long long i = 0, j = 0; i < nrows && j < nrows;) {
+        const long long a0 = pa + i * sa, b0 = pb + j * sb;
+        if (a0 + a_len_bytes <= b0) i++;            // row i of A ends before row j of B, and every later row of B starts later still
+        else if (b0 + b_len_bytes <= a0) j++;
+        else return true;
+    }
+    return false;
 }
 
 }  // namespace qh

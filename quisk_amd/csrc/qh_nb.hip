@@ -291,7 +291,8 @@ int qh_nb_process(qh_nb *h, const void *d_in, long long in_stride, void *d_out, 
     if (!h || n < 0 || (n > 0 && (!d_in || !d_out || in_stride < n || out_stride < n)))
         return set_error(QH_ERR_INVALID, "qh_nb_process: bad arguments");
     if (n == 0) return QH_OK;
-    if (d_in == d_out) return set_error(QH_ERR_INVALID, "qh_nb_process: in place is not supported (tiles read their neighbours' input)");
+    if (rows_overlap(d_in, in_stride * 16, (long long)n * 16, d_out, out_stride * 16, (long long)n * 16, h->nch))
+        return set_error(QH_ERR_INVALID, "qh_nb_process: the output rows overlap the input rows (tiles read their neighbours' input)");
     QH_HIP(hipSetDevice(h->device));
     const double2 *in = static_cast<const double2 *>(d_in);
     double2 *out = static_cast<double2 *>(d_out);

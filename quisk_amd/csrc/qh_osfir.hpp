@@ -657,7 +657,8 @@ __global__ __launch_bounds__(NT, (osfir_min_waves<T, D, OUTMIX, NFFT>())) void o
         // samples: the last two or three of a channel (workgroup-uniform test; a sample two tiles share is written twice, the same value).  A copy
         // loop of its own BEHIND the tile's stores: taken from x[] after the loads it cost the /8 front kernel ten registers and DET 3 thirteen
         // spills, and in front of the loads it cost config 2's two kernels 1 % each (same-box A/B against the tree before, profiles/r06_notes.md).
-        // The rows of `out` never lie over the rows of `in` when the host asks for this (it asks only when the call is at least hist_len long).
+        // It reads in[] after other tiles have stored to out[]: sound because the rows of `out` never lie over the rows of `in` -- Stage::process_t
+        // (qh_stage.hpp) refuses such calls; the host's other condition, a call at least hist_len long, only makes the tiles' spans reach the end.
         if (a.hist_next && g0 + NFFT > a.n_in - a.hist_len) {
             C *hn = a.hist_next + (long long)ch * a.hist_stride;
             const int first = a.n_in - a.hist_len;

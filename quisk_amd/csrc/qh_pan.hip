@@ -1298,6 +1298,8 @@ int qh_pan_feed_decimate(qh_pan *h, const double *d_in, long long in_stride, int
     if (!d_in || !d_out || in_stride < n || p.fill != 0 || n % p.N) return set_error(QH_ERR_INVALID, "qh_pan_feed_decimate: whole blocks of %d samples at a block boundary", p.N);
     const int nblk = n / p.N, nout = n / p.fir_decim;
     if (out_stride < nout) return set_error(QH_ERR_INVALID, "qh_pan_feed_decimate: output stride shorter than %d samples", nout);
+    if (rows_overlap(d_in, in_stride * 16, (long long)n * 16, d_out, out_stride * 16, (long long)nout * 16, p.nch))
+        return set_error(QH_ERR_INVALID, "qh_pan_feed_decimate: the output rows overlap the input rows (in place is not supported)");
     QH_HIP(hipSetDevice(p.device));
     const long long need = (long long)p.nch * nblk * 512;
     if (need > p.fir_yf_cap) {

@@ -181,6 +181,9 @@ int qh_rat_process(qh_rat *h, const void *d_in, long long in_stride, int n_in, v
     if (n_in == 0) return QH_OK;
     const int m = count_for(h, n_in);
     if (!d_in || in_stride < n_in || (m > 0 && (!d_out || out_stride < m))) return set_error(QH_ERR_INVALID, "qh_rat_process: bad buffers");
+    const long long es = (long long)h->esize;
+    if (rows_overlap(d_in, in_stride * es, n_in * es, d_out, out_stride * es, m * es, h->nch))
+        return set_error(QH_ERR_INVALID, "qh_rat_process: the output rows overlap the input rows (in place is not supported)");
     QH_HIP(hipSetDevice(h->device));
     const int rc = h->dtype == QH_F64 ? run<double>(h, d_in, in_stride, n_in, d_out, out_stride, m)
                                       : run<float>(h, d_in, in_stride, n_in, d_out, out_stride, m);

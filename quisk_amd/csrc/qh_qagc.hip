@@ -616,6 +616,9 @@ int qh_qagc_process2(qh_qagc *h, const void *d_src, long long src_stride, void *
     if (!h || n < 0 || (n > 0 && (!d_src || !d_dst || src_stride < n || dst_stride < n)))
         return set_error(QH_ERR_INVALID, "qh_qagc_process: bad arguments");
     if (n == 0) return QH_OK;
+    // in place (one buffer, one stride: qh_qagc_process) or rows apart; a kernel's store must never land on a sample it has still to read
+    if (!(d_src == d_dst && src_stride == dst_stride) && rows_overlap(d_src, src_stride * 16, (long long)n * 16, d_dst, dst_stride * 16, (long long)n * 16, h->nch))
+        return set_error(QH_ERR_INVALID, "qh_qagc_process2: the output rows overlap the input rows (only d_src == d_dst with equal strides may)");
     QH_HIP(hipSetDevice(h->device));
     if (!h->inited) {               // first call: state set up, samples untouched
         h->inited = true;

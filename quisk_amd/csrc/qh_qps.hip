@@ -257,6 +257,9 @@ int qh_qps_process(qh_qps *h, const double *d_in, long long in_stride, int n, do
     if (n <= 0) return QH_OK;                                           // quisk.c:2336-2337
     if (!d_in || !d_out || in_stride < n) return set_error(QH_ERR_INVALID, "qh_qps_process: bad buffers");
     if (out_stride < h->out_capacity(n)) return set_error(QH_ERR_INVALID, "qh_qps_process: out_stride %lld is shorter than qh_qps_out_capacity = %d", out_stride, h->out_capacity(n));
+    // (the output rows are taken as qh_qps_out_capacity long: how many samples a call leaves is known only once it has run)
+    if (qh::rows_overlap(d_in, in_stride * 16, (long long)n * 16, d_out, out_stride * 16, (long long)h->out_capacity(n) * 16, h->nch))
+        return set_error(QH_ERR_INVALID, "qh_qps_process: the output rows overlap the input rows (in place is not supported)");
     const int nch = h->nch;
     const double2 *in = reinterpret_cast<const double2 *>(d_in);
     double2 *out = reinterpret_cast<double2 *>(d_out);

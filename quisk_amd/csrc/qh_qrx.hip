@@ -630,6 +630,8 @@ int qh_qrx_process(qh_qrx *h, const double *d_in, long long in_stride, int n_in,
     QH_HIP(hipSetDevice(q.device));
     const int total = qh_qrx_out_count(h, n_in);
     if (out_stride < total) return set_error(QH_ERR_INVALID, "output stride %lld shorter than %d samples", out_stride, total);
+    if (rows_overlap(d_in, in_stride * 16, (long long)n_in * 16, d_out, out_stride * 16, (long long)total * 16, q.nch))
+        return set_error(QH_ERR_INVALID, "qh_qrx_process: the output rows overlap the input rows (in place is not supported)");
     // intermediate buffers: the 6/5 stage is the only one that grows the count before the last step
     const long long need = (long long)(n_in > total ? n_in : total) * 5 / 4 + 64;
     if (need > q.buf_cap) {

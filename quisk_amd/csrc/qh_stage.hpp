@@ -448,10 +448,15 @@ struct Stage {
 
     template <typename T> int process_t(const void *in, long long in_stride, int n_in, void *out, long long out_stride, int *n_out)
     {
-        QH_HIP(hipSetDevice(device));
         const int nout = out_count(n_in);
         if (n_out) *n_out = nout;
         if (n_in <= 0) return QH_OK;
+        // all tiles of a call run at once: one tile's stores would land on input that its neighbour (or hist_next, hist_update_kernel)
+        // has still to read -- refused before any state moves
+        if (nout > 0 && rows_overlap(in, in_stride * (long long)sizeof(cplx<T>), (long long)n_in * (long long)sizeof(cplx<T>), out,
+                                     out_stride * (long long)sizeof(cplx<T>), (long long)nout * (long long)sizeof(cplx<T>), nch))
+            return set_error(QH_ERR_INVALID, "filter stage: the output rows overlap the input rows (in place is not supported)");
+        QH_HIP(hipSetDevice(device));
         OsfirArgs<T> a{};
         a.in = static_cast<const cplx<T> *>(in); a.in_stride = in_stride;
         a.hist = static_cast<const cplx<T> *>(hist[cur]); a.hist_stride = hist_len; a.hist_len = hist_len;
@@ -462,7 +467,9 @@ struct Stage {
         a.epi = epi;
         a.n_in = n_in; a.n_out = nout; a.P = P; a.Lout = Lf;
         // the kernel's own tiles leave the next call's delay line (OsfirArgs::hist_next): decimators / plain filters with raw history, a call
-        // that is at least one delay line long (the tiles' loads cover [off - P, off + ntiles * fold * Lf), which reaches n_in: off + decim * nout >= n_in)
+        // that is at least one delay line long (the tiles' loads cover [off - P, off + ntiles * fold * Lf), which reaches n_in: off + decim * nout >= n_in).
+        // The copy reads in[] behind other tiles' stores to out[]: that is sound only because the rows of out never lie over the rows of in
+        // (the rows_overlap refusal above), not because of the call's length.
         const bool paired_now = pair && !per_channel && !mix && !outmix && pick <= 1;
         const bool hist_in_kernel = nout > 0 && interp == 1 && !mix && !paired_now && n_in >= hist_len;
         if (hist_in_kernel) a.hist_next = static_cast<cplx<T> *>(hist[cur ^ 1]);
