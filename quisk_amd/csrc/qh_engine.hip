@@ -166,7 +166,6 @@ struct Engine {
     bool band6k = false;                    // 6144-point tiles on 384 lanes (osfir6k_kernel)
     int dbg_forms = [] { const char *e = std::getenv("QH_DBG_FORMS"); return e ? std::atoi(e) : 0; }();   // see process_chain
     int band_tile_pref = 0;                 // qh_rxa_set_band_tile: 0 / 4096: 4096-point tiles, 8192: the two-group tiles
-    double2 *band_stash = nullptr;          // osfir8s_kernel: [nch][4096], where the tile cut short by the end of a call parks A'
     std::vector<cd> band_mask(const std::vector<cd> &h) const;
     unsigned long long *nco_phase = nullptr, *nco_dphase = nullptr, *nco_parked = nullptr;
     double2 *nco_step = nullptr;
@@ -302,6 +301,13 @@ struct Engine {
     unsigned flags() const { return (unsigned)(cur_front | cur_nbp << 1 | cur_bp1 << 2 | cur_de << 3 | cur_aud << 4 | cur_snb << 5); }
     void set_flags(unsigned f) { cur_front = f & 1; cur_nbp = f >> 1 & 1; cur_bp1 = f >> 2 & 1; cur_de = f >> 3 & 1; cur_aud = f >> 4 & 1; cur_snb = f >> 5 & 1; }
     void drop_graphs() { for (auto &g : graph_slot) if (g.exec) { (void)hipGraphExecDestroy(g.exec); g.exec = nullptr; } }
+    // Growing, rebuilding or re-uploading a device buffer: captured launch sequences hold its address and launches queued on either
+    // stream may still use it, so nothing is freed or rewritten before quiesce() has waited for both streams and dropped the captures.
+    int quiesce();
+    // p holds old_n elements (none: 0): free it and allocate new_n in its place; dev_bytes follows.  The caller has quiesced.
+    template <typename T> int realloc_dev(T *&p, long long old_n, long long new_n);
+    // p holds cap units of `unit` elements: when need is more, quiesce and reallocate it for need units
+    template <typename T> int grow(T *&p, long long &cap, long long need, long long unit);
     int process_replayed(const double *d_in, long long in_stride, double *d_out, long long out_stride, int nblk);
     AgcParam *agc_prm = nullptr;
     AgcState *agc_state = nullptr;
@@ -348,6 +354,36 @@ struct Engine {
     int emnr_alloc();
     int process(const double *d_in, long long in_stride, double *d_out, long long out_stride, int nblk);
     int process_chain(const double *d_in, long long in_stride, double *d_out, long long out_stride, int nblk);
+    // One process_chain call: its sizes and rows, and the form every stage takes, each decided once where it is set below
+    struct ChainCall {
+        int nblk = 0, nc_max = 1, P = 0, P_am = 0;
+        long long n_in = 0, n_mid = 0;
+        const double2 *in = nullptr;
+        long long in_stride = 0, out_stride = 0;
+        double2 *out = nullptr;
+        double2 *cur = nullptr, *other = nullptr;       // the mixed path's working rows (buf[0] / buf[1], swapped as stages write)
+        bool any_nbp = false, any_bp1 = false, every_nbp = true, mixed = false, long_mode = false, meters_fused = false, eg_fused = false;
+        bool split = false, fm_theta_fused = false, direct = false, am_fused = false, am_lv_fused = false, side = false;
+        bool agc_direct = false;                        // set where xwcpagc runs (run_agc)
+    };
+    int chain_needs(ChainCall &k);
+    int plan_long(ChainCall &k);
+    void pick_band_tile(int nc_max);
+    int run_linear(ChainCall &k);
+    int plan_mixed(ChainCall &k);
+    int ensure_side_stream();
+    int fork_side();
+    int run_mixed_front(ChainCall &k);
+    int seg_groups(int count, long long n_mid) const;
+    template <bool SAM> void am_detect(const ChainCall &k, hipStream_t s, const int *list, int n, int G, const double *pts, long long pts_stride, double *gs);
+    int run_am(ChainCall &k);
+    int run_fm(ChainCall &k);
+    void snb_inplace(const ChainCall &k, const int *list, int n);
+    int run_snba(const ChainCall &k);
+    void lms_at(const ChainCall &k, int pos, double2 *b);
+    void bp1_at(const ChainCall &k, int pos);
+    int run_agc(ChainCall &k);
+    void run_output(const ChainCall &k);
     qh_rat *rsmpout = nullptr;          // xresample out (wdsp/RXA.c:596), only when out_rate != dsp_rate
     qh_rat *rsmpin = nullptr;           // xresample in for the rate ratios the overlap-save front stage does not cover (D == 0)
     double2 *fbuf = nullptr;            // its input: the shifted samples at in_rate
@@ -368,7 +404,6 @@ Engine::~Engine()
     (void)hipFree(obuf); (void)hipFree(abuf);
     for (int i = 0; i < 5; i++) { (void)hipFree(lmask[i]); (void)hipFree(lhist[i][0]); (void)hipFree(lhist[i][1]); }
     (void)hipFree(lcat); (void)hipFree(ltmp);
-    (void)hipFree(band_stash);
     (void)hipFree(mask_front); (void)hipFree(mask_nbp); (void)hipFree(mask_bp1); (void)hipFree(tw4096); (void)hipFree(tw_inv_front); (void)hipFree(tw8192);
     (void)hipFree(nco_phase); (void)hipFree(nco_dphase); (void)hipFree(nco_parked); (void)hipFree(nco_step); (void)hipFree(epi);
     (void)hipFree(lane_rot); (void)hipFree(tile_rot); (void)hipFree(front_taps); (void)hipFree(retune_list); (void)hipFree(retune_law);
@@ -397,6 +432,31 @@ static int upload(double2 *dst, const std::vector<cd> &v, hipStream_t s)
 {
     QH_HIP(hipMemcpyAsync(dst, v.data(), v.size() * sizeof(cd), hipMemcpyHostToDevice, s));
     QH_HIP(hipStreamSynchronize(s));        // the host vector dies with the caller's scope
+    return QH_OK;
+}
+
+int Engine::quiesce()
+{
+    QH_HIP(hipStreamSynchronize(stream));
+    if (side_stream) QH_HIP(hipStreamSynchronize(side_stream));
+    drop_graphs(); epoch++;
+    return QH_OK;
+}
+
+template <typename T> int Engine::realloc_dev(T *&p, long long old_n, long long new_n)
+{
+    if (p) { QH_HIP(hipFree(p)); dev_bytes -= old_n * (long long)sizeof(T); p = nullptr; }
+    QH_HIP(dev_alloc(&p, (size_t)new_n));
+    dev_bytes += new_n * (long long)sizeof(T);
+    return QH_OK;
+}
+
+template <typename T> int Engine::grow(T *&p, long long &cap, long long need, long long unit)
+{
+    if (need <= cap) return QH_OK;
+    if (int rc = quiesce()) return rc;
+    if (int rc = realloc_dev(p, cap * unit, need * unit)) return rc;
+    cap = need;
     return QH_OK;
 }
 
@@ -504,10 +564,6 @@ int Engine::init()
                                                       hipFuncAttributeMaxDynamicSharedMemorySize, osfir8k_lds_bytes()))
     QH_SET_LDS2G(false, false); QH_SET_LDS2G(true, false); QH_SET_LDS2G(false, true); QH_SET_LDS2G(true, true);
 #undef QH_SET_LDS2G
-#ifdef QH_EXP_BAND8_SEQ
-    QH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&osfir8s_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, kOsfir8kImage));
-    QH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&osfir8s_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, kOsfir8kImage));
-#endif
     QH_SET_LDS(2, false, false, false, true, false, true); QH_SET_LDS(4, false, false, false, true, false, true); QH_SET_LDS(8, false, false, false, true, false, true);
     QH_SET_LDS(2, false, true, false, true, false, true); QH_SET_LDS(4, false, true, false, true, false, true); QH_SET_LDS(8, false, true, false, true, false, true);
 #undef QH_SET_LDS
@@ -1260,7 +1316,7 @@ int Engine::snba_set_ovrlp(int ovrlp)
     snba_ovrlp = ovrlp;
     if (!snba_state) return QH_OK;                       // nothing built yet: snba_alloc plans with it
     QH_HIP(hipSetDevice(device));
-    QH_HIP(hipStreamSynchronize(stream));
+    if (int rc = quiesce()) return rc;
     const SnbaParam old = snba_prm;
     std::vector<double> frames((size_t)nch * 2 * kSnbX);
     QH_HIP(hipMemcpy2D(frames.data(), 2 * kSnbX * sizeof(double), snba_state, (size_t)old.state_doubles * sizeof(double), 2 * kSnbX * sizeof(double),
@@ -1274,7 +1330,6 @@ int Engine::snba_set_ovrlp(int ovrlp)
                        (size_t)nch, hipMemcpyHostToDevice));
     std::vector<SnbaIdx> ix((size_t)nch, SnbaIdx{ 0, 0, 0, 0, q.init_oaoutidx, { 0, 0, 0 } });
     QH_HIP(hipMemcpy(snba_idx, ix.data(), ix.size() * sizeof(SnbaIdx), hipMemcpyHostToDevice));
-    drop_graphs(); epoch++;
     return QH_OK;
 }
 
@@ -1424,16 +1479,9 @@ int Engine::emnr_alloc()
 int Engine::ensure_buffers(long long n_mid)
 {
     if (n_mid <= buf_cap) return QH_OK;
-    QH_HIP(hipStreamSynchronize(stream));
-    // captured launch sequences hold the old buffer addresses: whatever entry point grows the buffers, they are stale now
-    drop_graphs(); epoch++;
-    for (int i = 0; i < 2; i++) {
-        if (buf[i]) { QH_HIP(hipFree(buf[i])); dev_bytes -= buf_cap * nch * (long long)sizeof(double2); buf[i] = nullptr; }
-    }
-    for (int i = 0; i < 2; i++) {
-        QH_HIP(dev_alloc(&buf[i], (size_t)nch * (size_t)n_mid));
-        dev_bytes += n_mid * nch * (long long)sizeof(double2);
-    }
+    if (int rc = quiesce()) return rc;
+    for (double2 *&b : buf)
+        if (int rc = realloc_dev(b, buf_cap * nch, n_mid * nch)) return rc;
     buf_cap = n_mid;
     return QH_OK;
 }
@@ -1454,27 +1502,16 @@ int Engine::ensure_meter_partials(long long n_mid, int lout)
 {
     const long long need = ((n_mid + lout - 1) / lout) * (lout / 64);
     if (need <= m_part_cap) return QH_OK;
-    QH_HIP(hipStreamSynchronize(stream));
-    drop_graphs(); epoch++;
-    for (int i = 0; i < 2; i++) {
-        if (m_part[i]) { QH_HIP(hipFree(m_part[i])); dev_bytes -= m_part_cap * nch * (long long)sizeof(double2); m_part[i] = nullptr; }
-        QH_HIP(dev_alloc(&m_part[i], (size_t)nch * (size_t)need));
-        dev_bytes += need * nch * (long long)sizeof(double2);
-    }
+    if (int rc = quiesce()) return rc;
+    for (double2 *&m : m_part)
+        if (int rc = realloc_dev(m, m_part_cap * nch, need * nch)) return rc;
     m_part_cap = need;
     return QH_OK;
 }
 
 int Engine::ensure_abuf(long long n)
 {
-    if (n <= abuf_cap) return QH_OK;
-    QH_HIP(hipStreamSynchronize(stream));
-    drop_graphs(); epoch++;
-    if (abuf) { QH_HIP(hipFree(abuf)); dev_bytes -= abuf_cap * nch * (long long)sizeof(double2); abuf = nullptr; }
-    QH_HIP(dev_alloc(&abuf, (size_t)nch * (size_t)n));
-    abuf_cap = n;
-    dev_bytes += n * nch * (long long)sizeof(double2);
-    return QH_OK;
+    return grow(abuf, abuf_cap, n, nch);
 }
 
 void Engine::pack_audio(const double2 *src, long long src_stride, long long n)
@@ -1530,19 +1567,6 @@ static void launch_band6k(OsfirArgs<double> a, int ntiles, int nch, hipStream_t 
 static void launch_band2g(OsfirArgs<double> a, int ntiles, int nch, hipStream_t s, bool meter, bool egress)
 {
     a.ntiles = ntiles;
-    // QH_BAND8_FORM=seq: the two halves one after the other on 256 lanes (osfir8s_kernel) instead of the two lane groups side by side
-    // (osfir8k_kernel): same masks, same meter partials, same tile geometry.  Measured slower still (profiles/r05_notes.md: the second
-    // read of the tile and the parked half go through memory), so it is there for experiments only; never for narrowed outputs.
-    // The kernel is in experiment builds only (-DQH_EXP_BAND8_SEQ, tools/ab_bench.py).
-#ifdef QH_EXP_BAND8_SEQ
-    static const bool seq = [] { const char *e = std::getenv("QH_BAND8_FORM"); return e && std::strcmp(e, "seq") == 0; }();
-    if (!egress && seq && a.stash) {
-        dim3 g1((unsigned)ntiles * (unsigned)nch);
-        if (meter) hipLaunchKernelGGL((osfir8s_kernel<true>), g1, dim3(NT), kOsfir8kImage, s, a);
-        else hipLaunchKernelGGL((osfir8s_kernel<false>), g1, dim3(NT), kOsfir8kImage, s, a);
-        return;
-    }
-#endif
     dim3 grid((unsigned)ntiles * (unsigned)nch), block(kOsfir8kThreads);
     constexpr int lds = osfir8k_lds_bytes();
     if (meter && egress) hipLaunchKernelGGL((osfir8k_kernel<true, true>), grid, block, lds, s, a);
@@ -1574,14 +1598,7 @@ int Engine::run_front(const double2 *src, long long src_stride, double2 *dst, lo
         const int ntiles = (int)((n_mid + per_tile - 1) / per_tile);
         a.chan_list = list;
         const int nl = list ? nlist : nch;
-        if (part <= 1 && ntiles > tile_rot_cap) {
-            QH_HIP(hipStreamSynchronize(stream));
-            drop_graphs(); epoch++;
-            if (tile_rot) { QH_HIP(hipFree(tile_rot)); dev_bytes -= tile_rot_cap * nch * (long long)sizeof(double2); tile_rot = nullptr; }
-            QH_HIP(dev_alloc(&tile_rot, (size_t)nch * (size_t)ntiles));
-            tile_rot_cap = ntiles;
-            dev_bytes += (long long)ntiles * nch * (long long)sizeof(double2);
-        }
+        if (part <= 1) if (int rc = grow(tile_rot, tile_rot_cap, ntiles, nch)) return rc;
         // oscillator phasor at the first input index of every tile: g0 = off - P + tile * fold * Lout (qh_osfir.hpp)
         if (part <= 1) hipLaunchKernelGGL(nco_tile_kernel, dim3((unsigned)((ntiles + 255) / 256), (unsigned)nch), dim3(256), 0, stream,
                            (const unsigned long long *)nco_phase, (const unsigned long long *)nco_dphase, tile_rot, ntiles,
@@ -1623,14 +1640,7 @@ int Engine::run_front(const double2 *src, long long src_stride, double2 *dst, lo
     } else if (D == 0) {
         // any other ratio: xshift into the staging rows, then the polyphase resampler (its ring and phase live in qh_rat)
         if (pk_src) return set_error(QH_ERR_UNSUPPORTED, "packed input needs in_rate / dsp_rate in 2, 4, 8, 16");
-        if (n_in > fbuf_cap) {
-            QH_HIP(hipStreamSynchronize(stream));
-            drop_graphs(); epoch++;
-            if (fbuf) { QH_HIP(hipFree(fbuf)); dev_bytes -= fbuf_cap * nch * (long long)sizeof(double2); fbuf = nullptr; }
-            QH_HIP(dev_alloc(&fbuf, (size_t)nch * (size_t)n_in));
-            fbuf_cap = n_in;
-            dev_bytes += n_in * nch * (long long)sizeof(double2);
-        }
+        if (int rc = grow(fbuf, fbuf_cap, n_in, nch)) return rc;
         long long per = (n_in + NT - 1) / NT;
         dim3 g((unsigned)(per < 4096 ? per : 4096), (unsigned)nch);
         hipLaunchKernelGGL((pointwise_kernel<double, true>), g, dim3(NT), 0, stream, src, src_stride, fbuf, fbuf_cap,
@@ -1702,8 +1712,7 @@ static __global__ __launch_bounds__(NT) void long_migrate_kernel(double2 *hist, 
 int Engine::long_stage_alloc(int sid, bool shared_mask)
 {
     if (lmask[sid]) return QH_OK;
-    QH_HIP(hipStreamSynchronize(stream));
-    drop_graphs(); epoch++;
+    if (int rc = quiesce()) return rc;
     const size_t rows = shared_mask ? 1 : (size_t)nch;
     QH_HIP(dev_alloc(&lmask[sid], rows * kLongParts * kBandNfftMax));
     QH_HIP(hipMemsetAsync(lmask[sid], 0, rows * kLongParts * kBandNfftMax * sizeof(double2), stream));
@@ -1717,15 +1726,10 @@ int Engine::long_stage_alloc(int sid, bool shared_mask)
 int Engine::long_buffers()
 {
     if (lcat && lcat_cap == buf_cap) return QH_OK;
-    QH_HIP(hipStreamSynchronize(stream));
-    if (side_stream) QH_HIP(hipStreamSynchronize(side_stream));
-    drop_graphs(); epoch++;
-    if (lcat) dev_bytes -= (long long)nch * (2 * lcat_cap + kLongHist) * (long long)sizeof(double2);
-    (void)hipFree(lcat); (void)hipFree(ltmp); lcat = ltmp = nullptr;
-    QH_HIP(dev_alloc(&lcat, (size_t)nch * (size_t)(kLongHist + buf_cap)));
-    QH_HIP(dev_alloc(&ltmp, (size_t)nch * (size_t)buf_cap));
+    if (int rc = quiesce()) return rc;
+    if (int rc = realloc_dev(lcat, lcat ? nch * (kLongHist + lcat_cap) : 0, nch * (kLongHist + buf_cap))) return rc;
+    if (int rc = realloc_dev(ltmp, nch * lcat_cap, nch * buf_cap)) return rc;
     lcat_cap = buf_cap;
-    dev_bytes += (long long)nch * (2 * lcat_cap + kLongHist) * (long long)sizeof(double2);
     return QH_OK;
 }
 // the kLongParts partition masks of the impulse response h (8192-point spectra of its 4096-tap slices; the slices past its end zero)
@@ -1797,7 +1801,6 @@ void Engine::run_band(const double2 *src, long long src_stride, double2 *dst, lo
     a.mask = mask; a.mask_stride = mask_stride;
     a.tw_fwd = a.tw_inv = (bnfft == kNfft || band2g) ? tw4096 : tw8192;
     a.tw_r2 = tw8192 + 32;                  // second pass table of the 8192-point plan: exp(-2 pi i k / 8192), k < 256 (qh_design.cpp)
-    a.stash = band_stash;
     a.epi = ep;
     a.chan_list = list;
     a.n_in = (int)n_mid; a.n_out = (int)n_mid; a.off = 0; a.P = P; a.Lout = Lout;
@@ -1873,14 +1876,7 @@ int Engine::process(const double *d_in, long long in_stride, double *d_out, long
         return QH_OK;
     }
     const long long n_mid = (long long)nblk * dsp_size;
-    if (n_mid > obuf_cap) {
-        QH_HIP(hipStreamSynchronize(stream));
-        drop_graphs(); epoch++;
-        if (obuf) { QH_HIP(hipFree(obuf)); dev_bytes -= obuf_cap * nch * (long long)sizeof(double2); obuf = nullptr; }
-        QH_HIP(dev_alloc(&obuf, (size_t)nch * (size_t)n_mid));
-        obuf_cap = n_mid;
-        dev_bytes += n_mid * nch * (long long)sizeof(double2);
-    }
+    if (int rc = grow(obuf, obuf_cap, n_mid, nch)) return rc;
     if (int rc = process_chain(d_in, in_stride, reinterpret_cast<double *>(obuf), obuf_cap, nblk)) return rc;
     int got = 0;
     if (int rc = qh_rat_process(rsmpout, obuf, obuf_cap, (int)n_mid, d_out, out_stride, &got)) return rc;
@@ -1942,176 +1938,213 @@ int Engine::set_sb_phi(long long n, int S)
         QH_HIP(dev_alloc(&sb_sum, (size_t)nch * kSegWaves * kSegMaxGroups * kSbSum));
         QH_HIP(dev_alloc(&sb_start, (size_t)nch * kSegWaves * kSegMaxGroups * kSbSum));
     }
-    QH_HIP(hipStreamSynchronize(stream));
-    if (side_stream) QH_HIP(hipStreamSynchronize(side_stream));
-    drop_graphs(); epoch++;
+    if (int rc = quiesce()) return rc;
     QH_HIP(hipMemcpy(sb_phi, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
     sb_phi_key = key;
     return QH_OK;
 }
 
-int Engine::process_chain(const double *d_in, long long in_stride, double *d_out, long long out_stride, int nblk)
+// Whether two matrices of nch rows lie apart.  The extents are the rows' own: first sample of the first row to last sample of the last.
+// (nch * stride from a pointer INTO a matrix -- a caller walking along its rows call by call -- reaches past the matrix's end by the
+// offset, and whether that touches the other matrix depended on where the allocator had put the two: the same calls took one form or
+// the other -- AM channels' last bits, tests/test_gpu_properties_fullsize.py -- by address.)
+static bool extents_apart(const double2 *a, long long a_stride, long long a_n, const double2 *b, long long b_stride, long long b_n, int nch)
 {
-    if (nblk <= 0) return QH_OK;
-    QH_HIP(hipSetDevice(device));
-    // what the chain of every channel needs
-    bool any_nbp = false, any_bp1 = false, mixed = false, every_nbp = true;
-    int nc_max = 1;
+    const double2 *a_end = a + (size_t)(nch - 1) * (size_t)a_stride + (size_t)a_n, *b_end = b + (size_t)(nch - 1) * (size_t)b_stride + (size_t)b_n;
+    return (const char *)a_end <= (const char *)b || (const char *)b_end <= (const char *)a;
+}
+
+// what the chain of every channel needs
+int Engine::chain_needs(ChainCall &k)
+{
     for (const ChanCfg &c : cfg) {
         if (c.agc_run && c.agc_mode > 4)
             return set_error(QH_ERR_UNSUPPORTED, "AGC mode %d is not provided (0 fixed, 1-4 long/slow/med/fast)", c.agc_mode);
         // (SetRXAAMDRun can switch the AM detector on beside the FM one, RXA.c:594-595 then runs both in a row: not provided, and said so)
         if (c.amd_run && c.fmd_run) return set_error(QH_ERR_UNSUPPORTED, "channel %d: the AM and the FM detector both switched on", (int)(&c - cfg.data()));
-        if (c.amd_run || c.fmd_run || (c.agc_run && c.agc_mode != 0) || c.lms[0].run || c.lms[1].run || c.amsq_run || c.emnr_run || c.snba_run) mixed = true;
+        if (c.amd_run || c.fmd_run || (c.agc_run && c.agc_mode != 0) || c.lms[0].run || c.lms[1].run || c.amsq_run || c.emnr_run || c.snba_run) k.mixed = true;
         if (c.emnr_run && !emnr_tables) return set_error(QH_ERR_INVALID, "EMNR needs its gain tables first (qh_rxa_SetEMNRTables: WDSP's `calculus` and `zetaHat.bin` data)");
-        if (c.nbp_run) { any_nbp = true; if (c.nbp_nc > nc_max) nc_max = c.nbp_nc; } else every_nbp = false;
-        if (c.bp1_run) { any_bp1 = true; if (c.bp1_nc > nc_max) nc_max = c.bp1_nc; }
-        if (c.fmd_run && c.fm_nc > nc_max) nc_max = c.fm_nc;
+        if (c.nbp_run) { k.any_nbp = true; if (c.nbp_nc > k.nc_max) k.nc_max = c.nbp_nc; } else k.every_nbp = false;
+        if (c.bp1_run) { k.any_bp1 = true; if (c.bp1_nc > k.nc_max) k.nc_max = c.bp1_nc; }
+        if (c.fmd_run && c.fm_nc > k.nc_max) k.nc_max = c.fm_nc;
     }
-    if (nc_max > kLongNcMax) return set_error(QH_ERR_UNSUPPORTED, "nc = %d exceeds %d", nc_max, kLongNcMax);
-    // stages whose impulse response is longer than 4096 taps run in partitions (run_band): how many, per stage
-    bool long_mode = false;
-    {
-        auto parts = [](int nc) { return nc > kLongPart ? (nc + kLongPart - 1) / kLongPart : 1; };
-        int lp[5] = { 1, 1, 1, 1, 1 };
-        // Over every channel that runs the stage OR still holds a long delay line of it: a fircore keeps its delay line while it does not run (xbandpass / xnbp with run = 0
-        // only copy; SetRXABandpassRun, a mode change back to AM / FM, RXANBPSetRun switch it on again without a flush), so a channel with
-        // nc > 4096 that sits out holds 16383 samples the one-tile form has no room for.  Had the form followed the RUNNING channels,
-        // the only long channel leaving took the stage to the short form (its line cut to 4095 samples) and came back to zeros behind
-        // them: one long call 0.65 off (walk rxa_long 900190, found by round 6's seed sweep; in the suite since).
-        // (long_live: the channel has run the stage with such an nc since RXASetNC last zeroed its lines.)
-        for (ChanCfg &c : cfg) {
-            const int pn = parts(c.nbp_nc), pb = parts(c.bp1_nc), pf = parts(c.fm_nc);
-            if (c.nbp_run && pn > 1) c.long_live[0] = true;
-            if (c.bp1_run && pb > 1) c.long_live[1] = true;
-            if (c.fmd_run && pf > 1) c.long_live[2] = true;
-            if (c.snba_run && pn > 1) c.long_live[4] = true;
-            if (c.nbp_run || c.long_live[0]) lp[0] = std::max(lp[0], pn);
-            if (c.bp1_run || c.long_live[1]) lp[1] = std::max(lp[1], pb);
-            if (c.fmd_run || c.long_live[2]) lp[2] = lp[3] = std::max(lp[2], pf);
-            if (c.snba_run || c.long_live[4]) lp[4] = std::max(lp[4], pn);
-        }
-        for (int sid = 0; sid < 5; sid++) {
-            if (lp[sid] > 1) { long_mode = true; if (int rc = long_stage_alloc(sid, sid == 2 || sid == 3)) return rc; }
-            if (lp[sid] == long_parts[sid]) continue;
-            QH_HIP(hipStreamSynchronize(stream));
-            drop_graphs(); epoch++;
-            if ((lp[sid] > 1) != (long_parts[sid] > 1)) {       // the delay lines move with the form
-                double2 **hs = sid == 0 ? hist_nbp : sid == 1 ? hist_bp1 : sid == 2 ? hist_de : sid == 3 ? hist_aud : hist_snb;
-                // BOTH ping-pong halves: a channel that has left the stage's list (another mode, bp1 or SNBA switched off) keeps its rows in
-                // the half that was current when it left (bp1_hist_at, fm_hist_at, snb_hist_at), which need not be the current one
-                for (int half = 0; half < 2; half++)
-                    if (hs[half] && lhist[sid][half])
-                        hipLaunchKernelGGL(long_migrate_kernel, dim3(16, (unsigned)nch), dim3(NT), 0, stream, hs[half], lhist[sid][half], lp[sid] > 1 ? 1 : 0);
-            }
-            long_parts[sid] = lp[sid];
-            for (ChanCfg &c : cfg) {            // the stage's masks are laid out for another form now: all of them again
-                if (sid == 0) c.nbp_dirty = true;
-                if (sid == 1) c.bp1_dirty = true;
-                if (sid == 4) c.snb_dirty = true;
-            }
-            if (sid == 2 || sid == 3) fm_nc_built = 0;
-        }
+    if (k.nc_max > kLongNcMax) return set_error(QH_ERR_UNSUPPORTED, "nc = %d exceeds %d", k.nc_max, kLongNcMax);
+    return QH_OK;
+}
+
+// stages whose impulse response is longer than 4096 taps run in partitions (run_band): how many, per stage
+int Engine::plan_long(ChainCall &k)
+{
+    auto parts = [](int nc) { return nc > kLongPart ? (nc + kLongPart - 1) / kLongPart : 1; };
+    int lp[5] = { 1, 1, 1, 1, 1 };
+    // Over every channel that runs the stage OR still holds a long delay line of it: a fircore keeps its delay line while it does not run (xbandpass / xnbp with run = 0
+    // only copy; SetRXABandpassRun, a mode change back to AM / FM, RXANBPSetRun switch it on again without a flush), so a channel with
+    // nc > 4096 that sits out holds 16383 samples the one-tile form has no room for.  Had the form followed the RUNNING channels,
+    // the only long channel leaving took the stage to the short form (its line cut to 4095 samples) and came back to zeros behind
+    // them: one long call 0.65 off (walk rxa_long 900190, found by round 6's seed sweep; in the suite since).
+    // (long_live: the channel has run the stage with such an nc since RXASetNC last zeroed its lines.)
+    for (ChanCfg &c : cfg) {
+        const int pn = parts(c.nbp_nc), pb = parts(c.bp1_nc), pf = parts(c.fm_nc);
+        if (c.nbp_run && pn > 1) c.long_live[0] = true;
+        if (c.bp1_run && pb > 1) c.long_live[1] = true;
+        if (c.fmd_run && pf > 1) c.long_live[2] = true;
+        if (c.snba_run && pn > 1) c.long_live[4] = true;
+        if (c.nbp_run || c.long_live[0]) lp[0] = std::max(lp[0], pn);
+        if (c.bp1_run || c.long_live[1]) lp[1] = std::max(lp[1], pb);
+        if (c.fmd_run || c.long_live[2]) lp[2] = lp[3] = std::max(lp[2], pf);
+        if (c.snba_run || c.long_live[4]) lp[4] = std::max(lp[4], pn);
     }
-    {   // The fircore tile.  Impulse responses longer than 2048 taps need 8192 points (osfir_kernel<8192>, one wave per SIMD).
-        // Shorter ones run 4096-point tiles; the two-group 8192-point tile (osfir8k_kernel, 6144 instead of 2049 outputs per
-        // pair of transforms) is there on request (qh_rxa_set_band_tile) -- it measured slower, see qh_osfir.hpp.  The masks are
-        // spectra of the tile size, so a change rebuilds every one of them (the delay lines, kept 4095 samples deep, carry over).
-        static const bool force8k = [] { const char *e = std::getenv("QH_BAND_NFFT"); return e && std::atoi(e) == 8192; }();  // tuning experiments
-        const bool two_group = nc_max <= 2048 && band_tile_pref == 8192 && !force8k;
-        const bool six_k = nc_max <= 2048 && band_tile_pref == 6144 && !force8k;
-        const int want = six_k ? kOsfir6kN : (nc_max > 2048 || force8k || two_group) ? kBandNfftMax : kNfft;
-#ifdef QH_EXP_BAND8_SEQ
-        if (two_group && !band_stash) {         // (osfir8s_kernel's scratch rows: the experiment builds' kernel only)
-            QH_HIP(hipStreamSynchronize(stream));
-            drop_graphs(); epoch++;
-            QH_HIP(dev_alloc(&band_stash, (size_t)nch * 4096));
-            dev_bytes += (long long)nch * 4096 * (long long)sizeof(double2);
+    for (int sid = 0; sid < 5; sid++) {
+        if (lp[sid] > 1) { k.long_mode = true; if (int rc = long_stage_alloc(sid, sid == 2 || sid == 3)) return rc; }
+        if (lp[sid] == long_parts[sid]) continue;
+        if (int rc = quiesce()) return rc;
+        if ((lp[sid] > 1) != (long_parts[sid] > 1)) {       // the delay lines move with the form
+            double2 **hs = sid == 0 ? hist_nbp : sid == 1 ? hist_bp1 : sid == 2 ? hist_de : sid == 3 ? hist_aud : hist_snb;
+            // BOTH ping-pong halves: a channel that has left the stage's list (another mode, bp1 or SNBA switched off) keeps its rows in
+            // the half that was current when it left (bp1_hist_at, fm_hist_at, snb_hist_at), which need not be the current one
+            for (int half = 0; half < 2; half++)
+                if (hs[half] && lhist[sid][half])
+                    hipLaunchKernelGGL(long_migrate_kernel, dim3(16, (unsigned)nch), dim3(NT), 0, stream, hs[half], lhist[sid][half], lp[sid] > 1 ? 1 : 0);
         }
-#endif
-        if (want != bnfft || two_group != band2g || six_k != band6k) {
-            bnfft = want; band2g = two_group; band6k = six_k;
-            for (ChanCfg &c : cfg) { c.nbp_dirty = c.bp1_dirty = true; c.snb_dirty = true; }
+        long_parts[sid] = lp[sid];
+        for (ChanCfg &c : cfg) {            // the stage's masks are laid out for another form now: all of them again
+            if (sid == 0) c.nbp_dirty = true;
+            if (sid == 1) c.bp1_dirty = true;
+            if (sid == 4) c.snb_dirty = true;
         }
+        if (sid == 2 || sid == 3) fm_nc_built = 0;
     }
+    return QH_OK;
+}
+
+// The fircore tile.  Impulse responses longer than 2048 taps need 8192 points (osfir_kernel<8192>, one wave per SIMD).
+// Shorter ones run 4096-point tiles; the two-group 8192-point tile (osfir8k_kernel, 6144 instead of 2049 outputs per
+// pair of transforms) is there on request (qh_rxa_set_band_tile) -- it measured slower, see qh_osfir.hpp.  The masks are
+// spectra of the tile size, so a change rebuilds every one of them (the delay lines, kept 4095 samples deep, carry over).
+void Engine::pick_band_tile(int nc_max)
+{
+    const bool two_group = nc_max <= 2048 && band_tile_pref == 8192;
+    const bool six_k = nc_max <= 2048 && band_tile_pref == 6144;
+    const int want = six_k ? kOsfir6kN : (nc_max > 2048 || two_group) ? kBandNfftMax : kNfft;
+    if (want != bnfft || two_group != band2g || six_k != band6k) {
+        bnfft = want; band2g = two_group; band6k = six_k;
+        for (ChanCfg &c : cfg) { c.nbp_dirty = c.bp1_dirty = true; c.snb_dirty = true; }
+    }
+}
+
+// xrxa (wdsp/RXA.c:560-597) for every channel: the linear chains' fast path, or the per-mode stages on channel lists
+int Engine::process_chain(const double *d_in, long long in_stride, double *d_out, long long out_stride, int nblk)
+{
+    if (nblk <= 0) return QH_OK;
+    QH_HIP(hipSetDevice(device));
+    ChainCall k;
+    k.nblk = nblk;
+    if (int rc = chain_needs(k)) return rc;
+    if (int rc = plan_long(k)) return rc;
+    pick_band_tile(k.nc_max);
     // The three meters of xrxa (adc, S, agc: RXA.c:566,569,589) ride on the nbp0 launch when the chain is linear (nbp0 runs,
     // bp1 does not, fixed AGC gain): the band tile then starts on a multiple of 256 samples so that a register holds one
     // 64-sample chunk per wavefront.  Any other chain takes the per-mode path with the stand-alone meter kernel.
-    const bool meters_fused = meters_on && !mixed && any_nbp && !any_bp1 && dsp_size >= 64 && dsp_size <= 2048 && !long_mode;
-    if (meters_on && !meters_fused) mixed = true;
+    k.meters_fused = meters_on && !k.mixed && k.any_nbp && !k.any_bp1 && dsp_size >= 64 && dsp_size <= 2048 && !k.long_mode;
+    if (meters_on && !k.meters_fused) k.mixed = true;
     if (meters_on) if (int rc = meters_alloc()) return rc;
     if (int rc = refresh_params()) return rc;
-    if (mixed) if (int rc = refresh_demod()) return rc;
+    if (k.mixed) if (int rc = refresh_demod()) return rc;
     if (n_snba) if (int rc = refresh_params()) return rc;       // bpsnba's mask needs the buffers the line above may just have made
 
-    const long long n_in = (long long)nblk * dsp_insize;
-    const long long n_mid = (long long)nblk * dsp_size;
-    if (n_in > 0x7fffffffLL) return set_error(QH_ERR_INVALID, "too many samples in one call");
-    if (int rc = ensure_buffers(n_mid)) return rc;
-    if (long_mode) if (int rc = long_buffers()) return rc;
+    k.n_in = (long long)nblk * dsp_insize;
+    k.n_mid = (long long)nblk * dsp_size;
+    if (k.n_in > 0x7fffffffLL) return set_error(QH_ERR_INVALID, "too many samples in one call");
+    if (int rc = ensure_buffers(k.n_mid)) return rc;
+    if (k.long_mode) if (int rc = long_buffers()) return rc;
     ev_used = 0;
 
-    const double2 *in = reinterpret_cast<const double2 *>(d_in);
-    double2 *out = reinterpret_cast<double2 *>(d_out);
+    k.in = reinterpret_cast<const double2 *>(d_in); k.in_stride = in_stride;
+    k.out = reinterpret_cast<double2 *>(d_out); k.out_stride = out_stride;
     // (with a partitioned stage in the call the others run 4096-tap tiles: their own nc is at most that)
-    const int P = band6k ? kOsfir6kP : band2g ? kOsfir8kP : meters_fused ? ((nc_max - 1 + 255) / 256) * 256 : long_mode ? kLongPart - 1 : nc_max - 1;
-
+    k.P = band6k ? kOsfir6kP : band2g ? kOsfir8kP : k.meters_fused ? ((k.nc_max - 1 + 255) / 256) * 256 : k.long_mode ? kLongPart - 1 : k.nc_max - 1;
     // audio egress (qh_rxa_process_audio): the narrowing rides in the store of the last kernel when that is an overlap-save
     // band stage or the per-mode path's output pass; other endings write complex doubles to the staging rows and narrow after
-    const bool eg_fused = eg.kind && (mixed ? n_amsq == 0 : ((any_nbp || any_bp1) && !long_mode));
-    if (eg.kind && !eg_fused) {
-        if (int rc = ensure_abuf(n_mid)) return rc;
-        out = abuf; out_stride = abuf_cap;
+    k.eg_fused = eg.kind && (k.mixed ? n_amsq == 0 : ((k.any_nbp || k.any_bp1) && !k.long_mode));
+    if (eg.kind && !k.eg_fused) {
+        if (int rc = ensure_abuf(k.n_mid)) return rc;
+        k.out = abuf; k.out_stride = abuf_cap;
     }
-    if (!mixed) {
-        // ---- every channel is a linear chain: the epilogue rides on the last stage, no extra pass
-        const int nstage = 1 + (any_nbp ? 1 : 0) + (any_bp1 ? 1 : 0);
-        int stage = 0, which = 0;
-        const double2 *cur = in;
-        long long cur_stride = in_stride;
-        auto dst_of = [&](int st, long long &stride) -> double2 * {
-            if (st == nstage - 1) { stride = out_stride; return out; }
-            stride = buf_cap;
-            double2 *p = buf[which];
-            which ^= 1;
-            return p;
-        };
-        {
-            long long dst_stride;
-            double2 *dst = dst_of(stage, dst_stride);
-            // A chain that is the front stage alone stores to the caller's rows while other tiles -- and the history pass behind the kernel --
-            // still read the input: when the rows of the two matrices overlap (include/quiskhip.h: the output may lie over the input) the
-            // stage goes to the engine's own rows and the output is written in a last pass.  (The rows' own extent, as in the mixed path.)
-            const bool over = nstage == 1 && !((const char *)(out + (size_t)(nch - 1) * (size_t)out_stride + (size_t)n_mid) <= (const char *)in ||
-                                              (const char *)in + ((size_t)(nch - 1) * (size_t)in_stride + (size_t)n_in) * sizeof(double2) <= (const char *)out);
-            if (over) { dst = buf[0]; dst_stride = buf_cap; }
-            if (int rc = run_front(cur, cur_stride, dst, dst_stride, stage == nstage - 1 ? epi : nullptr, n_in, n_mid)) return rc;
-            if (over) QH_HIP(hipMemcpy2DAsync(out, (size_t)out_stride * sizeof(double2), dst, (size_t)dst_stride * sizeof(double2),
-                                              (size_t)n_mid * sizeof(double2), (size_t)nch, hipMemcpyDeviceToDevice, stream));
-            cur = dst; cur_stride = dst_stride; stage++;
-        }
-        for (int f = 0; f < 2; f++) {
-            if (f == 0 ? !any_nbp : !any_bp1) continue;
-            long long dst_stride;
-            double2 *dst = dst_of(stage, dst_stride);
-            if (meters_fused) if (int rc = ensure_meter_partials(n_mid, bnfft - P)) return rc;
-            run_band(cur, cur_stride, dst, dst_stride, stage == nstage - 1 ? epi : nullptr, n_mid,
-                     f == 0 ? mask_nbp : mask_bp1, kBandNfftMax, f == 0 ? hist_nbp : hist_bp1, f == 0 ? cur_nbp : cur_bp1, P,
-                     nullptr, 0, meters_fused, eg_fused && stage == nstage - 1);
-            cur = dst; cur_stride = dst_stride; stage++;
-        }
-        if (meters_fused)
-            hipLaunchKernelGGL(meter_finish_kernel, dim3((unsigned)nch), dim3(kMeterFinishThreads), 0, stream, m_part[0], m_part[1],
-                               m_part_cap, (int)(n_mid / 64), dsp_size / 64, (bnfft - P) / 64, band6k ? 2 : band2g ? 1 : 0, m_adc, m_s, m_agc,
-                               -1.0 / ((double)dsp_rate * 0.100), -1.0 / ((double)dsp_rate * 0.100), (const double *)m_g2);
-        if (eg.kind && !eg_fused) pack_audio(out, out_stride, n_mid);
-        tick(3);
-        QH_HIP(hipGetLastError());
-        return QH_OK;
-    }
+    if (!k.mixed) return run_linear(k);
 
-    // ---- mixed modes: per-mode stages run on channel lists; gains/panel in a final pointwise pass
-    double2 *cur = buf[0], *other = buf[1];
+    // ---- mixed modes: per-mode stages run on channel lists; gains / panel in a final pointwise pass
+    if (int rc = plan_mixed(k)) return rc;
+    if (int rc = run_mixed_front(k)) return rc;     // xshift, xresample, adc meter, xnbp, S meter, xamsqcap, xbpsnbaout 0
+    if (int rc = run_am(k)) return rc;              // xamd's AM / SAM channels (and their bp1 when it ends their chain)
+    if (k.side) QH_HIP(hipEventRecord(ev_join, side_stream));
+    if (n_fm) if (int rc = run_fm(k)) return rc;    // xfmd
+    if (k.side) QH_HIP(hipStreamWaitEvent(stream, ev_join, 0));
+    if (n_snb[1]) snb_inplace(k, list_snb[1], n_snb[1]);       // xbpsnbain / xbpsnbaout at position 1 (RXA.c:576-577)
+    if (n_snb[0] || n_snb[1]) cur_snb ^= 1;
+    if (int rc = run_snba(k)) return rc;            // xsnba, RXA.c:578
+    // xanf, xanr, xbandpass(bp1) at position 0, xwcpagc, then the same three at position 1 (RXA.c:579-586).  The two bp1
+    // launches work on disjoint channel rows of one ping-pong history pair, so the pair flips once for both.
+    lms_at(k, 0, k.cur);
+    bp1_at(k, 0);
+    // xwcpagc modes 1-4 (sequential per channel); mode 0 rides in the output matrix below unless a position-1 stage follows
+    tick(1);
+    if (n_agc_cur || n_agc_other) if (int rc = run_agc(k)) return rc;
+    run_output(k);                                  // position 1, agc meter, xwcpagc mode 0 + xpanel, xamsq, egress
+    QH_HIP(hipGetLastError());
+    return QH_OK;
+}
+
+// ---- every channel is a linear chain: the epilogue rides on the last stage, no extra pass
+int Engine::run_linear(ChainCall &k)
+{
+    const long long n_mid = k.n_mid;
+    const int nstage = 1 + (k.any_nbp ? 1 : 0) + (k.any_bp1 ? 1 : 0);
+    int stage = 0, which = 0;
+    const double2 *cur = k.in;
+    long long cur_stride = k.in_stride;
+    auto dst_of = [&](int st, long long &stride) -> double2 * {
+        if (st == nstage - 1) { stride = k.out_stride; return k.out; }
+        stride = buf_cap;
+        double2 *p = buf[which];
+        which ^= 1;
+        return p;
+    };
+    {
+        long long dst_stride;
+        double2 *dst = dst_of(stage, dst_stride);
+        // A chain that is the front stage alone stores to the caller's rows while other tiles -- and the history pass behind the kernel --
+        // still read the input: when the rows of the two matrices overlap (include/quiskhip.h: the output may lie over the input) the
+        // stage goes to the engine's own rows and the output is written in a last pass.
+        const bool over = nstage == 1 && !extents_apart(k.out, k.out_stride, n_mid, k.in, k.in_stride, k.n_in, nch);
+        if (over) { dst = buf[0]; dst_stride = buf_cap; }
+        if (int rc = run_front(cur, cur_stride, dst, dst_stride, stage == nstage - 1 ? epi : nullptr, k.n_in, n_mid)) return rc;
+        if (over) QH_HIP(hipMemcpy2DAsync(k.out, (size_t)k.out_stride * sizeof(double2), dst, (size_t)dst_stride * sizeof(double2),
+                                          (size_t)n_mid * sizeof(double2), (size_t)nch, hipMemcpyDeviceToDevice, stream));
+        cur = dst; cur_stride = dst_stride; stage++;
+    }
+    for (int f = 0; f < 2; f++) {
+        if (f == 0 ? !k.any_nbp : !k.any_bp1) continue;
+        long long dst_stride;
+        double2 *dst = dst_of(stage, dst_stride);
+        if (k.meters_fused) if (int rc = ensure_meter_partials(n_mid, bnfft - k.P)) return rc;
+        run_band(cur, cur_stride, dst, dst_stride, stage == nstage - 1 ? epi : nullptr, n_mid,
+                 f == 0 ? mask_nbp : mask_bp1, kBandNfftMax, f == 0 ? hist_nbp : hist_bp1, f == 0 ? cur_nbp : cur_bp1, k.P,
+                 nullptr, 0, k.meters_fused, k.eg_fused && stage == nstage - 1);
+        cur = dst; cur_stride = dst_stride; stage++;
+    }
+    if (k.meters_fused)
+        hipLaunchKernelGGL(meter_finish_kernel, dim3((unsigned)nch), dim3(kMeterFinishThreads), 0, stream, m_part[0], m_part[1],
+                           m_part_cap, (int)(n_mid / 64), dsp_size / 64, (bnfft - k.P) / 64, band6k ? 2 : band2g ? 1 : 0, m_adc, m_s, m_agc,
+                           -1.0 / ((double)dsp_rate * 0.100), -1.0 / ((double)dsp_rate * 0.100), (const double *)m_g2);
+    if (eg.kind && !k.eg_fused) pack_audio(k.out, k.out_stride, n_mid);
+    tick(3);
+    QH_HIP(hipGetLastError());
+    return QH_OK;
+}
+
+// The forms of the per-mode path's stages, and the buffers they need
+int Engine::plan_mixed(ChainCall &k)
+{
     // FM channels have a long detector chain of kernels that fill a fraction of the chip (one lane per 256-sample tile of the loop,
     // a few workgroups per channel in the scans) while the other channels' work is dense filtering.  With both kinds in the call
     // the FM channels' front and nbp0 stages are launched first and their detector chain follows on the main stream; the other
@@ -2122,172 +2155,183 @@ int Engine::process_chain(const double *d_in, long long in_stride, double *d_out
     // 2 no envelope in nbp0's store, 3 no angles in nbp0's store, 4 no paired real filters, 5 no second stream at all, 6-7 where the second
     // stream forks (counted down from behind the FM channels' nbp0), 8 xfmd's dc removal as a pass of its own (fm_dc_tiled_kernel), 9 the AM
     // fade leveller as a pass of its own (am_level_tiled_kernel)
-    const bool split = n_fm > 0 && n_rest > 0 && D > 1 && !meters_on && !n_amsq && !n_snb[0] && !timing && !(dbg_forms & 1);
+    k.split = n_fm > 0 && n_rest > 0 && D > 1 && !meters_on && !n_amsq && !n_snb[0] && !timing && !(dbg_forms & 1);
     // ... and when nothing sits between a channel's last filter and the output matrix (no AGC state machine, LMS, EMNR, SNBA,
     // limiter, squelch or position-1 stage anywhere), that last stage -- nbp0 for the plain channels, bp1 for AM / SAM, the CTCSS
     // notch for FM -- applies the matrix in its store and writes the caller's buffer: the output pass (32 B per output sample) goes.
-    const bool fm_theta_fused = split && any_nbp && !band6k && !band2g && bnfft == kNfft && !(dbg_forms & 8);
+    k.fm_theta_fused = k.split && k.any_nbp && !band6k && !band2g && bnfft == kNfft && !(dbg_forms & 8);
     bool no_lms = true;
-    for (int f = 0; f < 2; f++) for (int k = 0; k < 3; k++) no_lms = no_lms && !n_lms[f][k];
-    bool agc_direct = false;            // set where xwcpagc runs: its gain multiply writes the caller's rows (see there)
-    const bool direct = split && !(dbg_forms & 2) && every_nbp && !eg.kind && !n_lim && !n_agc_cur && !n_agc_other && !n_snba && !n_snb[1] && no_lms &&
-                        !n_emnr[0] && !n_emnr[1] && !n_emnr[2] && !n_fix[0] && !n_fix[1] && !n_bp1p[1] && n_bp1p[0] == n_bp1 && n_rb == n_bp1 &&
-                        n_usb + n_fm == n_plain &&
-                        // the first stores to `out` come while other channels' input is still being read: not for a caller that works in place.
-                        // (The extents are the rows' own: first sample of the first row to last sample of the last.  nch * stride from a
-                        // pointer INTO a matrix -- a caller walking along its rows call by call -- reaches past the matrix's end by the
-                        // offset, and whether that touches the input depended on where the allocator had put the two: the same calls took
-                        // this form or the other -- AM channels' last bits, tests/test_gpu_properties_fullsize.py -- by address.)
-                        ((const char *)(out + (size_t)(nch - 1) * (size_t)out_stride + (size_t)n_mid) <= (const char *)in ||
-                         (const char *)in + ((size_t)(nch - 1) * (size_t)in_stride + (size_t)n_in) * sizeof(double2) <= (const char *)out);
+    for (int f = 0; f < 2; f++) for (int p = 0; p < 3; p++) no_lms = no_lms && !n_lms[f][p];
+    k.direct = k.split && !(dbg_forms & 2) && k.every_nbp && !eg.kind && !n_lim && !n_agc_cur && !n_agc_other && !n_snba && !n_snb[1] && no_lms &&
+               !n_emnr[0] && !n_emnr[1] && !n_emnr[2] && !n_fix[0] && !n_fix[1] && !n_bp1p[1] && n_bp1p[0] == n_bp1 && n_rb == n_bp1 &&
+               n_usb + n_fm == n_plain &&
+               // the first stores to `out` come while other channels' input is still being read: not for a caller that works in place
+               extents_apart(k.out, k.out_stride, k.n_mid, k.in, k.in_stride, k.n_in, nch);
     // ... and the AM channels' nbp0 leaves the envelope and every tile's share of the fade leveller's averages: one pass does the rest
-    const int P_am = ((P + 63) / 64) * 64;
-    const bool am_fused = direct && !(dbg_forms & 4) && n_am > 0 && n_rb == n_am + n_sam && !band6k && !band2g && bnfft == kNfft && P_am < bnfft;
+    k.P_am = ((k.P + 63) / 64) * 64;
+    k.am_fused = k.direct && !(dbg_forms & 4) && n_am > 0 && n_rb == n_am + n_sam && !band6k && !band2g && bnfft == kNfft && k.P_am < bnfft;
     // ... or, when the tiles are 2048 outputs behind 2048 samples of pre-roll and bp1 takes its channels two a tile, no pass at all: the
     // leveller's local share in nbp0's store (DET 3), the carried share in bp1's load
-    const bool am_lv_fused = am_fused && P_am == 2048 && bnfft - P_am == 2048 && np_am > 0 && n_bp1p[0] && long_parts[1] <= 1 && !(dbg_forms & (16 | 512));
-    if (am_fused) {
-        const long long nt = (n_mid + (bnfft - P_am) - 1) / (bnfft - P_am);
-        if (nt > am_tsum_cap) {
-            QH_HIP(hipStreamSynchronize(stream));
-            if (side_stream) QH_HIP(hipStreamSynchronize(side_stream));
-            drop_graphs(); epoch++;
-            (void)hipFree(am_tsum); am_tsum = nullptr;
-            QH_HIP(dev_alloc(&am_tsum, (size_t)nch * (size_t)nt * 2));
-            am_tsum_cap = nt;
-        }
-        if (am_lv_fused && am_tsum_cap + 1 > am_cin_cap) {
-            QH_HIP(hipStreamSynchronize(stream));
-            if (side_stream) QH_HIP(hipStreamSynchronize(side_stream));
-            drop_graphs(); epoch++;
-            (void)hipFree(am_cin); am_cin = nullptr;
-            QH_HIP(dev_alloc(&am_cin, (size_t)nch * (size_t)(am_tsum_cap + 1) * 2));
-            am_cin_cap = am_tsum_cap + 1;
-        }
+    k.am_lv_fused = k.am_fused && k.P_am == 2048 && bnfft - k.P_am == 2048 && np_am > 0 && n_bp1p[0] && long_parts[1] <= 1 && !(dbg_forms & (16 | 512));
+    // The AM / SAM detectors and the FM detector chain touch disjoint channel rows and disjoint state, and neither fills the
+    // chip (one workgroup or wavefront per channel): with both kinds of channel in the call the AM side runs on a second
+    // stream, forked and joined by events (which a launch-sequence capture records as graph edges).
+    k.side = k.split || ((n_am || n_sam) && n_fm && !(dbg_forms & 32));
+    if (k.am_fused) {
+        if (int rc = grow(am_tsum, am_tsum_cap, (k.n_mid + (bnfft - k.P_am) - 1) / (bnfft - k.P_am), 2LL * nch)) return rc;
+        if (k.am_lv_fused) if (int rc = grow(am_cin, am_cin_cap, am_tsum_cap + 1, 2LL * nch)) return rc;
     }
-    if (split) {
-        if (!side_stream) {
-            QH_HIP(hipStreamCreateWithFlags(&side_stream, hipStreamNonBlocking));
-            QH_HIP(hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming));
-            QH_HIP(hipEventCreateWithFlags(&ev_join, hipEventDisableTiming));
-        }
-        if (int rc = run_front(in, in_stride, cur, buf_cap, nullptr, n_in, n_mid, nullptr, 0, 1)) return rc;      // tile table, every channel
+    if (k.side) if (int rc = ensure_side_stream()) return rc;
+    for (double *&q : seg_sum)
+        if (!q) QH_HIP(dev_alloc(&q, (size_t)nch * kSegWaves * kSegMaxGroups * kSegSumW));
+    k.cur = buf[0]; k.other = buf[1];
+    return QH_OK;
+}
+
+int Engine::ensure_side_stream()
+{
+    if (side_stream) return QH_OK;
+    QH_HIP(hipStreamCreateWithFlags(&side_stream, hipStreamNonBlocking));
+    QH_HIP(hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming));
+    QH_HIP(hipEventCreateWithFlags(&ev_join, hipEventDisableTiming));
+    return QH_OK;
+}
+
+// what the second stream runs from here on follows what the main stream has launched so far
+int Engine::fork_side()
+{
+    QH_HIP(hipEventRecord(ev_fork, stream));
+    QH_HIP(hipStreamWaitEvent(side_stream, ev_fork, 0));
+    return QH_OK;
+}
+
+// The per-mode path's front and nbp0 stages, split over the two streams or not, the adc and S meters, xamsqcap and xbpsnbaout at
+// position 0
+int Engine::run_mixed_front(ChainCall &k)
+{
+    const long long n_in = k.n_in, n_mid = k.n_mid;
+    const int P = k.P;
+    double2 *&cur = k.cur, *&other = k.other;
+    if (k.split) {
+        if (int rc = run_front(k.in, k.in_stride, cur, buf_cap, nullptr, n_in, n_mid, nullptr, 0, 1)) return rc;      // tile table, every channel
         // Where the second stream starts: behind the FM channels' nbp0 (2; the default), behind their front (1) or at once (0) -- QH_DBG_FORMS
         // bits 6-7 count DOWN from 2 (experiments).  The FM channels' chain is the longer one and ends in kernels that cannot fill the chip
         // (the loop's lanes, the CTCSS notch's scans): with their front and nbp0 alone on the chip first, all of them run beside the other
         // channels' dense filters (config 4, one box: 10.45 ms forked at once, 10.31 forked here).
         const int fork_at = 2 - (((dbg_forms >> 6) & 3) > 2 ? 2 : ((dbg_forms >> 6) & 3));
-        if (fork_at == 0) { QH_HIP(hipEventRecord(ev_fork, stream)); QH_HIP(hipStreamWaitEvent(side_stream, ev_fork, 0)); }
-        if (int rc = run_front(in, in_stride, cur, buf_cap, nullptr, n_in, n_mid, list_fm, n_fm, 2)) return rc;
-        if (fork_at == 1) { QH_HIP(hipEventRecord(ev_fork, stream)); QH_HIP(hipStreamWaitEvent(side_stream, ev_fork, 0)); }
+        if (fork_at == 0) if (int rc = fork_side()) return rc;
+        if (int rc = run_front(k.in, k.in_stride, cur, buf_cap, nullptr, n_in, n_mid, list_fm, n_fm, 2)) return rc;
+        if (fork_at == 1) if (int rc = fork_side()) return rc;
         int hc = cur_nbp;
         // the FM channels' nbp0 feeds the loop's phase detector and nothing else: its store takes the angles (first half of the rows)
-        if (any_nbp) run_band(cur, buf_cap, other, buf_cap, nullptr, n_mid, mask_nbp, kBandNfftMax, hist_nbp, hc, P, list_fm, n_fm, false, false,
-                              fm_theta_fused ? 1 : 0, reinterpret_cast<double *>(other), 2 * buf_cap);
-        if (fork_at >= 2) { QH_HIP(hipEventRecord(ev_fork, stream)); QH_HIP(hipStreamWaitEvent(side_stream, ev_fork, 0)); }
+        if (k.any_nbp) run_band(cur, buf_cap, other, buf_cap, nullptr, n_mid, mask_nbp, kBandNfftMax, hist_nbp, hc, P, list_fm, n_fm, false, false,
+                                k.fm_theta_fused ? 1 : 0, reinterpret_cast<double *>(other), 2 * buf_cap);
+        if (fork_at >= 2) if (int rc = fork_side()) return rc;
         std::swap(stream, side_stream);
-        int rc2 = run_front(in, in_stride, cur, buf_cap, nullptr, n_in, n_mid, list_rest, n_rest, 2);
+        int rc2 = run_front(k.in, k.in_stride, cur, buf_cap, nullptr, n_in, n_mid, list_rest, n_rest, 2);
         hc = cur_nbp;
-        if (!rc2 && any_nbp) {
-            if (direct) {       // the plain channels end here: output matrix in the store, straight to the caller's buffer
-                if (n_usb) run_band(cur, buf_cap, out, out_stride, epi, n_mid, mask_nbp, kBandNfftMax, hist_nbp, hc, P, list_usb, n_usb);
+        if (!rc2 && k.any_nbp) {
+            if (k.direct) {     // the plain channels end here: output matrix in the store, straight to the caller's buffer
+                if (n_usb) run_band(cur, buf_cap, k.out, k.out_stride, epi, n_mid, mask_nbp, kBandNfftMax, hist_nbp, hc, P, list_usb, n_usb);
                 hc = cur_nbp;
-                if (am_fused) {
+                if (k.am_fused) {
                     if (n_sam) run_band(cur, buf_cap, other, buf_cap, nullptr, n_mid, mask_nbp, kBandNfftMax, hist_nbp, hc, P, list_sam, n_sam);
                     hc = cur_nbp;
-                    run_band(cur, buf_cap, other, buf_cap, nullptr, n_mid, mask_nbp, kBandNfftMax, hist_nbp, hc, P_am, list_am, n_am, false, false,
-                             am_lv_fused ? 3 : 2, reinterpret_cast<double *>(other), 2 * buf_cap);
+                    run_band(cur, buf_cap, other, buf_cap, nullptr, n_mid, mask_nbp, kBandNfftMax, hist_nbp, hc, k.P_am, list_am, n_am, false, false,
+                             k.am_lv_fused ? 3 : 2, reinterpret_cast<double *>(other), 2 * buf_cap);
                 } else if (n_rb) run_band(cur, buf_cap, other, buf_cap, nullptr, n_mid, mask_nbp, kBandNfftMax, hist_nbp, hc, P, list_rb, n_rb);
             } else run_band(cur, buf_cap, other, buf_cap, nullptr, n_mid, mask_nbp, kBandNfftMax, hist_nbp, hc, P, list_rest, n_rest);
         }
         std::swap(stream, side_stream);
         if (rc2) return rc2;
-        if (any_nbp) { cur_nbp ^= 1; std::swap(cur, other); }
-        if (int rc = run_front(in, in_stride, cur, buf_cap, nullptr, n_in, n_mid, nullptr, 0, 3)) return rc;          // histories, oscillator phases
+        if (k.any_nbp) { cur_nbp ^= 1; std::swap(cur, other); }
+        if (int rc = run_front(k.in, k.in_stride, cur, buf_cap, nullptr, n_in, n_mid, nullptr, 0, 3)) return rc;          // histories, oscillator phases
     } else {
-    if (int rc = run_front(in, in_stride, cur, buf_cap, nullptr, n_in, n_mid)) return rc;
-    if (meters_on) hipLaunchKernelGGL(meter_kernel, dim3((unsigned)nch), dim3(64), 0, stream, cur, buf_cap, nblk, dsp_size, m_adc,
-                                      m_prm, (const int *)nullptr);
-    if (any_nbp) {
-        run_band(cur, buf_cap, other, buf_cap, nullptr, n_mid, mask_nbp, kBandNfftMax, hist_nbp, cur_nbp, P, nullptr, 0);
-        std::swap(cur, other);
+        if (int rc = run_front(k.in, k.in_stride, cur, buf_cap, nullptr, n_in, n_mid)) return rc;
+        if (meters_on) hipLaunchKernelGGL(meter_kernel, dim3((unsigned)nch), dim3(64), 0, stream, cur, buf_cap, k.nblk, dsp_size, m_adc,
+                                          m_prm, (const int *)nullptr);
+        if (k.any_nbp) {
+            run_band(cur, buf_cap, other, buf_cap, nullptr, n_mid, mask_nbp, kBandNfftMax, hist_nbp, cur_nbp, P, nullptr, 0);
+            std::swap(cur, other);
+        }
     }
-    }
-    if (meters_on) hipLaunchKernelGGL(meter_kernel, dim3((unsigned)nch), dim3(64), 0, stream, cur, buf_cap, nblk, dsp_size, m_s,
+    if (meters_on) hipLaunchKernelGGL(meter_kernel, dim3((unsigned)nch), dim3(64), 0, stream, cur, buf_cap, k.nblk, dsp_size, m_s,
                                       m_prm, (const int *)nullptr);
     if (n_amsq) {           // xamsqcap (RXA.c:571): the magnitudes of the signal behind nbp0, for xamsq at the end of the chain
-        if (buf_cap > amsq_mag_cap) {
-            QH_HIP(hipStreamSynchronize(stream));
-            drop_graphs(); epoch++;
-            (void)hipFree(amsq_mag); amsq_mag = nullptr;
-            QH_HIP(dev_alloc(&amsq_mag, (size_t)nch * (size_t)buf_cap));
-            amsq_mag_cap = buf_cap;
-        }
+        if (int rc = grow(amsq_mag, amsq_mag_cap, buf_cap, nch)) return rc;
         long long per = (n_mid + NT - 1) / NT;
         hipLaunchKernelGGL(amsq_cap_kernel, dim3((unsigned)(per < 1024 ? per : 1024), (unsigned)n_amsq), dim3(NT), 0, stream, cur, buf_cap,
                            (int)n_mid, list_amsq, amsq_mag, amsq_mag_cap);
     }
     // xbpsnbaout at position 0 (RXA.c:572): the 250..5700 Hz filter of the signal ahead of nbp0 replaces nbp0's output
-    auto snb_inplace = [&](const int *list, int n) {
-        int hc = cur_snb;
-        run_band(cur, buf_cap, other, buf_cap, nullptr, n_mid, mask_snb, kBandNfftMax, hist_snb, hc, P, list, n);
-        long long per = (n_mid + NT - 1) / NT;
-        hipLaunchKernelGGL(copy_rows_kernel, dim3((unsigned)(per < 1024 ? per : 1024), (unsigned)n), dim3(NT), 0, stream, other, cur, buf_cap,
-                           (int)n_mid, list);
-    };
     if (n_snb[0]) {
-        if (any_nbp) { int hc = cur_snb; run_band(other, buf_cap, cur, buf_cap, nullptr, n_mid, mask_snb, kBandNfftMax, hist_snb, hc, P, list_snb[0], n_snb[0]); }
-        else snb_inplace(list_snb[0], n_snb[0]);
+        if (k.any_nbp) { int hc = cur_snb; run_band(other, buf_cap, cur, buf_cap, nullptr, n_mid, mask_snb, kBandNfftMax, hist_snb, hc, P, list_snb[0], n_snb[0]); }
+        else snb_inplace(k, list_snb[0], n_snb[0]);
     }
     tick(1);
-    // The AM / SAM detectors and the FM detector chain touch disjoint channel rows and disjoint state, and neither fills the
-    // chip (one workgroup or wavefront per channel): with both kinds of channel in the call the AM side runs on a second
-    // stream, forked and joined by events (which a launch-sequence capture records as graph edges).
-    const bool side = split || ((n_am || n_sam) && n_fm && !(dbg_forms & 32));
+    return QH_OK;
+}
+
+// bpsnba on the listed channels' rows of cur, through the rows of other
+void Engine::snb_inplace(const ChainCall &k, const int *list, int n)
+{
+    int hc = cur_snb;
+    run_band(k.cur, buf_cap, k.other, buf_cap, nullptr, k.n_mid, mask_snb, kBandNfftMax, hist_snb, hc, k.P, list, n);
+    long long per = (k.n_mid + NT - 1) / NT;
+    hipLaunchKernelGGL(copy_rows_kernel, dim3((unsigned)(per < 1024 ? per : 1024), (unsigned)n), dim3(NT), 0, stream, k.other, k.cur, buf_cap,
+                       (int)k.n_mid, list);
+}
+
+// Segment scans: one 16-wavefront workgroup per channel fills one CU.  With fewer channels of a kind than the chip has CUs the
+// call is cut into 16 G segments, G workgroups per channel, pass 1 and pass 2 as two launches (qh_wave.hpp, MODE 1 / 2).
+int Engine::seg_groups(int count, long long n_mid) const
+{
+    int G = count > 0 ? 256 / count : 1;
+    while (G > 1 && n_mid / (64LL * kSegWaves * G) < 8) G--;        // at least 8 batches of 64 samples per segment
+    return G < 1 ? 1 : G > kSegMaxGroups ? kSegMaxGroups : G;
+}
+
+// xamd's envelope and fade leveller over the listed channels' rows of cur in G segments (SAM: mixed with the phases pts):
+// pass 1, pass 2 and the commit of the carried states, or one pass
+template <bool SAM>
+void Engine::am_detect(const ChainCall &k, hipStream_t s, const int *list, int n, int G, const double *pts, long long pts_stride, double *gs)
+{
+    if (G > 1) {
+        hipLaunchKernelGGL((am_detect_tiled_kernel<SAM, 1>), dim3((unsigned)n, (unsigned)G), dim3(kSegThreads), 0, s, k.cur, buf_cap,
+                           (int)k.n_mid, list, levelfade, am_state, am_prm, pts, pts_stride, gs);
+        hipLaunchKernelGGL((am_detect_tiled_kernel<SAM, 2>), dim3((unsigned)n, (unsigned)G), dim3(kSegThreads), 0, s, k.cur, buf_cap,
+                           (int)k.n_mid, list, levelfade, am_state, am_prm, pts, pts_stride, gs, am_next);
+        hipLaunchKernelGGL(commit_am_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, am_state, (const AmState *)am_next, list, n, levelfade);
+    } else
+        hipLaunchKernelGGL((am_detect_tiled_kernel<SAM, 0>), dim3((unsigned)n), dim3(kSegThreads), 0, s, k.cur, buf_cap, (int)k.n_mid,
+                           list, levelfade, am_state, am_prm, pts, pts_stride, (double *)nullptr);
+}
+
+// xamd for the AM and SAM channels, on the second stream when the call has FM channels too; and bp1 behind them there when it is
+// their last stage
+int Engine::run_am(ChainCall &k)
+{
+    const long long n_mid = k.n_mid;
+    double2 *cur = k.cur, *other = k.other;
     hipStream_t am_stream = stream;
-    if (split) am_stream = side_stream;         // forked already: the AM detectors follow the other channels' filters there
-    else if (side) {
-        if (!side_stream) {
-            QH_HIP(hipStreamCreateWithFlags(&side_stream, hipStreamNonBlocking));
-            QH_HIP(hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming));
-            QH_HIP(hipEventCreateWithFlags(&ev_join, hipEventDisableTiming));
-        }
-        QH_HIP(hipEventRecord(ev_fork, stream));
-        QH_HIP(hipStreamWaitEvent(side_stream, ev_fork, 0));
+    if (k.split) am_stream = side_stream;         // forked already: the AM detectors follow the other channels' filters there
+    else if (k.side) {
+        if (int rc = fork_side()) return rc;
         am_stream = side_stream;
     }
-    // Segment scans: one 16-wavefront workgroup per channel fills one CU.  With fewer channels of a kind than the chip has CUs the
-    // call is cut into 16 G segments, G workgroups per channel, pass 1 and pass 2 as two launches (qh_wave.hpp, MODE 1 / 2).
-    auto seg_groups = [&](int count) {
-        int G = count > 0 ? 256 / count : 1;
-        while (G > 1 && n_mid / (64LL * kSegWaves * G) < 8) G--;        // at least 8 batches of 64 samples per segment
-        return G < 1 ? 1 : G > kSegMaxGroups ? kSegMaxGroups : G;
-    };
-    for (double *&q : seg_sum)
-        if (!q) QH_HIP(dev_alloc(&q, (size_t)nch * kSegWaves * kSegMaxGroups * kSegSumW));
     FmDcSrc amlv_src{ nullptr, 0, 0 };
-    if (n_am && am_lv_fused) {      // the envelope + the leveller's local share lie in the channels' own rows (first half); bp1 loads them from there
-        hipLaunchKernelGGL(am_lv_chain_kernel, dim3((unsigned)n_am), dim3(64), 0, am_stream, (int)n_mid, bnfft - P_am, list_am, (const int *)levelfade, am_state,
+    if (n_am && k.am_lv_fused) {    // the envelope + the leveller's local share lie in the channels' own rows (first half); bp1 loads them from there
+        hipLaunchKernelGGL(am_lv_chain_kernel, dim3((unsigned)n_am), dim3(64), 0, am_stream, (int)n_mid, bnfft - k.P_am, list_am, (const int *)levelfade, am_state,
                            am_prm, (const double *)am_tsum, am_tsum_cap, (const double *)am_last, am_cin, am_cin_cap);
         amlv_src = FmDcSrc{ reinterpret_cast<double *>(cur), 2 * buf_cap, 11 };
-    } else if (n_am && am_fused) {  // envelopes in the channels' own rows (first half), audio to the rows of `other`
-        const int G = seg_groups(n_am + (n_mid >= kSamTiledMin ? n_sam0 : 0));
+    } else if (n_am && k.am_fused) {  // envelopes in the channels' own rows (first half), audio to the rows of `other`
+        const int G = seg_groups(n_am + (n_mid >= kSamTiledMin ? n_sam0 : 0), n_mid);
         hipLaunchKernelGGL(am_level_tiled_kernel, dim3((unsigned)n_am, (unsigned)G), dim3(kSegThreads), 0, am_stream,
                            (const double *)reinterpret_cast<double *>(cur), 2 * buf_cap, other, buf_cap, (int)n_mid, list_am, levelfade, (const AmState *)am_state,
-                           am_prm, (const double *)am_tsum, am_tsum_cap, bnfft - P_am, am_next);
+                           am_prm, (const double *)am_tsum, am_tsum_cap, bnfft - k.P_am, am_next);
         hipLaunchKernelGGL(commit_am_kernel, dim3((unsigned)((n_am + 255) / 256)), dim3(256), 0, am_stream, am_state, (const AmState *)am_next, list_am, n_am, levelfade);
-    } else if (n_am) {
-        const int G = seg_groups(n_am + (n_mid >= kSamTiledMin ? n_sam0 : 0));
-        if (G > 1) {
-            hipLaunchKernelGGL((am_detect_tiled_kernel<false, 1>), dim3((unsigned)n_am, (unsigned)G), dim3(kSegThreads), 0, am_stream, cur, buf_cap,
-                               (int)n_mid, list_am, levelfade, am_state, am_prm, (const double *)nullptr, 0LL, seg_sum[0]);
-            hipLaunchKernelGGL((am_detect_tiled_kernel<false, 2>), dim3((unsigned)n_am, (unsigned)G), dim3(kSegThreads), 0, am_stream, cur, buf_cap,
-                               (int)n_mid, list_am, levelfade, am_state, am_prm, (const double *)nullptr, 0LL, seg_sum[0], am_next);
-            hipLaunchKernelGGL(commit_am_kernel, dim3((unsigned)((n_am + 255) / 256)), dim3(256), 0, am_stream, am_state, (const AmState *)am_next, list_am, n_am, levelfade);
-        } else
-            hipLaunchKernelGGL((am_detect_tiled_kernel<false, 0>), dim3((unsigned)n_am), dim3(kSegThreads), 0, am_stream, cur, buf_cap, (int)n_mid,
-                               list_am, levelfade, am_state, am_prm, (const double *)nullptr, 0LL, (double *)nullptr);
-    }
+    } else if (n_am)
+        am_detect<false>(k, am_stream, list_am, n_am, seg_groups(n_am + (n_mid >= kSamTiledMin ? n_sam0 : 0), n_mid), nullptr, 0, seg_sum[0]);
     {
         // SAM without sideband separation in a long call: angles, the loop one tile per lane with a warm-up, verify / repair,
         // then the mix with the phase each sample saw and the fade leveller over time segments (qh_tiled.hpp).  The channels'
@@ -2302,35 +2346,18 @@ int Engine::process_chain(const double *d_in, long long in_stride, double *d_out
                                (int)n_mid, list_sam, theta, 2 * buf_cap);
             const long long ntl = (n_mid + kSamTile - 1) / kSamTile;
             const int ngroups = (int)((ntl + 63) / 64);
-            if ((long long)ngroups * 64 > pll_ends_cap) {
-                QH_HIP(hipStreamSynchronize(stream));
-                if (side) QH_HIP(hipStreamSynchronize(side_stream));
-                drop_graphs(); epoch++;
-                (void)hipFree(pll_ends); pll_ends = nullptr;
-                QH_HIP(dev_alloc(&pll_ends, (size_t)nch * (size_t)ngroups * 64 * kPllEndsW));
-                pll_ends_cap = (long long)ngroups * 64;
-            }
+            if (int rc = grow(pll_ends, pll_ends_cap, (long long)ngroups * 64, (long long)nch * kPllEndsW)) return rc;
             hipLaunchKernelGGL((pll_lanes_kernel<true>), dim3((unsigned)ngroups, (unsigned)nt), dim3(64), 0, am_stream, (const double *)theta,
                                2 * buf_cap, pts, 2 * buf_cap, (int)n_mid, list_sam, (const PllState *)pll_state, pll_ends, pll_ends_cap * kPllEndsW,
                                sam_pll_prm, kSamTile, kSamWarm);
             hipLaunchKernelGGL((pll_verify_kernel<true>), dim3((unsigned)nt), dim3(64), 0, am_stream, (const double *)theta, 2 * buf_cap, pts,
                                2 * buf_cap, (int)n_mid, list_sam, pll_state, pll_ends, pll_ends_cap * kPllEndsW, sam_pll_prm, kSamTile, kSamWarm,
                                pll_nfixed, pll_check_only);
-            if (nt0) {
-                const int G = seg_groups(n_am + nt);
-                double *gs = seg_sum[0] + (size_t)n_am * kSegWaves * kSegMaxGroups * kSegSumW;       // behind the AM channels' rows
-                if (G > 1) {
-                    hipLaunchKernelGGL((am_detect_tiled_kernel<true, 1>), dim3((unsigned)nt0, (unsigned)G), dim3(kSegThreads), 0, am_stream, cur,
-                                       buf_cap, (int)n_mid, list_sam, levelfade, am_state, am_prm, (const double *)pts, 2 * buf_cap, gs);
-                    hipLaunchKernelGGL((am_detect_tiled_kernel<true, 2>), dim3((unsigned)nt0, (unsigned)G), dim3(kSegThreads), 0, am_stream, cur,
-                                       buf_cap, (int)n_mid, list_sam, levelfade, am_state, am_prm, (const double *)pts, 2 * buf_cap, gs, am_next);
-                    hipLaunchKernelGGL(commit_am_kernel, dim3((unsigned)((nt0 + 255) / 256)), dim3(256), 0, am_stream, am_state, (const AmState *)am_next, list_sam, nt0, levelfade);
-                } else
-                    hipLaunchKernelGGL((am_detect_tiled_kernel<true, 0>), dim3((unsigned)nt0), dim3(kSegThreads), 0, am_stream, cur, buf_cap,
-                                       (int)n_mid, list_sam, levelfade, am_state, am_prm, (const double *)pts, 2 * buf_cap, (double *)nullptr);
-            }
+            if (nt0)        // (the segment summaries behind the AM channels' rows)
+                am_detect<true>(k, am_stream, list_sam, nt0, seg_groups(n_am + nt, n_mid), pts, 2 * buf_cap,
+                                seg_sum[0] + (size_t)n_am * kSegWaves * kSegMaxGroups * kSegSumW);
             if (ntsb) {
-                const int G = seg_groups(n_am + nt), S = kSegWaves * G;
+                const int G = seg_groups(n_am + nt, n_mid), S = kSegWaves * G;
                 if (int rc = set_sb_phi(n_mid, S)) return rc;
                 const int *lst = list_sam + nt0;
                 double *gs = seg_sum[0] + (size_t)(n_am + nt0) * kSegWaves * kSegMaxGroups * kSegSumW;
@@ -2350,342 +2377,324 @@ int Engine::process_chain(const double *d_in, long long in_stride, double *d_out
         if (n_sam - nt) hipLaunchKernelGGL(sam_pll_kernel, dim3((unsigned)(n_sam - nt)), dim3(64), 0, am_stream, cur, buf_cap, (int)n_mid,
                                            list_sam + nt, pll_state, sam_prm, sam_pll_prm, am_state);
     }
-    if (direct && n_bp1p[0]) {      // bp1 is the AM / SAM channels' last stage: it follows their detectors on the second stream
+    if (k.direct && n_bp1p[0]) {      // bp1 is the AM / SAM channels' last stage: it follows their detectors on the second stream
         std::swap(stream, side_stream);
         int hc = cur_bp1;
-        if (am_fused) {
+        if (k.am_fused) {
             if (amlv_src.a) band_amlv = &amlv_src;
-            run_band(other, buf_cap, out, out_stride, epi, n_mid, mask_bp1, kBandNfftMax, hist_bp1, hc, P, list_am, n_am, false, false, 0, nullptr, 0,
+            run_band(other, buf_cap, k.out, k.out_stride, epi, n_mid, mask_bp1, kBandNfftMax, hist_bp1, hc, k.P, list_am, n_am, false, false, 0, nullptr, 0,
                      np_am && !(dbg_forms & 16) ? pairs_am : nullptr, np_am);
             band_amlv = nullptr;
             hc = cur_bp1;
-            if (n_sam) run_band(cur, buf_cap, out, out_stride, epi, n_mid, mask_bp1, kBandNfftMax, hist_bp1, hc, P, list_sam, n_sam, false, false, 0,
+            if (n_sam) run_band(cur, buf_cap, k.out, k.out_stride, epi, n_mid, mask_bp1, kBandNfftMax, hist_bp1, hc, k.P, list_sam, n_sam, false, false, 0,
                                 nullptr, 0, np_sam && !(dbg_forms & 16) ? pairs_sam : nullptr, np_sam);
-        } else run_band(cur, buf_cap, out, out_stride, epi, n_mid, mask_bp1, kBandNfftMax, hist_bp1, hc, P, list_bp1p[0], n_bp1p[0]);
+        } else run_band(cur, buf_cap, k.out, k.out_stride, epi, n_mid, mask_bp1, kBandNfftMax, hist_bp1, hc, k.P, list_bp1p[0], n_bp1p[0]);
         std::swap(stream, side_stream);
     }
-    if (side) QH_HIP(hipEventRecord(ev_join, side_stream));
-    if (n_fm) {
-        // xfmd's loop (fmd.c:151-172), time-tiled (qh_tiled.hpp): angles, then one loop per lane and tile, then dc removal + gain.
-        // The FM channels' rows of `other` are free here: first half = angles, second half = loop filter output.
-        const bool pair = de_real && np_fm && !band6k && !band2g && bnfft == kNfft && !(dbg_forms & 16);      // the de-emphasis stage two channels a tile
-        const bool fmdc_fused = pair && long_parts[2] <= 1 && !(dbg_forms & 256);
-        FmDcSrc fmdc_src{ nullptr, 0, 0 };
-        {
-            // fused: nbp0 left the angles in the channels' own rows (first half) and the loop output goes to the rows of `other`
-            double *theta = reinterpret_cast<double *>(fm_theta_fused ? cur : other), *fil = reinterpret_cast<double *>(other) + buf_cap;
-            if (fmdc_fused) fil = reinterpret_cast<double *>(cur) + buf_cap;     // (the de-emphasis stage reads it while it writes the rows of `other`)
-            const long long per = (n_mid + NT - 1) / NT;
-            if (!fm_theta_fused)
-                hipLaunchKernelGGL(pll_theta_kernel, dim3((unsigned)(per < 1024 ? per : 1024), (unsigned)n_fm), dim3(NT), 0, stream, cur, buf_cap,
-                                   (int)n_mid, list_fm, theta, 2 * buf_cap);
-            static const int fm_tile_env = getenv("QH_FM_TILE") ? atoi(getenv("QH_FM_TILE")) : 0;
-            // the longest tile that still gives the chip 512 wavefronts of 64 tiles: the 768-sample warm-up is 3/4 of a 256-sample
-            // tile's steps and 3/11 of a 2048-sample tile's
-            int fm_tile = kFmTile;
-            while (fm_tile < 2048 && (long long)n_fm * n_mid / (64LL * 2 * fm_tile) >= 512) fm_tile *= 2;
-            if (fm_tile_env > 0) fm_tile = fm_tile_env;
-            const long long ntl = (n_mid + fm_tile - 1) / fm_tile;
-            const int ngroups = (int)((ntl + 63) / 64);
-            if ((long long)ngroups * 64 > pll_ends_cap) {
-                QH_HIP(hipStreamSynchronize(stream));
-                drop_graphs(); epoch++;
-                (void)hipFree(pll_ends); pll_ends = nullptr;
-                QH_HIP(dev_alloc(&pll_ends, (size_t)nch * (size_t)ngroups * 64 * kPllEndsW));
-                pll_ends_cap = (long long)ngroups * 64;
-            }
-            // fmdc_fused: the dc removal and gain (fmd.c:169-171) do not get a pass of their own -- the loop kernels take the tile's own
-            // share of the average off (local_dc), a chain over the tiles' contributions gives the average ahead of every tile, and the
-            // de-emphasis stage's load takes the rest off and applies the gain (OsfirArgs::fmdc_*): 8 bytes per sample read there instead
-            // of 8 read + 16 written here and 16 read there
-            const bool fused_now = fmdc_fused && (fm_tile & (fm_tile - 1)) == 0 && fm_tile <= 2048;
-            if (fused_now && pll_ends_cap + 1 > fm_cin_cap) {
-                QH_HIP(hipStreamSynchronize(stream));
-                if (side_stream) QH_HIP(hipStreamSynchronize(side_stream));
-                drop_graphs(); epoch++;
-                (void)hipFree(fm_cin); fm_cin = nullptr;
-                QH_HIP(dev_alloc(&fm_cin, (size_t)nch * (size_t)(pll_ends_cap + 1)));
-                fm_cin_cap = pll_ends_cap + 1;
-            }
-            hipLaunchKernelGGL((pll_lanes_kernel<false>), dim3((unsigned)ngroups, (unsigned)n_fm), dim3(64), 0, stream, (const double *)theta,
-                               2 * buf_cap, fil, 2 * buf_cap, (int)n_mid, list_fm, (const PllState *)fm_pll_state, pll_ends, pll_ends_cap * kPllEndsW,
-                               fm_pll_prm, fm_tile, kFmWarm, fused_now ? 1 : 0);
-            hipLaunchKernelGGL((pll_verify_kernel<false>), dim3((unsigned)n_fm), dim3(64), 0, stream, (const double *)theta, 2 * buf_cap, fil,
-                               2 * buf_cap, (int)n_mid, list_fm, fm_pll_state, pll_ends, pll_ends_cap * kPllEndsW, fm_pll_prm, fm_tile, kFmWarm,
-                               pll_nfixed, pll_check_only, fused_now ? 1 : 0);
-            if (fused_now) {
-                hipLaunchKernelGGL(fm_dc_chain_kernel, dim3((unsigned)n_fm), dim3(64), 0, stream, (int)n_mid, fm_tile, list_fm, fm_pll_state, fm_pll_prm,
-                                   (const double *)pll_ends, pll_ends_cap * kPllEndsW, fm_cin, fm_cin_cap);
-                int sh = 0;
-                while ((1 << sh) < fm_tile) sh++;
-                fmdc_src = FmDcSrc{ fil, 2 * buf_cap, sh };
-            } else {
-                // dc removal + gain: the tiles' contributions are in `ends` already, one pass over `fil`
-                const int G = seg_groups(n_fm);
-                hipLaunchKernelGGL(fm_dc_tiled_kernel, dim3((unsigned)n_fm, (unsigned)G), dim3(kSegThreads), 0, stream, (const double *)fil,
-                                   2 * buf_cap, cur, buf_cap, (int)n_mid, list_fm, (const PllState *)fm_pll_state, (const double *)fm_again, fm_pll_prm,
-                                   (const double *)pll_ends, pll_ends_cap * kPllEndsW, fm_tile, fmdc_next);
-                hipLaunchKernelGGL(commit_fmdc_kernel, dim3((unsigned)((n_fm + 255) / 256)), dim3(256), 0, stream, fm_pll_state, (const double *)fmdc_next, list_fm, n_fm);
-            }
+    return QH_OK;
+}
+
+// xfmd (fmd.c): the loop, dc removal and gain, de-emphasis, audio filter, CTCSS notch and the detector limiter
+int Engine::run_fm(ChainCall &k)
+{
+    const long long n_mid = k.n_mid;
+    double2 *cur = k.cur, *other = k.other;
+    // xfmd's loop (fmd.c:151-172), time-tiled (qh_tiled.hpp): angles, then one loop per lane and tile, then dc removal + gain.
+    // The FM channels' rows of `other` are free here: first half = angles, second half = loop filter output.
+    const bool pair = de_real && np_fm && !band6k && !band2g && bnfft == kNfft && !(dbg_forms & 16);      // the de-emphasis stage two channels a tile
+    // fmdc_fused: the dc removal and gain (fmd.c:169-171) do not get a pass of their own -- the loop kernels take the tile's own
+    // share of the average off (local_dc), a chain over the tiles' contributions gives the average ahead of every tile, and the
+    // de-emphasis stage's load takes the rest off and applies the gain (OsfirArgs::fmdc_*): 8 bytes per sample read there instead
+    // of 8 read + 16 written here and 16 read there
+    const bool fmdc_fused = pair && long_parts[2] <= 1 && !(dbg_forms & 256);
+    FmDcSrc fmdc_src{ nullptr, 0, 0 };
+    {
+        // fused: nbp0 left the angles in the channels' own rows (first half) and the loop output goes to the rows of `other`
+        double *theta = reinterpret_cast<double *>(k.fm_theta_fused ? cur : other), *fil = reinterpret_cast<double *>(other) + buf_cap;
+        if (fmdc_fused) fil = reinterpret_cast<double *>(cur) + buf_cap;     // (the de-emphasis stage reads it while it writes the rows of `other`)
+        const long long per = (n_mid + NT - 1) / NT;
+        if (!k.fm_theta_fused)
+            hipLaunchKernelGGL(pll_theta_kernel, dim3((unsigned)(per < 1024 ? per : 1024), (unsigned)n_fm), dim3(NT), 0, stream, cur, buf_cap,
+                               (int)n_mid, list_fm, theta, 2 * buf_cap);
+        // the longest tile that still gives the chip 512 wavefronts of 64 tiles: the 768-sample warm-up is 3/4 of a 256-sample
+        // tile's steps and 3/11 of a 2048-sample tile's
+        int fm_tile = kFmTile;
+        while (fm_tile < 2048 && (long long)n_fm * n_mid / (64LL * 2 * fm_tile) >= 512) fm_tile *= 2;
+        const long long ntl = (n_mid + fm_tile - 1) / fm_tile;
+        const int ngroups = (int)((ntl + 63) / 64);
+        if (int rc = grow(pll_ends, pll_ends_cap, (long long)ngroups * 64, (long long)nch * kPllEndsW)) return rc;
+        if (fmdc_fused) if (int rc = grow(fm_cin, fm_cin_cap, pll_ends_cap + 1, nch)) return rc;
+        hipLaunchKernelGGL((pll_lanes_kernel<false>), dim3((unsigned)ngroups, (unsigned)n_fm), dim3(64), 0, stream, (const double *)theta,
+                           2 * buf_cap, fil, 2 * buf_cap, (int)n_mid, list_fm, (const PllState *)fm_pll_state, pll_ends, pll_ends_cap * kPllEndsW,
+                           fm_pll_prm, fm_tile, kFmWarm, fmdc_fused ? 1 : 0);
+        hipLaunchKernelGGL((pll_verify_kernel<false>), dim3((unsigned)n_fm), dim3(64), 0, stream, (const double *)theta, 2 * buf_cap, fil,
+                           2 * buf_cap, (int)n_mid, list_fm, fm_pll_state, pll_ends, pll_ends_cap * kPllEndsW, fm_pll_prm, fm_tile, kFmWarm,
+                           pll_nfixed, pll_check_only, fmdc_fused ? 1 : 0);
+        if (fmdc_fused) {
+            hipLaunchKernelGGL(fm_dc_chain_kernel, dim3((unsigned)n_fm), dim3(64), 0, stream, (int)n_mid, fm_tile, list_fm, fm_pll_state, fm_pll_prm,
+                               (const double *)pll_ends, pll_ends_cap * kPllEndsW, fm_cin, fm_cin_cap);
+            int sh = 0;
+            while ((1 << sh) < fm_tile) sh++;
+            fmdc_src = FmDcSrc{ fil, 2 * buf_cap, sh };
+        } else {
+            // dc removal + gain: the tiles' contributions are in `ends` already, one pass over `fil`
+            const int G = seg_groups(n_fm, n_mid);
+            hipLaunchKernelGGL(fm_dc_tiled_kernel, dim3((unsigned)n_fm, (unsigned)G), dim3(kSegThreads), 0, stream, (const double *)fil,
+                               2 * buf_cap, cur, buf_cap, (int)n_mid, list_fm, (const PllState *)fm_pll_state, (const double *)fm_again, fm_pll_prm,
+                               (const double *)pll_ends, pll_ends_cap * kPllEndsW, fm_tile, fmdc_next);
+            hipLaunchKernelGGL(commit_fmdc_kernel, dim3((unsigned)((n_fm + 255) / 256)), dim3(256), 0, stream, fm_pll_state, (const double *)fmdc_next, list_fm, n_fm);
         }
-        {   // de-emphasis: real taps on a real signal, two channels per tile
-            if (fmdc_src.a) band_fmdc = &fmdc_src;
-            run_band(cur, buf_cap, other, buf_cap, nullptr, n_mid, mask_de, 0, hist_de, cur_de, P, list_fm, n_fm, false, false, 0, nullptr, 0,
-                     pair ? pairs_fm : nullptr, np_fm);
-            band_fmdc = nullptr;
-        }
-        run_band(other, buf_cap, cur, buf_cap, nullptr, n_mid, mask_aud, 0, hist_aud, cur_aud, P, list_fm, n_fm);   // audio filter
-        tick(1);
-        {
-            const int G = seg_groups(n_fm);
-            if (G > 1) {
-                hipLaunchKernelGGL((snotch_tiled_kernel<1>), dim3((unsigned)n_fm, (unsigned)G), dim3(kSegThreads), 0, stream, cur, buf_cap, (int)n_mid,
-                                   list_fm, sn_prm, sn_state, seg_sum[2]);
-                hipLaunchKernelGGL((snotch_tiled_kernel<2>), dim3((unsigned)n_fm, (unsigned)G), dim3(kSegThreads), 0, stream, cur, buf_cap, (int)n_mid,
-                                   list_fm, sn_prm, sn_state, seg_sum[2], direct ? out : (double2 *)nullptr, out_stride, (const EpiParam *)epi, sn_next);
-                hipLaunchKernelGGL(commit_snotch_kernel, dim3((unsigned)((n_fm + 255) / 256)), dim3(256), 0, stream, sn_state, (const SnotchState *)sn_next, list_fm, n_fm,
-                                   (const SnotchParam *)sn_prm);
-            } else
-                hipLaunchKernelGGL((snotch_tiled_kernel<0>), dim3((unsigned)n_fm), dim3(kSegThreads), 0, stream, cur, buf_cap, (int)n_mid, list_fm,
-                                   sn_prm, sn_state, (double *)nullptr, direct ? out : (double2 *)nullptr, out_stride, (const EpiParam *)epi);
-        }
-        if (n_lim)      // detector limiter: lim_pre_gain 0.4, then its own wcpAGC (fmd.c:179-184)
-            hipLaunchKernelGGL(agc_form == 1 ? wcpagc_seq_kernel : wcpagc_kernel, dim3((unsigned)n_lim), dim3(64), 0, stream, cur, buf_cap,
-                               (int)n_mid, list_lim, lim_prm, lim_state, 0.4);
     }
-    if (side) QH_HIP(hipStreamWaitEvent(stream, ev_join, 0));
-    if (n_snb[1]) snb_inplace(list_snb[1], n_snb[1]);       // xbpsnbain / xbpsnbaout at position 1 (RXA.c:576-577)
-    if (n_snb[0] || n_snb[1]) cur_snb ^= 1;
-    if (n_snba) {                                           // xsnba, RXA.c:578
-        if (snba_tune_dirty) {
-            QH_HIP(hipMemcpyAsync(snba_tune, snba_tune_h.data(), snba_tune_h.size() * sizeof(SnbaTune), hipMemcpyHostToDevice, stream));
-            QH_HIP(hipStreamSynchronize(stream));
-            snba_tune_dirty = false;
-        }
-        hipLaunchKernelGGL(snba_kernel, dim3((unsigned)n_snba), dim3(64), 0, stream, cur, buf_cap, nblk, dsp_size, list_snba, snba_prm,
-                           snba_hin, snba_hout, snba_state, snba_idx, snba_scratch, (const SnbaTune *)snba_tune);
+    {   // de-emphasis: real taps on a real signal, two channels per tile
+        if (fmdc_src.a) band_fmdc = &fmdc_src;
+        run_band(cur, buf_cap, other, buf_cap, nullptr, n_mid, mask_de, 0, hist_de, cur_de, k.P, list_fm, n_fm, false, false, 0, nullptr, 0,
+                 pair ? pairs_fm : nullptr, np_fm);
+        band_fmdc = nullptr;
     }
-    // xanf, xanr, xbandpass(bp1) at position 0, xwcpagc, then the same three at position 1 (RXA.c:579-586).  The two bp1
-    // launches work on disjoint channel rows of one ping-pong history pair, so the pair flips once for both.
-    auto lms_on = [&](int k, double2 *b) {
-        for (int f = 0; f < 2; f++)
-            if (n_lms[f][k]) hipLaunchKernelGGL(lms_kernel, dim3((unsigned)n_lms[f][k]), dim3(64), 0, stream, b, buf_cap, (int)n_mid,
-                                                list_lms[f][k], lms_prm[f], lms_state[f]);
-        if (n_emnr[k])          // xemnr follows xanf and xanr at either position (RXA.c:581,585)
-            hipLaunchKernelGGL(emnr_kernel, dim3((unsigned)n_emnr[k]), dim3(NT), (size_t)emnr_lds_bytes(), stream, b, buf_cap, nblk, list_emnr[k],
-                               emnr_prm, emnr_chan, emnr_scal, emnr_state, emnr_window, tw4096, emnr_GG, emnr_GGS, emnr_zeta, emnr_zeta_true);
-    };
-    auto bp1_at = [&](int ps) {
-        int hc = cur_bp1;
-        if (n_bp1p[ps] && !direct) run_band(cur, buf_cap, other, buf_cap, nullptr, n_mid, mask_bp1, kBandNfftMax, hist_bp1, hc, P, list_bp1p[ps], n_bp1p[ps]);
-    };
-    lms_on(0, cur);
-    bp1_at(0);
-    // xwcpagc modes 1-4 (sequential per channel); mode 0 rides in the output matrix below unless a position-1 stage follows
+    run_band(other, buf_cap, cur, buf_cap, nullptr, n_mid, mask_aud, 0, hist_aud, cur_aud, k.P, list_fm, n_fm);   // audio filter
     tick(1);
-    if (n_agc_cur || n_agc_other) {
-        // Long calls: the level detector in time tiles, everything around it lane-parallel (qh_agc_tiled.hpp).  Short calls (the drop-in's
-        // blocks), a channel whose attack window moved in mid-stream, and the diagnostic forms: one wavefront per channel.
-        bool tiled = (agc_form == 0 || agc_form == 3) && n_mid >= kAgcTiledMin;      // (3: diagnostics, the tiles' check counts and repairs nothing)
-        int a_max = 0;
-        for (int ch = 0; ch < nch && tiled; ch++) {
-            ChanCfg &c = cfg[(size_t)ch];
-            if (!c.agc_on() || c.agc_stale) continue;
-            a_max = c.agc_abuf > a_max ? c.agc_abuf : a_max;
-        }
-        // the tiles take the channels at the head of each list, the stepping kernel the ones behind them (all of them in a short call)
-        const int nt_cur = tiled ? n_agc_cur - n_agc_cur_stale : 0, nt_other = tiled ? n_agc_other - n_agc_other_stale : 0;
-        if (nt_cur + nt_other == 0) tiled = false;
-        agc_last_tiled = nt_cur + nt_other;
-        for (ChanCfg &c : cfg) if (c.agc_on()) c.agc_ran = true;
-        // the reference's full ring (RB_SIZE entries): this call's last inputs go in where xwcpagc writes them; a channel whose attack
-        // window moved since its last call first takes its 2048-entry ring again from it (the entries the longer window jumped over)
-        if (!agc_lring) {
-            QH_HIP(hipStreamSynchronize(stream));
-            drop_graphs(); epoch++;
-            QH_HIP(dev_alloc(&agc_lring, (size_t)nch * kAgcLongRing));
-            QH_HIP(dev_alloc(&agc_labs, (size_t)nch * kAgcLongRing));
-            QH_HIP(dev_alloc(&agc_lout, (size_t)nch));
-            QH_HIP(dev_alloc(&agc_rewin_list, (size_t)nch));
-            QH_HIP(hipMemsetAsync(agc_lring, 0, (size_t)nch * kAgcLongRing * sizeof(double2), stream));
-            QH_HIP(hipMemsetAsync(agc_labs, 0, (size_t)nch * kAgcLongRing * sizeof(double), stream));
-            QH_HIP(hipMemsetAsync(agc_lout, 0xff, (size_t)nch * sizeof(int), stream));          // out_index = -1 (calc_wcpagc, wcpAGC.c:34)
-            dev_bytes += (long long)nch * kAgcLongRing * 24;
-        }
-        {
-            std::vector<int> rw;
-            for (int ch = 0; ch < nch; ch++) {
-                ChanCfg &c = cfg[(size_t)ch];
-                if (c.agc_on() && c.agc_rewindow) rw.push_back(ch);
-                if (c.agc_on()) c.agc_rewindow = false;
-            }
-            if (!rw.empty()) {
-                QH_HIP(hipMemcpyAsync(agc_rewin_list, rw.data(), rw.size() * sizeof(int), hipMemcpyHostToDevice, stream));
-                QH_HIP(hipStreamSynchronize(stream));
-                hipLaunchKernelGGL(agc_rewindow_kernel, dim3((unsigned)rw.size()), dim3(256), 0, stream, (const int *)agc_rewin_list, agc_state,
-                                   (const double2 *)agc_lring, (const double *)agc_labs, (const int *)agc_lout);
-            }
-        }
-        {
-            const long long span = n_mid < kAgcLongRing ? n_mid : kAgcLongRing;
-            const unsigned gx = (unsigned)((span + 255) / 256 < 120 ? (span + 255) / 256 : 120);
-            auto mirror = [&](const double2 *b, const int *lst, int cnt) {
-                if (!cnt) return;
-                hipLaunchKernelGGL(agc_long_mirror_kernel, dim3(gx, (unsigned)cnt), dim3(256), 0, stream, b, buf_cap, (int)n_mid, lst, (const AgcParam *)agc_prm,
-                                   agc_lring, agc_labs, (const int *)agc_lout);
-                hipLaunchKernelGGL(agc_long_advance_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, stream, (int)n_mid, lst, cnt, agc_lout);
-            };
-            mirror(cur, list_agc_cur, n_agc_cur);
-            mirror(other, list_agc_other, n_agc_other);
-        }
-        // ... and when every channel has the AGC as its last stage (nothing at position 1, no meters, squelch or audio frames), the gain
-        // multiply applies the output matrix and writes the caller's rows: the output pass goes
-        bool no_p1 = !n_bp1p[1] && !n_fix[0] && !n_fix[1] && !n_emnr[1] && !n_emnr[2] && !n_amsq && !meters_on && !eg.kind;
-        for (int f = 0; f < 2; f++) for (int k = 1; k < 3; k++) no_p1 = no_p1 && !n_lms[f][k];
-        agc_direct = tiled && no_p1 && nt_cur == n_plain && nt_other == n_bp1;
-        if (tiled) {
-            const int nl = nt_cur > nt_other ? nt_cur : nt_other;
-            const int ntile = (int)((n_mid + kAgcTile - 1) / kAgcTile), hp = (a_max + 15) & ~15;
-            // tiles short enough for one to two wavefronts of 64 tiles per SIMD
-            int L = 256;
-            while (L < 16384 && (long long)nl * n_mid / (64LL * 2 * L) >= 1024) L *= 2;
-            if (const char *e = getenv("QH_AGC_TILE")) { const int v = atoi(e); if (v > 0) L = (v + 63) / 64 * 64; }
-            const long long nt_l = (n_mid + L - 1) / L, ngroups = (nt_l + 63) / 64;
-            if (n_mid > agc_arr || ngroups * 64 > agc_ends_cap || (long long)ntile * hp > agc_halo_cap) {
-                QH_HIP(hipStreamSynchronize(stream));
-                if (side_stream) QH_HIP(hipStreamSynchronize(side_stream));
-                drop_graphs(); epoch++;
-                (void)hipFree(agc_scr); (void)hipFree(agc_ends); (void)hipFree(agc_halo); (void)hipFree(agc_tsum);
-                agc_scr = agc_ends = agc_tsum = nullptr; agc_halo = nullptr;
-                agc_arr = n_mid > agc_arr ? n_mid : agc_arr;
-                agc_ends_cap = ngroups * 64 > agc_ends_cap ? ngroups * 64 : agc_ends_cap;
-                agc_halo_cap = (long long)ntile * hp > agc_halo_cap ? (long long)ntile * hp : agc_halo_cap;
-                QH_HIP(dev_alloc(&agc_scr, (size_t)nch * 4 * (size_t)agc_arr));
-                QH_HIP(dev_alloc(&agc_ends, (size_t)nch * (size_t)agc_ends_cap * kAgcEndsW * 2));        // boundary states, then end states
-                QH_HIP(dev_alloc(&agc_halo, (size_t)nch * (size_t)agc_halo_cap));
-                QH_HIP(dev_alloc(&agc_tsum, (size_t)nch * (size_t)((agc_arr + kAgcTile - 1) / kAgcTile) * 2));
-                if (!agc_fin) {
-                    QH_HIP(dev_alloc(&agc_fin, (size_t)nch * 8));
-                    QH_HIP(dev_alloc(&agc_tail, (size_t)nch * kAgcRing));
-                    QH_HIP(dev_alloc(&agc_nfixed, (size_t)2));
-                    QH_HIP(hipMemsetAsync(agc_nfixed, 0, 2 * sizeof(int), stream));
-                    QH_HIP(dev_alloc(&agc_sege, (size_t)2 * nch * kAgcSegs * 8));        // two copies: a repair round reads one and writes the other
-                }
-            }
-            static bool agc_attr = false;
-            if (!agc_attr) {        // attack windows of up to kAgcRing samples: more dynamic LDS than the default limit
-                QH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(agc_prep_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           3 * (kAgcRing + kAgcTile) * (int)sizeof(double)));
-                QH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(agc_apply_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (kAgcRing + kAgcTile) * (int)sizeof(double2)));
-                agc_attr = true;
-            }
-            auto run = [&](double2 *b, const int *lst, int cnt) {
-                if (!cnt) return;
-                const int n = (int)n_mid;
-                int G = 256 / cnt;
-                while (G > 1 && n_mid / (64LL * kSegWaves * G) < 8) G--;
-                G = G < 1 ? 1 : G > kSegMaxGroups ? kSegMaxGroups : G;
-                const size_t lds_prep = (size_t)3 * (((size_t)a_max + 63) / 64 * 64 + kAgcTile) * sizeof(double);
-                const size_t lds_apply = ((size_t)a_max + kAgcTile) * sizeof(double2);
-                hipLaunchKernelGGL(agc_prep_kernel, dim3((unsigned)ntile, (unsigned)cnt), dim3(256), lds_prep, stream, (const double2 *)b, buf_cap, n,
-                                   lst, (const AgcParam *)agc_prm, (const AgcState *)agc_state, agc_scr, agc_arr, agc_halo, hp, 1.0, agc_tsum);
-                hipLaunchKernelGGL(agc_avg_tiled_kernel, dim3((unsigned)cnt, (unsigned)G), dim3(kSegThreads), 0, stream, (const double2 *)b,
-                                   buf_cap, n, lst, (const AgcParam *)agc_prm, (const AgcState *)agc_state, agc_scr, agc_arr, (const double *)agc_tsum,
-                                   ntile, 1.0);
-                double *bnd = agc_ends, *end = agc_ends + (size_t)nch * (size_t)agc_ends_cap * kAgcEndsW;
-                // the boundary pass over K super-segments per channel at once (a multiple of the tile length each)
-                int K = 1;
-                while (K < kAgcSegs && (long long)cnt * K < 4096 && n_mid / (2 * K) >= 8 * L && n_mid / (2 * K) >= 32768) K *= 2;
-                if (const char *e = getenv("QH_AGC_SEGS")) { const int v = atoi(e); if (v >= 1 && v <= kAgcSegs) K = v; }
-                const int seg = (int)(((n_mid + K - 1) / K + L - 1) / L) * L;
-                // No warm-up ahead of a segment by default: every segment starts from the state the call began in, and the repair rounds
-                // walk each one again from the end of the one before it until the two walks meet (agc_bounds_round_kernel) -- the work a
-                // warm-up long enough for every channel (400 attack windows on the bench input) spends on all of them, spent only where
-                // and for as long as the walks differ.
-                int wmul = 0, rounds = 3;
-                if (const char *e = getenv("QH_AGC_WARM")) { const int v = atoi(e); if (v >= 0) wmul = v; }
-                if (const char *e = getenv("QH_AGC_ROUNDS")) { const int v = atoi(e); if (v >= 0 && v <= 16) rounds = v; }
-                const int Wm = ((wmul * a_max + L - 1) / L) * L;
-                double *sg[2] = { agc_sege, agc_sege + (size_t)nch * kAgcSegs * 8 };
-                hipLaunchKernelGGL(agc_bounds_kernel, dim3((unsigned)cnt, (unsigned)K), dim3(64), 0, stream, n, lst, (const AgcParam *)agc_prm,
-                                   (const AgcState *)agc_state, (const double *)agc_scr, agc_arr, bnd, agc_ends_cap * kAgcEndsW, L, seg, Wm, sg[0]);
-                if (K > 1) {
-                    int at = 0;
-                    for (int r = 0; r < rounds; r++, at ^= 1)
-                        hipLaunchKernelGGL(agc_bounds_round_kernel, dim3((unsigned)cnt, (unsigned)K), dim3(64), 0, stream, n, lst,
-                                           (const AgcParam *)agc_prm, (const double *)agc_scr, agc_arr, bnd, agc_ends_cap * kAgcEndsW, L, seg, K,
-                                           (const double *)sg[at], sg[at ^ 1], agc_nfixed + 1);
-                    hipLaunchKernelGGL(agc_bounds_fix_kernel, dim3((unsigned)cnt), dim3(64), 0, stream, n, lst, (const AgcParam *)agc_prm,
-                                       (const double *)agc_scr, agc_arr, bnd, agc_ends_cap * kAgcEndsW, L, seg, K, sg[at], agc_nfixed + 1);
-                }
-                hipLaunchKernelGGL(agc_lanes_kernel, dim3((unsigned)ngroups, (unsigned)cnt), dim3(64), 0, stream, n, lst, (const AgcParam *)agc_prm,
-                                   agc_scr, agc_arr, (const double *)bnd, agc_ends_cap * kAgcEndsW, end, agc_ends_cap * kAgcEndsW, L);
-                hipLaunchKernelGGL(agc_verify_kernel, dim3((unsigned)cnt), dim3(64), 0, stream, n, lst, (const AgcParam *)agc_prm, agc_scr, agc_arr,
-                                   (const double *)bnd, agc_ends_cap * kAgcEndsW, end, agc_ends_cap * kAgcEndsW, L, agc_fin, agc_nfixed, agc_form == 3 ? 1 : 0);
-                hipLaunchKernelGGL(agc_tail_kernel, dim3((unsigned)cnt), dim3(256), 0, stream, (const double2 *)b, buf_cap, n, lst,
-                                   (const AgcParam *)agc_prm, agc_tail, 1.0);
-                hipLaunchKernelGGL(agc_apply_kernel, dim3((unsigned)ntile, (unsigned)cnt), dim3(256), lds_apply, stream, b, buf_cap, n, lst,
-                                   (const AgcParam *)agc_prm, (const double *)agc_scr, agc_arr, (const double2 *)agc_halo, hp, 1.0,
-                                   agc_direct ? out : (double2 *)nullptr, out_stride, (const EpiParam *)epi);
-                hipLaunchKernelGGL(agc_finish_kernel, dim3((unsigned)cnt), dim3(256), 0, stream, n, lst, (const AgcParam *)agc_prm, agc_state,
-                                   (const double *)agc_scr, agc_arr, (const double2 *)agc_tail, (const double *)agc_fin);
-            };
-            run(cur, list_agc_cur, nt_cur);
-            run(other, list_agc_other, nt_other);
-        }
-        if (const int ns = n_agc_cur - nt_cur)
-            hipLaunchKernelGGL(agc_form == 1 ? wcpagc_seq_kernel : wcpagc_kernel, dim3((unsigned)ns), dim3(64), 0, stream, cur, buf_cap, (int)n_mid,
-                               (const int *)(list_agc_cur + nt_cur), agc_prm, agc_state, 1.0);
-        if (const int ns = n_agc_other - nt_other)
-            hipLaunchKernelGGL(agc_form == 1 ? wcpagc_seq_kernel : wcpagc_kernel, dim3((unsigned)ns), dim3(64), 0, stream, other, buf_cap, (int)n_mid,
-                               (const int *)(list_agc_other + nt_other), agc_prm, agc_state, 1.0);
+    {
+        const int G = seg_groups(n_fm, n_mid);
+        if (G > 1) {
+            hipLaunchKernelGGL((snotch_tiled_kernel<1>), dim3((unsigned)n_fm, (unsigned)G), dim3(kSegThreads), 0, stream, cur, buf_cap, (int)n_mid,
+                               list_fm, sn_prm, sn_state, seg_sum[2]);
+            hipLaunchKernelGGL((snotch_tiled_kernel<2>), dim3((unsigned)n_fm, (unsigned)G), dim3(kSegThreads), 0, stream, cur, buf_cap, (int)n_mid,
+                               list_fm, sn_prm, sn_state, seg_sum[2], k.direct ? k.out : (double2 *)nullptr, k.out_stride, (const EpiParam *)epi, sn_next);
+            hipLaunchKernelGGL(commit_snotch_kernel, dim3((unsigned)((n_fm + 255) / 256)), dim3(256), 0, stream, sn_state, (const SnotchState *)sn_next, list_fm, n_fm,
+                               (const SnotchParam *)sn_prm);
+        } else
+            hipLaunchKernelGGL((snotch_tiled_kernel<0>), dim3((unsigned)n_fm), dim3(kSegThreads), 0, stream, cur, buf_cap, (int)n_mid, list_fm,
+                               sn_prm, sn_state, (double *)nullptr, k.direct ? k.out : (double2 *)nullptr, k.out_stride, (const EpiParam *)epi);
+    }
+    if (n_lim)      // detector limiter: lim_pre_gain 0.4, then its own wcpAGC (fmd.c:179-184)
+        hipLaunchKernelGGL(agc_form == 1 ? wcpagc_seq_kernel : wcpagc_kernel, dim3((unsigned)n_lim), dim3(64), 0, stream, cur, buf_cap,
+                           (int)n_mid, list_lim, lim_prm, lim_state, 0.4);
+    return QH_OK;
+}
+
+// xsnba, with the tuning the setters left uploaded first
+int Engine::run_snba(const ChainCall &k)
+{
+    if (!n_snba) return QH_OK;
+    if (snba_tune_dirty) {
+        QH_HIP(hipMemcpyAsync(snba_tune, snba_tune_h.data(), snba_tune_h.size() * sizeof(SnbaTune), hipMemcpyHostToDevice, stream));
+        QH_HIP(hipStreamSynchronize(stream));
+        snba_tune_dirty = false;
+    }
+    hipLaunchKernelGGL(snba_kernel, dim3((unsigned)n_snba), dim3(64), 0, stream, k.cur, buf_cap, k.nblk, dsp_size, list_snba, snba_prm,
+                       snba_hin, snba_hout, snba_state, snba_idx, snba_scratch, (const SnbaTune *)snba_tune);
+    return QH_OK;
+}
+
+// xanf and xanr of list entry pos ([f][0] position 0; [f][1 + b] position 1 with the data in cur / other), on the rows of b, and
+// xemnr behind them (RXA.c:581,585)
+void Engine::lms_at(const ChainCall &k, int pos, double2 *b)
+{
+    for (int f = 0; f < 2; f++)
+        if (n_lms[f][pos]) hipLaunchKernelGGL(lms_kernel, dim3((unsigned)n_lms[f][pos]), dim3(64), 0, stream, b, buf_cap, (int)k.n_mid,
+                                              list_lms[f][pos], lms_prm[f], lms_state[f]);
+    if (n_emnr[pos])
+        hipLaunchKernelGGL(emnr_kernel, dim3((unsigned)n_emnr[pos]), dim3(NT), (size_t)emnr_lds_bytes(), stream, b, buf_cap, k.nblk, list_emnr[pos],
+                           emnr_prm, emnr_chan, emnr_scal, emnr_state, emnr_window, tw4096, emnr_GG, emnr_GGS, emnr_zeta, emnr_zeta_true);
+}
+
+// xbandpass (bp1) at position pos, from the rows of cur to those of other -- unless bp1 ended the AM / SAM channels' chain already
+void Engine::bp1_at(const ChainCall &k, int pos)
+{
+    int hc = cur_bp1;
+    if (n_bp1p[pos] && !k.direct)
+        run_band(k.cur, buf_cap, k.other, buf_cap, nullptr, k.n_mid, mask_bp1, kBandNfftMax, hist_bp1, hc, k.P, list_bp1p[pos], n_bp1p[pos]);
+}
+
+// xwcpagc modes 1-4.  Long calls: the level detector in time tiles, everything around it lane-parallel (qh_agc_tiled.hpp).  Short
+// calls (the drop-in's blocks), a channel whose attack window moved in mid-stream, and the diagnostic forms: one wavefront per channel.
+int Engine::run_agc(ChainCall &k)
+{
+    const long long n_mid = k.n_mid;
+    double2 *cur = k.cur, *other = k.other;
+    bool tiled = (agc_form == 0 || agc_form == 3) && n_mid >= kAgcTiledMin;      // (3: diagnostics, the tiles' check counts and repairs nothing)
+    int a_max = 0;
+    for (int ch = 0; ch < nch && tiled; ch++) {
+        ChanCfg &c = cfg[(size_t)ch];
+        if (!c.agc_on() || c.agc_stale) continue;
+        a_max = c.agc_abuf > a_max ? c.agc_abuf : a_max;
+    }
+    // the tiles take the channels at the head of each list, the stepping kernel the ones behind them (all of them in a short call)
+    const int nt_cur = tiled ? n_agc_cur - n_agc_cur_stale : 0, nt_other = tiled ? n_agc_other - n_agc_other_stale : 0;
+    if (nt_cur + nt_other == 0) tiled = false;
+    agc_last_tiled = nt_cur + nt_other;
+    for (ChanCfg &c : cfg) if (c.agc_on()) c.agc_ran = true;
+    // the reference's full ring (RB_SIZE entries): this call's last inputs go in where xwcpagc writes them; a channel whose attack
+    // window moved since its last call first takes its 2048-entry ring again from it (the entries the longer window jumped over)
+    if (!agc_lring) {
+        if (int rc = quiesce()) return rc;
+        if (int rc = realloc_dev(agc_lring, 0, (long long)nch * kAgcLongRing)) return rc;
+        if (int rc = realloc_dev(agc_labs, 0, (long long)nch * kAgcLongRing)) return rc;
+        if (int rc = realloc_dev(agc_lout, 0, nch)) return rc;
+        if (int rc = realloc_dev(agc_rewin_list, 0, nch)) return rc;
+        QH_HIP(hipMemsetAsync(agc_lring, 0, (size_t)nch * kAgcLongRing * sizeof(double2), stream));
+        QH_HIP(hipMemsetAsync(agc_labs, 0, (size_t)nch * kAgcLongRing * sizeof(double), stream));
+        QH_HIP(hipMemsetAsync(agc_lout, 0xff, (size_t)nch * sizeof(int), stream));          // out_index = -1 (calc_wcpagc, wcpAGC.c:34)
     }
     {
-        long long per = (n_mid + NT - 1) / NT;
-        const unsigned gx = (unsigned)(per < 1024 ? per : 1024);
-        for (int b = 0; b < 2; b++)
-            if (n_fix[b]) hipLaunchKernelGGL(scale_kernel, dim3(gx, (unsigned)n_fix[b]), dim3(NT), 0, stream, b ? other : cur, buf_cap,
-                                             (int)n_mid, list_fix[b], fix_gain);
+        std::vector<int> rw;
+        for (int ch = 0; ch < nch; ch++) {
+            ChanCfg &c = cfg[(size_t)ch];
+            if (c.agc_on() && c.agc_rewindow) rw.push_back(ch);
+            if (c.agc_on()) c.agc_rewindow = false;
+        }
+        if (!rw.empty()) {
+            QH_HIP(hipMemcpyAsync(agc_rewin_list, rw.data(), rw.size() * sizeof(int), hipMemcpyHostToDevice, stream));
+            QH_HIP(hipStreamSynchronize(stream));
+            hipLaunchKernelGGL(agc_rewindow_kernel, dim3((unsigned)rw.size()), dim3(256), 0, stream, (const int *)agc_rewin_list, agc_state,
+                               (const double2 *)agc_lring, (const double *)agc_labs, (const int *)agc_lout);
+        }
     }
-    lms_on(1, cur);
-    lms_on(2, other);
-    bp1_at(1);
+    {
+        const long long span = n_mid < kAgcLongRing ? n_mid : kAgcLongRing;
+        const unsigned gx = (unsigned)((span + 255) / 256 < 120 ? (span + 255) / 256 : 120);
+        auto mirror = [&](const double2 *b, const int *lst, int cnt) {
+            if (!cnt) return;
+            hipLaunchKernelGGL(agc_long_mirror_kernel, dim3(gx, (unsigned)cnt), dim3(256), 0, stream, b, buf_cap, (int)n_mid, lst, (const AgcParam *)agc_prm,
+                               agc_lring, agc_labs, (const int *)agc_lout);
+            hipLaunchKernelGGL(agc_long_advance_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, stream, (int)n_mid, lst, cnt, agc_lout);
+        };
+        mirror(cur, list_agc_cur, n_agc_cur);
+        mirror(other, list_agc_other, n_agc_other);
+    }
+    // ... and when every channel has the AGC as its last stage (nothing at position 1, no meters, squelch or audio frames), the gain
+    // multiply applies the output matrix and writes the caller's rows: the output pass goes
+    bool no_p1 = !n_bp1p[1] && !n_fix[0] && !n_fix[1] && !n_emnr[1] && !n_emnr[2] && !n_amsq && !meters_on && !eg.kind;
+    for (int f = 0; f < 2; f++) for (int p = 1; p < 3; p++) no_p1 = no_p1 && !n_lms[f][p];
+    k.agc_direct = tiled && no_p1 && nt_cur == n_plain && nt_other == n_bp1;
+    if (tiled) {
+        const int nl = nt_cur > nt_other ? nt_cur : nt_other;
+        const int ntile = (int)((n_mid + kAgcTile - 1) / kAgcTile), hp = (a_max + 15) & ~15;
+        // tiles short enough for one to two wavefronts of 64 tiles per SIMD
+        int L = 256;
+        while (L < 16384 && (long long)nl * n_mid / (64LL * 2 * L) >= 1024) L *= 2;
+        const long long nt_l = (n_mid + L - 1) / L, ngroups = (nt_l + 63) / 64;
+        if (n_mid > agc_arr || ngroups * 64 > agc_ends_cap || (long long)ntile * hp > agc_halo_cap) {
+            if (int rc = quiesce()) return rc;
+            const long long arr = std::max(n_mid, agc_arr), ends = std::max(ngroups * 64, agc_ends_cap), halo = std::max((long long)ntile * hp, agc_halo_cap);
+            auto tiles = [](long long n) { return (n + kAgcTile - 1) / kAgcTile; };
+            if (int rc = realloc_dev(agc_scr, nch * 4 * agc_arr, nch * 4 * arr)) return rc;
+            if (int rc = realloc_dev(agc_ends, nch * agc_ends_cap * kAgcEndsW * 2, nch * ends * kAgcEndsW * 2)) return rc;    // boundary states, then end states
+            if (int rc = realloc_dev(agc_halo, nch * agc_halo_cap, nch * halo)) return rc;
+            if (int rc = realloc_dev(agc_tsum, nch * tiles(agc_arr) * 2, nch * tiles(arr) * 2)) return rc;
+            agc_arr = arr; agc_ends_cap = ends; agc_halo_cap = halo;
+            if (!agc_fin) {
+                if (int rc = realloc_dev(agc_fin, 0, nch * 8)) return rc;
+                if (int rc = realloc_dev(agc_tail, 0, (long long)nch * kAgcRing)) return rc;
+                if (int rc = realloc_dev(agc_nfixed, 0, 2)) return rc;
+                QH_HIP(hipMemsetAsync(agc_nfixed, 0, 2 * sizeof(int), stream));
+                if (int rc = realloc_dev(agc_sege, 0, 2LL * nch * kAgcSegs * 8)) return rc;    // two copies: a repair round reads one and writes the other
+            }
+        }
+        static bool agc_attr = false;
+        if (!agc_attr) {        // attack windows of up to kAgcRing samples: more dynamic LDS than the default limit
+            QH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(agc_prep_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       3 * (kAgcRing + kAgcTile) * (int)sizeof(double)));
+            QH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(agc_apply_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       (kAgcRing + kAgcTile) * (int)sizeof(double2)));
+            agc_attr = true;
+        }
+        auto run = [&](double2 *b, const int *lst, int cnt) {
+            if (!cnt) return;
+            const int n = (int)n_mid;
+            const int G = seg_groups(cnt, n_mid);
+            const size_t lds_prep = (size_t)3 * (((size_t)a_max + 63) / 64 * 64 + kAgcTile) * sizeof(double);
+            const size_t lds_apply = ((size_t)a_max + kAgcTile) * sizeof(double2);
+            hipLaunchKernelGGL(agc_prep_kernel, dim3((unsigned)ntile, (unsigned)cnt), dim3(256), lds_prep, stream, (const double2 *)b, buf_cap, n,
+                               lst, (const AgcParam *)agc_prm, (const AgcState *)agc_state, agc_scr, agc_arr, agc_halo, hp, 1.0, agc_tsum);
+            hipLaunchKernelGGL(agc_avg_tiled_kernel, dim3((unsigned)cnt, (unsigned)G), dim3(kSegThreads), 0, stream, (const double2 *)b,
+                               buf_cap, n, lst, (const AgcParam *)agc_prm, (const AgcState *)agc_state, agc_scr, agc_arr, (const double *)agc_tsum,
+                               ntile, 1.0);
+            double *bnd = agc_ends, *end = agc_ends + (size_t)nch * (size_t)agc_ends_cap * kAgcEndsW;
+            // the boundary pass over K super-segments per channel at once (a multiple of the tile length each)
+            int K = 1;
+            while (K < kAgcSegs && (long long)cnt * K < 4096 && n_mid / (2 * K) >= 8 * L && n_mid / (2 * K) >= 32768) K *= 2;
+            if (const char *e = getenv("QH_AGC_SEGS")) { const int v = atoi(e); if (v >= 1 && v <= kAgcSegs) K = v; }
+            const int seg = (int)(((n_mid + K - 1) / K + L - 1) / L) * L;
+            // No warm-up ahead of a segment by default: every segment starts from the state the call began in, and the repair rounds
+            // walk each one again from the end of the one before it until the two walks meet (agc_bounds_round_kernel) -- the work a
+            // warm-up long enough for every channel (400 attack windows on the bench input) spends on all of them, spent only where
+            // and for as long as the walks differ.
+            int wmul = 0, rounds = 3;
+            if (const char *e = getenv("QH_AGC_WARM")) { const int v = atoi(e); if (v >= 0) wmul = v; }
+            if (const char *e = getenv("QH_AGC_ROUNDS")) { const int v = atoi(e); if (v >= 0 && v <= 16) rounds = v; }
+            const int Wm = ((wmul * a_max + L - 1) / L) * L;
+            double *sg[2] = { agc_sege, agc_sege + (size_t)nch * kAgcSegs * 8 };
+            hipLaunchKernelGGL(agc_bounds_kernel, dim3((unsigned)cnt, (unsigned)K), dim3(64), 0, stream, n, lst, (const AgcParam *)agc_prm,
+                               (const AgcState *)agc_state, (const double *)agc_scr, agc_arr, bnd, agc_ends_cap * kAgcEndsW, L, seg, Wm, sg[0]);
+            if (K > 1) {
+                int at = 0;
+                for (int r = 0; r < rounds; r++, at ^= 1)
+                    hipLaunchKernelGGL(agc_bounds_round_kernel, dim3((unsigned)cnt, (unsigned)K), dim3(64), 0, stream, n, lst,
+                                       (const AgcParam *)agc_prm, (const double *)agc_scr, agc_arr, bnd, agc_ends_cap * kAgcEndsW, L, seg, K,
+                                       (const double *)sg[at], sg[at ^ 1], agc_nfixed + 1);
+                hipLaunchKernelGGL(agc_bounds_fix_kernel, dim3((unsigned)cnt), dim3(64), 0, stream, n, lst, (const AgcParam *)agc_prm,
+                                   (const double *)agc_scr, agc_arr, bnd, agc_ends_cap * kAgcEndsW, L, seg, K, sg[at], agc_nfixed + 1);
+            }
+            hipLaunchKernelGGL(agc_lanes_kernel, dim3((unsigned)ngroups, (unsigned)cnt), dim3(64), 0, stream, n, lst, (const AgcParam *)agc_prm,
+                               agc_scr, agc_arr, (const double *)bnd, agc_ends_cap * kAgcEndsW, end, agc_ends_cap * kAgcEndsW, L);
+            hipLaunchKernelGGL(agc_verify_kernel, dim3((unsigned)cnt), dim3(64), 0, stream, n, lst, (const AgcParam *)agc_prm, agc_scr, agc_arr,
+                               (const double *)bnd, agc_ends_cap * kAgcEndsW, end, agc_ends_cap * kAgcEndsW, L, agc_fin, agc_nfixed, agc_form == 3 ? 1 : 0);
+            hipLaunchKernelGGL(agc_tail_kernel, dim3((unsigned)cnt), dim3(256), 0, stream, (const double2 *)b, buf_cap, n, lst,
+                               (const AgcParam *)agc_prm, agc_tail, 1.0);
+            hipLaunchKernelGGL(agc_apply_kernel, dim3((unsigned)ntile, (unsigned)cnt), dim3(256), lds_apply, stream, b, buf_cap, n, lst,
+                               (const AgcParam *)agc_prm, (const double *)agc_scr, agc_arr, (const double2 *)agc_halo, hp, 1.0,
+                               k.agc_direct ? k.out : (double2 *)nullptr, k.out_stride, (const EpiParam *)epi);
+            hipLaunchKernelGGL(agc_finish_kernel, dim3((unsigned)cnt), dim3(256), 0, stream, n, lst, (const AgcParam *)agc_prm, agc_state,
+                               (const double *)agc_scr, agc_arr, (const double2 *)agc_tail, (const double *)agc_fin);
+        };
+        run(cur, list_agc_cur, nt_cur);
+        run(other, list_agc_other, nt_other);
+    }
+    if (const int ns = n_agc_cur - nt_cur)
+        hipLaunchKernelGGL(agc_form == 1 ? wcpagc_seq_kernel : wcpagc_kernel, dim3((unsigned)ns), dim3(64), 0, stream, cur, buf_cap, (int)n_mid,
+                           (const int *)(list_agc_cur + nt_cur), agc_prm, agc_state, 1.0);
+    if (const int ns = n_agc_other - nt_other)
+        hipLaunchKernelGGL(agc_form == 1 ? wcpagc_seq_kernel : wcpagc_kernel, dim3((unsigned)ns), dim3(64), 0, stream, other, buf_cap, (int)n_mid,
+                           (const int *)(list_agc_other + nt_other), agc_prm, agc_state, 1.0);
+    return QH_OK;
+}
+
+// xwcpagc mode 0 where a position-1 stage follows it, xanf / xanr / xemnr / bp1 at position 1, the agc meter, then xwcpagc mode 0 +
+// xpanel in the output pass, xamsq and the audio frames
+void Engine::run_output(const ChainCall &k)
+{
+    const long long n_mid = k.n_mid, per = (n_mid + NT - 1) / NT;
+    const unsigned gx = (unsigned)(per < 1024 ? per : 1024);
+    for (int b = 0; b < 2; b++)
+        if (n_fix[b]) hipLaunchKernelGGL(scale_kernel, dim3(gx, (unsigned)n_fix[b]), dim3(NT), 0, stream, b ? k.other : k.cur, buf_cap,
+                                         (int)n_mid, list_fix[b], fix_gain);
+    lms_at(k, 1, k.cur);
+    lms_at(k, 2, k.other);
+    bp1_at(k, 1);
     if (n_bp1) cur_bp1 ^= 1;
     if (meters_on) {    // agcmeter sits after xwcpagc (RXA.c:589); mode 0's gain multiply is applied below, so its
                         // level reading is taken on the fixed-gain input times g^2 (m_g2)
-        if (n_plain) hipLaunchKernelGGL(meter_kernel, dim3((unsigned)n_plain), dim3(64), 0, stream, cur, buf_cap, nblk, dsp_size,
+        if (n_plain) hipLaunchKernelGGL(meter_kernel, dim3((unsigned)n_plain), dim3(64), 0, stream, k.cur, buf_cap, k.nblk, dsp_size,
                                         m_agc, m_prm, list_plain, (const double *)m_g2);
-        if (n_bp1) hipLaunchKernelGGL(meter_kernel, dim3((unsigned)n_bp1), dim3(64), 0, stream, other, buf_cap, nblk, dsp_size,
+        if (n_bp1) hipLaunchKernelGGL(meter_kernel, dim3((unsigned)n_bp1), dim3(64), 0, stream, k.other, buf_cap, k.nblk, dsp_size,
                                       m_agc, m_prm, list_bp1, (const double *)m_g2);
     }
     tick(2);
-    // xwcpagc mode 0 + xpanel
-    long long per = (n_mid + NT - 1) / NT;
-    const unsigned gx = (unsigned)(per < 1024 ? per : 1024);
-    if (direct || agc_direct) {
-        // every channel's last stage has written the caller's buffer
-    } else if (eg_fused) {
-        if (n_plain) hipLaunchKernelGGL((pointwise_kernel<double, false, true>), dim3(gx, (unsigned)n_plain), dim3(NT), 0, stream, cur,
-                                        buf_cap, out, out_stride, (int)n_mid, (const unsigned long long *)nullptr,
-                                        (const unsigned long long *)nullptr, epi, list_plain, eg);
-        if (n_bp1) hipLaunchKernelGGL((pointwise_kernel<double, false, true>), dim3(gx, (unsigned)n_bp1), dim3(NT), 0, stream, other,
-                                      buf_cap, out, out_stride, (int)n_mid, (const unsigned long long *)nullptr,
-                                      (const unsigned long long *)nullptr, epi, list_bp1, eg);
-    } else {
-    if (n_plain) hipLaunchKernelGGL((pointwise_kernel<double, false>), dim3(gx, (unsigned)n_plain), dim3(NT), 0, stream, cur,
-                                    buf_cap, out, out_stride, (int)n_mid, (const unsigned long long *)nullptr,
-                                    (const unsigned long long *)nullptr, epi, list_plain);
-    if (n_bp1) hipLaunchKernelGGL((pointwise_kernel<double, false>), dim3(gx, (unsigned)n_bp1), dim3(NT), 0, stream, other,
-                                  buf_cap, out, out_stride, (int)n_mid, (const unsigned long long *)nullptr,
-                                  (const unsigned long long *)nullptr, epi, list_bp1);
+    // xwcpagc mode 0 + xpanel, narrowed in the store when the audio frames are fused -- unless every channel's last stage has written
+    // the caller's buffer
+    if (!k.direct && !k.agc_direct) {
+        auto *pass = k.eg_fused ? &pointwise_kernel<double, false, true> : &pointwise_kernel<double, false>;
+        const EgressFmt pass_eg = k.eg_fused ? eg : EgressFmt{};
+        if (n_plain) hipLaunchKernelGGL(pass, dim3(gx, (unsigned)n_plain), dim3(NT), 0, stream, k.cur, buf_cap, k.out, k.out_stride, (int)n_mid,
+                                        (const unsigned long long *)nullptr, (const unsigned long long *)nullptr, epi, list_plain, pass_eg);
+        if (n_bp1) hipLaunchKernelGGL(pass, dim3(gx, (unsigned)n_bp1), dim3(NT), 0, stream, k.other, buf_cap, k.out, k.out_stride, (int)n_mid,
+                                      (const unsigned long long *)nullptr, (const unsigned long long *)nullptr, epi, list_bp1, pass_eg);
     }
-    if (n_amsq) hipLaunchKernelGGL(amsq_apply_kernel, dim3((unsigned)n_amsq), dim3(64), 0, stream, out, out_stride, (int)n_mid, list_amsq,
+    if (n_amsq) hipLaunchKernelGGL(amsq_apply_kernel, dim3((unsigned)n_amsq), dim3(64), 0, stream, k.out, k.out_stride, (int)n_mid, list_amsq,
                                    amsq_mag, amsq_mag_cap, amsq_prm, amsq_state, amsq_cup, amsq_cdown);       // xamsq, RXA.c:596
-    if (eg.kind && !eg_fused) pack_audio(out, out_stride, n_mid);
+    if (eg.kind && !k.eg_fused) pack_audio(k.out, k.out_stride, n_mid);
     tick(3);
-    QH_HIP(hipGetLastError());
-    return QH_OK;
 }
 
 }  // namespace qh

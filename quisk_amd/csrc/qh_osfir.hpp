@@ -114,7 +114,6 @@ template <typename T> struct OsfirArgs {
     long long amlv_cstride;
     const double *amlv_pw;              // [2][2^amlv_shift]: mtauR^(k + 1), mtauI^(k + 1)
     int amlv_shift;
-    double2 *stash;                     // osfir8s_kernel: [nch][4096] scratch for the tile that the end of the call cuts short
 };
 
 
@@ -831,174 +830,6 @@ __global__ __launch_bounds__(kOsfir8kThreads, 4) void osfir8k_kernel(OsfirArgs<d
         }
     }
 }
-
-// (-DQH_EXP_BAND8_SEQ: experiment builds, tools/ab_bench.py; QH_BAND8_FORM=seq in the environment then selects it)
-#ifdef QH_EXP_BAND8_SEQ
-// ---- D = 1 stage on 8192-point tiles, the two halves of the radix-2 split ONE AFTER THE OTHER on 256 lanes ------------------------
-// The split of osfir8k_kernel (a = x[n] + x[n + 4096] -> even bins, b = (x[n] - x[n + 4096]) W^n -> odd bins) without its second
-// lane group: one 256-lane workgroup -- the register, LDS and occupancy budget of the 4096-point kernel, four workgroups per CU --
-// runs the 4096-point transform pair of the even bins, parks A'[n] (n = j + 256 s: every lane parks and later fetches its OWN sixteen
-// values, so no fence beyond the lane's own store -> load order is needed), reads the tile's samples a second time (from L2), runs
-// the pair of the odd bins and joins: y[n] = A'[n] + W^-n B'[n], y[n + 4096] = A'[n] - W^-n B'[n].  6144 outputs per four 4096-point
-// transforms and two butterfly stages instead of 2049 per two: 0.66 of the fp64 instructions per output, HBM bytes per output 0.67.
-// A' is parked in the tile's own stretch of the output rows (positions rel 2048 .. 6143, which the tile overwrites with y at its
-// end); a tile that the call's end cuts short parks in a per-channel scratch row instead (a.stash).  Masks [even | odd], meter
-// partials and tile geometry are osfir8k_kernel's (layout 1), so the engine's band2g plumbing serves both.  Not for EGRESS (the
-// parked values would be narrowed): the two-group kernel keeps those calls.
-template <bool METER>
-__global__ __launch_bounds__(NT, 4) void osfir8s_kernel(OsfirArgs<double> a)
-{
-    using C = double2;
-    using SF = FftSplit4096<false, C>;
-    using SI = FftSplit4096<true, C>;
-    constexpr int N = 8192, P = kOsfir8kP, L = kOsfir8kLout;
-    static_assert(NT / 64 * kMeterLdsDoublesPerWave * 8 <= SF::kLdsBytes, "meter blocks overlay the exchange image");
-    extern __shared__ __align__(16) unsigned char smem8s[];
-    const int j_ = threadIdx.x;
-    int tile, slot;
-    xcd_tile_map(a.ntiles, slot, tile);
-    // (the division of xcd_tile_map runs on the vector unit: said to be uniform, the tile and the channel -- and every row pointer formed
-    // from them -- live in scalar registers)
-    tile = __builtin_amdgcn_readfirstlane(tile);
-    const int ch = __builtin_amdgcn_readfirstlane(a.chan_list ? a.chan_list[slot] : slot);
-    const C *in = a.in + (long long)ch * a.in_stride;
-    const int g0_ = a.off - P + tile * L;
-    const bool interior = g0_ >= 0 && g0_ + N <= a.n_in;                  // workgroup-uniform
-    C *out = a.out + (long long)ch * a.out_stride + a.out_offset;
-    // where A' waits: the tile's own outputs rel 2048 + n (n < 4096) while all of them exist, the channel's scratch row otherwise
-    const bool whole = (long long)(tile + 1) * L <= (long long)a.n_out;
-    C *park = whole ? out + (long long)tile * L + 2048 : a.stash + (long long)ch * 4096;
-    // eight samples tile[n0 + 256 s]: plain loads inside the call's buffer, clamped history-aware ones at its ends (branch free)
-    auto load8_plain = [&](C (&v)[8], int g0, int n0) {
-        const C *p = in + g0 + n0;
-#pragma unroll
-        for (int s = 0; s < 8; s++) v[s] = p[256 * s];
-    };
-    auto load8_edge = [&](C (&v)[8], int g0, int n0) {
-        const C *hist = a.hist ? a.hist + (long long)ch * a.hist_stride : in;
-        const int hlen = a.hist ? a.hist_len : 0, last = a.n_in - 1;
-#pragma unroll
-        for (int s = 0; s < 8; s++) {
-            const int gi = g0 + n0 + 256 * s;
-            const int ii = gi > last ? last : gi, ih = gi + hlen < 0 ? 0 : gi + hlen;
-            const bool now = gi >= 0, ok = now ? gi <= last : gi + hlen >= 0;
-            // (one address from selected parts: a select between two finished pointers became a branch around every load)
-            const unsigned long long base = now ? (unsigned long long)in : (unsigned long long)hist;
-            const C w = *reinterpret_cast<const C *>(base + (unsigned long long)(unsigned)(now ? ii : ih) * sizeof(C));
-            v[s] = make_double2(ok ? w.x : 0.0, ok ? w.y : 0.0);
-        }
-    };
-
-#pragma nounroll
-    for (int g = 0; g < 2; g++) {                                       // g = 0: sums, even bins; g = 1: differences, odd bins
-        C x[16];
-        const double sgn = g ? -1.0 : 1.0;
-        // (the two phases share this code: what depends on the lane or the tile alone is formed again in each -- hoisted out of the
-        // loop, three dozen addresses and flags would be carried through both transform pairs in registers the transforms need)
-        int j = j_, g0 = g0_;
-        asm volatile("" : "+v"(j));
-        asm volatile("" : "+s"(g0));
-        // ---- the tile's samples n = j + 256 s and n + 4096, eight at a time; one straight-line copy for the tiles inside the call's
-        // buffer and one for those at its ends (a branch around every batch of loads made the register allocator park the batches in
-        // scratch memory at the joins)
-        auto gather = [&](auto load8) {
-#pragma unroll
-            for (int h = 0; h < 2; h++) {
-                // meter partials, layout 1 of meter_finish_kernel: 32 slots [wave][8] = chunks 32 + 4 s + wave (the upper samples of s < 8),
-                // then 64 slots [wave][16]: chunks 4 k + wave (the lower samples of s = 8 + k) and 64 + 4 k + wave (their upper ones)
-                double *blk = reinterpret_cast<double *>(smem8s) + (j >> 6) * kMeterLdsDoublesPerWave;
-                double2 *mdst = METER ? a.meter_in + (long long)ch * a.meter_stride + (long long)tile * (L >> 6) : nullptr;
-                C hi[8];
-                load8(hi, g0, j + 2048 * h + 4096);
-                if constexpr (METER) {
-                    if (g == 0) {
-                        if (h == 0) meter_tap<C, 8>(hi, 0, a.meter_w[j & 63], blk, mdst, j >> 6, j & 63, 8);
-                        else meter_tap<C, 8>(hi, 0, a.meter_w[j & 63], blk, mdst + 40, j >> 6, j & 63, 16);
-                    }
-                }
-                C lo[8];
-                load8(lo, g0, j + 2048 * h);
-                if constexpr (METER) {
-                    if (g == 0 && h == 1) meter_tap<C, 8>(lo, 0, a.meter_w[j & 63], blk, mdst + 32, j >> 6, j & 63, 16);
-                }
-#pragma unroll
-                for (int s = 0; s < 8; s++)
-                    x[8 * h + s] = make_double2(__builtin_fma(hi[s].x, sgn, lo[s].x), __builtin_fma(hi[s].y, sgn, lo[s].y));
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        };
-        if (interior) gather(load8_plain); else gather(load8_edge);
-        const C wj = a.tw_r2[j];                                        // W^j, W = exp(-2 pi i / 8192)
-        if (g) {                                                        // b[n] = (x[n] - x[n + 4096]) W^n, W^n = W^j exp(-i pi s / 16)
-#pragma unroll
-            for (int s = 0; s < 16; s++) x[s] = cmul(x[s], wj);
-            x[1] = mul_wconst<32, 1, false>(x[1]); x[2] = mul_wconst<32, 2, false>(x[2]); x[3] = mul_wconst<32, 3, false>(x[3]);
-            x[4] = mul_wconst<32, 4, false>(x[4]); x[5] = mul_wconst<32, 5, false>(x[5]); x[6] = mul_wconst<32, 6, false>(x[6]);
-            x[7] = mul_wconst<32, 7, false>(x[7]); x[8] = mul_wconst<32, 8, false>(x[8]); x[9] = mul_wconst<32, 9, false>(x[9]);
-            x[10] = mul_wconst<32, 10, false>(x[10]); x[11] = mul_wconst<32, 11, false>(x[11]); x[12] = mul_wconst<32, 12, false>(x[12]);
-            x[13] = mul_wconst<32, 13, false>(x[13]); x[14] = mul_wconst<32, 14, false>(x[14]); x[15] = mul_wconst<32, 15, false>(x[15]);
-        }
-        if constexpr (METER) __syncthreads();                           // the transform's image overlays the waves' meter blocks
-        SF::run(x, smem8s, FftRR<4096, false, C>::load(a.tw_fwd));
-        const C *mask = a.mask + (long long)ch * a.mask_stride + 4096 * g;
-#pragma unroll
-        for (int r = 0; r < 16; r++) {
-            x[r] = cmul(x[r], mask[j + 256 * r]);
-            if ((r + 1) % QH_MASK_BATCH == 0) __builtin_amdgcn_sched_barrier(0);
-        }
-        __syncthreads();
-        SI::run(x, smem8s, FftRR<4096, true, C>::load(a.tw_inv));
-        if (g == 0) {
-#pragma unroll
-            for (int s = 0; s < 16; s++) park[j + 256 * s] = x[s];
-            __syncthreads();                                            // everybody has read the image: the next phase's taps overlay it
-        } else {
-            // W^-n B'[n], then the halves: lower outputs y[n] (n >= 2048: s >= 8), upper outputs y[n + 4096] (every s)
-            int j2 = j;
-            asm volatile("" : "+v"(j2));                                // (lane-derived values formed again behind the transforms, not carried)
-            const C wt = a.tw_r2[j2], wc = make_double2(wt.x, -wt.y);
-#pragma unroll
-            for (int s = 0; s < 16; s++) x[s] = cmul(x[s], wc);
-            x[1] = mul_wconst<32, 1, true>(x[1]); x[2] = mul_wconst<32, 2, true>(x[2]); x[3] = mul_wconst<32, 3, true>(x[3]);
-            x[4] = mul_wconst<32, 4, true>(x[4]); x[5] = mul_wconst<32, 5, true>(x[5]); x[6] = mul_wconst<32, 6, true>(x[6]);
-            x[7] = mul_wconst<32, 7, true>(x[7]); x[8] = mul_wconst<32, 8, true>(x[8]); x[9] = mul_wconst<32, 9, true>(x[9]);
-            x[10] = mul_wconst<32, 10, true>(x[10]); x[11] = mul_wconst<32, 11, true>(x[11]); x[12] = mul_wconst<32, 12, true>(x[12]);
-            x[13] = mul_wconst<32, 13, true>(x[13]); x[14] = mul_wconst<32, 14, true>(x[14]); x[15] = mul_wconst<32, 15, true>(x[15]);
-            if constexpr (METER) __syncthreads();                       // other waves may still be reading the exchange image
-            EpiParam ep;
-            if (a.epi) ep = a.epi[ch]; else { ep.a = 1; ep.b = 0; ep.c = 0; ep.d = 1; }
-            double *blk = reinterpret_cast<double *>(smem8s) + (j2 >> 6) * kMeterLdsDoublesPerWave;
-            double2 *mdst = METER ? a.meter_out + (long long)ch * a.meter_stride + (long long)tile * (L >> 6) : nullptr;
-#pragma unroll
-            for (int h = 0; h < 2; h++) {
-                C up[8], dn[8];
-#pragma unroll
-                for (int s = 0; s < 8; s++) up[s] = park[j2 + 2048 * h + 256 * s];
-#pragma unroll
-                for (int s = 0; s < 8; s++) { dn[s] = cadd(up[s], x[8 * h + s]); up[s] = csub(up[s], x[8 * h + s]); }
-                if constexpr (METER) {
-                    if (h == 0) meter_tap<C, 8>(up, 0, a.meter_w[j2 & 63], blk, mdst, j2 >> 6, j2 & 63, 8);
-                    else {
-                        meter_tap<C, 8>(dn, 0, a.meter_w[j2 & 63], blk, mdst + 32, j2 >> 6, j2 & 63, 16);
-                        meter_tap<C, 8>(up, 0, a.meter_w[j2 & 63], blk, mdst + 40, j2 >> 6, j2 & 63, 16);
-                    }
-                }
-#pragma unroll
-                for (int s = 0; s < 8; s++) {
-                    const int n = j2 + 2048 * h + 256 * s;
-                    const long long mu = (long long)tile * L + 2048 + n;        // y[n + 4096]: rel = n + 4096 - P
-                    if (mu < a.n_out) out[mu] = make_double2(ep.a * up[s].x + ep.b * up[s].y, ep.c * up[s].x + ep.d * up[s].y);
-                    if (h == 1) {                                               // y[n], n >= 2048: rel = n - P
-                        const long long md = (long long)tile * L + (n - 2048);
-                        if (md < a.n_out) out[md] = make_double2(ep.a * dn[s].x + ep.b * dn[s].y, ep.c * dn[s].x + ep.d * dn[s].y);
-                    }
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-    }
-}
-#endif
 
 // ---- D = 1 stage on 6144-point tiles, 384 lanes ---------------------------------------------------------------------------
 // The 16 x 24 x 16 plan of qh_fft.hpp (Fft6144): 16 elements per lane like the 4096-point kernel, 4096 outputs per pair of
