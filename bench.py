@@ -8,7 +8,10 @@ With --gpus N every rank runs its own 256 channels (independent receivers shard 
 collective on the data path): weak scaling, value = all ranks' input samples / max-over-ranks time.
 --total-channels C instead splits C channels over the ranks (strong scaling; north_star's shape is 256 over 8).
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the headline
+figure, nothing more.  --full adds everything else the line can carry, each from runs of its own after the timed steps: the
+meters-off rate, per-kernel times and the roofline, the 24-bit and host-fed legs, the live counter passes, the other BASELINE
+configurations and the CPU baseline (the --no-* options skip single parts of it).
 """
 import argparse
 import json
@@ -259,8 +262,7 @@ def live_traffic(meters, timeout_s=240.0):
     if not rocprof:
         raise RuntimeError("no rocprofv3 on this box")
     log2 = 20
-    child = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--log2-samples", str(log2), "--meters", meters,
-             "--no-cpu-baseline", "--no-other-configs", "--no-le24", "--no-host-fed", "--no-live-traffic"]
+    child = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--log2-samples", str(log2), "--meters", meters]  # a plain run
     samples = 256.0 * (1 << log2)
     got = {}
     with tempfile.TemporaryDirectory(dir="/tmp") as td:
@@ -373,8 +375,8 @@ class DryLeg:
 def sharded_config(args, torch, dist, shard, rank, world, local_rank, dev, dry, sync):
     """BASELINE.json configurations 4 and 5 on N GPUs: channels are independent (wdsp/RXA.c:29, channel.c:29), every rank owns a
     contiguous range and runs the leg tools/bench_configs.py builds for it (the same setup_* functions the parity tests of the call
-    shapes use, tests/test_gpu_bench_shapes.py); barrier-bracketed timing, max over ranks, one line from rank 0 with every rank's own
-    kernel time and roofline.  Config 4: 256 channels per GPU, mode by the job-wide channel index mod 3 (2048 on eight GPUs);
+    shapes use, tests/test_gpu_bench_shapes.py); barrier-bracketed timing, max over ranks, one line from rank 0 (with --full, every
+    rank's own kernel time and roofline on it).  Config 4: 256 channels per GPU, mode by the job-wide channel index mod 3 (2048 on eight GPUs);
     --total-channels splits a fixed job instead.  Config 5: one 61.44 Msps fp32 channel per GPU (8 on eight)."""
     cfg = args.config
     if cfg == 5 and (args.channels != 1 or args.total_channels):
@@ -433,54 +435,55 @@ def sharded_config(args, torch, dist, shard, rank, world, local_rank, dev, dry, 
     if args.dump_outputs:               # config 4: every channel's audio; config 5: the valid part of the bandpass output
         dump_outputs(args.dump_outputs, rank, world,
                      {"y": torch.zeros((nch, 8), dtype=torch.complex128) if dry else leg.y if cfg == 4 else leg.yo[:, :last[0]]})
-    # the dominant kernel's own time on this rank, HIP events on the stream it is launched on
-    if dry:
-        kname, kms, algo = "dry", 1.0, 20.0
-    elif cfg == 4:
-        leg.eng.enable_timing(True)
-        kt = [0.0, 0.0, 0.0]
-        for _ in range(3):
-            leg.step()
-            kt = [a + b / 3 for a, b in zip(kt, leg.eng.timing_ms())]
-        leg.eng.enable_timing(False)
-        kname, kms, algo = "osfir_kernel<f64,4096,D=4,OUTMIX> front (shift + resample /4, shared by USB / AM / FM)", kt[0], 20.0
-    else:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        x, bufs, n = leg.x, leg.bufs, leg.n
-        sync()
-        e0.record(leg.stream)
-        for _ in range(5):
-            leg.casc.process_ptr(x.data_ptr(), n, n, bufs[-1].data_ptr(), bufs[-1].shape[1])
-        e1.record(leg.stream)
-        sync()
-        kname, kms, algo = "hb45_cascade_kernel<float,4> x 2 (4 + 4 half-band stages, one HBM pass)", e0.elapsed_time(e1) / 5, 8.0
-    achieved = algo * samples_rank / (kms * 1e-3) / 1e9 if kms > 0 else 0.0
-    mine_rec = {"rank": rank, "device": local_rank, "channels": [first, first + nch], "dominant_kernel_ms": kms,
-                "roofline": {"kernel": kname, "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBPS}}
-    per_rank = [mine_rec]
-    if world > 1:
-        per_rank = [None] * world
-        dist.all_gather_object(per_rank, mine_rec)
-    if rank == 0:
-        per_step = (float(total_channels) * (1 << args.log2_samples)) if (dry or cfg == 4) else samples_rank * world
-        total = per_step * args.steps
-        bytes_per_sample = 20.0 if cfg == 4 else 8.0
-        workload = ("config 4: %d channels/GPU x 192 kHz, mode by job-wide channel mod 3 = USB / AM / FM (amd / fmd / nbp), fp64, 2^%d input samples per channel per step"
-                    % (nch, args.log2_samples)) if cfg == 4 else \
-                   ("config 5: 1 channel/GPU x 61.44 Msps fp32: 8 x HB45 (fused cascade) + 245-tap /5 + overlap-save bandpass nc 2048, %d samples per step" % int(samples_rank))
-        line = {"metric": "Mcomplex-samples/s through RXA chain", "value": total / dt / 1e6, "unit": "Mcomplex-samples/s", "n_gpus": world,
-                "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": scaling,
-                "vs_baseline": None, "dtype": "f64" if cfg == 4 else "f32", "data": "synthetic",
-                "config": {"workload": workload, "baseline_config": cfg, "channels_per_gpu": nch, "total_channels": total_channels,
-                           "parallelism": "channel-sharded x%d (%s), no collective" % (world, scaling)},
-                "chain_algorithmic_GBps": bytes_per_sample * total / dt / 1e9,
-                "roofline": dict(per_rank[0]["roofline"], bound="latency", traffic=None,
-                                 algorithmic_bytes_per_launch=algo * samples_rank,
-                                 traffic_note="counter passes of this leg: profiles/ (tools/pmc_pass.py)"),
-                "per_rank": per_rank}
+    per_step = (float(total_channels) * (1 << args.log2_samples)) if (dry or cfg == 4) else samples_rank * world
+    total = per_step * args.steps
+    bytes_per_sample = 20.0 if cfg == 4 else 8.0
+    workload = ("config 4: %d channels/GPU x 192 kHz, mode by job-wide channel mod 3 = USB / AM / FM (amd / fmd / nbp), fp64, 2^%d input samples per channel per step"
+                % (nch, args.log2_samples)) if cfg == 4 else \
+               ("config 5: 1 channel/GPU x 61.44 Msps fp32: 8 x HB45 (fused cascade) + 245-tap /5 + overlap-save bandpass nc 2048, %d samples per step" % int(samples_rank))
+    line = {"metric": "Mcomplex-samples/s through RXA chain", "value": total / dt / 1e6, "unit": "Mcomplex-samples/s", "n_gpus": world,
+            "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": scaling,
+            "vs_baseline": None, "dtype": "f64" if cfg == 4 else "f32", "data": "synthetic",
+            "config": {"workload": workload, "baseline_config": cfg, "channels_per_gpu": nch, "total_channels": total_channels,
+                       "parallelism": "channel-sharded x%d (%s), no collective" % (world, scaling)},
+            "chain_algorithmic_GBps": bytes_per_sample * total / dt / 1e9}
+    if args.full:
+        # the dominant kernel's own time on this rank, HIP events on the stream it is launched on
         if dry:
-            line["dry_run"] = True
-            line["dry"] = {"rank0_channels": [first, first + nch], "steps_run": leg.calls}
+            kname, kms, algo = "dry", 1.0, 20.0
+        elif cfg == 4:
+            leg.eng.enable_timing(True)
+            kt = [0.0, 0.0, 0.0]
+            for _ in range(3):
+                leg.step()
+                kt = [a + b / 3 for a, b in zip(kt, leg.eng.timing_ms())]
+            leg.eng.enable_timing(False)
+            kname, kms, algo = "osfir_kernel<f64,4096,D=4,OUTMIX> front (shift + resample /4, shared by USB / AM / FM)", kt[0], 20.0
+        else:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            x, bufs, n = leg.x, leg.bufs, leg.n
+            sync()
+            e0.record(leg.stream)
+            for _ in range(5):
+                leg.casc.process_ptr(x.data_ptr(), n, n, bufs[-1].data_ptr(), bufs[-1].shape[1])
+            e1.record(leg.stream)
+            sync()
+            kname, kms, algo = "hb45_cascade_kernel<float,4> x 2 (4 + 4 half-band stages, one HBM pass)", e0.elapsed_time(e1) / 5, 8.0
+        achieved = algo * samples_rank / (kms * 1e-3) / 1e9 if kms > 0 else 0.0
+        mine_rec = {"rank": rank, "device": local_rank, "channels": [first, first + nch], "dominant_kernel_ms": kms,
+                    "roofline": {"kernel": kname, "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBPS}}
+        per_rank = [mine_rec]
+        if world > 1:
+            per_rank = [None] * world
+            dist.all_gather_object(per_rank, mine_rec)
+        line["roofline"] = dict(per_rank[0]["roofline"], bound="latency", traffic=None,
+                                algorithmic_bytes_per_launch=algo * samples_rank,
+                                traffic_note="counter passes of this leg: profiles/ (tools/pmc_pass.py)")
+        line["per_rank"] = per_rank
+    if dry:
+        line["dry_run"] = True
+        line["dry"] = {"rank0_channels": [first, first + nch], "steps_run": leg.calls}
+    if rank == 0:
         print(json.dumps(line), flush=True)
     if world > 1:
         _barrier(dist, dry)
@@ -540,6 +543,9 @@ def main():
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend of the barrier / max-over-ranks (nccl = RCCL)")
     ap.add_argument("--dry-run", action="store_true", help="plumbing test only: no GPU, no DSP (DryEngine); the line is not a measurement")
     ap.add_argument("--log2-samples", type=int, default=LOG2_SAMPLES, help="input samples per channel per step")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, measure and check everything else the line can carry (meters-off rate, per-kernel times, "
+                         "roofline, extra legs, CPU baseline); without it a run reports the headline figure alone")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-le24", action="store_true", help="skip the extra run from 24-bit wire samples (the test of the front kernel's HBM bound)")
     ap.add_argument("--no-other-configs", action="store_true", help="skip the extra legs (BASELINE configs 3, 4, 5 and the Quisk-native chain)")
@@ -547,7 +553,7 @@ def main():
     ap.add_argument("--no-host-fed", action="store_true", help="skip the host-fed leg (pinned host buffers, copies beside the kernels: what a receiver whose samples arrive on the host gets)")
     ap.add_argument("--meters", choices=["on", "off"], default="on",
                     help="on (default): xrxa's three meters run as in the reference (adc, S, agc: wdsp/RXA.c:566,569,589), "
-                         "fused into the nbp0 launch; the line also carries the rate of a second, untimed-for-`value` run with them off")
+                         "fused into the nbp0 launch; with --full the line also carries the rate of a second, untimed-for-`value` run with them off")
     ap.add_argument("--chunks", type=int, default=1,
                     help="split a step into this many consecutive time chunks (engine calls); the intermediate "
                          "buffer of a chunk then stays in the 256 MiB Infinity Cache")
@@ -689,12 +695,48 @@ def main():
         return shard.max_over_ranks(time.perf_counter() - t0, dev if not dry else None)
 
     dt = timed_run()                    # the measurement `value` reports
-    meter_db = [eng.GetRXAMeter(0, mt) for mt in (1, 3, 6)] if args.meters == "on" else None
+    meter_db = [eng.GetRXAMeter(0, mt) for mt in (1, 3, 6)] if args.full and args.meters == "on" else None
     if args.dump_outputs:               # the last timed step's output (before the meters-off run below writes y again) and meters
         outs = {"y": y}
         if args.meters == "on":
             outs["meters_dB"] = [[eng.GetRXAMeter(c, mt) for mt in (1, 3, 6)] for c in range(nch)]
         dump_outputs(args.dump_outputs, rank, world, outs)
+    total = float(total_channels) * n_in * args.steps            # all ranks' input samples in the timed steps
+    line = {
+        "metric": "Mcomplex-samples/s through RXA chain",
+        "value": total / dt / 1e6,
+        "unit": "Mcomplex-samples/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": dt / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": scaling,
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic",
+        "config": {"workload": "%d channels/GPU x 192 kHz IQ -> 48 kHz SSB RXA chain (shift + 561-tap resample/4 + adc meter + NBP nc 2048 "
+                               "+ S meter + fixed AGC + agc meter + panel), 2^%d input samples per channel per step" % (nch, args.log2_samples),
+                   "meters": args.meters, "ingest": args.ingest, "channels_per_gpu": nch, "total_channels": total_channels,
+                   "in_rate": IN_RATE, "dsp_rate": DSP_RATE, "dsp_size": DSP_SIZE,
+                   "parallelism": "channel-sharded x%d (%s), no collective" % (world, scaling)},
+        "chain_algorithmic_GBps": 20.0 * total / dt / 1e9,
+        # ~650 flop per input sample if the chain is evaluated in direct form like the reference; the
+        # overlap-save kernels execute about a quarter of that, which is how `value` can sit above the fp64-vector bound
+        # the survey derives from this count (78.6e12 / 650 = 121 Gsamp/s)
+        "chain_direct_form_equivalent_TFLOPs": 650.0 * total / dt / 1e12,
+    }
+    if dry:
+        line["dry_run"] = True
+        line["dry"] = {"rank0_channels": [first, first + nch], "setters": eng.setters}
+    if not args.full:                   # a plain run: the headline figure and nothing else
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        if world > 1:
+            _barrier(dist, dry)
+            dist.destroy_process_group()
+        return
+
     dt_off = None
     if args.meters == "on":             # the same steps once more with the meters off, reported beside it
         eng.enable_meters(False)
@@ -776,9 +818,6 @@ def main():
 
     if rank == 0:
         samples_per_step = float(nch) * n_in                     # this rank's launch (kernel-level figures below)
-        job_samples_per_step = float(total_channels) * n_in      # all ranks
-        total = job_samples_per_step * args.steps
-        value = total / dt / 1e6
         # dominant kernel and its algorithmic bytes per launch:
         #   front  (shift + resample /4): reads 16 B, writes 16/4 B per input sample        = 20 B / input sample
         #   band   (NBP overlap-save)   : reads 16 B, writes 16 B per DSP-rate sample (x1/4) =  8 B / input sample
@@ -826,29 +865,7 @@ def main():
                           "valu_frac": valu_dom["frac"] if valu_dom else None,
                           "time_with_input_bytes_halved_over_time": halved,
                           "rule": "hbm: >= 0.85 of the copy ceiling and < 0.8 of the time with 24-bit input; valu: >= 0.8 of 39.3 T lane-ops/s; else latency"}
-        line = {
-            "metric": "Mcomplex-samples/s through RXA chain",
-            "value": value,
-            "unit": "Mcomplex-samples/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": dt / args.steps * 1e3,
-            "higher_is_better": True,
-            "scaling": scaling,
-            "vs_baseline": None,
-            "dtype": "f64",
-            "data": "synthetic",
-            "config": {"workload": "%d channels/GPU x 192 kHz IQ -> 48 kHz SSB RXA chain (shift + 561-tap resample/4 + adc meter + NBP nc 2048 "
-                                   "+ S meter + fixed AGC + agc meter + panel), 2^%d input samples per channel per step" % (nch, args.log2_samples),
-                       "meters": args.meters, "ingest": args.ingest, "channels_per_gpu": nch, "total_channels": total_channels,
-                       "in_rate": IN_RATE, "dsp_rate": DSP_RATE, "dsp_size": DSP_SIZE,
-                       "parallelism": "channel-sharded x%d (%s), no collective" % (world, scaling)},
-            "chain_algorithmic_GBps": 20.0 * total / dt / 1e9,
-            # ~650 flop per input sample if the chain is evaluated in direct form like the reference; the
-            # overlap-save kernels execute about a quarter of that, which is how `value` can sit above the fp64-vector bound
-            # the survey derives from this count (78.6e12 / 650 = 121 Gsamp/s)
-            "chain_direct_form_equivalent_TFLOPs": 650.0 * total / dt / 1e12,
+        line.update({
             "kernel_ms": {"front_shift_resample": kt[0], "band_nbp": kt[1], "state_bookkeeping": kt[2]},
             "roofline": {"bound": bound, "bound_evidence": bound_evidence, "kernel": names[k], "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBPS, "traffic": traffic, "traffic_unit": "bytes per launch", "traffic_note": traffic_note,
@@ -858,16 +875,13 @@ def main():
                                                             "note": "SQ_INSTS_VALU x 64 per launch (stamped counter pass, profiles/c2_traffic.json) / the kernel's HIP-event time"},
                          "per_kernel": valu},
             "check_inband_gain": gain,
-        }
+        })
         if le24 is not None:
             line["ingest_le24"] = le24
         if hostfed is not None:
             line["host_fed"] = hostfed
         if world > 1:
             line["per_rank"] = per_rank
-        if dry:
-            line["dry_run"] = True
-            line["dry"] = {"rank0_channels": [first, first + nch], "setters": eng.setters}
         if dt_off is not None:
             line["value_meters_off"] = total / dt_off / 1e6
             line["ms_per_step_meters_off"] = dt_off / args.steps * 1e3

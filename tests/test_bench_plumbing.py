@@ -38,7 +38,7 @@ def _launch(world, extra, trace=None):
 
 
 def test_strong_split_two_ranks():
-    j = _launch(2, ["--total-channels", "256"])
+    j = _launch(2, ["--total-channels", "256", "--full"])
     assert j["dry_run"] is True and j["n_gpus"] == 2 and j["steps"] == 4 and j["warmup"] == 1
     assert j["scaling"] == "strong"
     assert j["config"]["total_channels"] == 256 and j["config"]["channels_per_gpu"] == 128
@@ -57,6 +57,27 @@ def test_weak_split_two_ranks_and_uneven_strong_split():
     assert abs(j["value"] - want) < 1e-6 * want
     j = _launch(2, ["--total-channels", "5"])          # 3 + 2
     assert j["config"]["channels_per_gpu"] == 3 and j["config"]["total_channels"] == 5
+
+
+HEADLINE_KEYS = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
+                 "data", "config", "chain_algorithmic_GBps"}
+
+
+def test_plain_runs_time_once_and_report_the_headline_alone(tmp_path):
+    """Without --full a run does only what its headline figure needs: one warm-up and one timed region on every rank, and a line
+    without the meters-off rate, kernel times, roofline or per-rank records -- configuration 2 and the sharded 4 and 5 alike."""
+    for extra, keys in (([], HEADLINE_KEYS | {"chain_direct_form_equivalent_TFLOPs"}), (["--config", "4"], HEADLINE_KEYS),
+                        (["--config", "5"], HEADLINE_KEYS)):
+        trace = str(tmp_path / ("trace_%s.txt" % (extra[1] if extra else "2")))
+        j = _launch(2, extra, trace=trace)
+        want = keys | {"dry_run", "dry"}
+        assert set(j) == want, sorted(set(j) ^ want)
+        assert j["n_gpus"] == 2 and j["steps"] == 4 and j["warmup"] == 1 and j["ms_per_step"] >= 2.0
+        ev = _read_trace(trace)
+        for what in ("warm_done", "timed_start", "steps_done", "timed_end"):
+            assert {r: len(t) for r, t in ev[what].items()} == {0: 1, 1: 1}, what
+        if extra:
+            assert j["dry"]["steps_run"] == 1 + 4         # the warm-up and the timed steps, no kernel-timing steps
 
 
 def test_single_process_dry_run():
@@ -82,7 +103,7 @@ def test_eight_ranks_strong_256_and_weak_2048(tmp_path):
     before every rank has left its warm-up, and none leaves it before every rank has done its steps."""
     for extra, per, total, scaling in ((["--total-channels", "256"], 32, 256, "strong"), (["--channels", "256"], 256, 2048, "weak")):
         trace = str(tmp_path / ("trace_%s.txt" % scaling))
-        j = _launch(8, extra, trace=trace)
+        j = _launch(8, extra + ["--full"], trace=trace)
         assert j["n_gpus"] == 8 and j["scaling"] == scaling
         assert j["config"]["channels_per_gpu"] == per and j["config"]["total_channels"] == total
         assert j["dry"]["rank0_channels"] == [0, per]
@@ -108,7 +129,7 @@ def test_self_spawn_eight_ranks_without_a_launcher(tmp_path):
     trace = str(tmp_path / "trace.txt")
     env["QH_BENCH_TRACE"] = trace
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--dry-run", "--backend", "gloo", "--steps", "3",
-                        "--warmup", "1", "--log2-samples", "12"], env=env, capture_output=True, text=True, timeout=600)
+                        "--warmup", "1", "--log2-samples", "12", "--full"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     js = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(js) == 1
@@ -136,7 +157,7 @@ def test_eight_ranks_of_configs_4_and_5(tmp_path):
     for extra, per, total, scaling in ((["--config", "4"], 256, 2048, "weak"), (["--config", "5"], 1, 8, "weak"),
                                        (["--config", "4", "--total-channels", "256"], 32, 256, "strong")):
         trace = str(tmp_path / ("trace_%s_%s.txt" % (extra[1], scaling)))
-        j = _launch(8, extra, trace=trace)
+        j = _launch(8, extra + ["--full"], trace=trace)
         assert j["n_gpus"] == 8 and j["scaling"] == scaling and j["dry_run"] is True
         assert j["config"]["baseline_config"] == int(extra[1])
         assert j["config"]["channels_per_gpu"] == per and j["config"]["total_channels"] == total
@@ -156,7 +177,7 @@ def test_eight_ranks_of_configs_4_and_5(tmp_path):
 
 
 def test_config_2_line_carries_every_ranks_roofline():
-    j = _launch(2, ["--channels", "8"])
+    j = _launch(2, ["--channels", "8", "--full"])
     assert all({"achieved", "peak", "unit", "kernel"} <= set(p["roofline"]) for p in j["per_rank"])
     assert j["roofline"]["bound"] in ("hbm", "valu", "latency") and "bound_evidence" in j["roofline"]
 

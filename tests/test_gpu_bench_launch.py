@@ -31,13 +31,18 @@ def _line(cmd):
     return json.loads(js[0])
 
 
-def _check(j):
+def _check_headline(j):
     assert j["metric"] == "Mcomplex-samples/s through RXA chain" and j["unit"] == "Mcomplex-samples/s"
     assert j["n_gpus"] == 1 and j["steps"] == 3 and j["warmup"] == 1 and j["higher_is_better"] is True
     assert j["scaling"] == "weak" and j["dtype"] == "f64" and j["data"] == "synthetic" and j["vs_baseline"] is None
     assert j["config"]["meters"] == "on" and j["config"]["channels_per_gpu"] == 256
     want = 256 * (1 << 18) / (j["ms_per_step"] * 1e-3) / 1e6
     assert abs(j["value"] - want) < 1e-6 * want and j["value"] > 1e4
+
+
+def _check(j):
+    """A --full line: the headline and the figures of the runs that follow the timed steps."""
+    _check_headline(j)
     r = j["roofline"]
     assert r["bound"] in ("hbm", "valu", "latency") and r["unit"] == "GB/s" and abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-9 and 0.05 < r["frac"] < 1.0
     ev = r["bound_evidence"]            # the label is a rule over measured numbers, and the numbers ride along
@@ -49,13 +54,13 @@ def _check(j):
 
 def test_torchrun_one_rank_over_rccl():
     j = _line([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
-               "--master-port", str(_free_port()), "bench.py", "--gpus", "1", "--no-live-traffic"] + ARGS)
+               "--master-port", str(_free_port()), "bench.py", "--gpus", "1", "--full", "--no-live-traffic"] + ARGS)
     _check(j)
     assert "x1" in j["config"]["parallelism"]
 
 
 def test_plain_python_launch():
-    j = _line([sys.executable, "bench.py"] + ARGS)
+    j = _line([sys.executable, "bench.py", "--full"] + ARGS)
     _check(j)
     hf = j["host_fed"]                  # what a receiver whose samples arrive on the host gets, never `value`
     for kind, bps in (("f64", 16), ("le24", 6)):
@@ -72,11 +77,15 @@ def test_plain_python_launch():
 
 def test_dump_outputs_are_the_same_from_run_to_run(tmp_path):
     """--dump-outputs: two runs with the same arguments write the same bits (the inputs are seeded, the chain is deterministic), and what
-    is written is the timed path's audio -- the in-band tone at the panel gain of 4 -- and its meters."""
+    is written is the timed path's audio -- the in-band tone at the panel gain of 4 -- and its meters.  A plain run (a) and a --full
+    run (b) write the same: what --full adds comes after the dump.  The plain line carries the headline and nothing else."""
     import numpy as np
-    args = ARGS + ["--no-le24", "--no-host-fed", "--no-live-traffic", "--no-other-configs"]
-    for d in ("a", "b"):
-        _check(_line([sys.executable, "bench.py"] + args + ["--dump-outputs", str(tmp_path / d)]))
+    plain = _line([sys.executable, "bench.py"] + ARGS + ["--dump-outputs", str(tmp_path / "a")])
+    _check_headline(plain)
+    assert set(plain) == {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
+                          "dtype", "data", "config", "chain_algorithmic_GBps", "chain_direct_form_equivalent_TFLOPs"}, sorted(plain)
+    full = ARGS + ["--full", "--no-le24", "--no-host-fed", "--no-live-traffic", "--no-other-configs"]
+    _check(_line([sys.executable, "bench.py"] + full + ["--dump-outputs", str(tmp_path / "b")]))
     names = sorted(f.name for f in (tmp_path / "a").iterdir())
     assert names == sorted(f.name for f in (tmp_path / "b").iterdir()) == ["meters_dB.npy", "y.npy", "y_cols.npy", "y_rows.npy"]
     for n in names:

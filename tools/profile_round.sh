@@ -7,7 +7,7 @@ tag=${1:-r06}
 root=$(pwd)
 out=$root/gpurun_out
 mkdir -p $out
-python3 bench.py > $out/${tag}_bench.json 2> $out/${tag}_bench.err
+python3 bench.py --full > $out/${tag}_bench.json 2> $out/${tag}_bench.err
 tail -c 300 $out/${tag}_bench.err
 tools/kstats.sh $out/${tag}_kernel_stats.csv python3 $root/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-other-configs --no-le24 --no-host-fed --no-live-traffic > /dev/null
 for leg in 3 4 5 2agc quisk; do
