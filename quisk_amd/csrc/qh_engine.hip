@@ -183,10 +183,12 @@ struct Engine {
     double2 *buf[2] = { nullptr, nullptr };
     long long buf_cap = 0;                  // complex samples per channel
     // long impulse responses (nc > 4096), per fircore stage s = 0 nbp0, 1 bp1, 2 FM de-emphasis, 3 FM audio filter, 4 bpsnba:
-    // long_parts[s] partitions (1: the ordinary path), their masks lmask[s] ([nch or 1][kLongParts][8192]), the stage's last kLongHist
-    // input samples lhist[s][ping-pong][nch][kLongHist]; lcat: history + block of the stage being run, ltmp: a partition's output
+    // long_parts[s] partitions (1: the ordinary path), their masks lmask[s] ([nch or 1][kLongParts][8192]), how many of them each mask row's
+    // own impulse response reaches lrow_parts[s] ([nch or 1]), the stage's last kLongHist input samples lhist[s][ping-pong][nch][kLongHist];
+    // lcat: history + block of the stage being run, ltmp: a partition's output
     int long_parts[5] = { 1, 1, 1, 1, 1 };
     double2 *lmask[5] = { nullptr, nullptr, nullptr, nullptr, nullptr };
+    int *lrow_parts[5] = { nullptr, nullptr, nullptr, nullptr, nullptr };
     double2 *lhist[5][2] = { { nullptr, nullptr }, { nullptr, nullptr }, { nullptr, nullptr }, { nullptr, nullptr }, { nullptr, nullptr } };
     double2 *lcat = nullptr, *ltmp = nullptr;
     long long lcat_cap = 0;                 // the buf_cap they were made for
@@ -402,7 +404,7 @@ Engine::~Engine()
     if (rsmpin) qh_rat_destroy(rsmpin);
     (void)hipFree(fbuf);
     (void)hipFree(obuf); (void)hipFree(abuf);
-    for (int i = 0; i < 5; i++) { (void)hipFree(lmask[i]); (void)hipFree(lhist[i][0]); (void)hipFree(lhist[i][1]); }
+    for (int i = 0; i < 5; i++) { (void)hipFree(lmask[i]); (void)hipFree(lrow_parts[i]); (void)hipFree(lhist[i][0]); (void)hipFree(lhist[i][1]); }
     (void)hipFree(lcat); (void)hipFree(ltmp);
     (void)hipFree(mask_front); (void)hipFree(mask_nbp); (void)hipFree(mask_bp1); (void)hipFree(tw4096); (void)hipFree(tw_inv_front); (void)hipFree(tw8192);
     (void)hipFree(nco_phase); (void)hipFree(nco_dphase); (void)hipFree(nco_parked); (void)hipFree(nco_step); (void)hipFree(epi);
@@ -1687,9 +1689,12 @@ static __global__ __launch_bounds__(NT) void long_hist_kernel(const double2 *cat
     double2 *h = hist + (long long)ch * kLongHist;
     for (int i = kLongHist - lh + blockIdx.x * NT + threadIdx.x; i < kLongHist; i += gridDim.x * NT) h[i] = c[i];
 }
-static __global__ __launch_bounds__(NT) void long_add_kernel(double2 *dst, long long dst_stride, const double2 *add, long long add_stride, int n, const int *chan_list)
+// partition p is added only where the channel's own impulse response reaches it (row_parts: per mask row, row_stride 0 for a shared mask)
+static __global__ __launch_bounds__(NT) void long_add_kernel(double2 *dst, long long dst_stride, const double2 *add, long long add_stride, int n, const int *chan_list,
+                                                             const int *row_parts, int row_stride, int p)
 {
     const int ch = chan_list ? chan_list[blockIdx.y] : (int)blockIdx.y;
+    if (p >= row_parts[(long long)ch * row_stride]) return;
     double2 *d = dst + (long long)ch * dst_stride;
     const double2 *a = add + (long long)ch * add_stride;
     for (int i = blockIdx.x * NT + threadIdx.x; i < n; i += gridDim.x * NT) { d[i].x += a[i].x; d[i].y += a[i].y; }
@@ -1716,11 +1721,13 @@ int Engine::long_stage_alloc(int sid, bool shared_mask)
     const size_t rows = shared_mask ? 1 : (size_t)nch;
     QH_HIP(dev_alloc(&lmask[sid], rows * kLongParts * kBandNfftMax));
     QH_HIP(hipMemsetAsync(lmask[sid], 0, rows * kLongParts * kBandNfftMax * sizeof(double2), stream));
+    QH_HIP(dev_alloc(&lrow_parts[sid], rows));
+    QH_HIP(hipMemsetAsync(lrow_parts[sid], 0, rows * sizeof(int), stream));
     for (int i = 0; i < 2; i++) {
         QH_HIP(dev_alloc(&lhist[sid][i], (size_t)nch * kLongHist));
         QH_HIP(hipMemsetAsync(lhist[sid][i], 0, (size_t)nch * kLongHist * sizeof(double2), stream));
     }
-    dev_bytes += (long long)(rows * kLongParts * kBandNfftMax + 2 * (size_t)nch * kLongHist) * (long long)sizeof(double2);
+    dev_bytes += (long long)(rows * kLongParts * kBandNfftMax + 2 * (size_t)nch * kLongHist) * (long long)sizeof(double2) + (long long)(rows * sizeof(int));
     return QH_OK;
 }
 int Engine::long_buffers()
@@ -1736,12 +1743,14 @@ int Engine::long_buffers()
 int Engine::long_masks_upload(int sid, long long row, const std::vector<cd> &h)
 {
     std::vector<cd> all((size_t)kLongParts * kBandNfftMax, cd(0.0, 0.0));
-    for (int p = 0; p < kLongParts && (size_t)p * kLongPart < h.size(); p++) {
+    const int own = (int)std::min<size_t>((h.size() + kLongPart - 1) / kLongPart, (size_t)kLongParts);
+    for (int p = 0; p < own; p++) {
         const size_t a = (size_t)p * kLongPart, b = std::min(h.size(), a + (size_t)kLongPart);
         const std::vector<cd> m = make_mask(std::vector<cd>(h.begin() + (long)a, h.begin() + (long)b), kBandNfftMax);
         std::copy(m.begin(), m.end(), all.begin() + (long)((size_t)p * kBandNfftMax));
     }
     QH_HIP(hipMemcpyAsync(lmask[sid] + (size_t)row * kLongParts * kBandNfftMax, all.data(), all.size() * sizeof(cd), hipMemcpyHostToDevice, stream));
+    QH_HIP(hipMemcpyAsync(lrow_parts[sid] + row, &own, sizeof(int), hipMemcpyHostToDevice, stream));
     QH_HIP(hipStreamSynchronize(stream));
     return QH_OK;
 }
@@ -1761,8 +1770,11 @@ void Engine::run_band(const double2 *src, long long src_stride, double2 *dst, lo
         const int K = long_parts[sid], Pk = kLongPart - 1, Lk = kBandNfftMax - Pk, nt = (int)((n_mid + Lk - 1) / Lk);
         const int nl = list ? nlist : nch;
         const long long cat_stride = kLongHist + lcat_cap;
-        // what the K partitions look back over; a channel's own nc may be shorter (its further masks are zero) and what lies beyond in its row is then
-        // whatever an earlier, longer form of the stage left there -- finite samples, times zero
+        // what the K partitions look back over.  A channel's own nc may be shorter: the partitions past its own impulse response are not
+        // added to its output (long_add_kernel), so it never depends on its row beyond its own nc -- what lies there may be an earlier,
+        // longer form's samples or a non-finite burst this channel had, and a zero mask would not cancel that (NaN * 0 = NaN).
+        // (The tile pass of such a partition still runs for that channel and its result is dropped: wasted work, not wrong; per-partition
+        // channel lists would save it.)
         const int lh = K * kLongPart - 1;
         const long long per = (lh + n_mid + NT - 1) / NT;
         tick(1);
@@ -1781,7 +1793,7 @@ void Engine::run_band(const double2 *src, long long src_stride, double2 *dst, lo
             launch_band<kBandNfftMax>(a, nt, nl, stream, false, false);
             const long long pn = (n_mid + NT - 1) / NT;
             if (p) hipLaunchKernelGGL(long_add_kernel, dim3((unsigned)(pn < 1024 ? pn : 1024), (unsigned)nl), dim3(NT), 0, stream, dst, dst_stride,
-                                      (const double2 *)ltmp, lcat_cap, (int)n_mid, list);
+                                      (const double2 *)ltmp, lcat_cap, (int)n_mid, list, (const int *)lrow_parts[sid], mask_stride ? 1 : 0, p);
         }
         const long long pn = (n_mid + NT - 1) / NT;
         if (ep) hipLaunchKernelGGL((pointwise_kernel<double, false>), dim3((unsigned)(pn < 1024 ? pn : 1024), (unsigned)nl), dim3(NT), 0, stream,
