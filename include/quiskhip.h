@@ -128,6 +128,21 @@ int qh_rxa_SetRXASNBApresamps(qh_rxa *e, int ch, int presamps);
 int qh_rxa_SetRXASNBApostsamps(qh_rxa *e, int ch, int postsamps);
 int qh_rxa_SetRXASNBApmultmin(qh_rxa *e, int ch, double pmultmin);
 int qh_rxa_SetRXASNBAovrlp(qh_rxa *e, int ch, int ovrlp);          /* snb.c:595; ch = -1: the frame advance is the engine's */
+/* xcbl, xspeak, xmpeak between the agc meter and the panel (wdsp/RXA.c:591-593), all off at create (RXA.c:403-445): the carrier block
+ * (wdsp/cblock.c:120-126), the CW audio peak filter (wdsp/iir.c:322-360: design 1, four stages; the design setters zero its state) and
+ * the two-tone peak filter (wdsp/iir.c:490-548: the sum of its enabled peaks; each peak's design setters zero that peak's state).
+ * npeaks outside [0, 2] and fil outside [0, 2) are refused with QH_ERR_INVALID (the reference indexes past its two-peak arrays). */
+int qh_rxa_SetRXACBLRun(qh_rxa *e, int ch, int run);                            /* wdsp/cblock.c:120-126 */
+int qh_rxa_SetRXASPCWRun(qh_rxa *e, int ch, int run);                           /* wdsp/iir.c:322-329 */
+int qh_rxa_SetRXASPCWFreq(qh_rxa *e, int ch, double freq);                      /* wdsp/iir.c:331-339 */
+int qh_rxa_SetRXASPCWBandwidth(qh_rxa *e, int ch, double bw);                   /* wdsp/iir.c:341-349 */
+int qh_rxa_SetRXASPCWGain(qh_rxa *e, int ch, double gain);                      /* wdsp/iir.c:351-359 */
+int qh_rxa_SetRXAmpeakRun(qh_rxa *e, int ch, int run);                          /* wdsp/iir.c:490-497 */
+int qh_rxa_SetRXAmpeakNpeaks(qh_rxa *e, int ch, int npeaks);                    /* wdsp/iir.c:499-506 */
+int qh_rxa_SetRXAmpeakFilEnable(qh_rxa *e, int ch, int fil, int enable);        /* wdsp/iir.c:508-515 */
+int qh_rxa_SetRXAmpeakFilFreq(qh_rxa *e, int ch, int fil, double freq);         /* wdsp/iir.c:517-526 */
+int qh_rxa_SetRXAmpeakFilBw(qh_rxa *e, int ch, int fil, double bw);             /* wdsp/iir.c:528-537 */
+int qh_rxa_SetRXAmpeakFilGain(qh_rxa *e, int ch, int fil, double gain);         /* wdsp/iir.c:539-548 */
 int qh_rxa_SetRXAAMSQThreshold(qh_rxa *e, int ch, double threshold_db);
 int qh_rxa_SetRXAAMSQMaxTail(qh_rxa *e, int ch, double tail_seconds);
 /* xanf / xanr (wdsp/anf.c:82-133, anr.c:82-133), setters wdsp/anf.c:175-239 and anr.c:175-238; which position (0 before
@@ -294,6 +309,17 @@ void SetRXAANRGain(int channel, double v);
 void SetRXAANRLeakage(int channel, double v);
 void SetRXAANRVals(int channel, int taps, int delay, double gain, double leakage);
 void SetRXAAMSQRun(int channel, int run);                                        /* wdsp/amsq.c:216-222 */
+void SetRXACBLRun(int channel, int setit);                                       /* wdsp/cblock.c:120-126, wdsp.h:277 */
+void SetRXASPCWRun(int channel, int run);                                        /* wdsp/iir.c:322-360, wdsp.h:557-560 */
+void SetRXASPCWFreq(int channel, double freq);
+void SetRXASPCWBandwidth(int channel, double bw);
+void SetRXASPCWGain(int channel, double gain);
+void SetRXAmpeakRun(int channel, int run);                                       /* wdsp/iir.c:490-548, wdsp.h:561-566 */
+void SetRXAmpeakNpeaks(int channel, int npeaks);
+void SetRXAmpeakFilEnable(int channel, int fil, int enable);
+void SetRXAmpeakFilFreq(int channel, int fil, double freq);
+void SetRXAmpeakFilBw(int channel, int fil, double bw);
+void SetRXAmpeakFilGain(int channel, int fil, double gain);
 void SetRXAAMSQThreshold(int channel, double threshold);                         /* wdsp/amsq.c:224-232, dB */
 void SetRXAAMSQMaxTail(int channel, double tail);                                /* wdsp/amsq.c:234-243, seconds */
 void SetRXAEMNRRun(int channel, int run);                                        /* wdsp/emnr.c:1096-1110; needs the files `calculus` and

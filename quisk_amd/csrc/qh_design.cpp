@@ -303,4 +303,26 @@ std::vector<cd> fft_twiddle_table(int n)
     return t;
 }
 
+// calc_speak, design 1, nstages 4 (wdsp/iir.c:180-214)
+SpeakDesign design_speak(double f, double bw, double gain, double rate)
+{
+    if (f < 200.0) f = 200.0;
+    const double ratio = bw / f;
+    const double bw_parm = 5.0, bw_corr = 1.13 * ratio - 0.956 * ratio * ratio, A = 2.5, f_min = 50.0;
+    if (f < f_min) f = f_min;
+    const double w0 = kTwoPi * f / rate;
+    const double sn = std::sin(w0);
+    const double cbw = bw_corr * f;
+    const double c = sn * std::sinh(0.5 * std::log((f + 0.5 * cbw * bw_parm) / (f - 0.5 * cbw * bw_parm)) * w0 / sn);
+    const double den = 1.0 + c / A;
+    SpeakDesign d;
+    d.a0 = (1.0 + c * A) / den;
+    d.a1 = -2.0 * std::cos(w0) / den;
+    d.a2 = (1 - c * A) / den;
+    d.b1 = -d.a1;
+    d.b2 = -(1 - c / A) / den;
+    d.fgain = gain / std::pow(A * A, 4.0);
+    return d;
+}
+
 }  // namespace qh

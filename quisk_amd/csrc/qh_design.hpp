@@ -37,6 +37,11 @@ std::vector<cd> fir_mbandpass(int N, const std::vector<std::pair<double, double>
 std::vector<cd> mp_imp(const std::vector<cd> &fir, int pfactor, int polarity);     // wdsp/fir.c:319-368
 std::vector<cd> make_mask(const std::vector<cd> &h, int nfft);
 
+// calc_speak, design 1 with create_rxa's four stages (wdsp/iir.c:180-214): the one biquad the stages share and the input gain.
+// f below 200 Hz is taken as 200 Hz, as the reference stores it back.
+struct SpeakDesign { double a0, a1, a2, b1, b2, fgain; };
+SpeakDesign design_speak(double f, double bw, double gain, double rate);
+
 // Concatenated per-pass twiddle tables for qh::FftRR<N> (see the Plan table in qh_fft.hpp).
 std::vector<cd> fft_twiddle_table(int n);
 

@@ -34,6 +34,7 @@
 #include "qh_agc_tiled.hpp"
 #include "qh_emnr.hpp"
 #include "qh_snba.hpp"
+#include "qh_audio_peak.hpp"
 #include "qh_internal.hpp"
 
 namespace qh {
@@ -125,10 +126,20 @@ struct ChanCfg {
     bool demod_dirty = true, ctcss_flush = false;
     bool nbp_dirty = true, bp1_dirty = true, nco_dirty = true, epi_dirty = true;
     bool nbp_flush = false, bp1_flush = false;
+    // xcbl, xspeak, xmpeak (create_rxa, RXA.c:403-445: all three made with run 0); the design setters zero their cascade (sp_flush,
+    // mp_flush) at the next block boundary
+    int cbl_run = 0, sp_run = 0, mp_run = 0, mp_npeaks = 2;
+    double sp_f = 600.0, sp_bw = 100.0, sp_gain = 2.0;
+    int mp_enable[kApPeaks] = { 1, 1 };
+    double mp_f[kApPeaks] = { 2125.0, 2295.0 }, mp_bw[kApPeaks] = { 75.0, 75.0 }, mp_gain[kApPeaks] = { 1.0, 1.0 };
+    bool ap_dirty = true, sp_flush = false, mp_flush[kApPeaks] = { false, false };
+    bool ap_on() const { return cbl_run || sp_run || mp_run; }
+    // (the new stages sit behind xwcpagc too, ahead of the panel: a fixed gain that changes while a peak still rings must not reach
+    // the ringing tail, so it is applied at the AGC's spot for them as well)
     bool fix_before() const
     {
         return agc_run && agc_mode == 0 && ((bp1_run && bp1_pos) || (lms[0].run && lms[0].position) || (lms[1].run && lms[1].position) ||
-                                            (emnr_run && emnr_pos));
+                                            (emnr_run && emnr_pos) || ap_on());
     }
 };
 
@@ -225,6 +236,18 @@ struct Engine {
     // changes, so it is applied where the reference applies it; [b] = which buffer holds the channel at that point
     int *list_fix[2] = { nullptr, nullptr }, n_fix[2] = { 0, 0 };
     double *fix_gain = nullptr;
+    // xcbl / xspeak / xmpeak (qh_audio_peak.hpp), made when a channel first runs one of them: lists per buffer ([0] cur: channels
+    // without bp1, [1] other), parameters, state [nch][kApW], the carry matrices T = A^ap_L [nch][kApDim^2] and the tiles' end / start
+    // states [nch][ap_ends_cap][kApW]
+    int *list_ap[2] = { nullptr, nullptr }, n_ap[2] = { 0, 0 };
+    int *ap_lists = nullptr;
+    ApParam *ap_prm = nullptr;
+    double *ap_state = nullptr, *ap_M = nullptr, *ap_ends = nullptr;
+    long long ap_ends_cap = 0;
+    int ap_L = 0;
+    std::vector<double> ap_M_h;
+    std::vector<ApParam> ap_prm_h;
+    int ap_alloc();
     // emnr: lists like the LMS filters' ([0] position 0; [1 + b] position 1 with the data in cur / other)
     int *list_emnr[3] = { nullptr, nullptr, nullptr }, n_emnr[3] = { 0, 0, 0 };
     // snba: bpsnba lists per position, the blanker's list, its parameters, taps, state and the Toeplitz-inverse scratch
@@ -385,6 +408,8 @@ struct Engine {
     void lms_at(const ChainCall &k, int pos, double2 *b);
     void bp1_at(const ChainCall &k, int pos);
     int run_agc(ChainCall &k);
+    int refresh_ap(const ChainCall &k);
+    void run_audio_peak(const ChainCall &k);
     void run_output(const ChainCall &k);
     qh_rat *rsmpout = nullptr;          // xresample out (wdsp/RXA.c:596), only when out_rate != dsp_rate
     qh_rat *rsmpin = nullptr;           // xresample in for the rate ratios the overlap-save front stage does not cover (D == 0)
@@ -420,6 +445,7 @@ Engine::~Engine()
     (void)hipFree(emnr_chan); (void)hipFree(emnr_scal); (void)hipFree(emnr_state); (void)hipFree(emnr_window); (void)hipFree(emnr_GG);
     (void)hipFree(emnr_GGS); (void)hipFree(emnr_zeta); (void)hipFree(emnr_zeta_true);
     (void)hipFree(amsq_prm); (void)hipFree(amsq_state); (void)hipFree(amsq_cup); (void)hipFree(amsq_cdown); (void)hipFree(amsq_mag);
+    (void)hipFree(ap_lists); (void)hipFree(ap_prm); (void)hipFree(ap_state); (void)hipFree(ap_M); (void)hipFree(ap_ends);
     (void)hipFree(fix_gain); (void)hipFree(lms_prm[0]); (void)hipFree(lms_prm[1]); (void)hipFree(lms_state[0]); (void)hipFree(lms_state[1]);
     (void)hipFree(sam_prm); (void)hipFree(sn_prm); (void)hipFree(sn_state); (void)hipFree(mask_de); (void)hipFree(mask_aud);
     for (int i = 0; i < 2; i++) { (void)hipFree(hist_de[i]); (void)hipFree(hist_aud[i]); }
@@ -902,7 +928,7 @@ int Engine::refresh_demod()
         if (c.agc_abuf != abuf) { c.agc_rewindow = true; if (!c.agc_stale) { c.agc_stale = true; lists_dirty = true; } }
     }
     if (lists_dirty) {
-        std::vector<int> la, ls, lf, lb, lp, lgc, lgo, lgc_s, lgo_s, ll, lms_l[2][3], lbp[2], lfix[2], lsq, lem[3], lsn[2], lsnba, lrest, lusb, lrb;
+        std::vector<int> la, ls, lf, lb, lp, lgc, lgo, lgc_s, lgo_s, ll, lms_l[2][3], lbp[2], lfix[2], lsq, lem[3], lsn[2], lsnba, lrest, lusb, lrb, lap[2];
         int n_sam0_new = 0;
         for (int ch = 0; ch < nch; ch++) {
             const ChanCfg &c = cfg[(size_t)ch];
@@ -914,6 +940,7 @@ int Engine::refresh_demod()
             for (int f = 0; f < 2; f++) if (c.lms[f].run) lms_l[f][c.lms[f].position ? 1 + at_agc : 0].push_back(ch);
             if (c.bp1_run) lbp[c.bp1_pos ? 1 : 0].push_back(ch);
             if (c.fix_before()) lfix[at_agc].push_back(ch);
+            if (c.ap_on()) lap[c.bp1_run ? 1 : 0].push_back(ch);        // where the channel is behind bp1 at either position
             if (c.fmd_run && c.lim_run) ll.push_back(ch);
             if (c.amd_run && c.amd_mode == 0) la.push_back(ch);
             if (c.amd_run && c.amd_mode == 1) { if (c.sbmode == 0) ls.insert(ls.begin() + n_sam0_new++, ch); else ls.push_back(ch); }
@@ -927,6 +954,8 @@ int Engine::refresh_demod()
         n_bp1p[0] = (int)lbp[0].size(); n_bp1p[1] = (int)lbp[1].size();
         n_fix[0] = (int)lfix[0].size(); n_fix[1] = (int)lfix[1].size();
         n_amsq = (int)lsq.size();
+        n_ap[0] = (int)lap[0].size(); n_ap[1] = (int)lap[1].size();
+        if ((n_ap[0] || n_ap[1]) && !ap_prm) if (int rc = ap_alloc()) return rc;
         for (int k = 0; k < 3; k++) n_emnr[k] = (int)lem[k].size();
         if ((n_emnr[0] || n_emnr[1] || n_emnr[2]) && !emnr_state) if (int rc = emnr_alloc()) return rc;
         n_snb[0] = (int)lsn[0].size(); n_snb[1] = (int)lsn[1].size(); n_snba = (int)lsnba.size();
@@ -1080,6 +1109,7 @@ int Engine::refresh_demod()
         for (int f = 0; f < 2; f++) for (int k = 0; k < 3; k++) QH_HIP(put(list_lms[f][k], lms_l[f][k]));
         QH_HIP(put(list_bp1p[0], lbp[0])); QH_HIP(put(list_bp1p[1], lbp[1]));
         QH_HIP(put(list_fix[0], lfix[0])); QH_HIP(put(list_fix[1], lfix[1])); QH_HIP(put(list_amsq, lsq));
+        if (ap_lists) { QH_HIP(put(list_ap[0], lap[0])); QH_HIP(put(list_ap[1], lap[1])); }
         for (int k = 0; k < 3; k++) QH_HIP(put(list_emnr[k], lem[k]));
         QH_HIP(put(list_snb[0], lsn[0])); QH_HIP(put(list_snb[1], lsn[1])); QH_HIP(put(list_snba, lsnba));
         std::vector<double> fg((size_t)nch);
@@ -1974,7 +2004,7 @@ int Engine::chain_needs(ChainCall &k)
             return set_error(QH_ERR_UNSUPPORTED, "AGC mode %d is not provided (0 fixed, 1-4 long/slow/med/fast)", c.agc_mode);
         // (SetRXAAMDRun can switch the AM detector on beside the FM one, RXA.c:594-595 then runs both in a row: not provided, and said so)
         if (c.amd_run && c.fmd_run) return set_error(QH_ERR_UNSUPPORTED, "channel %d: the AM and the FM detector both switched on", (int)(&c - cfg.data()));
-        if (c.amd_run || c.fmd_run || (c.agc_run && c.agc_mode != 0) || c.lms[0].run || c.lms[1].run || c.amsq_run || c.emnr_run || c.snba_run) k.mixed = true;
+        if (c.amd_run || c.fmd_run || (c.agc_run && c.agc_mode != 0) || c.lms[0].run || c.lms[1].run || c.amsq_run || c.emnr_run || c.snba_run || c.ap_on()) k.mixed = true;
         if (c.emnr_run && !emnr_tables) return set_error(QH_ERR_INVALID, "EMNR needs its gain tables first (qh_rxa_SetEMNRTables: WDSP's `calculus` and `zetaHat.bin` data)");
         if (c.nbp_run) { k.any_nbp = true; if (c.nbp_nc > k.nc_max) k.nc_max = c.nbp_nc; } else k.every_nbp = false;
         if (c.bp1_run) { k.any_bp1 = true; if (c.bp1_nc > k.nc_max) k.nc_max = c.bp1_nc; }
@@ -2069,6 +2099,7 @@ int Engine::process_chain(const double *d_in, long long in_stride, double *d_out
     if (k.n_in > 0x7fffffffLL) return set_error(QH_ERR_INVALID, "too many samples in one call");
     if (int rc = ensure_buffers(k.n_mid)) return rc;
     if (k.long_mode) if (int rc = long_buffers()) return rc;
+    if (int rc = refresh_ap(k)) return rc;
     ev_used = 0;
 
     k.in = reinterpret_cast<const double2 *>(d_in); k.in_stride = in_stride;
@@ -2176,7 +2207,7 @@ int Engine::plan_mixed(ChainCall &k)
     for (int f = 0; f < 2; f++) for (int p = 0; p < 3; p++) no_lms = no_lms && !n_lms[f][p];
     k.direct = k.split && !(dbg_forms & 2) && k.every_nbp && !eg.kind && !n_lim && !n_agc_cur && !n_agc_other && !n_snba && !n_snb[1] && no_lms &&
                !n_emnr[0] && !n_emnr[1] && !n_emnr[2] && !n_fix[0] && !n_fix[1] && !n_bp1p[1] && n_bp1p[0] == n_bp1 && n_rb == n_bp1 &&
-               n_usb + n_fm == n_plain &&
+               n_usb + n_fm == n_plain && !n_ap[0] && !n_ap[1] &&
                // the first stores to `out` come while other channels' input is still being read: not for a caller that works in place
                extents_apart(k.out, k.out_stride, k.n_mid, k.in, k.in_stride, k.n_in, nch);
     // ... and the AM channels' nbp0 leaves the envelope and every tile's share of the fade leveller's averages: one pass does the rest
@@ -2576,7 +2607,7 @@ int Engine::run_agc(ChainCall &k)
     }
     // ... and when every channel has the AGC as its last stage (nothing at position 1, no meters, squelch or audio frames), the gain
     // multiply applies the output matrix and writes the caller's rows: the output pass goes
-    bool no_p1 = !n_bp1p[1] && !n_fix[0] && !n_fix[1] && !n_emnr[1] && !n_emnr[2] && !n_amsq && !meters_on && !eg.kind;
+    bool no_p1 = !n_bp1p[1] && !n_fix[0] && !n_fix[1] && !n_emnr[1] && !n_emnr[2] && !n_amsq && !meters_on && !eg.kind && !n_ap[0] && !n_ap[1];
     for (int f = 0; f < 2; f++) for (int p = 1; p < 3; p++) no_p1 = no_p1 && !n_lms[f][p];
     k.agc_direct = tiled && no_p1 && nt_cur == n_plain && nt_other == n_bp1;
     if (tiled) {
@@ -2672,6 +2703,131 @@ int Engine::run_agc(ChainCall &k)
     return QH_OK;
 }
 
+// ---- xcbl, xspeak, xmpeak (qh_audio_peak.hpp)
+int Engine::ap_alloc()
+{
+    if (int rc = realloc_dev(ap_lists, 0, 2LL * nch)) return rc;
+    if (int rc = realloc_dev(ap_prm, 0, nch)) return rc;
+    if (int rc = realloc_dev(ap_state, 0, (long long)nch * kApW)) return rc;
+    if (int rc = realloc_dev(ap_M, 0, (long long)nch * kApDim * kApDim)) return rc;
+    QH_HIP(hipMemsetAsync(ap_state, 0, (size_t)nch * kApW * sizeof(double), stream));
+    list_ap[0] = ap_lists; list_ap[1] = ap_lists + nch;
+    ap_M_h.assign((size_t)nch * kApDim * kApDim, 0.0);
+    ap_prm_h.assign((size_t)nch, ApParam{});
+    ap_L = 0;
+    for (ChanCfg &c : cfg) { c.ap_dirty = true; c.sp_flush = false; for (bool &f : c.mp_flush) f = false; }    // the state starts at zero
+    return QH_OK;
+}
+
+// T = A^L: A's column i is where one step with zero input takes the unit state e_i (ap_step_linear, the kernel's own recurrence);
+// powers by squaring.  Stages that do not run leave their rows at the identity.
+static void ap_transition(const ApParam &q, int L, double *T)
+{
+    constexpr int N = kApDim;
+    std::vector<double> A((size_t)N * N), R((size_t)N * N, 0.0), tmp((size_t)N * N);
+    for (int i = 0; i < N; i++) {
+        double s[N] = {};
+        s[i] = 1.0;
+        (void)ap_step_linear(q, s, 0.0);
+        for (int r = 0; r < N; r++) A[(size_t)r * N + i] = s[r];
+    }
+    for (int i = 0; i < N; i++) R[(size_t)i * N + i] = 1.0;
+    auto mul = [&](const std::vector<double> &X, const std::vector<double> &Y, std::vector<double> &Z) {
+        for (int r = 0; r < N; r++)
+            for (int c = 0; c < N; c++) {
+                long double acc = 0.0L;
+                for (int k = 0; k < N; k++) acc += (long double)X[(size_t)r * N + k] * Y[(size_t)k * N + c];
+                Z[(size_t)r * N + c] = (double)acc;
+            }
+    };
+    for (int e = L; e > 0; e >>= 1) {
+        if (e & 1) { mul(R, A, tmp); R.swap(tmp); }
+        if (e > 1) { mul(A, A, tmp); A.swap(tmp); }
+    }
+    std::copy(R.begin(), R.end(), T);
+}
+
+// Parameters, carry matrices and flushes of the three stages, and the tile length of this call (before anything is enqueued)
+int Engine::refresh_ap(const ChainCall &k)
+{
+    if (!ap_prm) {
+        for (ChanCfg &c : cfg) { c.sp_flush = false; for (bool &f : c.mp_flush) f = false; }
+        return QH_OK;
+    }
+    const int nap = k.mixed ? n_ap[0] + n_ap[1] : 0;
+    int L = ap_L;
+    if (nap) {
+        // tiles short enough for about four wavefronts of 64 tiles per SIMD (1024 SIMDs), 256 .. 8192 samples
+        L = 256;
+        while (L < 8192 && (long long)nap * k.n_mid / L > 4LL * 64 * 1024) L *= 2;
+        const long long ntile = (k.n_mid + L - 1) / L;
+        if (int rc = grow(ap_ends, ap_ends_cap, ntile, (long long)kApW * nch)) return rc;
+    }
+    const double mtau = std::exp(-1.0 / ((double)dsp_rate * 0.02));       // calc_cbl, cblock.c:29-36 (tau 0.02, RXA.c:411)
+    auto bq = [&](double f, double bw, double g) {
+        const SpeakDesign d = design_speak(f, bw, g, (double)dsp_rate);
+        return ApBiquad{ d.a0, d.a1, d.a2, d.b1, d.b2, d.fgain };
+    };
+    bool up = false;
+    const ApParam *last_q = nullptr;
+    const double *last_T = nullptr;
+    for (int ch = 0; ch < nch; ch++) {
+        ChanCfg &c = cfg[(size_t)ch];
+        if (c.sp_flush || c.mp_flush[0] || c.mp_flush[1]) {            // flush_speak: that cascade's x / y history, I and Q
+            for (int comp = 0; comp < 2; comp++) {
+                double *st = ap_state + (size_t)ch * kApW + (size_t)comp * kApDim;
+                if (c.sp_flush) QH_HIP(hipMemsetAsync(st + kApSpeakAt, 0, kApCascade * sizeof(double), stream));
+                for (int p = 0; p < kApPeaks; p++)
+                    if (c.mp_flush[p]) QH_HIP(hipMemsetAsync(st + kApPeakAt + kApCascade * p, 0, kApCascade * sizeof(double), stream));
+            }
+            c.sp_flush = false;
+            for (bool &f : c.mp_flush) f = false;
+        }
+        if (!c.ap_dirty && !(nap && L != ap_L && c.ap_on())) continue;
+        ApParam &q = ap_prm_h[(size_t)ch];
+        q = ApParam{};
+        q.sp = bq(c.sp_f, c.sp_bw, c.sp_gain);
+        for (int p = 0; p < kApPeaks; p++) q.pk[p] = bq(c.mp_f[p], c.mp_bw[p], c.mp_gain[p]);
+        q.mtau = mtau;
+        q.flags = (c.cbl_run ? AP_CBL : 0) | (c.sp_run ? AP_SPEAK : 0) | (c.mp_run ? AP_MPEAK : 0);
+        for (int p = 0; p < kApPeaks; p++)
+            if (c.mp_run && c.mp_enable[p] && p < c.mp_npeaks) q.flags |= AP_PEAK0 << p;
+        double *T = ap_M_h.data() + (size_t)ch * kApDim * kApDim;
+        if (c.ap_on() && nap) {
+            if (last_q && std::memcmp(last_q, &q, sizeof(q)) == 0) std::copy(last_T, last_T + kApDim * kApDim, T);
+            else ap_transition(q, L, T);
+            last_q = &q; last_T = T;
+            QH_HIP(hipMemcpyAsync(ap_M + (size_t)ch * kApDim * kApDim, T, (size_t)kApDim * kApDim * sizeof(double), hipMemcpyHostToDevice, stream));
+        }
+        QH_HIP(hipMemcpyAsync(ap_prm + ch, &q, sizeof(q), hipMemcpyHostToDevice, stream));
+        c.ap_dirty = false;
+        up = true;
+    }
+    if (up) QH_HIP(hipStreamSynchronize(stream));
+    ap_L = L;
+    return QH_OK;
+}
+
+// the three stages of the listed channels, in place on the rows that hold them behind bp1 (cur / other)
+void Engine::run_audio_peak(const ChainCall &k)
+{
+    if (!ap_prm || (!n_ap[0] && !n_ap[1])) return;
+    const int n = (int)k.n_mid, L = ap_L;
+    const long long ntile = (k.n_mid + L - 1) / L, estride = ap_ends_cap * kApW;
+    const unsigned ngroups = (unsigned)((ntile + 63) / 64);
+    for (int b = 0; b < 2; b++) {
+        if (!n_ap[b]) continue;
+        double2 *rows = b ? k.other : k.cur;
+        if (ntile > 1)
+            hipLaunchKernelGGL(audio_peak_pass_kernel<0>, dim3(ngroups, (unsigned)n_ap[b]), dim3(64), 0, stream, rows, buf_cap, n,
+                               (const int *)list_ap[b], (const ApParam *)ap_prm, ap_state, ap_ends, estride, L);
+        hipLaunchKernelGGL(audio_peak_carry_kernel, dim3((unsigned)n_ap[b]), dim3(64), 0, stream, n, L, (const int *)list_ap[b],
+                           (const double *)ap_M, (const double *)ap_state, ap_ends, estride);
+        hipLaunchKernelGGL(audio_peak_pass_kernel<1>, dim3(ngroups, (unsigned)n_ap[b]), dim3(64), 0, stream, rows, buf_cap, n,
+                           (const int *)list_ap[b], (const ApParam *)ap_prm, ap_state, ap_ends, estride, L);
+    }
+}
+
 // xwcpagc mode 0 where a position-1 stage follows it, xanf / xanr / xemnr / bp1 at position 1, the agc meter, then xwcpagc mode 0 +
 // xpanel in the output pass, xamsq and the audio frames
 void Engine::run_output(const ChainCall &k)
@@ -2692,6 +2848,7 @@ void Engine::run_output(const ChainCall &k)
         if (n_bp1) hipLaunchKernelGGL(meter_kernel, dim3((unsigned)n_bp1), dim3(64), 0, stream, k.other, buf_cap, k.nblk, dsp_size,
                                       m_agc, m_prm, list_bp1, (const double *)m_g2);
     }
+    run_audio_peak(k);                  // xcbl, xspeak, xmpeak (RXA.c:591-593)
     tick(2);
     // xwcpagc mode 0 + xpanel, narrowed in the store when the audio frames are fused -- unless every channel's last stage has written
     // the caller's buffer
@@ -3211,6 +3368,47 @@ int qh_rxa_SetRXAAGCFixed(qh_rxa *h, int ch, double db)
     FOR_CH(h, ch, { c.agc_fixed = std::pow(10.0, db / 20.0); c.epi_dirty = true; c.lms[0].dirty = c.lms[1].dirty = true; });
 }
 
+// xcbl / xspeak / xmpeak.  Run flags, npeaks and the enables do not flush (cblock.c:120-126, iir.c:322-330, :490-515); the design
+// setters recompute and zero their cascade -- speak's, or that one peak's (calc_speak ends in flush_speak, iir.c:216, :332-360, :517-548).
+// npeaks outside [0, 2] and fil outside [0, 2) would index past the reference's two-peak arrays: refused, nothing changes.
+static void ap_run_set(qh_rxa *h, ChanCfg &c, int &flag, int run)
+{
+    run = run ? 1 : 0;
+    if (flag == run) return;
+    flag = run;
+    c.ap_dirty = true; c.epi_dirty = true;          // fix_before() follows ap_on()
+    h->e.lists_dirty = true;
+}
+int qh_rxa_SetRXACBLRun(qh_rxa *h, int ch, int run) { FOR_CH(h, ch, { ap_run_set(h, c, c.cbl_run, run); }); }
+int qh_rxa_SetRXASPCWRun(qh_rxa *h, int ch, int run) { FOR_CH(h, ch, { ap_run_set(h, c, c.sp_run, run); }); }
+int qh_rxa_SetRXASPCWFreq(qh_rxa *h, int ch, double f) { FOR_CH(h, ch, { c.sp_f = f < 200.0 ? 200.0 : f; c.ap_dirty = true; c.sp_flush = true; }); }
+int qh_rxa_SetRXASPCWBandwidth(qh_rxa *h, int ch, double bw) { FOR_CH(h, ch, { c.sp_bw = bw; c.ap_dirty = true; c.sp_flush = true; }); }
+int qh_rxa_SetRXASPCWGain(qh_rxa *h, int ch, double g) { FOR_CH(h, ch, { c.sp_gain = g; c.ap_dirty = true; c.sp_flush = true; }); }
+int qh_rxa_SetRXAmpeakRun(qh_rxa *h, int ch, int run) { FOR_CH(h, ch, { ap_run_set(h, c, c.mp_run, run); }); }
+int qh_rxa_SetRXAmpeakNpeaks(qh_rxa *h, int ch, int npeaks)
+{
+    if (npeaks < 0 || npeaks > kApPeaks) return set_error(QH_ERR_INVALID, "SetRXAmpeakNpeaks: npeaks %d outside [0, %d]", npeaks, kApPeaks);
+    FOR_CH(h, ch, { if (c.mp_npeaks != npeaks) { c.mp_npeaks = npeaks; c.ap_dirty = true; } });
+}
+int qh_rxa_SetRXAmpeakFilEnable(qh_rxa *h, int ch, int fil, int enable)
+{
+    if (fil < 0 || fil >= kApPeaks) return set_error(QH_ERR_INVALID, "SetRXAmpeakFilEnable: fil %d outside [0, %d)", fil, kApPeaks);
+    FOR_CH(h, ch, { enable = enable ? 1 : 0; if (c.mp_enable[fil] != enable) { c.mp_enable[fil] = enable; c.ap_dirty = true; } });
+}
+static int mpeak_design(qh_rxa *h, int ch, int fil, int what, double v)
+{
+    if (fil < 0 || fil >= kApPeaks) return set_error(QH_ERR_INVALID, "SetRXAmpeakFil*: fil %d outside [0, %d)", fil, kApPeaks);
+    FOR_CH(h, ch, {
+        if (what == 0) c.mp_f[fil] = v < 200.0 ? 200.0 : v;
+        else if (what == 1) c.mp_bw[fil] = v;
+        else c.mp_gain[fil] = v;
+        c.ap_dirty = true; c.mp_flush[fil] = true;
+    });
+}
+int qh_rxa_SetRXAmpeakFilFreq(qh_rxa *h, int ch, int fil, double f) { return mpeak_design(h, ch, fil, 0, f); }
+int qh_rxa_SetRXAmpeakFilBw(qh_rxa *h, int ch, int fil, double bw) { return mpeak_design(h, ch, fil, 1, bw); }
+int qh_rxa_SetRXAmpeakFilGain(qh_rxa *h, int ch, int fil, double g) { return mpeak_design(h, ch, fil, 2, g); }
+
 int qh_rxa_SetRXAPanelGain1(qh_rxa *h, int ch, double g) { FOR_CH(h, ch, { c.gain1 = g; c.epi_dirty = true; }); }
 int qh_rxa_SetRXAPanelGain2(qh_rxa *h, int ch, double gI, double gQ) { FOR_CH(h, ch, { c.gain2I = gI; c.gain2Q = gQ; c.epi_dirty = true; }); }
 int qh_rxa_SetRXAPanelSelect(qh_rxa *h, int ch, int s) { FOR_CH(h, ch, { c.inselect = s; c.epi_dirty = true; }); }
@@ -3412,6 +3610,7 @@ int qh_rxa_flush(qh_rxa *h)
     }
     for (ChanCfg &c : e.cfg) { c.lms[0].flush = c.lms[1].flush = true; c.emnr_flush = true; c.snba_flush = true; c.snb_flush = true; }    // flush_anf / flush_anr / flush_emnr, RXA.c:541-543
     if (e.amsq_state) QH_HIP(hipMemsetAsync(e.amsq_state, 0, (size_t)e.nch * sizeof(AmsqState), e.stream));     // flush_amsq
+    if (e.ap_state) QH_HIP(hipMemsetAsync(e.ap_state, 0, (size_t)e.nch * kApW * sizeof(double), e.stream));    // flush_cbl / _speak / _mpeak, RXA.c:553-555
     if (e.demod_alloc) {                        // flush_amd / flush_fmd / flush_snotch
         QH_HIP(hipMemsetAsync(e.am_state, 0, (size_t)e.nch * sizeof(AmState), e.stream));
         QH_HIP(hipMemsetAsync(e.pll_state, 0, (size_t)e.nch * sizeof(PllState), e.stream));

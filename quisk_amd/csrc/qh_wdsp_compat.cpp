@@ -690,6 +690,18 @@ void SetRXAEMNRtrainT2(int channel, double v) { WDSP_SETTER(qh_rxa_SetRXAEMNRtra
 void SetRXAAMSQRun(int channel, int run) { WDSP_SETTER(qh_rxa_SetRXAAMSQRun(L.c->eng, 0, run)); }
 void SetRXAAMSQThreshold(int channel, double threshold) { WDSP_SETTER(qh_rxa_SetRXAAMSQThreshold(L.c->eng, 0, threshold)); }
 void SetRXAAMSQMaxTail(int channel, double tail) { WDSP_SETTER(qh_rxa_SetRXAAMSQMaxTail(L.c->eng, 0, tail)); }
+// the carrier block and the audio peak filters, wdsp/cblock.c:120-126, iir.c:322-360, :490-548
+void SetRXACBLRun(int channel, int setit) { WDSP_SETTER(qh_rxa_SetRXACBLRun(L.c->eng, 0, setit)); }
+void SetRXASPCWRun(int channel, int run) { WDSP_SETTER(qh_rxa_SetRXASPCWRun(L.c->eng, 0, run)); }
+void SetRXASPCWFreq(int channel, double freq) { WDSP_SETTER(qh_rxa_SetRXASPCWFreq(L.c->eng, 0, freq)); }
+void SetRXASPCWBandwidth(int channel, double bw) { WDSP_SETTER(qh_rxa_SetRXASPCWBandwidth(L.c->eng, 0, bw)); }
+void SetRXASPCWGain(int channel, double gain) { WDSP_SETTER(qh_rxa_SetRXASPCWGain(L.c->eng, 0, gain)); }
+void SetRXAmpeakRun(int channel, int run) { WDSP_SETTER(qh_rxa_SetRXAmpeakRun(L.c->eng, 0, run)); }
+void SetRXAmpeakNpeaks(int channel, int npeaks) { WDSP_SETTER(qh_rxa_SetRXAmpeakNpeaks(L.c->eng, 0, npeaks)); }
+void SetRXAmpeakFilEnable(int channel, int fil, int enable) { WDSP_SETTER(qh_rxa_SetRXAmpeakFilEnable(L.c->eng, 0, fil, enable)); }
+void SetRXAmpeakFilFreq(int channel, int fil, double freq) { WDSP_SETTER(qh_rxa_SetRXAmpeakFilFreq(L.c->eng, 0, fil, freq)); }
+void SetRXAmpeakFilBw(int channel, int fil, double bw) { WDSP_SETTER(qh_rxa_SetRXAmpeakFilBw(L.c->eng, 0, fil, bw)); }
+void SetRXAmpeakFilGain(int channel, int fil, double gain) { WDSP_SETTER(qh_rxa_SetRXAmpeakFilGain(L.c->eng, 0, fil, gain)); }
 // the LMS auto-notch / noise reduction, wdsp/anf.c:175-239, anr.c:175-238
 void SetRXAANFRun(int channel, int v) { WDSP_SETTER(qh_rxa_SetRXAANFRun(L.c->eng, 0, v)); }
 void SetRXAANFTaps(int channel, int v) { WDSP_SETTER(qh_rxa_SetRXAANFTaps(L.c->eng, 0, v)); }

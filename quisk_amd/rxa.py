@@ -19,7 +19,9 @@ _SETTERS = ("SetRXAMode", "RXASetNC", "SetRXAShiftRun", "RXANBPSetRun", "SetRXAB
             "RXANBPSetShiftFrequency", "SetRXAFMLimRun", "SetRXAFMLimGain",
             "SetRXASNBARun", "SetRXASNBAOutputBandwidth", "SetRXASNBAasize", "SetRXASNBAnpasses", "SetRXASNBAk1", "SetRXASNBAk2", "SetRXASNBAbridge", "SetRXASNBApresamps", "SetRXASNBApostsamps", "SetRXASNBApmultmin", "SetRXASNBAovrlp", "SetRXAEMNRRun", "SetRXAEMNRgainMethod", "SetRXAEMNRnpeMethod", "SetRXAEMNRaeRun", "SetRXAEMNRPosition", "SetRXAEMNRaeZetaThresh", "SetRXAEMNRaePsi", "SetRXAEMNRtrainZetaThresh", "SetRXAEMNRtrainT2",
             "SetRXAAMSQRun", "SetRXAAMSQThreshold", "SetRXAAMSQMaxTail", "SetRXAANFRun", "SetRXAANFTaps", "SetRXAANFDelay", "SetRXAANFPosition", "SetRXAANFGain", "SetRXAANFLeakage", "SetRXAANFVals",
-            "SetRXAANRRun", "SetRXAANRTaps", "SetRXAANRDelay", "SetRXAANRPosition", "SetRXAANRGain", "SetRXAANRLeakage", "SetRXAANRVals")
+            "SetRXAANRRun", "SetRXAANRTaps", "SetRXAANRDelay", "SetRXAANRPosition", "SetRXAANRGain", "SetRXAANRLeakage", "SetRXAANRVals",
+            "SetRXACBLRun", "SetRXASPCWRun", "SetRXASPCWFreq", "SetRXASPCWBandwidth", "SetRXASPCWGain", "SetRXAmpeakRun",
+            "SetRXAmpeakNpeaks", "SetRXAmpeakFilEnable", "SetRXAmpeakFilFreq", "SetRXAmpeakFilBw", "SetRXAmpeakFilGain")
 
 
 class AudioFormat(C.Structure):
