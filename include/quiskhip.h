@@ -219,7 +219,9 @@ int qh_rxa_flush(qh_rxa *e);
 int qh_rxa_enable_timing(qh_rxa *e, int enable);
 int qh_rxa_timing(qh_rxa *e, double *ms, int n);
 
-/* Bytes of device memory the engine holds (state, masks, intermediate buffers). */
+/* Bytes of device memory the engine holds: the sum of its own live device allocations (state, masks,
+ * channel lists, intermediate buffers).  The qh_rat resamplers behind it (in_rate or out_rate ratios
+ * the overlap-save stages do not cover) keep their own memory and are not included. */
 long long qh_rxa_device_bytes(const qh_rxa *e);
 
 /* ------------------------------------------------------------------ 2. WDSP drop-in exports */

@@ -23,6 +23,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <map>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -206,7 +207,10 @@ struct Engine {
     int long_stage_alloc(int sid, bool shared_mask);
     int long_buffers();
     int long_masks_upload(int sid, long long row, const std::vector<cd> &h);
-    long long dev_bytes = 0;
+    // Every device buffer the engine owns, by its address, and its size in bytes: alloc() enters it, ~Engine frees it, dev_bytes()
+    // adds them up (the qh_rat resamplers hold their own)
+    std::map<void *, long long> owned;
+    long long dev_bytes() const { long long b = 0; for (const auto &o : owned) b += o.second; return b; }
     // timing
     bool timing = false;
     std::vector<hipEvent_t> ev;
@@ -216,31 +220,32 @@ struct Engine {
 
     // demodulators (allocated on first use)
     bool demod_alloc = false, lists_dirty = true;
-    int *list_buf = nullptr, *list_am = nullptr, *list_sam = nullptr, *list_fm = nullptr, *list_bp1 = nullptr, *list_plain = nullptr;
-    int n_am = 0, n_sam = 0, n_fm = 0, n_bp1 = 0, n_plain = 0, n_rest = 0, n_usb = 0, n_rb = 0;
-    int *list_usb = nullptr, *list_rb = nullptr;       // the non-FM channels without / with a bp1 stage
+    // The channel lists of the mixed-mode chain, one device block for all of them (build_lists): every list has nch slots, the
+    // pair lists 2 nch.  [L_LMS + 3 f + k]: anf (f = 0) / anr (f = 1) at position 0 (k = 0, always in `cur`) or at position 1 with
+    // the data in cur (k = 1: bp1 still to come or not running) or in other (k = 2: bp1 ran at position 0); L_EMNR likewise.
+    // [L_BP1P + p]: bp1 at position p.  [L_FIX + b], [L_AP + b], [L_AGC_CUR / OTHER]: by the buffer (0 cur, 1 other) that holds the
+    // channel at that stage.  [L_SNB + p]: bpsnba at position p.
+    enum ListId {
+        L_AM, L_SAM, L_FM, L_BP1, L_PLAIN, L_AGC_CUR, L_AGC_OTHER, L_LMS, L_BP1P = L_LMS + 6, L_FIX = L_BP1P + 2, L_AMSQ = L_FIX + 2, L_EMNR,
+        L_SNB = L_EMNR + 3, L_SNBA = L_SNB + 2,
+        L_REST,             // the channels that are not FM (the mixed-mode path runs the two kinds on two streams) ...
+        L_USB, L_RB,        // ... those of them without / with a bp1 stage
+        L_LIM, L_AP, L_PAIRS_FM = L_AP + 2, L_PAIRS_AM, L_PAIRS_SAM, L_COUNT
+    };
+    struct ChanList { int *dev = nullptr; int n = 0; };
+    ChanList lists[L_COUNT];
+    int *list_block = nullptr;
     // channel pairs for the real filters behind the detectors (osfir_kernel PAIR): FM de-emphasis (one mask for all), bp1 of the AM
     // and of the SAM channels (partners have the same design; count 0 when a channel of the kind has complex taps)
-    int *pairs_fm = nullptr, *pairs_am = nullptr, *pairs_sam = nullptr;
     int np_fm = 0, np_am = 0, np_sam = 0;
     bool de_real = false;
     bool all_nbp = false;
-    int *list_rest = nullptr;                // the channels that are not FM (the mixed-mode path runs the two kinds on two streams)
-    int n_sam0 = 0;                         // the first n_sam0 entries of list_sam have sbmode 0 (no all-pass chains): time-tiled in long calls
-    // anf / anr: lists per (filter, position), parameters and state per filter; bp1 lists per position
-    // [filter][0] = position 0 (always in `cur`); [filter][1 + b] = position 1 with the data in cur (b = 0: bp1 still to come
-    // or not running) or in other (b = 1: bp1 ran at position 0)
-    int *list_lms[2][3] = { { nullptr, nullptr, nullptr }, { nullptr, nullptr, nullptr } }, n_lms[2][3] = { { 0, 0, 0 }, { 0, 0, 0 } };
-    int *list_bp1p[2] = { nullptr, nullptr }, n_bp1p[2] = { 0, 0 };
+    int n_sam0 = 0;                         // the first n_sam0 entries of lists[L_SAM] have sbmode 0 (no all-pass chains): time-tiled in long calls
     // xwcpagc mode 0 ahead of a position-1 anf / anr / bp1: the fixed gain does not commute with what follows when it
-    // changes, so it is applied where the reference applies it; [b] = which buffer holds the channel at that point
-    int *list_fix[2] = { nullptr, nullptr }, n_fix[2] = { 0, 0 };
+    // changes, so it is applied where the reference applies it (lists[L_FIX + b])
     double *fix_gain = nullptr;
-    // xcbl / xspeak / xmpeak (qh_audio_peak.hpp), made when a channel first runs one of them: lists per buffer ([0] cur: channels
-    // without bp1, [1] other), parameters, state [nch][kApW], the carry matrices T = A^ap_L [nch][kApDim^2] and the tiles' end / start
-    // states [nch][ap_ends_cap][kApW]
-    int *list_ap[2] = { nullptr, nullptr }, n_ap[2] = { 0, 0 };
-    int *ap_lists = nullptr;
+    // xcbl / xspeak / xmpeak (qh_audio_peak.hpp), made when a channel first runs one of them: parameters, state [nch][kApW], the carry
+    // matrices T = A^ap_L [nch][kApDim^2] and the tiles' end / start states [nch][ap_ends_cap][kApW]
     ApParam *ap_prm = nullptr;
     double *ap_state = nullptr, *ap_M = nullptr, *ap_ends = nullptr;
     long long ap_ends_cap = 0;
@@ -248,10 +253,7 @@ struct Engine {
     std::vector<double> ap_M_h;
     std::vector<ApParam> ap_prm_h;
     int ap_alloc();
-    // emnr: lists like the LMS filters' ([0] position 0; [1 + b] position 1 with the data in cur / other)
-    int *list_emnr[3] = { nullptr, nullptr, nullptr }, n_emnr[3] = { 0, 0, 0 };
-    // snba: bpsnba lists per position, the blanker's list, its parameters, taps, state and the Toeplitz-inverse scratch
-    int *list_snb[2] = { nullptr, nullptr }, n_snb[2] = { 0, 0 }, *list_snba = nullptr, n_snba = 0;
+    // snba: the blanker's parameters, taps, state and the Toeplitz-inverse scratch
     SnbaParam snba_prm{};
     double *snba_state = nullptr, *snba_hin = nullptr, *snba_hout = nullptr, *snba_scratch = nullptr;
     SnbaIdx *snba_idx = nullptr;
@@ -270,7 +272,6 @@ struct Engine {
     int *emnr_zeta_true = nullptr;
     bool emnr_tables = false;
     std::vector<double> h_GG, h_GGS, h_zeta; std::vector<int> h_zeta_true; double h_zrange[4] = { 0, 0, 0, 0 };
-    int *list_amsq = nullptr, n_amsq = 0;
     AmsqParam *amsq_prm = nullptr;
     AmsqState *amsq_state = nullptr;
     double *amsq_cup = nullptr, *amsq_cdown = nullptr, *amsq_mag = nullptr;
@@ -329,8 +330,8 @@ struct Engine {
     // Growing, rebuilding or re-uploading a device buffer: captured launch sequences hold its address and launches queued on either
     // stream may still use it, so nothing is freed or rewritten before quiesce() has waited for both streams and dropped the captures.
     int quiesce();
-    // p holds old_n elements (none: 0): free it and allocate new_n in its place; dev_bytes follows.  The caller has quiesced.
-    template <typename T> int realloc_dev(T *&p, long long old_n, long long new_n);
+    // (Re)allocate p for n elements (dev_alloc), zeroed on `stream` when asked.  A buffer p held is freed first: the caller has quiesced.
+    template <typename T> int alloc(T *&p, long long n, bool zero = false);
     // p holds cap units of `unit` elements: when need is more, quiesce and reallocate it for need units
     template <typename T> int grow(T *&p, long long &cap, long long need, long long unit);
     int process_replayed(const double *d_in, long long in_stride, double *d_out, long long out_stride, int nblk);
@@ -342,7 +343,6 @@ struct Engine {
     int *agc_lout = nullptr, *agc_rewin_list = nullptr;
     AgcParam *lim_prm = nullptr;        // FM detector limiter: a wcpAGC of its own (fmd.c:48-72)
     AgcState *lim_state = nullptr;
-    int *list_lim = nullptr, n_lim = 0;
     bool meters_on = false;
     MeterState *m_adc = nullptr, *m_s = nullptr, *m_agc = nullptr;
     MeterParam m_prm{};
@@ -352,15 +352,39 @@ struct Engine {
     long long m_part_cap = 0;               // chunks per channel
     double *m_w = nullptr, *m_g2 = nullptr;
     int meters_alloc();
-    int *list_agc_cur = nullptr, *list_agc_other = nullptr;
-    int n_agc_cur = 0, n_agc_other = 0;
     int agc_last_tiled = 0;             // channels whose xwcpagc took the time tiles in the last call (diagnostics)
     int n_agc_cur_stale = 0, n_agc_other_stale = 0;     // ... of which, at the lists' ends, channels whose attack window moved in mid-stream
 
     ~Engine();
     int init();
     int refresh_params();
+    std::vector<cd> notched(const ChanCfg &c, double f_low, double f_high, double scale) const;
+    int snb_mask(ChanCfg &c, int ch);
+    int put_mask(double2 *mask, int ch, const std::vector<cd> &m);
+    // refresh_demod and its steps
     int refresh_demod();
+    int demod_init();
+    void build_lists(std::vector<int> (&h)[L_COUNT]);
+    int stages_alloc();
+    int refresh_lists();
+    struct Rows { double2 **h; int cur; int len; };     // a fircore's ping-pong delay lines, the half current for them, the row length
+    int follow_rows(std::vector<char> &listed, int ChanCfg::*at, int cur, const std::vector<int> &chans, std::initializer_list<Rows> rows);
+    int zero_rows(double2 *const h[2], double2 *const lh[2], int ch, int n = 1);
+    int prm_agc(ChanCfg &c, int ch);
+    int prm_emnr(ChanCfg &c, int ch);
+    int prm_snba(ChanCfg &c, int ch);
+    int prm_amsq(ChanCfg &c, int ch);
+    int prm_lms(ChanCfg &c, int ch);
+    int prm_lim(ChanCfg &c, int ch);
+    int prm_detect(ChanCfg &c, int ch);
+    int fm_filters(int want_nc);
+    // v -> dev[row] on `stream`, then a wait unless told not to (a caller that does not wait keeps v alive until it does)
+    template <typename T> int put_row(T *dev, long long row, const T &v, bool wait = true)
+    {
+        QH_HIP(hipMemcpyAsync(dev + row, &v, sizeof(T), hipMemcpyHostToDevice, stream));
+        if (wait) QH_HIP(hipStreamSynchronize(stream));
+        return QH_OK;
+    }
     int run_front(const double2 *src, long long src_stride, double2 *dst, long long dst_stride, const EpiParam *ep,
                   long long n_in, long long n_mid, const int *list = nullptr, int nlist = 0, int part = 0);
     const unsigned char *pk_src = nullptr;      // set for the duration of a qh_rxa_process_packed call
@@ -427,28 +451,7 @@ Engine::~Engine()
     drop_graphs();
     if (rsmpout) qh_rat_destroy(rsmpout);
     if (rsmpin) qh_rat_destroy(rsmpin);
-    (void)hipFree(fbuf);
-    (void)hipFree(obuf); (void)hipFree(abuf);
-    for (int i = 0; i < 5; i++) { (void)hipFree(lmask[i]); (void)hipFree(lrow_parts[i]); (void)hipFree(lhist[i][0]); (void)hipFree(lhist[i][1]); }
-    (void)hipFree(lcat); (void)hipFree(ltmp);
-    (void)hipFree(mask_front); (void)hipFree(mask_nbp); (void)hipFree(mask_bp1); (void)hipFree(tw4096); (void)hipFree(tw_inv_front); (void)hipFree(tw8192);
-    (void)hipFree(nco_phase); (void)hipFree(nco_dphase); (void)hipFree(nco_parked); (void)hipFree(nco_step); (void)hipFree(epi);
-    (void)hipFree(lane_rot); (void)hipFree(tile_rot); (void)hipFree(front_taps); (void)hipFree(retune_list); (void)hipFree(retune_law);
-    for (int i = 0; i < 2; i++) { (void)hipFree(hist_front[i]); (void)hipFree(hist_nbp[i]); (void)hipFree(hist_bp1[i]); (void)hipFree(buf[i]); }
-    (void)hipFree(list_buf); (void)hipFree(levelfade); (void)hipFree(am_state); (void)hipFree(am_next); (void)hipFree(sn_next); (void)hipFree(fmdc_next); (void)hipFree(fm_cin); (void)hipFree(fm_pw); (void)hipFree(am_cin); (void)hipFree(am_pw); (void)hipFree(am_last); (void)hipFree(pll_state); (void)hipFree(fm_pll_state); (void)hipFree(fm_again); (void)hipFree(pll_ends); (void)hipFree(pll_nfixed); (void)hipFree(am_tsum);
-    (void)hipFree(sb_phi); (void)hipFree(sb_sum); (void)hipFree(sb_start);
-    (void)hipFree(agc_scr); (void)hipFree(agc_ends); (void)hipFree(agc_fin); (void)hipFree(agc_halo); (void)hipFree(agc_tail); (void)hipFree(agc_nfixed); (void)hipFree(agc_sege); (void)hipFree(agc_tsum);
-    for (double *&q : seg_sum) { (void)hipFree(q); q = nullptr; }
-    (void)hipFree(agc_prm); (void)hipFree(agc_state); (void)hipFree(agc_lring); (void)hipFree(agc_labs); (void)hipFree(agc_lout); (void)hipFree(agc_rewin_list); (void)hipFree(lim_prm); (void)hipFree(lim_state); (void)hipFree(list_lim); (void)hipFree(m_adc); (void)hipFree(m_s); (void)hipFree(m_agc); (void)hipFree(m_part[0]); (void)hipFree(m_part[1]); (void)hipFree(m_w); (void)hipFree(m_g2);
-    (void)hipFree(mask_snb); (void)hipFree(hist_snb[0]); (void)hipFree(hist_snb[1]); (void)hipFree(snba_state); (void)hipFree(snba_hin);
-    (void)hipFree(snba_hout); (void)hipFree(snba_scratch); (void)hipFree(snba_idx); (void)hipFree(snba_tune);
-    (void)hipFree(emnr_chan); (void)hipFree(emnr_scal); (void)hipFree(emnr_state); (void)hipFree(emnr_window); (void)hipFree(emnr_GG);
-    (void)hipFree(emnr_GGS); (void)hipFree(emnr_zeta); (void)hipFree(emnr_zeta_true);
-    (void)hipFree(amsq_prm); (void)hipFree(amsq_state); (void)hipFree(amsq_cup); (void)hipFree(amsq_cdown); (void)hipFree(amsq_mag);
-    (void)hipFree(ap_lists); (void)hipFree(ap_prm); (void)hipFree(ap_state); (void)hipFree(ap_M); (void)hipFree(ap_ends);
-    (void)hipFree(fix_gain); (void)hipFree(lms_prm[0]); (void)hipFree(lms_prm[1]); (void)hipFree(lms_state[0]); (void)hipFree(lms_state[1]);
-    (void)hipFree(sam_prm); (void)hipFree(sn_prm); (void)hipFree(sn_state); (void)hipFree(mask_de); (void)hipFree(mask_aud);
-    for (int i = 0; i < 2; i++) { (void)hipFree(hist_de[i]); (void)hipFree(hist_aud[i]); }
+    for (const auto &o : owned) (void)hipFree(o.first);
     for (auto e : ev) (void)hipEventDestroy(e);
     if (side_stream) (void)hipStreamDestroy(side_stream);
     if (ev_fork) (void)hipEventDestroy(ev_fork);
@@ -471,11 +474,12 @@ int Engine::quiesce()
     return QH_OK;
 }
 
-template <typename T> int Engine::realloc_dev(T *&p, long long old_n, long long new_n)
+template <typename T> int Engine::alloc(T *&p, long long n, bool zero)
 {
-    if (p) { QH_HIP(hipFree(p)); dev_bytes -= old_n * (long long)sizeof(T); p = nullptr; }
-    QH_HIP(dev_alloc(&p, (size_t)new_n));
-    dev_bytes += new_n * (long long)sizeof(T);
+    if (p) { QH_HIP(hipFree(p)); owned.erase(p); p = nullptr; }
+    QH_HIP(dev_alloc(&p, (size_t)n));
+    owned[p] = n * (long long)sizeof(T);
+    if (zero) QH_HIP(hipMemsetAsync(p, 0, (size_t)n * sizeof(T), stream));
     return QH_OK;
 }
 
@@ -483,7 +487,7 @@ template <typename T> int Engine::grow(T *&p, long long &cap, long long need, lo
 {
     if (need <= cap) return QH_OK;
     if (int rc = quiesce()) return rc;
-    if (int rc = realloc_dev(p, cap * unit, need * unit)) return rc;
+    if (int rc = alloc(p, need * unit)) return rc;
     cap = need;
     return QH_OK;
 }
@@ -516,13 +520,11 @@ int Engine::init()
     snba_tune_h.assign((size_t)nch, SnbaTune{ 64, 2, 10, 2, 2, 0, 8.0, 20.0, 0.5 });         // create_snba's arguments, RXA.c:183-202
 
     std::vector<cd> tw = fft_twiddle_table(kNfft);
-    QH_HIP(dev_alloc(&tw4096, tw.size()));
+    if (int rc = alloc(tw4096, (long long)tw.size())) return rc;
     if (int rc = upload(tw4096, tw, stream)) return rc;
-    dev_bytes += tw.size() * sizeof(cd);
     tw = fft_twiddle_table(kBandNfftMax);
-    QH_HIP(dev_alloc(&tw8192, tw.size()));
+    if (int rc = alloc(tw8192, (long long)tw.size())) return rc;
     if (int rc = upload(tw8192, tw, stream)) return rc;
-    dev_bytes += tw.size() * sizeof(cd);
 
     if (D > 1) {
         // calc_resample, wdsp/resample.c:35-72 (L = 1): y[m] = sum_j h[j] x[D*m - j]
@@ -536,44 +538,31 @@ int Engine::init()
         front_L = (((kNfft - front_P) / front_fold) / front_pick) * front_pick;
         if (front_P > kHistFront) return set_error(QH_ERR_UNSUPPORTED, "resampler history %d too long", front_P);
         // the masks are per channel (taps modulated by the channel's shift): front_mask_kernel builds them in refresh_params
-        QH_HIP(dev_alloc(&mask_front, (size_t)nch * kNfft));
-        QH_HIP(dev_alloc(&lane_rot, (size_t)nch * NT));
-        QH_HIP(dev_alloc(&front_taps, (size_t)front_ntaps));
-        QH_HIP(dev_alloc(&retune_list, (size_t)nch));
-        QH_HIP(dev_alloc(&retune_law, (size_t)nch * 2));
+        if (int rc = alloc(mask_front, (long long)nch * kNfft)) return rc;
+        if (int rc = alloc(lane_rot, (long long)nch * NT)) return rc;
+        if (int rc = alloc(front_taps, front_ntaps)) return rc;
+        if (int rc = alloc(retune_list, nch)) return rc;
+        if (int rc = alloc(retune_law, 2LL * nch)) return rc;
         QH_HIP(hipMemcpyAsync(front_taps, rd.h.data(), (size_t)front_ntaps * sizeof(double), hipMemcpyHostToDevice, stream));
         QH_HIP(hipStreamSynchronize(stream));
         QH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&front_mask_kernel<kNfft>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                    (TileFft<kNfft, false, double2>::kLdsBytes)));
         std::vector<cd> twi = fft_twiddle_table(kNfft / front_fold);
-        QH_HIP(dev_alloc(&tw_inv_front, twi.size()));
+        if (int rc = alloc(tw_inv_front, (long long)twi.size())) return rc;
         if (int rc = upload(tw_inv_front, twi, stream)) return rc;
-        dev_bytes += twi.size() * sizeof(cd) + (size_t)nch * (kNfft + NT) * sizeof(double2) + (size_t)front_ntaps * 8 + (size_t)nch * 20;
-        for (int i = 0; i < 2; i++) {
-            QH_HIP(dev_alloc(&hist_front[i], (size_t)nch * kHistFront));
-            QH_HIP(hipMemsetAsync(hist_front[i], 0, (size_t)nch * kHistFront * sizeof(double2), stream));
-            dev_bytes += (size_t)nch * kHistFront * sizeof(double2);
-        }
+        for (double2 *&h : hist_front) if (int rc = alloc(h, (long long)nch * kHistFront, true)) return rc;
     }
-    QH_HIP(dev_alloc(&mask_nbp, (size_t)nch * kBandNfftMax));
-    QH_HIP(dev_alloc(&mask_bp1, (size_t)nch * kBandNfftMax));
-    dev_bytes += 2ll * nch * kBandNfftMax * sizeof(double2);
+    if (int rc = alloc(mask_nbp, (long long)nch * kBandNfftMax)) return rc;
+    if (int rc = alloc(mask_bp1, (long long)nch * kBandNfftMax)) return rc;
     for (int i = 0; i < 2; i++) {
-        QH_HIP(dev_alloc(&hist_nbp[i], (size_t)nch * kHistBand));
-        QH_HIP(dev_alloc(&hist_bp1[i], (size_t)nch * kHistBand));
-        QH_HIP(hipMemsetAsync(hist_nbp[i], 0, (size_t)nch * kHistBand * sizeof(double2), stream));
-        QH_HIP(hipMemsetAsync(hist_bp1[i], 0, (size_t)nch * kHistBand * sizeof(double2), stream));
-        dev_bytes += 2ll * nch * kHistBand * sizeof(double2);
+        if (int rc = alloc(hist_nbp[i], (long long)nch * kHistBand, true)) return rc;
+        if (int rc = alloc(hist_bp1[i], (long long)nch * kHistBand, true)) return rc;
     }
-    QH_HIP(dev_alloc(&nco_phase, (size_t)nch));
-    QH_HIP(dev_alloc(&nco_dphase, (size_t)nch));
-    QH_HIP(dev_alloc(&nco_parked, (size_t)nch));
-    QH_HIP(hipMemsetAsync(nco_parked, 0, (size_t)nch * sizeof(unsigned long long), stream));
-    QH_HIP(hipMemsetAsync(nco_dphase, 0, (size_t)nch * sizeof(unsigned long long), stream));
-    QH_HIP(dev_alloc(&nco_step, (size_t)nch));
-    QH_HIP(dev_alloc(&epi, (size_t)nch));
-    QH_HIP(hipMemsetAsync(nco_phase, 0, (size_t)nch * sizeof(unsigned long long), stream));
-    dev_bytes += (size_t)nch * (16 + 16 + sizeof(EpiParam));
+    if (int rc = alloc(nco_phase, nch, true)) return rc;
+    if (int rc = alloc(nco_dphase, nch, true)) return rc;
+    if (int rc = alloc(nco_parked, nch, true)) return rc;
+    if (int rc = alloc(nco_step, nch)) return rc;
+    if (int rc = alloc(epi, nch)) return rc;
 
     // dynamic LDS of the overlap-save kernels
 #define QH_SET_LDS(D, ...) QH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&osfir_kernel<double, 4096, D, __VA_ARGS__>), \
@@ -646,9 +635,7 @@ int Engine::refresh_params()
                 c.shift_on_device = c.shift_run ? 1 : 0;
             }
             // calc_shift, wdsp/shift.c:29-34: delta = 2*pi*shift/rate per input sample
-            unsigned long long d = c.shift_run ? turns_fx(c.shift_freq, (double)in_rate) : 0ull;
-            QH_HIP(hipMemcpyAsync(nco_dphase + ch, &d, sizeof(d), hipMemcpyHostToDevice, stream));
-            QH_HIP(hipStreamSynchronize(stream));
+            if (int rc = put_row(nco_dphase, ch, c.shift_run ? turns_fx(c.shift_freq, (double)in_rate) : 0ull)) return rc;
             c.nco_dirty = false;
         }
         if (c.epi_dirty) {
@@ -656,8 +643,8 @@ int Engine::refresh_params()
             // (with a position-1 anf / anr / bp1 behind it the gain is applied at the AGC's own spot instead: fix_before)
             const double g = (c.agc_run && c.agc_mode == 0 && !c.fix_before()) ? c.agc_fixed : 1.0;
             const double g2 = g * g;            // the agc meter reads |g z|^2 off the signal ahead of the output matrix
-            if (m_g2) QH_HIP(hipMemcpyAsync(m_g2 + ch, &g2, sizeof(double), hipMemcpyHostToDevice, stream));
-            if (fix_gain) QH_HIP(hipMemcpyAsync(fix_gain + ch, &c.agc_fixed, sizeof(double), hipMemcpyHostToDevice, stream));
+            if (m_g2) if (int rc = put_row(m_g2, ch, g2, false)) return rc;
+            if (fix_gain) if (int rc = put_row(fix_gain, ch, c.agc_fixed, false)) return rc;
             const double gI = c.gain1 * c.gain2I, gQ = c.gain1 * c.gain2Q;
             const double sI = (double)(c.inselect >> 1), sQ = (double)(c.inselect & 1);
             EpiParam e;
@@ -668,47 +655,12 @@ int Engine::refresh_params()
             case 2: e.a = 0; e.b = gI * sQ * g; e.c = 0; e.d = gQ * sQ * g; break;
             case 3: e.a = 0; e.b = gI * sQ * g; e.c = gQ * sI * g; e.d = 0; break;
             }
-            QH_HIP(hipMemcpyAsync(epi + ch, &e, sizeof(e), hipMemcpyHostToDevice, stream));
-            QH_HIP(hipStreamSynchronize(stream));
+            if (int rc = put_row(epi, ch, e)) return rc;
             c.epi_dirty = false;
         }
         if (c.nbp_dirty) c.snb_dirty = true;        // bpsnba's nbp shares nc, window, auto-increase, mp and the notch database with nbp0
-        if (c.snb_dirty && c.snba_run && mask_snb) {
-            // recalc_bpsnba_filter (snb.c:807-822) with RXAbpsnbaCheck's frequencies (RXA.c:829-881): 250..5700 Hz on the mode's side
-            double f_low = 0.0, f_high = 0.0;
-            int run_notches = 0;
-            switch (c.mode) {
-            case QH_LSB: case QH_CWL: case QH_DIGL: f_low = -5700.0; f_high = -250.0; run_notches = c.fnfrun; break;
-            case QH_USB: case QH_CWU: case QH_DIGU: f_low = 250.0; f_high = 5700.0; run_notches = c.fnfrun; break;
-            case QH_AM: case QH_SAM: case QH_DSB: case QH_FM: f_low = 250.0; f_high = 5700.0; break;
-            default: break;
-            }
-            std::vector<cd> h;
-            const double scale = 1.0 / (double)(2 * dsp_size);
-            if (long_parts[4] > 1) if (int rc = long_stage_alloc(4, false)) return rc;
-            if (run_notches) {
-                const double offset = c.ndb_tunefreq + c.ndb_shift;
-                const double minwidth = (c.nbp_wintype == 1 ? 2200.0 : 1600.0) / (c.nbp_nc / 256) * ((double)dsp_rate / 48000);
-                std::vector<std::pair<double, double>> bands = make_nbp(c.notches, minwidth, c.autoincr, f_low + offset, f_high + offset, nullptr);
-                for (auto &b : bands) { b.first -= offset; b.second -= offset; }
-                h = fir_mbandpass(c.nbp_nc, bands, (double)dsp_rate, scale, c.nbp_wintype);
-            } else
-                h = fir_bandpass(c.nbp_nc, f_low, f_high, (double)dsp_rate, c.nbp_wintype, 1, scale);
-            if (c.mp) h = mp_imp(h, 16, 0);
-            for (auto &v : h) v *= (double)(2 * dsp_size);
-            if (long_parts[4] > 1) if (int rc = long_masks_upload(4, ch, h)) return rc;
-            if ((int)h.size() > kLongPart) h.resize((size_t)kLongPart);      // (the one-tile mask is not used then)
-            const std::vector<cd> m = band_mask(h);
-            QH_HIP(hipMemcpyAsync(mask_snb + (size_t)ch * kBandNfftMax, m.data(), (size_t)bnfft * sizeof(cd), hipMemcpyHostToDevice, stream));
-            QH_HIP(hipStreamSynchronize(stream));
-            c.snb_dirty = false;
-        }
-        if (c.snb_flush && hist_snb[0]) {           // setNc_fircore zeroes the delay line
-            for (int i = 0; i < 2; i++) {
-                QH_HIP(hipMemsetAsync(hist_snb[i] + (size_t)ch * kHistBand, 0, kHistBand * sizeof(double2), stream));
-                if (lhist[4][i]) QH_HIP(hipMemsetAsync(lhist[4][i] + (size_t)ch * kLongHist, 0, kLongHist * sizeof(double2), stream));
-            }
-        }
+        if (c.snb_dirty && c.snba_run && mask_snb) if (int rc = snb_mask(c, ch)) return rc;
+        if (c.snb_flush && hist_snb[0]) if (int rc = zero_rows(hist_snb, lhist[4], ch)) return rc;         // setNc_fircore zeroes the delay line
         c.snb_flush = false;
         if (c.nbp_dirty) {
             // calc_nbp_impulse without notches, wdsp/nbp.c:234-238; identity when the filter is off
@@ -717,15 +669,9 @@ int Engine::refresh_params()
                         last_nbp_cfg->nbp_fhigh == c.nbp_fhigh && last_nbp_cfg->nbp_gain == c.nbp_gain && last_nbp_cfg->mp == c.mp;
             if (!same) {
                 std::vector<cd> h;
-                if (c.nbp_run && c.fnfrun) {
-                    // calc_nbp_impulse with the notches, wdsp/nbp.c:221-232: bands in absolute frequency, filter in baseband
-                    const double offset = c.ndb_tunefreq + c.ndb_shift;
-                    const double minwidth = (c.nbp_wintype == 1 ? 2200.0 : 1600.0) / (c.nbp_nc / 256) * ((double)dsp_rate / 48000);
-                    std::vector<std::pair<double, double>> bands =
-                        make_nbp(c.notches, minwidth, c.autoincr, c.nbp_flow + offset, c.nbp_fhigh + offset, nullptr);
-                    for (auto &b : bands) { b.first -= offset; b.second -= offset; }
-                    h = fir_mbandpass(c.nbp_nc, bands, (double)dsp_rate, c.nbp_gain / (double)(2 * dsp_size), c.nbp_wintype);
-                } else if (c.nbp_run)
+                if (c.nbp_run && c.fnfrun)
+                    h = notched(c, c.nbp_flow, c.nbp_fhigh, c.nbp_gain / (double)(2 * dsp_size));
+                else if (c.nbp_run)
                     h = fir_bandpass(c.nbp_nc, c.nbp_flow, c.nbp_fhigh, (double)dsp_rate, c.nbp_wintype, 1,
                                      c.nbp_gain / (double)(2 * dsp_size));
                 else
@@ -739,8 +685,7 @@ int Engine::refresh_params()
                 last_nbp_cfg = &c;
             }
             if (long_parts[0] > 1) if (int rc = long_masks_upload(0, ch, last_nbp_h)) return rc;
-            QH_HIP(hipMemcpyAsync(mask_nbp + (size_t)ch * kBandNfftMax, last_nbp.data(), (size_t)bnfft * sizeof(cd), hipMemcpyHostToDevice, stream));
-            QH_HIP(hipStreamSynchronize(stream));
+            if (int rc = put_mask(mask_nbp, ch, last_nbp)) return rc;
             c.nbp_dirty = false;
         }
         if (c.bp1_dirty) {
@@ -763,23 +708,16 @@ int Engine::refresh_params()
                 last_bp1_cfg = &c;
             }
             if (long_parts[1] > 1) if (int rc = long_masks_upload(1, ch, last_bp1_h)) return rc;
-            QH_HIP(hipMemcpyAsync(mask_bp1 + (size_t)ch * kBandNfftMax, last_bp1.data(), (size_t)bnfft * sizeof(cd), hipMemcpyHostToDevice, stream));
-            QH_HIP(hipStreamSynchronize(stream));
+            if (int rc = put_mask(mask_bp1, ch, last_bp1)) return rc;
             c.bp1_dirty = false;
             lists_dirty = true;             // the channel pairs of the real bp1 filters follow the designs
         }
-        if (c.nbp_flush) {      // setNc_fircore re-plans and so zeroes the delay line, wdsp/firmin.c:454-466
-            for (int i = 0; i < 2; i++) {
-                QH_HIP(hipMemsetAsync(hist_nbp[i] + (size_t)ch * kHistBand, 0, kHistBand * sizeof(double2), stream));
-                if (lhist[0][i]) QH_HIP(hipMemsetAsync(lhist[0][i] + (size_t)ch * kLongHist, 0, kLongHist * sizeof(double2), stream));
-            }
+        if (c.nbp_flush) {      // setNc_fircore re-plans and so zeroes the delay line
+            if (int rc = zero_rows(hist_nbp, lhist[0], ch)) return rc;
             c.nbp_flush = false;
         }
         if (c.bp1_flush) {      // flush_bandpass on off->on (RXA.c:825) and setNc_fircore
-            for (int i = 0; i < 2; i++) {
-                QH_HIP(hipMemsetAsync(hist_bp1[i] + (size_t)ch * kHistBand, 0, kHistBand * sizeof(double2), stream));
-                if (lhist[1][i]) QH_HIP(hipMemsetAsync(lhist[1][i] + (size_t)ch * kLongHist, 0, kLongHist * sizeof(double2), stream));
-            }
+            if (int rc = zero_rows(hist_bp1, lhist[1], ch)) return rc;
             c.bp1_flush = false;
         }
     }
@@ -790,6 +728,47 @@ int Engine::refresh_params()
     return QH_OK;
 }
 
+// calc_nbp_impulse with the notches, wdsp/nbp.c:221-232: bands in absolute frequency, filter in baseband
+std::vector<cd> Engine::notched(const ChanCfg &c, double f_low, double f_high, double scale) const
+{
+    const double offset = c.ndb_tunefreq + c.ndb_shift;
+    const double minwidth = (c.nbp_wintype == 1 ? 2200.0 : 1600.0) / (c.nbp_nc / 256) * ((double)dsp_rate / 48000);
+    std::vector<std::pair<double, double>> bands = make_nbp(c.notches, minwidth, c.autoincr, f_low + offset, f_high + offset, nullptr);
+    for (auto &b : bands) { b.first -= offset; b.second -= offset; }
+    return fir_mbandpass(c.nbp_nc, bands, (double)dsp_rate, scale, c.nbp_wintype);
+}
+
+// recalc_bpsnba_filter (snb.c:807-822) with RXAbpsnbaCheck's frequencies (RXA.c:829-881): 250..5700 Hz on the mode's side
+int Engine::snb_mask(ChanCfg &c, int ch)
+{
+    double f_low = 0.0, f_high = 0.0;
+    int run_notches = 0;
+    switch (c.mode) {
+    case QH_LSB: case QH_CWL: case QH_DIGL: f_low = -5700.0; f_high = -250.0; run_notches = c.fnfrun; break;
+    case QH_USB: case QH_CWU: case QH_DIGU: f_low = 250.0; f_high = 5700.0; run_notches = c.fnfrun; break;
+    case QH_AM: case QH_SAM: case QH_DSB: case QH_FM: f_low = 250.0; f_high = 5700.0; break;
+    default: break;
+    }
+    const double scale = 1.0 / (double)(2 * dsp_size);
+    if (long_parts[4] > 1) if (int rc = long_stage_alloc(4, false)) return rc;
+    std::vector<cd> h = run_notches ? notched(c, f_low, f_high, scale) : fir_bandpass(c.nbp_nc, f_low, f_high, (double)dsp_rate, c.nbp_wintype, 1, scale);
+    if (c.mp) h = mp_imp(h, 16, 0);
+    for (auto &v : h) v *= (double)(2 * dsp_size);
+    if (long_parts[4] > 1) if (int rc = long_masks_upload(4, ch, h)) return rc;
+    if ((int)h.size() > kLongPart) h.resize((size_t)kLongPart);      // (the one-tile mask is not used then)
+    if (int rc = put_mask(mask_snb, ch, band_mask(h))) return rc;
+    c.snb_dirty = false;
+    return QH_OK;
+}
+
+// a channel's row of a fircore stage's masks (the bnfft bins of the tile in use)
+int Engine::put_mask(double2 *mask, int ch, const std::vector<cd> &m)
+{
+    QH_HIP(hipMemcpyAsync(mask + (size_t)ch * kBandNfftMax, m.data(), (size_t)bnfft * sizeof(cd), hipMemcpyHostToDevice, stream));
+    QH_HIP(hipStreamSynchronize(stream));
+    return QH_OK;
+}
+
 // create_meter x3 (RXA.c:69-82,142-155,361-374): tau 0.1 s for average and peak decay; flush_meter -> -400 dB
 int Engine::meters_alloc()
 {
@@ -797,7 +776,7 @@ int Engine::meters_alloc()
     const double rate = (double)dsp_rate;
     std::vector<MeterState> init((size_t)nch, MeterState{ 0.0, 0.0, -400.0, -400.0 });
     for (MeterState **pm : { &m_adc, &m_s, &m_agc }) {
-        QH_HIP(dev_alloc(pm, (size_t)nch));
+        if (int rc = alloc(*pm, nch)) return rc;
         QH_HIP(hipMemcpyAsync(*pm, init.data(), (size_t)nch * sizeof(MeterState), hipMemcpyHostToDevice, stream));
     }
     m_prm.mult_average = std::exp(-1.0 / (rate * 0.100));
@@ -808,316 +787,479 @@ int Engine::meters_alloc()
         const ChanCfg &c = cfg[(size_t)ch];
         g2[(size_t)ch] = (c.agc_run && c.agc_mode == 0 && !c.fix_before()) ? c.agc_fixed * c.agc_fixed : 1.0;
     }
-    QH_HIP(dev_alloc(&m_w, (size_t)64));
-    QH_HIP(dev_alloc(&m_g2, (size_t)nch));
+    if (int rc = alloc(m_w, 64)) return rc;
+    if (int rc = alloc(m_g2, nch)) return rc;
     QH_HIP(hipMemcpyAsync(m_w, w.data(), 64 * sizeof(double), hipMemcpyHostToDevice, stream));
     QH_HIP(hipMemcpyAsync(m_g2, g2.data(), g2.size() * sizeof(double), hipMemcpyHostToDevice, stream));
     QH_HIP(hipStreamSynchronize(stream));
-    dev_bytes += (long long)nch * (3 * sizeof(MeterState) + 8) + 512;
     return QH_OK;
 }
 
-// Demodulator state, channel lists and FM filters (only engines that run AM/SAM/FM channels get here).
-int Engine::refresh_demod()
+// The one-time part of refresh_demod: the demodulators' state and the loop constants of the AM / SAM and FM detectors
+int Engine::demod_init()
 {
     const double rate = (double)dsp_rate;
-    if (!demod_alloc) {
-        QH_HIP(dev_alloc(&list_buf, (size_t)nch * 33));
-        list_rest = list_buf + 24 * nch; list_usb = list_buf + 25 * nch; list_rb = list_buf + 26 * nch;
-        pairs_fm = list_buf + 27 * nch; pairs_am = list_buf + 29 * nch; pairs_sam = list_buf + 31 * nch;
-        list_amsq = list_buf + 17 * nch;
-        for (int k = 0; k < 3; k++) list_emnr[k] = list_buf + (18 + k) * nch;
-        for (int f = 0; f < 2; f++) for (int k = 0; k < 3; k++) list_lms[f][k] = list_buf + (7 + 3 * f + k) * nch;
-        list_snb[0] = list_buf + 21 * nch; list_snb[1] = list_buf + 22 * nch; list_snba = list_buf + 23 * nch;
-        list_bp1p[0] = list_buf + 13 * nch; list_bp1p[1] = list_buf + 14 * nch;
-        list_fix[0] = list_buf + 15 * nch; list_fix[1] = list_buf + 16 * nch;
-        QH_HIP(dev_alloc(&fix_gain, (size_t)nch));
-        list_am = list_buf; list_sam = list_buf + nch; list_fm = list_buf + 2 * nch; list_bp1 = list_buf + 3 * nch;
-        list_plain = list_buf + 4 * nch; list_agc_cur = list_buf + 5 * nch; list_agc_other = list_buf + 6 * nch;
-        if (int rc = meters_alloc()) return rc;
-        QH_HIP(dev_alloc(&agc_prm, (size_t)nch));
-        QH_HIP(dev_alloc(&agc_state, (size_t)nch));
-        QH_HIP(hipMemsetAsync(agc_state, 0, (size_t)nch * sizeof(AgcState), stream));
-        {
-            std::vector<int> oi((size_t)nch, kAgcRing - 1);         // out_index = -1 (calc_wcpagc, wcpAGC.c:34)
-            for (int c = 0; c < nch; c++)
-                QH_HIP(hipMemcpyAsync(&agc_state[c].out_index, &oi[(size_t)c], sizeof(int), hipMemcpyHostToDevice, stream));
-            QH_HIP(hipStreamSynchronize(stream));
-        }
-        dev_bytes += (long long)nch * (sizeof(AgcParam) + sizeof(AgcState));
-        QH_HIP(dev_alloc(&levelfade, (size_t)nch));
-        QH_HIP(dev_alloc(&am_state, (size_t)nch));
-        QH_HIP(dev_alloc(&am_next, (size_t)nch));
-        QH_HIP(dev_alloc(&sn_next, (size_t)nch));
-        QH_HIP(dev_alloc(&fmdc_next, (size_t)nch));
-        QH_HIP(dev_alloc(&pll_state, (size_t)nch));
-        QH_HIP(dev_alloc(&fm_pll_state, (size_t)nch));
-        QH_HIP(dev_alloc(&fm_again, (size_t)nch));
-        QH_HIP(dev_alloc(&pll_nfixed, (size_t)1));
-        QH_HIP(hipMemsetAsync(pll_nfixed, 0, sizeof(int), stream));
-        QH_HIP(dev_alloc(&sam_prm, (size_t)nch));
-        QH_HIP(dev_alloc(&sn_prm, (size_t)nch));
-        QH_HIP(dev_alloc(&sn_state, (size_t)nch));
-        QH_HIP(hipMemsetAsync(am_state, 0, (size_t)nch * sizeof(AmState), stream));
-        QH_HIP(hipMemsetAsync(pll_state, 0, (size_t)nch * sizeof(PllState), stream));
-        QH_HIP(hipMemsetAsync(fm_pll_state, 0, (size_t)nch * sizeof(PllState), stream));
-        QH_HIP(hipMemsetAsync(sn_state, 0, (size_t)nch * sizeof(SnotchState), stream));
-        QH_HIP(dev_alloc(&mask_de, (size_t)kBandNfftMax));
-        QH_HIP(dev_alloc(&mask_aud, (size_t)kBandNfftMax));
-        for (int i = 0; i < 2; i++) {
-            QH_HIP(dev_alloc(&hist_de[i], (size_t)nch * kHistBand));
-            QH_HIP(dev_alloc(&hist_aud[i], (size_t)nch * kHistBand));
-            QH_HIP(hipMemsetAsync(hist_de[i], 0, (size_t)nch * kHistBand * sizeof(double2), stream));
-            QH_HIP(hipMemsetAsync(hist_aud[i], 0, (size_t)nch * kHistBand * sizeof(double2), stream));
-        }
-        dev_bytes += (long long)nch * (5 * 4 + 4 + sizeof(AmState) + sizeof(PllState) + 8 + sizeof(SamChanParam) +
-                                      sizeof(SnotchParam) + sizeof(SnotchState) + 4 * kHistBand * sizeof(double2)) +
-                     2ll * kBandNfftMax * sizeof(double2);
-        // init_amd (wdsp/amd.c:72-89) with create_rxa's constants (RXA.c:183-189)
-        {
-            const double zeta = 1.0, omegaN = 250.0, tauR = 0.02, tauI = 1.4;
-            PllParam &q = sam_pll_prm;
-            q.omega_min = kTwoPiRef * -2000.0 / rate; q.omega_max = kTwoPiRef * 2000.0 / rate;
-            q.g1 = 1.0 - std::exp(-2.0 * omegaN * zeta / rate);
-            q.g2 = -q.g1 + 2.0 * (1 - std::exp(-omegaN * zeta / rate) * std::cos(omegaN / rate * std::sqrt(1.0 - zeta * zeta)));
-            q.mtauR = std::exp(-1.0 / (rate * tauR)); q.onem_mtauR = 1.0 - q.mtauR;
-            q.mtauI = std::exp(-1.0 / (rate * tauI)); q.onem_mtauI = 1.0 - q.mtauI;
-            am_prm.mtauR = q.mtauR; am_prm.onem_mtauR = q.onem_mtauR; am_prm.mtauI = q.mtauI; am_prm.onem_mtauI = q.onem_mtauI;
-            std::vector<double> pw(2 * 2048);           // mtauR^(k + 1), mtauI^(k + 1): the carried averages' weights at sample k of a 2048-sample tile
-            for (int k = 0; k < 2048; k++) { pw[(size_t)k] = std::pow(q.mtauR, (double)(k + 1)); pw[(size_t)(2048 + k)] = std::pow(q.mtauI, (double)(k + 1)); }
-            // ... and the lanes' scan weights of the two averages (qh_wave.hpp PoleScan: pa = m^((lane & 15) + 1), pb = m^((lane & 31) + 1), pw = m^(lane + 1))
-            pw.resize(2 * 2048 + 6 * 64);
-            for (int f = 0; f < 2; f++) {
-                const double m = f ? q.mtauI : q.mtauR;
-                for (int l = 0; l < 64; l++) {
-                    pw[(size_t)(2 * 2048 + (3 * f + 0) * 64 + l)] = std::pow(m, (double)((l & 15) + 1));
-                    pw[(size_t)(2 * 2048 + (3 * f + 1) * 64 + l)] = std::pow(m, (double)((l & 31) + 1));
-                    pw[(size_t)(2 * 2048 + (3 * f + 2) * 64 + l)] = std::pow(m, (double)(l + 1));
-                }
-            }
-            QH_HIP(dev_alloc(&am_pw, pw.size()));
-            QH_HIP(dev_alloc(&am_last, (size_t)2 * nch));
-            QH_HIP(hipMemcpyAsync(am_pw, pw.data(), pw.size() * sizeof(double), hipMemcpyHostToDevice, stream));
-            QH_HIP(hipMemsetAsync(am_last, 0, (size_t)2 * nch * sizeof(double), stream));
-            QH_HIP(hipStreamSynchronize(stream));
-        }
-        // calc_fmd (wdsp/fmd.c:29-44) with create_rxa's constants (RXA.c:199-204)
-        {
-            const double zeta = 1.0, omegaN = 20000.0, tau = 0.02;
-            PllParam &q = fm_pll_prm;
-            q.omega_min = kTwoPiRef * -8000.0 / rate; q.omega_max = kTwoPiRef * 8000.0 / rate;
-            q.g1 = 1.0 - std::exp(-2.0 * omegaN * zeta / rate);
-            q.g2 = -q.g1 + 2.0 * (1 - std::exp(-omegaN * zeta / rate) * std::cos(omegaN / rate * std::sqrt(1.0 - zeta * zeta)));
-            q.mtau = std::exp(-1.0 / (rate * tau)); q.onem_mtau = 1.0 - q.mtau;
-            std::vector<double> pw(2048);               // mtau^(k + 1): the carried dc's weight at sample k of a tile (fm_audio_at)
-            for (int k = 0; k < 2048; k++) pw[(size_t)k] = std::pow(q.mtau, (double)(k + 1));
-            QH_HIP(dev_alloc(&fm_pw, (size_t)2048));
-            QH_HIP(hipMemcpyAsync(fm_pw, pw.data(), 2048 * sizeof(double), hipMemcpyHostToDevice, stream));
-            QH_HIP(hipStreamSynchronize(stream));
-        }
-        demod_alloc = true;
-        lists_dirty = true;
-        for (ChanCfg &c : cfg) c.demod_dirty = true;
+    if (int rc = alloc(list_block, (long long)nch * (L_COUNT + 3))) return rc;      // the three pair lists (last) take two rows each
+    for (int i = 0; i < L_COUNT; i++) lists[i].dev = list_block + (size_t)nch * (i <= L_PAIRS_FM ? i : 2 * i - L_PAIRS_FM);
+    if (int rc = alloc(fix_gain, nch)) return rc;
+    if (int rc = meters_alloc()) return rc;
+    if (int rc = alloc(agc_prm, nch)) return rc;
+    if (int rc = alloc(agc_state, nch, true)) return rc;
+    const int oi = kAgcRing - 1;                        // out_index = -1 (calc_wcpagc, wcpAGC.c:34)
+    for (int c = 0; c < nch; c++) if (int rc = put_row(&agc_state[c].out_index, 0, oi, false)) return rc;
+    QH_HIP(hipStreamSynchronize(stream));
+    if (int rc = alloc(levelfade, nch)) return rc;
+    if (int rc = alloc(am_state, nch, true)) return rc;
+    if (int rc = alloc(am_next, nch)) return rc;
+    if (int rc = alloc(sn_next, nch)) return rc;
+    if (int rc = alloc(fmdc_next, nch)) return rc;
+    if (int rc = alloc(pll_state, nch, true)) return rc;
+    if (int rc = alloc(fm_pll_state, nch, true)) return rc;
+    if (int rc = alloc(fm_again, nch)) return rc;
+    if (int rc = alloc(pll_nfixed, 1, true)) return rc;
+    if (int rc = alloc(sam_prm, nch)) return rc;
+    if (int rc = alloc(sn_prm, nch)) return rc;
+    if (int rc = alloc(sn_state, nch, true)) return rc;
+    if (int rc = alloc(mask_de, kBandNfftMax)) return rc;
+    if (int rc = alloc(mask_aud, kBandNfftMax)) return rc;
+    for (int i = 0; i < 2; i++) {
+        if (int rc = alloc(hist_de[i], (long long)nch * kHistBand, true)) return rc;
+        if (int rc = alloc(hist_aud[i], (long long)nch * kHistBand, true)) return rc;
     }
+    // init_amd (wdsp/amd.c:72-89) with create_rxa's constants (RXA.c:183-189)
+    {
+        const double zeta = 1.0, omegaN = 250.0, tauR = 0.02, tauI = 1.4;
+        PllParam &q = sam_pll_prm;
+        q.omega_min = kTwoPiRef * -2000.0 / rate; q.omega_max = kTwoPiRef * 2000.0 / rate;
+        q.g1 = 1.0 - std::exp(-2.0 * omegaN * zeta / rate);
+        q.g2 = -q.g1 + 2.0 * (1 - std::exp(-omegaN * zeta / rate) * std::cos(omegaN / rate * std::sqrt(1.0 - zeta * zeta)));
+        q.mtauR = std::exp(-1.0 / (rate * tauR)); q.onem_mtauR = 1.0 - q.mtauR;
+        q.mtauI = std::exp(-1.0 / (rate * tauI)); q.onem_mtauI = 1.0 - q.mtauI;
+        am_prm.mtauR = q.mtauR; am_prm.onem_mtauR = q.onem_mtauR; am_prm.mtauI = q.mtauI; am_prm.onem_mtauI = q.onem_mtauI;
+        std::vector<double> pw(2 * 2048);           // mtauR^(k + 1), mtauI^(k + 1): the carried averages' weights at sample k of a 2048-sample tile
+        for (int k = 0; k < 2048; k++) { pw[(size_t)k] = std::pow(q.mtauR, (double)(k + 1)); pw[(size_t)(2048 + k)] = std::pow(q.mtauI, (double)(k + 1)); }
+        // ... and the lanes' scan weights of the two averages (qh_wave.hpp PoleScan: pa = m^((lane & 15) + 1), pb = m^((lane & 31) + 1), pw = m^(lane + 1))
+        pw.resize(2 * 2048 + 6 * 64);
+        for (int f = 0; f < 2; f++) {
+            const double m = f ? q.mtauI : q.mtauR;
+            for (int l = 0; l < 64; l++) {
+                pw[(size_t)(2 * 2048 + (3 * f + 0) * 64 + l)] = std::pow(m, (double)((l & 15) + 1));
+                pw[(size_t)(2 * 2048 + (3 * f + 1) * 64 + l)] = std::pow(m, (double)((l & 31) + 1));
+                pw[(size_t)(2 * 2048 + (3 * f + 2) * 64 + l)] = std::pow(m, (double)(l + 1));
+            }
+        }
+        if (int rc = alloc(am_pw, (long long)pw.size())) return rc;
+        if (int rc = alloc(am_last, 2LL * nch, true)) return rc;
+        QH_HIP(hipMemcpyAsync(am_pw, pw.data(), pw.size() * sizeof(double), hipMemcpyHostToDevice, stream));
+        QH_HIP(hipStreamSynchronize(stream));
+    }
+    // calc_fmd (wdsp/fmd.c:29-44) with create_rxa's constants (RXA.c:199-204)
+    {
+        const double zeta = 1.0, omegaN = 20000.0, tau = 0.02;
+        PllParam &q = fm_pll_prm;
+        q.omega_min = kTwoPiRef * -8000.0 / rate; q.omega_max = kTwoPiRef * 8000.0 / rate;
+        q.g1 = 1.0 - std::exp(-2.0 * omegaN * zeta / rate);
+        q.g2 = -q.g1 + 2.0 * (1 - std::exp(-omegaN * zeta / rate) * std::cos(omegaN / rate * std::sqrt(1.0 - zeta * zeta)));
+        q.mtau = std::exp(-1.0 / (rate * tau)); q.onem_mtau = 1.0 - q.mtau;
+        std::vector<double> pw(2048);               // mtau^(k + 1): the carried dc's weight at sample k of a tile (fm_audio_at)
+        for (int k = 0; k < 2048; k++) pw[(size_t)k] = std::pow(q.mtau, (double)(k + 1));
+        if (int rc = alloc(fm_pw, 2048)) return rc;
+        QH_HIP(hipMemcpyAsync(fm_pw, pw.data(), 2048 * sizeof(double), hipMemcpyHostToDevice, stream));
+        QH_HIP(hipStreamSynchronize(stream));
+    }
+    demod_alloc = true;
+    lists_dirty = true;
+    for (ChanCfg &c : cfg) c.demod_dirty = true;
+    return QH_OK;
+}
+
+// Every channel list from the channels' settings (host side: h[id]), with their counts
+void Engine::build_lists(std::vector<int> (&h)[L_COUNT])
+{
+    std::vector<int> stale_cur, stale_other;
+    int sam0 = 0;
+    for (int ch = 0; ch < nch; ch++) {
+        const ChanCfg &c = cfg[(size_t)ch];
+        if (c.amsq_run) h[L_AMSQ].push_back(ch);
+        if (c.snba_run) h[L_SNBA].push_back(ch);
+        if (c.snb_pos() >= 0) h[L_SNB + c.snb_pos()].push_back(ch);
+        const int at_agc = (c.bp1_run && !c.bp1_pos) ? 1 : 0;       // the buffer the channel is in when xwcpagc runs
+        if (c.emnr_run) h[L_EMNR + (c.emnr_pos ? 1 + at_agc : 0)].push_back(ch);
+        for (int f = 0; f < 2; f++) if (c.lms[f].run) h[L_LMS + 3 * f + (c.lms[f].position ? 1 + at_agc : 0)].push_back(ch);
+        if (c.bp1_run) h[L_BP1P + (c.bp1_pos ? 1 : 0)].push_back(ch);
+        if (c.fix_before()) h[L_FIX + at_agc].push_back(ch);
+        if (c.ap_on()) h[L_AP + (c.bp1_run ? 1 : 0)].push_back(ch);        // where the channel is behind bp1 at either position
+        if (c.fmd_run && c.lim_run) h[L_LIM].push_back(ch);
+        if (c.amd_run && c.amd_mode == 0) h[L_AM].push_back(ch);
+        // SAM channels with sbmode 0 (no all-pass chains) first
+        if (c.amd_run && c.amd_mode == 1) { if (c.sbmode == 0) h[L_SAM].insert(h[L_SAM].begin() + sam0++, ch); else h[L_SAM].push_back(ch); }
+        if (c.fmd_run) h[L_FM].push_back(ch); else { h[L_REST].push_back(ch); h[c.bp1_run ? L_RB : L_USB].push_back(ch); }
+        h[c.bp1_run ? L_BP1 : L_PLAIN].push_back(ch);
+        // xwcpagc sits between the two bp1 positions (RXA.c:581-586): a position-1 channel is still in `cur` there; channels whose
+        // attack window moved in mid-stream go last
+        if (c.agc_run && c.agc_mode != 0) (at_agc ? (c.agc_stale ? stale_other : h[L_AGC_OTHER]) : (c.agc_stale ? stale_cur : h[L_AGC_CUR])).push_back(ch);
+    }
+    n_sam0 = sam0;
+    n_agc_cur_stale = (int)stale_cur.size(); n_agc_other_stale = (int)stale_other.size();
+    h[L_AGC_CUR].insert(h[L_AGC_CUR].end(), stale_cur.begin(), stale_cur.end());
+    h[L_AGC_OTHER].insert(h[L_AGC_OTHER].end(), stale_other.begin(), stale_other.end());
+    // partners: neighbours in the list, ordered so that equal designs are neighbours; a channel left over is its own partner
+    auto bp1_real = [&](int ch) { const ChanCfg &c = cfg[(size_t)ch]; return c.bp1_run && c.bp1_flow == -c.bp1_fhigh && !c.mp; };
+    auto bp1_same = [&](int x, int y) {
+        const ChanCfg &p = cfg[(size_t)x], &q = cfg[(size_t)y];
+        return p.bp1_nc == q.bp1_nc && p.bp1_wintype == q.bp1_wintype && p.bp1_fhigh == q.bp1_fhigh && p.bp1_gain == q.bp1_gain;
+    };
+    auto bp1_pairs = [&](std::vector<int> v) {
+        std::vector<int> pr;
+        for (int ch : v) if (!bp1_real(ch)) return pr;
+        std::stable_sort(v.begin(), v.end(), [&](int x, int y) {
+            const ChanCfg &p = cfg[(size_t)x], &q = cfg[(size_t)y];
+            if (p.bp1_fhigh != q.bp1_fhigh) return p.bp1_fhigh < q.bp1_fhigh;
+            if (p.bp1_nc != q.bp1_nc) return p.bp1_nc < q.bp1_nc;
+            if (p.bp1_wintype != q.bp1_wintype) return p.bp1_wintype < q.bp1_wintype;
+            return p.bp1_gain < q.bp1_gain;
+        });
+        for (size_t i = 0; i < v.size();) {
+            if (i + 1 < v.size() && bp1_same(v[i], v[i + 1])) { pr.push_back(v[i]); pr.push_back(v[i + 1]); i += 2; }
+            else { pr.push_back(v[i]); pr.push_back(v[i]); i += 1; }
+        }
+        return pr;
+    };
+    const std::vector<int> &fm = h[L_FM];
+    for (size_t i = 0; i < fm.size(); i += 2) { h[L_PAIRS_FM].push_back(fm[i]); h[L_PAIRS_FM].push_back(i + 1 < fm.size() ? fm[i + 1] : fm[i]); }
+    h[L_PAIRS_AM] = bp1_pairs(h[L_AM]);
+    h[L_PAIRS_SAM] = bp1_pairs(h[L_SAM]);
+    np_fm = (int)h[L_PAIRS_FM].size() / 2; np_am = (int)h[L_PAIRS_AM].size() / 2; np_sam = (int)h[L_PAIRS_SAM].size() / 2;
+    for (int i = 0; i < L_COUNT; i++) lists[i].n = (int)h[i].size();
+}
+
+// The stages made when a channel first runs one of them (the lists' counts say which)
+int Engine::stages_alloc()
+{
+    const double rate = (double)dsp_rate;
+    if ((lists[L_AP].n || lists[L_AP + 1].n) && !ap_prm) if (int rc = ap_alloc()) return rc;
+    if ((lists[L_EMNR].n || lists[L_EMNR + 1].n || lists[L_EMNR + 2].n) && !emnr_state) if (int rc = emnr_alloc()) return rc;
+    if (lists[L_SNBA].n && !snba_state) if (int rc = snba_alloc()) return rc;
+    if (lists[L_AMSQ].n && !amsq_prm) {
+        if (int rc = alloc(amsq_prm, nch)) return rc;
+        if (int rc = alloc(amsq_state, nch, true)) return rc;
+        // compute_slews, amsq.c:28-46, with muted_gain 0 and 70 ms up / down (RXA.c:166-167,172): theta accumulates as there
+        amsq_ntup = (int)(0.070 * rate); amsq_ntdown = (int)(0.070 * rate);
+        std::vector<double> up((size_t)amsq_ntup + 1), down((size_t)amsq_ntdown + 1);
+        double delta = kPiRef / (double)amsq_ntup, theta = 0.0;
+        for (int i = 0; i <= amsq_ntup; i++) { up[(size_t)i] = 0.0 + (1.0 - 0.0) * 0.5 * (1.0 - std::cos(theta)); theta += delta; }
+        delta = kPiRef / (double)amsq_ntdown; theta = 0.0;
+        for (int i = 0; i <= amsq_ntdown; i++) { down[(size_t)i] = 0.0 + (1.0 - 0.0) * 0.5 * (1.0 + std::cos(theta)); theta += delta; }
+        if (int rc = alloc(amsq_cup, (long long)up.size())) return rc;
+        if (int rc = alloc(amsq_cdown, (long long)down.size())) return rc;
+        QH_HIP(hipMemcpyAsync(amsq_cup, up.data(), up.size() * 8, hipMemcpyHostToDevice, stream));
+        QH_HIP(hipMemcpyAsync(amsq_cdown, down.data(), down.size() * 8, hipMemcpyHostToDevice, stream));
+        QH_HIP(hipStreamSynchronize(stream));
+        for (ChanCfg &c : cfg) c.amsq_dirty = true;
+    }
+    bool any_lms = false;
+    for (int k = 0; k < 6; k++) any_lms = any_lms || lists[L_LMS + k].n;
+    if (any_lms && !lms_prm[0]) {
+        for (int f = 0; f < 2; f++) {
+            if (int rc = alloc(lms_prm[f], nch)) return rc;
+            if (int rc = alloc(lms_state[f], nch)) return rc;
+            // create_anf: lidx 1.0, ngamma 6.25e-12; create_anr: lidx 120.0, ngamma 0.001 (RXA.c:289-292,309-312)
+            std::vector<LmsState> init((size_t)nch);
+            std::memset(init.data(), 0, init.size() * sizeof(LmsState));
+            for (LmsState &st : init) { st.lidx = f ? 120.0 : 1.0; st.ngamma = f ? 0.001 : 6.25e-12; }
+            QH_HIP(hipMemcpyAsync(lms_state[f], init.data(), init.size() * sizeof(LmsState), hipMemcpyHostToDevice, stream));
+            QH_HIP(hipStreamSynchronize(stream));
+        }
+        for (ChanCfg &c : cfg) { c.lms[0].dirty = c.lms[1].dirty = true; c.lms[0].flush = c.lms[1].flush = false; }
+    }
+    if (lists[L_LIM].n && !lim_prm) {
+        if (int rc = alloc(lim_prm, nch)) return rc;
+        if (int rc = alloc(lim_state, nch)) return rc;
+        for (ChanCfg &c : cfg) c.lim_dirty = true;
+    }
+    return QH_OK;
+}
+
+// A fircore keeps its delay lines while its channel is off the stage's list, and the ping-pong pair flips for the listed channels
+// only: a channel that (re)joins the list finds its rows in the half that was current when it left (c.*at), and they move to the
+// current one.  rows: the stage's short and long delay lines, each with the half that is current for it.
+int Engine::follow_rows(std::vector<char> &listed, int ChanCfg::*at, int cur, const std::vector<int> &chans, std::initializer_list<Rows> rows)
+{
+    if (listed.size() != (size_t)nch) listed.assign((size_t)nch, 0);
+    for (int ch = 0; ch < nch; ch++) if (listed[(size_t)ch]) cfg[(size_t)ch].*at = cur;
+    std::fill(listed.begin(), listed.end(), 0);
+    for (int ch : chans) {
+        int &a = cfg[(size_t)ch].*at;
+        if (a != cur)
+            for (const Rows &r : rows)
+                if (r.h[0] && r.h[1])
+                    QH_HIP(hipMemcpyAsync(r.h[r.cur] + (size_t)ch * r.len, r.h[a] + (size_t)ch * r.len, (size_t)r.len * sizeof(double2),
+                                          hipMemcpyDeviceToDevice, stream));
+        a = cur;
+        listed[(size_t)ch] = 1;
+    }
+    return QH_OK;
+}
+
+// setNc_fircore's flush (wdsp/firmin.c:454-466): zero n channels' delay lines from channel ch on, short and long, in both halves
+int Engine::zero_rows(double2 *const h[2], double2 *const lh[2], int ch, int n)
+{
+    for (int i = 0; i < 2; i++) {
+        QH_HIP(hipMemsetAsync(h[i] + (size_t)ch * kHistBand, 0, (size_t)n * kHistBand * sizeof(double2), stream));
+        if (lh[i]) QH_HIP(hipMemsetAsync(lh[i] + (size_t)ch * kLongHist, 0, (size_t)n * kLongHist * sizeof(double2), stream));
+    }
+    return QH_OK;
+}
+
+// Lists, stages and delay-line rows after a setter moved a channel between lists
+int Engine::refresh_lists()
+{
+    std::vector<int> h[L_COUNT];
+    build_lists(h);
+    if (int rc = stages_alloc()) return rc;
+    if (snba_state) {       // bpsnba's fircore (the partitioned form's 16383-sample delay line goes along: nc > 4096)
+        std::vector<int> snb(h[L_SNB]);
+        snb.insert(snb.end(), h[L_SNB + 1].begin(), h[L_SNB + 1].end());
+        if (int rc = follow_rows(snb_listed, &ChanCfg::snb_hist_at, cur_snb, snb, { { hist_snb, cur_snb, kHistBand }, { lhist[4], cur_snb, kLongHist } }))
+            return rc;
+    }
+    // bp1's: SetRXABandpassRun (bandpass.c:385-390) switches it on without RXAbp1Set's flush (RXA.c:825)
+    if (int rc = follow_rows(bp1_listed, &ChanCfg::bp1_hist_at, cur_bp1, h[L_BP1], { { hist_bp1, cur_bp1, kHistBand }, { lhist[1], cur_bp1, kLongHist } }))
+        return rc;
+    // the FM de-emphasis / audio fircores' while the channel is in another mode (SetRXAMode only clears fmd's run flag, RXA.c:758-776);
+    // fm_hist_at follows the de-emphasis filter's half
+    if (int rc = follow_rows(fm_listed, &ChanCfg::fm_hist_at, cur_de, h[L_FM], { { hist_de, cur_de, kHistBand }, { hist_aud, cur_aud, kHistBand },
+                                                                                { lhist[2], cur_de, kLongHist }, { lhist[3], cur_aud, kLongHist } }))
+        return rc;
+    std::vector<int> all((size_t)nch * (L_COUNT + 3));
+    for (int i = 0; i < L_COUNT; i++) std::copy(h[i].begin(), h[i].end(), all.begin() + (lists[i].dev - list_block));
+    std::vector<double> fg((size_t)nch);
+    for (int ch = 0; ch < nch; ch++) fg[(size_t)ch] = cfg[(size_t)ch].agc_fixed;
+    QH_HIP(hipMemcpyAsync(list_block, all.data(), all.size() * sizeof(int), hipMemcpyHostToDevice, stream));
+    QH_HIP(hipMemcpyAsync(fix_gain, fg.data(), fg.size() * sizeof(double), hipMemcpyHostToDevice, stream));
+    QH_HIP(hipStreamSynchronize(stream));
+    lists_dirty = false;
+    return QH_OK;
+}
+
+// loadWcpAGC, wdsp/wcpAGC.c:115-146, in its order of expressions; the arguments in create_wcpagc's
+static AgcParam load_wcpagc(double rate, double tau_attack, double tau_decay, double n_tau, double max_gain, double var_gain, double max_input,
+                            double out_targ, double tau_fast_back, double tau_fast_decay, double pop_ratio, int hang_enable, double tau_hang_backmult,
+                            double hangtime, double hang_thresh, double tau_hang_decay)
+{
+    AgcParam q{};
+    q.attack_buffsize = (int)std::ceil(rate * n_tau * tau_attack);
+    q.attack_mult = 1.0 - std::exp(-1.0 / (rate * tau_attack));
+    q.decay_mult = 1.0 - std::exp(-1.0 / (rate * tau_decay));
+    q.fast_decay_mult = 1.0 - std::exp(-1.0 / (rate * tau_fast_decay));
+    q.fast_backmult = 1.0 - std::exp(-1.0 / (rate * tau_fast_back));
+    q.onemfast_backmult = 1.0 - q.fast_backmult;
+    q.out_target = out_targ * (1.0 - std::exp(-n_tau)) * 0.9999;
+    q.min_volts = q.out_target / (var_gain * max_gain);
+    q.inv_out_target = 1.0 / q.out_target;
+    double tmp = std::log10(q.out_target / (max_input * var_gain * max_gain));
+    if (tmp == 0.0) tmp = 1e-16;
+    q.slope_constant = (q.out_target * (1.0 - 1.0 / var_gain)) / tmp;
+    q.inv_max_input = 1.0 / max_input;
+    tmp = std::pow(10.0, (hang_thresh - 1.0) / 0.125);
+    q.hang_level = (max_input * tmp + (q.out_target / (var_gain * max_gain)) * (1.0 - tmp)) * 0.637;
+    q.hang_backmult = 1.0 - std::exp(-1.0 / (rate * tau_hang_backmult));
+    q.onemhang_backmult = 1.0 - q.hang_backmult;
+    q.hang_decay_mult = 1.0 - std::exp(-1.0 / (rate * tau_hang_decay));
+    q.pop_ratio = pop_ratio;
+    q.hang_count_init = (int)(hangtime * rate);
+    q.hang_enable = hang_enable;
+    q.pmode = 1;
+    return q;
+}
+
+// ---- per-channel parameters of the demodulator stages (refresh_demod: each only when its setter has run)
+int Engine::prm_agc(ChanCfg &c, int ch)
+{
+    if (!c.agc_dirty) return QH_OK;
+    // create_rxa's constants (RXA.c:335-358)
+    const AgcParam q = load_wcpagc((double)dsp_rate, c.agc_tau_attack, c.agc_tau_decay, 4.0, c.agc_max_gain, c.agc_var_gain, 1.0, 1.0, 0.250, 0.005,
+                                   5.0, 1, 0.500, c.agc_hangtime, c.agc_hang_thresh, 0.100);
+    if (q.attack_buffsize + 2 > kAgcRing)
+        return set_error(QH_ERR_UNSUPPORTED, "AGC attack of %g s needs a look-ahead of %d samples (limit %d)", c.agc_tau_attack,
+                         q.attack_buffsize, kAgcRing - 2);
+    c.agc_abuf = q.attack_buffsize;
+    if (int rc = put_row(agc_prm, ch, q)) return rc;
+    c.agc_dirty = false;
+    return QH_OK;
+}
+
+int Engine::prm_emnr(ChanCfg &c, int ch)
+{
+    if (emnr_chan && c.emnr_dirty) {
+        if (c.emnr_run && (c.emnr_npe < 0 || c.emnr_npe > 2 || c.emnr_gain_method < 0 || c.emnr_gain_method > 3))
+            return set_error(QH_ERR_UNSUPPORTED, "EMNR: gain methods 0..3 and noise estimators 0..2");
+        const EmnrChan ec{ c.emnr_gain_method, c.emnr_npe, c.emnr_ae, 0, c.emnr_ae_zeta, c.emnr_ae_psi, c.emnr_train_zeta, c.emnr_train_t2 };
+        if (int rc = put_row(emnr_chan, ch, ec)) return rc;
+        c.emnr_dirty = false;
+    }
+    if (emnr_state && c.emnr_flush) {           // flush_emnr, emnr.c:583-596: the accumulators and their indices, not the estimators
+        EmnrScalars sc;
+        QH_HIP(hipMemcpyAsync(&sc, emnr_scal + ch, sizeof(sc), hipMemcpyDeviceToHost, stream));
+        QH_HIP(hipStreamSynchronize(stream));
+        sc.iainidx = sc.iaoutidx = sc.oaoutidx = sc.nsamps = sc.saveidx = 0; sc.oainidx = emnr_prm.init_oainidx;
+        if (int rc = put_row(emnr_scal, ch, sc, false)) return rc;
+        QH_HIP(hipMemsetAsync(emnr_state + (size_t)ch * kEmnrStateDoubles, 0, (size_t)EO_PREVG * sizeof(double), stream));
+        QH_HIP(hipStreamSynchronize(stream));
+        c.emnr_flush = false;
+    }
+    return QH_OK;
+}
+
+int Engine::prm_snba(ChanCfg &c, int ch)
+{
+    const SnbaParam &q = snba_prm;
+    if (snba_state && c.snba_taps_dirty) {
+        // calc_resample for outresamp (12 kHz -> dsp_rate, gain 2, resample.c:35-79) with the channel's output bandwidth
+        if (q.ratio > 1) {
+            const int L = q.ratio, ncoef = q.cpp_out * L;
+            const double full = (double)(12000 * L), fc = c.snba_f_high == 0.0 ? 0.45 * 12000.0 : c.snba_f_high;
+            const double lo = c.snba_f_low < 0.0 ? -fc / full : c.snba_f_low / full;
+            const std::vector<cd> imp = fir_bandpass(ncoef, lo, fc / full, 1.0, 1, 0, 2.0 * (double)L);
+            std::vector<double> hp((size_t)ncoef);
+            size_t i = 0;
+            for (int j = 0; j < L; j++) for (int k = 0; k < ncoef; k += L) hp[i++] = imp[(size_t)(j + k)].real();
+            QH_HIP(hipMemcpyAsync(snba_hout + (size_t)ch * ncoef, hp.data(), hp.size() * sizeof(double), hipMemcpyHostToDevice, stream));
+            QH_HIP(hipStreamSynchronize(stream));
+        }
+        c.snba_taps_dirty = false;
+    }
+    if (snba_state && (c.snba_flush || c.snba_rout_flush)) {
+        double *st = snba_state + (size_t)ch * q.state_doubles;
+        if (q.cpp_out > 1) QH_HIP(hipMemsetAsync(st + q.off_rout, 0, (size_t)(q.cpp_out - 1) * sizeof(double), stream));
+        if (c.snba_flush) {         // flush_snba, snb.c:161-185: the frame half of xbase, the accumulators, both resamplers
+            QH_HIP(hipMemsetAsync(st + kSnbX, 0, (size_t)kSnbX * sizeof(double), stream));
+            QH_HIP(hipMemsetAsync(st + q.off_inacc, 0, (size_t)(q.state_doubles - q.off_inacc) * sizeof(double), stream));
+            if (int rc = put_row(snba_idx, ch, SnbaIdx{ 0, 0, 0, 0, q.init_oaoutidx, { 0, 0, 0 } })) return rc;
+        }
+    }
+    c.snba_flush = c.snba_rout_flush = false;
+    return QH_OK;
+}
+
+int Engine::prm_amsq(ChanCfg &c, int ch)
+{
+    if (!amsq_prm || !c.amsq_dirty) return QH_OK;
+    // calc_amsq, amsq.c:48-64: 10 ms average (RXA.c:165)
+    const double rate = (double)dsp_rate;
+    AmsqParam q{};
+    q.avm = std::exp(-1.0 / (rate * 0.010)); q.onem_avm = 1.0 - q.avm;
+    q.tail_thresh = c.amsq_tail_thresh; q.unmute_thresh = c.amsq_unmute_thresh; q.min_tail = 0.0; q.max_tail = c.amsq_max_tail;
+    q.muted_gain = 0.0; q.rate = rate; q.ntup = amsq_ntup; q.ntdown = amsq_ntdown;
+    if (int rc = put_row(amsq_prm, ch, q)) return rc;
+    c.amsq_dirty = false;
+    return QH_OK;
+}
+
+int Engine::prm_lms(ChanCfg &c, int ch)
+{
+    for (int f = 0; f < 2 && lms_prm[0]; f++) {
+        ChanCfg::Lms &m = c.lms[f];
+        if (m.dirty) {
+            if (m.run && (m.taps < 1 || m.taps > 64 || m.delay < 1 || m.delay > 64))
+                return set_error(QH_ERR_UNSUPPORTED, "%s: taps %d / delay %d (1..64 each: one tap per lane)", f ? "ANR" : "ANF", m.taps, m.delay);
+            // lidx_min, lidx_max, den_mult, lincr, ldecr of create_rxa (RXA.c:290-295,310-315)
+            if (int rc = put_row(lms_prm[f], ch, LmsParam{ m.taps, m.delay, f, 0, m.two_mu, m.gamma, f ? 120.0 : 0.0, 200.0, 6.25e-10, 1.0, 3.0 }))
+                return rc;
+            m.dirty = false;
+        }
+        if (m.flush) {          // flush_anf (anf.c:135-140): delay line and weights; lidx / ngamma carry on
+            QH_HIP(hipMemsetAsync(lms_state[f] + ch, 0, offsetof(LmsState, lidx), stream));
+            m.flush = false;
+        }
+    }
+    return QH_OK;
+}
+
+int Engine::prm_lim(ChanCfg &c, int ch)
+{
+    if (!c.lim_dirty || !lim_prm) return QH_OK;
+    // calc_fmd's create_wcpagc(1, 5, 1, ..., 0.001, 0.008, 4, lim_gain, 1.0, 1.0, 1.0, 0.9, 0.250, 0.004, 4.0, 0,
+    // 0.500, 0.500, 2.000, 0.100) (fmd.c:48-72) through loadWcpAGC; a new limiter starts cleared
+    const AgcParam q = load_wcpagc((double)dsp_rate, 0.001, 0.008, 4.0, c.lim_gain, 1.0, 1.0, 0.9, 0.250, 0.004, 4.0, 0, 0.500, 0.500, 2.000, 0.100);
+    if (int rc = put_row(lim_prm, ch, q, false)) return rc;
+    QH_HIP(hipMemsetAsync(lim_state + ch, 0, sizeof(AgcState), stream));
+    if (int rc = put_row(&lim_state[ch].out_index, 0, kAgcRing - 1)) return rc;        // out_index = -1 (calc_wcpagc, wcpAGC.c:34)
+    c.lim_dirty = false;
+    return QH_OK;
+}
+
+// the detectors' own parameters: AM's fade leveller, SAM's sideband mode, FM's gain and its CTCSS notch
+int Engine::prm_detect(ChanCfg &c, int ch)
+{
+    if (!c.demod_dirty) return QH_OK;
+    const int lf = c.levelfade;
+    const double again = (double)dsp_rate / (c.fm_dev * kTwoPiRef);     // wdsp/fmd.c:44
+    const SamChanParam sp{ c.sbmode, c.levelfade };
+    SnotchParam sn{};
+    {   // calc_snotch, wdsp/iir.c:35-49 (bw 0.0002, fmd.c:47)
+        const double fn = c.ctcss_freq / (double)dsp_rate, csn = std::cos(kTwoPiRef * fn), qr = 1.0 - 3.0 * 0.0002;
+        const double qk = (1.0 - 2.0 * qr * csn + qr * qr) / (2.0 * (1.0 - csn));
+        sn.a0 = qk; sn.a1 = -2.0 * qk * csn; sn.a2 = qk; sn.b1 = 2.0 * qr * csn; sn.b2 = -qr * qr; sn.run = c.ctcss_run;
+    }
+    if (int rc = put_row(levelfade, ch, lf, false)) return rc;
+    if (int rc = put_row(fm_again, ch, again, false)) return rc;
+    if (int rc = put_row(sam_prm, ch, sp, false)) return rc;
+    if (int rc = put_row(sn_prm, ch, sn, false)) return rc;
+    if (c.ctcss_flush) {                    // calc_snotch ends with flush_snotch, wdsp/iir.c:48
+        QH_HIP(hipMemsetAsync(sn_state + ch, 0, sizeof(SnotchState), stream));
+        c.ctcss_flush = false;
+    }
+    QH_HIP(hipStreamSynchronize(stream));
+    c.demod_dirty = false;
+    return QH_OK;
+}
+
+// create_fmd, wdsp/fmd.c:108-116: the de-emphasis and audio filters the FM channels share, rebuilt when their nc, RXASetMP or the band
+// tile moved
+int Engine::fm_filters(int want_nc)
+{
+    if (!want_nc || (want_nc == fm_nc_built && fm_mp == fm_mp_built && fm_nfft_built == 2 * bnfft + (band2g ? 1 : 0))) return QH_OK;
+    // de-emphasis by frequency sampling, audio band-pass 0.8*f_low .. 1.1*f_high
+    const double rate = (double)dsp_rate, f_low = 300.0, f_high = 3000.0, afgain = 0.5;
+    std::vector<cd> de = fc_impulse(want_nc, f_low, f_high, +20.0 * std::log10(f_high / f_low), 0.0, 1, rate, 1.0 / (2.0 * dsp_size), 0, 0);
+    std::vector<cd> au = fir_bandpass(want_nc, 0.8 * f_low, 1.1 * f_high, rate, 0, 1, afgain / (2.0 * dsp_size));
+    if (fm_mp) { de = mp_imp(de, 16, 0); au = mp_imp(au, 16, 0); }     // SetRXAFMMPde / MPaud, wdsp/RXA.c:956-957
+    fm_mp_built = fm_mp;
+    for (auto &v : de) v *= (double)(2 * dsp_size);
+    for (auto &v : au) v *= (double)(2 * dsp_size);
+    de_real = true;
+    for (const cd &v : de) de_real = de_real && v.imag() == 0.0;
+    if (long_parts[2] > 1) {
+        if (int rc = long_masks_upload(2, 0, de)) return rc;
+        if (int rc = long_masks_upload(3, 0, au)) return rc;
+        de.resize((size_t)kLongPart); au.resize((size_t)kLongPart);      // (the one-tile masks are not used then)
+    }
+    if (int rc = upload(mask_de, band_mask(de), stream)) return rc;
+    if (int rc = upload(mask_aud, band_mask(au), stream)) return rc;
+    fm_nfft_built = 2 * bnfft + (band2g ? 1 : 0);
+    if (fm_nc_built && fm_nc_built != want_nc) {      // setNc_fircore zeroes the delay lines
+        if (int rc = zero_rows(hist_de, lhist[2], 0, nch)) return rc;
+        if (int rc = zero_rows(hist_aud, lhist[3], 0, nch)) return rc;
+    }
+    fm_nc_built = want_nc;
+    return QH_OK;
+}
+
+// Demodulator state, channel lists and FM filters (only engines that run AM/SAM/FM channels get here).  Every step looks at flags
+// first: a call with nothing dirty allocates, copies and waits for nothing.
+int Engine::refresh_demod()
+{
+    if (!demod_alloc) if (int rc = demod_init()) return rc;
     // a channel whose attack window moves after its AGC has run keeps the reference's ring_max, which may then be a value the window
     // no longer holds (wcpAGC.c:197-210 only rescans when the sample that leaves equals it): the time tiles take the window's maximum,
     // so that channel stays on the kernel that steps the reference's bookkeeping -- it alone: the lists put such channels last
     for (ChanCfg &c : cfg) {
         if (!c.agc_dirty || !c.agc_ran) continue;
-        const int abuf = (int)std::ceil(rate * 4.0 * c.agc_tau_attack);
+        const int abuf = (int)std::ceil((double)dsp_rate * 4.0 * c.agc_tau_attack);
         if (c.agc_abuf != abuf) { c.agc_rewindow = true; if (!c.agc_stale) { c.agc_stale = true; lists_dirty = true; } }
     }
-    if (lists_dirty) {
-        std::vector<int> la, ls, lf, lb, lp, lgc, lgo, lgc_s, lgo_s, ll, lms_l[2][3], lbp[2], lfix[2], lsq, lem[3], lsn[2], lsnba, lrest, lusb, lrb, lap[2];
-        int n_sam0_new = 0;
-        for (int ch = 0; ch < nch; ch++) {
-            const ChanCfg &c = cfg[(size_t)ch];
-            if (c.amsq_run) lsq.push_back(ch);
-            if (c.snba_run) lsnba.push_back(ch);
-            if (c.snb_pos() >= 0) lsn[c.snb_pos()].push_back(ch);
-            if (c.emnr_run) lem[c.emnr_pos ? 1 + ((c.bp1_run && !c.bp1_pos) ? 1 : 0) : 0].push_back(ch);
-            const int at_agc = (c.bp1_run && !c.bp1_pos) ? 1 : 0;       // the buffer the channel is in when xwcpagc runs
-            for (int f = 0; f < 2; f++) if (c.lms[f].run) lms_l[f][c.lms[f].position ? 1 + at_agc : 0].push_back(ch);
-            if (c.bp1_run) lbp[c.bp1_pos ? 1 : 0].push_back(ch);
-            if (c.fix_before()) lfix[at_agc].push_back(ch);
-            if (c.ap_on()) lap[c.bp1_run ? 1 : 0].push_back(ch);        // where the channel is behind bp1 at either position
-            if (c.fmd_run && c.lim_run) ll.push_back(ch);
-            if (c.amd_run && c.amd_mode == 0) la.push_back(ch);
-            if (c.amd_run && c.amd_mode == 1) { if (c.sbmode == 0) ls.insert(ls.begin() + n_sam0_new++, ch); else ls.push_back(ch); }
-            if (c.fmd_run) lf.push_back(ch); else { lrest.push_back(ch); (c.bp1_run ? lrb : lusb).push_back(ch); }
-            if (c.bp1_run) lb.push_back(ch); else lp.push_back(ch);
-            // xwcpagc sits between the two bp1 positions (RXA.c:581-586): a position-1 channel is still in `cur` there
-            if (c.agc_run && c.agc_mode != 0) (c.bp1_run && !c.bp1_pos ? (c.agc_stale ? lgo_s : lgo) : (c.agc_stale ? lgc_s : lgc)).push_back(ch);
-        }
-        bool any_lms = false;
-        for (int f = 0; f < 2; f++) for (int k = 0; k < 3; k++) { n_lms[f][k] = (int)lms_l[f][k].size(); any_lms = any_lms || n_lms[f][k]; }
-        n_bp1p[0] = (int)lbp[0].size(); n_bp1p[1] = (int)lbp[1].size();
-        n_fix[0] = (int)lfix[0].size(); n_fix[1] = (int)lfix[1].size();
-        n_amsq = (int)lsq.size();
-        n_ap[0] = (int)lap[0].size(); n_ap[1] = (int)lap[1].size();
-        if ((n_ap[0] || n_ap[1]) && !ap_prm) if (int rc = ap_alloc()) return rc;
-        for (int k = 0; k < 3; k++) n_emnr[k] = (int)lem[k].size();
-        if ((n_emnr[0] || n_emnr[1] || n_emnr[2]) && !emnr_state) if (int rc = emnr_alloc()) return rc;
-        n_snb[0] = (int)lsn[0].size(); n_snb[1] = (int)lsn[1].size(); n_snba = (int)lsnba.size();
-        if (n_snba && !snba_state) if (int rc = snba_alloc()) return rc;
-        if (snba_state) {
-            // bpsnba's fircore keeps its delay line while it does not run: a channel that (re)joins the list finds its rows in
-            // the ping-pong half that was current when it left
-            for (int ch = 0; ch < nch; ch++) if (snb_listed[(size_t)ch]) cfg[(size_t)ch].snb_hist_at = cur_snb;
-            std::fill(snb_listed.begin(), snb_listed.end(), 0);
-            for (int ps = 0; ps < 2; ps++)
-                for (int ch : lsn[ps]) {
-                    ChanCfg &c = cfg[(size_t)ch];
-                    if (c.snb_hist_at != cur_snb) {
-                        QH_HIP(hipMemcpyAsync(hist_snb[cur_snb] + (size_t)ch * kHistBand, hist_snb[c.snb_hist_at] + (size_t)ch * kHistBand,
-                                              kHistBand * sizeof(double2), hipMemcpyDeviceToDevice, stream));
-                        if (lhist[4][0] && lhist[4][1])         // the partitioned form's 16383-sample delay line goes along (nc > 4096)
-                            QH_HIP(hipMemcpyAsync(lhist[4][cur_snb] + (size_t)ch * kLongHist, lhist[4][c.snb_hist_at] + (size_t)ch * kLongHist,
-                                                  kLongHist * sizeof(double2), hipMemcpyDeviceToDevice, stream));
-                    }
-                    c.snb_hist_at = cur_snb;
-                    snb_listed[(size_t)ch] = 1;
-                }
-        }
-        {
-            // bp1's fircore keeps its delay line while it does not run, and SetRXABandpassRun (bandpass.c:385-390) switches it on without
-            // RXAbp1Set's flush (RXA.c:825): the rows are in the half that was current when the channel left the list
-            if (bp1_listed.size() != (size_t)nch) bp1_listed.assign((size_t)nch, 0);
-            for (int ch = 0; ch < nch; ch++) if (bp1_listed[(size_t)ch]) cfg[(size_t)ch].bp1_hist_at = cur_bp1;
-            std::fill(bp1_listed.begin(), bp1_listed.end(), 0);
-            for (int ch : lb) {
-                ChanCfg &c = cfg[(size_t)ch];
-                if (c.bp1_hist_at != cur_bp1) {
-                    QH_HIP(hipMemcpyAsync(hist_bp1[cur_bp1] + (size_t)ch * kHistBand, hist_bp1[c.bp1_hist_at] + (size_t)ch * kHistBand,
-                                          kHistBand * sizeof(double2), hipMemcpyDeviceToDevice, stream));
-                    if (lhist[1][0] && lhist[1][1])
-                        QH_HIP(hipMemcpyAsync(lhist[1][cur_bp1] + (size_t)ch * kLongHist, lhist[1][c.bp1_hist_at] + (size_t)ch * kLongHist,
-                                              kLongHist * sizeof(double2), hipMemcpyDeviceToDevice, stream));
-                }
-                c.bp1_hist_at = cur_bp1;
-                bp1_listed[(size_t)ch] = 1;
-            }
-        }
-        {
-            // the FM de-emphasis / audio fircores keep their delay lines while the channel is in another mode (SetRXAMode only
-            // clears fmd's run flag, RXA.c:758-776): the ping-pong pair flips for the listed channels only, so a channel that
-            // comes back finds its rows in the half that was current when it left
-            if (fm_listed.size() != (size_t)nch) fm_listed.assign((size_t)nch, 0);
-            for (int ch = 0; ch < nch; ch++) if (fm_listed[(size_t)ch]) cfg[(size_t)ch].fm_hist_at = cur_de;
-            std::fill(fm_listed.begin(), fm_listed.end(), 0);
-            for (int ch : lf) {
-                ChanCfg &c = cfg[(size_t)ch];
-                if (c.fm_hist_at != cur_de) {
-                    QH_HIP(hipMemcpyAsync(hist_de[cur_de] + (size_t)ch * kHistBand, hist_de[c.fm_hist_at] + (size_t)ch * kHistBand,
-                                          kHistBand * sizeof(double2), hipMemcpyDeviceToDevice, stream));
-                    QH_HIP(hipMemcpyAsync(hist_aud[cur_aud] + (size_t)ch * kHistBand, hist_aud[c.fm_hist_at] + (size_t)ch * kHistBand,
-                                          kHistBand * sizeof(double2), hipMemcpyDeviceToDevice, stream));
-                    if (lhist[2][0] && lhist[2][1])             // ... and the partitioned forms' long delay lines (nc > 4096)
-                        QH_HIP(hipMemcpyAsync(lhist[2][cur_de] + (size_t)ch * kLongHist, lhist[2][c.fm_hist_at] + (size_t)ch * kLongHist,
-                                              kLongHist * sizeof(double2), hipMemcpyDeviceToDevice, stream));
-                    if (lhist[3][0] && lhist[3][1])
-                        QH_HIP(hipMemcpyAsync(lhist[3][cur_aud] + (size_t)ch * kLongHist, lhist[3][c.fm_hist_at] + (size_t)ch * kLongHist,
-                                              kLongHist * sizeof(double2), hipMemcpyDeviceToDevice, stream));
-                }
-                c.fm_hist_at = cur_de;
-                fm_listed[(size_t)ch] = 1;
-            }
-        }
-        if (n_amsq && !amsq_prm) {
-            QH_HIP(dev_alloc(&amsq_prm, (size_t)nch));
-            QH_HIP(dev_alloc(&amsq_state, (size_t)nch));
-            QH_HIP(hipMemsetAsync(amsq_state, 0, (size_t)nch * sizeof(AmsqState), stream));
-            // compute_slews, amsq.c:28-46, with muted_gain 0 and 70 ms up / down (RXA.c:166-167,172): theta accumulates as there
-            amsq_ntup = (int)(0.070 * rate); amsq_ntdown = (int)(0.070 * rate);
-            std::vector<double> up((size_t)amsq_ntup + 1), down((size_t)amsq_ntdown + 1);
-            double delta = kPiRef / (double)amsq_ntup, theta = 0.0;
-            for (int i = 0; i <= amsq_ntup; i++) { up[(size_t)i] = 0.0 + (1.0 - 0.0) * 0.5 * (1.0 - std::cos(theta)); theta += delta; }
-            delta = kPiRef / (double)amsq_ntdown; theta = 0.0;
-            for (int i = 0; i <= amsq_ntdown; i++) { down[(size_t)i] = 0.0 + (1.0 - 0.0) * 0.5 * (1.0 + std::cos(theta)); theta += delta; }
-            QH_HIP(dev_alloc(&amsq_cup, up.size()));
-            QH_HIP(dev_alloc(&amsq_cdown, down.size()));
-            QH_HIP(hipMemcpyAsync(amsq_cup, up.data(), up.size() * 8, hipMemcpyHostToDevice, stream));
-            QH_HIP(hipMemcpyAsync(amsq_cdown, down.data(), down.size() * 8, hipMemcpyHostToDevice, stream));
-            QH_HIP(hipStreamSynchronize(stream));
-            dev_bytes += (long long)nch * (sizeof(AmsqParam) + sizeof(AmsqState)) + (long long)(up.size() + down.size()) * 8;
-            for (ChanCfg &c : cfg) c.amsq_dirty = true;
-        }
-        if (any_lms && !lms_prm[0]) {
-            for (int f = 0; f < 2; f++) {
-                QH_HIP(dev_alloc(&lms_prm[f], (size_t)nch));
-                QH_HIP(dev_alloc(&lms_state[f], (size_t)nch));
-                // create_anf: lidx 1.0, ngamma 6.25e-12; create_anr: lidx 120.0, ngamma 0.001 (RXA.c:289-292,309-312)
-                std::vector<LmsState> init((size_t)nch);
-                std::memset(init.data(), 0, init.size() * sizeof(LmsState));
-                for (LmsState &st : init) { st.lidx = f ? 120.0 : 1.0; st.ngamma = f ? 0.001 : 6.25e-12; }
-                QH_HIP(hipMemcpyAsync(lms_state[f], init.data(), init.size() * sizeof(LmsState), hipMemcpyHostToDevice, stream));
-                QH_HIP(hipStreamSynchronize(stream));
-                dev_bytes += (long long)nch * (sizeof(LmsParam) + sizeof(LmsState));
-            }
-            for (ChanCfg &c : cfg) { c.lms[0].dirty = c.lms[1].dirty = true; c.lms[0].flush = c.lms[1].flush = false; }
-        }
-        n_sam0 = n_sam0_new;
-        n_am = (int)la.size(); n_sam = (int)ls.size(); n_fm = (int)lf.size(); n_bp1 = (int)lb.size(); n_plain = (int)lp.size();
-        n_agc_cur_stale = (int)lgc_s.size(); n_agc_other_stale = (int)lgo_s.size();
-        lgc.insert(lgc.end(), lgc_s.begin(), lgc_s.end()); lgo.insert(lgo.end(), lgo_s.begin(), lgo_s.end());
-        n_agc_cur = (int)lgc.size(); n_agc_other = (int)lgo.size();
-        n_lim = (int)ll.size();
-        if (n_lim) {
-            if (!list_lim) {
-                QH_HIP(dev_alloc(&list_lim, (size_t)nch));
-                QH_HIP(dev_alloc(&lim_prm, (size_t)nch));
-                QH_HIP(dev_alloc(&lim_state, (size_t)nch));
-                dev_bytes += (long long)nch * (sizeof(AgcParam) + sizeof(AgcState) + sizeof(int));
-                for (ChanCfg &c : cfg) c.lim_dirty = true;
-            }
-            QH_HIP(hipMemcpyAsync(list_lim, ll.data(), ll.size() * sizeof(int), hipMemcpyHostToDevice, stream));
-        }
-        auto put = [&](int *dst, const std::vector<int> &v) -> hipError_t {
-            return v.empty() ? hipSuccess : hipMemcpyAsync(dst, v.data(), v.size() * sizeof(int), hipMemcpyHostToDevice, stream);
-        };
-        QH_HIP(put(list_am, la)); QH_HIP(put(list_sam, ls)); QH_HIP(put(list_fm, lf)); QH_HIP(put(list_bp1, lb)); QH_HIP(put(list_plain, lp));
-        QH_HIP(put(list_agc_cur, lgc)); QH_HIP(put(list_agc_other, lgo)); QH_HIP(put(list_rest, lrest)); QH_HIP(put(list_usb, lusb)); QH_HIP(put(list_rb, lrb));
-        n_rest = (int)lrest.size(); n_usb = (int)lusb.size(); n_rb = (int)lrb.size();
-        {
-            // partners: neighbours in the list, ordered so that equal designs are neighbours; a channel left over is its own partner
-            auto bp1_real = [&](int ch) { const ChanCfg &c = cfg[(size_t)ch]; return c.bp1_run && c.bp1_flow == -c.bp1_fhigh && !c.mp; };
-            auto bp1_same = [&](int x, int y) {
-                const ChanCfg &p = cfg[(size_t)x], &q = cfg[(size_t)y];
-                return p.bp1_nc == q.bp1_nc && p.bp1_wintype == q.bp1_wintype && p.bp1_fhigh == q.bp1_fhigh && p.bp1_gain == q.bp1_gain;
-            };
-            auto bp1_pairs = [&](std::vector<int> v) {
-                std::vector<int> pr;
-                for (int ch : v) if (!bp1_real(ch)) return pr;
-                std::stable_sort(v.begin(), v.end(), [&](int x, int y) {
-                    const ChanCfg &p = cfg[(size_t)x], &q = cfg[(size_t)y];
-                    if (p.bp1_fhigh != q.bp1_fhigh) return p.bp1_fhigh < q.bp1_fhigh;
-                    if (p.bp1_nc != q.bp1_nc) return p.bp1_nc < q.bp1_nc;
-                    if (p.bp1_wintype != q.bp1_wintype) return p.bp1_wintype < q.bp1_wintype;
-                    return p.bp1_gain < q.bp1_gain;
-                });
-                for (size_t i = 0; i < v.size();) {
-                    if (i + 1 < v.size() && bp1_same(v[i], v[i + 1])) { pr.push_back(v[i]); pr.push_back(v[i + 1]); i += 2; }
-                    else { pr.push_back(v[i]); pr.push_back(v[i]); i += 1; }
-                }
-                return pr;
-            };
-            std::vector<int> pf, pa = bp1_pairs(la), ps = bp1_pairs(ls);
-            for (size_t i = 0; i < lf.size(); i += 2) { pf.push_back(lf[i]); pf.push_back(i + 1 < lf.size() ? lf[i + 1] : lf[i]); }
-            QH_HIP(put(pairs_fm, pf)); QH_HIP(put(pairs_am, pa)); QH_HIP(put(pairs_sam, ps));
-            np_fm = (int)pf.size() / 2; np_am = (int)pa.size() / 2; np_sam = (int)ps.size() / 2;
-        }
-        for (int f = 0; f < 2; f++) for (int k = 0; k < 3; k++) QH_HIP(put(list_lms[f][k], lms_l[f][k]));
-        QH_HIP(put(list_bp1p[0], lbp[0])); QH_HIP(put(list_bp1p[1], lbp[1]));
-        QH_HIP(put(list_fix[0], lfix[0])); QH_HIP(put(list_fix[1], lfix[1])); QH_HIP(put(list_amsq, lsq));
-        if (ap_lists) { QH_HIP(put(list_ap[0], lap[0])); QH_HIP(put(list_ap[1], lap[1])); }
-        for (int k = 0; k < 3; k++) QH_HIP(put(list_emnr[k], lem[k]));
-        QH_HIP(put(list_snb[0], lsn[0])); QH_HIP(put(list_snb[1], lsn[1])); QH_HIP(put(list_snba, lsnba));
-        std::vector<double> fg((size_t)nch);
-        for (int ch = 0; ch < nch; ch++) fg[(size_t)ch] = cfg[(size_t)ch].agc_fixed;
-        QH_HIP(hipMemcpyAsync(fix_gain, fg.data(), fg.size() * sizeof(double), hipMemcpyHostToDevice, stream));
-        QH_HIP(hipStreamSynchronize(stream));
-        lists_dirty = false;
-    }
+    if (lists_dirty) if (int rc = refresh_lists()) return rc;
     int want_nc = 0, want_mp = -1;
     for (int ch = 0; ch < nch; ch++) {
         ChanCfg &c = cfg[(size_t)ch];
@@ -1129,203 +1271,16 @@ int Engine::refresh_demod()
             if (want_mp >= 0 && want_mp != c.mp) return set_error(QH_ERR_UNSUPPORTED, "FM channels with different RXASetMP in one engine");
             want_mp = c.mp;
         }
-        if (c.agc_dirty) {
-            // loadWcpAGC, wdsp/wcpAGC.c:115-146, with create_rxa's constants (RXA.c:335-358)
-            const double n_tau = 4.0, max_input = 1.0, out_targ = 1.0, tau_fast_back = 0.250, tau_fast_decay = 0.005;
-            const double tau_hang_backmult = 0.500, tau_hang_decay = 0.100;
-            AgcParam q{};
-            q.attack_buffsize = (int)std::ceil(rate * n_tau * c.agc_tau_attack);
-            if (q.attack_buffsize + 2 > kAgcRing)
-                return set_error(QH_ERR_UNSUPPORTED, "AGC attack of %g s needs a look-ahead of %d samples (limit %d)", c.agc_tau_attack,
-                                 q.attack_buffsize, kAgcRing - 2);
-            c.agc_abuf = q.attack_buffsize;
-            q.attack_mult = 1.0 - std::exp(-1.0 / (rate * c.agc_tau_attack));
-            q.decay_mult = 1.0 - std::exp(-1.0 / (rate * c.agc_tau_decay));
-            q.fast_decay_mult = 1.0 - std::exp(-1.0 / (rate * tau_fast_decay));
-            q.fast_backmult = 1.0 - std::exp(-1.0 / (rate * tau_fast_back));
-            q.onemfast_backmult = 1.0 - q.fast_backmult;
-            q.out_target = out_targ * (1.0 - std::exp(-n_tau)) * 0.9999;
-            q.min_volts = q.out_target / (c.agc_var_gain * c.agc_max_gain);
-            q.inv_out_target = 1.0 / q.out_target;
-            double tmp = std::log10(q.out_target / (max_input * c.agc_var_gain * c.agc_max_gain));
-            if (tmp == 0.0) tmp = 1e-16;
-            q.slope_constant = (q.out_target * (1.0 - 1.0 / c.agc_var_gain)) / tmp;
-            q.inv_max_input = 1.0 / max_input;
-            tmp = std::pow(10.0, (c.agc_hang_thresh - 1.0) / 0.125);
-            q.hang_level = (max_input * tmp + (q.out_target / (c.agc_var_gain * c.agc_max_gain)) * (1.0 - tmp)) * 0.637;
-            q.hang_backmult = 1.0 - std::exp(-1.0 / (rate * tau_hang_backmult));
-            q.onemhang_backmult = 1.0 - q.hang_backmult;
-            q.hang_decay_mult = 1.0 - std::exp(-1.0 / (rate * tau_hang_decay));
-            q.pop_ratio = 5.0;
-            q.hang_count_init = (int)(c.agc_hangtime * rate);
-            q.hang_enable = 1;
-            q.pmode = 1;
-            QH_HIP(hipMemcpyAsync(agc_prm + ch, &q, sizeof(q), hipMemcpyHostToDevice, stream));
-            QH_HIP(hipStreamSynchronize(stream));
-            c.agc_dirty = false;
-        }
-        if (emnr_chan && c.emnr_dirty) {
-            if (c.emnr_run && (c.emnr_npe < 0 || c.emnr_npe > 2 || c.emnr_gain_method < 0 || c.emnr_gain_method > 3))
-                return set_error(QH_ERR_UNSUPPORTED, "EMNR: gain methods 0..3 and noise estimators 0..2");
-            const EmnrChan ec{ c.emnr_gain_method, c.emnr_npe, c.emnr_ae, 0, c.emnr_ae_zeta, c.emnr_ae_psi, c.emnr_train_zeta, c.emnr_train_t2 };
-            QH_HIP(hipMemcpyAsync(emnr_chan + ch, &ec, sizeof(ec), hipMemcpyHostToDevice, stream));
-            QH_HIP(hipStreamSynchronize(stream));
-            c.emnr_dirty = false;
-        }
-        if (emnr_state && c.emnr_flush) {           // flush_emnr, emnr.c:583-596: the accumulators and their indices, not the estimators
-            EmnrScalars sc;
-            QH_HIP(hipMemcpyAsync(&sc, emnr_scal + ch, sizeof(sc), hipMemcpyDeviceToHost, stream));
-            QH_HIP(hipStreamSynchronize(stream));
-            sc.iainidx = sc.iaoutidx = sc.oaoutidx = sc.nsamps = sc.saveidx = 0; sc.oainidx = emnr_prm.init_oainidx;
-            QH_HIP(hipMemcpyAsync(emnr_scal + ch, &sc, sizeof(sc), hipMemcpyHostToDevice, stream));
-            QH_HIP(hipMemsetAsync(emnr_state + (size_t)ch * kEmnrStateDoubles, 0, (size_t)EO_PREVG * sizeof(double), stream));
-            QH_HIP(hipStreamSynchronize(stream));
-            c.emnr_flush = false;
-        }
-        if (snba_state && c.snba_taps_dirty) {
-            // calc_resample for outresamp (12 kHz -> dsp_rate, gain 2, resample.c:35-79) with the channel's output bandwidth
-            const SnbaParam &q = snba_prm;
-            if (q.ratio > 1) {
-                const int L = q.ratio, ncoef = q.cpp_out * L;
-                const double full = (double)(12000 * L), fc = c.snba_f_high == 0.0 ? 0.45 * 12000.0 : c.snba_f_high;
-                const double lo = c.snba_f_low < 0.0 ? -fc / full : c.snba_f_low / full;
-                const std::vector<cd> imp = fir_bandpass(ncoef, lo, fc / full, 1.0, 1, 0, 2.0 * (double)L);
-                std::vector<double> hp((size_t)ncoef);
-                size_t i = 0;
-                for (int j = 0; j < L; j++) for (int k = 0; k < ncoef; k += L) hp[i++] = imp[(size_t)(j + k)].real();
-                QH_HIP(hipMemcpyAsync(snba_hout + (size_t)ch * ncoef, hp.data(), hp.size() * sizeof(double), hipMemcpyHostToDevice, stream));
-                QH_HIP(hipStreamSynchronize(stream));
-            }
-            c.snba_taps_dirty = false;
-        }
-        if (snba_state && (c.snba_flush || c.snba_rout_flush)) {
-            const SnbaParam &q = snba_prm;
-            double *st = snba_state + (size_t)ch * q.state_doubles;
-            if (q.cpp_out > 1) QH_HIP(hipMemsetAsync(st + q.off_rout, 0, (size_t)(q.cpp_out - 1) * sizeof(double), stream));
-            if (c.snba_flush) {         // flush_snba, snb.c:161-185: the frame half of xbase, the accumulators, both resamplers
-                QH_HIP(hipMemsetAsync(st + kSnbX, 0, (size_t)kSnbX * sizeof(double), stream));
-                QH_HIP(hipMemsetAsync(st + q.off_inacc, 0, (size_t)(q.state_doubles - q.off_inacc) * sizeof(double), stream));
-                const SnbaIdx ix{ 0, 0, 0, 0, q.init_oaoutidx, { 0, 0, 0 } };
-                QH_HIP(hipMemcpyAsync(snba_idx + ch, &ix, sizeof(ix), hipMemcpyHostToDevice, stream));
-                QH_HIP(hipStreamSynchronize(stream));
-            }
-        }
-        c.snba_flush = c.snba_rout_flush = false;
-        if (amsq_prm && c.amsq_dirty) {
-            // calc_amsq, amsq.c:48-64: 10 ms average (RXA.c:165)
-            AmsqParam q{};
-            q.avm = std::exp(-1.0 / (rate * 0.010)); q.onem_avm = 1.0 - q.avm;
-            q.tail_thresh = c.amsq_tail_thresh; q.unmute_thresh = c.amsq_unmute_thresh; q.min_tail = 0.0; q.max_tail = c.amsq_max_tail;
-            q.muted_gain = 0.0; q.rate = rate; q.ntup = amsq_ntup; q.ntdown = amsq_ntdown;
-            QH_HIP(hipMemcpyAsync(amsq_prm + ch, &q, sizeof(q), hipMemcpyHostToDevice, stream));
-            QH_HIP(hipStreamSynchronize(stream));
-            c.amsq_dirty = false;
-        }
-        for (int f = 0; f < 2 && lms_prm[0]; f++) {
-            ChanCfg::Lms &m = c.lms[f];
-            if (m.dirty) {
-                if (m.run && (m.taps < 1 || m.taps > 64 || m.delay < 1 || m.delay > 64))
-                    return set_error(QH_ERR_UNSUPPORTED, "%s: taps %d / delay %d (1..64 each: one tap per lane)", f ? "ANR" : "ANF", m.taps, m.delay);
-                // lidx_min, lidx_max, den_mult, lincr, ldecr of create_rxa (RXA.c:290-295,310-315)
-                const LmsParam q{ m.taps, m.delay, f, 0, m.two_mu, m.gamma, f ? 120.0 : 0.0, 200.0, 6.25e-10, 1.0, 3.0 };
-                QH_HIP(hipMemcpyAsync(lms_prm[f] + ch, &q, sizeof(q), hipMemcpyHostToDevice, stream));
-                QH_HIP(hipStreamSynchronize(stream));
-                m.dirty = false;
-            }
-            if (m.flush) {          // flush_anf (anf.c:135-140): delay line and weights; lidx / ngamma carry on
-                QH_HIP(hipMemsetAsync(lms_state[f] + ch, 0, offsetof(LmsState, lidx), stream));
-                m.flush = false;
-            }
-        }
-        if (c.lim_dirty && lim_prm) {
-            // calc_fmd's create_wcpagc(1, 5, 1, ..., 0.001, 0.008, 4, lim_gain, 1.0, 1.0, 1.0, 0.9, 0.250, 0.004, 4.0, 0,
-            // 0.500, 0.500, 2.000, 0.100) (fmd.c:48-72) through loadWcpAGC (wcpAGC.c:115-146); a new limiter starts cleared
-            const double tau_attack = 0.001, tau_decay = 0.008, n_tau = 4.0, max_gain = c.lim_gain, var_gain = 1.0, max_input = 1.0,
-                         out_targ = 0.9, tau_fast_back = 0.250, tau_fast_decay = 0.004, tau_hang_backmult = 0.500, hangtime = 0.500,
-                         hang_thresh = 2.000, tau_hang_decay = 0.100;
-            AgcParam q{};
-            q.attack_buffsize = (int)std::ceil(rate * n_tau * tau_attack);
-            q.attack_mult = 1.0 - std::exp(-1.0 / (rate * tau_attack));
-            q.decay_mult = 1.0 - std::exp(-1.0 / (rate * tau_decay));
-            q.fast_decay_mult = 1.0 - std::exp(-1.0 / (rate * tau_fast_decay));
-            q.fast_backmult = 1.0 - std::exp(-1.0 / (rate * tau_fast_back));
-            q.onemfast_backmult = 1.0 - q.fast_backmult;
-            q.out_target = out_targ * (1.0 - std::exp(-n_tau)) * 0.9999;
-            q.min_volts = q.out_target / (var_gain * max_gain);
-            q.inv_out_target = 1.0 / q.out_target;
-            double tmp = std::log10(q.out_target / (max_input * var_gain * max_gain));
-            if (tmp == 0.0) tmp = 1e-16;
-            q.slope_constant = (q.out_target * (1.0 - 1.0 / var_gain)) / tmp;
-            q.inv_max_input = 1.0 / max_input;
-            tmp = std::pow(10.0, (hang_thresh - 1.0) / 0.125);
-            q.hang_level = (max_input * tmp + (q.out_target / (var_gain * max_gain)) * (1.0 - tmp)) * 0.637;
-            q.hang_backmult = 1.0 - std::exp(-1.0 / (rate * tau_hang_backmult));
-            q.onemhang_backmult = 1.0 - q.hang_backmult;
-            q.hang_decay_mult = 1.0 - std::exp(-1.0 / (rate * tau_hang_decay));
-            q.pop_ratio = 4.0;
-            q.hang_count_init = (int)(hangtime * rate);
-            q.hang_enable = 0;
-            q.pmode = 1;
-            QH_HIP(hipMemcpyAsync(lim_prm + ch, &q, sizeof(q), hipMemcpyHostToDevice, stream));
-            QH_HIP(hipMemsetAsync(lim_state + ch, 0, sizeof(AgcState), stream));
-            const int oi = kAgcRing - 1;                            // out_index = -1 (calc_wcpagc, wcpAGC.c:34)
-            QH_HIP(hipMemcpyAsync(&lim_state[ch].out_index, &oi, sizeof(int), hipMemcpyHostToDevice, stream));
-            QH_HIP(hipStreamSynchronize(stream));
-            c.lim_dirty = false;
-        }
-        if (!c.demod_dirty) continue;
-        const int lf = c.levelfade;
-        const double again = rate / (c.fm_dev * kTwoPiRef);                 // wdsp/fmd.c:44
-        SamChanParam sp{ c.sbmode, c.levelfade };
-        SnotchParam sn{};
-        {   // calc_snotch, wdsp/iir.c:35-49 (bw 0.0002, fmd.c:47)
-            const double fn = c.ctcss_freq / (double)dsp_rate, csn = std::cos(kTwoPiRef * fn), qr = 1.0 - 3.0 * 0.0002;
-            const double qk = (1.0 - 2.0 * qr * csn + qr * qr) / (2.0 * (1.0 - csn));
-            sn.a0 = qk; sn.a1 = -2.0 * qk * csn; sn.a2 = qk; sn.b1 = 2.0 * qr * csn; sn.b2 = -qr * qr; sn.run = c.ctcss_run;
-        }
-        QH_HIP(hipMemcpyAsync(levelfade + ch, &lf, sizeof(int), hipMemcpyHostToDevice, stream));
-        QH_HIP(hipMemcpyAsync(fm_again + ch, &again, sizeof(double), hipMemcpyHostToDevice, stream));
-        QH_HIP(hipMemcpyAsync(sam_prm + ch, &sp, sizeof(sp), hipMemcpyHostToDevice, stream));
-        QH_HIP(hipMemcpyAsync(sn_prm + ch, &sn, sizeof(sn), hipMemcpyHostToDevice, stream));
-        if (c.ctcss_flush) {                    // calc_snotch ends with flush_snotch, wdsp/iir.c:48
-            QH_HIP(hipMemsetAsync(sn_state + ch, 0, sizeof(SnotchState), stream));
-            c.ctcss_flush = false;
-        }
-        QH_HIP(hipStreamSynchronize(stream));
-        c.demod_dirty = false;
+        if (int rc = prm_agc(c, ch)) return rc;
+        if (int rc = prm_emnr(c, ch)) return rc;
+        if (int rc = prm_snba(c, ch)) return rc;
+        if (int rc = prm_amsq(c, ch)) return rc;
+        if (int rc = prm_lms(c, ch)) return rc;
+        if (int rc = prm_lim(c, ch)) return rc;
+        if (int rc = prm_detect(c, ch)) return rc;
     }
     if (want_mp >= 0) fm_mp = want_mp;
-    if (want_nc && (want_nc != fm_nc_built || fm_mp != fm_mp_built || fm_nfft_built != 2 * bnfft + (band2g ? 1 : 0))) {
-        // create_fmd, wdsp/fmd.c:108-116: de-emphasis by frequency sampling, audio band-pass 0.8*f_low .. 1.1*f_high
-        const double f_low = 300.0, f_high = 3000.0, afgain = 0.5;
-        std::vector<cd> de = fc_impulse(want_nc, f_low, f_high, +20.0 * std::log10(f_high / f_low), 0.0, 1, rate,
-                                        1.0 / (2.0 * dsp_size), 0, 0);
-        std::vector<cd> au = fir_bandpass(want_nc, 0.8 * f_low, 1.1 * f_high, rate, 0, 1, afgain / (2.0 * dsp_size));
-        if (fm_mp) { de = mp_imp(de, 16, 0); au = mp_imp(au, 16, 0); }     // SetRXAFMMPde / MPaud, wdsp/RXA.c:956-957
-        fm_mp_built = fm_mp;
-        for (auto &v : de) v *= (double)(2 * dsp_size);
-        for (auto &v : au) v *= (double)(2 * dsp_size);
-        de_real = true;
-        for (const cd &v : de) de_real = de_real && v.imag() == 0.0;
-        if (long_parts[2] > 1) {
-            if (int rc = long_masks_upload(2, 0, de)) return rc;
-            if (int rc = long_masks_upload(3, 0, au)) return rc;
-            de.resize((size_t)kLongPart); au.resize((size_t)kLongPart);      // (the one-tile masks are not used then)
-        }
-        if (int rc = upload(mask_de, band_mask(de), stream)) return rc;
-        if (int rc = upload(mask_aud, band_mask(au), stream)) return rc;
-        fm_nfft_built = 2 * bnfft + (band2g ? 1 : 0);
-        if (fm_nc_built && fm_nc_built != want_nc) {      // setNc_fircore zeroes the delay lines, wdsp/firmin.c:454-466
-            for (int i = 0; i < 2; i++) {
-                if (lhist[2][i]) QH_HIP(hipMemsetAsync(lhist[2][i], 0, (size_t)nch * kLongHist * sizeof(double2), stream));
-                if (lhist[3][i]) QH_HIP(hipMemsetAsync(lhist[3][i], 0, (size_t)nch * kLongHist * sizeof(double2), stream));
-                QH_HIP(hipMemsetAsync(hist_de[i], 0, (size_t)nch * kHistBand * sizeof(double2), stream));
-                QH_HIP(hipMemsetAsync(hist_aud[i], 0, (size_t)nch * kHistBand * sizeof(double2), stream));
-            }
-        }
-        fm_nc_built = want_nc;
-    }
-    return QH_OK;
+    return fm_filters(want_nc);
 }
 
 // the frame advance and the two accumulators' sizes for an overlap (calc_snba, snb.c:45-65)
@@ -1355,8 +1310,7 @@ int Engine::snba_set_ovrlp(int ovrlp)
                        (size_t)nch, hipMemcpyDeviceToHost));
     snba_plan(ovrlp);
     const SnbaParam &q = snba_prm;
-    (void)hipFree(snba_state); snba_state = nullptr;
-    QH_HIP(dev_alloc(&snba_state, (size_t)nch * q.state_doubles));
+    if (int rc = alloc(snba_state, (long long)nch * q.state_doubles)) return rc;
     QH_HIP(qh::dev_zero(snba_state, (size_t)nch * q.state_doubles * sizeof(double)));
     QH_HIP(hipMemcpy2D(snba_state, (size_t)q.state_doubles * sizeof(double), frames.data(), 2 * kSnbX * sizeof(double), 2 * kSnbX * sizeof(double),
                        (size_t)nch, hipMemcpyHostToDevice));
@@ -1379,16 +1333,15 @@ int Engine::snba_alloc()
     q.cpp_out = q.ratio > 1 ? 141 : 1;
     q.asize = 64; q.npasses = 2; q.b = 10; q.pre = 2; q.post = 2; q.k1 = 8.0; q.k2 = 20.0; q.pmultmin = 0.5;
     snba_plan(snba_ovrlp);
-    QH_HIP(dev_alloc(&snba_state, (size_t)nch * q.state_doubles));
-    QH_HIP(hipMemsetAsync(snba_state, 0, (size_t)nch * q.state_doubles * sizeof(double), stream));
-    QH_HIP(dev_alloc(&snba_idx, (size_t)nch));
+    if (int rc = alloc(snba_state, (long long)nch * q.state_doubles, true)) return rc;
+    if (int rc = alloc(snba_idx, nch)) return rc;
     std::vector<SnbaIdx> ix((size_t)nch, SnbaIdx{ 0, 0, 0, 0, q.init_oaoutidx, { 0, 0, 0 } });
     QH_HIP(hipMemcpyAsync(snba_idx, ix.data(), ix.size() * sizeof(SnbaIdx), hipMemcpyHostToDevice, stream));
-    QH_HIP(dev_alloc(&snba_scratch, (size_t)nch * kSnbX * kSnbX));
-    QH_HIP(dev_alloc(&snba_tune, (size_t)nch));
+    if (int rc = alloc(snba_scratch, (long long)nch * kSnbX * kSnbX)) return rc;
+    if (int rc = alloc(snba_tune, nch)) return rc;
     snba_tune_dirty = true;
-    QH_HIP(dev_alloc(&snba_hin, (size_t)q.cpp_in));
-    QH_HIP(dev_alloc(&snba_hout, (size_t)nch * q.cpp_out * q.ratio));
+    if (int rc = alloc(snba_hin, q.cpp_in)) return rc;
+    if (int rc = alloc(snba_hout, (long long)nch * q.cpp_out * q.ratio)) return rc;
     std::vector<double> hin((size_t)q.cpp_in, 1.0);
     if (q.ratio > 1) {      // inresamp: dsp_rate -> 12 kHz, 250 .. 5400 Hz, gain 2 (snb.c:43-44)
         const double full = (double)dsp_rate;
@@ -1396,13 +1349,9 @@ int Engine::snba_alloc()
         for (int i = 0; i < q.cpp_in; i++) hin[(size_t)i] = imp[(size_t)i].real();
     }
     QH_HIP(hipMemcpyAsync(snba_hin, hin.data(), hin.size() * sizeof(double), hipMemcpyHostToDevice, stream));
-    QH_HIP(dev_alloc(&mask_snb, (size_t)nch * kBandNfftMax));
-    for (int i = 0; i < 2; i++) {
-        QH_HIP(dev_alloc(&hist_snb[i], (size_t)nch * kHistBand));
-        QH_HIP(hipMemsetAsync(hist_snb[i], 0, (size_t)nch * kHistBand * sizeof(double2), stream));
-    }
+    if (int rc = alloc(mask_snb, (long long)nch * kBandNfftMax)) return rc;
+    for (double2 *&h : hist_snb) if (int rc = alloc(h, (long long)nch * kHistBand, true)) return rc;
     QH_HIP(hipStreamSynchronize(stream));
-    dev_bytes += (long long)nch * ((long long)q.state_doubles * 8 + (long long)kSnbX * kSnbX * 8 + (long long)kBandNfftMax * 16 + 2LL * kHistBand * 16);
     snb_listed.assign((size_t)nch, 0);
     for (ChanCfg &c : cfg) { c.snba_taps_dirty = true; c.snb_dirty = true; c.snba_flush = c.snba_rout_flush = false; c.snb_flush = false; c.snb_hist_at = cur_snb; }
     return QH_OK;
@@ -1483,14 +1432,14 @@ int Engine::emnr_alloc()
         for (int ku = 0; ku < kEmnrU; ku++) st[(size_t)(EO_AMB + ku * kEmnrPad + k)] = 1.0e300;
         st[(size_t)(EO_SSIG + k)] = 0.5; st[(size_t)(EO_SPBAR + k)] = 0.5;
     }
-    QH_HIP(dev_alloc(&emnr_state, (size_t)nch * kEmnrStateDoubles));
-    QH_HIP(dev_alloc(&emnr_scal, (size_t)nch));
-    QH_HIP(dev_alloc(&emnr_chan, (size_t)nch));
-    QH_HIP(dev_alloc(&emnr_window, (size_t)kEmnrF));
-    QH_HIP(dev_alloc(&emnr_GG, (size_t)241 * 241));
-    QH_HIP(dev_alloc(&emnr_GGS, (size_t)241 * 241));
-    QH_HIP(dev_alloc(&emnr_zeta, (size_t)3600));
-    QH_HIP(dev_alloc(&emnr_zeta_true, (size_t)3600));
+    if (int rc = alloc(emnr_state, (long long)nch * kEmnrStateDoubles)) return rc;
+    if (int rc = alloc(emnr_scal, nch)) return rc;
+    if (int rc = alloc(emnr_chan, nch)) return rc;
+    if (int rc = alloc(emnr_window, kEmnrF)) return rc;
+    if (int rc = alloc(emnr_GG, 241 * 241)) return rc;
+    if (int rc = alloc(emnr_GGS, 241 * 241)) return rc;
+    if (int rc = alloc(emnr_zeta, 3600)) return rc;
+    if (int rc = alloc(emnr_zeta_true, 3600)) return rc;
     const EmnrScalars sc0{ 0, 0, q.init_oainidx, 0, 0, 0, q.V, 0, 1.0 };
     for (int ch = 0; ch < nch; ch++) {
         QH_HIP(hipMemcpyAsync(emnr_state + (size_t)ch * kEmnrStateDoubles, st.data(), st.size() * 8, hipMemcpyHostToDevice, stream));
@@ -1503,7 +1452,6 @@ int Engine::emnr_alloc()
     QH_HIP(hipMemcpyAsync(emnr_zeta_true, h_zeta_true.data(), h_zeta_true.size() * 4, hipMemcpyHostToDevice, stream));
     QH_HIP(hipStreamSynchronize(stream));
     QH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&emnr_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, emnr_lds_bytes()));
-    dev_bytes += (long long)nch * (kEmnrStateDoubles * 8 + sizeof(EmnrScalars) + sizeof(EmnrChan)) + 2 * 241 * 241 * 8;
     for (ChanCfg &c : cfg) { c.emnr_dirty = true; c.emnr_flush = false; }
     return QH_OK;
 }
@@ -1513,7 +1461,7 @@ int Engine::ensure_buffers(long long n_mid)
     if (n_mid <= buf_cap) return QH_OK;
     if (int rc = quiesce()) return rc;
     for (double2 *&b : buf)
-        if (int rc = realloc_dev(b, buf_cap * nch, n_mid * nch)) return rc;
+        if (int rc = alloc(b, n_mid * nch)) return rc;
     buf_cap = n_mid;
     return QH_OK;
 }
@@ -1536,7 +1484,7 @@ int Engine::ensure_meter_partials(long long n_mid, int lout)
     if (need <= m_part_cap) return QH_OK;
     if (int rc = quiesce()) return rc;
     for (double2 *&m : m_part)
-        if (int rc = realloc_dev(m, m_part_cap * nch, need * nch)) return rc;
+        if (int rc = alloc(m, need * nch)) return rc;
     m_part_cap = need;
     return QH_OK;
 }
@@ -1748,24 +1696,18 @@ int Engine::long_stage_alloc(int sid, bool shared_mask)
 {
     if (lmask[sid]) return QH_OK;
     if (int rc = quiesce()) return rc;
-    const size_t rows = shared_mask ? 1 : (size_t)nch;
-    QH_HIP(dev_alloc(&lmask[sid], rows * kLongParts * kBandNfftMax));
-    QH_HIP(hipMemsetAsync(lmask[sid], 0, rows * kLongParts * kBandNfftMax * sizeof(double2), stream));
-    QH_HIP(dev_alloc(&lrow_parts[sid], rows));
-    QH_HIP(hipMemsetAsync(lrow_parts[sid], 0, rows * sizeof(int), stream));
-    for (int i = 0; i < 2; i++) {
-        QH_HIP(dev_alloc(&lhist[sid][i], (size_t)nch * kLongHist));
-        QH_HIP(hipMemsetAsync(lhist[sid][i], 0, (size_t)nch * kLongHist * sizeof(double2), stream));
-    }
-    dev_bytes += (long long)(rows * kLongParts * kBandNfftMax + 2 * (size_t)nch * kLongHist) * (long long)sizeof(double2) + (long long)(rows * sizeof(int));
+    const long long rows = shared_mask ? 1 : nch;
+    if (int rc = alloc(lmask[sid], rows * kLongParts * kBandNfftMax, true)) return rc;
+    if (int rc = alloc(lrow_parts[sid], rows, true)) return rc;
+    for (double2 *&h : lhist[sid]) if (int rc = alloc(h, (long long)nch * kLongHist, true)) return rc;
     return QH_OK;
 }
 int Engine::long_buffers()
 {
     if (lcat && lcat_cap == buf_cap) return QH_OK;
     if (int rc = quiesce()) return rc;
-    if (int rc = realloc_dev(lcat, lcat ? nch * (kLongHist + lcat_cap) : 0, nch * (kLongHist + buf_cap))) return rc;
-    if (int rc = realloc_dev(ltmp, nch * lcat_cap, nch * buf_cap)) return rc;
+    if (int rc = alloc(lcat, nch * (kLongHist + buf_cap))) return rc;
+    if (int rc = alloc(ltmp, nch * buf_cap)) return rc;
     lcat_cap = buf_cap;
     return QH_OK;
 }
@@ -1780,9 +1722,7 @@ int Engine::long_masks_upload(int sid, long long row, const std::vector<cd> &h)
         std::copy(m.begin(), m.end(), all.begin() + (long)((size_t)p * kBandNfftMax));
     }
     QH_HIP(hipMemcpyAsync(lmask[sid] + (size_t)row * kLongParts * kBandNfftMax, all.data(), all.size() * sizeof(cd), hipMemcpyHostToDevice, stream));
-    QH_HIP(hipMemcpyAsync(lrow_parts[sid] + row, &own, sizeof(int), hipMemcpyHostToDevice, stream));
-    QH_HIP(hipStreamSynchronize(stream));
-    return QH_OK;
+    return put_row(lrow_parts[sid], row, own);
 }
 
 // one fircore stage (overlap-save, D = 1) over all channels (list == nullptr) or a sub-set
@@ -1976,9 +1916,9 @@ int Engine::set_sb_phi(long long n, int S)
             for (int i = 0; i < W * W; i++) h[((size_t)li * 2 + set) * W * W + i] = (double)p[(size_t)i];
         }
     if (!sb_phi) {
-        QH_HIP(dev_alloc(&sb_phi, h.size()));
-        QH_HIP(dev_alloc(&sb_sum, (size_t)nch * kSegWaves * kSegMaxGroups * kSbSum));
-        QH_HIP(dev_alloc(&sb_start, (size_t)nch * kSegWaves * kSegMaxGroups * kSbSum));
+        if (int rc = alloc(sb_phi, (long long)h.size())) return rc;
+        if (int rc = alloc(sb_sum, (long long)nch * kSegWaves * kSegMaxGroups * kSbSum)) return rc;
+        if (int rc = alloc(sb_start, (long long)nch * kSegWaves * kSegMaxGroups * kSbSum)) return rc;
     }
     if (int rc = quiesce()) return rc;
     QH_HIP(hipMemcpy(sb_phi, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
@@ -2092,7 +2032,7 @@ int Engine::process_chain(const double *d_in, long long in_stride, double *d_out
     if (meters_on) if (int rc = meters_alloc()) return rc;
     if (int rc = refresh_params()) return rc;
     if (k.mixed) if (int rc = refresh_demod()) return rc;
-    if (n_snba) if (int rc = refresh_params()) return rc;       // bpsnba's mask needs the buffers the line above may just have made
+    if (lists[L_SNBA].n) if (int rc = refresh_params()) return rc;       // bpsnba's mask needs the buffers the line above may just have made
 
     k.n_in = (long long)nblk * dsp_insize;
     k.n_mid = (long long)nblk * dsp_size;
@@ -2108,7 +2048,7 @@ int Engine::process_chain(const double *d_in, long long in_stride, double *d_out
     k.P = band6k ? kOsfir6kP : band2g ? kOsfir8kP : k.meters_fused ? ((k.nc_max - 1 + 255) / 256) * 256 : k.long_mode ? kLongPart - 1 : k.nc_max - 1;
     // audio egress (qh_rxa_process_audio): the narrowing rides in the store of the last kernel when that is an overlap-save
     // band stage or the per-mode path's output pass; other endings write complex doubles to the staging rows and narrow after
-    k.eg_fused = eg.kind && (k.mixed ? n_amsq == 0 : ((k.any_nbp || k.any_bp1) && !k.long_mode));
+    k.eg_fused = eg.kind && (k.mixed ? lists[L_AMSQ].n == 0 : ((k.any_nbp || k.any_bp1) && !k.long_mode));
     if (eg.kind && !k.eg_fused) {
         if (int rc = ensure_abuf(k.n_mid)) return rc;
         k.out = abuf; k.out_stride = abuf_cap;
@@ -2120,10 +2060,10 @@ int Engine::process_chain(const double *d_in, long long in_stride, double *d_out
     if (int rc = run_mixed_front(k)) return rc;     // xshift, xresample, adc meter, xnbp, S meter, xamsqcap, xbpsnbaout 0
     if (int rc = run_am(k)) return rc;              // xamd's AM / SAM channels (and their bp1 when it ends their chain)
     if (k.side) QH_HIP(hipEventRecord(ev_join, side_stream));
-    if (n_fm) if (int rc = run_fm(k)) return rc;    // xfmd
+    if (lists[L_FM].n) if (int rc = run_fm(k)) return rc;    // xfmd
     if (k.side) QH_HIP(hipStreamWaitEvent(stream, ev_join, 0));
-    if (n_snb[1]) snb_inplace(k, list_snb[1], n_snb[1]);       // xbpsnbain / xbpsnbaout at position 1 (RXA.c:576-577)
-    if (n_snb[0] || n_snb[1]) cur_snb ^= 1;
+    if (lists[L_SNB + 1].n) snb_inplace(k, lists[L_SNB + 1].dev, lists[L_SNB + 1].n);       // xbpsnbain / xbpsnbaout at position 1 (RXA.c:576-577)
+    if (lists[L_SNB].n || lists[L_SNB + 1].n) cur_snb ^= 1;
     if (int rc = run_snba(k)) return rc;            // xsnba, RXA.c:578
     // xanf, xanr, xbandpass(bp1) at position 0, xwcpagc, then the same three at position 1 (RXA.c:579-586).  The two bp1
     // launches work on disjoint channel rows of one ping-pong history pair, so the pair flips once for both.
@@ -2131,7 +2071,7 @@ int Engine::process_chain(const double *d_in, long long in_stride, double *d_out
     bp1_at(k, 0);
     // xwcpagc modes 1-4 (sequential per channel); mode 0 rides in the output matrix below unless a position-1 stage follows
     tick(1);
-    if (n_agc_cur || n_agc_other) if (int rc = run_agc(k)) return rc;
+    if (lists[L_AGC_CUR].n || lists[L_AGC_OTHER].n) if (int rc = run_agc(k)) return rc;
     run_output(k);                                  // position 1, agc meter, xwcpagc mode 0 + xpanel, xamsq, egress
     QH_HIP(hipGetLastError());
     return QH_OK;
@@ -2198,35 +2138,35 @@ int Engine::plan_mixed(ChainCall &k)
     // 2 no envelope in nbp0's store, 3 no angles in nbp0's store, 4 no paired real filters, 5 no second stream at all, 6-7 where the second
     // stream forks (counted down from behind the FM channels' nbp0), 8 xfmd's dc removal as a pass of its own (fm_dc_tiled_kernel), 9 the AM
     // fade leveller as a pass of its own (am_level_tiled_kernel)
-    k.split = n_fm > 0 && n_rest > 0 && D > 1 && !meters_on && !n_amsq && !n_snb[0] && !timing && !(dbg_forms & 1);
+    k.split = lists[L_FM].n > 0 && lists[L_REST].n > 0 && D > 1 && !meters_on && !lists[L_AMSQ].n && !lists[L_SNB].n && !timing && !(dbg_forms & 1);
     // ... and when nothing sits between a channel's last filter and the output matrix (no AGC state machine, LMS, EMNR, SNBA,
     // limiter, squelch or position-1 stage anywhere), that last stage -- nbp0 for the plain channels, bp1 for AM / SAM, the CTCSS
     // notch for FM -- applies the matrix in its store and writes the caller's buffer: the output pass (32 B per output sample) goes.
     k.fm_theta_fused = k.split && k.any_nbp && !band6k && !band2g && bnfft == kNfft && !(dbg_forms & 8);
     bool no_lms = true;
-    for (int f = 0; f < 2; f++) for (int p = 0; p < 3; p++) no_lms = no_lms && !n_lms[f][p];
-    k.direct = k.split && !(dbg_forms & 2) && k.every_nbp && !eg.kind && !n_lim && !n_agc_cur && !n_agc_other && !n_snba && !n_snb[1] && no_lms &&
-               !n_emnr[0] && !n_emnr[1] && !n_emnr[2] && !n_fix[0] && !n_fix[1] && !n_bp1p[1] && n_bp1p[0] == n_bp1 && n_rb == n_bp1 &&
-               n_usb + n_fm == n_plain && !n_ap[0] && !n_ap[1] &&
+    for (int f = 0; f < 2; f++) for (int p = 0; p < 3; p++) no_lms = no_lms && !lists[L_LMS + 3 * f + p].n;
+    k.direct = k.split && !(dbg_forms & 2) && k.every_nbp && !eg.kind && !lists[L_LIM].n && !lists[L_AGC_CUR].n && !lists[L_AGC_OTHER].n && !lists[L_SNBA].n && !lists[L_SNB + 1].n && no_lms &&
+               !lists[L_EMNR].n && !lists[L_EMNR + 1].n && !lists[L_EMNR + 2].n && !lists[L_FIX].n && !lists[L_FIX + 1].n && !lists[L_BP1P + 1].n && lists[L_BP1P].n == lists[L_BP1].n && lists[L_RB].n == lists[L_BP1].n &&
+               lists[L_USB].n + lists[L_FM].n == lists[L_PLAIN].n && !lists[L_AP].n && !lists[L_AP + 1].n &&
                // the first stores to `out` come while other channels' input is still being read: not for a caller that works in place
                extents_apart(k.out, k.out_stride, k.n_mid, k.in, k.in_stride, k.n_in, nch);
     // ... and the AM channels' nbp0 leaves the envelope and every tile's share of the fade leveller's averages: one pass does the rest
     k.P_am = ((k.P + 63) / 64) * 64;
-    k.am_fused = k.direct && !(dbg_forms & 4) && n_am > 0 && n_rb == n_am + n_sam && !band6k && !band2g && bnfft == kNfft && k.P_am < bnfft;
+    k.am_fused = k.direct && !(dbg_forms & 4) && lists[L_AM].n > 0 && lists[L_RB].n == lists[L_AM].n + lists[L_SAM].n && !band6k && !band2g && bnfft == kNfft && k.P_am < bnfft;
     // ... or, when the tiles are 2048 outputs behind 2048 samples of pre-roll and bp1 takes its channels two a tile, no pass at all: the
     // leveller's local share in nbp0's store (DET 3), the carried share in bp1's load
-    k.am_lv_fused = k.am_fused && k.P_am == 2048 && bnfft - k.P_am == 2048 && np_am > 0 && n_bp1p[0] && long_parts[1] <= 1 && !(dbg_forms & (16 | 512));
+    k.am_lv_fused = k.am_fused && k.P_am == 2048 && bnfft - k.P_am == 2048 && np_am > 0 && lists[L_BP1P].n && long_parts[1] <= 1 && !(dbg_forms & (16 | 512));
     // The AM / SAM detectors and the FM detector chain touch disjoint channel rows and disjoint state, and neither fills the
     // chip (one workgroup or wavefront per channel): with both kinds of channel in the call the AM side runs on a second
     // stream, forked and joined by events (which a launch-sequence capture records as graph edges).
-    k.side = k.split || ((n_am || n_sam) && n_fm && !(dbg_forms & 32));
+    k.side = k.split || ((lists[L_AM].n || lists[L_SAM].n) && lists[L_FM].n && !(dbg_forms & 32));
     if (k.am_fused) {
         if (int rc = grow(am_tsum, am_tsum_cap, (k.n_mid + (bnfft - k.P_am) - 1) / (bnfft - k.P_am), 2LL * nch)) return rc;
         if (k.am_lv_fused) if (int rc = grow(am_cin, am_cin_cap, am_tsum_cap + 1, 2LL * nch)) return rc;
     }
     if (k.side) if (int rc = ensure_side_stream()) return rc;
     for (double *&q : seg_sum)
-        if (!q) QH_HIP(dev_alloc(&q, (size_t)nch * kSegWaves * kSegMaxGroups * kSegSumW));
+        if (!q) if (int rc = alloc(q, (long long)nch * kSegWaves * kSegMaxGroups * kSegSumW)) return rc;
     k.cur = buf[0]; k.other = buf[1];
     return QH_OK;
 }
@@ -2263,27 +2203,27 @@ int Engine::run_mixed_front(ChainCall &k)
         // channels' dense filters (config 4, one box: 10.45 ms forked at once, 10.31 forked here).
         const int fork_at = 2 - (((dbg_forms >> 6) & 3) > 2 ? 2 : ((dbg_forms >> 6) & 3));
         if (fork_at == 0) if (int rc = fork_side()) return rc;
-        if (int rc = run_front(k.in, k.in_stride, cur, buf_cap, nullptr, n_in, n_mid, list_fm, n_fm, 2)) return rc;
+        if (int rc = run_front(k.in, k.in_stride, cur, buf_cap, nullptr, n_in, n_mid, lists[L_FM].dev, lists[L_FM].n, 2)) return rc;
         if (fork_at == 1) if (int rc = fork_side()) return rc;
         int hc = cur_nbp;
         // the FM channels' nbp0 feeds the loop's phase detector and nothing else: its store takes the angles (first half of the rows)
-        if (k.any_nbp) run_band(cur, buf_cap, other, buf_cap, nullptr, n_mid, mask_nbp, kBandNfftMax, hist_nbp, hc, P, list_fm, n_fm, false, false,
+        if (k.any_nbp) run_band(cur, buf_cap, other, buf_cap, nullptr, n_mid, mask_nbp, kBandNfftMax, hist_nbp, hc, P, lists[L_FM].dev, lists[L_FM].n, false, false,
                                 k.fm_theta_fused ? 1 : 0, reinterpret_cast<double *>(other), 2 * buf_cap);
         if (fork_at >= 2) if (int rc = fork_side()) return rc;
         std::swap(stream, side_stream);
-        int rc2 = run_front(k.in, k.in_stride, cur, buf_cap, nullptr, n_in, n_mid, list_rest, n_rest, 2);
+        int rc2 = run_front(k.in, k.in_stride, cur, buf_cap, nullptr, n_in, n_mid, lists[L_REST].dev, lists[L_REST].n, 2);
         hc = cur_nbp;
         if (!rc2 && k.any_nbp) {
             if (k.direct) {     // the plain channels end here: output matrix in the store, straight to the caller's buffer
-                if (n_usb) run_band(cur, buf_cap, k.out, k.out_stride, epi, n_mid, mask_nbp, kBandNfftMax, hist_nbp, hc, P, list_usb, n_usb);
+                if (lists[L_USB].n) run_band(cur, buf_cap, k.out, k.out_stride, epi, n_mid, mask_nbp, kBandNfftMax, hist_nbp, hc, P, lists[L_USB].dev, lists[L_USB].n);
                 hc = cur_nbp;
                 if (k.am_fused) {
-                    if (n_sam) run_band(cur, buf_cap, other, buf_cap, nullptr, n_mid, mask_nbp, kBandNfftMax, hist_nbp, hc, P, list_sam, n_sam);
+                    if (lists[L_SAM].n) run_band(cur, buf_cap, other, buf_cap, nullptr, n_mid, mask_nbp, kBandNfftMax, hist_nbp, hc, P, lists[L_SAM].dev, lists[L_SAM].n);
                     hc = cur_nbp;
-                    run_band(cur, buf_cap, other, buf_cap, nullptr, n_mid, mask_nbp, kBandNfftMax, hist_nbp, hc, k.P_am, list_am, n_am, false, false,
+                    run_band(cur, buf_cap, other, buf_cap, nullptr, n_mid, mask_nbp, kBandNfftMax, hist_nbp, hc, k.P_am, lists[L_AM].dev, lists[L_AM].n, false, false,
                              k.am_lv_fused ? 3 : 2, reinterpret_cast<double *>(other), 2 * buf_cap);
-                } else if (n_rb) run_band(cur, buf_cap, other, buf_cap, nullptr, n_mid, mask_nbp, kBandNfftMax, hist_nbp, hc, P, list_rb, n_rb);
-            } else run_band(cur, buf_cap, other, buf_cap, nullptr, n_mid, mask_nbp, kBandNfftMax, hist_nbp, hc, P, list_rest, n_rest);
+                } else if (lists[L_RB].n) run_band(cur, buf_cap, other, buf_cap, nullptr, n_mid, mask_nbp, kBandNfftMax, hist_nbp, hc, P, lists[L_RB].dev, lists[L_RB].n);
+            } else run_band(cur, buf_cap, other, buf_cap, nullptr, n_mid, mask_nbp, kBandNfftMax, hist_nbp, hc, P, lists[L_REST].dev, lists[L_REST].n);
         }
         std::swap(stream, side_stream);
         if (rc2) return rc2;
@@ -2300,16 +2240,16 @@ int Engine::run_mixed_front(ChainCall &k)
     }
     if (meters_on) hipLaunchKernelGGL(meter_kernel, dim3((unsigned)nch), dim3(64), 0, stream, cur, buf_cap, k.nblk, dsp_size, m_s,
                                       m_prm, (const int *)nullptr);
-    if (n_amsq) {           // xamsqcap (RXA.c:571): the magnitudes of the signal behind nbp0, for xamsq at the end of the chain
+    if (lists[L_AMSQ].n) {           // xamsqcap (RXA.c:571): the magnitudes of the signal behind nbp0, for xamsq at the end of the chain
         if (int rc = grow(amsq_mag, amsq_mag_cap, buf_cap, nch)) return rc;
         long long per = (n_mid + NT - 1) / NT;
-        hipLaunchKernelGGL(amsq_cap_kernel, dim3((unsigned)(per < 1024 ? per : 1024), (unsigned)n_amsq), dim3(NT), 0, stream, cur, buf_cap,
-                           (int)n_mid, list_amsq, amsq_mag, amsq_mag_cap);
+        hipLaunchKernelGGL(amsq_cap_kernel, dim3((unsigned)(per < 1024 ? per : 1024), (unsigned)lists[L_AMSQ].n), dim3(NT), 0, stream, cur, buf_cap,
+                           (int)n_mid, lists[L_AMSQ].dev, amsq_mag, amsq_mag_cap);
     }
     // xbpsnbaout at position 0 (RXA.c:572): the 250..5700 Hz filter of the signal ahead of nbp0 replaces nbp0's output
-    if (n_snb[0]) {
-        if (k.any_nbp) { int hc = cur_snb; run_band(other, buf_cap, cur, buf_cap, nullptr, n_mid, mask_snb, kBandNfftMax, hist_snb, hc, P, list_snb[0], n_snb[0]); }
-        else snb_inplace(k, list_snb[0], n_snb[0]);
+    if (lists[L_SNB].n) {
+        if (k.any_nbp) { int hc = cur_snb; run_band(other, buf_cap, cur, buf_cap, nullptr, n_mid, mask_snb, kBandNfftMax, hist_snb, hc, P, lists[L_SNB].dev, lists[L_SNB].n); }
+        else snb_inplace(k, lists[L_SNB].dev, lists[L_SNB].n);
     }
     tick(1);
     return QH_OK;
@@ -2363,47 +2303,47 @@ int Engine::run_am(ChainCall &k)
         am_stream = side_stream;
     }
     FmDcSrc amlv_src{ nullptr, 0, 0 };
-    if (n_am && k.am_lv_fused) {    // the envelope + the leveller's local share lie in the channels' own rows (first half); bp1 loads them from there
-        hipLaunchKernelGGL(am_lv_chain_kernel, dim3((unsigned)n_am), dim3(64), 0, am_stream, (int)n_mid, bnfft - k.P_am, list_am, (const int *)levelfade, am_state,
+    if (lists[L_AM].n && k.am_lv_fused) {    // the envelope + the leveller's local share lie in the channels' own rows (first half); bp1 loads them from there
+        hipLaunchKernelGGL(am_lv_chain_kernel, dim3((unsigned)lists[L_AM].n), dim3(64), 0, am_stream, (int)n_mid, bnfft - k.P_am, lists[L_AM].dev, (const int *)levelfade, am_state,
                            am_prm, (const double *)am_tsum, am_tsum_cap, (const double *)am_last, am_cin, am_cin_cap);
         amlv_src = FmDcSrc{ reinterpret_cast<double *>(cur), 2 * buf_cap, 11 };
-    } else if (n_am && k.am_fused) {  // envelopes in the channels' own rows (first half), audio to the rows of `other`
-        const int G = seg_groups(n_am + (n_mid >= kSamTiledMin ? n_sam0 : 0), n_mid);
-        hipLaunchKernelGGL(am_level_tiled_kernel, dim3((unsigned)n_am, (unsigned)G), dim3(kSegThreads), 0, am_stream,
-                           (const double *)reinterpret_cast<double *>(cur), 2 * buf_cap, other, buf_cap, (int)n_mid, list_am, levelfade, (const AmState *)am_state,
+    } else if (lists[L_AM].n && k.am_fused) {  // envelopes in the channels' own rows (first half), audio to the rows of `other`
+        const int G = seg_groups(lists[L_AM].n + (n_mid >= kSamTiledMin ? n_sam0 : 0), n_mid);
+        hipLaunchKernelGGL(am_level_tiled_kernel, dim3((unsigned)lists[L_AM].n, (unsigned)G), dim3(kSegThreads), 0, am_stream,
+                           (const double *)reinterpret_cast<double *>(cur), 2 * buf_cap, other, buf_cap, (int)n_mid, lists[L_AM].dev, levelfade, (const AmState *)am_state,
                            am_prm, (const double *)am_tsum, am_tsum_cap, bnfft - k.P_am, am_next);
-        hipLaunchKernelGGL(commit_am_kernel, dim3((unsigned)((n_am + 255) / 256)), dim3(256), 0, am_stream, am_state, (const AmState *)am_next, list_am, n_am, levelfade);
-    } else if (n_am)
-        am_detect<false>(k, am_stream, list_am, n_am, seg_groups(n_am + (n_mid >= kSamTiledMin ? n_sam0 : 0), n_mid), nullptr, 0, seg_sum[0]);
+        hipLaunchKernelGGL(commit_am_kernel, dim3((unsigned)((lists[L_AM].n + 255) / 256)), dim3(256), 0, am_stream, am_state, (const AmState *)am_next, lists[L_AM].dev, lists[L_AM].n, levelfade);
+    } else if (lists[L_AM].n)
+        am_detect<false>(k, am_stream, lists[L_AM].dev, lists[L_AM].n, seg_groups(lists[L_AM].n + (n_mid >= kSamTiledMin ? n_sam0 : 0), n_mid), nullptr, 0, seg_sum[0]);
     {
         // SAM without sideband separation in a long call: angles, the loop one tile per lane with a warm-up, verify / repair,
         // then the mix with the phase each sample saw and the fade leveller over time segments (qh_tiled.hpp).  The channels'
         // rows of `other` are free here: first half = angles, second half = phases.  Short calls and the all-pass modes
         // (SAM-L / SAM-U) take the sequential kernel.
-        // (the channels with a sideband selected follow the others in list_sam: the loop is the same, the chains come behind it)
-        const int nt = n_mid >= kSamTiledMin ? n_sam : 0, nt0 = nt ? n_sam0 : 0, ntsb = nt - nt0;
+        // (the channels with a sideband selected follow the others in lists[L_SAM].dev: the loop is the same, the chains come behind it)
+        const int nt = n_mid >= kSamTiledMin ? lists[L_SAM].n : 0, nt0 = nt ? n_sam0 : 0, ntsb = nt - nt0;
         if (nt) {
             double *theta = reinterpret_cast<double *>(other), *pts = theta + buf_cap;
             const long long per = (n_mid + NT - 1) / NT;
             hipLaunchKernelGGL(pll_theta_kernel, dim3((unsigned)(per < 1024 ? per : 1024), (unsigned)nt), dim3(NT), 0, am_stream, cur, buf_cap,
-                               (int)n_mid, list_sam, theta, 2 * buf_cap);
+                               (int)n_mid, lists[L_SAM].dev, theta, 2 * buf_cap);
             const long long ntl = (n_mid + kSamTile - 1) / kSamTile;
             const int ngroups = (int)((ntl + 63) / 64);
             if (int rc = grow(pll_ends, pll_ends_cap, (long long)ngroups * 64, (long long)nch * kPllEndsW)) return rc;
             hipLaunchKernelGGL((pll_lanes_kernel<true>), dim3((unsigned)ngroups, (unsigned)nt), dim3(64), 0, am_stream, (const double *)theta,
-                               2 * buf_cap, pts, 2 * buf_cap, (int)n_mid, list_sam, (const PllState *)pll_state, pll_ends, pll_ends_cap * kPllEndsW,
+                               2 * buf_cap, pts, 2 * buf_cap, (int)n_mid, lists[L_SAM].dev, (const PllState *)pll_state, pll_ends, pll_ends_cap * kPllEndsW,
                                sam_pll_prm, kSamTile, kSamWarm);
             hipLaunchKernelGGL((pll_verify_kernel<true>), dim3((unsigned)nt), dim3(64), 0, am_stream, (const double *)theta, 2 * buf_cap, pts,
-                               2 * buf_cap, (int)n_mid, list_sam, pll_state, pll_ends, pll_ends_cap * kPllEndsW, sam_pll_prm, kSamTile, kSamWarm,
+                               2 * buf_cap, (int)n_mid, lists[L_SAM].dev, pll_state, pll_ends, pll_ends_cap * kPllEndsW, sam_pll_prm, kSamTile, kSamWarm,
                                pll_nfixed, pll_check_only);
             if (nt0)        // (the segment summaries behind the AM channels' rows)
-                am_detect<true>(k, am_stream, list_sam, nt0, seg_groups(n_am + nt, n_mid), pts, 2 * buf_cap,
-                                seg_sum[0] + (size_t)n_am * kSegWaves * kSegMaxGroups * kSegSumW);
+                am_detect<true>(k, am_stream, lists[L_SAM].dev, nt0, seg_groups(lists[L_AM].n + nt, n_mid), pts, 2 * buf_cap,
+                                seg_sum[0] + (size_t)lists[L_AM].n * kSegWaves * kSegMaxGroups * kSegSumW);
             if (ntsb) {
-                const int G = seg_groups(n_am + nt, n_mid), S = kSegWaves * G;
+                const int G = seg_groups(lists[L_AM].n + nt, n_mid), S = kSegWaves * G;
                 if (int rc = set_sb_phi(n_mid, S)) return rc;
-                const int *lst = list_sam + nt0;
-                double *gs = seg_sum[0] + (size_t)(n_am + nt0) * kSegWaves * kSegMaxGroups * kSegSumW;
+                const int *lst = lists[L_SAM].dev + nt0;
+                double *gs = seg_sum[0] + (size_t)(lists[L_AM].n + nt0) * kSegWaves * kSegMaxGroups * kSegSumW;
                 hipLaunchKernelGGL((sam_sb_tiled_kernel<1>), dim3((unsigned)ntsb, (unsigned)(S / kSbWaves)), dim3(64 * kSbWaves), 0, am_stream, cur, buf_cap, (int)n_mid,
                                    lst, (const SamChanParam *)sam_prm, (const double *)pts, 2 * buf_cap, pll_state, sb_sum, (const double *)sb_start);
                 hipLaunchKernelGGL(sam_sb_chain_kernel, dim3((unsigned)ntsb), dim3(64), 0, am_stream, (int)n_mid, S, lst, (const PllState *)pll_state,
@@ -2417,21 +2357,21 @@ int Engine::run_am(ChainCall &k)
                 hipLaunchKernelGGL(commit_am_kernel, dim3((unsigned)((ntsb + 255) / 256)), dim3(256), 0, am_stream, am_state, (const AmState *)am_next, lst, ntsb, levelfade);
             }
         }
-        if (n_sam - nt) hipLaunchKernelGGL(sam_pll_kernel, dim3((unsigned)(n_sam - nt)), dim3(64), 0, am_stream, cur, buf_cap, (int)n_mid,
-                                           list_sam + nt, pll_state, sam_prm, sam_pll_prm, am_state);
+        if (lists[L_SAM].n - nt) hipLaunchKernelGGL(sam_pll_kernel, dim3((unsigned)(lists[L_SAM].n - nt)), dim3(64), 0, am_stream, cur, buf_cap, (int)n_mid,
+                                           lists[L_SAM].dev + nt, pll_state, sam_prm, sam_pll_prm, am_state);
     }
-    if (k.direct && n_bp1p[0]) {      // bp1 is the AM / SAM channels' last stage: it follows their detectors on the second stream
+    if (k.direct && lists[L_BP1P].n) {      // bp1 is the AM / SAM channels' last stage: it follows their detectors on the second stream
         std::swap(stream, side_stream);
         int hc = cur_bp1;
         if (k.am_fused) {
             if (amlv_src.a) band_amlv = &amlv_src;
-            run_band(other, buf_cap, k.out, k.out_stride, epi, n_mid, mask_bp1, kBandNfftMax, hist_bp1, hc, k.P, list_am, n_am, false, false, 0, nullptr, 0,
-                     np_am && !(dbg_forms & 16) ? pairs_am : nullptr, np_am);
+            run_band(other, buf_cap, k.out, k.out_stride, epi, n_mid, mask_bp1, kBandNfftMax, hist_bp1, hc, k.P, lists[L_AM].dev, lists[L_AM].n, false, false, 0, nullptr, 0,
+                     np_am && !(dbg_forms & 16) ? lists[L_PAIRS_AM].dev : nullptr, np_am);
             band_amlv = nullptr;
             hc = cur_bp1;
-            if (n_sam) run_band(cur, buf_cap, k.out, k.out_stride, epi, n_mid, mask_bp1, kBandNfftMax, hist_bp1, hc, k.P, list_sam, n_sam, false, false, 0,
-                                nullptr, 0, np_sam && !(dbg_forms & 16) ? pairs_sam : nullptr, np_sam);
-        } else run_band(cur, buf_cap, k.out, k.out_stride, epi, n_mid, mask_bp1, kBandNfftMax, hist_bp1, hc, k.P, list_bp1p[0], n_bp1p[0]);
+            if (lists[L_SAM].n) run_band(cur, buf_cap, k.out, k.out_stride, epi, n_mid, mask_bp1, kBandNfftMax, hist_bp1, hc, k.P, lists[L_SAM].dev, lists[L_SAM].n, false, false, 0,
+                                nullptr, 0, np_sam && !(dbg_forms & 16) ? lists[L_PAIRS_SAM].dev : nullptr, np_sam);
+        } else run_band(cur, buf_cap, k.out, k.out_stride, epi, n_mid, mask_bp1, kBandNfftMax, hist_bp1, hc, k.P, lists[L_BP1P].dev, lists[L_BP1P].n);
         std::swap(stream, side_stream);
     }
     return QH_OK;
@@ -2457,74 +2397,74 @@ int Engine::run_fm(ChainCall &k)
         if (fmdc_fused) fil = reinterpret_cast<double *>(cur) + buf_cap;     // (the de-emphasis stage reads it while it writes the rows of `other`)
         const long long per = (n_mid + NT - 1) / NT;
         if (!k.fm_theta_fused)
-            hipLaunchKernelGGL(pll_theta_kernel, dim3((unsigned)(per < 1024 ? per : 1024), (unsigned)n_fm), dim3(NT), 0, stream, cur, buf_cap,
-                               (int)n_mid, list_fm, theta, 2 * buf_cap);
+            hipLaunchKernelGGL(pll_theta_kernel, dim3((unsigned)(per < 1024 ? per : 1024), (unsigned)lists[L_FM].n), dim3(NT), 0, stream, cur, buf_cap,
+                               (int)n_mid, lists[L_FM].dev, theta, 2 * buf_cap);
         // the longest tile that still gives the chip 512 wavefronts of 64 tiles: the 768-sample warm-up is 3/4 of a 256-sample
         // tile's steps and 3/11 of a 2048-sample tile's
         int fm_tile = kFmTile;
-        while (fm_tile < 2048 && (long long)n_fm * n_mid / (64LL * 2 * fm_tile) >= 512) fm_tile *= 2;
+        while (fm_tile < 2048 && (long long)lists[L_FM].n * n_mid / (64LL * 2 * fm_tile) >= 512) fm_tile *= 2;
         const long long ntl = (n_mid + fm_tile - 1) / fm_tile;
         const int ngroups = (int)((ntl + 63) / 64);
         if (int rc = grow(pll_ends, pll_ends_cap, (long long)ngroups * 64, (long long)nch * kPllEndsW)) return rc;
         if (fmdc_fused) if (int rc = grow(fm_cin, fm_cin_cap, pll_ends_cap + 1, nch)) return rc;
-        hipLaunchKernelGGL((pll_lanes_kernel<false>), dim3((unsigned)ngroups, (unsigned)n_fm), dim3(64), 0, stream, (const double *)theta,
-                           2 * buf_cap, fil, 2 * buf_cap, (int)n_mid, list_fm, (const PllState *)fm_pll_state, pll_ends, pll_ends_cap * kPllEndsW,
+        hipLaunchKernelGGL((pll_lanes_kernel<false>), dim3((unsigned)ngroups, (unsigned)lists[L_FM].n), dim3(64), 0, stream, (const double *)theta,
+                           2 * buf_cap, fil, 2 * buf_cap, (int)n_mid, lists[L_FM].dev, (const PllState *)fm_pll_state, pll_ends, pll_ends_cap * kPllEndsW,
                            fm_pll_prm, fm_tile, kFmWarm, fmdc_fused ? 1 : 0);
-        hipLaunchKernelGGL((pll_verify_kernel<false>), dim3((unsigned)n_fm), dim3(64), 0, stream, (const double *)theta, 2 * buf_cap, fil,
-                           2 * buf_cap, (int)n_mid, list_fm, fm_pll_state, pll_ends, pll_ends_cap * kPllEndsW, fm_pll_prm, fm_tile, kFmWarm,
+        hipLaunchKernelGGL((pll_verify_kernel<false>), dim3((unsigned)lists[L_FM].n), dim3(64), 0, stream, (const double *)theta, 2 * buf_cap, fil,
+                           2 * buf_cap, (int)n_mid, lists[L_FM].dev, fm_pll_state, pll_ends, pll_ends_cap * kPllEndsW, fm_pll_prm, fm_tile, kFmWarm,
                            pll_nfixed, pll_check_only, fmdc_fused ? 1 : 0);
         if (fmdc_fused) {
-            hipLaunchKernelGGL(fm_dc_chain_kernel, dim3((unsigned)n_fm), dim3(64), 0, stream, (int)n_mid, fm_tile, list_fm, fm_pll_state, fm_pll_prm,
+            hipLaunchKernelGGL(fm_dc_chain_kernel, dim3((unsigned)lists[L_FM].n), dim3(64), 0, stream, (int)n_mid, fm_tile, lists[L_FM].dev, fm_pll_state, fm_pll_prm,
                                (const double *)pll_ends, pll_ends_cap * kPllEndsW, fm_cin, fm_cin_cap);
             int sh = 0;
             while ((1 << sh) < fm_tile) sh++;
             fmdc_src = FmDcSrc{ fil, 2 * buf_cap, sh };
         } else {
             // dc removal + gain: the tiles' contributions are in `ends` already, one pass over `fil`
-            const int G = seg_groups(n_fm, n_mid);
-            hipLaunchKernelGGL(fm_dc_tiled_kernel, dim3((unsigned)n_fm, (unsigned)G), dim3(kSegThreads), 0, stream, (const double *)fil,
-                               2 * buf_cap, cur, buf_cap, (int)n_mid, list_fm, (const PllState *)fm_pll_state, (const double *)fm_again, fm_pll_prm,
+            const int G = seg_groups(lists[L_FM].n, n_mid);
+            hipLaunchKernelGGL(fm_dc_tiled_kernel, dim3((unsigned)lists[L_FM].n, (unsigned)G), dim3(kSegThreads), 0, stream, (const double *)fil,
+                               2 * buf_cap, cur, buf_cap, (int)n_mid, lists[L_FM].dev, (const PllState *)fm_pll_state, (const double *)fm_again, fm_pll_prm,
                                (const double *)pll_ends, pll_ends_cap * kPllEndsW, fm_tile, fmdc_next);
-            hipLaunchKernelGGL(commit_fmdc_kernel, dim3((unsigned)((n_fm + 255) / 256)), dim3(256), 0, stream, fm_pll_state, (const double *)fmdc_next, list_fm, n_fm);
+            hipLaunchKernelGGL(commit_fmdc_kernel, dim3((unsigned)((lists[L_FM].n + 255) / 256)), dim3(256), 0, stream, fm_pll_state, (const double *)fmdc_next, lists[L_FM].dev, lists[L_FM].n);
         }
     }
     {   // de-emphasis: real taps on a real signal, two channels per tile
         if (fmdc_src.a) band_fmdc = &fmdc_src;
-        run_band(cur, buf_cap, other, buf_cap, nullptr, n_mid, mask_de, 0, hist_de, cur_de, k.P, list_fm, n_fm, false, false, 0, nullptr, 0,
-                 pair ? pairs_fm : nullptr, np_fm);
+        run_band(cur, buf_cap, other, buf_cap, nullptr, n_mid, mask_de, 0, hist_de, cur_de, k.P, lists[L_FM].dev, lists[L_FM].n, false, false, 0, nullptr, 0,
+                 pair ? lists[L_PAIRS_FM].dev : nullptr, np_fm);
         band_fmdc = nullptr;
     }
-    run_band(other, buf_cap, cur, buf_cap, nullptr, n_mid, mask_aud, 0, hist_aud, cur_aud, k.P, list_fm, n_fm);   // audio filter
+    run_band(other, buf_cap, cur, buf_cap, nullptr, n_mid, mask_aud, 0, hist_aud, cur_aud, k.P, lists[L_FM].dev, lists[L_FM].n);   // audio filter
     tick(1);
     {
-        const int G = seg_groups(n_fm, n_mid);
+        const int G = seg_groups(lists[L_FM].n, n_mid);
         if (G > 1) {
-            hipLaunchKernelGGL((snotch_tiled_kernel<1>), dim3((unsigned)n_fm, (unsigned)G), dim3(kSegThreads), 0, stream, cur, buf_cap, (int)n_mid,
-                               list_fm, sn_prm, sn_state, seg_sum[2]);
-            hipLaunchKernelGGL((snotch_tiled_kernel<2>), dim3((unsigned)n_fm, (unsigned)G), dim3(kSegThreads), 0, stream, cur, buf_cap, (int)n_mid,
-                               list_fm, sn_prm, sn_state, seg_sum[2], k.direct ? k.out : (double2 *)nullptr, k.out_stride, (const EpiParam *)epi, sn_next);
-            hipLaunchKernelGGL(commit_snotch_kernel, dim3((unsigned)((n_fm + 255) / 256)), dim3(256), 0, stream, sn_state, (const SnotchState *)sn_next, list_fm, n_fm,
+            hipLaunchKernelGGL((snotch_tiled_kernel<1>), dim3((unsigned)lists[L_FM].n, (unsigned)G), dim3(kSegThreads), 0, stream, cur, buf_cap, (int)n_mid,
+                               lists[L_FM].dev, sn_prm, sn_state, seg_sum[2]);
+            hipLaunchKernelGGL((snotch_tiled_kernel<2>), dim3((unsigned)lists[L_FM].n, (unsigned)G), dim3(kSegThreads), 0, stream, cur, buf_cap, (int)n_mid,
+                               lists[L_FM].dev, sn_prm, sn_state, seg_sum[2], k.direct ? k.out : (double2 *)nullptr, k.out_stride, (const EpiParam *)epi, sn_next);
+            hipLaunchKernelGGL(commit_snotch_kernel, dim3((unsigned)((lists[L_FM].n + 255) / 256)), dim3(256), 0, stream, sn_state, (const SnotchState *)sn_next, lists[L_FM].dev, lists[L_FM].n,
                                (const SnotchParam *)sn_prm);
         } else
-            hipLaunchKernelGGL((snotch_tiled_kernel<0>), dim3((unsigned)n_fm), dim3(kSegThreads), 0, stream, cur, buf_cap, (int)n_mid, list_fm,
+            hipLaunchKernelGGL((snotch_tiled_kernel<0>), dim3((unsigned)lists[L_FM].n), dim3(kSegThreads), 0, stream, cur, buf_cap, (int)n_mid, lists[L_FM].dev,
                                sn_prm, sn_state, (double *)nullptr, k.direct ? k.out : (double2 *)nullptr, k.out_stride, (const EpiParam *)epi);
     }
-    if (n_lim)      // detector limiter: lim_pre_gain 0.4, then its own wcpAGC (fmd.c:179-184)
-        hipLaunchKernelGGL(agc_form == 1 ? wcpagc_seq_kernel : wcpagc_kernel, dim3((unsigned)n_lim), dim3(64), 0, stream, cur, buf_cap,
-                           (int)n_mid, list_lim, lim_prm, lim_state, 0.4);
+    if (lists[L_LIM].n)      // detector limiter: lim_pre_gain 0.4, then its own wcpAGC (fmd.c:179-184)
+        hipLaunchKernelGGL(agc_form == 1 ? wcpagc_seq_kernel : wcpagc_kernel, dim3((unsigned)lists[L_LIM].n), dim3(64), 0, stream, cur, buf_cap,
+                           (int)n_mid, lists[L_LIM].dev, lim_prm, lim_state, 0.4);
     return QH_OK;
 }
 
 // xsnba, with the tuning the setters left uploaded first
 int Engine::run_snba(const ChainCall &k)
 {
-    if (!n_snba) return QH_OK;
+    if (!lists[L_SNBA].n) return QH_OK;
     if (snba_tune_dirty) {
         QH_HIP(hipMemcpyAsync(snba_tune, snba_tune_h.data(), snba_tune_h.size() * sizeof(SnbaTune), hipMemcpyHostToDevice, stream));
         QH_HIP(hipStreamSynchronize(stream));
         snba_tune_dirty = false;
     }
-    hipLaunchKernelGGL(snba_kernel, dim3((unsigned)n_snba), dim3(64), 0, stream, k.cur, buf_cap, k.nblk, dsp_size, list_snba, snba_prm,
+    hipLaunchKernelGGL(snba_kernel, dim3((unsigned)lists[L_SNBA].n), dim3(64), 0, stream, k.cur, buf_cap, k.nblk, dsp_size, lists[L_SNBA].dev, snba_prm,
                        snba_hin, snba_hout, snba_state, snba_idx, snba_scratch, (const SnbaTune *)snba_tune);
     return QH_OK;
 }
@@ -2534,10 +2474,10 @@ int Engine::run_snba(const ChainCall &k)
 void Engine::lms_at(const ChainCall &k, int pos, double2 *b)
 {
     for (int f = 0; f < 2; f++)
-        if (n_lms[f][pos]) hipLaunchKernelGGL(lms_kernel, dim3((unsigned)n_lms[f][pos]), dim3(64), 0, stream, b, buf_cap, (int)k.n_mid,
-                                              list_lms[f][pos], lms_prm[f], lms_state[f]);
-    if (n_emnr[pos])
-        hipLaunchKernelGGL(emnr_kernel, dim3((unsigned)n_emnr[pos]), dim3(NT), (size_t)emnr_lds_bytes(), stream, b, buf_cap, k.nblk, list_emnr[pos],
+        if (lists[L_LMS + 3 * f + pos].n) hipLaunchKernelGGL(lms_kernel, dim3((unsigned)lists[L_LMS + 3 * f + pos].n), dim3(64), 0, stream, b, buf_cap, (int)k.n_mid,
+                                              lists[L_LMS + 3 * f + pos].dev, lms_prm[f], lms_state[f]);
+    if (lists[L_EMNR + pos].n)
+        hipLaunchKernelGGL(emnr_kernel, dim3((unsigned)lists[L_EMNR + pos].n), dim3(NT), (size_t)emnr_lds_bytes(), stream, b, buf_cap, k.nblk, lists[L_EMNR + pos].dev,
                            emnr_prm, emnr_chan, emnr_scal, emnr_state, emnr_window, tw4096, emnr_GG, emnr_GGS, emnr_zeta, emnr_zeta_true);
 }
 
@@ -2545,8 +2485,8 @@ void Engine::lms_at(const ChainCall &k, int pos, double2 *b)
 void Engine::bp1_at(const ChainCall &k, int pos)
 {
     int hc = cur_bp1;
-    if (n_bp1p[pos] && !k.direct)
-        run_band(k.cur, buf_cap, k.other, buf_cap, nullptr, k.n_mid, mask_bp1, kBandNfftMax, hist_bp1, hc, k.P, list_bp1p[pos], n_bp1p[pos]);
+    if (lists[L_BP1P + pos].n && !k.direct)
+        run_band(k.cur, buf_cap, k.other, buf_cap, nullptr, k.n_mid, mask_bp1, kBandNfftMax, hist_bp1, hc, k.P, lists[L_BP1P + pos].dev, lists[L_BP1P + pos].n);
 }
 
 // xwcpagc modes 1-4.  Long calls: the level detector in time tiles, everything around it lane-parallel (qh_agc_tiled.hpp).  Short
@@ -2563,7 +2503,7 @@ int Engine::run_agc(ChainCall &k)
         a_max = c.agc_abuf > a_max ? c.agc_abuf : a_max;
     }
     // the tiles take the channels at the head of each list, the stepping kernel the ones behind them (all of them in a short call)
-    const int nt_cur = tiled ? n_agc_cur - n_agc_cur_stale : 0, nt_other = tiled ? n_agc_other - n_agc_other_stale : 0;
+    const int nt_cur = tiled ? lists[L_AGC_CUR].n - n_agc_cur_stale : 0, nt_other = tiled ? lists[L_AGC_OTHER].n - n_agc_other_stale : 0;
     if (nt_cur + nt_other == 0) tiled = false;
     agc_last_tiled = nt_cur + nt_other;
     for (ChanCfg &c : cfg) if (c.agc_on()) c.agc_ran = true;
@@ -2571,12 +2511,10 @@ int Engine::run_agc(ChainCall &k)
     // window moved since its last call first takes its 2048-entry ring again from it (the entries the longer window jumped over)
     if (!agc_lring) {
         if (int rc = quiesce()) return rc;
-        if (int rc = realloc_dev(agc_lring, 0, (long long)nch * kAgcLongRing)) return rc;
-        if (int rc = realloc_dev(agc_labs, 0, (long long)nch * kAgcLongRing)) return rc;
-        if (int rc = realloc_dev(agc_lout, 0, nch)) return rc;
-        if (int rc = realloc_dev(agc_rewin_list, 0, nch)) return rc;
-        QH_HIP(hipMemsetAsync(agc_lring, 0, (size_t)nch * kAgcLongRing * sizeof(double2), stream));
-        QH_HIP(hipMemsetAsync(agc_labs, 0, (size_t)nch * kAgcLongRing * sizeof(double), stream));
+        if (int rc = alloc(agc_lring, (long long)nch * kAgcLongRing, true)) return rc;
+        if (int rc = alloc(agc_labs, (long long)nch * kAgcLongRing, true)) return rc;
+        if (int rc = alloc(agc_lout, nch)) return rc;
+        if (int rc = alloc(agc_rewin_list, nch)) return rc;
         QH_HIP(hipMemsetAsync(agc_lout, 0xff, (size_t)nch * sizeof(int), stream));          // out_index = -1 (calc_wcpagc, wcpAGC.c:34)
     }
     {
@@ -2602,14 +2540,14 @@ int Engine::run_agc(ChainCall &k)
                                agc_lring, agc_labs, (const int *)agc_lout);
             hipLaunchKernelGGL(agc_long_advance_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, stream, (int)n_mid, lst, cnt, agc_lout);
         };
-        mirror(cur, list_agc_cur, n_agc_cur);
-        mirror(other, list_agc_other, n_agc_other);
+        mirror(cur, lists[L_AGC_CUR].dev, lists[L_AGC_CUR].n);
+        mirror(other, lists[L_AGC_OTHER].dev, lists[L_AGC_OTHER].n);
     }
     // ... and when every channel has the AGC as its last stage (nothing at position 1, no meters, squelch or audio frames), the gain
     // multiply applies the output matrix and writes the caller's rows: the output pass goes
-    bool no_p1 = !n_bp1p[1] && !n_fix[0] && !n_fix[1] && !n_emnr[1] && !n_emnr[2] && !n_amsq && !meters_on && !eg.kind && !n_ap[0] && !n_ap[1];
-    for (int f = 0; f < 2; f++) for (int p = 1; p < 3; p++) no_p1 = no_p1 && !n_lms[f][p];
-    k.agc_direct = tiled && no_p1 && nt_cur == n_plain && nt_other == n_bp1;
+    bool no_p1 = !lists[L_BP1P + 1].n && !lists[L_FIX].n && !lists[L_FIX + 1].n && !lists[L_EMNR + 1].n && !lists[L_EMNR + 2].n && !lists[L_AMSQ].n && !meters_on && !eg.kind && !lists[L_AP].n && !lists[L_AP + 1].n;
+    for (int f = 0; f < 2; f++) for (int p = 1; p < 3; p++) no_p1 = no_p1 && !lists[L_LMS + 3 * f + p].n;
+    k.agc_direct = tiled && no_p1 && nt_cur == lists[L_PLAIN].n && nt_other == lists[L_BP1].n;
     if (tiled) {
         const int nl = nt_cur > nt_other ? nt_cur : nt_other;
         const int ntile = (int)((n_mid + kAgcTile - 1) / kAgcTile), hp = (a_max + 15) & ~15;
@@ -2621,17 +2559,16 @@ int Engine::run_agc(ChainCall &k)
             if (int rc = quiesce()) return rc;
             const long long arr = std::max(n_mid, agc_arr), ends = std::max(ngroups * 64, agc_ends_cap), halo = std::max((long long)ntile * hp, agc_halo_cap);
             auto tiles = [](long long n) { return (n + kAgcTile - 1) / kAgcTile; };
-            if (int rc = realloc_dev(agc_scr, nch * 4 * agc_arr, nch * 4 * arr)) return rc;
-            if (int rc = realloc_dev(agc_ends, nch * agc_ends_cap * kAgcEndsW * 2, nch * ends * kAgcEndsW * 2)) return rc;    // boundary states, then end states
-            if (int rc = realloc_dev(agc_halo, nch * agc_halo_cap, nch * halo)) return rc;
-            if (int rc = realloc_dev(agc_tsum, nch * tiles(agc_arr) * 2, nch * tiles(arr) * 2)) return rc;
+            if (int rc = alloc(agc_scr, nch * 4 * arr)) return rc;
+            if (int rc = alloc(agc_ends, nch * ends * kAgcEndsW * 2)) return rc;    // boundary states, then end states
+            if (int rc = alloc(agc_halo, nch * halo)) return rc;
+            if (int rc = alloc(agc_tsum, nch * tiles(arr) * 2)) return rc;
             agc_arr = arr; agc_ends_cap = ends; agc_halo_cap = halo;
             if (!agc_fin) {
-                if (int rc = realloc_dev(agc_fin, 0, nch * 8)) return rc;
-                if (int rc = realloc_dev(agc_tail, 0, (long long)nch * kAgcRing)) return rc;
-                if (int rc = realloc_dev(agc_nfixed, 0, 2)) return rc;
-                QH_HIP(hipMemsetAsync(agc_nfixed, 0, 2 * sizeof(int), stream));
-                if (int rc = realloc_dev(agc_sege, 0, 2LL * nch * kAgcSegs * 8)) return rc;    // two copies: a repair round reads one and writes the other
+                if (int rc = alloc(agc_fin, nch * 8)) return rc;
+                if (int rc = alloc(agc_tail, (long long)nch * kAgcRing)) return rc;
+                if (int rc = alloc(agc_nfixed, 2, true)) return rc;
+                if (int rc = alloc(agc_sege, 2LL * nch * kAgcSegs * 8)) return rc;    // two copies: a repair round reads one and writes the other
             }
         }
         static bool agc_attr = false;
@@ -2691,27 +2628,24 @@ int Engine::run_agc(ChainCall &k)
             hipLaunchKernelGGL(agc_finish_kernel, dim3((unsigned)cnt), dim3(256), 0, stream, n, lst, (const AgcParam *)agc_prm, agc_state,
                                (const double *)agc_scr, agc_arr, (const double2 *)agc_tail, (const double *)agc_fin);
         };
-        run(cur, list_agc_cur, nt_cur);
-        run(other, list_agc_other, nt_other);
+        run(cur, lists[L_AGC_CUR].dev, nt_cur);
+        run(other, lists[L_AGC_OTHER].dev, nt_other);
     }
-    if (const int ns = n_agc_cur - nt_cur)
+    if (const int ns = lists[L_AGC_CUR].n - nt_cur)
         hipLaunchKernelGGL(agc_form == 1 ? wcpagc_seq_kernel : wcpagc_kernel, dim3((unsigned)ns), dim3(64), 0, stream, cur, buf_cap, (int)n_mid,
-                           (const int *)(list_agc_cur + nt_cur), agc_prm, agc_state, 1.0);
-    if (const int ns = n_agc_other - nt_other)
+                           (const int *)(lists[L_AGC_CUR].dev + nt_cur), agc_prm, agc_state, 1.0);
+    if (const int ns = lists[L_AGC_OTHER].n - nt_other)
         hipLaunchKernelGGL(agc_form == 1 ? wcpagc_seq_kernel : wcpagc_kernel, dim3((unsigned)ns), dim3(64), 0, stream, other, buf_cap, (int)n_mid,
-                           (const int *)(list_agc_other + nt_other), agc_prm, agc_state, 1.0);
+                           (const int *)(lists[L_AGC_OTHER].dev + nt_other), agc_prm, agc_state, 1.0);
     return QH_OK;
 }
 
 // ---- xcbl, xspeak, xmpeak (qh_audio_peak.hpp)
 int Engine::ap_alloc()
 {
-    if (int rc = realloc_dev(ap_lists, 0, 2LL * nch)) return rc;
-    if (int rc = realloc_dev(ap_prm, 0, nch)) return rc;
-    if (int rc = realloc_dev(ap_state, 0, (long long)nch * kApW)) return rc;
-    if (int rc = realloc_dev(ap_M, 0, (long long)nch * kApDim * kApDim)) return rc;
-    QH_HIP(hipMemsetAsync(ap_state, 0, (size_t)nch * kApW * sizeof(double), stream));
-    list_ap[0] = ap_lists; list_ap[1] = ap_lists + nch;
+    if (int rc = alloc(ap_prm, nch)) return rc;
+    if (int rc = alloc(ap_state, (long long)nch * kApW, true)) return rc;
+    if (int rc = alloc(ap_M, (long long)nch * kApDim * kApDim)) return rc;
     ap_M_h.assign((size_t)nch * kApDim * kApDim, 0.0);
     ap_prm_h.assign((size_t)nch, ApParam{});
     ap_L = 0;
@@ -2754,7 +2688,7 @@ int Engine::refresh_ap(const ChainCall &k)
         for (ChanCfg &c : cfg) { c.sp_flush = false; for (bool &f : c.mp_flush) f = false; }
         return QH_OK;
     }
-    const int nap = k.mixed ? n_ap[0] + n_ap[1] : 0;
+    const int nap = k.mixed ? lists[L_AP].n + lists[L_AP + 1].n : 0;
     int L = ap_L;
     if (nap) {
         // tiles short enough for about four wavefronts of 64 tiles per SIMD (1024 SIMDs), 256 .. 8192 samples
@@ -2811,20 +2745,20 @@ int Engine::refresh_ap(const ChainCall &k)
 // the three stages of the listed channels, in place on the rows that hold them behind bp1 (cur / other)
 void Engine::run_audio_peak(const ChainCall &k)
 {
-    if (!ap_prm || (!n_ap[0] && !n_ap[1])) return;
+    if (!ap_prm || (!lists[L_AP].n && !lists[L_AP + 1].n)) return;
     const int n = (int)k.n_mid, L = ap_L;
     const long long ntile = (k.n_mid + L - 1) / L, estride = ap_ends_cap * kApW;
     const unsigned ngroups = (unsigned)((ntile + 63) / 64);
     for (int b = 0; b < 2; b++) {
-        if (!n_ap[b]) continue;
+        if (!lists[L_AP + b].n) continue;
         double2 *rows = b ? k.other : k.cur;
         if (ntile > 1)
-            hipLaunchKernelGGL(audio_peak_pass_kernel<0>, dim3(ngroups, (unsigned)n_ap[b]), dim3(64), 0, stream, rows, buf_cap, n,
-                               (const int *)list_ap[b], (const ApParam *)ap_prm, ap_state, ap_ends, estride, L);
-        hipLaunchKernelGGL(audio_peak_carry_kernel, dim3((unsigned)n_ap[b]), dim3(64), 0, stream, n, L, (const int *)list_ap[b],
+            hipLaunchKernelGGL(audio_peak_pass_kernel<0>, dim3(ngroups, (unsigned)lists[L_AP + b].n), dim3(64), 0, stream, rows, buf_cap, n,
+                               (const int *)lists[L_AP + b].dev, (const ApParam *)ap_prm, ap_state, ap_ends, estride, L);
+        hipLaunchKernelGGL(audio_peak_carry_kernel, dim3((unsigned)lists[L_AP + b].n), dim3(64), 0, stream, n, L, (const int *)lists[L_AP + b].dev,
                            (const double *)ap_M, (const double *)ap_state, ap_ends, estride);
-        hipLaunchKernelGGL(audio_peak_pass_kernel<1>, dim3(ngroups, (unsigned)n_ap[b]), dim3(64), 0, stream, rows, buf_cap, n,
-                           (const int *)list_ap[b], (const ApParam *)ap_prm, ap_state, ap_ends, estride, L);
+        hipLaunchKernelGGL(audio_peak_pass_kernel<1>, dim3(ngroups, (unsigned)lists[L_AP + b].n), dim3(64), 0, stream, rows, buf_cap, n,
+                           (const int *)lists[L_AP + b].dev, (const ApParam *)ap_prm, ap_state, ap_ends, estride, L);
     }
 }
 
@@ -2835,18 +2769,18 @@ void Engine::run_output(const ChainCall &k)
     const long long n_mid = k.n_mid, per = (n_mid + NT - 1) / NT;
     const unsigned gx = (unsigned)(per < 1024 ? per : 1024);
     for (int b = 0; b < 2; b++)
-        if (n_fix[b]) hipLaunchKernelGGL(scale_kernel, dim3(gx, (unsigned)n_fix[b]), dim3(NT), 0, stream, b ? k.other : k.cur, buf_cap,
-                                         (int)n_mid, list_fix[b], fix_gain);
+        if (lists[L_FIX + b].n) hipLaunchKernelGGL(scale_kernel, dim3(gx, (unsigned)lists[L_FIX + b].n), dim3(NT), 0, stream, b ? k.other : k.cur, buf_cap,
+                                         (int)n_mid, lists[L_FIX + b].dev, fix_gain);
     lms_at(k, 1, k.cur);
     lms_at(k, 2, k.other);
     bp1_at(k, 1);
-    if (n_bp1) cur_bp1 ^= 1;
+    if (lists[L_BP1].n) cur_bp1 ^= 1;
     if (meters_on) {    // agcmeter sits after xwcpagc (RXA.c:589); mode 0's gain multiply is applied below, so its
                         // level reading is taken on the fixed-gain input times g^2 (m_g2)
-        if (n_plain) hipLaunchKernelGGL(meter_kernel, dim3((unsigned)n_plain), dim3(64), 0, stream, k.cur, buf_cap, k.nblk, dsp_size,
-                                        m_agc, m_prm, list_plain, (const double *)m_g2);
-        if (n_bp1) hipLaunchKernelGGL(meter_kernel, dim3((unsigned)n_bp1), dim3(64), 0, stream, k.other, buf_cap, k.nblk, dsp_size,
-                                      m_agc, m_prm, list_bp1, (const double *)m_g2);
+        if (lists[L_PLAIN].n) hipLaunchKernelGGL(meter_kernel, dim3((unsigned)lists[L_PLAIN].n), dim3(64), 0, stream, k.cur, buf_cap, k.nblk, dsp_size,
+                                        m_agc, m_prm, lists[L_PLAIN].dev, (const double *)m_g2);
+        if (lists[L_BP1].n) hipLaunchKernelGGL(meter_kernel, dim3((unsigned)lists[L_BP1].n), dim3(64), 0, stream, k.other, buf_cap, k.nblk, dsp_size,
+                                      m_agc, m_prm, lists[L_BP1].dev, (const double *)m_g2);
     }
     run_audio_peak(k);                  // xcbl, xspeak, xmpeak (RXA.c:591-593)
     tick(2);
@@ -2855,12 +2789,12 @@ void Engine::run_output(const ChainCall &k)
     if (!k.direct && !k.agc_direct) {
         auto *pass = k.eg_fused ? &pointwise_kernel<double, false, true> : &pointwise_kernel<double, false>;
         const EgressFmt pass_eg = k.eg_fused ? eg : EgressFmt{};
-        if (n_plain) hipLaunchKernelGGL(pass, dim3(gx, (unsigned)n_plain), dim3(NT), 0, stream, k.cur, buf_cap, k.out, k.out_stride, (int)n_mid,
-                                        (const unsigned long long *)nullptr, (const unsigned long long *)nullptr, epi, list_plain, pass_eg);
-        if (n_bp1) hipLaunchKernelGGL(pass, dim3(gx, (unsigned)n_bp1), dim3(NT), 0, stream, k.other, buf_cap, k.out, k.out_stride, (int)n_mid,
-                                      (const unsigned long long *)nullptr, (const unsigned long long *)nullptr, epi, list_bp1, pass_eg);
+        if (lists[L_PLAIN].n) hipLaunchKernelGGL(pass, dim3(gx, (unsigned)lists[L_PLAIN].n), dim3(NT), 0, stream, k.cur, buf_cap, k.out, k.out_stride, (int)n_mid,
+                                        (const unsigned long long *)nullptr, (const unsigned long long *)nullptr, epi, lists[L_PLAIN].dev, pass_eg);
+        if (lists[L_BP1].n) hipLaunchKernelGGL(pass, dim3(gx, (unsigned)lists[L_BP1].n), dim3(NT), 0, stream, k.other, buf_cap, k.out, k.out_stride, (int)n_mid,
+                                      (const unsigned long long *)nullptr, (const unsigned long long *)nullptr, epi, lists[L_BP1].dev, pass_eg);
     }
-    if (n_amsq) hipLaunchKernelGGL(amsq_apply_kernel, dim3((unsigned)n_amsq), dim3(64), 0, stream, k.out, k.out_stride, (int)n_mid, list_amsq,
+    if (lists[L_AMSQ].n) hipLaunchKernelGGL(amsq_apply_kernel, dim3((unsigned)lists[L_AMSQ].n), dim3(64), 0, stream, k.out, k.out_stride, (int)n_mid, lists[L_AMSQ].dev,
                                    amsq_mag, amsq_mag_cap, amsq_prm, amsq_state, amsq_cup, amsq_cdown);       // xamsq, RXA.c:596
     if (eg.kind && !k.eg_fused) pack_audio(k.out, k.out_stride, n_mid);
     tick(3);
@@ -2929,7 +2863,7 @@ int qh_rxa_nch(const qh_rxa *h) { return h->e.nch; }
 int qh_rxa_dsp_insize(const qh_rxa *h) { return h->e.dsp_insize; }
 int qh_rxa_dsp_outsize(const qh_rxa *h) { return h->e.dsp_outsize; }
 void *qh_rxa_stream(const qh_rxa *h) { return h ? (void *)h->e.stream : nullptr; }
-long long qh_rxa_device_bytes(const qh_rxa *h) { return h->e.dev_bytes; }
+long long qh_rxa_device_bytes(const qh_rxa *h) { return h->e.dev_bytes(); }
 
 #define FOR_CH(h, ch, body)                                                                       \
     do {                                                                                          \
