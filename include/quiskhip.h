@@ -143,6 +143,13 @@ int qh_rxa_SetRXAmpeakFilEnable(qh_rxa *e, int ch, int fil, int enable);        
 int qh_rxa_SetRXAmpeakFilFreq(qh_rxa *e, int ch, int fil, double freq);         /* wdsp/iir.c:517-526 */
 int qh_rxa_SetRXAmpeakFilBw(qh_rxa *e, int ch, int fil, double bw);             /* wdsp/iir.c:528-537 */
 int qh_rxa_SetRXAmpeakFilGain(qh_rxa *e, int ch, int fil, double gain);         /* wdsp/iir.c:539-548 */
+/* xssql, the syllabic squelch between xmpeak and the panel (wdsp/RXA.c:594), off at create (RXA.c:447-461); a channel that turns it on
+ * starts muted.  No setter flushes; qh_rxa_flush zeroes its blocker, crossing ring and low-pass only (ssql.c:208-220).  The threshold
+ * setter keeps threshold / 2.  A tau below 0 or not finite, or a threshold that is not finite, is refused with QH_ERR_INVALID. */
+int qh_rxa_SetRXASSQLRun(qh_rxa *e, int ch, int run);                           /* wdsp/ssql.c:330-336 */
+int qh_rxa_SetRXASSQLThreshold(qh_rxa *e, int ch, double threshold);            /* wdsp/ssql.c:338-346 */
+int qh_rxa_SetRXASSQLTauMute(qh_rxa *e, int ch, double tau_mute);               /* wdsp/ssql.c:348-358 */
+int qh_rxa_SetRXASSQLTauUnMute(qh_rxa *e, int ch, double tau_unmute);           /* wdsp/ssql.c:360-370 */
 int qh_rxa_SetRXAAMSQThreshold(qh_rxa *e, int ch, double threshold_db);
 int qh_rxa_SetRXAAMSQMaxTail(qh_rxa *e, int ch, double tail_seconds);
 /* xanf / xanr (wdsp/anf.c:82-133, anr.c:82-133), setters wdsp/anf.c:175-239 and anr.c:175-238; which position (0 before
@@ -322,6 +329,10 @@ void SetRXAmpeakFilEnable(int channel, int fil, int enable);
 void SetRXAmpeakFilFreq(int channel, int fil, double freq);
 void SetRXAmpeakFilBw(int channel, int fil, double bw);
 void SetRXAmpeakFilGain(int channel, int fil, double gain);
+void SetRXASSQLRun(int channel, int run);                                        /* wdsp/ssql.c:330-336 */
+void SetRXASSQLThreshold(int channel, double threshold);                         /* wdsp/ssql.c:338-346 */
+void SetRXASSQLTauMute(int channel, double tau_mute);                            /* wdsp/ssql.c:348-358 */
+void SetRXASSQLTauUnMute(int channel, double tau_unmute);                        /* wdsp/ssql.c:360-370 */
 void SetRXAAMSQThreshold(int channel, double threshold);                         /* wdsp/amsq.c:224-232, dB */
 void SetRXAAMSQMaxTail(int channel, double tail);                                /* wdsp/amsq.c:234-243, seconds */
 void SetRXAEMNRRun(int channel, int run);                                        /* wdsp/emnr.c:1096-1110; needs the files `calculus` and

@@ -36,6 +36,7 @@
 #include "qh_emnr.hpp"
 #include "qh_snba.hpp"
 #include "qh_audio_peak.hpp"
+#include "qh_ssql.hpp"
 #include "qh_internal.hpp"
 
 namespace qh {
@@ -135,12 +136,17 @@ struct ChanCfg {
     double mp_f[kApPeaks] = { 2125.0, 2295.0 }, mp_bw[kApPeaks] = { 75.0, 75.0 }, mp_gain[kApPeaks] = { 1.0, 1.0 };
     bool ap_dirty = true, sp_flush = false, mp_flush[kApPeaks] = { false, false };
     bool ap_on() const { return cbl_run || sp_run || mp_run; }
+    // xssql (create_ssql of create_rxa, RXA.c:447-461: run 0, wthresh 0.08, tau_mute = tau_unmute = 0.1); no setter flushes it
+    int ssql_run = 0;
+    double ssql_wthresh = 0.08, ssql_tau_mute = 0.1, ssql_tau_unmute = 0.1;
+    bool ssql_dirty = true;
+    bool ssql_on() const { return ssql_run != 0; }
     // (the new stages sit behind xwcpagc too, ahead of the panel: a fixed gain that changes while a peak still rings must not reach
-    // the ringing tail, so it is applied at the AGC's spot for them as well)
+    // the ringing tail, so it is applied at the AGC's spot for them as well; SSQL's detector reads amplitude, so it needs the gain too)
     bool fix_before() const
     {
         return agc_run && agc_mode == 0 && ((bp1_run && bp1_pos) || (lms[0].run && lms[0].position) || (lms[1].run && lms[1].position) ||
-                                            (emnr_run && emnr_pos) || ap_on());
+                                            (emnr_run && emnr_pos) || ap_on() || ssql_on());
     }
 };
 
@@ -253,6 +259,22 @@ struct Engine {
     std::vector<double> ap_M_h;
     std::vector<ApParam> ap_prm_h;
     int ap_alloc();
+    // xssql (qh_ssql.hpp), made when a channel first runs it: its two channel lists (by the buffer that holds the row, as L_AP; a
+    // block of their own, so that an engine without SSQL allocates what it did before), parameters, state, the ramps, the tiles' rows
+    // [nch][ssql_ends_cap][kSsE], the crossing / window / trigger bits [3][nch][ssql_wcap] and the words' machine records [nch][ssql_wcap]
+    ChanList ssql_lists[2];
+    std::vector<int> ssql_h[2];
+    int *ssql_list_block = nullptr;
+    SsqlParam *ssql_prm = nullptr;
+    SsqlState *ssql_state = nullptr;
+    double *ssql_cup = nullptr, *ssql_cdown = nullptr, *ssql_ends = nullptr;
+    unsigned long long *ssql_bits = nullptr;
+    int *ssql_rec = nullptr;
+    long long ssql_ends_cap = 0, ssql_wcap = 0, ssql_rec_cap = 0;
+    int ssql_L = 0, ssql_ntup = 0, ssql_ntdown = 0;
+    std::vector<SsqlParam> ssql_prm_h;
+    int ssql_alloc();
+    bool ssql_listed() const { return ssql_lists[0].n || ssql_lists[1].n; }
     // snba: the blanker's parameters, taps, state and the Toeplitz-inverse scratch
     SnbaParam snba_prm{};
     double *snba_state = nullptr, *snba_hin = nullptr, *snba_hout = nullptr, *snba_scratch = nullptr;
@@ -434,6 +456,8 @@ struct Engine {
     int run_agc(ChainCall &k);
     int refresh_ap(const ChainCall &k);
     void run_audio_peak(const ChainCall &k);
+    int refresh_ssql(const ChainCall &k);
+    void run_ssql(const ChainCall &k);
     void run_output(const ChainCall &k);
     qh_rat *rsmpout = nullptr;          // xresample out (wdsp/RXA.c:596), only when out_rate != dsp_rate
     qh_rat *rsmpin = nullptr;           // xresample in for the rate ratios the overlap-save front stage does not cover (D == 0)
@@ -878,6 +902,7 @@ void Engine::build_lists(std::vector<int> (&h)[L_COUNT])
 {
     std::vector<int> stale_cur, stale_other;
     int sam0 = 0;
+    ssql_h[0].clear(); ssql_h[1].clear();
     for (int ch = 0; ch < nch; ch++) {
         const ChanCfg &c = cfg[(size_t)ch];
         if (c.amsq_run) h[L_AMSQ].push_back(ch);
@@ -889,6 +914,7 @@ void Engine::build_lists(std::vector<int> (&h)[L_COUNT])
         if (c.bp1_run) h[L_BP1P + (c.bp1_pos ? 1 : 0)].push_back(ch);
         if (c.fix_before()) h[L_FIX + at_agc].push_back(ch);
         if (c.ap_on()) h[L_AP + (c.bp1_run ? 1 : 0)].push_back(ch);        // where the channel is behind bp1 at either position
+        if (c.ssql_on()) ssql_h[c.bp1_run ? 1 : 0].push_back(ch);
         if (c.fmd_run && c.lim_run) h[L_LIM].push_back(ch);
         if (c.amd_run && c.amd_mode == 0) h[L_AM].push_back(ch);
         // SAM channels with sbmode 0 (no all-pass chains) first
@@ -931,6 +957,7 @@ void Engine::build_lists(std::vector<int> (&h)[L_COUNT])
     h[L_PAIRS_SAM] = bp1_pairs(h[L_SAM]);
     np_fm = (int)h[L_PAIRS_FM].size() / 2; np_am = (int)h[L_PAIRS_AM].size() / 2; np_sam = (int)h[L_PAIRS_SAM].size() / 2;
     for (int i = 0; i < L_COUNT; i++) lists[i].n = (int)h[i].size();
+    for (int b = 0; b < 2; b++) ssql_lists[b].n = (int)ssql_h[b].size();
 }
 
 // The stages made when a channel first runs one of them (the lists' counts say which)
@@ -938,6 +965,7 @@ int Engine::stages_alloc()
 {
     const double rate = (double)dsp_rate;
     if ((lists[L_AP].n || lists[L_AP + 1].n) && !ap_prm) if (int rc = ap_alloc()) return rc;
+    if (ssql_listed() && !ssql_prm) if (int rc = ssql_alloc()) return rc;
     if ((lists[L_EMNR].n || lists[L_EMNR + 1].n || lists[L_EMNR + 2].n) && !emnr_state) if (int rc = emnr_alloc()) return rc;
     if (lists[L_SNBA].n && !snba_state) if (int rc = snba_alloc()) return rc;
     if (lists[L_AMSQ].n && !amsq_prm) {
@@ -1037,6 +1065,12 @@ int Engine::refresh_lists()
     for (int ch = 0; ch < nch; ch++) fg[(size_t)ch] = cfg[(size_t)ch].agc_fixed;
     QH_HIP(hipMemcpyAsync(list_block, all.data(), all.size() * sizeof(int), hipMemcpyHostToDevice, stream));
     QH_HIP(hipMemcpyAsync(fix_gain, fg.data(), fg.size() * sizeof(double), hipMemcpyHostToDevice, stream));
+    std::vector<int> ss;
+    if (ssql_list_block) {
+        ss.assign((size_t)nch * 2, 0);
+        for (int b = 0; b < 2; b++) std::copy(ssql_h[b].begin(), ssql_h[b].end(), ss.begin() + (size_t)nch * b);
+        QH_HIP(hipMemcpyAsync(ssql_list_block, ss.data(), ss.size() * sizeof(int), hipMemcpyHostToDevice, stream));
+    }
     QH_HIP(hipStreamSynchronize(stream));
     lists_dirty = false;
     return QH_OK;
@@ -1944,7 +1978,9 @@ int Engine::chain_needs(ChainCall &k)
             return set_error(QH_ERR_UNSUPPORTED, "AGC mode %d is not provided (0 fixed, 1-4 long/slow/med/fast)", c.agc_mode);
         // (SetRXAAMDRun can switch the AM detector on beside the FM one, RXA.c:594-595 then runs both in a row: not provided, and said so)
         if (c.amd_run && c.fmd_run) return set_error(QH_ERR_UNSUPPORTED, "channel %d: the AM and the FM detector both switched on", (int)(&c - cfg.data()));
-        if (c.amd_run || c.fmd_run || (c.agc_run && c.agc_mode != 0) || c.lms[0].run || c.lms[1].run || c.amsq_run || c.emnr_run || c.snba_run || c.ap_on()) k.mixed = true;
+        if (c.amd_run || c.fmd_run || (c.agc_run && c.agc_mode != 0) || c.lms[0].run || c.lms[1].run || c.amsq_run || c.emnr_run || c.snba_run || c.ap_on() || c.ssql_on()) k.mixed = true;
+        if (c.ssql_on() && ((int)(0.070 * dsp_rate) < 64))
+            return set_error(QH_ERR_UNSUPPORTED, "SSQL needs ramps of 64 samples or more: dsp_rate %d is too low", dsp_rate);
         if (c.emnr_run && !emnr_tables) return set_error(QH_ERR_INVALID, "EMNR needs its gain tables first (qh_rxa_SetEMNRTables: WDSP's `calculus` and `zetaHat.bin` data)");
         if (c.nbp_run) { k.any_nbp = true; if (c.nbp_nc > k.nc_max) k.nc_max = c.nbp_nc; } else k.every_nbp = false;
         if (c.bp1_run) { k.any_bp1 = true; if (c.bp1_nc > k.nc_max) k.nc_max = c.bp1_nc; }
@@ -2040,6 +2076,7 @@ int Engine::process_chain(const double *d_in, long long in_stride, double *d_out
     if (int rc = ensure_buffers(k.n_mid)) return rc;
     if (k.long_mode) if (int rc = long_buffers()) return rc;
     if (int rc = refresh_ap(k)) return rc;
+    if (int rc = refresh_ssql(k)) return rc;
     ev_used = 0;
 
     k.in = reinterpret_cast<const double2 *>(d_in); k.in_stride = in_stride;
@@ -2147,7 +2184,7 @@ int Engine::plan_mixed(ChainCall &k)
     for (int f = 0; f < 2; f++) for (int p = 0; p < 3; p++) no_lms = no_lms && !lists[L_LMS + 3 * f + p].n;
     k.direct = k.split && !(dbg_forms & 2) && k.every_nbp && !eg.kind && !lists[L_LIM].n && !lists[L_AGC_CUR].n && !lists[L_AGC_OTHER].n && !lists[L_SNBA].n && !lists[L_SNB + 1].n && no_lms &&
                !lists[L_EMNR].n && !lists[L_EMNR + 1].n && !lists[L_EMNR + 2].n && !lists[L_FIX].n && !lists[L_FIX + 1].n && !lists[L_BP1P + 1].n && lists[L_BP1P].n == lists[L_BP1].n && lists[L_RB].n == lists[L_BP1].n &&
-               lists[L_USB].n + lists[L_FM].n == lists[L_PLAIN].n && !lists[L_AP].n && !lists[L_AP + 1].n &&
+               lists[L_USB].n + lists[L_FM].n == lists[L_PLAIN].n && !lists[L_AP].n && !lists[L_AP + 1].n && !ssql_listed() &&
                // the first stores to `out` come while other channels' input is still being read: not for a caller that works in place
                extents_apart(k.out, k.out_stride, k.n_mid, k.in, k.in_stride, k.n_in, nch);
     // ... and the AM channels' nbp0 leaves the envelope and every tile's share of the fade leveller's averages: one pass does the rest
@@ -2545,7 +2582,8 @@ int Engine::run_agc(ChainCall &k)
     }
     // ... and when every channel has the AGC as its last stage (nothing at position 1, no meters, squelch or audio frames), the gain
     // multiply applies the output matrix and writes the caller's rows: the output pass goes
-    bool no_p1 = !lists[L_BP1P + 1].n && !lists[L_FIX].n && !lists[L_FIX + 1].n && !lists[L_EMNR + 1].n && !lists[L_EMNR + 2].n && !lists[L_AMSQ].n && !meters_on && !eg.kind && !lists[L_AP].n && !lists[L_AP + 1].n;
+    bool no_p1 = !lists[L_BP1P + 1].n && !lists[L_FIX].n && !lists[L_FIX + 1].n && !lists[L_EMNR + 1].n && !lists[L_EMNR + 2].n && !lists[L_AMSQ].n && !meters_on && !eg.kind && !lists[L_AP].n && !lists[L_AP + 1].n &&
+                 !ssql_listed();
     for (int f = 0; f < 2; f++) for (int p = 1; p < 3; p++) no_p1 = no_p1 && !lists[L_LMS + 3 * f + p].n;
     k.agc_direct = tiled && no_p1 && nt_cur == lists[L_PLAIN].n && nt_other == lists[L_BP1].n;
     if (tiled) {
@@ -2762,6 +2800,150 @@ void Engine::run_audio_peak(const ChainCall &k)
     }
 }
 
+// ---- xssql (qh_ssql.hpp)
+int Engine::ssql_alloc()
+{
+    const double rate = (double)dsp_rate;
+    if (int rc = alloc(ssql_list_block, 2LL * nch)) return rc;
+    for (int b = 0; b < 2; b++) ssql_lists[b].dev = ssql_list_block + (size_t)nch * b;
+    if (int rc = alloc(ssql_prm, nch)) return rc;
+    if (int rc = alloc(ssql_state, nch)) return rc;
+    SsqlState z{};                                  // calc_ssql (ssql.c:133-140): all zero but the trigger voltage, MUTED
+    z.v = kSsTrThresh; z.state = SS_MUTED; z.count = 0;
+    std::vector<SsqlState> st((size_t)nch, z);
+    QH_HIP(hipMemcpyAsync(ssql_state, st.data(), st.size() * sizeof(SsqlState), hipMemcpyHostToDevice, stream));
+    // compute_ssql_slews (ssql.c:110-127), muted_gain 0, tup = tdown = 0.070 (RXA.c:452-454): theta accumulates as there
+    const double mg = 0.0;
+    ssql_ntup = (int)(0.070 * rate); ssql_ntdown = (int)(0.070 * rate);
+    std::vector<double> up((size_t)ssql_ntup + 1), down((size_t)ssql_ntdown + 1);
+    double delta = kPiRef / (double)ssql_ntup, theta = 0.0;
+    for (int i = 0; i <= ssql_ntup; i++) { up[(size_t)i] = mg + (1.0 - mg) * 0.5 * (1.0 - std::cos(theta)); theta += delta; }
+    delta = kPiRef / (double)ssql_ntdown; theta = 0.0;
+    for (int i = 0; i <= ssql_ntdown; i++) { down[(size_t)i] = mg + (1.0 - mg) * 0.5 * (1.0 + std::cos(theta)); theta += delta; }
+    if (int rc = alloc(ssql_cup, (long long)up.size())) return rc;
+    if (int rc = alloc(ssql_cdown, (long long)down.size())) return rc;
+    QH_HIP(hipMemcpyAsync(ssql_cup, up.data(), up.size() * sizeof(double), hipMemcpyHostToDevice, stream));
+    QH_HIP(hipMemcpyAsync(ssql_cdown, down.data(), down.size() * sizeof(double), hipMemcpyHostToDevice, stream));
+    QH_HIP(hipStreamSynchronize(stream));
+    ssql_prm_h.assign((size_t)nch, SsqlParam{});
+    ssql_L = 0;
+    for (ChanCfg &c : cfg) c.ssql_dirty = true;
+    return QH_OK;
+}
+
+// A^L for a D x D transition A (row-major), by squaring in long double
+static void ssql_power(const double *A0, int D, int L, double *T)
+{
+    std::vector<long double> A(A0, A0 + D * D), R((size_t)D * D, 0.0L), tmp((size_t)D * D);
+    for (int i = 0; i < D; i++) R[(size_t)i * D + i] = 1.0L;
+    auto mul = [&](const std::vector<long double> &X, const std::vector<long double> &Y, std::vector<long double> &Z) {
+        for (int r = 0; r < D; r++)
+            for (int c = 0; c < D; c++) {
+                long double acc = 0.0L;
+                for (int k = 0; k < D; k++) acc += X[(size_t)r * D + k] * Y[(size_t)k * D + c];
+                Z[(size_t)r * D + c] = acc;
+            }
+    };
+    for (int e = L; e > 0; e >>= 1) {
+        if (e & 1) { mul(R, A, tmp); R.swap(tmp); }
+        if (e > 1) { mul(A, A, tmp); A.swap(tmp); }
+    }
+    for (int i = 0; i < D * D; i++) T[i] = (double)R[(size_t)i];
+}
+
+// Parameters and carry transitions of the listed channels, and the tile length of this call (before anything is enqueued)
+int Engine::refresh_ssql(const ChainCall &k)
+{
+    if (!ssql_prm) return QH_OK;
+    const int nss = k.mixed ? ssql_lists[0].n + ssql_lists[1].n : 0;
+    int L = ssql_L;
+    if (nss) {
+        // as the audio-peak stages: about four wavefronts of 64 tiles per SIMD, 256 .. 8192 samples (a multiple of 64: whole words)
+        L = 256;
+        while (L < 8192 && (long long)nss * k.n_mid / L > 4LL * 64 * 1024) L *= 2;
+        const long long ntile = (k.n_mid + L - 1) / L, nw = kSsHistW + (k.n_mid + 63) / 64 + 1;
+        if (int rc = grow(ssql_ends, ssql_ends_cap, ntile, (long long)kSsE * nch)) return rc;
+        if (int rc = grow(ssql_bits, ssql_wcap, nw, 3LL * nch)) return rc;
+        if (int rc = grow(ssql_rec, ssql_rec_cap, nw, (long long)nch)) return rc;      // grows with ssql_wcap: the same stride
+    }
+    const double rate = (double)dsp_rate;
+    SsqlParam base{};
+    base.mtau = std::exp(-1.0 / (rate * 0.02));                         // calc_cbl, cblock.c:35 (create_cbl of calc_ssql, tau 0.02)
+    base.div = 2000.0 * 2.0 * kSsRing / rate;                          // create_ftov, ssql.c:51 (fmax 2000, rsize 2400)
+    {                                                                   // calc_dbqlp, iir.c:829-843: fc 11.3, Q 1.0
+        const double w0 = kTwoPiRef * 11.3 / rate, cs = std::cos(w0), c = std::sin(w0) / (2.0 * 1.0), den = 1.0 + c;
+        base.a0 = 0.5 * (1.0 - cs) / den; base.a1 = (1.0 - cs) / den; base.a2 = 0.5 * (1.0 - cs) / den;
+        base.b1 = 2.0 * cs / den; base.b2 = (c - 1.0) / den;
+    }
+    base.wdmult = std::exp(-1.0 / (rate * 0.5));                        // calc_ssql, ssql.c:136 (wdtau 0.5)
+    base.muted_gain = 0.0;
+    base.ntup = ssql_ntup; base.ntdown = ssql_ntdown;
+    if (nss) {
+        const double Ac[4] = { 0.0, 0.0, -1.0, base.mtau };             // (xp, y) -> (0, -xp + mtau y)
+        const double om = 1.0 - base.wdmult;                            // (y1, y2, w) -> (y0, y1, wdmult w + (1 - wdmult) y0)
+        const double Al[9] = { base.b1, base.b2, 0.0, 1.0, 0.0, 0.0, om * base.b1, om * base.b2, base.wdmult };
+        ssql_power(Ac, 2, L, base.Tc);
+        ssql_power(Al, 3, L, base.Tl);
+    }
+    bool up = false;
+    for (int ch = 0; ch < nch; ch++) {
+        ChanCfg &c = cfg[(size_t)ch];
+        if (!c.ssql_dirty && !(nss && L != ssql_L && c.ssql_on())) continue;
+        SsqlParam &q = ssql_prm_h[(size_t)ch];
+        q = base;
+        q.wthresh = c.ssql_wthresh;
+        q.mute_mult = 1.0 - std::exp(-1.0 / (rate * c.ssql_tau_mute));            // ssql.c:137-138, :339-370
+        q.unmute_mult = 1.0 - std::exp(-1.0 / (rate * c.ssql_tau_unmute));
+        QH_HIP(hipMemcpyAsync(ssql_prm + ch, &q, sizeof(q), hipMemcpyHostToDevice, stream));
+        c.ssql_dirty = false;
+        up = true;
+    }
+    if (up) QH_HIP(hipStreamSynchronize(stream));
+    if (nss) ssql_L = L;
+    return QH_OK;
+}
+
+// the squelch of the listed channels, in place on the rows that hold them behind bp1 (cur / other)
+void Engine::run_ssql(const ChainCall &k)
+{
+    if (!ssql_prm || !ssql_listed()) return;
+    const int n = (int)k.n_mid, L = ssql_L;
+    const long long ntile = (k.n_mid + L - 1) / L, estride = ssql_ends_cap * kSsE, ws = ssql_wcap;
+    unsigned long long *xb = ssql_bits, *wdb = xb + (size_t)nch * ws, *trb = wdb + (size_t)nch * ws;
+    const unsigned ngroups = (unsigned)((ntile + 63) / 64);
+    const long long per = (k.n_mid + 255) / 256;
+    const unsigned gx = (unsigned)(per < 1024 ? per : 1024);
+    for (int b = 0; b < 2; b++) {
+        const int nl = ssql_lists[b].n;
+        if (!nl) continue;
+        double2 *rows = b ? k.other : k.cur;
+        const int *lst = ssql_lists[b].dev;
+        const dim3 tiles(ngroups, (unsigned)nl);
+        if (ntile > 1)
+            hipLaunchKernelGGL(ssql_cbl_kernel<0>, tiles, dim3(64), 0, stream, (const double2 *)rows, buf_cap, n, lst, (const SsqlParam *)ssql_prm,
+                               ssql_state, ssql_ends, estride, xb, ws, L);
+        hipLaunchKernelGGL((ssql_carry_kernel<2, false>), dim3((unsigned)nl), dim3(64), 0, stream, n, L, lst, (const SsqlParam *)ssql_prm,
+                           (const SsqlState *)ssql_state, ssql_ends, estride);
+        hipLaunchKernelGGL(ssql_cbl_kernel<1>, tiles, dim3(64), 0, stream, (const double2 *)rows, buf_cap, n, lst, (const SsqlParam *)ssql_prm,
+                           ssql_state, ssql_ends, estride, xb, ws, L);
+        if (ntile > 1)
+            hipLaunchKernelGGL(ssql_lp_kernel<0>, tiles, dim3(64), 0, stream, n, lst, (const SsqlParam *)ssql_prm, ssql_state, ssql_ends, estride,
+                               (const unsigned long long *)xb, wdb, ws, L);
+        hipLaunchKernelGGL((ssql_carry_kernel<3, false>), dim3((unsigned)nl), dim3(64), 0, stream, n, L, lst, (const SsqlParam *)ssql_prm,
+                           (const SsqlState *)ssql_state, ssql_ends, estride);
+        hipLaunchKernelGGL(ssql_lp_kernel<1>, tiles, dim3(64), 0, stream, n, lst, (const SsqlParam *)ssql_prm, ssql_state, ssql_ends, estride,
+                           (const unsigned long long *)xb, wdb, ws, L);
+        hipLaunchKernelGGL((ssql_carry_kernel<1, true>), dim3((unsigned)nl), dim3(64), 0, stream, n, L, lst, (const SsqlParam *)ssql_prm,
+                           (const SsqlState *)ssql_state, ssql_ends, estride);
+        hipLaunchKernelGGL(ssql_trigger_kernel, tiles, dim3(64), 0, stream, n, lst, (const SsqlParam *)ssql_prm, ssql_state,
+                           (const double *)ssql_ends, estride, (const unsigned long long *)wdb, trb, ws, L);
+        hipLaunchKernelGGL(ssql_walk_kernel, dim3((unsigned)nl), dim3(64), 0, stream, n, lst, (const SsqlParam *)ssql_prm, ssql_state,
+                           (const unsigned long long *)trb, ssql_rec, (const unsigned long long *)xb, ws);
+        hipLaunchKernelGGL(ssql_apply_kernel, dim3(gx, (unsigned)nl), dim3(256), 0, stream, rows, buf_cap, n, lst, (const SsqlParam *)ssql_prm,
+                           (const unsigned long long *)trb, (const int *)ssql_rec, ws, (const double *)ssql_cup, (const double *)ssql_cdown);
+    }
+}
+
 // xwcpagc mode 0 where a position-1 stage follows it, xanf / xanr / xemnr / bp1 at position 1, the agc meter, then xwcpagc mode 0 +
 // xpanel in the output pass, xamsq and the audio frames
 void Engine::run_output(const ChainCall &k)
@@ -2783,6 +2965,7 @@ void Engine::run_output(const ChainCall &k)
                                       m_agc, m_prm, lists[L_BP1].dev, (const double *)m_g2);
     }
     run_audio_peak(k);                  // xcbl, xspeak, xmpeak (RXA.c:591-593)
+    run_ssql(k);                        // xssql (RXA.c:594)
     tick(2);
     // xwcpagc mode 0 + xpanel, narrowed in the store when the audio frames are fused -- unless every channel's last stage has written
     // the caller's buffer
@@ -3343,6 +3526,32 @@ int qh_rxa_SetRXAmpeakFilFreq(qh_rxa *h, int ch, int fil, double f) { return mpe
 int qh_rxa_SetRXAmpeakFilBw(qh_rxa *h, int ch, int fil, double bw) { return mpeak_design(h, ch, fil, 1, bw); }
 int qh_rxa_SetRXAmpeakFilGain(qh_rxa *h, int ch, int fil, double g) { return mpeak_design(h, ch, fil, 2, g); }
 
+// xssql (ssql.c:330-370).  No setter flushes; SetRXASSQLThreshold keeps half its argument; each tau setter recomputes its own
+// multiplier.  A tau below 0 or not finite, and a threshold that is not finite, are refused and change nothing (the reference's
+// trigger recurrence diverges on them); a tau of 0 gives a multiplier of 1, as there.
+int qh_rxa_SetRXASSQLRun(qh_rxa *h, int ch, int run)
+{
+    FOR_CH(h, ch, {
+        run = run ? 1 : 0;
+        if (c.ssql_run != run) { c.ssql_run = run; c.ssql_dirty = true; c.epi_dirty = true; h->e.lists_dirty = true; }   // fix_before() follows
+    });
+}
+int qh_rxa_SetRXASSQLThreshold(qh_rxa *h, int ch, double threshold)
+{
+    if (!std::isfinite(threshold)) return set_error(QH_ERR_INVALID, "SetRXASSQLThreshold: threshold %g is not finite", threshold);
+    FOR_CH(h, ch, { c.ssql_wthresh = threshold / 2.0; c.ssql_dirty = true; });
+}
+int qh_rxa_SetRXASSQLTauMute(qh_rxa *h, int ch, double tau)
+{
+    if (!std::isfinite(tau) || tau < 0.0) return set_error(QH_ERR_INVALID, "SetRXASSQLTauMute: tau %g is negative or not finite", tau);
+    FOR_CH(h, ch, { c.ssql_tau_mute = tau; c.ssql_dirty = true; });
+}
+int qh_rxa_SetRXASSQLTauUnMute(qh_rxa *h, int ch, double tau)
+{
+    if (!std::isfinite(tau) || tau < 0.0) return set_error(QH_ERR_INVALID, "SetRXASSQLTauUnMute: tau %g is negative or not finite", tau);
+    FOR_CH(h, ch, { c.ssql_tau_unmute = tau; c.ssql_dirty = true; });
+}
+
 int qh_rxa_SetRXAPanelGain1(qh_rxa *h, int ch, double g) { FOR_CH(h, ch, { c.gain1 = g; c.epi_dirty = true; }); }
 int qh_rxa_SetRXAPanelGain2(qh_rxa *h, int ch, double gI, double gQ) { FOR_CH(h, ch, { c.gain2I = gI; c.gain2Q = gQ; c.epi_dirty = true; }); }
 int qh_rxa_SetRXAPanelSelect(qh_rxa *h, int ch, int s) { FOR_CH(h, ch, { c.inselect = s; c.epi_dirty = true; }); }
@@ -3545,6 +3754,7 @@ int qh_rxa_flush(qh_rxa *h)
     for (ChanCfg &c : e.cfg) { c.lms[0].flush = c.lms[1].flush = true; c.emnr_flush = true; c.snba_flush = true; c.snb_flush = true; }    // flush_anf / flush_anr / flush_emnr, RXA.c:541-543
     if (e.amsq_state) QH_HIP(hipMemsetAsync(e.amsq_state, 0, (size_t)e.nch * sizeof(AmsqState), e.stream));     // flush_amsq
     if (e.ap_state) QH_HIP(hipMemsetAsync(e.ap_state, 0, (size_t)e.nch * kApW * sizeof(double), e.stream));    // flush_cbl / _speak / _mpeak, RXA.c:553-555
+    if (e.ssql_state) hipLaunchKernelGGL(ssql_flush_kernel, dim3((unsigned)e.nch), dim3(64), 0, e.stream, e.ssql_state);    // flush_ssql, RXA.c:556
     if (e.demod_alloc) {                        // flush_amd / flush_fmd / flush_snotch
         QH_HIP(hipMemsetAsync(e.am_state, 0, (size_t)e.nch * sizeof(AmState), e.stream));
         QH_HIP(hipMemsetAsync(e.pll_state, 0, (size_t)e.nch * sizeof(PllState), e.stream));

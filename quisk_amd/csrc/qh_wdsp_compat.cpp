@@ -702,6 +702,11 @@ void SetRXAmpeakFilEnable(int channel, int fil, int enable) { WDSP_SETTER(qh_rxa
 void SetRXAmpeakFilFreq(int channel, int fil, double freq) { WDSP_SETTER(qh_rxa_SetRXAmpeakFilFreq(L.c->eng, 0, fil, freq)); }
 void SetRXAmpeakFilBw(int channel, int fil, double bw) { WDSP_SETTER(qh_rxa_SetRXAmpeakFilBw(L.c->eng, 0, fil, bw)); }
 void SetRXAmpeakFilGain(int channel, int fil, double gain) { WDSP_SETTER(qh_rxa_SetRXAmpeakFilGain(L.c->eng, 0, fil, gain)); }
+// the syllabic squelch, wdsp/ssql.c:330-370
+void SetRXASSQLRun(int channel, int run) { WDSP_SETTER(qh_rxa_SetRXASSQLRun(L.c->eng, 0, run)); }
+void SetRXASSQLThreshold(int channel, double threshold) { WDSP_SETTER(qh_rxa_SetRXASSQLThreshold(L.c->eng, 0, threshold)); }
+void SetRXASSQLTauMute(int channel, double tau_mute) { WDSP_SETTER(qh_rxa_SetRXASSQLTauMute(L.c->eng, 0, tau_mute)); }
+void SetRXASSQLTauUnMute(int channel, double tau_unmute) { WDSP_SETTER(qh_rxa_SetRXASSQLTauUnMute(L.c->eng, 0, tau_unmute)); }
 // the LMS auto-notch / noise reduction, wdsp/anf.c:175-239, anr.c:175-238
 void SetRXAANFRun(int channel, int v) { WDSP_SETTER(qh_rxa_SetRXAANFRun(L.c->eng, 0, v)); }
 void SetRXAANFTaps(int channel, int v) { WDSP_SETTER(qh_rxa_SetRXAANFTaps(L.c->eng, 0, v)); }

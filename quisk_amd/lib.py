@@ -67,11 +67,13 @@ def load():
         f.restype = i
     for n in ("SetRXAANFVals", "SetRXAANRVals"):
         getattr(L, "qh_rxa_" + n).argtypes = [vp, i, i, i, d, d]
-    # the carrier block and the audio peak filters (wdsp/cblock.c, wdsp/iir.c)
+    # the carrier block, the audio peak filters and the syllabic squelch (wdsp/cblock.c, wdsp/iir.c, wdsp/ssql.c)
     for n, a in (("SetRXACBLRun", [vp, i, i]), ("SetRXASPCWRun", [vp, i, i]), ("SetRXASPCWFreq", [vp, i, d]),
                  ("SetRXASPCWBandwidth", [vp, i, d]), ("SetRXASPCWGain", [vp, i, d]), ("SetRXAmpeakRun", [vp, i, i]),
                  ("SetRXAmpeakNpeaks", [vp, i, i]), ("SetRXAmpeakFilEnable", [vp, i, i, i]), ("SetRXAmpeakFilFreq", [vp, i, i, d]),
-                 ("SetRXAmpeakFilBw", [vp, i, i, d]), ("SetRXAmpeakFilGain", [vp, i, i, d])):
+                 ("SetRXAmpeakFilBw", [vp, i, i, d]), ("SetRXAmpeakFilGain", [vp, i, i, d]),
+                 ("SetRXASSQLRun", [vp, i, i]), ("SetRXASSQLThreshold", [vp, i, d]), ("SetRXASSQLTauMute", [vp, i, d]),
+                 ("SetRXASSQLTauUnMute", [vp, i, d])):
         f = getattr(L, "qh_rxa_" + n)
         f.argtypes = a
         f.restype = i

@@ -21,7 +21,8 @@ _SETTERS = ("SetRXAMode", "RXASetNC", "SetRXAShiftRun", "RXANBPSetRun", "SetRXAB
             "SetRXAAMSQRun", "SetRXAAMSQThreshold", "SetRXAAMSQMaxTail", "SetRXAANFRun", "SetRXAANFTaps", "SetRXAANFDelay", "SetRXAANFPosition", "SetRXAANFGain", "SetRXAANFLeakage", "SetRXAANFVals",
             "SetRXAANRRun", "SetRXAANRTaps", "SetRXAANRDelay", "SetRXAANRPosition", "SetRXAANRGain", "SetRXAANRLeakage", "SetRXAANRVals",
             "SetRXACBLRun", "SetRXASPCWRun", "SetRXASPCWFreq", "SetRXASPCWBandwidth", "SetRXASPCWGain", "SetRXAmpeakRun",
-            "SetRXAmpeakNpeaks", "SetRXAmpeakFilEnable", "SetRXAmpeakFilFreq", "SetRXAmpeakFilBw", "SetRXAmpeakFilGain")
+            "SetRXAmpeakNpeaks", "SetRXAmpeakFilEnable", "SetRXAmpeakFilFreq", "SetRXAmpeakFilBw", "SetRXAmpeakFilGain",
+            "SetRXASSQLRun", "SetRXASSQLThreshold", "SetRXASSQLTauMute", "SetRXASSQLTauUnMute")
 
 
 class AudioFormat(C.Structure):
