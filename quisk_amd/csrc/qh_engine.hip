@@ -3641,6 +3641,7 @@ int qh_rxa_set_band_tile(qh_rxa *h, int nfft)
     if (!h || (nfft != 0 && nfft != 4096 && nfft != 6144 && nfft != 8192)) return set_error(QH_ERR_INVALID, "qh_rxa_set_band_tile: 0 (default), 4096, 6144 or 8192");
     QH_RXA_LOCK(h);
     h->e.band_tile_pref = nfft;
+    h->e.epoch++;                   // the next call picks the tile anew (pick_band_tile): a captured launch sequence runs the old one
     return QH_OK;
 }
 int qh_rxa_band_tile(const qh_rxa *h) { return h ? h->e.bnfft : 0; }

@@ -52,23 +52,29 @@ def test_names_seeded_walk_against_restatement(qh):
     other = [("SetRXAMode", (1,)), ("SetRXAMode", (4,)), ("RXASetPassband", (D(200.0), D(2800.0))),
              ("RXASetPassband", (D(300.0), D(3000.0))), ("SetRXAAGCMode", (2,)), ("SetRXAAGCMode", (3,)), ("SetRXAAGCTop", (D(70.0),))]
     rng = np.random.default_rng(5)
-    nblk = 120
+    nblk, walk = 180, 120                 # the seeded walk, then a stretch in which the parameters stand still
     x = synth.make_input_numpy(1, nblk * IN)[0]
     ya, yb = [], []
     pending = {}
+    launches0 = lib.qh_wdsp_graph_launches()
+    steady = 0                              # fexchange0 calls with no setter on their channel since the call before
     try:
         for k in range(nblk):
-            if k % 6 == 3:
+            touched = set()
+            if k % 6 == 3 and k < walk:
                 for _ in range(2):
                     if rng.random() < 0.7:
                         name, args = new[int(rng.integers(0, len(new)))]
                         getattr(lib, name)(A, *[D(v) if isinstance(v, float) else v for v in args])
                         pending.setdefault(k + LAT, []).append((name, args))
+                        touched.add(A)
                     else:
                         name, args = other[int(rng.integers(0, len(other)))]
                         getattr(lib, name)(A, *args)
                         getattr(lib, name)(B, *args)
+                        touched.update((A, B))
                     assert lib.qh_wdsp_status() == 0, (name, lib.qh_last_error())
+            steady += 2 - len(touched)
             blk = x[k * IN:(k + 1) * IN]
             ya.append(_block(lib, A, blk))
             for name, args in pending.pop(k, []):
@@ -77,6 +83,8 @@ def test_names_seeded_walk_against_restatement(qh):
         ya, yb = np.concatenate(ya), np.concatenate(yb)
         assert np.any(ya != 0)
         assert rel_rms(ya, yb) < 1e-9, rel_rms(ya, yb)
+        # OpenChannel switches the launch replay on: what was compared above came out of replayed graphs, not plain launches only
+        assert lib.qh_wdsp_graph_launches() - launches0 >= steady // 2, (lib.qh_wdsp_graph_launches() - launches0, steady)
     finally:
         lib.CloseChannel(A)
         lib.CloseChannel(B)

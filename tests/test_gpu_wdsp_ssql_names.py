@@ -52,6 +52,7 @@ def test_names_against_restatement(qh):
     x = 0.3 * syllabic(nblk * IN, 192000.0, seed=3) * np.exp(-2j * np.pi * ((shift * t) % 1.0))
     ya, yr, gr = [], [], []
     pending = {}
+    launches0 = lib.qh_wdsp_graph_launches()
     try:
         for k in range(nblk):
             for name, args in script.get(k, []):
@@ -69,6 +70,10 @@ def test_names_against_restatement(qh):
         assert op >= 2 and cl >= 2, (op, cl)
         assert not np.any(ya[gr == 0.0])
         assert rel_rms(ya, yr) < 1e-9, rel_rms(ya, yr)
+        # OpenChannel switches the launch replay on: what was compared above came out of replayed graphs, not plain launches only.
+        # Parameters stood still for every call but the ones behind a setter (A's six; B has none): at least half of those replayed
+        steady = 2 * nblk - len(script)
+        assert lib.qh_wdsp_graph_launches() - launches0 >= steady // 2, (lib.qh_wdsp_graph_launches() - launches0, steady)
     finally:
         lib.CloseChannel(A)
         lib.CloseChannel(B)
