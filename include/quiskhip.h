@@ -286,6 +286,27 @@ void SetRXAFMDeviation(int channel, double deviation);                          
 void SetRXACTCSSFreq(int channel, double freq);                                  /* wdsp/fmd.c:248-258 */
 void SetRXACTCSSRun(int channel, int run);                                       /* wdsp/fmd.c:260-267 */
 double GetRXAMeter(int channel, int mt);                                         /* wdsp/meter.c:133-142 */
+/* The blanker WDSP's callers run in front of fexchange0 (wdsp/nob.c:307-422, wdsp.h:620-665): ids 0..31, each a one-channel qh_anb bank
+ * with staging rows of its own, so in == out works as it does for the reference's callers; buffsize is the n of xanbEXT.  in / out
+ * are host pointers, as fexchange0's are; samples that are already on the GPU go through qh_wdsp_xanbEXT_device, as fexchange0's go
+ * through qh_wdsp_fexchange0_device.  Errors (a bad or empty id, a refused value: see qh_anb_create) go to qh_wdsp_status() and change
+ * nothing.  Not provided: xanbEXTF and the "legacy interface" (nob.c:424-448), the pointer-based pSetRCVRANB* (nob.c:226-299). */
+void create_anbEXT(int id, int run, int buffsize, double samplerate, double tau, double hangtime, double advtime, double backtau,
+                   double threshold);                                            /* wdsp/nob.c:310-324 */
+void destroy_anbEXT(int id);                                                     /* wdsp/nob.c:326-330 */
+void flush_anbEXT(int id);                                                       /* wdsp/nob.c:332-336 */
+void xanbEXT(int id, double *in, double *out);                                   /* wdsp/nob.c:338-345 */
+void SetEXTANBRun(int id, int run);                                              /* wdsp/nob.c:347-354 */
+void SetEXTANBBuffsize(int id, int size);                                        /* wdsp/nob.c:356-363 */
+void SetEXTANBSamplerate(int id, int rate);                                      /* wdsp/nob.c:365-373 */
+void SetEXTANBTau(int id, double tau);                                           /* wdsp/nob.c:375-383 */
+void SetEXTANBHangtime(int id, double time);                                     /* wdsp/nob.c:385-393 */
+void SetEXTANBAdvtime(int id, double time);                                      /* wdsp/nob.c:395-403 */
+void SetEXTANBBacktau(int id, double tau);                                       /* wdsp/nob.c:405-413 */
+void SetEXTANBThreshold(int id, double thresh);                                  /* wdsp/nob.c:415-422 */
+/* xanbEXT for buffsize samples in device memory (d_in == d_out allowed): enqueued on the id's stream, which is ordered behind `stream`
+ * on entry; `stream` is ordered behind it on return.  Nothing is waited for.  The same samples as xanbEXT, bit for bit. */
+int qh_wdsp_xanbEXT_device(int id, const void *d_in, void *d_out, void *stream);
 /* Quisk's re-blocking shim around fexchange0 (quisk_wdsp.c:24-69): any nSamples in, scaled by 1/CLIP32 into
  * in_size blocks, results scaled back; returns the number of samples written to cSamples.  qh_wdsp_set_parameter
  * is the C form of quisk_wdsp_set_parameter (quisk_wdsp.c:71-91; in_size <= 0 / in_use < 0 leave the value).  One deviation: a CHANGE
@@ -637,6 +658,38 @@ int qh_nb_reset(qh_nb *b);
 int qh_nb_process(qh_nb *b, const void *d_in, long long in_stride, void *d_out, long long out_stride, int n);
 int qh_nb_process_host(qh_nb *b, const void *h_in, long long in_stride, void *h_out, long long out_stride, int n);
 int qh_nb_synchronize(qh_nb *b);
+/* ------------------------------------------------------------------ 10b. WDSP's noise blanker (ANB) */
+/* xanb (wdsp/nob.c:107-187) for `nch` fp64 complex streams at the receiver's input rate, where WDSP's callers run it: in front of
+ * fexchange0.  Every channel has its own settings and state, so channels with different delays run in one launch.  While a channel
+ * runs, its output lags its input by qh_anb_delay() = trans_count + adv_count samples (initBlanker, nob.c:33-52: max(2, (int)(tau *
+ * samplerate)) + (int)(advtime * samplerate)); with run = 0 samples pass undelayed and the delay line and every other piece of state
+ * stand still (nob.c:185-186).  The detector's average is stepped in time tiles whose start values come from a scan (qh_anb.hip): a
+ * trigger can differ from a sample-serial run only where |x| lies within eps / (1 - backmult) of avg * threshold; given the triggers
+ * the output is the reference's bit for bit.  htime survives a restart and is not set on entry to the hang state, as in the reference
+ * (the first quiet hang lasts hang_count samples longer than the later ones).
+ * Refused with QH_ERR_INVALID, nothing changed: tau or advtime outside [0, 0.002] and a rate outside (0, 1536000] (the reference sizes
+ * wave[] and the delay line for these and never checks, nob.c:29-31,80-82), a backtau that is not finite and positive, a threshold that
+ * is not finite, a negative hangtime, a hangtime * samplerate of 2^30 samples or more (hang_count is an int).  Setters: ch = -1 means
+ * every channel; they take effect at the next process call. */
+typedef struct qh_anb qh_anb;
+qh_anb *qh_anb_create(int device, int nch, double samplerate, double tau, double hangtime, double advtime, double backtau, double threshold,
+                      void *stream);                                             /* create_anb + initBlanker, nob.c:33-87; run = 1 */
+void qh_anb_destroy(qh_anb *b);                                                  /* nob.c:89-97 */
+int qh_anb_delay(qh_anb *b, int ch);                                             /* trans_count + adv_count, nob.c:36-41 */
+int qh_anb_set_run(qh_anb *b, int ch, int run);                                  /* nob.c:348-354: resets nothing */
+int qh_anb_set_samplerate(qh_anb *b, int ch, double samplerate);                 /* nob.c:365-373: initBlanker, a full restart that zeroes the delay line */
+int qh_anb_set_tau(qh_anb *b, int ch, double tau);                               /* nob.c:375-383: restart */
+int qh_anb_set_hangtime(qh_anb *b, int ch, double hangtime);                     /* nob.c:385-393: restart */
+int qh_anb_set_advtime(qh_anb *b, int ch, double advtime);                       /* nob.c:395-403: restart */
+int qh_anb_set_backtau(qh_anb *b, int ch, double backtau);                       /* nob.c:405-413: restart */
+int qh_anb_set_threshold(qh_anb *b, int ch, double threshold);                   /* nob.c:415-422: resets nothing */
+int qh_anb_flush(qh_anb *b, int ch);                                             /* flush_anb, nob.c:99-105: restart */
+/* xanb (nob.c:107-187) over n >= 0 samples of every channel: device rows [nch][stride] of interleaved complex doubles, strides in
+ * complex samples, asynchronous on the bank's stream.  Output rows that share a byte with the input rows are refused (QH_ERR_INVALID,
+ * state untouched); the _host form (synchronous, pageable memory) takes h_out == h_in. */
+int qh_anb_process(qh_anb *b, const void *d_in, long long in_stride, void *d_out, long long out_stride, int n);
+int qh_anb_process_host(qh_anb *b, const void *h_in, long long in_stride, void *h_out, long long out_stride, int n);
+int qh_anb_synchronize(qh_anb *b);
 /* dAutoNotch (quisk.c:786-963; 8(f) rank 3) inside the receiver bank, where the mode calls it (on the real audio after
  * the Rx filter; after the interpolators for FM; DGT-IQ has none): set_auto_notch(i) (quisk.c:4596) -- stores the flag
  * and starts the notch over -- with rit_freq as set_sidetone passes it (quisk.c:4712): the CW modes keep the notch off

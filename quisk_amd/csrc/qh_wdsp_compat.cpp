@@ -982,3 +982,145 @@ void SetRXASNBAovrlp(int channel, int ovrlp) { WDSP_SETTER(qh_rxa_SetRXASNBAovrl
 void SetRXASNBApmultmin(int channel, double pmultmin) { WDSP_SETTER(qh_rxa_SetRXASNBApmultmin(L.c->eng, 0, pmultmin)); }  // snb.c:653
 
 }  // extern "C"
+
+// ---- the blanker in front of fexchange0: create_anbEXT ... SetEXTANBThreshold (wdsp/nob.c:307-422) ----------------------------
+// panb[id], nob.c:307-308: each id a one-channel qh_anb bank on a stream of its own, with staging rows that let in == out
+namespace {
+constexpr int kMaxExtAnbs = 32;     // MAX_EXT_ANBS, nob.c:307
+struct ExtAnb {
+    qh_anb *b = nullptr;
+    int buffsize = 0, cap = 0;
+    hipStream_t stream = nullptr;
+    double *d_in = nullptr, *d_out = nullptr;
+    hipEvent_t ev_in = nullptr, ev_out = nullptr;
+};
+ExtAnb g_anb[kMaxExtAnbs];
+std::recursive_mutex g_anb_mtx[kMaxExtAnbs];
+
+void anb_release(ExtAnb &a)
+{
+    if (a.b) qh_anb_destroy(a.b);               // (waits for the stream)
+    (void)hipFree(a.d_in); (void)hipFree(a.d_out);
+    if (a.ev_in) (void)hipEventDestroy(a.ev_in);
+    if (a.ev_out) (void)hipEventDestroy(a.ev_out);
+    if (a.stream) (void)hipStreamDestroy(a.stream);
+    a = ExtAnb();
+}
+
+struct LockedAnb {
+    ExtAnb *a = nullptr;
+    std::unique_lock<std::recursive_mutex> lk;
+    explicit LockedAnb(int id)
+    {
+        g_status = QH_OK;
+        if (id < 0 || id >= kMaxExtAnbs) { g_status = qh::set_error(QH_ERR_INVALID, "ANB id %d out of range", id); return; }
+        lk = std::unique_lock<std::recursive_mutex>(g_anb_mtx[id]);
+        if (!g_anb[id].b) { g_status = qh::set_error(QH_ERR_INVALID, "ANB id %d has not been created", id); return; }
+        a = &g_anb[id];
+    }
+};
+
+int anb_staging(ExtAnb &a)
+{
+    if (a.buffsize <= a.cap) return QH_OK;
+    if (hipStreamSynchronize(a.stream) != hipSuccess) return qh::set_error(QH_ERR_HIP, "xanbEXT: synchronize failed");
+    (void)hipFree(a.d_in); (void)hipFree(a.d_out);
+    a.d_in = nullptr; a.d_out = nullptr; a.cap = 0;
+    if (hipMalloc((void **)&a.d_in, (size_t)a.buffsize * 16) != hipSuccess || hipMalloc((void **)&a.d_out, (size_t)a.buffsize * 16) != hipSuccess)
+        return qh::set_error(QH_ERR_HIP, "xanbEXT: staging allocation failed");
+    a.cap = a.buffsize;
+    return QH_OK;
+}
+}  // namespace
+
+extern "C" {
+
+void create_anbEXT(int id, int run, int buffsize, double samplerate, double tau, double hangtime, double advtime, double backtau, double threshold)
+{
+    g_status = QH_OK;
+    if (id < 0 || id >= kMaxExtAnbs) { g_status = qh::set_error(QH_ERR_INVALID, "ANB id %d out of range", id); return; }
+    std::unique_lock<std::recursive_mutex> lk(g_anb_mtx[id]);
+    ExtAnb &a = g_anb[id];
+    if (a.b) { g_status = qh::set_error(QH_ERR_INVALID, "ANB id %d already exists", id); return; }
+    if (buffsize <= 0) { g_status = qh::set_error(QH_ERR_INVALID, "create_anbEXT: bad buffer size"); return; }
+    if (hipStreamCreateWithFlags(&a.stream, hipStreamNonBlocking) != hipSuccess) {
+        a.stream = nullptr;
+        g_status = qh::set_error(QH_ERR_NO_DEVICE, "create_anbEXT: no HIP device (libquiskhip has no CPU fallback)");
+        return;
+    }
+    a.b = qh_anb_create(0, 1, samplerate, tau, hangtime, advtime, backtau, threshold, a.stream);
+    if (!a.b) { g_status = QH_ERR_INVALID; anb_release(a); return; }       // message already set
+    a.buffsize = buffsize;
+    int rc = qh_anb_set_run(a.b, 0, run);
+    if (!rc) rc = anb_staging(a);
+    if (rc) { g_status = rc; anb_release(a); }
+}
+
+void destroy_anbEXT(int id)
+{
+    LockedAnb L(id);
+    if (L.a) anb_release(*L.a);
+}
+
+void flush_anbEXT(int id)
+{
+    LockedAnb L(id);
+    if (L.a) g_status = qh_anb_flush(L.a->b, 0);
+}
+
+void xanbEXT(int id, double *in, double *out)
+{
+    LockedAnb L(id);
+    if (!L.a) return;
+    ExtAnb &a = *L.a;
+    if (!in || !out) { g_status = qh::set_error(QH_ERR_INVALID, "xanbEXT: null buffer"); return; }
+    if (int rc = anb_staging(a)) { g_status = rc; return; }
+    const size_t bytes = (size_t)a.buffsize * 16;
+    if (hipMemcpyAsync(a.d_in, in, bytes, hipMemcpyHostToDevice, a.stream) != hipSuccess) { g_status = qh::set_error(QH_ERR_HIP, "xanbEXT: upload failed"); return; }
+    if (int rc = qh_anb_process(a.b, a.d_in, a.buffsize, a.d_out, a.buffsize, a.buffsize)) { g_status = rc; return; }
+    if (hipMemcpyAsync(out, a.d_out, bytes, hipMemcpyDeviceToHost, a.stream) != hipSuccess || hipStreamSynchronize(a.stream) != hipSuccess)
+        g_status = qh::set_error(QH_ERR_HIP, "xanbEXT: download failed");
+}
+
+int qh_wdsp_xanbEXT_device(int id, const void *d_in, void *d_out, void *stream)
+{
+    LockedAnb L(id);
+    if (!L.a) return g_status;
+    ExtAnb &a = *L.a;
+    if (!d_in || !d_out) return g_status = qh::set_error(QH_ERR_INVALID, "qh_wdsp_xanbEXT_device: null buffer");
+    if (int rc = anb_staging(a)) return g_status = rc;
+    hipStream_t cs = (hipStream_t)stream;
+    if (!a.ev_in && (hipEventCreateWithFlags(&a.ev_in, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&a.ev_out, hipEventDisableTiming) != hipSuccess))
+        return g_status = qh::set_error(QH_ERR_HIP, "qh_wdsp_xanbEXT_device: event creation failed");
+    const size_t bytes = (size_t)a.buffsize * 16;
+    if (cs != a.stream) { (void)hipEventRecord(a.ev_in, cs); (void)hipStreamWaitEvent(a.stream, a.ev_in, 0); }
+    int rc = QH_OK;
+    if (hipMemcpyAsync(a.d_in, d_in, bytes, hipMemcpyDeviceToDevice, a.stream) != hipSuccess) rc = qh::set_error(QH_ERR_HIP, "qh_wdsp_xanbEXT_device: copy failed");
+    if (!rc) rc = qh_anb_process(a.b, a.d_in, a.buffsize, a.d_out, a.buffsize, a.buffsize);
+    if (!rc && hipMemcpyAsync(d_out, a.d_out, bytes, hipMemcpyDeviceToDevice, a.stream) != hipSuccess) rc = qh::set_error(QH_ERR_HIP, "qh_wdsp_xanbEXT_device: copy failed");
+    if (cs != a.stream) { (void)hipEventRecord(a.ev_out, a.stream); (void)hipStreamWaitEvent(cs, a.ev_out, 0); }
+    return g_status = rc;
+}
+
+#define ANB_SETTER(call)                    \
+    do {                                    \
+        LockedAnb L(id);                    \
+        if (L.a) g_status = (call);         \
+    } while (0)
+
+void SetEXTANBRun(int id, int run) { ANB_SETTER(qh_anb_set_run(L.a->b, 0, run)); }
+void SetEXTANBBuffsize(int id, int size)
+{
+    LockedAnb L(id);
+    if (!L.a) return;
+    if (size <= 0) { g_status = qh::set_error(QH_ERR_INVALID, "SetEXTANBBuffsize: bad buffer size"); return; }
+    L.a->buffsize = size;
+}
+void SetEXTANBSamplerate(int id, int rate) { ANB_SETTER(qh_anb_set_samplerate(L.a->b, 0, (double)rate)); }
+void SetEXTANBTau(int id, double tau) { ANB_SETTER(qh_anb_set_tau(L.a->b, 0, tau)); }
+void SetEXTANBHangtime(int id, double time) { ANB_SETTER(qh_anb_set_hangtime(L.a->b, 0, time)); }
+void SetEXTANBAdvtime(int id, double time) { ANB_SETTER(qh_anb_set_advtime(L.a->b, 0, time)); }
+void SetEXTANBBacktau(int id, double tau) { ANB_SETTER(qh_anb_set_backtau(L.a->b, 0, tau)); }
+void SetEXTANBThreshold(int id, double thresh) { ANB_SETTER(qh_anb_set_threshold(L.a->b, 0, thresh)); }
+
+}  // extern "C"

@@ -249,6 +249,29 @@ def load():
     L.qh_nb_process.argtypes = [vp, vp, ll, vp, ll, i]
     L.qh_nb_process_host.argtypes = [vp, vp, ll, vp, ll, i]
     L.qh_nb_synchronize.argtypes = [vp]
+    # WDSP's noise blanker (wdsp/nob.c): the bank and the EXT names in front of fexchange0
+    L.qh_anb_create.restype = vp
+    L.qh_anb_create.argtypes = [i, i, d, d, d, d, d, d, vp]
+    L.qh_anb_destroy.argtypes = [vp]
+    L.qh_anb_destroy.restype = None
+    L.qh_anb_delay.argtypes = [vp, i]
+    L.qh_anb_set_run.argtypes = [vp, i, i]
+    for n in ("samplerate", "tau", "hangtime", "advtime", "backtau", "threshold"):
+        getattr(L, "qh_anb_set_" + n).argtypes = [vp, i, d]
+    L.qh_anb_flush.argtypes = [vp, i]
+    L.qh_anb_process.argtypes = [vp, vp, ll, vp, ll, i]
+    L.qh_anb_process_host.argtypes = [vp, vp, ll, vp, ll, i]
+    L.qh_anb_synchronize.argtypes = [vp]
+    L.create_anbEXT.argtypes = [i, i, i, d, d, d, d, d, d]
+    L.create_anbEXT.restype = None
+    L.xanbEXT.argtypes = [i, vp, vp]
+    L.xanbEXT.restype = None
+    L.qh_wdsp_xanbEXT_device.argtypes = [i, vp, vp, vp]
+    for n, a in (("destroy_anbEXT", [i]), ("flush_anbEXT", [i]), ("SetEXTANBRun", [i, i]), ("SetEXTANBBuffsize", [i, i]),
+                 ("SetEXTANBSamplerate", [i, i]), ("SetEXTANBTau", [i, d]), ("SetEXTANBHangtime", [i, d]), ("SetEXTANBAdvtime", [i, d]),
+                 ("SetEXTANBBacktau", [i, d]), ("SetEXTANBThreshold", [i, d])):
+        getattr(L, n).argtypes = a
+        getattr(L, n).restype = None
     L.qh_qrx_set_noise_blanker.argtypes = [vp, i]
     L.qh_qrx_set_auto_notch.argtypes = [vp, i, i]
     L.qh_quisk_set_auto_notch.argtypes = [i, i]
