@@ -307,6 +307,28 @@ void SetEXTANBThreshold(int id, double thresh);                                 
 /* xanbEXT for buffsize samples in device memory (d_in == d_out allowed): enqueued on the id's stream, which is ordered behind `stream`
  * on entry; `stream` is ordered behind it on return.  Nothing is waited for.  The same samples as xanbEXT, bit for bit. */
 int qh_wdsp_xanbEXT_device(int id, const void *d_in, void *d_out, void *stream);
+/* WDSP's second blanker, the callers' "NB2" (wdsp/nobII.c:605-734): ids 0..31, each a one-channel qh_nob bank with staging rows of its
+ * own, so in == out works; buffsize is the n of xnobEXT.  slewtime is both the advance and the hang slew time and max_imp_seq_time is
+ * 0.025 s, as create_nobEXT fixes them (nobII.c:622-624).  Errors (a bad or empty id, a refused value: see qh_nob_create) go to
+ * qh_wdsp_status() and change nothing.  Not provided: xnobEXTF and the "legacy interface" (nobII.c:742-760), the pointer-based
+ * pSetRCVRNOB* (nobII.c:521-597). */
+void create_nobEXT(int id, int run, int mode, int buffsize, double samplerate, double slewtime, double hangtime, double advtime,
+                   double backtau, double threshold);                            /* wdsp/nobII.c:608-626 */
+void destroy_nobEXT(int id);                                                     /* wdsp/nobII.c:628-632 */
+void flush_nobEXT(int id);                                                       /* wdsp/nobII.c:634-638 */
+void xnobEXT(int id, double *in, double *out);                                   /* wdsp/nobII.c:640-647 */
+void SetEXTNOBRun(int id, int run);                                              /* wdsp/nobII.c:649-656 */
+void SetEXTNOBMode(int id, int mode);                                            /* wdsp/nobII.c:658-665 */
+void SetEXTNOBBuffsize(int id, int size);                                        /* wdsp/nobII.c:667-674 */
+void SetEXTNOBSamplerate(int id, int rate);                                      /* wdsp/nobII.c:676-684 */
+void SetEXTNOBTau(int id, double tau);                                           /* wdsp/nobII.c:686-695 */
+void SetEXTNOBHangtime(int id, double time);                                     /* wdsp/nobII.c:697-705 */
+void SetEXTNOBAdvtime(int id, double time);                                      /* wdsp/nobII.c:707-715 */
+void SetEXTNOBBacktau(int id, double tau);                                       /* wdsp/nobII.c:717-725 */
+void SetEXTNOBThreshold(int id, double thresh);                                  /* wdsp/nobII.c:727-734 */
+/* xnobEXT for buffsize samples in device memory (d_in == d_out allowed): enqueued on the id's stream, which is ordered behind `stream`
+ * on entry; `stream` is ordered behind it on return.  Nothing is waited for.  The same samples as xnobEXT, bit for bit. */
+int qh_wdsp_xnobEXT_device(int id, const void *d_in, void *d_out, void *stream);
 /* Quisk's re-blocking shim around fexchange0 (quisk_wdsp.c:24-69): any nSamples in, scaled by 1/CLIP32 into
  * in_size blocks, results scaled back; returns the number of samples written to cSamples.  qh_wdsp_set_parameter
  * is the C form of quisk_wdsp_set_parameter (quisk_wdsp.c:71-91; in_size <= 0 / in_use < 0 leave the value).  One deviation: a CHANGE
@@ -690,6 +712,47 @@ int qh_anb_flush(qh_anb *b, int ch);                                            
 int qh_anb_process(qh_anb *b, const void *d_in, long long in_stride, void *d_out, long long out_stride, int n);
 int qh_anb_process_host(qh_anb *b, const void *h_in, long long in_stride, void *h_out, long long out_stride, int n);
 int qh_anb_synchronize(qh_anb *b);
+/* ------------------------------------------------------------------ 10c. WDSP's second noise blanker (NOB, "NB2") */
+/* xnob (wdsp/nobII.c:157-495) for `nch` fp64 complex streams at the receiver's input rate, in front of fexchange0 like ANB.  Every
+ * channel has its own settings and state.  While a channel runs, its output lags its input by qh_nob_delay() = adv_slew + adv + 1 +
+ * max_imp_seq + hang + hang_slew + 10 samples (flush_nob, nobII.c:143-145; the counts are (int)(time * samplerate), nobII.c:40-44, with
+ * max_imp_seq_time 0.025 s and both slew times `slewtime`, as create_nobEXT fixes them); with run = 0 samples pass undelayed and every
+ * piece of state stands still (nobII.c:492-493).  mode: 0 zeros, 1 hold the 10-tap sum of the clean samples before the blank, 2 the mean
+ * of that and the sum of the clean samples after it, 3 the sum after it, 4 a line between the two (nobII.c:288-320).  The detector's
+ * average is stepped in time tiles whose start values come from a scan (qh_nob.hip): an impulse flag can differ from a sample-serial run
+ * only where |x| lies within eps / (1 - backmult) of avg * threshold; given the flags the output is the reference's bit for bit, the
+ * mode-4 line (repeated addition) included, and so are the reference's reads ahead of its write position, which find what the ring held
+ * dline_size = 50690 samples earlier (nobII.c:94-98, 225-235, 264-276).
+ * Refused with QH_ERR_INVALID, nothing changed: a rate outside (0, 1536000] or below 40 (max_imp_seq would be 0 and a blank would never
+ * end); slewtime, hangtime or advtime outside [0, 0.002] (the reference sizes awave[], hwave[] and the ring for these and never checks,
+ * nobII.c:29-34, 94-102); any setting whose delay reaches dline_size (1.536 MHz with every time at 0.002: flush_nob would start the write
+ * position beyond the ring, nobII.c:145, 177); a backtau that is not finite and positive; a threshold that is not finite; a mode outside
+ * 0..4.  Two departures besides: the gather of the ten clean samples after a blank (nobII.c:262-278) stops after one turn of the ring
+ * and takes zeros for the taps it has not found, where the reference's loop does not return (fewer than ten unflagged slots in the ring:
+ * a threshold below 1 on a steady signal); and the ten clean samples before a blank come from the last 50752 samples, zeros beyond,
+ * where bfbuff could still hold older ones.  Setters: ch = -1 means every channel; they take effect at the next process call.  Every
+ * call of a running channel copies that channel's history (50752 samples and their flags, 0.8 MB read and as much written), however
+ * small n is. */
+typedef struct qh_nob qh_nob;
+qh_nob *qh_nob_create(int device, int nch, double samplerate, int mode, double slewtime, double hangtime, double advtime, double backtau,
+                      double threshold, void *stream);                           /* create_nob + init_nob, nobII.c:36-124; run = 1 */
+void qh_nob_destroy(qh_nob *b);                                                  /* nobII.c:126-138 */
+int qh_nob_delay(qh_nob *b, int ch);                                             /* in_idx - out_idx, nobII.c:143-145 */
+int qh_nob_set_run(qh_nob *b, int ch, int run);                                  /* nobII.c:649-656: resets nothing */
+int qh_nob_set_mode(qh_nob *b, int ch, int mode);                                /* nobII.c:658-665: resets nothing; shows at the next impulse set-up */
+int qh_nob_set_samplerate(qh_nob *b, int ch, double samplerate);                 /* nobII.c:676-684: init_nob, a full restart that zeroes the ring */
+int qh_nob_set_tau(qh_nob *b, int ch, double tau);                               /* nobII.c:686-695: both slew times; restart */
+int qh_nob_set_hangtime(qh_nob *b, int ch, double hangtime);                     /* nobII.c:697-705: restart */
+int qh_nob_set_advtime(qh_nob *b, int ch, double advtime);                       /* nobII.c:707-715: restart */
+int qh_nob_set_backtau(qh_nob *b, int ch, double backtau);                       /* nobII.c:717-725: restart */
+int qh_nob_set_threshold(qh_nob *b, int ch, double threshold);                   /* nobII.c:727-734: resets nothing */
+int qh_nob_flush(qh_nob *b, int ch);                                             /* flush_nob, nobII.c:140-155 */
+/* xnob (nobII.c:157-495) over n >= 0 samples of every channel: device rows [nch][stride] of interleaved complex doubles, strides in
+ * complex samples, asynchronous on the bank's stream.  Output rows that share a byte with the input rows are refused (QH_ERR_INVALID,
+ * state untouched); the _host form (synchronous, pageable memory) takes h_out == h_in. */
+int qh_nob_process(qh_nob *b, const void *d_in, long long in_stride, void *d_out, long long out_stride, int n);
+int qh_nob_process_host(qh_nob *b, const void *h_in, long long in_stride, void *h_out, long long out_stride, int n);
+int qh_nob_synchronize(qh_nob *b);
 /* dAutoNotch (quisk.c:786-963; 8(f) rank 3) inside the receiver bank, where the mode calls it (on the real audio after
  * the Rx filter; after the interpolators for FM; DGT-IQ has none): set_auto_notch(i) (quisk.c:4596) -- stores the flag
  * and starts the notch over -- with rit_freq as set_sidetone passes it (quisk.c:4712): the CW modes keep the notch off

@@ -60,4 +60,7 @@ static inline bool rows_overlap(const void *a, long long a_stride_bytes, long lo
     return false;
 }
 
+// QH_OK, or QH_ERR_INVALID with the message set, for the settings qh_nob_create refuses (qh_nob.hip)
+int nob_check_settings(double samplerate, int mode, double slewtime, double hangtime, double advtime, double backtau, double threshold);
+
 }  // namespace qh

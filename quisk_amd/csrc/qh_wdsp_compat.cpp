@@ -1124,3 +1124,148 @@ void SetEXTANBBacktau(int id, double tau) { ANB_SETTER(qh_anb_set_backtau(L.a->b
 void SetEXTANBThreshold(int id, double thresh) { ANB_SETTER(qh_anb_set_threshold(L.a->b, 0, thresh)); }
 
 }  // extern "C"
+
+// ---- the second blanker ("NB2"): create_nobEXT ... SetEXTNOBThreshold (wdsp/nobII.c:605-734) ----------------------------------
+// pnob[id], nobII.c:605-606: each id a one-channel qh_nob bank on a stream of its own, with staging rows that let in == out
+namespace {
+constexpr int kMaxExtNobs = 32;     // MAX_EXT_NOBS, nobII.c:605
+struct ExtNob {
+    qh_nob *b = nullptr;
+    int buffsize = 0, cap = 0;
+    hipStream_t stream = nullptr;
+    double *d_in = nullptr, *d_out = nullptr;
+    hipEvent_t ev_in = nullptr, ev_out = nullptr;
+};
+ExtNob g_nob[kMaxExtNobs];
+std::recursive_mutex g_nob_mtx[kMaxExtNobs];
+
+void nob_release(ExtNob &a)
+{
+    if (a.b) qh_nob_destroy(a.b);               // (waits for the stream)
+    (void)hipFree(a.d_in); (void)hipFree(a.d_out);
+    if (a.ev_in) (void)hipEventDestroy(a.ev_in);
+    if (a.ev_out) (void)hipEventDestroy(a.ev_out);
+    if (a.stream) (void)hipStreamDestroy(a.stream);
+    a = ExtNob();
+}
+
+struct LockedNob {
+    ExtNob *a = nullptr;
+    std::unique_lock<std::recursive_mutex> lk;
+    explicit LockedNob(int id)
+    {
+        g_status = QH_OK;
+        if (id < 0 || id >= kMaxExtNobs) { g_status = qh::set_error(QH_ERR_INVALID, "NOB id %d out of range", id); return; }
+        lk = std::unique_lock<std::recursive_mutex>(g_nob_mtx[id]);
+        if (!g_nob[id].b) { g_status = qh::set_error(QH_ERR_INVALID, "NOB id %d has not been created", id); return; }
+        a = &g_nob[id];
+    }
+};
+
+int nob_staging(ExtNob &a)
+{
+    if (a.buffsize <= a.cap) return QH_OK;
+    if (hipStreamSynchronize(a.stream) != hipSuccess) return qh::set_error(QH_ERR_HIP, "xnobEXT: synchronize failed");
+    (void)hipFree(a.d_in); (void)hipFree(a.d_out);
+    a.d_in = nullptr; a.d_out = nullptr; a.cap = 0;
+    if (hipMalloc((void **)&a.d_in, (size_t)a.buffsize * 16) != hipSuccess || hipMalloc((void **)&a.d_out, (size_t)a.buffsize * 16) != hipSuccess)
+        return qh::set_error(QH_ERR_HIP, "xnobEXT: staging allocation failed");
+    a.cap = a.buffsize;
+    return QH_OK;
+}
+}  // namespace
+
+extern "C" {
+
+void create_nobEXT(int id, int run, int mode, int buffsize, double samplerate, double slewtime, double hangtime, double advtime, double backtau,
+                   double threshold)
+{
+    g_status = QH_OK;
+    if (id < 0 || id >= kMaxExtNobs) { g_status = qh::set_error(QH_ERR_INVALID, "NOB id %d out of range", id); return; }
+    std::unique_lock<std::recursive_mutex> lk(g_nob_mtx[id]);
+    ExtNob &a = g_nob[id];
+    if (a.b) { g_status = qh::set_error(QH_ERR_INVALID, "NOB id %d already exists", id); return; }
+    if (buffsize <= 0) { g_status = qh::set_error(QH_ERR_INVALID, "create_nobEXT: bad buffer size"); return; }
+    if (int rc = qh::nob_check_settings(samplerate, mode, slewtime, hangtime, advtime, backtau, threshold)) { g_status = rc; return; }
+    if (hipStreamCreateWithFlags(&a.stream, hipStreamNonBlocking) != hipSuccess) {
+        a.stream = nullptr;
+        g_status = qh::set_error(QH_ERR_NO_DEVICE, "create_nobEXT: no HIP device (libquiskhip has no CPU fallback)");
+        return;
+    }
+    a.b = qh_nob_create(0, 1, samplerate, mode, slewtime, hangtime, advtime, backtau, threshold, a.stream);
+    if (!a.b) { g_status = QH_ERR_HIP; nob_release(a); return; }           // the settings were good: the device (message already set)
+    a.buffsize = buffsize;
+    int rc = qh_nob_set_run(a.b, 0, run);
+    if (!rc) rc = nob_staging(a);
+    if (rc) { g_status = rc; nob_release(a); }
+}
+
+void destroy_nobEXT(int id)
+{
+    LockedNob L(id);
+    if (L.a) nob_release(*L.a);
+}
+
+void flush_nobEXT(int id)
+{
+    LockedNob L(id);
+    if (L.a) g_status = qh_nob_flush(L.a->b, 0);
+}
+
+void xnobEXT(int id, double *in, double *out)
+{
+    LockedNob L(id);
+    if (!L.a) return;
+    ExtNob &a = *L.a;
+    if (!in || !out) { g_status = qh::set_error(QH_ERR_INVALID, "xnobEXT: null buffer"); return; }
+    if (int rc = nob_staging(a)) { g_status = rc; return; }
+    const size_t bytes = (size_t)a.buffsize * 16;
+    if (hipMemcpyAsync(a.d_in, in, bytes, hipMemcpyHostToDevice, a.stream) != hipSuccess) { g_status = qh::set_error(QH_ERR_HIP, "xnobEXT: upload failed"); return; }
+    if (int rc = qh_nob_process(a.b, a.d_in, a.buffsize, a.d_out, a.buffsize, a.buffsize)) { g_status = rc; return; }
+    if (hipMemcpyAsync(out, a.d_out, bytes, hipMemcpyDeviceToHost, a.stream) != hipSuccess || hipStreamSynchronize(a.stream) != hipSuccess)
+        g_status = qh::set_error(QH_ERR_HIP, "xnobEXT: download failed");
+}
+
+int qh_wdsp_xnobEXT_device(int id, const void *d_in, void *d_out, void *stream)
+{
+    LockedNob L(id);
+    if (!L.a) return g_status;
+    ExtNob &a = *L.a;
+    if (!d_in || !d_out) return g_status = qh::set_error(QH_ERR_INVALID, "qh_wdsp_xnobEXT_device: null buffer");
+    if (int rc = nob_staging(a)) return g_status = rc;
+    hipStream_t cs = (hipStream_t)stream;
+    if (!a.ev_in && (hipEventCreateWithFlags(&a.ev_in, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&a.ev_out, hipEventDisableTiming) != hipSuccess))
+        return g_status = qh::set_error(QH_ERR_HIP, "qh_wdsp_xnobEXT_device: event creation failed");
+    const size_t bytes = (size_t)a.buffsize * 16;
+    if (cs != a.stream) { (void)hipEventRecord(a.ev_in, cs); (void)hipStreamWaitEvent(a.stream, a.ev_in, 0); }
+    int rc = QH_OK;
+    if (hipMemcpyAsync(a.d_in, d_in, bytes, hipMemcpyDeviceToDevice, a.stream) != hipSuccess) rc = qh::set_error(QH_ERR_HIP, "qh_wdsp_xnobEXT_device: copy failed");
+    if (!rc) rc = qh_nob_process(a.b, a.d_in, a.buffsize, a.d_out, a.buffsize, a.buffsize);
+    if (!rc && hipMemcpyAsync(d_out, a.d_out, bytes, hipMemcpyDeviceToDevice, a.stream) != hipSuccess) rc = qh::set_error(QH_ERR_HIP, "qh_wdsp_xnobEXT_device: copy failed");
+    if (cs != a.stream) { (void)hipEventRecord(a.ev_out, a.stream); (void)hipStreamWaitEvent(cs, a.ev_out, 0); }
+    return g_status = rc;
+}
+
+#define NOB_SETTER(call)                    \
+    do {                                    \
+        LockedNob L(id);                    \
+        if (L.a) g_status = (call);         \
+    } while (0)
+
+void SetEXTNOBRun(int id, int run) { NOB_SETTER(qh_nob_set_run(L.a->b, 0, run)); }
+void SetEXTNOBMode(int id, int mode) { NOB_SETTER(qh_nob_set_mode(L.a->b, 0, mode)); }
+void SetEXTNOBBuffsize(int id, int size)
+{
+    LockedNob L(id);
+    if (!L.a) return;
+    if (size <= 0) { g_status = qh::set_error(QH_ERR_INVALID, "SetEXTNOBBuffsize: bad buffer size"); return; }
+    L.a->buffsize = size;
+}
+void SetEXTNOBSamplerate(int id, int rate) { NOB_SETTER(qh_nob_set_samplerate(L.a->b, 0, (double)rate)); }
+void SetEXTNOBTau(int id, double tau) { NOB_SETTER(qh_nob_set_tau(L.a->b, 0, tau)); }
+void SetEXTNOBHangtime(int id, double time) { NOB_SETTER(qh_nob_set_hangtime(L.a->b, 0, time)); }
+void SetEXTNOBAdvtime(int id, double time) { NOB_SETTER(qh_nob_set_advtime(L.a->b, 0, time)); }
+void SetEXTNOBBacktau(int id, double tau) { NOB_SETTER(qh_nob_set_backtau(L.a->b, 0, tau)); }
+void SetEXTNOBThreshold(int id, double thresh) { NOB_SETTER(qh_nob_set_threshold(L.a->b, 0, thresh)); }
+
+}  // extern "C"

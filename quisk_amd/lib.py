@@ -272,6 +272,30 @@ def load():
                  ("SetEXTANBBacktau", [i, d]), ("SetEXTANBThreshold", [i, d])):
         getattr(L, n).argtypes = a
         getattr(L, n).restype = None
+    # WDSP's second noise blanker (wdsp/nobII.c): the bank and the EXT names
+    L.qh_nob_create.restype = vp
+    L.qh_nob_create.argtypes = [i, i, d, i, d, d, d, d, d, vp]
+    L.qh_nob_destroy.argtypes = [vp]
+    L.qh_nob_destroy.restype = None
+    L.qh_nob_delay.argtypes = [vp, i]
+    L.qh_nob_set_run.argtypes = [vp, i, i]
+    L.qh_nob_set_mode.argtypes = [vp, i, i]
+    for n in ("samplerate", "tau", "hangtime", "advtime", "backtau", "threshold"):
+        getattr(L, "qh_nob_set_" + n).argtypes = [vp, i, d]
+    L.qh_nob_flush.argtypes = [vp, i]
+    L.qh_nob_process.argtypes = [vp, vp, ll, vp, ll, i]
+    L.qh_nob_process_host.argtypes = [vp, vp, ll, vp, ll, i]
+    L.qh_nob_synchronize.argtypes = [vp]
+    L.create_nobEXT.argtypes = [i, i, i, i, d, d, d, d, d, d]
+    L.create_nobEXT.restype = None
+    L.xnobEXT.argtypes = [i, vp, vp]
+    L.xnobEXT.restype = None
+    L.qh_wdsp_xnobEXT_device.argtypes = [i, vp, vp, vp]
+    for n, a in (("destroy_nobEXT", [i]), ("flush_nobEXT", [i]), ("SetEXTNOBRun", [i, i]), ("SetEXTNOBMode", [i, i]), ("SetEXTNOBBuffsize", [i, i]),
+                 ("SetEXTNOBSamplerate", [i, i]), ("SetEXTNOBTau", [i, d]), ("SetEXTNOBHangtime", [i, d]), ("SetEXTNOBAdvtime", [i, d]),
+                 ("SetEXTNOBBacktau", [i, d]), ("SetEXTNOBThreshold", [i, d])):
+        getattr(L, n).argtypes = a
+        getattr(L, n).restype = None
     L.qh_qrx_set_noise_blanker.argtypes = [vp, i]
     L.qh_qrx_set_auto_notch.argtypes = [vp, i, i]
     L.qh_quisk_set_auto_notch.argtypes = [i, i]
