@@ -4,11 +4,8 @@
 // The reference steps, per sample: mag = |x|; avg = backmult avg + (1 - backmult) mag; a trigger (mag > avg threshold) loads `count`
 // with T = trans_count + adv_count; a five-state machine looks at count (pass / cosine fall / dead time / hang / cosine rise) and
 // scales the sample T behind the newest one; count drops by one.  So the machine sees count > 0 at sample i exactly when a trigger
-// lies in (i - T, i], and the call is cut as qh_ssql.hpp cuts the syllabic squelch:
-//   det 0    time tiles of kAnbL samples, one per lane: avg stepped from 0, each tile's end value               (one read of the rows)
-//   carry    a <- backmult^L a + e_j over the tiles (an affine scan, 64 tiles a step): every tile's true start value
-//   det 1    avg from the true start, the reference's two multiplies and one add in its order, uncontracted; the trigger bits,
-//            64 samples a word                                                                                   (one read of the rows)
+// lies in (i - T, i], and the call is cut into passes:
+//   det 0 / carry / det 1    the detector of qh_blank_det.hpp: the trigger bits, 64 samples a word              (two reads of the rows)
 //   walk     one wavefront per channel, 64 words at a time: the trigger bits dilated by T (the "count > 0" bits, kept for the apply
 //            pass), then the machine from event to event -- the next set / clear bit by __ballot and a bit scan, a ramp, the dead
 //            time and a quiet hang skipped whole.  It leaves (state, timer, power, htime) at every word's first sample and the
@@ -17,25 +14,19 @@
 //            segment (event by event, uniform over the wavefront); the sample i - T comes from the call's rows or from the history
 //            of the last kAnbHist input samples; copy, zeros or the reference's product                 (one read, one write)
 //   hist     the last kAnbHist input samples of every running channel to the other history buffer
-// avg inside a tile is the reference's recurrence; only its start value carries the rounding of the scan, eps / (1 - backmult)
-// relative at worst, so a trigger bit can differ from a sample-serial run only where mag sits that close to avg threshold.  Given the
-// bits, the output is the reference's bit for bit: wave[], backmult and the counts are computed on the host with the C library the
-// reference calls, and the two products of a scaled sample are the reference's.
+// Given the trigger bits (see the header for where they can differ from a sample-serial run), the output is the reference's bit for
+// bit: wave[], backmult and the counts are computed on the host with the C library the reference calls, and the two products of a
+// scaled sample are the reference's.
 #include <algorithm>
 #include <climits>
 #include <cmath>
-#include <mutex>
 #include <vector>
-#include "qh_internal.hpp"
+#include "qh_blank_det.hpp"
 
 using namespace qh;
 
 namespace {
 
-typedef unsigned long long u64;
-
-constexpr int kAnbL = 128;                              // samples per lane tile (two words of bits)
-constexpr int kAnbB = 8, kAnbPitch = kAnbB + 1;         // samples per tile and trip through LDS; padded against bank conflicts
 constexpr double kAnbMaxTau = 0.002, kAnbMaxAdv = 0.002, kAnbMaxRate = 1536000.0;      // nob.c:29-31
 constexpr int kAnbMaxTrans = 3072;                      // (int)(MAX_SAMPLERATE * MAX_TAU), nob.c:80
 constexpr int kAnbWave = kAnbMaxTrans + 1;              // doubles of wave[] per channel
@@ -43,16 +34,18 @@ constexpr int kAnbHist = 2 * kAnbMaxTrans;              // the longest delay, no
 
 struct AnbParam {
     double backmult, ombackmult, threshold;
-    double carry;                       // backmult^kAnbL
+    double carry;                       // backmult^kDetL
     int tc, adv, hang, T;               // trans_count, adv_count, hang_count, tc + adv
     int run, pad;
 };
+static_assert(sizeof(AnbParam) == 56, "the layout the kernels and the upload share");
 
 // what xanb keeps from call to call, but for the delay line (hist).  timer: dtime, atime or itime, whichever the state counts
 struct AnbState {
     double avg, power;
     int state, timer, htime, count;
 };
+static_assert(sizeof(AnbState) == 32, "the layout the kernels share");
 
 struct AnbRec {                         // the machine at a word's first sample: st = state | timer << 3
     double power;
@@ -75,101 +68,6 @@ __device__ __forceinline__ int anb_first(u64 bits, int from)
 {
     const u64 m = from >= 64 ? 0ull : bits & (~0ull << from);
     return m ? __ffsll((long long)m) - 1 : 64;
-}
-
-// every set bit smeared over the T - 1 bits above it (inside the word)
-__device__ __forceinline__ u64 anb_dilate(u64 x, int T)
-{
-    if (!x) return 0ull;
-    if (T >= 64) return ~0ull << (__ffsll((long long)x) - 1);
-    u64 r = x;
-    for (int have = 1; have < T;) {
-        const int sh = have < T - have ? have : T - have;
-        r |= r << sh;
-        have += sh;
-    }
-    return r;
-}
-
-// det 0 / det 1.  One wavefront = 64 consecutive tiles of one channel; lane l owns samples [q L, min((q + 1) L, n)), q = 64 blockIdx.x
-// + l.  The samples travel HBM -> |x| -> LDS in runs of kAnbB per tile (128 contiguous bytes per eight lanes), each lane then steps
-// its own row.  ends: [ch][estride], one double per tile.  trb: [ch][wstride] words of trigger bits, bits at and beyond n clear.
-template <int PASS>
-__global__ __launch_bounds__(64) void anb_det_kernel(const double2 *in, long long stride, int n, const AnbParam *prm, AnbState *state,
-                                                     double *ends, long long estride, u64 *trb, long long wstride)
-{
-#pragma clang fp contract(off)
-    constexpr int L = kAnbL, B = kAnbB, RPI = 64 / B;
-    __shared__ double lds[64 * kAnbPitch];
-    const int ch = blockIdx.y, lane = threadIdx.x;
-    if (!prm[ch].run) return;
-    const long long t0 = (long long)blockIdx.x * 64, first = t0 * L;
-    const long long ntile = ((long long)n + L - 1) / L, q = t0 + lane;
-    if (first >= n || (PASS == 0 && t0 >= ntile - 1)) return;
-    const bool live = PASS == 0 ? q < ntile - 1 : q < ntile;
-    const double bm = prm[ch].backmult, om = prm[ch].ombackmult, th = prm[ch].threshold;
-    double *erow = ends + (long long)ch * estride;
-    double avg = PASS == 1 && live ? erow[q] : 0.0;
-    const int tn = live ? (int)((long long)n - q * L < L ? (long long)n - q * L : (long long)L) : 0;
-    const double2 *b = in + (long long)ch * stride + first;
-    const long long nrem = (long long)n - first;
-    u64 *wout = trb + (long long)ch * wstride + q * (L / 64), word = 0;
-    const int frow = lane / B, fcol = lane % B;
-    for (int i0 = 0; i0 < L; i0 += B) {
-#pragma unroll
-        for (int j = 0; j < B; j++) {
-            const int row = RPI * j + frow;
-            const long long off = (long long)row * L + i0 + fcol;
-            double m = 0.0;
-            if (off < nrem) {
-                const double2 z = b[off];
-                m = __builtin_sqrt(z.x * z.x + z.y * z.y);                  // nob.c:118
-            }
-            lds[row * kAnbPitch + fcol] = m;
-        }
-        __syncthreads();
-        if (i0 < tn) {
-#pragma unroll
-            for (int k = 0; k < B; k++) {
-                if (i0 + k < tn) {
-                    const double mag = lds[lane * kAnbPitch + k];
-                    avg = bm * avg + om * mag;                              // nob.c:119
-                    if (PASS == 1 && mag > avg * th) word |= 1ull << ((i0 + k) & 63);      // nob.c:122
-                }
-            }
-        }
-        if (PASS == 1 && ((i0 + B) & 63) == 0) {
-            if (i0 + B - 64 < tn) wout[(i0 + B - 64) >> 6] = word;
-            word = 0;
-        }
-        __syncthreads();
-    }
-    if (PASS == 0 && live) erow[q] = avg;
-    if (PASS == 1 && live && q == ntile - 1) state[ch].avg = avg;
-}
-
-// The carry, one wavefront per channel: 64 tiles a step, the maps a -> M a + e_j composed by a scan over the lanes.  Row j holds e_j
-// (tiles before the last) and receives tile j's start value.
-__global__ __launch_bounds__(64) void anb_carry_kernel(int n, const AnbParam *prm, const AnbState *state, double *ends, long long estride)
-{
-    const int ch = blockIdx.x, lane = threadIdx.x;
-    if (!prm[ch].run) return;
-    const long long ntile = ((long long)n + kAnbL - 1) / kAnbL;
-    const double M = prm[ch].carry;
-    double s = state[ch].avg;
-    double *rows = ends + (long long)ch * estride;
-    for (long long j0 = 0; j0 < ntile; j0 += 64) {
-        const long long j = j0 + lane;
-        double A = M, E = j < ntile - 1 ? rows[j] : 0.0;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const double Au = __shfl_up(A, d, 64), Eu = __shfl_up(E, d, 64);
-            if (lane >= d) { E = fma(A, Eu, E); A *= Au; }
-        }
-        const double Ax = __shfl_up(A, 1, 64), Ex = __shfl_up(E, 1, 64);
-        if (j < ntile) rows[j] = lane ? fma(Ax, s, Ex) : s;
-        s = fma(__shfl(A, 63, 64), s, __shfl(E, 63, 64));
-    }
 }
 
 // The event walk, one wavefront per channel, 64 words (4096 samples) at a time; lane l holds word l.  cb: the "count > 0" bits.
@@ -201,7 +99,7 @@ __global__ __launch_bounds__(64) void anb_walk_kernel(int n, const AnbParam *prm
         }
         const long long ex = __shfl_up(inc, 1, 64);
         const long long ltb = lane && ex > lt ? ex : lt;
-        u64 cbw = anb_dilate(tw, T);
+        u64 cbw = dilate(tw, T);
         const long long left = (long long)T - (ws - ltb);                   // samples of the word a trigger before it still covers
         if (left > 0) cbw |= left >= 64 ? ~0ull : (1ull << left) - 1ull;
         cbw &= anb_range(ws, cs, ce);
@@ -377,125 +275,99 @@ const char *anb_refusal(const AnbSettings &s)
 
 }  // namespace
 
-struct qh_anb {
-    int device = 0, nch = 0;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
-    std::mutex mtx;                                     // setters may come from another thread than process (cs_update, nob.c:83)
+int qh::anb_check_settings(double samplerate, double tau, double hangtime, double advtime, double backtau, double threshold)
+{
+    const char *why = anb_refusal(AnbSettings{samplerate, tau, hangtime, advtime, backtau, threshold, 1});
+    return why ? set_error(QH_ERR_INVALID, "qh_anb_create: %s", why) : QH_OK;       // (the text create_anbEXT has always reported)
+}
+
+struct qh_anb : Bank {
     std::vector<AnbSettings> set;
     std::vector<AnbParam> prm;
     std::vector<double> wave;                           // [nch][kAnbWave]
     std::vector<char> wave_dirty;
-    bool dirty = true;
     AnbParam *d_prm = nullptr;
     AnbState *d_state = nullptr;
     double *d_wave = nullptr;
     double2 *hist[2] = { nullptr, nullptr };
-    int cur = 0;
-    // per-call scratch, grown with n
-    int cap = 0;
-    double *d_ends = nullptr;
-    u64 *d_trb = nullptr, *d_cb = nullptr;
+    // per-call scratch beside the detector's, grown with it
+    u64 *d_cb = nullptr;
     AnbRec *d_rec = nullptr;
-    void free_scratch()
+    void free_walk()
     {
-        (void)hipFree(d_ends); (void)hipFree(d_trb); (void)hipFree(d_cb); (void)hipFree(d_rec);
-        d_ends = nullptr; d_trb = nullptr; d_cb = nullptr; d_rec = nullptr; cap = 0;
+        (void)hipFree(d_cb); (void)hipFree(d_rec);
+        d_cb = nullptr; d_rec = nullptr;
     }
     ~qh_anb()
     {
-        (void)hipSetDevice(device);
-        if (stream) (void)hipStreamSynchronize(stream);
-        free_scratch();
+        quiesce();
+        free_walk();
         (void)hipFree(d_prm); (void)hipFree(d_state); (void)hipFree(d_wave); (void)hipFree(hist[0]); (void)hipFree(hist[1]);
-        if (own_stream && stream) (void)hipStreamDestroy(stream);
+    }
+
+    static const char *refusal(const AnbSettings &s) { return anb_refusal(s); }
+
+    // initBlanker's numbers (nob.c:36-50), with the C library's exp and cos
+    void derive(int ch)
+    {
+        const AnbSettings &s = set[ch];
+        AnbParam &p = prm[ch];
+        p.tc = (int)(s.tau * s.samplerate);
+        if (p.tc < 2) p.tc = 2;
+        p.hang = (int)(s.hangtime * s.samplerate);
+        p.adv = (int)(s.advtime * s.samplerate);
+        p.T = p.tc + p.adv;
+        const double coef = 3.1415926535897932 / p.tc;      // PI, comm.h
+        p.backmult = std::exp(-1.0 / (s.samplerate * s.backtau));
+        p.ombackmult = 1.0 - p.backmult;
+        p.carry = std::pow(p.backmult, (double)kDetL);
+        p.threshold = s.threshold;
+        p.run = s.run;
+        p.pad = 0;
+        double *w = wave.data() + (size_t)ch * kAnbWave;
+        for (int i = 0; i <= p.tc; i++) w[i] = 0.5 * std::cos(i * coef);
+        wave_dirty[ch] = 1;
+        dirty = true;
+    }
+
+    void apply_light(int ch) { prm[ch].threshold = set[ch].threshold; prm[ch].run = set[ch].run; }
+
+    int restart(int ch0, int count)
+    {
+        hipLaunchKernelGGL(anb_reset_kernel, dim3((kAnbHist + 255) / 256, (unsigned)count), dim3(256), 0, stream, d_state, hist[cur], ch0);
+        QH_HIP(hipGetLastError());
+        return QH_OK;
+    }
+
+    // host settings -> device, behind everything enqueued so far (the copies are synchronous: the vectors may change right after)
+    int upload()
+    {
+        if (!dirty) return QH_OK;
+        QH_HIP(hipStreamSynchronize(stream));
+        QH_HIP(hipMemcpy(d_prm, prm.data(), (size_t)nch * sizeof(AnbParam), hipMemcpyHostToDevice));
+        for (int ch = 0; ch < nch; ch++) {
+            if (!wave_dirty[ch]) continue;
+            QH_HIP(hipMemcpy(d_wave + (size_t)ch * kAnbWave, wave.data() + (size_t)ch * kAnbWave, (size_t)(prm[ch].tc + 1) * sizeof(double),
+                             hipMemcpyHostToDevice));
+            wave_dirty[ch] = 0;
+        }
+        dirty = false;
+        return QH_OK;
+    }
+
+    int scratch(int n)
+    {
+        if (n <= cap) return QH_OK;
+        if (int rc = bank_grow(this, n, kDetL, "qh_anb_process")) return rc;
+        free_walk();
+        if (dev_alloc(&d_cb, (size_t)nch * (size_t)nw) != hipSuccess || dev_alloc(&d_rec, (size_t)nch * (size_t)nw) != hipSuccess) {
+            free_walk();
+            free_scratch();
+            return set_error(QH_ERR_HIP, "qh_anb_process: scratch allocation failed");
+        }
+        return QH_OK;
     }
 };
-
-namespace {
-
-// initBlanker's numbers (nob.c:36-50), with the C library's exp and cos
-void anb_derive(qh_anb *h, int ch)
-{
-    const AnbSettings &s = h->set[ch];
-    AnbParam &p = h->prm[ch];
-    p.tc = (int)(s.tau * s.samplerate);
-    if (p.tc < 2) p.tc = 2;
-    p.hang = (int)(s.hangtime * s.samplerate);
-    p.adv = (int)(s.advtime * s.samplerate);
-    p.T = p.tc + p.adv;
-    const double coef = 3.1415926535897932 / p.tc;      // PI, comm.h
-    p.backmult = std::exp(-1.0 / (s.samplerate * s.backtau));
-    p.ombackmult = 1.0 - p.backmult;
-    p.carry = std::pow(p.backmult, (double)kAnbL);
-    p.threshold = s.threshold;
-    p.run = s.run;
-    p.pad = 0;
-    double *w = h->wave.data() + (size_t)ch * kAnbWave;
-    for (int i = 0; i <= p.tc; i++) w[i] = 0.5 * std::cos(i * coef);
-    h->wave_dirty[ch] = 1;
-    h->dirty = true;
-}
-
-// host settings -> device, behind everything enqueued so far (the copies are synchronous: the vectors may change right after)
-int anb_upload(qh_anb *h)
-{
-    if (!h->dirty) return QH_OK;
-    QH_HIP(hipStreamSynchronize(h->stream));
-    QH_HIP(hipMemcpy(h->d_prm, h->prm.data(), (size_t)h->nch * sizeof(AnbParam), hipMemcpyHostToDevice));
-    for (int ch = 0; ch < h->nch; ch++) {
-        if (!h->wave_dirty[ch]) continue;
-        QH_HIP(hipMemcpy(h->d_wave + (size_t)ch * kAnbWave, h->wave.data() + (size_t)ch * kAnbWave, (size_t)(h->prm[ch].tc + 1) * sizeof(double),
-                         hipMemcpyHostToDevice));
-        h->wave_dirty[ch] = 0;
-    }
-    h->dirty = false;
-    return QH_OK;
-}
-
-int anb_restart(qh_anb *h, int ch0, int count)
-{
-    hipLaunchKernelGGL(anb_reset_kernel, dim3((kAnbHist + 255) / 256, (unsigned)count), dim3(256), 0, h->stream, h->d_state, h->hist[h->cur], ch0);
-    QH_HIP(hipGetLastError());
-    return QH_OK;
-}
-
-// One setter: `edit` changes a copy of the settings of channel ch (-1: every channel); a refusal leaves everything as it was.
-template <typename F> int anb_set(qh_anb *h, int ch, const char *name, bool restart, F edit)
-{
-    if (!h || ch < -1 || ch >= h->nch) return set_error(QH_ERR_INVALID, "%s: bad arguments", name);
-    std::lock_guard<std::mutex> lk(h->mtx);
-    const int c0 = ch < 0 ? 0 : ch, c1 = ch < 0 ? h->nch : ch + 1;
-    std::vector<AnbSettings> next(h->set.begin() + c0, h->set.begin() + c1);
-    for (AnbSettings &s : next) {
-        edit(s);
-        if (const char *why = anb_refusal(s)) return set_error(QH_ERR_INVALID, "%s: %s", name, why);
-    }
-    QH_HIP(hipSetDevice(h->device));
-    for (int c = c0; c < c1; c++) {
-        h->set[c] = next[c - c0];
-        if (restart) anb_derive(h, c);
-        else { h->prm[c].threshold = h->set[c].threshold; h->prm[c].run = h->set[c].run; h->dirty = true; }
-    }
-    return restart ? anb_restart(h, c0, c1 - c0) : QH_OK;
-}
-
-int anb_scratch(qh_anb *h, int n)
-{
-    if (n <= h->cap) return QH_OK;
-    QH_HIP(hipStreamSynchronize(h->stream));
-    h->free_scratch();
-    const size_t nw = ((size_t)n + 63) / 64 + 1, nt = ((size_t)n + kAnbL - 1) / kAnbL + 1;
-    if (dev_alloc(&h->d_ends, (size_t)h->nch * nt) != hipSuccess || dev_alloc(&h->d_trb, (size_t)h->nch * nw) != hipSuccess ||
-        dev_alloc(&h->d_cb, (size_t)h->nch * nw) != hipSuccess || dev_alloc(&h->d_rec, (size_t)h->nch * nw) != hipSuccess) {
-        h->free_scratch();
-        return set_error(QH_ERR_HIP, "qh_anb_process: scratch allocation failed");
-    }
-    h->cap = n;
-    return QH_OK;
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -505,26 +377,15 @@ qh_anb *qh_anb_create(int device, int nch, double samplerate, double tau, double
     const AnbSettings s0{samplerate, tau, hangtime, advtime, backtau, threshold, 1};
     if (nch <= 0) { set_error(QH_ERR_INVALID, "qh_anb_create: bad arguments"); return nullptr; }
     if (const char *why = anb_refusal(s0)) { set_error(QH_ERR_INVALID, "qh_anb_create: %s", why); return nullptr; }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
-        set_error(QH_ERR_NO_DEVICE, "no HIP device %d (libquiskhip has no CPU fallback)", device);
-        return nullptr;
-    }
     qh_anb *h = new qh_anb();
-    h->device = device; h->nch = nch;
+    h->nch = nch;
     auto fail = [&](const char *what) -> qh_anb * { set_error(QH_ERR_HIP, "qh_anb_create: %s failed", what); delete h; return nullptr; };
-    if (hipSetDevice(device) != hipSuccess) return fail("hipSetDevice");
-    hipStream_t s = (hipStream_t)stream;
-    if (!s) {
-        if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) return fail("stream creation");
-        h->own_stream = true;
-    }
-    h->stream = s;
+    if (bank_open(h, device, stream, "qh_anb_create") != QH_OK) { delete h; return nullptr; }
     h->set.assign((size_t)nch, s0);
     h->prm.assign((size_t)nch, AnbParam{});
     h->wave.assign((size_t)nch * kAnbWave, 0.0);
     h->wave_dirty.assign((size_t)nch, 1);
-    anb_derive(h, 0);
+    h->derive(0);
     for (int ch = 1; ch < nch; ch++) {
         h->prm[ch] = h->prm[0];
         std::copy(h->wave.begin(), h->wave.begin() + kAnbWave, h->wave.begin() + (size_t)ch * kAnbWave);
@@ -538,7 +399,7 @@ qh_anb *qh_anb_create(int device, int nch, double samplerate, double tau, double
     if (dev_zero(h->d_state, (size_t)nch * sizeof(AnbState)) != hipSuccess || dev_zero(h->d_wave, (size_t)nch * kAnbWave * sizeof(double)) != hipSuccess ||
         dev_zero(h->hist[1], hb * sizeof(double2)) != hipSuccess)
         return fail("hipMemset");
-    if (anb_restart(h, 0, nch) != QH_OK) { delete h; return nullptr; }
+    if (h->restart(0, nch) != QH_OK) { delete h; return nullptr; }
     return h;
 }
 
@@ -551,40 +412,32 @@ int qh_anb_delay(qh_anb *h, int ch)
     return h->prm[ch].T;
 }
 
-int qh_anb_set_run(qh_anb *h, int ch, int run) { return anb_set(h, ch, "qh_anb_set_run", false, [=](AnbSettings &s) { s.run = run != 0; }); }
-int qh_anb_set_samplerate(qh_anb *h, int ch, double samplerate) { return anb_set(h, ch, "qh_anb_set_samplerate", true, [=](AnbSettings &s) { s.samplerate = samplerate; }); }
-int qh_anb_set_tau(qh_anb *h, int ch, double tau) { return anb_set(h, ch, "qh_anb_set_tau", true, [=](AnbSettings &s) { s.tau = tau; }); }
-int qh_anb_set_hangtime(qh_anb *h, int ch, double hangtime) { return anb_set(h, ch, "qh_anb_set_hangtime", true, [=](AnbSettings &s) { s.hangtime = hangtime; }); }
-int qh_anb_set_advtime(qh_anb *h, int ch, double advtime) { return anb_set(h, ch, "qh_anb_set_advtime", true, [=](AnbSettings &s) { s.advtime = advtime; }); }
-int qh_anb_set_backtau(qh_anb *h, int ch, double backtau) { return anb_set(h, ch, "qh_anb_set_backtau", true, [=](AnbSettings &s) { s.backtau = backtau; }); }
-int qh_anb_set_threshold(qh_anb *h, int ch, double threshold) { return anb_set(h, ch, "qh_anb_set_threshold", false, [=](AnbSettings &s) { s.threshold = threshold; }); }
-int qh_anb_flush(qh_anb *h, int ch) { return anb_set(h, ch, "qh_anb_flush", true, [](AnbSettings &) {}); }
+int qh_anb_set_run(qh_anb *h, int ch, int run) { return bank_set(h, ch, "qh_anb_set_run", false, [=](AnbSettings &s) { s.run = run != 0; }); }
+int qh_anb_set_samplerate(qh_anb *h, int ch, double samplerate) { return bank_set(h, ch, "qh_anb_set_samplerate", true, [=](AnbSettings &s) { s.samplerate = samplerate; }); }
+int qh_anb_set_tau(qh_anb *h, int ch, double tau) { return bank_set(h, ch, "qh_anb_set_tau", true, [=](AnbSettings &s) { s.tau = tau; }); }
+int qh_anb_set_hangtime(qh_anb *h, int ch, double hangtime) { return bank_set(h, ch, "qh_anb_set_hangtime", true, [=](AnbSettings &s) { s.hangtime = hangtime; }); }
+int qh_anb_set_advtime(qh_anb *h, int ch, double advtime) { return bank_set(h, ch, "qh_anb_set_advtime", true, [=](AnbSettings &s) { s.advtime = advtime; }); }
+int qh_anb_set_backtau(qh_anb *h, int ch, double backtau) { return bank_set(h, ch, "qh_anb_set_backtau", true, [=](AnbSettings &s) { s.backtau = backtau; }); }
+int qh_anb_set_threshold(qh_anb *h, int ch, double threshold) { return bank_set(h, ch, "qh_anb_set_threshold", false, [=](AnbSettings &s) { s.threshold = threshold; }); }
+int qh_anb_flush(qh_anb *h, int ch) { return bank_set(h, ch, "qh_anb_flush", true, [](AnbSettings &) {}); }
 
 int qh_anb_process(qh_anb *h, const void *d_in, long long in_stride, void *d_out, long long out_stride, int n)
 {
-    if (!h || n < 0 || (n > 0 && (!d_in || !d_out || in_stride < n || out_stride < n)))
-        return set_error(QH_ERR_INVALID, "qh_anb_process: bad arguments");
+    if (int rc = bank_check_rows("qh_anb_process", h, d_in, in_stride, d_out, out_stride, n, "an output is the input T samples back")) return rc;
     if (n == 0) return QH_OK;
-    if (rows_overlap(d_in, in_stride * 16, (long long)n * 16, d_out, out_stride * 16, (long long)n * 16, h->nch))
-        return set_error(QH_ERR_INVALID, "qh_anb_process: the output rows overlap the input rows (an output is the input T samples back)");
     std::lock_guard<std::mutex> lk(h->mtx);
     QH_HIP(hipSetDevice(h->device));
-    if (int rc = anb_upload(h)) return rc;
-    if (int rc = anb_scratch(h, n)) return rc;
+    if (int rc = h->upload()) return rc;
+    if (int rc = h->scratch(n)) return rc;
     const double2 *in = static_cast<const double2 *>(d_in);
     double2 *out = static_cast<double2 *>(d_out);
-    const long long nw = ((long long)h->cap + 63) / 64 + 1, nt = ((long long)h->cap + kAnbL - 1) / kAnbL + 1;
-    const unsigned ntile = (unsigned)((n + kAnbL - 1) / kAnbL), nch = (unsigned)h->nch;
+    const long long nw = h->nw;
+    const unsigned nch = (unsigned)h->nch;
     bool any = false;
     for (const AnbParam &p : h->prm) any = any || p.run;
     hipStream_t s = h->stream;
     if (any) {
-        if (ntile > 1)
-            hipLaunchKernelGGL((anb_det_kernel<0>), dim3((ntile + 63) / 64, nch), dim3(64), 0, s, in, in_stride, n, h->d_prm, h->d_state, h->d_ends, nt,
-                               h->d_trb, nw);
-        hipLaunchKernelGGL(anb_carry_kernel, dim3(nch), dim3(64), 0, s, n, h->d_prm, h->d_state, h->d_ends, nt);
-        hipLaunchKernelGGL((anb_det_kernel<1>), dim3((ntile + 63) / 64, nch), dim3(64), 0, s, in, in_stride, n, h->d_prm, h->d_state, h->d_ends, nt,
-                           h->d_trb, nw);
+        det_enqueue(*h, in, in_stride, n, h->d_prm, h->d_state);
         hipLaunchKernelGGL(anb_walk_kernel, dim3(nch), dim3(64), 0, s, n, h->d_prm, h->d_state, h->d_wave, h->d_trb, h->d_cb, h->d_rec, nw);
     }
     hipLaunchKernelGGL(anb_apply_kernel, dim3((unsigned)((n + 255) / 256), nch), dim3(256), 0, s, in, in_stride, out, out_stride, n, h->d_prm,
@@ -600,31 +453,9 @@ int qh_anb_process(qh_anb *h, const void *d_in, long long in_stride, void *d_out
 
 int qh_anb_process_host(qh_anb *h, const void *h_in, long long in_stride, void *h_out, long long out_stride, int n)
 {
-    if (!h || n < 0 || (n > 0 && (!h_in || !h_out || in_stride < n || out_stride < n)))
-        return set_error(QH_ERR_INVALID, "qh_anb_process_host: bad arguments");
-    if (n == 0) return QH_OK;
-    QH_HIP(hipSetDevice(h->device));
-    double2 *d = nullptr, *o = nullptr;
-    QH_HIP(hipMalloc((void **)&d, (size_t)h->nch * (size_t)n * sizeof(double2)));
-    if (hipMalloc((void **)&o, (size_t)h->nch * (size_t)n * sizeof(double2)) != hipSuccess) { (void)hipFree(d); return set_error(QH_ERR_HIP, "hipMalloc failed"); }
-    int rc = QH_OK;
-    if (hipMemcpy2DAsync(d, (size_t)n * 16, h_in, (size_t)in_stride * 16, (size_t)n * 16, (size_t)h->nch, hipMemcpyHostToDevice, h->stream) != hipSuccess)
-        rc = set_error(QH_ERR_HIP, "upload failed");
-    if (rc == QH_OK) rc = qh_anb_process(h, d, n, o, n, n);
-    if (rc == QH_OK && hipMemcpy2DAsync(h_out, (size_t)out_stride * 16, o, (size_t)n * 16, (size_t)n * 16, (size_t)h->nch, hipMemcpyDeviceToHost,
-                                         h->stream) != hipSuccess)
-        rc = set_error(QH_ERR_HIP, "download failed");
-    if (hipStreamSynchronize(h->stream) != hipSuccess && rc == QH_OK) rc = set_error(QH_ERR_HIP, "synchronize failed");
-    (void)hipFree(d); (void)hipFree(o);
-    return rc;
+    return bank_process_host(h, h_in, in_stride, h_out, out_stride, n, qh_anb_process, "qh_anb_process_host");
 }
 
-int qh_anb_synchronize(qh_anb *h)
-{
-    if (!h) return set_error(QH_ERR_INVALID, "qh_anb_synchronize: null handle");
-    QH_HIP(hipSetDevice(h->device));
-    QH_HIP(hipStreamSynchronize(h->stream));
-    return QH_OK;
-}
+int qh_anb_synchronize(qh_anb *h) { return bank_synchronize(h, "qh_anb_synchronize"); }
 
 }  // extern "C"

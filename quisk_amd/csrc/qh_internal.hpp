@@ -60,7 +60,9 @@ static inline bool rows_overlap(const void *a, long long a_stride_bytes, long lo
     return false;
 }
 
-// QH_OK, or QH_ERR_INVALID with the message set, for the settings qh_nob_create refuses (qh_nob.hip)
+// QH_OK, or QH_ERR_INVALID with the message set, for the settings qh_anb_create / qh_nob_create refuse (qh_anb.hip, qh_nob.hip): what
+// lets create_anbEXT / create_nobEXT tell refused settings from a device that failed
+int anb_check_settings(double samplerate, double tau, double hangtime, double advtime, double backtau, double threshold);
 int nob_check_settings(double samplerate, int mode, double slewtime, double hangtime, double advtime, double backtau, double threshold);
 
 }  // namespace qh

@@ -15,7 +15,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <vector>
-#include "qh_internal.hpp"
+#include "qh_bank.hpp"
 #include "qh_kernels.hpp"
 
 using namespace qh;
@@ -212,13 +212,9 @@ extern "C" {
 qh_nb *qh_nb_create(int device, int nch, int sample_rate, void *stream)
 {
     if (nch <= 0 || sample_rate < 8000) { set_error(QH_ERR_INVALID, "qh_nb_create: bad arguments"); return nullptr; }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
-        set_error(QH_ERR_NO_DEVICE, "no HIP device %d (libquiskhip has no CPU fallback)", device);
-        return nullptr;
-    }
     qh_nb *h = new qh_nb();
-    h->device = device; h->nch = nch; h->sample_rate = sample_rate;
+    h->nch = nch; h->sample_rate = sample_rate;
+    if (bank_open(h, device, stream, "qh_nb_create") != QH_OK) { delete h; return nullptr; }
     h->hw = (int)(sample_rate * 500.E-6 + 0.5);             // QUISK_NB_HWINDOW_SECS, quisk.c:679,702
     h->S = 3 * h->hw;                                        // save_size, quisk.c:703
     h->H = 7 * h->hw;                                        // look-back of the first output: 2 S + hw - 1
@@ -239,13 +235,7 @@ qh_nb *qh_nb_create(int device, int nch, int sample_rate, void *stream)
         return nullptr;
     }
     auto fail = [&](const char *what) -> qh_nb * { set_error(QH_ERR_HIP, "qh_nb_create: %s failed", what); delete h; return nullptr; };
-    if (hipSetDevice(device) != hipSuccess) return fail("hipSetDevice");
-    hipStream_t s = (hipStream_t)stream;
-    if (!s) {
-        if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) return fail("stream creation");
-        h->own_stream = true;
-    }
-    h->stream = s;
+    hipStream_t s = h->stream;
     for (int i = 0; i < 2; i++) {
         if (hipMalloc((void **)&h->hist[i], (size_t)nch * (size_t)h->H * sizeof(double2)) != hipSuccess) return fail("hipMalloc");
         if (hipMemsetAsync(h->hist[i], 0, (size_t)nch * (size_t)h->H * sizeof(double2), s) != hipSuccess) return fail("hipMemset");
@@ -325,31 +315,9 @@ int qh_nb_process(qh_nb *h, const void *d_in, long long in_stride, void *d_out, 
 
 int qh_nb_process_host(qh_nb *h, const void *h_in, long long in_stride, void *h_out, long long out_stride, int n)
 {
-    if (!h || n < 0 || (n > 0 && (!h_in || !h_out || in_stride < n || out_stride < n)))
-        return set_error(QH_ERR_INVALID, "qh_nb_process_host: bad arguments");
-    if (n == 0) return QH_OK;
-    QH_HIP(hipSetDevice(h->device));
-    double2 *d = nullptr, *o = nullptr;
-    QH_HIP(hipMalloc((void **)&d, (size_t)h->nch * (size_t)n * sizeof(double2)));
-    if (hipMalloc((void **)&o, (size_t)h->nch * (size_t)n * sizeof(double2)) != hipSuccess) { (void)hipFree(d); return set_error(QH_ERR_HIP, "hipMalloc failed"); }
-    int rc = QH_OK;
-    if (hipMemcpy2DAsync(d, (size_t)n * 16, h_in, (size_t)in_stride * 16, (size_t)n * 16, (size_t)h->nch, hipMemcpyHostToDevice, h->stream) != hipSuccess)
-        rc = set_error(QH_ERR_HIP, "upload failed");
-    if (rc == QH_OK) rc = qh_nb_process(h, d, n, o, n, n);
-    if (rc == QH_OK && hipMemcpy2DAsync(h_out, (size_t)out_stride * 16, o, (size_t)n * 16, (size_t)n * 16, (size_t)h->nch, hipMemcpyDeviceToHost,
-                                         h->stream) != hipSuccess)
-        rc = set_error(QH_ERR_HIP, "download failed");
-    if (hipStreamSynchronize(h->stream) != hipSuccess && rc == QH_OK) rc = set_error(QH_ERR_HIP, "synchronize failed");
-    (void)hipFree(d); (void)hipFree(o);
-    return rc;
+    return bank_process_host(h, h_in, in_stride, h_out, out_stride, n, qh_nb_process, "qh_nb_process_host");
 }
 
-int qh_nb_synchronize(qh_nb *h)
-{
-    if (!h) return set_error(QH_ERR_INVALID, "qh_nb_synchronize: null handle");
-    QH_HIP(hipSetDevice(h->device));
-    QH_HIP(hipStreamSynchronize(h->stream));
-    return QH_OK;
-}
+int qh_nb_synchronize(qh_nb *h) { return bank_synchronize(h, "qh_nb_synchronize"); }
 
 }  // extern "C"

@@ -8,8 +8,7 @@
 // after -- which the states 1-4 then play out (slew, fill, slew); a sequence longer than max_imp_seq goes through states 5-9 (zeros
 // until a whole window of flags is clear).  Positions here are stream indices relative to the call's first sample: at step s the
 // newest sample is s, the output is sample s - D, the scan point is s - (D - S0).  The call is cut as qh_anb.hip cuts xanb:
-//   det 0 / carry / det 1    the detector's average in lane tiles with scanned start values, the reference's arithmetic uncontracted in
-//            the last pass; the impulse flags, 64 samples a word                                              (two reads of the rows)
+//   det 0 / carry / det 1    the detector of qh_blank_det.hpp: the impulse flags, 64 samples a word           (two reads of the rows)
 //   copy     one thread per output sample: the sample D back, from the call's rows or the history             (one read, one write)
 //   walk     one wavefront per channel, from event to event: quiet stretches are skipped by bit scans (a __ballot over 64 words), a
 //            set-up does the reference's merging loop with a dilation of the flags by hang + hang_slew + 1 and bit scans, gathers the
@@ -20,16 +19,13 @@
 // A read of the reference that runs ahead of its write position (the look-ahead, the forward gather) finds the slot as it was
 // dline_size samples earlier: position u > s means u - dline_size (nob_bits64, nob_samp), which is why a channel keeps dline_size
 // samples and flags of history.  bfbuff is rebuilt at each set-up from the flags and samples behind it.
-// avg inside a tile is the reference's recurrence; only its start value carries the rounding of the scan, eps / (1 - backmult)
-// relative at worst, so a flag can differ from a sample-serial run only where mag sits that close to avg threshold.  Given the flags
-// the output is the reference's bit for bit: the tables, backmult and the counts come from the host's C library, the sums and
-// products are the reference's in its order.
+// Given the flags (see the header for where they can differ from a sample-serial run) the output is the reference's bit for bit: the
+// tables, backmult and the counts come from the host's C library, the sums and products are the reference's in its order.
 #include <algorithm>
 #include <climits>
 #include <cmath>
-#include <mutex>
 #include <vector>
-#include "qh_internal.hpp"
+#include "qh_blank_det.hpp"
 
 #pragma clang fp contract(off)
 
@@ -37,10 +33,6 @@ using namespace qh;
 
 namespace {
 
-typedef unsigned long long u64;
-
-constexpr int kNobL = 128;                              // samples per lane tile (two words of flags)
-constexpr int kNobB = 8, kNobPitch = kNobB + 1;         // samples per tile and trip through LDS; padded against bank conflicts
 constexpr double kNobMaxTime = 0.002, kNobMaxSeqTime = 0.025, kNobMaxRate = 1536000.0;     // nobII.c:29-34
 constexpr int kNobSize = (int)(kNobMaxRate * (kNobMaxTime + kNobMaxTime + kNobMaxTime + kNobMaxTime + kNobMaxSeqTime) + 2);    // dline_size, nobII.c:94-98
 constexpr int kNobHW = (kNobSize + 63) / 64;            // words of flags kept per channel
@@ -52,108 +44,18 @@ constexpr long long kNobNone = LLONG_MAX;
 
 struct NobParam {
     double backmult, ombackmult, threshold;
-    double carry;                       // backmult^kNobL
+    double carry;                       // backmult^kDetL
     int asl, adv, hang, hsl, mseq;      // adv_slew_count, adv_count, hang_count, hang_slew_count, max_imp_seq
     int D, mode, run;
 };
+static_assert(sizeof(NobParam) == 64, "the layout the kernels and the upload share");
 
 // what xnob keeps from call to call, but for the ring (the history buffers) and bfbuff (rebuilt)
 struct NobState {
     double avg, I, Q, dI, dQ, Il, Ql, In, Qn;
     int S, tm, blank, pad;
 };
-
-// every set bit smeared over the T - 1 bits above it (inside the word)
-__device__ __forceinline__ u64 nob_dilate(u64 x, int T)
-{
-    if (!x) return 0ull;
-    if (T >= 64) return ~0ull << (__ffsll((long long)x) - 1);
-    u64 r = x;
-    for (int have = 1; have < T;) {
-        const int sh = have < T - have ? have : T - have;
-        r |= r << sh;
-        have += sh;
-    }
-    return r;
-}
-
-// det 0 / det 1, the carry: qh_anb.hip's detector (nobII.c:179-184 is nob.c:118-122).  One wavefront = 64 consecutive tiles of one
-// channel; lane l owns samples [q L, min((q + 1) L, n)), q = 64 blockIdx.x + l.  ends: [ch][estride], one double per tile.  trb:
-// [ch][wstride] words of flags, bits at and beyond n clear in the words written (words wholly beyond n are not written).
-template <int PASS>
-__global__ __launch_bounds__(64) void nob_det_kernel(const double2 *in, long long stride, int n, const NobParam *prm, NobState *state,
-                                                     double *ends, long long estride, u64 *trb, long long wstride)
-{
-    constexpr int L = kNobL, B = kNobB, RPI = 64 / B;
-    __shared__ double lds[64 * kNobPitch];
-    const int ch = blockIdx.y, lane = threadIdx.x;
-    if (!prm[ch].run) return;
-    const long long t0 = (long long)blockIdx.x * 64, first = t0 * L;
-    const long long ntile = ((long long)n + L - 1) / L, q = t0 + lane;
-    if (first >= n || (PASS == 0 && t0 >= ntile - 1)) return;
-    const bool live = PASS == 0 ? q < ntile - 1 : q < ntile;
-    const double bm = prm[ch].backmult, om = prm[ch].ombackmult, th = prm[ch].threshold;
-    double *erow = ends + (long long)ch * estride;
-    double avg = PASS == 1 && live ? erow[q] : 0.0;
-    const int tn = live ? (int)((long long)n - q * L < L ? (long long)n - q * L : (long long)L) : 0;
-    const double2 *b = in + (long long)ch * stride + first;
-    const long long nrem = (long long)n - first;
-    u64 *wout = trb + (long long)ch * wstride + q * (L / 64), word = 0;
-    const int frow = lane / B, fcol = lane % B;
-    for (int i0 = 0; i0 < L; i0 += B) {
-#pragma unroll
-        for (int j = 0; j < B; j++) {
-            const int row = RPI * j + frow;
-            const long long off = (long long)row * L + i0 + fcol;
-            double m = 0.0;
-            if (off < nrem) {
-                const double2 z = b[off];
-                m = __builtin_sqrt(z.x * z.x + z.y * z.y);                  // nobII.c:179
-            }
-            lds[row * kNobPitch + fcol] = m;
-        }
-        __syncthreads();
-        if (i0 < tn) {
-#pragma unroll
-            for (int k = 0; k < B; k++) {
-                if (i0 + k < tn) {
-                    const double mag = lds[lane * kNobPitch + k];
-                    avg = bm * avg + om * mag;                              // nobII.c:180
-                    if (PASS == 1 && mag > avg * th) word |= 1ull << ((i0 + k) & 63);      // nobII.c:181
-                }
-            }
-        }
-        if (PASS == 1 && ((i0 + B) & 63) == 0) {
-            if (i0 + B - 64 < tn) wout[(i0 + B - 64) >> 6] = word;
-            word = 0;
-        }
-        __syncthreads();
-    }
-    if (PASS == 0 && live) erow[q] = avg;
-    if (PASS == 1 && live && q == ntile - 1) state[ch].avg = avg;
-}
-
-__global__ __launch_bounds__(64) void nob_carry_kernel(int n, const NobParam *prm, const NobState *state, double *ends, long long estride)
-{
-    const int ch = blockIdx.x, lane = threadIdx.x;
-    if (!prm[ch].run) return;
-    const long long ntile = ((long long)n + kNobL - 1) / kNobL;
-    const double M = prm[ch].carry;
-    double s = state[ch].avg;
-    double *rows = ends + (long long)ch * estride;
-    for (long long j0 = 0; j0 < ntile; j0 += 64) {
-        const long long j = j0 + lane;
-        double A = M, E = j < ntile - 1 ? rows[j] : 0.0;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const double Au = __shfl_up(A, d, 64), Eu = __shfl_up(E, d, 64);
-            if (lane >= d) { E = fma(A, Eu, E); A *= Au; }
-        }
-        const double Ax = __shfl_up(A, 1, 64), Ex = __shfl_up(E, 1, 64);
-        if (j < ntile) rows[j] = lane ? fma(Ax, s, Ex) : s;
-        s = fma(__shfl(A, 63, 64), s, __shfl(E, 63, 64));
-    }
-}
+static_assert(sizeof(NobState) == 88, "the layout the kernels share");
 
 // One channel's samples and flags as the walk sees them: positions >= 0 are the call's (flags in tw, nw words), positions in
 // [-kNobHist, 0) the history's; older ones read as the flush's zeros.
@@ -263,7 +165,7 @@ __device__ long long nob_run_end(const NobCtx &c, long long p, long long cap, in
         }
         const long long ex = __shfl_up(inc, 1, 64);
         const long long ltb = lane && ex > lt ? ex : lt;
-        u64 cov = nob_dilate(tw, G + 1);
+        u64 cov = dilate(tw, G + 1);
         const long long left = (long long)G + 1 - (ws - ltb);               // bits of the word a flag before it still holds
         if (left > 0) cov |= left >= 64 ? ~0ull : (1ull << left) - 1ull;
         const u64 bal = __ballot(~cov != 0ull);
@@ -563,134 +465,81 @@ int qh::nob_check_settings(double samplerate, int mode, double slewtime, double 
     return why ? set_error(QH_ERR_INVALID, "%s", why) : QH_OK;
 }
 
-struct qh_nob {
-    int device = 0, nch = 0;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
-    std::mutex mtx;                                     // setters may come from another thread than process (cs_update, nobII.c:119)
+struct qh_nob : Bank {
     std::vector<NobSettings> set;
     std::vector<NobParam> prm;
     std::vector<double> awave, hwave;                   // [nch][kNobWave]
     std::vector<char> wave_dirty;
-    bool dirty = true;
     NobParam *d_prm = nullptr;
     NobState *d_state = nullptr;
     double *d_awave = nullptr, *d_hwave = nullptr;
     double2 *hist[2] = { nullptr, nullptr };
     u64 *bits[2] = { nullptr, nullptr };
-    int cur = 0;
-    // per-call scratch, grown with n
-    int cap = 0;
-    double *d_ends = nullptr;
-    u64 *d_trb = nullptr;
-    void free_scratch()
-    {
-        (void)hipFree(d_ends); (void)hipFree(d_trb);
-        d_ends = nullptr; d_trb = nullptr; cap = 0;
-    }
     ~qh_nob()
     {
-        (void)hipSetDevice(device);
-        if (stream) (void)hipStreamSynchronize(stream);
-        free_scratch();
+        quiesce();
         (void)hipFree(d_prm); (void)hipFree(d_state); (void)hipFree(d_awave); (void)hipFree(d_hwave);
         (void)hipFree(hist[0]); (void)hipFree(hist[1]); (void)hipFree(bits[0]); (void)hipFree(bits[1]);
-        if (own_stream && stream) (void)hipStreamDestroy(stream);
+    }
+
+    static const char *refusal(const NobSettings &s) { return nob_refusal(s); }
+
+    // init_nob's numbers (nobII.c:40-58), with the C library's exp and cos
+    void derive(int ch)
+    {
+        const NobSettings &s = set[ch];
+        NobParam &p = prm[ch];
+        const NobCounts c = nob_counts(s);
+        p.asl = c.asl; p.adv = c.adv; p.hang = c.hang; p.hsl = c.hsl; p.mseq = c.mseq; p.D = c.D;
+        p.backmult = std::exp(-1.0 / (s.samplerate * s.backtau));
+        p.ombackmult = 1.0 - p.backmult;
+        p.carry = std::pow(p.backmult, (double)kDetL);
+        p.threshold = s.threshold;
+        p.mode = s.mode;
+        p.run = s.run;
+        const double PI = 3.1415926535897932;               // comm.h
+        double *a = awave.data() + (size_t)ch * kNobWave, *w = hwave.data() + (size_t)ch * kNobWave;
+        if (p.asl > 0) {
+            const double coef = PI / (p.asl + 1);
+            for (int i = 0; i < p.asl; i++) a[i] = 0.5 * std::cos((i + 1) * coef);
+        }
+        if (p.hsl > 0) {
+            const double coef = PI / p.hsl;
+            for (int i = 0; i < p.hsl; i++) w[i] = 0.5 * std::cos(i * coef);
+        }
+        wave_dirty[ch] = 1;
+        dirty = true;
+    }
+
+    void apply_light(int ch) { prm[ch].threshold = set[ch].threshold; prm[ch].run = set[ch].run; prm[ch].mode = set[ch].mode; }
+
+    int restart(int ch0, int count)
+    {
+        hipLaunchKernelGGL(nob_reset_kernel, dim3((kNobHist + 255) / 256, (unsigned)count), dim3(256), 0, stream, d_state, hist[cur], bits[cur], ch0);
+        QH_HIP(hipGetLastError());
+        return QH_OK;
+    }
+
+    // host settings -> device, behind everything enqueued so far (the copies are synchronous: the vectors may change right after)
+    int upload()
+    {
+        if (!dirty) return QH_OK;
+        QH_HIP(hipStreamSynchronize(stream));
+        QH_HIP(hipMemcpy(d_prm, prm.data(), (size_t)nch * sizeof(NobParam), hipMemcpyHostToDevice));
+        for (int ch = 0; ch < nch; ch++) {
+            if (!wave_dirty[ch]) continue;
+            if (prm[ch].asl > 0)
+                QH_HIP(hipMemcpy(d_awave + (size_t)ch * kNobWave, awave.data() + (size_t)ch * kNobWave, (size_t)prm[ch].asl * sizeof(double),
+                                 hipMemcpyHostToDevice));
+            if (prm[ch].hsl > 0)
+                QH_HIP(hipMemcpy(d_hwave + (size_t)ch * kNobWave, hwave.data() + (size_t)ch * kNobWave, (size_t)prm[ch].hsl * sizeof(double),
+                                 hipMemcpyHostToDevice));
+            wave_dirty[ch] = 0;
+        }
+        dirty = false;
+        return QH_OK;
     }
 };
-
-namespace {
-
-// init_nob's numbers (nobII.c:40-58), with the C library's exp and cos
-void nob_derive(qh_nob *h, int ch)
-{
-    const NobSettings &s = h->set[ch];
-    NobParam &p = h->prm[ch];
-    const NobCounts c = nob_counts(s);
-    p.asl = c.asl; p.adv = c.adv; p.hang = c.hang; p.hsl = c.hsl; p.mseq = c.mseq; p.D = c.D;
-    p.backmult = std::exp(-1.0 / (s.samplerate * s.backtau));
-    p.ombackmult = 1.0 - p.backmult;
-    p.carry = std::pow(p.backmult, (double)kNobL);
-    p.threshold = s.threshold;
-    p.mode = s.mode;
-    p.run = s.run;
-    const double PI = 3.1415926535897932;               // comm.h
-    double *a = h->awave.data() + (size_t)ch * kNobWave, *w = h->hwave.data() + (size_t)ch * kNobWave;
-    if (p.asl > 0) {
-        const double coef = PI / (p.asl + 1);
-        for (int i = 0; i < p.asl; i++) a[i] = 0.5 * std::cos((i + 1) * coef);
-    }
-    if (p.hsl > 0) {
-        const double coef = PI / p.hsl;
-        for (int i = 0; i < p.hsl; i++) w[i] = 0.5 * std::cos(i * coef);
-    }
-    h->wave_dirty[ch] = 1;
-    h->dirty = true;
-}
-
-// host settings -> device, behind everything enqueued so far (the copies are synchronous: the vectors may change right after)
-int nob_upload(qh_nob *h)
-{
-    if (!h->dirty) return QH_OK;
-    QH_HIP(hipStreamSynchronize(h->stream));
-    QH_HIP(hipMemcpy(h->d_prm, h->prm.data(), (size_t)h->nch * sizeof(NobParam), hipMemcpyHostToDevice));
-    for (int ch = 0; ch < h->nch; ch++) {
-        if (!h->wave_dirty[ch]) continue;
-        if (h->prm[ch].asl > 0)
-            QH_HIP(hipMemcpy(h->d_awave + (size_t)ch * kNobWave, h->awave.data() + (size_t)ch * kNobWave, (size_t)h->prm[ch].asl * sizeof(double),
-                             hipMemcpyHostToDevice));
-        if (h->prm[ch].hsl > 0)
-            QH_HIP(hipMemcpy(h->d_hwave + (size_t)ch * kNobWave, h->hwave.data() + (size_t)ch * kNobWave, (size_t)h->prm[ch].hsl * sizeof(double),
-                             hipMemcpyHostToDevice));
-        h->wave_dirty[ch] = 0;
-    }
-    h->dirty = false;
-    return QH_OK;
-}
-
-int nob_restart(qh_nob *h, int ch0, int count)
-{
-    hipLaunchKernelGGL(nob_reset_kernel, dim3((kNobHist + 255) / 256, (unsigned)count), dim3(256), 0, h->stream, h->d_state, h->hist[h->cur],
-                       h->bits[h->cur], ch0);
-    QH_HIP(hipGetLastError());
-    return QH_OK;
-}
-
-// One setter: `edit` changes a copy of the settings of channel ch (-1: every channel); a refusal leaves everything as it was.
-template <typename F> int nob_set(qh_nob *h, int ch, const char *name, bool restart, F edit)
-{
-    if (!h || ch < -1 || ch >= h->nch) return set_error(QH_ERR_INVALID, "%s: bad arguments", name);
-    std::lock_guard<std::mutex> lk(h->mtx);
-    const int c0 = ch < 0 ? 0 : ch, c1 = ch < 0 ? h->nch : ch + 1;
-    std::vector<NobSettings> next(h->set.begin() + c0, h->set.begin() + c1);
-    for (NobSettings &s : next) {
-        edit(s);
-        if (const char *why = nob_refusal(s)) return set_error(QH_ERR_INVALID, "%s: %s", name, why);
-    }
-    QH_HIP(hipSetDevice(h->device));
-    for (int c = c0; c < c1; c++) {
-        h->set[c] = next[c - c0];
-        if (restart) nob_derive(h, c);
-        else { h->prm[c].threshold = h->set[c].threshold; h->prm[c].run = h->set[c].run; h->prm[c].mode = h->set[c].mode; h->dirty = true; }
-    }
-    return restart ? nob_restart(h, c0, c1 - c0) : QH_OK;
-}
-
-int nob_scratch(qh_nob *h, int n)
-{
-    if (n <= h->cap) return QH_OK;
-    QH_HIP(hipStreamSynchronize(h->stream));
-    h->free_scratch();
-    const size_t nw = ((size_t)n + 63) / 64 + 1, nt = ((size_t)n + kNobL - 1) / kNobL + 1;
-    if (dev_alloc(&h->d_ends, (size_t)h->nch * nt) != hipSuccess || dev_alloc(&h->d_trb, (size_t)h->nch * nw) != hipSuccess) {
-        h->free_scratch();
-        return set_error(QH_ERR_HIP, "qh_nob_process: scratch allocation failed");
-    }
-    h->cap = n;
-    return QH_OK;
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -700,27 +549,16 @@ qh_nob *qh_nob_create(int device, int nch, double samplerate, int mode, double s
     const NobSettings s0{samplerate, slewtime, hangtime, advtime, backtau, threshold, mode, 1};
     if (nch <= 0) { set_error(QH_ERR_INVALID, "qh_nob_create: bad arguments"); return nullptr; }
     if (const char *why = nob_refusal(s0)) { set_error(QH_ERR_INVALID, "qh_nob_create: %s", why); return nullptr; }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
-        set_error(QH_ERR_NO_DEVICE, "no HIP device %d (libquiskhip has no CPU fallback)", device);
-        return nullptr;
-    }
     qh_nob *h = new qh_nob();
-    h->device = device; h->nch = nch;
+    h->nch = nch;
     auto fail = [&](const char *what) -> qh_nob * { set_error(QH_ERR_HIP, "qh_nob_create: %s failed", what); delete h; return nullptr; };
-    if (hipSetDevice(device) != hipSuccess) return fail("hipSetDevice");
-    hipStream_t s = (hipStream_t)stream;
-    if (!s) {
-        if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) return fail("stream creation");
-        h->own_stream = true;
-    }
-    h->stream = s;
+    if (bank_open(h, device, stream, "qh_nob_create") != QH_OK) { delete h; return nullptr; }
     h->set.assign((size_t)nch, s0);
     h->prm.assign((size_t)nch, NobParam{});
     h->awave.assign((size_t)nch * kNobWave, 0.0);
     h->hwave.assign((size_t)nch * kNobWave, 0.0);
     h->wave_dirty.assign((size_t)nch, 1);
-    nob_derive(h, 0);
+    h->derive(0);
     for (int ch = 1; ch < nch; ch++) {
         h->prm[ch] = h->prm[0];
         std::copy(h->awave.begin(), h->awave.begin() + kNobWave, h->awave.begin() + (size_t)ch * kNobWave);
@@ -737,7 +575,7 @@ qh_nob *qh_nob_create(int device, int nch, double samplerate, int mode, double s
         dev_zero(h->d_hwave, (size_t)nch * kNobWave * sizeof(double)) != hipSuccess || dev_zero(h->hist[1], hb * sizeof(double2)) != hipSuccess ||
         dev_zero(h->bits[1], bw * sizeof(u64)) != hipSuccess)
         return fail("hipMemset");
-    if (nob_restart(h, 0, nch) != QH_OK) { delete h; return nullptr; }
+    if (h->restart(0, nch) != QH_OK) { delete h; return nullptr; }
     return h;
 }
 
@@ -750,42 +588,32 @@ int qh_nob_delay(qh_nob *h, int ch)
     return h->prm[ch].D;
 }
 
-int qh_nob_set_run(qh_nob *h, int ch, int run) { return nob_set(h, ch, "qh_nob_set_run", false, [=](NobSettings &s) { s.run = run != 0; }); }
-int qh_nob_set_mode(qh_nob *h, int ch, int mode) { return nob_set(h, ch, "qh_nob_set_mode", false, [=](NobSettings &s) { s.mode = mode; }); }
-int qh_nob_set_samplerate(qh_nob *h, int ch, double samplerate) { return nob_set(h, ch, "qh_nob_set_samplerate", true, [=](NobSettings &s) { s.samplerate = samplerate; }); }
-int qh_nob_set_tau(qh_nob *h, int ch, double tau) { return nob_set(h, ch, "qh_nob_set_tau", true, [=](NobSettings &s) { s.slewtime = tau; }); }
-int qh_nob_set_hangtime(qh_nob *h, int ch, double hangtime) { return nob_set(h, ch, "qh_nob_set_hangtime", true, [=](NobSettings &s) { s.hangtime = hangtime; }); }
-int qh_nob_set_advtime(qh_nob *h, int ch, double advtime) { return nob_set(h, ch, "qh_nob_set_advtime", true, [=](NobSettings &s) { s.advtime = advtime; }); }
-int qh_nob_set_backtau(qh_nob *h, int ch, double backtau) { return nob_set(h, ch, "qh_nob_set_backtau", true, [=](NobSettings &s) { s.backtau = backtau; }); }
-int qh_nob_set_threshold(qh_nob *h, int ch, double threshold) { return nob_set(h, ch, "qh_nob_set_threshold", false, [=](NobSettings &s) { s.threshold = threshold; }); }
-int qh_nob_flush(qh_nob *h, int ch) { return nob_set(h, ch, "qh_nob_flush", true, [](NobSettings &) {}); }
+int qh_nob_set_run(qh_nob *h, int ch, int run) { return bank_set(h, ch, "qh_nob_set_run", false, [=](NobSettings &s) { s.run = run != 0; }); }
+int qh_nob_set_mode(qh_nob *h, int ch, int mode) { return bank_set(h, ch, "qh_nob_set_mode", false, [=](NobSettings &s) { s.mode = mode; }); }
+int qh_nob_set_samplerate(qh_nob *h, int ch, double samplerate) { return bank_set(h, ch, "qh_nob_set_samplerate", true, [=](NobSettings &s) { s.samplerate = samplerate; }); }
+int qh_nob_set_tau(qh_nob *h, int ch, double tau) { return bank_set(h, ch, "qh_nob_set_tau", true, [=](NobSettings &s) { s.slewtime = tau; }); }
+int qh_nob_set_hangtime(qh_nob *h, int ch, double hangtime) { return bank_set(h, ch, "qh_nob_set_hangtime", true, [=](NobSettings &s) { s.hangtime = hangtime; }); }
+int qh_nob_set_advtime(qh_nob *h, int ch, double advtime) { return bank_set(h, ch, "qh_nob_set_advtime", true, [=](NobSettings &s) { s.advtime = advtime; }); }
+int qh_nob_set_backtau(qh_nob *h, int ch, double backtau) { return bank_set(h, ch, "qh_nob_set_backtau", true, [=](NobSettings &s) { s.backtau = backtau; }); }
+int qh_nob_set_threshold(qh_nob *h, int ch, double threshold) { return bank_set(h, ch, "qh_nob_set_threshold", false, [=](NobSettings &s) { s.threshold = threshold; }); }
+int qh_nob_flush(qh_nob *h, int ch) { return bank_set(h, ch, "qh_nob_flush", true, [](NobSettings &) {}); }
 
 int qh_nob_process(qh_nob *h, const void *d_in, long long in_stride, void *d_out, long long out_stride, int n)
 {
-    if (!h || n < 0 || (n > 0 && (!d_in || !d_out || in_stride < n || out_stride < n)))
-        return set_error(QH_ERR_INVALID, "qh_nob_process: bad arguments");
+    if (int rc = bank_check_rows("qh_nob_process", h, d_in, in_stride, d_out, out_stride, n, "an output is the input D samples back")) return rc;
     if (n == 0) return QH_OK;
-    if (rows_overlap(d_in, in_stride * 16, (long long)n * 16, d_out, out_stride * 16, (long long)n * 16, h->nch))
-        return set_error(QH_ERR_INVALID, "qh_nob_process: the output rows overlap the input rows (an output is the input D samples back)");
     std::lock_guard<std::mutex> lk(h->mtx);
     QH_HIP(hipSetDevice(h->device));
-    if (int rc = nob_upload(h)) return rc;
-    if (int rc = nob_scratch(h, n)) return rc;
+    if (int rc = h->upload()) return rc;
+    if (int rc = bank_grow(h, n, kDetL, "qh_nob_process")) return rc;
     const double2 *in = static_cast<const double2 *>(d_in);
     double2 *out = static_cast<double2 *>(d_out);
-    const long long nw = ((long long)h->cap + 63) / 64 + 1, nt = ((long long)h->cap + kNobL - 1) / kNobL + 1;
-    const unsigned ntile = (unsigned)((n + kNobL - 1) / kNobL), nch = (unsigned)h->nch;
+    const long long nw = h->nw;
+    const unsigned nch = (unsigned)h->nch;
     bool any = false;
     for (const NobParam &p : h->prm) any = any || p.run;
     hipStream_t s = h->stream;
-    if (any) {
-        if (ntile > 1)
-            hipLaunchKernelGGL((nob_det_kernel<0>), dim3((ntile + 63) / 64, nch), dim3(64), 0, s, in, in_stride, n, h->d_prm, h->d_state, h->d_ends, nt,
-                               h->d_trb, nw);
-        hipLaunchKernelGGL(nob_carry_kernel, dim3(nch), dim3(64), 0, s, n, h->d_prm, h->d_state, h->d_ends, nt);
-        hipLaunchKernelGGL((nob_det_kernel<1>), dim3((ntile + 63) / 64, nch), dim3(64), 0, s, in, in_stride, n, h->d_prm, h->d_state, h->d_ends, nt,
-                           h->d_trb, nw);
-    }
+    if (any) det_enqueue(*h, in, in_stride, n, h->d_prm, h->d_state);
     hipLaunchKernelGGL(nob_copy_kernel, dim3((unsigned)((n + 255) / 256), nch), dim3(256), 0, s, in, in_stride, out, out_stride, n, h->d_prm,
                        h->hist[h->cur]);
     if (any) {
@@ -801,31 +629,9 @@ int qh_nob_process(qh_nob *h, const void *d_in, long long in_stride, void *d_out
 
 int qh_nob_process_host(qh_nob *h, const void *h_in, long long in_stride, void *h_out, long long out_stride, int n)
 {
-    if (!h || n < 0 || (n > 0 && (!h_in || !h_out || in_stride < n || out_stride < n)))
-        return set_error(QH_ERR_INVALID, "qh_nob_process_host: bad arguments");
-    if (n == 0) return QH_OK;
-    QH_HIP(hipSetDevice(h->device));
-    double2 *d = nullptr, *o = nullptr;
-    QH_HIP(hipMalloc((void **)&d, (size_t)h->nch * (size_t)n * sizeof(double2)));
-    if (hipMalloc((void **)&o, (size_t)h->nch * (size_t)n * sizeof(double2)) != hipSuccess) { (void)hipFree(d); return set_error(QH_ERR_HIP, "hipMalloc failed"); }
-    int rc = QH_OK;
-    if (hipMemcpy2DAsync(d, (size_t)n * 16, h_in, (size_t)in_stride * 16, (size_t)n * 16, (size_t)h->nch, hipMemcpyHostToDevice, h->stream) != hipSuccess)
-        rc = set_error(QH_ERR_HIP, "upload failed");
-    if (rc == QH_OK) rc = qh_nob_process(h, d, n, o, n, n);
-    if (rc == QH_OK && hipMemcpy2DAsync(h_out, (size_t)out_stride * 16, o, (size_t)n * 16, (size_t)n * 16, (size_t)h->nch, hipMemcpyDeviceToHost,
-                                         h->stream) != hipSuccess)
-        rc = set_error(QH_ERR_HIP, "download failed");
-    if (hipStreamSynchronize(h->stream) != hipSuccess && rc == QH_OK) rc = set_error(QH_ERR_HIP, "synchronize failed");
-    (void)hipFree(d); (void)hipFree(o);
-    return rc;
+    return bank_process_host(h, h_in, in_stride, h_out, out_stride, n, qh_nob_process, "qh_nob_process_host");
 }
 
-int qh_nob_synchronize(qh_nob *h)
-{
-    if (!h) return set_error(QH_ERR_INVALID, "qh_nob_synchronize: null handle");
-    QH_HIP(hipSetDevice(h->device));
-    QH_HIP(hipStreamSynchronize(h->stream));
-    return QH_OK;
-}
+int qh_nob_synchronize(qh_nob *h) { return bank_synchronize(h, "qh_nob_synchronize"); }
 
 }  // extern "C"

@@ -983,54 +983,131 @@ void SetRXASNBApmultmin(int channel, double pmultmin) { WDSP_SETTER(qh_rxa_SetRX
 
 }  // extern "C"
 
-// ---- the blanker in front of fexchange0: create_anbEXT ... SetEXTANBThreshold (wdsp/nob.c:307-422) ----------------------------
-// panb[id], nob.c:307-308: each id a one-channel qh_anb bank on a stream of its own, with staging rows that let in == out
+// ---- the blankers in front of fexchange0: create_anbEXT ... SetEXTANBThreshold (wdsp/nob.c:307-422), and the second one ("NB2"),
+// create_nobEXT ... SetEXTNOBThreshold (wdsp/nobII.c:605-734) --------------------------------------------------------------------------
+// panb[id], nob.c:307-308, and pnob[id], nobII.c:605-606: each id a one-channel bank on a stream of its own, with staging rows that
+// let in == out
 namespace {
-constexpr int kMaxExtAnbs = 32;     // MAX_EXT_ANBS, nob.c:307
-struct ExtAnb {
-    qh_anb *b = nullptr;
+template <typename B> struct Ext {
+    B *b = nullptr;
     int buffsize = 0, cap = 0;
     hipStream_t stream = nullptr;
     double *d_in = nullptr, *d_out = nullptr;
     hipEvent_t ev_in = nullptr, ev_out = nullptr;
 };
-ExtAnb g_anb[kMaxExtAnbs];
-std::recursive_mutex g_anb_mtx[kMaxExtAnbs];
 
-void anb_release(ExtAnb &a)
+constexpr int kMaxExtAnbs = 32;     // MAX_EXT_ANBS, nob.c:307
+Ext<qh_anb> g_anb[kMaxExtAnbs];
+std::recursive_mutex g_anb_mtx[kMaxExtAnbs];
+constexpr int kMaxExtNobs = 32;     // MAX_EXT_NOBS, nobII.c:605
+Ext<qh_nob> g_nob[kMaxExtNobs];
+std::recursive_mutex g_nob_mtx[kMaxExtNobs];
+
+// What tells the two apart: the table, the bank's functions, and the names the messages carry
+struct AnbExt {
+    typedef qh_anb Bank;
+    static constexpr int count = kMaxExtAnbs;
+    static Ext<qh_anb> *slots() { return g_anb; }
+    static std::recursive_mutex *mutexes() { return g_anb_mtx; }
+    static constexpr auto destroy = qh_anb_destroy;
+    static constexpr auto process = qh_anb_process;
+    static constexpr const char *tag = "ANB", *x_host = "xanbEXT", *x_device = "qh_wdsp_xanbEXT_device";
+};
+struct NobExt {
+    typedef qh_nob Bank;
+    static constexpr int count = kMaxExtNobs;
+    static Ext<qh_nob> *slots() { return g_nob; }
+    static std::recursive_mutex *mutexes() { return g_nob_mtx; }
+    static constexpr auto destroy = qh_nob_destroy;
+    static constexpr auto process = qh_nob_process;
+    static constexpr const char *tag = "NOB", *x_host = "xnobEXT", *x_device = "qh_wdsp_xnobEXT_device";
+};
+
+template <typename X> void ext_release(Ext<typename X::Bank> &a)
 {
-    if (a.b) qh_anb_destroy(a.b);               // (waits for the stream)
+    if (a.b) X::destroy(a.b);                   // (waits for the stream)
     (void)hipFree(a.d_in); (void)hipFree(a.d_out);
     if (a.ev_in) (void)hipEventDestroy(a.ev_in);
     if (a.ev_out) (void)hipEventDestroy(a.ev_out);
     if (a.stream) (void)hipStreamDestroy(a.stream);
-    a = ExtAnb();
+    a = Ext<typename X::Bank>();
 }
 
-struct LockedAnb {
-    ExtAnb *a = nullptr;
+// The slot of a created blanker, locked
+template <typename X> struct LockedExt {
+    Ext<typename X::Bank> *a = nullptr;
     std::unique_lock<std::recursive_mutex> lk;
-    explicit LockedAnb(int id)
+    explicit LockedExt(int id)
     {
         g_status = QH_OK;
-        if (id < 0 || id >= kMaxExtAnbs) { g_status = qh::set_error(QH_ERR_INVALID, "ANB id %d out of range", id); return; }
-        lk = std::unique_lock<std::recursive_mutex>(g_anb_mtx[id]);
-        if (!g_anb[id].b) { g_status = qh::set_error(QH_ERR_INVALID, "ANB id %d has not been created", id); return; }
-        a = &g_anb[id];
+        if (id < 0 || id >= X::count) { g_status = qh::set_error(QH_ERR_INVALID, "%s id %d out of range", X::tag, id); return; }
+        lk = std::unique_lock<std::recursive_mutex>(X::mutexes()[id]);
+        if (!X::slots()[id].b) { g_status = qh::set_error(QH_ERR_INVALID, "%s id %d has not been created", X::tag, id); return; }
+        a = &X::slots()[id];
     }
 };
 
-int anb_staging(ExtAnb &a)
+template <typename X> int ext_staging(Ext<typename X::Bank> &a)
 {
     if (a.buffsize <= a.cap) return QH_OK;
-    if (hipStreamSynchronize(a.stream) != hipSuccess) return qh::set_error(QH_ERR_HIP, "xanbEXT: synchronize failed");
+    if (hipStreamSynchronize(a.stream) != hipSuccess) return qh::set_error(QH_ERR_HIP, "%s: synchronize failed", X::x_host);
     (void)hipFree(a.d_in); (void)hipFree(a.d_out);
     a.d_in = nullptr; a.d_out = nullptr; a.cap = 0;
     if (hipMalloc((void **)&a.d_in, (size_t)a.buffsize * 16) != hipSuccess || hipMalloc((void **)&a.d_out, (size_t)a.buffsize * 16) != hipSuccess)
-        return qh::set_error(QH_ERR_HIP, "xanbEXT: staging allocation failed");
+        return qh::set_error(QH_ERR_HIP, "%s: staging allocation failed", X::x_host);
     a.cap = a.buffsize;
     return QH_OK;
 }
+
+// x*EXT: one buffer of host samples through the bank; returns when `out` holds the result
+template <typename X> void ext_x_host(int id, double *in, double *out)
+{
+    LockedExt<X> L(id);
+    if (!L.a) return;
+    Ext<typename X::Bank> &a = *L.a;
+    if (!in || !out) { g_status = qh::set_error(QH_ERR_INVALID, "%s: null buffer", X::x_host); return; }
+    if (int rc = ext_staging<X>(a)) { g_status = rc; return; }
+    const size_t bytes = (size_t)a.buffsize * 16;
+    if (hipMemcpyAsync(a.d_in, in, bytes, hipMemcpyHostToDevice, a.stream) != hipSuccess) { g_status = qh::set_error(QH_ERR_HIP, "%s: upload failed", X::x_host); return; }
+    if (int rc = X::process(a.b, a.d_in, a.buffsize, a.d_out, a.buffsize, a.buffsize)) { g_status = rc; return; }
+    if (hipMemcpyAsync(out, a.d_out, bytes, hipMemcpyDeviceToHost, a.stream) != hipSuccess || hipStreamSynchronize(a.stream) != hipSuccess)
+        g_status = qh::set_error(QH_ERR_HIP, "%s: download failed", X::x_host);
+}
+
+// qh_wdsp_x*EXT_device: the same on device buffers, in order with the caller's stream
+template <typename X> int ext_x_device(int id, const void *d_in, void *d_out, void *stream)
+{
+    LockedExt<X> L(id);
+    if (!L.a) return g_status;
+    Ext<typename X::Bank> &a = *L.a;
+    if (!d_in || !d_out) return g_status = qh::set_error(QH_ERR_INVALID, "%s: null buffer", X::x_device);
+    if (int rc = ext_staging<X>(a)) return g_status = rc;
+    hipStream_t cs = (hipStream_t)stream;
+    if (!a.ev_in && (hipEventCreateWithFlags(&a.ev_in, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&a.ev_out, hipEventDisableTiming) != hipSuccess))
+        return g_status = qh::set_error(QH_ERR_HIP, "%s: event creation failed", X::x_device);
+    const size_t bytes = (size_t)a.buffsize * 16;
+    if (cs != a.stream) { (void)hipEventRecord(a.ev_in, cs); (void)hipStreamWaitEvent(a.stream, a.ev_in, 0); }
+    int rc = QH_OK;
+    if (hipMemcpyAsync(a.d_in, d_in, bytes, hipMemcpyDeviceToDevice, a.stream) != hipSuccess) rc = qh::set_error(QH_ERR_HIP, "%s: copy failed", X::x_device);
+    if (!rc) rc = X::process(a.b, a.d_in, a.buffsize, a.d_out, a.buffsize, a.buffsize);
+    if (!rc && hipMemcpyAsync(d_out, a.d_out, bytes, hipMemcpyDeviceToDevice, a.stream) != hipSuccess) rc = qh::set_error(QH_ERR_HIP, "%s: copy failed", X::x_device);
+    if (cs != a.stream) { (void)hipEventRecord(a.ev_out, a.stream); (void)hipStreamWaitEvent(cs, a.ev_out, 0); }
+    return g_status = rc;
+}
+
+template <typename X> void ext_set_buffsize(int id, int size, const char *name)
+{
+    LockedExt<X> L(id);
+    if (!L.a) return;
+    if (size <= 0) { g_status = qh::set_error(QH_ERR_INVALID, "%s: bad buffer size", name); return; }
+    L.a->buffsize = size;
+}
+
+#define EXT_SETTER(X, call)                 \
+    do {                                    \
+        LockedExt<X> L(id);                 \
+        if (L.a) g_status = (call);         \
+    } while (0)
 }  // namespace
 
 extern "C" {
@@ -1040,142 +1117,36 @@ void create_anbEXT(int id, int run, int buffsize, double samplerate, double tau,
     g_status = QH_OK;
     if (id < 0 || id >= kMaxExtAnbs) { g_status = qh::set_error(QH_ERR_INVALID, "ANB id %d out of range", id); return; }
     std::unique_lock<std::recursive_mutex> lk(g_anb_mtx[id]);
-    ExtAnb &a = g_anb[id];
+    Ext<qh_anb> &a = g_anb[id];
     if (a.b) { g_status = qh::set_error(QH_ERR_INVALID, "ANB id %d already exists", id); return; }
     if (buffsize <= 0) { g_status = qh::set_error(QH_ERR_INVALID, "create_anbEXT: bad buffer size"); return; }
+    if (int rc = qh::anb_check_settings(samplerate, tau, hangtime, advtime, backtau, threshold)) { g_status = rc; return; }
     if (hipStreamCreateWithFlags(&a.stream, hipStreamNonBlocking) != hipSuccess) {
         a.stream = nullptr;
         g_status = qh::set_error(QH_ERR_NO_DEVICE, "create_anbEXT: no HIP device (libquiskhip has no CPU fallback)");
         return;
     }
     a.b = qh_anb_create(0, 1, samplerate, tau, hangtime, advtime, backtau, threshold, a.stream);
-    if (!a.b) { g_status = QH_ERR_INVALID; anb_release(a); return; }       // message already set
+    if (!a.b) { g_status = QH_ERR_HIP; ext_release<AnbExt>(a); return; }   // the settings were good: the device (message already set)
     a.buffsize = buffsize;
     int rc = qh_anb_set_run(a.b, 0, run);
-    if (!rc) rc = anb_staging(a);
-    if (rc) { g_status = rc; anb_release(a); }
+    if (!rc) rc = ext_staging<AnbExt>(a);
+    if (rc) { g_status = rc; ext_release<AnbExt>(a); }
 }
 
-void destroy_anbEXT(int id)
-{
-    LockedAnb L(id);
-    if (L.a) anb_release(*L.a);
-}
+void destroy_anbEXT(int id) { LockedExt<AnbExt> L(id); if (L.a) ext_release<AnbExt>(*L.a); }
+void flush_anbEXT(int id) { EXT_SETTER(AnbExt, qh_anb_flush(L.a->b, 0)); }
+void xanbEXT(int id, double *in, double *out) { ext_x_host<AnbExt>(id, in, out); }
+int qh_wdsp_xanbEXT_device(int id, const void *d_in, void *d_out, void *stream) { return ext_x_device<AnbExt>(id, d_in, d_out, stream); }
 
-void flush_anbEXT(int id)
-{
-    LockedAnb L(id);
-    if (L.a) g_status = qh_anb_flush(L.a->b, 0);
-}
-
-void xanbEXT(int id, double *in, double *out)
-{
-    LockedAnb L(id);
-    if (!L.a) return;
-    ExtAnb &a = *L.a;
-    if (!in || !out) { g_status = qh::set_error(QH_ERR_INVALID, "xanbEXT: null buffer"); return; }
-    if (int rc = anb_staging(a)) { g_status = rc; return; }
-    const size_t bytes = (size_t)a.buffsize * 16;
-    if (hipMemcpyAsync(a.d_in, in, bytes, hipMemcpyHostToDevice, a.stream) != hipSuccess) { g_status = qh::set_error(QH_ERR_HIP, "xanbEXT: upload failed"); return; }
-    if (int rc = qh_anb_process(a.b, a.d_in, a.buffsize, a.d_out, a.buffsize, a.buffsize)) { g_status = rc; return; }
-    if (hipMemcpyAsync(out, a.d_out, bytes, hipMemcpyDeviceToHost, a.stream) != hipSuccess || hipStreamSynchronize(a.stream) != hipSuccess)
-        g_status = qh::set_error(QH_ERR_HIP, "xanbEXT: download failed");
-}
-
-int qh_wdsp_xanbEXT_device(int id, const void *d_in, void *d_out, void *stream)
-{
-    LockedAnb L(id);
-    if (!L.a) return g_status;
-    ExtAnb &a = *L.a;
-    if (!d_in || !d_out) return g_status = qh::set_error(QH_ERR_INVALID, "qh_wdsp_xanbEXT_device: null buffer");
-    if (int rc = anb_staging(a)) return g_status = rc;
-    hipStream_t cs = (hipStream_t)stream;
-    if (!a.ev_in && (hipEventCreateWithFlags(&a.ev_in, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&a.ev_out, hipEventDisableTiming) != hipSuccess))
-        return g_status = qh::set_error(QH_ERR_HIP, "qh_wdsp_xanbEXT_device: event creation failed");
-    const size_t bytes = (size_t)a.buffsize * 16;
-    if (cs != a.stream) { (void)hipEventRecord(a.ev_in, cs); (void)hipStreamWaitEvent(a.stream, a.ev_in, 0); }
-    int rc = QH_OK;
-    if (hipMemcpyAsync(a.d_in, d_in, bytes, hipMemcpyDeviceToDevice, a.stream) != hipSuccess) rc = qh::set_error(QH_ERR_HIP, "qh_wdsp_xanbEXT_device: copy failed");
-    if (!rc) rc = qh_anb_process(a.b, a.d_in, a.buffsize, a.d_out, a.buffsize, a.buffsize);
-    if (!rc && hipMemcpyAsync(d_out, a.d_out, bytes, hipMemcpyDeviceToDevice, a.stream) != hipSuccess) rc = qh::set_error(QH_ERR_HIP, "qh_wdsp_xanbEXT_device: copy failed");
-    if (cs != a.stream) { (void)hipEventRecord(a.ev_out, a.stream); (void)hipStreamWaitEvent(cs, a.ev_out, 0); }
-    return g_status = rc;
-}
-
-#define ANB_SETTER(call)                    \
-    do {                                    \
-        LockedAnb L(id);                    \
-        if (L.a) g_status = (call);         \
-    } while (0)
-
-void SetEXTANBRun(int id, int run) { ANB_SETTER(qh_anb_set_run(L.a->b, 0, run)); }
-void SetEXTANBBuffsize(int id, int size)
-{
-    LockedAnb L(id);
-    if (!L.a) return;
-    if (size <= 0) { g_status = qh::set_error(QH_ERR_INVALID, "SetEXTANBBuffsize: bad buffer size"); return; }
-    L.a->buffsize = size;
-}
-void SetEXTANBSamplerate(int id, int rate) { ANB_SETTER(qh_anb_set_samplerate(L.a->b, 0, (double)rate)); }
-void SetEXTANBTau(int id, double tau) { ANB_SETTER(qh_anb_set_tau(L.a->b, 0, tau)); }
-void SetEXTANBHangtime(int id, double time) { ANB_SETTER(qh_anb_set_hangtime(L.a->b, 0, time)); }
-void SetEXTANBAdvtime(int id, double time) { ANB_SETTER(qh_anb_set_advtime(L.a->b, 0, time)); }
-void SetEXTANBBacktau(int id, double tau) { ANB_SETTER(qh_anb_set_backtau(L.a->b, 0, tau)); }
-void SetEXTANBThreshold(int id, double thresh) { ANB_SETTER(qh_anb_set_threshold(L.a->b, 0, thresh)); }
-
-}  // extern "C"
-
-// ---- the second blanker ("NB2"): create_nobEXT ... SetEXTNOBThreshold (wdsp/nobII.c:605-734) ----------------------------------
-// pnob[id], nobII.c:605-606: each id a one-channel qh_nob bank on a stream of its own, with staging rows that let in == out
-namespace {
-constexpr int kMaxExtNobs = 32;     // MAX_EXT_NOBS, nobII.c:605
-struct ExtNob {
-    qh_nob *b = nullptr;
-    int buffsize = 0, cap = 0;
-    hipStream_t stream = nullptr;
-    double *d_in = nullptr, *d_out = nullptr;
-    hipEvent_t ev_in = nullptr, ev_out = nullptr;
-};
-ExtNob g_nob[kMaxExtNobs];
-std::recursive_mutex g_nob_mtx[kMaxExtNobs];
-
-void nob_release(ExtNob &a)
-{
-    if (a.b) qh_nob_destroy(a.b);               // (waits for the stream)
-    (void)hipFree(a.d_in); (void)hipFree(a.d_out);
-    if (a.ev_in) (void)hipEventDestroy(a.ev_in);
-    if (a.ev_out) (void)hipEventDestroy(a.ev_out);
-    if (a.stream) (void)hipStreamDestroy(a.stream);
-    a = ExtNob();
-}
-
-struct LockedNob {
-    ExtNob *a = nullptr;
-    std::unique_lock<std::recursive_mutex> lk;
-    explicit LockedNob(int id)
-    {
-        g_status = QH_OK;
-        if (id < 0 || id >= kMaxExtNobs) { g_status = qh::set_error(QH_ERR_INVALID, "NOB id %d out of range", id); return; }
-        lk = std::unique_lock<std::recursive_mutex>(g_nob_mtx[id]);
-        if (!g_nob[id].b) { g_status = qh::set_error(QH_ERR_INVALID, "NOB id %d has not been created", id); return; }
-        a = &g_nob[id];
-    }
-};
-
-int nob_staging(ExtNob &a)
-{
-    if (a.buffsize <= a.cap) return QH_OK;
-    if (hipStreamSynchronize(a.stream) != hipSuccess) return qh::set_error(QH_ERR_HIP, "xnobEXT: synchronize failed");
-    (void)hipFree(a.d_in); (void)hipFree(a.d_out);
-    a.d_in = nullptr; a.d_out = nullptr; a.cap = 0;
-    if (hipMalloc((void **)&a.d_in, (size_t)a.buffsize * 16) != hipSuccess || hipMalloc((void **)&a.d_out, (size_t)a.buffsize * 16) != hipSuccess)
-        return qh::set_error(QH_ERR_HIP, "xnobEXT: staging allocation failed");
-    a.cap = a.buffsize;
-    return QH_OK;
-}
-}  // namespace
-
-extern "C" {
+void SetEXTANBRun(int id, int run) { EXT_SETTER(AnbExt, qh_anb_set_run(L.a->b, 0, run)); }
+void SetEXTANBBuffsize(int id, int size) { ext_set_buffsize<AnbExt>(id, size, "SetEXTANBBuffsize"); }
+void SetEXTANBSamplerate(int id, int rate) { EXT_SETTER(AnbExt, qh_anb_set_samplerate(L.a->b, 0, (double)rate)); }
+void SetEXTANBTau(int id, double tau) { EXT_SETTER(AnbExt, qh_anb_set_tau(L.a->b, 0, tau)); }
+void SetEXTANBHangtime(int id, double time) { EXT_SETTER(AnbExt, qh_anb_set_hangtime(L.a->b, 0, time)); }
+void SetEXTANBAdvtime(int id, double time) { EXT_SETTER(AnbExt, qh_anb_set_advtime(L.a->b, 0, time)); }
+void SetEXTANBBacktau(int id, double tau) { EXT_SETTER(AnbExt, qh_anb_set_backtau(L.a->b, 0, tau)); }
+void SetEXTANBThreshold(int id, double thresh) { EXT_SETTER(AnbExt, qh_anb_set_threshold(L.a->b, 0, thresh)); }
 
 void create_nobEXT(int id, int run, int mode, int buffsize, double samplerate, double slewtime, double hangtime, double advtime, double backtau,
                    double threshold)
@@ -1183,7 +1154,7 @@ void create_nobEXT(int id, int run, int mode, int buffsize, double samplerate, d
     g_status = QH_OK;
     if (id < 0 || id >= kMaxExtNobs) { g_status = qh::set_error(QH_ERR_INVALID, "NOB id %d out of range", id); return; }
     std::unique_lock<std::recursive_mutex> lk(g_nob_mtx[id]);
-    ExtNob &a = g_nob[id];
+    Ext<qh_nob> &a = g_nob[id];
     if (a.b) { g_status = qh::set_error(QH_ERR_INVALID, "NOB id %d already exists", id); return; }
     if (buffsize <= 0) { g_status = qh::set_error(QH_ERR_INVALID, "create_nobEXT: bad buffer size"); return; }
     if (int rc = qh::nob_check_settings(samplerate, mode, slewtime, hangtime, advtime, backtau, threshold)) { g_status = rc; return; }
@@ -1193,79 +1164,26 @@ void create_nobEXT(int id, int run, int mode, int buffsize, double samplerate, d
         return;
     }
     a.b = qh_nob_create(0, 1, samplerate, mode, slewtime, hangtime, advtime, backtau, threshold, a.stream);
-    if (!a.b) { g_status = QH_ERR_HIP; nob_release(a); return; }           // the settings were good: the device (message already set)
+    if (!a.b) { g_status = QH_ERR_HIP; ext_release<NobExt>(a); return; }   // the settings were good: the device (message already set)
     a.buffsize = buffsize;
     int rc = qh_nob_set_run(a.b, 0, run);
-    if (!rc) rc = nob_staging(a);
-    if (rc) { g_status = rc; nob_release(a); }
+    if (!rc) rc = ext_staging<NobExt>(a);
+    if (rc) { g_status = rc; ext_release<NobExt>(a); }
 }
 
-void destroy_nobEXT(int id)
-{
-    LockedNob L(id);
-    if (L.a) nob_release(*L.a);
-}
+void destroy_nobEXT(int id) { LockedExt<NobExt> L(id); if (L.a) ext_release<NobExt>(*L.a); }
+void flush_nobEXT(int id) { EXT_SETTER(NobExt, qh_nob_flush(L.a->b, 0)); }
+void xnobEXT(int id, double *in, double *out) { ext_x_host<NobExt>(id, in, out); }
+int qh_wdsp_xnobEXT_device(int id, const void *d_in, void *d_out, void *stream) { return ext_x_device<NobExt>(id, d_in, d_out, stream); }
 
-void flush_nobEXT(int id)
-{
-    LockedNob L(id);
-    if (L.a) g_status = qh_nob_flush(L.a->b, 0);
-}
-
-void xnobEXT(int id, double *in, double *out)
-{
-    LockedNob L(id);
-    if (!L.a) return;
-    ExtNob &a = *L.a;
-    if (!in || !out) { g_status = qh::set_error(QH_ERR_INVALID, "xnobEXT: null buffer"); return; }
-    if (int rc = nob_staging(a)) { g_status = rc; return; }
-    const size_t bytes = (size_t)a.buffsize * 16;
-    if (hipMemcpyAsync(a.d_in, in, bytes, hipMemcpyHostToDevice, a.stream) != hipSuccess) { g_status = qh::set_error(QH_ERR_HIP, "xnobEXT: upload failed"); return; }
-    if (int rc = qh_nob_process(a.b, a.d_in, a.buffsize, a.d_out, a.buffsize, a.buffsize)) { g_status = rc; return; }
-    if (hipMemcpyAsync(out, a.d_out, bytes, hipMemcpyDeviceToHost, a.stream) != hipSuccess || hipStreamSynchronize(a.stream) != hipSuccess)
-        g_status = qh::set_error(QH_ERR_HIP, "xnobEXT: download failed");
-}
-
-int qh_wdsp_xnobEXT_device(int id, const void *d_in, void *d_out, void *stream)
-{
-    LockedNob L(id);
-    if (!L.a) return g_status;
-    ExtNob &a = *L.a;
-    if (!d_in || !d_out) return g_status = qh::set_error(QH_ERR_INVALID, "qh_wdsp_xnobEXT_device: null buffer");
-    if (int rc = nob_staging(a)) return g_status = rc;
-    hipStream_t cs = (hipStream_t)stream;
-    if (!a.ev_in && (hipEventCreateWithFlags(&a.ev_in, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&a.ev_out, hipEventDisableTiming) != hipSuccess))
-        return g_status = qh::set_error(QH_ERR_HIP, "qh_wdsp_xnobEXT_device: event creation failed");
-    const size_t bytes = (size_t)a.buffsize * 16;
-    if (cs != a.stream) { (void)hipEventRecord(a.ev_in, cs); (void)hipStreamWaitEvent(a.stream, a.ev_in, 0); }
-    int rc = QH_OK;
-    if (hipMemcpyAsync(a.d_in, d_in, bytes, hipMemcpyDeviceToDevice, a.stream) != hipSuccess) rc = qh::set_error(QH_ERR_HIP, "qh_wdsp_xnobEXT_device: copy failed");
-    if (!rc) rc = qh_nob_process(a.b, a.d_in, a.buffsize, a.d_out, a.buffsize, a.buffsize);
-    if (!rc && hipMemcpyAsync(d_out, a.d_out, bytes, hipMemcpyDeviceToDevice, a.stream) != hipSuccess) rc = qh::set_error(QH_ERR_HIP, "qh_wdsp_xnobEXT_device: copy failed");
-    if (cs != a.stream) { (void)hipEventRecord(a.ev_out, a.stream); (void)hipStreamWaitEvent(cs, a.ev_out, 0); }
-    return g_status = rc;
-}
-
-#define NOB_SETTER(call)                    \
-    do {                                    \
-        LockedNob L(id);                    \
-        if (L.a) g_status = (call);         \
-    } while (0)
-
-void SetEXTNOBRun(int id, int run) { NOB_SETTER(qh_nob_set_run(L.a->b, 0, run)); }
-void SetEXTNOBMode(int id, int mode) { NOB_SETTER(qh_nob_set_mode(L.a->b, 0, mode)); }
-void SetEXTNOBBuffsize(int id, int size)
-{
-    LockedNob L(id);
-    if (!L.a) return;
-    if (size <= 0) { g_status = qh::set_error(QH_ERR_INVALID, "SetEXTNOBBuffsize: bad buffer size"); return; }
-    L.a->buffsize = size;
-}
-void SetEXTNOBSamplerate(int id, int rate) { NOB_SETTER(qh_nob_set_samplerate(L.a->b, 0, (double)rate)); }
-void SetEXTNOBTau(int id, double tau) { NOB_SETTER(qh_nob_set_tau(L.a->b, 0, tau)); }
-void SetEXTNOBHangtime(int id, double time) { NOB_SETTER(qh_nob_set_hangtime(L.a->b, 0, time)); }
-void SetEXTNOBAdvtime(int id, double time) { NOB_SETTER(qh_nob_set_advtime(L.a->b, 0, time)); }
-void SetEXTNOBBacktau(int id, double tau) { NOB_SETTER(qh_nob_set_backtau(L.a->b, 0, tau)); }
-void SetEXTNOBThreshold(int id, double thresh) { NOB_SETTER(qh_nob_set_threshold(L.a->b, 0, thresh)); }
+void SetEXTNOBRun(int id, int run) { EXT_SETTER(NobExt, qh_nob_set_run(L.a->b, 0, run)); }
+void SetEXTNOBMode(int id, int mode) { EXT_SETTER(NobExt, qh_nob_set_mode(L.a->b, 0, mode)); }
+void SetEXTNOBBuffsize(int id, int size) { ext_set_buffsize<NobExt>(id, size, "SetEXTNOBBuffsize"); }
+void SetEXTNOBSamplerate(int id, int rate) { EXT_SETTER(NobExt, qh_nob_set_samplerate(L.a->b, 0, (double)rate)); }
+void SetEXTNOBTau(int id, double tau) { EXT_SETTER(NobExt, qh_nob_set_tau(L.a->b, 0, tau)); }
+void SetEXTNOBHangtime(int id, double time) { EXT_SETTER(NobExt, qh_nob_set_hangtime(L.a->b, 0, time)); }
+void SetEXTNOBAdvtime(int id, double time) { EXT_SETTER(NobExt, qh_nob_set_advtime(L.a->b, 0, time)); }
+void SetEXTNOBBacktau(int id, double tau) { EXT_SETTER(NobExt, qh_nob_set_backtau(L.a->b, 0, tau)); }
+void SetEXTNOBThreshold(int id, double thresh) { EXT_SETTER(NobExt, qh_nob_set_threshold(L.a->b, 0, thresh)); }
 
 }  // extern "C"

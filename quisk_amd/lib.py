@@ -249,53 +249,31 @@ def load():
     L.qh_nb_process.argtypes = [vp, vp, ll, vp, ll, i]
     L.qh_nb_process_host.argtypes = [vp, vp, ll, vp, ll, i]
     L.qh_nb_synchronize.argtypes = [vp]
-    # WDSP's noise blanker (wdsp/nob.c): the bank and the EXT names in front of fexchange0
-    L.qh_anb_create.restype = vp
-    L.qh_anb_create.argtypes = [i, i, d, d, d, d, d, d, vp]
-    L.qh_anb_destroy.argtypes = [vp]
-    L.qh_anb_destroy.restype = None
-    L.qh_anb_delay.argtypes = [vp, i]
-    L.qh_anb_set_run.argtypes = [vp, i, i]
-    for n in ("samplerate", "tau", "hangtime", "advtime", "backtau", "threshold"):
-        getattr(L, "qh_anb_set_" + n).argtypes = [vp, i, d]
-    L.qh_anb_flush.argtypes = [vp, i]
-    L.qh_anb_process.argtypes = [vp, vp, ll, vp, ll, i]
-    L.qh_anb_process_host.argtypes = [vp, vp, ll, vp, ll, i]
-    L.qh_anb_synchronize.argtypes = [vp]
-    L.create_anbEXT.argtypes = [i, i, i, d, d, d, d, d, d]
-    L.create_anbEXT.restype = None
-    L.xanbEXT.argtypes = [i, vp, vp]
-    L.xanbEXT.restype = None
-    L.qh_wdsp_xanbEXT_device.argtypes = [i, vp, vp, vp]
-    for n, a in (("destroy_anbEXT", [i]), ("flush_anbEXT", [i]), ("SetEXTANBRun", [i, i]), ("SetEXTANBBuffsize", [i, i]),
-                 ("SetEXTANBSamplerate", [i, i]), ("SetEXTANBTau", [i, d]), ("SetEXTANBHangtime", [i, d]), ("SetEXTANBAdvtime", [i, d]),
-                 ("SetEXTANBBacktau", [i, d]), ("SetEXTANBThreshold", [i, d])):
-        getattr(L, n).argtypes = a
-        getattr(L, n).restype = None
-    # WDSP's second noise blanker (wdsp/nobII.c): the bank and the EXT names
-    L.qh_nob_create.restype = vp
-    L.qh_nob_create.argtypes = [i, i, d, i, d, d, d, d, d, vp]
-    L.qh_nob_destroy.argtypes = [vp]
-    L.qh_nob_destroy.restype = None
-    L.qh_nob_delay.argtypes = [vp, i]
-    L.qh_nob_set_run.argtypes = [vp, i, i]
-    L.qh_nob_set_mode.argtypes = [vp, i, i]
-    for n in ("samplerate", "tau", "hangtime", "advtime", "backtau", "threshold"):
-        getattr(L, "qh_nob_set_" + n).argtypes = [vp, i, d]
-    L.qh_nob_flush.argtypes = [vp, i]
-    L.qh_nob_process.argtypes = [vp, vp, ll, vp, ll, i]
-    L.qh_nob_process_host.argtypes = [vp, vp, ll, vp, ll, i]
-    L.qh_nob_synchronize.argtypes = [vp]
-    L.create_nobEXT.argtypes = [i, i, i, i, d, d, d, d, d, d]
-    L.create_nobEXT.restype = None
-    L.xnobEXT.argtypes = [i, vp, vp]
-    L.xnobEXT.restype = None
-    L.qh_wdsp_xnobEXT_device.argtypes = [i, vp, vp, vp]
-    for n, a in (("destroy_nobEXT", [i]), ("flush_nobEXT", [i]), ("SetEXTNOBRun", [i, i]), ("SetEXTNOBMode", [i, i]), ("SetEXTNOBBuffsize", [i, i]),
-                 ("SetEXTNOBSamplerate", [i, i]), ("SetEXTNOBTau", [i, d]), ("SetEXTNOBHangtime", [i, d]), ("SetEXTNOBAdvtime", [i, d]),
-                 ("SetEXTNOBBacktau", [i, d]), ("SetEXTNOBThreshold", [i, d])):
-        getattr(L, n).argtypes = a
-        getattr(L, n).restype = None
+    # WDSP's noise blankers (wdsp/nob.c, wdsp/nobII.c): the banks and the EXT names in front of fexchange0; the second has a mode
+    for b, create, ext_create, extra in (("anb", [i, i, d, d, d, d, d, d, vp], [i, i, i, d, d, d, d, d, d], ()),
+                                         ("nob", [i, i, d, i, d, d, d, d, d, vp], [i, i, i, i, d, d, d, d, d, d], ("mode",))):
+        bank = lambda n: getattr(L, "qh_%s_%s" % (b, n))
+        bank("create").restype = vp
+        bank("create").argtypes = create
+        bank("destroy").argtypes = [vp]
+        bank("destroy").restype = None
+        bank("delay").argtypes = [vp, i]
+        for n in ("run",) + extra:
+            bank("set_" + n).argtypes = [vp, i, i]
+        for n in ("samplerate", "tau", "hangtime", "advtime", "backtau", "threshold"):
+            bank("set_" + n).argtypes = [vp, i, d]
+        bank("flush").argtypes = [vp, i]
+        bank("process").argtypes = [vp, vp, ll, vp, ll, i]
+        bank("process_host").argtypes = [vp, vp, ll, vp, ll, i]
+        bank("synchronize").argtypes = [vp]
+        B = b.upper()
+        getattr(L, "qh_wdsp_x%sEXT_device" % b).argtypes = [i, vp, vp, vp]
+        for n, a in [["create_%sEXT" % b, ext_create], ["x%sEXT" % b, [i, vp, vp]], ["destroy_%sEXT" % b, [i]], ["flush_%sEXT" % b, [i]],
+                     ["SetEXT%sRun" % B, [i, i]], ["SetEXT%sBuffsize" % B, [i, i]], ["SetEXT%sSamplerate" % B, [i, i]]] + \
+                [["SetEXT%s%s" % (B, n.capitalize()), [i, i]] for n in extra] + \
+                [["SetEXT%s%s" % (B, n), [i, d]] for n in ("Tau", "Hangtime", "Advtime", "Backtau", "Threshold")]:
+            getattr(L, n).argtypes = a
+            getattr(L, n).restype = None
     L.qh_qrx_set_noise_blanker.argtypes = [vp, i]
     L.qh_qrx_set_auto_notch.argtypes = [vp, i, i]
     L.qh_quisk_set_auto_notch.argtypes = [i, i]

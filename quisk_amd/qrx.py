@@ -309,63 +309,63 @@ class NoiseBlanker:
             pass
 
 
-class WdspNoiseBlanker:
-    """WDSP's noise blanker ANB (xanb, wdsp/nob.c:107-187) for `nch` streams at the receiver's input rate, every channel with its own
-    settings; keyword names as create_anb's.  The setters take a channel, or -1 for every channel."""
+class _WdspBlankerBank:
+    """What WdspNoiseBlanker and WdspNoiseBlanker2 share: a bank handle of the C names `_prefix` + ..., its setters and its calls."""
 
-    def __init__(self, nch, samplerate, tau=1e-4, hangtime=1e-4, advtime=1e-4, backtau=0.05, threshold=30.0, device=0, stream=None):
+    _prefix = None
+
+    def _open(self, nch, *args):
         self._L = load()
-        self._h = self._L.qh_anb_create(device, nch, samplerate, tau, hangtime, advtime, backtau, threshold, stream)
+        self._h = self._c("create")(*args)
         if not self._h:
-            raise QuiskHipError("qh_anb_create failed: %s" % self._L.qh_last_error().decode(errors="replace"))
+            raise QuiskHipError("%screate failed: %s" % (self._prefix, self._L.qh_last_error().decode(errors="replace")))
         self.nch = nch
 
-    def delay(self, ch=0):
-        """trans_count + adv_count of channel ch: how far its output lags its input while it runs."""
-        return self._L.qh_anb_delay(self._h, ch)
+    def _c(self, name):
+        return getattr(self._L, self._prefix + name)
 
     def set_run(self, run, ch=-1):
-        check(self._L.qh_anb_set_run(self._h, ch, int(run)))
+        check(self._c("set_run")(self._h, ch, int(run)))
 
     def set_samplerate(self, samplerate, ch=-1):
-        check(self._L.qh_anb_set_samplerate(self._h, ch, samplerate))
+        check(self._c("set_samplerate")(self._h, ch, samplerate))
 
     def set_tau(self, tau, ch=-1):
-        check(self._L.qh_anb_set_tau(self._h, ch, tau))
+        check(self._c("set_tau")(self._h, ch, tau))
 
     def set_hangtime(self, hangtime, ch=-1):
-        check(self._L.qh_anb_set_hangtime(self._h, ch, hangtime))
+        check(self._c("set_hangtime")(self._h, ch, hangtime))
 
     def set_advtime(self, advtime, ch=-1):
-        check(self._L.qh_anb_set_advtime(self._h, ch, advtime))
+        check(self._c("set_advtime")(self._h, ch, advtime))
 
     def set_backtau(self, backtau, ch=-1):
-        check(self._L.qh_anb_set_backtau(self._h, ch, backtau))
+        check(self._c("set_backtau")(self._h, ch, backtau))
 
     def set_threshold(self, threshold, ch=-1):
-        check(self._L.qh_anb_set_threshold(self._h, ch, threshold))
+        check(self._c("set_threshold")(self._h, ch, threshold))
 
     def flush(self, ch=-1):
-        check(self._L.qh_anb_flush(self._h, ch))
+        check(self._c("flush")(self._h, ch))
 
     def process_ptr(self, d_in, in_stride, d_out, out_stride, n):
         """Device pointers, strides in complex samples; rows of d_out apart from those of d_in.  Asynchronous on the bank's stream."""
-        check(self._L.qh_anb_process(self._h, d_in, in_stride, d_out, out_stride, n))
+        check(self._c("process")(self._h, d_in, in_stride, d_out, out_stride, n))
 
     def process_host(self, x):
         x = np.ascontiguousarray(x, dtype=np.complex128)
         if x.ndim != 2 or x.shape[0] != self.nch:
             raise ValueError("expected [nch, n] complex128")
         out = np.empty_like(x)
-        check(self._L.qh_anb_process_host(self._h, x.ctypes.data, x.shape[1], out.ctypes.data, x.shape[1], x.shape[1]))
+        check(self._c("process_host")(self._h, x.ctypes.data, x.shape[1], out.ctypes.data, x.shape[1], x.shape[1]))
         return out
 
     def synchronize(self):
-        check(self._L.qh_anb_synchronize(self._h))
+        check(self._c("synchronize")(self._h))
 
     def close(self):
         if getattr(self, "_h", None):
-            self._L.qh_anb_destroy(self._h)
+            self._c("destroy")(self._h)
             self._h = None
 
     def __del__(self):
@@ -375,71 +375,33 @@ class WdspNoiseBlanker:
             pass
 
 
-class WdspNoiseBlanker2:
+class WdspNoiseBlanker(_WdspBlankerBank):
+    """WDSP's noise blanker ANB (xanb, wdsp/nob.c:107-187) for `nch` streams at the receiver's input rate, every channel with its own
+    settings; keyword names as create_anb's.  The setters take a channel, or -1 for every channel."""
+
+    _prefix = "qh_anb_"
+
+    def __init__(self, nch, samplerate, tau=1e-4, hangtime=1e-4, advtime=1e-4, backtau=0.05, threshold=30.0, device=0, stream=None):
+        self._open(nch, device, nch, samplerate, tau, hangtime, advtime, backtau, threshold, stream)
+
+    def delay(self, ch=0):
+        """trans_count + adv_count of channel ch: how far its output lags its input while it runs."""
+        return self._c("delay")(self._h, ch)
+
+
+class WdspNoiseBlanker2(_WdspBlankerBank):
     """WDSP's second noise blanker NOB, the callers' "NB2" (xnob, wdsp/nobII.c:157-495) for `nch` streams at the receiver's input rate,
     every channel with its own settings; keyword names as create_nobEXT's.  mode: 0 zeros, 1 hold the clean samples before the blank, 2
     the mean of before and after, 3 after, 4 a line between them.  The setters take a channel, or -1 for every channel."""
 
+    _prefix = "qh_nob_"
+
     def __init__(self, nch, samplerate, mode=0, slewtime=1e-4, hangtime=1e-4, advtime=1e-4, backtau=0.05, threshold=30.0, device=0, stream=None):
-        self._L = load()
-        self._h = self._L.qh_nob_create(device, nch, samplerate, int(mode), slewtime, hangtime, advtime, backtau, threshold, stream)
-        if not self._h:
-            raise QuiskHipError("qh_nob_create failed: %s" % self._L.qh_last_error().decode(errors="replace"))
-        self.nch = nch
+        self._open(nch, device, nch, samplerate, int(mode), slewtime, hangtime, advtime, backtau, threshold, stream)
 
     def delay(self, ch=0):
         """How far the output of channel ch lags its input while it runs (adv_slew + adv + 1 + max_imp_seq + hang + hang_slew + 10)."""
-        return self._L.qh_nob_delay(self._h, ch)
-
-    def set_run(self, run, ch=-1):
-        check(self._L.qh_nob_set_run(self._h, ch, int(run)))
+        return self._c("delay")(self._h, ch)
 
     def set_mode(self, mode, ch=-1):
-        check(self._L.qh_nob_set_mode(self._h, ch, int(mode)))
-
-    def set_samplerate(self, samplerate, ch=-1):
-        check(self._L.qh_nob_set_samplerate(self._h, ch, samplerate))
-
-    def set_tau(self, tau, ch=-1):
-        check(self._L.qh_nob_set_tau(self._h, ch, tau))
-
-    def set_hangtime(self, hangtime, ch=-1):
-        check(self._L.qh_nob_set_hangtime(self._h, ch, hangtime))
-
-    def set_advtime(self, advtime, ch=-1):
-        check(self._L.qh_nob_set_advtime(self._h, ch, advtime))
-
-    def set_backtau(self, backtau, ch=-1):
-        check(self._L.qh_nob_set_backtau(self._h, ch, backtau))
-
-    def set_threshold(self, threshold, ch=-1):
-        check(self._L.qh_nob_set_threshold(self._h, ch, threshold))
-
-    def flush(self, ch=-1):
-        check(self._L.qh_nob_flush(self._h, ch))
-
-    def process_ptr(self, d_in, in_stride, d_out, out_stride, n):
-        """Device pointers, strides in complex samples; rows of d_out apart from those of d_in.  Asynchronous on the bank's stream."""
-        check(self._L.qh_nob_process(self._h, d_in, in_stride, d_out, out_stride, n))
-
-    def process_host(self, x):
-        x = np.ascontiguousarray(x, dtype=np.complex128)
-        if x.ndim != 2 or x.shape[0] != self.nch:
-            raise ValueError("expected [nch, n] complex128")
-        out = np.empty_like(x)
-        check(self._L.qh_nob_process_host(self._h, x.ctypes.data, x.shape[1], out.ctypes.data, x.shape[1], x.shape[1]))
-        return out
-
-    def synchronize(self):
-        check(self._L.qh_nob_synchronize(self._h))
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.qh_nob_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        check(self._c("set_mode")(self._h, ch, int(mode)))

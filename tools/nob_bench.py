@@ -3,7 +3,8 @@ and call at 192 kHz, fp64, a typical caller's settings (slew = hangtime = advtim
 the same shape from the same library in the same process, so that the spread from box to box drops out of the ratio.  One JSON line:
 per input (quiet; one 2-sample pulse per 20000 samples) and mode (0 and 4) the mean call with min and max, the same for ANB, the ratio
 to ANB and to the traffic floor.  For the kernels' own times run it under
-`rocprofv3 --kernel-trace --stats -- python tools/nob_bench.py` (nob_*_kernel, anb_*_kernel), one input and mode a run
+`rocprofv3 --kernel-trace --stats -- python tools/nob_bench.py` (nob_*_kernel, anb_*_kernel, and the detector's det_kernel<0 | 1, ...> and
+carry_kernel<...>, one instance per bank's Param and State), one input and mode a run
 (QH_NOB_INPUTS=quiet|pulsed, QH_NOB_MODES=0|4), since the statistics are per kernel name; QH_NOB_N and QH_NOB_PULSE_EVERY vary the
 samples and the events to show what each kernel's time follows.
 
@@ -13,22 +14,14 @@ As built the detector reads the rows twice (det 0 and det 1), the copy reads and
 import json
 import os
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from blanker_bench_common import add_pulses, noise, time_calls  # noqa: E402
 
 
-def _time(bank, x, y, n, steps, warmup=2):
-    for _ in range(warmup):
-        bank.process_ptr(x.data_ptr(), n, y.data_ptr(), n, n)
-    bank.synchronize()
-    ms = []
-    for _ in range(steps):
-        t0 = time.perf_counter()
-        bank.process_ptr(x.data_ptr(), n, y.data_ptr(), n, n)
-        bank.synchronize()
-        ms.append((time.perf_counter() - t0) * 1e3)
+def _time(bank, x, y, n, steps):
+    ms = time_calls(bank, x, y, n, steps)
     return {"mean_ms": sum(ms) / len(ms), "min_ms": min(ms), "max_ms": max(ms)}
 
 
@@ -42,16 +35,8 @@ def main():
     rate = float(os.environ.get("QH_NOB_RATE", "192000"))
     inputs = os.environ.get("QH_NOB_INPUTS", "quiet,pulsed").split(",")
     modes = [int(m) for m in os.environ.get("QH_NOB_MODES", "0,4").split(",")]
-    gen = torch.Generator(device=dev)
-    gen.manual_seed(7)
-    quiet = torch.empty((nch, n), dtype=torch.complex128, device=dev)
-    for c in range(nch):
-        quiet[c] = torch.complex(torch.randn(n, dtype=torch.float64, device=dev, generator=gen), torch.randn(n, dtype=torch.float64, device=dev, generator=gen)) * 0.8
-    pulsed = quiet.clone()
-    for c in range(nch):
-        p = torch.arange((37 * c) % every + 100, n - 2, every, device=dev)
-        pulsed[c, p] += 48.0
-        pulsed[c, p + 1] += 48.0
+    quiet = noise(torch, dev, nch, n)
+    pulsed = add_pulses(torch, quiet.clone(), every)
     y = torch.empty_like(quiet)
     torch.cuda.synchronize(dev)
     one = nch * n * 16
