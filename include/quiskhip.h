@@ -203,9 +203,9 @@ int qh_rxa_process_host(qh_rxa *e, const double *h_in, long long in_stride, doub
 /* Tiles of the time-tiled FM loop that had to be re-run sequentially so far (diagnostics; 0 on carriers, a fraction of a
  * percent of the 256-sample tiles on noise alone). */
 long long qh_rxa_pll_repairs(qh_rxa *h);
-int qh_rxa_debug_pll(qh_rxa *h, int check_only, int ch, double *out, int max);   /* diagnostics, see qh_engine.hip */
+int qh_rxa_debug_pll(qh_rxa *h, int check_only, int ch, double *out, int max);   /* diagnostics, see qh_rxa_api.hip */
 int qh_rxa_debug_agc(qh_rxa *h, int form);                                         /* diagnostics: 0 time tiles for long calls (default), 1 sample by sample, 2 batches of 64 */
-int qh_rxa_debug_agc_ends(qh_rxa *h, int slot, double *out, int max);                /* diagnostics, see qh_engine.hip */
+int qh_rxa_debug_agc_ends(qh_rxa *h, int slot, double *out, int max);                /* diagnostics, see qh_rxa_api.hip */
 long long qh_rxa_agc_repairs(qh_rxa *h);                                            /* wcpAGC time tiles the verify pass re-ran in order */
 long long qh_rxa_agc_segments_rerun(qh_rxa *h);                                     /* super-segments of its boundary pass walked again */
 int qh_rxa_agc_tiled_channels(qh_rxa *h);                                           /* channels whose xwcpagc took the time tiles in the last call */

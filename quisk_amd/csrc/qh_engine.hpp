@@ -1,0 +1,501 @@
+// qh_engine.hpp -- the batched RXA receive engine for MI355X: its constants, the channels' settings (ChanCfg), the engine's state
+// (Engine) and the handle of the C ABI.  Declarations only: qh_engine.hip launches, qh_engine_params.hip designs, allocates and uploads,
+// qh_rxa_api.hip is the C ABI.  Besides alloc / grow / put_row and one-line accessors no function is defined here, and no ABI function.
+//
+// Mirrors create_rxa()/xrxa() of the reference (wdsp/RXA.c:31-598) for the blocks on the hot path.
+// Per-channel differences are data (NCO step, masks, 2x2 output matrix), not control flow, so one
+// launch per stage covers every channel:
+//
+//   front   : xshift + xresample(in)      -> qh::osfir_kernel<NFFT, D = in_rate/dsp_rate, MIX>
+//   nbp0    : xnbp (fircore)              -> qh::osfir_kernel<NFFT, 1>
+//   bp1     : xbandpass (fircore)         -> qh::osfir_kernel<NFFT, 1>      (only when some channel runs it)
+//   epilogue: xwcpagc mode 0 + xpanel     -> fused into the last launch (2x2 real matrix per channel)
+//
+// State carried between calls (all device resident, right-aligned rows of the most recent samples):
+//   hist_front [2][nch][HF]  raw input samples (the reference's resampler ring holds them behind xshift; here the
+//                            oscillator sits behind the filter, qh_osfir.hpp OUTMIX, and nco_retune_hist_kernel
+//                            rewrites the row when a channel's shift changes)
+//   hist_nbp   [2][nch][HB]  nbp0 input samples  (the reference's fircore delay line)
+//   hist_bp1   [2][nch][HB]
+//   nco_phase  [nch]         64-bit fixed-point turns
+#pragma once
+#include <hip/hip_runtime.h>
+#include <algorithm>
+#include <cmath>
+#include <cstdarg>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <map>
+#include <mutex>
+#include <string>
+#include <vector>
+#include "../../include/quiskhip.h"
+#include "qh_design.hpp"
+// the stage headers, for the parameter and state types held by value; each of their `static` kernels is launched by one unit only
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Wunused-function"
+#include "qh_kernels.hpp"
+#include "qh_demod.hpp"
+#include "qh_tiled.hpp"
+#include "qh_agc_tiled.hpp"
+#include "qh_emnr.hpp"
+#include "qh_snba.hpp"
+#include "qh_audio_peak.hpp"
+#include "qh_ssql.hpp"
+#pragma clang diagnostic pop
+#include "qh_internal.hpp"
+
+namespace qh {
+
+static constexpr int kNfft = 4096;          // FFT size of the front stage and, for nc <= 2048, of the fircore stages
+static constexpr int kBandNfftMax = 8192;   // fircore stages with 2048 < nc <= 4096 run 8192-point tiles (Engine::bnfft)
+static constexpr int kHistBand = 4095;      // fircore history capacity: nc up to 4096
+// nc = 8192 ... 65536 (RXASetNC, wdsp/RXA.c:934-946): the impulse response in partitions of 4096 taps, every partition an ordinary
+// 8192-point tile pass over a view of the stream that starts 4096 p samples earlier, the passes added (Engine::run_band)
+static constexpr int kLongPart = 4096, kLongNcMax = 65536, kLongParts = kLongNcMax / kLongPart, kLongHist = kLongNcMax - 1;
+static constexpr int kHistFront = 2240;     // resampler history capacity: 140 * D taps, D <= 16
+// FM PLL time tiles (qh_tiled.hpp).  On a carrier the loop (double pole at 0.66 per sample) forgets its start state in ~100
+// samples; on noise alone two runs meet after ~135 samples on average with an exponential tail, so a 768-sample warm-up
+// leaves a fraction of a percent of the tiles to the verify kernel's sequential re-run.
+static constexpr int kFmTile = 256;        // shortest tile; long calls take up to 2048 samples per lane (Engine::process_chain)
+static constexpr int kFmWarm = 768;
+// SAM's loop (omega_N 250 rad/s, zeta 1, RXA.c:185-186) forgets a state in exp(-250 t): 1e-16 after 0.147 s = 7068 samples at 48 kHz
+static constexpr int kSamTile = 4096;
+static constexpr int kSamWarm = 8192;
+static constexpr long long kSamTiledMin = 4 * 8192;     // shorter calls take the sequential kernel
+static constexpr int kAgcSegs = 16;                     // super-segments of the AGC boundary pass, at most
+static constexpr long long kAgcTiledMin = 16384;        // xwcpagc in time tiles from this many detector samples per call (qh_agc_tiled.hpp)
+
+struct ChanCfg {
+    int mode = QH_LSB;                                          // RXA.c:33
+    int shift_run = 1; double shift_freq = 0.0;                 // RXA.c:39-45
+    int shift_on_device = 1;                                    // whether the device phase is live or parked (nco_park_kernel)
+    int nbp_run = 1, nbp_nc = 2048, nbp_wintype = 0;            // RXA.c:90-106
+    int mp = 0;                                                 // RXASetMP, RXA.c:948
+    // notch database (create_notchdb RXA.c:85-87) and nbp0's use of it (fnfrun 0, autoincr 1: RXA.c:92,104)
+    std::vector<Notch> notches;
+    double ndb_tunefreq = 0.0, ndb_shift = 0.0;
+    int fnfrun = 0, autoincr = 1;
+    double nbp_flow = -4150.0, nbp_fhigh = -150.0, nbp_gain = 1.0;
+    int amd_run = 0, amd_mode = 0, fmd_run = 0;                 // RXA.c:175-212
+    int agc_run = 1, agc_mode = 3; double agc_fixed = 1000.0;   // RXA.c:335-358
+    double agc_tau_attack = 0.001, agc_tau_decay = 0.250, agc_max_gain = 10000.0, agc_var_gain = 1.5;
+    double agc_hangtime = 0.250, agc_hang_thresh = 0.250;
+    bool agc_dirty = true;
+    bool agc_on() const { return agc_run && agc_mode != 0; }
+    int agc_abuf = -1;                  // attack_buffsize last uploaded
+    bool agc_rewindow = false;          // the attack window moved in mid-stream: the state's ring is taken again from the full one
+    bool agc_ran = false, agc_stale = false;    // the window moved while the ring held samples: ring_max may be stale (qh_agc_tiled.hpp)
+    int bp1_run = 1, bp1_nc = 2048, bp1_wintype = 1;            // RXA.c:377-389
+    bool long_live[5] = { false, false, false, false, false };  // the channel holds a delay line of stage sid longer than 4095 samples (process_chain)
+    double bp1_flow = -4150.0, bp1_fhigh = -150.0, bp1_gain = 1.0;
+    double gain1 = 4.0, gain2I = 1.0, gain2Q = 1.0;             // RXA.c:464-474
+    int inselect = 3, copy = 0;
+    int levelfade = 1, sbmode = 0;                              // RXA.c:180-181
+    double fm_dev = 5000.0, ctcss_freq = 254.1;                 // RXA.c:198,208
+    int ctcss_run = 1, fm_nc = 2048;                            // RXA.c:207,209-212
+    int lim_run = 0; double lim_gain = 2.5; bool lim_dirty = true;   // FM detector limiter, fmd.c:106-108
+    // anf / anr (create_anf / create_anr of create_rxa, RXA.c:278-315): [0] = anf, [1] = anr
+    struct Lms { int run = 0, position = 0, taps = 64, delay = 16; double two_mu = 0.0001, gamma = 0.1; bool dirty = true, flush = false; } lms[2];
+    // emnr (create_emnr of create_rxa, RXA.c:319-332)
+    // snba (wdsp/snb.c) and its bandpass bpsnba (snb.c:696-855; run / position follow the mode, RXA.c:883-917)
+    int snba_run = 0, snb_hist_at = 0;
+    int fm_hist_at = 0;                                         // ping-pong half that holds this channel's FM fircore delay lines
+    int bp1_hist_at = 0;                                        // ... and bp1's (SetRXABandpassRun switches it on WITHOUT the flush of RXAbp1Set)
+    bool snba_flush = false, snba_taps_dirty = true, snba_rout_flush = false, snb_dirty = true, snb_flush = false;
+    double snba_f_low = 200.0, snba_f_high = 0.0;               // outresamp fc_low / fcin (snb.c:45-46, resample.c:195-204)
+    int snb_pos() const {
+        if (!snba_run) return -1;
+        switch (mode) {
+        case QH_LSB: case QH_CWL: case QH_DIGL: case QH_USB: case QH_CWU: case QH_DIGU: return 0;
+        case QH_AM: case QH_SAM: case QH_DSB: case QH_FM: return 1;
+        default: return -1;
+        }
+    }
+    int emnr_run = 0, emnr_pos = 0, emnr_gain_method = 2, emnr_npe = 0, emnr_ae = 1; bool emnr_dirty = true, emnr_flush = false;
+    double emnr_ae_zeta = 0.75, emnr_ae_psi = 20.0, emnr_train_zeta = -2.0, emnr_train_t2 = 0.20;       // emnr.c:332,491-493
+    // amsq (create_amsq of create_rxa, RXA.c:158-172)
+    int amsq_run = 0; double amsq_tail_thresh = 0.009, amsq_unmute_thresh = 0.010, amsq_max_tail = 1.5; bool amsq_dirty = true;
+    int bp1_pos = 0;                                            // SetRXAANFPosition / SetRXAANRPosition set it too (anf.c:236)
+    // xwcpagc mode 0 with a position-1 stage behind it: the gain is applied in place at the AGC's spot, not in the epilogue
+    bool demod_dirty = true, ctcss_flush = false;
+    bool nbp_dirty = true, bp1_dirty = true, nco_dirty = true, epi_dirty = true;
+    bool nbp_flush = false, bp1_flush = false;
+    // xcbl, xspeak, xmpeak (create_rxa, RXA.c:403-445: all three made with run 0); the design setters zero their cascade (sp_flush,
+    // mp_flush) at the next block boundary
+    int cbl_run = 0, sp_run = 0, mp_run = 0, mp_npeaks = 2;
+    double sp_f = 600.0, sp_bw = 100.0, sp_gain = 2.0;
+    int mp_enable[kApPeaks] = { 1, 1 };
+    double mp_f[kApPeaks] = { 2125.0, 2295.0 }, mp_bw[kApPeaks] = { 75.0, 75.0 }, mp_gain[kApPeaks] = { 1.0, 1.0 };
+    bool ap_dirty = true, sp_flush = false, mp_flush[kApPeaks] = { false, false };
+    bool ap_on() const { return cbl_run || sp_run || mp_run; }
+    // xssql (create_ssql of create_rxa, RXA.c:447-461: run 0, wthresh 0.08, tau_mute = tau_unmute = 0.1); no setter flushes it
+    int ssql_run = 0;
+    double ssql_wthresh = 0.08, ssql_tau_mute = 0.1, ssql_tau_unmute = 0.1;
+    bool ssql_dirty = true;
+    bool ssql_on() const { return ssql_run != 0; }
+    // (the new stages sit behind xwcpagc too, ahead of the panel: a fixed gain that changes while a peak still rings must not reach
+    // the ringing tail, so it is applied at the AGC's spot for them as well; SSQL's detector reads amplitude, so it needs the gain too)
+    bool fix_before() const
+    {
+        return agc_run && agc_mode == 0 && ((bp1_run && bp1_pos) || (lms[0].run && lms[0].position) || (lms[1].run && lms[1].position) ||
+                                            (emnr_run && emnr_pos) || ap_on() || ssql_on());
+    }
+};
+
+struct Engine {
+    int device = 0, nch = 0, dsp_size = 0, in_rate = 0, dsp_rate = 0, out_rate = 0;
+    int D = 1, dsp_insize = 0, dsp_outsize = 0, front_fold = 1, front_pick = 1;
+    unsigned long long epoch = 0;       // bumped by every setter / flush: a captured launch sequence is stale when it moves
+    // Launch-sequence replay (qh_rxa_set_graph_replay): a process() call whose arguments and parameters repeat is
+    // captured into a hipGraph, one per state of the ping-pong history flags, and replayed.  Everything the host
+    // side of process() changes from call to call is those flags, so a slot also records the flags it leaves behind.
+    struct GraphKey {
+        const void *in = nullptr; void *out = nullptr; long long in_stride = 0, out_stride = 0; int nblk = 0;
+        unsigned long long epoch = ~0ull;
+        bool operator==(const GraphKey &o) const
+        { return in == o.in && out == o.out && in_stride == o.in_stride && out_stride == o.out_stride && nblk == o.nblk && epoch == o.epoch; }
+    };
+    struct GraphSlot { hipGraphExec_t exec = nullptr; unsigned after = 0; };
+    bool graph_on = false, graph_seen = false;
+    GraphKey graph_key;
+    GraphSlot graph_slot[64];
+    long long graph_launches = 0;
+    hipStream_t stream = nullptr;
+    bool own_stream = false;
+    // the AM / SAM detectors of a call run beside the FM detector chain: other channels' rows, other state (process_chain)
+    hipStream_t side_stream = nullptr;
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    std::vector<ChanCfg> cfg;
+    // front (resampler) design
+    int front_ntaps = 0, front_P = 0, front_L = 0;
+    // device state
+    double2 *mask_front = nullptr, *mask_nbp = nullptr, *mask_bp1 = nullptr;
+    double2 *tw4096 = nullptr, *tw_inv_front = nullptr, *tw8192 = nullptr;
+    int bnfft = kNfft;                      // tile size of the fircore stages: what their masks are built for (4096 or 8192)
+    bool band2g = false;                    // 8192-point tiles shared by two lane groups (osfir8k_kernel): masks stored [even | odd]
+    bool band6k = false;                    // 6144-point tiles on 384 lanes (osfir6k_kernel)
+    int dbg_forms = [] { const char *e = std::getenv("QH_DBG_FORMS"); return e ? std::atoi(e) : 0; }();   // see process_chain
+    int band_tile_pref = 0;                 // qh_rxa_set_band_tile: 0 / 4096: 4096-point tiles, 8192: the two-group tiles
+    std::vector<cd> band_mask(const std::vector<cd> &h) const;
+    unsigned long long *nco_phase = nullptr, *nco_dphase = nullptr, *nco_parked = nullptr;
+    double2 *nco_step = nullptr;
+    // output-side oscillator of the front stage (D > 1): per-channel lane table, per-launch tile table, the resampler taps,
+    // and the scratch lists of refresh_params (channel list, new phase law)
+    double2 *lane_rot = nullptr, *tile_rot = nullptr;
+    long long tile_rot_cap = 0;             // tiles per channel
+    double *front_taps = nullptr;
+    int *retune_list = nullptr;
+    unsigned long long *retune_law = nullptr;
+    EpiParam *epi = nullptr;
+    double2 *hist_front[2] = { nullptr, nullptr }, *hist_nbp[2] = { nullptr, nullptr }, *hist_bp1[2] = { nullptr, nullptr };
+    int cur_front = 0, cur_nbp = 0, cur_bp1 = 0, cur_snb = 0;
+    double2 *mask_snb = nullptr, *hist_snb[2] = { nullptr, nullptr };
+    double2 *buf[2] = { nullptr, nullptr };
+    long long buf_cap = 0;                  // complex samples per channel
+    // long impulse responses (nc > 4096), per fircore stage s = 0 nbp0, 1 bp1, 2 FM de-emphasis, 3 FM audio filter, 4 bpsnba:
+    // long_parts[s] partitions (1: the ordinary path), their masks lmask[s] ([nch or 1][kLongParts][8192]), how many of them each mask row's
+    // own impulse response reaches lrow_parts[s] ([nch or 1]), the stage's last kLongHist input samples lhist[s][ping-pong][nch][kLongHist];
+    // lcat: history + block of the stage being run, ltmp: a partition's output
+    int long_parts[5] = { 1, 1, 1, 1, 1 };
+    double2 *lmask[5] = { nullptr, nullptr, nullptr, nullptr, nullptr };
+    int *lrow_parts[5] = { nullptr, nullptr, nullptr, nullptr, nullptr };
+    double2 *lhist[5][2] = { { nullptr, nullptr }, { nullptr, nullptr }, { nullptr, nullptr }, { nullptr, nullptr }, { nullptr, nullptr } };
+    double2 *lcat = nullptr, *ltmp = nullptr;
+    long long lcat_cap = 0;                 // the buf_cap they were made for
+    int long_stage_alloc(int sid, bool shared_mask);
+    int long_buffers();
+    int long_masks_upload(int sid, long long row, const std::vector<cd> &h);
+    // Every device buffer the engine owns, by its address, and its size in bytes: alloc() enters it, ~Engine frees it, dev_bytes()
+    // adds them up (the qh_rat resamplers hold their own)
+    std::map<void *, long long> owned;
+    long long dev_bytes() const { long long b = 0; for (const auto &o : owned) b += o.second; return b; }
+    // timing
+    bool timing = false;
+    std::vector<hipEvent_t> ev;
+    std::vector<int> ev_cat;
+    int ev_used = 0;
+    double last_ms[3] = { 0, 0, 0 };
+
+    // demodulators (allocated on first use)
+    bool demod_alloc = false, lists_dirty = true;
+    // The channel lists of the mixed-mode chain, one device block for all of them (build_lists): every list has nch slots, the
+    // pair lists 2 nch.  [L_LMS + 3 f + k]: anf (f = 0) / anr (f = 1) at position 0 (k = 0, always in `cur`) or at position 1 with
+    // the data in cur (k = 1: bp1 still to come or not running) or in other (k = 2: bp1 ran at position 0); L_EMNR likewise.
+    // [L_BP1P + p]: bp1 at position p.  [L_FIX + b], [L_AP + b], [L_AGC_CUR / OTHER]: by the buffer (0 cur, 1 other) that holds the
+    // channel at that stage.  [L_SNB + p]: bpsnba at position p.
+    enum ListId {
+        L_AM, L_SAM, L_FM, L_BP1, L_PLAIN, L_AGC_CUR, L_AGC_OTHER, L_LMS, L_BP1P = L_LMS + 6, L_FIX = L_BP1P + 2, L_AMSQ = L_FIX + 2, L_EMNR,
+        L_SNB = L_EMNR + 3, L_SNBA = L_SNB + 2,
+        L_REST,             // the channels that are not FM (the mixed-mode path runs the two kinds on two streams) ...
+        L_USB, L_RB,        // ... those of them without / with a bp1 stage
+        L_LIM, L_AP, L_PAIRS_FM = L_AP + 2, L_PAIRS_AM, L_PAIRS_SAM, L_COUNT
+    };
+    struct ChanList { int *dev = nullptr; int n = 0; };
+    ChanList lists[L_COUNT];
+    int *list_block = nullptr;
+    // channel pairs for the real filters behind the detectors (osfir_kernel PAIR): FM de-emphasis (one mask for all), bp1 of the AM
+    // and of the SAM channels (partners have the same design; count 0 when a channel of the kind has complex taps)
+    int np_fm = 0, np_am = 0, np_sam = 0;
+    bool de_real = false;
+    bool all_nbp = false;
+    int n_sam0 = 0;                         // the first n_sam0 entries of lists[L_SAM] have sbmode 0 (no all-pass chains): time-tiled in long calls
+    // xwcpagc mode 0 ahead of a position-1 anf / anr / bp1: the fixed gain does not commute with what follows when it
+    // changes, so it is applied where the reference applies it (lists[L_FIX + b])
+    double *fix_gain = nullptr;
+    // xcbl / xspeak / xmpeak (qh_audio_peak.hpp), made when a channel first runs one of them: parameters, state [nch][kApW], the carry
+    // matrices T = A^ap_L [nch][kApDim^2] and the tiles' end / start states [nch][ap_ends_cap][kApW]
+    ApParam *ap_prm = nullptr;
+    double *ap_state = nullptr, *ap_M = nullptr, *ap_ends = nullptr;
+    long long ap_ends_cap = 0;
+    int ap_L = 0;
+    std::vector<double> ap_M_h;
+    std::vector<ApParam> ap_prm_h;
+    int ap_alloc();
+    // xssql (qh_ssql.hpp), made when a channel first runs it: its two channel lists (by the buffer that holds the row, as L_AP; a
+    // block of their own, so that an engine without SSQL allocates what it did before), parameters, state, the ramps, the tiles' rows
+    // [nch][ssql_ends_cap][kSsE], the crossing / window / trigger bits [3][nch][ssql_wcap] and the words' machine records [nch][ssql_wcap]
+    ChanList ssql_lists[2];
+    std::vector<int> ssql_h[2];
+    int *ssql_list_block = nullptr;
+    SsqlParam *ssql_prm = nullptr;
+    SsqlState *ssql_state = nullptr;
+    double *ssql_cup = nullptr, *ssql_cdown = nullptr, *ssql_ends = nullptr;
+    unsigned long long *ssql_bits = nullptr;
+    int *ssql_rec = nullptr;
+    long long ssql_ends_cap = 0, ssql_wcap = 0, ssql_rec_cap = 0;
+    int ssql_L = 0, ssql_ntup = 0, ssql_ntdown = 0;
+    std::vector<SsqlParam> ssql_prm_h;
+    int ssql_alloc();
+    bool ssql_listed() const { return ssql_lists[0].n || ssql_lists[1].n; }
+    // snba: the blanker's parameters, taps, state and the Toeplitz-inverse scratch
+    SnbaParam snba_prm{};
+    double *snba_state = nullptr, *snba_hin = nullptr, *snba_hout = nullptr, *snba_scratch = nullptr;
+    SnbaIdx *snba_idx = nullptr;
+    SnbaTune *snba_tune = nullptr;          // [nch]; host copy below, uploaded when a tuning setter has run
+    std::vector<SnbaTune> snba_tune_h;
+    bool snba_tune_dirty = true;
+    std::vector<char> snb_listed, fm_listed, bp1_listed;
+    int snba_alloc();
+    int snba_ovrlp = 4;                 // create_rxa's overlap (RXA.c:244): incr = xsize / 4
+    void snba_plan(int ovrlp);
+    int snba_set_ovrlp(int ovrlp);
+    EmnrParam emnr_prm{};
+    EmnrChan *emnr_chan = nullptr;
+    EmnrScalars *emnr_scal = nullptr;
+    double *emnr_state = nullptr, *emnr_window = nullptr, *emnr_GG = nullptr, *emnr_GGS = nullptr, *emnr_zeta = nullptr;
+    int *emnr_zeta_true = nullptr;
+    bool emnr_tables = false;
+    std::vector<double> h_GG, h_GGS, h_zeta; std::vector<int> h_zeta_true; double h_zrange[4] = { 0, 0, 0, 0 };
+    AmsqParam *amsq_prm = nullptr;
+    AmsqState *amsq_state = nullptr;
+    double *amsq_cup = nullptr, *amsq_cdown = nullptr, *amsq_mag = nullptr;
+    long long amsq_mag_cap = 0;
+    int amsq_ntup = 0, amsq_ntdown = 0;
+    LmsParam *lms_prm[2] = { nullptr, nullptr };
+    LmsState *lms_state[2] = { nullptr, nullptr };
+    int *levelfade = nullptr;
+    AmState *am_state = nullptr;
+    // carries of the grid-segmented scans (qh_tiled.hpp: a launch reads the state of its channels and leaves the new one here; a
+    // commit kernel behind it moves it in): [nch] each
+    AmState *am_next = nullptr;
+    SnotchState *sn_next = nullptr;
+    double *fmdc_next = nullptr;
+    double *fm_cin = nullptr, *fm_pw = nullptr;       // xfmd's dc removal taken in the de-emphasis stage's load: fmdc ahead of every tile, mtau^(k + 1)
+    long long fm_cin_cap = 0;
+    struct FmDcSrc { const double *a; long long stride; int shift; } ;
+    const FmDcSrc *band_fmdc = nullptr;               // set around the run_band call of that stage
+    double *am_cin = nullptr, *am_pw = nullptr, *am_last = nullptr;      // the fade leveller's carried share taken in bp1's load (osfir_kernel DET 3)
+    long long am_cin_cap = 0;
+    const FmDcSrc *band_amlv = nullptr;
+    AmParam am_prm{};
+    PllState *pll_state = nullptr;          // the SAM detector's loop (amd.c) ...
+    PllState *fm_pll_state = nullptr;       // ... and the FM detector's (fmd.c): two objects in the reference, each keeps its state while the other runs
+    double *fm_again = nullptr;
+    // time-tiled FM loop (qh_tiled.hpp): per tile the loop state where its warm-up and where the tile ends, and the count of
+    // tiles pll_verify_kernel had to re-run
+    double *pll_ends = nullptr;
+    long long pll_ends_cap = 0;             // tiles per channel
+    double *am_tsum = nullptr;              // [nch][am_tsum_cap][2]: the AM nbp0 tiles' contributions to the fade leveller (osfir_kernel DET 2)
+    long long am_tsum_cap = 0;
+    double *seg_sum[3] = { nullptr, nullptr, nullptr };     // segment summaries of the multi-workgroup scans: AM / SAM, (unused), snotch
+    int *pll_nfixed = nullptr;
+    // xwcpagc in time tiles (qh_agc_tiled.hpp): streams RM / fba / hba / volts per listed channel, the tiles' halos, the last samples
+    // of the rows, the lanes' states, the final states, tiles re-run
+    double *agc_scr = nullptr, *agc_ends = nullptr, *agc_fin = nullptr, *agc_sege = nullptr, *agc_tsum = nullptr;
+    double2 *agc_halo = nullptr, *agc_tail = nullptr;
+    long long agc_arr = 0, agc_ends_cap = 0, agc_halo_cap = 0;
+    int *agc_nfixed = nullptr;
+    // SAM sideband modes over time segments (qh_tiled.hpp, sam_sb_*): the chains' transition matrices for the two segment lengths of
+    // the current call shape, the segments' zero-state end states and their start states
+    double *sb_phi = nullptr, *sb_sum = nullptr, *sb_start = nullptr;
+    long long sb_phi_key = -1;
+    int set_sb_phi(long long n, int S);
+    int pll_check_only = 0;                 // diagnostics (qh_rxa_debug_pll): count unconverged tiles without re-running them
+    int agc_form = 0;                       // diagnostics (qh_rxa_debug_agc): 1 = the sample-by-sample form of the wcpAGC loop
+    SamChanParam *sam_prm = nullptr;
+    PllParam sam_pll_prm{}, fm_pll_prm{};
+    SnotchParam *sn_prm = nullptr;
+    SnotchState *sn_state = nullptr;
+    double2 *mask_de = nullptr, *mask_aud = nullptr, *hist_de[2] = { nullptr, nullptr }, *hist_aud[2] = { nullptr, nullptr };
+    int cur_de = 0, cur_aud = 0, fm_nc_built = 0, fm_mp = 0, fm_mp_built = 0, fm_nfft_built = 0;
+    unsigned flags() const { return (unsigned)(cur_front | cur_nbp << 1 | cur_bp1 << 2 | cur_de << 3 | cur_aud << 4 | cur_snb << 5); }
+    void set_flags(unsigned f) { cur_front = f & 1; cur_nbp = f >> 1 & 1; cur_bp1 = f >> 2 & 1; cur_de = f >> 3 & 1; cur_aud = f >> 4 & 1; cur_snb = f >> 5 & 1; }
+    void drop_graphs() { for (auto &g : graph_slot) if (g.exec) { (void)hipGraphExecDestroy(g.exec); g.exec = nullptr; } }
+    // Growing, rebuilding or re-uploading a device buffer: captured launch sequences hold its address and launches queued on either
+    // stream may still use it, so nothing is freed or rewritten before quiesce() has waited for both streams and dropped the captures.
+    int quiesce();
+    // (Re)allocate p for n elements (dev_alloc), zeroed on `stream` when asked.  A buffer p held is freed first: the caller has quiesced.
+    template <typename T> int alloc(T *&p, long long n, bool zero = false);
+    // p holds cap units of `unit` elements: when need is more, quiesce and reallocate it for need units
+    template <typename T> int grow(T *&p, long long &cap, long long need, long long unit);
+    int process_replayed(const double *d_in, long long in_stride, double *d_out, long long out_stride, int nblk);
+    AgcParam *agc_prm = nullptr;
+    AgcState *agc_state = nullptr;
+    // xwcpagc's ring in full (RB_SIZE entries per channel, qh_demod.hpp: agc_long_mirror_kernel), made when a state machine first runs
+    double2 *agc_lring = nullptr;
+    double *agc_labs = nullptr;
+    int *agc_lout = nullptr, *agc_rewin_list = nullptr;
+    AgcParam *lim_prm = nullptr;        // FM detector limiter: a wcpAGC of its own (fmd.c:48-72)
+    AgcState *lim_state = nullptr;
+    bool meters_on = false;
+    MeterState *m_adc = nullptr, *m_s = nullptr, *m_agc = nullptr;
+    MeterParam m_prm{};
+    // meters fused into the nbp0 launch of the linear fast path (qh_osfir.hpp METER): chunk partials of the stage's input and
+    // output, the chunk weights, and g^2 of a fixed AGC gain that the output matrix applies behind the agc meter's tap
+    double2 *m_part[2] = { nullptr, nullptr };
+    long long m_part_cap = 0;               // chunks per channel
+    double *m_w = nullptr, *m_g2 = nullptr;
+    int meters_alloc();
+    int agc_last_tiled = 0;             // channels whose xwcpagc took the time tiles in the last call (diagnostics)
+    int n_agc_cur_stale = 0, n_agc_other_stale = 0;     // ... of which, at the lists' ends, channels whose attack window moved in mid-stream
+
+    ~Engine();
+    int init();
+    int flush();
+    // what the parameter side needs of the kernels, defined where they are launched from (qh_engine.hip): the dynamic-LDS limits of the
+    // tile kernels and of emnr_kernel, and the launches of refresh_params and flush
+    int tile_lds_limits();
+    int emnr_lds_limit();
+    void launch_nco_retune(int n);
+    void launch_nco_park(int ch, int run);
+    void launch_front_masks(int n);
+    void launch_ssql_flush();
+    int refresh_params();
+    std::vector<cd> notched(const ChanCfg &c, double f_low, double f_high, double scale) const;
+    int snb_mask(ChanCfg &c, int ch);
+    int put_mask(double2 *mask, int ch, const std::vector<cd> &m);
+    // refresh_demod and its steps
+    int refresh_demod();
+    int demod_init();
+    void build_lists(std::vector<int> (&h)[L_COUNT]);
+    int stages_alloc();
+    int refresh_lists();
+    struct Rows { double2 **h; int cur; int len; };     // a fircore's ping-pong delay lines, the half current for them, the row length
+    int follow_rows(std::vector<char> &listed, int ChanCfg::*at, int cur, const std::vector<int> &chans, std::initializer_list<Rows> rows);
+    int zero_rows(double2 *const h[2], double2 *const lh[2], int ch, int n = 1);
+    int prm_agc(ChanCfg &c, int ch);
+    int prm_emnr(ChanCfg &c, int ch);
+    int prm_snba(ChanCfg &c, int ch);
+    int prm_amsq(ChanCfg &c, int ch);
+    int prm_lms(ChanCfg &c, int ch);
+    int prm_lim(ChanCfg &c, int ch);
+    int prm_detect(ChanCfg &c, int ch);
+    int fm_filters(int want_nc);
+    // v -> dev[row] on `stream`, then a wait unless told not to (a caller that does not wait keeps v alive until it does)
+    template <typename T> int put_row(T *dev, long long row, const T &v, bool wait = true)
+    {
+        QH_HIP(hipMemcpyAsync(dev + row, &v, sizeof(T), hipMemcpyHostToDevice, stream));
+        if (wait) QH_HIP(hipStreamSynchronize(stream));
+        return QH_OK;
+    }
+    int run_front(const double2 *src, long long src_stride, double2 *dst, long long dst_stride, const EpiParam *ep,
+                  long long n_in, long long n_mid, const int *list = nullptr, int nlist = 0, int part = 0);
+    const unsigned char *pk_src = nullptr;      // set for the duration of a qh_rxa_process_packed call
+    PackedFmt pk{};
+    EgressFmt eg{};                             // set (kind != 0) for the duration of a qh_rxa_process_audio call
+    double2 *abuf = nullptr;                    // complex-double staging of an audio call whose last stage cannot narrow in its store
+    long long abuf_cap = 0;
+    int ensure_abuf(long long n);
+    void pack_audio(const double2 *src, long long src_stride, long long n);
+    void run_band(const double2 *src, long long src_stride, double2 *dst, long long dst_stride, const EpiParam *ep,
+                  long long n_mid, const double2 *mask, long long mask_stride, double2 **hist, int &hc, int P,
+                  const int *list, int nlist, bool meter = false, bool egress = false, int det = 0, double *det_out = nullptr,
+                  long long det_stride = 0, const int *pairs = nullptr, int npairs = 0);
+    int ensure_buffers(long long n_mid);
+    int ensure_meter_partials(long long n_mid, int lout);
+    int emnr_alloc();
+    int process(const double *d_in, long long in_stride, double *d_out, long long out_stride, int nblk);
+    int process_chain(const double *d_in, long long in_stride, double *d_out, long long out_stride, int nblk);
+    // One process_chain call: its sizes and rows, and the form every stage takes, each decided once where it is set below
+    struct ChainCall {
+        int nblk = 0, nc_max = 1, P = 0, P_am = 0;
+        long long n_in = 0, n_mid = 0;
+        const double2 *in = nullptr;
+        long long in_stride = 0, out_stride = 0;
+        double2 *out = nullptr;
+        double2 *cur = nullptr, *other = nullptr;       // the mixed path's working rows (buf[0] / buf[1], swapped as stages write)
+        bool any_nbp = false, any_bp1 = false, every_nbp = true, mixed = false, long_mode = false, meters_fused = false, eg_fused = false;
+        bool split = false, fm_theta_fused = false, direct = false, am_fused = false, am_lv_fused = false, side = false;
+        bool agc_direct = false;                        // set where xwcpagc runs (run_agc)
+    };
+    int chain_needs(ChainCall &k);
+    int plan_long(ChainCall &k);
+    void pick_band_tile(int nc_max);
+    int run_linear(ChainCall &k);
+    int plan_mixed(ChainCall &k);
+    int ensure_side_stream();
+    int fork_side();
+    int run_mixed_front(ChainCall &k);
+    int seg_groups(int count, long long n_mid) const;
+    template <bool SAM> void am_detect(const ChainCall &k, hipStream_t s, const int *list, int n, int G, const double *pts, long long pts_stride, double *gs);
+    int run_am(ChainCall &k);
+    int run_fm(ChainCall &k);
+    void snb_inplace(const ChainCall &k, const int *list, int n);
+    int run_snba(const ChainCall &k);
+    void lms_at(const ChainCall &k, int pos, double2 *b);
+    void bp1_at(const ChainCall &k, int pos);
+    int run_agc(ChainCall &k);
+    int refresh_ap(const ChainCall &k);
+    void run_audio_peak(const ChainCall &k);
+    int refresh_ssql(const ChainCall &k);
+    void run_ssql(const ChainCall &k);
+    void run_output(const ChainCall &k);
+    qh_rat *rsmpout = nullptr;          // xresample out (wdsp/RXA.c:596), only when out_rate != dsp_rate
+    qh_rat *rsmpin = nullptr;           // xresample in for the rate ratios the overlap-save front stage does not cover (D == 0)
+    double2 *fbuf = nullptr;            // its input: the shifted samples at in_rate
+    long long fbuf_cap = 0;
+    double2 *obuf = nullptr;
+    long long obuf_cap = 0;
+    void tick(int cat);
+};
+
+// egress_pack_kernel over nch rows of n samples (Engine::pack_audio, qh_audio_pack)
+void launch_egress_pack(const double2 *src, long long src_stride, int nch, long long n, const EgressFmt &f, hipStream_t s);
+
+template <typename T> int Engine::alloc(T *&p, long long n, bool zero)
+{
+    if (p) { QH_HIP(hipFree(p)); owned.erase(p); p = nullptr; }
+    QH_HIP(dev_alloc(&p, (size_t)n));
+    owned[p] = n * (long long)sizeof(T);
+    if (zero) QH_HIP(hipMemsetAsync(p, 0, (size_t)n * sizeof(T), stream));
+    return QH_OK;
+}
+
+template <typename T> int Engine::grow(T *&p, long long &cap, long long need, long long unit)
+{
+    if (need <= cap) return QH_OK;
+    if (int rc = quiesce()) return rc;
+    if (int rc = alloc(p, need * unit)) return rc;
+    cap = need;
+    return QH_OK;
+}
+
+}  // namespace qh
+
+// One lock per engine: setters may come from another thread than the one that runs the blocks (Quisk's GUI thread against its
+// sound thread; WDSP's setters take csDSP).  A setter only edits the host-side configuration and marks it dirty; the next
+// process call uploads what changed before it enqueues the block, so parameters swap on a block boundary.
+struct qh_rxa { qh::Engine e; std::recursive_mutex mtx; };
+#define QH_RXA_LOCK(h) std::lock_guard<std::recursive_mutex> _lk((h)->mtx)

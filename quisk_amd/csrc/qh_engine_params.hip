@@ -1,0 +1,1388 @@
+// qh_engine_params.hip -- the parameter side of the RXA engine (qh_engine.hpp): what runs when a setter has marked something dirty or a
+// stage is first used -- filter designs, masks, channel lists, per-channel parameter rows, first-use allocation, buffer growth, flush.
+// Host code only: the few kernels that rewrite state for new parameters (oscillator retune, front masks, SSQL flush) are launched through
+// Engine::launch_* of qh_engine.hip, so this unit's object holds no device code.  No ABI function lives here (qh_rxa_api.hip).
+#include "qh_engine.hpp"
+
+namespace qh {
+
+thread_local std::string g_last_error;
+
+int set_error(int code, const char *fmt, ...)
+{
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof(buf), fmt, ap);
+    va_end(ap);
+    g_last_error = buf;
+    return code;
+}
+
+Engine::~Engine()
+{
+    (void)hipSetDevice(device);
+    if (stream) (void)hipStreamSynchronize(stream);
+    drop_graphs();
+    if (rsmpout) qh_rat_destroy(rsmpout);
+    if (rsmpin) qh_rat_destroy(rsmpin);
+    for (const auto &o : owned) (void)hipFree(o.first);
+    for (auto e : ev) (void)hipEventDestroy(e);
+    if (side_stream) (void)hipStreamDestroy(side_stream);
+    if (ev_fork) (void)hipEventDestroy(ev_fork);
+    if (ev_join) (void)hipEventDestroy(ev_join);
+    if (own_stream && stream) (void)hipStreamDestroy(stream);
+}
+
+static int upload(double2 *dst, const std::vector<cd> &v, hipStream_t s)
+{
+    QH_HIP(hipMemcpyAsync(dst, v.data(), v.size() * sizeof(cd), hipMemcpyHostToDevice, s));
+    QH_HIP(hipStreamSynchronize(s));        // the host vector dies with the caller's scope
+    return QH_OK;
+}
+
+int Engine::quiesce()
+{
+    QH_HIP(hipStreamSynchronize(stream));
+    if (side_stream) QH_HIP(hipStreamSynchronize(side_stream));
+    drop_graphs(); epoch++;
+    return QH_OK;
+}
+
+int Engine::init()
+{
+    QH_HIP(hipSetDevice(device));
+    if (!stream) { QH_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking)); own_stream = true; }
+    // pre_main_build, wdsp/channel.c:39-47
+    dsp_insize = D > 0 ? dsp_size * D : (int)((long long)dsp_size * in_rate / dsp_rate);
+    if (D == 0) {
+        // create_resample(..., in_rate, dsp_rate, 0.0, 0, 1.0), wdsp/RXA.c:48-57
+        const ResamplerDesign rd = design_resampler(in_rate, dsp_rate, 0.0, 0, 1.0);
+        std::vector<double> taps(rd.h);
+        for (double &v : taps) v /= (double)rd.L;           // qh_rat applies the gain `interp` itself (quisk_cInterpDecim's convention)
+        rsmpin = qh_rat_create(device, nch, taps.data(), rd.ncoef, rd.L, rd.M, QH_F64, stream);
+        if (!rsmpin) return QH_ERR_HIP;
+    }
+    dsp_outsize = out_rate >= dsp_rate ? dsp_size * (out_rate / dsp_rate) : dsp_size / (dsp_rate / out_rate);    // channel.c:47-50
+    if (out_rate != dsp_rate) {
+        // create_resample(..., dsp_rate, out_rate, 0.0, 0, 1.0), wdsp/RXA.c:474-484; the polyphase loop of xresample
+        // (resample.c:120-157) is quisk_cInterpDecim's with the gain already in the taps
+        const ResamplerDesign rd = design_resampler(dsp_rate, out_rate, 0.0, 0, 1.0);
+        std::vector<double> taps(rd.h);
+        for (double &v : taps) v /= (double)rd.L;
+        rsmpout = qh_rat_create(device, nch, taps.data(), rd.ncoef, rd.L, rd.M, QH_F64, stream);
+        if (!rsmpout) return QH_ERR_HIP;
+    }
+    cfg.assign((size_t)nch, ChanCfg());
+    snba_tune_h.assign((size_t)nch, SnbaTune{ 64, 2, 10, 2, 2, 0, 8.0, 20.0, 0.5 });         // create_snba's arguments, RXA.c:183-202
+
+    std::vector<cd> tw = fft_twiddle_table(kNfft);
+    if (int rc = alloc(tw4096, (long long)tw.size())) return rc;
+    if (int rc = upload(tw4096, tw, stream)) return rc;
+    tw = fft_twiddle_table(kBandNfftMax);
+    if (int rc = alloc(tw8192, (long long)tw.size())) return rc;
+    if (int rc = upload(tw8192, tw, stream)) return rc;
+
+    if (D > 1) {
+        // calc_resample, wdsp/resample.c:35-72 (L = 1): y[m] = sum_j h[j] x[D*m - j]
+        ResamplerDesign rd = design_resampler(in_rate, dsp_rate, 0.0, 0, 1.0);
+        if (rd.L != 1 || rd.M != D) return set_error(QH_ERR_UNSUPPORTED, "resampler L/M = %d/%d not supported", rd.L, rd.M);
+        front_ntaps = rd.ncoef;
+        // spectral fold by min(D, 8); the rest of the decimation (D = 16) keeps every second folded sample
+        front_fold = D > 8 ? 8 : D;
+        front_pick = D / front_fold;
+        front_P = ((front_ntaps - 1 + front_fold - 1) / front_fold) * front_fold;
+        front_L = (((kNfft - front_P) / front_fold) / front_pick) * front_pick;
+        if (front_P > kHistFront) return set_error(QH_ERR_UNSUPPORTED, "resampler history %d too long", front_P);
+        // the masks are per channel (taps modulated by the channel's shift): front_mask_kernel builds them in refresh_params
+        if (int rc = alloc(mask_front, (long long)nch * kNfft)) return rc;
+        if (int rc = alloc(lane_rot, (long long)nch * NT)) return rc;
+        if (int rc = alloc(front_taps, front_ntaps)) return rc;
+        if (int rc = alloc(retune_list, nch)) return rc;
+        if (int rc = alloc(retune_law, 2LL * nch)) return rc;
+        QH_HIP(hipMemcpyAsync(front_taps, rd.h.data(), (size_t)front_ntaps * sizeof(double), hipMemcpyHostToDevice, stream));
+        QH_HIP(hipStreamSynchronize(stream));
+        std::vector<cd> twi = fft_twiddle_table(kNfft / front_fold);
+        if (int rc = alloc(tw_inv_front, (long long)twi.size())) return rc;
+        if (int rc = upload(tw_inv_front, twi, stream)) return rc;
+        for (double2 *&h : hist_front) if (int rc = alloc(h, (long long)nch * kHistFront, true)) return rc;
+    }
+    if (int rc = alloc(mask_nbp, (long long)nch * kBandNfftMax)) return rc;
+    if (int rc = alloc(mask_bp1, (long long)nch * kBandNfftMax)) return rc;
+    for (int i = 0; i < 2; i++) {
+        if (int rc = alloc(hist_nbp[i], (long long)nch * kHistBand, true)) return rc;
+        if (int rc = alloc(hist_bp1[i], (long long)nch * kHistBand, true)) return rc;
+    }
+    if (int rc = alloc(nco_phase, nch, true)) return rc;
+    if (int rc = alloc(nco_dphase, nch, true)) return rc;
+    if (int rc = alloc(nco_parked, nch, true)) return rc;
+    if (int rc = alloc(nco_step, nch)) return rc;
+    if (int rc = alloc(epi, nch)) return rc;
+
+    if (int rc = tile_lds_limits()) return rc;
+    QH_HIP(hipStreamSynchronize(stream));
+    return QH_OK;
+}
+
+// fixed-point turns for a frequency ratio f / rate
+static unsigned long long turns_fx(double f, double rate)
+{
+    long double t = (long double)f / (long double)rate;
+    t -= floorl(t);
+    long double s = t * 18446744073709551616.0L;
+    if (s >= 18446744073709551616.0L) s = 0;
+    return (unsigned long long)s;
+}
+
+int Engine::refresh_params()
+{
+    // one pass over the channels; upload only what changed
+    std::vector<cd> last_nbp, last_bp1, last_nbp_h, last_bp1_h;      // masks and impulse responses of the last design made
+    const ChanCfg *last_nbp_cfg = nullptr, *last_bp1_cfg = nullptr;
+    // Oscillator changes (SetRXAShiftFreq / SetRXAShiftRun).  With a front FIR stage (D > 1) the oscillator sits behind
+    // the filter: first the stored raw history of every changed channel is re-expressed for its new phase law (the kernel
+    // reads the old law from the device arrays, so it goes first), then the arrays are updated, then the channel's
+    // modulated mask and phasor tables are rebuilt.
+    std::vector<int> nco_list;
+    if (D > 1) {
+        std::vector<unsigned long long> law;
+        for (int ch = 0; ch < nch; ch++) {
+            const ChanCfg &c = cfg[(size_t)ch];
+            if (!c.nco_dirty) continue;
+            nco_list.push_back(ch);
+            const bool flip = (c.shift_run != 0) != (c.shift_on_device != 0);
+            law.push_back(flip ? (c.shift_run ? 2ull : 1ull) : 0ull);
+            law.push_back(c.shift_run ? turns_fx(c.shift_freq, (double)in_rate) : 0ull);
+        }
+        if (!nco_list.empty()) {
+            QH_HIP(hipMemcpyAsync(retune_list, nco_list.data(), nco_list.size() * sizeof(int), hipMemcpyHostToDevice, stream));
+            QH_HIP(hipMemcpyAsync(retune_law, law.data(), law.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, stream));
+            launch_nco_retune((int)nco_list.size());
+            QH_HIP(hipStreamSynchronize(stream));           // the host vectors die with this scope
+        }
+    }
+    for (int ch = 0; ch < nch; ch++) {
+        ChanCfg &c = cfg[(size_t)ch];
+        if (c.nco_dirty) {
+            if ((c.shift_run != 0) != (c.shift_on_device != 0)) {
+                launch_nco_park(ch, c.shift_run ? 1 : 0);
+                c.shift_on_device = c.shift_run ? 1 : 0;
+            }
+            // calc_shift, wdsp/shift.c:29-34: delta = 2*pi*shift/rate per input sample
+            if (int rc = put_row(nco_dphase, ch, c.shift_run ? turns_fx(c.shift_freq, (double)in_rate) : 0ull)) return rc;
+            c.nco_dirty = false;
+        }
+        if (c.epi_dirty) {
+            // xwcpagc mode 0 (wcpAGC.c:167-175) then xpanel (patchpanel.c:55-101) as one 2x2 real matrix
+            // (with a position-1 anf / anr / bp1 behind it the gain is applied at the AGC's own spot instead: fix_before)
+            const double g = (c.agc_run && c.agc_mode == 0 && !c.fix_before()) ? c.agc_fixed : 1.0;
+            const double g2 = g * g;            // the agc meter reads |g z|^2 off the signal ahead of the output matrix
+            if (m_g2) if (int rc = put_row(m_g2, ch, g2, false)) return rc;
+            if (fix_gain) if (int rc = put_row(fix_gain, ch, c.agc_fixed, false)) return rc;
+            const double gI = c.gain1 * c.gain2I, gQ = c.gain1 * c.gain2Q;
+            const double sI = (double)(c.inselect >> 1), sQ = (double)(c.inselect & 1);
+            EpiParam e;
+            switch (c.copy) {
+            default:
+            case 0: e.a = gI * sI * g; e.b = 0; e.c = 0; e.d = gQ * sQ * g; break;
+            case 1: e.a = gI * sI * g; e.b = 0; e.c = gQ * sI * g; e.d = 0; break;
+            case 2: e.a = 0; e.b = gI * sQ * g; e.c = 0; e.d = gQ * sQ * g; break;
+            case 3: e.a = 0; e.b = gI * sQ * g; e.c = gQ * sI * g; e.d = 0; break;
+            }
+            if (int rc = put_row(epi, ch, e)) return rc;
+            c.epi_dirty = false;
+        }
+        if (c.nbp_dirty) c.snb_dirty = true;        // bpsnba's nbp shares nc, window, auto-increase, mp and the notch database with nbp0
+        if (c.snb_dirty && c.snba_run && mask_snb) if (int rc = snb_mask(c, ch)) return rc;
+        if (c.snb_flush && hist_snb[0]) if (int rc = zero_rows(hist_snb, lhist[4], ch)) return rc;         // setNc_fircore zeroes the delay line
+        c.snb_flush = false;
+        if (c.nbp_dirty) {
+            // calc_nbp_impulse without notches, wdsp/nbp.c:234-238; identity when the filter is off
+            bool same = !c.fnfrun && last_nbp_cfg && !last_nbp_cfg->fnfrun && last_nbp_cfg->nbp_run == c.nbp_run && last_nbp_cfg->nbp_nc == c.nbp_nc &&
+                        last_nbp_cfg->nbp_wintype == c.nbp_wintype && last_nbp_cfg->nbp_flow == c.nbp_flow &&
+                        last_nbp_cfg->nbp_fhigh == c.nbp_fhigh && last_nbp_cfg->nbp_gain == c.nbp_gain && last_nbp_cfg->mp == c.mp;
+            if (!same) {
+                std::vector<cd> h;
+                if (c.nbp_run && c.fnfrun)
+                    h = notched(c, c.nbp_flow, c.nbp_fhigh, c.nbp_gain / (double)(2 * dsp_size));
+                else if (c.nbp_run)
+                    h = fir_bandpass(c.nbp_nc, c.nbp_flow, c.nbp_fhigh, (double)dsp_rate, c.nbp_wintype, 1,
+                                     c.nbp_gain / (double)(2 * dsp_size));
+                else
+                    h.assign(1, cd(1.0, 0.0));
+                if (c.nbp_run && c.mp) h = mp_imp(h, 16, 0);            // calc_fircore, wdsp/firmin.c:327-328
+                // the reference's unnormalised inverse FFT of 2*size points restores the 1/(2*size)
+                if (c.nbp_run) for (auto &v : h) v *= (double)(2 * dsp_size);
+                last_nbp_h = h;
+                if ((int)h.size() > kLongPart) h.resize((size_t)kLongPart);      // (the one-tile mask is not used then)
+                last_nbp = band_mask(h);
+                last_nbp_cfg = &c;
+            }
+            if (long_parts[0] > 1) if (int rc = long_masks_upload(0, ch, last_nbp_h)) return rc;
+            if (int rc = put_mask(mask_nbp, ch, last_nbp)) return rc;
+            c.nbp_dirty = false;
+        }
+        if (c.bp1_dirty) {
+            bool same = last_bp1_cfg && last_bp1_cfg->bp1_run == c.bp1_run && last_bp1_cfg->bp1_nc == c.bp1_nc &&
+                        last_bp1_cfg->bp1_wintype == c.bp1_wintype && last_bp1_cfg->bp1_flow == c.bp1_flow &&
+                        last_bp1_cfg->bp1_fhigh == c.bp1_fhigh && last_bp1_cfg->bp1_gain == c.bp1_gain && last_bp1_cfg->mp == c.mp;
+            if (!same) {
+                std::vector<cd> h;
+                if (c.bp1_run) {
+                    h = fir_bandpass(c.bp1_nc, c.bp1_flow, c.bp1_fhigh, (double)dsp_rate, c.bp1_wintype, 1,
+                                     c.bp1_gain / (double)(2 * dsp_size));     // wdsp/bandpass.c:302
+                    if (c.mp) h = mp_imp(h, 16, 0);
+                    for (auto &v : h) v *= (double)(2 * dsp_size);
+                } else {
+                    h.assign(1, cd(1.0, 0.0));
+                }
+                last_bp1_h = h;
+                if ((int)h.size() > kLongPart) h.resize((size_t)kLongPart);
+                last_bp1 = band_mask(h);
+                last_bp1_cfg = &c;
+            }
+            if (long_parts[1] > 1) if (int rc = long_masks_upload(1, ch, last_bp1_h)) return rc;
+            if (int rc = put_mask(mask_bp1, ch, last_bp1)) return rc;
+            c.bp1_dirty = false;
+            lists_dirty = true;             // the channel pairs of the real bp1 filters follow the designs
+        }
+        if (c.nbp_flush) {      // setNc_fircore re-plans and so zeroes the delay line
+            if (int rc = zero_rows(hist_nbp, lhist[0], ch)) return rc;
+            c.nbp_flush = false;
+        }
+        if (c.bp1_flush) {      // flush_bandpass on off->on (RXA.c:825) and setNc_fircore
+            if (int rc = zero_rows(hist_bp1, lhist[1], ch)) return rc;
+            c.bp1_flush = false;
+        }
+    }
+    if (!nco_list.empty())      // retune_list still holds the channels; the new dphase values are in place
+        launch_front_masks((int)nco_list.size());
+    return QH_OK;
+}
+
+// calc_nbp_impulse with the notches, wdsp/nbp.c:221-232: bands in absolute frequency, filter in baseband
+std::vector<cd> Engine::notched(const ChanCfg &c, double f_low, double f_high, double scale) const
+{
+    const double offset = c.ndb_tunefreq + c.ndb_shift;
+    const double minwidth = (c.nbp_wintype == 1 ? 2200.0 : 1600.0) / (c.nbp_nc / 256) * ((double)dsp_rate / 48000);
+    std::vector<std::pair<double, double>> bands = make_nbp(c.notches, minwidth, c.autoincr, f_low + offset, f_high + offset, nullptr);
+    for (auto &b : bands) { b.first -= offset; b.second -= offset; }
+    return fir_mbandpass(c.nbp_nc, bands, (double)dsp_rate, scale, c.nbp_wintype);
+}
+
+// recalc_bpsnba_filter (snb.c:807-822) with RXAbpsnbaCheck's frequencies (RXA.c:829-881): 250..5700 Hz on the mode's side
+int Engine::snb_mask(ChanCfg &c, int ch)
+{
+    double f_low = 0.0, f_high = 0.0;
+    int run_notches = 0;
+    switch (c.mode) {
+    case QH_LSB: case QH_CWL: case QH_DIGL: f_low = -5700.0; f_high = -250.0; run_notches = c.fnfrun; break;
+    case QH_USB: case QH_CWU: case QH_DIGU: f_low = 250.0; f_high = 5700.0; run_notches = c.fnfrun; break;
+    case QH_AM: case QH_SAM: case QH_DSB: case QH_FM: f_low = 250.0; f_high = 5700.0; break;
+    default: break;
+    }
+    const double scale = 1.0 / (double)(2 * dsp_size);
+    if (long_parts[4] > 1) if (int rc = long_stage_alloc(4, false)) return rc;
+    std::vector<cd> h = run_notches ? notched(c, f_low, f_high, scale) : fir_bandpass(c.nbp_nc, f_low, f_high, (double)dsp_rate, c.nbp_wintype, 1, scale);
+    if (c.mp) h = mp_imp(h, 16, 0);
+    for (auto &v : h) v *= (double)(2 * dsp_size);
+    if (long_parts[4] > 1) if (int rc = long_masks_upload(4, ch, h)) return rc;
+    if ((int)h.size() > kLongPart) h.resize((size_t)kLongPart);      // (the one-tile mask is not used then)
+    if (int rc = put_mask(mask_snb, ch, band_mask(h))) return rc;
+    c.snb_dirty = false;
+    return QH_OK;
+}
+
+// a channel's row of a fircore stage's masks (the bnfft bins of the tile in use)
+int Engine::put_mask(double2 *mask, int ch, const std::vector<cd> &m)
+{
+    QH_HIP(hipMemcpyAsync(mask + (size_t)ch * kBandNfftMax, m.data(), (size_t)bnfft * sizeof(cd), hipMemcpyHostToDevice, stream));
+    QH_HIP(hipStreamSynchronize(stream));
+    return QH_OK;
+}
+
+// create_meter x3 (RXA.c:69-82,142-155,361-374): tau 0.1 s for average and peak decay; flush_meter -> -400 dB
+int Engine::meters_alloc()
+{
+    if (m_adc) return QH_OK;
+    const double rate = (double)dsp_rate;
+    std::vector<MeterState> init((size_t)nch, MeterState{ 0.0, 0.0, -400.0, -400.0 });
+    for (MeterState **pm : { &m_adc, &m_s, &m_agc }) {
+        if (int rc = alloc(*pm, nch)) return rc;
+        QH_HIP(hipMemcpyAsync(*pm, init.data(), (size_t)nch * sizeof(MeterState), hipMemcpyHostToDevice, stream));
+    }
+    m_prm.mult_average = std::exp(-1.0 / (rate * 0.100));
+    m_prm.mult_peak = std::exp(-1.0 / (rate * 0.100));
+    std::vector<double> w(64), g2((size_t)nch);
+    for (int i = 0; i < 64; i++) w[(size_t)i] = (1.0 - m_prm.mult_average) * std::pow(m_prm.mult_average, (double)(63 - i));
+    for (int ch = 0; ch < nch; ch++) {
+        const ChanCfg &c = cfg[(size_t)ch];
+        g2[(size_t)ch] = (c.agc_run && c.agc_mode == 0 && !c.fix_before()) ? c.agc_fixed * c.agc_fixed : 1.0;
+    }
+    if (int rc = alloc(m_w, 64)) return rc;
+    if (int rc = alloc(m_g2, nch)) return rc;
+    QH_HIP(hipMemcpyAsync(m_w, w.data(), 64 * sizeof(double), hipMemcpyHostToDevice, stream));
+    QH_HIP(hipMemcpyAsync(m_g2, g2.data(), g2.size() * sizeof(double), hipMemcpyHostToDevice, stream));
+    QH_HIP(hipStreamSynchronize(stream));
+    return QH_OK;
+}
+
+// The one-time part of refresh_demod: the demodulators' state and the loop constants of the AM / SAM and FM detectors
+int Engine::demod_init()
+{
+    const double rate = (double)dsp_rate;
+    if (int rc = alloc(list_block, (long long)nch * (L_COUNT + 3))) return rc;      // the three pair lists (last) take two rows each
+    for (int i = 0; i < L_COUNT; i++) lists[i].dev = list_block + (size_t)nch * (i <= L_PAIRS_FM ? i : 2 * i - L_PAIRS_FM);
+    if (int rc = alloc(fix_gain, nch)) return rc;
+    if (int rc = meters_alloc()) return rc;
+    if (int rc = alloc(agc_prm, nch)) return rc;
+    if (int rc = alloc(agc_state, nch, true)) return rc;
+    const int oi = kAgcRing - 1;                        // out_index = -1 (calc_wcpagc, wcpAGC.c:34)
+    for (int c = 0; c < nch; c++) if (int rc = put_row(&agc_state[c].out_index, 0, oi, false)) return rc;
+    QH_HIP(hipStreamSynchronize(stream));
+    if (int rc = alloc(levelfade, nch)) return rc;
+    if (int rc = alloc(am_state, nch, true)) return rc;
+    if (int rc = alloc(am_next, nch)) return rc;
+    if (int rc = alloc(sn_next, nch)) return rc;
+    if (int rc = alloc(fmdc_next, nch)) return rc;
+    if (int rc = alloc(pll_state, nch, true)) return rc;
+    if (int rc = alloc(fm_pll_state, nch, true)) return rc;
+    if (int rc = alloc(fm_again, nch)) return rc;
+    if (int rc = alloc(pll_nfixed, 1, true)) return rc;
+    if (int rc = alloc(sam_prm, nch)) return rc;
+    if (int rc = alloc(sn_prm, nch)) return rc;
+    if (int rc = alloc(sn_state, nch, true)) return rc;
+    if (int rc = alloc(mask_de, kBandNfftMax)) return rc;
+    if (int rc = alloc(mask_aud, kBandNfftMax)) return rc;
+    for (int i = 0; i < 2; i++) {
+        if (int rc = alloc(hist_de[i], (long long)nch * kHistBand, true)) return rc;
+        if (int rc = alloc(hist_aud[i], (long long)nch * kHistBand, true)) return rc;
+    }
+    // init_amd (wdsp/amd.c:72-89) with create_rxa's constants (RXA.c:183-189)
+    {
+        const double zeta = 1.0, omegaN = 250.0, tauR = 0.02, tauI = 1.4;
+        PllParam &q = sam_pll_prm;
+        q.omega_min = kTwoPiRef * -2000.0 / rate; q.omega_max = kTwoPiRef * 2000.0 / rate;
+        q.g1 = 1.0 - std::exp(-2.0 * omegaN * zeta / rate);
+        q.g2 = -q.g1 + 2.0 * (1 - std::exp(-omegaN * zeta / rate) * std::cos(omegaN / rate * std::sqrt(1.0 - zeta * zeta)));
+        q.mtauR = std::exp(-1.0 / (rate * tauR)); q.onem_mtauR = 1.0 - q.mtauR;
+        q.mtauI = std::exp(-1.0 / (rate * tauI)); q.onem_mtauI = 1.0 - q.mtauI;
+        am_prm.mtauR = q.mtauR; am_prm.onem_mtauR = q.onem_mtauR; am_prm.mtauI = q.mtauI; am_prm.onem_mtauI = q.onem_mtauI;
+        std::vector<double> pw(2 * 2048);           // mtauR^(k + 1), mtauI^(k + 1): the carried averages' weights at sample k of a 2048-sample tile
+        for (int k = 0; k < 2048; k++) { pw[(size_t)k] = std::pow(q.mtauR, (double)(k + 1)); pw[(size_t)(2048 + k)] = std::pow(q.mtauI, (double)(k + 1)); }
+        // ... and the lanes' scan weights of the two averages (qh_wave.hpp PoleScan: pa = m^((lane & 15) + 1), pb = m^((lane & 31) + 1), pw = m^(lane + 1))
+        pw.resize(2 * 2048 + 6 * 64);
+        for (int f = 0; f < 2; f++) {
+            const double m = f ? q.mtauI : q.mtauR;
+            for (int l = 0; l < 64; l++) {
+                pw[(size_t)(2 * 2048 + (3 * f + 0) * 64 + l)] = std::pow(m, (double)((l & 15) + 1));
+                pw[(size_t)(2 * 2048 + (3 * f + 1) * 64 + l)] = std::pow(m, (double)((l & 31) + 1));
+                pw[(size_t)(2 * 2048 + (3 * f + 2) * 64 + l)] = std::pow(m, (double)(l + 1));
+            }
+        }
+        if (int rc = alloc(am_pw, (long long)pw.size())) return rc;
+        if (int rc = alloc(am_last, 2LL * nch, true)) return rc;
+        QH_HIP(hipMemcpyAsync(am_pw, pw.data(), pw.size() * sizeof(double), hipMemcpyHostToDevice, stream));
+        QH_HIP(hipStreamSynchronize(stream));
+    }
+    // calc_fmd (wdsp/fmd.c:29-44) with create_rxa's constants (RXA.c:199-204)
+    {
+        const double zeta = 1.0, omegaN = 20000.0, tau = 0.02;
+        PllParam &q = fm_pll_prm;
+        q.omega_min = kTwoPiRef * -8000.0 / rate; q.omega_max = kTwoPiRef * 8000.0 / rate;
+        q.g1 = 1.0 - std::exp(-2.0 * omegaN * zeta / rate);
+        q.g2 = -q.g1 + 2.0 * (1 - std::exp(-omegaN * zeta / rate) * std::cos(omegaN / rate * std::sqrt(1.0 - zeta * zeta)));
+        q.mtau = std::exp(-1.0 / (rate * tau)); q.onem_mtau = 1.0 - q.mtau;
+        std::vector<double> pw(2048);               // mtau^(k + 1): the carried dc's weight at sample k of a tile (fm_audio_at)
+        for (int k = 0; k < 2048; k++) pw[(size_t)k] = std::pow(q.mtau, (double)(k + 1));
+        if (int rc = alloc(fm_pw, 2048)) return rc;
+        QH_HIP(hipMemcpyAsync(fm_pw, pw.data(), 2048 * sizeof(double), hipMemcpyHostToDevice, stream));
+        QH_HIP(hipStreamSynchronize(stream));
+    }
+    demod_alloc = true;
+    lists_dirty = true;
+    for (ChanCfg &c : cfg) c.demod_dirty = true;
+    return QH_OK;
+}
+
+// Every channel list from the channels' settings (host side: h[id]), with their counts
+void Engine::build_lists(std::vector<int> (&h)[L_COUNT])
+{
+    std::vector<int> stale_cur, stale_other;
+    int sam0 = 0;
+    ssql_h[0].clear(); ssql_h[1].clear();
+    for (int ch = 0; ch < nch; ch++) {
+        const ChanCfg &c = cfg[(size_t)ch];
+        if (c.amsq_run) h[L_AMSQ].push_back(ch);
+        if (c.snba_run) h[L_SNBA].push_back(ch);
+        if (c.snb_pos() >= 0) h[L_SNB + c.snb_pos()].push_back(ch);
+        const int at_agc = (c.bp1_run && !c.bp1_pos) ? 1 : 0;       // the buffer the channel is in when xwcpagc runs
+        if (c.emnr_run) h[L_EMNR + (c.emnr_pos ? 1 + at_agc : 0)].push_back(ch);
+        for (int f = 0; f < 2; f++) if (c.lms[f].run) h[L_LMS + 3 * f + (c.lms[f].position ? 1 + at_agc : 0)].push_back(ch);
+        if (c.bp1_run) h[L_BP1P + (c.bp1_pos ? 1 : 0)].push_back(ch);
+        if (c.fix_before()) h[L_FIX + at_agc].push_back(ch);
+        if (c.ap_on()) h[L_AP + (c.bp1_run ? 1 : 0)].push_back(ch);        // where the channel is behind bp1 at either position
+        if (c.ssql_on()) ssql_h[c.bp1_run ? 1 : 0].push_back(ch);
+        if (c.fmd_run && c.lim_run) h[L_LIM].push_back(ch);
+        if (c.amd_run && c.amd_mode == 0) h[L_AM].push_back(ch);
+        // SAM channels with sbmode 0 (no all-pass chains) first
+        if (c.amd_run && c.amd_mode == 1) { if (c.sbmode == 0) h[L_SAM].insert(h[L_SAM].begin() + sam0++, ch); else h[L_SAM].push_back(ch); }
+        if (c.fmd_run) h[L_FM].push_back(ch); else { h[L_REST].push_back(ch); h[c.bp1_run ? L_RB : L_USB].push_back(ch); }
+        h[c.bp1_run ? L_BP1 : L_PLAIN].push_back(ch);
+        // xwcpagc sits between the two bp1 positions (RXA.c:581-586): a position-1 channel is still in `cur` there; channels whose
+        // attack window moved in mid-stream go last
+        if (c.agc_run && c.agc_mode != 0) (at_agc ? (c.agc_stale ? stale_other : h[L_AGC_OTHER]) : (c.agc_stale ? stale_cur : h[L_AGC_CUR])).push_back(ch);
+    }
+    n_sam0 = sam0;
+    n_agc_cur_stale = (int)stale_cur.size(); n_agc_other_stale = (int)stale_other.size();
+    h[L_AGC_CUR].insert(h[L_AGC_CUR].end(), stale_cur.begin(), stale_cur.end());
+    h[L_AGC_OTHER].insert(h[L_AGC_OTHER].end(), stale_other.begin(), stale_other.end());
+    // partners: neighbours in the list, ordered so that equal designs are neighbours; a channel left over is its own partner
+    auto bp1_real = [&](int ch) { const ChanCfg &c = cfg[(size_t)ch]; return c.bp1_run && c.bp1_flow == -c.bp1_fhigh && !c.mp; };
+    auto bp1_same = [&](int x, int y) {
+        const ChanCfg &p = cfg[(size_t)x], &q = cfg[(size_t)y];
+        return p.bp1_nc == q.bp1_nc && p.bp1_wintype == q.bp1_wintype && p.bp1_fhigh == q.bp1_fhigh && p.bp1_gain == q.bp1_gain;
+    };
+    auto bp1_pairs = [&](std::vector<int> v) {
+        std::vector<int> pr;
+        for (int ch : v) if (!bp1_real(ch)) return pr;
+        std::stable_sort(v.begin(), v.end(), [&](int x, int y) {
+            const ChanCfg &p = cfg[(size_t)x], &q = cfg[(size_t)y];
+            if (p.bp1_fhigh != q.bp1_fhigh) return p.bp1_fhigh < q.bp1_fhigh;
+            if (p.bp1_nc != q.bp1_nc) return p.bp1_nc < q.bp1_nc;
+            if (p.bp1_wintype != q.bp1_wintype) return p.bp1_wintype < q.bp1_wintype;
+            return p.bp1_gain < q.bp1_gain;
+        });
+        for (size_t i = 0; i < v.size();) {
+            if (i + 1 < v.size() && bp1_same(v[i], v[i + 1])) { pr.push_back(v[i]); pr.push_back(v[i + 1]); i += 2; }
+            else { pr.push_back(v[i]); pr.push_back(v[i]); i += 1; }
+        }
+        return pr;
+    };
+    const std::vector<int> &fm = h[L_FM];
+    for (size_t i = 0; i < fm.size(); i += 2) { h[L_PAIRS_FM].push_back(fm[i]); h[L_PAIRS_FM].push_back(i + 1 < fm.size() ? fm[i + 1] : fm[i]); }
+    h[L_PAIRS_AM] = bp1_pairs(h[L_AM]);
+    h[L_PAIRS_SAM] = bp1_pairs(h[L_SAM]);
+    np_fm = (int)h[L_PAIRS_FM].size() / 2; np_am = (int)h[L_PAIRS_AM].size() / 2; np_sam = (int)h[L_PAIRS_SAM].size() / 2;
+    for (int i = 0; i < L_COUNT; i++) lists[i].n = (int)h[i].size();
+    for (int b = 0; b < 2; b++) ssql_lists[b].n = (int)ssql_h[b].size();
+}
+
+// The stages made when a channel first runs one of them (the lists' counts say which)
+int Engine::stages_alloc()
+{
+    const double rate = (double)dsp_rate;
+    if ((lists[L_AP].n || lists[L_AP + 1].n) && !ap_prm) if (int rc = ap_alloc()) return rc;
+    if (ssql_listed() && !ssql_prm) if (int rc = ssql_alloc()) return rc;
+    if ((lists[L_EMNR].n || lists[L_EMNR + 1].n || lists[L_EMNR + 2].n) && !emnr_state) if (int rc = emnr_alloc()) return rc;
+    if (lists[L_SNBA].n && !snba_state) if (int rc = snba_alloc()) return rc;
+    if (lists[L_AMSQ].n && !amsq_prm) {
+        if (int rc = alloc(amsq_prm, nch)) return rc;
+        if (int rc = alloc(amsq_state, nch, true)) return rc;
+        // compute_slews, amsq.c:28-46, with muted_gain 0 and 70 ms up / down (RXA.c:166-167,172): theta accumulates as there
+        amsq_ntup = (int)(0.070 * rate); amsq_ntdown = (int)(0.070 * rate);
+        std::vector<double> up((size_t)amsq_ntup + 1), down((size_t)amsq_ntdown + 1);
+        double delta = kPiRef / (double)amsq_ntup, theta = 0.0;
+        for (int i = 0; i <= amsq_ntup; i++) { up[(size_t)i] = 0.0 + (1.0 - 0.0) * 0.5 * (1.0 - std::cos(theta)); theta += delta; }
+        delta = kPiRef / (double)amsq_ntdown; theta = 0.0;
+        for (int i = 0; i <= amsq_ntdown; i++) { down[(size_t)i] = 0.0 + (1.0 - 0.0) * 0.5 * (1.0 + std::cos(theta)); theta += delta; }
+        if (int rc = alloc(amsq_cup, (long long)up.size())) return rc;
+        if (int rc = alloc(amsq_cdown, (long long)down.size())) return rc;
+        QH_HIP(hipMemcpyAsync(amsq_cup, up.data(), up.size() * 8, hipMemcpyHostToDevice, stream));
+        QH_HIP(hipMemcpyAsync(amsq_cdown, down.data(), down.size() * 8, hipMemcpyHostToDevice, stream));
+        QH_HIP(hipStreamSynchronize(stream));
+        for (ChanCfg &c : cfg) c.amsq_dirty = true;
+    }
+    bool any_lms = false;
+    for (int k = 0; k < 6; k++) any_lms = any_lms || lists[L_LMS + k].n;
+    if (any_lms && !lms_prm[0]) {
+        for (int f = 0; f < 2; f++) {
+            if (int rc = alloc(lms_prm[f], nch)) return rc;
+            if (int rc = alloc(lms_state[f], nch)) return rc;
+            // create_anf: lidx 1.0, ngamma 6.25e-12; create_anr: lidx 120.0, ngamma 0.001 (RXA.c:289-292,309-312)
+            std::vector<LmsState> init((size_t)nch);
+            std::memset(init.data(), 0, init.size() * sizeof(LmsState));
+            for (LmsState &st : init) { st.lidx = f ? 120.0 : 1.0; st.ngamma = f ? 0.001 : 6.25e-12; }
+            QH_HIP(hipMemcpyAsync(lms_state[f], init.data(), init.size() * sizeof(LmsState), hipMemcpyHostToDevice, stream));
+            QH_HIP(hipStreamSynchronize(stream));
+        }
+        for (ChanCfg &c : cfg) { c.lms[0].dirty = c.lms[1].dirty = true; c.lms[0].flush = c.lms[1].flush = false; }
+    }
+    if (lists[L_LIM].n && !lim_prm) {
+        if (int rc = alloc(lim_prm, nch)) return rc;
+        if (int rc = alloc(lim_state, nch)) return rc;
+        for (ChanCfg &c : cfg) c.lim_dirty = true;
+    }
+    return QH_OK;
+}
+
+// A fircore keeps its delay lines while its channel is off the stage's list, and the ping-pong pair flips for the listed channels
+// only: a channel that (re)joins the list finds its rows in the half that was current when it left (c.*at), and they move to the
+// current one.  rows: the stage's short and long delay lines, each with the half that is current for it.
+int Engine::follow_rows(std::vector<char> &listed, int ChanCfg::*at, int cur, const std::vector<int> &chans, std::initializer_list<Rows> rows)
+{
+    if (listed.size() != (size_t)nch) listed.assign((size_t)nch, 0);
+    for (int ch = 0; ch < nch; ch++) if (listed[(size_t)ch]) cfg[(size_t)ch].*at = cur;
+    std::fill(listed.begin(), listed.end(), 0);
+    for (int ch : chans) {
+        int &a = cfg[(size_t)ch].*at;
+        if (a != cur)
+            for (const Rows &r : rows)
+                if (r.h[0] && r.h[1])
+                    QH_HIP(hipMemcpyAsync(r.h[r.cur] + (size_t)ch * r.len, r.h[a] + (size_t)ch * r.len, (size_t)r.len * sizeof(double2),
+                                          hipMemcpyDeviceToDevice, stream));
+        a = cur;
+        listed[(size_t)ch] = 1;
+    }
+    return QH_OK;
+}
+
+// setNc_fircore's flush (wdsp/firmin.c:454-466): zero n channels' delay lines from channel ch on, short and long, in both halves
+int Engine::zero_rows(double2 *const h[2], double2 *const lh[2], int ch, int n)
+{
+    for (int i = 0; i < 2; i++) {
+        QH_HIP(hipMemsetAsync(h[i] + (size_t)ch * kHistBand, 0, (size_t)n * kHistBand * sizeof(double2), stream));
+        if (lh[i]) QH_HIP(hipMemsetAsync(lh[i] + (size_t)ch * kLongHist, 0, (size_t)n * kLongHist * sizeof(double2), stream));
+    }
+    return QH_OK;
+}
+
+// Lists, stages and delay-line rows after a setter moved a channel between lists
+int Engine::refresh_lists()
+{
+    std::vector<int> h[L_COUNT];
+    build_lists(h);
+    if (int rc = stages_alloc()) return rc;
+    if (snba_state) {       // bpsnba's fircore (the partitioned form's 16383-sample delay line goes along: nc > 4096)
+        std::vector<int> snb(h[L_SNB]);
+        snb.insert(snb.end(), h[L_SNB + 1].begin(), h[L_SNB + 1].end());
+        if (int rc = follow_rows(snb_listed, &ChanCfg::snb_hist_at, cur_snb, snb, { { hist_snb, cur_snb, kHistBand }, { lhist[4], cur_snb, kLongHist } }))
+            return rc;
+    }
+    // bp1's: SetRXABandpassRun (bandpass.c:385-390) switches it on without RXAbp1Set's flush (RXA.c:825)
+    if (int rc = follow_rows(bp1_listed, &ChanCfg::bp1_hist_at, cur_bp1, h[L_BP1], { { hist_bp1, cur_bp1, kHistBand }, { lhist[1], cur_bp1, kLongHist } }))
+        return rc;
+    // the FM de-emphasis / audio fircores' while the channel is in another mode (SetRXAMode only clears fmd's run flag, RXA.c:758-776);
+    // fm_hist_at follows the de-emphasis filter's half
+    if (int rc = follow_rows(fm_listed, &ChanCfg::fm_hist_at, cur_de, h[L_FM], { { hist_de, cur_de, kHistBand }, { hist_aud, cur_aud, kHistBand },
+                                                                                { lhist[2], cur_de, kLongHist }, { lhist[3], cur_aud, kLongHist } }))
+        return rc;
+    std::vector<int> all((size_t)nch * (L_COUNT + 3));
+    for (int i = 0; i < L_COUNT; i++) std::copy(h[i].begin(), h[i].end(), all.begin() + (lists[i].dev - list_block));
+    std::vector<double> fg((size_t)nch);
+    for (int ch = 0; ch < nch; ch++) fg[(size_t)ch] = cfg[(size_t)ch].agc_fixed;
+    QH_HIP(hipMemcpyAsync(list_block, all.data(), all.size() * sizeof(int), hipMemcpyHostToDevice, stream));
+    QH_HIP(hipMemcpyAsync(fix_gain, fg.data(), fg.size() * sizeof(double), hipMemcpyHostToDevice, stream));
+    std::vector<int> ss;
+    if (ssql_list_block) {
+        ss.assign((size_t)nch * 2, 0);
+        for (int b = 0; b < 2; b++) std::copy(ssql_h[b].begin(), ssql_h[b].end(), ss.begin() + (size_t)nch * b);
+        QH_HIP(hipMemcpyAsync(ssql_list_block, ss.data(), ss.size() * sizeof(int), hipMemcpyHostToDevice, stream));
+    }
+    QH_HIP(hipStreamSynchronize(stream));
+    lists_dirty = false;
+    return QH_OK;
+}
+
+// loadWcpAGC, wdsp/wcpAGC.c:115-146, in its order of expressions; the arguments in create_wcpagc's
+static AgcParam load_wcpagc(double rate, double tau_attack, double tau_decay, double n_tau, double max_gain, double var_gain, double max_input,
+                            double out_targ, double tau_fast_back, double tau_fast_decay, double pop_ratio, int hang_enable, double tau_hang_backmult,
+                            double hangtime, double hang_thresh, double tau_hang_decay)
+{
+    AgcParam q{};
+    q.attack_buffsize = (int)std::ceil(rate * n_tau * tau_attack);
+    q.attack_mult = 1.0 - std::exp(-1.0 / (rate * tau_attack));
+    q.decay_mult = 1.0 - std::exp(-1.0 / (rate * tau_decay));
+    q.fast_decay_mult = 1.0 - std::exp(-1.0 / (rate * tau_fast_decay));
+    q.fast_backmult = 1.0 - std::exp(-1.0 / (rate * tau_fast_back));
+    q.onemfast_backmult = 1.0 - q.fast_backmult;
+    q.out_target = out_targ * (1.0 - std::exp(-n_tau)) * 0.9999;
+    q.min_volts = q.out_target / (var_gain * max_gain);
+    q.inv_out_target = 1.0 / q.out_target;
+    double tmp = std::log10(q.out_target / (max_input * var_gain * max_gain));
+    if (tmp == 0.0) tmp = 1e-16;
+    q.slope_constant = (q.out_target * (1.0 - 1.0 / var_gain)) / tmp;
+    q.inv_max_input = 1.0 / max_input;
+    tmp = std::pow(10.0, (hang_thresh - 1.0) / 0.125);
+    q.hang_level = (max_input * tmp + (q.out_target / (var_gain * max_gain)) * (1.0 - tmp)) * 0.637;
+    q.hang_backmult = 1.0 - std::exp(-1.0 / (rate * tau_hang_backmult));
+    q.onemhang_backmult = 1.0 - q.hang_backmult;
+    q.hang_decay_mult = 1.0 - std::exp(-1.0 / (rate * tau_hang_decay));
+    q.pop_ratio = pop_ratio;
+    q.hang_count_init = (int)(hangtime * rate);
+    q.hang_enable = hang_enable;
+    q.pmode = 1;
+    return q;
+}
+
+// ---- per-channel parameters of the demodulator stages (refresh_demod: each only when its setter has run)
+int Engine::prm_agc(ChanCfg &c, int ch)
+{
+    if (!c.agc_dirty) return QH_OK;
+    // create_rxa's constants (RXA.c:335-358)
+    const AgcParam q = load_wcpagc((double)dsp_rate, c.agc_tau_attack, c.agc_tau_decay, 4.0, c.agc_max_gain, c.agc_var_gain, 1.0, 1.0, 0.250, 0.005,
+                                   5.0, 1, 0.500, c.agc_hangtime, c.agc_hang_thresh, 0.100);
+    if (q.attack_buffsize + 2 > kAgcRing)
+        return set_error(QH_ERR_UNSUPPORTED, "AGC attack of %g s needs a look-ahead of %d samples (limit %d)", c.agc_tau_attack,
+                         q.attack_buffsize, kAgcRing - 2);
+    c.agc_abuf = q.attack_buffsize;
+    if (int rc = put_row(agc_prm, ch, q)) return rc;
+    c.agc_dirty = false;
+    return QH_OK;
+}
+
+int Engine::prm_emnr(ChanCfg &c, int ch)
+{
+    if (emnr_chan && c.emnr_dirty) {
+        if (c.emnr_run && (c.emnr_npe < 0 || c.emnr_npe > 2 || c.emnr_gain_method < 0 || c.emnr_gain_method > 3))
+            return set_error(QH_ERR_UNSUPPORTED, "EMNR: gain methods 0..3 and noise estimators 0..2");
+        const EmnrChan ec{ c.emnr_gain_method, c.emnr_npe, c.emnr_ae, 0, c.emnr_ae_zeta, c.emnr_ae_psi, c.emnr_train_zeta, c.emnr_train_t2 };
+        if (int rc = put_row(emnr_chan, ch, ec)) return rc;
+        c.emnr_dirty = false;
+    }
+    if (emnr_state && c.emnr_flush) {           // flush_emnr, emnr.c:583-596: the accumulators and their indices, not the estimators
+        EmnrScalars sc;
+        QH_HIP(hipMemcpyAsync(&sc, emnr_scal + ch, sizeof(sc), hipMemcpyDeviceToHost, stream));
+        QH_HIP(hipStreamSynchronize(stream));
+        sc.iainidx = sc.iaoutidx = sc.oaoutidx = sc.nsamps = sc.saveidx = 0; sc.oainidx = emnr_prm.init_oainidx;
+        if (int rc = put_row(emnr_scal, ch, sc, false)) return rc;
+        QH_HIP(hipMemsetAsync(emnr_state + (size_t)ch * kEmnrStateDoubles, 0, (size_t)EO_PREVG * sizeof(double), stream));
+        QH_HIP(hipStreamSynchronize(stream));
+        c.emnr_flush = false;
+    }
+    return QH_OK;
+}
+
+int Engine::prm_snba(ChanCfg &c, int ch)
+{
+    const SnbaParam &q = snba_prm;
+    if (snba_state && c.snba_taps_dirty) {
+        // calc_resample for outresamp (12 kHz -> dsp_rate, gain 2, resample.c:35-79) with the channel's output bandwidth
+        if (q.ratio > 1) {
+            const int L = q.ratio, ncoef = q.cpp_out * L;
+            const double full = (double)(12000 * L), fc = c.snba_f_high == 0.0 ? 0.45 * 12000.0 : c.snba_f_high;
+            const double lo = c.snba_f_low < 0.0 ? -fc / full : c.snba_f_low / full;
+            const std::vector<cd> imp = fir_bandpass(ncoef, lo, fc / full, 1.0, 1, 0, 2.0 * (double)L);
+            std::vector<double> hp((size_t)ncoef);
+            size_t i = 0;
+            for (int j = 0; j < L; j++) for (int k = 0; k < ncoef; k += L) hp[i++] = imp[(size_t)(j + k)].real();
+            QH_HIP(hipMemcpyAsync(snba_hout + (size_t)ch * ncoef, hp.data(), hp.size() * sizeof(double), hipMemcpyHostToDevice, stream));
+            QH_HIP(hipStreamSynchronize(stream));
+        }
+        c.snba_taps_dirty = false;
+    }
+    if (snba_state && (c.snba_flush || c.snba_rout_flush)) {
+        double *st = snba_state + (size_t)ch * q.state_doubles;
+        if (q.cpp_out > 1) QH_HIP(hipMemsetAsync(st + q.off_rout, 0, (size_t)(q.cpp_out - 1) * sizeof(double), stream));
+        if (c.snba_flush) {         // flush_snba, snb.c:161-185: the frame half of xbase, the accumulators, both resamplers
+            QH_HIP(hipMemsetAsync(st + kSnbX, 0, (size_t)kSnbX * sizeof(double), stream));
+            QH_HIP(hipMemsetAsync(st + q.off_inacc, 0, (size_t)(q.state_doubles - q.off_inacc) * sizeof(double), stream));
+            if (int rc = put_row(snba_idx, ch, SnbaIdx{ 0, 0, 0, 0, q.init_oaoutidx, { 0, 0, 0 } })) return rc;
+        }
+    }
+    c.snba_flush = c.snba_rout_flush = false;
+    return QH_OK;
+}
+
+int Engine::prm_amsq(ChanCfg &c, int ch)
+{
+    if (!amsq_prm || !c.amsq_dirty) return QH_OK;
+    // calc_amsq, amsq.c:48-64: 10 ms average (RXA.c:165)
+    const double rate = (double)dsp_rate;
+    AmsqParam q{};
+    q.avm = std::exp(-1.0 / (rate * 0.010)); q.onem_avm = 1.0 - q.avm;
+    q.tail_thresh = c.amsq_tail_thresh; q.unmute_thresh = c.amsq_unmute_thresh; q.min_tail = 0.0; q.max_tail = c.amsq_max_tail;
+    q.muted_gain = 0.0; q.rate = rate; q.ntup = amsq_ntup; q.ntdown = amsq_ntdown;
+    if (int rc = put_row(amsq_prm, ch, q)) return rc;
+    c.amsq_dirty = false;
+    return QH_OK;
+}
+
+int Engine::prm_lms(ChanCfg &c, int ch)
+{
+    for (int f = 0; f < 2 && lms_prm[0]; f++) {
+        ChanCfg::Lms &m = c.lms[f];
+        if (m.dirty) {
+            if (m.run && (m.taps < 1 || m.taps > 64 || m.delay < 1 || m.delay > 64))
+                return set_error(QH_ERR_UNSUPPORTED, "%s: taps %d / delay %d (1..64 each: one tap per lane)", f ? "ANR" : "ANF", m.taps, m.delay);
+            // lidx_min, lidx_max, den_mult, lincr, ldecr of create_rxa (RXA.c:290-295,310-315)
+            if (int rc = put_row(lms_prm[f], ch, LmsParam{ m.taps, m.delay, f, 0, m.two_mu, m.gamma, f ? 120.0 : 0.0, 200.0, 6.25e-10, 1.0, 3.0 }))
+                return rc;
+            m.dirty = false;
+        }
+        if (m.flush) {          // flush_anf (anf.c:135-140): delay line and weights; lidx / ngamma carry on
+            QH_HIP(hipMemsetAsync(lms_state[f] + ch, 0, offsetof(LmsState, lidx), stream));
+            m.flush = false;
+        }
+    }
+    return QH_OK;
+}
+
+int Engine::prm_lim(ChanCfg &c, int ch)
+{
+    if (!c.lim_dirty || !lim_prm) return QH_OK;
+    // calc_fmd's create_wcpagc(1, 5, 1, ..., 0.001, 0.008, 4, lim_gain, 1.0, 1.0, 1.0, 0.9, 0.250, 0.004, 4.0, 0,
+    // 0.500, 0.500, 2.000, 0.100) (fmd.c:48-72) through loadWcpAGC; a new limiter starts cleared
+    const AgcParam q = load_wcpagc((double)dsp_rate, 0.001, 0.008, 4.0, c.lim_gain, 1.0, 1.0, 0.9, 0.250, 0.004, 4.0, 0, 0.500, 0.500, 2.000, 0.100);
+    if (int rc = put_row(lim_prm, ch, q, false)) return rc;
+    QH_HIP(hipMemsetAsync(lim_state + ch, 0, sizeof(AgcState), stream));
+    if (int rc = put_row(&lim_state[ch].out_index, 0, kAgcRing - 1)) return rc;        // out_index = -1 (calc_wcpagc, wcpAGC.c:34)
+    c.lim_dirty = false;
+    return QH_OK;
+}
+
+// the detectors' own parameters: AM's fade leveller, SAM's sideband mode, FM's gain and its CTCSS notch
+int Engine::prm_detect(ChanCfg &c, int ch)
+{
+    if (!c.demod_dirty) return QH_OK;
+    const int lf = c.levelfade;
+    const double again = (double)dsp_rate / (c.fm_dev * kTwoPiRef);     // wdsp/fmd.c:44
+    const SamChanParam sp{ c.sbmode, c.levelfade };
+    SnotchParam sn{};
+    {   // calc_snotch, wdsp/iir.c:35-49 (bw 0.0002, fmd.c:47)
+        const double fn = c.ctcss_freq / (double)dsp_rate, csn = std::cos(kTwoPiRef * fn), qr = 1.0 - 3.0 * 0.0002;
+        const double qk = (1.0 - 2.0 * qr * csn + qr * qr) / (2.0 * (1.0 - csn));
+        sn.a0 = qk; sn.a1 = -2.0 * qk * csn; sn.a2 = qk; sn.b1 = 2.0 * qr * csn; sn.b2 = -qr * qr; sn.run = c.ctcss_run;
+    }
+    if (int rc = put_row(levelfade, ch, lf, false)) return rc;
+    if (int rc = put_row(fm_again, ch, again, false)) return rc;
+    if (int rc = put_row(sam_prm, ch, sp, false)) return rc;
+    if (int rc = put_row(sn_prm, ch, sn, false)) return rc;
+    if (c.ctcss_flush) {                    // calc_snotch ends with flush_snotch, wdsp/iir.c:48
+        QH_HIP(hipMemsetAsync(sn_state + ch, 0, sizeof(SnotchState), stream));
+        c.ctcss_flush = false;
+    }
+    QH_HIP(hipStreamSynchronize(stream));
+    c.demod_dirty = false;
+    return QH_OK;
+}
+
+// create_fmd, wdsp/fmd.c:108-116: the de-emphasis and audio filters the FM channels share, rebuilt when their nc, RXASetMP or the band
+// tile moved
+int Engine::fm_filters(int want_nc)
+{
+    if (!want_nc || (want_nc == fm_nc_built && fm_mp == fm_mp_built && fm_nfft_built == 2 * bnfft + (band2g ? 1 : 0))) return QH_OK;
+    // de-emphasis by frequency sampling, audio band-pass 0.8*f_low .. 1.1*f_high
+    const double rate = (double)dsp_rate, f_low = 300.0, f_high = 3000.0, afgain = 0.5;
+    std::vector<cd> de = fc_impulse(want_nc, f_low, f_high, +20.0 * std::log10(f_high / f_low), 0.0, 1, rate, 1.0 / (2.0 * dsp_size), 0, 0);
+    std::vector<cd> au = fir_bandpass(want_nc, 0.8 * f_low, 1.1 * f_high, rate, 0, 1, afgain / (2.0 * dsp_size));
+    if (fm_mp) { de = mp_imp(de, 16, 0); au = mp_imp(au, 16, 0); }     // SetRXAFMMPde / MPaud, wdsp/RXA.c:956-957
+    fm_mp_built = fm_mp;
+    for (auto &v : de) v *= (double)(2 * dsp_size);
+    for (auto &v : au) v *= (double)(2 * dsp_size);
+    de_real = true;
+    for (const cd &v : de) de_real = de_real && v.imag() == 0.0;
+    if (long_parts[2] > 1) {
+        if (int rc = long_masks_upload(2, 0, de)) return rc;
+        if (int rc = long_masks_upload(3, 0, au)) return rc;
+        de.resize((size_t)kLongPart); au.resize((size_t)kLongPart);      // (the one-tile masks are not used then)
+    }
+    if (int rc = upload(mask_de, band_mask(de), stream)) return rc;
+    if (int rc = upload(mask_aud, band_mask(au), stream)) return rc;
+    fm_nfft_built = 2 * bnfft + (band2g ? 1 : 0);
+    if (fm_nc_built && fm_nc_built != want_nc) {      // setNc_fircore zeroes the delay lines
+        if (int rc = zero_rows(hist_de, lhist[2], 0, nch)) return rc;
+        if (int rc = zero_rows(hist_aud, lhist[3], 0, nch)) return rc;
+    }
+    fm_nc_built = want_nc;
+    return QH_OK;
+}
+
+// Demodulator state, channel lists and FM filters (only engines that run AM/SAM/FM channels get here).  Every step looks at flags
+// first: a call with nothing dirty allocates, copies and waits for nothing.
+int Engine::refresh_demod()
+{
+    if (!demod_alloc) if (int rc = demod_init()) return rc;
+    // a channel whose attack window moves after its AGC has run keeps the reference's ring_max, which may then be a value the window
+    // no longer holds (wcpAGC.c:197-210 only rescans when the sample that leaves equals it): the time tiles take the window's maximum,
+    // so that channel stays on the kernel that steps the reference's bookkeeping -- it alone: the lists put such channels last
+    for (ChanCfg &c : cfg) {
+        if (!c.agc_dirty || !c.agc_ran) continue;
+        const int abuf = (int)std::ceil((double)dsp_rate * 4.0 * c.agc_tau_attack);
+        if (c.agc_abuf != abuf) { c.agc_rewindow = true; if (!c.agc_stale) { c.agc_stale = true; lists_dirty = true; } }
+    }
+    if (lists_dirty) if (int rc = refresh_lists()) return rc;
+    int want_nc = 0, want_mp = -1;
+    for (int ch = 0; ch < nch; ch++) {
+        ChanCfg &c = cfg[(size_t)ch];
+        if (c.fmd_run) {
+            if (want_nc && want_nc != c.fm_nc) return set_error(QH_ERR_UNSUPPORTED, "FM channels with different nc in one engine");
+            want_nc = c.fm_nc;
+            // RXASetMP reaches the FM filters of ITS channel (SetRXAFMMPde / MPaud, wdsp/RXA.c:956-957): the one design the engine's FM
+            // channels share follows them, not whichever channel was set last
+            if (want_mp >= 0 && want_mp != c.mp) return set_error(QH_ERR_UNSUPPORTED, "FM channels with different RXASetMP in one engine");
+            want_mp = c.mp;
+        }
+        if (int rc = prm_agc(c, ch)) return rc;
+        if (int rc = prm_emnr(c, ch)) return rc;
+        if (int rc = prm_snba(c, ch)) return rc;
+        if (int rc = prm_amsq(c, ch)) return rc;
+        if (int rc = prm_lms(c, ch)) return rc;
+        if (int rc = prm_lim(c, ch)) return rc;
+        if (int rc = prm_detect(c, ch)) return rc;
+    }
+    if (want_mp >= 0) fm_mp = want_mp;
+    return fm_filters(want_nc);
+}
+
+// the frame advance and the two accumulators' sizes for an overlap (calc_snba, snb.c:45-65)
+void Engine::snba_plan(int ovrlp)
+{
+    SnbaParam &q = snba_prm;
+    q.incr = kSnbX / ovrlp;
+    q.iasize = q.incr > q.isize ? q.incr : q.isize;
+    q.oasize = q.iasize;
+    q.init_oaoutidx = q.incr > q.isize ? q.isize : 0;
+    q.off_inacc = 2 * kSnbX; q.off_outacc = q.off_inacc + q.iasize; q.off_rin = q.off_outacc + q.oasize;
+    q.off_rout = q.off_rin + (q.cpp_in - 1); q.state_doubles = q.off_rout + (q.cpp_out - 1);
+}
+
+// SetRXASNBAovrlp (snb.c:595-603): decalc_snba + calc_snba with the new overlap -- the frame memory (xbase, made by create_snba) stays,
+// the accumulators, their indices and both resamplers start over
+int Engine::snba_set_ovrlp(int ovrlp)
+{
+    if (ovrlp < 1 || ovrlp > kSnbX || kSnbX / ovrlp < 1) return set_error(QH_ERR_INVALID, "SetRXASNBAovrlp: 1 .. %d", kSnbX);
+    snba_ovrlp = ovrlp;
+    if (!snba_state) return QH_OK;                       // nothing built yet: snba_alloc plans with it
+    QH_HIP(hipSetDevice(device));
+    if (int rc = quiesce()) return rc;
+    const SnbaParam old = snba_prm;
+    std::vector<double> frames((size_t)nch * 2 * kSnbX);
+    QH_HIP(hipMemcpy2D(frames.data(), 2 * kSnbX * sizeof(double), snba_state, (size_t)old.state_doubles * sizeof(double), 2 * kSnbX * sizeof(double),
+                       (size_t)nch, hipMemcpyDeviceToHost));
+    snba_plan(ovrlp);
+    const SnbaParam &q = snba_prm;
+    if (int rc = alloc(snba_state, (long long)nch * q.state_doubles)) return rc;
+    QH_HIP(qh::dev_zero(snba_state, (size_t)nch * q.state_doubles * sizeof(double)));
+    QH_HIP(hipMemcpy2D(snba_state, (size_t)q.state_doubles * sizeof(double), frames.data(), 2 * kSnbX * sizeof(double), 2 * kSnbX * sizeof(double),
+                       (size_t)nch, hipMemcpyHostToDevice));
+    std::vector<SnbaIdx> ix((size_t)nch, SnbaIdx{ 0, 0, 0, 0, q.init_oaoutidx, { 0, 0, 0 } });
+    QH_HIP(hipMemcpy(snba_idx, ix.data(), ix.size() * sizeof(SnbaIdx), hipMemcpyHostToDevice));
+    return QH_OK;
+}
+
+// calc_emnr (wdsp/emnr.c:240-497) with create_rxa's arguments (RXA.c:319-332): parameters, window, start values of every array
+int Engine::snba_alloc()
+{
+    // calc_snba, snb.c:31-66, with create_rxa's arguments (RXA.c:237-255)
+    SnbaParam &q = snba_prm;
+    if (dsp_rate % 12000 || (dsp_rate / 12000 != 1 && dsp_rate / 12000 != 2 && dsp_rate / 12000 != 4) || dsp_size > kSnbMaxDsp ||
+        dsp_size % (dsp_rate / 12000))
+        return set_error(QH_ERR_UNSUPPORTED, "SNBA: dsp_rate 12000, 24000 or 48000 and dsp_size up to %d", kSnbMaxDsp);
+    q.ratio = dsp_rate / 12000;
+    q.isize = dsp_size / q.ratio;
+    q.cpp_in = q.ratio > 1 ? 140 * q.ratio + 1 : 1;
+    q.cpp_out = q.ratio > 1 ? 141 : 1;
+    q.asize = 64; q.npasses = 2; q.b = 10; q.pre = 2; q.post = 2; q.k1 = 8.0; q.k2 = 20.0; q.pmultmin = 0.5;
+    snba_plan(snba_ovrlp);
+    if (int rc = alloc(snba_state, (long long)nch * q.state_doubles, true)) return rc;
+    if (int rc = alloc(snba_idx, nch)) return rc;
+    std::vector<SnbaIdx> ix((size_t)nch, SnbaIdx{ 0, 0, 0, 0, q.init_oaoutidx, { 0, 0, 0 } });
+    QH_HIP(hipMemcpyAsync(snba_idx, ix.data(), ix.size() * sizeof(SnbaIdx), hipMemcpyHostToDevice, stream));
+    if (int rc = alloc(snba_scratch, (long long)nch * kSnbX * kSnbX)) return rc;
+    if (int rc = alloc(snba_tune, nch)) return rc;
+    snba_tune_dirty = true;
+    if (int rc = alloc(snba_hin, q.cpp_in)) return rc;
+    if (int rc = alloc(snba_hout, (long long)nch * q.cpp_out * q.ratio)) return rc;
+    std::vector<double> hin((size_t)q.cpp_in, 1.0);
+    if (q.ratio > 1) {      // inresamp: dsp_rate -> 12 kHz, 250 .. 5400 Hz, gain 2 (snb.c:43-44)
+        const double full = (double)dsp_rate;
+        const std::vector<cd> imp = fir_bandpass(q.cpp_in, 250.0 / full, 0.45 * 12000.0 / full, 1.0, 1, 0, 2.0);
+        for (int i = 0; i < q.cpp_in; i++) hin[(size_t)i] = imp[(size_t)i].real();
+    }
+    QH_HIP(hipMemcpyAsync(snba_hin, hin.data(), hin.size() * sizeof(double), hipMemcpyHostToDevice, stream));
+    if (int rc = alloc(mask_snb, (long long)nch * kBandNfftMax)) return rc;
+    for (double2 *&h : hist_snb) if (int rc = alloc(h, (long long)nch * kHistBand, true)) return rc;
+    QH_HIP(hipStreamSynchronize(stream));
+    snb_listed.assign((size_t)nch, 0);
+    for (ChanCfg &c : cfg) { c.snba_taps_dirty = true; c.snb_dirty = true; c.snba_flush = c.snba_rout_flush = false; c.snb_flush = false; c.snb_hist_at = cur_snb; }
+    return QH_OK;
+}
+
+int Engine::emnr_alloc()
+{
+    if (dsp_size > kEmnrIncr) return set_error(QH_ERR_UNSUPPORTED, "EMNR: dsp_size up to %d", kEmnrIncr);
+    const double rate = (double)dsp_rate, incr = (double)kEmnrIncr;
+    EmnrParam &q = emnr_prm;
+    auto tc = [&](double base) { const double tau = -128.0 / 8000.0 / std::log(base); return std::exp(-incr / rate / tau); };
+    q.gain = 1.0 / kEmnrF / 4.0;
+    q.gf1p5 = std::sqrt(kPiRef) / 2.0;
+    q.alpha = tc(0.985);
+    q.eps_floor = 1.0e-300; q.gamma_max = 40.0; q.xi_min = std::pow(10.0, -40.0 / 10.0); q.q = 0.2; q.gmax = 10000.0;
+    q.dim_zeta = 60;
+    q.z_gamma_min = h_zrange[0]; q.z_gamma_max = h_zrange[1]; q.z_xihat_min = h_zrange[2]; q.z_xihat_max = h_zrange[3];
+    q.alphaCsmooth = tc(0.7); q.alphaMax = tc(0.96); q.alphaCmin = tc(0.7); q.alphaMin_max_value = tc(0.3);
+    q.snrq = -incr / (0.064 * rate);
+    q.betamax = tc(0.8);
+    q.invQeqMax = 0.5; q.av = 2.12;
+    const double Dtime = 8.0 * 12.0 * 128.0 / 8000.0;
+    q.U = 8;
+    q.V = (int)(0.5 + (Dtime * rate / (q.U * incr)));
+    if (q.V < 4) q.V = 4;
+    if ((q.U = (int)(0.5 + (Dtime * rate / (q.V * incr)))) < 1) q.U = 1;
+    if (q.U > kEmnrU) return set_error(QH_ERR_UNSUPPORTED, "EMNR: %d minimum sub-windows at this rate (up to %d)", q.U, kEmnrU);
+    q.D = q.U * q.V;
+    {
+        static const double Dvals[18] = { 1.0, 2.0, 5.0, 8.0, 10.0, 15.0, 20.0, 30.0, 40.0, 60.0, 80.0, 120.0, 140.0, 160.0, 180.0, 220.0, 260.0, 300.0 };
+        static const double Mvals[18] = { 0.000, 0.260, 0.480, 0.580, 0.610, 0.668, 0.705, 0.762, 0.800, 0.841, 0.865, 0.890, 0.900, 0.910,
+                                          0.920, 0.930, 0.935, 0.940 };
+        auto interpM = [&](double x) {              // emnr.c:185-202
+            if (x <= Dvals[0]) return Mvals[0];
+            if (x >= Dvals[17]) return Mvals[17];
+            int idx = 0;
+            while (x >= Dvals[idx]) idx++;
+            const double xllow = std::log10(Dvals[idx - 1]), xlhigh = std::log10(Dvals[idx]);
+            const double frac = (std::log10(x) - xllow) / (xlhigh - xllow);
+            return Mvals[idx - 1] + frac * (Mvals[idx] - Mvals[idx - 1]);
+        };
+        q.MofD = interpM((double)q.D); q.MofV = interpM((double)q.V);
+    }
+    q.invQbar_points[0] = 0.03; q.invQbar_points[1] = 0.05; q.invQbar_points[2] = 0.06; q.invQbar_points[3] = 1.0e300;
+    {
+        const double f[4] = { 8.0, 4.0, 2.0, 1.2 };
+        for (int i = 0; i < 4; i++) {
+            const double db = 10.0 * std::log10(f[i]) / (12.0 * 128 / 8000);
+            q.nsmax[i] = std::pow(10.0, db / 10.0 * q.V * incr / rate);
+        }
+    }
+    q.alpha_pow = tc(0.8); q.alpha_Pbar = tc(0.9);
+    q.epsH1 = std::pow(10.0, 15.0 / 10.0); q.epsH1r = q.epsH1 / (1.0 + q.epsH1);
+    {   // npl, emnr.c:458-489
+        auto tl = [&](double base) { const double tau = -256.0 / (20100.0 * std::log(base)); return std::exp(-incr / (rate * tau)); };
+        q.l_eta = tl(0.7); q.l_gamma = tl(0.998); q.l_beta = tl(0.8); q.l_alpha_d = tl(0.85); q.l_alpha_p = tl(0.2);
+        q.delta_LF = 1000.0 / (rate / 2) * kEmnrM; q.delta_MF = 3000.0 / (rate / 2) * kEmnrM;
+    }
+    q.bsize = dsp_size;
+    q.oasize = dsp_size > kEmnrIncr ? dsp_size : kEmnrIncr;
+    q.init_oainidx = (kEmnrF - dsp_size - kEmnrIncr) % q.oasize;
+    // window (calc_window, wintype 0, emnr.c:160-183)
+    std::vector<double> win(kEmnrF);
+    {
+        const double arg = 2.0 * kPiRef / (double)kEmnrF;
+        double sum = 0.0;
+        for (int i = 0; i < kEmnrF; i++) { win[(size_t)i] = std::sqrt(0.54 - 0.46 * std::cos((double)i * arg)); sum += win[(size_t)i]; }
+        const double inv_coherent_gain = (double)kEmnrF / sum;
+        for (double &w : win) w *= inv_coherent_gain;
+    }
+    // start values (emnr.c:309-313,409-426,452-456)
+    std::vector<double> st((size_t)kEmnrStateDoubles, 0.0);
+    for (int k = 0; k < kEmnrM; k++) {
+        st[(size_t)(EO_PREVG + k)] = 1.0; st[(size_t)(EO_PREVM + k)] = 1.0;
+        st[(size_t)(EO_P + k)] = 0.5; st[(size_t)(EO_SIG + k)] = 0.5; st[(size_t)(EO_PBAR + k)] = 0.5; st[(size_t)(EO_PMINU + k)] = 0.5;
+        st[(size_t)(EO_P2BAR + k)] = 0.25;
+        st[(size_t)(EO_ACTMIN + k)] = 1.0e300; st[(size_t)(EO_ACTSUB + k)] = 1.0e300;
+        for (int ku = 0; ku < kEmnrU; ku++) st[(size_t)(EO_AMB + ku * kEmnrPad + k)] = 1.0e300;
+        st[(size_t)(EO_SSIG + k)] = 0.5; st[(size_t)(EO_SPBAR + k)] = 0.5;
+    }
+    if (int rc = alloc(emnr_state, (long long)nch * kEmnrStateDoubles)) return rc;
+    if (int rc = alloc(emnr_scal, nch)) return rc;
+    if (int rc = alloc(emnr_chan, nch)) return rc;
+    if (int rc = alloc(emnr_window, kEmnrF)) return rc;
+    if (int rc = alloc(emnr_GG, 241 * 241)) return rc;
+    if (int rc = alloc(emnr_GGS, 241 * 241)) return rc;
+    if (int rc = alloc(emnr_zeta, 3600)) return rc;
+    if (int rc = alloc(emnr_zeta_true, 3600)) return rc;
+    const EmnrScalars sc0{ 0, 0, q.init_oainidx, 0, 0, 0, q.V, 0, 1.0 };
+    for (int ch = 0; ch < nch; ch++) {
+        QH_HIP(hipMemcpyAsync(emnr_state + (size_t)ch * kEmnrStateDoubles, st.data(), st.size() * 8, hipMemcpyHostToDevice, stream));
+        QH_HIP(hipMemcpyAsync(emnr_scal + ch, &sc0, sizeof(sc0), hipMemcpyHostToDevice, stream));
+    }
+    QH_HIP(hipMemcpyAsync(emnr_window, win.data(), win.size() * 8, hipMemcpyHostToDevice, stream));
+    QH_HIP(hipMemcpyAsync(emnr_GG, h_GG.data(), h_GG.size() * 8, hipMemcpyHostToDevice, stream));
+    QH_HIP(hipMemcpyAsync(emnr_GGS, h_GGS.data(), h_GGS.size() * 8, hipMemcpyHostToDevice, stream));
+    QH_HIP(hipMemcpyAsync(emnr_zeta, h_zeta.data(), h_zeta.size() * 8, hipMemcpyHostToDevice, stream));
+    QH_HIP(hipMemcpyAsync(emnr_zeta_true, h_zeta_true.data(), h_zeta_true.size() * 4, hipMemcpyHostToDevice, stream));
+    QH_HIP(hipStreamSynchronize(stream));
+    if (int rc = emnr_lds_limit()) return rc;
+    for (ChanCfg &c : cfg) { c.emnr_dirty = true; c.emnr_flush = false; }
+    return QH_OK;
+}
+
+int Engine::ensure_buffers(long long n_mid)
+{
+    if (n_mid <= buf_cap) return QH_OK;
+    if (int rc = quiesce()) return rc;
+    for (double2 *&b : buf)
+        if (int rc = alloc(b, n_mid * nch)) return rc;
+    buf_cap = n_mid;
+    return QH_OK;
+}
+
+// the mask of a fircore stage for the tile in use; the two-group tile reads even bins in group A, odd bins in group B
+std::vector<cd> Engine::band_mask(const std::vector<cd> &h) const
+{
+    std::vector<cd> m = make_mask(h, bnfft);
+    if (!band2g) return m;
+    std::vector<cd> p(m.size());
+    const size_t half = m.size() / 2;
+    for (size_t k = 0; k < half; k++) { p[k] = m[2 * k]; p[half + k] = m[2 * k + 1]; }
+    return p;
+}
+
+// chunk partials of the fused meters: whole tiles per channel (a tile's store is not bounds-checked)
+int Engine::ensure_meter_partials(long long n_mid, int lout)
+{
+    const long long need = ((n_mid + lout - 1) / lout) * (lout / 64);
+    if (need <= m_part_cap) return QH_OK;
+    if (int rc = quiesce()) return rc;
+    for (double2 *&m : m_part)
+        if (int rc = alloc(m, need * nch)) return rc;
+    m_part_cap = need;
+    return QH_OK;
+}
+
+int Engine::ensure_abuf(long long n)
+{
+    return grow(abuf, abuf_cap, n, nch);
+}
+
+int Engine::long_stage_alloc(int sid, bool shared_mask)
+{
+    if (lmask[sid]) return QH_OK;
+    if (int rc = quiesce()) return rc;
+    const long long rows = shared_mask ? 1 : nch;
+    if (int rc = alloc(lmask[sid], rows * kLongParts * kBandNfftMax, true)) return rc;
+    if (int rc = alloc(lrow_parts[sid], rows, true)) return rc;
+    for (double2 *&h : lhist[sid]) if (int rc = alloc(h, (long long)nch * kLongHist, true)) return rc;
+    return QH_OK;
+}
+int Engine::long_buffers()
+{
+    if (lcat && lcat_cap == buf_cap) return QH_OK;
+    if (int rc = quiesce()) return rc;
+    if (int rc = alloc(lcat, nch * (kLongHist + buf_cap))) return rc;
+    if (int rc = alloc(ltmp, nch * buf_cap)) return rc;
+    lcat_cap = buf_cap;
+    return QH_OK;
+}
+// the kLongParts partition masks of the impulse response h (8192-point spectra of its 4096-tap slices; the slices past its end zero)
+int Engine::long_masks_upload(int sid, long long row, const std::vector<cd> &h)
+{
+    std::vector<cd> all((size_t)kLongParts * kBandNfftMax, cd(0.0, 0.0));
+    const int own = (int)std::min<size_t>((h.size() + kLongPart - 1) / kLongPart, (size_t)kLongParts);
+    for (int p = 0; p < own; p++) {
+        const size_t a = (size_t)p * kLongPart, b = std::min(h.size(), a + (size_t)kLongPart);
+        const std::vector<cd> m = make_mask(std::vector<cd>(h.begin() + (long)a, h.begin() + (long)b), kBandNfftMax);
+        std::copy(m.begin(), m.end(), all.begin() + (long)((size_t)p * kBandNfftMax));
+    }
+    QH_HIP(hipMemcpyAsync(lmask[sid] + (size_t)row * kLongParts * kBandNfftMax, all.data(), all.size() * sizeof(cd), hipMemcpyHostToDevice, stream));
+    return put_row(lrow_parts[sid], row, own);
+}
+
+// The chains' transition over a segment: the one-sample map of the 17 words (ds, x_j[n-1], x_j[n-2]; input 0) raised to the segment's
+// length, for the two lengths a call of n samples in S segments has (q and q + 1 batches of 64), chains a / c (coefficients c0, input
+// one sample late through ds) and b / d (c1).  Long double on the host; kept until the call shape changes.
+int Engine::set_sb_phi(long long n, int S)
+{
+    const long long key = n * 1024 + S;
+    if (key == sb_phi_key) return QH_OK;
+    static const long double c0[7] = { -0.328201924180698L, -0.744171491539427L, -0.923022915444215L, -0.978490468768238L,
+                                       -0.994128272402075L, -0.998458978159551L, -0.999790306259206L };
+    static const long double c1[7] = { -0.0991227952747244L, -0.565619728761389L, -0.857467122550052L, -0.959123933111275L,
+                                       -0.988739372718090L, -0.996959189310611L, -0.999282492800792L };
+    constexpr int W = 17;
+    typedef std::vector<long double> Mat;
+    auto mul = [&](const Mat &a, const Mat &b) {
+        Mat r((size_t)W * W, 0.0L);
+        for (int i = 0; i < W; i++)
+            for (int k = 0; k < W; k++) {
+                const long double v = a[(size_t)i * W + k];
+                if (v != 0.0L) for (int j = 0; j < W; j++) r[(size_t)i * W + j] += v * b[(size_t)k * W + j];
+            }
+        return r;
+    };
+    auto one_step = [&](const long double *c, bool delayed) {
+        Mat m((size_t)W * W, 0.0L);
+        for (int col = 0; col < W; col++) {
+            long double v[W] = { 0 }, x[8];
+            v[col] = 1.0L;
+            x[0] = delayed ? v[0] : 0.0L;                               // the chain's input: ds (a, c) or the external input, 0 here
+            for (int j = 0; j < 7; j++) x[j + 1] = c[j] * (x[j] - v[2 + 2 * (j + 1)]) + v[2 + 2 * j];       // amd.c:172-175
+            long double nv[W];
+            nv[0] = 0.0L;
+            for (int j = 0; j < 8; j++) { nv[1 + 2 * j] = x[j]; nv[2 + 2 * j] = v[1 + 2 * j]; }
+            for (int r = 0; r < W; r++) m[(size_t)r * W + col] = nv[r];
+        }
+        return m;
+    };
+    auto power = [&](Mat b, long long e) {
+        Mat r((size_t)W * W, 0.0L);
+        for (int i = 0; i < W; i++) r[(size_t)i * W + i] = 1.0L;
+        while (e > 0) { if (e & 1) r = mul(b, r); b = mul(b, b); e >>= 1; }
+        return r;
+    };
+    const long long q = ((n + 63) / 64) / S;
+    std::vector<double> h((size_t)2 * 2 * W * W);
+    for (int li = 0; li < 2; li++)
+        for (int set = 0; set < 2; set++) {
+            const Mat p = power(one_step(set ? c1 : c0, set == 0), 64 * (q + li));
+            for (int i = 0; i < W * W; i++) h[((size_t)li * 2 + set) * W * W + i] = (double)p[(size_t)i];
+        }
+    if (!sb_phi) {
+        if (int rc = alloc(sb_phi, (long long)h.size())) return rc;
+        if (int rc = alloc(sb_sum, (long long)nch * kSegWaves * kSegMaxGroups * kSbSum)) return rc;
+        if (int rc = alloc(sb_start, (long long)nch * kSegWaves * kSegMaxGroups * kSbSum)) return rc;
+    }
+    if (int rc = quiesce()) return rc;
+    QH_HIP(hipMemcpy(sb_phi, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
+    sb_phi_key = key;
+    return QH_OK;
+}
+
+// The tile length of a stage that runs one lane per tile (audio peak, SSQL) over `rows` listed channels: tiles short enough for about
+// four wavefronts of 64 tiles per SIMD (1024 SIMDs), 256 .. 8192 samples
+static int lane_tile_len(int rows, long long n_mid)
+{
+    int L = 256;
+    while (L < 8192 && (long long)rows * n_mid / L > 4LL * 64 * 1024) L *= 2;
+    return L;
+}
+
+// ---- xcbl, xspeak, xmpeak (qh_audio_peak.hpp)
+int Engine::ap_alloc()
+{
+    if (int rc = alloc(ap_prm, nch)) return rc;
+    if (int rc = alloc(ap_state, (long long)nch * kApW, true)) return rc;
+    if (int rc = alloc(ap_M, (long long)nch * kApDim * kApDim)) return rc;
+    ap_M_h.assign((size_t)nch * kApDim * kApDim, 0.0);
+    ap_prm_h.assign((size_t)nch, ApParam{});
+    ap_L = 0;
+    for (ChanCfg &c : cfg) { c.ap_dirty = true; c.sp_flush = false; for (bool &f : c.mp_flush) f = false; }    // the state starts at zero
+    return QH_OK;
+}
+
+// T = A^L: A's column i is where one step with zero input takes the unit state e_i (ap_step_linear, the kernel's own recurrence);
+// powers by squaring.  Stages that do not run leave their rows at the identity.
+static void ap_transition(const ApParam &q, int L, double *T)
+{
+    constexpr int N = kApDim;
+    std::vector<double> A((size_t)N * N), R((size_t)N * N, 0.0), tmp((size_t)N * N);
+    for (int i = 0; i < N; i++) {
+        double s[N] = {};
+        s[i] = 1.0;
+        (void)ap_step_linear(q, s, 0.0);
+        for (int r = 0; r < N; r++) A[(size_t)r * N + i] = s[r];
+    }
+    for (int i = 0; i < N; i++) R[(size_t)i * N + i] = 1.0;
+    auto mul = [&](const std::vector<double> &X, const std::vector<double> &Y, std::vector<double> &Z) {
+        for (int r = 0; r < N; r++)
+            for (int c = 0; c < N; c++) {
+                long double acc = 0.0L;
+                for (int k = 0; k < N; k++) acc += (long double)X[(size_t)r * N + k] * Y[(size_t)k * N + c];
+                Z[(size_t)r * N + c] = (double)acc;
+            }
+    };
+    for (int e = L; e > 0; e >>= 1) {
+        if (e & 1) { mul(R, A, tmp); R.swap(tmp); }
+        if (e > 1) { mul(A, A, tmp); A.swap(tmp); }
+    }
+    std::copy(R.begin(), R.end(), T);
+}
+
+// Parameters, carry matrices and flushes of the three stages, and the tile length of this call (before anything is enqueued)
+int Engine::refresh_ap(const ChainCall &k)
+{
+    if (!ap_prm) {
+        for (ChanCfg &c : cfg) { c.sp_flush = false; for (bool &f : c.mp_flush) f = false; }
+        return QH_OK;
+    }
+    const int nap = k.mixed ? lists[L_AP].n + lists[L_AP + 1].n : 0;
+    int L = ap_L;
+    if (nap) {
+        L = lane_tile_len(nap, k.n_mid);
+        const long long ntile = (k.n_mid + L - 1) / L;
+        if (int rc = grow(ap_ends, ap_ends_cap, ntile, (long long)kApW * nch)) return rc;
+    }
+    const double mtau = std::exp(-1.0 / ((double)dsp_rate * 0.02));       // calc_cbl, cblock.c:29-36 (tau 0.02, RXA.c:411)
+    auto bq = [&](double f, double bw, double g) {
+        const SpeakDesign d = design_speak(f, bw, g, (double)dsp_rate);
+        return ApBiquad{ d.a0, d.a1, d.a2, d.b1, d.b2, d.fgain };
+    };
+    bool up = false;
+    const ApParam *last_q = nullptr;
+    const double *last_T = nullptr;
+    for (int ch = 0; ch < nch; ch++) {
+        ChanCfg &c = cfg[(size_t)ch];
+        if (c.sp_flush || c.mp_flush[0] || c.mp_flush[1]) {            // flush_speak: that cascade's x / y history, I and Q
+            for (int comp = 0; comp < 2; comp++) {
+                double *st = ap_state + (size_t)ch * kApW + (size_t)comp * kApDim;
+                if (c.sp_flush) QH_HIP(hipMemsetAsync(st + kApSpeakAt, 0, kApCascade * sizeof(double), stream));
+                for (int p = 0; p < kApPeaks; p++)
+                    if (c.mp_flush[p]) QH_HIP(hipMemsetAsync(st + kApPeakAt + kApCascade * p, 0, kApCascade * sizeof(double), stream));
+            }
+            c.sp_flush = false;
+            for (bool &f : c.mp_flush) f = false;
+        }
+        if (!c.ap_dirty && !(nap && L != ap_L && c.ap_on())) continue;
+        ApParam &q = ap_prm_h[(size_t)ch];
+        q = ApParam{};
+        q.sp = bq(c.sp_f, c.sp_bw, c.sp_gain);
+        for (int p = 0; p < kApPeaks; p++) q.pk[p] = bq(c.mp_f[p], c.mp_bw[p], c.mp_gain[p]);
+        q.mtau = mtau;
+        q.flags = (c.cbl_run ? AP_CBL : 0) | (c.sp_run ? AP_SPEAK : 0) | (c.mp_run ? AP_MPEAK : 0);
+        for (int p = 0; p < kApPeaks; p++)
+            if (c.mp_run && c.mp_enable[p] && p < c.mp_npeaks) q.flags |= AP_PEAK0 << p;
+        double *T = ap_M_h.data() + (size_t)ch * kApDim * kApDim;
+        if (c.ap_on() && nap) {
+            if (last_q && std::memcmp(last_q, &q, sizeof(q)) == 0) std::copy(last_T, last_T + kApDim * kApDim, T);
+            else ap_transition(q, L, T);
+            last_q = &q; last_T = T;
+            QH_HIP(hipMemcpyAsync(ap_M + (size_t)ch * kApDim * kApDim, T, (size_t)kApDim * kApDim * sizeof(double), hipMemcpyHostToDevice, stream));
+        }
+        QH_HIP(hipMemcpyAsync(ap_prm + ch, &q, sizeof(q), hipMemcpyHostToDevice, stream));
+        c.ap_dirty = false;
+        up = true;
+    }
+    if (up) QH_HIP(hipStreamSynchronize(stream));
+    ap_L = L;
+    return QH_OK;
+}
+
+// ---- xssql (qh_ssql.hpp)
+int Engine::ssql_alloc()
+{
+    const double rate = (double)dsp_rate;
+    if (int rc = alloc(ssql_list_block, 2LL * nch)) return rc;
+    for (int b = 0; b < 2; b++) ssql_lists[b].dev = ssql_list_block + (size_t)nch * b;
+    if (int rc = alloc(ssql_prm, nch)) return rc;
+    if (int rc = alloc(ssql_state, nch)) return rc;
+    SsqlState z{};                                  // calc_ssql (ssql.c:133-140): all zero but the trigger voltage, MUTED
+    z.v = kSsTrThresh; z.state = SS_MUTED; z.count = 0;
+    std::vector<SsqlState> st((size_t)nch, z);
+    QH_HIP(hipMemcpyAsync(ssql_state, st.data(), st.size() * sizeof(SsqlState), hipMemcpyHostToDevice, stream));
+    // compute_ssql_slews (ssql.c:110-127), muted_gain 0, tup = tdown = 0.070 (RXA.c:452-454): theta accumulates as there
+    const double mg = 0.0;
+    ssql_ntup = (int)(0.070 * rate); ssql_ntdown = (int)(0.070 * rate);
+    std::vector<double> up((size_t)ssql_ntup + 1), down((size_t)ssql_ntdown + 1);
+    double delta = kPiRef / (double)ssql_ntup, theta = 0.0;
+    for (int i = 0; i <= ssql_ntup; i++) { up[(size_t)i] = mg + (1.0 - mg) * 0.5 * (1.0 - std::cos(theta)); theta += delta; }
+    delta = kPiRef / (double)ssql_ntdown; theta = 0.0;
+    for (int i = 0; i <= ssql_ntdown; i++) { down[(size_t)i] = mg + (1.0 - mg) * 0.5 * (1.0 + std::cos(theta)); theta += delta; }
+    if (int rc = alloc(ssql_cup, (long long)up.size())) return rc;
+    if (int rc = alloc(ssql_cdown, (long long)down.size())) return rc;
+    QH_HIP(hipMemcpyAsync(ssql_cup, up.data(), up.size() * sizeof(double), hipMemcpyHostToDevice, stream));
+    QH_HIP(hipMemcpyAsync(ssql_cdown, down.data(), down.size() * sizeof(double), hipMemcpyHostToDevice, stream));
+    QH_HIP(hipStreamSynchronize(stream));
+    ssql_prm_h.assign((size_t)nch, SsqlParam{});
+    ssql_L = 0;
+    for (ChanCfg &c : cfg) c.ssql_dirty = true;
+    return QH_OK;
+}
+
+// A^L for a D x D transition A (row-major), by squaring in long double
+static void ssql_power(const double *A0, int D, int L, double *T)
+{
+    std::vector<long double> A(A0, A0 + D * D), R((size_t)D * D, 0.0L), tmp((size_t)D * D);
+    for (int i = 0; i < D; i++) R[(size_t)i * D + i] = 1.0L;
+    auto mul = [&](const std::vector<long double> &X, const std::vector<long double> &Y, std::vector<long double> &Z) {
+        for (int r = 0; r < D; r++)
+            for (int c = 0; c < D; c++) {
+                long double acc = 0.0L;
+                for (int k = 0; k < D; k++) acc += X[(size_t)r * D + k] * Y[(size_t)k * D + c];
+                Z[(size_t)r * D + c] = acc;
+            }
+    };
+    for (int e = L; e > 0; e >>= 1) {
+        if (e & 1) { mul(R, A, tmp); R.swap(tmp); }
+        if (e > 1) { mul(A, A, tmp); A.swap(tmp); }
+    }
+    for (int i = 0; i < D * D; i++) T[i] = (double)R[(size_t)i];
+}
+
+// Parameters and carry transitions of the listed channels, and the tile length of this call (before anything is enqueued)
+int Engine::refresh_ssql(const ChainCall &k)
+{
+    if (!ssql_prm) return QH_OK;
+    const int nss = k.mixed ? ssql_lists[0].n + ssql_lists[1].n : 0;
+    int L = ssql_L;
+    if (nss) {
+        L = lane_tile_len(nss, k.n_mid);       // (a multiple of 64: whole words)
+        const long long ntile = (k.n_mid + L - 1) / L, nw = kSsHistW + (k.n_mid + 63) / 64 + 1;
+        if (int rc = grow(ssql_ends, ssql_ends_cap, ntile, (long long)kSsE * nch)) return rc;
+        if (int rc = grow(ssql_bits, ssql_wcap, nw, 3LL * nch)) return rc;
+        if (int rc = grow(ssql_rec, ssql_rec_cap, nw, (long long)nch)) return rc;      // grows with ssql_wcap: the same stride
+    }
+    const double rate = (double)dsp_rate;
+    SsqlParam base{};
+    base.mtau = std::exp(-1.0 / (rate * 0.02));                         // calc_cbl, cblock.c:35 (create_cbl of calc_ssql, tau 0.02)
+    base.div = 2000.0 * 2.0 * kSsRing / rate;                          // create_ftov, ssql.c:51 (fmax 2000, rsize 2400)
+    {                                                                   // calc_dbqlp, iir.c:829-843: fc 11.3, Q 1.0
+        const double w0 = kTwoPiRef * 11.3 / rate, cs = std::cos(w0), c = std::sin(w0) / (2.0 * 1.0), den = 1.0 + c;
+        base.a0 = 0.5 * (1.0 - cs) / den; base.a1 = (1.0 - cs) / den; base.a2 = 0.5 * (1.0 - cs) / den;
+        base.b1 = 2.0 * cs / den; base.b2 = (c - 1.0) / den;
+    }
+    base.wdmult = std::exp(-1.0 / (rate * 0.5));                        // calc_ssql, ssql.c:136 (wdtau 0.5)
+    base.muted_gain = 0.0;
+    base.ntup = ssql_ntup; base.ntdown = ssql_ntdown;
+    if (nss) {
+        const double Ac[4] = { 0.0, 0.0, -1.0, base.mtau };             // (xp, y) -> (0, -xp + mtau y)
+        const double om = 1.0 - base.wdmult;                            // (y1, y2, w) -> (y0, y1, wdmult w + (1 - wdmult) y0)
+        const double Al[9] = { base.b1, base.b2, 0.0, 1.0, 0.0, 0.0, om * base.b1, om * base.b2, base.wdmult };
+        ssql_power(Ac, 2, L, base.Tc);
+        ssql_power(Al, 3, L, base.Tl);
+    }
+    bool up = false;
+    for (int ch = 0; ch < nch; ch++) {
+        ChanCfg &c = cfg[(size_t)ch];
+        if (!c.ssql_dirty && !(nss && L != ssql_L && c.ssql_on())) continue;
+        SsqlParam &q = ssql_prm_h[(size_t)ch];
+        q = base;
+        q.wthresh = c.ssql_wthresh;
+        q.mute_mult = 1.0 - std::exp(-1.0 / (rate * c.ssql_tau_mute));            // ssql.c:137-138, :339-370
+        q.unmute_mult = 1.0 - std::exp(-1.0 / (rate * c.ssql_tau_unmute));
+        QH_HIP(hipMemcpyAsync(ssql_prm + ch, &q, sizeof(q), hipMemcpyHostToDevice, stream));
+        c.ssql_dirty = false;
+        up = true;
+    }
+    if (up) QH_HIP(hipStreamSynchronize(stream));
+    if (nss) ssql_L = L;
+    return QH_OK;
+}
+
+// flush_rxa (wdsp/RXA.c:527-559): NCO phase, resampler ring and fircore delay lines back to zero
+int Engine::flush()
+{
+    epoch++;
+    QH_HIP(hipSetDevice(device));
+    QH_HIP(hipMemsetAsync(nco_phase, 0, (size_t)nch * sizeof(unsigned long long), stream));
+    QH_HIP(hipMemsetAsync(nco_parked, 0, (size_t)nch * sizeof(unsigned long long), stream));
+    if (rsmpout) if (int rc = qh_rat_reset(rsmpout)) return rc;        // flush_resample, wdsp/resample.c:159-165
+    if (rsmpin) if (int rc = qh_rat_reset(rsmpin)) return rc;
+    for (int i = 0; i < 2; i++) {
+        if (hist_front[i]) QH_HIP(hipMemsetAsync(hist_front[i], 0, (size_t)nch * kHistFront * sizeof(double2), stream));
+        QH_HIP(hipMemsetAsync(hist_nbp[i], 0, (size_t)nch * kHistBand * sizeof(double2), stream));
+        QH_HIP(hipMemsetAsync(hist_bp1[i], 0, (size_t)nch * kHistBand * sizeof(double2), stream));
+        if (demod_alloc) {
+            QH_HIP(hipMemsetAsync(hist_de[i], 0, (size_t)nch * kHistBand * sizeof(double2), stream));
+            QH_HIP(hipMemsetAsync(hist_aud[i], 0, (size_t)nch * kHistBand * sizeof(double2), stream));
+        }
+        for (int sid = 0; sid < 5; sid++)
+            if (lhist[sid][i]) QH_HIP(hipMemsetAsync(lhist[sid][i], 0, (size_t)nch * kLongHist * sizeof(double2), stream));
+    }
+    if (demod_alloc) {                        // flush_wcpagc zeroes the ring (wcpAGC.c:154-159)
+        for (int c = 0; c < nch; c++) {
+            QH_HIP(hipMemsetAsync(agc_state[c].ring, 0, sizeof(agc_state[c].ring), stream));
+            QH_HIP(hipMemsetAsync(agc_state[c].abs_ring, 0, sizeof(agc_state[c].abs_ring), stream));
+            QH_HIP(hipMemsetAsync(&agc_state[c].ring_max, 0, sizeof(double), stream));
+            if (cfg[(size_t)c].agc_stale) lists_dirty = true;
+            cfg[(size_t)c].agc_stale = false;     // an empty ring and ring_max = 0: nothing stale (qh_agc_tiled.hpp)
+        }
+        if (agc_lring) {
+            QH_HIP(hipMemsetAsync(agc_lring, 0, (size_t)nch * kAgcLongRing * sizeof(double2), stream));
+            QH_HIP(hipMemsetAsync(agc_labs, 0, (size_t)nch * kAgcLongRing * sizeof(double), stream));
+        }
+    }
+    for (ChanCfg &c : cfg) { c.lms[0].flush = c.lms[1].flush = true; c.emnr_flush = true; c.snba_flush = true; c.snb_flush = true; }    // flush_anf / flush_anr / flush_emnr, RXA.c:541-543
+    if (amsq_state) QH_HIP(hipMemsetAsync(amsq_state, 0, (size_t)nch * sizeof(AmsqState), stream));     // flush_amsq
+    if (ap_state) QH_HIP(hipMemsetAsync(ap_state, 0, (size_t)nch * kApW * sizeof(double), stream));    // flush_cbl / _speak / _mpeak, RXA.c:553-555
+    if (ssql_state) launch_ssql_flush();        // flush_ssql, RXA.c:556
+    if (demod_alloc) {                        // flush_amd / flush_fmd / flush_snotch
+        QH_HIP(hipMemsetAsync(am_state, 0, (size_t)nch * sizeof(AmState), stream));
+        QH_HIP(hipMemsetAsync(pll_state, 0, (size_t)nch * sizeof(PllState), stream));
+        QH_HIP(hipMemsetAsync(fm_pll_state, 0, (size_t)nch * sizeof(PllState), stream));
+        QH_HIP(hipMemsetAsync(sn_state, 0, (size_t)nch * sizeof(SnotchState), stream));
+    }
+    return QH_OK;
+}
+
+}  // namespace qh

@@ -1,6 +1,6 @@
 """qh_rxa_set_graph_replay across the engine's stages: a call replayed from a captured hipGraph must leave the bits a plain call leaves.
 
-The replay rests on one rule (qh_engine.hip, struct Engine): the host side of process() changes nothing from call to call but the six
+The replay rests on one rule (qh_engine.hpp, struct Engine): the host side of process() changes nothing from call to call but the six
 ping-pong flags.  A stage that keeps anything else per call on the host -- a ring index, a carry slot, a kernel argument passed by
 value -- works on the plain path and replays a stale argument from the graph.  This file holds every stage to that rule.
 
