@@ -150,6 +150,17 @@ int qh_rxa_SetRXASSQLRun(qh_rxa *e, int ch, int run);                           
 int qh_rxa_SetRXASSQLThreshold(qh_rxa *e, int ch, double threshold);            /* wdsp/ssql.c:338-346 */
 int qh_rxa_SetRXASSQLTauMute(qh_rxa *e, int ch, double tau_mute);               /* wdsp/ssql.c:348-358 */
 int qh_rxa_SetRXASSQLTauUnMute(qh_rxa *e, int ch, double tau_unmute);           /* wdsp/ssql.c:360-370 */
+/* xfmsq, the FM noise squelch right behind xfmd (wdsp/RXA.c:575), off at create with thresholds 0.750 / 0.562 (RXA.c:214-234; not 0.9
+ * apart until the threshold setter runs); a channel that turns it on starts muted and stays so for the 0.1 s ready delay.  While it is
+ * off nothing of it runs and its noise filter, averages and state stay as they were.  qh_rxa_flush does flush_fmsq (fmsq.c:122-130).
+ * A threshold that is not finite is refused with QH_ERR_INVALID.  nc: a power of two in [dsp_size, 4096]; a larger one is accepted by the
+ * setter (RXASetNC forwards here) and refused with QH_ERR_UNSUPPORTED at the next process call while the channel runs the stage.  Refused
+ * there too: FMSQ on a channel whose FM detector is off, a dsp rate at or below twice the FM loop's pole (about 15.8 kHz), and FMSQ
+ * channels of one engine with different nc or mp (they share one noise filter, as the FM channels share their filters). */
+int qh_rxa_SetRXAFMSQRun(qh_rxa *e, int ch, int run);                           /* wdsp/fmsq.c:235-241 */
+int qh_rxa_SetRXAFMSQThreshold(qh_rxa *e, int ch, double threshold);            /* wdsp/fmsq.c:243-250: tail = threshold, unmute = 0.9 threshold */
+int qh_rxa_SetRXAFMSQNC(qh_rxa *e, int ch, int nc);                             /* wdsp/fmsq.c:252-267 */
+int qh_rxa_SetRXAFMSQMP(qh_rxa *e, int ch, int mp);                             /* wdsp/fmsq.c:269-279 */
 int qh_rxa_SetRXAAMSQThreshold(qh_rxa *e, int ch, double threshold_db);
 int qh_rxa_SetRXAAMSQMaxTail(qh_rxa *e, int ch, double tail_seconds);
 /* xanf / xanr (wdsp/anf.c:82-133, anr.c:82-133), setters wdsp/anf.c:175-239 and anr.c:175-238; which position (0 before
@@ -204,6 +215,7 @@ int qh_rxa_process_host(qh_rxa *e, const double *h_in, long long in_stride, doub
  * percent of the 256-sample tiles on noise alone). */
 long long qh_rxa_pll_repairs(qh_rxa *h);
 int qh_rxa_debug_pll(qh_rxa *h, int check_only, int ch, double *out, int max);   /* diagnostics, see qh_rxa_api.hip */
+int qh_rxa_debug_fmsq(qh_rxa *h, int ch, double *out, int max);                      /* diagnostics: avnoise, longnoise, state, count, ready at the last call's end (wdsp/fmsq.c:141-205) */
 int qh_rxa_debug_agc(qh_rxa *h, int form);                                         /* diagnostics: 0 time tiles for long calls (default), 1 sample by sample, 2 batches of 64 */
 int qh_rxa_debug_agc_ends(qh_rxa *h, int slot, double *out, int max);                /* diagnostics, see qh_rxa_api.hip */
 long long qh_rxa_agc_repairs(qh_rxa *h);                                            /* wcpAGC time tiles the verify pass re-ran in order */
@@ -376,6 +388,10 @@ void SetRXASSQLRun(int channel, int run);                                       
 void SetRXASSQLThreshold(int channel, double threshold);                         /* wdsp/ssql.c:338-346 */
 void SetRXASSQLTauMute(int channel, double tau_mute);                            /* wdsp/ssql.c:348-358 */
 void SetRXASSQLTauUnMute(int channel, double tau_unmute);                        /* wdsp/ssql.c:360-370 */
+void SetRXAFMSQRun(int channel, int run);                                        /* wdsp/fmsq.c:235-241 */
+void SetRXAFMSQThreshold(int channel, double threshold);                         /* wdsp/fmsq.c:243-250 */
+void SetRXAFMSQNC(int channel, int nc);                                          /* wdsp/fmsq.c:252-267 */
+void SetRXAFMSQMP(int channel, int mp);                                          /* wdsp/fmsq.c:269-279 */
 void SetRXAAMSQThreshold(int channel, double threshold);                         /* wdsp/amsq.c:224-232, dB */
 void SetRXAAMSQMaxTail(int channel, double tail);                                /* wdsp/amsq.c:234-243, seconds */
 void SetRXAEMNRRun(int channel, int run);                                        /* wdsp/emnr.c:1096-1110; needs the files `calculus` and

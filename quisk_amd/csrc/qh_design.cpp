@@ -84,6 +84,25 @@ static std::vector<double> fsamp_window(int N, int wintype)
     return w;
 }
 
+// fir_fsamp (wdsp/fir.c:151-181), even nc, rtype 1, scale 1: the linear-phase frequency-sampling taps of the magnitudes mag[0 .. nc / 2)
+// at the bin centres, h[n] = (A_0 + 2 sum_{k=1}^{nc/2-1} A_k cos(2 pi (n - M) k / nc)) / nc with M = (nc - 1) / 2, even about M (one half
+// evaluated), under a Blackman-Harris window
+static std::vector<cd> fsamp_even(int nc, const std::vector<double> &mag, int wintype)
+{
+    const int bins = nc / 2;
+    const double centre = (double)(nc - 1) / 2.0;
+    const std::vector<double> w = fsamp_window(nc, wintype);
+    std::vector<cd> h((size_t)nc);
+    for (int n = 0; n < bins; n++) {
+        double acc = 0.0;
+        for (int k = 1; k < bins; k++) acc += 2.0 * mag[(size_t)k] * std::cos(kTwoPi * (n - centre) * k / nc);
+        const double tap = (1.0 / nc) * (mag[0] + acc);
+        h[(size_t)n] = cd(tap * w[(size_t)n], 0.0);
+        h[(size_t)(nc - 1 - n)] = cd(tap * w[(size_t)(nc - 1 - n)], 0.0);
+    }
+    return h;
+}
+
 // The FM de-emphasis / pre-emphasis curve as an FIR (what wdsp/fcurve.c:29-145 builds through fir_fsamp, wdsp/fir.c:129-185), even nc.
 //
 // Wanted magnitude at the nc / 2 bin centres f_i = (i + 1/2) / (nc / 2) * fs / 2: a 6 dB / octave line through (f0, g0 dB), rising
@@ -118,17 +137,76 @@ std::vector<cd> fc_impulse(int nc, double f0, double f1, double g0, double /*g1*
             mag[(size_t)k] = skirt;
         }
     }
-    const double centre = (double)(nc - 1) / 2.0;
-    const std::vector<double> w = fsamp_window(nc, wintype);
-    std::vector<cd> h((size_t)nc);
-    for (int n = 0; n < bins; n++) {
-        double acc = 0.0;
-        for (int k = 1; k < bins; k++) acc += 2.0 * mag[(size_t)k] * std::cos(kTwoPi * (n - centre) * k / nc);
-        const double tap = (1.0 / nc) * (mag[0] + acc);
-        h[(size_t)n] = cd(tap * w[(size_t)n], 0.0);
-        h[(size_t)(nc - 1 - n)] = cd(tap * w[(size_t)(nc - 1 - n)], 0.0);
+    return fsamp_even(nc, mag, wintype);
+}
+
+// eq_impulse (wdsp/eq.c:39-158), even N: the wanted magnitude is piecewise linear in dB over frequency through the nfreqs points
+// (F[1..nfreqs] Hz, G[1..nfreqs] dB), G[0] a preamp in dB added everywhere.  As there: 2 F / rate is clamped to [0, 1], the pairs are
+// sorted by frequency, the first and last gains are held out to 0 and to Nyquist, and the grid is the nc / 2 bin centres
+// (i + 1/2) / (nc / 2).  With ctfmode 0 the bins below the first and above the last point are the running fourth-power skirts of
+// fc_impulse above (floor 1e-100).  The taps come from the same frequency-sampling sum and window (fir_fsamp, fir.c:127-185).
+// (A tie between two clamped frequencies leaves the reference's qsort order open; the stable sort here keeps the input order.)
+std::vector<cd> eq_impulse(int N, int nfreqs, const double *F, const double *G, double samplerate, double scale, int ctfmode, int wintype)
+{
+    if (N & 1) throw std::runtime_error("eq_impulse: odd N is not used by the RXA chain");
+    if (nfreqs < 1) throw std::runtime_error("eq_impulse: no design points");
+    std::vector<double> fp((size_t)nfreqs + 2, 0.0), gp((size_t)nfreqs + 2, 0.0);
+    fp[0] = 0.0;
+    fp[(size_t)nfreqs + 1] = 1.0;
+    const double gpreamp = G[0];
+    std::vector<std::pair<double, double>> sary((size_t)nfreqs);
+    for (int i = 1; i <= nfreqs; i++) {
+        double f = 2.0 * F[i] / samplerate;
+        if (f < 0.0) f = 0.0;
+        if (f > 1.0) f = 1.0;
+        sary[(size_t)i - 1] = { f, G[i] };
     }
-    return h;
+    std::stable_sort(sary.begin(), sary.end(), [](const std::pair<double, double> &a, const std::pair<double, double> &b) { return a.first < b.first; });
+    for (int i = 1; i <= nfreqs; i++) { fp[(size_t)i] = sary[(size_t)i - 1].first; gp[(size_t)i] = sary[(size_t)i - 1].second; }
+    gp[0] = gp[1];
+    gp[(size_t)nfreqs + 1] = gp[(size_t)nfreqs];
+    const int mid = N / 2;
+    std::vector<double> A((size_t)mid + 1, 0.0);
+    for (int i = 0, j = 0; i < mid; i++) {
+        const double f = ((double)i + 0.5) / (double)mid;
+        while (f > fp[(size_t)j + 1]) j++;
+        const double frac = (f - fp[(size_t)j]) / (fp[(size_t)j + 1] - fp[(size_t)j]);
+        A[(size_t)i] = std::pow(10.0, 0.05 * (frac * gp[(size_t)j + 1] + (1.0 - frac) * gp[(size_t)j] + gpreamp)) * scale;
+    }
+    if (ctfmode == 0) {
+        const int low = (int)(fp[1] * mid - 0.5), high = (int)(fp[(size_t)nfreqs] * mid - 0.5);
+        double lowmag = A[(size_t)low], highmag = A[(size_t)high];
+        const double flow4 = std::pow((double)low / (double)mid, 4.0), fhigh4 = std::pow((double)high / (double)mid, 4.0);
+        for (int k = low - 1; k >= 0; k--) {
+            const double f = (double)k / (double)mid;
+            lowmag *= (f * f * f * f) / flow4;
+            if (lowmag < 1.0e-100) lowmag = 1.0e-100;
+            A[(size_t)k] = lowmag;
+        }
+        for (int k = high + 1; k < mid; k++) {
+            const double f = (double)k / (double)mid;
+            highmag *= fhigh4 / (f * f * f * f);
+            if (highmag < 1.0e-100) highmag = 1.0e-100;
+            A[(size_t)k] = highmag;
+        }
+    }
+    return fsamp_even(N, A, wintype);
+}
+
+// calc_fmd's pllpole (wdsp/fmd.c:39): the pole frequency of xfmd's loop, Hz
+double fm_pllpole(double zeta, double omegaN)
+{
+    return omegaN * std::sqrt(2.0 * zeta * zeta + 1.0 + std::sqrt((2.0 * zeta * zeta + 1.0) * (2.0 * zeta * zeta + 1.0) + 1)) / kTwoPi;
+}
+
+// calc_fmsq's noise filter (wdsp/fmsq.c:36-44) with create_rxa's constants (RXA.c:222-223): flat to fc = 5000 Hz, +3 dB at the loop's
+// pole, then the loop's own roll-off made up to 20 kHz; ctfmode 0, 4-term window
+std::vector<cd> fmsq_impulse(int nc, double samplerate, double scale)
+{
+    const double pllpole = fm_pllpole(1.0, 20000.0);
+    const double F[4] = { 0.0, 5000.0, pllpole, 20000.0 };
+    const double G[4] = { 0.0, 0.0, 3.0, +20.0 * std::log10(20000.0 / pllpole) };
+    return eq_impulse(nc, 3, F, G, samplerate, scale, 0, 0);
 }
 
 void host_fft(std::vector<cd> &x, int sign)

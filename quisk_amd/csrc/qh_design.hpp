@@ -25,6 +25,13 @@ ResamplerDesign design_resampler(int in_rate, int out_rate, double fc, int ncoef
 std::vector<cd> fc_impulse(int nc, double f0, double f1, double g0, double g1, int curve, double samplerate,
                            double scale, int ctfmode, int wintype);
 
+// WDSP's piecewise-linear-in-dB frequency-sampling design, wdsp/eq.c:39-158 through fir_fsamp (fir.c:127-185), even N (odd N throws).
+// F[1..nfreqs] in Hz and G[1..nfreqs] in dB are the design points (any order), G[0] the preamp in dB; F[0] is not read.
+std::vector<cd> eq_impulse(int N, int nfreqs, const double *F, const double *G, double samplerate, double scale, int ctfmode, int wintype);
+// calc_fmd's pllpole (wdsp/fmd.c:39) and the FM squelch's noise filter made from it (calc_fmsq, wdsp/fmsq.c:36-44; RXA.c:222-223)
+double fm_pllpole(double zeta, double omegaN);
+std::vector<cd> fmsq_impulse(int nc, double samplerate, double scale);
+
 // Unnormalised forward DFT (power of two), double data with long double twiddles.
 void host_fft(std::vector<cd> &x, int sign);
 

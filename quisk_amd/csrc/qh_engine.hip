@@ -133,6 +133,11 @@ void Engine::launch_ssql_flush()
     hipLaunchKernelGGL(ssql_flush_kernel, dim3((unsigned)nch), dim3(64), 0, stream, ssql_state);
 }
 
+void Engine::launch_fmsq_flush()
+{
+    hipLaunchKernelGGL(fmsq_flush_kernel, dim3((unsigned)((nch + 63) / 64)), dim3(64), 0, stream, fq_state, nch, fq_nready);
+}
+
 // ---- stage helpers ---------------------------------------------------------------------------
 // front: xshift + xresample(in) over all channels
 // part 0: the whole stage.  The mixed-mode path runs the FM channels and the others on two streams: part 1 = the oscillator's tile
@@ -276,8 +281,8 @@ void Engine::run_band(const double2 *src, long long src_stride, double2 *dst, lo
                       const int *list, int nlist, bool meter, bool egress, int det, double *det_out, long long det_stride,
                       const int *pairs, int npairs)
 {
-    const int sid = hist == hist_nbp ? 0 : hist == hist_bp1 ? 1 : hist == hist_de ? 2 : hist == hist_aud ? 3 : 4;
-    if (long_parts[sid] > 1) {
+    const int sid = hist == hist_nbp ? 0 : hist == hist_bp1 ? 1 : hist == hist_de ? 2 : hist == hist_aud ? 3 : hist == hist_fq ? 5 : 4;    // (5, xfmsq's noise filter: never partitioned)
+    if (sid < 5 && long_parts[sid] > 1) {
         // nc > 4096: y = sum_p h_p * (x delayed by 4096 p).  lcat holds the stage's last 16383 samples and the block in one row per
         // channel, so partition p is the ordinary tile pass (4096 taps, 8192 points, 4097 outputs per tile) over a row that begins
         // 4096 p samples further back; the partitions' outputs are added, the epilogue follows as a pass of its own.  (The callers
@@ -436,6 +441,26 @@ int Engine::chain_needs(ChainCall &k)
         if (c.nbp_run) { k.any_nbp = true; if (c.nbp_nc > k.nc_max) k.nc_max = c.nbp_nc; } else k.every_nbp = false;
         if (c.bp1_run) { k.any_bp1 = true; if (c.bp1_nc > k.nc_max) k.nc_max = c.bp1_nc; }
         if (c.fmd_run && c.fm_nc > k.nc_max) k.nc_max = c.fm_nc;
+        if (c.fmsq_run) {
+            const int ch = (int)(&c - cfg.data());
+            // (the reference would run its noise filter over the audio buffer xfmd last wrote, however long ago)
+            if (!c.fmd_run) return set_error(QH_ERR_UNSUPPORTED, "channel %d: FMSQ runs while the FM detector is off", ch);
+            // 2 F / rate of the design's upper two points would both clamp to 1.0 (eq.c:53-55) and the order qsort leaves them in is not defined
+            if ((double)dsp_rate <= 2.0 * fm_pllpole(1.0, 20000.0))
+                return set_error(QH_ERR_UNSUPPORTED, "FMSQ needs a dsp rate above twice the FM loop's pole frequency (%.0f Hz): %d is too low",
+                                 2.0 * fm_pllpole(1.0, 20000.0), dsp_rate);
+            if (c.fmsq_nc > kLongPart) return set_error(QH_ERR_UNSUPPORTED, "channel %d: FMSQ nc = %d exceeds %d", ch, c.fmsq_nc, kLongPart);
+            if (c.fmsq_nc > k.nc_max) k.nc_max = c.fmsq_nc;
+        }
+    }
+    {   // one noise filter design for the engine's FMSQ channels, as the FM channels share theirs (refresh_demod)
+        const ChanCfg *first = nullptr;
+        for (const ChanCfg &c : cfg) {
+            if (!c.fmsq_run) continue;
+            if (first && (first->fmsq_nc != c.fmsq_nc || first->fmsq_mp != c.fmsq_mp))
+                return set_error(QH_ERR_UNSUPPORTED, "FMSQ channels with different nc or mp in one engine");
+            if (!first) first = &c;
+        }
     }
     if (k.nc_max > kLongNcMax) return set_error(QH_ERR_UNSUPPORTED, "nc = %d exceeds %d", k.nc_max, kLongNcMax);
     return QH_OK;
@@ -528,6 +553,7 @@ int Engine::process_chain(const double *d_in, long long in_stride, double *d_out
     if (k.long_mode) if (int rc = long_buffers()) return rc;
     if (int rc = refresh_ap(k)) return rc;
     if (int rc = refresh_ssql(k)) return rc;
+    if (fq_list.n) if (int rc = grow(fq_noise, fq_noise_cap, buf_cap, nch)) return rc;     // the noise filter's output rows
     ev_used = 0;
 
     k.in = reinterpret_cast<const double2 *>(d_in); k.in_stride = in_stride;
@@ -916,6 +942,15 @@ int Engine::run_fm(ChainCall &k)
             hipLaunchKernelGGL(commit_fmdc_kernel, dim3((unsigned)((lists[L_FM].n + 255) / 256)), dim3(256), 0, stream, fm_pll_state, (const double *)fmdc_next, lists[L_FM].dev, lists[L_FM].n);
         }
     }
+    if (fq_list.n) {
+        // xfmsq's noise filter (fmsq.c:147) over the trigger, xfmd's audio ahead of de-emphasis (RXA.c:220): the FMSQ channels' rows only,
+        // with the stage's own mask and delay lines.  Where the audio is made in the load (fmdc_fused) it is loaded the same way here, two
+        // channels a tile (the taps are real); otherwise it lies in the rows of cur.
+        if (fmdc_src.a) band_fmdc = &fmdc_src;
+        run_band(cur, buf_cap, fq_noise, fq_noise_cap, nullptr, n_mid, mask_fq, 0, hist_fq, cur_fq, k.P, fq_list.dev, fq_list.n, false, false, 0, nullptr, 0,
+                 fmdc_src.a ? fq_pairs.dev : nullptr, np_fq);
+        band_fmdc = nullptr;
+    }
     {   // de-emphasis: real taps on a real signal, two channels per tile
         if (fmdc_src.a) band_fmdc = &fmdc_src;
         run_band(cur, buf_cap, other, buf_cap, nullptr, n_mid, mask_de, 0, hist_de, cur_de, k.P, lists[L_FM].dev, lists[L_FM].n, false, false, 0, nullptr, 0,
@@ -940,7 +975,19 @@ int Engine::run_fm(ChainCall &k)
     if (lists[L_LIM].n)      // detector limiter: lim_pre_gain 0.4, then its own wcpAGC (fmd.c:179-184)
         hipLaunchKernelGGL(agc_form == 1 ? wcpagc_seq_kernel : wcpagc_kernel, dim3((unsigned)lists[L_LIM].n), dim3(64), 0, stream, cur, buf_cap,
                            (int)n_mid, lists[L_LIM].dev, lim_prm, lim_state, 0.4);
+    run_fmsq(k);            // xfmsq, RXA.c:575
     return QH_OK;
+}
+
+// The squelch of the listed FM channels behind xfmd: averages, state machine and gain in place on their rows of cur -- or, where the
+// CTCSS notch has applied the output matrix and written the caller's rows (direct), on those: the gain is a real scalar on I and Q and
+// commutes with the matrix, a muted sample is stored as 0 either way, and no other channel's path changes because one squelch runs.
+void Engine::run_fmsq(const ChainCall &k)
+{
+    if (!fq_list.n) return;
+    hipLaunchKernelGGL(fmsq_kernel, dim3((unsigned)fq_list.n), dim3(64), 0, stream, k.direct ? k.out : k.cur, k.direct ? k.out_stride : buf_cap, (int)k.n_mid,
+                       (const int *)fq_list.dev, (const double2 *)fq_noise, fq_noise_cap, (const FmsqParam *)fq_prm, fq_state, (const double *)fq_cup,
+                       (const double *)fq_cdown);
 }
 
 // xsnba, with the tuning the setters left uploaded first

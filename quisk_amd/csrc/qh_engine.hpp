@@ -43,6 +43,7 @@
 #include "qh_snba.hpp"
 #include "qh_audio_peak.hpp"
 #include "qh_ssql.hpp"
+#include "qh_fmsq.hpp"
 #pragma clang diagnostic pop
 #include "qh_internal.hpp"
 
@@ -135,6 +136,11 @@ struct ChanCfg {
     double ssql_wthresh = 0.08, ssql_tau_mute = 0.1, ssql_tau_unmute = 0.1;
     bool ssql_dirty = true;
     bool ssql_on() const { return ssql_run != 0; }
+    // xfmsq (create_fmsq of create_rxa, RXA.c:214-234: run 0, tail 0.750, unmute 0.562 -- not 0.9 apart until SetRXAFMSQThreshold runs --,
+    // nc max(2048, dsp_size), mp 0); fmsq_hist_at: the ping-pong half that holds the noise filter's delay line while the stage is off
+    int fmsq_run = 0, fmsq_nc = 2048, fmsq_mp = 0, fmsq_hist_at = 0;
+    double fmsq_tail_thresh = 0.750, fmsq_unmute_thresh = 0.562;
+    bool fmsq_dirty = true;
     // (the new stages sit behind xwcpagc too, ahead of the panel: a fixed gain that changes while a peak still rings must not reach
     // the ringing tail, so it is applied at the AGC's spot for them as well; SSQL's detector reads amplitude, so it needs the gain too)
     bool fix_before() const
@@ -160,7 +166,7 @@ struct Engine {
     struct GraphSlot { hipGraphExec_t exec = nullptr; unsigned after = 0; };
     bool graph_on = false, graph_seen = false;
     GraphKey graph_key;
-    GraphSlot graph_slot[64];
+    GraphSlot graph_slot[128];
     long long graph_launches = 0;
     hipStream_t stream = nullptr;
     bool own_stream = false;
@@ -269,6 +275,24 @@ struct Engine {
     std::vector<SsqlParam> ssql_prm_h;
     int ssql_alloc();
     bool ssql_listed() const { return ssql_lists[0].n || ssql_lists[1].n; }
+    // xfmsq (qh_fmsq.hpp), made when a channel first runs it, in blocks of its own: the list of its channels and their pairs for the
+    // noise filter (as L_PAIRS_FM), parameters, state, the ramps, the noise filter's mask (one design for the engine's FMSQ channels, as
+    // the FM filters), its delay lines and its output rows [nch][fq_noise_cap]
+    ChanList fq_list, fq_pairs;
+    std::vector<int> fq_h, fq_pairs_h;
+    std::vector<char> fq_listed;
+    int *fq_list_block = nullptr;
+    int np_fq = 0;
+    FmsqParam *fq_prm = nullptr;
+    FmsqState *fq_state = nullptr;
+    double *fq_cup = nullptr, *fq_cdown = nullptr;
+    double2 *mask_fq = nullptr, *hist_fq[2] = { nullptr, nullptr }, *fq_noise = nullptr;
+    long long fq_noise_cap = 0;
+    int cur_fq = 0, fq_ntup = 0, fq_ntdown = 0, fq_nready = 0, fq_nc_built = 0, fq_mp_built = 0, fq_nfft_built = 0;
+    int fmsq_alloc();
+    int prm_fmsq(ChanCfg &c, int ch);
+    int fmsq_filter();
+    void launch_fmsq_flush();
     // snba: the blanker's parameters, taps, state and the Toeplitz-inverse scratch
     SnbaParam snba_prm{};
     double *snba_state = nullptr, *snba_hin = nullptr, *snba_hout = nullptr, *snba_scratch = nullptr;
@@ -340,8 +364,8 @@ struct Engine {
     SnotchState *sn_state = nullptr;
     double2 *mask_de = nullptr, *mask_aud = nullptr, *hist_de[2] = { nullptr, nullptr }, *hist_aud[2] = { nullptr, nullptr };
     int cur_de = 0, cur_aud = 0, fm_nc_built = 0, fm_mp = 0, fm_mp_built = 0, fm_nfft_built = 0;
-    unsigned flags() const { return (unsigned)(cur_front | cur_nbp << 1 | cur_bp1 << 2 | cur_de << 3 | cur_aud << 4 | cur_snb << 5); }
-    void set_flags(unsigned f) { cur_front = f & 1; cur_nbp = f >> 1 & 1; cur_bp1 = f >> 2 & 1; cur_de = f >> 3 & 1; cur_aud = f >> 4 & 1; cur_snb = f >> 5 & 1; }
+    unsigned flags() const { return (unsigned)(cur_front | cur_nbp << 1 | cur_bp1 << 2 | cur_de << 3 | cur_aud << 4 | cur_snb << 5 | cur_fq << 6); }
+    void set_flags(unsigned f) { cur_front = f & 1; cur_nbp = f >> 1 & 1; cur_bp1 = f >> 2 & 1; cur_de = f >> 3 & 1; cur_aud = f >> 4 & 1; cur_snb = f >> 5 & 1; cur_fq = f >> 6 & 1; }
     void drop_graphs() { for (auto &g : graph_slot) if (g.exec) { (void)hipGraphExecDestroy(g.exec); g.exec = nullptr; } }
     // Growing, rebuilding or re-uploading a device buffer: captured launch sequences hold its address and launches queued on either
     // stream may still use it, so nothing is freed or rewritten before quiesce() has waited for both streams and dropped the captures.
@@ -461,6 +485,7 @@ struct Engine {
     void run_audio_peak(const ChainCall &k);
     int refresh_ssql(const ChainCall &k);
     void run_ssql(const ChainCall &k);
+    void run_fmsq(const ChainCall &k);
     void run_output(const ChainCall &k);
     qh_rat *rsmpout = nullptr;          // xresample out (wdsp/RXA.c:596), only when out_rate != dsp_rate
     qh_rat *rsmpin = nullptr;           // xresample in for the rate ratios the overlap-save front stage does not cover (D == 0)

@@ -411,6 +411,7 @@ void Engine::build_lists(std::vector<int> (&h)[L_COUNT])
     std::vector<int> stale_cur, stale_other;
     int sam0 = 0;
     ssql_h[0].clear(); ssql_h[1].clear();
+    fq_h.clear(); fq_pairs_h.clear();
     for (int ch = 0; ch < nch; ch++) {
         const ChanCfg &c = cfg[(size_t)ch];
         if (c.amsq_run) h[L_AMSQ].push_back(ch);
@@ -424,6 +425,7 @@ void Engine::build_lists(std::vector<int> (&h)[L_COUNT])
         if (c.ap_on()) h[L_AP + (c.bp1_run ? 1 : 0)].push_back(ch);        // where the channel is behind bp1 at either position
         if (c.ssql_on()) ssql_h[c.bp1_run ? 1 : 0].push_back(ch);
         if (c.fmd_run && c.lim_run) h[L_LIM].push_back(ch);
+        if (c.fmd_run && c.fmsq_run) fq_h.push_back(ch);
         if (c.amd_run && c.amd_mode == 0) h[L_AM].push_back(ch);
         // SAM channels with sbmode 0 (no all-pass chains) first
         if (c.amd_run && c.amd_mode == 1) { if (c.sbmode == 0) h[L_SAM].insert(h[L_SAM].begin() + sam0++, ch); else h[L_SAM].push_back(ch); }
@@ -466,6 +468,8 @@ void Engine::build_lists(std::vector<int> (&h)[L_COUNT])
     np_fm = (int)h[L_PAIRS_FM].size() / 2; np_am = (int)h[L_PAIRS_AM].size() / 2; np_sam = (int)h[L_PAIRS_SAM].size() / 2;
     for (int i = 0; i < L_COUNT; i++) lists[i].n = (int)h[i].size();
     for (int b = 0; b < 2; b++) ssql_lists[b].n = (int)ssql_h[b].size();
+    for (size_t i = 0; i < fq_h.size(); i += 2) { fq_pairs_h.push_back(fq_h[i]); fq_pairs_h.push_back(i + 1 < fq_h.size() ? fq_h[i + 1] : fq_h[i]); }
+    fq_list.n = (int)fq_h.size(); np_fq = (int)fq_pairs_h.size() / 2;
 }
 
 // The stages made when a channel first runs one of them (the lists' counts say which)
@@ -474,6 +478,7 @@ int Engine::stages_alloc()
     const double rate = (double)dsp_rate;
     if ((lists[L_AP].n || lists[L_AP + 1].n) && !ap_prm) if (int rc = ap_alloc()) return rc;
     if (ssql_listed() && !ssql_prm) if (int rc = ssql_alloc()) return rc;
+    if (fq_list.n && !fq_prm) if (int rc = fmsq_alloc()) return rc;
     if ((lists[L_EMNR].n || lists[L_EMNR + 1].n || lists[L_EMNR + 2].n) && !emnr_state) if (int rc = emnr_alloc()) return rc;
     if (lists[L_SNBA].n && !snba_state) if (int rc = snba_alloc()) return rc;
     if (lists[L_AMSQ].n && !amsq_prm) {
@@ -567,6 +572,8 @@ int Engine::refresh_lists()
     if (int rc = follow_rows(fm_listed, &ChanCfg::fm_hist_at, cur_de, h[L_FM], { { hist_de, cur_de, kHistBand }, { hist_aud, cur_aud, kHistBand },
                                                                                 { lhist[2], cur_de, kLongHist }, { lhist[3], cur_aud, kLongHist } }))
         return rc;
+    // xfmsq's noise filter keeps its delay line while the stage is off (xfmsq with run 0 does not call its fircore, fmsq.c:143-147)
+    if (fq_prm) if (int rc = follow_rows(fq_listed, &ChanCfg::fmsq_hist_at, cur_fq, fq_h, { { hist_fq, cur_fq, kHistBand } })) return rc;
     std::vector<int> all((size_t)nch * (L_COUNT + 3));
     for (int i = 0; i < L_COUNT; i++) std::copy(h[i].begin(), h[i].end(), all.begin() + (lists[i].dev - list_block));
     std::vector<double> fg((size_t)nch);
@@ -578,6 +585,13 @@ int Engine::refresh_lists()
         ss.assign((size_t)nch * 2, 0);
         for (int b = 0; b < 2; b++) std::copy(ssql_h[b].begin(), ssql_h[b].end(), ss.begin() + (size_t)nch * b);
         QH_HIP(hipMemcpyAsync(ssql_list_block, ss.data(), ss.size() * sizeof(int), hipMemcpyHostToDevice, stream));
+    }
+    std::vector<int> fq;
+    if (fq_list_block) {
+        fq.assign((size_t)nch * 3, 0);
+        std::copy(fq_h.begin(), fq_h.end(), fq.begin());
+        std::copy(fq_pairs_h.begin(), fq_pairs_h.end(), fq.begin() + (size_t)nch);
+        QH_HIP(hipMemcpyAsync(fq_list_block, fq.data(), fq.size() * sizeof(int), hipMemcpyHostToDevice, stream));
     }
     QH_HIP(hipStreamSynchronize(stream));
     lists_dirty = false;
@@ -817,12 +831,14 @@ int Engine::refresh_demod()
         if (int rc = prm_emnr(c, ch)) return rc;
         if (int rc = prm_snba(c, ch)) return rc;
         if (int rc = prm_amsq(c, ch)) return rc;
+        if (int rc = prm_fmsq(c, ch)) return rc;
         if (int rc = prm_lms(c, ch)) return rc;
         if (int rc = prm_lim(c, ch)) return rc;
         if (int rc = prm_detect(c, ch)) return rc;
     }
     if (want_mp >= 0) fm_mp = want_mp;
-    return fm_filters(want_nc);
+    if (int rc = fm_filters(want_nc)) return rc;
+    return fmsq_filter();
 }
 
 // the frame advance and the two accumulators' sizes for an overlap (calc_snba, snb.c:45-65)
@@ -1339,6 +1355,80 @@ int Engine::refresh_ssql(const ChainCall &k)
     return QH_OK;
 }
 
+// ---- xfmsq (qh_fmsq.hpp)
+int Engine::fmsq_alloc()
+{
+    const double rate = (double)dsp_rate;
+    if (int rc = alloc(fq_list_block, 3LL * nch)) return rc;
+    fq_list.dev = fq_list_block; fq_pairs.dev = fq_list_block + (size_t)nch;
+    if (int rc = alloc(fq_prm, nch)) return rc;
+    if (int rc = alloc(fq_state, nch)) return rc;
+    if (int rc = alloc(mask_fq, kBandNfftMax)) return rc;
+    for (int i = 0; i < 2; i++) if (int rc = alloc(hist_fq[i], (long long)nch * kHistBand, true)) return rc;
+    // the ready delay (fmsq.c:153-154, tdelay 0.100: RXA.c:224): the additions of rstep that take ramp to tdelay, counted as they are made
+    {
+        const double rstep = 1.0 / rate, tdelay = 0.100;
+        double ramp = 0.0;
+        fq_nready = 0;
+        do { ramp += rstep; fq_nready++; } while (!(ramp >= tdelay));
+    }
+    // calc_fmsq (fmsq.c:50-78): avnoise 100, longnoise 1, MUTED, not ready; tup 0.050, tdown 0.010 (RXA.c:227-228), theta accumulates as there
+    FmsqState z{};
+    z.avnoise = 100.0; z.longnoise = 1.0; z.state = FQ_MUTED; z.count = 0; z.wait = fq_nready;
+    std::vector<FmsqState> st((size_t)nch, z);
+    QH_HIP(hipMemcpyAsync(fq_state, st.data(), st.size() * sizeof(FmsqState), hipMemcpyHostToDevice, stream));
+    fq_ntup = (int)(0.050 * rate); fq_ntdown = (int)(0.010 * rate);
+    std::vector<double> up((size_t)fq_ntup + 1), down((size_t)fq_ntdown + 1);
+    double delta = kPiRef / (double)fq_ntup, theta = 0.0;
+    for (int i = 0; i <= fq_ntup; i++) { up[(size_t)i] = 0.5 * (1.0 - std::cos(theta)); theta += delta; }
+    delta = kPiRef / (double)fq_ntdown; theta = 0.0;
+    for (int i = 0; i <= fq_ntdown; i++) { down[(size_t)i] = 0.5 * (1 + std::cos(theta)); theta += delta; }
+    if (int rc = alloc(fq_cup, (long long)up.size())) return rc;
+    if (int rc = alloc(fq_cdown, (long long)down.size())) return rc;
+    QH_HIP(hipMemcpyAsync(fq_cup, up.data(), up.size() * sizeof(double), hipMemcpyHostToDevice, stream));
+    QH_HIP(hipMemcpyAsync(fq_cdown, down.data(), down.size() * sizeof(double), hipMemcpyHostToDevice, stream));
+    QH_HIP(hipStreamSynchronize(stream));
+    fq_nc_built = 0;
+    for (ChanCfg &c : cfg) { c.fmsq_dirty = true; c.fmsq_hist_at = cur_fq; }
+    return QH_OK;
+}
+
+int Engine::prm_fmsq(ChanCfg &c, int ch)
+{
+    if (!fq_prm || !c.fmsq_dirty) return QH_OK;
+    // calc_fmsq, fmsq.c:48-53 with avtau 0.001, longtau 0.100, min_tail 0, max_tail 1.2 (RXA.c:225-226,231-232)
+    const double rate = (double)dsp_rate;
+    FmsqParam q{};
+    q.avm = std::exp(-1.0 / (rate * 0.001)); q.onem_avm = 1.0 - q.avm;
+    q.longavm = std::exp(-1.0 / (rate * 0.100)); q.onem_longavm = 1.0 - q.longavm;
+    q.tail_thresh = c.fmsq_tail_thresh; q.unmute_thresh = c.fmsq_unmute_thresh; q.min_tail = 0.000; q.max_tail = 1.200;
+    q.rate = rate; q.ntup = fq_ntup; q.ntdown = fq_ntdown;
+    if (int rc = put_row(fq_prm, ch, q)) return rc;
+    c.fmsq_dirty = false;
+    return QH_OK;
+}
+
+// The noise filter the engine's FMSQ channels share (calc_fmsq, fmsq.c:36-46; SetRXAFMSQNC / MP, fmsq.c:252-279), rebuilt when their
+// nc, mp or the band tile moved.  A minimum-phase design keeps the real parts of mp_imp's taps, so that the stage stays a real filter (two
+// channels a tile): the response of a real even filter has a real minimum-phase form, and what the cepstral method leaves beside it on
+// its 16 nc-point grid is 4e-10 of the largest tap at nc 4096.  With taps yr + j yi on the signal (t, t) the reference's noise is
+// sqrt(2 (yr^2 + yi^2)): the residue enters in second order (tests/test_design_eq_host.py holds it under 1e-12 of the noise's RMS).
+int Engine::fmsq_filter()
+{
+    if (!fq_prm || !fq_list.n) return QH_OK;
+    const ChanCfg &c = cfg[(size_t)fq_h[0]];        // (chain_needs has refused FMSQ channels that differ)
+    const int nfft_key = 2 * bnfft + (band2g ? 1 : 0);
+    if (c.fmsq_nc == fq_nc_built && c.fmsq_mp == fq_mp_built && nfft_key == fq_nfft_built) return QH_OK;
+    std::vector<cd> h = fmsq_impulse(c.fmsq_nc, (double)dsp_rate, 1.0 / (2.0 * dsp_size));
+    if (c.fmsq_mp) h = mp_imp(h, 16, 0);
+    for (auto &v : h) v = cd(v.real() * (double)(2 * dsp_size), 0.0);
+    if (int rc = upload(mask_fq, band_mask(h), stream)) return rc;
+    if (fq_nc_built && fq_nc_built != c.fmsq_nc)       // setNc_fircore zeroes the delay line
+        for (int i = 0; i < 2; i++) QH_HIP(hipMemsetAsync(hist_fq[i], 0, (size_t)nch * kHistBand * sizeof(double2), stream));
+    fq_nc_built = c.fmsq_nc; fq_mp_built = c.fmsq_mp; fq_nfft_built = nfft_key;
+    return QH_OK;
+}
+
 // flush_rxa (wdsp/RXA.c:527-559): NCO phase, resampler ring and fircore delay lines back to zero
 int Engine::flush()
 {
@@ -1376,6 +1466,10 @@ int Engine::flush()
     if (amsq_state) QH_HIP(hipMemsetAsync(amsq_state, 0, (size_t)nch * sizeof(AmsqState), stream));     // flush_amsq
     if (ap_state) QH_HIP(hipMemsetAsync(ap_state, 0, (size_t)nch * kApW * sizeof(double), stream));    // flush_cbl / _speak / _mpeak, RXA.c:553-555
     if (ssql_state) launch_ssql_flush();        // flush_ssql, RXA.c:556
+    if (fq_state) {                             // flush_fmsq, RXA.c:544
+        for (int i = 0; i < 2; i++) QH_HIP(hipMemsetAsync(hist_fq[i], 0, (size_t)nch * kHistBand * sizeof(double2), stream));
+        launch_fmsq_flush();
+    }
     if (demod_alloc) {                        // flush_amd / flush_fmd / flush_snotch
         QH_HIP(hipMemsetAsync(am_state, 0, (size_t)nch * sizeof(AmState), stream));
         QH_HIP(hipMemsetAsync(pll_state, 0, (size_t)nch * sizeof(PllState), stream));

@@ -244,7 +244,8 @@ int qh_rxa_RXASetNC(qh_rxa *h, int ch, int nc)
         if (c.nbp_nc != nc) { c.nbp_nc = nc; c.nbp_dirty = true; c.nbp_flush = true; c.snb_flush = true; c.long_live[0] = c.long_live[4] = false; }
         if (c.bp1_nc != nc) { c.bp1_nc = nc; c.bp1_dirty = true; c.bp1_flush = true; c.long_live[1] = false; }
         if (c.fm_nc != nc) c.long_live[2] = false;     // (setNc_fircore zeroes the delay lines, firmin.c:454-466: nothing long is held any more)
-        c.fm_nc = nc;                           // SetRXAFMNCde / SetRXAFMNCaud, wdsp/RXA.c:942-943
+        c.fm_nc = nc;                           // SetRXAFMNCde / SetRXAFMNCaud, wdsp/RXA.c:943-944
+        c.fmsq_nc = nc;                         // SetRXAFMSQNC, wdsp/RXA.c:942
     });
 }
 
@@ -336,6 +337,7 @@ int qh_rxa_RXASetMP(qh_rxa *h, int ch, int mp)
     mp = mp ? 1 : 0;
     FOR_CH(h, ch, {
         if (c.mp != mp) { c.mp = mp; c.nbp_dirty = true; c.bp1_dirty = true; c.demod_dirty = true; }
+        c.fmsq_mp = mp;                         // SetRXAFMSQMP, wdsp/RXA.c:955
     });
 }
 
@@ -563,6 +565,28 @@ int qh_rxa_SetRXASSQLTauUnMute(qh_rxa *h, int ch, double tau)
     FOR_CH(h, ch, { c.ssql_tau_unmute = tau; c.ssql_dirty = true; });
 }
 
+// xfmsq (fmsq.c:235-279).  The noise filter's nc and mp are taken up at the next process call (one design for the engine's FMSQ
+// channels); nothing here flushes the averages or the state machine, as there.
+int qh_rxa_SetRXAFMSQRun(qh_rxa *h, int ch, int run)
+{
+    FOR_CH(h, ch, {
+        run = run ? 1 : 0;
+        if (c.fmsq_run != run) { c.fmsq_run = run; h->e.lists_dirty = true; }
+    });
+}
+int qh_rxa_SetRXAFMSQThreshold(qh_rxa *h, int ch, double threshold)
+{
+    if (!std::isfinite(threshold)) return set_error(QH_ERR_INVALID, "SetRXAFMSQThreshold: threshold %g is not finite", threshold);
+    FOR_CH(h, ch, { c.fmsq_tail_thresh = threshold; c.fmsq_unmute_thresh = 0.9 * threshold; c.fmsq_dirty = true; });
+}
+int qh_rxa_SetRXAFMSQNC(qh_rxa *h, int ch, int nc)
+{
+    if (nc < 1 || (nc & (nc - 1)) || nc > kLongNcMax || (h && nc < h->e.dsp_size))
+        return set_error(QH_ERR_UNSUPPORTED, "nc must be a power of two in [dsp_size, %d]", kLongNcMax);
+    FOR_CH(h, ch, { c.fmsq_nc = nc; });
+}
+int qh_rxa_SetRXAFMSQMP(qh_rxa *h, int ch, int mp) { FOR_CH(h, ch, { c.fmsq_mp = mp ? 1 : 0; }); }
+
 int qh_rxa_SetRXAPanelGain1(qh_rxa *h, int ch, double g) { FOR_CH(h, ch, { c.gain1 = g; c.epi_dirty = true; }); }
 int qh_rxa_SetRXAPanelGain2(qh_rxa *h, int ch, double gI, double gQ) { FOR_CH(h, ch, { c.gain2I = gI; c.gain2Q = gQ; c.epi_dirty = true; }); }
 int qh_rxa_SetRXAPanelSelect(qh_rxa *h, int ch, int s) { FOR_CH(h, ch, { c.inselect = s; c.epi_dirty = true; }); }
@@ -750,6 +774,23 @@ int qh_rxa_debug_pll(qh_rxa *h, int check_only, int ch, double *out, int max)
     if (n > max) n = max;
     QH_HIP(hipMemcpy(out, e.pll_ends + (long long)ch * e.pll_ends_cap * kPllEndsW, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
     return (int)n;
+}
+
+// Diagnostics: channel ch's FM squelch at the end of the last call: avnoise, longnoise, state (0 MUTED, 1 INCREASE, 2 UNMUTED, 3 TAIL,
+// 4 DECREASE), count, ready.  Returns the doubles written (5), 0 while no channel of the engine has run the stage.
+int qh_rxa_debug_fmsq(qh_rxa *h, int ch, double *out, int max)
+{
+    if (!h) return set_error(QH_ERR_INVALID, "null engine");
+    QH_RXA_LOCK(h);
+    Engine &e = h->e;
+    if (ch < 0 || ch >= e.nch) return set_error(QH_ERR_INVALID, "channel %d out of range", ch);
+    if (!out || max < 5 || !e.fq_state) return 0;
+    QH_HIP(hipSetDevice(e.device));
+    QH_HIP(hipStreamSynchronize(e.stream));
+    FmsqState st;
+    QH_HIP(hipMemcpy(&st, e.fq_state + ch, sizeof(st), hipMemcpyDeviceToHost));
+    out[0] = st.avnoise; out[1] = st.longnoise; out[2] = (double)st.state; out[3] = (double)st.count; out[4] = st.wait == 0 ? 1.0 : 0.0;
+    return 5;
 }
 
 // Diagnostics: the lanes' states of the last time-tiled wcpAGC call, list slot `slot`: [tile][kAgcEndsW]

@@ -707,6 +707,11 @@ void SetRXASSQLRun(int channel, int run) { WDSP_SETTER(qh_rxa_SetRXASSQLRun(L.c-
 void SetRXASSQLThreshold(int channel, double threshold) { WDSP_SETTER(qh_rxa_SetRXASSQLThreshold(L.c->eng, 0, threshold)); }
 void SetRXASSQLTauMute(int channel, double tau_mute) { WDSP_SETTER(qh_rxa_SetRXASSQLTauMute(L.c->eng, 0, tau_mute)); }
 void SetRXASSQLTauUnMute(int channel, double tau_unmute) { WDSP_SETTER(qh_rxa_SetRXASSQLTauUnMute(L.c->eng, 0, tau_unmute)); }
+// the FM squelch, wdsp/fmsq.c:235-279
+void SetRXAFMSQRun(int channel, int run) { WDSP_SETTER(qh_rxa_SetRXAFMSQRun(L.c->eng, 0, run)); }
+void SetRXAFMSQThreshold(int channel, double threshold) { WDSP_SETTER(qh_rxa_SetRXAFMSQThreshold(L.c->eng, 0, threshold)); }
+void SetRXAFMSQNC(int channel, int nc) { WDSP_SETTER(qh_rxa_SetRXAFMSQNC(L.c->eng, 0, nc)); }
+void SetRXAFMSQMP(int channel, int mp) { WDSP_SETTER(qh_rxa_SetRXAFMSQMP(L.c->eng, 0, mp)); }
 // the LMS auto-notch / noise reduction, wdsp/anf.c:175-239, anr.c:175-238
 void SetRXAANFRun(int channel, int v) { WDSP_SETTER(qh_rxa_SetRXAANFRun(L.c->eng, 0, v)); }
 void SetRXAANFTaps(int channel, int v) { WDSP_SETTER(qh_rxa_SetRXAANFTaps(L.c->eng, 0, v)); }

@@ -73,10 +73,18 @@ def load():
                  ("SetRXAmpeakNpeaks", [vp, i, i]), ("SetRXAmpeakFilEnable", [vp, i, i, i]), ("SetRXAmpeakFilFreq", [vp, i, i, d]),
                  ("SetRXAmpeakFilBw", [vp, i, i, d]), ("SetRXAmpeakFilGain", [vp, i, i, d]),
                  ("SetRXASSQLRun", [vp, i, i]), ("SetRXASSQLThreshold", [vp, i, d]), ("SetRXASSQLTauMute", [vp, i, d]),
-                 ("SetRXASSQLTauUnMute", [vp, i, d])):
+                 ("SetRXASSQLTauUnMute", [vp, i, d]),
+                 ("SetRXAFMSQRun", [vp, i, i]), ("SetRXAFMSQThreshold", [vp, i, d]), ("SetRXAFMSQNC", [vp, i, i]), ("SetRXAFMSQMP", [vp, i, i])):
         f = getattr(L, "qh_rxa_" + n)
         f.argtypes = a
         f.restype = i
+    # the FM squelch's WDSP names (wdsp/fmsq.c:235-279) and its diagnostic
+    for n, a in (("SetRXAFMSQRun", [i, i]), ("SetRXAFMSQThreshold", [i, d]), ("SetRXAFMSQNC", [i, i]), ("SetRXAFMSQMP", [i, i])):
+        f = getattr(L, n)
+        f.argtypes = a
+        f.restype = None
+    L.qh_rxa_debug_fmsq.argtypes = [vp, i, C.POINTER(d), i]
+    L.qh_rxa_debug_fmsq.restype = i
     L.qh_rxa_SetEMNRTables.argtypes = [vp, vp, vp, vp, vp, d, d, d, d]
     L.qh_rxa_process.argtypes = [vp, vp, ll, vp, ll, i]
     L.qh_rxa_process.restype = i

@@ -22,7 +22,8 @@ _SETTERS = ("SetRXAMode", "RXASetNC", "SetRXAShiftRun", "RXANBPSetRun", "SetRXAB
             "SetRXAANRRun", "SetRXAANRTaps", "SetRXAANRDelay", "SetRXAANRPosition", "SetRXAANRGain", "SetRXAANRLeakage", "SetRXAANRVals",
             "SetRXACBLRun", "SetRXASPCWRun", "SetRXASPCWFreq", "SetRXASPCWBandwidth", "SetRXASPCWGain", "SetRXAmpeakRun",
             "SetRXAmpeakNpeaks", "SetRXAmpeakFilEnable", "SetRXAmpeakFilFreq", "SetRXAmpeakFilBw", "SetRXAmpeakFilGain",
-            "SetRXASSQLRun", "SetRXASSQLThreshold", "SetRXASSQLTauMute", "SetRXASSQLTauUnMute")
+            "SetRXASSQLRun", "SetRXASSQLThreshold", "SetRXASSQLTauMute", "SetRXASSQLTauUnMute",
+            "SetRXAFMSQRun", "SetRXAFMSQThreshold", "SetRXAFMSQNC", "SetRXAFMSQMP")
 
 
 class AudioFormat(C.Structure):
@@ -144,6 +145,14 @@ class RxaEngine:
 
     def pll_repairs(self):
         return self._L.qh_rxa_pll_repairs(self._h)
+
+    def debug_fmsq(self, ch):
+        """diagnostics: the FM squelch of channel ch at the last call's end: (avnoise, longnoise, state, count, ready), or None while no
+        channel of the engine has run it"""
+        buf = (C.c_double * 5)()
+        n = self._L.qh_rxa_debug_fmsq(self._h, ch, buf, 5)
+        check(n if n < 0 else 0)
+        return (buf[0], buf[1], int(buf[2]), int(buf[3]), int(buf[4])) if n == 5 else None
 
     def debug_agc(self, form):
         """diagnostics: 0 = time tiles for long calls (default), 1 = the sample-by-sample form of the wcpAGC loop, 2 = 64 samples per step"""
