@@ -161,6 +161,23 @@ int qh_rxa_SetRXAFMSQRun(qh_rxa *e, int ch, int run);                           
 int qh_rxa_SetRXAFMSQThreshold(qh_rxa *e, int ch, double threshold);            /* wdsp/fmsq.c:243-250: tail = threshold, unmute = 0.9 threshold */
 int qh_rxa_SetRXAFMSQNC(qh_rxa *e, int ch, int nc);                             /* wdsp/fmsq.c:252-267 */
 int qh_rxa_SetRXAFMSQMP(qh_rxa *e, int ch, int mp);                             /* wdsp/fmsq.c:269-279 */
+/* xeqp, the receive equalizer between xsnba and xanf (wdsp/RXA.c:579), off at create with ten frequencies 32 ... 16000 Hz at 0 dB, nc
+ * max(2048, dsp_size), mp 0, ctfmode 0, wintype 0 (RXA.c:257-275).  The filter is designed on the host (eq_impulse, eq.c:39-158) at the
+ * next process call and runs as a fircore stage of its own with one design per channel.  While a channel's equalizer is off nothing of it
+ * runs and its delay line stays as it was; SetRXAEQNC with a new nc zeroes the line, every other setter keeps it; qh_rxa_flush zeroes it
+ * (flush_eqp).  F and G hold nfreqs + 1 values: G[0] is the preamp in dB, F[0] is not read.  Refused by the setter with QH_ERR_INVALID,
+ * changing nothing: an nc that is not a power of two in [dsp_size, 65536], nfreqs < 1, a value of F or G that is not finite, a null
+ * pointer.  Refused with QH_ERR_UNSUPPORTED at the next process call while the channel runs the stage, nothing run: an nc above 4096,
+ * and a profile in which two frequencies coincide after the clamp to [0, dsp_rate / 2] while their gains differ (the reference's qsort
+ * leaves their order undefined, eq.c:53-63; coinciding frequencies with equal gains are accepted). */
+int qh_rxa_SetRXAEQRun(qh_rxa *e, int ch, int run);                             /* wdsp/eq.c:242-248 */
+int qh_rxa_SetRXAEQNC(qh_rxa *e, int ch, int nc);                               /* wdsp/eq.c:250-265 */
+int qh_rxa_SetRXAEQMP(qh_rxa *e, int ch, int mp);                               /* wdsp/eq.c:267-277 */
+int qh_rxa_SetRXAEQProfile(qh_rxa *e, int ch, int nfreqs, const double *F, const double *G);   /* wdsp/eq.c:279-296 */
+int qh_rxa_SetRXAEQCtfmode(qh_rxa *e, int ch, int mode);                        /* wdsp/eq.c:298-308 */
+int qh_rxa_SetRXAEQWintype(qh_rxa *e, int ch, int wintype);                     /* wdsp/eq.c:310-320 */
+int qh_rxa_SetRXAGrphEQ(qh_rxa *e, int ch, const int *rxeq);                    /* wdsp/eq.c:322-346: 4 values: preamp, then 150 and 400 Hz (both rxeq[1]), 1500, 6000 Hz; ctfmode 0 */
+int qh_rxa_SetRXAGrphEQ10(qh_rxa *e, int ch, const int *rxeq);                  /* wdsp/eq.c:348-377: 11 values: preamp, then 32 ... 16000 Hz; ctfmode 0 */
 int qh_rxa_SetRXAAMSQThreshold(qh_rxa *e, int ch, double threshold_db);
 int qh_rxa_SetRXAAMSQMaxTail(qh_rxa *e, int ch, double tail_seconds);
 /* xanf / xanr (wdsp/anf.c:82-133, anr.c:82-133), setters wdsp/anf.c:175-239 and anr.c:175-238; which position (0 before
@@ -216,6 +233,7 @@ int qh_rxa_process_host(qh_rxa *e, const double *h_in, long long in_stride, doub
 long long qh_rxa_pll_repairs(qh_rxa *h);
 int qh_rxa_debug_pll(qh_rxa *h, int check_only, int ch, double *out, int max);   /* diagnostics, see qh_rxa_api.hip */
 int qh_rxa_debug_fmsq(qh_rxa *h, int ch, double *out, int max);                      /* diagnostics: avnoise, longnoise, state, count, ready at the last call's end (wdsp/fmsq.c:141-205) */
+int qh_rxa_debug_eqp(qh_rxa *h, int ch, double *taps, int max);                      /* diagnostics: returns nc and copies the complex taps behind the mask the channel's equalizer last got (2 nc doubles; a setter's design shows after the next process call that runs it); 0 while no channel of the engine has run the stage */
 int qh_rxa_debug_agc(qh_rxa *h, int form);                                         /* diagnostics: 0 time tiles for long calls (default), 1 sample by sample, 2 batches of 64 */
 int qh_rxa_debug_agc_ends(qh_rxa *h, int slot, double *out, int max);                /* diagnostics, see qh_rxa_api.hip */
 long long qh_rxa_agc_repairs(qh_rxa *h);                                            /* wcpAGC time tiles the verify pass re-ran in order */
@@ -392,6 +410,14 @@ void SetRXAFMSQRun(int channel, int run);                                       
 void SetRXAFMSQThreshold(int channel, double threshold);                         /* wdsp/fmsq.c:243-250 */
 void SetRXAFMSQNC(int channel, int nc);                                          /* wdsp/fmsq.c:252-267 */
 void SetRXAFMSQMP(int channel, int mp);                                          /* wdsp/fmsq.c:269-279 */
+void SetRXAEQRun(int channel, int run);                                          /* wdsp/eq.c:242-248 */
+void SetRXAEQNC(int channel, int nc);                                            /* wdsp/eq.c:250-265 */
+void SetRXAEQMP(int channel, int mp);                                            /* wdsp/eq.c:267-277 */
+void SetRXAEQProfile(int channel, int nfreqs, double *F, double *G);             /* wdsp/eq.c:279-296 */
+void SetRXAEQCtfmode(int channel, int mode);                                     /* wdsp/eq.c:298-308 */
+void SetRXAEQWintype(int channel, int wintype);                                  /* wdsp/eq.c:310-320 */
+void SetRXAGrphEQ(int channel, int *rxeq);                                       /* wdsp/eq.c:322-346 */
+void SetRXAGrphEQ10(int channel, int *rxeq);                                     /* wdsp/eq.c:348-377 */
 void SetRXAAMSQThreshold(int channel, double threshold);                         /* wdsp/amsq.c:224-232, dB */
 void SetRXAAMSQMaxTail(int channel, double tail);                                /* wdsp/amsq.c:234-243, seconds */
 void SetRXAEMNRRun(int channel, int run);                                        /* wdsp/emnr.c:1096-1110; needs the files `calculus` and

@@ -281,7 +281,7 @@ void Engine::run_band(const double2 *src, long long src_stride, double2 *dst, lo
                       const int *list, int nlist, bool meter, bool egress, int det, double *det_out, long long det_stride,
                       const int *pairs, int npairs)
 {
-    const int sid = hist == hist_nbp ? 0 : hist == hist_bp1 ? 1 : hist == hist_de ? 2 : hist == hist_aud ? 3 : hist == hist_fq ? 5 : 4;    // (5, xfmsq's noise filter: never partitioned)
+    const int sid = hist == hist_nbp ? 0 : hist == hist_bp1 ? 1 : hist == hist_de ? 2 : hist == hist_aud ? 3 : (hist == hist_fq || hist == hist_eqp) ? 5 : 4;    // (5, xfmsq's noise filter and xeqp: never partitioned)
     if (sid < 5 && long_parts[sid] > 1) {
         // nc > 4096: y = sum_p h_p * (x delayed by 4096 p).  lcat holds the stage's last 16383 samples and the block in one row per
         // channel, so partition p is the ordinary tile pass (4096 taps, 8192 points, 4097 outputs per tile) over a row that begins
@@ -453,6 +453,15 @@ int Engine::chain_needs(ChainCall &k)
             if (c.fmsq_nc > k.nc_max) k.nc_max = c.fmsq_nc;
         }
     }
+    for (const ChanCfg &c : cfg) {
+        if (!c.eqp_run) continue;
+        const int ch = (int)(&c - cfg.data());
+        k.any_eqp = true;
+        if (c.eqp_nc > kLongPart) return set_error(QH_ERR_UNSUPPORTED, "channel %d: EQ nc = %d exceeds %d", ch, c.eqp_nc, kLongPart);
+        // qsort leaves the order of equal keys undefined (eq.c:53-63), and with it the design
+        if (c.eqp_tie) return set_error(QH_ERR_UNSUPPORTED, "channel %d: two EQ frequencies coincide in [0, rate / 2] while their gains differ", ch);
+        if (c.eqp_nc > k.nc_max) k.nc_max = c.eqp_nc;
+    }
     {   // one noise filter design for the engine's FMSQ channels, as the FM channels share theirs (refresh_demod)
         const ChanCfg *first = nullptr;
         for (const ChanCfg &c : cfg) {
@@ -539,12 +548,13 @@ int Engine::process_chain(const double *d_in, long long in_stride, double *d_out
     // The three meters of xrxa (adc, S, agc: RXA.c:566,569,589) ride on the nbp0 launch when the chain is linear (nbp0 runs,
     // bp1 does not, fixed AGC gain): the band tile then starts on a multiple of 256 samples so that a register holds one
     // 64-sample chunk per wavefront.  Any other chain takes the per-mode path with the stand-alone meter kernel.
-    k.meters_fused = meters_on && !k.mixed && k.any_nbp && !k.any_bp1 && dsp_size >= 64 && dsp_size <= 2048 && !k.long_mode;
+    k.meters_fused = meters_on && !k.mixed && k.any_nbp && !k.any_bp1 && !k.any_eqp && dsp_size >= 64 && dsp_size <= 2048 && !k.long_mode;
     if (meters_on && !k.meters_fused) k.mixed = true;
     if (meters_on) if (int rc = meters_alloc()) return rc;
     if (int rc = refresh_params()) return rc;
     if (k.mixed) if (int rc = refresh_demod()) return rc;
     if (lists[L_SNBA].n) if (int rc = refresh_params()) return rc;       // bpsnba's mask needs the buffers the line above may just have made
+    if (k.any_eqp || eq_lists_dirty) if (int rc = refresh_eqp()) return rc;
 
     k.n_in = (long long)nblk * dsp_insize;
     k.n_mid = (long long)nblk * dsp_size;
@@ -562,7 +572,7 @@ int Engine::process_chain(const double *d_in, long long in_stride, double *d_out
     k.P = band6k ? kOsfir6kP : band2g ? kOsfir8kP : k.meters_fused ? ((k.nc_max - 1 + 255) / 256) * 256 : k.long_mode ? kLongPart - 1 : k.nc_max - 1;
     // audio egress (qh_rxa_process_audio): the narrowing rides in the store of the last kernel when that is an overlap-save
     // band stage or the per-mode path's output pass; other endings write complex doubles to the staging rows and narrow after
-    k.eg_fused = eg.kind && (k.mixed ? lists[L_AMSQ].n == 0 : ((k.any_nbp || k.any_bp1) && !k.long_mode));
+    k.eg_fused = eg.kind && (k.mixed ? lists[L_AMSQ].n == 0 : ((k.any_nbp || k.any_bp1 || k.any_eqp) && !k.long_mode));
     if (eg.kind && !k.eg_fused) {
         if (int rc = ensure_abuf(k.n_mid)) return rc;
         k.out = abuf; k.out_stride = abuf_cap;
@@ -579,6 +589,7 @@ int Engine::process_chain(const double *d_in, long long in_stride, double *d_out
     if (lists[L_SNB + 1].n) snb_inplace(k, lists[L_SNB + 1].dev, lists[L_SNB + 1].n);       // xbpsnbain / xbpsnbaout at position 1 (RXA.c:576-577)
     if (lists[L_SNB].n || lists[L_SNB + 1].n) cur_snb ^= 1;
     if (int rc = run_snba(k)) return rc;            // xsnba, RXA.c:578
+    eqp_inplace(k);                                 // xeqp, RXA.c:579
     // xanf, xanr, xbandpass(bp1) at position 0, xwcpagc, then the same three at position 1 (RXA.c:579-586).  The two bp1
     // launches work on disjoint channel rows of one ping-pong history pair, so the pair flips once for both.
     lms_at(k, 0, k.cur);
@@ -595,7 +606,7 @@ int Engine::process_chain(const double *d_in, long long in_stride, double *d_out
 int Engine::run_linear(ChainCall &k)
 {
     const long long n_mid = k.n_mid;
-    const int nstage = 1 + (k.any_nbp ? 1 : 0) + (k.any_bp1 ? 1 : 0);
+    const int nstage = 1 + (k.any_nbp ? 1 : 0) + (k.any_eqp ? 1 : 0) + (k.any_bp1 ? 1 : 0);
     int stage = 0, which = 0;
     const double2 *cur = k.in;
     long long cur_stride = k.in_stride;
@@ -619,10 +630,29 @@ int Engine::run_linear(ChainCall &k)
                                           (size_t)n_mid * sizeof(double2), (size_t)nch, hipMemcpyDeviceToDevice, stream));
         cur = dst; cur_stride = dst_stride; stage++;
     }
-    for (int f = 0; f < 2; f++) {
-        if (f == 0 ? !k.any_nbp : !k.any_bp1) continue;
+    for (int f = 0; f < 3; f++) {       // xnbp, xeqp, xbandpass (RXA.c:568,579,582)
+        if (f == 0 ? !k.any_nbp : f == 1 ? !k.any_eqp : !k.any_bp1) continue;
         long long dst_stride;
         double2 *dst = dst_of(stage, dst_stride);
+        if (f == 1) {
+            // the equalizer's channels through their tiles, each with its own mask and delay line; a channel that does not run it is
+            // passed on as it is (xeqp with run 0 copies, eq.c:206-207, and its fircore's delay line stays as it was)
+            const bool last = stage == nstage - 1;
+            run_band(cur, cur_stride, dst, dst_stride, last ? epi : nullptr, n_mid, mask_eqp, kBandNfftMax, hist_eqp, cur_eqp, k.P, eq_list.dev, eq_list.n,
+                     false, k.eg_fused && last);
+            if (eq_rest.n) {
+                const long long per = (n_mid + NT - 1) / NT;
+                const dim3 g((unsigned)(per < 1024 ? per : 1024), (unsigned)eq_rest.n);
+                if (!last) hipLaunchKernelGGL(copy_rows_kernel, g, dim3(NT), 0, stream, cur, dst, buf_cap, (int)n_mid, (const int *)eq_rest.dev);
+                else {
+                    auto *pass = k.eg_fused ? &pointwise_kernel<double, false, true> : &pointwise_kernel<double, false>;
+                    hipLaunchKernelGGL(pass, g, dim3(NT), 0, stream, cur, cur_stride, dst, dst_stride, (int)n_mid, (const unsigned long long *)nullptr,
+                                       (const unsigned long long *)nullptr, (const EpiParam *)epi, (const int *)eq_rest.dev, k.eg_fused ? eg : EgressFmt{});
+                }
+            }
+            cur = dst; cur_stride = dst_stride; stage++;
+            continue;
+        }
         if (k.meters_fused) if (int rc = ensure_meter_partials(n_mid, bnfft - k.P)) return rc;
         run_band(cur, cur_stride, dst, dst_stride, stage == nstage - 1 ? epi : nullptr, n_mid,
                  f == 0 ? mask_nbp : mask_bp1, kBandNfftMax, f == 0 ? hist_nbp : hist_bp1, f == 0 ? cur_nbp : cur_bp1, k.P,
@@ -659,7 +689,7 @@ int Engine::plan_mixed(ChainCall &k)
     k.fm_theta_fused = k.split && k.any_nbp && !band6k && !band2g && bnfft == kNfft && !(dbg_forms & 8);
     bool no_lms = true;
     for (int f = 0; f < 2; f++) for (int p = 0; p < 3; p++) no_lms = no_lms && !lists[L_LMS + 3 * f + p].n;
-    k.direct = k.split && !(dbg_forms & 2) && k.every_nbp && !eg.kind && !lists[L_LIM].n && !lists[L_AGC_CUR].n && !lists[L_AGC_OTHER].n && !lists[L_SNBA].n && !lists[L_SNB + 1].n && no_lms &&
+    k.direct = k.split && !(dbg_forms & 2) && !eq_list.n && k.every_nbp && !eg.kind && !lists[L_LIM].n && !lists[L_AGC_CUR].n && !lists[L_AGC_OTHER].n && !lists[L_SNBA].n && !lists[L_SNB + 1].n && no_lms &&
                !lists[L_EMNR].n && !lists[L_EMNR + 1].n && !lists[L_EMNR + 2].n && !lists[L_FIX].n && !lists[L_FIX + 1].n && !lists[L_BP1P + 1].n && lists[L_BP1P].n == lists[L_BP1].n && lists[L_RB].n == lists[L_BP1].n &&
                lists[L_USB].n + lists[L_FM].n == lists[L_PLAIN].n && !lists[L_AP].n && !lists[L_AP + 1].n && !ssql_listed() &&
                // the first stores to `out` come while other channels' input is still being read: not for a caller that works in place
@@ -777,6 +807,17 @@ void Engine::snb_inplace(const ChainCall &k, const int *list, int n)
     long long per = (k.n_mid + NT - 1) / NT;
     hipLaunchKernelGGL(copy_rows_kernel, dim3((unsigned)(per < 1024 ? per : 1024), (unsigned)n), dim3(NT), 0, stream, k.other, k.cur, buf_cap,
                        (int)k.n_mid, list);
+}
+
+// xeqp (RXA.c:579) on the listed channels' rows of cur, through the rows of other: every channel of the call lies in cur here, behind
+// its detector, bpsnba and xsnba.  (The stores that write the caller's rows ahead of this point are off for such a call: plan_mixed.)
+void Engine::eqp_inplace(const ChainCall &k)
+{
+    if (!eq_list.n) return;
+    run_band(k.cur, buf_cap, k.other, buf_cap, nullptr, k.n_mid, mask_eqp, kBandNfftMax, hist_eqp, cur_eqp, k.P, eq_list.dev, eq_list.n);
+    long long per = (k.n_mid + NT - 1) / NT;
+    hipLaunchKernelGGL(copy_rows_kernel, dim3((unsigned)(per < 1024 ? per : 1024), (unsigned)eq_list.n), dim3(NT), 0, stream, k.other, k.cur, buf_cap,
+                       (int)k.n_mid, (const int *)eq_list.dev);
 }
 
 // Segment scans: one 16-wavefront workgroup per channel fills one CU.  With fewer channels of a kind than the chip has CUs the

@@ -141,6 +141,13 @@ struct ChanCfg {
     int fmsq_run = 0, fmsq_nc = 2048, fmsq_mp = 0, fmsq_hist_at = 0;
     double fmsq_tail_thresh = 0.750, fmsq_unmute_thresh = 0.562;
     bool fmsq_dirty = true;
+    // xeqp (create_eqp of create_rxa, RXA.c:257-275: run 0, nc max(2048, dsp_size) -- Engine::init --, mp 0, ten frequencies with 0 dB each,
+    // ctfmode 0, wintype 0).  eqp_F / eqp_G: nfreqs + 1 entries, G[0] the preamp, F[0] not read.  eqp_flush: SetRXAEQNC took a new nc
+    // (setNc_fircore zeroes the delay line); eqp_tie: two frequencies coincide after eq_impulse's clamp while their gains differ;
+    // eqp_hist_at: the ping-pong half that holds the delay line while the stage is off
+    int eqp_run = 0, eqp_nc = 2048, eqp_mp = 0, eqp_ctfmode = 0, eqp_wintype = 0, eqp_hist_at = 0;
+    std::vector<double> eqp_F = { 0.0, 32.0, 63.0, 125.0, 250.0, 500.0, 1000.0, 2000.0, 4000.0, 8000.0, 16000.0 }, eqp_G = std::vector<double>(11, 0.0);
+    bool eqp_dirty = true, eqp_flush = false, eqp_tie = false;
     // (the new stages sit behind xwcpagc too, ahead of the panel: a fixed gain that changes while a peak still rings must not reach
     // the ringing tail, so it is applied at the AGC's spot for them as well; SSQL's detector reads amplitude, so it needs the gain too)
     bool fix_before() const
@@ -166,7 +173,7 @@ struct Engine {
     struct GraphSlot { hipGraphExec_t exec = nullptr; unsigned after = 0; };
     bool graph_on = false, graph_seen = false;
     GraphKey graph_key;
-    GraphSlot graph_slot[128];
+    GraphSlot graph_slot[256];
     long long graph_launches = 0;
     hipStream_t stream = nullptr;
     bool own_stream = false;
@@ -293,6 +300,20 @@ struct Engine {
     int prm_fmsq(ChanCfg &c, int ch);
     int fmsq_filter();
     void launch_fmsq_flush();
+    // xeqp (wdsp/eq.c:166-208), made when a channel first runs it, in blocks of their own: the list of its channels and of the others
+    // (the linear path passes those on in a pointwise pass), one mask row per channel (EQ profiles are per channel, as bp1's designs) and
+    // the delay lines [2][nch][kHistBand]
+    ChanList eq_list, eq_rest;
+    std::vector<int> eq_h, eq_rest_h;
+    std::vector<char> eq_listed;
+    std::vector<std::vector<cd>> eq_taps_h;     // per channel: the taps behind the mask row last uploaded (qh_rxa_debug_eqp); empty until then
+    int *eq_list_block = nullptr;
+    double2 *mask_eqp = nullptr, *hist_eqp[2] = { nullptr, nullptr };
+    int cur_eqp = 0, eq_nfft_built = 0;
+    bool eq_lists_dirty = false;
+    std::vector<cd> eqp_taps(const ChanCfg &c) const;
+    int eqp_alloc();
+    int refresh_eqp();
     // snba: the blanker's parameters, taps, state and the Toeplitz-inverse scratch
     SnbaParam snba_prm{};
     double *snba_state = nullptr, *snba_hin = nullptr, *snba_hout = nullptr, *snba_scratch = nullptr;
@@ -364,8 +385,8 @@ struct Engine {
     SnotchState *sn_state = nullptr;
     double2 *mask_de = nullptr, *mask_aud = nullptr, *hist_de[2] = { nullptr, nullptr }, *hist_aud[2] = { nullptr, nullptr };
     int cur_de = 0, cur_aud = 0, fm_nc_built = 0, fm_mp = 0, fm_mp_built = 0, fm_nfft_built = 0;
-    unsigned flags() const { return (unsigned)(cur_front | cur_nbp << 1 | cur_bp1 << 2 | cur_de << 3 | cur_aud << 4 | cur_snb << 5 | cur_fq << 6); }
-    void set_flags(unsigned f) { cur_front = f & 1; cur_nbp = f >> 1 & 1; cur_bp1 = f >> 2 & 1; cur_de = f >> 3 & 1; cur_aud = f >> 4 & 1; cur_snb = f >> 5 & 1; cur_fq = f >> 6 & 1; }
+    unsigned flags() const { return (unsigned)(cur_front | cur_nbp << 1 | cur_bp1 << 2 | cur_de << 3 | cur_aud << 4 | cur_snb << 5 | cur_fq << 6 | cur_eqp << 7); }
+    void set_flags(unsigned f) { cur_front = f & 1; cur_nbp = f >> 1 & 1; cur_bp1 = f >> 2 & 1; cur_de = f >> 3 & 1; cur_aud = f >> 4 & 1; cur_snb = f >> 5 & 1; cur_fq = f >> 6 & 1; cur_eqp = f >> 7 & 1; }
     void drop_graphs() { for (auto &g : graph_slot) if (g.exec) { (void)hipGraphExecDestroy(g.exec); g.exec = nullptr; } }
     // Growing, rebuilding or re-uploading a device buffer: captured launch sequences hold its address and launches queued on either
     // stream may still use it, so nothing is freed or rewritten before quiesce() has waited for both streams and dropped the captures.
@@ -460,7 +481,7 @@ struct Engine {
         long long in_stride = 0, out_stride = 0;
         double2 *out = nullptr;
         double2 *cur = nullptr, *other = nullptr;       // the mixed path's working rows (buf[0] / buf[1], swapped as stages write)
-        bool any_nbp = false, any_bp1 = false, every_nbp = true, mixed = false, long_mode = false, meters_fused = false, eg_fused = false;
+        bool any_nbp = false, any_bp1 = false, any_eqp = false, every_nbp = true, mixed = false, long_mode = false, meters_fused = false, eg_fused = false;
         bool split = false, fm_theta_fused = false, direct = false, am_fused = false, am_lv_fused = false, side = false;
         bool agc_direct = false;                        // set where xwcpagc runs (run_agc)
     };
@@ -478,6 +499,7 @@ struct Engine {
     int run_fm(ChainCall &k);
     void snb_inplace(const ChainCall &k, const int *list, int n);
     int run_snba(const ChainCall &k);
+    void eqp_inplace(const ChainCall &k);
     void lms_at(const ChainCall &k, int pos, double2 *b);
     void bp1_at(const ChainCall &k, int pos);
     int run_agc(ChainCall &k);

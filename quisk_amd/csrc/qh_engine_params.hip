@@ -74,6 +74,7 @@ int Engine::init()
         if (!rsmpout) return QH_ERR_HIP;
     }
     cfg.assign((size_t)nch, ChanCfg());
+    for (ChanCfg &c : cfg) c.eqp_nc = std::max(2048, dsp_size);        // create_eqp's nc, RXA.c:265
     snba_tune_h.assign((size_t)nch, SnbaTune{ 64, 2, 10, 2, 2, 0, 8.0, 20.0, 0.5 });         // create_snba's arguments, RXA.c:183-202
 
     std::vector<cd> tw = fft_twiddle_table(kNfft);
@@ -1429,6 +1430,77 @@ int Engine::fmsq_filter()
     return QH_OK;
 }
 
+// ---- xeqp (wdsp/eq.c:166-208)
+// The taps a channel's fircore holds: eq_impulse as create_eqp and the setters call it (eq.c:185), through mp_imp when mp is set
+// (calc_fircore, firmin.c:327-328), its complex taps kept as fircore uses them.  Scale 1 / (2 dsp_size), as there.
+std::vector<cd> Engine::eqp_taps(const ChanCfg &c) const
+{
+    std::vector<cd> h = eq_impulse(c.eqp_nc, (int)c.eqp_F.size() - 1, c.eqp_F.data(), c.eqp_G.data(), (double)dsp_rate, 1.0 / (2.0 * dsp_size), c.eqp_ctfmode,
+                                   c.eqp_wintype);
+    if (c.eqp_mp) h = mp_imp(h, 16, 0);
+    return h;
+}
+
+int Engine::eqp_alloc()
+{
+    if (int rc = quiesce()) return rc;
+    if (int rc = alloc(eq_list_block, 2LL * nch)) return rc;
+    eq_list.dev = eq_list_block; eq_rest.dev = eq_list_block + (size_t)nch;
+    if (int rc = alloc(mask_eqp, (long long)nch * kBandNfftMax)) return rc;
+    for (int i = 0; i < 2; i++) if (int rc = alloc(hist_eqp[i], (long long)nch * kHistBand, true)) return rc;
+    for (ChanCfg &c : cfg) { c.eqp_dirty = true; c.eqp_flush = false; c.eqp_hist_at = cur_eqp; }
+    return QH_OK;
+}
+
+// The equalizer's channel lists, delay-line rows and masks after a setter, a change of the band tile or of the two-group layout.
+// SetRXAEQNC with a new nc zeroes the channel's delay line (setNc_fircore); every other setter swaps the mask and keeps the line
+// (setImpulse_fircore(..., 1)); a channel that does not run the stage keeps its line where it was (xeqp, eq.c:204-207).
+int Engine::refresh_eqp()
+{
+    if (eq_lists_dirty) {
+        eq_h.clear(); eq_rest_h.clear();
+        for (int ch = 0; ch < nch; ch++) (cfg[(size_t)ch].eqp_run ? eq_h : eq_rest_h).push_back(ch);
+        if (!eq_h.empty() && !mask_eqp) if (int rc = eqp_alloc()) return rc;
+        eq_list.n = (int)eq_h.size(); eq_rest.n = mask_eqp ? (int)eq_rest_h.size() : 0;
+        if (mask_eqp) {
+            if (int rc = follow_rows(eq_listed, &ChanCfg::eqp_hist_at, cur_eqp, eq_h, { { hist_eqp, cur_eqp, kHistBand } })) return rc;
+            std::vector<int> all((size_t)nch * 2, 0);
+            std::copy(eq_h.begin(), eq_h.end(), all.begin());
+            std::copy(eq_rest_h.begin(), eq_rest_h.end(), all.begin() + (size_t)nch);
+            QH_HIP(hipMemcpyAsync(eq_list_block, all.data(), all.size() * sizeof(int), hipMemcpyHostToDevice, stream));
+            QH_HIP(hipStreamSynchronize(stream));
+        }
+        eq_lists_dirty = false;
+    }
+    if (!mask_eqp) return QH_OK;
+    const int nfft_key = 2 * bnfft + (band2g ? 1 : 0);
+    if (nfft_key != eq_nfft_built) { for (ChanCfg &c : cfg) c.eqp_dirty = true; eq_nfft_built = nfft_key; }
+    std::vector<cd> last, last_taps;
+    const ChanCfg *last_cfg = nullptr;
+    if (eq_taps_h.size() != (size_t)nch) eq_taps_h.assign((size_t)nch, std::vector<cd>());
+    for (int ch = 0; ch < nch; ch++) {
+        ChanCfg &c = cfg[(size_t)ch];
+        if (c.eqp_flush) {
+            double2 *const none[2] = { nullptr, nullptr };
+            if (int rc = zero_rows(hist_eqp, none, ch)) return rc;
+            c.eqp_flush = false;
+        }
+        if (!c.eqp_run || !c.eqp_dirty) continue;       // (a channel that does not run keeps eqp_dirty until it does)
+        const bool same = last_cfg && last_cfg->eqp_nc == c.eqp_nc && last_cfg->eqp_mp == c.eqp_mp && last_cfg->eqp_ctfmode == c.eqp_ctfmode &&
+                          last_cfg->eqp_wintype == c.eqp_wintype && last_cfg->eqp_F == c.eqp_F && last_cfg->eqp_G == c.eqp_G;
+        if (!same) {
+            std::vector<cd> h = last_taps = eqp_taps(c);
+            for (auto &v : h) v *= (double)(2 * dsp_size);      // the engine's mask convention, as fmsq_filter
+            last = band_mask(h);
+            last_cfg = &c;
+        }
+        if (int rc = put_mask(mask_eqp, ch, last)) return rc;
+        eq_taps_h[(size_t)ch] = last_taps;
+        c.eqp_dirty = false;
+    }
+    return QH_OK;
+}
+
 // flush_rxa (wdsp/RXA.c:527-559): NCO phase, resampler ring and fircore delay lines back to zero
 int Engine::flush()
 {
@@ -1466,6 +1538,8 @@ int Engine::flush()
     if (amsq_state) QH_HIP(hipMemsetAsync(amsq_state, 0, (size_t)nch * sizeof(AmsqState), stream));     // flush_amsq
     if (ap_state) QH_HIP(hipMemsetAsync(ap_state, 0, (size_t)nch * kApW * sizeof(double), stream));    // flush_cbl / _speak / _mpeak, RXA.c:553-555
     if (ssql_state) launch_ssql_flush();        // flush_ssql, RXA.c:556
+    if (hist_eqp[0])                            // flush_eqp, RXA.c:545
+        for (int i = 0; i < 2; i++) QH_HIP(hipMemsetAsync(hist_eqp[i], 0, (size_t)nch * kHistBand * sizeof(double2), stream));
     if (fq_state) {                             // flush_fmsq, RXA.c:544
         for (int i = 0; i < 2; i++) QH_HIP(hipMemsetAsync(hist_fq[i], 0, (size_t)nch * kHistBand * sizeof(double2), stream));
         launch_fmsq_flush();

@@ -246,6 +246,7 @@ int qh_rxa_RXASetNC(qh_rxa *h, int ch, int nc)
         if (c.fm_nc != nc) c.long_live[2] = false;     // (setNc_fircore zeroes the delay lines, firmin.c:454-466: nothing long is held any more)
         c.fm_nc = nc;                           // SetRXAFMNCde / SetRXAFMNCaud, wdsp/RXA.c:943-944
         c.fmsq_nc = nc;                         // SetRXAFMSQNC, wdsp/RXA.c:942
+        if (c.eqp_nc != nc) { c.eqp_nc = nc; c.eqp_dirty = true; c.eqp_flush = true; }      // SetRXAEQNC, wdsp/RXA.c:941
     });
 }
 
@@ -338,6 +339,7 @@ int qh_rxa_RXASetMP(qh_rxa *h, int ch, int mp)
     FOR_CH(h, ch, {
         if (c.mp != mp) { c.mp = mp; c.nbp_dirty = true; c.bp1_dirty = true; c.demod_dirty = true; }
         c.fmsq_mp = mp;                         // SetRXAFMSQMP, wdsp/RXA.c:955
+        if (c.eqp_mp != mp) { c.eqp_mp = mp; c.eqp_dirty = true; }      // SetRXAEQMP, wdsp/RXA.c:954
     });
 }
 
@@ -587,6 +589,69 @@ int qh_rxa_SetRXAFMSQNC(qh_rxa *h, int ch, int nc)
 }
 int qh_rxa_SetRXAFMSQMP(qh_rxa *h, int ch, int mp) { FOR_CH(h, ch, { c.fmsq_mp = mp ? 1 : 0; }); }
 
+// xeqp (eq.c:242-377).  A setter edits the channel's settings; the design is made on the host at the next process call (Engine::refresh_eqp).
+int qh_rxa_SetRXAEQRun(qh_rxa *h, int ch, int run)
+{
+    FOR_CH(h, ch, {
+        run = run ? 1 : 0;
+        if (c.eqp_run != run) { c.eqp_run = run; h->e.eq_lists_dirty = true; }
+    });
+}
+int qh_rxa_SetRXAEQNC(qh_rxa *h, int ch, int nc)
+{
+    if (nc < 1 || (nc & (nc - 1)) || nc > kLongNcMax || (h && nc < h->e.dsp_size))
+        return set_error(QH_ERR_INVALID, "SetRXAEQNC: nc must be a power of two in [dsp_size, %d]", kLongNcMax);
+    FOR_CH(h, ch, { if (c.eqp_nc != nc) { c.eqp_nc = nc; c.eqp_dirty = true; c.eqp_flush = true; } });
+}
+int qh_rxa_SetRXAEQMP(qh_rxa *h, int ch, int mp)
+{
+    FOR_CH(h, ch, { mp = mp ? 1 : 0; if (c.eqp_mp != mp) { c.eqp_mp = mp; c.eqp_dirty = true; } });
+}
+// whether two of the profile's frequencies coincide after eq_impulse's clamp to [0, 1] (eq.c:53-55) while their gains differ
+static bool eqp_profile_tie(const std::vector<double> &F, const std::vector<double> &G, double rate)
+{
+    for (size_t i = 1; i < F.size(); i++)
+        for (size_t j = i + 1; j < F.size(); j++) {
+            const double a = std::min(1.0, std::max(0.0, 2.0 * F[i] / rate)), b = std::min(1.0, std::max(0.0, 2.0 * F[j] / rate));
+            if (a == b && G[i] != G[j]) return true;
+        }
+    return false;
+}
+static int eqp_set_profile(qh_rxa *h, int ch, int nfreqs, const double *F, const double *G, int ctfmode)
+{
+    if (!F || !G) return set_error(QH_ERR_INVALID, "EQ profile: null pointer");
+    if (nfreqs < 1) return set_error(QH_ERR_INVALID, "EQ profile: nfreqs = %d", nfreqs);
+    if (!std::isfinite(G[0])) return set_error(QH_ERR_INVALID, "EQ profile: the preamp gain is not finite");
+    for (int i = 1; i <= nfreqs; i++)
+        if (!std::isfinite(F[i]) || !std::isfinite(G[i])) return set_error(QH_ERR_INVALID, "EQ profile: point %d is not finite", i);
+    std::vector<double> f(F, F + nfreqs + 1), g(G, G + nfreqs + 1);
+    f[0] = 0.0;     // (not read by eq_impulse)
+    FOR_CH(h, ch, {
+        c.eqp_F = f; c.eqp_G = g;
+        if (ctfmode >= 0) c.eqp_ctfmode = ctfmode;
+        c.eqp_tie = eqp_profile_tie(f, g, (double)h->e.dsp_rate);
+        c.eqp_dirty = true;
+    });
+}
+int qh_rxa_SetRXAEQProfile(qh_rxa *h, int ch, int nfreqs, const double *F, const double *G) { return eqp_set_profile(h, ch, nfreqs, F, G, -1); }
+int qh_rxa_SetRXAEQCtfmode(qh_rxa *h, int ch, int mode) { FOR_CH(h, ch, { c.eqp_ctfmode = mode; c.eqp_dirty = true; }); }
+int qh_rxa_SetRXAEQWintype(qh_rxa *h, int ch, int wintype) { FOR_CH(h, ch, { c.eqp_wintype = wintype; c.eqp_dirty = true; }); }
+int qh_rxa_SetRXAGrphEQ(qh_rxa *h, int ch, const int *rxeq)
+{
+    if (!rxeq) return set_error(QH_ERR_INVALID, "SetRXAGrphEQ: null pointer");
+    const double F[5] = { 0.0, 150.0, 400.0, 1500.0, 6000.0 };
+    const double G[5] = { (double)rxeq[0], (double)rxeq[1], (double)rxeq[1], (double)rxeq[2], (double)rxeq[3] };
+    return eqp_set_profile(h, ch, 4, F, G, 0);
+}
+int qh_rxa_SetRXAGrphEQ10(qh_rxa *h, int ch, const int *rxeq)
+{
+    if (!rxeq) return set_error(QH_ERR_INVALID, "SetRXAGrphEQ10: null pointer");
+    const double F[11] = { 0.0, 32.0, 63.0, 125.0, 250.0, 500.0, 1000.0, 2000.0, 4000.0, 8000.0, 16000.0 };
+    double G[11];
+    for (int i = 0; i <= 10; i++) G[i] = (double)rxeq[i];
+    return eqp_set_profile(h, ch, 10, F, G, 0);
+}
+
 int qh_rxa_SetRXAPanelGain1(qh_rxa *h, int ch, double g) { FOR_CH(h, ch, { c.gain1 = g; c.epi_dirty = true; }); }
 int qh_rxa_SetRXAPanelGain2(qh_rxa *h, int ch, double gI, double gQ) { FOR_CH(h, ch, { c.gain2I = gI; c.gain2Q = gQ; c.epi_dirty = true; }); }
 int qh_rxa_SetRXAPanelSelect(qh_rxa *h, int ch, int s) { FOR_CH(h, ch, { c.inselect = s; c.epi_dirty = true; }); }
@@ -791,6 +856,27 @@ int qh_rxa_debug_fmsq(qh_rxa *h, int ch, double *out, int max)
     QH_HIP(hipMemcpy(&st, e.fq_state + ch, sizeof(st), hipMemcpyDeviceToHost));
     out[0] = st.avnoise; out[1] = st.longnoise; out[2] = (double)st.state; out[3] = (double)st.count; out[4] = st.wait == 0 ? 1.0 : 0.0;
     return 5;
+}
+
+// Diagnostics: the complex taps behind the mask row channel ch's equalizer last got (eq_impulse, through mp_imp when mp is set; scale
+// 1 / (2 dsp_size) as the reference's fircore gets them), kept on the host when the row was uploaded: 2 nc doubles.  A setter's new design
+// shows here after the next process call in which the channel runs the stage, when the device holds it.  For a channel that has not run
+// the stage yet (another channel of the engine has): what its current settings design.  Returns the number of taps, or 0 while no channel
+// of the engine has run the stage or `max` is too small.
+int qh_rxa_debug_eqp(qh_rxa *h, int ch, double *taps, int max)
+{
+    if (!h) return set_error(QH_ERR_INVALID, "null engine");
+    QH_RXA_LOCK(h);
+    Engine &e = h->e;
+    if (ch < 0 || ch >= e.nch) return set_error(QH_ERR_INVALID, "channel %d out of range", ch);
+    const ChanCfg &c = e.cfg[(size_t)ch];
+    if (!e.mask_eqp || !taps) return 0;
+    const bool held = (size_t)ch < e.eq_taps_h.size() && !e.eq_taps_h[(size_t)ch].empty();
+    if (!held && c.eqp_nc > kLongPart) return 0;
+    const std::vector<cd> t = held ? e.eq_taps_h[(size_t)ch] : e.eqp_taps(c);
+    if (max < 2 * (int)t.size()) return 0;
+    std::memcpy(taps, t.data(), t.size() * sizeof(cd));
+    return (int)t.size();
 }
 
 // Diagnostics: the lanes' states of the last time-tiled wcpAGC call, list slot `slot`: [tile][kAgcEndsW]

@@ -712,6 +712,15 @@ void SetRXAFMSQRun(int channel, int run) { WDSP_SETTER(qh_rxa_SetRXAFMSQRun(L.c-
 void SetRXAFMSQThreshold(int channel, double threshold) { WDSP_SETTER(qh_rxa_SetRXAFMSQThreshold(L.c->eng, 0, threshold)); }
 void SetRXAFMSQNC(int channel, int nc) { WDSP_SETTER(qh_rxa_SetRXAFMSQNC(L.c->eng, 0, nc)); }
 void SetRXAFMSQMP(int channel, int mp) { WDSP_SETTER(qh_rxa_SetRXAFMSQMP(L.c->eng, 0, mp)); }
+// the equalizer, wdsp/eq.c:242-377
+void SetRXAEQRun(int channel, int run) { WDSP_SETTER(qh_rxa_SetRXAEQRun(L.c->eng, 0, run)); }
+void SetRXAEQNC(int channel, int nc) { WDSP_SETTER(qh_rxa_SetRXAEQNC(L.c->eng, 0, nc)); }
+void SetRXAEQMP(int channel, int mp) { WDSP_SETTER(qh_rxa_SetRXAEQMP(L.c->eng, 0, mp)); }
+void SetRXAEQProfile(int channel, int nfreqs, double *F, double *G) { WDSP_SETTER(qh_rxa_SetRXAEQProfile(L.c->eng, 0, nfreqs, F, G)); }
+void SetRXAEQCtfmode(int channel, int mode) { WDSP_SETTER(qh_rxa_SetRXAEQCtfmode(L.c->eng, 0, mode)); }
+void SetRXAEQWintype(int channel, int wintype) { WDSP_SETTER(qh_rxa_SetRXAEQWintype(L.c->eng, 0, wintype)); }
+void SetRXAGrphEQ(int channel, int *rxeq) { WDSP_SETTER(qh_rxa_SetRXAGrphEQ(L.c->eng, 0, rxeq)); }
+void SetRXAGrphEQ10(int channel, int *rxeq) { WDSP_SETTER(qh_rxa_SetRXAGrphEQ10(L.c->eng, 0, rxeq)); }
 // the LMS auto-notch / noise reduction, wdsp/anf.c:175-239, anr.c:175-238
 void SetRXAANFRun(int channel, int v) { WDSP_SETTER(qh_rxa_SetRXAANFRun(L.c->eng, 0, v)); }
 void SetRXAANFTaps(int channel, int v) { WDSP_SETTER(qh_rxa_SetRXAANFTaps(L.c->eng, 0, v)); }

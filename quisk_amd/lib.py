@@ -74,7 +74,10 @@ def load():
                  ("SetRXAmpeakFilBw", [vp, i, i, d]), ("SetRXAmpeakFilGain", [vp, i, i, d]),
                  ("SetRXASSQLRun", [vp, i, i]), ("SetRXASSQLThreshold", [vp, i, d]), ("SetRXASSQLTauMute", [vp, i, d]),
                  ("SetRXASSQLTauUnMute", [vp, i, d]),
-                 ("SetRXAFMSQRun", [vp, i, i]), ("SetRXAFMSQThreshold", [vp, i, d]), ("SetRXAFMSQNC", [vp, i, i]), ("SetRXAFMSQMP", [vp, i, i])):
+                 ("SetRXAFMSQRun", [vp, i, i]), ("SetRXAFMSQThreshold", [vp, i, d]), ("SetRXAFMSQNC", [vp, i, i]), ("SetRXAFMSQMP", [vp, i, i]),
+                 ("SetRXAEQRun", [vp, i, i]), ("SetRXAEQNC", [vp, i, i]), ("SetRXAEQMP", [vp, i, i]),
+                 ("SetRXAEQProfile", [vp, i, i, C.POINTER(d), C.POINTER(d)]), ("SetRXAEQCtfmode", [vp, i, i]), ("SetRXAEQWintype", [vp, i, i]),
+                 ("SetRXAGrphEQ", [vp, i, C.POINTER(i)]), ("SetRXAGrphEQ10", [vp, i, C.POINTER(i)])):
         f = getattr(L, "qh_rxa_" + n)
         f.argtypes = a
         f.restype = i
@@ -83,6 +86,14 @@ def load():
         f = getattr(L, n)
         f.argtypes = a
         f.restype = None
+    # the equalizer's WDSP names (wdsp/eq.c:242-377) and its diagnostic
+    for n, a in (("SetRXAEQRun", [i, i]), ("SetRXAEQNC", [i, i]), ("SetRXAEQMP", [i, i]), ("SetRXAEQProfile", [i, i, C.POINTER(d), C.POINTER(d)]),
+                 ("SetRXAEQCtfmode", [i, i]), ("SetRXAEQWintype", [i, i]), ("SetRXAGrphEQ", [i, C.POINTER(i)]), ("SetRXAGrphEQ10", [i, C.POINTER(i)])):
+        f = getattr(L, n)
+        f.argtypes = a
+        f.restype = None
+    L.qh_rxa_debug_eqp.argtypes = [vp, i, C.POINTER(d), i]
+    L.qh_rxa_debug_eqp.restype = i
     L.qh_rxa_debug_fmsq.argtypes = [vp, i, C.POINTER(d), i]
     L.qh_rxa_debug_fmsq.restype = i
     L.qh_rxa_SetEMNRTables.argtypes = [vp, vp, vp, vp, vp, d, d, d, d]

@@ -23,7 +23,10 @@ _SETTERS = ("SetRXAMode", "RXASetNC", "SetRXAShiftRun", "RXANBPSetRun", "SetRXAB
             "SetRXACBLRun", "SetRXASPCWRun", "SetRXASPCWFreq", "SetRXASPCWBandwidth", "SetRXASPCWGain", "SetRXAmpeakRun",
             "SetRXAmpeakNpeaks", "SetRXAmpeakFilEnable", "SetRXAmpeakFilFreq", "SetRXAmpeakFilBw", "SetRXAmpeakFilGain",
             "SetRXASSQLRun", "SetRXASSQLThreshold", "SetRXASSQLTauMute", "SetRXASSQLTauUnMute",
-            "SetRXAFMSQRun", "SetRXAFMSQThreshold", "SetRXAFMSQNC", "SetRXAFMSQMP")
+            "SetRXAFMSQRun", "SetRXAFMSQThreshold", "SetRXAFMSQNC", "SetRXAFMSQMP",
+            "SetRXAEQRun", "SetRXAEQNC", "SetRXAEQMP", "SetRXAEQProfile", "SetRXAEQCtfmode", "SetRXAEQWintype", "SetRXAGrphEQ", "SetRXAGrphEQ10")
+# the setters that take arrays: (element type, position among the arguments behind the channel)
+_ARRAYS = {"SetRXAEQProfile": ((C.c_double, 1), (C.c_double, 2)), "SetRXAGrphEQ": ((C.c_int, 0),), "SetRXAGrphEQ10": ((C.c_int, 0),)}
 
 
 class AudioFormat(C.Structure):
@@ -71,6 +74,10 @@ class RxaEngine:
             f = getattr(self._L, "qh_rxa_" + name)
 
             def call(ch, *args):
+                args = list(args)
+                for t, pos in _ARRAYS.get(name, ()):        # sequences -> C arrays (None stays a null pointer)
+                    if args[pos] is not None:
+                        args[pos] = (t * len(args[pos]))(*args[pos])
                 check(f(self._h, ch, *args))
             return call
         raise AttributeError(name)
@@ -153,6 +160,15 @@ class RxaEngine:
         n = self._L.qh_rxa_debug_fmsq(self._h, ch, buf, 5)
         check(n if n < 0 else 0)
         return (buf[0], buf[1], int(buf[2]), int(buf[3]), int(buf[4])) if n == 5 else None
+
+    def debug_eqp(self, ch, max_nc=4096):
+        """diagnostics: the complex taps behind the mask channel ch's equalizer last got (nc of them, scale 1 / (2 dsp_size) as WDSP's
+        fircore gets them; a setter's new design shows after the next process call that runs the channel's equalizer), or None while no
+        channel of the engine has run the stage"""
+        buf = (C.c_double * (2 * max_nc))()
+        n = self._L.qh_rxa_debug_eqp(self._h, ch, buf, 2 * max_nc)
+        check(n if n < 0 else 0)
+        return np.frombuffer(buf, dtype=np.complex128, count=n).copy() if n > 0 else None
 
     def debug_agc(self, form):
         """diagnostics: 0 = time tiles for long calls (default), 1 = the sample-by-sample form of the wcpAGC loop, 2 = 64 samples per step"""
