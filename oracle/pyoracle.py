@@ -38,6 +38,8 @@ def lib():
         L.wo_fexchange0.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
         L.wo_xrxa_block.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.wo_xrxa_blocks.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        L.wo_set_stage_hook.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        L.wo_set_stage_hook.restype = None
         for n in ("wo_dsp_insize", "wo_dsp_outsize", "wo_out_size"):
             getattr(L, n).argtypes = [C.c_void_p]
             getattr(L, n).restype = C.c_int
@@ -228,12 +230,42 @@ class WdspChannel:
         nb = x.size // self.dsp_insize
         out = np.empty(nb * self.dsp_outsize, dtype=np.complex128)
         self.L.wo_xrxa_blocks(self.h, x.ctypes.data, out.ctypes.data, nb)
+        err = self.__dict__.get("_hook_error")
+        if err is not None:
+            self._hook_error = None
+            raise err
         return out
+
+    HOOK_FMSQ, HOOK_EQP, HOOK_AUDIO = 0, 1, 2          # wdsp_oracle.h: the sites of xfmsq, xeqp and xcbl .. xssql (RXA.c:575, 579, 591-594)
+    _HOOK_T = C.CFUNCTYPE(None, C.c_void_p, C.c_int, c_double_p, C.c_int, c_double_p)
+
+    def set_stage_hook(self, fn, sites=(0, 1, 2)):
+        """fn(where, buf, aux) once per DSP block at each of `sites`: buf is midbuff as a writable complex128 view (change it in place),
+        aux xfmd's audio as a float64 view of the block's n samples at HOOK_FMSQ, else None.  fn None unsets it.  An exception in fn is
+        kept and raised by the xrxa call it happened in."""
+        self._hook_error = None
+        if fn is None:
+            self._hook = None
+            self.L.wo_set_stage_hook(self.h, None, None, 0)
+            return
+
+        def tramp(ctx, where, buf, n, aux):
+            if self._hook_error is not None:
+                return
+            try:
+                z = np.ctypeslib.as_array(buf, shape=(2 * n,)).view(np.complex128)
+                a = np.ctypeslib.as_array(aux, shape=(2 * n,))[0::2] if aux else None
+                fn(where, z, a)
+            except BaseException as ex:            # (ctypes would print and swallow it)
+                self._hook_error = ex
+        self._hook = self._HOOK_T(tramp)           # kept alive here: the library holds only the address
+        self.L.wo_set_stage_hook(self.h, C.cast(self._hook, C.c_void_p), None, sum(1 << int(s) for s in sites))
 
     def close(self):
         if self.h:
             self.L.wo_close(self.h)
             self.h = None
+            self._hook = None
 
     def __del__(self):
         try:

@@ -577,6 +577,8 @@ struct wo_channel {
         int ustate, ucount, ndelup, ntup, upflag;
         double *cup;
     } iob;
+    /* optional stage hook (unset: xrxa as it always was): the call sites of xfmsq, xeqp and xcbl .. xssql, which this file does not restate */
+    wo_stage_hook hook; void *hook_ctx; int hook_mask;
 };
 
 int wo_dsp_insize(const wo_channel *c) { return c->dsp_insize; }
@@ -1127,8 +1129,10 @@ static void xrxa(wo_channel *c)
     if (c->bpsnba.run && c->bpsnba.position == 0) wo_fircore_exec(c->bpsnba.p, c->bpsnba.buff, c->midbuff);           /* xbpsnbaout, RXA.c:572 */
     xamd(c, c->midbuff, n);
     xfmd(c, c->midbuff, n);
+    if (c->hook && (c->hook_mask & 1)) c->hook(c->hook_ctx, WO_HOOK_FMSQ, c->midbuff, n, c->fmd.audio);                 /* xfmsq, RXA.c:575: the trigger is xfmd's audio (RXA.c:220) */
     if (c->bpsnba.run && c->bpsnba.position == 1) wo_fircore_exec(c->bpsnba.p, c->midbuff, c->midbuff);              /* RXA.c:576-577 */
     wo_snba_exec(c->snba, c->midbuff);                                                                                 /* xsnba, RXA.c:578 */
+    if (c->hook && (c->hook_mask & 2)) c->hook(c->hook_ctx, WO_HOOK_EQP, c->midbuff, n, NULL);                          /* xeqp, RXA.c:579 */
     xlms(&c->anf, 0, 0, c->midbuff, n);
     xlms(&c->anr, 1, 0, c->midbuff, n);
     wo_emnr_exec(c->emnr, 0, c->midbuff);
@@ -1139,10 +1143,18 @@ static void xrxa(wo_channel *c)
     wo_emnr_exec(c->emnr, 1, c->midbuff);
     if (c->bp1.run && c->bp1.position == 1) wo_fircore_exec(c->bp1.p, c->midbuff, c->midbuff);
     meter_exec(&c->agcmeter, c->midbuff, n, c->meter, &c->agc.gain);
+    if (c->hook && (c->hook_mask & 4)) c->hook(c->hook_ctx, WO_HOOK_AUDIO, c->midbuff, n, NULL);                        /* xcbl, xspeak, xmpeak, xssql, RXA.c:591-594 */
     xpanel(c, c->midbuff, n);
     xamsq(c, c->midbuff, n);                                                        /* RXA.c:596 */
     if (c->rsmpout->run) wo_resample_exec(c->rsmpout, c->midbuff, n, c->outbuff);
     else memcpy(c->outbuff, c->midbuff, (size_t)n * 2 * sizeof(double));
+}
+
+/* hook: called once per DSP block at the sites in mask (bit 0 WO_HOOK_FMSQ, 1 WO_HOOK_EQP, 2 WO_HOOK_AUDIO) with midbuff (n complex samples,
+ * processed in place) and, at the FMSQ site, xfmd's audio buffer; NULL unsets it */
+void wo_set_stage_hook(wo_channel *c, wo_stage_hook hook, void *ctx, int mask)
+{
+    c->hook = hook; c->hook_ctx = ctx; c->hook_mask = hook ? mask : 0;
 }
 
 void wo_xrxa_block(wo_channel *c, const double *in, double *out)

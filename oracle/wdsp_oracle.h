@@ -45,6 +45,13 @@ void wo_fexchange0(wo_channel *c, const double *in, double *out, int *error);
 void wo_xrxa_block(wo_channel *c, const double *in, double *out);
 void wo_xrxa_blocks(wo_channel *c, const double *in, double *out, int nblk);
 
+/* the call sites of xrxa that this oracle does not restate (RXA.c:575, 579, 591-594): an optional callback, once per DSP block and site,
+ * on midbuff in place (n complex samples); aux is xfmd's audio buffer (FMSQ's trigger, RXA.c:220) at WO_HOOK_FMSQ, NULL elsewhere.
+ * mask: bit `where` set = that site is called.  Unset (the default), xrxa computes what it computed without them. */
+enum { WO_HOOK_FMSQ = 0, WO_HOOK_EQP = 1, WO_HOOK_AUDIO = 2 };
+typedef void (*wo_stage_hook)(void *ctx, int where, double *buf, int n, const double *aux);
+void wo_set_stage_hook(wo_channel *c, wo_stage_hook hook, void *ctx, int mask);
+
 int wo_dsp_insize(const wo_channel *c);
 int wo_dsp_outsize(const wo_channel *c);
 int wo_out_size(const wo_channel *c);

@@ -553,6 +553,15 @@ int Engine::process_chain(const double *d_in, long long in_stride, double *d_out
     if (meters_on) if (int rc = meters_alloc()) return rc;
     if (int rc = refresh_params()) return rc;
     if (k.mixed) if (int rc = refresh_demod()) return rc;
+    // bp1 on the linear path (SetRXABandpassRun on an all-SSB engine): run_linear flips bp1's ping-pong pair like the per-mode path, but
+    // refresh_lists, which keeps bp1_listed / bp1_hist_at, runs from refresh_demod only.  Left alone, the first per-mode call found no
+    // channel listed and bp1_hist_at still at the half of the engine's first call, and after an odd number of linear calls copied that
+    // stale half over the channel's current delay line (test_gpu_rxa_stage_combinations.py: `fmsq beside bp1`).
+    if (!k.mixed && k.any_bp1) {
+        std::vector<int> run;
+        for (int ch = 0; ch < nch; ch++) if (cfg[(size_t)ch].bp1_run) run.push_back(ch);
+        if (int rc = follow_rows(bp1_listed, &ChanCfg::bp1_hist_at, cur_bp1, run, { { hist_bp1, cur_bp1, kHistBand }, { lhist[1], cur_bp1, kLongHist } })) return rc;
+    }
     if (lists[L_SNBA].n) if (int rc = refresh_params()) return rc;       // bpsnba's mask needs the buffers the line above may just have made
     if (k.any_eqp || eq_lists_dirty) if (int rc = refresh_eqp()) return rc;
 

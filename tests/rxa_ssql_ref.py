@@ -3,7 +3,9 @@
 Written from the reference's semantics (wdsp/ssql.c, the carrier block of wdsp/cblock.c:29-94, dbqlp of wdsp/iir.c:829-916, create_rxa's
 arguments RXA.c:447-461), not from the HIP code.  Every step that takes a decision is stepped sample by sample as written; the biquad
 low-pass goes through scipy.signal.lfilter with its state carried from call to call.  `process` works on one channel's complex block
-and returns the squelched block; it also leaves the per-sample gain and trigger of that block in `gain` and `tr`.
+and returns the squelched block; it also leaves the per-sample gain and trigger of that block in `gain` and `tr`, and what its
+decisions were taken on in `wdist` (|lp - wdaverage|, held against wthresh), `trv` (the trigger voltage, held against tr_thresh) and `zc`
+(see `margins`).  Every piece of state is carried from call to call, so calls of one DSP block give what one long call gives.
 """
 import math
 
@@ -69,6 +71,7 @@ class Ssql:
         self.flush_parts()
         self.gain = np.zeros(0)
         self.tr = np.zeros(0, dtype=np.int8)
+        self.wdist, self.trv, self.zc = np.zeros(0), np.zeros(0), np.inf
 
     def flush_parts(self):
         """what flush_ssql zeroes (ssql.c:208-220): the blocker, the ftov ring, rcount and inlast, the biquad"""
@@ -114,6 +117,13 @@ class Ssql:
         """xftov (ssql.c:70-108)"""
         out = np.empty(len(x))
         ring, rptr, rcount, last = self.ring, self.rptr, self.rcount, self.inlast
+        # (diagnostics, `margins`: how far the crossings' two tests were from going the other way)
+        xs = np.asarray(x, dtype=np.float64)
+        prev = np.concatenate([[last], xs[:-1]])
+        step, near0 = np.abs(prev - xs), np.minimum(np.abs(prev), np.abs(xs))
+        sign = prev * xs < 0.0
+        # (a sample that is exactly 0 -- the line's start, a stage ahead that puts out 0.0 -- is no near miss: its product is exactly 0)
+        self.zc = min(float(np.min(np.abs(step[sign] - 0.01), initial=np.inf)) / 0.01, float(np.min(near0[(step > 0.01) & (near0 > 0.0)], initial=np.inf)) / 0.01)
         for i, v in enumerate(x.tolist()):
             if ring[rptr] == 1:
                 rcount -= 1
@@ -137,16 +147,20 @@ class Ssql:
     def window(self, lp):
         """the window detector (ssql.c:241-250): 0 = unmute, 1 = mute"""
         wd = np.empty(len(lp), dtype=np.int8)
+        dist = np.empty(len(lp))
         w, m, om, th = self.wdaverage, self.wdmult, 1.0 - self.wdmult, self.wthresh
         for i, v in enumerate(lp.tolist()):
             w = m * w + om * v
             wd[i] = 0 if (v - w) > th or (w - v) > th else 1
+            dist[i] = abs(v - w)
         self.wdaverage = w
+        self.wdist = dist
         return wd
 
     def trigger(self, wd):
         """ssql.c:252-260: 1 = unmuted"""
         tr = np.empty(len(wd), dtype=np.int8)
+        trv = np.empty(len(wd))
         v = self.tr_voltage
         for i, d in enumerate(wd.tolist()):
             if d == 0:
@@ -154,7 +168,9 @@ class Ssql:
             else:
                 v += (self.tr_ss_mute - v) * self.mute_mult
             tr[i] = 0 if v > self.tr_thresh else 1
+            trv[i] = v
         self.tr_voltage = v
+        self.trv = trv
         return tr
 
     def machine(self, tr):
@@ -188,6 +204,7 @@ class Ssql:
         if not self.run:
             self.gain = np.ones(len(z))
             self.tr = np.zeros(0, dtype=np.int8)
+            self.wdist, self.trv, self.zc = np.zeros(0), np.zeros(0), np.inf
             return z.copy()
         i = self.cbl_i(np.ascontiguousarray(z.real))
         lp = self.lowpass(self.ftov(i))
@@ -201,6 +218,16 @@ class Ssql:
         return out
 
 
+def crossing_margin(v, th):
+    """the smallest relative distance from th of the samples on both sides of any crossing of it (inf where v never crosses)"""
+    v = np.asarray(v)
+    below = v < th
+    x = np.flatnonzero(below[1:] != below[:-1])
+    if not x.size:
+        return np.inf
+    return min(float(np.min(np.abs(v[x] - th))), float(np.min(np.abs(v[x + 1] - th)))) / th
+
+
 def edges(gain):
     """(opens, closes): the ramps up and down that start within `gain` (a ramp start is a sample after a muted / unit one)"""
     g = np.asarray(gain)
@@ -210,9 +237,11 @@ def edges(gain):
     return opens, closes
 
 
-def syllabic(n, rate, seed=0, amp=0.3, on=1.0, off=1.5, lo=400.0, hi=1800.0):
+def syllabic(n, rate, seed=0, amp=0.3, on=1.0, off=1.5, lo=400.0, hi=1800.0, rest=None):
     """a tone hopping between about lo and hi Hz every 60-150 ms, with a little noise, gated on for `on` s and off (zero) for `off` s
-    in turn (complex, at baseband)"""
+    in turn (complex, at baseband).  rest: a steady tone of that frequency through the off periods instead of nothing -- with silence the
+    window detector's average (tau 0.5 s, ssql.c:129-154) takes most of a second to come down to the silence and let the squelch close;
+    a steady tone near the hops' mean frequency is within the window at once, and the squelch closes after tau_mute"""
     rng = np.random.default_rng(seed)
     f = np.empty(n)
     i = 0
@@ -223,4 +252,7 @@ def syllabic(n, rate, seed=0, amp=0.3, on=1.0, off=1.5, lo=400.0, hi=1800.0):
     ph = 2.0 * np.pi * np.cumsum(f) / rate
     t = np.arange(n) / rate
     gate = (t % (on + off)) < on
-    return (amp * np.exp(1j * ph) + 0.001 * (rng.standard_normal(n) + 1j * rng.standard_normal(n))) * gate
+    z = (amp * np.exp(1j * ph) + 0.001 * (rng.standard_normal(n) + 1j * rng.standard_normal(n))) * gate
+    if rest is not None:
+        z = z + amp * np.exp(2j * np.pi * ((rest * t) % 1.0)) * ~gate
+    return z
