@@ -246,6 +246,20 @@ int qh_rxa_synchronize(qh_rxa *e);
 int qh_rxa_enable_meters(qh_rxa *e, int enable);
 int qh_rxa_GetRXAMeter(qh_rxa *e, int ch, int mt, double *value);
 
+/* The chain's two data taps: xsender behind nbp0 (wdsp/RXA.c:570) and xsiphon behind xwcpagc (wdsp/RXA.c:590).  Neither changes the
+ * signal.  Both are OFF until enabled, per channel -- the reference runs the siphon of every channel (RXA.c:392-401): a tap costs a
+ * pass, and a call with any tap on takes the per-mode path, as one with unfused meters does.  ch -1 = every channel.
+ * Sender: later calls leave the channel's signal behind nbp0 as (I, Q) float pairs in engine-owned device rows, n samples of the last
+ * call per row; rows of channels whose sender is off are not written.  Siphon: a ring of the newest 4096 samples (sipsize, RXA.c:392-401),
+ * mode 0 only; get_sip returns the newest `size` complex samples, oldest first, zeros where fewer have arrived since the last flush.
+ * Deviation: size < 0 or > 4096 returns QH_ERR_INVALID and leaves `out` alone (suck leaves sipout stale then, siphon.c:150, and
+ * RXAGetaSipF reads `size` samples of it, past its end); a channel whose siphon is off is refused too.  It waits for the engine's stream. */
+int qh_rxa_set_sender(qh_rxa *e, int ch, int run);                                 /* wdsp/sender.c:66-68 (run && flag) */
+int qh_rxa_sender_rows(qh_rxa *e, const float **d_rows, long long *stride, int *n); /* wdsp/sender.c:75-80: [nch][stride] float pairs on the device */
+int qh_rxa_sender_rows_host(qh_rxa *e, int ch, float *out, int max, int *n);        /* wdsp/sender.c:75-80: one channel's row, 2 n floats; waits */
+int qh_rxa_set_siphon(qh_rxa *e, int ch, int run);                                 /* wdsp/siphon.c:96-130, mode 0; switched on, it starts flushed (siphon.c:88-94) */
+int qh_rxa_get_sip(qh_rxa *e, int ch, double *out, int size);                      /* wdsp/siphon.c:148-163 (suck): 2 size doubles */
+
 /* flush_rxa (wdsp/RXA.c:527-559): zero the NCO phase and every filter history of every channel. */
 int qh_rxa_flush(qh_rxa *e);
 
@@ -316,6 +330,14 @@ void SetRXAFMDeviation(int channel, double deviation);                          
 void SetRXACTCSSFreq(int channel, double freq);                                  /* wdsp/fmd.c:248-258 */
 void SetRXACTCSSRun(int channel, int run);                                       /* wdsp/fmd.c:260-267 */
 double GetRXAMeter(int channel, int mt);                                         /* wdsp/meter.c:133-142 */
+/* The sender runs on channel 0 only, as create_rxa makes it (RXA.c:131): on another channel the call is accepted and does nothing.  With
+ * flag set, every DSP block of channel 0 feeds display `disp` (XCreateAnalyzer), sub-span ss, on the device; the display is looked up at
+ * each block, and one that does not exist or whose buff_size is not dsp_size sets qh_wdsp_status() and is fed nothing.  The siphon is off
+ * until a channel's first RXAGetaSipF / RXAGetaSipF1 call, which switches it on and returns a flushed siphon's zeros (deviation: the
+ * reference runs it from create_rxa on); size outside 0 .. 4096 sets qh_wdsp_status() and leaves `out` alone. */
+void SetRXASpectrum(int channel, int flag, int disp, int ss, int LO);           /* wdsp/sender.c:111-122 */
+void RXAGetaSipF(int channel, float *out, int size);                            /* wdsp/siphon.c:182-195: I only */
+void RXAGetaSipF1(int channel, float *out, int size);                           /* wdsp/siphon.c:197-211: I, Q */
 /* The blanker WDSP's callers run in front of fexchange0 (wdsp/nob.c:307-422, wdsp.h:620-665): ids 0..31, each a one-channel qh_anb bank
  * with staging rows of its own, so in == out works as it does for the reference's callers; buffsize is the n of xanbEXT.  in / out
  * are host pointers, as fexchange0's are; samples that are already on the GPU go through qh_wdsp_xanbEXT_device, as fexchange0's go
@@ -830,6 +852,17 @@ int qh_ana_reset_pixel_buffers(qh_ana *a);
  * memory (qh_ana_feed_host; swap_iq = 1 reads Spectrum0's (Q, I) pair order).  *frames = pixel rows published by this call. */
 int qh_ana_feed(qh_ana *a, int ss, const void *d_iq, long long disp_stride, int n, int *frames);
 int qh_ana_feed_host(qh_ana *a, int ss, const double *h_iq, long long disp_stride, int n, int swap_iq, int *frames);
+/* The same for (I, Q) float pairs on the device, as xsender leaves them; swap_iq = 1 reads Spectrum2's (Q, I) pair order.  The bank's
+ * stream reads the rows behind everything producer_stream holds when the call is made (an event, no host wait); NULL: already ordered. */
+int qh_ana_feed_f32(qh_ana *a, int ss, const void *d_iq, long long disp_stride, int n, int swap_iq, void *producer_stream, int *frames);   /* wdsp/sender.c:81 -> Spectrum2, analyzer.c:1490-1533 */
+/* xsender -> Spectrum2 bank to bank, on the device: attach makes every later process call of the engine (device, host, packed, audio) end
+ * by feeding its dsp_size * nblk sender samples per channel to sub-span ss, display d from channel d, in the pair order Spectrum2 reads
+ * (swap_iq = 1: it takes element 2i + 1 as I, analyzer.c:1503-1507, of rows xsender hands over unswapped).  It needs ndisp = the engine's
+ * channels, buff_size = dsp_size and the engine's device, switches every channel's sender on and refuses to switch one off while attached.
+ * The two streams are ordered by events both ways.  a = NULL detaches (the senders stay on); the bank must outlive the attachment.
+ * feed_display does one such feed of the last call's rows (every channel's sender on). */
+int qh_rxa_attach_display(qh_rxa *e, qh_ana *a, int ss);                           /* wdsp/sender.c:81 */
+int qh_rxa_feed_display(qh_rxa *e, qh_ana *a, int ss);                             /* wdsp/sender.c:81 */
 /* GetPixels for one display of the bank: *flag = 1 and num_pixels floats (dB) if a row has been published since the last read */
 int qh_ana_get_pixels(qh_ana *a, int disp, int pixout, float *pix, int *flag);
 /* every row of the last feed call, [ndisp][frames][num_pixels] floats: device pointer / host copy */
@@ -843,6 +876,9 @@ int qh_ana_snap_wait(qh_ana *a, double *snap_buff, int timeout_ms, int *flag);
 void *qh_ana_stream(qh_ana *a);
 long long qh_ana_frames(qh_ana *a);
 int qh_ana_buff_size(qh_ana *a);
+int qh_ana_ndisp(qh_ana *a);
+int qh_ana_device(qh_ana *a);
+int qh_ana_num_stitch(qh_ana *a);
 int qh_ana_num_pixels(qh_ana *a);
 /* WDSP's own names and signatures (wdsp/analyzer.h:100-193, wdsp.h), one display per id 0..63, host pointers */
 void XCreateAnalyzer(int disp, int *success, int m_size, int m_LO, int m_stitch, char *app_data_path);

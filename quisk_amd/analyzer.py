@@ -63,12 +63,19 @@ class AnalyzerBank:
         _check(self._L, self._L.qh_ana_feed(self._h, ss, d_iq, disp_stride, n, C.byref(frames)))
         return frames.value
 
-    def feed_host(self, ss, x):
+    def feed_host(self, ss, x, swap_iq=0):
+        """swap_iq = 1: the pairs are read as Spectrum0 / Spectrum2 read theirs, second element I (analyzer.c:1503-1507,1550-1553)"""
         x = np.ascontiguousarray(x, dtype=np.complex128)
         if x.ndim != 2 or x.shape[0] != self.ndisp:
             raise ValueError("expected [ndisp, n] complex128")
         frames = C.c_int(0)
-        _check(self._L, self._L.qh_ana_feed_host(self._h, ss, x.ctypes.data, x.shape[1], x.shape[1], 0, C.byref(frames)))
+        _check(self._L, self._L.qh_ana_feed_host(self._h, ss, x.ctypes.data, x.shape[1], x.shape[1], int(swap_iq), C.byref(frames)))
+        return frames.value
+
+    def feed_f32(self, ss, d_iq, disp_stride, n, swap_iq=0, producer_stream=None):
+        """n complex64 samples per display on the device (a sender's rows), read behind what producer_stream holds now"""
+        frames = C.c_int(0)
+        _check(self._L, self._L.qh_ana_feed_f32(self._h, ss, d_iq, disp_stride, n, int(swap_iq), producer_stream, C.byref(frames)))
         return frames.value
 
     def rows_host(self, pixout, max_frames=4096):

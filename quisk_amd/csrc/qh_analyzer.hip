@@ -36,8 +36,10 @@ constexpr int kMaxStitch = 4, kMaxPixels = 16384, kMaxAverage = 60, kMaxPixouts 
 constexpr int kMaxR = 64;
 
 // ---- kernels --------------------------------------------------------------------------------------------------------
-// old tail + new samples -> the other stream buffer; new samples arrive as (I, Q) doubles and are narrowed to float
-__global__ void ana_append_kernel(const float2 *old_buf, long long old_stride, int drop, int keep, const double2 *src, long long src_stride,
+// old tail + new samples -> the other stream buffer; new samples arrive as (I, Q) doubles and are narrowed to float, or as the float
+// pairs a sender has narrowed already (Src = float2: qh_ana_feed_f32)
+template <typename Src>
+__global__ void ana_append_kernel(const float2 *old_buf, long long old_stride, int drop, int keep, const Src *src, long long src_stride,
                                   int n, int swap_iq, float2 *dst, long long dst_stride)
 {
     const int d = blockIdx.y;
@@ -46,7 +48,7 @@ __global__ void ana_append_kernel(const float2 *old_buf, long long old_stride, i
     float2 v;
     if (i < keep) v = old_buf[(long long)d * old_stride + drop + i];
     else {
-        const double2 z = src[(long long)d * src_stride + (i - keep)];
+        const Src z = src[(long long)d * src_stride + (i - keep)];
         v = swap_iq ? make_float2((float)z.y, (float)z.x) : make_float2((float)z.x, (float)z.y);
     }
     dst[(long long)d * dst_stride + i] = v;
@@ -357,11 +359,13 @@ struct qh_ana {
     DevVec<double2> staging;            // host-pointer entry points
     std::vector<float> h_open_I[kMaxStitch], h_open_Q[kMaxStitch];
     long long frames_total = 0;
+    hipEvent_t ev_producer = nullptr;   // qh_ana_feed_f32: recorded on the producer's stream, waited for by this one
 
     ~qh_ana()
     {
         (void)hipSetDevice(device);
         if (stream) (void)hipStreamSynchronize(stream);
+        if (ev_producer) (void)hipEventDestroy(ev_producer);
         if (own_stream && stream) (void)hipStreamDestroy(stream);
     }
 };
@@ -670,8 +674,9 @@ void dispatch(qh_ana &a)
     }
 }
 
-// n = k * buff_size new samples of sub-span ss for every display: device (I, Q) doubles
-int push(qh_ana &a, int ss, const double2 *d_src, long long src_stride, int n, int swap_iq)
+// n = k * buff_size new samples of sub-span ss for every display: device (I, Q) doubles or floats
+template <typename Src>
+int push(qh_ana &a, int ss, const Src *d_src, long long src_stride, int n, int swap_iq)
 {
     const int from = a.cur[ss], to = from ^ 1;
     // samples a frame may still need: from the next frame's start, or from the start of a frame of this sub-span that
@@ -689,7 +694,7 @@ int push(qh_ana &a, int ss, const double2 *d_src, long long src_stride, int n, i
         QH_HIP(a.sbuf[ss][to].ensure((size_t)(cap * a.ndisp)));
         a.stride[ss][to] = cap;
     }
-    hipLaunchKernelGGL(ana_append_kernel, dim3((unsigned)((need + 255) / 256), (unsigned)a.ndisp), dim3(256), 0, a.stream,
+    hipLaunchKernelGGL(ana_append_kernel<Src>, dim3((unsigned)((need + 255) / 256), (unsigned)a.ndisp), dim3(256), 0, a.stream,
                        (const float2 *)a.sbuf[ss][from].p, a.stride[ss][from], (int)drop, keep, d_src, src_stride, n, swap_iq, a.sbuf[ss][to].p, cap);
     QH_HIP(hipGetLastError());
     a.cur[ss] = to;
@@ -978,6 +983,31 @@ int qh_ana_feed_host(qh_ana *h, int ss, const double *h_iq, long long disp_strid
     return QH_OK;
 }
 
+// qh_ana_feed for float pairs on the device, as a sender leaves them (wdsp/sender.c:75-81 -> Spectrum2, analyzer.c:1490-1533): swap_iq = 1
+// for Spectrum2's (Q, I) pair order.  The rows are read on the bank's stream behind everything producer_stream holds at this moment
+// (an event; no host wait); producer_stream = NULL: the caller has ordered the two itself.
+int qh_ana_feed_f32(qh_ana *h, int ss, const void *d_iq, long long disp_stride, int n, int swap_iq, void *producer_stream, int *frames)
+{
+    if (int e = check_config(h, "qh_ana_feed_f32")) return e;
+    std::lock_guard<std::recursive_mutex> lk(h->mu);
+    qh_ana &a = *h;
+    if (frames) *frames = 0;
+    if (ss < 0 || ss >= a.num_stitch || n < 0 || (n > 0 && (!d_iq || disp_stride < n)) || n % a.buff_size)
+        return set_error(QH_ERR_INVALID, "qh_ana_feed_f32: bad arguments (n must be a multiple of buff_size)");
+    if (n == 0) return QH_OK;
+    QH_HIP(hipSetDevice(a.device));
+    if (producer_stream && (hipStream_t)producer_stream != a.stream) {
+        if (!a.ev_producer) QH_HIP(hipEventCreateWithFlags(&a.ev_producer, hipEventDisableTiming));
+        QH_HIP(hipEventRecord(a.ev_producer, (hipStream_t)producer_stream));
+        QH_HIP(hipStreamWaitEvent(a.stream, a.ev_producer, 0));
+    }
+    if (int e = push(a, ss, (const float2 *)d_iq, disp_stride, n, swap_iq)) return e;
+    const int nf = (int)a.pending.size() / kMaxStitch;
+    if (int e = run_pending(a)) return e;
+    if (frames) *frames = nf;
+    return QH_OK;
+}
+
 // SnapSpectrum, analyzer.c:1337-1367: the next frame's transform of (display, sub-span) -- size complex values, fft-shifted (the second
 // half of fft_out first, analyzer.c:710-711).  qh_ana_snap_arm asks for it, the feed call that completes that frame takes it,
 // qh_ana_snap_take hands it over (*flag = 0: not there yet); qh_ana_snap_wait blocks like the reference (another thread feeds),
@@ -1061,6 +1091,9 @@ int qh_ana_rows_host(qh_ana *h, int pixout, float *out, int max_frames, int *fra
 void *qh_ana_stream(qh_ana *h) { return h ? (void *)h->stream : nullptr; }
 long long qh_ana_frames(qh_ana *h) { return h ? h->frames_total : 0; }
 int qh_ana_buff_size(qh_ana *h) { return h ? h->buff_size : 0; }
+int qh_ana_ndisp(qh_ana *h) { return h ? h->ndisp : 0; }
+int qh_ana_device(qh_ana *h) { return h ? h->device : -1; }
+int qh_ana_num_stitch(qh_ana *h) { return h ? h->num_stitch : 0; }
 int qh_ana_num_pixels(qh_ana *h) { return h ? h->num_pixels : 0; }
 
 
@@ -1076,6 +1109,21 @@ qh_ana *disp_of(int disp, const char *who)
     return g_disp[disp];
 }
 }  // namespace
+
+// The display of an id with the table of displays held, so that DestroyAnalyzer waits for the caller: the sender of a WDSP channel looks
+// its display up at every block (SetRXASpectrum, qh_wdsp_compat.cpp).  nullptr (and nothing held) when there is no such display.
+extern "C++" {
+namespace qh {
+qh_ana *wdsp_display_hold(int disp)
+{
+    g_disp_mu.lock();
+    if (disp >= 0 && disp < kMaxDisplays && g_disp[disp]) return g_disp[disp];
+    g_disp_mu.unlock();
+    return nullptr;
+}
+void wdsp_display_release() { g_disp_mu.unlock(); }
+}  // namespace qh
+}  // extern "C++"
 
 void XCreateAnalyzer(int disp, int *success, int m_size, int m_LO, int m_stitch, char *app_data_path)      // analyzer.c:1140
 {

@@ -435,6 +435,8 @@ int Engine::chain_needs(ChainCall &k)
         // (SetRXAAMDRun can switch the AM detector on beside the FM one, RXA.c:594-595 then runs both in a row: not provided, and said so)
         if (c.amd_run && c.fmd_run) return set_error(QH_ERR_UNSUPPORTED, "channel %d: the AM and the FM detector both switched on", (int)(&c - cfg.data()));
         if (c.amd_run || c.fmd_run || (c.agc_run && c.agc_mode != 0) || c.lms[0].run || c.lms[1].run || c.amsq_run || c.emnr_run || c.snba_run || c.ap_on() || c.ssql_on()) k.mixed = true;
+        // the taps' points lie between stages: the per-mode path has them, as for the meters it cannot fuse (process_chain)
+        if (c.sender_run || c.sip_run) k.mixed = k.taps = true;
         if (c.ssql_on() && ((int)(0.070 * dsp_rate) < 64))
             return set_error(QH_ERR_UNSUPPORTED, "SSQL needs ramps of 64 samples or more: dsp_rate %d is too low", dsp_rate);
         if (c.emnr_run && !emnr_tables) return set_error(QH_ERR_INVALID, "EMNR needs its gain tables first (qh_rxa_SetEMNRTables: WDSP's `calculus` and `zetaHat.bin` data)");
@@ -573,6 +575,8 @@ int Engine::process_chain(const double *d_in, long long in_stride, double *d_out
     if (int rc = refresh_ap(k)) return rc;
     if (int rc = refresh_ssql(k)) return rc;
     if (fq_list.n) if (int rc = grow(fq_noise, fq_noise_cap, buf_cap, nch)) return rc;     // the noise filter's output rows
+    if (k.taps && tap_lists[0].n) if (int rc = grow(snd_rows, snd_cap, buf_cap, nch)) return rc;      // the sender's float rows
+    snd_n = k.taps && tap_lists[0].n ? k.n_mid : 0;
     ev_used = 0;
 
     k.in = reinterpret_cast<const double2 *>(d_in); k.in_stride = in_stride;
@@ -691,7 +695,7 @@ int Engine::plan_mixed(ChainCall &k)
     // 2 no envelope in nbp0's store, 3 no angles in nbp0's store, 4 no paired real filters, 5 no second stream at all, 6-7 where the second
     // stream forks (counted down from behind the FM channels' nbp0), 8 xfmd's dc removal as a pass of its own (fm_dc_tiled_kernel), 9 the AM
     // fade leveller as a pass of its own (am_level_tiled_kernel)
-    k.split = lists[L_FM].n > 0 && lists[L_REST].n > 0 && D > 1 && !meters_on && !lists[L_AMSQ].n && !lists[L_SNB].n && !timing && !(dbg_forms & 1);
+    k.split = lists[L_FM].n > 0 && lists[L_REST].n > 0 && D > 1 && !meters_on && !k.taps && !lists[L_AMSQ].n && !lists[L_SNB].n && !timing && !(dbg_forms & 1);
     // ... and when nothing sits between a channel's last filter and the output matrix (no AGC state machine, LMS, EMNR, SNBA,
     // limiter, squelch or position-1 stage anywhere), that last stage -- nbp0 for the plain channels, bp1 for AM / SAM, the CTCSS
     // notch for FM -- applies the matrix in its store and writes the caller's buffer: the output pass (32 B per output sample) goes.
@@ -793,6 +797,7 @@ int Engine::run_mixed_front(ChainCall &k)
     }
     if (meters_on) hipLaunchKernelGGL(meter_kernel, dim3((unsigned)nch), dim3(64), 0, stream, cur, buf_cap, k.nblk, dsp_size, m_s,
                                       m_prm, (const int *)nullptr);
+    run_sender(k);                   // xsender (RXA.c:570)
     if (lists[L_AMSQ].n) {           // xamsqcap (RXA.c:571): the magnitudes of the signal behind nbp0, for xamsq at the end of the chain
         if (int rc = grow(amsq_mag, amsq_mag_cap, buf_cap, nch)) return rc;
         long long per = (n_mid + NT - 1) / NT;
@@ -1130,7 +1135,7 @@ int Engine::run_agc(ChainCall &k)
     }
     // ... and when every channel has the AGC as its last stage (nothing at position 1, no meters, squelch or audio frames), the gain
     // multiply applies the output matrix and writes the caller's rows: the output pass goes
-    bool no_p1 = !lists[L_BP1P + 1].n && !lists[L_FIX].n && !lists[L_FIX + 1].n && !lists[L_EMNR + 1].n && !lists[L_EMNR + 2].n && !lists[L_AMSQ].n && !meters_on && !eg.kind && !lists[L_AP].n && !lists[L_AP + 1].n &&
+    bool no_p1 = !lists[L_BP1P + 1].n && !lists[L_FIX].n && !lists[L_FIX + 1].n && !lists[L_EMNR + 1].n && !lists[L_EMNR + 2].n && !lists[L_AMSQ].n && !meters_on && !k.taps && !eg.kind && !lists[L_AP].n && !lists[L_AP + 1].n &&
                  !ssql_listed();
     for (int f = 0; f < 2; f++) for (int p = 1; p < 3; p++) no_p1 = no_p1 && !lists[L_LMS + 3 * f + p].n;
     k.agc_direct = tiled && no_p1 && nt_cur == lists[L_PLAIN].n && nt_other == lists[L_BP1].n;
@@ -1226,6 +1231,64 @@ int Engine::run_agc(ChainCall &k)
     return QH_OK;
 }
 
+// xsender (RXA.c:570): the listed channels' rows behind nbp0 and the S meter, ahead of xamsqcap and bpsnba, narrowed to float pairs
+void Engine::run_sender(const ChainCall &k)
+{
+    if (!k.taps || !tap_lists[0].n) return;
+    const long long per = (k.n_mid + NT - 1) / NT;
+    hipLaunchKernelGGL(sender_tap_kernel, dim3((unsigned)(per < 1024 ? per : 1024), (unsigned)tap_lists[0].n), dim3(NT), 0, stream,
+                       (const double2 *)k.cur, buf_cap, (int)k.n_mid, (const int *)tap_lists[0].dev, snd_rows, snd_cap);
+}
+
+// xsiphon (RXA.c:590): the listed channels' rows behind bp1 at position 1 and the agc meter (cur / other, as the meter reads them), ahead
+// of xcbl; a fixed AGC gain that the output matrix has still to apply goes in with the copy (tap_gain)
+void Engine::run_siphon(const ChainCall &k)
+{
+    if (!k.taps || (!tap_lists[1].n && !tap_lists[2].n)) return;
+    const long long span = k.n_mid < kSipSize ? k.n_mid : kSipSize;
+    const unsigned gx = (unsigned)((span + NT - 1) / NT);
+    for (int b = 0; b < 2; b++) {
+        const ChanList &l = tap_lists[1 + b];
+        if (!l.n) continue;
+        hipLaunchKernelGGL(siphon_tap_kernel, dim3(gx, (unsigned)l.n), dim3(NT), 0, stream, (const double2 *)(b ? k.other : k.cur), buf_cap,
+                           (int)k.n_mid, dsp_size, (const int *)l.dev, (const double *)tap_gain, sip_ring, (const int *)sip_idx);
+        if (dsp_size < kSipSize)
+            hipLaunchKernelGGL(siphon_advance_kernel, dim3((unsigned)((l.n + 255) / 256)), dim3(256), 0, stream, (int)k.n_mid, (const int *)l.dev, l.n, sip_idx);
+    }
+}
+
+// The last call's sender rows to sub-span ss of a display bank with a display per channel, on the device: the bank's stream waits for
+// the engine's (qh_ana_feed_f32), and the engine's next call for the bank's append (process_fed) -- events both ways, no host wait.
+// Spectrum2 reads element 2i + 1 as I (analyzer.c:1503-1507) and xsender hands it the chain's (I, Q) rows as they are: swap_iq = 1.
+int Engine::feed_display(qh_ana *a, int ss)
+{
+    if (!a) return set_error(QH_ERR_INVALID, "null analyzer");
+    if (qh_ana_ndisp(a) != nch || qh_ana_buff_size(a) != dsp_size || qh_ana_device(a) != device)
+        return set_error(QH_ERR_INVALID, "the display bank needs a display per channel (%d), buff_size = dsp_size (%d) and the engine's device", nch, dsp_size);
+    if (!snd_rows || snd_n <= 0 || tap_lists[0].n != nch) return set_error(QH_ERR_INVALID, "the last call left no sender rows of every channel");
+    QH_HIP(hipSetDevice(device));
+    if (!disp_fed) QH_HIP(hipEventCreateWithFlags(&disp_fed, hipEventDisableTiming));
+    if (int rc = qh_ana_feed_f32(a, ss, snd_rows, snd_cap, (int)snd_n, 1, stream, nullptr)) return rc;
+    QH_HIP(hipEventRecord(disp_fed, (hipStream_t)qh_ana_stream(a)));
+    disp_fed_pending = true;
+    return QH_OK;
+}
+
+// A process call of the C ABI: the chain (replayed from its captured launch sequence or not), then the attached display's feed.  The
+// feed is host-orchestrated (which frames are complete decides the launches), so it stays outside the captured sequence, and so does
+// the wait for the last feed's append, which has read the rows this call overwrites.
+int Engine::process_fed(bool replay, const double *d_in, long long in_stride, double *d_out, long long out_stride, int nblk)
+{
+    if (disp_fed_pending) {
+        QH_HIP(hipSetDevice(device));
+        QH_HIP(hipStreamWaitEvent(stream, disp_fed, 0));
+        disp_fed_pending = false;
+    }
+    const int rc = replay ? process_replayed(d_in, in_stride, d_out, out_stride, nblk) : process(d_in, in_stride, d_out, out_stride, nblk);
+    if (rc || !disp || nblk <= 0) return rc;
+    return feed_display(disp, disp_ss);
+}
+
 // the three stages of the listed channels, in place on the rows that hold them behind bp1 (cur / other)
 void Engine::run_audio_peak(const ChainCall &k)
 {
@@ -1307,6 +1370,7 @@ void Engine::run_output(const ChainCall &k)
         if (lists[L_BP1].n) hipLaunchKernelGGL(meter_kernel, dim3((unsigned)lists[L_BP1].n), dim3(64), 0, stream, k.other, buf_cap, k.nblk, dsp_size,
                                       m_agc, m_prm, lists[L_BP1].dev, (const double *)m_g2);
     }
+    run_siphon(k);                      // xsiphon (RXA.c:590)
     run_audio_peak(k);                  // xcbl, xspeak, xmpeak (RXA.c:591-593)
     run_ssql(k);                        // xssql (RXA.c:594)
     tick(2);

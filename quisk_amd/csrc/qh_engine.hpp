@@ -44,6 +44,7 @@
 #include "qh_audio_peak.hpp"
 #include "qh_ssql.hpp"
 #include "qh_fmsq.hpp"
+#include "qh_taps.hpp"
 #pragma clang diagnostic pop
 #include "qh_internal.hpp"
 
@@ -148,6 +149,9 @@ struct ChanCfg {
     int eqp_run = 0, eqp_nc = 2048, eqp_mp = 0, eqp_ctfmode = 0, eqp_wintype = 0, eqp_hist_at = 0;
     std::vector<double> eqp_F = { 0.0, 32.0, 63.0, 125.0, 250.0, 500.0, 1000.0, 2000.0, 4000.0, 8000.0, 16000.0 }, eqp_G = std::vector<double>(11, 0.0);
     bool eqp_dirty = true, eqp_flush = false, eqp_tie = false;
+    // xsender / xsiphon (qh_taps.hpp): both off until enabled -- a tap costs a pass (the reference runs the siphon of every channel,
+    // RXA.c:392-401, and the sender of channel 0, RXA.c:131)
+    int sender_run = 0, sip_run = 0;
     // (the new stages sit behind xwcpagc too, ahead of the panel: a fixed gain that changes while a peak still rings must not reach
     // the ringing tail, so it is applied at the AGC's spot for them as well; SSQL's detector reads amplitude, so it needs the gain too)
     bool fix_before() const
@@ -314,6 +318,28 @@ struct Engine {
     std::vector<cd> eqp_taps(const ChanCfg &c) const;
     int eqp_alloc();
     int refresh_eqp();
+    // xsender / xsiphon (qh_taps.hpp), made when a channel first runs one of them, in blocks of their own: the lists of their channels
+    // ([0] the sender's; [1] / [2] the siphon's by the buffer that holds the row behind bp1, as L_AP), the sender's float rows of the last
+    // call [nch][snd_cap] (snd_n samples each), the siphon's rings [nch][kSipSize] with their write indices [nch], and per channel the
+    // fixed AGC gain that the output matrix applies behind the siphon's point (1.0 where it does not: refresh_params)
+    ChanList tap_lists[3];
+    std::vector<int> tap_h[3];
+    int *tap_list_block = nullptr;
+    float2 *snd_rows = nullptr;
+    long long snd_cap = 0, snd_n = 0;
+    double2 *sip_ring = nullptr;
+    int *sip_idx = nullptr;
+    double *tap_gain = nullptr;
+    bool taps_listed() const { return tap_lists[0].n || tap_lists[1].n || tap_lists[2].n; }
+    int taps_alloc();
+    // a display bank fed from the sender rows at the end of every call (qh_rxa_attach_display); disp_fed: recorded on the bank's stream
+    // behind its append of the rows, waited for by the engine's stream ahead of the next call's launches
+    qh_ana *disp = nullptr;
+    int disp_ss = 0;
+    hipEvent_t disp_fed = nullptr;
+    bool disp_fed_pending = false;
+    int feed_display(qh_ana *a, int ss);
+    int process_fed(bool replay, const double *d_in, long long in_stride, double *d_out, long long out_stride, int nblk);
     // snba: the blanker's parameters, taps, state and the Toeplitz-inverse scratch
     SnbaParam snba_prm{};
     double *snba_state = nullptr, *snba_hin = nullptr, *snba_hout = nullptr, *snba_scratch = nullptr;
@@ -484,6 +510,7 @@ struct Engine {
         bool any_nbp = false, any_bp1 = false, any_eqp = false, every_nbp = true, mixed = false, long_mode = false, meters_fused = false, eg_fused = false;
         bool split = false, fm_theta_fused = false, direct = false, am_fused = false, am_lv_fused = false, side = false;
         bool agc_direct = false;                        // set where xwcpagc runs (run_agc)
+        bool taps = false;                              // a channel runs its sender or its siphon: the stores that skip their points are off
     };
     int chain_needs(ChainCall &k);
     int plan_long(ChainCall &k);
@@ -508,6 +535,8 @@ struct Engine {
     int refresh_ssql(const ChainCall &k);
     void run_ssql(const ChainCall &k);
     void run_fmsq(const ChainCall &k);
+    void run_sender(const ChainCall &k);
+    void run_siphon(const ChainCall &k);
     void run_output(const ChainCall &k);
     qh_rat *rsmpout = nullptr;          // xresample out (wdsp/RXA.c:596), only when out_rate != dsp_rate
     qh_rat *rsmpin = nullptr;           // xresample in for the rate ratios the overlap-save front stage does not cover (D == 0)

@@ -31,6 +31,7 @@ Engine::~Engine()
     if (side_stream) (void)hipStreamDestroy(side_stream);
     if (ev_fork) (void)hipEventDestroy(ev_fork);
     if (ev_join) (void)hipEventDestroy(ev_join);
+    if (disp_fed) (void)hipEventDestroy(disp_fed);
     if (own_stream && stream) (void)hipStreamDestroy(stream);
 }
 
@@ -179,6 +180,7 @@ int Engine::refresh_params()
             const double g = (c.agc_run && c.agc_mode == 0 && !c.fix_before()) ? c.agc_fixed : 1.0;
             const double g2 = g * g;            // the agc meter reads |g z|^2 off the signal ahead of the output matrix
             if (m_g2) if (int rc = put_row(m_g2, ch, g2, false)) return rc;
+            if (tap_gain) if (int rc = put_row(tap_gain, ch, g, false)) return rc;      // the siphon reads g z there too
             if (fix_gain) if (int rc = put_row(fix_gain, ch, c.agc_fixed, false)) return rc;
             const double gI = c.gain1 * c.gain2I, gQ = c.gain1 * c.gain2Q;
             const double sI = (double)(c.inselect >> 1), sQ = (double)(c.inselect & 1);
@@ -413,8 +415,11 @@ void Engine::build_lists(std::vector<int> (&h)[L_COUNT])
     int sam0 = 0;
     ssql_h[0].clear(); ssql_h[1].clear();
     fq_h.clear(); fq_pairs_h.clear();
+    for (std::vector<int> &t : tap_h) t.clear();
     for (int ch = 0; ch < nch; ch++) {
         const ChanCfg &c = cfg[(size_t)ch];
+        if (c.sender_run) tap_h[0].push_back(ch);
+        if (c.sip_run) tap_h[c.bp1_run ? 2 : 1].push_back(ch);          // where the agc meter finds the channel (L_PLAIN / L_BP1)
         if (c.amsq_run) h[L_AMSQ].push_back(ch);
         if (c.snba_run) h[L_SNBA].push_back(ch);
         if (c.snb_pos() >= 0) h[L_SNB + c.snb_pos()].push_back(ch);
@@ -469,8 +474,34 @@ void Engine::build_lists(std::vector<int> (&h)[L_COUNT])
     np_fm = (int)h[L_PAIRS_FM].size() / 2; np_am = (int)h[L_PAIRS_AM].size() / 2; np_sam = (int)h[L_PAIRS_SAM].size() / 2;
     for (int i = 0; i < L_COUNT; i++) lists[i].n = (int)h[i].size();
     for (int b = 0; b < 2; b++) ssql_lists[b].n = (int)ssql_h[b].size();
+    for (int t = 0; t < 3; t++) tap_lists[t].n = (int)tap_h[t].size();
     for (size_t i = 0; i < fq_h.size(); i += 2) { fq_pairs_h.push_back(fq_h[i]); fq_pairs_h.push_back(i + 1 < fq_h.size() ? fq_h[i + 1] : fq_h[i]); }
     fq_list.n = (int)fq_h.size(); np_fq = (int)fq_pairs_h.size() / 2;
+}
+
+// xsender / xsiphon (qh_taps.hpp): the lists at the first enable of either, the siphon's rings, indices and gains at its own (the sender's
+// rows follow the call's length: process_chain)
+int Engine::taps_alloc()
+{
+    if (!tap_list_block) {
+        if (int rc = quiesce()) return rc;
+        if (int rc = alloc(tap_list_block, 3LL * nch)) return rc;
+        for (int t = 0; t < 3; t++) tap_lists[t].dev = tap_list_block + (size_t)nch * t;
+    }
+    if ((tap_lists[1].n || tap_lists[2].n) && !sip_ring) {
+        if (int rc = quiesce()) return rc;
+        if (int rc = alloc(sip_ring, (long long)nch * kSipSize, true)) return rc;       // create_siphon: malloc0, idx 0 (siphon.c:66-67)
+        if (int rc = alloc(sip_idx, nch, true)) return rc;
+        if (int rc = alloc(tap_gain, nch)) return rc;
+        std::vector<double> g((size_t)nch);
+        for (int ch = 0; ch < nch; ch++) {
+            const ChanCfg &c = cfg[(size_t)ch];
+            g[(size_t)ch] = (c.agc_run && c.agc_mode == 0 && !c.fix_before()) ? c.agc_fixed : 1.0;
+        }
+        QH_HIP(hipMemcpyAsync(tap_gain, g.data(), g.size() * sizeof(double), hipMemcpyHostToDevice, stream));
+        QH_HIP(hipStreamSynchronize(stream));
+    }
+    return QH_OK;
 }
 
 // The stages made when a channel first runs one of them (the lists' counts say which)
@@ -480,6 +511,7 @@ int Engine::stages_alloc()
     if ((lists[L_AP].n || lists[L_AP + 1].n) && !ap_prm) if (int rc = ap_alloc()) return rc;
     if (ssql_listed() && !ssql_prm) if (int rc = ssql_alloc()) return rc;
     if (fq_list.n && !fq_prm) if (int rc = fmsq_alloc()) return rc;
+    if (taps_listed()) if (int rc = taps_alloc()) return rc;
     if ((lists[L_EMNR].n || lists[L_EMNR + 1].n || lists[L_EMNR + 2].n) && !emnr_state) if (int rc = emnr_alloc()) return rc;
     if (lists[L_SNBA].n && !snba_state) if (int rc = snba_alloc()) return rc;
     if (lists[L_AMSQ].n && !amsq_prm) {
@@ -586,6 +618,12 @@ int Engine::refresh_lists()
         ss.assign((size_t)nch * 2, 0);
         for (int b = 0; b < 2; b++) std::copy(ssql_h[b].begin(), ssql_h[b].end(), ss.begin() + (size_t)nch * b);
         QH_HIP(hipMemcpyAsync(ssql_list_block, ss.data(), ss.size() * sizeof(int), hipMemcpyHostToDevice, stream));
+    }
+    std::vector<int> tp;
+    if (tap_list_block) {
+        tp.assign((size_t)nch * 3, 0);
+        for (int t = 0; t < 3; t++) std::copy(tap_h[t].begin(), tap_h[t].end(), tp.begin() + (size_t)nch * t);
+        QH_HIP(hipMemcpyAsync(tap_list_block, tp.data(), tp.size() * sizeof(int), hipMemcpyHostToDevice, stream));
     }
     std::vector<int> fq;
     if (fq_list_block) {
@@ -1540,6 +1578,11 @@ int Engine::flush()
     if (ssql_state) launch_ssql_flush();        // flush_ssql, RXA.c:556
     if (hist_eqp[0])                            // flush_eqp, RXA.c:545
         for (int i = 0; i < 2; i++) QH_HIP(hipMemsetAsync(hist_eqp[i], 0, (size_t)nch * kHistBand * sizeof(double2), stream));
+    if (snd_rows) QH_HIP(hipMemsetAsync(snd_rows, 0, (size_t)nch * (size_t)snd_cap * sizeof(float2), stream));       // flush_sender, RXA.c:538
+    if (sip_ring) {                             // flush_siphon, RXA.c:552 (siphon.c:88-94)
+        QH_HIP(hipMemsetAsync(sip_ring, 0, (size_t)nch * kSipSize * sizeof(double2), stream));
+        QH_HIP(hipMemsetAsync(sip_idx, 0, (size_t)nch * sizeof(int), stream));
+    }
     if (fq_state) {                             // flush_fmsq, RXA.c:544
         for (int i = 0; i < 2; i++) QH_HIP(hipMemsetAsync(hist_fq[i], 0, (size_t)nch * kHistBand * sizeof(double2), stream));
         launch_fmsq_flush();

@@ -65,4 +65,8 @@ static inline bool rows_overlap(const void *a, long long a_stride_bytes, long lo
 int anb_check_settings(double samplerate, double tau, double hangtime, double advtime, double backtau, double threshold);
 int nob_check_settings(double samplerate, int mode, double slewtime, double hangtime, double advtime, double backtau, double threshold);
 
+// The display bank behind a WDSP display id (XCreateAnalyzer), held until wdsp_display_release: DestroyAnalyzer waits (qh_analyzer.hip)
+qh_ana *wdsp_display_hold(int disp);
+void wdsp_display_release();
+
 }  // namespace qh

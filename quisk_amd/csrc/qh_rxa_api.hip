@@ -664,8 +664,7 @@ int qh_rxa_process(qh_rxa *h, const double *d_in, long long in_stride, double *d
     if (!d_in || !d_out) return set_error(QH_ERR_INVALID, "null buffer");
     if (in_stride < (long long)nblk * h->e.dsp_insize || out_stride < (long long)nblk * h->e.dsp_outsize)
         return set_error(QH_ERR_INVALID, "stride shorter than nblk blocks");
-    if (h->e.graph_on) return h->e.process_replayed(d_in, in_stride, d_out, out_stride, nblk);
-    return h->e.process(d_in, in_stride, d_out, out_stride, nblk);
+    return h->e.process_fed(h->e.graph_on, d_in, in_stride, d_out, out_stride, nblk);
 }
 
 // ---- audio egress ---------------------------------------------------------------------------------------------------
@@ -703,7 +702,7 @@ int qh_rxa_process_audio(qh_rxa *h, const double *d_in, long long in_stride, voi
                      (long long)nblk * h->e.dsp_outsize * egress_frame_bytes(fmt), h->e.nch))
         return set_error(QH_ERR_INVALID, "qh_rxa_process_audio: the output rows overlap the input rows (in place is not supported)");
     h->e.eg = f;
-    const int rc = h->e.process(d_in, in_stride, nullptr, 0, nblk);
+    const int rc = h->e.process_fed(false, d_in, in_stride, nullptr, 0, nblk);
     h->e.eg = EgressFmt{};
     return rc;
 }
@@ -759,7 +758,7 @@ int qh_rxa_process_packed(qh_rxa *h, const void *d_src, long long src_bytes, con
     h->e.pk_src = static_cast<const unsigned char *>(d_src);
     h->e.pk = pk;
     // process() wants an input pointer; the packed kernels never touch it
-    const int rc = h->e.process(reinterpret_cast<const double *>(d_src), (long long)nblk * h->e.dsp_insize, d_out, out_stride, nblk);
+    const int rc = h->e.process_fed(false, reinterpret_cast<const double *>(d_src), (long long)nblk * h->e.dsp_insize, d_out, out_stride, nblk);
     h->e.pk_src = nullptr;
     return rc;
 }
@@ -770,6 +769,102 @@ int qh_rxa_flush(qh_rxa *h)
     if (!h) return set_error(QH_ERR_INVALID, "null engine");
     QH_RXA_LOCK(h);
     return h->e.flush();
+}
+
+// ---- the data taps (qh_taps.hpp) -------------------------------------------------------------------------------------
+// xsender's run && flag (sender.c:66-68) of channel ch, -1 = all: later calls leave the channel's signal behind nbp0 as float pairs
+int qh_rxa_set_sender(qh_rxa *h, int ch, int run)
+{
+    if (h && h->e.disp && !run) return set_error(QH_ERR_INVALID, "qh_rxa_set_sender: a display is attached (qh_rxa_attach_display), it reads every channel's rows");
+    FOR_CH(h, ch, { run = run ? 1 : 0; if (c.sender_run != run) { c.sender_run = run; h->e.lists_dirty = true; } });
+}
+
+int qh_rxa_sender_rows(qh_rxa *h, const float **d_rows, long long *stride, int *n)
+{
+    if (!h || !d_rows || !stride || !n) return set_error(QH_ERR_INVALID, "qh_rxa_sender_rows: null argument");
+    QH_RXA_LOCK(h);
+    *d_rows = reinterpret_cast<const float *>(h->e.snd_rows); *stride = h->e.snd_cap; *n = (int)h->e.snd_n;
+    return QH_OK;
+}
+
+int qh_rxa_sender_rows_host(qh_rxa *h, int ch, float *out, int max, int *n)
+{
+    if (!h || !out || !n) return set_error(QH_ERR_INVALID, "qh_rxa_sender_rows_host: null argument");
+    QH_RXA_LOCK(h);
+    Engine &e = h->e;
+    if (ch < 0 || ch >= e.nch) return set_error(QH_ERR_INVALID, "channel %d out of range", ch);
+    if (!e.cfg[(size_t)ch].sender_run) return set_error(QH_ERR_INVALID, "channel %d: the sender is off (qh_rxa_set_sender)", ch);
+    *n = (int)e.snd_n;
+    if (e.snd_n > max) return set_error(QH_ERR_INVALID, "qh_rxa_sender_rows_host: %lld samples, room for %d", e.snd_n, max);
+    if (e.snd_n == 0) return QH_OK;
+    QH_HIP(hipSetDevice(e.device));
+    QH_HIP(hipMemcpyAsync(out, e.snd_rows + (size_t)ch * (size_t)e.snd_cap, (size_t)e.snd_n * sizeof(float2), hipMemcpyDeviceToHost, e.stream));
+    QH_HIP(hipStreamSynchronize(e.stream));
+    return QH_OK;
+}
+
+// xsiphon's run (siphon.c:100) of channel ch, -1 = all.  A siphon that is switched on starts as flush_siphon leaves it (siphon.c:88-94).
+int qh_rxa_set_siphon(qh_rxa *h, int ch, int run)
+{
+    FOR_CH(h, ch, {
+        run = run ? 1 : 0;
+        if (c.sip_run == run) continue;
+        c.sip_run = run; h->e.lists_dirty = true;
+        if (run && h->e.sip_ring) {
+            QH_HIP(hipSetDevice(h->e.device));
+            QH_HIP(hipMemsetAsync(h->e.sip_ring + (size_t)_i * kSipSize, 0, (size_t)kSipSize * sizeof(double2), h->e.stream));
+            QH_HIP(hipMemsetAsync(h->e.sip_idx + _i, 0, sizeof(int), h->e.stream));
+        }
+    });
+}
+
+// suck (siphon.c:148-163) with outsize = size: the newest `size` samples, oldest first, as (I, Q) doubles.  The reference leaves sipout as
+// it was when outsize > sipsize and its callers then read `size` samples of a sipsize buffer; here such a size is refused.
+int qh_rxa_get_sip(qh_rxa *h, int ch, double *out, int size)
+{
+    if (!h || !out) return set_error(QH_ERR_INVALID, "qh_rxa_get_sip: null argument");
+    QH_RXA_LOCK(h);
+    Engine &e = h->e;
+    if (ch < 0 || ch >= e.nch) return set_error(QH_ERR_INVALID, "channel %d out of range", ch);
+    if (size < 0 || size > kSipSize) return set_error(QH_ERR_INVALID, "qh_rxa_get_sip: size %d outside 0 .. %d", size, kSipSize);
+    if (!e.cfg[(size_t)ch].sip_run) return set_error(QH_ERR_INVALID, "channel %d: the siphon is off (qh_rxa_set_siphon)", ch);
+    if (size == 0) return QH_OK;
+    if (!e.sip_ring) { std::memset(out, 0, (size_t)size * 2 * sizeof(double)); return QH_OK; }      // no call since it was switched on
+    QH_HIP(hipSetDevice(e.device));
+    QH_HIP(hipStreamSynchronize(e.stream));
+    int idx = 0;
+    QH_HIP(hipMemcpy(&idx, e.sip_idx + ch, sizeof(int), hipMemcpyDeviceToHost));
+    const double2 *ring = e.sip_ring + (size_t)ch * kSipSize;
+    const int j = (idx - size) & (kSipSize - 1), first = kSipSize - j < size ? kSipSize - j : size;
+    QH_HIP(hipMemcpy(out, ring + j, (size_t)first * sizeof(double2), hipMemcpyDeviceToHost));
+    if (first < size) QH_HIP(hipMemcpy(out + 2 * (size_t)first, ring, (size_t)(size - first) * sizeof(double2), hipMemcpyDeviceToHost));
+    return QH_OK;
+}
+
+// The last call's sender rows to sub-span ss of a display bank, once (Engine::feed_display); every channel's sender must be on
+int qh_rxa_feed_display(qh_rxa *h, qh_ana *a, int ss)
+{
+    if (!h) return set_error(QH_ERR_INVALID, "null engine");
+    QH_RXA_LOCK(h);
+    return h->e.feed_display(a, ss);
+}
+
+// xsender -> Spectrum2 (sender.c:81) bank to bank: every later process call ends by feeding its sender rows to sub-span ss of a's
+// displays, display d from channel d.  a = NULL detaches (the senders stay on).  The bank must outlive the attachment.
+int qh_rxa_attach_display(qh_rxa *h, qh_ana *a, int ss)
+{
+    if (!h) return set_error(QH_ERR_INVALID, "null engine");
+    QH_RXA_LOCK(h);
+    Engine &e = h->e;
+    if (!a) { e.disp = nullptr; return QH_OK; }
+    if (qh_ana_ndisp(a) != e.nch || qh_ana_buff_size(a) != e.dsp_size || qh_ana_device(a) != e.device)
+        return set_error(QH_ERR_INVALID, "qh_rxa_attach_display: the bank needs a display per channel (%d), buff_size = dsp_size (%d) and the engine's device",
+                         e.nch, e.dsp_size);
+    if (ss < 0 || ss >= qh_ana_num_stitch(a)) return set_error(QH_ERR_INVALID, "qh_rxa_attach_display: sub-span %d outside the bank's", ss);
+    for (ChanCfg &c : e.cfg) if (!c.sender_run) { c.sender_run = 1; e.lists_dirty = true; }
+    e.epoch++;
+    e.disp = a; e.disp_ss = ss;
+    return QH_OK;
 }
 
 // Meters (wdsp/meter.c): enable != 0 makes later process calls maintain the ADC, S and AGC meters.
@@ -958,7 +1053,7 @@ int qh_rxa_process_host(qh_rxa *h, const double *h_in, long long in_stride, doub
     int rc = QH_OK;
     const hipError_t err = hipMemcpy2DAsync(din, (size_t)n_in * sizeof(double2), h_in, (size_t)in_stride * sizeof(double2),
                                             (size_t)n_in * sizeof(double2), (size_t)e.nch, hipMemcpyHostToDevice, e.stream);
-    if (err == hipSuccess) rc = e.process(reinterpret_cast<const double *>(din), n_in, reinterpret_cast<double *>(dout), n_out, nblk);
+    if (err == hipSuccess) rc = e.process_fed(false, reinterpret_cast<const double *>(din), n_in, reinterpret_cast<double *>(dout), n_out, nblk);
     return finish_host(e, rc, err, h_out, out_stride, n_out, din, dout);
 }
 

@@ -169,6 +169,9 @@ struct Chan {
     bool dev_mode = false;
     double *d_r1 = nullptr, *d_r2 = nullptr;
     DevSlew *d_up = nullptr;
+    // xsender's flag and arguments (SetRXASpectrum, sender.c:111-122); the siphon is off until RXAGetaSipF / RXAGetaSipF1 first asks
+    int spec_flag = 0, spec_disp = 0, spec_ss = 1;
+    bool sip_on = false;
 };
 
 Chan g_ch[kMaxChannels];
@@ -232,6 +235,19 @@ int apply_slew(Chan &c, const Slew &sl, double *buf, int n, long long p0, int ri
 
 long long g_graph_launches = 0;      // blocks replayed by engines that have since been closed
 
+// xsender (sender.c:66-86) behind a DSP block: run is `channel == 0` (RXA.c:131).  The block's float rows go to the display on the device
+// (Spectrum2's part, sender.c:81); the display is looked up now and held while it is fed, so DestroyAnalyzer leaves nothing dangling.  A
+// display that is not there, or whose buff_size is not dsp_size, is an error in qh_wdsp_status() and the block's audio is as it was.
+void send_spectrum(Chan &c)
+{
+    if (!c.spec_flag || &c != &g_ch[0]) return;
+    qh_ana *a = qh::wdsp_display_hold(c.spec_disp);
+    if (!a) { g_status = qh::set_error(QH_ERR_INVALID, "SetRXASpectrum: display %d does not exist", c.spec_disp); return; }
+    const int rc = qh_rxa_feed_display(c.eng, a, c.spec_ss);
+    qh::wdsp_display_release();
+    if (rc) g_status = rc;
+}
+
 // one DSP-thread iteration: dexchange (wdsp/iobuffs.c:583-604) then xrxa on the GPU
 int dsp_iteration(Chan &c)
 {
@@ -269,6 +285,7 @@ int dsp_iteration(Chan &c)
         rc = qh_rxa_process(c.eng, c.h_in, c.dsp_insize, c.h_out, c.dsp_outsize, 1);
     }
     if (rc) return rc;
+    send_spectrum(c);
     rc = qh_rxa_synchronize(c.eng);
     if (rc) return rc;
     std::memcpy(c.outbuff.data(), c.h_out, (size_t)c.dsp_outsize * 2 * sizeof(double));
@@ -367,6 +384,7 @@ void OpenChannel(int channel, int in_size, int dsp_size, int input_samplerate, i
     c.in_rate = input_samplerate; c.dsp_rate = dsp_rate; c.out_rate = output_samplerate;
     c.tdelayup = tdelayup; c.tslewup = tslewup; c.tdelaydown = tdelaydown; c.tslewdown = tslewdown;
     c.bfo = bfo; c.state = state;
+    c.spec_flag = 0; c.spec_disp = 0; c.spec_ss = 1; c.sip_on = false;     // create_sender / create_siphon, RXA.c:130-139,392-401
     // pre_main_build, wdsp/channel.c:39-52
     c.dsp_insize = qh_rxa_dsp_insize(c.eng);
     c.dsp_outsize = qh_rxa_dsp_outsize(c.eng);
@@ -581,6 +599,7 @@ int fexchange0_dev(Chan &c, const double *d_in, double *d_out, int *error)
             (void)hipMemsetAsync(d_out, 0, (size_t)c.out_size * 16, s);
             return rc;
         }
+        send_spectrum(c);
     }
     if (!out_done) { output(); launch(); }
     if (hipGetLastError() != hipSuccess) return qh::set_error(QH_ERR_HIP, "fexchange0: launch failed");
@@ -789,6 +808,37 @@ void SetRXAAMDFadeLevel(int channel, int levelfade) { WDSP_SETTER(qh_rxa_SetRXAA
 void SetRXAFMDeviation(int channel, double deviation) { WDSP_SETTER(qh_rxa_SetRXAFMDeviation(L.c->eng, 0, deviation)); }
 void SetRXACTCSSFreq(int channel, double freq) { WDSP_SETTER(qh_rxa_SetRXACTCSSFreq(L.c->eng, 0, freq)); }
 void SetRXACTCSSRun(int channel, int run) { WDSP_SETTER(qh_rxa_SetRXACTCSSRun(L.c->eng, 0, run)); }
+
+void SetRXASpectrum(int channel, int flag, int disp, int ss, int LO)
+{
+    (void)LO;
+    g_status = QH_OK;
+    Locked L(channel);
+    if (!L.c) return;
+    L.c->spec_flag = flag; L.c->spec_disp = disp; L.c->spec_ss = ss;
+    if (channel != 0) return;               // the sender of every other channel is made with run 0 (RXA.c:131) and nothing sets it
+    if (int rc = qh_rxa_set_sender(L.c->eng, 0, flag ? 1 : 0)) g_status = rc;
+}
+
+// RXAGetaSipF (iq = 0) / RXAGetaSipF1 (iq = 1)
+static void get_sip(int channel, float *out, int size, int iq)
+{
+    g_status = QH_OK;
+    Locked L(channel);
+    if (!L.c || !out) return;
+    if (!L.c->sip_on) {
+        if (int rc = qh_rxa_set_siphon(L.c->eng, 0, 1)) { g_status = rc; return; }
+        L.c->sip_on = true;
+    }
+    std::vector<double> z(size > 0 && size <= 4096 ? (size_t)size * 2 : 2);
+    if (int rc = qh_rxa_get_sip(L.c->eng, 0, z.data(), size)) { g_status = rc; return; }
+    for (int i = 0; i < size; i++) {
+        if (iq) { out[2 * i] = (float)z[(size_t)2 * i]; out[2 * i + 1] = (float)z[(size_t)2 * i + 1]; }
+        else out[i] = (float)z[(size_t)2 * i];
+    }
+}
+void RXAGetaSipF(int channel, float *out, int size) { get_sip(channel, out, size, 0); }
+void RXAGetaSipF1(int channel, float *out, int size) { get_sip(channel, out, size, 1); }
 
 double GetRXAMeter(int channel, int mt)
 {

@@ -127,6 +127,19 @@ def load():
     L.qh_wdsp_fexchange0_device.argtypes = [i, vp, i, vp]
     L.qh_wdsp_fexchange0_device.restype = i
     L.qh_rxa_GetRXAMeter.argtypes = [vp, i, i, C.POINTER(d)]
+    L.qh_rxa_set_sender.argtypes = [vp, i, i]
+    L.qh_rxa_sender_rows.argtypes = [vp, C.POINTER(vp), C.POINTER(ll), C.POINTER(i)]
+    L.qh_rxa_sender_rows_host.argtypes = [vp, i, vp, i, C.POINTER(i)]
+    L.qh_rxa_set_siphon.argtypes = [vp, i, i]
+    L.qh_rxa_get_sip.argtypes = [vp, i, vp, i]
+    L.qh_rxa_attach_display.argtypes = [vp, vp, i]
+    L.qh_rxa_feed_display.argtypes = [vp, vp, i]
+    L.SetRXASpectrum.argtypes = [i, i, i, i, i]
+    L.SetRXASpectrum.restype = None
+    L.RXAGetaSipF.argtypes = [i, vp, i]
+    L.RXAGetaSipF.restype = None
+    L.RXAGetaSipF1.argtypes = [i, vp, i]
+    L.RXAGetaSipF1.restype = None
     L.qh_rxa_flush.argtypes = [vp]
     L.qh_rxa_flush.restype = i
     L.qh_rxa_enable_timing.argtypes = [vp, i]
@@ -220,6 +233,9 @@ def load():
     L.qh_ana_reset_pixel_buffers.argtypes = [vp]
     L.qh_ana_feed.argtypes = [vp, i, vp, ll, i, C.POINTER(i)]
     L.qh_ana_feed_host.argtypes = [vp, i, vp, ll, i, i, C.POINTER(i)]
+    L.qh_ana_feed_f32.argtypes = [vp, i, vp, ll, i, i, vp, C.POINTER(i)]
+    for n in ("ndisp", "device", "num_stitch", "buff_size"):
+        getattr(L, "qh_ana_" + n).argtypes = [vp]
     L.qh_ana_get_pixels.argtypes = [vp, i, i, vp, C.POINTER(i)]
     L.qh_ana_rows.argtypes = [vp, i, C.POINTER(vp), C.POINTER(i), C.POINTER(i)]
     L.qh_ana_rows_host.argtypes = [vp, i, vp, i, C.POINTER(i)]

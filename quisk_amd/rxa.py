@@ -150,6 +150,41 @@ class RxaEngine:
         check(self._L.qh_rxa_GetRXAMeter(self._h, ch, mt, C.byref(v)))
         return v.value
 
+    # the data taps (wdsp/sender.c, wdsp/siphon.c): off until enabled, ch -1 = every channel
+    def set_sender(self, ch, run=True):
+        """xsender (RXA.c:570): later calls leave channel ch's signal behind nbp0 as float pairs on the device"""
+        check(self._L.qh_rxa_set_sender(self._h, ch, 1 if run else 0))
+
+    def sender_rows_ptr(self):
+        """(device pointer, row stride in float pairs, samples per row) of the last call's sender rows"""
+        p, s, n = C.c_void_p(), C.c_longlong(0), C.c_int(0)
+        check(self._L.qh_rxa_sender_rows(self._h, C.byref(p), C.byref(s), C.byref(n)))
+        return p.value, s.value, n.value
+
+    def sender_rows_host(self, ch):
+        """complex64 [n]: the last call's sender row of channel ch (I + jQ, the chain's order)"""
+        _, _, n = self.sender_rows_ptr()
+        out = np.zeros(max(n, 1), dtype=np.complex64)
+        got = C.c_int(0)
+        check(self._L.qh_rxa_sender_rows_host(self._h, ch, out.ctypes.data, out.size, C.byref(got)))
+        return out[:got.value]
+
+    def set_siphon(self, ch, run=True):
+        """xsiphon (RXA.c:590): later calls keep the newest 4096 samples of channel ch's audio behind the AGC"""
+        check(self._L.qh_rxa_set_siphon(self._h, ch, 1 if run else 0))
+
+    def get_sip(self, ch, size):
+        """complex128 [size]: the newest `size` samples of channel ch's siphon, oldest first (suck, siphon.c:148-163)"""
+        out = np.zeros(max(int(size), 0), dtype=np.complex128)
+        check(self._L.qh_rxa_get_sip(self._h, ch, out.ctypes.data if out.size else np.zeros(1, dtype=np.complex128).ctypes.data, int(size)))
+        return out
+
+    def attach_display(self, bank, ss=0):
+        """Every later process call ends by feeding its sender rows to sub-span ss of an AnalyzerBank with a display per channel
+        (None detaches).  The bank is kept alive while it is attached."""
+        check(self._L.qh_rxa_attach_display(self._h, bank._h if bank is not None else None, ss))
+        self._display = bank
+
     def pll_repairs(self):
         return self._L.qh_rxa_pll_repairs(self._h)
 
