@@ -260,6 +260,25 @@ int qh_rxa_sender_rows_host(qh_rxa *e, int ch, float *out, int max, int *n);    
 int qh_rxa_set_siphon(qh_rxa *e, int ch, int run);                                 /* wdsp/siphon.c:96-130, mode 0; switched on, it starts flushed (siphon.c:88-94) */
 int qh_rxa_get_sip(qh_rxa *e, int ch, double *out, int size);                      /* wdsp/siphon.c:148-163 (suck): 2 size doubles */
 
+/* gen0, the signal generator at the head of xrxa (wdsp/gen.c:173-354, RXA.c:60-66,565).  A channel whose generator runs has its buffer
+ * behind xshift / xresample REPLACED by the generated signal (both still run and keep their state; the call's input is not looked at
+ * otherwise): the adc meter, the notched band-pass and everything behind them see the generator.  Created with run 0, mode 2, as create_rxa
+ * does.  Modes: 0 tone, 1 two tones (0.5 / 0.5 at 900 / 1700 Hz, no RXA setter), 2 noise, 3 sweep, 6 a keyed 1 kHz pulse (0.25 Hz, duty
+ * 0.25, 2 ms edges, no RXA setter), any other silence.  Every mode keeps its own state and only the running mode's moves.  ch -1 = every
+ * channel.  Deviations: modes 4 and 5 (sawtooth, triangle: "audio only", no RXA setter) are refused while the generator runs -- the next
+ * process call returns QH_ERR_UNSUPPORTED and runs nothing; the noise is the reference's polar method on a counter-based source keyed by
+ * (seed, channel, sample), not rand() seeded by the clock and shared by the process; a sweep whose period exceeds 2^27 samples resets at
+ * the closed form's instants, not the addition chain's. */
+int qh_rxa_SetRXAPreGenRun(qh_rxa *e, int ch, int run);                            /* wdsp/gen.c:384-390 */
+int qh_rxa_SetRXAPreGenMode(qh_rxa *e, int ch, int mode);                          /* wdsp/gen.c:392-398 */
+int qh_rxa_SetRXAPreGenToneMag(qh_rxa *e, int ch, double mag);                     /* wdsp/gen.c:400-406 */
+int qh_rxa_SetRXAPreGenToneFreq(qh_rxa *e, int ch, double freq);                   /* wdsp/gen.c:408-415: the phase goes to 0 (calc_tone) */
+int qh_rxa_SetRXAPreGenNoiseMag(qh_rxa *e, int ch, double mag);                    /* wdsp/gen.c:417-423 */
+int qh_rxa_SetRXAPreGenSweepMag(qh_rxa *e, int ch, double mag);                    /* wdsp/gen.c:425-431 */
+int qh_rxa_SetRXAPreGenSweepFreq(qh_rxa *e, int ch, double freq1, double freq2);   /* wdsp/gen.c:433-441: the sweep starts again (calc_sweep) */
+int qh_rxa_SetRXAPreGenSweepRate(qh_rxa *e, int ch, double rate);                  /* wdsp/gen.c:443-450: the sweep starts again (calc_sweep) */
+int qh_rxa_set_gen_seed(qh_rxa *e, int ch, unsigned long long seed);               /* wdsp/gen.c:131 (srand): the noise stream's seed; default: a fixed function of ch */
+
 /* flush_rxa (wdsp/RXA.c:527-559): zero the NCO phase and every filter history of every channel. */
 int qh_rxa_flush(qh_rxa *e);
 
@@ -330,6 +349,16 @@ void SetRXAFMDeviation(int channel, double deviation);                          
 void SetRXACTCSSFreq(int channel, double freq);                                  /* wdsp/fmd.c:248-258 */
 void SetRXACTCSSRun(int channel, int run);                                       /* wdsp/fmd.c:260-267 */
 double GetRXAMeter(int channel, int mt);                                         /* wdsp/meter.c:133-142 */
+/* gen0 (see qh_rxa_SetRXAPreGenRun).  SetRXAPreGenMode 4 or 5 while the generator runs: the next fexchange0 sets qh_wdsp_status() and leaves
+ * its output buffer alone. */
+void SetRXAPreGenRun(int channel, int run);                                      /* wdsp/gen.c:384-390 */
+void SetRXAPreGenMode(int channel, int mode);                                    /* wdsp/gen.c:392-398 */
+void SetRXAPreGenToneMag(int channel, double mag);                               /* wdsp/gen.c:400-406 */
+void SetRXAPreGenToneFreq(int channel, double freq);                             /* wdsp/gen.c:408-415 */
+void SetRXAPreGenNoiseMag(int channel, double mag);                              /* wdsp/gen.c:417-423 */
+void SetRXAPreGenSweepMag(int channel, double mag);                              /* wdsp/gen.c:425-431 */
+void SetRXAPreGenSweepFreq(int channel, double freq1, double freq2);             /* wdsp/gen.c:433-441 */
+void SetRXAPreGenSweepRate(int channel, double rate);                            /* wdsp/gen.c:443-450 */
 /* The sender runs on channel 0 only, as create_rxa makes it (RXA.c:131): on another channel the call is accepted and does nothing.  With
  * flag set, every DSP block of channel 0 feeds display `disp` (XCreateAnalyzer), sub-span ss, on the device; the display is looked up at
  * each block, and one that does not exist or whose buff_size is not dsp_size sets qh_wdsp_status() and is fed nothing.  The siphon is off

@@ -403,4 +403,33 @@ SpeakDesign design_speak(double f, double bw, double gain, double rate)
     return d;
 }
 
+SweepWalk sweep_walk(double rate, double f1, double f2, double sweeprate, long long max_walk, int ck_step)
+{
+    const double twopi = kTwoPi;
+    SweepWalk w;
+    w.dphs0 = twopi * f1 / rate;                    // calc_sweep, gen.c:49-55
+    w.d2phs = twopi * sweeprate / (rate * rate);
+    const double dphsmax = twopi * f2 / rate;
+    if (!std::isfinite(w.dphs0) || !std::isfinite(w.d2phs) || !std::isfinite(dphsmax)) return w;       // no comparison ever holds: no reset
+    if (w.d2phs > 0.0 && w.dphs0 <= dphsmax && (dphsmax - w.dphs0) / w.d2phs >= (double)max_walk) {
+        const long double est = std::floor(((long double)dphsmax - (long double)w.dphs0) / (long double)w.d2phs) + 1.0L;
+        w.walked = false;
+        w.P = est < 9.0e18L ? (long long)est : 0;
+        const long double tp = 6.283185307179586476925286766559L, P = (long double)w.P;
+        w.full = (double)std::fmod(std::fmod(P * (long double)w.dphs0, tp) + std::fmod((long double)w.d2phs * (0.5L * P * (P - 1.0L)), tp), tp);
+        return w;
+    }
+    double phs = 0.0, dphs = w.dphs0;
+    for (long long n = 0;;) {
+        if (n % ck_step == 0) w.ck.emplace_back(phs, dphs);
+        phs += dphs;                                // gen.c:253-258
+        dphs += w.d2phs;
+        if (phs >= twopi) phs -= twopi;
+        if (phs < 0.0) phs += twopi;
+        n++;
+        if (dphs > dphsmax) { w.P = n; w.full = phs; return w; }
+        if (!(w.d2phs > 0.0) || dphs + w.d2phs == dphs) { w.P = 0; w.ck.clear(); return w; }      // it never will (or the sum has stopped moving)
+    }
+}
+
 }  // namespace qh

@@ -49,6 +49,17 @@ std::vector<cd> make_mask(const std::vector<cd> &h, int nfft);
 struct SpeakDesign { double a0, a1, a2, b1, b2, fgain; };
 SpeakDesign design_speak(double f, double bw, double gain, double rate);
 
+// The sweep of WDSP's signal generator (wdsp/gen.c:49-55, 246-261) by the reference's own chain: dphs starts at TWOPI f1 / rate,
+// `phs += dphs; dphs += d2phs` once a sample with phs wrapped into [0, 2 pi), and the sample whose sum exceeds dphsmax = TWOPI f2 / rate
+// resets dphs.  P: the samples from one reset to the next (the same every period: a reset restarts from the same expression), 0 when
+// the chain never gets there (d2phs <= 0 and the first sum does not exceed).  The instants hang on the sums' rounding -- at the defaults
+// exact arithmetic gives a tie that the chain decides one sample earlier -- so P is counted, not solved for.  ck: (phs, dphs) of the chain
+// every ck_step samples of a period, phs from 0 at the reset; full: phs when the period ends.  Where the closed-form estimate of P
+// exceeds max_walk additions the chain is not walked: P is the closed form's count (floor((dphsmax - dphs) / d2phs) + 1), ck stays
+// empty, full is the exact quadratic's, and `walked` is false.
+struct SweepWalk { long long P = 0; double dphs0 = 0.0, d2phs = 0.0, full = 0.0; bool walked = true; std::vector<std::pair<double, double>> ck; };
+SweepWalk sweep_walk(double rate, double f1, double f2, double sweeprate, long long max_walk, int ck_step);
+
 // Concatenated per-pass twiddle tables for qh::FftRR<N> (see the Plan table in qh_fft.hpp).
 std::vector<cd> fft_twiddle_table(int n);
 

@@ -437,6 +437,14 @@ int Engine::chain_needs(ChainCall &k)
         if (c.amd_run || c.fmd_run || (c.agc_run && c.agc_mode != 0) || c.lms[0].run || c.lms[1].run || c.amsq_run || c.emnr_run || c.snba_run || c.ap_on() || c.ssql_on()) k.mixed = true;
         // the taps' points lie between stages: the per-mode path has them, as for the meters it cannot fuse (process_chain)
         if (c.sender_run || c.sip_run) k.mixed = k.taps = true;
+        // gen0 writes between the front stage and the adc meter: the per-mode path has that point too.  The sawtooth's and the triangle's
+        // wraps (`t += delta; if (t > period) t -= period`, gen.c:267-284) hang on the rounding of a sum that is not periodic, which only
+        // the sequential chain reproduces; the reference marks both "audio only" and no RXA setter reaches their parameters: refused.
+        if (c.gen_run) {
+            if (c.gen_mode == 4 || c.gen_mode == 5)
+                return set_error(QH_ERR_UNSUPPORTED, "channel %d: gen0 mode %d (%s) is not provided", (int)(&c - cfg.data()), c.gen_mode, c.gen_mode == 4 ? "sawtooth" : "triangle");
+            k.mixed = k.gen = true;
+        }
         if (c.ssql_on() && ((int)(0.070 * dsp_rate) < 64))
             return set_error(QH_ERR_UNSUPPORTED, "SSQL needs ramps of 64 samples or more: dsp_rate %d is too low", dsp_rate);
         if (c.emnr_run && !emnr_tables) return set_error(QH_ERR_INVALID, "EMNR needs its gain tables first (qh_rxa_SetEMNRTables: WDSP's `calculus` and `zetaHat.bin` data)");
@@ -555,6 +563,7 @@ int Engine::process_chain(const double *d_in, long long in_stride, double *d_out
     if (meters_on) if (int rc = meters_alloc()) return rc;
     if (int rc = refresh_params()) return rc;
     if (k.mixed) if (int rc = refresh_demod()) return rc;
+    if (k.gen) if (int rc = refresh_gen()) return rc;
     // bp1 on the linear path (SetRXABandpassRun on an all-SSB engine): run_linear flips bp1's ping-pong pair like the per-mode path, but
     // refresh_lists, which keeps bp1_listed / bp1_hist_at, runs from refresh_demod only.  Left alone, the first per-mode call found no
     // channel listed and bp1_hist_at still at the half of the engine's first call, and after an odd number of linear calls copied that
@@ -695,7 +704,7 @@ int Engine::plan_mixed(ChainCall &k)
     // 2 no envelope in nbp0's store, 3 no angles in nbp0's store, 4 no paired real filters, 5 no second stream at all, 6-7 where the second
     // stream forks (counted down from behind the FM channels' nbp0), 8 xfmd's dc removal as a pass of its own (fm_dc_tiled_kernel), 9 the AM
     // fade leveller as a pass of its own (am_level_tiled_kernel)
-    k.split = lists[L_FM].n > 0 && lists[L_REST].n > 0 && D > 1 && !meters_on && !k.taps && !lists[L_AMSQ].n && !lists[L_SNB].n && !timing && !(dbg_forms & 1);
+    k.split = lists[L_FM].n > 0 && lists[L_REST].n > 0 && D > 1 && !meters_on && !k.taps && !k.gen && !lists[L_AMSQ].n && !lists[L_SNB].n && !timing && !(dbg_forms & 1);
     // ... and when nothing sits between a channel's last filter and the output matrix (no AGC state machine, LMS, EMNR, SNBA,
     // limiter, squelch or position-1 stage anywhere), that last stage -- nbp0 for the plain channels, bp1 for AM / SAM, the CTCSS
     // notch for FM -- applies the matrix in its store and writes the caller's buffer: the output pass (32 B per output sample) goes.
@@ -788,6 +797,7 @@ int Engine::run_mixed_front(ChainCall &k)
         if (int rc = run_front(k.in, k.in_stride, cur, buf_cap, nullptr, n_in, n_mid, nullptr, 0, 3)) return rc;          // histories, oscillator phases
     } else {
         if (int rc = run_front(k.in, k.in_stride, cur, buf_cap, nullptr, n_in, n_mid)) return rc;
+        run_gen(k);                  // xgen (RXA.c:565)
         if (meters_on) hipLaunchKernelGGL(meter_kernel, dim3((unsigned)nch), dim3(64), 0, stream, cur, buf_cap, k.nblk, dsp_size, m_adc,
                                           m_prm, (const int *)nullptr);
         if (k.any_nbp) {
@@ -1238,6 +1248,18 @@ void Engine::run_sender(const ChainCall &k)
     const long long per = (k.n_mid + NT - 1) / NT;
     hipLaunchKernelGGL(sender_tap_kernel, dim3((unsigned)(per < 1024 ? per : 1024), (unsigned)tap_lists[0].n), dim3(NT), 0, stream,
                        (const double2 *)k.cur, buf_cap, (int)k.n_mid, (const int *)tap_lists[0].dev, snd_rows, snd_cap);
+}
+
+// xgen (RXA.c:565): the listed channels' rows behind xshift and xresample, which have run and moved their state on, are replaced; the
+// adc meter, bpsnba's input, nbp0 and everything behind them read the generated signal.  Then the running modes' state moves on.
+void Engine::run_gen(const ChainCall &k)
+{
+    if (!k.gen || !gen_list.n) return;
+    const long long per = (k.n_mid + NT - 1) / NT;
+    hipLaunchKernelGGL(gen_kernel, dim3((unsigned)(per < 1024 ? per : 1024), (unsigned)gen_list.n), dim3(NT), 0, stream, k.cur, buf_cap, (int)k.n_mid,
+                       (const int *)gen_list.dev, (const GenParam *)gen_prm, (const GenState *)gen_state, (const double2 *)gen_ck, (const double *)gen_ctrans);
+    hipLaunchKernelGGL(gen_advance_kernel, dim3((unsigned)((gen_list.n + 255) / 256)), dim3(256), 0, stream, (int)k.n_mid, (const int *)gen_list.dev, gen_list.n,
+                       (const GenParam *)gen_prm, gen_state);
 }
 
 // xsiphon (RXA.c:590): the listed channels' rows behind bp1 at position 1 and the agc meter (cur / other, as the meter reads them), ahead

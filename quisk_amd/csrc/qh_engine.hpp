@@ -45,6 +45,7 @@
 #include "qh_ssql.hpp"
 #include "qh_fmsq.hpp"
 #include "qh_taps.hpp"
+#include "qh_gen.hpp"
 #pragma clang diagnostic pop
 #include "qh_internal.hpp"
 
@@ -152,6 +153,13 @@ struct ChanCfg {
     // xsender / xsiphon (qh_taps.hpp): both off until enabled -- a tap costs a pass (the reference runs the siphon of every channel,
     // RXA.c:392-401, and the sender of channel 0, RXA.c:131)
     int sender_run = 0, sip_run = 0;
+    // gen0 (qh_gen.hpp) as create_rxa makes it (RXA.c:60-66: run 0, mode 2) with create_gen's defaults (gen.c:113-152); the two-tone and
+    // pulse settings have no RXA setter.  gen_seed_set: qh_rxa_set_gen_seed has replaced the default seed, a fixed function of the channel.
+    int gen_run = 0, gen_mode = 2;
+    double gen_tone_mag = 1.0, gen_tone_freq = 1000.0, gen_noise_mag = 1.0;
+    double gen_sweep_mag = 1.0, gen_sweep_f1 = -20000.0, gen_sweep_f2 = 20000.0, gen_sweep_rate = 4000.0;
+    unsigned long long gen_seed = 0;
+    bool gen_seed_set = false, gen_dirty = true, gen_sweep_dirty = true, gen_tone_reset = false, gen_sweep_reset = false;
     // (the new stages sit behind xwcpagc too, ahead of the panel: a fixed gain that changes while a peak still rings must not reach
     // the ringing tail, so it is applied at the AGC's spot for them as well; SSQL's detector reads amplitude, so it needs the gain too)
     bool fix_before() const
@@ -332,6 +340,19 @@ struct Engine {
     double *tap_gain = nullptr;
     bool taps_listed() const { return tap_lists[0].n || tap_lists[1].n || tap_lists[2].n; }
     int taps_alloc();
+    // gen0 (qh_gen.hpp), made when a channel first runs it: the list of its channels, their parameters and state, the sweep tables
+    // [nch][kGenCkMax] and the pulse's raised-cosine edge [pntrans + 1] (calc_pulse, gen.c:88-95)
+    ChanList gen_list;
+    std::vector<int> gen_h;
+    GenParam *gen_prm = nullptr;
+    GenState *gen_state = nullptr;
+    double2 *gen_ck = nullptr;
+    double *gen_ctrans = nullptr;
+    std::vector<GenParam> gen_prm_h;
+    int gen_pntrans = 0, gen_pnon = 0, gen_pnoff = 0;
+    int gen_alloc();
+    int prm_gen(ChanCfg &c, int ch);
+    int refresh_gen();
     // a display bank fed from the sender rows at the end of every call (qh_rxa_attach_display); disp_fed: recorded on the bank's stream
     // behind its append of the rows, waited for by the engine's stream ahead of the next call's launches
     qh_ana *disp = nullptr;
@@ -510,6 +531,7 @@ struct Engine {
         bool any_nbp = false, any_bp1 = false, any_eqp = false, every_nbp = true, mixed = false, long_mode = false, meters_fused = false, eg_fused = false;
         bool split = false, fm_theta_fused = false, direct = false, am_fused = false, am_lv_fused = false, side = false;
         bool agc_direct = false;                        // set where xwcpagc runs (run_agc)
+        bool gen = false;                               // a channel runs gen0: no two-stream split, the generating launch behind the front stage
         bool taps = false;                              // a channel runs its sender or its siphon: the stores that skip their points are off
     };
     int chain_needs(ChainCall &k);
@@ -536,6 +558,7 @@ struct Engine {
     void run_ssql(const ChainCall &k);
     void run_fmsq(const ChainCall &k);
     void run_sender(const ChainCall &k);
+    void run_gen(const ChainCall &k);
     void run_siphon(const ChainCall &k);
     void run_output(const ChainCall &k);
     qh_rat *rsmpout = nullptr;          // xresample out (wdsp/RXA.c:596), only when out_rate != dsp_rate

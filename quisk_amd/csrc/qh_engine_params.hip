@@ -416,9 +416,11 @@ void Engine::build_lists(std::vector<int> (&h)[L_COUNT])
     ssql_h[0].clear(); ssql_h[1].clear();
     fq_h.clear(); fq_pairs_h.clear();
     for (std::vector<int> &t : tap_h) t.clear();
+    gen_h.clear();
     for (int ch = 0; ch < nch; ch++) {
         const ChanCfg &c = cfg[(size_t)ch];
         if (c.sender_run) tap_h[0].push_back(ch);
+        if (c.gen_run) gen_h.push_back(ch);
         if (c.sip_run) tap_h[c.bp1_run ? 2 : 1].push_back(ch);          // where the agc meter finds the channel (L_PLAIN / L_BP1)
         if (c.amsq_run) h[L_AMSQ].push_back(ch);
         if (c.snba_run) h[L_SNBA].push_back(ch);
@@ -475,6 +477,7 @@ void Engine::build_lists(std::vector<int> (&h)[L_COUNT])
     for (int i = 0; i < L_COUNT; i++) lists[i].n = (int)h[i].size();
     for (int b = 0; b < 2; b++) ssql_lists[b].n = (int)ssql_h[b].size();
     for (int t = 0; t < 3; t++) tap_lists[t].n = (int)tap_h[t].size();
+    gen_list.n = (int)gen_h.size();
     for (size_t i = 0; i < fq_h.size(); i += 2) { fq_pairs_h.push_back(fq_h[i]); fq_pairs_h.push_back(i + 1 < fq_h.size() ? fq_h[i + 1] : fq_h[i]); }
     fq_list.n = (int)fq_h.size(); np_fq = (int)fq_pairs_h.size() / 2;
 }
@@ -504,6 +507,86 @@ int Engine::taps_alloc()
     return QH_OK;
 }
 
+// gen0 (qh_gen.hpp) at the first run of a channel's generator: state as create_gen leaves it (all zero: phases 0, the pulse OFF with
+// pnoff samples to go, gen.c:86-87), every channel's parameters, the pulse's edge table
+int Engine::gen_alloc()
+{
+    const double rate = (double)dsp_rate;
+    if (int rc = quiesce()) return rc;
+    if (int rc = alloc(gen_list.dev, nch)) return rc;
+    if (int rc = alloc(gen_prm, nch, true)) return rc;
+    if (int rc = alloc(gen_state, nch, true)) return rc;
+    if (int rc = alloc(gen_ck, (long long)nch * kGenCkMax, true)) return rc;
+    // calc_pulse (gen.c:73-96) at create_gen's pf 0.25, duty 0.25, 2 ms edges: theta accumulates as there
+    const double pperiod = 1.0 / 0.25;
+    gen_pntrans = (int)(0.002 * rate);
+    gen_pnon = (int)(0.25 * pperiod * rate);
+    gen_pnoff = (int)(pperiod * rate) - gen_pnon - 2 * gen_pntrans;
+    if (gen_pnoff < 0) gen_pnoff = 0;
+    std::vector<double> ct((size_t)gen_pntrans + 1);
+    const double delta = kPiRef / (double)gen_pntrans;
+    double theta = 0.0;
+    for (int i = 0; i <= gen_pntrans; i++) { ct[(size_t)i] = 0.5 * (1.0 - std::cos(theta)); theta += delta; }
+    if (int rc = alloc(gen_ctrans, (long long)ct.size())) return rc;
+    QH_HIP(hipMemcpyAsync(gen_ctrans, ct.data(), ct.size() * sizeof(double), hipMemcpyHostToDevice, stream));
+    QH_HIP(hipStreamSynchronize(stream));
+    gen_prm_h.assign((size_t)nch, GenParam{});
+    for (ChanCfg &c : cfg) {
+        c.gen_dirty = c.gen_sweep_dirty = true;
+        c.gen_tone_reset = c.gen_sweep_reset = false;       // (the state is new)
+    }
+    return QH_OK;
+}
+
+// One channel's gen0 parameters.  The sweep's period and table come from the reference's own chain (sweep_walk), walked when a setter ran
+// calc_sweep; setters that run calc_tone / calc_sweep also zero the phase (and the sweep's position) in stream order.
+int Engine::prm_gen(ChanCfg &c, int ch)
+{
+    const double rate = (double)dsp_rate;
+    GenParam &q = gen_prm_h[(size_t)ch];
+    q.mode = c.gen_mode; q.pntrans = gen_pntrans; q.pnon = gen_pnon; q.pnoff = gen_pnoff;
+    q.tone_mag = c.gen_tone_mag; q.tone_delta = kTwoPiRef * c.gen_tone_freq / rate;
+    q.tt_mag1 = 0.5; q.tt_mag2 = 0.5; q.tt_delta1 = kTwoPiRef * 900.0 / rate; q.tt_delta2 = kTwoPiRef * 1700.0 / rate;      // gen.c:126-129
+    q.noise_mag = c.gen_noise_mag;
+    q.noise_key = gen_mix64((c.gen_seed_set ? c.gen_seed : kGenGolden * (unsigned long long)(ch + 1)) + kGenGolden * (unsigned long long)(ch + 1));
+    q.sweep_mag = c.gen_sweep_mag;
+    q.pulse_mag = 1.0; q.pulse_tdelta = kTwoPiRef * 1000.0 / rate;                                                         // gen.c:145-149
+    if (c.gen_sweep_dirty) {
+        const SweepWalk w = sweep_walk(rate, c.gen_sweep_f1, c.gen_sweep_f2, c.gen_sweep_rate, kGenWalkMax, kGenCkStep);
+        q.sweep_P = w.P; q.sweep_dphs0 = w.dphs0; q.sweep_d2phs = w.d2phs; q.sweep_full = w.full;
+        q.sweep_nck = (int)w.ck.size();
+        if (q.sweep_nck > kGenCkMax) return set_error(QH_ERR_HIP, "gen0: sweep table of %d entries", q.sweep_nck);
+        if (q.sweep_nck) {
+            std::vector<double2> t(w.ck.size());
+            for (size_t i = 0; i < t.size(); i++) t[i] = make_double2(w.ck[i].first, w.ck[i].second);
+            QH_HIP(hipMemcpyAsync(gen_ck + (size_t)ch * kGenCkMax, t.data(), t.size() * sizeof(double2), hipMemcpyHostToDevice, stream));
+            QH_HIP(hipStreamSynchronize(stream));
+        }
+        c.gen_sweep_dirty = false;
+    }
+    if (c.gen_tone_reset) QH_HIP(hipMemsetAsync(&gen_state[ch].tone_phs, 0, sizeof(double), stream));                       // calc_tone, gen.c:31
+    if (c.gen_sweep_reset) QH_HIP(hipMemsetAsync(&gen_state[ch].sweep_phs, 0, sizeof(double) + sizeof(long long), stream)); // calc_sweep, gen.c:51-52
+    c.gen_tone_reset = c.gen_sweep_reset = false;
+    QH_HIP(hipMemcpyAsync(gen_prm + ch, &q, sizeof(q), hipMemcpyHostToDevice, stream));
+    c.gen_dirty = false;
+    return QH_OK;
+}
+
+// what the setters changed since the last call, uploaded ahead of the call's launches
+int Engine::refresh_gen()
+{
+    if (!gen_prm) return QH_OK;
+    bool up = false;
+    for (int ch = 0; ch < nch; ch++) {
+        ChanCfg &c = cfg[(size_t)ch];
+        if (!c.gen_dirty) continue;
+        if (int rc = prm_gen(c, ch)) return rc;
+        up = true;
+    }
+    if (up) QH_HIP(hipStreamSynchronize(stream));
+    return QH_OK;
+}
+
 // The stages made when a channel first runs one of them (the lists' counts say which)
 int Engine::stages_alloc()
 {
@@ -512,6 +595,7 @@ int Engine::stages_alloc()
     if (ssql_listed() && !ssql_prm) if (int rc = ssql_alloc()) return rc;
     if (fq_list.n && !fq_prm) if (int rc = fmsq_alloc()) return rc;
     if (taps_listed()) if (int rc = taps_alloc()) return rc;
+    if (gen_list.n && !gen_prm) if (int rc = gen_alloc()) return rc;
     if ((lists[L_EMNR].n || lists[L_EMNR + 1].n || lists[L_EMNR + 2].n) && !emnr_state) if (int rc = emnr_alloc()) return rc;
     if (lists[L_SNBA].n && !snba_state) if (int rc = snba_alloc()) return rc;
     if (lists[L_AMSQ].n && !amsq_prm) {
@@ -625,6 +709,7 @@ int Engine::refresh_lists()
         for (int t = 0; t < 3; t++) std::copy(tap_h[t].begin(), tap_h[t].end(), tp.begin() + (size_t)nch * t);
         QH_HIP(hipMemcpyAsync(tap_list_block, tp.data(), tp.size() * sizeof(int), hipMemcpyHostToDevice, stream));
     }
+    if (gen_list.dev && gen_list.n) QH_HIP(hipMemcpyAsync(gen_list.dev, gen_h.data(), gen_h.size() * sizeof(int), hipMemcpyHostToDevice, stream));
     std::vector<int> fq;
     if (fq_list_block) {
         fq.assign((size_t)nch * 3, 0);
@@ -1583,6 +1668,8 @@ int Engine::flush()
         QH_HIP(hipMemsetAsync(sip_ring, 0, (size_t)nch * kSipSize * sizeof(double2), stream));
         QH_HIP(hipMemsetAsync(sip_idx, 0, (size_t)nch * sizeof(int), stream));
     }
+    if (gen_state)                              // flush_gen, RXA.c:534 (gen.c:160-163): the pulse's state machine alone
+        hipLaunchKernelGGL(gen_flush_kernel, dim3((unsigned)((nch + 255) / 256)), dim3(256), 0, stream, nch, (const GenParam *)gen_prm, gen_state);
     if (fq_state) {                             // flush_fmsq, RXA.c:544
         for (int i = 0; i < 2; i++) QH_HIP(hipMemsetAsync(hist_fq[i], 0, (size_t)nch * kHistBand * sizeof(double2), stream));
         launch_fmsq_flush();

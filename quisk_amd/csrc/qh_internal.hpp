@@ -69,4 +69,8 @@ int nob_check_settings(double samplerate, int mode, double slewtime, double hang
 qh_ana *wdsp_display_hold(int disp);
 void wdsp_display_release();
 
+// gen0 set to a mode the engine refuses (4, 5) on a channel whose generator runs: the error the next process call would return, ahead
+// of it -- fexchange0 asks before it takes the caller's samples, so that a refused call leaves its rings and the output buffer alone
+int rxa_gen_check(qh_rxa *h);
+
 }  // namespace qh

@@ -867,6 +867,29 @@ int qh_rxa_attach_display(qh_rxa *h, qh_ana *a, int ss)
     return QH_OK;
 }
 
+// ---- gen0 (qh_gen.hpp): the SetRXAPreGen* setters of wdsp/gen.c:384-450 on (engine, channel), ch -1 = every channel -------------------
+int qh_rxa_SetRXAPreGenRun(qh_rxa *h, int ch, int run)
+{
+    FOR_CH(h, ch, { run = run ? 1 : 0; if (c.gen_run != run) { c.gen_run = run; h->e.lists_dirty = true; } });
+}
+int qh_rxa_SetRXAPreGenMode(qh_rxa *h, int ch, int mode) { FOR_CH(h, ch, { c.gen_mode = mode; c.gen_dirty = true; }); }
+int qh_rxa_SetRXAPreGenToneMag(qh_rxa *h, int ch, double mag) { FOR_CH(h, ch, { c.gen_tone_mag = mag; c.gen_dirty = true; }); }
+// (calc_tone: the phase goes to 0, gen.c:31)
+int qh_rxa_SetRXAPreGenToneFreq(qh_rxa *h, int ch, double freq) { FOR_CH(h, ch, { c.gen_tone_freq = freq; c.gen_tone_reset = true; c.gen_dirty = true; }); }
+int qh_rxa_SetRXAPreGenNoiseMag(qh_rxa *h, int ch, double mag) { FOR_CH(h, ch, { c.gen_noise_mag = mag; c.gen_dirty = true; }); }
+int qh_rxa_SetRXAPreGenSweepMag(qh_rxa *h, int ch, double mag) { FOR_CH(h, ch, { c.gen_sweep_mag = mag; c.gen_dirty = true; }); }
+// (calc_sweep: the phase goes to 0 and dphs back to its start, gen.c:51-52)
+int qh_rxa_SetRXAPreGenSweepFreq(qh_rxa *h, int ch, double freq1, double freq2)
+{
+    FOR_CH(h, ch, { c.gen_sweep_f1 = freq1; c.gen_sweep_f2 = freq2; c.gen_sweep_dirty = c.gen_sweep_reset = true; c.gen_dirty = true; });
+}
+int qh_rxa_SetRXAPreGenSweepRate(qh_rxa *h, int ch, double rate)
+{
+    FOR_CH(h, ch, { c.gen_sweep_rate = rate; c.gen_sweep_dirty = c.gen_sweep_reset = true; c.gen_dirty = true; });
+}
+// The seed of the channel's noise stream (the default is a fixed function of the channel); the stream goes on from the sample it has reached
+int qh_rxa_set_gen_seed(qh_rxa *h, int ch, unsigned long long seed) { FOR_CH(h, ch, { c.gen_seed = seed; c.gen_seed_set = true; c.gen_dirty = true; }); }
+
 // Meters (wdsp/meter.c): enable != 0 makes later process calls maintain the ADC, S and AGC meters.
 int qh_rxa_enable_meters(qh_rxa *h, int enable)
 {
@@ -1103,3 +1126,15 @@ int qh_rxa_timing(qh_rxa *h, double *ms, int n)
 }
 
 }  // extern "C"
+
+namespace qh {
+int rxa_gen_check(qh_rxa *h)
+{
+    if (!h) return QH_OK;
+    QH_RXA_LOCK(h);
+    for (const ChanCfg &c : h->e.cfg)
+        if (c.gen_run && (c.gen_mode == 4 || c.gen_mode == 5))
+            return set_error(QH_ERR_UNSUPPORTED, "channel %d: gen0 mode %d (%s) is not provided", (int)(&c - h->e.cfg.data()), c.gen_mode, c.gen_mode == 4 ? "sawtooth" : "triangle");
+    return QH_OK;
+}
+}  // namespace qh

@@ -466,6 +466,7 @@ void fexchange0(int channel, double *in, double *out, int *error)
     Chan &c = *L.c;
     if (!c.exchange) return;                        // wdsp/iobuffs.c:471: `out` is left untouched
     if (int rc = set_mode(c, false)) { g_status = rc; *error = -1; return; }
+    if (int rc = qh::rxa_gen_check(c.eng)) { g_status = rc; *error = -1; return; }      // SetRXAPreGenMode 4 / 5: refused, `out` left alone
     std::memcpy(c.r1.data() + 2 * c.r1_inidx, in, (size_t)c.in_size * 2 * sizeof(double));
     if (c.up.armed) {
         // iobuffs.c:98-160 as bookkeeping: the envelope is triggered by the first non-zero sample; the flag drops at the end of
@@ -808,6 +809,16 @@ void SetRXAAMDFadeLevel(int channel, int levelfade) { WDSP_SETTER(qh_rxa_SetRXAA
 void SetRXAFMDeviation(int channel, double deviation) { WDSP_SETTER(qh_rxa_SetRXAFMDeviation(L.c->eng, 0, deviation)); }
 void SetRXACTCSSFreq(int channel, double freq) { WDSP_SETTER(qh_rxa_SetRXACTCSSFreq(L.c->eng, 0, freq)); }
 void SetRXACTCSSRun(int channel, int run) { WDSP_SETTER(qh_rxa_SetRXACTCSSRun(L.c->eng, 0, run)); }
+
+// gen0 (wdsp/gen.c:384-450)
+void SetRXAPreGenRun(int channel, int run) { WDSP_SETTER(qh_rxa_SetRXAPreGenRun(L.c->eng, 0, run)); }
+void SetRXAPreGenMode(int channel, int mode) { WDSP_SETTER(qh_rxa_SetRXAPreGenMode(L.c->eng, 0, mode)); }
+void SetRXAPreGenToneMag(int channel, double mag) { WDSP_SETTER(qh_rxa_SetRXAPreGenToneMag(L.c->eng, 0, mag)); }
+void SetRXAPreGenToneFreq(int channel, double freq) { WDSP_SETTER(qh_rxa_SetRXAPreGenToneFreq(L.c->eng, 0, freq)); }
+void SetRXAPreGenNoiseMag(int channel, double mag) { WDSP_SETTER(qh_rxa_SetRXAPreGenNoiseMag(L.c->eng, 0, mag)); }
+void SetRXAPreGenSweepMag(int channel, double mag) { WDSP_SETTER(qh_rxa_SetRXAPreGenSweepMag(L.c->eng, 0, mag)); }
+void SetRXAPreGenSweepFreq(int channel, double freq1, double freq2) { WDSP_SETTER(qh_rxa_SetRXAPreGenSweepFreq(L.c->eng, 0, freq1, freq2)); }
+void SetRXAPreGenSweepRate(int channel, double rate) { WDSP_SETTER(qh_rxa_SetRXAPreGenSweepRate(L.c->eng, 0, rate)); }
 
 void SetRXASpectrum(int channel, int flag, int disp, int ss, int LO)
 {

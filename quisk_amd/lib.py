@@ -140,6 +140,18 @@ def load():
     L.RXAGetaSipF.restype = None
     L.RXAGetaSipF1.argtypes = [i, vp, i]
     L.RXAGetaSipF1.restype = None
+    for n in ("Run", "Mode"):
+        getattr(L, "qh_rxa_SetRXAPreGen" + n).argtypes = [vp, i, i]
+        getattr(L, "SetRXAPreGen" + n).argtypes = [i, i]
+        getattr(L, "SetRXAPreGen" + n).restype = None
+    for n in ("ToneMag", "ToneFreq", "NoiseMag", "SweepMag", "SweepRate"):
+        getattr(L, "qh_rxa_SetRXAPreGen" + n).argtypes = [vp, i, d]
+        getattr(L, "SetRXAPreGen" + n).argtypes = [i, d]
+        getattr(L, "SetRXAPreGen" + n).restype = None
+    L.qh_rxa_SetRXAPreGenSweepFreq.argtypes = [vp, i, d, d]
+    L.SetRXAPreGenSweepFreq.argtypes = [i, d, d]
+    L.SetRXAPreGenSweepFreq.restype = None
+    L.qh_rxa_set_gen_seed.argtypes = [vp, i, C.c_ulonglong]
     L.qh_rxa_flush.argtypes = [vp]
     L.qh_rxa_flush.restype = i
     L.qh_rxa_enable_timing.argtypes = [vp, i]

@@ -185,6 +185,37 @@ class RxaEngine:
         check(self._L.qh_rxa_attach_display(self._h, bank._h if bank is not None else None, ss))
         self._display = bank
 
+    # gen0, the signal generator at the head of the chain (wdsp/gen.c:384-450): ch -1 = every channel
+    def SetRXAPreGenRun(self, ch, run):
+        """a running generator replaces the channel's signal behind the front stage (RXA.c:565)"""
+        check(self._L.qh_rxa_SetRXAPreGenRun(self._h, ch, 1 if run else 0))
+
+    def SetRXAPreGenMode(self, ch, mode):
+        """0 tone, 1 two-tone, 2 noise, 3 sweep, 6 pulse, any other silence; 4 and 5 are refused at the next call"""
+        check(self._L.qh_rxa_SetRXAPreGenMode(self._h, ch, int(mode)))
+
+    def SetRXAPreGenToneMag(self, ch, mag):
+        check(self._L.qh_rxa_SetRXAPreGenToneMag(self._h, ch, float(mag)))
+
+    def SetRXAPreGenToneFreq(self, ch, freq):
+        check(self._L.qh_rxa_SetRXAPreGenToneFreq(self._h, ch, float(freq)))
+
+    def SetRXAPreGenNoiseMag(self, ch, mag):
+        check(self._L.qh_rxa_SetRXAPreGenNoiseMag(self._h, ch, float(mag)))
+
+    def SetRXAPreGenSweepMag(self, ch, mag):
+        check(self._L.qh_rxa_SetRXAPreGenSweepMag(self._h, ch, float(mag)))
+
+    def SetRXAPreGenSweepFreq(self, ch, freq1, freq2):
+        check(self._L.qh_rxa_SetRXAPreGenSweepFreq(self._h, ch, float(freq1), float(freq2)))
+
+    def SetRXAPreGenSweepRate(self, ch, rate):
+        check(self._L.qh_rxa_SetRXAPreGenSweepRate(self._h, ch, float(rate)))
+
+    def set_gen_seed(self, ch, seed):
+        """the seed of the channel's noise stream (the default is a fixed function of the channel)"""
+        check(self._L.qh_rxa_set_gen_seed(self._h, ch, int(seed) & 0xFFFFFFFFFFFFFFFF))
+
     def pll_repairs(self):
         return self._L.qh_rxa_pll_repairs(self._h)
 
