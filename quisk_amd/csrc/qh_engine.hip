@@ -275,19 +275,21 @@ static __global__ __launch_bounds__(NT) void long_migrate_kernel(double2 *hist, 
     }
 }
 
-// one fircore stage (overlap-save, D = 1) over all channels (list == nullptr) or a sub-set
+// one fircore stage (overlap-save, D = 1) over all channels (list == nullptr) or a sub-set: from the half f.cur of its delay lines to
+// the other one.  The caller flips the pair (f.flip()) once it has run the stage over every list of the call.
 void Engine::run_band(const double2 *src, long long src_stride, double2 *dst, long long dst_stride, const EpiParam *ep,
-                      long long n_mid, const double2 *mask, long long mask_stride, double2 **hist, int &hc, int P,
+                      long long n_mid, Fircore &f, int P,
                       const int *list, int nlist, bool meter, bool egress, int det, double *det_out, long long det_stride,
                       const int *pairs, int npairs)
 {
-    const int sid = hist == hist_nbp ? 0 : hist == hist_bp1 ? 1 : hist == hist_de ? 2 : hist == hist_aud ? 3 : (hist == hist_fq || hist == hist_eqp) ? 5 : 4;    // (5, xfmsq's noise filter and xeqp: never partitioned)
-    if (sid < 5 && long_parts[sid] > 1) {
+    const int hc = f.cur;
+    double2 *const *hist = f.hist;
+    if (f.parts > 1) {
         // nc > 4096: y = sum_p h_p * (x delayed by 4096 p).  lcat holds the stage's last 16383 samples and the block in one row per
         // channel, so partition p is the ordinary tile pass (4096 taps, 8192 points, 4097 outputs per tile) over a row that begins
         // 4096 p samples further back; the partitions' outputs are added, the epilogue follows as a pass of its own.  (The callers
         // switch every fusion off for such a call: no meters, audio frames or detector steps in this stage's stores.)
-        const int K = long_parts[sid], Pk = kLongPart - 1, Lk = kBandNfftMax - Pk, nt = (int)((n_mid + Lk - 1) / Lk);
+        const int K = f.parts, Pk = kLongPart - 1, Lk = kBandNfftMax - Pk, nt = (int)((n_mid + Lk - 1) / Lk);
         const int nl = list ? nlist : nch;
         const long long cat_stride = kLongHist + lcat_cap;
         // what the K partitions look back over.  A channel's own nc may be shorter: the partitions past its own impulse response are not
@@ -298,14 +300,14 @@ void Engine::run_band(const double2 *src, long long src_stride, double2 *dst, lo
         const int lh = K * kLongPart - 1;
         const long long per = (lh + n_mid + NT - 1) / NT;
         tick(1);
-        hipLaunchKernelGGL(long_gather_kernel, dim3((unsigned)(per < 2048 ? per : 2048), (unsigned)nl), dim3(NT), 0, stream, (const double2 *)lhist[sid][hc], src,
+        hipLaunchKernelGGL(long_gather_kernel, dim3((unsigned)(per < 2048 ? per : 2048), (unsigned)nl), dim3(NT), 0, stream, (const double2 *)f.lhist[hc], src,
                            src_stride, (int)n_mid, lcat, cat_stride, list, lh);
         for (int p = 0; p < K; p++) {
             OsfirArgs<double> a{};
             a.in = lcat + kLongHist - (long long)kLongPart * p; a.in_stride = cat_stride;
             a.hist = a.in - Pk; a.hist_stride = cat_stride; a.hist_len = Pk;
             a.out = p ? ltmp : dst; a.out_stride = p ? lcat_cap : dst_stride; a.out_offset = 0;
-            a.mask = lmask[sid] + (size_t)p * kBandNfftMax; a.mask_stride = mask_stride ? (long long)kLongParts * kBandNfftMax : 0;
+            a.mask = f.lmask + (size_t)p * kBandNfftMax; a.mask_stride = f.mask_stride ? (long long)kLongParts * kBandNfftMax : 0;
             a.tw_fwd = a.tw_inv = tw8192;
             a.tw_r2 = tw8192 + 32;
             a.chan_list = list;
@@ -313,15 +315,14 @@ void Engine::run_band(const double2 *src, long long src_stride, double2 *dst, lo
             launch_band<kBandNfftMax>(a, nt, nl, stream, false, false);
             const long long pn = (n_mid + NT - 1) / NT;
             if (p) hipLaunchKernelGGL(long_add_kernel, dim3((unsigned)(pn < 1024 ? pn : 1024), (unsigned)nl), dim3(NT), 0, stream, dst, dst_stride,
-                                      (const double2 *)ltmp, lcat_cap, (int)n_mid, list, (const int *)lrow_parts[sid], mask_stride ? 1 : 0, p);
+                                      (const double2 *)ltmp, lcat_cap, (int)n_mid, list, (const int *)f.lrow_parts, f.mask_stride ? 1 : 0, p);
         }
         const long long pn = (n_mid + NT - 1) / NT;
         if (ep) hipLaunchKernelGGL((pointwise_kernel<double, false>), dim3((unsigned)(pn < 1024 ? pn : 1024), (unsigned)nl), dim3(NT), 0, stream,
                                    (const double2 *)dst, dst_stride, dst, dst_stride, (int)n_mid, (const unsigned long long *)nullptr,
                                    (const unsigned long long *)nullptr, ep, list);
         tick(2);
-        hipLaunchKernelGGL(long_hist_kernel, dim3(64, (unsigned)nl), dim3(NT), 0, stream, (const double2 *)lcat, cat_stride, (int)n_mid, lhist[sid][hc ^ 1], list, lh);
-        hc ^= 1;
+        hipLaunchKernelGGL(long_hist_kernel, dim3(64, (unsigned)nl), dim3(NT), 0, stream, (const double2 *)lcat, cat_stride, (int)n_mid, f.lhist[hc ^ 1], list, lh);
         return;
     }
     const int Lout = bnfft - P;
@@ -330,7 +331,7 @@ void Engine::run_band(const double2 *src, long long src_stride, double2 *dst, lo
     a.in = src; a.in_stride = src_stride;
     a.hist = hist[hc]; a.hist_stride = kHistBand; a.hist_len = kHistBand;
     a.out = dst; a.out_stride = dst_stride; a.out_offset = 0;
-    a.mask = mask; a.mask_stride = mask_stride;
+    a.mask = f.mask; a.mask_stride = f.mask_stride;
     a.tw_fwd = a.tw_inv = (bnfft == kNfft || band2g) ? tw4096 : tw8192;
     a.tw_r2 = tw8192 + 32;                  // second pass table of the 8192-point plan: exp(-2 pi i k / 8192), k < 256 (qh_design.cpp)
     a.epi = ep;
@@ -386,7 +387,6 @@ void Engine::run_band(const double2 *src, long long src_stride, double2 *dst, lo
                            hist[hc], hist[hc ^ 1], kHistBand, (const unsigned long long *)nullptr,
                            (const unsigned long long *)nullptr, list);
     // (a listed stage reads and writes the history rows of its own channels only)
-    hc ^= 1;
 }
 
 // xrxa's last step (wdsp/RXA.c:596): rsmpout runs when out_rate != dsp_rate (RXAResCheck, RXA.c:789-798)
@@ -489,43 +489,42 @@ int Engine::chain_needs(ChainCall &k)
 int Engine::plan_long(ChainCall &k)
 {
     auto parts = [](int nc) { return nc > kLongPart ? (nc + kLongPart - 1) / kLongPart : 1; };
-    int lp[5] = { 1, 1, 1, 1, 1 };
+    int lp[FC_COUNT];
+    for (int &v : lp) v = 1;
     // Over every channel that runs the stage OR still holds a long delay line of it: a fircore keeps its delay line while it does not run (xbandpass / xnbp with run = 0
     // only copy; SetRXABandpassRun, a mode change back to AM / FM, RXANBPSetRun switch it on again without a flush), so a channel with
     // nc > 4096 that sits out holds 16383 samples the one-tile form has no room for.  Had the form followed the RUNNING channels,
     // the only long channel leaving took the stage to the short form (its line cut to 4095 samples) and came back to zeros behind
     // them: one long call 0.65 off (walk rxa_long 900190, found by round 6's seed sweep; in the suite since).
     // (long_live: the channel has run the stage with such an nc since RXASetNC last zeroed its lines.)
-    for (ChanCfg &c : cfg) {
-        const int pn = parts(c.nbp_nc), pb = parts(c.bp1_nc), pf = parts(c.fm_nc);
-        if (c.nbp_run && pn > 1) c.long_live[0] = true;
-        if (c.bp1_run && pb > 1) c.long_live[1] = true;
-        if (c.fmd_run && pf > 1) c.long_live[2] = true;
-        if (c.snba_run && pn > 1) c.long_live[4] = true;
-        if (c.nbp_run || c.long_live[0]) lp[0] = std::max(lp[0], pn);
-        if (c.bp1_run || c.long_live[1]) lp[1] = std::max(lp[1], pb);
-        if (c.fmd_run || c.long_live[2]) lp[2] = lp[3] = std::max(lp[2], pf);
-        if (c.snba_run || c.long_live[4]) lp[4] = std::max(lp[4], pn);
+    // The FM pair takes its count from fm_nc together, bpsnba follows nbp0's nc (its nbp shares it, refresh_params).
+    for (int ch = 0; ch < nch; ch++) {
+        const ChanCfg &c = cfg[(size_t)ch];
+        const int run[FC_COUNT] = { c.nbp_run, c.bp1_run, c.fmd_run, c.fmd_run, c.snba_run, 0, 0 };
+        const int nc[FC_COUNT] = { c.nbp_nc, c.bp1_nc, c.fm_nc, c.fm_nc, c.nbp_nc, 0, 0 };
+        for (int s = 0; s < FC_COUNT; s++) {
+            if (!fc[s].can_long) continue;
+            Fircore::Chan &r = fc[s].chan[(size_t)ch];
+            if (run[s] && parts(nc[s]) > 1) r.long_live = true;
+            if (run[s] || r.long_live) lp[s] = std::max(lp[s], parts(nc[s]));
+        }
     }
-    for (int sid = 0; sid < 5; sid++) {
-        if (lp[sid] > 1) { k.long_mode = true; if (int rc = long_stage_alloc(sid, sid == 2 || sid == 3)) return rc; }
-        if (lp[sid] == long_parts[sid]) continue;
+    for (int s = 0; s < FC_COUNT; s++) {
+        Fircore &f = fc[s];
+        if (lp[s] > 1) { k.long_mode = true; if (int rc = long_stage_alloc(f)) return rc; }
+        if (lp[s] == f.parts) continue;
         if (int rc = quiesce()) return rc;
-        if ((lp[sid] > 1) != (long_parts[sid] > 1)) {       // the delay lines move with the form
-            double2 **hs = sid == 0 ? hist_nbp : sid == 1 ? hist_bp1 : sid == 2 ? hist_de : sid == 3 ? hist_aud : hist_snb;
+        if ((lp[s] > 1) != (f.parts > 1)) {       // the delay lines move with the form
             // BOTH ping-pong halves: a channel that has left the stage's list (another mode, bp1 or SNBA switched off) keeps its rows in
-            // the half that was current when it left (bp1_hist_at, fm_hist_at, snb_hist_at), which need not be the current one
+            // the half that was current when it left (Fircore::Chan::at), which need not be the current one
             for (int half = 0; half < 2; half++)
-                if (hs[half] && lhist[sid][half])
-                    hipLaunchKernelGGL(long_migrate_kernel, dim3(16, (unsigned)nch), dim3(NT), 0, stream, hs[half], lhist[sid][half], lp[sid] > 1 ? 1 : 0);
+                if (f.hist[half] && f.lhist[half])
+                    hipLaunchKernelGGL(long_migrate_kernel, dim3(16, (unsigned)nch), dim3(NT), 0, stream, f.hist[half], f.lhist[half], lp[s] > 1 ? 1 : 0);
         }
-        long_parts[sid] = lp[sid];
-        for (ChanCfg &c : cfg) {            // the stage's masks are laid out for another form now: all of them again
-            if (sid == 0) c.nbp_dirty = true;
-            if (sid == 1) c.bp1_dirty = true;
-            if (sid == 4) c.snb_dirty = true;
-        }
-        if (sid == 2 || sid == 3) fm_nc_built = 0;
+        f.parts = lp[s];
+        // the stage's masks are laid out for another form now: all of them again
+        if (f.dirty) for (ChanCfg &c : cfg) c.*f.dirty = true;
+        else fm_nc_built = 0;       // (the FM pair's shared designs)
     }
     return QH_OK;
 }
@@ -565,13 +564,13 @@ int Engine::process_chain(const double *d_in, long long in_stride, double *d_out
     if (k.mixed) if (int rc = refresh_demod()) return rc;
     if (k.gen) if (int rc = refresh_gen()) return rc;
     // bp1 on the linear path (SetRXABandpassRun on an all-SSB engine): run_linear flips bp1's ping-pong pair like the per-mode path, but
-    // refresh_lists, which keeps bp1_listed / bp1_hist_at, runs from refresh_demod only.  Left alone, the first per-mode call found no
-    // channel listed and bp1_hist_at still at the half of the engine's first call, and after an odd number of linear calls copied that
+    // refresh_lists, which tells bp1's record who runs it, is a step of refresh_demod only.  Left alone, the first per-mode call found no
+    // channel listed and every line still at the half of the engine's first call, and after an odd number of linear calls copied that
     // stale half over the channel's current delay line (test_gpu_rxa_stage_combinations.py: `fmsq beside bp1`).
     if (!k.mixed && k.any_bp1) {
         std::vector<int> run;
         for (int ch = 0; ch < nch; ch++) if (cfg[(size_t)ch].bp1_run) run.push_back(ch);
-        if (int rc = follow_rows(bp1_listed, &ChanCfg::bp1_hist_at, cur_bp1, run, { { hist_bp1, cur_bp1, kHistBand }, { lhist[1], cur_bp1, kLongHist } })) return rc;
+        if (int rc = fc_follow(fc[FC_BP1], run)) return rc;
     }
     if (lists[L_SNBA].n) if (int rc = refresh_params()) return rc;       // bpsnba's mask needs the buffers the line above may just have made
     if (k.any_eqp || eq_lists_dirty) if (int rc = refresh_eqp()) return rc;
@@ -609,7 +608,7 @@ int Engine::process_chain(const double *d_in, long long in_stride, double *d_out
     if (lists[L_FM].n) if (int rc = run_fm(k)) return rc;    // xfmd
     if (k.side) QH_HIP(hipStreamWaitEvent(stream, ev_join, 0));
     if (lists[L_SNB + 1].n) snb_inplace(k, lists[L_SNB + 1].dev, lists[L_SNB + 1].n);       // xbpsnbain / xbpsnbaout at position 1 (RXA.c:576-577)
-    if (lists[L_SNB].n || lists[L_SNB + 1].n) cur_snb ^= 1;
+    if (lists[L_SNB].n || lists[L_SNB + 1].n) fc[FC_SNB].flip();     // both positions' launches read the one half
     if (int rc = run_snba(k)) return rc;            // xsnba, RXA.c:578
     eqp_inplace(k);                                 // xeqp, RXA.c:579
     // xanf, xanr, xbandpass(bp1) at position 0, xwcpagc, then the same three at position 1 (RXA.c:579-586).  The two bp1
@@ -660,8 +659,8 @@ int Engine::run_linear(ChainCall &k)
             // the equalizer's channels through their tiles, each with its own mask and delay line; a channel that does not run it is
             // passed on as it is (xeqp with run 0 copies, eq.c:206-207, and its fircore's delay line stays as it was)
             const bool last = stage == nstage - 1;
-            run_band(cur, cur_stride, dst, dst_stride, last ? epi : nullptr, n_mid, mask_eqp, kBandNfftMax, hist_eqp, cur_eqp, k.P, eq_list.dev, eq_list.n,
-                     false, k.eg_fused && last);
+            run_band(cur, cur_stride, dst, dst_stride, last ? epi : nullptr, n_mid, fc[FC_EQP], k.P, eq_list.dev, eq_list.n, false, k.eg_fused && last);
+            fc[FC_EQP].flip();
             if (eq_rest.n) {
                 const long long per = (n_mid + NT - 1) / NT;
                 const dim3 g((unsigned)(per < 1024 ? per : 1024), (unsigned)eq_rest.n);
@@ -676,9 +675,9 @@ int Engine::run_linear(ChainCall &k)
             continue;
         }
         if (k.meters_fused) if (int rc = ensure_meter_partials(n_mid, bnfft - k.P)) return rc;
-        run_band(cur, cur_stride, dst, dst_stride, stage == nstage - 1 ? epi : nullptr, n_mid,
-                 f == 0 ? mask_nbp : mask_bp1, kBandNfftMax, f == 0 ? hist_nbp : hist_bp1, f == 0 ? cur_nbp : cur_bp1, k.P,
-                 nullptr, 0, k.meters_fused, k.eg_fused && stage == nstage - 1);
+        Fircore &band = fc[f == 0 ? FC_NBP : FC_BP1];
+        run_band(cur, cur_stride, dst, dst_stride, stage == nstage - 1 ? epi : nullptr, n_mid, band, k.P, nullptr, 0, k.meters_fused, k.eg_fused && stage == nstage - 1);
+        band.flip();
         cur = dst; cur_stride = dst_stride; stage++;
     }
     if (k.meters_fused)
@@ -721,7 +720,7 @@ int Engine::plan_mixed(ChainCall &k)
     k.am_fused = k.direct && !(dbg_forms & 4) && lists[L_AM].n > 0 && lists[L_RB].n == lists[L_AM].n + lists[L_SAM].n && !band6k && !band2g && bnfft == kNfft && k.P_am < bnfft;
     // ... or, when the tiles are 2048 outputs behind 2048 samples of pre-roll and bp1 takes its channels two a tile, no pass at all: the
     // leveller's local share in nbp0's store (DET 3), the carried share in bp1's load
-    k.am_lv_fused = k.am_fused && k.P_am == 2048 && bnfft - k.P_am == 2048 && np_am > 0 && lists[L_BP1P].n && long_parts[1] <= 1 && !(dbg_forms & (16 | 512));
+    k.am_lv_fused = k.am_fused && k.P_am == 2048 && bnfft - k.P_am == 2048 && np_am > 0 && lists[L_BP1P].n && fc[FC_BP1].parts <= 1 && !(dbg_forms & (16 | 512));
     // The AM / SAM detectors and the FM detector chain touch disjoint channel rows and disjoint state, and neither fills the
     // chip (one workgroup or wavefront per channel): with both kinds of channel in the call the AM side runs on a second
     // stream, forked and joined by events (which a launch-sequence capture records as graph edges).
@@ -771,29 +770,27 @@ int Engine::run_mixed_front(ChainCall &k)
         if (fork_at == 0) if (int rc = fork_side()) return rc;
         if (int rc = run_front(k.in, k.in_stride, cur, buf_cap, nullptr, n_in, n_mid, lists[L_FM].dev, lists[L_FM].n, 2)) return rc;
         if (fork_at == 1) if (int rc = fork_side()) return rc;
-        int hc = cur_nbp;
+        // nbp0 over the lists of the two streams, each on its own channels' rows of the one half: the pair flips once, below
+        Fircore &nbp = fc[FC_NBP];
         // the FM channels' nbp0 feeds the loop's phase detector and nothing else: its store takes the angles (first half of the rows)
-        if (k.any_nbp) run_band(cur, buf_cap, other, buf_cap, nullptr, n_mid, mask_nbp, kBandNfftMax, hist_nbp, hc, P, lists[L_FM].dev, lists[L_FM].n, false, false,
+        if (k.any_nbp) run_band(cur, buf_cap, other, buf_cap, nullptr, n_mid, nbp, P, lists[L_FM].dev, lists[L_FM].n, false, false,
                                 k.fm_theta_fused ? 1 : 0, reinterpret_cast<double *>(other), 2 * buf_cap);
         if (fork_at >= 2) if (int rc = fork_side()) return rc;
         std::swap(stream, side_stream);
         int rc2 = run_front(k.in, k.in_stride, cur, buf_cap, nullptr, n_in, n_mid, lists[L_REST].dev, lists[L_REST].n, 2);
-        hc = cur_nbp;
         if (!rc2 && k.any_nbp) {
             if (k.direct) {     // the plain channels end here: output matrix in the store, straight to the caller's buffer
-                if (lists[L_USB].n) run_band(cur, buf_cap, k.out, k.out_stride, epi, n_mid, mask_nbp, kBandNfftMax, hist_nbp, hc, P, lists[L_USB].dev, lists[L_USB].n);
-                hc = cur_nbp;
+                if (lists[L_USB].n) run_band(cur, buf_cap, k.out, k.out_stride, epi, n_mid, nbp, P, lists[L_USB].dev, lists[L_USB].n);
                 if (k.am_fused) {
-                    if (lists[L_SAM].n) run_band(cur, buf_cap, other, buf_cap, nullptr, n_mid, mask_nbp, kBandNfftMax, hist_nbp, hc, P, lists[L_SAM].dev, lists[L_SAM].n);
-                    hc = cur_nbp;
-                    run_band(cur, buf_cap, other, buf_cap, nullptr, n_mid, mask_nbp, kBandNfftMax, hist_nbp, hc, k.P_am, lists[L_AM].dev, lists[L_AM].n, false, false,
+                    if (lists[L_SAM].n) run_band(cur, buf_cap, other, buf_cap, nullptr, n_mid, nbp, P, lists[L_SAM].dev, lists[L_SAM].n);
+                    run_band(cur, buf_cap, other, buf_cap, nullptr, n_mid, nbp, k.P_am, lists[L_AM].dev, lists[L_AM].n, false, false,
                              k.am_lv_fused ? 3 : 2, reinterpret_cast<double *>(other), 2 * buf_cap);
-                } else if (lists[L_RB].n) run_band(cur, buf_cap, other, buf_cap, nullptr, n_mid, mask_nbp, kBandNfftMax, hist_nbp, hc, P, lists[L_RB].dev, lists[L_RB].n);
-            } else run_band(cur, buf_cap, other, buf_cap, nullptr, n_mid, mask_nbp, kBandNfftMax, hist_nbp, hc, P, lists[L_REST].dev, lists[L_REST].n);
+                } else if (lists[L_RB].n) run_band(cur, buf_cap, other, buf_cap, nullptr, n_mid, nbp, P, lists[L_RB].dev, lists[L_RB].n);
+            } else run_band(cur, buf_cap, other, buf_cap, nullptr, n_mid, nbp, P, lists[L_REST].dev, lists[L_REST].n);
         }
         std::swap(stream, side_stream);
         if (rc2) return rc2;
-        if (k.any_nbp) { cur_nbp ^= 1; std::swap(cur, other); }
+        if (k.any_nbp) { nbp.flip(); std::swap(cur, other); }
         if (int rc = run_front(k.in, k.in_stride, cur, buf_cap, nullptr, n_in, n_mid, nullptr, 0, 3)) return rc;          // histories, oscillator phases
     } else {
         if (int rc = run_front(k.in, k.in_stride, cur, buf_cap, nullptr, n_in, n_mid)) return rc;
@@ -801,7 +798,8 @@ int Engine::run_mixed_front(ChainCall &k)
         if (meters_on) hipLaunchKernelGGL(meter_kernel, dim3((unsigned)nch), dim3(64), 0, stream, cur, buf_cap, k.nblk, dsp_size, m_adc,
                                           m_prm, (const int *)nullptr);
         if (k.any_nbp) {
-            run_band(cur, buf_cap, other, buf_cap, nullptr, n_mid, mask_nbp, kBandNfftMax, hist_nbp, cur_nbp, P, nullptr, 0);
+            run_band(cur, buf_cap, other, buf_cap, nullptr, n_mid, fc[FC_NBP], P, nullptr, 0);
+            fc[FC_NBP].flip();
             std::swap(cur, other);
         }
     }
@@ -816,18 +814,17 @@ int Engine::run_mixed_front(ChainCall &k)
     }
     // xbpsnbaout at position 0 (RXA.c:572): the 250..5700 Hz filter of the signal ahead of nbp0 replaces nbp0's output
     if (lists[L_SNB].n) {
-        if (k.any_nbp) { int hc = cur_snb; run_band(other, buf_cap, cur, buf_cap, nullptr, n_mid, mask_snb, kBandNfftMax, hist_snb, hc, P, lists[L_SNB].dev, lists[L_SNB].n); }
+        if (k.any_nbp) run_band(other, buf_cap, cur, buf_cap, nullptr, n_mid, fc[FC_SNB], P, lists[L_SNB].dev, lists[L_SNB].n);
         else snb_inplace(k, lists[L_SNB].dev, lists[L_SNB].n);
     }
     tick(1);
     return QH_OK;
 }
 
-// bpsnba on the listed channels' rows of cur, through the rows of other
+// bpsnba on the listed channels' rows of cur, through the rows of other (process_chain flips the stage's pair behind position 1)
 void Engine::snb_inplace(const ChainCall &k, const int *list, int n)
 {
-    int hc = cur_snb;
-    run_band(k.cur, buf_cap, k.other, buf_cap, nullptr, k.n_mid, mask_snb, kBandNfftMax, hist_snb, hc, k.P, list, n);
+    run_band(k.cur, buf_cap, k.other, buf_cap, nullptr, k.n_mid, fc[FC_SNB], k.P, list, n);
     long long per = (k.n_mid + NT - 1) / NT;
     hipLaunchKernelGGL(copy_rows_kernel, dim3((unsigned)(per < 1024 ? per : 1024), (unsigned)n), dim3(NT), 0, stream, k.other, k.cur, buf_cap,
                        (int)k.n_mid, list);
@@ -838,7 +835,8 @@ void Engine::snb_inplace(const ChainCall &k, const int *list, int n)
 void Engine::eqp_inplace(const ChainCall &k)
 {
     if (!eq_list.n) return;
-    run_band(k.cur, buf_cap, k.other, buf_cap, nullptr, k.n_mid, mask_eqp, kBandNfftMax, hist_eqp, cur_eqp, k.P, eq_list.dev, eq_list.n);
+    run_band(k.cur, buf_cap, k.other, buf_cap, nullptr, k.n_mid, fc[FC_EQP], k.P, eq_list.dev, eq_list.n);
+    fc[FC_EQP].flip();
     long long per = (k.n_mid + NT - 1) / NT;
     hipLaunchKernelGGL(copy_rows_kernel, dim3((unsigned)(per < 1024 ? per : 1024), (unsigned)eq_list.n), dim3(NT), 0, stream, k.other, k.cur, buf_cap,
                        (int)k.n_mid, (const int *)eq_list.dev);
@@ -941,16 +939,15 @@ int Engine::run_am(ChainCall &k)
     }
     if (k.direct && lists[L_BP1P].n) {      // bp1 is the AM / SAM channels' last stage: it follows their detectors on the second stream
         std::swap(stream, side_stream);
-        int hc = cur_bp1;
+        Fircore &bp1 = fc[FC_BP1];       // (run_output flips its pair)
         if (k.am_fused) {
             if (amlv_src.a) band_amlv = &amlv_src;
-            run_band(other, buf_cap, k.out, k.out_stride, epi, n_mid, mask_bp1, kBandNfftMax, hist_bp1, hc, k.P, lists[L_AM].dev, lists[L_AM].n, false, false, 0, nullptr, 0,
+            run_band(other, buf_cap, k.out, k.out_stride, epi, n_mid, bp1, k.P, lists[L_AM].dev, lists[L_AM].n, false, false, 0, nullptr, 0,
                      np_am && !(dbg_forms & 16) ? lists[L_PAIRS_AM].dev : nullptr, np_am);
             band_amlv = nullptr;
-            hc = cur_bp1;
-            if (lists[L_SAM].n) run_band(cur, buf_cap, k.out, k.out_stride, epi, n_mid, mask_bp1, kBandNfftMax, hist_bp1, hc, k.P, lists[L_SAM].dev, lists[L_SAM].n, false, false, 0,
+            if (lists[L_SAM].n) run_band(cur, buf_cap, k.out, k.out_stride, epi, n_mid, bp1, k.P, lists[L_SAM].dev, lists[L_SAM].n, false, false, 0,
                                 nullptr, 0, np_sam && !(dbg_forms & 16) ? lists[L_PAIRS_SAM].dev : nullptr, np_sam);
-        } else run_band(cur, buf_cap, k.out, k.out_stride, epi, n_mid, mask_bp1, kBandNfftMax, hist_bp1, hc, k.P, lists[L_BP1P].dev, lists[L_BP1P].n);
+        } else run_band(cur, buf_cap, k.out, k.out_stride, epi, n_mid, bp1, k.P, lists[L_BP1P].dev, lists[L_BP1P].n);
         std::swap(stream, side_stream);
     }
     return QH_OK;
@@ -968,7 +965,7 @@ int Engine::run_fm(ChainCall &k)
     // share of the average off (local_dc), a chain over the tiles' contributions gives the average ahead of every tile, and the
     // de-emphasis stage's load takes the rest off and applies the gain (OsfirArgs::fmdc_*): 8 bytes per sample read there instead
     // of 8 read + 16 written here and 16 read there
-    const bool fmdc_fused = pair && long_parts[2] <= 1 && !(dbg_forms & 256);
+    const bool fmdc_fused = pair && fc[FC_DE].parts <= 1 && !(dbg_forms & 256);
     FmDcSrc fmdc_src{ nullptr, 0, 0 };
     {
         // fused: nbp0 left the angles in the channels' own rows (first half) and the loop output goes to the rows of `other`
@@ -1012,17 +1009,20 @@ int Engine::run_fm(ChainCall &k)
         // with the stage's own mask and delay lines.  Where the audio is made in the load (fmdc_fused) it is loaded the same way here, two
         // channels a tile (the taps are real); otherwise it lies in the rows of cur.
         if (fmdc_src.a) band_fmdc = &fmdc_src;
-        run_band(cur, buf_cap, fq_noise, fq_noise_cap, nullptr, n_mid, mask_fq, 0, hist_fq, cur_fq, k.P, fq_list.dev, fq_list.n, false, false, 0, nullptr, 0,
+        run_band(cur, buf_cap, fq_noise, fq_noise_cap, nullptr, n_mid, fc[FC_FQ], k.P, fq_list.dev, fq_list.n, false, false, 0, nullptr, 0,
                  fmdc_src.a ? fq_pairs.dev : nullptr, np_fq);
+        fc[FC_FQ].flip();
         band_fmdc = nullptr;
     }
     {   // de-emphasis: real taps on a real signal, two channels per tile
         if (fmdc_src.a) band_fmdc = &fmdc_src;
-        run_band(cur, buf_cap, other, buf_cap, nullptr, n_mid, mask_de, 0, hist_de, cur_de, k.P, lists[L_FM].dev, lists[L_FM].n, false, false, 0, nullptr, 0,
+        run_band(cur, buf_cap, other, buf_cap, nullptr, n_mid, fc[FC_DE], k.P, lists[L_FM].dev, lists[L_FM].n, false, false, 0, nullptr, 0,
                  pair ? lists[L_PAIRS_FM].dev : nullptr, np_fm);
         band_fmdc = nullptr;
     }
-    run_band(other, buf_cap, cur, buf_cap, nullptr, n_mid, mask_aud, 0, hist_aud, cur_aud, k.P, lists[L_FM].dev, lists[L_FM].n);   // audio filter
+    run_band(other, buf_cap, cur, buf_cap, nullptr, n_mid, fc[FC_AUD], k.P, lists[L_FM].dev, lists[L_FM].n);   // audio filter
+    // the pair's two stages run in every call of run_fm and flip together, here and nowhere else: their halves never differ
+    fc[FC_DE].flip(); fc[FC_AUD].flip();
     tick(1);
     {
         const int G = seg_groups(lists[L_FM].n, n_mid);
@@ -1084,9 +1084,8 @@ void Engine::lms_at(const ChainCall &k, int pos, double2 *b)
 // xbandpass (bp1) at position pos, from the rows of cur to those of other -- unless bp1 ended the AM / SAM channels' chain already
 void Engine::bp1_at(const ChainCall &k, int pos)
 {
-    int hc = cur_bp1;
     if (lists[L_BP1P + pos].n && !k.direct)
-        run_band(k.cur, buf_cap, k.other, buf_cap, nullptr, k.n_mid, mask_bp1, kBandNfftMax, hist_bp1, hc, k.P, lists[L_BP1P + pos].dev, lists[L_BP1P + pos].n);
+        run_band(k.cur, buf_cap, k.other, buf_cap, nullptr, k.n_mid, fc[FC_BP1], k.P, lists[L_BP1P + pos].dev, lists[L_BP1P + pos].n);
 }
 
 // xwcpagc modes 1-4.  Long calls: the level detector in time tiles, everything around it lane-parallel (qh_agc_tiled.hpp).  Short
@@ -1384,7 +1383,7 @@ void Engine::run_output(const ChainCall &k)
     lms_at(k, 1, k.cur);
     lms_at(k, 2, k.other);
     bp1_at(k, 1);
-    if (lists[L_BP1].n) cur_bp1 ^= 1;
+    if (lists[L_BP1].n) fc[FC_BP1].flip();       // the launches of both positions, and of run_am, read the one half
     if (meters_on) {    // agcmeter sits after xwcpagc (RXA.c:589); mode 0's gain multiply is applied below, so its
                         // level reading is taken on the fixed-gain input times g^2 (m_g2)
         if (lists[L_PLAIN].n) hipLaunchKernelGGL(meter_kernel, dim3((unsigned)lists[L_PLAIN].n), dim3(64), 0, stream, k.cur, buf_cap, k.nblk, dsp_size,

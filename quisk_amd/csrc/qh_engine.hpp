@@ -15,8 +15,7 @@
 //   hist_front [2][nch][HF]  raw input samples (the reference's resampler ring holds them behind xshift; here the
 //                            oscillator sits behind the filter, qh_osfir.hpp OUTMIX, and nco_retune_hist_kernel
 //                            rewrites the row when a channel's shift changes)
-//   hist_nbp   [2][nch][HB]  nbp0 input samples  (the reference's fircore delay line)
-//   hist_bp1   [2][nch][HB]
+//   fc[s].hist [2][nch][HB]  the input samples of fircore stage s (the reference's fircore delay line)
 //   nco_phase  [nch]         64-bit fixed-point turns
 #pragma once
 #include <hip/hip_runtime.h>
@@ -91,7 +90,6 @@ struct ChanCfg {
     bool agc_rewindow = false;          // the attack window moved in mid-stream: the state's ring is taken again from the full one
     bool agc_ran = false, agc_stale = false;    // the window moved while the ring held samples: ring_max may be stale (qh_agc_tiled.hpp)
     int bp1_run = 1, bp1_nc = 2048, bp1_wintype = 1;            // RXA.c:377-389
-    bool long_live[5] = { false, false, false, false, false };  // the channel holds a delay line of stage sid longer than 4095 samples (process_chain)
     double bp1_flow = -4150.0, bp1_fhigh = -150.0, bp1_gain = 1.0;
     double gain1 = 4.0, gain2I = 1.0, gain2Q = 1.0;             // RXA.c:464-474
     int inselect = 3, copy = 0;
@@ -103,9 +101,7 @@ struct ChanCfg {
     struct Lms { int run = 0, position = 0, taps = 64, delay = 16; double two_mu = 0.0001, gamma = 0.1; bool dirty = true, flush = false; } lms[2];
     // emnr (create_emnr of create_rxa, RXA.c:319-332)
     // snba (wdsp/snb.c) and its bandpass bpsnba (snb.c:696-855; run / position follow the mode, RXA.c:883-917)
-    int snba_run = 0, snb_hist_at = 0;
-    int fm_hist_at = 0;                                         // ping-pong half that holds this channel's FM fircore delay lines
-    int bp1_hist_at = 0;                                        // ... and bp1's (SetRXABandpassRun switches it on WITHOUT the flush of RXAbp1Set)
+    int snba_run = 0;
     bool snba_flush = false, snba_taps_dirty = true, snba_rout_flush = false, snb_dirty = true, snb_flush = false;
     double snba_f_low = 200.0, snba_f_high = 0.0;               // outresamp fc_low / fcin (snb.c:45-46, resample.c:195-204)
     int snb_pos() const {
@@ -139,15 +135,14 @@ struct ChanCfg {
     bool ssql_dirty = true;
     bool ssql_on() const { return ssql_run != 0; }
     // xfmsq (create_fmsq of create_rxa, RXA.c:214-234: run 0, tail 0.750, unmute 0.562 -- not 0.9 apart until SetRXAFMSQThreshold runs --,
-    // nc max(2048, dsp_size), mp 0); fmsq_hist_at: the ping-pong half that holds the noise filter's delay line while the stage is off
-    int fmsq_run = 0, fmsq_nc = 2048, fmsq_mp = 0, fmsq_hist_at = 0;
+    // nc max(2048, dsp_size), mp 0)
+    int fmsq_run = 0, fmsq_nc = 2048, fmsq_mp = 0;
     double fmsq_tail_thresh = 0.750, fmsq_unmute_thresh = 0.562;
     bool fmsq_dirty = true;
     // xeqp (create_eqp of create_rxa, RXA.c:257-275: run 0, nc max(2048, dsp_size) -- Engine::init --, mp 0, ten frequencies with 0 dB each,
     // ctfmode 0, wintype 0).  eqp_F / eqp_G: nfreqs + 1 entries, G[0] the preamp, F[0] not read.  eqp_flush: SetRXAEQNC took a new nc
-    // (setNc_fircore zeroes the delay line); eqp_tie: two frequencies coincide after eq_impulse's clamp while their gains differ;
-    // eqp_hist_at: the ping-pong half that holds the delay line while the stage is off
-    int eqp_run = 0, eqp_nc = 2048, eqp_mp = 0, eqp_ctfmode = 0, eqp_wintype = 0, eqp_hist_at = 0;
+    // (setNc_fircore zeroes the delay line); eqp_tie: two frequencies coincide after eq_impulse's clamp while their gains differ
+    int eqp_run = 0, eqp_nc = 2048, eqp_mp = 0, eqp_ctfmode = 0, eqp_wintype = 0;
     std::vector<double> eqp_F = { 0.0, 32.0, 63.0, 125.0, 250.0, 500.0, 1000.0, 2000.0, 4000.0, 8000.0, 16000.0 }, eqp_G = std::vector<double>(11, 0.0);
     bool eqp_dirty = true, eqp_flush = false, eqp_tie = false;
     // xsender / xsiphon (qh_taps.hpp): both off until enabled -- a tap costs a pass (the reference runs the siphon of every channel,
@@ -167,6 +162,35 @@ struct ChanCfg {
         return agc_run && agc_mode == 0 && ((bp1_run && bp1_pos) || (lms[0].run && lms[0].position) || (lms[1].run && lms[1].position) ||
                                             (emnr_run && emnr_pos) || ap_on() || ssql_on());
     }
+};
+
+// The overlap-save "fircore" stages of the chain (wdsp/firmin.c), in the order of their ping-pong bits in Engine::flags():
+// nbp0, bp1, the FM de-emphasis and audio filters, bpsnba, xfmsq's noise filter, xeqp
+enum FcId { FC_NBP, FC_BP1, FC_DE, FC_AUD, FC_SNB, FC_FQ, FC_EQP, FC_COUNT };
+
+// One fircore stage: its mask rows, its delay lines and where each channel's line lies.
+// The delay lines are a ping-pong pair [2][nch][kHistBand]: a launch reads half `cur` and writes the other one for its own channels, and
+// the pair flips once per call in which the stage ran (flip(): the callers' step, so that one call may run the stage over several
+// channel lists).  A fircore keeps its delay line while its channel sits the stage out (xbandpass / xnbp / xeqp with run 0 only copy),
+// so a channel that is not listed keeps its rows in the half that was current when it left: chan[ch].at (Engine::fc_follow).
+// Long impulse responses (nc > 4096, kLongPart): `parts` partitions (1: the ordinary path), their masks lmask ([nch or 1][kLongParts][8192]),
+// how many of them each mask row's own impulse response reaches lrow_parts ([nch or 1]) and the stage's last kLongHist input samples
+// lhist [2][nch][kLongHist].  can_long: xfmsq's noise filter and xeqp never take that form (Engine::chain_needs refuses such an nc).
+struct Fircore {
+    double2 *mask = nullptr;
+    long long mask_stride = 0;              // kBandNfftMax: one mask row per channel; 0: one row shared by the stage's channels
+    double2 *hist[2] = { nullptr, nullptr };
+    int cur = 0;
+    bool ChanCfg::*dirty = nullptr;         // nbp0, bp1, bpsnba: the channel's flag that has its mask row designed and uploaded again (plan_long)
+    bool can_long = true;
+    int parts = 1;
+    double2 *lmask = nullptr, *lhist[2] = { nullptr, nullptr };
+    int *lrow_parts = nullptr;
+    // listed: the channel ran the stage when its lists were last made; at: the half that holds its rows; long_live: it has run the stage
+    // with nc > 4096 since RXASetNC last zeroed its lines, so it holds more than the one-tile form has room for (Engine::plan_long)
+    struct Chan { bool listed = false, long_live = false; int at = 0; };
+    std::vector<Chan> chan;
+    void flip() { cur ^= 1; }
 };
 
 struct Engine {
@@ -196,7 +220,7 @@ struct Engine {
     // front (resampler) design
     int front_ntaps = 0, front_P = 0, front_L = 0;
     // device state
-    double2 *mask_front = nullptr, *mask_nbp = nullptr, *mask_bp1 = nullptr;
+    double2 *mask_front = nullptr;
     double2 *tw4096 = nullptr, *tw_inv_front = nullptr, *tw8192 = nullptr;
     int bnfft = kNfft;                      // tile size of the fircore stages: what their masks are built for (4096 or 8192)
     bool band2g = false;                    // 8192-point tiles shared by two lane groups (osfir8k_kernel): masks stored [even | odd]
@@ -214,24 +238,17 @@ struct Engine {
     int *retune_list = nullptr;
     unsigned long long *retune_law = nullptr;
     EpiParam *epi = nullptr;
-    double2 *hist_front[2] = { nullptr, nullptr }, *hist_nbp[2] = { nullptr, nullptr }, *hist_bp1[2] = { nullptr, nullptr };
-    int cur_front = 0, cur_nbp = 0, cur_bp1 = 0, cur_snb = 0;
-    double2 *mask_snb = nullptr, *hist_snb[2] = { nullptr, nullptr };
+    double2 *hist_front[2] = { nullptr, nullptr };
+    int cur_front = 0;
+    Fircore fc[FC_COUNT];
     double2 *buf[2] = { nullptr, nullptr };
     long long buf_cap = 0;                  // complex samples per channel
-    // long impulse responses (nc > 4096), per fircore stage s = 0 nbp0, 1 bp1, 2 FM de-emphasis, 3 FM audio filter, 4 bpsnba:
-    // long_parts[s] partitions (1: the ordinary path), their masks lmask[s] ([nch or 1][kLongParts][8192]), how many of them each mask row's
-    // own impulse response reaches lrow_parts[s] ([nch or 1]), the stage's last kLongHist input samples lhist[s][ping-pong][nch][kLongHist];
-    // lcat: history + block of the stage being run, ltmp: a partition's output
-    int long_parts[5] = { 1, 1, 1, 1, 1 };
-    double2 *lmask[5] = { nullptr, nullptr, nullptr, nullptr, nullptr };
-    int *lrow_parts[5] = { nullptr, nullptr, nullptr, nullptr, nullptr };
-    double2 *lhist[5][2] = { { nullptr, nullptr }, { nullptr, nullptr }, { nullptr, nullptr }, { nullptr, nullptr }, { nullptr, nullptr } };
+    // long impulse responses (Fircore::parts > 1): lcat: history + block of the stage being run, ltmp: a partition's output
     double2 *lcat = nullptr, *ltmp = nullptr;
     long long lcat_cap = 0;                 // the buf_cap they were made for
-    int long_stage_alloc(int sid, bool shared_mask);
+    int long_stage_alloc(Fircore &f);
     int long_buffers();
-    int long_masks_upload(int sid, long long row, const std::vector<cd> &h);
+    int long_masks_upload(Fircore &f, long long row, const std::vector<cd> &h);
     // Every device buffer the engine owns, by its address, and its size in bytes: alloc() enters it, ~Engine frees it, dev_bytes()
     // adds them up (the qh_rat resamplers hold their own)
     std::map<void *, long long> owned;
@@ -295,33 +312,30 @@ struct Engine {
     int ssql_alloc();
     bool ssql_listed() const { return ssql_lists[0].n || ssql_lists[1].n; }
     // xfmsq (qh_fmsq.hpp), made when a channel first runs it, in blocks of its own: the list of its channels and their pairs for the
-    // noise filter (as L_PAIRS_FM), parameters, state, the ramps, the noise filter's mask (one design for the engine's FMSQ channels, as
-    // the FM filters), its delay lines and its output rows [nch][fq_noise_cap]
+    // noise filter (as L_PAIRS_FM), parameters, state, the ramps, the noise filter (fc[FC_FQ]: one design for the engine's FMSQ channels,
+    // as the FM filters) and its output rows [nch][fq_noise_cap]
     ChanList fq_list, fq_pairs;
     std::vector<int> fq_h, fq_pairs_h;
-    std::vector<char> fq_listed;
     int *fq_list_block = nullptr;
     int np_fq = 0;
     FmsqParam *fq_prm = nullptr;
     FmsqState *fq_state = nullptr;
     double *fq_cup = nullptr, *fq_cdown = nullptr;
-    double2 *mask_fq = nullptr, *hist_fq[2] = { nullptr, nullptr }, *fq_noise = nullptr;
+    double2 *fq_noise = nullptr;
     long long fq_noise_cap = 0;
-    int cur_fq = 0, fq_ntup = 0, fq_ntdown = 0, fq_nready = 0, fq_nc_built = 0, fq_mp_built = 0, fq_nfft_built = 0;
+    int fq_ntup = 0, fq_ntdown = 0, fq_nready = 0, fq_nc_built = 0, fq_mp_built = 0, fq_key_built = 0;
     int fmsq_alloc();
     int prm_fmsq(ChanCfg &c, int ch);
     int fmsq_filter();
     void launch_fmsq_flush();
     // xeqp (wdsp/eq.c:166-208), made when a channel first runs it, in blocks of their own: the list of its channels and of the others
-    // (the linear path passes those on in a pointwise pass), one mask row per channel (EQ profiles are per channel, as bp1's designs) and
-    // the delay lines [2][nch][kHistBand]
+    // (the linear path passes those on in a pointwise pass) and fc[FC_EQP], one mask row per channel (EQ profiles are per channel, as bp1's
+    // designs)
     ChanList eq_list, eq_rest;
     std::vector<int> eq_h, eq_rest_h;
-    std::vector<char> eq_listed;
     std::vector<std::vector<cd>> eq_taps_h;     // per channel: the taps behind the mask row last uploaded (qh_rxa_debug_eqp); empty until then
     int *eq_list_block = nullptr;
-    double2 *mask_eqp = nullptr, *hist_eqp[2] = { nullptr, nullptr };
-    int cur_eqp = 0, eq_nfft_built = 0;
+    int eq_key_built = 0;
     bool eq_lists_dirty = false;
     std::vector<cd> eqp_taps(const ChanCfg &c) const;
     int eqp_alloc();
@@ -368,7 +382,6 @@ struct Engine {
     SnbaTune *snba_tune = nullptr;          // [nch]; host copy below, uploaded when a tuning setter has run
     std::vector<SnbaTune> snba_tune_h;
     bool snba_tune_dirty = true;
-    std::vector<char> snb_listed, fm_listed, bp1_listed;
     int snba_alloc();
     int snba_ovrlp = 4;                 // create_rxa's overlap (RXA.c:244): incr = xsize / 4
     void snba_plan(int ovrlp);
@@ -430,10 +443,11 @@ struct Engine {
     PllParam sam_pll_prm{}, fm_pll_prm{};
     SnotchParam *sn_prm = nullptr;
     SnotchState *sn_state = nullptr;
-    double2 *mask_de = nullptr, *mask_aud = nullptr, *hist_de[2] = { nullptr, nullptr }, *hist_aud[2] = { nullptr, nullptr };
-    int cur_de = 0, cur_aud = 0, fm_nc_built = 0, fm_mp = 0, fm_mp_built = 0, fm_nfft_built = 0;
-    unsigned flags() const { return (unsigned)(cur_front | cur_nbp << 1 | cur_bp1 << 2 | cur_de << 3 | cur_aud << 4 | cur_snb << 5 | cur_fq << 6 | cur_eqp << 7); }
-    void set_flags(unsigned f) { cur_front = f & 1; cur_nbp = f >> 1 & 1; cur_bp1 = f >> 2 & 1; cur_de = f >> 3 & 1; cur_aud = f >> 4 & 1; cur_snb = f >> 5 & 1; cur_fq = f >> 6 & 1; cur_eqp = f >> 7 & 1; }
+    int fm_nc_built = 0, fm_mp = 0, fm_mp_built = 0, fm_key_built = 0;
+    // the ping-pong halves in use: bit 0 the front stage's, bit 1 + s fircore stage s's -- one captured launch sequence per value
+    static_assert(sizeof(graph_slot) / sizeof(graph_slot[0]) == 1u << (1 + FC_COUNT), "one graph slot per state of the ping-pong flags");
+    unsigned flags() const { unsigned f = (unsigned)cur_front; for (int s = 0; s < FC_COUNT; s++) f |= (unsigned)fc[s].cur << (1 + s); return f; }
+    void set_flags(unsigned f) { cur_front = f & 1; for (int s = 0; s < FC_COUNT; s++) fc[s].cur = f >> (1 + s) & 1; }
     void drop_graphs() { for (auto &g : graph_slot) if (g.exec) { (void)hipGraphExecDestroy(g.exec); g.exec = nullptr; } }
     // Growing, rebuilding or re-uploading a device buffer: captured launch sequences hold its address and launches queued on either
     // stream may still use it, so nothing is freed or rewritten before quiesce() has waited for both streams and dropped the captures.
@@ -477,16 +491,18 @@ struct Engine {
     int refresh_params();
     std::vector<cd> notched(const ChanCfg &c, double f_low, double f_high, double scale) const;
     int snb_mask(ChanCfg &c, int ch);
-    int put_mask(double2 *mask, int ch, const std::vector<cd> &m);
+    // the layout the one-tile masks are built for: a stage's masks are made again when it moves (pick_band_tile)
+    int mask_key() const { return 2 * bnfft + (band2g ? 1 : 0); }
+    int fc_alloc(Fircore &f);
+    int put_taps(Fircore &f, int row, const std::vector<cd> &h, std::vector<cd> &m);
     // refresh_demod and its steps
     int refresh_demod();
     int demod_init();
     void build_lists(std::vector<int> (&h)[L_COUNT]);
     int stages_alloc();
     int refresh_lists();
-    struct Rows { double2 **h; int cur; int len; };     // a fircore's ping-pong delay lines, the half current for them, the row length
-    int follow_rows(std::vector<char> &listed, int ChanCfg::*at, int cur, const std::vector<int> &chans, std::initializer_list<Rows> rows);
-    int zero_rows(double2 *const h[2], double2 *const lh[2], int ch, int n = 1);
+    int fc_follow(Fircore &f, const std::vector<int> &chans);
+    int zero_rows(Fircore &f, int ch, int n = 1);
     int prm_agc(ChanCfg &c, int ch);
     int prm_emnr(ChanCfg &c, int ch);
     int prm_snba(ChanCfg &c, int ch);
@@ -512,7 +528,7 @@ struct Engine {
     int ensure_abuf(long long n);
     void pack_audio(const double2 *src, long long src_stride, long long n);
     void run_band(const double2 *src, long long src_stride, double2 *dst, long long dst_stride, const EpiParam *ep,
-                  long long n_mid, const double2 *mask, long long mask_stride, double2 **hist, int &hc, int P,
+                  long long n_mid, Fircore &f, int P,
                   const int *list, int nlist, bool meter = false, bool egress = false, int det = 0, double *det_out = nullptr,
                   long long det_stride = 0, const int *pairs = nullptr, int npairs = 0);
     int ensure_buffers(long long n_mid);

@@ -77,6 +77,13 @@ int Engine::init()
     cfg.assign((size_t)nch, ChanCfg());
     for (ChanCfg &c : cfg) c.eqp_nc = std::max(2048, dsp_size);        // create_eqp's nc, RXA.c:265
     snba_tune_h.assign((size_t)nch, SnbaTune{ 64, 2, 10, 2, 2, 0, 8.0, 20.0, 0.5 });         // create_snba's arguments, RXA.c:183-202
+    // the fircore stages: the FM pair and xfmsq's noise filter share one design among their channels, the others hold one per channel
+    for (int s = 0; s < FC_COUNT; s++) {
+        fc[s].mask_stride = s == FC_DE || s == FC_AUD || s == FC_FQ ? 0 : kBandNfftMax;
+        fc[s].chan.assign((size_t)nch, Fircore::Chan());
+    }
+    fc[FC_NBP].dirty = &ChanCfg::nbp_dirty; fc[FC_BP1].dirty = &ChanCfg::bp1_dirty; fc[FC_SNB].dirty = &ChanCfg::snb_dirty;
+    fc[FC_FQ].can_long = fc[FC_EQP].can_long = false;
 
     std::vector<cd> tw = fft_twiddle_table(kNfft);
     if (int rc = alloc(tw4096, (long long)tw.size())) return rc;
@@ -109,12 +116,8 @@ int Engine::init()
         if (int rc = upload(tw_inv_front, twi, stream)) return rc;
         for (double2 *&h : hist_front) if (int rc = alloc(h, (long long)nch * kHistFront, true)) return rc;
     }
-    if (int rc = alloc(mask_nbp, (long long)nch * kBandNfftMax)) return rc;
-    if (int rc = alloc(mask_bp1, (long long)nch * kBandNfftMax)) return rc;
-    for (int i = 0; i < 2; i++) {
-        if (int rc = alloc(hist_nbp[i], (long long)nch * kHistBand, true)) return rc;
-        if (int rc = alloc(hist_bp1[i], (long long)nch * kHistBand, true)) return rc;
-    }
+    if (int rc = fc_alloc(fc[FC_NBP])) return rc;
+    if (int rc = fc_alloc(fc[FC_BP1])) return rc;
     if (int rc = alloc(nco_phase, nch, true)) return rc;
     if (int rc = alloc(nco_dphase, nch, true)) return rc;
     if (int rc = alloc(nco_parked, nch, true)) return rc;
@@ -139,8 +142,29 @@ static unsigned long long turns_fx(double f, double rate)
 int Engine::refresh_params()
 {
     // one pass over the channels; upload only what changed
-    std::vector<cd> last_nbp, last_bp1, last_nbp_h, last_bp1_h;      // masks and impulse responses of the last design made
-    const ChanCfg *last_nbp_cfg = nullptr, *last_bp1_cfg = nullptr;
+    // nbp0's and bp1's designs: what they are made from, and the last one made (its impulse response and one-tile mask), which the next
+    // channel with the same settings takes over.  notch: nbp0 with its notch database, which is the channel's own -- never taken over.
+    struct BandSet {
+        int run, nc, wintype, mp, notch; double flow, fhigh, gain;
+        bool operator==(const BandSet &o) const
+        { return run == o.run && nc == o.nc && wintype == o.wintype && mp == o.mp && notch == o.notch && flow == o.flow && fhigh == o.fhigh && gain == o.gain; }
+    };
+    struct BandLast { bool any = false; BandSet set; std::vector<cd> h, mask; } last_nbp, last_bp1;
+    auto design_band = [&](Fircore &f, const ChanCfg &c, int ch, const BandSet &d, BandLast &last) -> int {
+        if (!(last.any && !d.notch && last.set == d)) {
+            std::vector<cd> &h = last.h;
+            if (d.run) {
+                // calc_nbp_impulse, wdsp/nbp.c:221-238; bp1: wdsp/bandpass.c:302
+                const double scale = d.gain / (double)(2 * dsp_size);
+                h = d.notch ? notched(c, d.flow, d.fhigh, scale) : fir_bandpass(d.nc, d.flow, d.fhigh, (double)dsp_rate, d.wintype, 1, scale);
+                if (d.mp) h = mp_imp(h, 16, 0);             // calc_fircore, wdsp/firmin.c:327-328
+                // the reference's unnormalised inverse FFT of 2*size points restores the 1/(2*size)
+                for (auto &v : h) v *= (double)(2 * dsp_size);
+            } else h.assign(1, cd(1.0, 0.0));               // identity when the filter is off
+            last.mask.clear(); last.set = d; last.any = true;
+        }
+        return put_taps(f, ch, last.h, last.mask);
+    };
     // Oscillator changes (SetRXAShiftFreq / SetRXAShiftRun).  With a front FIR stage (D > 1) the oscillator sits behind
     // the filter: first the stored raw history of every changed channel is re-expressed for its new phase law (the kernel
     // reads the old law from the device arrays, so it goes first), then the arrays are updated, then the channel's
@@ -196,65 +220,24 @@ int Engine::refresh_params()
             c.epi_dirty = false;
         }
         if (c.nbp_dirty) c.snb_dirty = true;        // bpsnba's nbp shares nc, window, auto-increase, mp and the notch database with nbp0
-        if (c.snb_dirty && c.snba_run && mask_snb) if (int rc = snb_mask(c, ch)) return rc;
-        if (c.snb_flush && hist_snb[0]) if (int rc = zero_rows(hist_snb, lhist[4], ch)) return rc;         // setNc_fircore zeroes the delay line
+        if (c.snb_dirty && c.snba_run && fc[FC_SNB].mask) if (int rc = snb_mask(c, ch)) return rc;
+        if (c.snb_flush && fc[FC_SNB].hist[0]) if (int rc = zero_rows(fc[FC_SNB], ch)) return rc;         // setNc_fircore zeroes the delay line
         c.snb_flush = false;
         if (c.nbp_dirty) {
-            // calc_nbp_impulse without notches, wdsp/nbp.c:234-238; identity when the filter is off
-            bool same = !c.fnfrun && last_nbp_cfg && !last_nbp_cfg->fnfrun && last_nbp_cfg->nbp_run == c.nbp_run && last_nbp_cfg->nbp_nc == c.nbp_nc &&
-                        last_nbp_cfg->nbp_wintype == c.nbp_wintype && last_nbp_cfg->nbp_flow == c.nbp_flow &&
-                        last_nbp_cfg->nbp_fhigh == c.nbp_fhigh && last_nbp_cfg->nbp_gain == c.nbp_gain && last_nbp_cfg->mp == c.mp;
-            if (!same) {
-                std::vector<cd> h;
-                if (c.nbp_run && c.fnfrun)
-                    h = notched(c, c.nbp_flow, c.nbp_fhigh, c.nbp_gain / (double)(2 * dsp_size));
-                else if (c.nbp_run)
-                    h = fir_bandpass(c.nbp_nc, c.nbp_flow, c.nbp_fhigh, (double)dsp_rate, c.nbp_wintype, 1,
-                                     c.nbp_gain / (double)(2 * dsp_size));
-                else
-                    h.assign(1, cd(1.0, 0.0));
-                if (c.nbp_run && c.mp) h = mp_imp(h, 16, 0);            // calc_fircore, wdsp/firmin.c:327-328
-                // the reference's unnormalised inverse FFT of 2*size points restores the 1/(2*size)
-                if (c.nbp_run) for (auto &v : h) v *= (double)(2 * dsp_size);
-                last_nbp_h = h;
-                if ((int)h.size() > kLongPart) h.resize((size_t)kLongPart);      // (the one-tile mask is not used then)
-                last_nbp = band_mask(h);
-                last_nbp_cfg = &c;
-            }
-            if (long_parts[0] > 1) if (int rc = long_masks_upload(0, ch, last_nbp_h)) return rc;
-            if (int rc = put_mask(mask_nbp, ch, last_nbp)) return rc;
+            if (int rc = design_band(fc[FC_NBP], c, ch, { c.nbp_run, c.nbp_nc, c.nbp_wintype, c.mp, c.fnfrun, c.nbp_flow, c.nbp_fhigh, c.nbp_gain }, last_nbp)) return rc;
             c.nbp_dirty = false;
         }
         if (c.bp1_dirty) {
-            bool same = last_bp1_cfg && last_bp1_cfg->bp1_run == c.bp1_run && last_bp1_cfg->bp1_nc == c.bp1_nc &&
-                        last_bp1_cfg->bp1_wintype == c.bp1_wintype && last_bp1_cfg->bp1_flow == c.bp1_flow &&
-                        last_bp1_cfg->bp1_fhigh == c.bp1_fhigh && last_bp1_cfg->bp1_gain == c.bp1_gain && last_bp1_cfg->mp == c.mp;
-            if (!same) {
-                std::vector<cd> h;
-                if (c.bp1_run) {
-                    h = fir_bandpass(c.bp1_nc, c.bp1_flow, c.bp1_fhigh, (double)dsp_rate, c.bp1_wintype, 1,
-                                     c.bp1_gain / (double)(2 * dsp_size));     // wdsp/bandpass.c:302
-                    if (c.mp) h = mp_imp(h, 16, 0);
-                    for (auto &v : h) v *= (double)(2 * dsp_size);
-                } else {
-                    h.assign(1, cd(1.0, 0.0));
-                }
-                last_bp1_h = h;
-                if ((int)h.size() > kLongPart) h.resize((size_t)kLongPart);
-                last_bp1 = band_mask(h);
-                last_bp1_cfg = &c;
-            }
-            if (long_parts[1] > 1) if (int rc = long_masks_upload(1, ch, last_bp1_h)) return rc;
-            if (int rc = put_mask(mask_bp1, ch, last_bp1)) return rc;
+            if (int rc = design_band(fc[FC_BP1], c, ch, { c.bp1_run, c.bp1_nc, c.bp1_wintype, c.mp, 0, c.bp1_flow, c.bp1_fhigh, c.bp1_gain }, last_bp1)) return rc;
             c.bp1_dirty = false;
             lists_dirty = true;             // the channel pairs of the real bp1 filters follow the designs
         }
         if (c.nbp_flush) {      // setNc_fircore re-plans and so zeroes the delay line
-            if (int rc = zero_rows(hist_nbp, lhist[0], ch)) return rc;
+            if (int rc = zero_rows(fc[FC_NBP], ch)) return rc;
             c.nbp_flush = false;
         }
         if (c.bp1_flush) {      // flush_bandpass on off->on (RXA.c:825) and setNc_fircore
-            if (int rc = zero_rows(hist_bp1, lhist[1], ch)) return rc;
+            if (int rc = zero_rows(fc[FC_BP1], ch)) return rc;
             c.bp1_flush = false;
         }
     }
@@ -285,22 +268,34 @@ int Engine::snb_mask(ChanCfg &c, int ch)
     default: break;
     }
     const double scale = 1.0 / (double)(2 * dsp_size);
-    if (long_parts[4] > 1) if (int rc = long_stage_alloc(4, false)) return rc;
+    if (fc[FC_SNB].parts > 1) if (int rc = long_stage_alloc(fc[FC_SNB])) return rc;
     std::vector<cd> h = run_notches ? notched(c, f_low, f_high, scale) : fir_bandpass(c.nbp_nc, f_low, f_high, (double)dsp_rate, c.nbp_wintype, 1, scale);
     if (c.mp) h = mp_imp(h, 16, 0);
     for (auto &v : h) v *= (double)(2 * dsp_size);
-    if (long_parts[4] > 1) if (int rc = long_masks_upload(4, ch, h)) return rc;
-    if ((int)h.size() > kLongPart) h.resize((size_t)kLongPart);      // (the one-tile mask is not used then)
-    if (int rc = put_mask(mask_snb, ch, band_mask(h))) return rc;
+    std::vector<cd> m;
+    if (int rc = put_taps(fc[FC_SNB], ch, h, m)) return rc;
     c.snb_dirty = false;
     return QH_OK;
 }
 
-// a channel's row of a fircore stage's masks (the bnfft bins of the tile in use)
-int Engine::put_mask(double2 *mask, int ch, const std::vector<cd> &m)
+// The taps h of row `row` of a fircore stage's masks (a channel's row, or row 0 of a shared mask) onto the device: the partitions' masks
+// when the stage runs its long form, and the one-tile mask (the bnfft bins of the tile in use; of the first kLongPart taps, and not used,
+// in the long form).  m: that mask, made here when the caller passes it empty and left to it for the next row of the same design.
+int Engine::put_taps(Fircore &f, int row, const std::vector<cd> &h, std::vector<cd> &m)
 {
-    QH_HIP(hipMemcpyAsync(mask + (size_t)ch * kBandNfftMax, m.data(), (size_t)bnfft * sizeof(cd), hipMemcpyHostToDevice, stream));
-    QH_HIP(hipStreamSynchronize(stream));
+    if (f.parts > 1) if (int rc = long_masks_upload(f, row, h)) return rc;
+    if (m.empty()) m = band_mask((int)h.size() > kLongPart ? std::vector<cd>(h.begin(), h.begin() + kLongPart) : h);
+    QH_HIP(hipMemcpyAsync(f.mask + (size_t)row * (size_t)f.mask_stride, m.data(), (size_t)bnfft * sizeof(cd), hipMemcpyHostToDevice, stream));
+    QH_HIP(hipStreamSynchronize(stream));       // the host vectors die with the callers' scopes
+    return QH_OK;
+}
+
+// A fircore stage's device rows: its masks and its delay lines, zeroed; every channel's line lies in the half that is current
+int Engine::fc_alloc(Fircore &f)
+{
+    if (int rc = alloc(f.mask, (f.mask_stride ? (long long)nch : 1LL) * kBandNfftMax)) return rc;
+    for (double2 *&h : f.hist) if (int rc = alloc(h, (long long)nch * kHistBand, true)) return rc;
+    for (Fircore::Chan &r : f.chan) { r.listed = false; r.at = f.cur; }
     return QH_OK;
 }
 
@@ -355,12 +350,8 @@ int Engine::demod_init()
     if (int rc = alloc(sam_prm, nch)) return rc;
     if (int rc = alloc(sn_prm, nch)) return rc;
     if (int rc = alloc(sn_state, nch, true)) return rc;
-    if (int rc = alloc(mask_de, kBandNfftMax)) return rc;
-    if (int rc = alloc(mask_aud, kBandNfftMax)) return rc;
-    for (int i = 0; i < 2; i++) {
-        if (int rc = alloc(hist_de[i], (long long)nch * kHistBand, true)) return rc;
-        if (int rc = alloc(hist_aud[i], (long long)nch * kHistBand, true)) return rc;
-    }
+    if (int rc = fc_alloc(fc[FC_DE])) return rc;
+    if (int rc = fc_alloc(fc[FC_AUD])) return rc;
     // init_amd (wdsp/amd.c:72-89) with create_rxa's constants (RXA.c:183-189)
     {
         const double zeta = 1.0, omegaN = 250.0, tauR = 0.02, tauI = 1.4;
@@ -638,33 +629,34 @@ int Engine::stages_alloc()
     return QH_OK;
 }
 
-// A fircore keeps its delay lines while its channel is off the stage's list, and the ping-pong pair flips for the listed channels
-// only: a channel that (re)joins the list finds its rows in the half that was current when it left (c.*at), and they move to the
-// current one.  rows: the stage's short and long delay lines, each with the half that is current for it.
-int Engine::follow_rows(std::vector<char> &listed, int ChanCfg::*at, int cur, const std::vector<int> &chans, std::initializer_list<Rows> rows)
+// The channels that run stage f from here on.  A fircore keeps its delay lines while its channel is off the stage's list, and the
+// ping-pong pair flips for the listed channels only: a channel that (re)joins the list finds its rows, short and long, in the half that
+// was current when it left (Chan::at), and they move to the current one.  Called wherever the set of a stage's running channels may have
+// changed, on either path; a stage that has not been made yet has nothing to follow.
+int Engine::fc_follow(Fircore &f, const std::vector<int> &chans)
 {
-    if (listed.size() != (size_t)nch) listed.assign((size_t)nch, 0);
-    for (int ch = 0; ch < nch; ch++) if (listed[(size_t)ch]) cfg[(size_t)ch].*at = cur;
-    std::fill(listed.begin(), listed.end(), 0);
+    if (!f.hist[0]) return QH_OK;
+    for (Fircore::Chan &r : f.chan) { if (r.listed) r.at = f.cur; r.listed = false; }
     for (int ch : chans) {
-        int &a = cfg[(size_t)ch].*at;
-        if (a != cur)
-            for (const Rows &r : rows)
-                if (r.h[0] && r.h[1])
-                    QH_HIP(hipMemcpyAsync(r.h[r.cur] + (size_t)ch * r.len, r.h[a] + (size_t)ch * r.len, (size_t)r.len * sizeof(double2),
-                                          hipMemcpyDeviceToDevice, stream));
-        a = cur;
-        listed[(size_t)ch] = 1;
+        Fircore::Chan &r = f.chan[(size_t)ch];
+        if (r.at != f.cur) {
+            QH_HIP(hipMemcpyAsync(f.hist[f.cur] + (size_t)ch * kHistBand, f.hist[r.at] + (size_t)ch * kHistBand, (size_t)kHistBand * sizeof(double2),
+                                  hipMemcpyDeviceToDevice, stream));
+            if (f.lhist[0]) QH_HIP(hipMemcpyAsync(f.lhist[f.cur] + (size_t)ch * kLongHist, f.lhist[r.at] + (size_t)ch * kLongHist,
+                                                  (size_t)kLongHist * sizeof(double2), hipMemcpyDeviceToDevice, stream));
+        }
+        r.at = f.cur;
+        r.listed = true;
     }
     return QH_OK;
 }
 
-// setNc_fircore's flush (wdsp/firmin.c:454-466): zero n channels' delay lines from channel ch on, short and long, in both halves
-int Engine::zero_rows(double2 *const h[2], double2 *const lh[2], int ch, int n)
+// setNc_fircore's flush (wdsp/firmin.c:454-466): zero n channels' delay lines of stage f from channel ch on, short and long, in both halves
+int Engine::zero_rows(Fircore &f, int ch, int n)
 {
     for (int i = 0; i < 2; i++) {
-        QH_HIP(hipMemsetAsync(h[i] + (size_t)ch * kHistBand, 0, (size_t)n * kHistBand * sizeof(double2), stream));
-        if (lh[i]) QH_HIP(hipMemsetAsync(lh[i] + (size_t)ch * kLongHist, 0, (size_t)n * kLongHist * sizeof(double2), stream));
+        QH_HIP(hipMemsetAsync(f.hist[i] + (size_t)ch * kHistBand, 0, (size_t)n * kHistBand * sizeof(double2), stream));
+        if (f.lhist[i]) QH_HIP(hipMemsetAsync(f.lhist[i] + (size_t)ch * kLongHist, 0, (size_t)n * kLongHist * sizeof(double2), stream));
     }
     return QH_OK;
 }
@@ -675,22 +667,17 @@ int Engine::refresh_lists()
     std::vector<int> h[L_COUNT];
     build_lists(h);
     if (int rc = stages_alloc()) return rc;
-    if (snba_state) {       // bpsnba's fircore (the partitioned form's 16383-sample delay line goes along: nc > 4096)
-        std::vector<int> snb(h[L_SNB]);
-        snb.insert(snb.end(), h[L_SNB + 1].begin(), h[L_SNB + 1].end());
-        if (int rc = follow_rows(snb_listed, &ChanCfg::snb_hist_at, cur_snb, snb, { { hist_snb, cur_snb, kHistBand }, { lhist[4], cur_snb, kLongHist } }))
-            return rc;
-    }
+    // bpsnba's fircore (the partitioned form's 16383-sample delay line goes along: nc > 4096)
+    std::vector<int> snb(h[L_SNB]);
+    snb.insert(snb.end(), h[L_SNB + 1].begin(), h[L_SNB + 1].end());
+    if (int rc = fc_follow(fc[FC_SNB], snb)) return rc;
     // bp1's: SetRXABandpassRun (bandpass.c:385-390) switches it on without RXAbp1Set's flush (RXA.c:825)
-    if (int rc = follow_rows(bp1_listed, &ChanCfg::bp1_hist_at, cur_bp1, h[L_BP1], { { hist_bp1, cur_bp1, kHistBand }, { lhist[1], cur_bp1, kLongHist } }))
-        return rc;
-    // the FM de-emphasis / audio fircores' while the channel is in another mode (SetRXAMode only clears fmd's run flag, RXA.c:758-776);
-    // fm_hist_at follows the de-emphasis filter's half
-    if (int rc = follow_rows(fm_listed, &ChanCfg::fm_hist_at, cur_de, h[L_FM], { { hist_de, cur_de, kHistBand }, { hist_aud, cur_aud, kHistBand },
-                                                                                { lhist[2], cur_de, kLongHist }, { lhist[3], cur_aud, kLongHist } }))
-        return rc;
+    if (int rc = fc_follow(fc[FC_BP1], h[L_BP1])) return rc;
+    // the FM de-emphasis / audio fircores' while the channel is in another mode (SetRXAMode only clears fmd's run flag, RXA.c:758-776)
+    if (int rc = fc_follow(fc[FC_DE], h[L_FM])) return rc;
+    if (int rc = fc_follow(fc[FC_AUD], h[L_FM])) return rc;
     // xfmsq's noise filter keeps its delay line while the stage is off (xfmsq with run 0 does not call its fircore, fmsq.c:143-147)
-    if (fq_prm) if (int rc = follow_rows(fq_listed, &ChanCfg::fmsq_hist_at, cur_fq, fq_h, { { hist_fq, cur_fq, kHistBand } })) return rc;
+    if (int rc = fc_follow(fc[FC_FQ], fq_h)) return rc;
     std::vector<int> all((size_t)nch * (L_COUNT + 3));
     for (int i = 0; i < L_COUNT; i++) std::copy(h[i].begin(), h[i].end(), all.begin() + (lists[i].dev - list_block));
     std::vector<double> fg((size_t)nch);
@@ -899,7 +886,7 @@ int Engine::prm_detect(ChanCfg &c, int ch)
 // tile moved
 int Engine::fm_filters(int want_nc)
 {
-    if (!want_nc || (want_nc == fm_nc_built && fm_mp == fm_mp_built && fm_nfft_built == 2 * bnfft + (band2g ? 1 : 0))) return QH_OK;
+    if (!want_nc || (want_nc == fm_nc_built && fm_mp == fm_mp_built && fm_key_built == mask_key())) return QH_OK;
     // de-emphasis by frequency sampling, audio band-pass 0.8*f_low .. 1.1*f_high
     const double rate = (double)dsp_rate, f_low = 300.0, f_high = 3000.0, afgain = 0.5;
     std::vector<cd> de = fc_impulse(want_nc, f_low, f_high, +20.0 * std::log10(f_high / f_low), 0.0, 1, rate, 1.0 / (2.0 * dsp_size), 0, 0);
@@ -910,17 +897,13 @@ int Engine::fm_filters(int want_nc)
     for (auto &v : au) v *= (double)(2 * dsp_size);
     de_real = true;
     for (const cd &v : de) de_real = de_real && v.imag() == 0.0;
-    if (long_parts[2] > 1) {
-        if (int rc = long_masks_upload(2, 0, de)) return rc;
-        if (int rc = long_masks_upload(3, 0, au)) return rc;
-        de.resize((size_t)kLongPart); au.resize((size_t)kLongPart);      // (the one-tile masks are not used then)
-    }
-    if (int rc = upload(mask_de, band_mask(de), stream)) return rc;
-    if (int rc = upload(mask_aud, band_mask(au), stream)) return rc;
-    fm_nfft_built = 2 * bnfft + (band2g ? 1 : 0);
+    std::vector<cd> m_de, m_au;
+    if (int rc = put_taps(fc[FC_DE], 0, de, m_de)) return rc;
+    if (int rc = put_taps(fc[FC_AUD], 0, au, m_au)) return rc;
+    fm_key_built = mask_key();
     if (fm_nc_built && fm_nc_built != want_nc) {      // setNc_fircore zeroes the delay lines
-        if (int rc = zero_rows(hist_de, lhist[2], 0, nch)) return rc;
-        if (int rc = zero_rows(hist_aud, lhist[3], 0, nch)) return rc;
+        if (int rc = zero_rows(fc[FC_DE], 0, nch)) return rc;
+        if (int rc = zero_rows(fc[FC_AUD], 0, nch)) return rc;
     }
     fm_nc_built = want_nc;
     return QH_OK;
@@ -1031,11 +1014,9 @@ int Engine::snba_alloc()
         for (int i = 0; i < q.cpp_in; i++) hin[(size_t)i] = imp[(size_t)i].real();
     }
     QH_HIP(hipMemcpyAsync(snba_hin, hin.data(), hin.size() * sizeof(double), hipMemcpyHostToDevice, stream));
-    if (int rc = alloc(mask_snb, (long long)nch * kBandNfftMax)) return rc;
-    for (double2 *&h : hist_snb) if (int rc = alloc(h, (long long)nch * kHistBand, true)) return rc;
+    if (int rc = fc_alloc(fc[FC_SNB])) return rc;
     QH_HIP(hipStreamSynchronize(stream));
-    snb_listed.assign((size_t)nch, 0);
-    for (ChanCfg &c : cfg) { c.snba_taps_dirty = true; c.snb_dirty = true; c.snba_flush = c.snba_rout_flush = false; c.snb_flush = false; c.snb_hist_at = cur_snb; }
+    for (ChanCfg &c : cfg) { c.snba_taps_dirty = true; c.snb_dirty = true; c.snba_flush = c.snba_rout_flush = false; c.snb_flush = false; }
     return QH_OK;
 }
 
@@ -1176,14 +1157,14 @@ int Engine::ensure_abuf(long long n)
     return grow(abuf, abuf_cap, n, nch);
 }
 
-int Engine::long_stage_alloc(int sid, bool shared_mask)
+int Engine::long_stage_alloc(Fircore &f)
 {
-    if (lmask[sid]) return QH_OK;
+    if (f.lmask) return QH_OK;
     if (int rc = quiesce()) return rc;
-    const long long rows = shared_mask ? 1 : nch;
-    if (int rc = alloc(lmask[sid], rows * kLongParts * kBandNfftMax, true)) return rc;
-    if (int rc = alloc(lrow_parts[sid], rows, true)) return rc;
-    for (double2 *&h : lhist[sid]) if (int rc = alloc(h, (long long)nch * kLongHist, true)) return rc;
+    const long long rows = f.mask_stride ? nch : 1;
+    if (int rc = alloc(f.lmask, rows * kLongParts * kBandNfftMax, true)) return rc;
+    if (int rc = alloc(f.lrow_parts, rows, true)) return rc;
+    for (double2 *&h : f.lhist) if (int rc = alloc(h, (long long)nch * kLongHist, true)) return rc;
     return QH_OK;
 }
 int Engine::long_buffers()
@@ -1196,7 +1177,7 @@ int Engine::long_buffers()
     return QH_OK;
 }
 // the kLongParts partition masks of the impulse response h (8192-point spectra of its 4096-tap slices; the slices past its end zero)
-int Engine::long_masks_upload(int sid, long long row, const std::vector<cd> &h)
+int Engine::long_masks_upload(Fircore &f, long long row, const std::vector<cd> &h)
 {
     std::vector<cd> all((size_t)kLongParts * kBandNfftMax, cd(0.0, 0.0));
     const int own = (int)std::min<size_t>((h.size() + kLongPart - 1) / kLongPart, (size_t)kLongParts);
@@ -1205,8 +1186,8 @@ int Engine::long_masks_upload(int sid, long long row, const std::vector<cd> &h)
         const std::vector<cd> m = make_mask(std::vector<cd>(h.begin() + (long)a, h.begin() + (long)b), kBandNfftMax);
         std::copy(m.begin(), m.end(), all.begin() + (long)((size_t)p * kBandNfftMax));
     }
-    QH_HIP(hipMemcpyAsync(lmask[sid] + (size_t)row * kLongParts * kBandNfftMax, all.data(), all.size() * sizeof(cd), hipMemcpyHostToDevice, stream));
-    return put_row(lrow_parts[sid], row, own);
+    QH_HIP(hipMemcpyAsync(f.lmask + (size_t)row * kLongParts * kBandNfftMax, all.data(), all.size() * sizeof(cd), hipMemcpyHostToDevice, stream));
+    return put_row(f.lrow_parts, row, own);
 }
 
 // The chains' transition over a segment: the one-sample map of the 17 words (ds, x_j[n-1], x_j[n-2]; input 0) raised to the segment's
@@ -1487,8 +1468,7 @@ int Engine::fmsq_alloc()
     fq_list.dev = fq_list_block; fq_pairs.dev = fq_list_block + (size_t)nch;
     if (int rc = alloc(fq_prm, nch)) return rc;
     if (int rc = alloc(fq_state, nch)) return rc;
-    if (int rc = alloc(mask_fq, kBandNfftMax)) return rc;
-    for (int i = 0; i < 2; i++) if (int rc = alloc(hist_fq[i], (long long)nch * kHistBand, true)) return rc;
+    if (int rc = fc_alloc(fc[FC_FQ])) return rc;
     // the ready delay (fmsq.c:153-154, tdelay 0.100: RXA.c:224): the additions of rstep that take ramp to tdelay, counted as they are made
     {
         const double rstep = 1.0 / rate, tdelay = 0.100;
@@ -1513,7 +1493,7 @@ int Engine::fmsq_alloc()
     QH_HIP(hipMemcpyAsync(fq_cdown, down.data(), down.size() * sizeof(double), hipMemcpyHostToDevice, stream));
     QH_HIP(hipStreamSynchronize(stream));
     fq_nc_built = 0;
-    for (ChanCfg &c : cfg) { c.fmsq_dirty = true; c.fmsq_hist_at = cur_fq; }
+    for (ChanCfg &c : cfg) c.fmsq_dirty = true;
     return QH_OK;
 }
 
@@ -1541,15 +1521,14 @@ int Engine::fmsq_filter()
 {
     if (!fq_prm || !fq_list.n) return QH_OK;
     const ChanCfg &c = cfg[(size_t)fq_h[0]];        // (chain_needs has refused FMSQ channels that differ)
-    const int nfft_key = 2 * bnfft + (band2g ? 1 : 0);
-    if (c.fmsq_nc == fq_nc_built && c.fmsq_mp == fq_mp_built && nfft_key == fq_nfft_built) return QH_OK;
+    if (c.fmsq_nc == fq_nc_built && c.fmsq_mp == fq_mp_built && fq_key_built == mask_key()) return QH_OK;
     std::vector<cd> h = fmsq_impulse(c.fmsq_nc, (double)dsp_rate, 1.0 / (2.0 * dsp_size));
     if (c.fmsq_mp) h = mp_imp(h, 16, 0);
     for (auto &v : h) v = cd(v.real() * (double)(2 * dsp_size), 0.0);
-    if (int rc = upload(mask_fq, band_mask(h), stream)) return rc;
-    if (fq_nc_built && fq_nc_built != c.fmsq_nc)       // setNc_fircore zeroes the delay line
-        for (int i = 0; i < 2; i++) QH_HIP(hipMemsetAsync(hist_fq[i], 0, (size_t)nch * kHistBand * sizeof(double2), stream));
-    fq_nc_built = c.fmsq_nc; fq_mp_built = c.fmsq_mp; fq_nfft_built = nfft_key;
+    std::vector<cd> m;
+    if (int rc = put_taps(fc[FC_FQ], 0, h, m)) return rc;
+    if (fq_nc_built && fq_nc_built != c.fmsq_nc) if (int rc = zero_rows(fc[FC_FQ], 0, nch)) return rc;       // setNc_fircore zeroes the delay line
+    fq_nc_built = c.fmsq_nc; fq_mp_built = c.fmsq_mp; fq_key_built = mask_key();
     return QH_OK;
 }
 
@@ -1569,9 +1548,8 @@ int Engine::eqp_alloc()
     if (int rc = quiesce()) return rc;
     if (int rc = alloc(eq_list_block, 2LL * nch)) return rc;
     eq_list.dev = eq_list_block; eq_rest.dev = eq_list_block + (size_t)nch;
-    if (int rc = alloc(mask_eqp, (long long)nch * kBandNfftMax)) return rc;
-    for (int i = 0; i < 2; i++) if (int rc = alloc(hist_eqp[i], (long long)nch * kHistBand, true)) return rc;
-    for (ChanCfg &c : cfg) { c.eqp_dirty = true; c.eqp_flush = false; c.eqp_hist_at = cur_eqp; }
+    if (int rc = fc_alloc(fc[FC_EQP])) return rc;
+    for (ChanCfg &c : cfg) { c.eqp_dirty = true; c.eqp_flush = false; }
     return QH_OK;
 }
 
@@ -1580,13 +1558,14 @@ int Engine::eqp_alloc()
 // (setImpulse_fircore(..., 1)); a channel that does not run the stage keeps its line where it was (xeqp, eq.c:204-207).
 int Engine::refresh_eqp()
 {
+    Fircore &eq = fc[FC_EQP];
     if (eq_lists_dirty) {
         eq_h.clear(); eq_rest_h.clear();
         for (int ch = 0; ch < nch; ch++) (cfg[(size_t)ch].eqp_run ? eq_h : eq_rest_h).push_back(ch);
-        if (!eq_h.empty() && !mask_eqp) if (int rc = eqp_alloc()) return rc;
-        eq_list.n = (int)eq_h.size(); eq_rest.n = mask_eqp ? (int)eq_rest_h.size() : 0;
-        if (mask_eqp) {
-            if (int rc = follow_rows(eq_listed, &ChanCfg::eqp_hist_at, cur_eqp, eq_h, { { hist_eqp, cur_eqp, kHistBand } })) return rc;
+        if (!eq_h.empty() && !eq.mask) if (int rc = eqp_alloc()) return rc;
+        eq_list.n = (int)eq_h.size(); eq_rest.n = eq.mask ? (int)eq_rest_h.size() : 0;
+        if (eq.mask) {
+            if (int rc = fc_follow(eq, eq_h)) return rc;
             std::vector<int> all((size_t)nch * 2, 0);
             std::copy(eq_h.begin(), eq_h.end(), all.begin());
             std::copy(eq_rest_h.begin(), eq_rest_h.end(), all.begin() + (size_t)nch);
@@ -1595,29 +1574,27 @@ int Engine::refresh_eqp()
         }
         eq_lists_dirty = false;
     }
-    if (!mask_eqp) return QH_OK;
-    const int nfft_key = 2 * bnfft + (band2g ? 1 : 0);
-    if (nfft_key != eq_nfft_built) { for (ChanCfg &c : cfg) c.eqp_dirty = true; eq_nfft_built = nfft_key; }
-    std::vector<cd> last, last_taps;
+    if (!eq.mask) return QH_OK;
+    if (eq_key_built != mask_key()) { for (ChanCfg &c : cfg) c.eqp_dirty = true; eq_key_built = mask_key(); }
+    std::vector<cd> last_h, last, last_taps;
     const ChanCfg *last_cfg = nullptr;
     if (eq_taps_h.size() != (size_t)nch) eq_taps_h.assign((size_t)nch, std::vector<cd>());
     for (int ch = 0; ch < nch; ch++) {
         ChanCfg &c = cfg[(size_t)ch];
         if (c.eqp_flush) {
-            double2 *const none[2] = { nullptr, nullptr };
-            if (int rc = zero_rows(hist_eqp, none, ch)) return rc;
+            if (int rc = zero_rows(eq, ch)) return rc;
             c.eqp_flush = false;
         }
         if (!c.eqp_run || !c.eqp_dirty) continue;       // (a channel that does not run keeps eqp_dirty until it does)
         const bool same = last_cfg && last_cfg->eqp_nc == c.eqp_nc && last_cfg->eqp_mp == c.eqp_mp && last_cfg->eqp_ctfmode == c.eqp_ctfmode &&
                           last_cfg->eqp_wintype == c.eqp_wintype && last_cfg->eqp_F == c.eqp_F && last_cfg->eqp_G == c.eqp_G;
         if (!same) {
-            std::vector<cd> h = last_taps = eqp_taps(c);
-            for (auto &v : h) v *= (double)(2 * dsp_size);      // the engine's mask convention, as fmsq_filter
-            last = band_mask(h);
+            last_h = last_taps = eqp_taps(c);
+            for (auto &v : last_h) v *= (double)(2 * dsp_size);      // the engine's mask convention, as fmsq_filter
+            last.clear();
             last_cfg = &c;
         }
-        if (int rc = put_mask(mask_eqp, ch, last)) return rc;
+        if (int rc = put_taps(eq, ch, last_h, last)) return rc;
         eq_taps_h[(size_t)ch] = last_taps;
         c.eqp_dirty = false;
     }
@@ -1635,15 +1612,11 @@ int Engine::flush()
     if (rsmpin) if (int rc = qh_rat_reset(rsmpin)) return rc;
     for (int i = 0; i < 2; i++) {
         if (hist_front[i]) QH_HIP(hipMemsetAsync(hist_front[i], 0, (size_t)nch * kHistFront * sizeof(double2), stream));
-        QH_HIP(hipMemsetAsync(hist_nbp[i], 0, (size_t)nch * kHistBand * sizeof(double2), stream));
-        QH_HIP(hipMemsetAsync(hist_bp1[i], 0, (size_t)nch * kHistBand * sizeof(double2), stream));
-        if (demod_alloc) {
-            QH_HIP(hipMemsetAsync(hist_de[i], 0, (size_t)nch * kHistBand * sizeof(double2), stream));
-            QH_HIP(hipMemsetAsync(hist_aud[i], 0, (size_t)nch * kHistBand * sizeof(double2), stream));
-        }
-        for (int sid = 0; sid < 5; sid++)
-            if (lhist[sid][i]) QH_HIP(hipMemsetAsync(lhist[sid][i], 0, (size_t)nch * kLongHist * sizeof(double2), stream));
     }
+    // the fircore stages that have been made: flush_nbp, flush_bandpass, flush_fmd, flush_bpsnba, flush_fmsq, flush_eqp (RXA.c:536-549).
+    // (bpsnba's short rows were left to snb_flush and the next refresh_params; that zeroes them on this stream ahead of the next call's
+    // launches, which nothing on the stream can tell from zeroing them here.)
+    for (Fircore &f : fc) if (f.hist[0]) if (int rc = zero_rows(f, 0, nch)) return rc;
     if (demod_alloc) {                        // flush_wcpagc zeroes the ring (wcpAGC.c:154-159)
         for (int c = 0; c < nch; c++) {
             QH_HIP(hipMemsetAsync(agc_state[c].ring, 0, sizeof(agc_state[c].ring), stream));
@@ -1657,12 +1630,10 @@ int Engine::flush()
             QH_HIP(hipMemsetAsync(agc_labs, 0, (size_t)nch * kAgcLongRing * sizeof(double), stream));
         }
     }
-    for (ChanCfg &c : cfg) { c.lms[0].flush = c.lms[1].flush = true; c.emnr_flush = true; c.snba_flush = true; c.snb_flush = true; }    // flush_anf / flush_anr / flush_emnr, RXA.c:541-543
+    for (ChanCfg &c : cfg) { c.lms[0].flush = c.lms[1].flush = true; c.emnr_flush = true; c.snba_flush = true; }    // flush_anf / flush_anr / flush_emnr, RXA.c:541-543
     if (amsq_state) QH_HIP(hipMemsetAsync(amsq_state, 0, (size_t)nch * sizeof(AmsqState), stream));     // flush_amsq
     if (ap_state) QH_HIP(hipMemsetAsync(ap_state, 0, (size_t)nch * kApW * sizeof(double), stream));    // flush_cbl / _speak / _mpeak, RXA.c:553-555
     if (ssql_state) launch_ssql_flush();        // flush_ssql, RXA.c:556
-    if (hist_eqp[0])                            // flush_eqp, RXA.c:545
-        for (int i = 0; i < 2; i++) QH_HIP(hipMemsetAsync(hist_eqp[i], 0, (size_t)nch * kHistBand * sizeof(double2), stream));
     if (snd_rows) QH_HIP(hipMemsetAsync(snd_rows, 0, (size_t)nch * (size_t)snd_cap * sizeof(float2), stream));       // flush_sender, RXA.c:538
     if (sip_ring) {                             // flush_siphon, RXA.c:552 (siphon.c:88-94)
         QH_HIP(hipMemsetAsync(sip_ring, 0, (size_t)nch * kSipSize * sizeof(double2), stream));
@@ -1670,10 +1641,7 @@ int Engine::flush()
     }
     if (gen_state)                              // flush_gen, RXA.c:534 (gen.c:160-163): the pulse's state machine alone
         hipLaunchKernelGGL(gen_flush_kernel, dim3((unsigned)((nch + 255) / 256)), dim3(256), 0, stream, nch, (const GenParam *)gen_prm, gen_state);
-    if (fq_state) {                             // flush_fmsq, RXA.c:544
-        for (int i = 0; i < 2; i++) QH_HIP(hipMemsetAsync(hist_fq[i], 0, (size_t)nch * kHistBand * sizeof(double2), stream));
-        launch_fmsq_flush();
-    }
+    if (fq_state) launch_fmsq_flush();          // flush_fmsq, RXA.c:544 (its noise filter's lines: above)
     if (demod_alloc) {                        // flush_amd / flush_fmd / flush_snotch
         QH_HIP(hipMemsetAsync(am_state, 0, (size_t)nch * sizeof(AmState), stream));
         QH_HIP(hipMemsetAsync(pll_state, 0, (size_t)nch * sizeof(PllState), stream));

@@ -241,9 +241,12 @@ int qh_rxa_RXASetNC(qh_rxa *h, int ch, int nc)
     if (nc < 1 || (nc & (nc - 1)) || nc > kLongNcMax || (h && nc < h->e.dsp_size))
         return set_error(QH_ERR_UNSUPPORTED, "nc must be a power of two in [dsp_size, %d]", kLongNcMax);
     FOR_CH(h, ch, {
-        if (c.nbp_nc != nc) { c.nbp_nc = nc; c.nbp_dirty = true; c.nbp_flush = true; c.snb_flush = true; c.long_live[0] = c.long_live[4] = false; }
-        if (c.bp1_nc != nc) { c.bp1_nc = nc; c.bp1_dirty = true; c.bp1_flush = true; c.long_live[1] = false; }
-        if (c.fm_nc != nc) c.long_live[2] = false;     // (setNc_fircore zeroes the delay lines, firmin.c:454-466: nothing long is held any more)
+        // (setNc_fircore zeroes the delay lines, firmin.c:454-466: nothing long is held any more)
+        Fircore *fc = h->e.fc;
+        const size_t i = (size_t)(&c - h->e.cfg.data());
+        if (c.nbp_nc != nc) { c.nbp_nc = nc; c.nbp_dirty = true; c.nbp_flush = true; c.snb_flush = true; fc[FC_NBP].chan[i].long_live = fc[FC_SNB].chan[i].long_live = false; }
+        if (c.bp1_nc != nc) { c.bp1_nc = nc; c.bp1_dirty = true; c.bp1_flush = true; fc[FC_BP1].chan[i].long_live = false; }
+        if (c.fm_nc != nc) fc[FC_DE].chan[i].long_live = fc[FC_AUD].chan[i].long_live = false;
         c.fm_nc = nc;                           // SetRXAFMNCde / SetRXAFMNCaud, wdsp/RXA.c:943-944
         c.fmsq_nc = nc;                         // SetRXAFMSQNC, wdsp/RXA.c:942
         if (c.eqp_nc != nc) { c.eqp_nc = nc; c.eqp_dirty = true; c.eqp_flush = true; }      // SetRXAEQNC, wdsp/RXA.c:941
@@ -988,7 +991,7 @@ int qh_rxa_debug_eqp(qh_rxa *h, int ch, double *taps, int max)
     Engine &e = h->e;
     if (ch < 0 || ch >= e.nch) return set_error(QH_ERR_INVALID, "channel %d out of range", ch);
     const ChanCfg &c = e.cfg[(size_t)ch];
-    if (!e.mask_eqp || !taps) return 0;
+    if (!e.fc[FC_EQP].mask || !taps) return 0;
     const bool held = (size_t)ch < e.eq_taps_h.size() && !e.eq_taps_h[(size_t)ch].empty();
     if (!held && c.eqp_nc > kLongPart) return 0;
     const std::vector<cd> t = held ? e.eq_taps_h[(size_t)ch] : e.eqp_taps(c);

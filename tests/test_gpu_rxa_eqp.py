@@ -8,7 +8,10 @@ The whole-chain oracle has no equalizer, so two identities make the reference (t
   pre-filter: with the shift off and in_rate = dsp_rate = out_rate, everything ahead of xeqp in an SSB chain is linear and time-invariant
       at the dsp rate, so engine(EQ on)(x) = oracle(EQ off)(EQ_ref(x)), whatever follows the equalizer (AGC, ANF).
 
-Calls of (1, 3, 9, 1, 40, 17, 2) blocks of 256 dsp samples: less than a tile, across the 2049-output tile of nc 2048, many tiles."""
+Calls of (1, 3, 9, 1, 40, 17, 2) blocks of 256 dsp samples: less than a tile, across the 2049-output tile of nc 2048, many tiles.
+
+A channel that sits the stage out while another keeps the stage's ping-pong pair flipping is held against the whole-chain reference
+(tests/rxa_chain_ref.py) on both paths: test_equalizer_keeps_its_delay_line_while_a_channel_sits_it_out."""
 import numpy as np
 import pytest
 
@@ -303,3 +306,76 @@ def test_refusals(qh):
         assert np.array_equal(ya, n.process_host(blk[5])) and np.all(np.isfinite(ya.view(np.float64))) and np.any(ya[1])
     finally:
         a.close(); n.close()
+
+
+SIT_BLOCKS, SIT_BEFORE, SIT_AFTER = 3, 3, 2       # blocks a call; calls channel 1 runs the stage before it sits out, and from its return on
+
+
+def _sit_out(e, sat, per_mode):
+    """Two USB channels at the default sizes, a fixed gain (channel 0: AGC mode 3 where the per-mode path is asked for), the equalizer on in
+    both; channel 1 switches it off for `sat` calls after SIT_BEFORE calls and on again.  e: the engine, or None for the references alone.
+    Against the whole-chain reference (tests/rxa_chain_ref.py), whose xeqp keeps its line while run is 0 (eq.c:204-207).  Returns the
+    engine's calls (or None), the references' calls, and channel 1's call of return from a reference whose line was zeroed there."""
+    from rxa_chain_ref import RxaChainRef
+    refs, lost = [RxaChainRef(), RxaChainRef()], RxaChainRef()
+
+    def both(name, c, *a):
+        for t, lead in ((e, (c,)), (refs[c], ())) + (((lost, ()),) if c == 1 else ()):
+            if t is not None:
+                getattr(t, name)(*lead, *a)
+
+    for c in range(2):
+        both("SetRXAShiftRun", c, 1); both("SetRXAShiftFreq", c, synth.shift_freq(c)); both("RXANBPSetRun", c, 1)
+        both("SetRXAMode", c, USB); both("RXASetPassband", c, 150.0, 4000.0)
+        both("SetRXAAGCMode", c, 3 if per_mode and c == 0 else 0); both("SetRXAAGCFixed", c, 10.0)
+        both("SetRXAEQRun", c, 1)
+    both("SetRXAGrphEQ10", 0, G10); both("SetRXAEQProfile", 1, *P3)
+    ncalls, n = SIT_BEFORE + sat + SIT_AFTER, SIT_BLOCKS * 1024
+    t = np.arange(ncalls * n) / 192000.0
+    # a steady two-tone inside the passband (USB takes the input's negative side) on each channel's carrier: 768 dsp samples a call, well
+    # inside the 2047-sample line
+    x = np.stack([(0.2 * np.exp(-2j * np.pi * (((600.0 + 100 * c) * t) % 1.0)) + 0.15 * np.exp(-2j * np.pi * (((1700.0 + 150 * c) * t) % 1.0)))
+                  * np.exp(-2j * np.pi * ((synth.shift_freq(c) * t) % 1.0)) for c in range(2)])
+    ys, rs, lost_back = [], [], None
+    for k in range(ncalls):
+        if k == SIT_BEFORE:
+            both("SetRXAEQRun", 1, 0)
+        if k == SIT_BEFORE + sat:
+            both("SetRXAEQRun", 1, 1)
+            lost.eqp.delay[:] = 0.0
+        seg = np.ascontiguousarray(x[:, k * n:(k + 1) * n])
+        if e is not None:
+            ys.append(e.process_host(seg))
+        rs.append(np.stack([r.xrxa(seg[c]) for c, r in enumerate(refs)]))
+        back = lost.xrxa(seg[1])
+        if k == SIT_BEFORE + sat:
+            lost_back = back
+    for r in refs + [lost]:
+        r.close()
+    return ys or None, rs, lost_back
+
+
+@pytest.mark.parametrize("path", ["linear", "per_mode"])
+@pytest.mark.parametrize("sat", [1, 2])
+def test_equalizer_keeps_its_delay_line_while_a_channel_sits_it_out(qh, sat, path):
+    """Channel 0 runs the equalizer throughout, so the stage's ping-pong pair flips on every call; channel 1 runs it for three calls, sits
+    out `sat` calls (an odd and an even number of flips) and runs it again: its first call back is gated on its own, channel 0 over the
+    run, 1e-6 relative RMS (the whole-chain reference's gate, tests/test_gpu_rxa_stage_combinations.py).  On the linear path and on the
+    per-mode one (AGC mode 3 on channel 0).  First the reference's own sensitivity: with the line zeroed at the return the call of
+    return differs by more than 1e-3 (it does by 1.0: the 768 samples of a call do not reach the centre tap of the 2048)."""
+    e = qh.RxaEngine(2)
+    try:
+        ys, rs, lost_back = _sit_out(e, sat, path == "per_mode")
+    finally:
+        e.close()
+    back = SIT_BEFORE + sat
+    sens = rel_rms(lost_back, rs[back][1])
+    print("sat out %d, %s: a lost line changes the call of return by %.3g relative RMS" % (sat, path, sens))
+    assert sens > 1e-3, sens
+    per = ["%.1e/%.1e" % (rel_rms(y[0], r[0]), rel_rms(y[1], r[1])) for y, r in zip(ys, rs)]
+    e_back = rel_rms(ys[back][1], rs[back][1])
+    e0 = rel_rms(np.concatenate([y[0] for y in ys]), np.concatenate([r[0] for r in rs]))
+    e1 = rel_rms(np.concatenate([y[1] for y in ys]), np.concatenate([r[1] for r in rs]))
+    print("channel 1's call of return %.3g; over the run: channel 0 %.3g, channel 1 %.3g; per call (channel 0/channel 1) %r" % (e_back, e0, e1, per))
+    assert e_back < 1e-6, (e_back, per)
+    assert e0 < 1e-6 and e1 < 1e-6, (e0, e1, per)

@@ -14,8 +14,8 @@ closer than 1e-3 to an integer (test_gpu_rxa_fmsq.py's figures).
 
 DEFECT FOUND AND FIXED, by `fmsq beside bp1`: a channel whose bp1 was forced on by SetRXABandpassRun while every channel of the engine was
 a linear chain (Engine::run_linear) lost bp1's delay line in the call in which other channels took the engine to the per-mode path.
-run_linear flips bp1's ping-pong pair, but the record of which half holds a channel's line (bp1_listed / bp1_hist_at) was kept on the
-per-mode path only, so after an odd number of linear calls the first per-mode call copied the stale half over the current one.  Seen on
+run_linear flips bp1's ping-pong pair, but the record of which half holds a channel's line (Fircore::Chan, then two loose members) was
+kept on the per-mode path only, so after an odd number of linear calls the first per-mode call copied the stale half over the current one.  Seen on
 the MI355X before the fix, channel 1 of (USB, USB, USB) with a fixed gain, channels 0 and 2 set to FM before call 3 of (1, 3, 9, 1, 40, 17,
 2, 11, 5, 25): rms error / rms of the reference per call 6.8e-14 / 0.82 (call 2), 1.1 / 1.1 (call 3, the first on the per-mode path), 0.31 /
 1.1 (call 4), 2.0e-12 / 1.1 from call 5 on; 0.194 over the run.  The same with and without the FM squelch, and with AM in FM's place.
