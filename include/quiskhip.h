@@ -410,6 +410,21 @@ void SetEXTNOBThreshold(int id, double thresh);                                 
 /* xnobEXT for buffsize samples in device memory (d_in == d_out allowed): enqueued on the id's stream, which is ordered behind `stream`
  * on entry; `stream` is ordered behind it on return.  Nothing is waited for.  The same samples as xnobEXT, bit for bit. */
 int qh_wdsp_xnobEXT_device(int id, const void *d_in, void *d_out, void *stream);
+/* The variable-ratio resampler WDSP's callers put behind fexchange0 (wdsp/varsamp.c:228-250): every pointer a one-channel qh_varsamp
+ * bank (section 10d) with run 1, fc 0, fc_low -1, gain 1, var 1 and varmode 1, as create_varsampV fixes them, on a stream and with an
+ * input staging row of its own, so input == output works.  input / output are host pointers; output needs room for the samples the
+ * call makes (about numsamps * var * out_rate / in_rate, at most qh_wdsp_varsampV_max_out), as the reference's does.  Errors (a
+ * pointer that create_varsampV did not return, a refused value: see qh_varsamp_create) go to qh_wdsp_status(), change nothing and
+ * report *outsamps = 0; create_varsampV then returns null.  Not provided: rmatch.c (create_rmatchV, xrmatchIN, xrmatchOUT ...), which
+ * is host threading around this call. */
+void *create_varsampV(int in_rate, int out_rate, int R);                         /* wdsp/varsamp.c:230-234 */
+void xvarsampV(double *input, double *output, int numsamps, double var, int *outsamps, void *ptr);  /* wdsp/varsamp.c:236-244 */
+void destroy_varsampV(void *ptr);                                                /* wdsp/varsamp.c:246-250 */
+long long qh_wdsp_varsampV_max_out(void *ptr, int numsamps, double var);         /* qh_varsamp_max_out of the pointer's bank */
+/* xvarsampV for numsamps samples in device memory (d_in == d_out allowed; d_out with room for qh_wdsp_varsampV_max_out samples;
+ * d_count: device, one int): enqueued on the pointer's stream, which is ordered behind `stream` on entry; `stream` is ordered behind
+ * it on return.  Nothing is waited for.  The same samples and count as xvarsampV, bit for bit. */
+int qh_wdsp_xvarsampV_device(void *ptr, const void *d_in, void *d_out, int numsamps, double var, int *d_count, void *stream);
 /* Quisk's re-blocking shim around fexchange0 (quisk_wdsp.c:24-69): any nSamples in, scaled by 1/CLIP32 into
  * in_size blocks, results scaled back; returns the number of samples written to cSamples.  qh_wdsp_set_parameter
  * is the C form of quisk_wdsp_set_parameter (quisk_wdsp.c:71-91; in_size <= 0 / in_use < 0 leave the value).  One deviation: a CHANGE
@@ -846,6 +861,55 @@ int qh_nob_flush(qh_nob *b, int ch);                                            
 int qh_nob_process(qh_nob *b, const void *d_in, long long in_stride, void *d_out, long long out_stride, int n);
 int qh_nob_process_host(qh_nob *b, const void *h_in, long long in_stride, void *h_out, long long out_stride, int n);
 int qh_nob_synchronize(qh_nob *b);
+/* ------------------------------------------------------------------ 10d. WDSP's variable-ratio resampler (VARSAMP) */
+/* xvarsamp (wdsp/varsamp.c:124-179) for `nch` fp64 complex streams, where WDSP's callers run it: behind fexchange0, between the
+ * receiver's audio and a sound device whose clock is not the radio's (rmatch.c is built on it).  Every call takes n input samples and a
+ * ratio correction `var` per channel and produces about n * var * out_rate / in_rate samples: the count of every channel comes back
+ * with the samples.  Every channel has its own design (rates, R, band edges, gain), varmode, run and state; channels with the same
+ * design share one copy of the R-times oversampled prototype h (calc_varsamp, varsamp.c:29-68: rsize = (int)(140 * norm_rate /
+ * min_rate) taps per output, ncoef = rsize * R + 1 coefficients).  fc = 0 selects 0.95 * 0.45 * min_rate and fc_low < 0 selects -fc
+ * (varsamp.c:52-57).  varmode 1 slides 1 / (var * nom_ratio) linearly from the previous call's value to this call's over the n samples,
+ * varmode 0 steps it (varsamp.c:133-138).
+ * A call is two kernels.  The control recurrence (inv_cvar, h_offset and isamps, varsamp.c:148-160,170-172) does not read the samples:
+ * one lane per channel walks it, statement for statement in IEEE doubles, and leaves for every output sample the input sample it is
+ * made at and the h_offset in force, and the channel's count.  The counts and the offsets are therefore the reference's bit for bit.
+ * The filter kernel then makes every output sample on its own: the rsize coefficients interpolated between neighbours of h (hshift,
+ * varsamp.c:112-122) times the newest rsize inputs, summed in the reference's order in fp64 (products may be fused).  The last
+ * rsize - 1 inputs of every channel are kept behind the call, so n may be smaller than rsize.  run = 0 copies the n samples and
+ * reports n; inv_cvar still follows the call's var, as in the reference (varsamp.c:129-138 stand in front of `if (a->run)`).
+ * n = 0 is accepted and produces nothing: with varmode 0 inv_cvar takes the call's value, with varmode 1 it keeps the previous one (the
+ * reference divides by size there, and keeps old_inv_cvar whatever the quotient is); nothing else moves.
+ * Refused with QH_ERR_INVALID, state untouched: rates <= 0; a rate ratio beyond 16 either way (rsize > 2240); R < 1; ncoef above
+ * 4194304; a gain, fc or fc_low that is not finite; a var that is not finite or lies outside [0.5, 2] (the reference never checks, and
+ * its loop does not end for var <= 0); an out_stride below qh_varsamp_max_out(b, n, var); output rows that share a byte with the input
+ * rows.  Setters: ch = -1 means every channel; they take effect at the next process call.  Every channel holds 2240 samples of history
+ * twice (70 KB), whatever its rsize.
+ * Not provided: rmatch.c.  Its ring, its control loop and xrmatchIN / xrmatchOUT are host threading on top of this call. */
+typedef struct qh_varsamp qh_varsamp;
+qh_varsamp *qh_varsamp_create(int device, int nch, int in_rate, int out_rate, int R, double fc, double fc_low, double gain, double var,
+                              int varmode, void *stream);                        /* create_varsamp + calc_varsamp, varsamp.c:29-96; run = 1 */
+void qh_varsamp_destroy(qh_varsamp *b);                                          /* varsamp.c:98-102 */
+int qh_varsamp_flush(qh_varsamp *b, int ch);                                     /* flush_varsamp, varsamp.c:104-110: keeps inv_cvar */
+int qh_varsamp_set_run(qh_varsamp *b, int ch, int run);                          /* resets nothing (varsamp.c:139,176) */
+int qh_varsamp_set_varmode(qh_varsamp *b, int ch, int varmode);                  /* resets nothing (varsamp.c:133) */
+/* setInRate_varsamp and setOutRate_varsamp, varsamp.c:193-205: calc_varsamp, which designs h again, empties the history, zeroes
+ * h_offset and isamps and sets inv_cvar to 1 / (var * nom_ratio) with the var of the last call */
+int qh_varsamp_set_rates(qh_varsamp *b, int ch, int in_rate, int out_rate);
+/* setBandwidth_varsamp, varsamp.c:217-226: calc_varsamp as above, but only for a channel whose fc_low or fc_high changes */
+int qh_varsamp_set_bandwidth(qh_varsamp *b, int ch, double fc_low, double fc_high);
+int qh_varsamp_rsize(qh_varsamp *b, int ch);                                     /* rsize, varsamp.c:58: the taps of one output sample */
+int qh_varsamp_synchronize(qh_varsamp *b);
+/* The largest count the next call of n samples with these var (host, [nch]) could report on any channel: a bound from every channel's
+ * earlier and new 1 / (var * nom_ratio), not the count itself (that hangs on state in device memory).  Negative: a qh_status. */
+long long qh_varsamp_max_out(qh_varsamp *b, int n, const double *var);
+/* xvarsamp (varsamp.c:124-179) over n >= 0 input samples of every channel: device rows [nch][stride] of interleaved complex doubles,
+ * strides in complex samples, out_stride >= qh_varsamp_max_out(b, n, var); var: host, [nch], read before the call returns; d_count:
+ * device, int[nch], the samples written to every output row (may be null).  Nothing is written behind a row's count.  Asynchronous on
+ * the bank's stream.  The _host form (synchronous, pageable memory; h_count host, int[nch]) takes h_out == h_in. */
+int qh_varsamp_process(qh_varsamp *b, const void *d_in, long long in_stride, void *d_out, long long out_stride, int n, const double *var,
+                       int *d_count);
+int qh_varsamp_process_host(qh_varsamp *b, const void *h_in, long long in_stride, void *h_out, long long out_stride, int n,
+                            const double *var, int *h_count);
 /* dAutoNotch (quisk.c:786-963; 8(f) rank 3) inside the receiver bank, where the mode calls it (on the real audio after
  * the Rx filter; after the interpolators for FM; DGT-IQ has none): set_auto_notch(i) (quisk.c:4596) -- stores the flag
  * and starts the notch over -- with rit_freq as set_sidetone passes it (quisk.c:4712): the CW modes keep the notch off

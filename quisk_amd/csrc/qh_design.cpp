@@ -74,6 +74,33 @@ ResamplerDesign design_resampler(int in_rate, int out_rate, double fc, int ncoef
     return d;
 }
 
+// calc_varsamp's sizes, wdsp/varsamp.c:40-51,58-60
+void varsamp_sizes(int in_rate, int out_rate, int R, int *rsize, long long *ncoef)
+{
+    const double min_rate = out_rate >= in_rate ? (double)in_rate : (double)out_rate;
+    const double norm_rate = out_rate >= in_rate ? min_rate : (double)in_rate;
+    *rsize = (int)(140.0 * norm_rate / min_rate);
+    *ncoef = (long long)*rsize * R + 1;
+}
+
+VarsampDesign design_varsamp(int in_rate, int out_rate, int R, double fc, double fc_low, double gain)
+{
+    VarsampDesign d;
+    d.nom_ratio = (double)out_rate / (double)in_rate;
+    const double min_rate = out_rate >= in_rate ? (double)in_rate : (double)out_rate;
+    const double norm_rate = out_rate >= in_rate ? min_rate : (double)in_rate;
+    if (fc == 0.0) fc = 0.95 * 0.45 * min_rate;
+    const double fc_norm_high = fc / norm_rate;
+    const double fc_norm_low = fc_low < 0.0 ? -fc_norm_high : fc_low / norm_rate;
+    long long ncoef;
+    varsamp_sizes(in_rate, out_rate, R, &d.rsize, &ncoef);
+    d.ncoef = (int)ncoef;
+    const std::vector<cd> imp = fir_bandpass(d.ncoef, fc_norm_low, fc_norm_high, (double)R, 1, 0, (double)R * gain);
+    d.h.resize((size_t)d.ncoef);
+    for (int i = 0; i < d.ncoef; i++) d.h[(size_t)i] = imp[(size_t)i].real();
+    return d;
+}
+
 static std::vector<double> fsamp_window(int N, int wintype)
 {
     std::vector<double> w((size_t)N, 1.0);

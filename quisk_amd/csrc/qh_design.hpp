@@ -21,6 +21,14 @@ std::vector<cd> fir_bandpass(int N, double f_low, double f_high, double samplera
 struct ResamplerDesign { int L, M, ncoef, cpp; std::vector<double> h; };
 ResamplerDesign design_resampler(int in_rate, int out_rate, double fc, int ncoef, double gain);
 
+// WDSP variable-ratio resampler prototype, calc_varsamp (wdsp/varsamp.c:29-68): nom_ratio = out_rate / in_rate, rsize = (int)(140 *
+// norm_rate / min_rate) taps per output sample, and the R-times oversampled low-pass h of ncoef = rsize * R + 1 real coefficients
+// (fir_bandpass at samplerate R, 7-term window, scale R * gain).  fc = 0 selects 0.95 * 0.45 * min_rate, fc_low < 0 selects -fc.
+// Rates and R must be positive (the caller checks, and caps ncoef).
+struct VarsampDesign { double nom_ratio; int rsize, ncoef; std::vector<double> h; };
+void varsamp_sizes(int in_rate, int out_rate, int R, int *rsize, long long *ncoef);
+VarsampDesign design_varsamp(int in_rate, int out_rate, int R, double fc, double fc_low, double gain);
+
 // WDSP FM de-emphasis curve by frequency sampling, wdsp/fcurve.c:29-145 + fir.c:129-185 (even nc).
 std::vector<cd> fc_impulse(int nc, double f0, double f1, double g0, double g1, int curve, double samplerate,
                            double scale, int ctfmode, int wintype);

@@ -64,6 +64,8 @@ static inline bool rows_overlap(const void *a, long long a_stride_bytes, long lo
 // lets create_anbEXT / create_nobEXT tell refused settings from a device that failed
 int anb_check_settings(double samplerate, double tau, double hangtime, double advtime, double backtau, double threshold);
 int nob_check_settings(double samplerate, int mode, double slewtime, double hangtime, double advtime, double backtau, double threshold);
+// the same for qh_varsamp_create (qh_varsamp.hip) and create_varsampV
+int varsamp_check_settings(int in_rate, int out_rate, int R, double fc, double fc_low, double gain);
 
 // The display bank behind a WDSP display id (XCreateAnalyzer), held until wdsp_display_release: DestroyAnalyzer waits (qh_analyzer.hip)
 qh_ana *wdsp_display_hold(int disp);

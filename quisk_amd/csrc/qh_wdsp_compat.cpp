@@ -9,6 +9,7 @@
 // bfo = 1 the caller blocks until output is available, so in sample terms the behaviour is
 // deterministic: output lags input by (DSP_MULT-1)*r2_size + dsp_outsize samples.  The same
 // sequence is executed here synchronously on the calling thread.
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -1260,5 +1261,154 @@ void SetEXTNOBHangtime(int id, double time) { EXT_SETTER(NobExt, qh_nob_set_hang
 void SetEXTNOBAdvtime(int id, double time) { EXT_SETTER(NobExt, qh_nob_set_advtime(L.a->b, 0, time)); }
 void SetEXTNOBBacktau(int id, double tau) { EXT_SETTER(NobExt, qh_nob_set_backtau(L.a->b, 0, tau)); }
 void SetEXTNOBThreshold(int id, double thresh) { EXT_SETTER(NobExt, qh_nob_set_threshold(L.a->b, 0, thresh)); }
+
+}  // extern "C"
+
+// ---- the variable-ratio resampler behind fexchange0: create_varsampV, xvarsampV, destroy_varsampV (wdsp/varsamp.c:228-250) ---------------
+// Every pointer a one-channel bank on a stream of its own, with an input staging row that lets input == output, an output staging row
+// for the host form and the count in device memory.  The reference hands out its VARSAMP; here the pointer is looked up in a table, so
+// one that create_varsampV did not return is refused instead of followed.
+namespace {
+struct VarsampV {
+    qh_varsamp *b = nullptr;
+    hipStream_t stream = nullptr;
+    double *d_in = nullptr, *d_out = nullptr;
+    long long cap_in = 0, cap_out = 0;
+    int *d_count = nullptr;
+    hipEvent_t ev_in = nullptr, ev_out = nullptr;
+    std::mutex mtx;
+};
+std::mutex g_vsv_mtx;
+std::vector<VarsampV *> g_vsv;
+
+void vsv_release(VarsampV *a)
+{
+    if (a->b) qh_varsamp_destroy(a->b);         // (waits for the stream)
+    (void)hipFree(a->d_in); (void)hipFree(a->d_out); (void)hipFree(a->d_count);
+    if (a->ev_in) (void)hipEventDestroy(a->ev_in);
+    if (a->ev_out) (void)hipEventDestroy(a->ev_out);
+    if (a->stream) (void)hipStreamDestroy(a->stream);
+    delete a;
+}
+
+VarsampV *vsv_find(void *ptr, const char *name)
+{
+    g_status = QH_OK;
+    std::lock_guard<std::mutex> lk(g_vsv_mtx);
+    for (VarsampV *a : g_vsv)
+        if (a == ptr) return a;
+    g_status = qh::set_error(QH_ERR_INVALID, "%s: not a pointer create_varsampV returned", name);
+    return nullptr;
+}
+
+int vsv_row(VarsampV &a, double **row, long long *cap, long long want, const char *name)
+{
+    if (want <= *cap) return QH_OK;
+    if (hipStreamSynchronize(a.stream) != hipSuccess) return qh::set_error(QH_ERR_HIP, "%s: synchronize failed", name);
+    (void)hipFree(*row);
+    *row = nullptr; *cap = 0;
+    want += want / 8 + 64;
+    if (hipMalloc((void **)row, (size_t)want * 16) != hipSuccess) { *row = nullptr; return qh::set_error(QH_ERR_HIP, "%s: staging allocation failed", name); }
+    *cap = want;
+    return QH_OK;
+}
+}  // namespace
+
+extern "C" {
+
+void *create_varsampV(int in_rate, int out_rate, int R)
+{
+    g_status = QH_OK;
+    if (int rc = qh::varsamp_check_settings(in_rate, out_rate, R, 0.0, -1.0, 1.0)) { g_status = rc; return nullptr; }
+    VarsampV *a = new VarsampV();
+    if (hipStreamCreateWithFlags(&a->stream, hipStreamNonBlocking) != hipSuccess) {
+        a->stream = nullptr;
+        g_status = qh::set_error(QH_ERR_NO_DEVICE, "create_varsampV: no HIP device (libquiskhip has no CPU fallback)");
+        vsv_release(a);
+        return nullptr;
+    }
+    a->b = qh_varsamp_create(0, 1, in_rate, out_rate, R, 0.0, -1.0, 1.0, 1.0, 1, a->stream);       // varsamp.c:233
+    if (!a->b) { g_status = QH_ERR_HIP; vsv_release(a); return nullptr; }     // the settings were good: the device (message already set)
+    if (hipMalloc((void **)&a->d_count, sizeof(int)) != hipSuccess) {
+        a->d_count = nullptr;
+        g_status = qh::set_error(QH_ERR_HIP, "create_varsampV: allocation failed");
+        vsv_release(a);
+        return nullptr;
+    }
+    std::lock_guard<std::mutex> lk(g_vsv_mtx);
+    g_vsv.push_back(a);
+    return a;
+}
+
+void destroy_varsampV(void *ptr)
+{
+    VarsampV *a = vsv_find(ptr, "destroy_varsampV");
+    if (!a) return;
+    {
+        std::lock_guard<std::mutex> lk(g_vsv_mtx);
+        g_vsv.erase(std::find(g_vsv.begin(), g_vsv.end(), a));
+    }
+    { std::lock_guard<std::mutex> lk(a->mtx); }
+    vsv_release(a);
+}
+
+long long qh_wdsp_varsampV_max_out(void *ptr, int numsamps, double var)
+{
+    VarsampV *a = vsv_find(ptr, "qh_wdsp_varsampV_max_out");
+    if (!a) return g_status;
+    const long long mo = qh_varsamp_max_out(a->b, numsamps, &var);
+    if (mo < 0) g_status = (int)mo;
+    return mo;
+}
+
+void xvarsampV(double *input, double *output, int numsamps, double var, int *outsamps, void *ptr)
+{
+    if (outsamps) *outsamps = 0;
+    VarsampV *a = vsv_find(ptr, "xvarsampV");
+    if (!a) return;
+    std::lock_guard<std::mutex> lk(a->mtx);
+    if (!outsamps || numsamps < 0 || (numsamps > 0 && (!input || !output))) { g_status = qh::set_error(QH_ERR_INVALID, "xvarsampV: bad arguments"); return; }
+    const long long mo = qh_varsamp_max_out(a->b, numsamps, &var);
+    if (mo < 0) { g_status = (int)mo; return; }
+    if (int rc = vsv_row(*a, &a->d_in, &a->cap_in, numsamps, "xvarsampV")) { g_status = rc; return; }
+    if (int rc = vsv_row(*a, &a->d_out, &a->cap_out, mo, "xvarsampV")) { g_status = rc; return; }
+    if (numsamps > 0 && hipMemcpyAsync(a->d_in, input, (size_t)numsamps * 16, hipMemcpyHostToDevice, a->stream) != hipSuccess) {
+        g_status = qh::set_error(QH_ERR_HIP, "xvarsampV: upload failed");
+        return;
+    }
+    if (int rc = qh_varsamp_process(a->b, a->d_in, std::max(numsamps, 1), a->d_out, std::max<long long>(mo, 1), numsamps, &var, a->d_count)) { g_status = rc; return; }
+    int count = 0;
+    if (hipMemcpyAsync(&count, a->d_count, sizeof(int), hipMemcpyDeviceToHost, a->stream) != hipSuccess || hipStreamSynchronize(a->stream) != hipSuccess) {
+        g_status = qh::set_error(QH_ERR_HIP, "xvarsampV: download failed");
+        return;
+    }
+    if (count > 0 && (hipMemcpyAsync(output, a->d_out, (size_t)count * 16, hipMemcpyDeviceToHost, a->stream) != hipSuccess ||
+                      hipStreamSynchronize(a->stream) != hipSuccess)) {
+        g_status = qh::set_error(QH_ERR_HIP, "xvarsampV: download failed");
+        return;
+    }
+    *outsamps = count;
+}
+
+int qh_wdsp_xvarsampV_device(void *ptr, const void *d_in, void *d_out, int numsamps, double var, int *d_count, void *stream)
+{
+    VarsampV *a = vsv_find(ptr, "qh_wdsp_xvarsampV_device");
+    if (!a) return g_status;
+    std::lock_guard<std::mutex> lk(a->mtx);
+    if (numsamps < 0 || !d_count || (numsamps > 0 && (!d_in || !d_out))) return g_status = qh::set_error(QH_ERR_INVALID, "qh_wdsp_xvarsampV_device: bad arguments");
+    const long long mo = qh_varsamp_max_out(a->b, numsamps, &var);
+    if (mo < 0) return g_status = (int)mo;
+    if (int rc = vsv_row(*a, &a->d_in, &a->cap_in, numsamps, "qh_wdsp_xvarsampV_device")) return g_status = rc;
+    hipStream_t cs = (hipStream_t)stream;
+    if (!a->ev_in && (hipEventCreateWithFlags(&a->ev_in, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&a->ev_out, hipEventDisableTiming) != hipSuccess))
+        return g_status = qh::set_error(QH_ERR_HIP, "qh_wdsp_xvarsampV_device: event creation failed");
+    if (cs != a->stream) { (void)hipEventRecord(a->ev_in, cs); (void)hipStreamWaitEvent(a->stream, a->ev_in, 0); }
+    int rc = QH_OK;
+    if (numsamps > 0 && hipMemcpyAsync(a->d_in, d_in, (size_t)numsamps * 16, hipMemcpyDeviceToDevice, a->stream) != hipSuccess)
+        rc = qh::set_error(QH_ERR_HIP, "qh_wdsp_xvarsampV_device: copy failed");
+    if (!rc) rc = qh_varsamp_process(a->b, a->d_in, std::max(numsamps, 1), d_out, std::max<long long>(mo, 1), numsamps, &var, d_count);
+    if (cs != a->stream) { (void)hipEventRecord(a->ev_out, a->stream); (void)hipStreamWaitEvent(cs, a->ev_out, 0); }
+    return g_status = rc;
+}
 
 }  // extern "C"

@@ -321,6 +321,31 @@ def load():
                 [["SetEXT%s%s" % (B, n), [i, d]] for n in ("Tau", "Hangtime", "Advtime", "Backtau", "Threshold")]:
             getattr(L, n).argtypes = a
             getattr(L, n).restype = None
+    # WDSP's variable-ratio resampler (wdsp/varsamp.c): the bank and the V names behind fexchange0
+    L.qh_varsamp_create.restype = vp
+    L.qh_varsamp_create.argtypes = [i, i, i, i, i, d, d, d, d, i, vp]
+    L.qh_varsamp_destroy.argtypes = [vp]
+    L.qh_varsamp_destroy.restype = None
+    for n in ("flush", "rsize"):
+        getattr(L, "qh_varsamp_" + n).argtypes = [vp, i]
+    for n in ("set_run", "set_varmode"):
+        getattr(L, "qh_varsamp_" + n).argtypes = [vp, i, i]
+    L.qh_varsamp_set_rates.argtypes = [vp, i, i, i]
+    L.qh_varsamp_set_bandwidth.argtypes = [vp, i, d, d]
+    L.qh_varsamp_synchronize.argtypes = [vp]
+    L.qh_varsamp_max_out.argtypes = [vp, i, vp]
+    L.qh_varsamp_max_out.restype = ll
+    L.qh_varsamp_process.argtypes = [vp, vp, ll, vp, ll, i, vp, vp]
+    L.qh_varsamp_process_host.argtypes = [vp, vp, ll, vp, ll, i, vp, vp]
+    L.create_varsampV.restype = vp
+    L.create_varsampV.argtypes = [i, i, i]
+    L.xvarsampV.argtypes = [vp, vp, i, d, C.POINTER(i), vp]
+    L.xvarsampV.restype = None
+    L.destroy_varsampV.argtypes = [vp]
+    L.destroy_varsampV.restype = None
+    L.qh_wdsp_varsampV_max_out.argtypes = [vp, i, d]
+    L.qh_wdsp_varsampV_max_out.restype = ll
+    L.qh_wdsp_xvarsampV_device.argtypes = [vp, vp, vp, i, d, vp, vp]
     L.qh_qrx_set_noise_blanker.argtypes = [vp, i]
     L.qh_qrx_set_auto_notch.argtypes = [vp, i, i]
     L.qh_quisk_set_auto_notch.argtypes = [i, i]

@@ -405,3 +405,82 @@ class WdspNoiseBlanker2(_WdspBlankerBank):
 
     def set_mode(self, mode, ch=-1):
         check(self._c("set_mode")(self._h, ch, int(mode)))
+
+
+class WdspVarResampler:
+    """WDSP's variable-ratio resampler VARSAMP (xvarsamp, wdsp/varsamp.c:124-179) for `nch` streams, every channel with its own design,
+    varmode, run and state; keyword names as create_varsamp's.  A call takes n input samples and one ratio correction `var` per channel
+    and makes about n * var * out_rate / in_rate samples of every channel: the counts come back with the samples.  The setters take a
+    channel, or -1 for every channel."""
+
+    def __init__(self, nch, in_rate, out_rate, R=1024, fc=0.0, fc_low=-1.0, gain=1.0, var=1.0, varmode=1, device=0, stream=None):
+        self._L = load()
+        self._h = self._L.qh_varsamp_create(device, nch, int(in_rate), int(out_rate), int(R), fc, fc_low, gain, var, int(varmode), stream)
+        if not self._h:
+            raise QuiskHipError("qh_varsamp_create failed: %s" % self._L.qh_last_error().decode(errors="replace"))
+        self.nch = nch
+
+    def _var(self, var):
+        v = np.ascontiguousarray(np.broadcast_to(np.asarray(var, dtype=np.float64), (self.nch,)))
+        return v
+
+    def set_run(self, run, ch=-1):
+        check(self._L.qh_varsamp_set_run(self._h, ch, int(run)))
+
+    def set_varmode(self, varmode, ch=-1):
+        check(self._L.qh_varsamp_set_varmode(self._h, ch, int(varmode)))
+
+    def set_rates(self, in_rate, out_rate, ch=-1):
+        """setInRate_varsamp / setOutRate_varsamp: a new design, and the channel starts over"""
+        check(self._L.qh_varsamp_set_rates(self._h, ch, int(in_rate), int(out_rate)))
+
+    def set_bandwidth(self, fc_low, fc_high, ch=-1):
+        check(self._L.qh_varsamp_set_bandwidth(self._h, ch, fc_low, fc_high))
+
+    def flush(self, ch=-1):
+        check(self._L.qh_varsamp_flush(self._h, ch))
+
+    def rsize(self, ch=0):
+        """the taps of one output sample of channel ch"""
+        return self._L.qh_varsamp_rsize(self._h, ch)
+
+    def max_out(self, n, var):
+        """the largest count the next call of n samples with these var could report on any channel"""
+        v = self._var(var)
+        m = self._L.qh_varsamp_max_out(self._h, int(n), v.ctypes.data)
+        if m < 0:
+            check(int(m))
+        return int(m)
+
+    def process_ptr(self, d_in, in_stride, d_out, out_stride, n, var, d_count=None):
+        """Device pointers, strides in complex samples, out_stride >= max_out(n, var); rows of d_out apart from those of d_in; d_count:
+        device int[nch] or None.  Asynchronous on the bank's stream."""
+        v = self._var(var)
+        check(self._L.qh_varsamp_process(self._h, d_in, in_stride, d_out, out_stride, n, v.ctypes.data, d_count))
+
+    def process_host(self, x, var):
+        """x [nch, n] complex128, var a number or [nch] -> (y [nch, max_out], counts [nch]); row c of y holds counts[c] samples, zeros behind"""
+        x = np.ascontiguousarray(x, dtype=np.complex128)
+        if x.ndim != 2 or x.shape[0] != self.nch:
+            raise ValueError("expected [nch, n] complex128")
+        v = self._var(var)
+        n = x.shape[1]
+        mo = max(self.max_out(n, v), 1)
+        out = np.zeros((self.nch, mo), dtype=np.complex128)
+        counts = np.zeros(self.nch, dtype=np.int32)
+        check(self._L.qh_varsamp_process_host(self._h, x.ctypes.data, max(n, 1), out.ctypes.data, mo, n, v.ctypes.data, counts.ctypes.data))
+        return out, counts
+
+    def synchronize(self):
+        check(self._L.qh_varsamp_synchronize(self._h))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.qh_varsamp_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
