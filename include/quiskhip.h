@@ -410,6 +410,31 @@ void SetEXTNOBThreshold(int id, double thresh);                                 
 /* xnobEXT for buffsize samples in device memory (d_in == d_out allowed): enqueued on the id's stream, which is ordered behind `stream`
  * on entry; `stream` is ordered behind it on return.  Nothing is waited for.  The same samples as xnobEXT, bit for bit. */
 int qh_wdsp_xnobEXT_device(int id, const void *d_in, void *d_out, void *stream);
+/* The diversity combiner WDSP's callers run behind the blankers and in front of fexchange0 (wdsp/div.c:104-187): ids 0..31 (WDSP's own
+ * array holds 2, MAX_EXT_DIVS, div.c:104), each a one-group qh_div bank (section 10e) with staging rows of its own.  xdivEXT takes
+ * nsamples as the size and the first nr pointers of `in`; in[i] and out are host pointers.  out == in[k] is recognised by pointer
+ * equality and gives what the reference gives: in the mixing mode every receiver whose pointer is `out` contributes the running sum in
+ * place of its samples (the memset has zeroed them, div.c:81), and a copy of in[output] onto itself does nothing.  Refused, to
+ * qh_wdsp_status() with nothing changed: a bad or empty id; a null pointer among those the call reads (in, out, in[i] of the receivers
+ * it reads); any other overlap of out with an input that is read; nsamples < 0; output > nr while the id runs; nr outside 1..8,
+ * output outside 0..8, SetEXTDIVRotate's nr outside 0..8, a null or non-finite rotate array (the reference reads a stale or null pointer
+ * or writes past Irotate[8] there).  SetEXTDIVBuffsize stores the size (a negative one is refused); xdivEXT's nsamples is what counts,
+ * as in the reference.  flush_divEXT does nothing, as there.  The setters are order-free and act on the next xdivEXT.
+ * Not provided: xdivEXTF and the "legacy interface" (div.c:189-219). */
+void create_divEXT(int id, int run, int nr, int size);                           /* wdsp/div.c:107-111: output 0, rotates 0 */
+void destroy_divEXT(int id);                                                     /* wdsp/div.c:113-117 */
+void flush_divEXT(int id);                                                       /* wdsp/div.c:119-123 */
+void xdivEXT(int id, int nsamples, double **in, double *out);                    /* wdsp/div.c:125-134 */
+void SetEXTDIVRun(int id, int run);                                              /* wdsp/div.c:137-144 */
+void SetEXTDIVBuffsize(int id, int size);                                        /* wdsp/div.c:147-154 */
+void SetEXTDIVNr(int id, int nr);                                                /* wdsp/div.c:157-164 */
+void SetEXTDIVOutput(int id, int output);                                        /* wdsp/div.c:168-175 */
+void SetEXTDIVRotate(int id, int nr, double *Irotate, double *Qrotate);          /* wdsp/div.c:179-187 */
+/* xdivEXT for nsamples samples in device memory: d_in is a host array of nr device pointers, read before the call returns; d_out ==
+ * d_in[k] is recognised as in xdivEXT.  Enqueued on the id's stream, which is ordered behind `stream` on entry; `stream` is ordered
+ * behind it on return.  Nothing is waited for.  The same samples as xdivEXT, bit for bit.  The rows the call reads are gathered into
+ * the id's staging rows first (one device copy each); a caller whose receivers already lie in strided rows uses qh_div_process. */
+int qh_wdsp_xdivEXT_device(int id, int nsamples, const void *const *d_in, void *d_out, void *stream);
 /* The variable-ratio resampler WDSP's callers put behind fexchange0 (wdsp/varsamp.c:228-250): every pointer a one-channel qh_varsamp
  * bank (section 10d) with run 1, fc 0, fc_low -1, gain 1, var 1 and varmode 1, as create_varsampV fixes them, on a stream and with an
  * input staging row of its own, so input == output works.  input / output are host pointers; output needs room for the samples the
@@ -910,6 +935,41 @@ int qh_varsamp_process(qh_varsamp *b, const void *d_in, long long in_stride, voi
                        int *d_count);
 int qh_varsamp_process_host(qh_varsamp *b, const void *h_in, long long in_stride, void *h_out, long long out_stride, int n,
                             const double *var, int *h_count);
+/* ------------------------------------------------------------------ 10e. WDSP's diversity combiner (DIV) */
+/* xdiv (wdsp/div.c:67-95) for `ngroups` groups of up to eight phase-coherent receivers, fp64 complex, where WDSP's callers run it:
+ * behind the blankers, in front of fexchange0.  Every group has its own run, nr (1..8), output (0..nr) and eight rotate pairs.  run = 0:
+ * the output is receiver 0.  output != nr: the output is receiver `output`.  output == nr: the output is the sum over i = 0 .. nr-1, in
+ * that order, of (Irotate[i] + j Qrotate[i]) times receiver i -- what nulls an interferer with two antennas.  The sum is the
+ * reference's bit for bit: it starts from +0.0, and every product, the difference or sum inside the bracket and the accumulation are
+ * rounded on their own, nothing fused (all-zero inputs with a negative rotate give +0.0).  There is no fp32 form, as in the reference.
+ * Nothing is kept from call to call.  A call is one kernel launch for all groups, copies included: nr reads and one write per sample.
+ * Rows: receiver i of group g lies at d_in + (g * group_stride + i * rx_stride) complex doubles, the output of group g at d_out +
+ * g * out_stride.  An output row may be exactly one of its own group's receiver rows: d_out == d_in + k * rx_stride with out_stride ==
+ * group_stride, for some k < 8.  The result is then the reference's with out == in[k]: its memset zeroes that receiver's samples before
+ * they are read, so the receiver contributes the running sum in place of its samples (S <- S + rotate[k] S, with the partial sum of
+ * receivers 0 .. k-1); a group that copies receiver k writes nothing, one that copies another receiver overwrites row k.
+ * Refused with QH_ERR_INVALID, nothing written and no setting changed: any other sharing of bytes between an output row and a receiver
+ * row that the call reads (a group reads its first nr rows when it mixes, else the one row it copies); n < 0; a stride below n (so
+ * output rows never share bytes with each other); a group with run != 0 and output > nr at the call (the reference would read a
+ * receiver pointer nobody set); at the setters nr outside 1..8, output outside 0..8, qh_div_set_rotate's nr outside 0..8, a null array,
+ * a value that is not finite (the reference writes past Irotate[8] or reads what it was not given).  n == 0 is accepted and does
+ * nothing.  The setters are order-free, as in the reference: nr may come before or after output; g = -1 means every group; they take
+ * effect at the next process call. */
+typedef struct qh_div qh_div;
+qh_div *qh_div_create(int device, int ngroups, int run, int nr, void *stream);   /* create_div, div.c:31-48: output 0, rotates 0 */
+void qh_div_destroy(qh_div *b);                                                  /* div.c:50-60 */
+int qh_div_set_run(qh_div *b, int g, int run);                                   /* div.c:137-144 */
+int qh_div_set_nr(qh_div *b, int g, int nr);                                     /* div.c:157-164 */
+int qh_div_set_output(qh_div *b, int g, int output);                             /* div.c:168-175 */
+/* div.c:179-187: the first nr values of both arrays; this nr is the call's own, not the group's */
+int qh_div_set_rotate(qh_div *b, int g, int nr, const double *Irotate, const double *Qrotate);
+/* The settings of group g as the next call will use them; any pointer may be null; Irotate8 / Qrotate8: 8 doubles each */
+int qh_div_get(qh_div *b, int g, int *run, int *nr, int *output, double *Irotate8, double *Qrotate8);
+int qh_div_synchronize(qh_div *b);
+/* xdiv (div.c:67-95) over n >= 0 samples of every group: device rows of interleaved complex doubles, strides in complex samples,
+ * asynchronous on the bank's stream.  The _host form (synchronous, pageable memory) takes the same layouts, the in-place one included. */
+int qh_div_process(qh_div *b, const void *d_in, long long rx_stride, long long group_stride, void *d_out, long long out_stride, int n);
+int qh_div_process_host(qh_div *b, const void *h_in, long long rx_stride, long long group_stride, void *h_out, long long out_stride, int n);
 /* dAutoNotch (quisk.c:786-963; 8(f) rank 3) inside the receiver bank, where the mode calls it (on the real audio after
  * the Rx filter; after the interpolators for FM; DGT-IQ has none): set_auto_notch(i) (quisk.c:4596) -- stores the flag
  * and starts the notch over -- with rit_freq as set_sidetone passes it (quisk.c:4712): the CW modes keep the notch off

@@ -1,5 +1,5 @@
 // qh_bank.hpp -- the host code the channel banks in front of the receiver have in common (qh_anb.hip, qh_nob.hip; qh_nb.hip takes
-// bank_open, bank_process_host and bank_synchronize): a handle is `nch` streams on one device and one HIP stream, with settings that
+// bank_open, bank_process_host and bank_synchronize, qh_div.hip bank_open, bank_set and bank_synchronize): a handle is `nch` streams on one device and one HIP stream, with settings that
 // another thread may change between calls.
 #pragma once
 #include <mutex>

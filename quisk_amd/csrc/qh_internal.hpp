@@ -67,6 +67,11 @@ int nob_check_settings(double samplerate, int mode, double slewtime, double hang
 // the same for qh_varsamp_create (qh_varsamp.hip) and create_varsampV
 int varsamp_check_settings(int in_rate, int out_rate, int R, double fc, double fc_low, double gain);
 
+// qh_div_process (qh_div.hip) on rows the caller has staged on the device, apart from the output rows: bit i of `alias` says that the
+// caller's receiver i of every group was the very row its output goes to (xdivEXT's out == in[i]), so that it contributes the running sum
+int div_process_staged(qh_div *b, const void *d_in, long long rx_stride, long long group_stride, void *d_out, long long out_stride, int n,
+                       unsigned alias);
+
 // The display bank behind a WDSP display id (XCreateAnalyzer), held until wdsp_display_release: DestroyAnalyzer waits (qh_analyzer.hip)
 qh_ana *wdsp_display_hold(int disp);
 void wdsp_display_release();

@@ -1264,6 +1264,150 @@ void SetEXTNOBThreshold(int id, double thresh) { EXT_SETTER(NobExt, qh_nob_set_t
 
 }  // extern "C"
 
+// ---- the diversity combiner between the blankers and fexchange0: create_divEXT ... SetEXTDIVRotate (wdsp/div.c:104-187) -------------------
+// pdiv[id], div.c:104-105: each id a one-group bank on a stream of its own.  The caller's receivers are pointers of their own, the
+// bank's are rows a stride apart: the rows a call reads are gathered into d_in [8][cap] first, and the receivers whose pointer is `out`
+// go to the bank as a mask (qh::div_process_staged), so out == in[k] needs no copy to undo.
+namespace {
+constexpr int kMaxExtDivs = 32;     // (MAX_EXT_DIVS is 2, div.c:104; 32 as the other EXT families here)
+constexpr int kDivRows = 8;         // MAX_NR, div.c:29
+Ext<qh_div> g_div[kMaxExtDivs];
+std::recursive_mutex g_div_mtx[kMaxExtDivs];
+
+struct DivExt {
+    typedef qh_div Bank;
+    static constexpr int count = kMaxExtDivs;
+    static Ext<qh_div> *slots() { return g_div; }
+    static std::recursive_mutex *mutexes() { return g_div_mtx; }
+    static constexpr auto destroy = qh_div_destroy;
+    static constexpr const char *tag = "DIV", *x_host = "xdivEXT", *x_device = "qh_wdsp_xdivEXT_device";
+};
+
+int div_staging(Ext<qh_div> &a, int n, const char *name)
+{
+    if (n <= a.cap) return QH_OK;
+    if (hipStreamSynchronize(a.stream) != hipSuccess) return qh::set_error(QH_ERR_HIP, "%s: synchronize failed", name);
+    (void)hipFree(a.d_in); (void)hipFree(a.d_out);
+    a.d_in = nullptr; a.d_out = nullptr; a.cap = 0;
+    if (hipMalloc((void **)&a.d_in, (size_t)kDivRows * (size_t)n * 16) != hipSuccess || hipMalloc((void **)&a.d_out, (size_t)n * 16) != hipSuccess)
+        return qh::set_error(QH_ERR_HIP, "%s: staging allocation failed", name);
+    a.cap = n;
+    return QH_OK;
+}
+
+// What a call of nsamples on pointers in[0 .. nr-1] / out reads and where out lies over it (host or device addresses alike): the first
+// row read and their count, the receivers whose pointer is out, and whether nothing is to be done (a copy of in[output] onto itself)
+struct DivCall {
+    int first = 0, count = 0;
+    unsigned alias = 0;
+    bool nothing = false;
+};
+
+int div_call(Ext<qh_div> &a, int nsamples, const void *const *in, const void *out, const char *name, DivCall *c)
+{
+    int run = 0, nr = 0, output = 0;
+    if (int rc = qh_div_get(a.b, 0, &run, &nr, &output, nullptr, nullptr)) return rc;
+    if (nsamples < 0 || !in || !out) return qh::set_error(QH_ERR_INVALID, "%s: bad arguments", name);
+    if (run && output > nr) return qh::set_error(QH_ERR_INVALID, "%s: output %d is above nr %d (the reference reads a receiver nobody handed it)", name, output, nr);
+    const bool mix = run && output == nr;
+    c->first = !run || mix ? 0 : output;
+    c->count = mix ? nr : 1;
+    const long long o = (long long)reinterpret_cast<uintptr_t>(out), len = (long long)nsamples * 16;
+    for (int i = c->first; i < c->first + c->count; i++) {
+        if (!in[i]) return qh::set_error(QH_ERR_INVALID, "%s: in[%d] is null", name, i);
+        const long long p = (long long)reinterpret_cast<uintptr_t>(in[i]);
+        if (p == o) c->alias |= 1u << i;
+        else if (p < o + len && o < p + len) return qh::set_error(QH_ERR_INVALID, "%s: out overlaps in[%d] without being it", name, i);
+    }
+    c->nothing = nsamples == 0 || (!mix && c->alias);
+    return QH_OK;
+}
+}  // namespace
+
+extern "C" {
+
+void create_divEXT(int id, int run, int nr, int size)
+{
+    g_status = QH_OK;
+    if (id < 0 || id >= kMaxExtDivs) { g_status = qh::set_error(QH_ERR_INVALID, "DIV id %d out of range", id); return; }
+    std::unique_lock<std::recursive_mutex> lk(g_div_mtx[id]);
+    Ext<qh_div> &a = g_div[id];
+    if (a.b) { g_status = qh::set_error(QH_ERR_INVALID, "DIV id %d already exists", id); return; }
+    if (size < 0 || nr < 1 || nr > kDivRows) { g_status = qh::set_error(QH_ERR_INVALID, "create_divEXT: nr must lie in 1..8 and the size must not be negative"); return; }
+    if (hipStreamCreateWithFlags(&a.stream, hipStreamNonBlocking) != hipSuccess) {
+        a.stream = nullptr;
+        g_status = qh::set_error(QH_ERR_NO_DEVICE, "create_divEXT: no HIP device (libquiskhip has no CPU fallback)");
+        return;
+    }
+    a.b = qh_div_create(0, 1, run, nr, a.stream);
+    if (!a.b) { g_status = QH_ERR_HIP; ext_release<DivExt>(a); return; }   // the settings were good: the device (message already set)
+    a.buffsize = size;
+    if (int rc = div_staging(a, size, "create_divEXT")) { g_status = rc; ext_release<DivExt>(a); }
+}
+
+void destroy_divEXT(int id) { LockedExt<DivExt> L(id); if (L.a) ext_release<DivExt>(*L.a); }
+void flush_divEXT(int id) { LockedExt<DivExt> L(id); }                    // flush_div is empty, div.c:62-65
+
+void xdivEXT(int id, int nsamples, double **in, double *out)
+{
+    LockedExt<DivExt> L(id);
+    if (!L.a) return;
+    Ext<qh_div> &a = *L.a;
+    DivCall c;
+    if (int rc = div_call(a, nsamples, (const void *const *)in, out, DivExt::x_host, &c)) { g_status = rc; return; }
+    if (c.nothing) return;
+    if (int rc = div_staging(a, nsamples, DivExt::x_host)) { g_status = rc; return; }
+    const size_t bytes = (size_t)nsamples * 16;
+    for (int i = c.first; i < c.first + c.count; i++)
+        if (!((c.alias >> i) & 1u) &&                                       // (the samples of a receiver that is `out` are never read)
+            hipMemcpyAsync(a.d_in + (size_t)i * (size_t)a.cap * 2, in[i], bytes, hipMemcpyHostToDevice, a.stream) != hipSuccess) {
+            (void)hipStreamSynchronize(a.stream);
+            g_status = qh::set_error(QH_ERR_HIP, "%s: upload failed", DivExt::x_host);
+            return;
+        }
+    int rc = qh::div_process_staged(a.b, a.d_in, a.cap, (long long)kDivRows * a.cap, a.d_out, a.cap, nsamples, c.alias);
+    if (!rc && hipMemcpyAsync(out, a.d_out, bytes, hipMemcpyDeviceToHost, a.stream) != hipSuccess) rc = qh::set_error(QH_ERR_HIP, "%s: download failed", DivExt::x_host);
+    if (hipStreamSynchronize(a.stream) != hipSuccess && !rc) rc = qh::set_error(QH_ERR_HIP, "%s: download failed", DivExt::x_host);
+    g_status = rc;
+}
+
+int qh_wdsp_xdivEXT_device(int id, int nsamples, const void *const *d_in, void *d_out, void *stream)
+{
+    LockedExt<DivExt> L(id);
+    if (!L.a) return g_status;
+    Ext<qh_div> &a = *L.a;
+    DivCall c;
+    if (int rc = div_call(a, nsamples, d_in, d_out, DivExt::x_device, &c)) return g_status = rc;
+    if (c.nothing) return QH_OK;
+    if (int rc = div_staging(a, nsamples, DivExt::x_device)) return g_status = rc;
+    hipStream_t cs = (hipStream_t)stream;
+    if (!a.ev_in && (hipEventCreateWithFlags(&a.ev_in, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&a.ev_out, hipEventDisableTiming) != hipSuccess))
+        return g_status = qh::set_error(QH_ERR_HIP, "%s: event creation failed", DivExt::x_device);
+    const size_t bytes = (size_t)nsamples * 16;
+    if (cs != a.stream) { (void)hipEventRecord(a.ev_in, cs); (void)hipStreamWaitEvent(a.stream, a.ev_in, 0); }
+    int rc = QH_OK;
+    for (int i = c.first; i < c.first + c.count && !rc; i++)
+        if (!((c.alias >> i) & 1u) && hipMemcpyAsync(a.d_in + (size_t)i * (size_t)a.cap * 2, d_in[i], bytes, hipMemcpyDeviceToDevice, a.stream) != hipSuccess)
+            rc = qh::set_error(QH_ERR_HIP, "%s: copy failed", DivExt::x_device);
+    if (!rc) rc = qh::div_process_staged(a.b, a.d_in, a.cap, (long long)kDivRows * a.cap, d_out, nsamples, nsamples, c.alias);
+    if (cs != a.stream) { (void)hipEventRecord(a.ev_out, a.stream); (void)hipStreamWaitEvent(cs, a.ev_out, 0); }
+    return g_status = rc;
+}
+
+void SetEXTDIVRun(int id, int run) { EXT_SETTER(DivExt, qh_div_set_run(L.a->b, 0, run)); }
+void SetEXTDIVBuffsize(int id, int size)
+{
+    LockedExt<DivExt> L(id);
+    if (!L.a) return;
+    if (size < 0) { g_status = qh::set_error(QH_ERR_INVALID, "SetEXTDIVBuffsize: bad buffer size"); return; }
+    L.a->buffsize = size;
+}
+void SetEXTDIVNr(int id, int nr) { EXT_SETTER(DivExt, qh_div_set_nr(L.a->b, 0, nr)); }
+void SetEXTDIVOutput(int id, int output) { EXT_SETTER(DivExt, qh_div_set_output(L.a->b, 0, output)); }
+void SetEXTDIVRotate(int id, int nr, double *Irotate, double *Qrotate) { EXT_SETTER(DivExt, qh_div_set_rotate(L.a->b, 0, nr, Irotate, Qrotate)); }
+
+}  // extern "C"
+
 // ---- the variable-ratio resampler behind fexchange0: create_varsampV, xvarsampV, destroy_varsampV (wdsp/varsamp.c:228-250) ---------------
 // Every pointer a one-channel bank on a stream of its own, with an input staging row that lets input == output, an output staging row
 // for the host form and the count in device memory.  The reference hands out its VARSAMP; here the pointer is looked up in a table, so

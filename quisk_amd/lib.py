@@ -346,6 +346,24 @@ def load():
     L.qh_wdsp_varsampV_max_out.argtypes = [vp, i, d]
     L.qh_wdsp_varsampV_max_out.restype = ll
     L.qh_wdsp_xvarsampV_device.argtypes = [vp, vp, vp, i, d, vp, vp]
+    # WDSP's diversity combiner (wdsp/div.c): the bank and the EXT names between the blankers and fexchange0
+    L.qh_div_create.restype = vp
+    L.qh_div_create.argtypes = [i, i, i, i, vp]
+    L.qh_div_destroy.argtypes = [vp]
+    L.qh_div_destroy.restype = None
+    for n in ("set_run", "set_nr", "set_output"):
+        getattr(L, "qh_div_" + n).argtypes = [vp, i, i]
+    L.qh_div_set_rotate.argtypes = [vp, i, i, vp, vp]
+    L.qh_div_get.argtypes = [vp, i, C.POINTER(i), C.POINTER(i), C.POINTER(i), vp, vp]
+    L.qh_div_synchronize.argtypes = [vp]
+    L.qh_div_process.argtypes = [vp, vp, ll, ll, vp, ll, i]
+    L.qh_div_process_host.argtypes = [vp, vp, ll, ll, vp, ll, i]
+    for n, a in (("create_divEXT", [i, i, i, i]), ("destroy_divEXT", [i]), ("flush_divEXT", [i]), ("xdivEXT", [i, i, C.POINTER(vp), vp]),
+                 ("SetEXTDIVRun", [i, i]), ("SetEXTDIVBuffsize", [i, i]), ("SetEXTDIVNr", [i, i]), ("SetEXTDIVOutput", [i, i]),
+                 ("SetEXTDIVRotate", [i, i, vp, vp])):
+        getattr(L, n).argtypes = a
+        getattr(L, n).restype = None
+    L.qh_wdsp_xdivEXT_device.argtypes = [i, i, C.POINTER(vp), vp, vp]
     L.qh_qrx_set_noise_blanker.argtypes = [vp, i]
     L.qh_qrx_set_auto_notch.argtypes = [vp, i, i]
     L.qh_quisk_set_auto_notch.argtypes = [i, i]

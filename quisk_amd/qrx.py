@@ -484,3 +484,81 @@ class WdspVarResampler:
             self.close()
         except Exception:
             pass
+
+
+class WdspDiversity:
+    """WDSP's diversity combiner DIV (xdiv, wdsp/div.c:67-95) for `ngroups` groups of up to eight phase-coherent receivers, every group
+    with its own run, nr, output and rotate factors.  run = 0 gives receiver 0, output != nr gives receiver `output`, output == nr the sum
+    of the receivers times their complex rotate factors, bit for bit the reference's.  The setters take a group, or -1 for every group."""
+
+    MAX_NR = 8
+
+    def __init__(self, ngroups, nr, run=1, device=0, stream=None):
+        self._L = load()
+        self._h = self._L.qh_div_create(device, ngroups, int(run), int(nr), stream)
+        if not self._h:
+            raise QuiskHipError("qh_div_create failed: %s" % self._L.qh_last_error().decode(errors="replace"))
+        self.ngroups = ngroups
+
+    def set_run(self, run, g=-1):
+        check(self._L.qh_div_set_run(self._h, g, int(run)))
+
+    def set_nr(self, nr, g=-1):
+        check(self._L.qh_div_set_nr(self._h, g, int(nr)))
+
+    def set_output(self, output, g=-1):
+        """which receiver to put out; output == nr mixes"""
+        check(self._L.qh_div_set_output(self._h, g, int(output)))
+
+    def set_rotate(self, irotate, qrotate, g=-1):
+        """the rotate factors of the first len(irotate) receivers (SetEXTDIVRotate's nr is the length)"""
+        ir = np.ascontiguousarray(irotate, dtype=np.float64).ravel()
+        qr = np.ascontiguousarray(qrotate, dtype=np.float64).ravel()
+        if ir.size != qr.size:
+            raise ValueError("irotate and qrotate differ in length")
+        check(self._L.qh_div_set_rotate(self._h, g, int(ir.size), ir.ctypes.data, qr.ctypes.data))
+
+    def get(self, g):
+        """-> dict(run, nr, output, irotate[8], qrotate[8]) as the next call will use them"""
+        run, nr, output = C.c_int(0), C.c_int(0), C.c_int(0)
+        ir, qr = np.zeros(self.MAX_NR), np.zeros(self.MAX_NR)
+        check(self._L.qh_div_get(self._h, g, C.byref(run), C.byref(nr), C.byref(output), ir.ctypes.data, qr.ctypes.data))
+        return dict(run=run.value, nr=nr.value, output=output.value, irotate=ir, qrotate=qr)
+
+    def process_ptr(self, d_in, rx_stride, group_stride, d_out, out_stride, n):
+        """Device pointers, strides in complex samples: receiver i of group g at d_in + g group_stride + i rx_stride, its output at d_out +
+        g out_stride.  d_out may be d_in + k rx_stride with out_stride == group_stride (the reference's out == in[k]); any other overlap
+        is refused.  Asynchronous on the bank's stream."""
+        check(self._L.qh_div_process(self._h, d_in, rx_stride, group_stride, d_out, out_stride, n))
+
+    def process_host(self, x, onto=None):
+        """x [ngroups, nr_max, n] complex128 -> [ngroups, n].  onto=k lays the output over receiver k as the reference's callers do with
+        out == in[k]: the result is what the reference leaves there (x itself is not changed)."""
+        x = np.ascontiguousarray(x, dtype=np.complex128)
+        if x.ndim != 3 or x.shape[0] != self.ngroups:
+            raise ValueError("expected [ngroups, nr_max, n] complex128")
+        nrm, n = x.shape[1], x.shape[2]
+        if onto is None:
+            out = np.empty((self.ngroups, n), dtype=np.complex128)
+            check(self._L.qh_div_process_host(self._h, x.ctypes.data, max(n, 1), max(nrm * n, 1), out.ctypes.data, max(n, 1), n))
+            return out
+        k = int(onto)
+        if not 0 <= k < nrm:
+            raise ValueError("onto must name one of the receivers of x")
+        buf = x.copy()
+        check(self._L.qh_div_process_host(self._h, buf.ctypes.data, max(n, 1), max(nrm * n, 1), buf[:, k].ctypes.data, max(nrm * n, 1), n))
+        return buf[:, k].copy()
+
+    def synchronize(self):
+        check(self._L.qh_div_synchronize(self._h))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.qh_div_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
