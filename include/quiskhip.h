@@ -450,6 +450,27 @@ long long qh_wdsp_varsampV_max_out(void *ptr, int numsamps, double var);        
  * d_count: device, one int): enqueued on the pointer's stream, which is ordered behind `stream` on entry; `stream` is ordered behind
  * it on return.  Nothing is waited for.  The same samples and count as xvarsampV, bit for bit. */
 int qh_wdsp_xvarsampV_device(void *ptr, const void *d_in, void *d_out, int numsamps, double var, int *d_count, void *stream);
+/* The fixed-ratio resampler WDSP's callers use beside fexchange0 (wdsp/resample.c:206-228, 332-354): every pointer a one-channel
+ * qh_resample bank (section 10f) on a stream and with staging rows of its own -- complex doubles with run 1, fc 0, ncoef 0 and gain 1
+ * for the V names, real floats for the FV names -- looked up in a table, not followed.  *outsamps is the number of samples the call
+ * makes (ceil((numsamps L - phnum) / M), at most qh_wdsp_resampleV_max_out), as the reference's is.  input == output works where
+ * L <= M and gives the reference's result there (it never reads a sample it has overwritten); where L > M the reference overwrites
+ * samples it has yet to read, and the call is refused.  Errors (a pointer that create did not return, a refused rate pair: see
+ * qh_resample_create, input == output with L > M) go to qh_wdsp_status(), change nothing and report *outsamps = 0; create then returns
+ * null.  Not provided: create_resample, destroy_resample, flush_resample, xresample and the set..._resample names, whose argument is
+ * WDSP's own struct; qh_resample_* has their function. */
+void *create_resampleV(int in_rate, int out_rate);                                /* wdsp/resample.c:208-212 */
+void xresampleV(double *input, double *output, int numsamps, int *outsamps, void *ptr);   /* wdsp/resample.c:214-222 */
+void destroy_resampleV(void *ptr);                                                /* wdsp/resample.c:224-228 */
+void *create_resampleFV(int in_rate, int out_rate);                               /* wdsp/resample.c:334-338 */
+void xresampleFV(float *input, float *output, int numsamps, int *outsamps, void *ptr);    /* wdsp/resample.c:340-348 */
+void destroy_resampleFV(void *ptr);                                               /* wdsp/resample.c:350-354 */
+long long qh_wdsp_resampleV_max_out(void *ptr, int numsamps);                     /* qh_resample_max_out of a V or FV pointer's bank */
+/* xresampleV / xresampleFV for numsamps samples in device memory (d_out with room for qh_wdsp_resampleV_max_out samples; d_in ==
+ * d_out as above; *outsamps: host, set before the call returns): enqueued on the pointer's stream, which is ordered behind `stream` on
+ * entry; `stream` is ordered behind it on return.  Nothing is waited for.  The same samples and count as the host forms, bit for bit. */
+int qh_wdsp_xresampleV_device(void *ptr, const void *d_in, void *d_out, int numsamps, int *outsamps, void *stream);
+int qh_wdsp_xresampleFV_device(void *ptr, const void *d_in, void *d_out, int numsamps, int *outsamps, void *stream);
 /* Quisk's re-blocking shim around fexchange0 (quisk_wdsp.c:24-69): any nSamples in, scaled by 1/CLIP32 into
  * in_size blocks, results scaled back; returns the number of samples written to cSamples.  qh_wdsp_set_parameter
  * is the C form of quisk_wdsp_set_parameter (quisk_wdsp.c:71-91; in_size <= 0 / in_use < 0 leave the value).  One deviation: a CHANGE
@@ -978,6 +999,53 @@ int qh_qrx_set_auto_notch(qh_qrx *r, int on, int rit_freq);
 /* The receiver bank with the blanker in front of its tune, as quisk_process_samples has it; 0 = off (default). */
 int qh_qrx_set_noise_blanker(qh_qrx *r, int level);
 
+/* ------------------------------------------------------------------ 10f. WDSP's fixed-ratio resampler (RESAMPLE, RESAMPLEF) */
+/* xresample (wdsp/resample.c:121-157) for `nch` fp64 complex streams, or xresampleF (resample.c:296-330) for `nch` fp32 real streams
+ * whose ring, taps and sums are fp64 ((double)in[i] on the way in, (float)I on the way out), as a stand-alone stream: a call takes n
+ * input samples of every channel and reports how many output samples it made of each, so rate ratios that are whole in neither
+ * direction (48 k -> 44.1 k) run as a proper stream.  Every channel has its own design, run and state; channels with equal designs
+ * share one copy of the taps.  calc_resample (resample.c:35-78): L = out_rate / gcd, M = in_rate / gcd; fc = 0 selects 0.45 min_rate;
+ * fc_low < 0 selects -fc; ncoef = 0 selects (int)(140 in_rate L / min_rate); ncoef is rounded up to (ncoef / L + 1) L, cpp = ncoef / L
+ * taps meet every output.  The real-float form has create_resampleF's design instead (resample.c:250-273): fc = 0.45 min_rate, ncoef =
+ * (int)(60 / fc_norm) rounded the same way, gain 1; the fc, ncoef and gain given to create are not used there.
+ * Output m of a call sits at upsampled position p = phnum + m M: tap row p % L of the phase-major h[L][cpp] against inputs p / L,
+ * p / L - 1, ..., summed j = 0 .. cpp - 1 in fp64 as resample.c:139-144 (products may be fused), with the last cpp - 1 inputs of the
+ * earlier calls in front of the call's first sample.  The count, ceil((n L - phnum) / M), and the next phnum are evaluated on the host:
+ * `counts` is filled when process returns, and no device count exists.  A call is one kernel, the history behind it included.
+ * A new design (set_rates always; set_fc_low and set_bandwidth only when a value changes, resample.c:185-204) empties the channel's
+ * history and sets its phase to 0, as calc_resample does.  n = 0 is accepted, makes nothing and moves nothing.
+ * Deviations: run = 0 copies the channel's n samples and reports 0, what xresample returns (the V names fix run = 1).  Refused with
+ * QH_ERR_INVALID, nothing changed: rates <= 0; in_rate * L beyond int (the reference's full_rate overflows); ncoef < 0; ncoef beyond
+ * 4194304 after rounding; an fc, fc_low or gain that is not finite; set_fc_low and set_bandwidth on the real-float form; an out_stride
+ * below qh_resample_max_out(b, n); output rows that share a byte with the input rows; a null handle or pointer.  The reference checks
+ * none of these.  Setters: ch = -1 means every channel; they take effect at the next process call. */
+enum { QH_RESAMPLE_C64 = 0, QH_RESAMPLE_R32 = 1 };  /* interleaved complex doubles / real floats */
+typedef struct qh_resample qh_resample;
+qh_resample *qh_resample_create(int device, int nch, int in_rate, int out_rate, double fc, int ncoef, double gain, int dtype,
+                                void *stream);                                   /* create_resample, resample.c:86-103; create_resampleF, 236-280; run = 1 */
+void qh_resample_destroy(qh_resample *b);                                        /* resample.c:105-110, 282-287 */
+int qh_resample_set_run(qh_resample *b, int ch, int run);                        /* resets nothing (resample.c:124,154) */
+int qh_resample_set_rates(qh_resample *b, int ch, int in_rate, int out_rate);    /* setInRate_ / setOutRate_resample, resample.c:171-183 */
+int qh_resample_set_fc_low(qh_resample *b, int ch, double fc_low);               /* setFCLow_resample, resample.c:185-193 */
+int qh_resample_set_bandwidth(qh_resample *b, int ch, double fc_low, double fc_high);    /* setBandwidth_resample, resample.c:195-204 */
+int qh_resample_flush(qh_resample *b, int ch);                                   /* flush_resample, resample.c:112-118 (setSize_resample: 165-169) */
+int qh_resample_L(qh_resample *b, int ch);                                       /* resample.c:53 */
+int qh_resample_M(qh_resample *b, int ch);                                       /* resample.c:54 */
+int qh_resample_cpp(qh_resample *b, int ch);                                     /* resample.c:66 */
+/* the phase-major h[L][cpp] in force on channel ch (resample.c:69-72) -> out, which has room for cap doubles; returns L * cpp */
+int qh_resample_taps(qh_resample *b, int ch, double *out, int cap);
+/* what the next call of n samples makes of channel ch (0 while it does not run); negative: a qh_status */
+long long qh_resample_out_count(qh_resample *b, int ch, int n);
+/* the most samples a call of n samples can write to any output row, whatever the phases: ceil(n L / M) of a channel that runs, n of
+ * one that does not; negative: a qh_status */
+long long qh_resample_max_out(qh_resample *b, int n);
+/* xresample / xresampleF over n >= 0 input samples of every channel: device rows [nch][stride] of the bank's sample type, strides in
+ * samples, out_stride >= qh_resample_max_out(b, n); counts: host, int[nch], the samples made of every channel.  Nothing is written
+ * behind a row's count (behind n for a channel that does not run).  Asynchronous on the bank's stream.  The _host form (synchronous,
+ * pageable memory) takes h_out == h_in. */
+int qh_resample_process(qh_resample *b, const void *d_in, long long in_stride, void *d_out, long long out_stride, int n, int *counts);
+int qh_resample_process_host(qh_resample *b, const void *h_in, long long in_stride, void *h_out, long long out_stride, int n, int *counts);
+int qh_resample_synchronize(qh_resample *b);
 /* ------------------------------------------------------------------ 11. WDSP display engine (analyzer) */
 /* wdsp/analyzer.c for a bank of `ndisp` displays that share one configuration: Spectrum0's sample
  * rings, the windowed transform every size - overlap samples, clip / flip / stitch (Celiminate, eliminate, stitch,

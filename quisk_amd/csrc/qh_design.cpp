@@ -52,7 +52,7 @@ std::vector<cd> fir_bandpass(int N, double f_low, double f_high, double samplera
     return h;
 }
 
-ResamplerDesign design_resampler(int in_rate, int out_rate, double fc, int ncoef, double gain)
+ResamplerDesign design_resampler(int in_rate, int out_rate, double fc, int ncoef, double gain, double fc_low)
 {
     ResamplerDesign d;
     int x = in_rate, y = out_rate;
@@ -63,7 +63,7 @@ ResamplerDesign design_resampler(int in_rate, int out_rate, double fc, int ncoef
     if (fc == 0.0) fc = 0.45 * (double)min_rate;
     const double full_rate = (double)in_rate * d.L;
     const double fc_norm_high = fc / full_rate;
-    const double fc_norm_low = -fc_norm_high;
+    const double fc_norm_low = fc_low < 0.0 ? -fc_norm_high : fc_low / full_rate;    // resample.c:60-63
     if (ncoef == 0) ncoef = (int)(140.0 * full_rate / min_rate);
     ncoef = (ncoef / d.L + 1) * d.L;
     d.ncoef = ncoef;
@@ -72,6 +72,53 @@ ResamplerDesign design_resampler(int in_rate, int out_rate, double fc, int ncoef
     d.h.resize((size_t)ncoef);
     for (int i = 0; i < ncoef; i++) d.h[i] = imp[i].real();
     return d;
+}
+
+// create_resampleF's design, wdsp/resample.c:250-273, the reference's statements in doubles
+ResamplerDesign design_resampler_fv(int in_rate, int out_rate)
+{
+    ResamplerDesign d;
+    int x = in_rate, y = out_rate;
+    while (y != 0) { int z = y; y = x % y; x = z; }
+    d.L = out_rate / x;
+    d.M = in_rate / x;
+    const int min_rate = in_rate < out_rate ? in_rate : out_rate;
+    const double fc = 0.45 * (double)min_rate;
+    const double full_rate = (double)in_rate * d.L;
+    const double fc_norm = fc / full_rate;
+    int ncoef = (int)(60.0 / fc_norm);
+    ncoef = (ncoef / d.L + 1) * d.L;
+    d.ncoef = ncoef;
+    d.cpp = ncoef / d.L;
+    const std::vector<cd> imp = fir_bandpass(ncoef, -fc_norm, +fc_norm, 1.0, 1, 0, (double)d.L);
+    d.h.resize((size_t)ncoef);
+    for (int i = 0; i < ncoef; i++) d.h[(size_t)i] = imp[(size_t)i].real();
+    return d;
+}
+
+// resample.c:64-66 and 265-267 in 64 bits: the caller refuses what the reference's ints do not hold
+void resampler_sizes(int in_rate, int out_rate, int ncoef_in, bool fv, int *L, int *M, long long *ncoef)
+{
+    long long x = in_rate, y = out_rate;
+    while (y != 0) { long long z = y; y = x % y; x = z; }
+    *L = (int)(out_rate / x);
+    *M = (int)(in_rate / x);
+    const int min_rate = in_rate < out_rate ? in_rate : out_rate;
+    const double full_rate = (double)in_rate * *L;
+    long long nc = ncoef_in;
+    if (fv) nc = (long long)(60.0 / (0.45 * (double)min_rate / full_rate));
+    else if (nc == 0) nc = (long long)(140.0 * full_rate / min_rate);
+    *ncoef = (nc / *L + 1) * *L;
+}
+
+// resample.c:69-72: row j holds impulse[j], impulse[j + L], ...
+std::vector<double> resampler_phase_major(const ResamplerDesign &d)
+{
+    std::vector<double> h((size_t)d.ncoef);
+    size_t i = 0;
+    for (int j = 0; j < d.L; j++)
+        for (int k = 0; k < d.ncoef; k += d.L) h[i++] = d.h[(size_t)(j + k)];
+    return h;
 }
 
 // calc_varsamp's sizes, wdsp/varsamp.c:40-51,58-60

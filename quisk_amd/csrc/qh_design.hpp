@@ -19,7 +19,15 @@ std::vector<cd> fir_bandpass(int N, double f_low, double f_high, double samplera
 // WDSP resampler prototype, wdsp/resample.c:35-72: taps in natural (time) order, real.
 // Returns L, M and the tap count; `gain` as in create_resample.
 struct ResamplerDesign { int L, M, ncoef, cpp; std::vector<double> h; };
-ResamplerDesign design_resampler(int in_rate, int out_rate, double fc, int ncoef, double gain);
+ResamplerDesign design_resampler(int in_rate, int out_rate, double fc, int ncoef, double gain, double fc_low = -1.0);
+// fc_low >= 0 is the lower band edge in Hz (resample.c:60-63, setFCLow_resample / setBandwidth_resample); below 0 selects -fc, and the
+// taps are then the ones the five-argument call always gave.
+// create_resampleF's design (resample.c:250-273): fc = 0.45 min_rate, ncoef = (int)(60 / fc_norm) rounded up to a whole row per phase,
+// gain 1.  resampler_sizes: L, M and the rounded ncoef of either design in 64 bits, for the caller's refusals (rates must be positive).
+// resampler_phase_major: h[L][cpp] as calc_resample stores it (resample.c:69-72).
+ResamplerDesign design_resampler_fv(int in_rate, int out_rate);
+void resampler_sizes(int in_rate, int out_rate, int ncoef_in, bool fv, int *L, int *M, long long *ncoef);
+std::vector<double> resampler_phase_major(const ResamplerDesign &d);
 
 // WDSP variable-ratio resampler prototype, calc_varsamp (wdsp/varsamp.c:29-68): nom_ratio = out_rate / in_rate, rsize = (int)(140 *
 // norm_rate / min_rate) taps per output sample, and the R-times oversampled low-pass h of ncoef = rsize * R + 1 real coefficients

@@ -66,6 +66,8 @@ int anb_check_settings(double samplerate, double tau, double hangtime, double ad
 int nob_check_settings(double samplerate, int mode, double slewtime, double hangtime, double advtime, double backtau, double threshold);
 // the same for qh_varsamp_create (qh_varsamp.hip) and create_varsampV
 int varsamp_check_settings(int in_rate, int out_rate, int R, double fc, double fc_low, double gain);
+// the same for qh_resample_create (qh_resample.hip) and create_resampleV / create_resampleFV
+int resample_check_settings(int in_rate, int out_rate, double fc, int ncoef, double gain, int dtype);
 
 // qh_div_process (qh_div.hip) on rows the caller has staged on the device, apart from the output rows: bit i of `alias` says that the
 // caller's receiver i of every group was the very row its output goes to (xdivEXT's out == in[i]), so that it contributes the running sum

@@ -1556,3 +1556,174 @@ int qh_wdsp_xvarsampV_device(void *ptr, const void *d_in, void *d_out, int numsa
 }
 
 }  // extern "C"
+
+// ---- the fixed-ratio resampler beside fexchange0: create_resampleV, xresampleV, destroy_resampleV and the FV names (wdsp/resample.c:206-228,
+// 332-354) ----------------------------------------------------------------------------------------------------------------------------------
+// As the varsamp names above: every pointer a one-channel bank on a stream of its own with staging rows, looked up in a table.  One
+// table holds both kinds, so a V pointer handed to an FV name is refused as well.
+namespace {
+struct ResampleV {
+    qh_resample *b = nullptr;
+    bool fv = false;
+    hipStream_t stream = nullptr;
+    void *d_in = nullptr, *d_out = nullptr;
+    long long cap_in = 0, cap_out = 0;          // samples
+    hipEvent_t ev_in = nullptr, ev_out = nullptr;
+    std::mutex mtx;
+    size_t es() const { return fv ? sizeof(float) : 2 * sizeof(double); }
+};
+std::mutex g_rsv_mtx;
+std::vector<ResampleV *> g_rsv;
+
+void rsv_release(ResampleV *a)
+{
+    if (a->b) qh_resample_destroy(a->b);        // (waits for the stream)
+    (void)hipFree(a->d_in); (void)hipFree(a->d_out);
+    if (a->ev_in) (void)hipEventDestroy(a->ev_in);
+    if (a->ev_out) (void)hipEventDestroy(a->ev_out);
+    if (a->stream) (void)hipStreamDestroy(a->stream);
+    delete a;
+}
+
+// fv < 0: either kind
+ResampleV *rsv_find(void *ptr, int fv, const char *name)
+{
+    g_status = QH_OK;
+    std::lock_guard<std::mutex> lk(g_rsv_mtx);
+    for (ResampleV *a : g_rsv)
+        if (a == ptr && (fv < 0 || a->fv == (fv != 0))) return a;
+    g_status = qh::set_error(QH_ERR_INVALID, "%s: not a pointer create_resample%s returned", name, fv > 0 ? "FV" : "V");
+    return nullptr;
+}
+
+int rsv_row(ResampleV &a, void **row, long long *cap, long long want, const char *name)
+{
+    if (want <= *cap) return QH_OK;
+    if (hipStreamSynchronize(a.stream) != hipSuccess) return qh::set_error(QH_ERR_HIP, "%s: synchronize failed", name);
+    (void)hipFree(*row);
+    *row = nullptr; *cap = 0;
+    want += want / 8 + 64;
+    if (hipMalloc(row, (size_t)want * a.es()) != hipSuccess) { *row = nullptr; return qh::set_error(QH_ERR_HIP, "%s: staging allocation failed", name); }
+    *cap = want;
+    return QH_OK;
+}
+
+void *rsv_create(int in_rate, int out_rate, bool fv, const char *name)
+{
+    g_status = QH_OK;
+    const int dtype = fv ? QH_RESAMPLE_R32 : QH_RESAMPLE_C64;
+    if (int rc = qh::resample_check_settings(in_rate, out_rate, 0.0, 0, 1.0, dtype)) { g_status = rc; return nullptr; }
+    ResampleV *a = new ResampleV();
+    a->fv = fv;
+    if (hipStreamCreateWithFlags(&a->stream, hipStreamNonBlocking) != hipSuccess) {
+        a->stream = nullptr;
+        g_status = qh::set_error(QH_ERR_NO_DEVICE, "%s: no HIP device (libquiskhip has no CPU fallback)", name);
+        rsv_release(a);
+        return nullptr;
+    }
+    a->b = qh_resample_create(0, 1, in_rate, out_rate, 0.0, 0, 1.0, dtype, a->stream);         // resample.c:211, 337
+    if (!a->b) { g_status = QH_ERR_HIP; rsv_release(a); return nullptr; }     // the settings were good: the device (message already set)
+    std::lock_guard<std::mutex> lk(g_rsv_mtx);
+    g_rsv.push_back(a);
+    return a;
+}
+
+void rsv_destroy(void *ptr, bool fv, const char *name)
+{
+    ResampleV *a = rsv_find(ptr, fv, name);
+    if (!a) return;
+    {
+        std::lock_guard<std::mutex> lk(g_rsv_mtx);
+        g_rsv.erase(std::find(g_rsv.begin(), g_rsv.end(), a));
+    }
+    { std::lock_guard<std::mutex> lk(a->mtx); }
+    rsv_release(a);
+}
+
+// resample.c:130-152 with out == in: output m is written behind the input it is made at only while m <= p / L, which holds for every m
+// where L <= M; where L > M the reference overwrites inputs it has yet to read
+bool rsv_in_place_ok(ResampleV &a) { return qh_resample_L(a.b, 0) <= qh_resample_M(a.b, 0); }
+
+void rsv_x(const void *input, void *output, int numsamps, int *outsamps, void *ptr, bool fv, const char *name)
+{
+    if (outsamps) *outsamps = 0;
+    ResampleV *a = rsv_find(ptr, fv, name);
+    if (!a) return;
+    std::lock_guard<std::mutex> lk(a->mtx);
+    if (!outsamps || numsamps < 0 || (numsamps > 0 && (!input || !output))) { g_status = qh::set_error(QH_ERR_INVALID, "%s: bad arguments", name); return; }
+    if (numsamps > 0 && input == output && !rsv_in_place_ok(*a)) {
+        g_status = qh::set_error(QH_ERR_INVALID, "%s: input == output needs L <= M (the reference overwrites samples it has yet to read)", name);
+        return;
+    }
+    const long long mo = qh_resample_max_out(a->b, numsamps);
+    if (mo < 0) { g_status = (int)mo; return; }
+    if (int rc = rsv_row(*a, &a->d_in, &a->cap_in, numsamps, name)) { g_status = rc; return; }
+    if (int rc = rsv_row(*a, &a->d_out, &a->cap_out, mo, name)) { g_status = rc; return; }
+    const size_t es = a->es();
+    if (numsamps > 0 && hipMemcpyAsync(a->d_in, input, (size_t)numsamps * es, hipMemcpyHostToDevice, a->stream) != hipSuccess) {
+        g_status = qh::set_error(QH_ERR_HIP, "%s: upload failed", name);
+        return;
+    }
+    int count = 0;
+    if (int rc = qh_resample_process(a->b, a->d_in, std::max(numsamps, 1), a->d_out, std::max<long long>(mo, 1), numsamps, &count)) { g_status = rc; return; }
+    if ((count > 0 && hipMemcpyAsync(output, a->d_out, (size_t)count * es, hipMemcpyDeviceToHost, a->stream) != hipSuccess) ||
+        hipStreamSynchronize(a->stream) != hipSuccess) {
+        g_status = qh::set_error(QH_ERR_HIP, "%s: download failed", name);
+        return;
+    }
+    *outsamps = count;
+}
+
+int rsv_x_device(void *ptr, const void *d_in, void *d_out, int numsamps, int *outsamps, void *stream, bool fv, const char *name)
+{
+    if (outsamps) *outsamps = 0;
+    ResampleV *a = rsv_find(ptr, fv, name);
+    if (!a) return g_status;
+    std::lock_guard<std::mutex> lk(a->mtx);
+    if (numsamps < 0 || !outsamps || (numsamps > 0 && (!d_in || !d_out))) return g_status = qh::set_error(QH_ERR_INVALID, "%s: bad arguments", name);
+    if (numsamps > 0 && d_in == d_out && !rsv_in_place_ok(*a))
+        return g_status = qh::set_error(QH_ERR_INVALID, "%s: d_in == d_out needs L <= M (the reference overwrites samples it has yet to read)", name);
+    const long long mo = qh_resample_max_out(a->b, numsamps);
+    if (mo < 0) return g_status = (int)mo;
+    if (int rc = rsv_row(*a, &a->d_in, &a->cap_in, numsamps, name)) return g_status = rc;
+    hipStream_t cs = (hipStream_t)stream;
+    if (!a->ev_in && (hipEventCreateWithFlags(&a->ev_in, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&a->ev_out, hipEventDisableTiming) != hipSuccess))
+        return g_status = qh::set_error(QH_ERR_HIP, "%s: event creation failed", name);
+    if (cs != a->stream) { (void)hipEventRecord(a->ev_in, cs); (void)hipStreamWaitEvent(a->stream, a->ev_in, 0); }
+    int rc = QH_OK;
+    if (numsamps > 0 && hipMemcpyAsync(a->d_in, d_in, (size_t)numsamps * a->es(), hipMemcpyDeviceToDevice, a->stream) != hipSuccess)
+        rc = qh::set_error(QH_ERR_HIP, "%s: copy failed", name);
+    if (!rc) rc = qh_resample_process(a->b, a->d_in, std::max(numsamps, 1), d_out, std::max<long long>(mo, 1), numsamps, outsamps);
+    if (cs != a->stream) { (void)hipEventRecord(a->ev_out, a->stream); (void)hipStreamWaitEvent(cs, a->ev_out, 0); }
+    return g_status = rc;
+}
+}  // namespace
+
+extern "C" {
+
+void *create_resampleV(int in_rate, int out_rate) { return rsv_create(in_rate, out_rate, false, "create_resampleV"); }
+void *create_resampleFV(int in_rate, int out_rate) { return rsv_create(in_rate, out_rate, true, "create_resampleFV"); }
+void destroy_resampleV(void *ptr) { rsv_destroy(ptr, false, "destroy_resampleV"); }
+void destroy_resampleFV(void *ptr) { rsv_destroy(ptr, true, "destroy_resampleFV"); }
+void xresampleV(double *input, double *output, int numsamps, int *outsamps, void *ptr) { rsv_x(input, output, numsamps, outsamps, ptr, false, "xresampleV"); }
+void xresampleFV(float *input, float *output, int numsamps, int *outsamps, void *ptr) { rsv_x(input, output, numsamps, outsamps, ptr, true, "xresampleFV"); }
+
+long long qh_wdsp_resampleV_max_out(void *ptr, int numsamps)
+{
+    ResampleV *a = rsv_find(ptr, -1, "qh_wdsp_resampleV_max_out");
+    if (!a) return g_status;
+    const long long mo = qh_resample_max_out(a->b, numsamps);
+    if (mo < 0) g_status = (int)mo;
+    return mo;
+}
+
+int qh_wdsp_xresampleV_device(void *ptr, const void *d_in, void *d_out, int numsamps, int *outsamps, void *stream)
+{
+    return rsv_x_device(ptr, d_in, d_out, numsamps, outsamps, stream, false, "qh_wdsp_xresampleV_device");
+}
+int qh_wdsp_xresampleFV_device(void *ptr, const void *d_in, void *d_out, int numsamps, int *outsamps, void *stream)
+{
+    return rsv_x_device(ptr, d_in, d_out, numsamps, outsamps, stream, true, "qh_wdsp_xresampleFV_device");
+}
+
+}  // extern "C"

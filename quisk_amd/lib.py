@@ -346,6 +346,35 @@ def load():
     L.qh_wdsp_varsampV_max_out.argtypes = [vp, i, d]
     L.qh_wdsp_varsampV_max_out.restype = ll
     L.qh_wdsp_xvarsampV_device.argtypes = [vp, vp, vp, i, d, vp, vp]
+    # WDSP's fixed-ratio resampler (wdsp/resample.c): the bank and the V / FV names beside fexchange0
+    L.qh_resample_create.restype = vp
+    L.qh_resample_create.argtypes = [i, i, i, i, d, i, d, i, vp]
+    L.qh_resample_destroy.argtypes = [vp]
+    L.qh_resample_destroy.restype = None
+    for n in ("flush", "L", "M", "cpp"):
+        getattr(L, "qh_resample_" + n).argtypes = [vp, i]
+    L.qh_resample_set_run.argtypes = [vp, i, i]
+    L.qh_resample_set_rates.argtypes = [vp, i, i, i]
+    L.qh_resample_set_fc_low.argtypes = [vp, i, d]
+    L.qh_resample_set_bandwidth.argtypes = [vp, i, d, d]
+    L.qh_resample_taps.argtypes = [vp, i, vp, i]
+    L.qh_resample_out_count.argtypes = [vp, i, i]
+    L.qh_resample_out_count.restype = ll
+    L.qh_resample_max_out.argtypes = [vp, i]
+    L.qh_resample_max_out.restype = ll
+    L.qh_resample_synchronize.argtypes = [vp]
+    L.qh_resample_process.argtypes = [vp, vp, ll, vp, ll, i, vp]
+    L.qh_resample_process_host.argtypes = [vp, vp, ll, vp, ll, i, vp]
+    for n in ("V", "FV"):
+        getattr(L, "create_resample" + n).restype = vp
+        getattr(L, "create_resample" + n).argtypes = [i, i]
+        getattr(L, "xresample" + n).argtypes = [vp, vp, i, C.POINTER(i), vp]
+        getattr(L, "xresample" + n).restype = None
+        getattr(L, "destroy_resample" + n).argtypes = [vp]
+        getattr(L, "destroy_resample" + n).restype = None
+        getattr(L, "qh_wdsp_xresample%s_device" % n).argtypes = [vp, vp, vp, i, C.POINTER(i), vp]
+    L.qh_wdsp_resampleV_max_out.argtypes = [vp, i]
+    L.qh_wdsp_resampleV_max_out.restype = ll
     # WDSP's diversity combiner (wdsp/div.c): the bank and the EXT names between the blankers and fexchange0
     L.qh_div_create.restype = vp
     L.qh_div_create.argtypes = [i, i, i, i, vp]

@@ -486,6 +486,130 @@ class WdspVarResampler:
             pass
 
 
+class WdspResampler:
+    """WDSP's fixed-ratio resampler (xresample / xresampleF, wdsp/resample.c:121-157, 296-330) for `nch` streams, every channel with its
+    own design, run and state; keyword names as create_resample's.  dtype "c64": complex128 samples; "r32": float32 samples with the
+    ring, the taps and the sums in doubles and create_resampleF's design (fc, ncoef and gain are not used there).  A call takes n input
+    samples and makes ceil((n L - phnum) / M) of every channel: the counts come back with the samples.  The setters take a channel, or
+    -1 for every channel."""
+
+    C64, R32 = 0, 1
+
+    def __init__(self, nch, in_rate, out_rate, fc=0.0, ncoef=0, gain=1.0, dtype="c64", device=0, stream=None):
+        self._L = load()
+        if dtype not in ("c64", "r32"):
+            raise ValueError("dtype is 'c64' or 'r32'")
+        self.dtype = dtype
+        self.np_dtype = np.complex128 if dtype == "c64" else np.float32
+        self._h = self._L.qh_resample_create(device, nch, int(in_rate), int(out_rate), fc, int(ncoef), gain, self.C64 if dtype == "c64" else self.R32,
+                                             stream)
+        if not self._h:
+            raise QuiskHipError("qh_resample_create failed: %s" % self._L.qh_last_error().decode(errors="replace"))
+        self.nch = nch
+        self._own_stream = stream is None
+
+    def set_run(self, run, ch=-1):
+        check(self._L.qh_resample_set_run(self._h, ch, int(run)))
+
+    def set_rates(self, in_rate, out_rate, ch=-1):
+        """setInRate_resample / setOutRate_resample: a new design, and the channel starts over"""
+        check(self._L.qh_resample_set_rates(self._h, ch, int(in_rate), int(out_rate)))
+
+    def set_fc_low(self, fc_low, ch=-1):
+        check(self._L.qh_resample_set_fc_low(self._h, ch, fc_low))
+
+    def set_bandwidth(self, fc_low, fc_high, ch=-1):
+        check(self._L.qh_resample_set_bandwidth(self._h, ch, fc_low, fc_high))
+
+    def flush(self, ch=-1):
+        check(self._L.qh_resample_flush(self._h, ch))
+
+    def L(self, ch=0):
+        return self._L.qh_resample_L(self._h, ch)
+
+    def M(self, ch=0):
+        return self._L.qh_resample_M(self._h, ch)
+
+    def cpp(self, ch=0):
+        """the taps of one output sample of channel ch"""
+        return self._L.qh_resample_cpp(self._h, ch)
+
+    def taps(self, ch=0):
+        """the phase-major h[L, cpp] in force on channel ch"""
+        h = np.empty((self.L(ch), self.cpp(ch)), dtype=np.float64)
+        r = self._L.qh_resample_taps(self._h, ch, h.ctypes.data, h.size)
+        if r != h.size:
+            check(r if r < 0 else -2)
+        return h
+
+    def out_count(self, n, ch=0):
+        """what the next call of n samples makes of channel ch"""
+        m = self._L.qh_resample_out_count(self._h, ch, int(n))
+        if m < 0:
+            check(int(m))
+        return int(m)
+
+    def max_out(self, n):
+        """the most samples a call of n samples can write to any output row"""
+        m = self._L.qh_resample_max_out(self._h, int(n))
+        if m < 0:
+            check(int(m))
+        return int(m)
+
+    def process_ptr(self, d_in, in_stride, d_out, out_stride, n):
+        """Device pointers, strides in samples, out_stride >= max_out(n); rows of d_out apart from those of d_in.  Asynchronous on the
+        bank's stream -> counts [nch]"""
+        counts = np.zeros(self.nch, dtype=np.int32)
+        check(self._L.qh_resample_process(self._h, d_in, in_stride, d_out, out_stride, int(n), counts.ctypes.data))
+        return counts
+
+    def process(self, x, out=None):
+        """x: a torch device tensor [nch, n] of the bank's sample type, rows contiguous -> (y [nch, max_out(n)], counts [nch]); row c of y
+        holds counts[c] samples.  `out`: a tensor to write to in place of a new one.  Asynchronous on the bank's stream: y is complete
+        after synchronize().  A bank made with stream=None runs on a stream of its own, so torch's current stream is waited for first
+        (x has to be there); pass stream=torch.cuda.current_stream().cuda_stream to stay in torch's order with no wait at all."""
+        import torch
+        want = torch.complex128 if self.dtype == "c64" else torch.float32
+        if x.dim() != 2 or x.shape[0] != self.nch or x.dtype != want or not x.is_cuda or x.stride(1) != 1:
+            raise ValueError("expected a device tensor [nch, n] of %s with contiguous rows" % want)
+        n = x.shape[1]
+        mo = max(self.max_out(n), 1)
+        if out is None:
+            out = torch.zeros((self.nch, mo), dtype=want, device=x.device)
+        elif out.dim() != 2 or out.shape[0] != self.nch or out.dtype != want or not out.is_cuda or out.stride(1) != 1 or out.shape[1] < mo:
+            raise ValueError("out: a device tensor [nch, >= max_out(n)] of %s with contiguous rows" % want)
+        if self._own_stream:
+            torch.cuda.current_stream(x.device).synchronize()
+        return out, self.process_ptr(x.data_ptr(), x.stride(0) if n else 1, out.data_ptr(), out.stride(0), n)
+
+    def process_host(self, x):
+        """x [nch, n] -> (y [nch, max_out(n)], counts [nch]); row c of y holds counts[c] samples (the n copied ones of a channel that
+        does not run), zeros behind"""
+        x = np.ascontiguousarray(x, dtype=self.np_dtype)
+        if x.ndim != 2 or x.shape[0] != self.nch:
+            raise ValueError("expected [nch, n]")
+        n = x.shape[1]
+        mo = max(self.max_out(n), 1)
+        out = np.zeros((self.nch, mo), dtype=self.np_dtype)
+        counts = np.zeros(self.nch, dtype=np.int32)
+        check(self._L.qh_resample_process_host(self._h, x.ctypes.data, max(n, 1), out.ctypes.data, mo, n, counts.ctypes.data))
+        return out, counts
+
+    def synchronize(self):
+        check(self._L.qh_resample_synchronize(self._h))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.qh_resample_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class WdspDiversity:
     """WDSP's diversity combiner DIV (xdiv, wdsp/div.c:67-95) for `ngroups` groups of up to eight phase-coherent receivers, every group
     with its own run, nr, output and rotate factors.  run = 0 gives receiver 0, output != nr gives receiver `output`, output == nr the sum
