@@ -294,6 +294,26 @@ int qh_rxa_timing(qh_rxa *e, double *ms, int n);
  * the overlap-save stages do not cover) keep their own memory and are not included. */
 long long qh_rxa_device_bytes(const qh_rxa *e);
 
+/* The run-time rate and buffer-size setters of wdsp/channel.c:169-258 on a live engine.  Every per-channel setting survives; a call that
+ * changes nothing does nothing (channel.c's `if (x != ch[channel].x)`: the captured launch sequences stay too); a value qh_rxa_create
+ * would refuse, a dsp_size above a channel's nc (nbp.c:308) or a dsp_size change under an attached display is refused with create's
+ * status and changes nothing.  What each change does to each stage's state follows setInputSamplerate_rxa ... setDSPBuffsize_rxa
+ * (wdsp/RXA.c:600-740), tabled in DESIGN.md row b24: a new in_rate restarts the shift at phase 0 and makes rsmpin anew, a new out_rate
+ * makes rsmpout anew -- both leave everything at the DSP rate running; a new dsp_rate or dsp_size starts every stage from zero, except
+ * what the reference keeps: anf / anr's lidx and ngamma and snba's frame memory (both changes); the delay lines of nbp0, bp1, eqp and
+ * xfmd's filters (nc <= 4096) and the SAM detector's sideband chains (a new dsp_rate); the whole AM / SAM detector and gen0's phases and
+ * positions, its pulse flushed (a new dsp_size).
+ * qh_rxa_dsp_insize / _outsize and qh_rxa_device_bytes follow. */
+int qh_rxa_set_rates(qh_rxa *e, int in_rate, int dsp_rate, int out_rate);    /* SetAllRates, wdsp/channel.c:242-258 */
+int qh_rxa_set_in_rate(qh_rxa *e, int in_rate);                              /* SetInputSamplerate, wdsp/channel.c:198-210 + RXA.c:600-614 */
+int qh_rxa_set_dsp_rate(qh_rxa *e, int dsp_rate);                            /* SetDSPSamplerate, wdsp/channel.c:212-226 + RXA.c:627-671 */
+int qh_rxa_set_out_rate(qh_rxa *e, int out_rate);                            /* SetOutputSamplerate, wdsp/channel.c:228-240 + RXA.c:616-625 */
+int qh_rxa_set_dsp_size(qh_rxa *e, int dsp_size);                            /* SetDSPBuffsize, wdsp/channel.c:182-196 + RXA.c:673-740 */
+int qh_rxa_in_rate(const qh_rxa *e);                                         /* ch[].in_rate, wdsp/channel.c:81 */
+int qh_rxa_dsp_rate(const qh_rxa *e);                                        /* ch[].dsp_rate, wdsp/channel.c:82 */
+int qh_rxa_out_rate(const qh_rxa *e);                                        /* ch[].out_rate, wdsp/channel.c:83 */
+int qh_rxa_dsp_size(const qh_rxa *e);                                        /* ch[].dsp_size, wdsp/channel.c:80 */
+
 /* ------------------------------------------------------------------ 2. WDSP drop-in exports */
 /* Signatures are the reference's: wdsp/channel.h:62, wdsp/iobuffs.h:89-90, and the PORT functions
  * cited per line.  Channel numbers 0..31 (wdsp/comm.h:117).  Each open channel is a 1-channel
@@ -304,6 +324,25 @@ void OpenChannel(int channel, int in_size, int dsp_size, int input_samplerate, i
                  double tdelaydown, double tslewdown, int bfo);                  /* wdsp/channel.c:75-103 */
 void CloseChannel(int channel);                                                  /* wdsp/channel.c:122-128 */
 int SetChannelState(int channel, int state, int dmode);                          /* wdsp/channel.c:260-298 */
+/* The channel's run-time setters.  Each rebuilds the iobuffs as pre_main_destroy / post_main_destroy / pre_main_build do (out_size, the
+ * rings as create_iobuffs leaves them, the slews from the stored times at the new rates, the staging; samples in flight are lost) and
+ * hands the engine its part (qh_rxa_set_*).  SetDSPBuffsize and SetDSPSamplerate bracket the change with SetChannelState(channel, 0, 1)
+ * and SetChannelState(channel, old, 0): a channel that was running has its up-slew armed again; the others arm nothing.  A value the
+ * engine refuses (qh_rxa_set_rates), an in_size <= 0 or a channel that is not open sets qh_wdsp_status() and changes nothing.  SetType:
+ * type 0 does nothing, any other type is refused (QH_ERR_UNSUPPORTED) as OpenChannel does.  The re-blocking shim (wdspFexchange0) holds
+ * its own in_size (qh_wdsp_set_parameter) and its ring, on the host or the device, is sized by that: SetInputBuffsize does not touch it,
+ * and qh_wdsp_fexchange0_device refuses to run while the two sizes differ -- give the shim the new size with qh_wdsp_set_parameter. */
+void SetType(int channel, int type);                                             /* wdsp/channel.c:158-167 */
+void SetInputBuffsize(int channel, int in_size);                                 /* wdsp/channel.c:169-180 */
+void SetDSPBuffsize(int channel, int dsp_size);                                  /* wdsp/channel.c:182-196 */
+void SetInputSamplerate(int channel, int samplerate);                            /* wdsp/channel.c:198-210 */
+void SetDSPSamplerate(int channel, int samplerate);                              /* wdsp/channel.c:212-226 */
+void SetOutputSamplerate(int channel, int samplerate);                           /* wdsp/channel.c:228-240 */
+void SetAllRates(int channel, int in_rate, int dsp_rate, int out_rate);          /* wdsp/channel.c:242-258 */
+void SetChannelTDelayUp(int channel, double time);                               /* wdsp/channel.c:301-311: flush_slews */
+void SetChannelTSlewUp(int channel, double time);                                /* wdsp/channel.c:313-323: the slews are made anew */
+void SetChannelTDelayDown(int channel, double time);                             /* wdsp/channel.c:325-335: flush_slews */
+void SetChannelTSlewDown(int channel, double time);                              /* wdsp/channel.c:337-347: the slews are made anew */
 void fexchange0(int channel, double *in, double *out, int *error);               /* wdsp/iobuffs.c:464-516 */
 void fexchange2(int channel, float *Iin, float *Qin, float *Iout, float *Qout, int *error);     /* wdsp/iobuffs.c:518-582 */
 void SetRXAMode(int channel, int mode);                                          /* wdsp/RXA.c:748-787 */

@@ -190,6 +190,9 @@ struct Fircore {
     // with nc > 4096 since RXASetNC last zeroed its lines, so it holds more than the one-tile form has room for (Engine::plan_long)
     struct Chan { bool listed = false, long_live = false; int at = 0; };
     std::vector<Chan> chan;
+    // Engine::rebuild has put the delay lines the stage held before a change of the DSP rate in place (setImpulse_fircore(..., 1) keeps
+    // them, firmin.c:449-453): the fc_alloc that makes the stage keeps them and the rows' places, once
+    bool carried = false;
     void flip() { cur ^= 1; }
 };
 
@@ -454,6 +457,8 @@ struct Engine {
     int quiesce();
     // (Re)allocate p for n elements (dev_alloc), zeroed on `stream` when asked.  A buffer p held is freed first: the caller has quiesced.
     template <typename T> int alloc(T *&p, long long n, bool zero = false);
+    // give a buffer alloc() made back (the caller has quiesced)
+    template <typename T> void release(T *&p) { if (p) { (void)hipFree(p); owned.erase(p); p = nullptr; } }
     // p holds cap units of `unit` elements: when need is more, quiesce and reallocate it for need units
     template <typename T> int grow(T *&p, long long &cap, long long need, long long unit);
     int process_replayed(const double *d_in, long long in_stride, double *d_out, long long out_stride, int nblk);
@@ -479,6 +484,18 @@ struct Engine {
 
     ~Engine();
     int init();
+    // init's two rate-dependent ends, each made again on its own when its rate changes (set_rates): the front stage for in_rate / dsp_rate
+    // (dsp_insize, D, the overlap-save tables and delay line or the polyphase rsmpin) and rsmpout for dsp_rate / out_rate (dsp_outsize)
+    int front_build();
+    int out_build();
+    // The run-time setters of wdsp/channel.c:169-258 on a live engine (qh_rxa_set_rates ...): see the definition for what survives
+    int set_rates(int new_in, int new_dsp, int new_out, int new_size);
+    int rebuild(int new_in, int new_dsp, int new_out, int new_size, int new_D);
+    // State of stages that are made on first use, read off the device by rebuild and waiting for the allocation that makes the stage
+    // again (stages_alloc, snba_alloc, gen_alloc take it and empty it): anf / anr's lidx and ngamma [nch][2] (flush_anf / flush_anr leave
+    // them, anf.c:135-140), snba's frame memory [nch][2 kSnbX] (xbase / xaux are create_snba's, calc_snba does not touch them,
+    // snb.c:31-66) and, across a new dsp_size, gen0's phases and positions [nch] (setSize_gen only flushes the pulse, gen.c:160-163,369-373)
+    struct Carry { std::vector<double> lms[2], snba_frames; std::vector<GenState> gen; } carry;
     int flush();
     // what the parameter side needs of the kernels, defined where they are launched from (qh_engine.hip): the dynamic-LDS limits of the
     // tile kernels and of emnr_kernel, and the launches of refresh_params and flush
@@ -585,6 +602,12 @@ struct Engine {
     long long obuf_cap = 0;
     void tick(int cat);
 };
+
+// What qh_rxa_create accepts (wdsp/channel.c:39-52): the status it sets, QH_OK with *D = in_rate / dsp_rate where the overlap-save front
+// stage covers the ratio (1, 2, 4, 8, 16), else 0 (the polyphase form of xresample).  `who` heads the message.
+int check_rates(const char *who, int dsp_size, int in_rate, int dsp_rate, int out_rate, int *D);
+// whether two of an EQ profile's frequencies coincide after eq_impulse's clamp to [0, 1] (eq.c:53-55) while their gains differ
+bool eqp_profile_tie(const std::vector<double> &F, const std::vector<double> &G, double rate);
 
 // egress_pack_kernel over nch rows of n samples (Engine::pack_audio, qh_audio_pack)
 void launch_egress_pack(const double2 *src, long long src_stride, int nch, long long n, const EgressFmt &f, hipStream_t s);

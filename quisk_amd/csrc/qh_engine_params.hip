@@ -3,6 +3,7 @@
 // Host code only: the few kernels that rewrite state for new parameters (oscillator retune, front masks, SSQL flush) are launched through
 // Engine::launch_* of qh_engine.hip, so this unit's object holds no device code.  No ABI function lives here (qh_rxa_api.hip).
 #include "qh_engine.hpp"
+#include <new>
 
 namespace qh {
 
@@ -50,12 +51,42 @@ int Engine::quiesce()
     return QH_OK;
 }
 
-int Engine::init()
+int check_rates(const char *who, int dsp_size, int in_rate, int dsp_rate, int out_rate, int *D)
 {
-    QH_HIP(hipSetDevice(device));
-    if (!stream) { QH_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking)); own_stream = true; }
-    // pre_main_build, wdsp/channel.c:39-47
+    if (dsp_size <= 0 || (dsp_size & (dsp_size - 1)) || in_rate <= 0 || dsp_rate <= 0) return set_error(QH_ERR_INVALID, "%s: bad arguments", who);
+    if (out_rate <= 0 || (out_rate % dsp_rate && dsp_rate % out_rate) || (out_rate < dsp_rate && dsp_size % (dsp_rate / out_rate)))
+        return set_error(QH_ERR_UNSUPPORTED, "out_rate must be an integer multiple or fraction of dsp_rate (wdsp/channel.c:47-52)");
+    // in_rate / dsp_rate 1, 2, 4, 8, 16: the overlap-save front stage.  Any other whole ratio, up or down (3, 5, 6 ...; 1/2,
+    // 1/4 ...): xshift as a pointwise pass + the polyphase form of xresample (wdsp/resample.c:35-157) -- D = 0 marks it.  The
+    // reference sizes its blocks with integer divisions of the two rates (pre_main_build, wdsp/channel.c:39-42): a ratio that is
+    // not whole one way or the other does not give it consistent block sizes, and is refused here.
+    *D = (in_rate % dsp_rate) ? 0 : in_rate / dsp_rate;
+    if (*D != 1 && *D != 2 && *D != 4 && *D != 8 && *D != 16) *D = 0;
+    if (*D == 0 && !((in_rate > dsp_rate && in_rate % dsp_rate == 0) ||
+                     (in_rate < dsp_rate && dsp_rate % in_rate == 0 && dsp_size % (dsp_rate / in_rate) == 0)))
+        // (a CPU test of the reference's arithmetic, test_rates_that_are_whole_in_neither_direction_recycle_stale_buffer_tails, shows what it
+        // does with 96 k -> 64 k -> 48 k: every block's tail is what the block before left in the buffer)
+        return set_error(QH_ERR_UNSUPPORTED, "in_rate / dsp_rate must be a whole number or the reciprocal of one (wdsp/channel.c:39-42)");
+    return QH_OK;
+}
+
+bool eqp_profile_tie(const std::vector<double> &F, const std::vector<double> &G, double rate)
+{
+    for (size_t i = 1; i < F.size(); i++)
+        for (size_t j = i + 1; j < F.size(); j++) {
+            const double a = std::min(1.0, std::max(0.0, 2.0 * F[i] / rate)), b = std::min(1.0, std::max(0.0, 2.0 * F[j] / rate));
+            if (a == b && G[i] != G[j]) return true;
+        }
+    return false;
+}
+
+// xresample in (wdsp/RXA.c:48-57) for in_rate / dsp_rate: D > 1 the overlap-save tile stage and its delay line, zeroed; D = 0 the polyphase
+// rsmpin; D = 1 neither (RXAResCheck, RXA.c:789-798).  What an earlier ratio had made and this one does not use is given back.
+int Engine::front_build()
+{
+    // pre_main_build, wdsp/channel.c:39-42
     dsp_insize = D > 0 ? dsp_size * D : (int)((long long)dsp_size * in_rate / dsp_rate);
+    if (rsmpin) { qh_rat_destroy(rsmpin); rsmpin = nullptr; }
     if (D == 0) {
         // create_resample(..., in_rate, dsp_rate, 0.0, 0, 1.0), wdsp/RXA.c:48-57
         const ResamplerDesign rd = design_resampler(in_rate, dsp_rate, 0.0, 0, 1.0);
@@ -64,34 +95,6 @@ int Engine::init()
         rsmpin = qh_rat_create(device, nch, taps.data(), rd.ncoef, rd.L, rd.M, QH_F64, stream);
         if (!rsmpin) return QH_ERR_HIP;
     }
-    dsp_outsize = out_rate >= dsp_rate ? dsp_size * (out_rate / dsp_rate) : dsp_size / (dsp_rate / out_rate);    // channel.c:47-50
-    if (out_rate != dsp_rate) {
-        // create_resample(..., dsp_rate, out_rate, 0.0, 0, 1.0), wdsp/RXA.c:474-484; the polyphase loop of xresample
-        // (resample.c:120-157) is quisk_cInterpDecim's with the gain already in the taps
-        const ResamplerDesign rd = design_resampler(dsp_rate, out_rate, 0.0, 0, 1.0);
-        std::vector<double> taps(rd.h);
-        for (double &v : taps) v /= (double)rd.L;
-        rsmpout = qh_rat_create(device, nch, taps.data(), rd.ncoef, rd.L, rd.M, QH_F64, stream);
-        if (!rsmpout) return QH_ERR_HIP;
-    }
-    cfg.assign((size_t)nch, ChanCfg());
-    for (ChanCfg &c : cfg) c.eqp_nc = std::max(2048, dsp_size);        // create_eqp's nc, RXA.c:265
-    snba_tune_h.assign((size_t)nch, SnbaTune{ 64, 2, 10, 2, 2, 0, 8.0, 20.0, 0.5 });         // create_snba's arguments, RXA.c:183-202
-    // the fircore stages: the FM pair and xfmsq's noise filter share one design among their channels, the others hold one per channel
-    for (int s = 0; s < FC_COUNT; s++) {
-        fc[s].mask_stride = s == FC_DE || s == FC_AUD || s == FC_FQ ? 0 : kBandNfftMax;
-        fc[s].chan.assign((size_t)nch, Fircore::Chan());
-    }
-    fc[FC_NBP].dirty = &ChanCfg::nbp_dirty; fc[FC_BP1].dirty = &ChanCfg::bp1_dirty; fc[FC_SNB].dirty = &ChanCfg::snb_dirty;
-    fc[FC_FQ].can_long = fc[FC_EQP].can_long = false;
-
-    std::vector<cd> tw = fft_twiddle_table(kNfft);
-    if (int rc = alloc(tw4096, (long long)tw.size())) return rc;
-    if (int rc = upload(tw4096, tw, stream)) return rc;
-    tw = fft_twiddle_table(kBandNfftMax);
-    if (int rc = alloc(tw8192, (long long)tw.size())) return rc;
-    if (int rc = upload(tw8192, tw, stream)) return rc;
-
     if (D > 1) {
         // calc_resample, wdsp/resample.c:35-72 (L = 1): y[m] = sum_j h[j] x[D*m - j]
         ResamplerDesign rd = design_resampler(in_rate, dsp_rate, 0.0, 0, 1.0);
@@ -115,7 +118,55 @@ int Engine::init()
         if (int rc = alloc(tw_inv_front, (long long)twi.size())) return rc;
         if (int rc = upload(tw_inv_front, twi, stream)) return rc;
         for (double2 *&h : hist_front) if (int rc = alloc(h, (long long)nch * kHistFront, true)) return rc;
+    } else {
+        front_fold = front_pick = 1; front_ntaps = front_P = front_L = 0;
+        release(mask_front); release(lane_rot); release(front_taps); release(retune_list); release(retune_law); release(tw_inv_front);
+        for (double2 *&h : hist_front) release(h);
     }
+    return QH_OK;
+}
+
+// xresample out (wdsp/RXA.c:474-484) for dsp_rate / out_rate; none when the two are equal (RXAResCheck, RXA.c:789-798)
+int Engine::out_build()
+{
+    dsp_outsize = out_rate >= dsp_rate ? dsp_size * (out_rate / dsp_rate) : dsp_size / (dsp_rate / out_rate);    // channel.c:44-47
+    if (rsmpout) { qh_rat_destroy(rsmpout); rsmpout = nullptr; }
+    if (out_rate != dsp_rate) {
+        // create_resample(..., dsp_rate, out_rate, 0.0, 0, 1.0), wdsp/RXA.c:474-484; the polyphase loop of xresample
+        // (resample.c:120-157) is quisk_cInterpDecim's with the gain already in the taps
+        const ResamplerDesign rd = design_resampler(dsp_rate, out_rate, 0.0, 0, 1.0);
+        std::vector<double> taps(rd.h);
+        for (double &v : taps) v /= (double)rd.L;
+        rsmpout = qh_rat_create(device, nch, taps.data(), rd.ncoef, rd.L, rd.M, QH_F64, stream);
+        if (!rsmpout) return QH_ERR_HIP;
+    }
+    return QH_OK;
+}
+
+int Engine::init()
+{
+    QH_HIP(hipSetDevice(device));
+    if (!stream) { QH_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking)); own_stream = true; }
+    cfg.assign((size_t)nch, ChanCfg());
+    for (ChanCfg &c : cfg) c.eqp_nc = std::max(2048, dsp_size);        // create_eqp's nc, RXA.c:265
+    snba_tune_h.assign((size_t)nch, SnbaTune{ 64, 2, 10, 2, 2, 0, 8.0, 20.0, 0.5 });         // create_snba's arguments, RXA.c:183-202
+    // the fircore stages: the FM pair and xfmsq's noise filter share one design among their channels, the others hold one per channel
+    for (int s = 0; s < FC_COUNT; s++) {
+        fc[s].mask_stride = s == FC_DE || s == FC_AUD || s == FC_FQ ? 0 : kBandNfftMax;
+        fc[s].chan.assign((size_t)nch, Fircore::Chan());
+    }
+    fc[FC_NBP].dirty = &ChanCfg::nbp_dirty; fc[FC_BP1].dirty = &ChanCfg::bp1_dirty; fc[FC_SNB].dirty = &ChanCfg::snb_dirty;
+    fc[FC_FQ].can_long = fc[FC_EQP].can_long = false;
+
+    std::vector<cd> tw = fft_twiddle_table(kNfft);
+    if (int rc = alloc(tw4096, (long long)tw.size())) return rc;
+    if (int rc = upload(tw4096, tw, stream)) return rc;
+    tw = fft_twiddle_table(kBandNfftMax);
+    if (int rc = alloc(tw8192, (long long)tw.size())) return rc;
+    if (int rc = upload(tw8192, tw, stream)) return rc;
+
+    if (int rc = front_build()) return rc;
+    if (int rc = out_build()) return rc;
     if (int rc = fc_alloc(fc[FC_NBP])) return rc;
     if (int rc = fc_alloc(fc[FC_BP1])) return rc;
     if (int rc = alloc(nco_phase, nch, true)) return rc;
@@ -294,6 +345,7 @@ int Engine::put_taps(Fircore &f, int row, const std::vector<cd> &h, std::vector<
 int Engine::fc_alloc(Fircore &f)
 {
     if (int rc = alloc(f.mask, (f.mask_stride ? (long long)nch : 1LL) * kBandNfftMax)) return rc;
+    if (f.carried) { f.carried = false; return QH_OK; }
     for (double2 *&h : f.hist) if (int rc = alloc(h, (long long)nch * kHistBand, true)) return rc;
     for (Fircore::Chan &r : f.chan) { r.listed = false; r.at = f.cur; }
     return QH_OK;
@@ -520,7 +572,10 @@ int Engine::gen_alloc()
     for (int i = 0; i <= gen_pntrans; i++) { ct[(size_t)i] = 0.5 * (1.0 - std::cos(theta)); theta += delta; }
     if (int rc = alloc(gen_ctrans, (long long)ct.size())) return rc;
     QH_HIP(hipMemcpyAsync(gen_ctrans, ct.data(), ct.size() * sizeof(double), hipMemcpyHostToDevice, stream));
+    if (carry.gen.size() == (size_t)nch)        // the state a new dsp_size left standing (Engine::rebuild)
+        QH_HIP(hipMemcpyAsync(gen_state, carry.gen.data(), (size_t)nch * sizeof(GenState), hipMemcpyHostToDevice, stream));
     QH_HIP(hipStreamSynchronize(stream));
+    carry.gen.clear();
     gen_prm_h.assign((size_t)nch, GenParam{});
     for (ChanCfg &c : cfg) {
         c.gen_dirty = c.gen_sweep_dirty = true;
@@ -616,6 +671,9 @@ int Engine::stages_alloc()
             std::vector<LmsState> init((size_t)nch);
             std::memset(init.data(), 0, init.size() * sizeof(LmsState));
             for (LmsState &st : init) { st.lidx = f ? 120.0 : 1.0; st.ngamma = f ? 0.001 : 6.25e-12; }
+            if (carry.lms[f].size() == 2 * (size_t)nch)         // what ran on across a new dsp_rate or dsp_size (Engine::rebuild)
+                for (int ch = 0; ch < nch; ch++) { init[(size_t)ch].lidx = carry.lms[f][2 * (size_t)ch]; init[(size_t)ch].ngamma = carry.lms[f][2 * (size_t)ch + 1]; }
+            carry.lms[f].clear();
             QH_HIP(hipMemcpyAsync(lms_state[f], init.data(), init.size() * sizeof(LmsState), hipMemcpyHostToDevice, stream));
             QH_HIP(hipStreamSynchronize(stream));
         }
@@ -1014,8 +1072,12 @@ int Engine::snba_alloc()
         for (int i = 0; i < q.cpp_in; i++) hin[(size_t)i] = imp[(size_t)i].real();
     }
     QH_HIP(hipMemcpyAsync(snba_hin, hin.data(), hin.size() * sizeof(double), hipMemcpyHostToDevice, stream));
+    if (carry.snba_frames.size() == (size_t)nch * 2 * kSnbX)    // the frame memory stays across decalc_snba / calc_snba (Engine::rebuild)
+        QH_HIP(hipMemcpy2DAsync(snba_state, (size_t)q.state_doubles * sizeof(double), carry.snba_frames.data(), 2 * kSnbX * sizeof(double),
+                                2 * kSnbX * sizeof(double), (size_t)nch, hipMemcpyHostToDevice, stream));
     if (int rc = fc_alloc(fc[FC_SNB])) return rc;
     QH_HIP(hipStreamSynchronize(stream));
+    carry.snba_frames.clear();
     for (ChanCfg &c : cfg) { c.snba_taps_dirty = true; c.snb_dirty = true; c.snba_flush = c.snba_rout_flush = false; c.snb_flush = false; }
     return QH_OK;
 }
@@ -1648,6 +1710,187 @@ int Engine::flush()
         QH_HIP(hipMemsetAsync(fm_pll_state, 0, (size_t)nch * sizeof(PllState), stream));
         QH_HIP(hipMemsetAsync(sn_state, 0, (size_t)nch * sizeof(SnotchState), stream));
     }
+    return QH_OK;
+}
+
+// ---- the run-time setters of wdsp/channel.c:169-258 on a live engine ---------------------------------------------------------
+// SetInputSamplerate, SetOutputSamplerate, SetDSPSamplerate, SetDSPBuffsize and SetAllRates as one call: any subset of the four values
+// may differ from the current ones.  What the reference does to each stage (setInputSamplerate_rxa ... setDSPBuffsize_rxa, RXA.c:600-740,
+// and every stage's setSamplerate_* / setSize_*) is tabled in DESIGN.md row b24; in short:
+//   in_rate   shift restarts at phase 0 (shift.c:93-98), rsmpin is made anew (resample.c:171-176), nothing at the DSP rate is touched
+//   out_rate  rsmpout is made anew (resample.c:178-183), nothing else is touched
+//   dsp_rate  every stage at the DSP rate is designed again from the kept settings; both resamplers and most state start from zero
+//             (decalc / calc or flush).  Kept: the delay lines of nbp0, bp1, eqp and xfmd's two filters (a new impulse response only),
+//             anf / anr's lidx and ngamma, snba's frame memory, the SAM detector's sideband all-pass chains
+//   dsp_size  the same without the redesign, but setSize_fircore re-plans those five filters, so their delay lines go; setSize_amd keeps
+//             the whole AM / SAM detector and setSize_gen all of gen0 but the pulse's state
+// The first two are done in place: only the front stage or rsmpout is made again, every other buffer and all state run on.  The last two
+// leave so little standing that the engine is made anew in place (rebuild) with the settings and the kept state carried over.
+// A refused call returns the status qh_rxa_create would set and has changed nothing.
+int Engine::set_rates(int new_in, int new_dsp, int new_out, int new_size)
+{
+    if (new_in == in_rate && new_dsp == dsp_rate && new_out == out_rate && new_size == dsp_size) return QH_OK;
+    int new_D = 0;
+    if (int rc = check_rates("qh_rxa_set_rates", new_size, new_in, new_dsp, new_out, &new_D)) return rc;
+    for (const ChanCfg &c : cfg) {
+        // setSize_nbp / setSize_bandpass: "'size' must be <= 'nc'" (nbp.c:308, bandpass.c:345); the other fircores are planned the same way
+        const int nc = std::min({ c.nbp_nc, c.bp1_nc, c.fm_nc, c.fmsq_nc, c.eqp_nc });
+        if (new_size > nc) return set_error(QH_ERR_UNSUPPORTED, "dsp_size %d above nc %d of channel %d: size must be <= nc (wdsp/nbp.c:308)", new_size, nc, (int)(&c - cfg.data()));
+        if (c.emnr_run && new_size > kEmnrIncr) return set_error(QH_ERR_UNSUPPORTED, "EMNR: dsp_size up to %d", kEmnrIncr);
+        if (c.snba_run && (new_dsp % 12000 || (new_dsp / 12000 != 1 && new_dsp / 12000 != 2 && new_dsp / 12000 != 4) || new_size > kSnbMaxDsp ||
+                           new_size % (new_dsp / 12000)))
+            return set_error(QH_ERR_UNSUPPORTED, "SNBA: dsp_rate 12000, 24000 or 48000 and dsp_size up to %d", kSnbMaxDsp);
+    }
+    if (disp && qh_ana_buff_size(disp) != new_size)
+        return set_error(QH_ERR_INVALID, "the attached display bank has buff_size %d: detach it before dsp_size becomes %d", qh_ana_buff_size(disp), new_size);
+    QH_HIP(hipSetDevice(device));
+    if (new_dsp != dsp_rate || new_size != dsp_size) return rebuild(new_in, new_dsp, new_out, new_size, new_D);
+    if (int rc = quiesce()) return rc;
+    if (new_in != in_rate) {        // setInputSamplerate_rxa, RXA.c:600-614
+        in_rate = new_in; D = new_D;
+        if (int rc = front_build()) return rc;
+        if (int rc = tile_lds_limits()) return rc;
+        QH_HIP(hipMemsetAsync(nco_phase, 0, (size_t)nch * sizeof(unsigned long long), stream));         // setSamplerate_shift, shift.c:93-98
+        QH_HIP(hipMemsetAsync(nco_parked, 0, (size_t)nch * sizeof(unsigned long long), stream));
+        for (ChanCfg &c : cfg) c.nco_dirty = true;          // calc_shift: delta is per sample of the new rate
+    }
+    if (new_out != out_rate) {      // setOutputSamplerate_rxa, RXA.c:616-625
+        out_rate = new_out;
+        if (int rc = out_build()) return rc;
+    }
+    QH_HIP(hipStreamSynchronize(stream));
+    return QH_OK;
+}
+
+// A channel's settings as a setter list replayed on a fresh engine would leave them: every value kept, every note of work pending or
+// done (dirty, flush, what is on the device) as ChanCfg() has it.
+static ChanCfg settings_of(const ChanCfg &o, int dsp_rate)
+{
+    // a member added to ChanCfg is a setting (kept by the copy below) or a note of work (to be put back to its default here): this
+    // reminder fails to compile until its author has looked
+    static_assert(sizeof(ChanCfg) == 872, "ChanCfg changed: see to settings_of, then update the size");
+    ChanCfg c = o;
+    const ChanCfg d;
+    c.shift_on_device = d.shift_on_device;
+    c.agc_dirty = d.agc_dirty; c.agc_abuf = d.agc_abuf; c.agc_rewindow = d.agc_rewindow; c.agc_ran = d.agc_ran; c.agc_stale = d.agc_stale;
+    for (int f = 0; f < 2; f++) { c.lms[f].dirty = d.lms[f].dirty; c.lms[f].flush = d.lms[f].flush; }
+    c.snba_flush = d.snba_flush; c.snba_taps_dirty = d.snba_taps_dirty; c.snba_rout_flush = d.snba_rout_flush; c.snb_dirty = d.snb_dirty; c.snb_flush = d.snb_flush;
+    c.snba_f_low = d.snba_f_low; c.snba_f_high = d.snba_f_high;     // calc_snba makes outresamp with its creation arguments (snb.c:43-44)
+    c.emnr_dirty = d.emnr_dirty; c.emnr_flush = d.emnr_flush; c.amsq_dirty = d.amsq_dirty;
+    c.demod_dirty = d.demod_dirty; c.ctcss_flush = d.ctcss_flush;
+    c.nbp_dirty = d.nbp_dirty; c.bp1_dirty = d.bp1_dirty; c.nco_dirty = d.nco_dirty; c.epi_dirty = d.epi_dirty; c.nbp_flush = d.nbp_flush; c.bp1_flush = d.bp1_flush;
+    c.ap_dirty = d.ap_dirty; c.sp_flush = d.sp_flush;
+    for (int i = 0; i < kApPeaks; i++) c.mp_flush[i] = d.mp_flush[i];
+    c.ssql_dirty = d.ssql_dirty; c.fmsq_dirty = d.fmsq_dirty; c.lim_dirty = d.lim_dirty;
+    c.eqp_dirty = d.eqp_dirty; c.eqp_flush = d.eqp_flush; c.eqp_tie = eqp_profile_tie(c.eqp_F, c.eqp_G, (double)dsp_rate);
+    c.gen_dirty = d.gen_dirty; c.gen_sweep_dirty = d.gen_sweep_dirty; c.gen_tone_reset = d.gen_tone_reset; c.gen_sweep_reset = d.gen_sweep_reset;
+    return c;
+}
+
+// A new dsp_rate or dsp_size (setDSPSamplerate_rxa, setDSPBuffsize_rxa: RXA.c:627-740).  The engine is destroyed and constructed again
+// where it stands -- same handle, lock, stream, device and channel count -- so every buffer goes through alloc() and `owned` again and
+// every stage starts as create_rxa leaves it.  Carried over: the channels' settings (settings_of) and the engine-wide ones, and of the
+// state
+//   dsp_rate alone   the delay lines of nbp0, bp1, eqp and xfmd's two filters, where the stage holds its one-tile form (nc <= 4096; a
+//                    partitioned stage's 65535-sample line is not carried and starts from zero: a stated deviation);
+//                    the SAM detector's sideband chains (init_amd leaves them)
+//   dsp_size alone   the whole AM / SAM detector (setSize_amd writes the size and nothing else, amd.c:253-256); gen0's phases and
+//                    positions, the pulse flushed (setSize_gen, gen.c:369-373)
+//   both             anf / anr's lidx and ngamma (flush_anf / flush_anr), snba's frame memory (calc_snba does not make it)
+// State of a stage that is made on first use waits in `carry` for the allocation that makes the stage again.
+int Engine::rebuild(int new_in, int new_dsp, int new_out, int new_size, int new_D)
+{
+    if (int rc = quiesce()) return rc;
+    if (disp_fed_pending) QH_HIP(hipEventSynchronize(disp_fed));
+    const bool rate = new_dsp != dsp_rate, size = new_size != dsp_size;
+    struct Line { double2 *hist[2] = { nullptr, nullptr }; int cur = 0; std::vector<Fircore::Chan> chan; long long bytes = 0; } line[FC_COUNT];
+    if (!size)
+        for (int s : { (int)FC_NBP, (int)FC_BP1, (int)FC_DE, (int)FC_AUD, (int)FC_EQP }) {
+            Fircore &f = fc[s];
+            if (!f.hist[0] || f.parts > 1) continue;
+            Line &l = line[s];
+            l.cur = f.cur; l.chan = f.chan; l.bytes = owned[f.hist[0]];
+            for (Fircore::Chan &r : l.chan) r.long_live = false;
+            for (int i = 0; i < 2; i++) { l.hist[i] = f.hist[i]; owned.erase(f.hist[i]); f.hist[i] = nullptr; }
+        }
+    // the AM / SAM detector: setSize_amd keeps all of it; init_amd (a new dsp_rate) zeroes the loop and the two averages and leaves the
+    // sideband all-pass chains (amd.c:72-113 writes no a[], b[], c[], d[], dsI, dsQ)
+    AmState *am_keep = nullptr;
+    PllState *pll_keep = nullptr;
+    if (demod_alloc) { am_keep = am_state; pll_keep = pll_state; owned.erase(am_state); owned.erase(pll_state); am_state = nullptr; pll_state = nullptr; }
+    // the stages made on first use: what is on the device now, or what an earlier rebuild left waiting for a stage not made since
+    Carry keep = std::move(carry);
+    for (int f = 0; f < 2; f++)
+        if (lms_state[f]) {
+            keep.lms[f].resize(2 * (size_t)nch);
+            QH_HIP(hipMemcpy2D(keep.lms[f].data(), 2 * sizeof(double), &lms_state[f][0].lidx, sizeof(LmsState), 2 * sizeof(double), (size_t)nch, hipMemcpyDeviceToHost));
+        }
+    if (snba_state) {
+        keep.snba_frames.resize((size_t)nch * 2 * kSnbX);
+        QH_HIP(hipMemcpy2D(keep.snba_frames.data(), 2 * kSnbX * sizeof(double), snba_state, (size_t)snba_prm.state_doubles * sizeof(double),
+                           2 * kSnbX * sizeof(double), (size_t)nch, hipMemcpyDeviceToHost));
+    }
+    if (rate) keep.gen.clear();         // calc_gen starts every phase again (gen.c:98-105,362-367)
+    else if (gen_state) {
+        keep.gen.resize((size_t)nch);
+        QH_HIP(hipMemcpy(keep.gen.data(), gen_state, (size_t)nch * sizeof(GenState), hipMemcpyDeviceToHost));
+        for (GenState &g : keep.gen) {  // flush_gen, as gen_flush_kernel: the pulse goes to OFF for as long as its state had left
+            const long long pos = g.pulse_pos, up = gen_pnoff, on = up + gen_pntrans, down = on + gen_pnon, T = down + gen_pntrans;
+            if (pos >= up) g.pulse_pos = (long long)gen_pnoff - ((pos < on ? on : pos < down ? down : T) - pos);
+        }
+    }
+    std::vector<ChanCfg> keep_cfg;
+    for (const ChanCfg &c : cfg) keep_cfg.push_back(settings_of(c, new_dsp));
+    // the engine-wide settings: one Engine member set through the C ABI outside cfg that is not listed here is lost by a rebuild
+    static_assert(sizeof(Engine) == 8840, "Engine changed: see to Engine::rebuild's Wide and carried state, then update the size");
+    struct Wide {
+        int device, nch; hipStream_t stream; bool own_stream; unsigned long long epoch;
+        bool graph_on; long long graph_launches; bool timing, meters_on; int band_tile_pref, snba_ovrlp; std::vector<SnbaTune> snba_tune_h;
+        qh_ana *disp; int disp_ss, pll_check_only, agc_form;
+        bool emnr_tables; std::vector<double> h_GG, h_GGS, h_zeta; std::vector<int> h_zeta_true; double h_zrange[4];
+    } was{ device, nch, stream, own_stream, epoch, graph_on, graph_launches, timing, meters_on, band_tile_pref, snba_ovrlp, snba_tune_h,
+           disp, disp_ss, pll_check_only, agc_form, emnr_tables, std::move(h_GG), std::move(h_GGS), std::move(h_zeta), std::move(h_zeta_true),
+           { h_zrange[0], h_zrange[1], h_zrange[2], h_zrange[3] } };
+    own_stream = false;                     // the stream stays: callers hold it (qh_rxa_stream)
+    this->~Engine();
+    new (this) Engine();
+    device = was.device; nch = was.nch; stream = was.stream; own_stream = was.own_stream; epoch = was.epoch + 1;
+    in_rate = new_in; dsp_rate = new_dsp; out_rate = new_out; dsp_size = new_size; D = new_D;
+    int rc = init();
+    graph_on = was.graph_on; graph_launches = was.graph_launches; timing = was.timing; meters_on = was.meters_on;
+    band_tile_pref = was.band_tile_pref; snba_ovrlp = was.snba_ovrlp; snba_tune_h = was.snba_tune_h; snba_tune_dirty = true;
+    disp = was.disp; disp_ss = was.disp_ss; pll_check_only = was.pll_check_only; agc_form = was.agc_form;
+    emnr_tables = was.emnr_tables; h_GG = std::move(was.h_GG); h_GGS = std::move(was.h_GGS); h_zeta = std::move(was.h_zeta); h_zeta_true = std::move(was.h_zeta_true);
+    std::copy(was.h_zrange, was.h_zrange + 4, h_zrange);
+    carry = std::move(keep);
+    if (!rc) {
+        cfg = keep_cfg;
+        lists_dirty = true; eq_lists_dirty = true;
+    }
+    for (int s = 0; s < FC_COUNT; s++) {
+        Line &l = line[s];
+        if (!l.hist[0]) continue;
+        Fircore &f = fc[s];
+        for (int i = 0; i < 2; i++) { release(f.hist[i]); f.hist[i] = l.hist[i]; owned[l.hist[i]] = l.bytes; }
+        f.cur = l.cur; f.chan = l.chan;
+        f.carried = !f.mask;                // a stage init() has not made keeps the lines through the fc_alloc that makes it
+    }
+    if (am_keep) {
+        if (!rc) rc = demod_init();
+        if (!rc && !rate) {
+            QH_HIP(hipMemcpyAsync(am_state, am_keep, (size_t)nch * sizeof(AmState), hipMemcpyDeviceToDevice, stream));
+            QH_HIP(hipMemcpyAsync(pll_state, pll_keep, (size_t)nch * sizeof(PllState), hipMemcpyDeviceToDevice, stream));
+            QH_HIP(hipStreamSynchronize(stream));
+        } else if (!rc) {
+            const size_t at = offsetof(PllState, dsI);
+            QH_HIP(hipMemcpy2DAsync(reinterpret_cast<char *>(pll_state) + at, sizeof(PllState), reinterpret_cast<const char *>(pll_keep) + at, sizeof(PllState),
+                                    sizeof(PllState) - at, (size_t)nch, hipMemcpyDeviceToDevice, stream));
+            QH_HIP(hipStreamSynchronize(stream));
+        }
+        (void)hipFree(am_keep); (void)hipFree(pll_keep);
+    }
+    if (rc) return rc;
+    QH_HIP(hipStreamSynchronize(stream));
     return QH_OK;
 }
 

@@ -19,27 +19,12 @@ int qh_device_count(void)
 
 qh_rxa *qh_rxa_create(int device, int nch, int dsp_size, int in_rate, int dsp_rate, int out_rate, void *stream)
 {
-    if (nch <= 0 || dsp_size <= 0 || (dsp_size & (dsp_size - 1)) || in_rate <= 0 || dsp_rate <= 0) {
+    int D = 0;
+    if (nch <= 0) {
         set_error(QH_ERR_INVALID, "qh_rxa_create: bad arguments");
         return nullptr;
     }
-    if (out_rate <= 0 || (out_rate % dsp_rate && dsp_rate % out_rate) || (out_rate < dsp_rate && dsp_size % (dsp_rate / out_rate))) {
-        set_error(QH_ERR_UNSUPPORTED, "out_rate must be an integer multiple or fraction of dsp_rate (wdsp/channel.c:47-52)");
-        return nullptr;
-    }
-    // in_rate / dsp_rate 1, 2, 4, 8, 16: the overlap-save front stage.  Any other whole ratio, up or down (3, 5, 6 ...; 1/2,
-    // 1/4 ...): xshift as a pointwise pass + the polyphase form of xresample (wdsp/resample.c:35-157) -- D = 0 marks it.  The
-    // reference sizes its blocks with integer divisions of the two rates (pre_main_build, wdsp/channel.c:39-42): a ratio that is
-    // not whole one way or the other does not give it consistent block sizes, and is refused here.
-    int D = (in_rate % dsp_rate) ? 0 : in_rate / dsp_rate;
-    if (D != 1 && D != 2 && D != 4 && D != 8 && D != 16) D = 0;
-    if (D == 0 && !((in_rate > dsp_rate && in_rate % dsp_rate == 0) ||
-                    (in_rate < dsp_rate && dsp_rate % in_rate == 0 && dsp_size % (dsp_rate / in_rate) == 0))) {
-        // (a CPU test of the reference's arithmetic, test_rates_that_are_whole_in_neither_direction_recycle_stale_buffer_tails, shows what it
-        // does with 96 k -> 64 k -> 48 k: every block's tail is what the block before left in the buffer)
-        set_error(QH_ERR_UNSUPPORTED, "in_rate / dsp_rate must be a whole number or the reciprocal of one (wdsp/channel.c:39-42)");
-        return nullptr;
-    }
+    if (check_rates("qh_rxa_create", dsp_size, in_rate, dsp_rate, out_rate, &D)) return nullptr;
     if (qh_device_count() <= device || device < 0) {
         set_error(QH_ERR_NO_DEVICE, "no HIP device %d (libquiskhip has no CPU fallback)", device);
         return nullptr;
@@ -58,6 +43,31 @@ int qh_rxa_dsp_insize(const qh_rxa *h) { return h->e.dsp_insize; }
 int qh_rxa_dsp_outsize(const qh_rxa *h) { return h->e.dsp_outsize; }
 void *qh_rxa_stream(const qh_rxa *h) { return h ? (void *)h->e.stream : nullptr; }
 long long qh_rxa_device_bytes(const qh_rxa *h) { return h->e.dev_bytes(); }
+int qh_rxa_in_rate(const qh_rxa *h) { return h ? h->e.in_rate : 0; }
+int qh_rxa_dsp_rate(const qh_rxa *h) { return h ? h->e.dsp_rate : 0; }
+int qh_rxa_out_rate(const qh_rxa *h) { return h ? h->e.out_rate : 0; }
+int qh_rxa_dsp_size(const qh_rxa *h) { return h ? h->e.dsp_size : 0; }
+
+// The run-time setters of wdsp/channel.c:169-258 on a live engine: Engine::set_rates under the engine lock.  A value < 0 stands for the
+// current one.  A call that changes nothing does nothing (`if (x != ch[channel].x)`, channel.c:172,185,201,215,231,245): the captured
+// launch sequences stay.  A refused call sets the status qh_rxa_create would and changes nothing.
+static int set_rates_locked(qh_rxa *h, int in_rate, int dsp_rate, int out_rate, int dsp_size)
+{
+    if (!h) return set_error(QH_ERR_INVALID, "null engine");
+    QH_RXA_LOCK(h);
+    const Engine &e = h->e;
+    return h->e.set_rates(in_rate < 0 ? e.in_rate : in_rate, dsp_rate < 0 ? e.dsp_rate : dsp_rate, out_rate < 0 ? e.out_rate : out_rate,
+                          dsp_size < 0 ? e.dsp_size : dsp_size);
+}
+int qh_rxa_set_rates(qh_rxa *h, int in_rate, int dsp_rate, int out_rate)
+{
+    if (in_rate < 0 || dsp_rate < 0 || out_rate < 0) return set_error(QH_ERR_INVALID, "qh_rxa_set_rates: bad arguments");
+    return set_rates_locked(h, in_rate, dsp_rate, out_rate, -1);
+}
+int qh_rxa_set_in_rate(qh_rxa *h, int in_rate) { return in_rate < 0 ? set_error(QH_ERR_INVALID, "qh_rxa_set_in_rate: bad arguments") : set_rates_locked(h, in_rate, -1, -1, -1); }
+int qh_rxa_set_dsp_rate(qh_rxa *h, int dsp_rate) { return dsp_rate < 0 ? set_error(QH_ERR_INVALID, "qh_rxa_set_dsp_rate: bad arguments") : set_rates_locked(h, -1, dsp_rate, -1, -1); }
+int qh_rxa_set_out_rate(qh_rxa *h, int out_rate) { return out_rate < 0 ? set_error(QH_ERR_INVALID, "qh_rxa_set_out_rate: bad arguments") : set_rates_locked(h, -1, -1, out_rate, -1); }
+int qh_rxa_set_dsp_size(qh_rxa *h, int dsp_size) { return dsp_size < 0 ? set_error(QH_ERR_INVALID, "qh_rxa_set_dsp_size: bad arguments") : set_rates_locked(h, -1, -1, -1, dsp_size); }
 
 #define FOR_CH(h, ch, body)                                                                       \
     do {                                                                                          \
@@ -609,16 +619,6 @@ int qh_rxa_SetRXAEQNC(qh_rxa *h, int ch, int nc)
 int qh_rxa_SetRXAEQMP(qh_rxa *h, int ch, int mp)
 {
     FOR_CH(h, ch, { mp = mp ? 1 : 0; if (c.eqp_mp != mp) { c.eqp_mp = mp; c.eqp_dirty = true; } });
-}
-// whether two of the profile's frequencies coincide after eq_impulse's clamp to [0, 1] (eq.c:53-55) while their gains differ
-static bool eqp_profile_tie(const std::vector<double> &F, const std::vector<double> &G, double rate)
-{
-    for (size_t i = 1; i < F.size(); i++)
-        for (size_t j = i + 1; j < F.size(); j++) {
-            const double a = std::min(1.0, std::max(0.0, 2.0 * F[i] / rate)), b = std::min(1.0, std::max(0.0, 2.0 * F[j] / rate));
-            if (a == b && G[i] != G[j]) return true;
-        }
-    return false;
 }
 static int eqp_set_profile(qh_rxa *h, int ch, int nfreqs, const double *F, const double *G, int ctfmode)
 {

@@ -337,6 +337,69 @@ int set_mode(Chan &c, bool dev)
     return QH_OK;
 }
 
+// pre_main_build + create_iobuffs (wdsp/channel.c:37-58, iobuffs.c:384-423) from the channel's sizes, rates and slew times and the
+// engine's block sizes: out_size, the ring sizes, the rings as init_rings leaves them, the slews, the pinned and device staging and,
+// for a channel in device mode, the device rings.  What the channel held of these is given back first.
+int build_iobuffs(Chan &c)
+{
+    const bool dev = c.dev_mode;
+    free_staging(c);
+    c.dsp_insize = qh_rxa_dsp_insize(c.eng);
+    c.dsp_outsize = qh_rxa_dsp_outsize(c.eng);
+    if (c.in_rate >= c.out_rate) c.out_size = c.in_size / (c.in_rate / c.out_rate);
+    else c.out_size = c.in_size * (c.out_rate / c.in_rate);
+    c.r1_outsize = c.dsp_insize;
+    c.r1_size = c.r1_outsize > c.in_size ? c.r1_outsize : c.in_size;
+    c.r2_insize = c.dsp_outsize;
+    c.r2_size = c.out_size > c.r2_insize ? c.out_size : c.r2_insize;
+    c.r1_active = kDspMult * c.r1_size;
+    c.r2_active = kDspMult * c.r2_size;
+    if (hipMalloc((void **)&c.d_in, (size_t)c.dsp_insize * 2 * sizeof(double)) != hipSuccess ||
+        hipMalloc((void **)&c.d_out, (size_t)c.dsp_outsize * 2 * sizeof(double)) != hipSuccess ||
+        hipHostMalloc((void **)&c.h_in, (size_t)c.dsp_insize * 2 * sizeof(double), hipHostMallocDefault) != hipSuccess ||
+        hipHostMalloc((void **)&c.h_out, (size_t)c.dsp_outsize * 2 * sizeof(double), hipHostMallocDefault) != hipSuccess)
+        return QH_ERR_HIP;
+    if (dev) {
+        if (hipMalloc((void **)&c.d_r1, (size_t)c.r1_active * 16) != hipSuccess || hipMalloc((void **)&c.d_r2, (size_t)c.r2_active * 16) != hipSuccess ||
+            hipMalloc((void **)&c.d_up, sizeof(DevSlew)) != hipSuccess)
+            return QH_ERR_HIP;
+        c.dev_mode = true;
+    }
+    init_rings(c);
+    create_slews(c);
+    push_up(c);
+    return QH_OK;
+}
+
+// pre_main_destroy, post_main_destroy, pre_main_build and post_main_build around a change of a size or a rate (wdsp/channel.c:169-258)
+// as one step: the exchange is off while the iobuffs are made again -- what the rings held is lost, as there -- and comes back on if
+// the channel's state is 1 (channel.c:64-65).  The engine has its new values already, so a channel whose iobuffs cannot be made again has
+// nothing left to run on: it is closed (CloseChannel's steps), the status says so, and every later call on it reports a channel that is not open.
+void shut_channel(Chan &c)
+{
+    free_staging(c);
+    qh_wdsp_shim_release_device((int)(&c - g_ch));
+    g_graph_launches += qh_rxa_graph_launches(c.eng);
+    qh_rxa_destroy(c.eng);
+    c.eng = nullptr;
+    c.open = false;
+    c.emnr_tables = false;
+    c.exchange = 0;
+}
+
+int rebuild_iobuffs(Chan &c)
+{
+    c.exchange = 0;
+    int rc = qh_rxa_synchronize(c.eng);
+    if (!rc && build_iobuffs(c)) rc = QH_ERR_HIP;
+    if (rc) {
+        shut_channel(c);
+        return qh::set_error(rc, "WDSP channel %d: its buffers could not be made again, the channel is closed", (int)(&c - g_ch));
+    }
+    if (c.state == 1) c.exchange = 1;
+    return QH_OK;
+}
+
 struct Locked {
     Chan *c = nullptr;
     std::unique_lock<std::recursive_mutex> lk;
@@ -386,24 +449,7 @@ void OpenChannel(int channel, int in_size, int dsp_size, int input_samplerate, i
     c.tdelayup = tdelayup; c.tslewup = tslewup; c.tdelaydown = tdelaydown; c.tslewdown = tslewdown;
     c.bfo = bfo; c.state = state;
     c.spec_flag = 0; c.spec_disp = 0; c.spec_ss = 1; c.sip_on = false;     // create_sender / create_siphon, RXA.c:130-139,392-401
-    // pre_main_build, wdsp/channel.c:39-52
-    c.dsp_insize = qh_rxa_dsp_insize(c.eng);
-    c.dsp_outsize = qh_rxa_dsp_outsize(c.eng);
-    if (c.in_rate >= c.out_rate) c.out_size = in_size / (c.in_rate / c.out_rate);
-    else c.out_size = in_size * (c.out_rate / c.in_rate);
-    // create_iobuffs, wdsp/iobuffs.c:384-423
-    c.r1_outsize = c.dsp_insize;
-    c.r1_size = c.r1_outsize > in_size ? c.r1_outsize : in_size;
-    c.r2_insize = c.dsp_outsize;
-    c.r2_size = c.out_size > c.r2_insize ? c.out_size : c.r2_insize;
-    c.r1_active = kDspMult * c.r1_size;
-    c.r2_active = kDspMult * c.r2_size;
-    init_rings(c);
-    create_slews(c);
-    if (hipMalloc((void **)&c.d_in, (size_t)c.dsp_insize * 2 * sizeof(double)) != hipSuccess ||
-        hipMalloc((void **)&c.d_out, (size_t)c.dsp_outsize * 2 * sizeof(double)) != hipSuccess ||
-        hipHostMalloc((void **)&c.h_in, (size_t)c.dsp_insize * 2 * sizeof(double), hipHostMallocDefault) != hipSuccess ||
-        hipHostMalloc((void **)&c.h_out, (size_t)c.dsp_outsize * 2 * sizeof(double), hipHostMallocDefault) != hipSuccess) {
+    if (build_iobuffs(c)) {
         g_status = qh::set_error(QH_ERR_HIP, "OpenChannel: staging allocation failed");
         free_staging(c);
         qh_rxa_destroy(c.eng);
@@ -424,13 +470,7 @@ void CloseChannel(int channel)
     Locked L(channel);
     if (!L.c) return;
     Chan &c = *L.c;
-    free_staging(c);
-    qh_wdsp_shim_release_device(channel);       // the re-blocking ring keeps its samples (the reference's statics outlive the channel), on the host
-    g_graph_launches += qh_rxa_graph_launches(c.eng);
-    qh_rxa_destroy(c.eng);
-    c.eng = nullptr;
-    c.open = false;
-    c.emnr_tables = false;
+    shut_channel(c);       // (the re-blocking ring keeps its samples -- the reference's statics outlive the channel --, on the host)
 }
 
 int SetChannelState(int channel, int state, int dmode)
@@ -625,6 +665,89 @@ extern "C" {
         int rc = (call);                                    \
         if (rc) g_status = rc;                              \
     } while (0)
+
+// ---- the channel's run-time setters, wdsp/channel.c:158-258,301-347.  The engine takes its new values first: a value it refuses
+// leaves qh_wdsp_status() set and the channel as it was.
+void SetType(int channel, int type)     // channel.c:158-167: only RXA channels exist here, as in OpenChannel
+{
+    g_status = QH_OK;
+    Locked L(channel);
+    if (!L.c) return;
+    if (type != 0) g_status = qh::set_error(QH_ERR_UNSUPPORTED, "only RXA channels (type 0) are provided");
+}
+
+void SetInputBuffsize(int channel, int in_size)     // channel.c:169-180: main did not change
+{
+    g_status = QH_OK;
+    Locked L(channel);
+    if (!L.c) return;
+    Chan &c = *L.c;
+    if (in_size <= 0) { g_status = qh::set_error(QH_ERR_INVALID, "SetInputBuffsize: in_size %d", in_size); return; }
+    if (in_size == c.in_size) return;
+    c.in_size = in_size;
+    if (int rc = rebuild_iobuffs(c)) g_status = rc;
+}
+
+// the rates' three setters and SetAllRates (channel.c:198-258); a rate < 0 stands for the channel's current one.  Only SetDSPSamplerate
+// brackets the change with SetChannelState (channel.c:217,224): the others arm nothing.
+static void set_rates(int channel, int in_rate, int dsp_rate, int out_rate, bool bracket)
+{
+    g_status = QH_OK;
+    Locked L(channel);
+    if (!L.c) return;
+    Chan &c = *L.c;
+    if (in_rate < 0) in_rate = c.in_rate;
+    if (dsp_rate < 0) dsp_rate = c.dsp_rate;
+    if (out_rate < 0) out_rate = c.out_rate;
+    if (in_rate == c.in_rate && dsp_rate == c.dsp_rate && out_rate == c.out_rate) return;
+    if (int rc = qh_rxa_set_rates(c.eng, in_rate, dsp_rate, out_rate)) { g_status = rc; return; }
+    const int old = bracket ? SetChannelState(channel, 0, 1) : 0;
+    c.in_rate = in_rate; c.dsp_rate = dsp_rate; c.out_rate = out_rate;
+    if (int rc = rebuild_iobuffs(c)) { g_status = rc; return; }
+    if (bracket) (void)SetChannelState(channel, old, 0);        // a running channel's up-slew is armed again
+}
+void SetInputSamplerate(int channel, int in_rate) { set_rates(channel, in_rate < 0 ? 0 : in_rate, -1, -1, false); }
+void SetOutputSamplerate(int channel, int out_rate) { set_rates(channel, -1, -1, out_rate < 0 ? 0 : out_rate, false); }
+void SetDSPSamplerate(int channel, int dsp_rate) { set_rates(channel, -1, dsp_rate < 0 ? 0 : dsp_rate, -1, true); }
+void SetAllRates(int channel, int in_rate, int dsp_rate, int out_rate)
+{
+    set_rates(channel, in_rate < 0 ? 0 : in_rate, dsp_rate < 0 ? 0 : dsp_rate, out_rate < 0 ? 0 : out_rate, false);
+}
+
+void SetDSPBuffsize(int channel, int dsp_size)      // channel.c:182-196
+{
+    g_status = QH_OK;
+    Locked L(channel);
+    if (!L.c) return;
+    Chan &c = *L.c;
+    if (dsp_size == c.dsp_size) return;
+    if (int rc = qh_rxa_set_dsp_size(c.eng, dsp_size)) { g_status = rc; return; }
+    const int old = SetChannelState(channel, 0, 1);
+    c.dsp_size = dsp_size;
+    if (int rc = rebuild_iobuffs(c)) { g_status = rc; return; }
+    (void)SetChannelState(channel, old, 0);
+}
+
+// channel.c:301-347: the delays store the time, take the count at the in / out rate and flush the slews; the ramps store the time and
+// make the slews anew (create_slews: nothing armed, nothing under way)
+static void set_slew_time(int channel, double Chan::*t, double time, bool recreate)
+{
+    g_status = QH_OK;
+    Locked L(channel);
+    if (!L.c) return;
+    Chan &c = *L.c;
+    c.*t = time;
+    if (recreate) create_slews(c);
+    else {
+        c.up.delay = (int)(c.tdelayup * c.in_rate); c.down.delay = (int)(c.tdelaydown * c.out_rate);
+        c.up.reset(); c.down.reset();
+    }
+    push_up(c);
+}
+void SetChannelTDelayUp(int channel, double time) { set_slew_time(channel, &Chan::tdelayup, time, false); }
+void SetChannelTSlewUp(int channel, double time) { set_slew_time(channel, &Chan::tslewup, time, true); }
+void SetChannelTDelayDown(int channel, double time) { set_slew_time(channel, &Chan::tdelaydown, time, false); }
+void SetChannelTSlewDown(int channel, double time) { set_slew_time(channel, &Chan::tslewdown, time, true); }
 
 void SetRXAMode(int channel, int mode) { WDSP_SETTER(qh_rxa_SetRXAMode(L.c->eng, 0, mode)); }
 void RXASetPassband(int channel, double f_low, double f_high) { WDSP_SETTER(qh_rxa_RXASetPassband(L.c->eng, 0, f_low, f_high)); }

@@ -154,6 +154,21 @@ def load():
     L.qh_rxa_set_gen_seed.argtypes = [vp, i, C.c_ulonglong]
     L.qh_rxa_flush.argtypes = [vp]
     L.qh_rxa_flush.restype = i
+    # the run-time rate and buffer-size setters (wdsp/channel.c:158-258,301-347)
+    for n in ("qh_rxa_in_rate", "qh_rxa_dsp_rate", "qh_rxa_out_rate", "qh_rxa_dsp_size"):
+        getattr(L, n).argtypes = [vp]
+        getattr(L, n).restype = i
+    L.qh_rxa_set_rates.argtypes = [vp, i, i, i]
+    for n in ("qh_rxa_set_in_rate", "qh_rxa_set_dsp_rate", "qh_rxa_set_out_rate", "qh_rxa_set_dsp_size"):
+        getattr(L, n).argtypes = [vp, i]
+    for n in ("SetType", "SetInputBuffsize", "SetDSPBuffsize", "SetInputSamplerate", "SetDSPSamplerate", "SetOutputSamplerate"):
+        getattr(L, n).argtypes = [i, i]
+        getattr(L, n).restype = None
+    L.SetAllRates.argtypes = [i, i, i, i]
+    L.SetAllRates.restype = None
+    for n in ("SetChannelTDelayUp", "SetChannelTSlewUp", "SetChannelTDelayDown", "SetChannelTSlewDown"):
+        getattr(L, n).argtypes = [i, d]
+        getattr(L, n).restype = None
     L.qh_rxa_enable_timing.argtypes = [vp, i]
     L.qh_rxa_enable_timing.restype = i
     L.qh_rxa_timing.argtypes = [vp, C.POINTER(d), i]

@@ -281,6 +281,43 @@ class RxaEngine:
     def device_bytes(self):
         return self._L.qh_rxa_device_bytes(self._h)
 
+    # the run-time rate and buffer-size setters (wdsp/channel.c:169-258; include/quiskhip.h): every per-channel setting survives
+    def _resized(self, rc):
+        check(rc)
+        self.dsp_insize = self._L.qh_rxa_dsp_insize(self._h)
+        self.dsp_outsize = self._L.qh_rxa_dsp_outsize(self._h)
+
+    def set_rates(self, in_rate, dsp_rate, out_rate):
+        self._resized(self._L.qh_rxa_set_rates(self._h, int(in_rate), int(dsp_rate), int(out_rate)))
+
+    def set_in_rate(self, in_rate):
+        self._resized(self._L.qh_rxa_set_in_rate(self._h, int(in_rate)))
+
+    def set_dsp_rate(self, dsp_rate):
+        self._resized(self._L.qh_rxa_set_dsp_rate(self._h, int(dsp_rate)))
+
+    def set_out_rate(self, out_rate):
+        self._resized(self._L.qh_rxa_set_out_rate(self._h, int(out_rate)))
+
+    def set_dsp_size(self, dsp_size):
+        self._resized(self._L.qh_rxa_set_dsp_size(self._h, int(dsp_size)))
+
+    @property
+    def in_rate(self):
+        return self._L.qh_rxa_in_rate(self._h)
+
+    @property
+    def dsp_rate(self):
+        return self._L.qh_rxa_dsp_rate(self._h)
+
+    @property
+    def out_rate(self):
+        return self._L.qh_rxa_out_rate(self._h)
+
+    @property
+    def dsp_size(self):
+        return self._L.qh_rxa_dsp_size(self._h)
+
     def close(self):
         if getattr(self, "_h", None):
             self._L.qh_rxa_destroy(self._h)
