@@ -181,7 +181,9 @@ int qh_rxa_SetRXAGrphEQ10(qh_rxa *e, int ch, const int *rxeq);                  
 int qh_rxa_SetRXAAMSQThreshold(qh_rxa *e, int ch, double threshold_db);
 int qh_rxa_SetRXAAMSQMaxTail(qh_rxa *e, int ch, double tail_seconds);
 /* xanf / xanr (wdsp/anf.c:82-133, anr.c:82-133), setters wdsp/anf.c:175-239 and anr.c:175-238; which position (0 before
- * bp1 and the AGC, 1 after the AGC) also moves bp1, as in the reference.  Taps and delay 1..64. */
+ * bp1 and the AGC, 1 after the AGC) also moves bp1, as in the reference.  The reference's whole range runs: taps 1..2048 and
+ * delay 0..2047 (ANF_DLINE_SIZE); a window that wraps the 2048-sample line (taps + delay > 2048) lands on the newest samples as it
+ * does there.  Values outside are refused with QH_ERR_INVALID and change nothing. */
 int qh_rxa_SetRXAANFRun(qh_rxa *e, int ch, int v);
 int qh_rxa_SetRXAANFTaps(qh_rxa *e, int ch, int v);
 int qh_rxa_SetRXAANFDelay(qh_rxa *e, int ch, int v);
@@ -526,7 +528,8 @@ void qh_wdsp_set_parameter(int channel, int in_size, int in_use);
 int qh_wdsp_fexchange0_device(int channel, void *d_samples, int nSamples, void *stream);
 /* accepted and ignored: these blocks are run = 0 on the hot path */
 /* anf / anr: the leaky-LMS automatic notch filter and noise reduction of the RXA chain (wdsp/anf.c:175-239, anr.c:175-238);
- * up to 64 taps and a delay of up to 64 samples (defaults 64 / 16, RXA.c:285-286,305-306) */
+ * taps 1..2048 and delay 0..2047, the reference's delay line (defaults 64 / 16, RXA.c:285-286,305-306); a value outside is refused,
+ * nothing changes and qh_wdsp_status() says so */
 void SetRXAANFRun(int channel, int v);
 void SetRXAANFTaps(int channel, int v);
 void SetRXAANFDelay(int channel, int v);

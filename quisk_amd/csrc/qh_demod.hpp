@@ -706,6 +706,87 @@ static __global__ __launch_bounds__(64) void lms_kernel(double2 *buf, long long 
     if (lane == 0) { sp->lidx = lidx; sp->ngamma = ngamma; }
 }
 
+// The long form of xanf / xanr: taps 1..2048, delay 0..2047 (ANF_DLINE_SIZE, anf.h), for the channels lms_kernel's one tap per lane
+// does not hold (Engine::lms_long_form).  Still one wavefront per channel -- the recurrence is the same -- with lane l keeping taps
+// l + 64 k, k < K, in registers and the reference's own 2048-sample ring d[] in LDS, indexed as anf.c:99 does:
+// tap j reads d[(in_idx + j + delay) & 2047], so a window that wraps (taps + delay > 2048) lands on the newest samples, the current
+// one included, as it does there.  Per sample: lane 0 writes the input at in_idx, every lane reads its K window samples (consecutive
+// addresses across the lanes for each k), sums its own w x and x x over k, the wave reduces both (wave_sum_d), the step-size logic
+// runs uniformly in the reference's operation order and the weights update from the registers that hold the window.  sigma is summed
+// afresh for every sample, as the reference does, and 1 / (sigma + 1e-10) is the division it writes.  FMA contraction off.
+// State: lidx / ngamma in LmsState, as the short form; w[2048] then d[2048] per channel in `rows`, the ring stored from in_idx on
+// (row[2048 + m] = x[last - m + 1], m = 1..2047), which is what in_idx = 0 finds in place, so that zeroed rows are flush_anf's.
+constexpr int kLmsLine = 2048;              // ANF_DLINE_SIZE / ANR_DLINE_SIZE
+constexpr int kLmsLongRow = 2 * kLmsLine;   // doubles per channel: the weights, then the ring
+// taps per lane the long form is compiled for (register arrays with static indices): the smallest of 2, 4, 8, 16, 32 that holds `taps`
+__host__ __device__ inline int lms_long_K(int taps) { int K = 2; while (64 * K < taps) K *= 2; return K; }
+
+template <int K>
+static __global__ __launch_bounds__(64) void lms_long_kernel(double2 *buf, long long stride, int n, const int *chan_list, const LmsParam *prm,
+                                                             LmsState *state, double *rows)
+{
+#pragma clang fp contract(off)
+    __shared__ double d[kLmsLine];
+    const int ch = chan_list[blockIdx.x], lane = threadIdx.x;
+    const LmsParam q = prm[ch];
+    if (lms_long_K(q.taps) != K) return;                                // another instantiation's channel (uniform)
+    LmsState *sp = state + ch;
+    double2 *p = buf + (long long)ch * stride;
+    double *row = rows + (long long)ch * kLmsLongRow;
+    // K is the smallest that holds the taps: above 2, the lower half of a lane's taps is always in use
+    constexpr int KF = K > 2 ? K / 2 : 0;
+    double w[K], x[K];
+#pragma unroll
+    for (int k = 0; k < K; k++) w[k] = (k < KF || lane + 64 * k < q.taps) ? row[lane + 64 * k] : 0.0;
+    for (int i = lane; i < kLmsLine; i += 64) d[i] = row[kLmsLine + i];
+    double lidx = sp->lidx, ngamma = sp->ngamma;
+    int in_idx = 0;
+    __syncthreads();
+    for (int base = 0; base < n; base += 64) {
+        const int cnt = n - base < 64 ? n - base : 64;
+        const double xin = lane < cnt ? p[base + lane].x : 0.0;
+        double myout = 0.0;
+        for (int i = 0; i < cnt; i++) {
+            const double xn = lane_bcast(xin, i);
+            if (lane == 0) d[in_idx] = xn;
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            const int first = in_idx + q.delay + lane;
+            double py = 0.0, ps = 0.0;
+#pragma unroll
+            for (int k = 0; k < K; k++) {
+                const double v = d[(first + 64 * k) & (kLmsLine - 1)];
+                x[k] = (k < KF || lane + 64 * k < q.taps) ? v : 0.0;
+                py += w[k] * x[k];
+                ps += x[k] * x[k];
+            }
+            const double y = wave_sum_d(py), sigma = wave_sum_d(ps);
+            const double inv_sigp = 1.0 / (sigma + 1e-10);
+            const double error = xn - y;
+            if (lane == i) myout = q.is_anr ? y : error;
+            double nel = error * (1.0 - q.two_mu * sigma * inv_sigp);
+            if (nel < 0.0) nel = -nel;
+            double nev = xn - (1.0 - q.two_mu * ngamma) * y - q.two_mu * error * sigma * inv_sigp;
+            if (nev < 0.0) nev = -nev;
+            if (nev < nel) { lidx += q.lincr; if (lidx > q.lidx_max) lidx = q.lidx_max; }
+            else { lidx -= q.ldecr; if (lidx < q.lidx_min) lidx = q.lidx_min; }
+            ngamma = q.gamma * (lidx * lidx) * (lidx * lidx) * q.den_mult;
+            const double c0 = 1.0 - q.two_mu * ngamma, c1 = q.two_mu * error * inv_sigp;
+#pragma unroll
+            for (int k = 0; k < K; k++) if ((k < KF || lane + 64 * k < q.taps)) w[k] = c0 * w[k] + c1 * x[k];
+            in_idx = (in_idx + (kLmsLine - 1)) & (kLmsLine - 1);
+            __builtin_amdgcn_wave_barrier();            // the next sample's input overwrites a slot this one has read
+        }
+        if (lane < cnt) p[base + lane] = make_double2(myout, 0.0);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < K; k++) if ((k < KF || lane + 64 * k < q.taps)) row[lane + 64 * k] = w[k];
+    for (int i = lane; i < kLmsLine; i += 64) row[kLmsLine + i] = d[(in_idx + i) & (kLmsLine - 1)];
+    if (lane == 0) { sp->lidx = lidx; sp->ngamma = ngamma; }
+}
+
 // AM squelch, wdsp/amsq.c: xamsqcap (:189-192) keeps the signal behind nbp0, xamsq (:119-187) at the end of the chain runs a
 // five-state machine (muted / raised-cosine up / unmuted / tail / raised-cosine down) on the 10 ms average of its magnitude.
 // The average is a linear recurrence (wave scan); the state machine is sequential: one wavefront per channel, uniform state,

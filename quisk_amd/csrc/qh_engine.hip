@@ -709,7 +709,7 @@ int Engine::plan_mixed(ChainCall &k)
     // notch for FM -- applies the matrix in its store and writes the caller's buffer: the output pass (32 B per output sample) goes.
     k.fm_theta_fused = k.split && k.any_nbp && !band6k && !band2g && bnfft == kNfft && !(dbg_forms & 8);
     bool no_lms = true;
-    for (int f = 0; f < 2; f++) for (int p = 0; p < 3; p++) no_lms = no_lms && !lists[L_LMS + 3 * f + p].n;
+    for (int f = 0; f < 2; f++) for (int p = 0; p < 3; p++) no_lms = no_lms && !lms_n(3 * f + p);
     k.direct = k.split && !(dbg_forms & 2) && !eq_list.n && k.every_nbp && !eg.kind && !lists[L_LIM].n && !lists[L_AGC_CUR].n && !lists[L_AGC_OTHER].n && !lists[L_SNBA].n && !lists[L_SNB + 1].n && no_lms &&
                !lists[L_EMNR].n && !lists[L_EMNR + 1].n && !lists[L_EMNR + 2].n && !lists[L_FIX].n && !lists[L_FIX + 1].n && !lists[L_BP1P + 1].n && lists[L_BP1P].n == lists[L_BP1].n && lists[L_RB].n == lists[L_BP1].n &&
                lists[L_USB].n + lists[L_FM].n == lists[L_PLAIN].n && !lists[L_AP].n && !lists[L_AP + 1].n && !ssql_listed() &&
@@ -1076,6 +1076,16 @@ void Engine::lms_at(const ChainCall &k, int pos, double2 *b)
     for (int f = 0; f < 2; f++)
         if (lists[L_LMS + 3 * f + pos].n) hipLaunchKernelGGL(lms_kernel, dim3((unsigned)lists[L_LMS + 3 * f + pos].n), dim3(64), 0, stream, b, buf_cap, (int)k.n_mid,
                                               lists[L_LMS + 3 * f + pos].dev, lms_prm[f], lms_state[f]);
+    // the long form over the other channels, one launch per K in use: a launch's blocks leave another K's channels alone
+    for (int f = 0; f < 2; f++) {
+        const ChanList &l = lms_long_lists[3 * f + pos];
+        if (!l.n) continue;
+        const unsigned Ks = lms_long_Ks[3 * f + pos];
+#define QH_LMS_LONG(K) if (Ks & K) hipLaunchKernelGGL(lms_long_kernel<K>, dim3((unsigned)l.n), dim3(64), 0, stream, b, buf_cap, (int)k.n_mid, (const int *)l.dev, \
+                                                      (const LmsParam *)lms_prm[f], lms_state[f], lms_long_rows[f])
+        QH_LMS_LONG(2); QH_LMS_LONG(4); QH_LMS_LONG(8); QH_LMS_LONG(16); QH_LMS_LONG(32);
+#undef QH_LMS_LONG
+    }
     if (lists[L_EMNR + pos].n)
         hipLaunchKernelGGL(emnr_kernel, dim3((unsigned)lists[L_EMNR + pos].n), dim3(NT), (size_t)emnr_lds_bytes(), stream, b, buf_cap, k.nblk, lists[L_EMNR + pos].dev,
                            emnr_prm, emnr_chan, emnr_scal, emnr_state, emnr_window, tw4096, emnr_GG, emnr_GGS, emnr_zeta, emnr_zeta_true);
@@ -1146,7 +1156,7 @@ int Engine::run_agc(ChainCall &k)
     // multiply applies the output matrix and writes the caller's rows: the output pass goes
     bool no_p1 = !lists[L_BP1P + 1].n && !lists[L_FIX].n && !lists[L_FIX + 1].n && !lists[L_EMNR + 1].n && !lists[L_EMNR + 2].n && !lists[L_AMSQ].n && !meters_on && !k.taps && !eg.kind && !lists[L_AP].n && !lists[L_AP + 1].n &&
                  !ssql_listed();
-    for (int f = 0; f < 2; f++) for (int p = 1; p < 3; p++) no_p1 = no_p1 && !lists[L_LMS + 3 * f + p].n;
+    for (int f = 0; f < 2; f++) for (int p = 1; p < 3; p++) no_p1 = no_p1 && !lms_n(3 * f + p);
     k.agc_direct = tiled && no_p1 && nt_cur == lists[L_PLAIN].n && nt_other == lists[L_BP1].n;
     if (tiled) {
         const int nl = nt_cur > nt_other ? nt_cur : nt_other;

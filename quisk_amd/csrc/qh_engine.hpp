@@ -403,6 +403,17 @@ struct Engine {
     int amsq_ntup = 0, amsq_ntdown = 0;
     LmsParam *lms_prm[2] = { nullptr, nullptr };
     LmsState *lms_state[2] = { nullptr, nullptr };
+    // The long form of anf / anr (lms_long_kernel: more than 64 taps, or a delay of 0 or above 64).  lists[L_LMS + 3 f + k] holds the
+    // short-form channels alone and lms_long_lists[3 f + k] the others, in a block of their own made with the first of them (an engine
+    // without one allocates what it did before); lms_long_Ks: bit log2(K) set when a channel of the list runs at K taps per lane.
+    // lms_long_rows[f]: weights and ring [nch][kLmsLongRow], made when filter f first has such a channel.
+    ChanList lms_long_lists[6];
+    std::vector<int> lms_long_h[6];
+    unsigned lms_long_Ks[6] = { 0, 0, 0, 0, 0, 0 };
+    int *lms_long_list_block = nullptr;
+    double *lms_long_rows[2] = { nullptr, nullptr };
+    static bool lms_long_form(const ChanCfg::Lms &m) { return m.taps > 64 || m.delay < 1 || m.delay > 64; }
+    int lms_n(int k) const { return lists[L_LMS + k].n + lms_long_lists[k].n; }       // channels of either form on LMS list k
     int *levelfade = nullptr;
     AmState *am_state = nullptr;
     // carries of the grid-segmented scans (qh_tiled.hpp: a launch reads the state of its channels and leaves the new one here; a

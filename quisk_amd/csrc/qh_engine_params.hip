@@ -460,6 +460,7 @@ void Engine::build_lists(std::vector<int> (&h)[L_COUNT])
     fq_h.clear(); fq_pairs_h.clear();
     for (std::vector<int> &t : tap_h) t.clear();
     gen_h.clear();
+    for (int k = 0; k < 6; k++) { lms_long_h[k].clear(); lms_long_Ks[k] = 0; }
     for (int ch = 0; ch < nch; ch++) {
         const ChanCfg &c = cfg[(size_t)ch];
         if (c.sender_run) tap_h[0].push_back(ch);
@@ -470,7 +471,13 @@ void Engine::build_lists(std::vector<int> (&h)[L_COUNT])
         if (c.snb_pos() >= 0) h[L_SNB + c.snb_pos()].push_back(ch);
         const int at_agc = (c.bp1_run && !c.bp1_pos) ? 1 : 0;       // the buffer the channel is in when xwcpagc runs
         if (c.emnr_run) h[L_EMNR + (c.emnr_pos ? 1 + at_agc : 0)].push_back(ch);
-        for (int f = 0; f < 2; f++) if (c.lms[f].run) h[L_LMS + 3 * f + (c.lms[f].position ? 1 + at_agc : 0)].push_back(ch);
+        for (int f = 0; f < 2; f++) {
+            if (!c.lms[f].run) continue;
+            const int k = 3 * f + (c.lms[f].position ? 1 + at_agc : 0);
+            if (!lms_long_form(c.lms[f])) { h[L_LMS + k].push_back(ch); continue; }
+            lms_long_h[k].push_back(ch);
+            lms_long_Ks[k] |= (unsigned)lms_long_K(c.lms[f].taps);          // K is a power of two: its own bit
+        }
         if (c.bp1_run) h[L_BP1P + (c.bp1_pos ? 1 : 0)].push_back(ch);
         if (c.fix_before()) h[L_FIX + at_agc].push_back(ch);
         if (c.ap_on()) h[L_AP + (c.bp1_run ? 1 : 0)].push_back(ch);        // where the channel is behind bp1 at either position
@@ -519,6 +526,7 @@ void Engine::build_lists(std::vector<int> (&h)[L_COUNT])
     np_fm = (int)h[L_PAIRS_FM].size() / 2; np_am = (int)h[L_PAIRS_AM].size() / 2; np_sam = (int)h[L_PAIRS_SAM].size() / 2;
     for (int i = 0; i < L_COUNT; i++) lists[i].n = (int)h[i].size();
     for (int b = 0; b < 2; b++) ssql_lists[b].n = (int)ssql_h[b].size();
+    for (int k = 0; k < 6; k++) lms_long_lists[k].n = (int)lms_long_h[k].size();
     for (int t = 0; t < 3; t++) tap_lists[t].n = (int)tap_h[t].size();
     gen_list.n = (int)gen_h.size();
     for (size_t i = 0; i < fq_h.size(); i += 2) { fq_pairs_h.push_back(fq_h[i]); fq_pairs_h.push_back(i + 1 < fq_h.size() ? fq_h[i + 1] : fq_h[i]); }
@@ -662,7 +670,7 @@ int Engine::stages_alloc()
         for (ChanCfg &c : cfg) c.amsq_dirty = true;
     }
     bool any_lms = false;
-    for (int k = 0; k < 6; k++) any_lms = any_lms || lists[L_LMS + k].n;
+    for (int k = 0; k < 6; k++) any_lms = any_lms || lms_n(k);
     if (any_lms && !lms_prm[0]) {
         for (int f = 0; f < 2; f++) {
             if (int rc = alloc(lms_prm[f], nch)) return rc;
@@ -678,6 +686,17 @@ int Engine::stages_alloc()
             QH_HIP(hipStreamSynchronize(stream));
         }
         for (ChanCfg &c : cfg) { c.lms[0].dirty = c.lms[1].dirty = true; c.lms[0].flush = c.lms[1].flush = false; }
+    }
+    // the long form's lists, and the rows of a filter that has a channel on them: zero, as create_anf / flush_anf leave w[] and d[]
+    for (int f = 0; f < 2; f++) {
+        if (!lms_long_lists[3 * f].n && !lms_long_lists[3 * f + 1].n && !lms_long_lists[3 * f + 2].n) continue;
+        if (lms_long_list_block && lms_long_rows[f]) continue;
+        if (int rc = quiesce()) return rc;
+        if (!lms_long_list_block) {
+            if (int rc = alloc(lms_long_list_block, 6LL * nch)) return rc;
+            for (int k = 0; k < 6; k++) lms_long_lists[k].dev = lms_long_list_block + (size_t)nch * k;
+        }
+        if (!lms_long_rows[f]) if (int rc = alloc(lms_long_rows[f], (long long)nch * kLmsLongRow, true)) return rc;
     }
     if (lists[L_LIM].n && !lim_prm) {
         if (int rc = alloc(lim_prm, nch)) return rc;
@@ -747,6 +766,12 @@ int Engine::refresh_lists()
         ss.assign((size_t)nch * 2, 0);
         for (int b = 0; b < 2; b++) std::copy(ssql_h[b].begin(), ssql_h[b].end(), ss.begin() + (size_t)nch * b);
         QH_HIP(hipMemcpyAsync(ssql_list_block, ss.data(), ss.size() * sizeof(int), hipMemcpyHostToDevice, stream));
+    }
+    std::vector<int> ll;
+    if (lms_long_list_block) {
+        ll.assign((size_t)nch * 6, 0);
+        for (int k = 0; k < 6; k++) std::copy(lms_long_h[k].begin(), lms_long_h[k].end(), ll.begin() + (size_t)nch * k);
+        QH_HIP(hipMemcpyAsync(lms_long_list_block, ll.data(), ll.size() * sizeof(int), hipMemcpyHostToDevice, stream));
     }
     std::vector<int> tp;
     if (tap_list_block) {
@@ -886,8 +911,6 @@ int Engine::prm_lms(ChanCfg &c, int ch)
     for (int f = 0; f < 2 && lms_prm[0]; f++) {
         ChanCfg::Lms &m = c.lms[f];
         if (m.dirty) {
-            if (m.run && (m.taps < 1 || m.taps > 64 || m.delay < 1 || m.delay > 64))
-                return set_error(QH_ERR_UNSUPPORTED, "%s: taps %d / delay %d (1..64 each: one tap per lane)", f ? "ANR" : "ANF", m.taps, m.delay);
             // lidx_min, lidx_max, den_mult, lincr, ldecr of create_rxa (RXA.c:290-295,310-315)
             if (int rc = put_row(lms_prm[f], ch, LmsParam{ m.taps, m.delay, f, 0, m.two_mu, m.gamma, f ? 120.0 : 0.0, 200.0, 6.25e-10, 1.0, 3.0 }))
                 return rc;
@@ -895,6 +918,7 @@ int Engine::prm_lms(ChanCfg &c, int ch)
         }
         if (m.flush) {          // flush_anf (anf.c:135-140): delay line and weights; lidx / ngamma carry on
             QH_HIP(hipMemsetAsync(lms_state[f] + ch, 0, offsetof(LmsState, lidx), stream));
+            if (lms_long_rows[f]) QH_HIP(hipMemsetAsync(lms_long_rows[f] + (size_t)ch * kLmsLongRow, 0, (size_t)kLmsLongRow * sizeof(double), stream));
             m.flush = false;
         }
     }
@@ -1842,7 +1866,7 @@ int Engine::rebuild(int new_in, int new_dsp, int new_out, int new_size, int new_
     std::vector<ChanCfg> keep_cfg;
     for (const ChanCfg &c : cfg) keep_cfg.push_back(settings_of(c, new_dsp));
     // the engine-wide settings: one Engine member set through the C ABI outside cfg that is not listed here is lost by a rebuild
-    static_assert(sizeof(Engine) == 8840, "Engine changed: see to Engine::rebuild's Wide and carried state, then update the size");
+    static_assert(sizeof(Engine) == 9128, "Engine changed: see to Engine::rebuild's Wide and carried state, then update the size");
     struct Wide {
         int device, nch; hipStream_t stream; bool own_stream; unsigned long long epoch;
         bool graph_on; long long graph_launches; bool timing, meters_on; int band_tile_pref, snba_ovrlp; std::vector<SnbaTune> snba_tune_h;

@@ -446,10 +446,19 @@ static int lms_run(qh_rxa *h, int ch, int which, int run)
 }
 static int lms_vals(qh_rxa *h, int ch, int which, const int *taps, const int *delay, const double *gain, const double *leakage)
 {
+    // n_taps above ANF_DLINE_SIZE has the reference write past w[]; its mask would fold a delay outside the line, which no client means
+    const bool bad_taps = taps && (*taps < 1 || *taps > kLmsLine);
+    if (bad_taps || (delay && (*delay < 0 || *delay > kLmsLine - 1)))
+        return set_error(QH_ERR_INVALID, "%s: %s %d (taps 1..%d, delay 0..%d)", which ? "ANR" : "ANF", bad_taps ? "taps" : "delay", bad_taps ? *taps : *delay,
+                         kLmsLine, kLmsLine - 1);
     FOR_CH(h, ch, {
         ChanCfg::Lms &m = c.lms[which];
+        const ChanCfg::Lms was = m;
         if (taps) m.taps = *taps;
         if (delay) m.delay = *delay;
+        // the channel moves between lms_kernel's list and the long form's, or to another K of the long form
+        if (Engine::lms_long_form(was) != Engine::lms_long_form(m) || (Engine::lms_long_form(m) && lms_long_K(was.taps) != lms_long_K(m.taps)))
+            h->e.lists_dirty = true;
         if (gain) m.two_mu = *gain;
         if (leakage) m.gamma = *leakage;
         m.flush = true; m.dirty = true;
