@@ -281,7 +281,7 @@ int qh::anb_check_settings(double samplerate, double tau, double hangtime, doubl
     return why ? set_error(QH_ERR_INVALID, "qh_anb_create: %s", why) : QH_OK;       // (the text create_anbEXT has always reported)
 }
 
-struct qh_anb : Bank {
+struct qh_anb : DetBank {
     std::vector<AnbSettings> set;
     std::vector<AnbParam> prm;
     std::vector<double> wave;                           // [nch][kAnbWave]

@@ -1,6 +1,10 @@
-// qh_bank.hpp -- the host code the channel banks in front of the receiver have in common (qh_anb.hip, qh_nob.hip; qh_nb.hip takes
-// bank_open, bank_process_host and bank_synchronize, qh_div.hip bank_open, bank_set and bank_synchronize): a handle is `nch` streams on one device and one HIP stream, with settings that
-// another thread may change between calls.
+// qh_bank.hpp -- the host code the channel banks around the receiver have in common: a handle is `nch` streams on one device and one HIP
+// stream, with settings that another thread may change between calls.  Who takes what:
+//   Bank, bank_open, bank_synchronize               qh_anb.hip, qh_nob.hip, qh_div.hip, qh_varsamp.hip, qh_resample.hip
+//   DetBank (the detector's scratch), bank_grow     qh_anb.hip, qh_nob.hip, and det_enqueue of qh_blank_det.hpp
+//   bank_set                                        qh_anb.hip, qh_nob.hip, qh_div.hip (the resamplers' setter is in qh_design_bank.hpp)
+//   bank_check_rows, bank_process_host              qh_anb.hip, qh_nob.hip
+// qh_nb.hip, whose handle is a struct of its own, takes bank_open, bank_process_host and bank_synchronize.
 #pragma once
 #include <mutex>
 #include <vector>
@@ -8,7 +12,7 @@
 
 namespace qh {
 
-// What every blanker bank holds besides its own settings, tables and history, and the scratch of the detector (qh_blank_det.hpp).
+// What every bank holds besides its own settings, tables and history.
 struct Bank {
     int device = 0, nch = 0;
     hipStream_t stream = nullptr;
@@ -16,26 +20,34 @@ struct Bank {
     std::mutex mtx;                                     // setters may come from another thread than process (cs_update)
     bool dirty = true;                                  // host settings newer than the device's
     int cur = 0;                                        // which of a bank's two history buffers is the current one
-    // per-call scratch of the detector, grown with n: [nch][nt] tile values, [nch][nw] words of bits
-    int cap = 0;
-    long long nt = 0, nw = 0;
-    double *d_ends = nullptr;
-    unsigned long long *d_trb = nullptr;
     void quiesce()
     {
         (void)hipSetDevice(device);
         if (stream) (void)hipStreamSynchronize(stream);
     }
+    ~Bank()                                             // (a bank's own destructor has freed its buffers behind a quiesce of its own)
+    {
+        quiesce();
+        if (own_stream && stream) (void)hipStreamDestroy(stream);
+    }
+};
+
+// A blanker bank: the handle and the per-call scratch of the detector (qh_blank_det.hpp), grown with n: [nch][nt] tile values,
+// [nch][nw] words of bits.  Freed behind a quiesce, before ~Bank destroys the stream.
+struct DetBank : Bank {
+    int cap = 0;
+    long long nt = 0, nw = 0;
+    double *d_ends = nullptr;
+    unsigned long long *d_trb = nullptr;
     void free_scratch()
     {
         (void)hipFree(d_ends); (void)hipFree(d_trb);
         d_ends = nullptr; d_trb = nullptr; cap = 0;
     }
-    ~Bank()                                             // (a bank's own destructor has freed its buffers behind a quiesce of its own)
+    ~DetBank()
     {
         quiesce();
         free_scratch();
-        if (own_stream && stream) (void)hipStreamDestroy(stream);
     }
 };
 
@@ -57,7 +69,7 @@ template <typename H> int bank_open(H *h, int device, void *stream, const char *
 }
 
 // The detector's scratch for calls of up to n samples, in tiles of `tile` samples; behind everything enqueued so far when it grows.
-static inline int bank_grow(Bank *h, int n, int tile, const char *what)
+static inline int bank_grow(DetBank *h, int n, int tile, const char *what)
 {
     if (n <= h->cap) return QH_OK;
     QH_HIP(hipStreamSynchronize(h->stream));

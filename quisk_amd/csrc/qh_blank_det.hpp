@@ -122,7 +122,7 @@ __global__ __launch_bounds__(64) void carry_kernel(int n, const Param *prm, cons
 
 // det 0, the carry and det 1 of one call of n samples on the bank's stream; the flags are in h.d_trb (row stride h.nw) behind them.
 template <typename Param, typename State>
-void det_enqueue(const Bank &h, const double2 *in, long long in_stride, int n, const Param *d_prm, State *d_state)
+void det_enqueue(const DetBank &h, const double2 *in, long long in_stride, int n, const Param *d_prm, State *d_state)
 {
     const unsigned ntile = (unsigned)((n + kDetL - 1) / kDetL), nch = (unsigned)h.nch;
     if (ntile > 1)

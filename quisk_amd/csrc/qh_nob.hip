@@ -465,7 +465,7 @@ int qh::nob_check_settings(double samplerate, int mode, double slewtime, double 
     return why ? set_error(QH_ERR_INVALID, "%s", why) : QH_OK;
 }
 
-struct qh_nob : Bank {
+struct qh_nob : DetBank {
     std::vector<NobSettings> set;
     std::vector<NobParam> prm;
     std::vector<double> awave, hwave;                   // [nch][kNobWave]

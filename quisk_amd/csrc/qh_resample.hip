@@ -25,7 +25,7 @@
 #include <memory>
 #include <utility>
 #include <vector>
-#include "qh_bank.hpp"
+#include "qh_design_bank.hpp"
 #include "qh_design.hpp"
 
 using namespace qh;
@@ -254,21 +254,14 @@ int qh::resample_check_settings(int in_rate, int out_rate, double fc, int ncoef,
     return why ? set_error(QH_ERR_INVALID, "qh_resample_create: %s", why) : QH_OK;
 }
 
-struct qh_resample : Bank {
+struct qh_resample : DesignBank<RsSettings, RsDesign, RsParam, kRsSlots> {
     int dtype = QH_RESAMPLE_C64;
     int g_first = 8;                                    // the G tried first for L >= 16: measured 2 .. 16, DESIGN.md row b23 (QH_RESAMPLE_G,
                                                         // diagnostics: a power of two, 1 .. 256, read at create)
-    std::vector<RsSettings> set;
-    std::vector<std::shared_ptr<RsDesign>> des;
-    std::vector<RsParam> prm;
     std::vector<int> phnum;
-    RsParam *d_prm = nullptr;
     RsCall *d_call = nullptr, *h_call = nullptr;        // h_call: a ring of rows in pinned host memory, a row free again when its copy has run
     void *hist[2] = { nullptr, nullptr };
     int hcap = 0;
-    hipEvent_t ev[kRsSlots] = {};
-    bool ev_used[kRsSlots] = {};
-    int slot = 0;
 
     bool fv() const { return rs_fv(dtype); }
     size_t es_io() const { return fv() ? sizeof(float) : sizeof(double2); }
@@ -277,29 +270,22 @@ struct qh_resample : Bank {
     ~qh_resample()
     {
         quiesce();
-        (void)hipFree(d_prm); (void)hipFree(d_call); (void)hipFree(hist[0]); (void)hipFree(hist[1]);
+        (void)hipFree(d_call); (void)hipFree(hist[0]); (void)hipFree(hist[1]);
         if (h_call) (void)hipHostFree(h_call);
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-        des.clear();                                    // (behind the quiesce: no kernel reads an h any more)
     }
 
+    const char *refusal(const RsSettings &s) const { return rs_refusal(s, fv()); }
+
     // The design of `s`: one a channel of the bank (or of `more`) already has, or a new one with h in device memory.  Null: the message is set.
-    std::shared_ptr<RsDesign> design(const RsSettings &s, const std::vector<std::shared_ptr<RsDesign>> &more, const char *name)
+    std::shared_ptr<RsDesign> design(const RsSettings &s, const Designs &more, const char *name)
     {
-        for (const std::vector<std::shared_ptr<RsDesign>> *list : { &std::as_const(des), &more })
-            for (const auto &d : *list)
-                if (d && d->is(s)) return d;
+        if (auto d = cached(s, more)) return d;
         const ResamplerDesign hd = fv() ? design_resampler_fv(s.in_rate, s.out_rate) : design_resampler(s.in_rate, s.out_rate, s.fc, s.ncoef, s.gain, s.fc_low);
         auto d = std::make_shared<RsDesign>();
         d->in_rate = s.in_rate; d->out_rate = s.out_rate; d->ncoef_in = s.ncoef; d->fc = s.fc; d->fc_low = s.fc_low; d->gain = s.gain;
         d->L = hd.L; d->M = hd.M; d->cpp = hd.cpp; d->ncoef = hd.ncoef;
         d->h = resampler_phase_major(hd);
-        if (dev_alloc(&d->d_h, (size_t)hd.ncoef) != hipSuccess || hipMemcpy(d->d_h, d->h.data(), (size_t)hd.ncoef * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
-            set_error(QH_ERR_HIP, "%s: the upload of %d coefficients failed", name, hd.ncoef);
-            return nullptr;
-        }
-        return d;
+        return with_taps(d, d->h.data(), hd.ncoef, name);
     }
 
     void fill_param(int ch)
@@ -322,16 +308,6 @@ struct qh_resample : Bank {
         if (!prm[ch].lds) return 0;
         int Q;
         return rs_need(prm[ch].L, prm[ch].M, prm[ch].cpp, prm[ch].G, &Q);
-    }
-
-    // host settings -> device, behind everything enqueued so far
-    int upload()
-    {
-        if (!dirty) return QH_OK;
-        QH_HIP(hipStreamSynchronize(stream));
-        QH_HIP(hipMemcpy(d_prm, prm.data(), (size_t)nch * sizeof(RsParam), hipMemcpyHostToDevice));
-        dirty = false;
-        return QH_OK;
     }
 
     // history rows of at least `want` samples: the rows move to the end of longer ones, behind everything enqueued so far
@@ -357,8 +333,20 @@ struct qh_resample : Bank {
         return QH_OK;
     }
 
+    // design_bank_set's steps: the history must hold cpp - 1 samples of the new designs; the restart reads nothing of d_prm, so the new
+    // rows wait for the next call's upload
+    int before_adopt(const Designs &fresh, const char *name)
+    {
+        int want = 0;
+        for (const auto &d : fresh)
+            if (d) want = std::max(want, d->cpp - 1);
+        return grow_hist(want, name);
+    }
+    void designed(int) {}
+    int before_restart() { return QH_OK; }
+
     // flush_resample (resample.c:113-118): the ring zeroed and phnum 0
-    int restart(int ch)
+    int restart(int ch, int)
     {
         QH_HIP(hipMemsetAsync(static_cast<char *>(hist[cur]) + (size_t)ch * hcap * es_acc(), 0, (size_t)hcap * es_acc(), stream));
         phnum[ch] = 0;
@@ -385,43 +373,12 @@ struct qh_resample : Bank {
 
 namespace {
 
-// One setter: `edit` changes a copy of the settings of channel ch (-1: every channel) and says whether the channel is to be restarted;
-// a refusal or a failed upload leaves everything as it was.  restart 0: nothing starts over; 1: flush; 2: calc_resample
-template <typename F> int rs_set(qh_resample *h, int ch, const char *name, int restart, bool cplx_only, F edit)
+// A setter of the band edges (a new design): the real-float form has none
+template <typename F> int rs_set_edges(qh_resample *h, int ch, const char *name, F edit)
 {
-    if (!h || ch < -1 || ch >= h->nch) return set_error(QH_ERR_INVALID, "%s: bad arguments", name);
-    if (cplx_only && h->fv()) return set_error(QH_ERR_INVALID, "%s: the real-float form has no band edges to set (create_resampleF fixes them)", name);
-    std::lock_guard<std::mutex> lk(h->mtx);
-    const int c0 = ch < 0 ? 0 : ch, c1 = ch < 0 ? h->nch : ch + 1;
-    std::vector<RsSettings> next(h->set.begin() + c0, h->set.begin() + c1);
-    std::vector<char> touched((size_t)(c1 - c0), 0);
-    for (int c = c0; c < c1; c++) {
-        touched[c - c0] = edit(next[c - c0]) ? 1 : 0;
-        if (const char *why = rs_refusal(next[c - c0], h->fv())) return set_error(QH_ERR_INVALID, "%s: %s", name, why);
-    }
-    QH_HIP(hipSetDevice(h->device));
-    std::vector<std::shared_ptr<RsDesign>> fresh((size_t)(c1 - c0));
-    if (restart == 2) {
-        int want = 0;
-        for (int c = c0; c < c1; c++) {
-            if (!touched[c - c0]) continue;
-            fresh[c - c0] = h->design(next[c - c0], fresh, name);
-            if (!fresh[c - c0]) return QH_ERR_HIP;
-            want = std::max(want, fresh[c - c0]->cpp - 1);
-        }
-        if (int rc = h->grow_hist(want, name)) return rc;
-        QH_HIP(hipStreamSynchronize(h->stream));       // a design nobody holds any more is freed below: no kernel may still read it
-    }
-    for (int c = c0; c < c1; c++) {
-        h->set[c] = next[c - c0];
-        if (restart == 2 && touched[c - c0]) h->des[c] = fresh[c - c0];
-        h->fill_param(c);
-    }
-    if (!restart) return QH_OK;
-    for (int c = c0; c < c1; c++)
-        if (touched[c - c0])
-            if (int rc = h->restart(c)) return rc;
-    return QH_OK;
+    if (h && ch >= -1 && ch < h->nch && h->fv())
+        return set_error(QH_ERR_INVALID, "%s: the real-float form has no band edges to set (create_resampleF fixes them)", name);
+    return design_bank_set(h, ch, name, 2, edit);
 }
 
 template <bool kCplx>
@@ -462,8 +419,7 @@ qh_resample *qh_resample_create(int device, int nch, int in_rate, int out_rate, 
     for (int ch = 0; ch < nch; ch++) h->fill_param(ch);
     if (dev_alloc(&h->d_prm, (size_t)nch) != hipSuccess || dev_alloc(&h->d_call, (size_t)nch) != hipSuccess) return fail("hipMalloc");
     if (hipHostMalloc((void **)&h->h_call, (size_t)kRsSlots * (size_t)nch * sizeof(RsCall), hipHostMallocDefault) != hipSuccess) { h->h_call = nullptr; return fail("hipHostMalloc"); }
-    for (hipEvent_t &e : h->ev)
-        if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { e = nullptr; return fail("event creation"); }
+    if (!h->create_slots()) return fail("event creation");
     // the ring of the reference is zeroed (malloc0, resample.c:74)
     if (h->grow_hist(std::max(d->cpp - 1, 1), "qh_resample_create") != QH_OK) { delete h; return nullptr; }
     if (h->upload() != QH_OK) { delete h; return nullptr; }
@@ -494,18 +450,18 @@ int qh_resample_taps(qh_resample *h, int ch, double *out, int cap)
     return d.ncoef;
 }
 
-int qh_resample_flush(qh_resample *h, int ch) { return rs_set(h, ch, "qh_resample_flush", 1, false, [](RsSettings &) { return true; }); }
+int qh_resample_flush(qh_resample *h, int ch) { return design_bank_set(h, ch, "qh_resample_flush", 1, [](RsSettings &) { return true; }); }
 int qh_resample_set_run(qh_resample *h, int ch, int run)
 {
-    return rs_set(h, ch, "qh_resample_set_run", 0, false, [=](RsSettings &s) { s.run = run != 0; return true; });
+    return design_bank_set(h, ch, "qh_resample_set_run", 0, [=](RsSettings &s) { s.run = run != 0; return true; });
 }
 int qh_resample_set_rates(qh_resample *h, int ch, int in_rate, int out_rate)
 {
-    return rs_set(h, ch, "qh_resample_set_rates", 2, false, [=](RsSettings &s) { s.in_rate = in_rate; s.out_rate = out_rate; return true; });
+    return design_bank_set(h, ch, "qh_resample_set_rates", 2, [=](RsSettings &s) { s.in_rate = in_rate; s.out_rate = out_rate; return true; });
 }
 int qh_resample_set_fc_low(qh_resample *h, int ch, double fc_low)
 {
-    return rs_set(h, ch, "qh_resample_set_fc_low", 2, true, [=](RsSettings &s) {
+    return rs_set_edges(h, ch, "qh_resample_set_fc_low", [=](RsSettings &s) {
         if (fc_low == s.fc_low) return false;           // resample.c:187
         s.fc_low = fc_low;
         return true;
@@ -513,7 +469,7 @@ int qh_resample_set_fc_low(qh_resample *h, int ch, double fc_low)
 }
 int qh_resample_set_bandwidth(qh_resample *h, int ch, double fc_low, double fc_high)
 {
-    return rs_set(h, ch, "qh_resample_set_bandwidth", 2, true, [=](RsSettings &s) {
+    return rs_set_edges(h, ch, "qh_resample_set_bandwidth", [=](RsSettings &s) {
         if (fc_low == s.fc_low && fc_high == s.fc) return false;        // resample.c:197
         s.fc_low = fc_low; s.fc = fc_high;
         return true;
@@ -552,8 +508,8 @@ int qh_resample_process(qh_resample *h, const void *d_in, long long in_stride, v
     QH_HIP(hipSetDevice(h->device));
     if (int rc = h->upload()) return rc;
     hipStream_t s = h->stream;
-    const int sl = h->slot;
-    if (h->ev_used[sl]) QH_HIP(hipEventSynchronize(h->ev[sl]));        // (only with kRsSlots calls in flight)
+    int sl;
+    if (int rc = h->take_slot(&sl)) return rc;
     RsCall *row = h->h_call + (size_t)sl * nch;
     std::vector<int> next((size_t)nch);
     long long ntiles = 1, need = 1;
@@ -576,9 +532,7 @@ int qh_resample_process(qh_resample *h, const void *d_in, long long in_stride, v
     const int nhb = (hist_rows + kRsBlock - 1) / kRsBlock;
     if (ntiles + nhb > INT_MAX) return set_error(QH_ERR_INVALID, "qh_resample_process: too many tiles for one launch");
     QH_HIP(hipMemcpyAsync(h->d_call, row, (size_t)nch * sizeof(RsCall), hipMemcpyHostToDevice, s));
-    QH_HIP(hipEventRecord(h->ev[sl], s));
-    h->ev_used[sl] = true;
-    h->slot = (sl + 1) % kRsSlots;
+    if (int rc = h->slot_enqueued()) return rc;
     const size_t lds = (size_t)need * h->es_acc();
     if (h->fv()) rs_launch<false>(h, d_in, in_stride, d_out, out_stride, n, (int)ntiles, nhb, lds);
     else rs_launch<true>(h, d_in, in_stride, d_out, out_stride, n, (int)ntiles, nhb, lds);

@@ -20,7 +20,7 @@
 #include <memory>
 #include <utility>
 #include <vector>
-#include "qh_bank.hpp"
+#include "qh_design_bank.hpp"
 #include "qh_design.hpp"
 #include "qh_varsamp.hpp"
 
@@ -202,13 +202,9 @@ int qh::varsamp_check_settings(int in_rate, int out_rate, int R, double fc, doub
     return why ? set_error(QH_ERR_INVALID, "qh_varsamp_create: %s", why) : QH_OK;
 }
 
-struct qh_varsamp : Bank {
-    std::vector<VsSettings> set;
-    std::vector<std::shared_ptr<VsDesign>> des;
-    std::vector<VsParam> prm;
+struct qh_varsamp : DesignBank<VsSettings, VsDesign, VsParam, kVsSlots> {
     // what the host knows of every channel's inv_cvar (the value itself is in device memory): the last var and bounds of where it stands
     std::vector<double> var_last, inv_lo, inv_hi;
-    VsParam *d_prm = nullptr;
     VarsampState *d_state = nullptr;
     double2 *hist[2] = { nullptr, nullptr };
     int *d_cnt = nullptr;
@@ -218,9 +214,6 @@ struct qh_varsamp : Bank {
     double *d_rec_h = nullptr;
     // the calls' var: a ring of rows in host memory that the device reads, a row free again when its call's walk has run
     double *h_var = nullptr, *dv_var = nullptr;
-    hipEvent_t ev[kVsSlots] = {};
-    bool ev_used[kVsSlots] = {};
-    int slot = 0;
 
     void free_rec()
     {
@@ -231,28 +224,21 @@ struct qh_varsamp : Bank {
     {
         quiesce();
         free_rec();
-        (void)hipFree(d_prm); (void)hipFree(d_state); (void)hipFree(hist[0]); (void)hipFree(hist[1]); (void)hipFree(d_cnt);
+        (void)hipFree(d_state); (void)hipFree(hist[0]); (void)hipFree(hist[1]); (void)hipFree(d_cnt);
         if (h_var) (void)hipHostFree(h_var);
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-        des.clear();                                    // (behind the quiesce: no kernel reads an h any more)
     }
 
+    static const char *refusal(const VsSettings &s) { return vs_refusal(s); }
+
     // The design of `s`: one a channel of the bank (or of `more`) already has, or a new one with h in device memory.  Null: the message is set.
-    std::shared_ptr<VsDesign> design(const VsSettings &s, const std::vector<std::shared_ptr<VsDesign>> &more, const char *name)
+    std::shared_ptr<VsDesign> design(const VsSettings &s, const Designs &more, const char *name)
     {
-        for (const std::vector<std::shared_ptr<VsDesign>> *list : { &std::as_const(des), &more })
-            for (const auto &d : *list)
-                if (d && d->is(s)) return d;
+        if (auto d = cached(s, more)) return d;
         const VarsampDesign hd = design_varsamp(s.in_rate, s.out_rate, s.R, s.fc, s.fc_low, s.gain);
         auto d = std::make_shared<VsDesign>();
         d->in_rate = s.in_rate; d->out_rate = s.out_rate; d->R = s.R; d->fc = s.fc; d->fc_low = s.fc_low; d->gain = s.gain;
         d->nom_ratio = hd.nom_ratio; d->rsize = hd.rsize; d->ncoef = hd.ncoef;
-        if (dev_alloc(&d->d_h, (size_t)hd.ncoef) != hipSuccess || hipMemcpy(d->d_h, hd.h.data(), (size_t)hd.ncoef * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
-            set_error(QH_ERR_HIP, "%s: the upload of %d coefficients failed", name, hd.ncoef);
-            return nullptr;
-        }
-        return d;
+        return with_taps(d, hd.h.data(), hd.ncoef, name);
     }
 
     void fill_param(int ch)
@@ -262,15 +248,10 @@ struct qh_varsamp : Bank {
         dirty = true;
     }
 
-    // host settings -> device, behind everything enqueued so far
-    int upload()
-    {
-        if (!dirty) return QH_OK;
-        QH_HIP(hipStreamSynchronize(stream));
-        QH_HIP(hipMemcpy(d_prm, prm.data(), (size_t)nch * sizeof(VsParam), hipMemcpyHostToDevice));
-        dirty = false;
-        return QH_OK;
-    }
+    // design_bank_set's steps: the reset kernel reads d_prm, so the new rows go up before a restart
+    int before_adopt(const Designs &, const char *) { return QH_OK; }
+    void designed(int ch) { inv_known(ch, var_last[ch]); }
+    int before_restart() { return upload(); }
 
     // inv_cvar = 1 / (var * nom_ratio) freshly set (calc_varsamp, or a call with varmode 0): its first step clears the 16 bits
     void inv_known(int ch, double var)
@@ -335,54 +316,15 @@ struct qh_varsamp : Bank {
         return QH_OK;
     }
 
-    int restart(int ch, int calc)
+    int restart(int ch, int mode)                       // mode 1: flush; 2: calc_varsamp
     {
-        hipLaunchKernelGGL(varsamp_reset_kernel, dim3((kVsHist + 255) / 256, 1), dim3(256), 0, stream, d_state, hist[cur], d_prm, ch, calc);
+        hipLaunchKernelGGL(varsamp_reset_kernel, dim3((kVsHist + 255) / 256, 1), dim3(256), 0, stream, d_state, hist[cur], d_prm, ch, (int)(mode == 2));
         QH_HIP(hipGetLastError());
         return QH_OK;
     }
 };
 
 namespace {
-
-// One setter: `edit` changes a copy of the settings of channel ch (-1: every channel) and says whether the channel is to be restarted;
-// a refusal or a failed upload leaves everything as it was.  restart 0: nothing starts over; 1: flush; 2: calc_varsamp
-template <typename F> int vs_set(qh_varsamp *h, int ch, const char *name, int restart, F edit)
-{
-    if (!h || ch < -1 || ch >= h->nch) return set_error(QH_ERR_INVALID, "%s: bad arguments", name);
-    std::lock_guard<std::mutex> lk(h->mtx);
-    const int c0 = ch < 0 ? 0 : ch, c1 = ch < 0 ? h->nch : ch + 1;
-    std::vector<VsSettings> next(h->set.begin() + c0, h->set.begin() + c1);
-    std::vector<char> touched((size_t)(c1 - c0), 0);
-    for (int c = c0; c < c1; c++) {
-        touched[c - c0] = edit(next[c - c0]) ? 1 : 0;
-        if (const char *why = vs_refusal(next[c - c0])) return set_error(QH_ERR_INVALID, "%s: %s", name, why);
-    }
-    QH_HIP(hipSetDevice(h->device));
-    std::vector<std::shared_ptr<VsDesign>> fresh((size_t)(c1 - c0));
-    if (restart == 2) {
-        for (int c = c0; c < c1; c++) {
-            if (!touched[c - c0]) continue;
-            fresh[c - c0] = h->design(next[c - c0], fresh, name);
-            if (!fresh[c - c0]) return QH_ERR_HIP;
-        }
-        QH_HIP(hipStreamSynchronize(h->stream));       // a design nobody holds any more is freed below: no kernel may still read it
-    }
-    for (int c = c0; c < c1; c++) {
-        h->set[c] = next[c - c0];
-        if (restart == 2 && touched[c - c0]) {
-            h->des[c] = fresh[c - c0];
-            h->inv_known(c, h->var_last[c]);
-        }
-        h->fill_param(c);
-    }
-    if (!restart) return QH_OK;
-    if (int rc = h->upload()) return rc;
-    for (int c = c0; c < c1; c++)
-        if (touched[c - c0])
-            if (int rc = h->restart(c, restart == 2)) return rc;
-    return QH_OK;
-}
 
 const char *vs_check_call(const qh_varsamp *h, const void *in, long long in_stride, const void *out, int n, const double *var)
 {
@@ -424,8 +366,7 @@ qh_varsamp *qh_varsamp_create(int device, int nch, int in_rate, int out_rate, in
         return fail("hipMalloc");
     if (hipHostMalloc((void **)&h->h_var, (size_t)kVsSlots * (size_t)nch * sizeof(double), hipHostMallocDefault) != hipSuccess) { h->h_var = nullptr; return fail("hipHostMalloc"); }
     if (hipHostGetDevicePointer((void **)&h->dv_var, h->h_var, 0) != hipSuccess) return fail("hipHostGetDevicePointer");
-    for (hipEvent_t &e : h->ev)
-        if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { e = nullptr; return fail("event creation"); }
+    if (!h->create_slots()) return fail("event creation");
     // the ring of the reference is zeroed (malloc0, varsamp.c:63)
     if (dev_zero(h->hist[0], hb * sizeof(double2)) != hipSuccess || dev_zero(h->hist[1], hb * sizeof(double2)) != hipSuccess ||
         dev_zero(h->d_cnt, (size_t)nch * sizeof(int)) != hipSuccess)
@@ -444,19 +385,19 @@ int qh_varsamp_rsize(qh_varsamp *h, int ch)
     return h->des[ch]->rsize;
 }
 
-int qh_varsamp_flush(qh_varsamp *h, int ch) { return vs_set(h, ch, "qh_varsamp_flush", 1, [](VsSettings &) { return true; }); }
-int qh_varsamp_set_run(qh_varsamp *h, int ch, int run) { return vs_set(h, ch, "qh_varsamp_set_run", 0, [=](VsSettings &s) { s.run = run != 0; return true; }); }
+int qh_varsamp_flush(qh_varsamp *h, int ch) { return design_bank_set(h, ch, "qh_varsamp_flush", 1, [](VsSettings &) { return true; }); }
+int qh_varsamp_set_run(qh_varsamp *h, int ch, int run) { return design_bank_set(h, ch, "qh_varsamp_set_run", 0, [=](VsSettings &s) { s.run = run != 0; return true; }); }
 int qh_varsamp_set_varmode(qh_varsamp *h, int ch, int varmode)
 {
-    return vs_set(h, ch, "qh_varsamp_set_varmode", 0, [=](VsSettings &s) { s.varmode = varmode != 0; return true; });
+    return design_bank_set(h, ch, "qh_varsamp_set_varmode", 0, [=](VsSettings &s) { s.varmode = varmode != 0; return true; });
 }
 int qh_varsamp_set_rates(qh_varsamp *h, int ch, int in_rate, int out_rate)
 {
-    return vs_set(h, ch, "qh_varsamp_set_rates", 2, [=](VsSettings &s) { s.in_rate = in_rate; s.out_rate = out_rate; return true; });
+    return design_bank_set(h, ch, "qh_varsamp_set_rates", 2, [=](VsSettings &s) { s.in_rate = in_rate; s.out_rate = out_rate; return true; });
 }
 int qh_varsamp_set_bandwidth(qh_varsamp *h, int ch, double fc_low, double fc_high)
 {
-    return vs_set(h, ch, "qh_varsamp_set_bandwidth", 2, [=](VsSettings &s) {
+    return design_bank_set(h, ch, "qh_varsamp_set_bandwidth", 2, [=](VsSettings &s) {
         if (fc_low == s.fc_low && fc_high == s.fc) return false;        // varsamp.c:219
         s.fc_low = fc_low; s.fc = fc_high;
         return true;
@@ -483,15 +424,13 @@ int qh_varsamp_process(qh_varsamp *h, const void *d_in, long long in_stride, voi
     if (int rc = h->scratch(mo)) return rc;
     const int nch = h->nch;
     hipStream_t s = h->stream;
-    const int sl = h->slot;
-    if (h->ev_used[sl]) QH_HIP(hipEventSynchronize(h->ev[sl]));        // (only with kVsSlots calls in flight)
+    int sl;
+    if (int rc = h->take_slot(&sl)) return rc;
     std::copy(var, var + nch, h->h_var + (size_t)sl * nch);
     hipLaunchKernelGGL(varsamp_walk_kernel, dim3((unsigned)((nch + 63) / 64)), dim3(64), 0, s, nch, n, h->d_prm, h->d_state, h->dv_var + (size_t)sl * nch,
                        h->d_rec_i, h->d_rec_h, (int)std::min<long long>(h->cap_out, 0x7fffffff), h->d_cnt, d_count);
     QH_HIP(hipGetLastError());
-    QH_HIP(hipEventRecord(h->ev[sl], s));
-    h->ev_used[sl] = true;
-    h->slot = (sl + 1) % kVsSlots;
+    if (int rc = h->slot_enqueued()) return rc;
     // the window a tile of a running channel can need, for the launch's LDS
     long long need = 1;
     int hist_rows = 0;

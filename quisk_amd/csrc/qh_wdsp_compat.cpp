@@ -18,11 +18,14 @@
 #include <functional>
 #include <mutex>
 #include <vector>
-#include "qh_internal.hpp"
+#include "qh_wdsp_internal.hpp"
 #include "qh_emnr_tables.hpp"
 
 extern "C" int qh_rxa_flush(qh_rxa *e);
 extern "C" void qh_wdsp_shim_release_device(int channel);
+
+thread_local int qh::wdsp::g_status = QH_OK;
+using qh::wdsp::g_status;
 
 namespace {
 
@@ -177,7 +180,6 @@ struct Chan {
 
 Chan g_ch[kMaxChannels];
 std::recursive_mutex g_mtx[kMaxChannels];   // csEXCH + csDSP: setters may come from another thread
-thread_local int g_status = QH_OK;
 
 bool valid(int channel)
 {
@@ -993,7 +995,7 @@ struct Shim {
     // qh_wdsp_fexchange0_device: the ring in device memory (d_cap samples; `dev`: it holds the ring's contents, not `buf`)
     double *d_buf = nullptr; int d_cap = 0; bool dev = false;
     int device = -1;                    // where d_buf and the events live (the device that was current when the ring went there)
-    hipEvent_t ev_in = nullptr, ev_out = nullptr;
+    qh::wdsp::StreamJoin join;
 };
 Shim g_shim[kMaxChannels];
 
@@ -1037,8 +1039,7 @@ extern "C" void qh_wdsp_shim_release_device(int channel)
     if (s.dev && shim_side(s, false, 0) != QH_OK) { s.sizeBuf = 0; s.W = 0; s.R = 0; s.nBuf = 0; }
     s.dev = false;
     if (s.d_buf) { (void)hipDeviceSynchronize(); (void)hipFree(s.d_buf); s.d_buf = nullptr; s.d_cap = 0; }
-    if (s.ev_in) { (void)hipEventDestroy(s.ev_in); s.ev_in = nullptr; }
-    if (s.ev_out) { (void)hipEventDestroy(s.ev_out); s.ev_out = nullptr; }
+    s.join.release();
     s.device = -1;
     if (moved) (void)hipSetDevice(cur);
 }
@@ -1121,11 +1122,7 @@ int qh_wdsp_fexchange0_device(int channel, void *d_samples, int nSamples, void *
     if (int rc = shim_side(s, true, want)) { g_status = rc; return 0; }
     s.sizeBuf = want;
     hipStream_t es = (hipStream_t)qh_rxa_stream(c.eng);
-    if (!s.ev_in && (hipEventCreateWithFlags(&s.ev_in, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&s.ev_out, hipEventDisableTiming) != hipSuccess)) {
-        g_status = qh::set_error(QH_ERR_HIP, "qh_wdsp_fexchange0_device: event creation failed");
-        return 0;
-    }
-    if (cs != es) { (void)hipEventRecord(s.ev_in, cs); (void)hipStreamWaitEvent(es, s.ev_in, 0); }
+    if (int rc = s.join.enter(cs, es, "qh_wdsp_fexchange0_device")) { g_status = rc; return 0; }
     hipLaunchKernelGGL(shim_in_kernel, dim3((unsigned)((nSamples + 255) / 256)), dim3(256), 0, es, (const double2 *)x, nSamples,
                        reinterpret_cast<double2 *>(s.d_buf), s.W, s.sizeBuf);         // (the ring is longer than the call: one wrap at most)
     s.W = (s.W + nSamples) % s.sizeBuf;
@@ -1140,7 +1137,7 @@ int qh_wdsp_fexchange0_device(int channel, void *d_samples, int nSamples, void *
     }
     if (nout > 0) hipLaunchKernelGGL(shim_scale_kernel, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0, es, x, nout);
     if (hipGetLastError() != hipSuccess) g_status = qh::set_error(QH_ERR_HIP, "qh_wdsp_fexchange0_device: launch failed");
-    if (cs != es) { (void)hipEventRecord(s.ev_out, es); (void)hipStreamWaitEvent(cs, s.ev_out, 0); }
+    s.join.leave(cs, es);
     return nout;
 }
 
@@ -1182,671 +1179,3 @@ void SetRXASNBApmultmin(int channel, double pmultmin) { WDSP_SETTER(qh_rxa_SetRX
 
 }  // extern "C"
 
-// ---- the blankers in front of fexchange0: create_anbEXT ... SetEXTANBThreshold (wdsp/nob.c:307-422), and the second one ("NB2"),
-// create_nobEXT ... SetEXTNOBThreshold (wdsp/nobII.c:605-734) --------------------------------------------------------------------------
-// panb[id], nob.c:307-308, and pnob[id], nobII.c:605-606: each id a one-channel bank on a stream of its own, with staging rows that
-// let in == out
-namespace {
-template <typename B> struct Ext {
-    B *b = nullptr;
-    int buffsize = 0, cap = 0;
-    hipStream_t stream = nullptr;
-    double *d_in = nullptr, *d_out = nullptr;
-    hipEvent_t ev_in = nullptr, ev_out = nullptr;
-};
-
-constexpr int kMaxExtAnbs = 32;     // MAX_EXT_ANBS, nob.c:307
-Ext<qh_anb> g_anb[kMaxExtAnbs];
-std::recursive_mutex g_anb_mtx[kMaxExtAnbs];
-constexpr int kMaxExtNobs = 32;     // MAX_EXT_NOBS, nobII.c:605
-Ext<qh_nob> g_nob[kMaxExtNobs];
-std::recursive_mutex g_nob_mtx[kMaxExtNobs];
-
-// What tells the two apart: the table, the bank's functions, and the names the messages carry
-struct AnbExt {
-    typedef qh_anb Bank;
-    static constexpr int count = kMaxExtAnbs;
-    static Ext<qh_anb> *slots() { return g_anb; }
-    static std::recursive_mutex *mutexes() { return g_anb_mtx; }
-    static constexpr auto destroy = qh_anb_destroy;
-    static constexpr auto process = qh_anb_process;
-    static constexpr const char *tag = "ANB", *x_host = "xanbEXT", *x_device = "qh_wdsp_xanbEXT_device";
-};
-struct NobExt {
-    typedef qh_nob Bank;
-    static constexpr int count = kMaxExtNobs;
-    static Ext<qh_nob> *slots() { return g_nob; }
-    static std::recursive_mutex *mutexes() { return g_nob_mtx; }
-    static constexpr auto destroy = qh_nob_destroy;
-    static constexpr auto process = qh_nob_process;
-    static constexpr const char *tag = "NOB", *x_host = "xnobEXT", *x_device = "qh_wdsp_xnobEXT_device";
-};
-
-template <typename X> void ext_release(Ext<typename X::Bank> &a)
-{
-    if (a.b) X::destroy(a.b);                   // (waits for the stream)
-    (void)hipFree(a.d_in); (void)hipFree(a.d_out);
-    if (a.ev_in) (void)hipEventDestroy(a.ev_in);
-    if (a.ev_out) (void)hipEventDestroy(a.ev_out);
-    if (a.stream) (void)hipStreamDestroy(a.stream);
-    a = Ext<typename X::Bank>();
-}
-
-// The slot of a created blanker, locked
-template <typename X> struct LockedExt {
-    Ext<typename X::Bank> *a = nullptr;
-    std::unique_lock<std::recursive_mutex> lk;
-    explicit LockedExt(int id)
-    {
-        g_status = QH_OK;
-        if (id < 0 || id >= X::count) { g_status = qh::set_error(QH_ERR_INVALID, "%s id %d out of range", X::tag, id); return; }
-        lk = std::unique_lock<std::recursive_mutex>(X::mutexes()[id]);
-        if (!X::slots()[id].b) { g_status = qh::set_error(QH_ERR_INVALID, "%s id %d has not been created", X::tag, id); return; }
-        a = &X::slots()[id];
-    }
-};
-
-template <typename X> int ext_staging(Ext<typename X::Bank> &a)
-{
-    if (a.buffsize <= a.cap) return QH_OK;
-    if (hipStreamSynchronize(a.stream) != hipSuccess) return qh::set_error(QH_ERR_HIP, "%s: synchronize failed", X::x_host);
-    (void)hipFree(a.d_in); (void)hipFree(a.d_out);
-    a.d_in = nullptr; a.d_out = nullptr; a.cap = 0;
-    if (hipMalloc((void **)&a.d_in, (size_t)a.buffsize * 16) != hipSuccess || hipMalloc((void **)&a.d_out, (size_t)a.buffsize * 16) != hipSuccess)
-        return qh::set_error(QH_ERR_HIP, "%s: staging allocation failed", X::x_host);
-    a.cap = a.buffsize;
-    return QH_OK;
-}
-
-// x*EXT: one buffer of host samples through the bank; returns when `out` holds the result
-template <typename X> void ext_x_host(int id, double *in, double *out)
-{
-    LockedExt<X> L(id);
-    if (!L.a) return;
-    Ext<typename X::Bank> &a = *L.a;
-    if (!in || !out) { g_status = qh::set_error(QH_ERR_INVALID, "%s: null buffer", X::x_host); return; }
-    if (int rc = ext_staging<X>(a)) { g_status = rc; return; }
-    const size_t bytes = (size_t)a.buffsize * 16;
-    if (hipMemcpyAsync(a.d_in, in, bytes, hipMemcpyHostToDevice, a.stream) != hipSuccess) { g_status = qh::set_error(QH_ERR_HIP, "%s: upload failed", X::x_host); return; }
-    if (int rc = X::process(a.b, a.d_in, a.buffsize, a.d_out, a.buffsize, a.buffsize)) { g_status = rc; return; }
-    if (hipMemcpyAsync(out, a.d_out, bytes, hipMemcpyDeviceToHost, a.stream) != hipSuccess || hipStreamSynchronize(a.stream) != hipSuccess)
-        g_status = qh::set_error(QH_ERR_HIP, "%s: download failed", X::x_host);
-}
-
-// qh_wdsp_x*EXT_device: the same on device buffers, in order with the caller's stream
-template <typename X> int ext_x_device(int id, const void *d_in, void *d_out, void *stream)
-{
-    LockedExt<X> L(id);
-    if (!L.a) return g_status;
-    Ext<typename X::Bank> &a = *L.a;
-    if (!d_in || !d_out) return g_status = qh::set_error(QH_ERR_INVALID, "%s: null buffer", X::x_device);
-    if (int rc = ext_staging<X>(a)) return g_status = rc;
-    hipStream_t cs = (hipStream_t)stream;
-    if (!a.ev_in && (hipEventCreateWithFlags(&a.ev_in, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&a.ev_out, hipEventDisableTiming) != hipSuccess))
-        return g_status = qh::set_error(QH_ERR_HIP, "%s: event creation failed", X::x_device);
-    const size_t bytes = (size_t)a.buffsize * 16;
-    if (cs != a.stream) { (void)hipEventRecord(a.ev_in, cs); (void)hipStreamWaitEvent(a.stream, a.ev_in, 0); }
-    int rc = QH_OK;
-    if (hipMemcpyAsync(a.d_in, d_in, bytes, hipMemcpyDeviceToDevice, a.stream) != hipSuccess) rc = qh::set_error(QH_ERR_HIP, "%s: copy failed", X::x_device);
-    if (!rc) rc = X::process(a.b, a.d_in, a.buffsize, a.d_out, a.buffsize, a.buffsize);
-    if (!rc && hipMemcpyAsync(d_out, a.d_out, bytes, hipMemcpyDeviceToDevice, a.stream) != hipSuccess) rc = qh::set_error(QH_ERR_HIP, "%s: copy failed", X::x_device);
-    if (cs != a.stream) { (void)hipEventRecord(a.ev_out, a.stream); (void)hipStreamWaitEvent(cs, a.ev_out, 0); }
-    return g_status = rc;
-}
-
-template <typename X> void ext_set_buffsize(int id, int size, const char *name)
-{
-    LockedExt<X> L(id);
-    if (!L.a) return;
-    if (size <= 0) { g_status = qh::set_error(QH_ERR_INVALID, "%s: bad buffer size", name); return; }
-    L.a->buffsize = size;
-}
-
-#define EXT_SETTER(X, call)                 \
-    do {                                    \
-        LockedExt<X> L(id);                 \
-        if (L.a) g_status = (call);         \
-    } while (0)
-}  // namespace
-
-extern "C" {
-
-void create_anbEXT(int id, int run, int buffsize, double samplerate, double tau, double hangtime, double advtime, double backtau, double threshold)
-{
-    g_status = QH_OK;
-    if (id < 0 || id >= kMaxExtAnbs) { g_status = qh::set_error(QH_ERR_INVALID, "ANB id %d out of range", id); return; }
-    std::unique_lock<std::recursive_mutex> lk(g_anb_mtx[id]);
-    Ext<qh_anb> &a = g_anb[id];
-    if (a.b) { g_status = qh::set_error(QH_ERR_INVALID, "ANB id %d already exists", id); return; }
-    if (buffsize <= 0) { g_status = qh::set_error(QH_ERR_INVALID, "create_anbEXT: bad buffer size"); return; }
-    if (int rc = qh::anb_check_settings(samplerate, tau, hangtime, advtime, backtau, threshold)) { g_status = rc; return; }
-    if (hipStreamCreateWithFlags(&a.stream, hipStreamNonBlocking) != hipSuccess) {
-        a.stream = nullptr;
-        g_status = qh::set_error(QH_ERR_NO_DEVICE, "create_anbEXT: no HIP device (libquiskhip has no CPU fallback)");
-        return;
-    }
-    a.b = qh_anb_create(0, 1, samplerate, tau, hangtime, advtime, backtau, threshold, a.stream);
-    if (!a.b) { g_status = QH_ERR_HIP; ext_release<AnbExt>(a); return; }   // the settings were good: the device (message already set)
-    a.buffsize = buffsize;
-    int rc = qh_anb_set_run(a.b, 0, run);
-    if (!rc) rc = ext_staging<AnbExt>(a);
-    if (rc) { g_status = rc; ext_release<AnbExt>(a); }
-}
-
-void destroy_anbEXT(int id) { LockedExt<AnbExt> L(id); if (L.a) ext_release<AnbExt>(*L.a); }
-void flush_anbEXT(int id) { EXT_SETTER(AnbExt, qh_anb_flush(L.a->b, 0)); }
-void xanbEXT(int id, double *in, double *out) { ext_x_host<AnbExt>(id, in, out); }
-int qh_wdsp_xanbEXT_device(int id, const void *d_in, void *d_out, void *stream) { return ext_x_device<AnbExt>(id, d_in, d_out, stream); }
-
-void SetEXTANBRun(int id, int run) { EXT_SETTER(AnbExt, qh_anb_set_run(L.a->b, 0, run)); }
-void SetEXTANBBuffsize(int id, int size) { ext_set_buffsize<AnbExt>(id, size, "SetEXTANBBuffsize"); }
-void SetEXTANBSamplerate(int id, int rate) { EXT_SETTER(AnbExt, qh_anb_set_samplerate(L.a->b, 0, (double)rate)); }
-void SetEXTANBTau(int id, double tau) { EXT_SETTER(AnbExt, qh_anb_set_tau(L.a->b, 0, tau)); }
-void SetEXTANBHangtime(int id, double time) { EXT_SETTER(AnbExt, qh_anb_set_hangtime(L.a->b, 0, time)); }
-void SetEXTANBAdvtime(int id, double time) { EXT_SETTER(AnbExt, qh_anb_set_advtime(L.a->b, 0, time)); }
-void SetEXTANBBacktau(int id, double tau) { EXT_SETTER(AnbExt, qh_anb_set_backtau(L.a->b, 0, tau)); }
-void SetEXTANBThreshold(int id, double thresh) { EXT_SETTER(AnbExt, qh_anb_set_threshold(L.a->b, 0, thresh)); }
-
-void create_nobEXT(int id, int run, int mode, int buffsize, double samplerate, double slewtime, double hangtime, double advtime, double backtau,
-                   double threshold)
-{
-    g_status = QH_OK;
-    if (id < 0 || id >= kMaxExtNobs) { g_status = qh::set_error(QH_ERR_INVALID, "NOB id %d out of range", id); return; }
-    std::unique_lock<std::recursive_mutex> lk(g_nob_mtx[id]);
-    Ext<qh_nob> &a = g_nob[id];
-    if (a.b) { g_status = qh::set_error(QH_ERR_INVALID, "NOB id %d already exists", id); return; }
-    if (buffsize <= 0) { g_status = qh::set_error(QH_ERR_INVALID, "create_nobEXT: bad buffer size"); return; }
-    if (int rc = qh::nob_check_settings(samplerate, mode, slewtime, hangtime, advtime, backtau, threshold)) { g_status = rc; return; }
-    if (hipStreamCreateWithFlags(&a.stream, hipStreamNonBlocking) != hipSuccess) {
-        a.stream = nullptr;
-        g_status = qh::set_error(QH_ERR_NO_DEVICE, "create_nobEXT: no HIP device (libquiskhip has no CPU fallback)");
-        return;
-    }
-    a.b = qh_nob_create(0, 1, samplerate, mode, slewtime, hangtime, advtime, backtau, threshold, a.stream);
-    if (!a.b) { g_status = QH_ERR_HIP; ext_release<NobExt>(a); return; }   // the settings were good: the device (message already set)
-    a.buffsize = buffsize;
-    int rc = qh_nob_set_run(a.b, 0, run);
-    if (!rc) rc = ext_staging<NobExt>(a);
-    if (rc) { g_status = rc; ext_release<NobExt>(a); }
-}
-
-void destroy_nobEXT(int id) { LockedExt<NobExt> L(id); if (L.a) ext_release<NobExt>(*L.a); }
-void flush_nobEXT(int id) { EXT_SETTER(NobExt, qh_nob_flush(L.a->b, 0)); }
-void xnobEXT(int id, double *in, double *out) { ext_x_host<NobExt>(id, in, out); }
-int qh_wdsp_xnobEXT_device(int id, const void *d_in, void *d_out, void *stream) { return ext_x_device<NobExt>(id, d_in, d_out, stream); }
-
-void SetEXTNOBRun(int id, int run) { EXT_SETTER(NobExt, qh_nob_set_run(L.a->b, 0, run)); }
-void SetEXTNOBMode(int id, int mode) { EXT_SETTER(NobExt, qh_nob_set_mode(L.a->b, 0, mode)); }
-void SetEXTNOBBuffsize(int id, int size) { ext_set_buffsize<NobExt>(id, size, "SetEXTNOBBuffsize"); }
-void SetEXTNOBSamplerate(int id, int rate) { EXT_SETTER(NobExt, qh_nob_set_samplerate(L.a->b, 0, (double)rate)); }
-void SetEXTNOBTau(int id, double tau) { EXT_SETTER(NobExt, qh_nob_set_tau(L.a->b, 0, tau)); }
-void SetEXTNOBHangtime(int id, double time) { EXT_SETTER(NobExt, qh_nob_set_hangtime(L.a->b, 0, time)); }
-void SetEXTNOBAdvtime(int id, double time) { EXT_SETTER(NobExt, qh_nob_set_advtime(L.a->b, 0, time)); }
-void SetEXTNOBBacktau(int id, double tau) { EXT_SETTER(NobExt, qh_nob_set_backtau(L.a->b, 0, tau)); }
-void SetEXTNOBThreshold(int id, double thresh) { EXT_SETTER(NobExt, qh_nob_set_threshold(L.a->b, 0, thresh)); }
-
-}  // extern "C"
-
-// ---- the diversity combiner between the blankers and fexchange0: create_divEXT ... SetEXTDIVRotate (wdsp/div.c:104-187) -------------------
-// pdiv[id], div.c:104-105: each id a one-group bank on a stream of its own.  The caller's receivers are pointers of their own, the
-// bank's are rows a stride apart: the rows a call reads are gathered into d_in [8][cap] first, and the receivers whose pointer is `out`
-// go to the bank as a mask (qh::div_process_staged), so out == in[k] needs no copy to undo.
-namespace {
-constexpr int kMaxExtDivs = 32;     // (MAX_EXT_DIVS is 2, div.c:104; 32 as the other EXT families here)
-constexpr int kDivRows = 8;         // MAX_NR, div.c:29
-Ext<qh_div> g_div[kMaxExtDivs];
-std::recursive_mutex g_div_mtx[kMaxExtDivs];
-
-struct DivExt {
-    typedef qh_div Bank;
-    static constexpr int count = kMaxExtDivs;
-    static Ext<qh_div> *slots() { return g_div; }
-    static std::recursive_mutex *mutexes() { return g_div_mtx; }
-    static constexpr auto destroy = qh_div_destroy;
-    static constexpr const char *tag = "DIV", *x_host = "xdivEXT", *x_device = "qh_wdsp_xdivEXT_device";
-};
-
-int div_staging(Ext<qh_div> &a, int n, const char *name)
-{
-    if (n <= a.cap) return QH_OK;
-    if (hipStreamSynchronize(a.stream) != hipSuccess) return qh::set_error(QH_ERR_HIP, "%s: synchronize failed", name);
-    (void)hipFree(a.d_in); (void)hipFree(a.d_out);
-    a.d_in = nullptr; a.d_out = nullptr; a.cap = 0;
-    if (hipMalloc((void **)&a.d_in, (size_t)kDivRows * (size_t)n * 16) != hipSuccess || hipMalloc((void **)&a.d_out, (size_t)n * 16) != hipSuccess)
-        return qh::set_error(QH_ERR_HIP, "%s: staging allocation failed", name);
-    a.cap = n;
-    return QH_OK;
-}
-
-// What a call of nsamples on pointers in[0 .. nr-1] / out reads and where out lies over it (host or device addresses alike): the first
-// row read and their count, the receivers whose pointer is out, and whether nothing is to be done (a copy of in[output] onto itself)
-struct DivCall {
-    int first = 0, count = 0;
-    unsigned alias = 0;
-    bool nothing = false;
-};
-
-int div_call(Ext<qh_div> &a, int nsamples, const void *const *in, const void *out, const char *name, DivCall *c)
-{
-    int run = 0, nr = 0, output = 0;
-    if (int rc = qh_div_get(a.b, 0, &run, &nr, &output, nullptr, nullptr)) return rc;
-    if (nsamples < 0 || !in || !out) return qh::set_error(QH_ERR_INVALID, "%s: bad arguments", name);
-    if (run && output > nr) return qh::set_error(QH_ERR_INVALID, "%s: output %d is above nr %d (the reference reads a receiver nobody handed it)", name, output, nr);
-    const bool mix = run && output == nr;
-    c->first = !run || mix ? 0 : output;
-    c->count = mix ? nr : 1;
-    const long long o = (long long)reinterpret_cast<uintptr_t>(out), len = (long long)nsamples * 16;
-    for (int i = c->first; i < c->first + c->count; i++) {
-        if (!in[i]) return qh::set_error(QH_ERR_INVALID, "%s: in[%d] is null", name, i);
-        const long long p = (long long)reinterpret_cast<uintptr_t>(in[i]);
-        if (p == o) c->alias |= 1u << i;
-        else if (p < o + len && o < p + len) return qh::set_error(QH_ERR_INVALID, "%s: out overlaps in[%d] without being it", name, i);
-    }
-    c->nothing = nsamples == 0 || (!mix && c->alias);
-    return QH_OK;
-}
-}  // namespace
-
-extern "C" {
-
-void create_divEXT(int id, int run, int nr, int size)
-{
-    g_status = QH_OK;
-    if (id < 0 || id >= kMaxExtDivs) { g_status = qh::set_error(QH_ERR_INVALID, "DIV id %d out of range", id); return; }
-    std::unique_lock<std::recursive_mutex> lk(g_div_mtx[id]);
-    Ext<qh_div> &a = g_div[id];
-    if (a.b) { g_status = qh::set_error(QH_ERR_INVALID, "DIV id %d already exists", id); return; }
-    if (size < 0 || nr < 1 || nr > kDivRows) { g_status = qh::set_error(QH_ERR_INVALID, "create_divEXT: nr must lie in 1..8 and the size must not be negative"); return; }
-    if (hipStreamCreateWithFlags(&a.stream, hipStreamNonBlocking) != hipSuccess) {
-        a.stream = nullptr;
-        g_status = qh::set_error(QH_ERR_NO_DEVICE, "create_divEXT: no HIP device (libquiskhip has no CPU fallback)");
-        return;
-    }
-    a.b = qh_div_create(0, 1, run, nr, a.stream);
-    if (!a.b) { g_status = QH_ERR_HIP; ext_release<DivExt>(a); return; }   // the settings were good: the device (message already set)
-    a.buffsize = size;
-    if (int rc = div_staging(a, size, "create_divEXT")) { g_status = rc; ext_release<DivExt>(a); }
-}
-
-void destroy_divEXT(int id) { LockedExt<DivExt> L(id); if (L.a) ext_release<DivExt>(*L.a); }
-void flush_divEXT(int id) { LockedExt<DivExt> L(id); }                    // flush_div is empty, div.c:62-65
-
-void xdivEXT(int id, int nsamples, double **in, double *out)
-{
-    LockedExt<DivExt> L(id);
-    if (!L.a) return;
-    Ext<qh_div> &a = *L.a;
-    DivCall c;
-    if (int rc = div_call(a, nsamples, (const void *const *)in, out, DivExt::x_host, &c)) { g_status = rc; return; }
-    if (c.nothing) return;
-    if (int rc = div_staging(a, nsamples, DivExt::x_host)) { g_status = rc; return; }
-    const size_t bytes = (size_t)nsamples * 16;
-    for (int i = c.first; i < c.first + c.count; i++)
-        if (!((c.alias >> i) & 1u) &&                                       // (the samples of a receiver that is `out` are never read)
-            hipMemcpyAsync(a.d_in + (size_t)i * (size_t)a.cap * 2, in[i], bytes, hipMemcpyHostToDevice, a.stream) != hipSuccess) {
-            (void)hipStreamSynchronize(a.stream);
-            g_status = qh::set_error(QH_ERR_HIP, "%s: upload failed", DivExt::x_host);
-            return;
-        }
-    int rc = qh::div_process_staged(a.b, a.d_in, a.cap, (long long)kDivRows * a.cap, a.d_out, a.cap, nsamples, c.alias);
-    if (!rc && hipMemcpyAsync(out, a.d_out, bytes, hipMemcpyDeviceToHost, a.stream) != hipSuccess) rc = qh::set_error(QH_ERR_HIP, "%s: download failed", DivExt::x_host);
-    if (hipStreamSynchronize(a.stream) != hipSuccess && !rc) rc = qh::set_error(QH_ERR_HIP, "%s: download failed", DivExt::x_host);
-    g_status = rc;
-}
-
-int qh_wdsp_xdivEXT_device(int id, int nsamples, const void *const *d_in, void *d_out, void *stream)
-{
-    LockedExt<DivExt> L(id);
-    if (!L.a) return g_status;
-    Ext<qh_div> &a = *L.a;
-    DivCall c;
-    if (int rc = div_call(a, nsamples, d_in, d_out, DivExt::x_device, &c)) return g_status = rc;
-    if (c.nothing) return QH_OK;
-    if (int rc = div_staging(a, nsamples, DivExt::x_device)) return g_status = rc;
-    hipStream_t cs = (hipStream_t)stream;
-    if (!a.ev_in && (hipEventCreateWithFlags(&a.ev_in, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&a.ev_out, hipEventDisableTiming) != hipSuccess))
-        return g_status = qh::set_error(QH_ERR_HIP, "%s: event creation failed", DivExt::x_device);
-    const size_t bytes = (size_t)nsamples * 16;
-    if (cs != a.stream) { (void)hipEventRecord(a.ev_in, cs); (void)hipStreamWaitEvent(a.stream, a.ev_in, 0); }
-    int rc = QH_OK;
-    for (int i = c.first; i < c.first + c.count && !rc; i++)
-        if (!((c.alias >> i) & 1u) && hipMemcpyAsync(a.d_in + (size_t)i * (size_t)a.cap * 2, d_in[i], bytes, hipMemcpyDeviceToDevice, a.stream) != hipSuccess)
-            rc = qh::set_error(QH_ERR_HIP, "%s: copy failed", DivExt::x_device);
-    if (!rc) rc = qh::div_process_staged(a.b, a.d_in, a.cap, (long long)kDivRows * a.cap, d_out, nsamples, nsamples, c.alias);
-    if (cs != a.stream) { (void)hipEventRecord(a.ev_out, a.stream); (void)hipStreamWaitEvent(cs, a.ev_out, 0); }
-    return g_status = rc;
-}
-
-void SetEXTDIVRun(int id, int run) { EXT_SETTER(DivExt, qh_div_set_run(L.a->b, 0, run)); }
-void SetEXTDIVBuffsize(int id, int size)
-{
-    LockedExt<DivExt> L(id);
-    if (!L.a) return;
-    if (size < 0) { g_status = qh::set_error(QH_ERR_INVALID, "SetEXTDIVBuffsize: bad buffer size"); return; }
-    L.a->buffsize = size;
-}
-void SetEXTDIVNr(int id, int nr) { EXT_SETTER(DivExt, qh_div_set_nr(L.a->b, 0, nr)); }
-void SetEXTDIVOutput(int id, int output) { EXT_SETTER(DivExt, qh_div_set_output(L.a->b, 0, output)); }
-void SetEXTDIVRotate(int id, int nr, double *Irotate, double *Qrotate) { EXT_SETTER(DivExt, qh_div_set_rotate(L.a->b, 0, nr, Irotate, Qrotate)); }
-
-}  // extern "C"
-
-// ---- the variable-ratio resampler behind fexchange0: create_varsampV, xvarsampV, destroy_varsampV (wdsp/varsamp.c:228-250) ---------------
-// Every pointer a one-channel bank on a stream of its own, with an input staging row that lets input == output, an output staging row
-// for the host form and the count in device memory.  The reference hands out its VARSAMP; here the pointer is looked up in a table, so
-// one that create_varsampV did not return is refused instead of followed.
-namespace {
-struct VarsampV {
-    qh_varsamp *b = nullptr;
-    hipStream_t stream = nullptr;
-    double *d_in = nullptr, *d_out = nullptr;
-    long long cap_in = 0, cap_out = 0;
-    int *d_count = nullptr;
-    hipEvent_t ev_in = nullptr, ev_out = nullptr;
-    std::mutex mtx;
-};
-std::mutex g_vsv_mtx;
-std::vector<VarsampV *> g_vsv;
-
-void vsv_release(VarsampV *a)
-{
-    if (a->b) qh_varsamp_destroy(a->b);         // (waits for the stream)
-    (void)hipFree(a->d_in); (void)hipFree(a->d_out); (void)hipFree(a->d_count);
-    if (a->ev_in) (void)hipEventDestroy(a->ev_in);
-    if (a->ev_out) (void)hipEventDestroy(a->ev_out);
-    if (a->stream) (void)hipStreamDestroy(a->stream);
-    delete a;
-}
-
-VarsampV *vsv_find(void *ptr, const char *name)
-{
-    g_status = QH_OK;
-    std::lock_guard<std::mutex> lk(g_vsv_mtx);
-    for (VarsampV *a : g_vsv)
-        if (a == ptr) return a;
-    g_status = qh::set_error(QH_ERR_INVALID, "%s: not a pointer create_varsampV returned", name);
-    return nullptr;
-}
-
-int vsv_row(VarsampV &a, double **row, long long *cap, long long want, const char *name)
-{
-    if (want <= *cap) return QH_OK;
-    if (hipStreamSynchronize(a.stream) != hipSuccess) return qh::set_error(QH_ERR_HIP, "%s: synchronize failed", name);
-    (void)hipFree(*row);
-    *row = nullptr; *cap = 0;
-    want += want / 8 + 64;
-    if (hipMalloc((void **)row, (size_t)want * 16) != hipSuccess) { *row = nullptr; return qh::set_error(QH_ERR_HIP, "%s: staging allocation failed", name); }
-    *cap = want;
-    return QH_OK;
-}
-}  // namespace
-
-extern "C" {
-
-void *create_varsampV(int in_rate, int out_rate, int R)
-{
-    g_status = QH_OK;
-    if (int rc = qh::varsamp_check_settings(in_rate, out_rate, R, 0.0, -1.0, 1.0)) { g_status = rc; return nullptr; }
-    VarsampV *a = new VarsampV();
-    if (hipStreamCreateWithFlags(&a->stream, hipStreamNonBlocking) != hipSuccess) {
-        a->stream = nullptr;
-        g_status = qh::set_error(QH_ERR_NO_DEVICE, "create_varsampV: no HIP device (libquiskhip has no CPU fallback)");
-        vsv_release(a);
-        return nullptr;
-    }
-    a->b = qh_varsamp_create(0, 1, in_rate, out_rate, R, 0.0, -1.0, 1.0, 1.0, 1, a->stream);       // varsamp.c:233
-    if (!a->b) { g_status = QH_ERR_HIP; vsv_release(a); return nullptr; }     // the settings were good: the device (message already set)
-    if (hipMalloc((void **)&a->d_count, sizeof(int)) != hipSuccess) {
-        a->d_count = nullptr;
-        g_status = qh::set_error(QH_ERR_HIP, "create_varsampV: allocation failed");
-        vsv_release(a);
-        return nullptr;
-    }
-    std::lock_guard<std::mutex> lk(g_vsv_mtx);
-    g_vsv.push_back(a);
-    return a;
-}
-
-void destroy_varsampV(void *ptr)
-{
-    VarsampV *a = vsv_find(ptr, "destroy_varsampV");
-    if (!a) return;
-    {
-        std::lock_guard<std::mutex> lk(g_vsv_mtx);
-        g_vsv.erase(std::find(g_vsv.begin(), g_vsv.end(), a));
-    }
-    { std::lock_guard<std::mutex> lk(a->mtx); }
-    vsv_release(a);
-}
-
-long long qh_wdsp_varsampV_max_out(void *ptr, int numsamps, double var)
-{
-    VarsampV *a = vsv_find(ptr, "qh_wdsp_varsampV_max_out");
-    if (!a) return g_status;
-    const long long mo = qh_varsamp_max_out(a->b, numsamps, &var);
-    if (mo < 0) g_status = (int)mo;
-    return mo;
-}
-
-void xvarsampV(double *input, double *output, int numsamps, double var, int *outsamps, void *ptr)
-{
-    if (outsamps) *outsamps = 0;
-    VarsampV *a = vsv_find(ptr, "xvarsampV");
-    if (!a) return;
-    std::lock_guard<std::mutex> lk(a->mtx);
-    if (!outsamps || numsamps < 0 || (numsamps > 0 && (!input || !output))) { g_status = qh::set_error(QH_ERR_INVALID, "xvarsampV: bad arguments"); return; }
-    const long long mo = qh_varsamp_max_out(a->b, numsamps, &var);
-    if (mo < 0) { g_status = (int)mo; return; }
-    if (int rc = vsv_row(*a, &a->d_in, &a->cap_in, numsamps, "xvarsampV")) { g_status = rc; return; }
-    if (int rc = vsv_row(*a, &a->d_out, &a->cap_out, mo, "xvarsampV")) { g_status = rc; return; }
-    if (numsamps > 0 && hipMemcpyAsync(a->d_in, input, (size_t)numsamps * 16, hipMemcpyHostToDevice, a->stream) != hipSuccess) {
-        g_status = qh::set_error(QH_ERR_HIP, "xvarsampV: upload failed");
-        return;
-    }
-    if (int rc = qh_varsamp_process(a->b, a->d_in, std::max(numsamps, 1), a->d_out, std::max<long long>(mo, 1), numsamps, &var, a->d_count)) { g_status = rc; return; }
-    int count = 0;
-    if (hipMemcpyAsync(&count, a->d_count, sizeof(int), hipMemcpyDeviceToHost, a->stream) != hipSuccess || hipStreamSynchronize(a->stream) != hipSuccess) {
-        g_status = qh::set_error(QH_ERR_HIP, "xvarsampV: download failed");
-        return;
-    }
-    if (count > 0 && (hipMemcpyAsync(output, a->d_out, (size_t)count * 16, hipMemcpyDeviceToHost, a->stream) != hipSuccess ||
-                      hipStreamSynchronize(a->stream) != hipSuccess)) {
-        g_status = qh::set_error(QH_ERR_HIP, "xvarsampV: download failed");
-        return;
-    }
-    *outsamps = count;
-}
-
-int qh_wdsp_xvarsampV_device(void *ptr, const void *d_in, void *d_out, int numsamps, double var, int *d_count, void *stream)
-{
-    VarsampV *a = vsv_find(ptr, "qh_wdsp_xvarsampV_device");
-    if (!a) return g_status;
-    std::lock_guard<std::mutex> lk(a->mtx);
-    if (numsamps < 0 || !d_count || (numsamps > 0 && (!d_in || !d_out))) return g_status = qh::set_error(QH_ERR_INVALID, "qh_wdsp_xvarsampV_device: bad arguments");
-    const long long mo = qh_varsamp_max_out(a->b, numsamps, &var);
-    if (mo < 0) return g_status = (int)mo;
-    if (int rc = vsv_row(*a, &a->d_in, &a->cap_in, numsamps, "qh_wdsp_xvarsampV_device")) return g_status = rc;
-    hipStream_t cs = (hipStream_t)stream;
-    if (!a->ev_in && (hipEventCreateWithFlags(&a->ev_in, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&a->ev_out, hipEventDisableTiming) != hipSuccess))
-        return g_status = qh::set_error(QH_ERR_HIP, "qh_wdsp_xvarsampV_device: event creation failed");
-    if (cs != a->stream) { (void)hipEventRecord(a->ev_in, cs); (void)hipStreamWaitEvent(a->stream, a->ev_in, 0); }
-    int rc = QH_OK;
-    if (numsamps > 0 && hipMemcpyAsync(a->d_in, d_in, (size_t)numsamps * 16, hipMemcpyDeviceToDevice, a->stream) != hipSuccess)
-        rc = qh::set_error(QH_ERR_HIP, "qh_wdsp_xvarsampV_device: copy failed");
-    if (!rc) rc = qh_varsamp_process(a->b, a->d_in, std::max(numsamps, 1), d_out, std::max<long long>(mo, 1), numsamps, &var, d_count);
-    if (cs != a->stream) { (void)hipEventRecord(a->ev_out, a->stream); (void)hipStreamWaitEvent(cs, a->ev_out, 0); }
-    return g_status = rc;
-}
-
-}  // extern "C"
-
-// ---- the fixed-ratio resampler beside fexchange0: create_resampleV, xresampleV, destroy_resampleV and the FV names (wdsp/resample.c:206-228,
-// 332-354) ----------------------------------------------------------------------------------------------------------------------------------
-// As the varsamp names above: every pointer a one-channel bank on a stream of its own with staging rows, looked up in a table.  One
-// table holds both kinds, so a V pointer handed to an FV name is refused as well.
-namespace {
-struct ResampleV {
-    qh_resample *b = nullptr;
-    bool fv = false;
-    hipStream_t stream = nullptr;
-    void *d_in = nullptr, *d_out = nullptr;
-    long long cap_in = 0, cap_out = 0;          // samples
-    hipEvent_t ev_in = nullptr, ev_out = nullptr;
-    std::mutex mtx;
-    size_t es() const { return fv ? sizeof(float) : 2 * sizeof(double); }
-};
-std::mutex g_rsv_mtx;
-std::vector<ResampleV *> g_rsv;
-
-void rsv_release(ResampleV *a)
-{
-    if (a->b) qh_resample_destroy(a->b);        // (waits for the stream)
-    (void)hipFree(a->d_in); (void)hipFree(a->d_out);
-    if (a->ev_in) (void)hipEventDestroy(a->ev_in);
-    if (a->ev_out) (void)hipEventDestroy(a->ev_out);
-    if (a->stream) (void)hipStreamDestroy(a->stream);
-    delete a;
-}
-
-// fv < 0: either kind
-ResampleV *rsv_find(void *ptr, int fv, const char *name)
-{
-    g_status = QH_OK;
-    std::lock_guard<std::mutex> lk(g_rsv_mtx);
-    for (ResampleV *a : g_rsv)
-        if (a == ptr && (fv < 0 || a->fv == (fv != 0))) return a;
-    g_status = qh::set_error(QH_ERR_INVALID, "%s: not a pointer create_resample%s returned", name, fv > 0 ? "FV" : "V");
-    return nullptr;
-}
-
-int rsv_row(ResampleV &a, void **row, long long *cap, long long want, const char *name)
-{
-    if (want <= *cap) return QH_OK;
-    if (hipStreamSynchronize(a.stream) != hipSuccess) return qh::set_error(QH_ERR_HIP, "%s: synchronize failed", name);
-    (void)hipFree(*row);
-    *row = nullptr; *cap = 0;
-    want += want / 8 + 64;
-    if (hipMalloc(row, (size_t)want * a.es()) != hipSuccess) { *row = nullptr; return qh::set_error(QH_ERR_HIP, "%s: staging allocation failed", name); }
-    *cap = want;
-    return QH_OK;
-}
-
-void *rsv_create(int in_rate, int out_rate, bool fv, const char *name)
-{
-    g_status = QH_OK;
-    const int dtype = fv ? QH_RESAMPLE_R32 : QH_RESAMPLE_C64;
-    if (int rc = qh::resample_check_settings(in_rate, out_rate, 0.0, 0, 1.0, dtype)) { g_status = rc; return nullptr; }
-    ResampleV *a = new ResampleV();
-    a->fv = fv;
-    if (hipStreamCreateWithFlags(&a->stream, hipStreamNonBlocking) != hipSuccess) {
-        a->stream = nullptr;
-        g_status = qh::set_error(QH_ERR_NO_DEVICE, "%s: no HIP device (libquiskhip has no CPU fallback)", name);
-        rsv_release(a);
-        return nullptr;
-    }
-    a->b = qh_resample_create(0, 1, in_rate, out_rate, 0.0, 0, 1.0, dtype, a->stream);         // resample.c:211, 337
-    if (!a->b) { g_status = QH_ERR_HIP; rsv_release(a); return nullptr; }     // the settings were good: the device (message already set)
-    std::lock_guard<std::mutex> lk(g_rsv_mtx);
-    g_rsv.push_back(a);
-    return a;
-}
-
-void rsv_destroy(void *ptr, bool fv, const char *name)
-{
-    ResampleV *a = rsv_find(ptr, fv, name);
-    if (!a) return;
-    {
-        std::lock_guard<std::mutex> lk(g_rsv_mtx);
-        g_rsv.erase(std::find(g_rsv.begin(), g_rsv.end(), a));
-    }
-    { std::lock_guard<std::mutex> lk(a->mtx); }
-    rsv_release(a);
-}
-
-// resample.c:130-152 with out == in: output m is written behind the input it is made at only while m <= p / L, which holds for every m
-// where L <= M; where L > M the reference overwrites inputs it has yet to read
-bool rsv_in_place_ok(ResampleV &a) { return qh_resample_L(a.b, 0) <= qh_resample_M(a.b, 0); }
-
-void rsv_x(const void *input, void *output, int numsamps, int *outsamps, void *ptr, bool fv, const char *name)
-{
-    if (outsamps) *outsamps = 0;
-    ResampleV *a = rsv_find(ptr, fv, name);
-    if (!a) return;
-    std::lock_guard<std::mutex> lk(a->mtx);
-    if (!outsamps || numsamps < 0 || (numsamps > 0 && (!input || !output))) { g_status = qh::set_error(QH_ERR_INVALID, "%s: bad arguments", name); return; }
-    if (numsamps > 0 && input == output && !rsv_in_place_ok(*a)) {
-        g_status = qh::set_error(QH_ERR_INVALID, "%s: input == output needs L <= M (the reference overwrites samples it has yet to read)", name);
-        return;
-    }
-    const long long mo = qh_resample_max_out(a->b, numsamps);
-    if (mo < 0) { g_status = (int)mo; return; }
-    if (int rc = rsv_row(*a, &a->d_in, &a->cap_in, numsamps, name)) { g_status = rc; return; }
-    if (int rc = rsv_row(*a, &a->d_out, &a->cap_out, mo, name)) { g_status = rc; return; }
-    const size_t es = a->es();
-    if (numsamps > 0 && hipMemcpyAsync(a->d_in, input, (size_t)numsamps * es, hipMemcpyHostToDevice, a->stream) != hipSuccess) {
-        g_status = qh::set_error(QH_ERR_HIP, "%s: upload failed", name);
-        return;
-    }
-    int count = 0;
-    if (int rc = qh_resample_process(a->b, a->d_in, std::max(numsamps, 1), a->d_out, std::max<long long>(mo, 1), numsamps, &count)) { g_status = rc; return; }
-    if ((count > 0 && hipMemcpyAsync(output, a->d_out, (size_t)count * es, hipMemcpyDeviceToHost, a->stream) != hipSuccess) ||
-        hipStreamSynchronize(a->stream) != hipSuccess) {
-        g_status = qh::set_error(QH_ERR_HIP, "%s: download failed", name);
-        return;
-    }
-    *outsamps = count;
-}
-
-int rsv_x_device(void *ptr, const void *d_in, void *d_out, int numsamps, int *outsamps, void *stream, bool fv, const char *name)
-{
-    if (outsamps) *outsamps = 0;
-    ResampleV *a = rsv_find(ptr, fv, name);
-    if (!a) return g_status;
-    std::lock_guard<std::mutex> lk(a->mtx);
-    if (numsamps < 0 || !outsamps || (numsamps > 0 && (!d_in || !d_out))) return g_status = qh::set_error(QH_ERR_INVALID, "%s: bad arguments", name);
-    if (numsamps > 0 && d_in == d_out && !rsv_in_place_ok(*a))
-        return g_status = qh::set_error(QH_ERR_INVALID, "%s: d_in == d_out needs L <= M (the reference overwrites samples it has yet to read)", name);
-    const long long mo = qh_resample_max_out(a->b, numsamps);
-    if (mo < 0) return g_status = (int)mo;
-    if (int rc = rsv_row(*a, &a->d_in, &a->cap_in, numsamps, name)) return g_status = rc;
-    hipStream_t cs = (hipStream_t)stream;
-    if (!a->ev_in && (hipEventCreateWithFlags(&a->ev_in, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&a->ev_out, hipEventDisableTiming) != hipSuccess))
-        return g_status = qh::set_error(QH_ERR_HIP, "%s: event creation failed", name);
-    if (cs != a->stream) { (void)hipEventRecord(a->ev_in, cs); (void)hipStreamWaitEvent(a->stream, a->ev_in, 0); }
-    int rc = QH_OK;
-    if (numsamps > 0 && hipMemcpyAsync(a->d_in, d_in, (size_t)numsamps * a->es(), hipMemcpyDeviceToDevice, a->stream) != hipSuccess)
-        rc = qh::set_error(QH_ERR_HIP, "%s: copy failed", name);
-    if (!rc) rc = qh_resample_process(a->b, a->d_in, std::max(numsamps, 1), d_out, std::max<long long>(mo, 1), numsamps, outsamps);
-    if (cs != a->stream) { (void)hipEventRecord(a->ev_out, a->stream); (void)hipStreamWaitEvent(cs, a->ev_out, 0); }
-    return g_status = rc;
-}
-}  // namespace
-
-extern "C" {
-
-void *create_resampleV(int in_rate, int out_rate) { return rsv_create(in_rate, out_rate, false, "create_resampleV"); }
-void *create_resampleFV(int in_rate, int out_rate) { return rsv_create(in_rate, out_rate, true, "create_resampleFV"); }
-void destroy_resampleV(void *ptr) { rsv_destroy(ptr, false, "destroy_resampleV"); }
-void destroy_resampleFV(void *ptr) { rsv_destroy(ptr, true, "destroy_resampleFV"); }
-void xresampleV(double *input, double *output, int numsamps, int *outsamps, void *ptr) { rsv_x(input, output, numsamps, outsamps, ptr, false, "xresampleV"); }
-void xresampleFV(float *input, float *output, int numsamps, int *outsamps, void *ptr) { rsv_x(input, output, numsamps, outsamps, ptr, true, "xresampleFV"); }
-
-long long qh_wdsp_resampleV_max_out(void *ptr, int numsamps)
-{
-    ResampleV *a = rsv_find(ptr, -1, "qh_wdsp_resampleV_max_out");
-    if (!a) return g_status;
-    const long long mo = qh_resample_max_out(a->b, numsamps);
-    if (mo < 0) g_status = (int)mo;
-    return mo;
-}
-
-int qh_wdsp_xresampleV_device(void *ptr, const void *d_in, void *d_out, int numsamps, int *outsamps, void *stream)
-{
-    return rsv_x_device(ptr, d_in, d_out, numsamps, outsamps, stream, false, "qh_wdsp_xresampleV_device");
-}
-int qh_wdsp_xresampleFV_device(void *ptr, const void *d_in, void *d_out, int numsamps, int *outsamps, void *stream)
-{
-    return rsv_x_device(ptr, d_in, d_out, numsamps, outsamps, stream, true, "qh_wdsp_xresampleFV_device");
-}
-
-}  // extern "C"

@@ -1,5 +1,5 @@
 """WDSP's two noise blankers side by side in one process: they share the detector's kernels (quisk_amd/csrc/qh_blank_det.hpp) and the
-banks' host scaffold (qh_bank.hpp), so what could newly go wrong is state or scratch of one bank reaching another.  A WdspNoiseBlanker
+banks' host scaffold (qh_bank.hpp: DetBank), so what could newly go wrong is state or scratch of one bank reaching another.  A WdspNoiseBlanker
 and two WdspNoiseBlanker2 (modes 0 and 4) work on one caller stream, their calls enqueued back to back cut by cut; after the third cut
 the first bank is destroyed and a fresh WdspNoiseBlanker2 takes its rows from there (a free of scratch another bank still used would
 show).  Every bank's output must be its restatement's, np.array_equal; as in test_gpu_anb.py and test_gpu_nob.py each restatement first

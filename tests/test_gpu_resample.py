@@ -367,3 +367,24 @@ def test_a_channel_does_not_see_its_neighbour(qh, oracle):
     for (wy, wc), (gy, gc) in zip(want, (g0, g1)):
         assert wc[0] == gc[0] and np.array_equal(wy[0, :wc[0]], gy[0, :gc[0]])     # channel 0's bits do not move
     assert g1[1][1] == 2 * 1700
+
+
+def test_a_refusal_for_every_channel_leaves_different_designs_alone(qh, oracle):
+    """A setter with ch = -1 that is refused, on a bank whose two channels hold different designs (48000 -> 44100 beside 48000 -> 24000):
+    QH_ERR_INVALID, and both channels' next outputs are those of a twin bank that never received the call, bit for bit.  No single value
+    is refused for one of the designs and taken by the other -- a refusal looks at the rates, ncoef and the band edges' finiteness, and a
+    ch = -1 call gives every channel the same ones -- so the designs are set apart with set_rates on channel 1 first."""
+    L = qh.load()
+    x = _input(2, 192, seed=37)
+    bank, twin = qh.WdspResampler(2, 48000, 44100), qh.WdspResampler(2, 48000, 44100)
+    for b in (bank, twin):
+        b.set_rates(48000, 24000, ch=1)
+        assert [(b.L(c), b.M(c), b.cpp(c)) for c in range(2)] == [(147, 160, 153), (1, 2, 281)]
+    refused = [lambda h: L.qh_resample_set_rates(h, -1, 48000, 0), lambda h: L.qh_resample_set_fc_low(h, -1, float("nan")),
+               lambda h: L.qh_resample_set_bandwidth(h, -1, 100.0, float("inf"))]
+    for k, call in enumerate([None] + refused[:2]):
+        if call:
+            assert call(bank._h) == -2 and refused[2](bank._h) == -2
+        (ya, ca), (yb, cb) = bank.process_host(x[:, 64 * k:64 * k + 64]), twin.process_host(x[:, 64 * k:64 * k + 64])
+        assert ca.tolist() == cb.tolist() and min(ca) > 0 and np.array_equal(ya, yb), k
+    assert [(bank.L(c), bank.M(c), bank.cpp(c)) for c in range(2)] == [(147, 160, 153), (1, 2, 281)]

@@ -269,3 +269,22 @@ def test_device_rows_nothing_behind_the_count_and_stream_order(qh, oracle):
     vs.process_ptr(d.data_ptr(), 3000, o.data_ptr(), 4, 0, var[1], c.data_ptr())
     vs.synchronize()
     assert c.tolist() == [0, 0, 0] and torch.all(torch.isnan(o.real)).item()
+
+
+def test_a_refusal_for_every_channel_leaves_different_designs_alone(qh, oracle):
+    """A setter with ch = -1 that is refused, on a bank whose two channels hold different designs (48000 -> 96000 beside 96000 -> 48000):
+    QH_ERR_INVALID, and both channels' next outputs are those of a twin bank that never received the call, bit for bit.  No single value
+    is refused for one of the designs and taken by the other -- a refusal looks at the rates, R and the band edges' finiteness, and a
+    ch = -1 call gives every channel the same ones -- so the designs are set apart with set_rates on channel 1 first (_bank)."""
+    L = qh.load()
+    designs = [(48000, 96000, 64), (96000, 48000, 64)]
+    x = _input(2, 192, seed=37)
+    var = np.array([[1.01, 0.97], [0.99, 1.02], [1.003, 0.98]])
+    bank, twin = _bank(qh, designs, 1), _bank(qh, designs, 1)
+    refused = [lambda h: L.qh_varsamp_set_rates(h, -1, 48000, 0), lambda h: L.qh_varsamp_set_bandwidth(h, -1, float("nan"), 3000.0),
+               lambda h: L.qh_varsamp_set_rates(h, -1, 48000, 48000 * 16 + 1)]
+    for k, call in enumerate([None] + refused[:2]):
+        if call:
+            assert call(bank._h) == -2 and refused[2](bank._h) == -2
+        (ya, ca), (yb, cb) = bank.process_host(x[:, 64 * k:64 * k + 64], var[k]), twin.process_host(x[:, 64 * k:64 * k + 64], var[k])
+        assert list(ca) == list(cb) and min(ca) > 0 and np.array_equal(ya, yb), k

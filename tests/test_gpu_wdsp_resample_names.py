@@ -171,3 +171,59 @@ def test_bad_pointers_and_values_are_reported_and_do_nothing(qh, oracle):
     got = C.c_int(7)
     lib.xresampleV(buf.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p), 64, C.byref(got), p)   # destroy, then use
     assert lib.qh_wdsp_status() == -2 and got.value == 0
+
+
+def test_pointers_of_three_kinds_alive_at_once(qh, oracle):
+    """A create_resampleV, a create_resampleFV and a create_varsampV pointer side by side: every x and destroy name handed a pointer
+    of another family or kind reports QH_ERR_INVALID, leaves the count 0 and the output as it was (test_bad_pointers_and_values_...
+    above holds only the V pointer under the FV names); and destroying one leaves the other two giving the bits of twins that never
+    had such a neighbour, one 64-sample call each."""
+    lib = qh.load()
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    xc, xf = _x(128, 7, "V"), _x(128, 7, "FV")
+
+    def rs(kind, p, blk):
+        return _call(lib, kind, p, blk, False, 96)
+
+    def vs(p, blk):
+        out, got = np.full(96, np.nan, dtype=np.complex128), C.c_int(-1)
+        lib.xvarsampV(vp(blk), vp(out), len(blk), C.c_double(1.01), C.byref(got), p)
+        assert lib.qh_wdsp_status() == 0, lib.qh_last_error()
+        return out[:got.value].copy()
+
+    made = [lib.create_resampleV(48000, 44100), lib.create_resampleFV(48000, 44100), lib.create_varsampV(48000, 48000, 64)]
+    twins = [lib.create_resampleV(48000, 44100), lib.create_resampleFV(48000, 44100), lib.create_varsampV(48000, 48000, 64)]
+    assert all(made) and all(twins) and len(set(made + twins)) == 6
+    v, f, s = made
+    try:
+        calls = {"xresampleV": lambda p, o, g: lib.xresampleV(vp(xc), vp(o), 64, C.byref(g), p),
+                 "xresampleFV": lambda p, o, g: lib.xresampleFV(vp(xf), vp(o), 64, C.byref(g), p),
+                 "xvarsampV": lambda p, o, g: lib.xvarsampV(vp(xc), vp(o), 64, C.c_double(1.0), C.byref(g), p)}
+        strangers = {"xresampleV": (f, s), "xresampleFV": (v, s), "xvarsampV": (v, f)}
+        for name, ptrs in strangers.items():
+            for p in ptrs:
+                out, got = np.full(96, np.nan, dtype=np.complex128), C.c_int(7)
+                calls[name](p, out, got)
+                assert lib.qh_wdsp_status() == -2 and got.value == 0 and np.all(np.isnan(out.real)), (name, made.index(p))
+                getattr(lib, "destroy_" + name[1:])(p)
+                assert lib.qh_wdsp_status() == -2, (name, made.index(p))
+        assert lib.qh_wdsp_resampleV_max_out(s, 64) == -2
+        assert lib.qh_wdsp_varsampV_max_out(v, 64, 1.0) == -2 and lib.qh_wdsp_varsampV_max_out(f, 64, 1.0) == -2
+        # the refused calls and destroys left all three alone
+        assert np.array_equal(rs("V", v, xc[:64]), rs("V", twins[0], xc[:64]))
+        assert np.array_equal(rs("FV", f, xf[:64]), rs("FV", twins[1], xf[:64]))
+        assert np.array_equal(vs(s, xc[:64]), vs(twins[2], xc[:64]))
+        lib.destroy_resampleFV(f)
+        assert lib.qh_wdsp_status() == 0
+        made[1] = None
+        assert np.array_equal(rs("V", v, xc[64:]), rs("V", twins[0], xc[64:]))
+        assert np.array_equal(vs(s, xc[64:]), vs(twins[2], xc[64:]))
+        lib.destroy_varsampV(s)
+        assert lib.qh_wdsp_status() == 0
+        made[2] = None
+        assert np.array_equal(rs("V", v, xc[:64]), rs("V", twins[0], xc[:64]))
+    finally:
+        for p, t, kind in zip(made, twins, ("resampleV", "resampleFV", "varsampV")):
+            for q in (p, t):
+                if q:
+                    getattr(lib, "destroy_" + kind)(q)
