@@ -156,7 +156,7 @@ int qh_rxa_SetRXASSQLTauUnMute(qh_rxa *e, int ch, double tau_unmute);           
  * A threshold that is not finite is refused with QH_ERR_INVALID.  nc: a power of two in [dsp_size, 4096]; a larger one is accepted by the
  * setter (RXASetNC forwards here) and refused with QH_ERR_UNSUPPORTED at the next process call while the channel runs the stage.  Refused
  * there too: FMSQ on a channel whose FM detector is off, a dsp rate at or below twice the FM loop's pole (about 15.8 kHz), and FMSQ
- * channels of one engine with different nc or mp (they share one noise filter, as the FM channels share their filters). */
+ * channels of one engine with different nc or mp (they share one noise filter). */
 int qh_rxa_SetRXAFMSQRun(qh_rxa *e, int ch, int run);                           /* wdsp/fmsq.c:235-241 */
 int qh_rxa_SetRXAFMSQThreshold(qh_rxa *e, int ch, double threshold);            /* wdsp/fmsq.c:243-250: tail = threshold, unmute = 0.9 threshold */
 int qh_rxa_SetRXAFMSQNC(qh_rxa *e, int ch, int nc);                             /* wdsp/fmsq.c:252-267 */
@@ -211,11 +211,26 @@ int qh_rxa_RXANBPSetShiftFrequency(qh_rxa *e, int ch, double shift);
 int qh_rxa_RXANBPSetNotchesRun(qh_rxa *e, int ch, int run);
 int qh_rxa_RXANBPSetWindow(qh_rxa *e, int ch, int wintype);
 int qh_rxa_RXANBPSetAutoIncrease(qh_rxa *e, int ch, int autoincr);
-int qh_rxa_RXASetMP(qh_rxa *e, int ch, int mp);                  /* wdsp/RXA.c:948-958: minimum-phase filters (mp_imp, fir.c:319); the FM channels of one engine share their filters' design: different flags among them are refused, like different nc */
+int qh_rxa_RXASetMP(qh_rxa *e, int ch, int mp);                  /* wdsp/RXA.c:948-958: minimum-phase filters (mp_imp, fir.c:319) in every fircore of the channel's chain */
 int qh_rxa_SetRXAAMDFadeLevel(qh_rxa *e, int ch, int levelfade);
 int qh_rxa_SetRXAFMDeviation(qh_rxa *e, int ch, double deviation);
 int qh_rxa_SetRXACTCSSFreq(qh_rxa *e, int ch, double freq);
 int qh_rxa_SetRXACTCSSRun(qh_rxa *e, int ch, int run);
+/* xfmd's de-emphasis and audio filters (create_fmd's pde and paud, wdsp/fmd.c:110-118), every channel its own: nc max(2048, dsp_size) and
+ * mp 0 for both, the audio band 300 .. 3000 Hz (RXA.c:196-197,209-212).  A setter acts only on a value that changed and takes effect at the
+ * next process call.  SetRXAFMAFFilter and the two MP setters keep both filters' delay lines (setImpulse_fircore / setMp_fircore); an NC
+ * setter zeroes the line of its own filter and leaves the other's (setNc_fircore, firmin.c:455-467).  RXASetNC and RXASetMP forward to the
+ * four NC / MP setters of their channel (RXA.c:943-944,956-957).  The engine keeps one mask row per distinct design among its running FM
+ * channels, so channels with equal settings share a row and, where the de-emphasis taps are real, a tile.
+ * Refused by the setter with QH_ERR_INVALID, nothing changed (the reference checks none of this): an nc that is not a power of two in
+ * [dsp_size, 65536]; a low or high that is not finite; low <= 0 (the de-emphasis design takes log10(high / low)); high <= low.
+ * Refused with QH_ERR_UNSUPPORTED at the next process call while the channel's FM detector runs, nothing run: a band with
+ * 1.1 * high >= dsp_rate / 2 (the audio filter's upper edge, fmd.c:115). */
+int qh_rxa_SetRXAFMAFFilter(qh_rxa *e, int ch, double low, double high);        /* wdsp/fmd.c:364-384 */
+int qh_rxa_SetRXAFMNCde(qh_rxa *e, int ch, int nc);                             /* wdsp/fmd.c:278-293 */
+int qh_rxa_SetRXAFMMPde(qh_rxa *e, int ch, int mp);                             /* wdsp/fmd.c:295-305 */
+int qh_rxa_SetRXAFMNCaud(qh_rxa *e, int ch, int nc);                            /* wdsp/fmd.c:307-322 */
+int qh_rxa_SetRXAFMMPaud(qh_rxa *e, int ch, int mp);                            /* wdsp/fmd.c:324-334 */
 
 /* Runs xrxa() (wdsp/RXA.c:561-598) over `nblk` consecutive DSP blocks of every channel.
  *   d_in  : device pointer, [nch][in_stride] interleaved complex double, nblk*dsp_insize samples used
@@ -234,6 +249,7 @@ int qh_rxa_process_host(qh_rxa *e, const double *h_in, long long in_stride, doub
  * percent of the 256-sample tiles on noise alone). */
 long long qh_rxa_pll_repairs(qh_rxa *h);
 int qh_rxa_debug_pll(qh_rxa *h, int check_only, int ch, double *out, int max);   /* diagnostics, see qh_rxa_api.hip */
+int qh_rxa_debug_fm_rows(qh_rxa *h, int *de_rows, int *aud_rows, long long *designed);   /* diagnostics: the design rows of xfmd's two filters on the device, and the rows designed on the host since the engine was made or rebuilt */
 int qh_rxa_debug_fmsq(qh_rxa *h, int ch, double *out, int max);                      /* diagnostics: avnoise, longnoise, state, count, ready at the last call's end (wdsp/fmsq.c:141-205) */
 int qh_rxa_debug_eqp(qh_rxa *h, int ch, double *taps, int max);                      /* diagnostics: returns nc and copies the complex taps behind the mask the channel's equalizer last got (2 nc doubles; a setter's design shows after the next process call that runs it); 0 while no channel of the engine has run the stage */
 int qh_rxa_debug_agc(qh_rxa *h, int form);                                         /* diagnostics: 0 time tiles for long calls (default), 1 sample by sample, 2 batches of 64 */
@@ -389,6 +405,11 @@ void SetRXAAMDFadeLevel(int channel, int levelfade);                            
 void SetRXAFMDeviation(int channel, double deviation);                           /* wdsp/fmd.c:236-246 */
 void SetRXACTCSSFreq(int channel, double freq);                                  /* wdsp/fmd.c:248-258 */
 void SetRXACTCSSRun(int channel, int run);                                       /* wdsp/fmd.c:260-267 */
+void SetRXAFMAFFilter(int channel, double low, double high);                     /* wdsp/fmd.c:364-384 */
+void SetRXAFMNCde(int channel, int nc);                                          /* wdsp/fmd.c:278-293 */
+void SetRXAFMMPde(int channel, int mp);                                          /* wdsp/fmd.c:295-305 */
+void SetRXAFMNCaud(int channel, int nc);                                         /* wdsp/fmd.c:307-322 */
+void SetRXAFMMPaud(int channel, int mp);                                         /* wdsp/fmd.c:324-334 */
 double GetRXAMeter(int channel, int mt);                                         /* wdsp/meter.c:133-142 */
 /* gen0 (see qh_rxa_SetRXAPreGenRun).  SetRXAPreGenMode 4 or 5 while the generator runs: the next fexchange0 sets qh_wdsp_status() and leaves
  * its output buffer alone. */

@@ -32,13 +32,19 @@ void Engine::tick(int cat)
 }
 
 template <int D, bool MIX, bool PACKED = false, bool METER = false, bool OUTMIX = false, bool EGRESS = false, int NFFT = kNfft, bool POLY = false,
-          int DET = 0, bool PAIR = false>
+          int DET = 0, bool PAIR = false, bool MROW = false>
 static void launch_osfir(OsfirArgs<double> a, int ntiles, int nch, hipStream_t s)
 {
     a.ntiles = ntiles;
     dim3 grid((unsigned)ntiles * (unsigned)nch), block(NT);      // 1-D: the kernel maps ids to (channel, tile), qh_osfir.hpp
     constexpr int lds = osfir_lds_bytes<double, NFFT, D, METER>();
-    hipLaunchKernelGGL((osfir_kernel<double, NFFT, D, MIX, PACKED, METER, OUTMIX, EGRESS, POLY, DET, PAIR>), grid, block, lds, s, a);
+    hipLaunchKernelGGL((osfir_kernel<double, NFFT, D, MIX, PACKED, METER, OUTMIX, EGRESS, POLY, DET, PAIR, MROW>), grid, block, lds, s, a);
+}
+// a stage that holds its mask rows by design (OsfirArgs::mask_row: the FM filters; no meters, no audio frames in their stores)
+template <int NFFT>
+static void launch_band_rows(OsfirArgs<double> a, int ntiles, int nch, hipStream_t s)
+{
+    launch_osfir<1, false, false, false, false, false, NFFT, false, 0, false, true>(a, ntiles, nch, s);
 }
 template <int NFFT>
 static void launch_band(OsfirArgs<double> a, int ntiles, int nch, hipStream_t s, bool meter, bool egress)
@@ -54,7 +60,8 @@ static void launch_band6k(OsfirArgs<double> a, int ntiles, int nch, hipStream_t 
     a.ntiles = ntiles;
     dim3 grid((unsigned)ntiles * (unsigned)nch), block(kOsfir6kThreads);
     constexpr int lds = osfir6k_lds_bytes();
-    if (meter && egress) hipLaunchKernelGGL((osfir6k_kernel<true, true>), grid, block, lds, s, a);
+    if (a.mask_row) hipLaunchKernelGGL((osfir6k_kernel<false, false, true>), grid, block, lds, s, a);
+    else if (meter && egress) hipLaunchKernelGGL((osfir6k_kernel<true, true>), grid, block, lds, s, a);
     else if (meter) hipLaunchKernelGGL((osfir6k_kernel<true, false>), grid, block, lds, s, a);
     else if (egress) hipLaunchKernelGGL((osfir6k_kernel<false, true>), grid, block, lds, s, a);
     else hipLaunchKernelGGL((osfir6k_kernel<false, false>), grid, block, lds, s, a);
@@ -65,7 +72,8 @@ static void launch_band2g(OsfirArgs<double> a, int ntiles, int nch, hipStream_t 
     a.ntiles = ntiles;
     dim3 grid((unsigned)ntiles * (unsigned)nch), block(kOsfir8kThreads);
     constexpr int lds = osfir8k_lds_bytes();
-    if (meter && egress) hipLaunchKernelGGL((osfir8k_kernel<true, true>), grid, block, lds, s, a);
+    if (a.mask_row) hipLaunchKernelGGL((osfir8k_kernel<false, false, true>), grid, block, lds, s, a);
+    else if (meter && egress) hipLaunchKernelGGL((osfir8k_kernel<true, true>), grid, block, lds, s, a);
     else if (meter) hipLaunchKernelGGL((osfir8k_kernel<true, false>), grid, block, lds, s, a);
     else if (egress) hipLaunchKernelGGL((osfir8k_kernel<false, true>), grid, block, lds, s, a);
     else hipLaunchKernelGGL((osfir8k_kernel<false, false>), grid, block, lds, s, a);
@@ -80,17 +88,19 @@ int Engine::tile_lds_limits()
                                                      hipFuncAttributeMaxDynamicSharedMemorySize, (osfir_lds_bytes<double, 4096, D, true>())))
     QH_SET_LDS(1, false); QH_SET_LDS(1, false, false, true);
     QH_SET_LDS(1, false, false, false, false, true); QH_SET_LDS(1, false, false, true, false, true);
+    QH_SET_LDS(1, false, false, false, false, false, false, 0, false, true); QH_SET_LDS(1, false, false, false, false, false, false, 0, true, true);   // MROW, plain and PAIR
 #define QH_SET_LDS8(...) QH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&osfir_kernel<double, kBandNfftMax, 1, false, false, __VA_ARGS__>), \
                                                      hipFuncAttributeMaxDynamicSharedMemorySize, (osfir_lds_bytes<double, kBandNfftMax, 1, true>())))
     QH_SET_LDS8(false, false, false); QH_SET_LDS8(true, false, false); QH_SET_LDS8(false, false, true); QH_SET_LDS8(true, false, true);
+    QH_SET_LDS8(false, false, false, false, 0, false, true);       // MROW
 #undef QH_SET_LDS8
 #define QH_SET_LDS6K(...) QH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&osfir6k_kernel<__VA_ARGS__>), \
         hipFuncAttributeMaxDynamicSharedMemorySize, osfir6k_lds_bytes()))
-    QH_SET_LDS6K(false, false); QH_SET_LDS6K(true, false); QH_SET_LDS6K(false, true); QH_SET_LDS6K(true, true);
+    QH_SET_LDS6K(false, false); QH_SET_LDS6K(true, false); QH_SET_LDS6K(false, true); QH_SET_LDS6K(true, true); QH_SET_LDS6K(false, false, true);
 #undef QH_SET_LDS6K
 #define QH_SET_LDS2G(...) QH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&osfir8k_kernel<__VA_ARGS__>), \
                                                       hipFuncAttributeMaxDynamicSharedMemorySize, osfir8k_lds_bytes()))
-    QH_SET_LDS2G(false, false); QH_SET_LDS2G(true, false); QH_SET_LDS2G(false, true); QH_SET_LDS2G(true, true);
+    QH_SET_LDS2G(false, false); QH_SET_LDS2G(true, false); QH_SET_LDS2G(false, true); QH_SET_LDS2G(true, true); QH_SET_LDS2G(false, false, true);
 #undef QH_SET_LDS2G
     QH_SET_LDS(2, false, false, false, true, false, true); QH_SET_LDS(4, false, false, false, true, false, true); QH_SET_LDS(8, false, false, false, true, false, true);
     QH_SET_LDS(2, false, true, false, true, false, true); QH_SET_LDS(4, false, true, false, true, false, true); QH_SET_LDS(8, false, true, false, true, false, true);
@@ -250,12 +260,13 @@ static __global__ __launch_bounds__(NT) void long_hist_kernel(const double2 *cat
     double2 *h = hist + (long long)ch * kLongHist;
     for (int i = kLongHist - lh + blockIdx.x * NT + threadIdx.x; i < kLongHist; i += gridDim.x * NT) h[i] = c[i];
 }
-// partition p is added only where the channel's own impulse response reaches it (row_parts: per mask row, row_stride 0 for a shared mask)
+// partition p is added only where the channel's own impulse response reaches it (row_parts: per mask row, row_stride 0 for a shared mask;
+// mask_row: the channels' rows of a stage that holds them by design, else null)
 static __global__ __launch_bounds__(NT) void long_add_kernel(double2 *dst, long long dst_stride, const double2 *add, long long add_stride, int n, const int *chan_list,
-                                                             const int *row_parts, int row_stride, int p)
+                                                             const int *row_parts, int row_stride, const int *mask_row, int p)
 {
     const int ch = chan_list ? chan_list[blockIdx.y] : (int)blockIdx.y;
-    if (p >= row_parts[(long long)ch * row_stride]) return;
+    if (p >= row_parts[mask_row ? (long long)mask_row[ch] : (long long)ch * row_stride]) return;
     double2 *d = dst + (long long)ch * dst_stride;
     const double2 *a = add + (long long)ch * add_stride;
     for (int i = blockIdx.x * NT + threadIdx.x; i < n; i += gridDim.x * NT) { d[i].x += a[i].x; d[i].y += a[i].y; }
@@ -308,14 +319,16 @@ void Engine::run_band(const double2 *src, long long src_stride, double2 *dst, lo
             a.hist = a.in - Pk; a.hist_stride = cat_stride; a.hist_len = Pk;
             a.out = p ? ltmp : dst; a.out_stride = p ? lcat_cap : dst_stride; a.out_offset = 0;
             a.mask = f.lmask + (size_t)p * kBandNfftMax; a.mask_stride = f.mask_stride ? (long long)kLongParts * kBandNfftMax : 0;
+            a.mask_row = f.mask_row;
             a.tw_fwd = a.tw_inv = tw8192;
             a.tw_r2 = tw8192 + 32;
             a.chan_list = list;
             a.n_in = (int)n_mid; a.n_out = (int)n_mid; a.off = 0; a.P = Pk; a.Lout = Lk;
-            launch_band<kBandNfftMax>(a, nt, nl, stream, false, false);
+            if (f.mask_row) launch_band_rows<kBandNfftMax>(a, nt, nl, stream);
+            else launch_band<kBandNfftMax>(a, nt, nl, stream, false, false);
             const long long pn = (n_mid + NT - 1) / NT;
             if (p) hipLaunchKernelGGL(long_add_kernel, dim3((unsigned)(pn < 1024 ? pn : 1024), (unsigned)nl), dim3(NT), 0, stream, dst, dst_stride,
-                                      (const double2 *)ltmp, lcat_cap, (int)n_mid, list, (const int *)f.lrow_parts, f.mask_stride ? 1 : 0, p);
+                                      (const double2 *)ltmp, lcat_cap, (int)n_mid, list, (const int *)f.lrow_parts, f.mask_stride ? 1 : 0, (const int *)f.mask_row, p);
         }
         const long long pn = (n_mid + NT - 1) / NT;
         if (ep) hipLaunchKernelGGL((pointwise_kernel<double, false>), dim3((unsigned)(pn < 1024 ? pn : 1024), (unsigned)nl), dim3(NT), 0, stream,
@@ -332,6 +345,7 @@ void Engine::run_band(const double2 *src, long long src_stride, double2 *dst, lo
     a.hist = hist[hc]; a.hist_stride = kHistBand; a.hist_len = kHistBand;
     a.out = dst; a.out_stride = dst_stride; a.out_offset = 0;
     a.mask = f.mask; a.mask_stride = f.mask_stride;
+    a.mask_row = f.mask_row;                // null but for a stage with more than one design row (fm_filters)
     a.tw_fwd = a.tw_inv = (bnfft == kNfft || band2g) ? tw4096 : tw8192;
     a.tw_r2 = tw8192 + 32;                  // second pass table of the 8192-point plan: exp(-2 pi i k / 8192), k < 256 (qh_design.cpp)
     a.epi = ep;
@@ -354,7 +368,8 @@ void Engine::run_band(const double2 *src, long long src_stride, double2 *dst, lo
             a.amlv_a = band_amlv->a; a.amlv_stride = band_amlv->stride; a.amlv_shift = band_amlv->shift;
             a.amlv_cin = am_cin; a.amlv_cstride = am_cin_cap; a.amlv_pw = am_pw;
         }
-        launch_osfir<1, false, false, false, false, false, kNfft, false, 0, true>(a, ntiles, npairs, stream);
+        if (a.mask_row) launch_osfir<1, false, false, false, false, false, kNfft, false, 0, true, true>(a, ntiles, npairs, stream);
+        else launch_osfir<1, false, false, false, false, false, kNfft, false, 0, true>(a, ntiles, npairs, stream);
     } else if (det) {       // the caller has checked: 4096-point tiles, no meters, no egress
         a.det_out = det_out; a.det_stride = det_stride;
         if (det == 2 || det == 3) {
@@ -372,6 +387,8 @@ void Engine::run_band(const double2 *src, long long src_stride, double2 *dst, lo
         } else launch_osfir<1, false, false, false, false, false, kNfft, false, 1>(a, ntiles, nl, stream);
     } else if (band6k) launch_band6k(a, ntiles, nl, stream, meter, egress);
     else if (band2g) launch_band2g(a, ntiles, nl, stream, meter, egress);
+    else if (a.mask_row && bnfft == kNfft) launch_band_rows<kNfft>(a, ntiles, nl, stream);
+    else if (a.mask_row) launch_band_rows<kBandNfftMax>(a, ntiles, nl, stream);
     else if (bnfft == kNfft) launch_band<kNfft>(a, ntiles, nl, stream, meter, egress);
     else launch_band<kBandNfftMax>(a, ntiles, nl, stream, meter, egress);
     tick(2);
@@ -450,7 +467,13 @@ int Engine::chain_needs(ChainCall &k)
         if (c.emnr_run && !emnr_tables) return set_error(QH_ERR_INVALID, "EMNR needs its gain tables first (qh_rxa_SetEMNRTables: WDSP's `calculus` and `zetaHat.bin` data)");
         if (c.nbp_run) { k.any_nbp = true; if (c.nbp_nc > k.nc_max) k.nc_max = c.nbp_nc; } else k.every_nbp = false;
         if (c.bp1_run) { k.any_bp1 = true; if (c.bp1_nc > k.nc_max) k.nc_max = c.bp1_nc; }
-        if (c.fmd_run && c.fm_nc > k.nc_max) k.nc_max = c.fm_nc;
+        if (c.fmd_run) {
+            k.nc_max = std::max({ k.nc_max, c.fm_nc_de, c.fm_nc_aud });
+            // fir_bandpass's upper edge 1.1 f_high (fmd.c:115) and fc_impulse's grid need it below the Nyquist frequency
+            if (1.1 * c.fm_f_high >= 0.5 * (double)dsp_rate)
+                return set_error(QH_ERR_UNSUPPORTED, "channel %d: FM audio band up to %g Hz needs 1.1 * high below dsp_rate / 2 = %g", (int)(&c - cfg.data()),
+                                 c.fm_f_high, 0.5 * (double)dsp_rate);
+        }
         if (c.fmsq_run) {
             const int ch = (int)(&c - cfg.data());
             // (the reference would run its noise filter over the audio buffer xfmd last wrote, however long ago)
@@ -472,7 +495,7 @@ int Engine::chain_needs(ChainCall &k)
         if (c.eqp_tie) return set_error(QH_ERR_UNSUPPORTED, "channel %d: two EQ frequencies coincide in [0, rate / 2] while their gains differ", ch);
         if (c.eqp_nc > k.nc_max) k.nc_max = c.eqp_nc;
     }
-    {   // one noise filter design for the engine's FMSQ channels, as the FM channels share theirs (refresh_demod)
+    {   // one noise filter design for the engine's FMSQ channels
         const ChanCfg *first = nullptr;
         for (const ChanCfg &c : cfg) {
             if (!c.fmsq_run) continue;
@@ -497,11 +520,12 @@ int Engine::plan_long(ChainCall &k)
     // the only long channel leaving took the stage to the short form (its line cut to 4095 samples) and came back to zeros behind
     // them: one long call 0.65 off (walk rxa_long 900190, found by round 6's seed sweep; in the suite since).
     // (long_live: the channel has run the stage with such an nc since RXASetNC last zeroed its lines.)
-    // The FM pair takes its count from fm_nc together, bpsnba follows nbp0's nc (its nbp shares it, refresh_params).
+    // The FM pair takes its count from the larger of nc_de / nc_aud together, bpsnba follows nbp0's nc (its nbp shares it, refresh_params).
     for (int ch = 0; ch < nch; ch++) {
         const ChanCfg &c = cfg[(size_t)ch];
         const int run[FC_COUNT] = { c.nbp_run, c.bp1_run, c.fmd_run, c.fmd_run, c.snba_run, 0, 0 };
-        const int nc[FC_COUNT] = { c.nbp_nc, c.bp1_nc, c.fm_nc, c.fm_nc, c.nbp_nc, 0, 0 };
+        const int fm_nc = std::max(c.fm_nc_de, c.fm_nc_aud);
+        const int nc[FC_COUNT] = { c.nbp_nc, c.bp1_nc, fm_nc, fm_nc, c.nbp_nc, 0, 0 };
         for (int s = 0; s < FC_COUNT; s++) {
             if (!fc[s].can_long) continue;
             Fircore::Chan &r = fc[s].chan[(size_t)ch];
@@ -524,7 +548,7 @@ int Engine::plan_long(ChainCall &k)
         f.parts = lp[s];
         // the stage's masks are laid out for another form now: all of them again
         if (f.dirty) for (ChanCfg &c : cfg) c.*f.dirty = true;
-        else fm_nc_built = 0;       // (the FM pair's shared designs)
+        else fm_dirty = fm_relayout = true;     // (the FM pair's design rows)
     }
     return QH_OK;
 }

@@ -95,7 +95,12 @@ struct ChanCfg {
     int inselect = 3, copy = 0;
     int levelfade = 1, sbmode = 0;                              // RXA.c:180-181
     double fm_dev = 5000.0, ctcss_freq = 254.1;                 // RXA.c:198,208
-    int ctcss_run = 1, fm_nc = 2048;                            // RXA.c:207,209-212
+    int ctcss_run = 1;                                          // RXA.c:207
+    // xfmd's de-emphasis and audio filters (create_fmd's arguments, RXA.c:209-212: nc max(2048, dsp_size) -- Engine::init --, mp 0; the
+    // audio band, RXA.c:196-197).  fm_de_flush / fm_aud_flush: SetRXAFMNCde / NCaud took a new nc (setNc_fircore zeroes that filter's line)
+    int fm_nc_de = 2048, fm_mp_de = 0, fm_nc_aud = 2048, fm_mp_aud = 0;
+    double fm_f_low = 300.0, fm_f_high = 3000.0;
+    bool fm_de_flush = false, fm_aud_flush = false;
     int lim_run = 0; double lim_gain = 2.5; bool lim_dirty = true;   // FM detector limiter, fmd.c:106-108
     // anf / anr (create_anf / create_anr of create_rxa, RXA.c:278-315): [0] = anf, [1] = anr
     struct Lms { int run = 0, position = 0, taps = 64, delay = 16; double two_mu = 0.0001, gamma = 0.1; bool dirty = true, flush = false; } lms[2];
@@ -179,6 +184,13 @@ enum FcId { FC_NBP, FC_BP1, FC_DE, FC_AUD, FC_SNB, FC_FQ, FC_EQP, FC_COUNT };
 struct Fircore {
     double2 *mask = nullptr;
     long long mask_stride = 0;              // kBandNfftMax: one mask row per channel; 0: one row shared by the stage's channels
+    // The FM de-emphasis and audio filters hold one mask row per distinct design among their running channels (Engine::fm_filters):
+    // by_design, `rows` of them allocated.  One row: mask_stride 0 and no mask_row, the shared row of old; more: mask_stride
+    // kBandNfftMax and mask_row [nch], the row of every channel (OsfirArgs::mask_row).  lmask / lrow_parts go by the same rows.
+    bool by_design = false;
+    int rows = 1;
+    int *mask_row = nullptr;
+    long long mask_rows(int nch) const { return by_design ? rows : mask_stride ? nch : 1; }
     double2 *hist[2] = { nullptr, nullptr };
     int cur = 0;
     bool ChanCfg::*dirty = nullptr;         // nbp0, bp1, bpsnba: the channel's flag that has its mask row designed and uploaded again (plan_long)
@@ -280,8 +292,9 @@ struct Engine {
     struct ChanList { int *dev = nullptr; int n = 0; };
     ChanList lists[L_COUNT];
     int *list_block = nullptr;
-    // channel pairs for the real filters behind the detectors (osfir_kernel PAIR): FM de-emphasis (one mask for all), bp1 of the AM
-    // and of the SAM channels (partners have the same design; count 0 when a channel of the kind has complex taps)
+    // channel pairs for the real filters behind the detectors (osfir_kernel PAIR): FM de-emphasis, bp1 of the AM and of the SAM channels
+    // (partners have the same design; bp1: count 0 when a channel of the kind has complex taps; FM: de_real says that no running
+    // channel's de-emphasis row has one)
     int np_fm = 0, np_am = 0, np_sam = 0;
     bool de_real = false;
     bool all_nbp = false;
@@ -315,8 +328,8 @@ struct Engine {
     int ssql_alloc();
     bool ssql_listed() const { return ssql_lists[0].n || ssql_lists[1].n; }
     // xfmsq (qh_fmsq.hpp), made when a channel first runs it, in blocks of its own: the list of its channels and their pairs for the
-    // noise filter (as L_PAIRS_FM), parameters, state, the ramps, the noise filter (fc[FC_FQ]: one design for the engine's FMSQ channels,
-    // as the FM filters) and its output rows [nch][fq_noise_cap]
+    // noise filter (neighbours in the list), parameters, state, the ramps, the noise filter (fc[FC_FQ]: one design for the engine's FMSQ
+    // channels) and its output rows [nch][fq_noise_cap]
     ChanList fq_list, fq_pairs;
     std::vector<int> fq_h, fq_pairs_h;
     int *fq_list_block = nullptr;
@@ -457,7 +470,20 @@ struct Engine {
     PllParam sam_pll_prm{}, fm_pll_prm{};
     SnotchParam *sn_prm = nullptr;
     SnotchState *sn_state = nullptr;
-    int fm_nc_built = 0, fm_mp = 0, fm_mp_built = 0, fm_key_built = 0;
+    // The design rows of xfmd's two filters ([0] de-emphasis, [1] audio) as they stand on the device: row r of the stage's masks holds
+    // fm_rows[s][r] (key and taps; the taps are kept so that a row that only moves is uploaded, not designed, again) and channel ch reads
+    // row fm_row_of[s][ch].  fm_dirty: a setter, the lists or the masks' layout moved; fm_relayout: every row is to be uploaded again.
+    struct FmRow {
+        int nc = 0, mp = 0; double f_low = 0.0, f_high = 0.0;
+        std::vector<cd> taps;
+        bool real = true;
+        bool same(const FmRow &o) const { return nc == o.nc && mp == o.mp && f_low == o.f_low && f_high == o.f_high; }
+    };
+    std::vector<FmRow> fm_rows[2];
+    std::vector<int> fm_row_of[2];
+    bool fm_dirty = true, fm_relayout = false;
+    int fm_key_built = 0;
+    long long fm_designed = 0;              // rows designed on the host so far (diagnostics: qh_rxa_debug_fm_rows)
     // the ping-pong halves in use: bit 0 the front stage's, bit 1 + s fircore stage s's -- one captured launch sequence per value
     static_assert(sizeof(graph_slot) / sizeof(graph_slot[0]) == 1u << (1 + FC_COUNT), "one graph slot per state of the ping-pong flags");
     unsigned flags() const { unsigned f = (unsigned)cur_front; for (int s = 0; s < FC_COUNT; s++) f |= (unsigned)fc[s].cur << (1 + s); return f; }
@@ -538,7 +564,8 @@ struct Engine {
     int prm_lms(ChanCfg &c, int ch);
     int prm_lim(ChanCfg &c, int ch);
     int prm_detect(ChanCfg &c, int ch);
-    int fm_filters(int want_nc);
+    int fm_filters();
+    int fm_rows_resize(Fircore &f, int rows);
     // v -> dev[row] on `stream`, then a wait unless told not to (a caller that does not wait keeps v alive until it does)
     template <typename T> int put_row(T *dev, long long row, const T &v, bool wait = true)
     {

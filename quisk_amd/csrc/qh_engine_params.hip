@@ -148,11 +148,13 @@ int Engine::init()
     QH_HIP(hipSetDevice(device));
     if (!stream) { QH_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking)); own_stream = true; }
     cfg.assign((size_t)nch, ChanCfg());
-    for (ChanCfg &c : cfg) c.eqp_nc = std::max(2048, dsp_size);        // create_eqp's nc, RXA.c:265
+    for (ChanCfg &c : cfg) c.eqp_nc = c.fm_nc_de = c.fm_nc_aud = std::max(2048, dsp_size);     // create_eqp's nc, RXA.c:265; create_fmd's, RXA.c:209,211
     snba_tune_h.assign((size_t)nch, SnbaTune{ 64, 2, 10, 2, 2, 0, 8.0, 20.0, 0.5 });         // create_snba's arguments, RXA.c:183-202
-    // the fircore stages: the FM pair and xfmsq's noise filter share one design among their channels, the others hold one per channel
+    // the fircore stages: the FM pair holds a mask row per distinct design among its channels (one row to begin with), xfmsq's noise
+    // filter one design for its channels, the others one per channel
     for (int s = 0; s < FC_COUNT; s++) {
         fc[s].mask_stride = s == FC_DE || s == FC_AUD || s == FC_FQ ? 0 : kBandNfftMax;
+        fc[s].by_design = s == FC_DE || s == FC_AUD;
         fc[s].chan.assign((size_t)nch, Fircore::Chan());
     }
     fc[FC_NBP].dirty = &ChanCfg::nbp_dirty; fc[FC_BP1].dirty = &ChanCfg::bp1_dirty; fc[FC_SNB].dirty = &ChanCfg::snb_dirty;
@@ -344,7 +346,7 @@ int Engine::put_taps(Fircore &f, int row, const std::vector<cd> &h, std::vector<
 // A fircore stage's device rows: its masks and its delay lines, zeroed; every channel's line lies in the half that is current
 int Engine::fc_alloc(Fircore &f)
 {
-    if (int rc = alloc(f.mask, (f.mask_stride ? (long long)nch : 1LL) * kBandNfftMax)) return rc;
+    if (int rc = alloc(f.mask, f.mask_rows(nch) * kBandNfftMax)) return rc;
     if (f.carried) { f.carried = false; return QH_OK; }
     for (double2 *&h : f.hist) if (int rc = alloc(h, (long long)nch * kHistBand, true)) return rc;
     for (Fircore::Chan &r : f.chan) { r.listed = false; r.at = f.cur; }
@@ -519,8 +521,17 @@ void Engine::build_lists(std::vector<int> (&h)[L_COUNT])
         }
         return pr;
     };
-    const std::vector<int> &fm = h[L_FM];
-    for (size_t i = 0; i < fm.size(); i += 2) { h[L_PAIRS_FM].push_back(fm[i]); h[L_PAIRS_FM].push_back(i + 1 < fm.size() ? fm[i + 1] : fm[i]); }
+    // the FM de-emphasis stage: by design row, which is by what the row is designed from (fm_filters); one design leaves the list's order
+    {
+        auto de_key = [&](int ch) { const ChanCfg &c = cfg[(size_t)ch]; return std::make_tuple(c.fm_nc_de, c.fm_mp_de, c.fm_f_low, c.fm_f_high); };
+        std::vector<int> fm(h[L_FM]);
+        std::stable_sort(fm.begin(), fm.end(), [&](int x, int y) { return de_key(x) < de_key(y); });
+        for (size_t i = 0; i < fm.size();) {
+            const bool two = i + 1 < fm.size() && de_key(fm[i]) == de_key(fm[i + 1]);
+            h[L_PAIRS_FM].push_back(fm[i]); h[L_PAIRS_FM].push_back(two ? fm[i + 1] : fm[i]);
+            i += two ? 2 : 1;
+        }
+    }
     h[L_PAIRS_AM] = bp1_pairs(h[L_AM]);
     h[L_PAIRS_SAM] = bp1_pairs(h[L_SAM]);
     np_fm = (int)h[L_PAIRS_FM].size() / 2; np_am = (int)h[L_PAIRS_AM].size() / 2; np_sam = (int)h[L_PAIRS_SAM].size() / 2;
@@ -789,6 +800,7 @@ int Engine::refresh_lists()
     }
     QH_HIP(hipStreamSynchronize(stream));
     lists_dirty = false;
+    fm_dirty = true;                // the design rows follow the running FM channels
     return QH_OK;
 }
 
@@ -964,30 +976,84 @@ int Engine::prm_detect(ChanCfg &c, int ch)
     return QH_OK;
 }
 
-// create_fmd, wdsp/fmd.c:108-116: the de-emphasis and audio filters the FM channels share, rebuilt when their nc, RXASetMP or the band
-// tile moved
-int Engine::fm_filters(int want_nc)
+// Room for `rows` design rows of an FM filter's masks (and of its partitions' masks where the stage has them): one row is the shared row
+// (stride 0, no mask_row), more are rows of kBandNfftMax with the channels' row numbers beside them.  What the rows held is lost.
+int Engine::fm_rows_resize(Fircore &f, int rows)
 {
-    if (!want_nc || (want_nc == fm_nc_built && fm_mp == fm_mp_built && fm_key_built == mask_key())) return QH_OK;
-    // de-emphasis by frequency sampling, audio band-pass 0.8*f_low .. 1.1*f_high
-    const double rate = (double)dsp_rate, f_low = 300.0, f_high = 3000.0, afgain = 0.5;
-    std::vector<cd> de = fc_impulse(want_nc, f_low, f_high, +20.0 * std::log10(f_high / f_low), 0.0, 1, rate, 1.0 / (2.0 * dsp_size), 0, 0);
-    std::vector<cd> au = fir_bandpass(want_nc, 0.8 * f_low, 1.1 * f_high, rate, 0, 1, afgain / (2.0 * dsp_size));
-    if (fm_mp) { de = mp_imp(de, 16, 0); au = mp_imp(au, 16, 0); }     // SetRXAFMMPde / MPaud, wdsp/RXA.c:956-957
-    fm_mp_built = fm_mp;
-    for (auto &v : de) v *= (double)(2 * dsp_size);
-    for (auto &v : au) v *= (double)(2 * dsp_size);
-    de_real = true;
-    for (const cd &v : de) de_real = de_real && v.imag() == 0.0;
-    std::vector<cd> m_de, m_au;
-    if (int rc = put_taps(fc[FC_DE], 0, de, m_de)) return rc;
-    if (int rc = put_taps(fc[FC_AUD], 0, au, m_au)) return rc;
-    fm_key_built = mask_key();
-    if (fm_nc_built && fm_nc_built != want_nc) {      // setNc_fircore zeroes the delay lines
-        if (int rc = zero_rows(fc[FC_DE], 0, nch)) return rc;
-        if (int rc = zero_rows(fc[FC_AUD], 0, nch)) return rc;
+    if (int rc = quiesce()) return rc;
+    f.rows = rows;
+    f.mask_stride = rows > 1 ? kBandNfftMax : 0;
+    if (int rc = alloc(f.mask, (long long)rows * kBandNfftMax)) return rc;
+    if (rows > 1) { if (int rc = alloc(f.mask_row, nch, true)) return rc; }
+    else release(f.mask_row);
+    if (f.lmask) {
+        if (int rc = alloc(f.lmask, (long long)rows * kLongParts * kBandNfftMax, true)) return rc;
+        if (int rc = alloc(f.lrow_parts, rows, true)) return rc;
     }
-    fm_nc_built = want_nc;
+    return QH_OK;
+}
+
+// create_fmd, wdsp/fmd.c:108-118: every channel's de-emphasis (pde) and audio (paud) filter, one mask row per distinct design among the
+// running FM channels -- (nc, mp, f_low, f_high) of the filter; dsp_rate, dsp_size and the masks' layout are the engine's.  Rows are
+// numbered in the order the channels first ask for them.  A row whose design stood on the device before is not designed again (its taps
+// are kept: it is uploaded again only where it moved or the masks were laid out anew); SetRXAFMNCde / NCaud's flush of the one line.
+int Engine::fm_filters()
+{
+    if (fm_key_built != mask_key()) fm_dirty = fm_relayout = true;
+    if (!fm_dirty) return QH_OK;
+    const double rate = (double)dsp_rate, afgain = 0.5;
+    for (int s = 0; s < 2; s++) {
+        Fircore &f = fc[s ? FC_AUD : FC_DE];
+        std::vector<FmRow> want;
+        std::vector<int> row_of((size_t)nch, 0);
+        for (int ch = 0; ch < nch; ch++) {
+            ChanCfg &c = cfg[(size_t)ch];
+            bool &flush = s ? c.fm_aud_flush : c.fm_de_flush;
+            if (flush) { if (int rc = zero_rows(f, ch)) return rc; flush = false; }      // setNc_fircore, firmin.c:455-467
+            if (!c.fmd_run) continue;
+            FmRow k;
+            k.nc = s ? c.fm_nc_aud : c.fm_nc_de; k.mp = s ? c.fm_mp_aud : c.fm_mp_de; k.f_low = c.fm_f_low; k.f_high = c.fm_f_high;
+            size_t r = 0;
+            while (r < want.size() && !want[r].same(k)) r++;
+            if (r == want.size()) want.push_back(k);
+            row_of[(size_t)ch] = (int)r;
+        }
+        if (want.empty()) continue;
+        std::vector<FmRow> &built = fm_rows[s];
+        const bool resized = (int)want.size() != f.rows;
+        if (resized) if (int rc = fm_rows_resize(f, (int)want.size())) return rc;
+        std::vector<char> fresh(want.size(), 0);
+        for (size_t r = 0; r < want.size(); r++) {
+            FmRow &w = want[r];
+            fresh[r] = resized || fm_relayout || r >= built.size() || !built[r].same(w);
+            for (FmRow &b : built) if (b.same(w) && !b.taps.empty()) { w.taps = b.taps; w.real = b.real; break; }
+            if (!w.taps.empty()) continue;
+            // de-emphasis by frequency sampling (fmd.c:112), audio band-pass 0.8 f_low .. 1.1 f_high (fmd.c:115)
+            w.taps = s ? fir_bandpass(w.nc, 0.8 * w.f_low, 1.1 * w.f_high, rate, 0, 1, afgain / (2.0 * dsp_size))
+                       : fc_impulse(w.nc, w.f_low, w.f_high, +20.0 * std::log10(w.f_high / w.f_low), 0.0, 1, rate, 1.0 / (2.0 * dsp_size), 0, 0);
+            if (w.mp) w.taps = mp_imp(w.taps, 16, 0);           // SetRXAFMMPde / MPaud, fmd.c:295-305,324-334
+            for (cd &v : w.taps) v *= (double)(2 * dsp_size);
+            w.real = true;
+            for (const cd &v : w.taps) w.real = w.real && v.imag() == 0.0;
+            fm_designed++;
+        }
+        for (size_t r = 0; r < want.size(); r++) {
+            if (!fresh[r]) continue;
+            std::vector<cd> m;
+            if (int rc = put_taps(f, (int)r, want[r].taps, m)) return rc;
+        }
+        if (f.mask_row && (resized || row_of != fm_row_of[s])) {
+            QH_HIP(hipMemcpyAsync(f.mask_row, row_of.data(), (size_t)nch * sizeof(int), hipMemcpyHostToDevice, stream));
+            QH_HIP(hipStreamSynchronize(stream));
+        }
+        built = std::move(want);
+        fm_row_of[s] = std::move(row_of);
+    }
+    // a row with a complex tap (minimum phase) takes no partner: the paired tile is for real filters, so the stage then runs unpaired
+    de_real = true;
+    for (const FmRow &r : fm_rows[0]) de_real = de_real && r.real;
+    fm_key_built = mask_key();
+    fm_dirty = fm_relayout = false;
     return QH_OK;
 }
 
@@ -1005,17 +1071,8 @@ int Engine::refresh_demod()
         if (c.agc_abuf != abuf) { c.agc_rewindow = true; if (!c.agc_stale) { c.agc_stale = true; lists_dirty = true; } }
     }
     if (lists_dirty) if (int rc = refresh_lists()) return rc;
-    int want_nc = 0, want_mp = -1;
     for (int ch = 0; ch < nch; ch++) {
         ChanCfg &c = cfg[(size_t)ch];
-        if (c.fmd_run) {
-            if (want_nc && want_nc != c.fm_nc) return set_error(QH_ERR_UNSUPPORTED, "FM channels with different nc in one engine");
-            want_nc = c.fm_nc;
-            // RXASetMP reaches the FM filters of ITS channel (SetRXAFMMPde / MPaud, wdsp/RXA.c:956-957): the one design the engine's FM
-            // channels share follows them, not whichever channel was set last
-            if (want_mp >= 0 && want_mp != c.mp) return set_error(QH_ERR_UNSUPPORTED, "FM channels with different RXASetMP in one engine");
-            want_mp = c.mp;
-        }
         if (int rc = prm_agc(c, ch)) return rc;
         if (int rc = prm_emnr(c, ch)) return rc;
         if (int rc = prm_snba(c, ch)) return rc;
@@ -1025,8 +1082,7 @@ int Engine::refresh_demod()
         if (int rc = prm_lim(c, ch)) return rc;
         if (int rc = prm_detect(c, ch)) return rc;
     }
-    if (want_mp >= 0) fm_mp = want_mp;
-    if (int rc = fm_filters(want_nc)) return rc;
+    if (int rc = fm_filters()) return rc;
     return fmsq_filter();
 }
 
@@ -1247,7 +1303,7 @@ int Engine::long_stage_alloc(Fircore &f)
 {
     if (f.lmask) return QH_OK;
     if (int rc = quiesce()) return rc;
-    const long long rows = f.mask_stride ? nch : 1;
+    const long long rows = f.mask_rows(nch);
     if (int rc = alloc(f.lmask, rows * kLongParts * kBandNfftMax, true)) return rc;
     if (int rc = alloc(f.lrow_parts, rows, true)) return rc;
     for (double2 *&h : f.lhist) if (int rc = alloc(h, (long long)nch * kLongHist, true)) return rc;
@@ -1758,7 +1814,7 @@ int Engine::set_rates(int new_in, int new_dsp, int new_out, int new_size)
     if (int rc = check_rates("qh_rxa_set_rates", new_size, new_in, new_dsp, new_out, &new_D)) return rc;
     for (const ChanCfg &c : cfg) {
         // setSize_nbp / setSize_bandpass: "'size' must be <= 'nc'" (nbp.c:308, bandpass.c:345); the other fircores are planned the same way
-        const int nc = std::min({ c.nbp_nc, c.bp1_nc, c.fm_nc, c.fmsq_nc, c.eqp_nc });
+        const int nc = std::min({ c.nbp_nc, c.bp1_nc, c.fm_nc_de, c.fm_nc_aud, c.fmsq_nc, c.eqp_nc });
         if (new_size > nc) return set_error(QH_ERR_UNSUPPORTED, "dsp_size %d above nc %d of channel %d: size must be <= nc (wdsp/nbp.c:308)", new_size, nc, (int)(&c - cfg.data()));
         if (c.emnr_run && new_size > kEmnrIncr) return set_error(QH_ERR_UNSUPPORTED, "EMNR: dsp_size up to %d", kEmnrIncr);
         if (c.snba_run && (new_dsp % 12000 || (new_dsp / 12000 != 1 && new_dsp / 12000 != 2 && new_dsp / 12000 != 4) || new_size > kSnbMaxDsp ||
@@ -1792,7 +1848,7 @@ static ChanCfg settings_of(const ChanCfg &o, int dsp_rate)
 {
     // a member added to ChanCfg is a setting (kept by the copy below) or a note of work (to be put back to its default here): this
     // reminder fails to compile until its author has looked
-    static_assert(sizeof(ChanCfg) == 872, "ChanCfg changed: see to settings_of, then update the size");
+    static_assert(sizeof(ChanCfg) == 904, "ChanCfg changed: see to settings_of, then update the size");
     ChanCfg c = o;
     const ChanCfg d;
     c.shift_on_device = d.shift_on_device;
@@ -1806,6 +1862,7 @@ static ChanCfg settings_of(const ChanCfg &o, int dsp_rate)
     c.ap_dirty = d.ap_dirty; c.sp_flush = d.sp_flush;
     for (int i = 0; i < kApPeaks; i++) c.mp_flush[i] = d.mp_flush[i];
     c.ssql_dirty = d.ssql_dirty; c.fmsq_dirty = d.fmsq_dirty; c.lim_dirty = d.lim_dirty;
+    c.fm_de_flush = d.fm_de_flush; c.fm_aud_flush = d.fm_aud_flush;
     c.eqp_dirty = d.eqp_dirty; c.eqp_flush = d.eqp_flush; c.eqp_tie = eqp_profile_tie(c.eqp_F, c.eqp_G, (double)dsp_rate);
     c.gen_dirty = d.gen_dirty; c.gen_sweep_dirty = d.gen_sweep_dirty; c.gen_tone_reset = d.gen_tone_reset; c.gen_sweep_reset = d.gen_sweep_reset;
     return c;
@@ -1866,7 +1923,7 @@ int Engine::rebuild(int new_in, int new_dsp, int new_out, int new_size, int new_
     std::vector<ChanCfg> keep_cfg;
     for (const ChanCfg &c : cfg) keep_cfg.push_back(settings_of(c, new_dsp));
     // the engine-wide settings: one Engine member set through the C ABI outside cfg that is not listed here is lost by a rebuild
-    static_assert(sizeof(Engine) == 9128, "Engine changed: see to Engine::rebuild's Wide and carried state, then update the size");
+    static_assert(sizeof(Engine) == 9336, "Engine changed: see to Engine::rebuild's Wide and carried state, then update the size");
     struct Wide {
         int device, nch; hipStream_t stream; bool own_stream; unsigned long long epoch;
         bool graph_on; long long graph_launches; bool timing, meters_on; int band_tile_pref, snba_ovrlp; std::vector<SnbaTune> snba_tune_h;

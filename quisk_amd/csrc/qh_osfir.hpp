@@ -114,6 +114,11 @@ template <typename T> struct OsfirArgs {
     long long amlv_cstride;
     const double *amlv_pw;              // [2][2^amlv_shift]: mtauR^(k + 1), mtauI^(k + 1)
     int amlv_shift;
+    // MROW kernels: [nch] the mask row of every channel, for a stage that holds one row per distinct design among its channels (the
+    // engine's FM de-emphasis and audio filters): mask + mask_row[ch] * mask_stride.  Null for every other stage (row = channel, or the
+    // one shared row with mask_stride 0), whose kernels are the instantiations without MROW and never read it.  Last, so that no other
+    // member moves.
+    const int *mask_row;
 };
 
 
@@ -301,8 +306,9 @@ __device__ __forceinline__ void meter_tap(const C (&x)[E], int r0, double wlane,
 // components (xamd: amd.c:139-140, xfmd: fmd.c:170-171): two channels with the same mask share a tile -- channel A in the real part,
 // channel B in the imaginary part, one transform pair for both, and (y, y) goes to each one's row.  chan_list holds the pairs
 // (A0, B0, A1, B1, ...; a channel without a partner is paired with itself).
+// MROW: the mask row comes from OsfirArgs::mask_row (with PAIR: partners share a design, so channel A's row serves both).
 template <typename T, int NFFT, int D, bool MIX, bool PACKED = false, bool METER = false, bool OUTMIX = false, bool EGRESS = false, bool POLY = false,
-          int DET = 0, bool PAIR = false>
+          int DET = 0, bool PAIR = false, bool MROW = false>
 __global__ __launch_bounds__(NT, (osfir_min_waves<T, D, OUTMIX, NFFT>())) void osfir_kernel(OsfirArgs<T> a)
 {
     using C = cplx<T>;
@@ -322,6 +328,9 @@ __global__ __launch_bounds__(NT, (osfir_min_waves<T, D, OUTMIX, NFFT>())) void o
     xcd_tile_map(a.ntiles, slot, tile);
     const int ch = PAIR ? a.chan_list[2 * slot] : a.chan_list ? a.chan_list[slot] : slot;
     const int ch_b = PAIR ? a.chan_list[2 * slot + 1] : ch;
+    // workgroup-uniform, so a scalar load; asked for here, ahead of the tile's loads and the forward transform, not in front of the
+    // mask loop where the masks' addresses would wait for it
+    const int mrow = MROW ? a.mask_row[ch] : ch;
     const C *in = a.in + (long long)ch * a.in_stride;
     const C *hist = a.hist ? a.hist + (long long)ch * a.hist_stride : nullptr;
     const int g0 = a.off - a.P + tile * (D * a.Lout);      // input index of element 0 of this tile (Lout counts folded samples)
@@ -469,7 +478,7 @@ __global__ __launch_bounds__(NT, (osfir_min_waves<T, D, OUTMIX, NFFT>())) void o
     QH_OPROBE(2);
 
     // ---- mask multiply + D-fold: lane holds bins t + NT*i; bins t + NT*(i' + EO*q) alias to t + NT*i'
-    const C *mask = a.mask + (long long)ch * a.mask_stride;
+    const C *mask = a.mask + (long long)mrow * a.mask_stride;
     C z[EO];
 #pragma unroll
     for (int i = 0; i < EO; i++) {
@@ -697,7 +706,7 @@ constexpr int kOsfir8kThreads = 512, kOsfir8kP = 2048, kOsfir8kLout = 6144;
 constexpr int kOsfir8kImage = FftSplit4096<false, double2>::kLdsBytes > 4 * 2 * 64 * 9 * 8 ? FftSplit4096<false, double2>::kLdsBytes : 4 * 2 * 64 * 9 * 8;   // image or meter blocks
 constexpr int osfir8k_lds_bytes() { return 2 * kOsfir8kImage; }
 
-template <bool METER, bool EGRESS>
+template <bool METER, bool EGRESS, bool MROW = false>
 __global__ __launch_bounds__(kOsfir8kThreads, 4) void osfir8k_kernel(OsfirArgs<double> a)
 {
     using C = double2;
@@ -712,6 +721,7 @@ __global__ __launch_bounds__(kOsfir8kThreads, 4) void osfir8k_kernel(OsfirArgs<d
     int tile, slot;
     xcd_tile_map(a.ntiles, slot, tile);
     const int ch = a.chan_list ? a.chan_list[slot] : slot;
+    const int mrow = MROW ? a.mask_row[ch] : ch;        // a scalar load ahead of the tile's loads (see osfir_kernel)
     const C *in = a.in + (long long)ch * a.in_stride;
     const C *hist = a.hist ? a.hist + (long long)ch * a.hist_stride : nullptr;
     const int g0 = a.off - P + tile * L;
@@ -770,7 +780,7 @@ __global__ __launch_bounds__(kOsfir8kThreads, 4) void osfir8k_kernel(OsfirArgs<d
     SF::run_at(x, image, FftRR<4096, false, C>::load_at(a.tw_fwd, j), j);
 
     // ---- mask: group A holds bins 2 (j + 256 r), group B the odd ones; the mask rows are [even | odd]
-    const C *mask = a.mask + (long long)ch * a.mask_stride + 4096 * g;
+    const C *mask = a.mask + (long long)mrow * a.mask_stride + 4096 * g;
 #pragma unroll
     for (int r = 0; r < 16; r++) {
         x[r] = cmul(x[r], mask[j + 256 * r]);
@@ -843,7 +853,7 @@ constexpr int osfir6k_lds_bytes()
     return kFft6kLdsBytes > m ? kFft6kLdsBytes : m;
 }
 
-template <bool METER, bool EGRESS>
+template <bool METER, bool EGRESS, bool MROW = false>
 __global__ __launch_bounds__(kOsfir6kThreads, 3) void osfir6k_kernel(OsfirArgs<double> a)
 {
     using C = double2;
@@ -853,6 +863,7 @@ __global__ __launch_bounds__(kOsfir6kThreads, 3) void osfir6k_kernel(OsfirArgs<d
     int tile, slot;
     xcd_tile_map(a.ntiles, slot, tile);
     const int ch = a.chan_list ? a.chan_list[slot] : slot;
+    const int mrow = MROW ? a.mask_row[ch] : ch;        // a scalar load ahead of the tile's loads (see osfir_kernel)
     const C *in = a.in + (long long)ch * a.in_stride;
     const C *hist = a.hist ? a.hist + (long long)ch * a.hist_stride : nullptr;
     const int g0 = a.off - P + tile * L;
@@ -883,7 +894,7 @@ __global__ __launch_bounds__(kOsfir6kThreads, 3) void osfir6k_kernel(OsfirArgs<d
     }
     Fft6144<false>::run(x, smem6k, Fft6144<false>::load(t), t);
 
-    const C *mask = a.mask + (long long)ch * a.mask_stride;
+    const C *mask = a.mask + (long long)mrow * a.mask_stride;
 #pragma unroll
     for (int r = 0; r < 16; r++) {
         x[r] = cmul(x[r], mask[t + TH * r]);

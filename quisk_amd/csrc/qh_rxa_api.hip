@@ -246,6 +246,70 @@ int qh_rxa_RXASetPassband(qh_rxa *h, int ch, double f_low, double f_high)
     return qh_rxa_RXANBPSetFreqs(h, ch, f_low, f_high);
 }
 
+// xfmd's de-emphasis and audio filters, per channel (fmd.c:278-384).  Each acts only on a changed value, as there; the design rows follow
+// at the next process call (Engine::fm_filters).  which: 0 the de-emphasis filter, 1 the audio filter.
+static void fm_set_nc(Engine &e, ChanCfg &c, int which, int nc)
+{
+    int &cur = which ? c.fm_nc_aud : c.fm_nc_de;
+    if (cur == nc) return;
+    cur = nc;
+    // setNc_fircore zeroes that filter's delay line (firmin.c:455-467): nothing long is held any more
+    (which ? c.fm_aud_flush : c.fm_de_flush) = true;
+    e.fc[which ? FC_AUD : FC_DE].chan[(size_t)(&c - e.cfg.data())].long_live = false;
+    e.fm_dirty = true;
+    if (!which) e.lists_dirty = true;       // the de-emphasis stage's channel pairs follow the designs
+}
+static void fm_set_mp(Engine &e, ChanCfg &c, int which, int mp)
+{
+    int &cur = which ? c.fm_mp_aud : c.fm_mp_de;
+    if (cur == mp) return;
+    cur = mp;                               // setMp_fircore: new masks, the line kept
+    e.fm_dirty = true;
+    if (!which) e.lists_dirty = true;
+}
+static int fm_nc_check(const qh_rxa *h, const char *who, int nc)
+{
+    if (nc < 1 || (nc & (nc - 1)) || nc > kLongNcMax || (h && nc < h->e.dsp_size))
+        return set_error(QH_ERR_INVALID, "%s: nc must be a power of two in [dsp_size, %d]", who, kLongNcMax);
+    return QH_OK;
+}
+int qh_rxa_SetRXAFMNCde(qh_rxa *h, int ch, int nc)
+{
+    if (int rc = fm_nc_check(h, "SetRXAFMNCde", nc)) return rc;
+    FOR_CH(h, ch, { fm_set_nc(h->e, c, 0, nc); });
+}
+int qh_rxa_SetRXAFMNCaud(qh_rxa *h, int ch, int nc)
+{
+    if (int rc = fm_nc_check(h, "SetRXAFMNCaud", nc)) return rc;
+    FOR_CH(h, ch, { fm_set_nc(h->e, c, 1, nc); });
+}
+int qh_rxa_SetRXAFMMPde(qh_rxa *h, int ch, int mp) { FOR_CH(h, ch, { fm_set_mp(h->e, c, 0, mp ? 1 : 0); }); }
+int qh_rxa_SetRXAFMMPaud(qh_rxa *h, int ch, int mp) { FOR_CH(h, ch, { fm_set_mp(h->e, c, 1, mp ? 1 : 0); }); }
+// SetRXAFMAFFilter (fmd.c:364-384): both filters designed again, both delay lines kept (setImpulse_fircore)
+int qh_rxa_SetRXAFMAFFilter(qh_rxa *h, int ch, double low, double high)
+{
+    if (!std::isfinite(low) || !std::isfinite(high)) return set_error(QH_ERR_INVALID, "SetRXAFMAFFilter: %g .. %g is not finite", low, high);
+    if (low <= 0.0) return set_error(QH_ERR_INVALID, "SetRXAFMAFFilter: low %g must be above 0 (the de-emphasis curve takes log10(high / low))", low);
+    if (high <= low) return set_error(QH_ERR_INVALID, "SetRXAFMAFFilter: high %g must be above low %g", high, low);
+    FOR_CH(h, ch, {
+        if (c.fm_f_low != low || c.fm_f_high != high) {
+            c.fm_f_low = low; c.fm_f_high = high;
+            h->e.fm_dirty = true;
+            h->e.lists_dirty = true;
+        }
+    });
+}
+// diagnostics: the design rows of the two filters on the device and the rows designed on the host since the engine was made
+int qh_rxa_debug_fm_rows(qh_rxa *h, int *de_rows, int *aud_rows, long long *designed)
+{
+    if (!h) return set_error(QH_ERR_INVALID, "null engine");
+    QH_RXA_LOCK(h);
+    if (de_rows) *de_rows = (int)h->e.fm_rows[0].size();
+    if (aud_rows) *aud_rows = (int)h->e.fm_rows[1].size();
+    if (designed) *designed = h->e.fm_designed;
+    return QH_OK;
+}
+
 int qh_rxa_RXASetNC(qh_rxa *h, int ch, int nc)
 {
     if (nc < 1 || (nc & (nc - 1)) || nc > kLongNcMax || (h && nc < h->e.dsp_size))
@@ -256,8 +320,7 @@ int qh_rxa_RXASetNC(qh_rxa *h, int ch, int nc)
         const size_t i = (size_t)(&c - h->e.cfg.data());
         if (c.nbp_nc != nc) { c.nbp_nc = nc; c.nbp_dirty = true; c.nbp_flush = true; c.snb_flush = true; fc[FC_NBP].chan[i].long_live = fc[FC_SNB].chan[i].long_live = false; }
         if (c.bp1_nc != nc) { c.bp1_nc = nc; c.bp1_dirty = true; c.bp1_flush = true; fc[FC_BP1].chan[i].long_live = false; }
-        if (c.fm_nc != nc) fc[FC_DE].chan[i].long_live = fc[FC_AUD].chan[i].long_live = false;
-        c.fm_nc = nc;                           // SetRXAFMNCde / SetRXAFMNCaud, wdsp/RXA.c:943-944
+        fm_set_nc(h->e, c, 0, nc); fm_set_nc(h->e, c, 1, nc);       // SetRXAFMNCde / SetRXAFMNCaud, wdsp/RXA.c:943-944
         c.fmsq_nc = nc;                         // SetRXAFMSQNC, wdsp/RXA.c:942
         if (c.eqp_nc != nc) { c.eqp_nc = nc; c.eqp_dirty = true; c.eqp_flush = true; }      // SetRXAEQNC, wdsp/RXA.c:941
     });
@@ -343,14 +406,13 @@ int qh_rxa_RXANBPSetNotchesRun(qh_rxa *h, int ch, int run) { FOR_CH(h, ch, { run
 int qh_rxa_RXANBPSetWindow(qh_rxa *h, int ch, int wintype) { FOR_CH(h, ch, { if (c.nbp_wintype != wintype) { c.nbp_wintype = wintype; c.nbp_dirty = true; } }); }
 int qh_rxa_RXANBPSetAutoIncrease(qh_rxa *h, int ch, int autoincr) { FOR_CH(h, ch, { if (c.autoincr != autoincr) { c.autoincr = autoincr; if (c.fnfrun) c.nbp_dirty = true; } }); }
 
-// RXASetMP (wdsp/RXA.c:948-958): minimum-phase impulse responses in every fircore of the chain.  nbp0 and bp1 have
-// per-channel masks; the FM de-emphasis / audio masks are shared by the channels of an engine and follow the
-// most recent call.
+// RXASetMP (wdsp/RXA.c:948-958): minimum-phase impulse responses in every fircore of the channel's chain.
 int qh_rxa_RXASetMP(qh_rxa *h, int ch, int mp)
 {
     mp = mp ? 1 : 0;
     FOR_CH(h, ch, {
         if (c.mp != mp) { c.mp = mp; c.nbp_dirty = true; c.bp1_dirty = true; c.demod_dirty = true; }
+        fm_set_mp(h->e, c, 0, mp); fm_set_mp(h->e, c, 1, mp);       // SetRXAFMMPde / SetRXAFMMPaud, wdsp/RXA.c:956-957
         c.fmsq_mp = mp;                         // SetRXAFMSQMP, wdsp/RXA.c:955
         if (c.eqp_mp != mp) { c.eqp_mp = mp; c.eqp_dirty = true; }      // SetRXAEQMP, wdsp/RXA.c:954
     });

@@ -856,6 +856,12 @@ void SetRXASSQLTauUnMute(int channel, double tau_unmute) { WDSP_SETTER(qh_rxa_Se
 // the FM squelch, wdsp/fmsq.c:235-279
 void SetRXAFMSQRun(int channel, int run) { WDSP_SETTER(qh_rxa_SetRXAFMSQRun(L.c->eng, 0, run)); }
 void SetRXAFMSQThreshold(int channel, double threshold) { WDSP_SETTER(qh_rxa_SetRXAFMSQThreshold(L.c->eng, 0, threshold)); }
+// xfmd's de-emphasis and audio filters (wdsp/fmd.c:278-384)
+void SetRXAFMAFFilter(int channel, double low, double high) { WDSP_SETTER(qh_rxa_SetRXAFMAFFilter(L.c->eng, 0, low, high)); }
+void SetRXAFMNCde(int channel, int nc) { WDSP_SETTER(qh_rxa_SetRXAFMNCde(L.c->eng, 0, nc)); }
+void SetRXAFMMPde(int channel, int mp) { WDSP_SETTER(qh_rxa_SetRXAFMMPde(L.c->eng, 0, mp)); }
+void SetRXAFMNCaud(int channel, int nc) { WDSP_SETTER(qh_rxa_SetRXAFMNCaud(L.c->eng, 0, nc)); }
+void SetRXAFMMPaud(int channel, int mp) { WDSP_SETTER(qh_rxa_SetRXAFMMPaud(L.c->eng, 0, mp)); }
 void SetRXAFMSQNC(int channel, int nc) { WDSP_SETTER(qh_rxa_SetRXAFMSQNC(L.c->eng, 0, nc)); }
 void SetRXAFMSQMP(int channel, int mp) { WDSP_SETTER(qh_rxa_SetRXAFMSQMP(L.c->eng, 0, mp)); }
 // the equalizer, wdsp/eq.c:242-377

@@ -92,6 +92,16 @@ def load():
         f = getattr(L, n)
         f.argtypes = a
         f.restype = None
+    # xfmd's filter setters (wdsp/fmd.c:278-384): the engine's, the WDSP names, and the design rows' diagnostic
+    for n, a in (("SetRXAFMAFFilter", [i, d, d]), ("SetRXAFMNCde", [i, i]), ("SetRXAFMMPde", [i, i]), ("SetRXAFMNCaud", [i, i]), ("SetRXAFMMPaud", [i, i])):
+        f = getattr(L, "qh_rxa_" + n)
+        f.argtypes = [vp] + a
+        f.restype = i
+        f = getattr(L, n)
+        f.argtypes = a
+        f.restype = None
+    L.qh_rxa_debug_fm_rows.argtypes = [vp, C.POINTER(i), C.POINTER(i), C.POINTER(ll)]
+    L.qh_rxa_debug_fm_rows.restype = i
     L.qh_rxa_debug_eqp.argtypes = [vp, i, C.POINTER(d), i]
     L.qh_rxa_debug_eqp.restype = i
     L.qh_rxa_debug_fmsq.argtypes = [vp, i, C.POINTER(d), i]

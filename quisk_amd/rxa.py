@@ -24,6 +24,7 @@ _SETTERS = ("SetRXAMode", "RXASetNC", "SetRXAShiftRun", "RXANBPSetRun", "SetRXAB
             "SetRXAmpeakNpeaks", "SetRXAmpeakFilEnable", "SetRXAmpeakFilFreq", "SetRXAmpeakFilBw", "SetRXAmpeakFilGain",
             "SetRXASSQLRun", "SetRXASSQLThreshold", "SetRXASSQLTauMute", "SetRXASSQLTauUnMute",
             "SetRXAFMSQRun", "SetRXAFMSQThreshold", "SetRXAFMSQNC", "SetRXAFMSQMP",
+            "SetRXAFMAFFilter", "SetRXAFMNCde", "SetRXAFMMPde", "SetRXAFMNCaud", "SetRXAFMMPaud",
             "SetRXAEQRun", "SetRXAEQNC", "SetRXAEQMP", "SetRXAEQProfile", "SetRXAEQCtfmode", "SetRXAEQWintype", "SetRXAGrphEQ", "SetRXAGrphEQ10")
 # the setters that take arrays: (element type, position among the arguments behind the channel)
 _ARRAYS = {"SetRXAEQProfile": ((C.c_double, 1), (C.c_double, 2)), "SetRXAGrphEQ": ((C.c_int, 0),), "SetRXAGrphEQ10": ((C.c_int, 0),)}
@@ -226,6 +227,13 @@ class RxaEngine:
         n = self._L.qh_rxa_debug_fmsq(self._h, ch, buf, 5)
         check(n if n < 0 else 0)
         return (buf[0], buf[1], int(buf[2]), int(buf[3]), int(buf[4])) if n == 5 else None
+
+    def debug_fm_rows(self):
+        """diagnostics: (de-emphasis rows, audio rows, rows designed so far): the mask rows xfmd's two filters hold on the device, one per
+        distinct design among the running FM channels, and how many designs the host has made since the engine was made or rebuilt"""
+        de, au, n = C.c_int(0), C.c_int(0), C.c_longlong(0)
+        check(self._L.qh_rxa_debug_fm_rows(self._h, C.byref(de), C.byref(au), C.byref(n)))
+        return de.value, au.value, n.value
 
     def debug_eqp(self, ch, max_nc=4096):
         """diagnostics: the complex taps behind the mask channel ch's equalizer last got (nc of them, scale 1 / (2 dsp_size) as WDSP's
