@@ -67,6 +67,12 @@ long long qh_rxa_graph_launches(const qh_rxa *e);                /* calls served
  * qh_rxa_band_tile: the size in use. */
 int qh_rxa_set_band_tile(qh_rxa *e, int nfft);
 int qh_rxa_band_tile(const qh_rxa *e);
+/* Form of xsnba.  0 (default): one kernel per call with both of the blanker's resamplers inside its block loop where that kernel can
+ * run (dsp_rate up to 48000 and dsp_size up to 1024); elsewhere, and everywhere with 1: three passes -- dsp_rate -> 12 kHz for the
+ * whole call, the frames on 12 kHz rows, 12 kHz -> dsp_rate.  The results agree in every bit and the state is one
+ * layout, so the form may change between calls; kept selectable for the comparison.  qh_rxa_snba_form: the value set. */
+int qh_rxa_set_snba_form(qh_rxa *e, int form);
+int qh_rxa_snba_form(const qh_rxa *e);
 
 /* Per-channel setters; `ch` indexes the batch, or -1 for every channel.  Same meaning as the WDSP
  * export of the same name (cited in section 2).  They take effect at the next qh_rxa_process call,
@@ -115,7 +121,9 @@ int qh_rxa_SetRXAEMNRtrainT2(qh_rxa *e, int ch, double v);
 /* xamsqcap / xamsq, the AM squelch (wdsp/amsq.c:119-192; create_amsq arguments RXA.c:158-172) */
 int qh_rxa_SetRXAAMSQRun(qh_rxa *e, int ch, int run);
 /* SNBA, wdsp/snb.c:579-593 (run; also switches bpsnba and bp1 as RXA.c:800-917) and :660-694 (pass band of its output resampler;
- * RXASetPassband calls it).  dsp_rate 12000 / 24000 / 48000, dsp_size <= 1024. */
+ * RXASetPassband calls it).  dsp_rate 12000 x 2^k, k = 0 .. 5 (12000 ... 384000: calc_snba's whole ratios to its 12 kHz internal rate),
+ * dsp_size a multiple of dsp_rate / 12000 and at most 4096; anything else is refused when the blanker is first needed, or by the
+ * rate / size setters below while a channel runs it. */
 int qh_rxa_SetRXASNBARun(qh_rxa *e, int ch, int run);
 int qh_rxa_SetRXASNBAOutputBandwidth(qh_rxa *e, int ch, double flow, double fhigh);
 /* the blanker's tuning, wdsp/snb.c:604-658 (defaults: create_rxa's 64, 2, 8.0, 20.0, 10, 2, 2, 0.5; SetRXASNBAovrlp is not provided) */

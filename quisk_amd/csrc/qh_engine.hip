@@ -606,6 +606,8 @@ int Engine::process_chain(const double *d_in, long long in_stride, double *d_out
     if (k.long_mode) if (int rc = long_buffers()) return rc;
     if (int rc = refresh_ap(k)) return rc;
     if (int rc = refresh_ssql(k)) return rc;
+    // (snba_state: a linear call keeps the lists of the last per-mode one, and that one may have ended in snba_alloc's refusal, before any ratio was set)
+    if (lists[L_SNBA].n && snba_state && snba_rows()) if (int rc = grow(snba_r12, snba_r12_cap, buf_cap / snba_prm.ratio, 2 * (long long)nch)) return rc;   // the blanker's 12 kHz rows
     if (fq_list.n) if (int rc = grow(fq_noise, fq_noise_cap, buf_cap, nch)) return rc;     // the noise filter's output rows
     if (k.taps && tap_lists[0].n) if (int rc = grow(snd_rows, snd_cap, buf_cap, nch)) return rc;      // the sender's float rows
     snd_n = k.taps && tap_lists[0].n ? k.n_mid : 0;
@@ -1088,8 +1090,28 @@ int Engine::run_snba(const ChainCall &k)
         QH_HIP(hipStreamSynchronize(stream));
         snba_tune_dirty = false;
     }
-    hipLaunchKernelGGL(snba_kernel, dim3((unsigned)lists[L_SNBA].n), dim3(64), 0, stream, k.cur, buf_cap, k.nblk, dsp_size, lists[L_SNBA].dev, snba_prm,
-                       snba_hin, snba_hout, snba_state, snba_idx, snba_scratch, (const SnbaTune *)snba_tune);
+    const SnbaParam &q = snba_prm;
+    const unsigned n = (unsigned)lists[L_SNBA].n;
+    const int *list = lists[L_SNBA].dev;
+    if (!snba_rows()) {
+        hipLaunchKernelGGL(snba_kernel<false>, dim3(n), dim3(64), 0, stream, k.cur, buf_cap, k.nblk, dsp_size, list, q, snba_hin, snba_hout,
+                           snba_state, snba_idx, snba_scratch, (const SnbaTune *)snba_tune, (const double *)nullptr, (double *)nullptr, 0LL);
+        return QH_OK;
+    }
+    // the three passes: dsp_rate -> 12 kHz for the whole call, the frames on the 12 kHz rows, 12 kHz -> dsp_rate; each resampler's
+    // history is written behind its pass, the input one's before the last pass overwrites the rows it is taken from
+    const int n12 = k.nblk * q.isize, T = snba_decim_T(q.ratio), hin = q.cpp_in - 1, hout = q.cpp_out - 1;
+    double *r_in = snba_r12, *r_out = snba_r12 + (long long)nch * snba_r12_cap;
+    hipLaunchKernelGGL(snba_decim_kernel, dim3((unsigned)((n12 + T - 1) / T), n), dim3((unsigned)T), (size_t)snba_decim_lds_doubles(q.ratio, T) * sizeof(double), stream,
+                       (const double2 *)k.cur, buf_cap, n12, list, q, (const double *)snba_hin, (const double *)snba_state, r_in, snba_r12_cap);
+    if (hin) hipLaunchKernelGGL(snba_hist_kernel, dim3(n), dim3(256), (size_t)hin * sizeof(double), stream, (const double *)reinterpret_cast<double *>(k.cur),
+                                2 * buf_cap, 2, (int)k.n_mid, list, snba_state, q.state_doubles, q.off_rin, hin);
+    hipLaunchKernelGGL(snba_kernel<true>, dim3(n), dim3(64), 0, stream, k.cur, buf_cap, k.nblk, dsp_size, list, q, snba_hin, snba_hout,
+                       snba_state, snba_idx, snba_scratch, (const SnbaTune *)snba_tune, (const double *)r_in, r_out, snba_r12_cap);
+    hipLaunchKernelGGL(snba_interp_kernel, dim3((unsigned)((k.n_mid + 255) / 256), n), dim3(256), 0, stream, k.cur, buf_cap, n12, list, q,
+                       (const double *)snba_hout, (const double *)snba_state, (const double *)r_out, snba_r12_cap);
+    if (hout) hipLaunchKernelGGL(snba_hist_kernel, dim3(n), dim3(256), (size_t)hout * sizeof(double), stream, (const double *)r_out, snba_r12_cap, 1, n12, list,
+                                 snba_state, q.state_doubles, q.off_rout, hout);
     return QH_OK;
 }
 

@@ -402,6 +402,16 @@ struct Engine {
     int snba_ovrlp = 4;                 // create_rxa's overlap (RXA.c:244): incr = xsize / 4
     void snba_plan(int ovrlp);
     int snba_set_ovrlp(int ovrlp);
+    // The blanker's two forms (qh_snba.hpp).  qh_rxa_set_snba_form: 0 = the single kernel where it can run (dsp_rate up to 48 kHz and
+    // dsp_size up to 1024) and the three passes elsewhere, 1 = the three passes everywhere.  The state is one layout for both, so the
+    // form may change between calls.  snba_r12: the passes' 12 kHz rows, [2][nch][snba_r12_cap] (into the frames | out of them).
+    int snba_form = 0;
+    double *snba_r12 = nullptr;
+    long long snba_r12_cap = 0;
+    bool snba_rows() const { return snba_form == 1 || snba_prm.ratio > kSnbFusedMaxRatio || dsp_size > kSnbFusedMaxDsp; }
+    // the dsp_rate / dsp_size pairs the blanker takes: 12000 * 2^k (k = 0 .. 5), the size a multiple of the ratio and at most 4096
+    static bool snba_accepts(int rate, int size);
+    static const char *snba_accepted() { return "SNBA: dsp_rate 12000, 24000, 48000, 96000, 192000 or 384000 and dsp_size a multiple of dsp_rate / 12000, up to 4096"; }
     EmnrParam emnr_prm{};
     EmnrChan *emnr_chan = nullptr;
     EmnrScalars *emnr_scal = nullptr;

@@ -1122,14 +1122,21 @@ int Engine::snba_set_ovrlp(int ovrlp)
     return QH_OK;
 }
 
-// calc_emnr (wdsp/emnr.c:240-497) with create_rxa's arguments (RXA.c:319-332): parameters, window, start values of every array
+// What calc_snba's integer divisions (snb.c:33-36) leave consistent: a whole ratio to the 12 kHz internal rate that the kernels are made
+// for (1 .. kSnbMaxRatio, powers of two) and a block the ratio divides, so that isize * ratio is dsp_size.
+bool Engine::snba_accepts(int rate, int size)
+{
+    if (rate < 12000 || rate % 12000) return false;
+    const int ratio = rate / 12000;
+    return ratio <= kSnbMaxRatio && (ratio & (ratio - 1)) == 0 && size > 0 && size <= kSnbMaxDsp && size % ratio == 0;
+}
+
+// calc_snba (wdsp/snb.c:31-66) with create_rxa's arguments (RXA.c:237-255): parameters, both resamplers' taps, the state of every channel
 int Engine::snba_alloc()
 {
     // calc_snba, snb.c:31-66, with create_rxa's arguments (RXA.c:237-255)
     SnbaParam &q = snba_prm;
-    if (dsp_rate % 12000 || (dsp_rate / 12000 != 1 && dsp_rate / 12000 != 2 && dsp_rate / 12000 != 4) || dsp_size > kSnbMaxDsp ||
-        dsp_size % (dsp_rate / 12000))
-        return set_error(QH_ERR_UNSUPPORTED, "SNBA: dsp_rate 12000, 24000 or 48000 and dsp_size up to %d", kSnbMaxDsp);
+    if (!snba_accepts(dsp_rate, dsp_size)) return set_error(QH_ERR_UNSUPPORTED, "%s", snba_accepted());
     q.ratio = dsp_rate / 12000;
     q.isize = dsp_size / q.ratio;
     q.cpp_in = q.ratio > 1 ? 140 * q.ratio + 1 : 1;
@@ -1162,6 +1169,7 @@ int Engine::snba_alloc()
     return QH_OK;
 }
 
+// calc_emnr (wdsp/emnr.c:240-497) with create_rxa's arguments (RXA.c:319-332): parameters, window, start values of every array
 int Engine::emnr_alloc()
 {
     if (dsp_size > kEmnrIncr) return set_error(QH_ERR_UNSUPPORTED, "EMNR: dsp_size up to %d", kEmnrIncr);
@@ -1817,9 +1825,7 @@ int Engine::set_rates(int new_in, int new_dsp, int new_out, int new_size)
         const int nc = std::min({ c.nbp_nc, c.bp1_nc, c.fm_nc_de, c.fm_nc_aud, c.fmsq_nc, c.eqp_nc });
         if (new_size > nc) return set_error(QH_ERR_UNSUPPORTED, "dsp_size %d above nc %d of channel %d: size must be <= nc (wdsp/nbp.c:308)", new_size, nc, (int)(&c - cfg.data()));
         if (c.emnr_run && new_size > kEmnrIncr) return set_error(QH_ERR_UNSUPPORTED, "EMNR: dsp_size up to %d", kEmnrIncr);
-        if (c.snba_run && (new_dsp % 12000 || (new_dsp / 12000 != 1 && new_dsp / 12000 != 2 && new_dsp / 12000 != 4) || new_size > kSnbMaxDsp ||
-                           new_size % (new_dsp / 12000)))
-            return set_error(QH_ERR_UNSUPPORTED, "SNBA: dsp_rate 12000, 24000 or 48000 and dsp_size up to %d", kSnbMaxDsp);
+        if (c.snba_run && !snba_accepts(new_dsp, new_size)) return set_error(QH_ERR_UNSUPPORTED, "%s", snba_accepted());
     }
     if (disp && qh_ana_buff_size(disp) != new_size)
         return set_error(QH_ERR_INVALID, "the attached display bank has buff_size %d: detach it before dsp_size becomes %d", qh_ana_buff_size(disp), new_size);
@@ -1923,13 +1929,13 @@ int Engine::rebuild(int new_in, int new_dsp, int new_out, int new_size, int new_
     std::vector<ChanCfg> keep_cfg;
     for (const ChanCfg &c : cfg) keep_cfg.push_back(settings_of(c, new_dsp));
     // the engine-wide settings: one Engine member set through the C ABI outside cfg that is not listed here is lost by a rebuild
-    static_assert(sizeof(Engine) == 9336, "Engine changed: see to Engine::rebuild's Wide and carried state, then update the size");
+    static_assert(sizeof(Engine) == 9360, "Engine changed: see to Engine::rebuild's Wide and carried state, then update the size");
     struct Wide {
         int device, nch; hipStream_t stream; bool own_stream; unsigned long long epoch;
-        bool graph_on; long long graph_launches; bool timing, meters_on; int band_tile_pref, snba_ovrlp; std::vector<SnbaTune> snba_tune_h;
+        bool graph_on; long long graph_launches; bool timing, meters_on; int band_tile_pref, snba_ovrlp, snba_form; std::vector<SnbaTune> snba_tune_h;
         qh_ana *disp; int disp_ss, pll_check_only, agc_form;
         bool emnr_tables; std::vector<double> h_GG, h_GGS, h_zeta; std::vector<int> h_zeta_true; double h_zrange[4];
-    } was{ device, nch, stream, own_stream, epoch, graph_on, graph_launches, timing, meters_on, band_tile_pref, snba_ovrlp, snba_tune_h,
+    } was{ device, nch, stream, own_stream, epoch, graph_on, graph_launches, timing, meters_on, band_tile_pref, snba_ovrlp, snba_form, snba_tune_h,
            disp, disp_ss, pll_check_only, agc_form, emnr_tables, std::move(h_GG), std::move(h_GGS), std::move(h_zeta), std::move(h_zeta_true),
            { h_zrange[0], h_zrange[1], h_zrange[2], h_zrange[3] } };
     own_stream = false;                     // the stream stays: callers hold it (qh_rxa_stream)
@@ -1940,6 +1946,7 @@ int Engine::rebuild(int new_in, int new_dsp, int new_out, int new_size, int new_
     int rc = init();
     graph_on = was.graph_on; graph_launches = was.graph_launches; timing = was.timing; meters_on = was.meters_on;
     band_tile_pref = was.band_tile_pref; snba_ovrlp = was.snba_ovrlp; snba_tune_h = was.snba_tune_h; snba_tune_dirty = true;
+    snba_form = was.snba_form;
     disp = was.disp; disp_ss = was.disp_ss; pll_check_only = was.pll_check_only; agc_form = was.agc_form;
     emnr_tables = was.emnr_tables; h_GG = std::move(was.h_GG); h_GGS = std::move(was.h_GGS); h_zeta = std::move(was.h_zeta); h_zeta_true = std::move(was.h_zeta_true);
     std::copy(was.h_zrange, was.h_zrange + 4, h_zrange);

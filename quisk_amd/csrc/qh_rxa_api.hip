@@ -817,6 +817,16 @@ int qh_rxa_set_band_tile(qh_rxa *h, int nfft)
 }
 int qh_rxa_band_tile(const qh_rxa *h) { return h ? h->e.bnfft : 0; }
 
+int qh_rxa_set_snba_form(qh_rxa *h, int form)
+{
+    if (!h || (form != 0 && form != 1)) return set_error(QH_ERR_INVALID, "qh_rxa_set_snba_form: 0 (default) or 1 (the three passes wherever they can run)");
+    QH_RXA_LOCK(h);
+    h->e.snba_form = form;
+    h->e.epoch++;                   // a captured launch sequence runs the other form's kernels; the state is one layout for both
+    return QH_OK;
+}
+int qh_rxa_snba_form(const qh_rxa *h) { return h ? h->e.snba_form : 0; }
+
 // The same chain fed with wire-format samples: the front kernel decodes them in its load.
 int qh_rxa_process_packed(qh_rxa *h, const void *d_src, long long src_bytes, const qh_iq_format *fmt, long long chan_stride,
                           double *d_out, long long out_stride, int nblk)

@@ -9,6 +9,14 @@
 // Every sum therefore has the reference's operation order (fp contraction off), which keeps the threshold decisions of the
 // detector identical.  The structured matrices A1 / A2 of xHat (snb.c:265-304) are never built: their entries are read off
 // the predictor `a` while P1 = A1'A2 is formed; the Toeplitz inverse (up to xsize x xsize) lives in a per-channel scratch.
+//
+// Two forms.  The single kernel (snba_kernel<false>) keeps both polyphase resamplers inside the serial block loop with their
+// windows in LDS: dsp_rate up to 48 kHz and dsp_size up to kSnbFusedMaxDsp.  The three-pass form takes them out, since they are
+// plain FIRs with no feedback from the frames: snba_decim_kernel makes the 12 kHz row of every listed channel for the whole call,
+// one thread per output; snba_kernel<true> runs the frames from that row into a second 12 kHz row, block by block with the same
+// ring indices; snba_interp_kernel writes the channel's row at the DSP rate, one thread per output.  snba_hist_kernel leaves
+// each resampler's history behind its pass.  Every sum has the same terms in the same order in both forms, so they agree in
+// every bit.  The second form runs ratios up to 32 (dsp_rate 384 kHz) and dsp_size up to kSnbMaxDsp.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "qh_wave.hpp"
@@ -17,8 +25,11 @@ namespace qh {
 
 constexpr int kSnbX = 256;          // xsize, RXA.c:245
 constexpr int kSnbMaxImp = 256;     // MAXIMP, snb.c:29
-constexpr int kSnbMaxDsp = 1024;    // dsp_size limit of this kernel
-constexpr int kSnbMaxCppIn = 561;   // 140 * (dsp_rate / 12000) + 1 with dsp_rate <= 48000
+constexpr int kSnbMaxDsp = 4096;    // dsp_size limit of the blanker (the three-pass form)
+constexpr int kSnbMaxRatio = 32;    // dsp_rate / 12000 up to 384 kHz (cpp_in = 140 * ratio + 1; the state's off_rin holds cpp_in - 1 samples)
+constexpr int kSnbFusedMaxDsp = 1024;       // the single kernel: dsp_size and ...
+constexpr int kSnbFusedMaxRatio = 4;        // ... dsp_rate / 12000 its LDS windows are made for
+constexpr int kSnbFusedMaxCppIn = 140 * kSnbFusedMaxRatio + 1;
 
 struct SnbaParam {
     int ratio, isize, incr, iasize, oasize, init_oaoutidx, cpp_in, cpp_out;     // calc_snba, snb.c:31-66
@@ -36,13 +47,18 @@ struct SnbaLds {
     double xb[2 * kSnbX];           // xbase | xaux
     double savex[kSnbX], v[kSnbX], vpwr[kSnbX], a[kSnbX], r[kSnbX + 1], z[kSnbX + 1], p2[kSnbX], xout[kSnbX], y[kSnbX], vv[kSnbX];
     double merit[kSnbMaxImp];
-    double sin_[kSnbMaxCppIn - 1 + kSnbMaxDsp];     // input resampler: history | block (real parts)
-    double sob[140 + kSnbMaxDsp];                   // output resampler: history | 12 kHz block
     double scal[4];
     int det[kSnbX], unfixed[kSnbX], bimp[kSnbMaxImp], limp[kSnbMaxImp], bef[kSnbMaxImp + 1], aft[kSnbMaxImp], popt[kSnbMaxImp],
         nextl[kSnbMaxImp];
     int nimp, next;
 };
+
+// the single kernel's resampler windows; the three-pass form's frame kernel has none
+template <bool ON> struct SnbaRsLds {
+    double sin_[kSnbFusedMaxCppIn - 1 + kSnbFusedMaxDsp];   // input resampler: history | block (real parts)
+    double sob[140 + kSnbFusedMaxDsp];                      // output resampler: history | 12 kHz block
+};
+template <> struct SnbaRsLds<false> { double sin_[1], sob[1]; };
 
 // asolve, lmath.c:96-127: x has at least asize valid samples in front of it
 static __device__ void snba_asolve(SnbaLds &s, int xsize, int asize, const double *x, int lane)
@@ -345,13 +361,18 @@ static __global__ __launch_bounds__(NT) void copy_rows_kernel(const double2 *src
     for (int i = blockIdx.x * NT + threadIdx.x; i < n; i += gridDim.x * NT) dst[o + i] = src[o + i];
 }
 
-// xsnba (snb.c:539-571) over nblk blocks of dsp_size samples, in place on the channel's row of buf
+// xsnba (snb.c:539-571) over nblk blocks of dsp_size samples, in place on the channel's row of buf.  ROWS: the three-pass form's
+// frame kernel -- the two resamplers run in passes of their own around it (below), and a block here takes its isize samples from the
+// channel's 12 kHz row in12 and leaves isize samples in out12 (both of stride12 doubles per channel), with the same ring indices.
+template <bool ROWS>
 static __global__ __launch_bounds__(64) void snba_kernel(double2 *buf, long long stride, int nblk, int dsp_size, const int *chan_list,
                                                          SnbaParam q, const double *h_in, const double *h_out, double *state,
-                                                         SnbaIdx *idx, double *scratch, const SnbaTune *tune)
+                                                         SnbaIdx *idx, double *scratch, const SnbaTune *tune,
+                                                         const double *in12, double *out12, long long stride12)
 {
 #pragma clang fp contract(off)
     __shared__ SnbaLds s;
+    __shared__ SnbaRsLds<!ROWS> rs;
     const int ch = chan_list[blockIdx.x], lane = threadIdx.x;
     {
         const SnbaTune t = tune[ch];
@@ -364,31 +385,39 @@ static __global__ __launch_bounds__(64) void snba_kernel(double2 *buf, long long
     const int hin = q.cpp_in - 1, hout = q.cpp_out - 1;
     SnbaIdx ix = idx[ch];
     for (int i = lane; i < 2 * kSnbX; i += 64) s.xb[i] = st[i];
-    for (int i = lane; i < hin; i += 64) s.sin_[i] = st[q.off_rin + i];
-    for (int i = lane; i < hout; i += 64) s.sob[i] = st[q.off_rout + i];
+    if (!ROWS) {
+        for (int i = lane; i < hin; i += 64) rs.sin_[i] = st[q.off_rin + i];
+        for (int i = lane; i < hout; i += 64) rs.sob[i] = st[q.off_rout + i];
+    }
     __syncthreads();
     double *inacc = st + q.off_inacc, *outacc = st + q.off_outacc;
     for (int blk = 0; blk < nblk; blk++) {
         double2 *p = row + (long long)blk * dsp_size;
-        // xresample (inresamp): L = 1, M = ratio; out[m] = sum_j h[j] x[m * ratio - j]
-        for (int i = lane; i < dsp_size; i += 64) s.sin_[hin + i] = p[i].x;
-        __syncthreads();
-        for (int m = lane; m < q.isize; m += 64) {
-            double acc;
-            if (q.ratio == 1) acc = s.sin_[hin + m];
-            else {
-                acc = 0.0;
-                const double *xp = s.sin_ + hin + m * q.ratio;
-                for (int j = 0; j < q.cpp_in; j++) acc += h_in[j] * xp[-j];
+        if (ROWS) {
+            const double *p12 = in12 + (long long)ch * stride12 + (long long)blk * q.isize;
+            for (int m = lane; m < q.isize; m += 64) inacc[(ix.iainidx + m) % q.iasize] = p12[m];
+            __syncthreads();
+        } else {
+            // xresample (inresamp): L = 1, M = ratio; out[m] = sum_j h[j] x[m * ratio - j]
+            for (int i = lane; i < dsp_size; i += 64) rs.sin_[hin + i] = p[i].x;
+            __syncthreads();
+            for (int m = lane; m < q.isize; m += 64) {
+                double acc;
+                if (q.ratio == 1) acc = rs.sin_[hin + m];
+                else {
+                    acc = 0.0;
+                    const double *xp = rs.sin_ + hin + m * q.ratio;
+                    for (int j = 0; j < q.cpp_in; j++) acc += h_in[j] * xp[-j];
+                }
+                inacc[(ix.iainidx + m) % q.iasize] = acc;
             }
-            inacc[(ix.iainidx + m) % q.iasize] = acc;
-        }
-        __syncthreads();
-        for (int base = 0; base < hin; base += 64) {         // slide the input history down by one block
-            const double keep = base + lane < hin ? s.sin_[dsp_size + base + lane] : 0.0;
             __syncthreads();
-            if (base + lane < hin) s.sin_[base + lane] = keep;
-            __syncthreads();
+            for (int base = 0; base < hin; base += 64) {         // slide the input history down by one block
+                const double keep = base + lane < hin ? rs.sin_[dsp_size + base + lane] : 0.0;
+                __syncthreads();
+                if (base + lane < hin) rs.sin_[base + lane] = keep;
+                __syncthreads();
+            }
         }
         ix.iainidx = (ix.iainidx + q.isize) % q.iasize;
         ix.nsamps += q.isize;
@@ -409,16 +438,23 @@ static __global__ __launch_bounds__(64) void snba_kernel(double2 *buf, long long
                 __syncthreads();
             }
         }
-        for (int i = lane; i < q.isize; i += 64) s.sob[hout + i] = outacc[(ix.oaoutidx + i) % q.oasize];
+        if (ROWS) {
+            double *p12 = out12 + (long long)ch * stride12 + (long long)blk * q.isize;
+            for (int i = lane; i < q.isize; i += 64) p12[i] = outacc[(ix.oaoutidx + i) % q.oasize];
+            ix.oaoutidx = (ix.oaoutidx + q.isize) % q.oasize;
+            __syncthreads();
+            continue;
+        }
+        for (int i = lane; i < q.isize; i += 64) rs.sob[hout + i] = outacc[(ix.oaoutidx + i) % q.oasize];
         ix.oaoutidx = (ix.oaoutidx + q.isize) % q.oasize;
         __syncthreads();
         // xresample (outresamp): L = ratio, M = 1; out[i * ratio + ph] = sum_j h[ph][j] o[i - j]
         for (int n = lane; n < dsp_size; n += 64) {
             double acc;
-            if (q.ratio == 1) acc = s.sob[hout + n];
+            if (q.ratio == 1) acc = rs.sob[hout + n];
             else {
                 const int i = n / q.ratio, ph = n - i * q.ratio;
-                const double *hp = ho + ph * q.cpp_out, *op = s.sob + hout + i;
+                const double *hp = ho + ph * q.cpp_out, *op = rs.sob + hout + i;
                 acc = 0.0;
                 for (int j = 0; j < q.cpp_out; j++) acc += hp[j] * op[-j];
             }
@@ -426,16 +462,121 @@ static __global__ __launch_bounds__(64) void snba_kernel(double2 *buf, long long
         }
         __syncthreads();
         for (int base = 0; base < hout; base += 64) {
-            const double keep = base + lane < hout ? s.sob[q.isize + base + lane] : 0.0;
+            const double keep = base + lane < hout ? rs.sob[q.isize + base + lane] : 0.0;
             __syncthreads();
-            if (base + lane < hout) s.sob[base + lane] = keep;
+            if (base + lane < hout) rs.sob[base + lane] = keep;
             __syncthreads();
         }
     }
     for (int i = lane; i < 2 * kSnbX; i += 64) st[i] = s.xb[i];
-    for (int i = lane; i < hin; i += 64) st[q.off_rin + i] = s.sin_[i];
-    for (int i = lane; i < hout; i += 64) st[q.off_rout + i] = s.sob[i];
+    if (!ROWS) {
+        for (int i = lane; i < hin; i += 64) st[q.off_rin + i] = rs.sin_[i];
+        for (int i = lane; i < hout; i += 64) st[q.off_rout + i] = rs.sob[i];
+    }
     if (lane == 0) idx[ch] = ix;
+}
+
+// ---- the three-pass form's resamplers: xresample (wdsp/resample.c:120-157) as plain FIRs over the whole call ------------------
+// A sample g of a pass's input, counted from the first one of this call: the call's own samples from g = 0 on, and the pass's saved
+// history (the last `hist` samples of the calls before, oldest first) in front of them.
+
+// outputs per block of the decimation pass: T * ratio = 2048 samples of window beside the cpp_in - 1 of history, at least one
+// wavefront and at most four (ratio 32: 64 outputs, 6733 doubles = 53 KB of LDS with the padding below; ratio 16: 128, 36 KB; ratio 8: 256, 28 KB)
+static inline int snba_decim_T(int ratio) { const int t = 2048 / ratio; return t < 64 ? 64 : t > 256 ? 256 : t; }
+
+// inresamp: L = 1, M = ratio.  y12[m] = sum_{j = 0 .. cpp_in - 1} h_in[j] x_re[m * ratio - j] for the n12 = nblk * isize outputs of the
+// call; block (x, y) takes outputs x * T .. x * T + T - 1 (T = blockDim.x) of listed channel y, their window of T * ratio + cpp_in - 1
+// real parts in LDS.  The taps are one array for all channels, read at a wave-uniform index.  The history is only read here.
+// The lanes of a wave read samples `ratio` doubles apart, which at ratio 32 is one LDS bank for all of them: window sample w is kept at
+// w + w / ratio, one double of padding per `ratio` samples (ratio is a power of two), so that the lanes are ratio + 1 doubles apart.
+static inline int snba_decim_lds_doubles(int ratio, int T) { return T * ratio + 140 * ratio + T + 141; }
+static __global__ __launch_bounds__(256) void snba_decim_kernel(const double2 *buf, long long stride, int n12, const int *chan_list, SnbaParam q,
+                                                                const double *h_in, const double *state, double *out12, long long stride12)
+{
+#pragma clang fp contract(off)
+    extern __shared__ double snba_win[];
+    const int ch = chan_list[blockIdx.y], T = blockDim.x, hin = q.cpp_in - 1;
+    const int m0 = blockIdx.x * T;
+    const int nout = n12 - m0 < T ? n12 - m0 : T;           // outputs of this block (the grid covers n12: at least 1)
+    const double2 *row = buf + (long long)ch * stride;
+    const double *hist = state + (size_t)ch * q.state_doubles + q.off_rin;
+    // window sample w is input g = m0 * ratio - hin + w; the last one needed is that of output m0 + nout - 1
+    const long long g0 = (long long)m0 * q.ratio - hin;
+    const int nwin = (nout - 1) * q.ratio + 1 + hin, lg = __ffs(q.ratio) - 1;
+    for (int w = threadIdx.x; w < nwin; w += T) {
+        const long long g = g0 + w;
+        snba_win[w + (w >> lg)] = g < 0 ? hist[hin + g] : row[g].x;
+    }
+    __syncthreads();
+    const int m = threadIdx.x;
+    if (m >= nout) return;
+    double acc;
+    if (q.ratio == 1) acc = snba_win[2 * m];
+    else {
+        // x[m * ratio - j] is window sample hin + m * ratio - j with hin = 140 * ratio: j = 0 is the first sample of padding group 140 + m,
+        // j = c * ratio + 1 ... (c + 1) * ratio are group 139 + m - c from its last sample down
+        const int top = (140 + m) << lg;
+        acc = 0.0;
+        acc += h_in[0] * snba_win[top + 140 + m];
+        const double *h = h_in + 1;
+        for (int c = 0; c < 140; c++) {
+            const double *xp = snba_win + (top - (c << lg) - 1) + (139 + m - c);
+            for (int i = 0; i < q.ratio; i++) acc += h[i] * xp[-i];
+            h += q.ratio;
+        }
+    }
+    out12[(long long)ch * stride12 + m0 + m] = acc;
+}
+
+// outresamp: L = ratio, M = 1.  out[i * ratio + ph] = sum_{j = 0 .. 140} h_out[ch][ph][j] o12[i - j] for the n = n12 * ratio samples of the
+// call, written as (acc, 0) into the channel's row; block (x, y) takes samples x * 256 .. of listed channel y, its window of
+// 256 / ratio (at least 1 ... 256) + 140 samples of the 12 kHz row in LDS.  The taps are the channel's own (SetRXASNBAOutputBandwidth).
+static __global__ __launch_bounds__(256) void snba_interp_kernel(double2 *buf, long long stride, int n12, const int *chan_list, SnbaParam q,
+                                                                 const double *h_out, const double *state, const double *in12, long long stride12)
+{
+#pragma clang fp contract(off)
+    __shared__ double win[256 + 140];
+    const int ch = chan_list[blockIdx.y], hout = q.cpp_out - 1;
+    const long long n = (long long)n12 * q.ratio, n0 = (long long)blockIdx.x * 256;
+    const int nout = n - n0 < 256 ? (int)(n - n0) : 256;
+    const int i0 = (int)(n0 / q.ratio);                      // 256 is a multiple of every ratio: the block starts at phase 0
+    const int nwin = (nout - 1) / q.ratio + 1 + hout;
+    const double *hist = state + (size_t)ch * q.state_doubles + q.off_rout;
+    const double *o12 = in12 + (long long)ch * stride12;
+    for (int w = threadIdx.x; w < nwin; w += 256) {
+        const int g = i0 - hout + w;
+        win[w] = g < 0 ? hist[hout + g] : o12[g];
+    }
+    __syncthreads();
+    const int t = threadIdx.x;
+    if (t >= nout) return;
+    double acc;
+    if (q.ratio == 1) acc = win[t];
+    else {
+        const int i = t / q.ratio, ph = t - i * q.ratio;
+        const double *hp = h_out + (size_t)ch * q.ratio * q.cpp_out + ph * q.cpp_out, *op = win + hout + i;
+        acc = 0.0;
+        for (int j = 0; j < q.cpp_out; j++) acc += hp[j] * op[-j];
+    }
+    buf[(long long)ch * stride + n0 + t] = make_double2(acc, 0.0);
+}
+
+// A pass's history behind it: the last `hist` samples of (old history | the n samples of this call), oldest first, at state offset
+// `off` of every listed channel.  src: the call's samples, `step` doubles apart (2: the real parts of a row of the chain buffer,
+// 1: a 12 kHz row).  One block per channel; the new history is complete in LDS before any of it is written, as n may be below hist.
+static __global__ __launch_bounds__(256) void snba_hist_kernel(const double *src, long long src_stride, int step, int n, const int *chan_list,
+                                                               double *state, int state_doubles, int off, int hist)
+{
+    extern __shared__ double snba_keep[];
+    const int ch = chan_list[blockIdx.x];
+    double *h = state + (size_t)ch * state_doubles + off;
+    const double *x = src + (long long)ch * src_stride;
+    for (int i = threadIdx.x; i < hist; i += 256) {
+        const long long g = (long long)i + n - hist;         // the sample that becomes history entry i
+        snba_keep[i] = g < 0 ? h[hist + g] : x[g * step];
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < hist; i += 256) h[i] = snba_keep[i];
 }
 
 }  // namespace qh

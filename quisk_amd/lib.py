@@ -117,6 +117,8 @@ def load():
     L.qh_rxa_set_graph_replay.argtypes = [vp, i]
     L.qh_rxa_set_band_tile.argtypes = [vp, i]
     L.qh_rxa_band_tile.argtypes = [vp]
+    L.qh_rxa_set_snba_form.argtypes = [vp, i]
+    L.qh_rxa_snba_form.argtypes = [vp]
     L.qh_rxa_graph_launches.argtypes = [vp]
     L.qh_rxa_graph_launches.restype = ll
     L.qh_rxa_pll_repairs.argtypes = [vp]

@@ -275,6 +275,13 @@ class RxaEngine:
     def band_tile(self):
         return self._L.qh_rxa_band_tile(self._h)
 
+    def set_snba_form(self, form=0):
+        """Form of xsnba: 0 = the single kernel where it can run (default), 1 = the three passes everywhere; the same bits."""
+        check(self._L.qh_rxa_set_snba_form(self._h, int(form)))
+
+    def snba_form(self):
+        return self._L.qh_rxa_snba_form(self._h)
+
     def graph_launches(self):
         return self._L.qh_rxa_graph_launches(self._h)
 
