@@ -19,6 +19,16 @@ def hb45_taps():
     return t
 
 
+def _state_rows(hist, nch, nh, np_dtype):
+    """A history as a contiguous [nch, nh] array of the bank's sample type, or None for zeros."""
+    if hist is None or nh == 0:
+        return None
+    hist = np.asarray(hist)
+    if hist.shape != (nch, nh):
+        raise ValueError("expected a history of shape [%d, %d]" % (nch, nh))
+    return np.ascontiguousarray(hist, dtype=np_dtype)
+
+
 class FirBank:
     def __init__(self, nch, taps, decim, dtype=F64, device=0, stream=None):
         self._L = load()
@@ -29,7 +39,7 @@ class FirBank:
                                         re.size, decim, dtype, stream)
         if not self._h:
             raise QuiskHipError("qh_fir_create failed: %s" % self._L.qh_last_error().decode(errors="replace"))
-        self.nch, self.decim, self.dtype = nch, decim, dtype
+        self.nch, self.ntaps, self.decim, self.dtype = nch, re.size, decim, dtype
         self.np_dtype = np.complex128 if dtype == F64 else np.complex64
 
     def out_count(self, n_in):
@@ -52,6 +62,12 @@ class FirBank:
 
     def reset(self):
         check(self._L.qh_fir_reset(self._h))
+
+    def set_state(self, hist, phase):
+        """Load the filter state: `hist` [nch, ntaps - 1] holds the most recent input samples of every channel, oldest first, in the
+        bank's sample type (None: zeros); `phase` is the decimation index, 0 <= phase < decim."""
+        rows = _state_rows(hist, self.nch, self.ntaps - 1, self.np_dtype)
+        check(self._L.qh_fir_set_state(self._h, rows.ctypes.data if rows is not None else None, phase))
 
     def synchronize(self):
         check(self._L.qh_fir_synchronize(self._h))
@@ -123,6 +139,7 @@ class RationalFir:
         if not self._h:
             raise QuiskHipError("qh_rat_create failed: %s" % self._L.qh_last_error().decode(errors="replace"))
         self.nch, self.interp, self.decim, self.dtype = nch, interp, decim, dtype
+        self.K = (t.size + interp - 1) // interp            # taps per phase; the bank remembers K - 1 samples
         self.np_dtype = np.complex128 if dtype == F64 else np.complex64
 
     def out_count(self, n_in):
@@ -149,6 +166,12 @@ class RationalFir:
 
     def reset(self):
         check(self._L.qh_rat_reset(self._h))
+
+    def set_state(self, hist, phase):
+        """Load the filter state: `hist` [nch, K - 1] holds the most recent input samples of every channel, oldest first, in the bank's
+        sample type (None: zeros); `phase` is the position of the next output on the interpolated grid (see `phase`)."""
+        rows = _state_rows(hist, self.nch, self.K - 1, self.np_dtype)
+        check(self._L.qh_rat_set_state(self._h, rows.ctypes.data if rows is not None else None, phase))
 
     def close(self):
         if getattr(self, "_h", None):

@@ -190,6 +190,7 @@ def load():
     L.qh_fir_destroy.argtypes = [vp]
     L.qh_fir_destroy.restype = None
     L.qh_fir_reset.argtypes = [vp]
+    L.qh_fir_set_state.argtypes = [vp, vp, i]
     L.qh_fir_out_count.argtypes = [vp, i]
     L.qh_fir_process.argtypes = [vp, vp, ll, i, vp, ll, C.POINTER(i)]
     L.qh_fir_process_host.argtypes = [vp, vp, ll, i, vp, ll, C.POINTER(i)]
