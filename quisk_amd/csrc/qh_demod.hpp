@@ -294,49 +294,34 @@ static __global__ __launch_bounds__(64) void meter_kernel(const double2 *buf, lo
     if (lane == 0) state[ch] = st;
 }
 
-// The same meters from the per-chunk partials the METER overlap-save kernel leaves behind (qh_osfir.hpp: x = sum over
-// the chunk's 64 samples of (1 - m) m^(63 - i) |z_i|^2, y = max |z_i|^2): the one-pole average advances a chunk at a time,
-// avg <- m^64 avg + x, and the peak a DSP block (cpb chunks) at a time, peak <- max(peak * mp^(64 cpb), block max).  Both
-// recurrences are linear (the second over (max, *)), so their value at the end of the call is a weighted sum / maximum of
-// independent pieces: every chunk's partial carries its own decay to the end of the call, and one reduction joins them
-// with the carried state.  One workgroup per channel serves the three meters: adc meter (partials of the stage input), S meter and agc
+// The same meters from the partials the METER overlap-save kernels leave behind (qh_osfir.hpp, "fused meters"): per tile and
+// row of 16 lanes, x = the one-pole average's response at the tile's nominal end (sample (T + 1) Lout) to the row's samples,
+// and y = their maximum carried to the block bT = ((T + 1) Lout - 1) / size that end lies in, decayed by mp^size per block.
+// Both recurrences are linear (the second over (max, *)), so their value at the end of the call is a weighted sum / maximum
+// of independent pieces: tile T's partials weigh m^(n - (T + 1) Lout) and mp^(size (nblocks - 1 - bT)) -- for a last tile the
+// call's end cuts short the exponents are negative, by less than a tile -- and one reduction joins them with the carried
+// state.  One workgroup per channel serves the three meters: adc meter (partials of the stage input), S meter and agc
 // meter (both on the stage output, the agc meter behind the fixed gain g: gain2 = g^2).
-// wdsp/RXA.c:566,569,589.  Storage: tile-major, inside a tile [wave][register] (cpt chunks per tile; layout 1: the
-// two-group tile's [A: wave][8], [B: wave][16]).
+// wdsp/RXA.c:566,569,589.  Storage: [tile][row], ppt partials per tile.
 static constexpr int kMeterFinishThreads = 1024;
 // m^k for the meters' decay factors m = exp(-1 / (rate tau)): exp(k ln m) with ln m exact by construction
 __device__ __forceinline__ double meter_decay(double ln_m, double k) { return exp(k * ln_m); }
 
 static __global__ __launch_bounds__(kMeterFinishThreads) void meter_finish_kernel(const double2 *part_in, const double2 *part_out,
-                                                                 long long stride, int nchunks, int cpb, int cpt, int layout, MeterState *m_adc,
+                                                                 long long stride, int n, int size, int lout, int ppt, MeterState *m_adc,
                                                                  MeterState *m_s, MeterState *m_agc, double ln_avg, double ln_pk,
                                                                  const double *gain2)
 {
     __shared__ double s_red[kMeterFinishThreads / 64][4];
     const int ch = blockIdx.x, T = threadIdx.x, lane = T & 63, wave = T >> 6;
     const double2 *pi = part_in + (long long)ch * stride, *po = part_out + (long long)ch * stride;
-    const int nseg = cpt >> 2, nblocks = nchunks / cpb;
-    // Both recurrences unrolled: chunk c of the call weighs m^(64 (nchunks - 1 - c)) in the average, and the peak of DSP
-    // block b weighs mp^(size (nblocks - 1 - b)) in the peak.  Lanes read consecutive partials (storage order) and weigh
-    // each by its own place in time.
+    const int ntiles = (n + lout - 1) / lout, nblocks = n / size;
     double avg_i = 0.0, peak_i = 0.0, avg_o = 0.0, peak_o = 0.0;        // adc meter (stage input), S meter (stage output)
-    const int nslots = (nchunks + cpt - 1) / cpt * cpt;                 // the last tile may hold fewer chunks than slots
-    for (int s0 = T; s0 < nslots; s0 += kMeterFinishThreads) {
-        const int tile = s0 / cpt, in = s0 - tile * cpt;
-        int c;
-        if (layout == 2) {                                              // 6144-point tile on six wavefronts (osfir6k_kernel): chunk 6 r + w - 32
-            const int w = in < 20 ? in / 10 : 2 + (in - 20) / 11, r = in < 20 ? 6 + in % 10 : 5 + (in - 20) % 11;
-            c = tile * cpt + 6 * r + w - 32;
-        } else if (layout == 0) c = tile * cpt + 4 * (in % nseg) + in / nseg;  // [wave][register] -> chunk 4 register + wave
-        else if (in < 32) c = tile * cpt + 32 + 4 * (in & 7) + (in >> 3);      // two-group tile (osfir8k_kernel): group A, registers 8 .. 15
-        else {                                                                  // group B: [wave][16 registers], the upper eight 4096 samples on
-            const int w = (in - 32) >> 4, k = (in - 32) & 15;
-            c = tile * cpt + (k < 8 ? 4 * k + w : 64 + 4 * (k - 8) + w);
-        }
-        if (c >= nchunks) continue;
+    for (int s0 = T; s0 < ntiles * ppt; s0 += kMeterFinishThreads) {
+        const long long end = ((long long)(s0 / ppt) + 1) * lout;       // the tile's nominal end
         const double2 vi = pi[s0], vo = po[s0];
-        const double wa = meter_decay(ln_avg, 64.0 * (double)(nchunks - 1 - c));
-        const double wp = meter_decay(ln_pk, 64.0 * (double)cpb * (double)(nblocks - 1 - c / cpb));
+        const double wa = meter_decay(ln_avg, (double)(n - end));
+        const double wp = meter_decay(ln_pk, (double)size * (double)(nblocks - 1 - (int)((end - 1) / size)));
         avg_i = __builtin_fma(vi.x, wa, avg_i); peak_i = fmax(peak_i, vi.y * wp);
         avg_o = __builtin_fma(vo.x, wa, avg_o); peak_o = fmax(peak_o, vo.y * wp);
     }
@@ -351,8 +336,8 @@ static __global__ __launch_bounds__(kMeterFinishThreads) void meter_finish_kerne
         MeterState *state = T == 0 ? m_adc : T == 1 ? m_s : m_agc;
         const double g2 = (T == 2 && gain2) ? gain2[ch] : 1.0;
         MeterState st = state[ch];
-        st.avg = st.avg * meter_decay(ln_avg, 64.0 * (double)nchunks) + g2 * a;
-        st.peak = fmax(st.peak * meter_decay(ln_pk, 64.0 * (double)nchunks), g2 * pk);
+        st.avg = st.avg * meter_decay(ln_avg, (double)n) + g2 * a;
+        st.peak = fmax(st.peak * meter_decay(ln_pk, (double)n), g2 * pk);
         st.res_av = 10.0 * mlog10_dev(st.avg + 1.0e-40);
         st.res_pk = 10.0 * mlog10_dev(st.peak + 1.0e-40);
         state[ch] = st;

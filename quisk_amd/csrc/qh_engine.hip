@@ -37,7 +37,7 @@ static void launch_osfir(OsfirArgs<double> a, int ntiles, int nch, hipStream_t s
 {
     a.ntiles = ntiles;
     dim3 grid((unsigned)ntiles * (unsigned)nch), block(NT);      // 1-D: the kernel maps ids to (channel, tile), qh_osfir.hpp
-    constexpr int lds = osfir_lds_bytes<double, NFFT, D, METER>();
+    constexpr int lds = osfir_lds_bytes<double, NFFT, D>();
     hipLaunchKernelGGL((osfir_kernel<double, NFFT, D, MIX, PACKED, METER, OUTMIX, EGRESS, POLY, DET, PAIR, MROW>), grid, block, lds, s, a);
 }
 // a stage that holds its mask rows by design (OsfirArgs::mask_row: the FM filters; no meters, no audio frames in their stores)
@@ -85,12 +85,12 @@ int Engine::tile_lds_limits()
 {
     // dynamic LDS of the overlap-save kernels
 #define QH_SET_LDS(D, ...) QH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&osfir_kernel<double, 4096, D, __VA_ARGS__>), \
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (osfir_lds_bytes<double, 4096, D, true>())))
+                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (osfir_lds_bytes<double, 4096, D>())))
     QH_SET_LDS(1, false); QH_SET_LDS(1, false, false, true);
     QH_SET_LDS(1, false, false, false, false, true); QH_SET_LDS(1, false, false, true, false, true);
     QH_SET_LDS(1, false, false, false, false, false, false, 0, false, true); QH_SET_LDS(1, false, false, false, false, false, false, 0, true, true);   // MROW, plain and PAIR
 #define QH_SET_LDS8(...) QH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&osfir_kernel<double, kBandNfftMax, 1, false, false, __VA_ARGS__>), \
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (osfir_lds_bytes<double, kBandNfftMax, 1, true>())))
+                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (osfir_lds_bytes<double, kBandNfftMax, 1>())))
     QH_SET_LDS8(false, false, false); QH_SET_LDS8(true, false, false); QH_SET_LDS8(false, false, true); QH_SET_LDS8(true, false, true);
     QH_SET_LDS8(false, false, false, false, 0, false, true);       // MROW
 #undef QH_SET_LDS8
@@ -352,7 +352,13 @@ void Engine::run_band(const double2 *src, long long src_stride, double2 *dst, lo
     a.chan_list = list;
     a.n_in = (int)n_mid; a.n_out = (int)n_mid; a.off = 0; a.P = P; a.Lout = Lout;
     tick(1);
-    if (meter) { a.meter_in = m_part[0]; a.meter_out = m_part[1]; a.meter_stride = m_part_cap; a.meter_w = m_w; }
+    if (meter) {            // the tables of Engine::meters_alloc
+        const int lanes = band6k ? kOsfir6kThreads : NT;
+        a.meter_in = m_part[0]; a.meter_out = m_part[1]; a.meter_stride = m_part_cap;
+        a.meter_w = m_w + (band6k ? kMeterW384 : 0); a.meter_pk = m_w + kMeterPk;
+        a.meter_mnt = std::exp(-(double)lanes / ((double)dsp_rate * 0.100));
+        a.meter_sshift = __builtin_ctz((unsigned)dsp_size);
+    }
     if (egress) a.eg = eg;
     const int nl = list ? nlist : nch;
     // the one-group tile kernel writes the next call's delay line itself when the call is at least one line long (OsfirArgs::hist_next)
@@ -579,8 +585,9 @@ int Engine::process_chain(const double *d_in, long long in_stride, double *d_out
     if (int rc = plan_long(k)) return rc;
     pick_band_tile(k.nc_max);
     // The three meters of xrxa (adc, S, agc: RXA.c:566,569,589) ride on the nbp0 launch when the chain is linear (nbp0 runs,
-    // bp1 does not, fixed AGC gain): the band tile then starts on a multiple of 256 samples so that a register holds one
-    // 64-sample chunk per wavefront.  Any other chain takes the per-mode path with the stand-alone meter kernel.
+    // bp1 does not, fixed AGC gain): the band tile then starts on a multiple of 256 samples, so that the 64 samples a wavefront
+    // holds in one register lie in one DSP block and the taps' peak decay is scalar work (qh_osfir.hpp, "fused meters").  Any
+    // other chain takes the per-mode path with the stand-alone meter kernel.
     k.meters_fused = meters_on && !k.mixed && k.any_nbp && !k.any_bp1 && !k.any_eqp && dsp_size >= 64 && dsp_size <= 2048 && !k.long_mode;
     if (meters_on && !k.meters_fused) k.mixed = true;
     if (meters_on) if (int rc = meters_alloc()) return rc;
@@ -708,7 +715,7 @@ int Engine::run_linear(ChainCall &k)
     }
     if (k.meters_fused)
         hipLaunchKernelGGL(meter_finish_kernel, dim3((unsigned)nch), dim3(kMeterFinishThreads), 0, stream, m_part[0], m_part[1],
-                           m_part_cap, (int)(n_mid / 64), dsp_size / 64, (bnfft - k.P) / 64, band6k ? 2 : band2g ? 1 : 0, m_adc, m_s, m_agc,
+                           m_part_cap, (int)n_mid, dsp_size, bnfft - k.P, meter_parts(), m_adc, m_s, m_agc,
                            -1.0 / ((double)dsp_rate * 0.100), -1.0 / ((double)dsp_rate * 0.100), (const double *)m_g2);
     if (eg.kind && !k.eg_fused) pack_audio(k.out, k.out_stride, n_mid);
     tick(3);

@@ -520,12 +520,14 @@ struct Engine {
     bool meters_on = false;
     MeterState *m_adc = nullptr, *m_s = nullptr, *m_agc = nullptr;
     MeterParam m_prm{};
-    // meters fused into the nbp0 launch of the linear fast path (qh_osfir.hpp METER): chunk partials of the stage's input and
-    // output, the chunk weights, and g^2 of a fixed AGC gain that the output matrix applies behind the agc meter's tap
+    // meters fused into the nbp0 launch of the linear fast path (qh_osfir.hpp METER): per tile and row of 16 lanes partials of the
+    // stage's input and output, the taps' tables (lane weights and the peak's decay per block: kMeterTabDoubles), and g^2 of a
+    // fixed AGC gain that the output matrix applies behind the agc meter's tap
     double2 *m_part[2] = { nullptr, nullptr };
-    long long m_part_cap = 0;               // chunks per channel
+    long long m_part_cap = 0;               // partials per channel
     double *m_w = nullptr, *m_g2 = nullptr;
     int meters_alloc();
+    int meter_parts() const { return kMeterRows * (band6k ? 6 : band2g ? 8 : 4); }       // a tile's partials: one per row of 16 lanes of the band tile in use
     int agc_last_tiled = 0;             // channels whose xwcpagc took the time tiles in the last call (diagnostics)
     int n_agc_cur_stale = 0, n_agc_other_stale = 0;     // ... of which, at the lists' ends, channels whose attack window moved in mid-stream
 

@@ -365,15 +365,20 @@ int Engine::meters_alloc()
     }
     m_prm.mult_average = std::exp(-1.0 / (rate * 0.100));
     m_prm.mult_peak = std::exp(-1.0 / (rate * 0.100));
-    std::vector<double> w(64), g2((size_t)nch);
-    for (int i = 0; i < 64; i++) w[(size_t)i] = (1.0 - m_prm.mult_average) * std::pow(m_prm.mult_average, (double)(63 - i));
+    // the fused taps' tables (qh_osfir.hpp): a lane's weight (1 - m) m^(lanes - 1 - t) for tiles of 256 and of 384 lanes, and the peak's
+    // decay over k blocks mp^(dsp_size k) -- a tile of at most 6144 samples meets 6144 / 64 + 1 blocks of 64 or more
+    std::vector<double> w((size_t)kMeterTabDoubles), g2((size_t)nch);
+    const double ln_m = -1.0 / (rate * 0.100);
+    for (int t = 0; t < 256; t++) w[(size_t)t] = (1.0 - m_prm.mult_average) * std::exp(ln_m * (double)(255 - t));
+    for (int t = 0; t < 384; t++) w[(size_t)(kMeterW384 + t)] = (1.0 - m_prm.mult_average) * std::exp(ln_m * (double)(383 - t));
+    for (int k = 0; k < kMeterPkLen; k++) w[(size_t)(kMeterPk + k)] = std::exp(ln_m * (double)dsp_size * (double)k);
     for (int ch = 0; ch < nch; ch++) {
         const ChanCfg &c = cfg[(size_t)ch];
         g2[(size_t)ch] = (c.agc_run && c.agc_mode == 0 && !c.fix_before()) ? c.agc_fixed * c.agc_fixed : 1.0;
     }
-    if (int rc = alloc(m_w, 64)) return rc;
+    if (int rc = alloc(m_w, kMeterTabDoubles)) return rc;
     if (int rc = alloc(m_g2, nch)) return rc;
-    QH_HIP(hipMemcpyAsync(m_w, w.data(), 64 * sizeof(double), hipMemcpyHostToDevice, stream));
+    QH_HIP(hipMemcpyAsync(m_w, w.data(), w.size() * sizeof(double), hipMemcpyHostToDevice, stream));
     QH_HIP(hipMemcpyAsync(m_g2, g2.data(), g2.size() * sizeof(double), hipMemcpyHostToDevice, stream));
     QH_HIP(hipStreamSynchronize(stream));
     return QH_OK;
@@ -1290,10 +1295,10 @@ std::vector<cd> Engine::band_mask(const std::vector<cd> &h) const
     return p;
 }
 
-// chunk partials of the fused meters: whole tiles per channel (a tile's store is not bounds-checked)
+// partials of the fused meters: one per tile and row of 16 lanes
 int Engine::ensure_meter_partials(long long n_mid, int lout)
 {
-    const long long need = ((n_mid + lout - 1) / lout) * (lout / 64);
+    const long long need = ((n_mid + lout - 1) / lout) * meter_parts();
     if (need <= m_part_cap) return QH_OK;
     if (int rc = quiesce()) return rc;
     for (double2 *&m : m_part)

@@ -71,16 +71,16 @@ template <typename T> struct OsfirArgs {
     int pick;                     // 0/1: every folded sample is an output; k > 1: every k-th (n_out counts final outputs)
     const unsigned char *pk_src;  // PACKED kernels: the wire-format input (qh_ingest.hpp) instead of `in`
     PackedFmt pk;
-    // METER kernels (D = 1, P and Lout multiples of 256): per 64-sample chunk of the stage's input (meter_in) and of its
-    // output ahead of the epilogue (meter_out), x = sum_i w[i] |z_i|^2 and y = max_i |z_i|^2 -- what xmeter's one-pole
-    // average and block peak (wdsp/meter.c:75-108) need from the chunk; meter_finish_kernel walks them in time order
+    // METER kernels (D = 1, P and Lout multiples of 256): per tile and row of 16 lanes, of the stage's input (meter_in) and of its
+    // output ahead of the epilogue (meter_out), x = the one-pole average's and y = the decaying block peak's response at the
+    // tile's end to the row's samples (wdsp/meter.c:75-108; "fused meters" below); meter_finish_kernel joins them
     // OUTMIX kernels: phasor of the NCO at input index g0 of every tile, at D*t for lane t, at D*256 (nco_step)
     const double2 *tile_rot;            // [nch][ntiles]
     const double2 *lane_rot;            // [nch][NT]
     EgressFmt eg;                       // EGRESS kernels: the outputs leave as audio frames (qh_egress.hpp) instead of through `out`
-    double2 *meter_in, *meter_out;      // [nch][meter_stride] chunk partials, chunk c = samples 64c .. 64c + 63 of this call
+    double2 *meter_in, *meter_out;      // [nch][meter_stride] partials, [tile][wavefront][row of 16 lanes]
     long long meter_stride;
-    const double *meter_w;              // [64]  (1 - m) m^(63 - i)
+    const double *meter_w;              // [lanes]  (1 - m) m^(lanes - 1 - t)  (lanes: 256, or 384 for osfir6k_kernel)
     const double2 *tw_r2;               // osfir8k_kernel: exp(-2 pi i k / 8192), k < 256
     // DET kernels: the stage feeds a detector only, and the detector's first step rides in the store.  One double per output leaves
     // (det_out [nch][det_stride]) instead of the complex sample:
@@ -116,9 +116,13 @@ template <typename T> struct OsfirArgs {
     int amlv_shift;
     // MROW kernels: [nch] the mask row of every channel, for a stage that holds one row per distinct design among its channels (the
     // engine's FM de-emphasis and audio filters): mask + mask_row[ch] * mask_stride.  Null for every other stage (row = channel, or the
-    // one shared row with mask_stride 0), whose kernels are the instantiations without MROW and never read it.  Last, so that no other
-    // member moves.
+    // one shared row with mask_stride 0), whose kernels are the instantiations without MROW and never read it.  Behind the others, so
+    // that none of them moves.
     const int *mask_row;
+    // METER kernels, likewise behind the others: mp^(dsp_size k) for the peak, m^lanes for the average's Horner step, log2 dsp_size
+    const double *meter_pk;
+    double meter_mnt;
+    int meter_sshift;
 };
 
 
@@ -194,11 +198,10 @@ __device__ __forceinline__ void xcd_tile_map(int ntiles, int &chan_slot, int &ti
 }
 
 // dynamic LDS of the two kernels below
-template <typename T, int NFFT, int D, bool METER = false> constexpr int osfir_lds_bytes()
+template <typename T, int NFFT, int D> constexpr int osfir_lds_bytes()
 {
     constexpr int a = TileFft<NFFT, false, cplx<T>>::kLdsBytes, b = TileFft<NFFT / D, true, cplx<T>>::kLdsBytes;
-    constexpr int m = METER ? NT / 64 * 2 * 64 * 9 * 8 : 0;        // the meter taps' per-wave blocks overlay the image (kMeterLdsDoublesPerWave)
-    return (a > b ? a : b) > m ? (a > b ? a : b) : m;
+    return a > b ? a : b;
 }
 template <typename T, int NFFT, int U> constexpr int osfir_interp_lds_bytes()
 {
@@ -240,63 +243,104 @@ __device__ long long g_osfir_probe[16];
 
 
 // ---- fused meters -----------------------------------------------------------------------------------------------
-// Lane t of a tile holds samples t + 256 r in register r, so a wavefront holds one 64-sample chunk per register.  The
-// eight chunks of a register group are reduced together: every lane writes its eight weighted magnitudes (and the
-// eight plain ones) into the wave's own LDS block as [register][lane], reads back eight consecutive lanes of one
-// register (segments of 8 doubles at a pitch of 9: conflict-free 64-bit accesses), adds / maxes them and finishes
-// across the eight lanes that share a register with three DPP steps.  No workgroup barrier inside; the caller
-// guarantees that nobody else uses the LDS image meanwhile.
-template <int CTRL> __device__ __forceinline__ double dpp_mov_d(double v)
-{
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_mov_dpp(lo, CTRL, 0xf, 0xf, false);
-    hi = __builtin_amdgcn_mov_dpp(hi, CTRL, 0xf, 0xf, false);
-    return __hiloint2double(hi, lo);
-}
-constexpr int kMeterLdsDoublesPerWave = 2 * 64 * 9;
-     // (sum set, max set) x 64 segments x pitch 9
+// xmeter's two recurrences (wdsp/meter.c:75-108) are linear -- the one-pole average over (+, *), the block peak with its
+// per-block decay over (max, *) -- so a tile's share of both at the tile's nominal end is a weighted sum / maximum of its own
+// samples, and a lane reduces the samples in its own registers first.  Lane t, register i holds sample rel = t + NTs i - j0
+// of the tile (NTs the lane stride, g = tile Lout + rel the sample's place in the call, S = dsp_size):
+//   average  H = sum_i (m^NTs)^(last - i) |z_i|^2 by Horner, one FMA per register, times the lane's weight (1 - m) m^(NTs - 1 - t):
+//            the tile's span j0 + Lout is the transform's length, so the last register's sample NTs - 1 - t short of the tile's end
+//   peak     M = max_i |z_i|^2 mp^(S (bT - g / S)), bT = ((tile + 1) Lout - 1) / S the block the tile's end lies in: a positive
+//            factor commutes with max, so this is the block maxima carried to block bT with WDSP's decay per block.  The factors
+//            mp^(S k) come from a table the host makes; every tile starts on a multiple of 64 samples, so a wavefront's 64 samples
+//            of one register lie in one block and the factor is a scalar load.
+// Samples outside the call (rel < 0 ahead of the first new one, g >= n_out) count 0.  One (sum, max) per row of 16 lanes and tap leaves:
+// no LDS, no barrier.  meter_finish_kernel (qh_demod.hpp) carries every tile's partials to the call's end.
+// The engine's table (Engine::meters_alloc): lane weights for strides 256 and 384, then mp^(S k).
+constexpr int kMeterW384 = 256, kMeterPk = 256 + 384, kMeterPkLen = 128, kMeterTabDoubles = kMeterPk + kMeterPkLen;
 
 // max of two numbers that are not NaN (squared magnitudes): fmax() would first re-quiet operands the compiler cannot
-// prove canonical (everything that comes back from LDS or a DPP move) with a v_max_f64 x, x each
+// prove canonical (everything that comes back from a DPP move) with a v_max_f64 x, x each
 __device__ __forceinline__ double max_nn(double a, double b)
 {
     double r;
     asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
     return r;
 }
-
-// x[r0 + k], k = 0 .. nseg - 1 (nseg = E - r0), are the registers to meter.  The wave's nseg partials go out as one
-// contiguous run: dst[wave * nseg + k] (meter_finish_kernel knows that chunk 4 k + wave of the tile sits there).
-template <typename C, int E>
-__device__ __forceinline__ void meter_tap(const C (&x)[E], int r0, double wlane, double *lds_wave, double2 *dst, int wave, int lane, int wstride = -1)
+template <int CTRL> __device__ __forceinline__ double row_shr_max(double v)
 {
-    const int ws = wstride < 0 ? E - r0 : wstride;      // a wave's run inside dst (callers that tap a tile's registers in several calls)
-    const int wr = (lane >> 3) * 9 + (lane & 7);        // write slot inside a register's 8 segments
-    const double *rd = lds_wave + lane * 9;
+    int lo = __double2loint(v), hi = __double2hiint(v);
+    lo = __builtin_amdgcn_mov_dpp(lo, CTRL, 0xf, 0xf, true);        // bound_ctrl: lanes shifted in from outside the row read 0
+    hi = __builtin_amdgcn_mov_dpp(hi, CTRL, 0xf, 0xf, true);
+    return max_nn(v, __hiloint2double(hi, lo));
+}
+struct MeterTile {              // workgroup-uniform
+    int g0, lim, bT, sh;        // tile Lout; the call's samples left from there; the tile's last block; log2 dsp_size
+    double mnt;                 // m^NTs
+    const double *pk;           // mp^(S k)
+};
+template <typename T> __device__ __forceinline__ MeterTile meter_tile(const OsfirArgs<T> &a, int tile, int lout)
+{
+    MeterTile q;
+    q.g0 = tile * lout; q.lim = a.n_out - q.g0; q.sh = a.meter_sshift; q.bT = (q.g0 + lout - 1) >> q.sh;
+    q.mnt = a.meter_mnt; q.pk = a.meter_pk;
+    return q;
+}
+struct MeterAcc { double h = 0.0, mx = 0.0; };
+// Registers RA .. RB - 1 hold the tile's samples rel0 + nts (r - RA); rel0 = lane (mod 64), so the wavefront's 64 samples of a
+// register lie in one block and what picks the peak's factor is scalar arithmetic on lane 0's rel0.  Straight-line: the table's
+// factors are asked for first, all of them in flight together and as scalar loads (the table never changes while a kernel runs: the
+// constant address space says so, whatever the kernel has stored meanwhile), then one pass over the registers, five operations each.
+// MASK: samples with rel < 0 or rel >= q.lim count 0; without it the caller knows that there are none, or that they hold 0.
+template <int RA, int RB, bool MASK, typename C, int E>
+__device__ __forceinline__ void meter_accum(MeterAcc &acc, const C (&x)[E], int rel0, int nts, const MeterTile &q)
+{
+    static_assert(0 <= RA && RA < RB && RB <= E, "registers of the tile");
+    typedef const double __attribute__((address_space(4))) *ConstTable;
+    const ConstTable pk = (ConstTable)q.pk;
+    const int relw = __builtin_amdgcn_readfirstlane(rel0);
+    double f[RB - RA];
 #pragma unroll
-    for (int g = 0; g < E / 8; g++) {
-        if (8 * (g + 1) <= r0) continue;                // workgroup-uniform
-#pragma unroll
-        for (int k = 0; k < 8; k++) {
-            const C v = x[8 * g + k];
-            double m2 = (double)v.x * (double)v.x;
-            m2 = __builtin_fma((double)v.y, (double)v.y, m2);       // wdsp/meter.c:90 (contracted)
-            lds_wave[k * 72 + wr] = m2 * wlane;
-            lds_wave[64 * 9 + k * 72 + wr] = m2;
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        double sum = rd[0], mx = rd[64 * 9];
-#pragma unroll
-        for (int k = 1; k < 8; k++) { sum += rd[k]; mx = max_nn(mx, rd[64 * 9 + k]); }
-        sum += dpp_mov_d<0xB1>(sum); mx = max_nn(mx, dpp_mov_d<0xB1>(mx));        // quad_perm [1,0,3,2]
-        sum += dpp_mov_d<0x4E>(sum); mx = max_nn(mx, dpp_mov_d<0x4E>(mx));        // quad_perm [2,3,0,1]
-        sum += dpp_mov_d<0x141>(sum); mx = max_nn(mx, dpp_mov_d<0x141>(mx));      // row_half_mirror
-        const int r = 8 * g + (lane >> 3);
-        if ((lane & 7) == 0 && r >= r0) dst[wave * ws + (r - r0)] = make_double2(sum, mx);
-        __builtin_amdgcn_wave_barrier();                // the next group overwrites the block
+    for (int r = RA; r < RB; r++) {
+        const int rel = relw + nts * (r - RA);
+        f[r - RA] = pk[q.bT - ((q.g0 + (MASK && rel < 0 ? 0 : rel)) >> q.sh)];
     }
+#pragma unroll
+    for (int r = RA; r < RB; r++) {
+        const int rel = rel0 + nts * (r - RA);
+        const C v = x[r];
+        double m2 = (double)v.x * (double)v.x;
+        m2 = __builtin_fma((double)v.y, (double)v.y, m2);           // wdsp/meter.c:90 (contracted)
+        if constexpr (MASK) m2 = (rel >= 0 && rel < q.lim) ? m2 : 0.0;
+        acc.h = __builtin_fma(acc.h, q.mnt, m2);
+        acc.mx = max_nn(acc.mx, m2 * f[r - RA]);
+    }
+}
+// The wavefront's partials leave by rows of 16 lanes: four DPP steps each for the sum and the maximum (values >= 0: the zeros shifted
+// in from outside a row leave both alone), and lane 15 of every row stores its row's pair -- dst[0 .. 3].  Carrying the four rows into
+// one lane would cost as much again in v_readlane.
+__device__ __forceinline__ void meter_store(const MeterAcc &acc, double wlane, double2 *dst, int lane)
+{
+    double s = acc.h * wlane, mx = acc.mx;
+    s = row_shr_add<0x111>(s); mx = row_shr_max<0x111>(mx);         // row_shr:1
+    s = row_shr_add<0x112>(s); mx = row_shr_max<0x112>(mx);         // row_shr:2
+    s = row_shr_add<0x114>(s); mx = row_shr_max<0x114>(mx);         // row_shr:4
+    s = row_shr_add<0x118>(s); mx = row_shr_max<0x118>(mx);         // row_shr:8
+    if ((lane & 15) == 15) dst[lane >> 4] = make_double2(s, mx);
+}
+constexpr int kMeterRows = 4;       // partials per wavefront
+// The tap of the 256-lane tile: register r holds sample t + 256 r - P of the tile, P a multiple of 256 and at most half the transform.
+// ZEROED: the registers past the call's end hold 0 (the stage's input, as the tile's load leaves it); else a tile the call's end cuts
+// short masks them (the stage's output).  Sixteen partials per tile: [wavefront][row].
+template <bool ZEROED, typename C, int E, typename T>
+__device__ __forceinline__ void meter_tap(const C (&x)[E], const OsfirArgs<T> &a, double2 *part, int ch, int tile, int t)
+{
+    const MeterTile q = meter_tile(a, tile, a.Lout);
+    MeterAcc acc;
+    asm volatile("" : "+v"(t));             // a kernel's two taps each derive what hangs on the lane, not one of them for both across the transforms
+    if (a.P < E / 2 * NT) meter_accum<0, E / 2, true>(acc, x, t - a.P, NT, q);  // workgroup-uniform; the registers ahead of P count 0
+    if (ZEROED || q.lim >= a.Lout) meter_accum<E / 2, E, false>(acc, x, t + E / 2 * NT - a.P, NT, q);
+    else meter_accum<E / 2, E, true>(acc, x, t + E / 2 * NT - a.P, NT, q);
+    meter_store(acc, a.meter_w[t], part + (long long)ch * a.meter_stride + ((long long)tile * (NT / 64) + (t >> 6)) * kMeterRows, t & 63);
 }
 
 // POLY: the forward transform stops ahead of the stage that combines the D decimated sequences and the mask holds the
@@ -464,11 +508,8 @@ __global__ __launch_bounds__(NT, (osfir_min_waves<T, D, OUTMIX, NFFT>())) void o
 
     if constexpr (METER) {
         static_assert(D == 1 && !MIX && !PACKED, "meters ride on a plain D = 1 stage");
-        static_assert(NT / 64 * kMeterLdsDoublesPerWave * 8 <= osfir_lds_bytes<T, NFFT, D, true>(), "meter blocks overlay the exchange image");
-        // the tile's new samples [tile * Lout, (tile + 1) * Lout) are chunks tile * Lout / 64 ...; register P / 256 holds the first
-        meter_tap<C, E>(x, a.P >> 8, a.meter_w[t & 63], reinterpret_cast<double *>(lds) + (t >> 6) * kMeterLdsDoublesPerWave,
-                        a.meter_in + (long long)ch * a.meter_stride + (long long)tile * (a.Lout >> 6), t >> 6, t & 63);
-        __syncthreads();                    // the transform's exchange image overlays the waves' meter blocks
+        // the tile's new samples [tile * Lout, (tile + 1) * Lout): register P / 256 holds the first (samples past the call's end were loaded as 0)
+        meter_tap<true, C, E>(x, a, a.meter_in, ch, tile, t);
     }
 
     // ---- forward FFT, registers -> registers
@@ -496,11 +537,7 @@ __global__ __launch_bounds__(NT, (osfir_min_waves<T, D, OUTMIX, NFFT>())) void o
     Inv::run(z, lds, Inv::load(a.tw_inv));
     QH_OPROBE(4);
     if constexpr (METER) {
-        __syncthreads();                    // other waves may still be reading the exchange image
-        int t2 = t;
-        asm volatile("" : "+v"(t2));        // the lane's weight and block address are derived again, not carried through both transforms
-        meter_tap<C, EO>(z, a.P >> 8, a.meter_w[t2 & 63], reinterpret_cast<double *>(lds) + (t2 >> 6) * kMeterLdsDoublesPerWave,
-                         a.meter_out + (long long)ch * a.meter_stride + (long long)tile * (a.Lout >> 6), t2 >> 6, t2 & 63);
+        meter_tap<false, C, EO>(z, a, a.meter_out, ch, tile, t);
     }
 
     if constexpr (OUTMIX) {
@@ -553,7 +590,7 @@ __global__ __launch_bounds__(NT, (osfir_min_waves<T, D, OUTMIX, NFFT>())) void o
         // segments' carries; the segments' end values go to `red`.  (Keeping mag, vR, vI of eight rows in registers spilled a hundred.)
         double *sv = reinterpret_cast<double *>(lds);           // [row][t]
         double *red = sv + NR * NT;                             // [segment 4 r + wave][2], then [t][2] for the call's last sample
-        static_assert((NR * NT + 2 * 4 * NR + 2) * 8 <= osfir_lds_bytes<T, NFFT, D, false>(), "the leveller's scans fit the exchange image");
+        static_assert((NR * NT + 2 * 4 * NR + 2) * 8 <= osfir_lds_bytes<T, NFFT, D>(), "the leveller's scans fit the exchange image");
         __syncthreads();                        // the inverse transform's last exchange has been read by everyone
         int lane2 = lane;
         asm volatile("" : "+v"(lane2));         // (the scans' weights are formed here, behind the transforms)
@@ -697,14 +734,32 @@ __global__ __launch_bounds__(NT, (osfir_min_waves<T, D, OUTMIX, NFFT>())) void o
 // instead of four 4-wavefront ones, the twenty barriers of a tile stop eight wavefronts at a time, and the VALU is busy 48 %
 // of the time instead of 79 %.  (A four-wavefront barrier through an LDS counter, to let the groups drift apart between the
 // hand-overs: 4.3 ms.)  The engine therefore runs 4096-point tiles unless qh_rxa_set_band_tile(e, 8192) asks for these.
-// The group index must be SCALAR (readfirstlane): as a vector condition it put the meter taps' wave barriers inside
-// exec-masked regions and the taps corrupted live registers of the lanes that do not store.
+// The group index is SCALAR (readfirstlane): the branches on it, the meter taps' among them (whose DPP reductions need every lane
+// of the wavefront), are scalar branches, not exec-masked regions.
 // component-wise select: `c ? a : b` on two lvalues of struct type is an lvalue (a select of ADDRESSES), which pins the
 // register arrays to scratch memory
 __device__ __forceinline__ double2 sel2(bool c, double2 a, double2 b) { return make_double2(c ? a.x : b.x, c ? a.y : b.y); }
 constexpr int kOsfir8kThreads = 512, kOsfir8kP = 2048, kOsfir8kLout = 6144;
-constexpr int kOsfir8kImage = FftSplit4096<false, double2>::kLdsBytes > 4 * 2 * 64 * 9 * 8 ? FftSplit4096<false, double2>::kLdsBytes : 4 * 2 * 64 * 9 * 8;   // image or meter blocks
+constexpr int kOsfir8kImage = FftSplit4096<false, double2>::kLdsBytes;
 constexpr int osfir8k_lds_bytes() { return 2 * kOsfir8kImage; }
+
+// The meter tap of the two-group tile (input and output registers lie alike).  New samples are tile[2048 ..]: group A's registers
+// 8 .. 15 hold outputs 2048 + j + 256 s, group B's 0 .. 7 outputs j + 256 r and 8 .. 15 outputs 4096 + j + 256 s.  A's run ends, and
+// B's first run is followed by a gap of, 2048 samples: m^2048 on the Horner sum there.  32 partials per tile, [group][wavefront][row].
+__device__ __forceinline__ void meter_tap8k(const double2 (&x)[16], const OsfirArgs<double> &a, double2 *part, int ch, int tile, int g, int j)
+{
+    const MeterTile q = meter_tile(a, tile, kOsfir8kLout);
+    asm volatile("" : "+v"(j));             // (see meter_tap)
+    const double m512 = q.mnt * q.mnt, m1024 = m512 * m512, m2048 = m1024 * m1024;
+    MeterAcc acc;
+    if (g) {                                            // wavefront-uniform
+        meter_accum<0, 8, true>(acc, x, j, 256, q);
+        acc.h *= m2048;
+    }
+    meter_accum<8, 16, true>(acc, x, (g ? 4096 : 2048) + j, 256, q);
+    if (!g) acc.h *= m2048;
+    meter_store(acc, a.meter_w[j], part + (long long)ch * a.meter_stride + ((long long)tile * (kOsfir8kThreads / 64) + 4 * g + (j >> 6)) * kMeterRows, j & 63);
+}
 
 template <bool METER, bool EGRESS, bool MROW = false>
 __global__ __launch_bounds__(kOsfir8kThreads, 4) void osfir8k_kernel(OsfirArgs<double> a)
@@ -742,14 +797,7 @@ __global__ __launch_bounds__(kOsfir8kThreads, 4) void osfir8k_kernel(OsfirArgs<d
             x[r] = v;
         }
     }
-    if constexpr (METER) {
-        // new samples: tile[2048 ..]: group A registers 8 .. 15 (chunks 32 ..), group B all sixteen (chunks 0 .. 31, 64 .. 95);
-        // a tile's 96 partials are stored [A: wave][8] then [B: wave][16] (meter_finish_kernel, layout 1)
-        double *blk = reinterpret_cast<double *>(image) + (j >> 6) * kMeterLdsDoublesPerWave;
-        double2 *dst = a.meter_in + (long long)ch * a.meter_stride + (long long)tile * (L >> 6) + (g ? 32 : 0);
-        meter_tap<C, 16>(x, g ? 0 : 8, a.meter_w[j & 63], blk, dst, j >> 6, j & 63);
-        __syncthreads();
-    }
+    if constexpr (METER) meter_tap8k(x, a, a.meter_in, ch, tile, g, j);
 
     // ---- forward radix-2 step and the hand-over
     {
@@ -813,14 +861,7 @@ __global__ __launch_bounds__(kOsfir8kThreads, 4) void osfir8k_kernel(OsfirArgs<d
             x[8 + s] = make_double2(minuend.x - subtrahend.x, minuend.y - subtrahend.y);
         }
     }
-    if constexpr (METER) {
-        __syncthreads();
-        int j2 = j;
-        asm volatile("" : "+v"(j2));
-        double *blk = reinterpret_cast<double *>(image) + (j2 >> 6) * kMeterLdsDoublesPerWave;
-        double2 *dst = a.meter_out + (long long)ch * a.meter_stride + (long long)tile * (L >> 6) + (g ? 32 : 0);
-        meter_tap<C, 16>(x, g ? 0 : 8, a.meter_w[j2 & 63], blk, dst, j2 >> 6, j2 & 63);
-    }
+    if constexpr (METER) meter_tap8k(x, a, a.meter_out, ch, tile, g, j);
 
     // ---- epilogue + store: register r of group g is output (r < 8 ? 2048 g : 4096 + 2048 g) + j + 256 (r & 7) - P of the tile
     C *out = a.out + (long long)ch * a.out_stride + a.out_offset;
@@ -847,10 +888,16 @@ __global__ __launch_bounds__(kOsfir8kThreads, 4) void osfir8k_kernel(OsfirArgs<d
 // Lane t holds tile elements t + 384 r; the new samples begin at element 2048 = register 5 of wavefronts 2 .. 5, register 6 of
 // wavefronts 0 and 1 (the meter taps take a per-wavefront first register).  Mask: the 6144-point spectrum in natural order.
 constexpr int kOsfir6kThreads = kFft6kThreads, kOsfir6kP = 2048, kOsfir6kLout = 4096, kOsfir6kN = 6144;
-constexpr int osfir6k_lds_bytes()
+constexpr int osfir6k_lds_bytes() { return kFft6kLdsBytes; }
+
+// The meter tap of the 384-lane tile: register r holds output t + 384 r - 2048 of the tile: new from register 5 (wavefronts 2 .. 5) or
+// 6 (0 and 1), which the tap's own test of rel >= 0 sorts out.  24 partials per tile: [wavefront][row].
+__device__ __forceinline__ void meter_tap6k(const double2 (&x)[16], const OsfirArgs<double> &a, double2 *part, int ch, int tile, int t)
 {
-    constexpr int m = kOsfir6kThreads / 64 * kMeterLdsDoublesPerWave * 8;
-    return kFft6kLdsBytes > m ? kFft6kLdsBytes : m;
+    MeterAcc acc;
+    asm volatile("" : "+v"(t));             // (see meter_tap)
+    meter_accum<5, 16, true>(acc, x, t + 5 * kOsfir6kThreads - kOsfir6kP, kOsfir6kThreads, meter_tile(a, tile, kOsfir6kLout));
+    meter_store(acc, a.meter_w[t], part + (long long)ch * a.meter_stride + ((long long)tile * (kOsfir6kThreads / 64) + (t >> 6)) * kMeterRows, t & 63);
 }
 
 template <bool METER, bool EGRESS, bool MROW = false>
@@ -883,14 +930,8 @@ __global__ __launch_bounds__(kOsfir6kThreads, 3) void osfir6k_kernel(OsfirArgs<d
             x[r] = v;
         }
     }
-    // meter taps: wavefront w's chunks are elements 64 w + 384 r; new from register 5 (w >= 2) or 6 (w < 2).  A tile's 64
-    // partials are stored [w = 0: 10][w = 1: 10][w = 2: 11] .. [w = 5: 11] (meter_finish_kernel, layout 2)
-    const int wv = __builtin_amdgcn_readfirstlane(t >> 6);
-    const int r0 = wv < 2 ? 6 : 5, moff = wv < 2 ? 10 * wv : 20 + 11 * (wv - 2);
     if constexpr (METER) {
-        double *blk = reinterpret_cast<double *>(smem6k) + wv * kMeterLdsDoublesPerWave;
-        meter_tap<C, 16>(x, r0, a.meter_w[t & 63], blk, a.meter_in + (long long)ch * a.meter_stride + (long long)tile * (L >> 6) + moff, 0, t & 63);
-        __syncthreads();
+        meter_tap6k(x, a, a.meter_in, ch, tile, t);
     }
     Fft6144<false>::run(x, smem6k, Fft6144<false>::load(t), t);
 
@@ -903,11 +944,7 @@ __global__ __launch_bounds__(kOsfir6kThreads, 3) void osfir6k_kernel(OsfirArgs<d
     __syncthreads();
     Fft6144<true>::run(x, smem6k, Fft6144<true>::load(t), t);
     if constexpr (METER) {
-        __syncthreads();
-        int t2 = t;
-        asm volatile("" : "+v"(t2));
-        double *blk = reinterpret_cast<double *>(smem6k) + wv * kMeterLdsDoublesPerWave;
-        meter_tap<C, 16>(x, r0, a.meter_w[t2 & 63], blk, a.meter_out + (long long)ch * a.meter_stride + (long long)tile * (L >> 6) + moff, 0, t2 & 63);
+        meter_tap6k(x, a, a.meter_out, ch, tile, t);
     }
 
     C *out = a.out + (long long)ch * a.out_stride + a.out_offset;
