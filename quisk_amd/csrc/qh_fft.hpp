@@ -120,6 +120,94 @@ template <int R, bool INV, typename C> struct Dft {
 };
 template <bool INV, typename C> struct Dft<1, INV, C> { static __device__ __forceinline__ void run(C (&)[1]) {} };
 
+// one rounding whatever the compiler's contraction setting
+__device__ __forceinline__ double fma1(double a, double b, double c) { return __builtin_fma(a, b, c); }
+__device__ __forceinline__ float fma1(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+
+// The same 16-point DFT (Dft<16>'s contract: natural order in and out) in 144 operations instead of 168: two radix-4 layers,
+//      n = n1 + 4 n2,  k = 4 k1 + k2:   X[4 k1 + k2] = sum_n1 W_4^(n1 k1) W_16^(n1 k2) sum_n2 W_4^(n2 k2) x[n1 + 4 n2],
+// 2 x 4 four-point butterflies of 16 additions, and the eight constants W_16^m (m = n1 k2 = 1, 2, 2, 3, 3, 6, 6, 9; W_16^4 = -+i
+// is free) at two operations each: W = s (1 + i t) i^q with |t| <= 1, |s| >= 0.707 known at compile time, so the rotation
+// a (1 + i t) is two FMAs (two additions where |t| = 1) and the real scale s rides in the FMAs of the second layer's butterfly,
+// which stays at 16 operations: v0 + s2 u2 and u1 +- u3 (|s1| = |s3| in every column), then y +- s1 z.
+//      m   forward W_16^m              s      rotation (u.x, u.y) of a
+//      1   c1 (1 - i t1)               c1     (a.x + t1 a.y,  a.y - t1 a.x)
+//      2   c2 (1 - i)                  c2     (a.x + a.y,     a.y - a.x)
+//      3   c1 (t1 - i)                 c1     (t1 a.x + a.y,  t1 a.y - a.x)         67.5 deg = 90 deg - 22.5 deg
+//      6   -c2 (1 + i)                -c2     (a.x - a.y,     a.x + a.y)            135 deg = 180 deg - 45 deg
+//      9   -c1 (1 - i t1)             -c1     as m = 1                               202.5 deg = 180 deg + 22.5 deg
+// c1 = cos(pi/8), t1 = tan(pi/8), c2 = cos(pi/4); the inverse takes the conjugates.
+template <bool INV, typename C> struct Dft16Lean {
+    using T = decltype(C{}.x);
+    static constexpr T kC1 = (T)0.92387953251128675613;
+    static constexpr T kC2 = (T)0.70710678118654752440;
+    static constexpr T kT1 = (T)0.41421356237309504880;
+    static constexpr T scale(int m) { return m == 1 || m == 3 ? kC1 : m == 2 ? kC2 : m == 6 ? -kC2 : m == 9 ? -kC1 : (T)1; }
+    // u with W_16^(+-M) a = scale(M) u
+    template <int M> static __device__ __forceinline__ C rot(C a)
+    {
+        static_assert(M == 1 || M == 2 || M == 3 || M == 4 || M == 6 || M == 9, "products n1 k2 of a 4 x 4 split");
+        C u;
+        if constexpr (M == 1 || M == 9) {
+            constexpr T t = INV ? -kT1 : kT1;
+            u.x = fma1(t, a.y, a.x); u.y = fma1(-t, a.x, a.y);
+        } else if constexpr (M == 3) {
+            if (INV) { u.x = fma1(kT1, a.x, -a.y); u.y = fma1(kT1, a.y, a.x); }
+            else     { u.x = fma1(kT1, a.x, a.y);  u.y = fma1(kT1, a.y, -a.x); }
+        } else if constexpr (M == 4) {
+            u = mul_mi<INV>(a);
+        } else if constexpr ((M == 2) != INV) {     // a (1 - i)
+            u.x = a.x + a.y; u.y = a.y - a.x;
+        } else {                                    // a (1 + i)
+            u.x = a.x - a.y; u.y = a.x + a.y;
+        }
+        return u;
+    }
+    static __device__ __forceinline__ void dft4(C &a0, C &a1, C &a2, C &a3)
+    {
+        const C y0 = cadd(a0, a2), y1 = csub(a0, a2), y2 = cadd(a1, a3), y3 = mul_mi<INV>(csub(a1, a3));
+        a0 = cadd(y0, y2); a1 = cadd(y1, y3); a2 = csub(y0, y2); a3 = csub(y1, y3);
+    }
+    // column k2 of the second layer: a[n1] = first-layer output (n1, K2), still without its twiddle; X[k1] = bin 4 k1 + K2
+    template <int K2> static __device__ __forceinline__ void column(C &a0, C &a1, C &a2, C &a3)
+    {
+        constexpr T s1 = scale(K2), s2 = scale(2 * K2), s3 = scale(3 * K2);
+        static_assert(s3 == s1 || s3 == -s1, "the odd inputs share their scale");
+        const C u1 = rot<K2>(a1), u2 = rot<2 * K2>(a2), u3 = rot<3 * K2>(a3);
+        C y0, y1, z2, z3;
+        if constexpr (s2 == (T)1) { y0 = cadd(a0, u2); y1 = csub(a0, u2); }
+        else {
+            y0.x = fma1(s2, u2.x, a0.x); y0.y = fma1(s2, u2.y, a0.y);
+            y1.x = fma1(-s2, u2.x, a0.x); y1.y = fma1(-s2, u2.y, a0.y);
+        }
+        if constexpr (s3 == s1) { z2 = cadd(u1, u3); z3 = csub(u1, u3); } else { z2 = csub(u1, u3); z3 = cadd(u1, u3); }
+        constexpr T sq = INV ? -s1 : s1;            // y1 -+ i s1 z3
+        a0.x = fma1(s1, z2.x, y0.x);  a0.y = fma1(s1, z2.y, y0.y);
+        a2.x = fma1(-s1, z2.x, y0.x); a2.y = fma1(-s1, z2.y, y0.y);
+        a1.x = fma1(sq, z3.y, y1.x);  a1.y = fma1(-sq, z3.x, y1.y);
+        a3.x = fma1(-sq, z3.y, y1.x); a3.y = fma1(sq, z3.x, y1.y);
+    }
+    static __device__ __forceinline__ void run(C (&x)[16])
+    {
+#pragma unroll
+        for (int n1 = 0; n1 < 4; n1++) dft4(x[n1], x[n1 + 4], x[n1 + 8], x[n1 + 12]);   // x[n1 + 4 k2] = layer-1 output (n1, k2)
+        dft4(x[0], x[1], x[2], x[3]);
+        column<1>(x[4], x[5], x[6], x[7]);
+        column<2>(x[8], x[9], x[10], x[11]);
+        column<3>(x[12], x[13], x[14], x[15]);
+        // x[4 k2 + k1] holds bin 4 k1 + k2: transpose to natural order (register renaming)
+#pragma unroll
+        for (int k1 = 0; k1 < 4; k1++)
+#pragma unroll
+            for (int k2 = k1 + 1; k2 < 4; k2++) { const C s = x[4 * k2 + k1]; x[4 * k2 + k1] = x[4 * k1 + k2]; x[4 * k1 + k2] = s; }
+    }
+};
+// the 16-point butterfly of a tile: the radix-2 recursion, or (LEAN16) the 144-operation form
+template <bool LEAN16, bool INV, typename C> __device__ __forceinline__ void dft16(C (&x)[16])
+{
+    if constexpr (LEAN16) Dft16Lean<INV, C>::run(x); else Dft<16, INV, C>::run(x);
+}
+
 // LDS image: element i lives at i + (i >> 4) (one 16-byte pad after every 16 elements = row pitch 17).
 // The stride-R scatter of the early passes then hits distinct banks (ds_write_b128 is served 8 lanes at a
 // time over 32 banks; pitch 17 elements = 68 dwords = 4 mod 32), and every access of a pass is
@@ -173,12 +261,13 @@ template <int R, typename C> __device__ __forceinline__ void apply_twiddle_power
 // Applies the inter-pass twiddle w1 = exp(-+2*pi*i*k/(Ns*R)), k = j mod Ns (Ns = product of the radices of
 // the earlier passes), then the R-point DFT, and returns the output position of x[0]; x[r] belongs at
 // base + r*Ns.  w1 depends on the lane only, so callers load it once per kernel (pass_twiddle below).
-template <int N, int R, int Ns, bool INV, typename C, bool LEAN = false>
+// LEAN16 (R = 16): Dft16Lean in place of Dft<16>
+template <int N, int R, int Ns, bool INV, typename C, bool LEAN = false, bool LEAN16 = false>
 __device__ __forceinline__ int stockham_butterfly(C (&x)[R], int j, C w1)
 {
     int k = j & (Ns - 1);
     if constexpr (Ns > 1) { if constexpr (LEAN) apply_twiddle_powers_lean<R>(x, w1); else apply_twiddle_powers<R>(x, w1); }
-    Dft<R, INV, C>::run(x);
+    if constexpr (R == 16) dft16<LEAN16, INV>(x); else Dft<R, INV, C>::run(x);
     return (j - k) * R + k;
 }
 
@@ -325,7 +414,8 @@ template <bool INV, typename C> struct FftRR<4096, INV, C> {
 #define QH_SPLIT_SWIZZLE 0
 #endif
 constexpr int split4096_lds_bytes(int scalar_bytes) { return (QH_SPLIT_SWIZZLE ? 4096 : 4096 + QH_SPLIT_PAD * 256) * scalar_bytes; }
-template <bool INV, typename C> struct FftSplit4096 {
+// LEAN16: the 16-point butterflies are Dft16Lean (the overlap-save tiles); the exchange and the LDS image do not depend on it
+template <bool INV, typename C, bool LEAN16 = false> struct FftSplit4096 {
     using T = decltype(C{}.x);
     using Tw = typename FftRR<4096, INV, C>::Tw;
     static constexpr bool kSwizzle = QH_SPLIT_SWIZZLE != 0;
@@ -382,15 +472,15 @@ template <bool INV, typename C> struct FftSplit4096 {
     static __device__ __forceinline__ void run_at(C (&x)[16], void *lds_raw, const Tw &t, int j)
     {
         T *lds = reinterpret_cast<T *>(lds_raw);
-        Dft<16, INV, C>::run(x);                                    // pass 1: x[r] = in[j + 256 r]
+        dft16<LEAN16, INV>(x);                                      // pass 1: x[r] = in[j + 256 r]
         // element j*16 + r  ->  j + 256 r'   (sphys: 18 j + r, and sphys(j) + 288 r')
         if constexpr (kSwizzle) exchange_sw<1>(x, lds, j, 0);
         else exchange<1, 256 + 16 * kPad>(x, lds, (16 + kPad) * j, sphys(j));
-        const int base = stockham_butterfly<4096, 16, 16, INV, C, LEAN>(x, j, t.a[0]);      // pass 2: outputs at base + 16 r
+        const int base = stockham_butterfly<4096, 16, 16, INV, C, LEAN, LEAN16>(x, j, t.a[0]);      // pass 2: outputs at base + 16 r
         __syncthreads();
         if constexpr (kSwizzle) exchange_sw<2>(x, lds, j, base);
         else exchange<16 + kPad, 256 + 16 * kPad>(x, lds, sphys(base), sphys(j));
-        stockham_butterfly<4096, 16, 256, INV, C, LEAN>(x, j, t.b);          // pass 3: x[r] is element j + 256 r
+        stockham_butterfly<4096, 16, 256, INV, C, LEAN, LEAN16>(x, j, t.b);          // pass 3: x[r] is element j + 256 r
     }
 
     // The transform WITHOUT the stage that would combine the D decimated sequences x[D m + a] (plan 16 x 16 x 16/D x [D], the last
@@ -405,10 +495,10 @@ template <bool INV, typename C> struct FftSplit4096 {
         constexpr int R3 = 16 / D;
         const int j = threadIdx.x;
         T *lds = reinterpret_cast<T *>(lds_raw);
-        Dft<16, INV, C>::run(x);
+        dft16<LEAN16, INV>(x);
         if constexpr (kSwizzle) exchange_sw<1>(x, lds, j, 0);
         else exchange<1, 256 + 16 * kPad>(x, lds, (16 + kPad) * j, sphys(j));
-        const int base = stockham_butterfly<4096, 16, 16, INV>(x, j, t.a[0]);
+        const int base = stockham_butterfly<4096, 16, 16, INV, C, false, LEAN16>(x, j, t.a[0]);
         __syncthreads();
         if constexpr (kSwizzle) exchange_sw<2>(x, lds, j, base);
         else exchange<16 + kPad, 256 + 16 * kPad>(x, lds, sphys(base), sphys(j));
@@ -592,7 +682,8 @@ template <bool INV> struct Fft6144 {
 };
 
 // What the overlap-save kernels call: registers (strided layout) -> registers, LDS image of lds_bytes.
-template <int N, bool INV, typename C> struct TileFft {
+// LEAN16 reaches the split fp64 4096-point transform only (FftSplit4096); every other plan keeps Dft<16>.
+template <int N, bool INV, typename C, bool LEAN16 = false> struct TileFft {
     static constexpr bool kSplit = N == 4096 && sizeof(C) == 16;
     static constexpr int kLdsBytes = kSplit ? split4096_lds_bytes(8) : lds_elems<N>() * (int)sizeof(C);
     using Tw = typename FftRR<N, INV, C>::Tw;
@@ -600,7 +691,7 @@ template <int N, bool INV, typename C> struct TileFft {
     static __device__ __forceinline__ void run(C (&x)[N / NT], void *lds, const Tw &t)
     {
         if constexpr (kSplit) {
-            FftSplit4096<INV, C>::run(x, lds, t);
+            FftSplit4096<INV, C, LEAN16>::run(x, lds, t);
         } else {
             FftRR<N, INV, C>::first(x, reinterpret_cast<C *>(lds));
             FftRR<N, INV, C>::rest(reinterpret_cast<C *>(lds), x, t);
@@ -609,7 +700,7 @@ template <int N, bool INV, typename C> struct TileFft {
     template <int D> static __device__ __forceinline__ void run_poly(C (&x)[N / NT], void *lds, const Tw &t)
     {
         static_assert(kSplit, "polyphase plan: the fp64 4096-point transform");
-        FftSplit4096<INV, C>::template run_poly<D>(x, lds, t);
+        FftSplit4096<INV, C, LEAN16>::template run_poly<D>(x, lds, t);
     }
 };
 

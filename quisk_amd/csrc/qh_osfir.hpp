@@ -362,8 +362,10 @@ __global__ __launch_bounds__(NT, (osfir_min_waves<T, D, OUTMIX, NFFT>())) void o
     static_assert(E % D == 0 && EO >= 1, "decimation must divide NFFT/256");
     static_assert(NOUT >= 2 * NT, "NFFT/D must be >= 512");
     static_assert(E <= 32, "validity bits are kept in one word");
-    using Fwd = TileFft<NFFT, false, C>;
-    using Inv = TileFft<NOUT, true, C>;
+    // fp64 4096-point tiles: 144-operation butterflies (Dft16Lean).  Not the PAIR tiles: they hold 128 registers either way, and with
+    // the new butterfly they spill 15 of them where they spill 8 with Dft<16> (profiles/dft16_lean.md)
+    using Fwd = TileFft<NFFT, false, C, !PAIR>;
+    using Inv = TileFft<NOUT, true, C, !PAIR>;
     extern __shared__ __align__(16) unsigned char smem[];
     void *lds = smem;
 
@@ -765,8 +767,8 @@ template <bool METER, bool EGRESS, bool MROW = false>
 __global__ __launch_bounds__(kOsfir8kThreads, 4) void osfir8k_kernel(OsfirArgs<double> a)
 {
     using C = double2;
-    using SF = FftSplit4096<false, C>;
-    using SI = FftSplit4096<true, C>;
+    using SF = FftSplit4096<false, C, true>;
+    using SI = FftSplit4096<true, C, true>;
     constexpr int N = 8192, P = kOsfir8kP, L = kOsfir8kLout;
     extern __shared__ __align__(16) unsigned char smem8k[];
     const int T = threadIdx.x, j = T & 255;
