@@ -98,6 +98,28 @@ int qh_rxa_SetRXAPanelGain1(qh_rxa *e, int ch, double gain);
 int qh_rxa_SetRXAPanelGain2(qh_rxa *e, int ch, double gainI, double gainQ);
 int qh_rxa_SetRXAPanelSelect(qh_rxa *e, int ch, int select);
 int qh_rxa_SetRXAPanelCopy(qh_rxa *e, int ch, int copy);
+int qh_rxa_SetRXAPanelPan(qh_rxa *e, int ch, double pan);       /* wdsp/patchpanel.c:158-176: writes gain2I / gain2Q, as SetRXAPanelGain2 does (the last writer wins); a pan that is not finite: QH_ERR_INVALID */
+int qh_rxa_SetRXAPanelBinaural(qh_rxa *e, int ch, int bin);     /* wdsp/patchpanel.c:186-192: copy = 1 - bin, the field SetRXAPanelCopy writes */
+/* The AGC's display-side knobs (wdsp/wcpAGC.c:440-557): host arithmetic on the values loadWcpAGC derives from the channel's settings
+ * (wcpAGC.c:115-146: out_target, min_volts, hang_level; create_rxa's out_targ 1.0 and n_tau 4, RXA.c:335-358).  A setter takes effect at
+ * the next process call; a getter (one channel, not -1) reads the host's settings and waits for nothing on the device.
+ *   SetRXAAGCThresh   max_gain = out_target / (var_gain 10^((thresh + noise_offset) / 20)), noise_offset = 10 log10((nbp0.fhigh -
+ *                     nbp0.flow) size / rate) with nbp0's edges at the moment of the call (a later RXANBPSetFreqs does not move max_gain)
+ *                     and the caller's display FFT size and rate
+ *   GetRXAAGCThresh   20 log10(min_volts) - noise_offset
+ *   SetRXAAGCHangLevel     max_input > min_volts: hang_thresh = 1 + 0.125 log10(max(1e-8, (10^(level / 20) - min_volts) / (max_input -
+ *                     min_volts))), else 1 -- the field SetRXAAGCHangThreshold writes as percent / 100
+ *   GetRXAAGCHangLevel     20 log10(hang_level / 0.637);  GetRXAAGCHangThreshold  (int)(100 hang_thresh);  GetRXAAGCTop  20 log10(max_gain)
+ * Refused with QH_ERR_INVALID, nothing changed (the reference checks none of this): an argument that is not finite; size or rate not
+ * above 0; an nbp0 band that is not wider than 0 (the reference would take the log of it); a thresh so far out that max_gain would not be
+ * a finite number above 0; a max_input that is not above 0. */
+int qh_rxa_SetRXAAGCThresh(qh_rxa *e, int ch, double thresh, double size, double rate);     /* wdsp/wcpAGC.c:499-511 */
+int qh_rxa_GetRXAAGCThresh(qh_rxa *e, int ch, double *thresh, double size, double rate);    /* wdsp/wcpAGC.c:487-497 */
+int qh_rxa_SetRXAAGCHangLevel(qh_rxa *e, int ch, double hangLevel);                         /* wdsp/wcpAGC.c:449-466 */
+int qh_rxa_GetRXAAGCHangLevel(qh_rxa *e, int ch, double *hangLevel);                        /* wdsp/wcpAGC.c:440-447 */
+int qh_rxa_GetRXAAGCHangThreshold(qh_rxa *e, int ch, int *hangthreshold);                   /* wdsp/wcpAGC.c:468-475 */
+int qh_rxa_GetRXAAGCTop(qh_rxa *e, int ch, double *max_agc);                                /* wdsp/wcpAGC.c:513-520 */
+int qh_rxa_SetRXAAGCMaxInputLevel(qh_rxa *e, int ch, double level);                         /* wdsp/wcpAGC.c:550-557 */
 int qh_rxa_SetRXAAMDSBMode(qh_rxa *e, int ch, int sbmode);
 int qh_rxa_SetRXAAMDRun(qh_rxa *e, int ch, int run);             /* wdsp/amd.c:264-277; run = 1 on a channel in FM mode (both detectors in a row in the reference) is refused at the next process call */
 int qh_rxa_SetRXAFMLimRun(qh_rxa *e, int ch, int run);           /* wdsp/fmd.c:336-347: the FM detector's limiter */
@@ -220,6 +242,17 @@ int qh_rxa_RXANBPSetNotchesRun(qh_rxa *e, int ch, int run);
 int qh_rxa_RXANBPSetWindow(qh_rxa *e, int ch, int wintype);
 int qh_rxa_RXANBPSetAutoIncrease(qh_rxa *e, int ch, int autoincr);
 int qh_rxa_RXASetMP(qh_rxa *e, int ch, int mp);                  /* wdsp/RXA.c:948-958: minimum-phase filters (mp_imp, fir.c:319) in every fircore of the channel's chain */
+/* nc, mp and window of nbp0, bpsnba and bp1, one setting per stage: RXASetNC / RXASetMP are these calls and the four FM, EQ and FMSQ ones
+ * (RXA.c:934-958).  Each acts only on a value that changed.  A new nc zeroes that one stage's delay line (setNc_fircore, firmin.c:455-467)
+ * and leaves every other stage's; a new mp or window designs the masks again and keeps the line (setMp_fircore, setImpulse_fircore).
+ * Refused with QH_ERR_INVALID, nothing changed: an nc that is not a power of two in [dsp_size, 65536]; a window type other than 0 or 1. */
+int qh_rxa_RXANBPSetNC(qh_rxa *e, int ch, int nc);                              /* wdsp/nbp.c:563-576 */
+int qh_rxa_RXANBPSetMP(qh_rxa *e, int ch, int mp);                              /* wdsp/nbp.c:578-588 */
+int qh_rxa_RXABPSNBASetNC(qh_rxa *e, int ch, int nc);                           /* wdsp/snb.c:829-842 */
+int qh_rxa_RXABPSNBASetMP(qh_rxa *e, int ch, int mp);                           /* wdsp/snb.c:844-855 */
+int qh_rxa_SetRXABandpassNC(qh_rxa *e, int ch, int nc);                         /* wdsp/bandpass.c:429-445 */
+int qh_rxa_SetRXABandpassMP(qh_rxa *e, int ch, int mp);                         /* wdsp/bandpass.c:447-457 */
+int qh_rxa_SetRXABandpassWindow(qh_rxa *e, int ch, int wintype);                /* wdsp/bandpass.c:411-427 */
 int qh_rxa_SetRXAAMDFadeLevel(qh_rxa *e, int ch, int levelfade);
 int qh_rxa_SetRXAFMDeviation(qh_rxa *e, int ch, double deviation);
 int qh_rxa_SetRXACTCSSFreq(qh_rxa *e, int ch, double freq);
@@ -394,6 +427,27 @@ void SetRXAPanelGain1(int channel, double gain);                                
 void SetRXAPanelGain2(int channel, double gainI, double gainQ);                  /* wdsp/patchpanel.c:147-154 */
 void SetRXAPanelSelect(int channel, int select);                                 /* wdsp/patchpanel.c:131-137 */
 void SetRXAPanelCopy(int channel, int copy);                                     /* wdsp/patchpanel.c:175-181 */
+void SetRXAPanelPan(int channel, double pan);                                    /* wdsp/patchpanel.c:158-176 */
+void SetRXAPanelBinaural(int channel, int bin);                                  /* wdsp/patchpanel.c:186-192 */
+/* (the refusals of the qh_rxa_* forms above set qh_wdsp_status(); a getter of a channel that is not open leaves its result alone) */
+void SetRXAAGCThresh(int channel, double thresh, double size, double rate);      /* wdsp/wcpAGC.c:499-511 */
+void GetRXAAGCThresh(int channel, double *thresh, double size, double rate);     /* wdsp/wcpAGC.c:487-497 */
+void SetRXAAGCHangLevel(int channel, double hangLevel);                          /* wdsp/wcpAGC.c:449-466 */
+void GetRXAAGCHangLevel(int channel, double *hangLevel);                         /* wdsp/wcpAGC.c:440-447 */
+void GetRXAAGCHangThreshold(int channel, int *hangthreshold);                    /* wdsp/wcpAGC.c:468-475 */
+void GetRXAAGCTop(int channel, double *max_agc);                                 /* wdsp/wcpAGC.c:513-520 */
+void SetRXAAGCMaxInputLevel(int channel, double level);                          /* wdsp/wcpAGC.c:550-557 */
+void RXANBPSetNC(int channel, int nc);                                           /* wdsp/nbp.c:563-576 */
+void RXANBPSetMP(int channel, int mp);                                           /* wdsp/nbp.c:578-588 */
+void RXABPSNBASetNC(int channel, int nc);                                        /* wdsp/snb.c:829-842 */
+void RXABPSNBASetMP(int channel, int mp);                                        /* wdsp/snb.c:844-855 */
+void SetRXABandpassNC(int channel, int nc);                                      /* wdsp/bandpass.c:429-445 */
+void SetRXABandpassMP(int channel, int mp);                                      /* wdsp/bandpass.c:447-457 */
+void SetRXABandpassWindow(int channel, int wintype);                             /* wdsp/bandpass.c:411-427 */
+/* There are no FFTW plans to make here: WDSPwisdom returns at once, as the reference does when its wisdom file already exists (it touches
+ * no file and ignores a null or unwritable directory), and the status string stays the empty one the reference has in that case. */
+void WDSPwisdom(char *directory);                                                /* wdsp/wisdom.c:38-121 */
+char *wisdom_get_status(void);                                                   /* wdsp/wisdom.c:32-36: a static, NUL-terminated string */
 void SetRXAAMDSBMode(int channel, int sbmode);                                   /* wdsp/amd.c:277-283 */
 void SetRXAAMDRun(int channel, int run);                                         /* wdsp/amd.c:264-277 */
 void SetRXAFMLimRun(int channel, int run);                                       /* wdsp/fmd.c:336-347 */

@@ -473,6 +473,7 @@ int Engine::chain_needs(ChainCall &k)
         if (c.emnr_run && !emnr_tables) return set_error(QH_ERR_INVALID, "EMNR needs its gain tables first (qh_rxa_SetEMNRTables: WDSP's `calculus` and `zetaHat.bin` data)");
         if (c.nbp_run) { k.any_nbp = true; if (c.nbp_nc > k.nc_max) k.nc_max = c.nbp_nc; } else k.every_nbp = false;
         if (c.bp1_run) { k.any_bp1 = true; if (c.bp1_nc > k.nc_max) k.nc_max = c.bp1_nc; }
+        if (c.snba_run && c.snb_nc > k.nc_max) k.nc_max = c.snb_nc;       // bpsnba's own nc (RXABPSNBASetNC)
         if (c.fmd_run) {
             k.nc_max = std::max({ k.nc_max, c.fm_nc_de, c.fm_nc_aud });
             // fir_bandpass's upper edge 1.1 f_high (fmd.c:115) and fc_impulse's grid need it below the Nyquist frequency
@@ -526,12 +527,12 @@ int Engine::plan_long(ChainCall &k)
     // the only long channel leaving took the stage to the short form (its line cut to 4095 samples) and came back to zeros behind
     // them: one long call 0.65 off (walk rxa_long 900190, found by round 6's seed sweep; in the suite since).
     // (long_live: the channel has run the stage with such an nc since RXASetNC last zeroed its lines.)
-    // The FM pair takes its count from the larger of nc_de / nc_aud together, bpsnba follows nbp0's nc (its nbp shares it, refresh_params).
+    // The FM pair takes its count from the larger of nc_de / nc_aud together; bpsnba goes by its own nc (RXABPSNBASetNC; RXASetNC keeps it at nbp0's).
     for (int ch = 0; ch < nch; ch++) {
         const ChanCfg &c = cfg[(size_t)ch];
         const int run[FC_COUNT] = { c.nbp_run, c.bp1_run, c.fmd_run, c.fmd_run, c.snba_run, 0, 0 };
         const int fm_nc = std::max(c.fm_nc_de, c.fm_nc_aud);
-        const int nc[FC_COUNT] = { c.nbp_nc, c.bp1_nc, fm_nc, fm_nc, c.nbp_nc, 0, 0 };
+        const int nc[FC_COUNT] = { c.nbp_nc, c.bp1_nc, fm_nc, fm_nc, c.snb_nc, 0, 0 };
         for (int s = 0; s < FC_COUNT; s++) {
             if (!fc[s].can_long) continue;
             Fircore::Chan &r = fc[s].chan[(size_t)ch];

@@ -74,7 +74,9 @@ struct ChanCfg {
     int shift_run = 1; double shift_freq = 0.0;                 // RXA.c:39-45
     int shift_on_device = 1;                                    // whether the device phase is live or parked (nco_park_kernel)
     int nbp_run = 1, nbp_nc = 2048, nbp_wintype = 0;            // RXA.c:90-106
-    int mp = 0;                                                 // RXASetMP, RXA.c:948
+    // minimum-phase impulse responses, one flag per fircore as in the reference (RXANBPSetMP nbp.c:578, SetRXABandpassMP bandpass.c:447,
+    // RXABPSNBASetMP snb.c:844); RXASetMP (RXA.c:948) writes all of them
+    int nbp_mp = 0, bp1_mp = 0, snb_mp = 0;
     // notch database (create_notchdb RXA.c:85-87) and nbp0's use of it (fnfrun 0, autoincr 1: RXA.c:92,104)
     std::vector<Notch> notches;
     double ndb_tunefreq = 0.0, ndb_shift = 0.0;
@@ -84,6 +86,7 @@ struct ChanCfg {
     int agc_run = 1, agc_mode = 3; double agc_fixed = 1000.0;   // RXA.c:335-358
     double agc_tau_attack = 0.001, agc_tau_decay = 0.250, agc_max_gain = 10000.0, agc_var_gain = 1.5;
     double agc_hangtime = 0.250, agc_hang_thresh = 0.250;
+    double agc_max_input = 1.0;                                 // SetRXAAGCMaxInputLevel, wcpAGC.c:550-557
     bool agc_dirty = true;
     bool agc_on() const { return agc_run && agc_mode != 0; }
     int agc_abuf = -1;                  // attack_buffsize last uploaded
@@ -107,6 +110,7 @@ struct ChanCfg {
     // emnr (create_emnr of create_rxa, RXA.c:319-332)
     // snba (wdsp/snb.c) and its bandpass bpsnba (snb.c:696-855; run / position follow the mode, RXA.c:883-917)
     int snba_run = 0;
+    int snb_nc = 2048;                                          // bpsnba's own nc (RXABPSNBASetNC, snb.c:829-842; made with nbp0's, RXA.c:114)
     bool snba_flush = false, snba_taps_dirty = true, snba_rout_flush = false, snb_dirty = true, snb_flush = false;
     double snba_f_low = 200.0, snba_f_high = 0.0;               // outresamp fc_low / fcin (snb.c:45-46, resample.c:195-204)
     int snb_pos() const {
@@ -555,7 +559,7 @@ struct Engine {
     void launch_front_masks(int n);
     void launch_ssql_flush();
     int refresh_params();
-    std::vector<cd> notched(const ChanCfg &c, double f_low, double f_high, double scale) const;
+    std::vector<cd> notched(const ChanCfg &c, int nc, double f_low, double f_high, double scale) const;
     int snb_mask(ChanCfg &c, int ch);
     // the layout the one-tile masks are built for: a stage's masks are made again when it moves (pick_band_tile)
     int mask_key() const { return 2 * bnfft + (band2g ? 1 : 0); }

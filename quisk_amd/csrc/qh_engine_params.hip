@@ -209,7 +209,7 @@ int Engine::refresh_params()
             if (d.run) {
                 // calc_nbp_impulse, wdsp/nbp.c:221-238; bp1: wdsp/bandpass.c:302
                 const double scale = d.gain / (double)(2 * dsp_size);
-                h = d.notch ? notched(c, d.flow, d.fhigh, scale) : fir_bandpass(d.nc, d.flow, d.fhigh, (double)dsp_rate, d.wintype, 1, scale);
+                h = d.notch ? notched(c, d.nc, d.flow, d.fhigh, scale) : fir_bandpass(d.nc, d.flow, d.fhigh, (double)dsp_rate, d.wintype, 1, scale);
                 if (d.mp) h = mp_imp(h, 16, 0);             // calc_fircore, wdsp/firmin.c:327-328
                 // the reference's unnormalised inverse FFT of 2*size points restores the 1/(2*size)
                 for (auto &v : h) v *= (double)(2 * dsp_size);
@@ -272,16 +272,16 @@ int Engine::refresh_params()
             if (int rc = put_row(epi, ch, e)) return rc;
             c.epi_dirty = false;
         }
-        if (c.nbp_dirty) c.snb_dirty = true;        // bpsnba's nbp shares nc, window, auto-increase, mp and the notch database with nbp0
+        if (c.nbp_dirty) c.snb_dirty = true;        // bpsnba's nbp shares window, auto-increase and the notch database with nbp0 (nc and mp are its own)
         if (c.snb_dirty && c.snba_run && fc[FC_SNB].mask) if (int rc = snb_mask(c, ch)) return rc;
         if (c.snb_flush && fc[FC_SNB].hist[0]) if (int rc = zero_rows(fc[FC_SNB], ch)) return rc;         // setNc_fircore zeroes the delay line
         c.snb_flush = false;
         if (c.nbp_dirty) {
-            if (int rc = design_band(fc[FC_NBP], c, ch, { c.nbp_run, c.nbp_nc, c.nbp_wintype, c.mp, c.fnfrun, c.nbp_flow, c.nbp_fhigh, c.nbp_gain }, last_nbp)) return rc;
+            if (int rc = design_band(fc[FC_NBP], c, ch, { c.nbp_run, c.nbp_nc, c.nbp_wintype, c.nbp_mp, c.fnfrun, c.nbp_flow, c.nbp_fhigh, c.nbp_gain }, last_nbp)) return rc;
             c.nbp_dirty = false;
         }
         if (c.bp1_dirty) {
-            if (int rc = design_band(fc[FC_BP1], c, ch, { c.bp1_run, c.bp1_nc, c.bp1_wintype, c.mp, 0, c.bp1_flow, c.bp1_fhigh, c.bp1_gain }, last_bp1)) return rc;
+            if (int rc = design_band(fc[FC_BP1], c, ch, { c.bp1_run, c.bp1_nc, c.bp1_wintype, c.bp1_mp, 0, c.bp1_flow, c.bp1_fhigh, c.bp1_gain }, last_bp1)) return rc;
             c.bp1_dirty = false;
             lists_dirty = true;             // the channel pairs of the real bp1 filters follow the designs
         }
@@ -299,14 +299,14 @@ int Engine::refresh_params()
     return QH_OK;
 }
 
-// calc_nbp_impulse with the notches, wdsp/nbp.c:221-232: bands in absolute frequency, filter in baseband
-std::vector<cd> Engine::notched(const ChanCfg &c, double f_low, double f_high, double scale) const
+// calc_nbp_impulse with the notches, wdsp/nbp.c:221-232: bands in absolute frequency, filter in baseband; nc: the stage's own (nbp0's or bpsnba's)
+std::vector<cd> Engine::notched(const ChanCfg &c, int nc, double f_low, double f_high, double scale) const
 {
     const double offset = c.ndb_tunefreq + c.ndb_shift;
-    const double minwidth = (c.nbp_wintype == 1 ? 2200.0 : 1600.0) / (c.nbp_nc / 256) * ((double)dsp_rate / 48000);
+    const double minwidth = (c.nbp_wintype == 1 ? 2200.0 : 1600.0) / (nc / 256) * ((double)dsp_rate / 48000);
     std::vector<std::pair<double, double>> bands = make_nbp(c.notches, minwidth, c.autoincr, f_low + offset, f_high + offset, nullptr);
     for (auto &b : bands) { b.first -= offset; b.second -= offset; }
-    return fir_mbandpass(c.nbp_nc, bands, (double)dsp_rate, scale, c.nbp_wintype);
+    return fir_mbandpass(nc, bands, (double)dsp_rate, scale, c.nbp_wintype);
 }
 
 // recalc_bpsnba_filter (snb.c:807-822) with RXAbpsnbaCheck's frequencies (RXA.c:829-881): 250..5700 Hz on the mode's side
@@ -322,8 +322,8 @@ int Engine::snb_mask(ChanCfg &c, int ch)
     }
     const double scale = 1.0 / (double)(2 * dsp_size);
     if (fc[FC_SNB].parts > 1) if (int rc = long_stage_alloc(fc[FC_SNB])) return rc;
-    std::vector<cd> h = run_notches ? notched(c, f_low, f_high, scale) : fir_bandpass(c.nbp_nc, f_low, f_high, (double)dsp_rate, c.nbp_wintype, 1, scale);
-    if (c.mp) h = mp_imp(h, 16, 0);
+    std::vector<cd> h = run_notches ? notched(c, c.snb_nc, f_low, f_high, scale) : fir_bandpass(c.snb_nc, f_low, f_high, (double)dsp_rate, c.nbp_wintype, 1, scale);
+    if (c.snb_mp) h = mp_imp(h, 16, 0);
     for (auto &v : h) v *= (double)(2 * dsp_size);
     std::vector<cd> m;
     if (int rc = put_taps(fc[FC_SNB], ch, h, m)) return rc;
@@ -505,7 +505,7 @@ void Engine::build_lists(std::vector<int> (&h)[L_COUNT])
     h[L_AGC_CUR].insert(h[L_AGC_CUR].end(), stale_cur.begin(), stale_cur.end());
     h[L_AGC_OTHER].insert(h[L_AGC_OTHER].end(), stale_other.begin(), stale_other.end());
     // partners: neighbours in the list, ordered so that equal designs are neighbours; a channel left over is its own partner
-    auto bp1_real = [&](int ch) { const ChanCfg &c = cfg[(size_t)ch]; return c.bp1_run && c.bp1_flow == -c.bp1_fhigh && !c.mp; };
+    auto bp1_real = [&](int ch) { const ChanCfg &c = cfg[(size_t)ch]; return c.bp1_run && c.bp1_flow == -c.bp1_fhigh && !c.bp1_mp; };
     auto bp1_same = [&](int x, int y) {
         const ChanCfg &p = cfg[(size_t)x], &q = cfg[(size_t)y];
         return p.bp1_nc == q.bp1_nc && p.bp1_wintype == q.bp1_wintype && p.bp1_fhigh == q.bp1_fhigh && p.bp1_gain == q.bp1_gain;
@@ -845,7 +845,7 @@ int Engine::prm_agc(ChanCfg &c, int ch)
 {
     if (!c.agc_dirty) return QH_OK;
     // create_rxa's constants (RXA.c:335-358)
-    const AgcParam q = load_wcpagc((double)dsp_rate, c.agc_tau_attack, c.agc_tau_decay, 4.0, c.agc_max_gain, c.agc_var_gain, 1.0, 1.0, 0.250, 0.005,
+    const AgcParam q = load_wcpagc((double)dsp_rate, c.agc_tau_attack, c.agc_tau_decay, 4.0, c.agc_max_gain, c.agc_var_gain, c.agc_max_input, 1.0, 0.250, 0.005,
                                    5.0, 1, 0.500, c.agc_hangtime, c.agc_hang_thresh, 0.100);
     if (q.attack_buffsize + 2 > kAgcRing)
         return set_error(QH_ERR_UNSUPPORTED, "AGC attack of %g s needs a look-ahead of %d samples (limit %d)", c.agc_tau_attack,
@@ -1827,7 +1827,7 @@ int Engine::set_rates(int new_in, int new_dsp, int new_out, int new_size)
     if (int rc = check_rates("qh_rxa_set_rates", new_size, new_in, new_dsp, new_out, &new_D)) return rc;
     for (const ChanCfg &c : cfg) {
         // setSize_nbp / setSize_bandpass: "'size' must be <= 'nc'" (nbp.c:308, bandpass.c:345); the other fircores are planned the same way
-        const int nc = std::min({ c.nbp_nc, c.bp1_nc, c.fm_nc_de, c.fm_nc_aud, c.fmsq_nc, c.eqp_nc });
+        const int nc = std::min({ c.nbp_nc, c.snb_nc, c.bp1_nc, c.fm_nc_de, c.fm_nc_aud, c.fmsq_nc, c.eqp_nc });
         if (new_size > nc) return set_error(QH_ERR_UNSUPPORTED, "dsp_size %d above nc %d of channel %d: size must be <= nc (wdsp/nbp.c:308)", new_size, nc, (int)(&c - cfg.data()));
         if (c.emnr_run && new_size > kEmnrIncr) return set_error(QH_ERR_UNSUPPORTED, "EMNR: dsp_size up to %d", kEmnrIncr);
         if (c.snba_run && !snba_accepts(new_dsp, new_size)) return set_error(QH_ERR_UNSUPPORTED, "%s", snba_accepted());
@@ -1859,7 +1859,7 @@ static ChanCfg settings_of(const ChanCfg &o, int dsp_rate)
 {
     // a member added to ChanCfg is a setting (kept by the copy below) or a note of work (to be put back to its default here): this
     // reminder fails to compile until its author has looked
-    static_assert(sizeof(ChanCfg) == 904, "ChanCfg changed: see to settings_of, then update the size");
+    static_assert(sizeof(ChanCfg) == 920, "ChanCfg changed: see to settings_of, then update the size");
     ChanCfg c = o;
     const ChanCfg d;
     c.shift_on_device = d.shift_on_device;

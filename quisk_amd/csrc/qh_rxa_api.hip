@@ -310,16 +310,63 @@ int qh_rxa_debug_fm_rows(qh_rxa *h, int *de_rows, int *aud_rows, long long *desi
     return QH_OK;
 }
 
+// nbp0's, bpsnba's and bp1's nc, mp and window, per stage (nbp.c:563-588, snb.c:829-855, bandpass.c:411-457).  Each acts only on a changed
+// value, as there.  A new nc zeroes that stage's delay line and nothing long is held any more (setNc_fircore, firmin.c:454-466); a new mp
+// or window designs the masks again and keeps the line (setMp_fircore, setImpulse_fircore).  which: FC_NBP, FC_SNB or FC_BP1.
+static void band_set_nc(Engine &e, ChanCfg &c, int which, int nc)
+{
+    int &cur = which == FC_NBP ? c.nbp_nc : which == FC_SNB ? c.snb_nc : c.bp1_nc;
+    if (cur == nc) return;
+    cur = nc;
+    (which == FC_NBP ? c.nbp_dirty : which == FC_SNB ? c.snb_dirty : c.bp1_dirty) = true;
+    (which == FC_NBP ? c.nbp_flush : which == FC_SNB ? c.snb_flush : c.bp1_flush) = true;
+    e.fc[which].chan[(size_t)(&c - e.cfg.data())].long_live = false;
+}
+static void band_set_mp(ChanCfg &c, int which, int mp)
+{
+    int &cur = which == FC_NBP ? c.nbp_mp : which == FC_SNB ? c.snb_mp : c.bp1_mp;
+    if (cur == mp) return;
+    cur = mp;
+    (which == FC_NBP ? c.nbp_dirty : which == FC_SNB ? c.snb_dirty : c.bp1_dirty) = true;
+}
+static int band_nc_check(const qh_rxa *h, const char *who, int nc)
+{
+    if (nc < 1 || (nc & (nc - 1)) || nc > kLongNcMax || (h && nc < h->e.dsp_size))
+        return set_error(QH_ERR_INVALID, "%s: nc must be a power of two in [dsp_size, %d]", who, kLongNcMax);
+    return QH_OK;
+}
+int qh_rxa_RXANBPSetNC(qh_rxa *h, int ch, int nc)
+{
+    if (int rc = band_nc_check(h, "RXANBPSetNC", nc)) return rc;
+    FOR_CH(h, ch, { band_set_nc(h->e, c, FC_NBP, nc); });
+}
+int qh_rxa_RXABPSNBASetNC(qh_rxa *h, int ch, int nc)
+{
+    if (int rc = band_nc_check(h, "RXABPSNBASetNC", nc)) return rc;
+    FOR_CH(h, ch, { band_set_nc(h->e, c, FC_SNB, nc); });
+}
+int qh_rxa_SetRXABandpassNC(qh_rxa *h, int ch, int nc)
+{
+    if (int rc = band_nc_check(h, "SetRXABandpassNC", nc)) return rc;
+    FOR_CH(h, ch, { band_set_nc(h->e, c, FC_BP1, nc); });
+}
+int qh_rxa_RXANBPSetMP(qh_rxa *h, int ch, int mp) { FOR_CH(h, ch, { band_set_mp(c, FC_NBP, mp ? 1 : 0); }); }
+int qh_rxa_RXABPSNBASetMP(qh_rxa *h, int ch, int mp) { FOR_CH(h, ch, { band_set_mp(c, FC_SNB, mp ? 1 : 0); }); }
+int qh_rxa_SetRXABandpassMP(qh_rxa *h, int ch, int mp) { FOR_CH(h, ch, { band_set_mp(c, FC_BP1, mp ? 1 : 0); }); }
+// (fir_bandpass knows the windows 0 and 1, fir.c:94-118: any other value is refused and changes nothing)
+int qh_rxa_SetRXABandpassWindow(qh_rxa *h, int ch, int wintype)
+{
+    if (wintype != 0 && wintype != 1) return set_error(QH_ERR_INVALID, "SetRXABandpassWindow: wintype %d (0 or 1)", wintype);
+    FOR_CH(h, ch, { if (c.bp1_wintype != wintype) { c.bp1_wintype = wintype; c.bp1_dirty = true; } });
+}
+
 int qh_rxa_RXASetNC(qh_rxa *h, int ch, int nc)
 {
     if (nc < 1 || (nc & (nc - 1)) || nc > kLongNcMax || (h && nc < h->e.dsp_size))
         return set_error(QH_ERR_UNSUPPORTED, "nc must be a power of two in [dsp_size, %d]", kLongNcMax);
     FOR_CH(h, ch, {
-        // (setNc_fircore zeroes the delay lines, firmin.c:454-466: nothing long is held any more)
-        Fircore *fc = h->e.fc;
-        const size_t i = (size_t)(&c - h->e.cfg.data());
-        if (c.nbp_nc != nc) { c.nbp_nc = nc; c.nbp_dirty = true; c.nbp_flush = true; c.snb_flush = true; fc[FC_NBP].chan[i].long_live = fc[FC_SNB].chan[i].long_live = false; }
-        if (c.bp1_nc != nc) { c.bp1_nc = nc; c.bp1_dirty = true; c.bp1_flush = true; fc[FC_BP1].chan[i].long_live = false; }
+        // RXANBPSetNC, RXABPSNBASetNC, SetRXABandpassNC, wdsp/RXA.c:938-940
+        band_set_nc(h->e, c, FC_NBP, nc); band_set_nc(h->e, c, FC_SNB, nc); band_set_nc(h->e, c, FC_BP1, nc);
         fm_set_nc(h->e, c, 0, nc); fm_set_nc(h->e, c, 1, nc);       // SetRXAFMNCde / SetRXAFMNCaud, wdsp/RXA.c:943-944
         c.fmsq_nc = nc;                         // SetRXAFMSQNC, wdsp/RXA.c:942
         if (c.eqp_nc != nc) { c.eqp_nc = nc; c.eqp_dirty = true; c.eqp_flush = true; }      // SetRXAEQNC, wdsp/RXA.c:941
@@ -411,7 +458,8 @@ int qh_rxa_RXASetMP(qh_rxa *h, int ch, int mp)
 {
     mp = mp ? 1 : 0;
     FOR_CH(h, ch, {
-        if (c.mp != mp) { c.mp = mp; c.nbp_dirty = true; c.bp1_dirty = true; c.demod_dirty = true; }
+        // RXANBPSetMP, RXABPSNBASetMP, SetRXABandpassMP, wdsp/RXA.c:951-953
+        band_set_mp(c, FC_NBP, mp); band_set_mp(c, FC_SNB, mp); band_set_mp(c, FC_BP1, mp);
         fm_set_mp(h->e, c, 0, mp); fm_set_mp(h->e, c, 1, mp);       // SetRXAFMMPde / SetRXAFMMPaud, wdsp/RXA.c:956-957
         c.fmsq_mp = mp;                         // SetRXAFMSQMP, wdsp/RXA.c:955
         if (c.eqp_mp != mp) { c.eqp_mp = mp; c.eqp_dirty = true; }      // SetRXAEQMP, wdsp/RXA.c:954
@@ -584,6 +632,110 @@ int qh_rxa_SetRXAAGCFixed(qh_rxa *h, int ch, double db)
     FOR_CH(h, ch, { c.agc_fixed = std::pow(10.0, db / 20.0); c.epi_dirty = true; c.lms[0].dirty = c.lms[1].dirty = true; });
 }
 
+// ---- the AGC's display-side knobs (wcpAGC.c:440-557): host arithmetic on what loadWcpAGC derives (wcpAGC.c:115-146).  Every setter of
+// the reference ends in loadWcpAGC, so the derived values are functions of the channel's current settings: out_target from create_rxa's
+// out_targ 1.0 and n_tau 4 (RXA.c:335-358), in loadWcpAGC's order of expressions.  The getters read the settings under the engine's lock
+// and touch neither the device nor the stream.
+static double agc_out_target() { return 1.0 * (1.0 - std::exp(-4.0)) * 0.9999; }
+static double agc_min_volts(const ChanCfg &c) { return agc_out_target() / (c.agc_var_gain * c.agc_max_gain); }
+static double agc_hang_level(const ChanCfg &c)
+{
+    const double tmp = std::pow(10.0, (c.agc_hang_thresh - 1.0) / 0.125);
+    return (c.agc_max_input * tmp + (agc_out_target() / (c.agc_var_gain * c.agc_max_gain)) * (1.0 - tmp)) * 0.637;
+}
+// 10 log10((nbp0.fhigh - nbp0.flow) size / rate) of Get / SetRXAAGCThresh: size and rate are the caller's display FFT size and rate.
+// The reference checks nothing and would take the log of 0 or less: refused here.
+static int agc_noise_offset(const char *who, const ChanCfg &c, double size, double rate, double *offset)
+{
+    if (!std::isfinite(size) || !std::isfinite(rate) || size <= 0.0 || rate <= 0.0)
+        return set_error(QH_ERR_INVALID, "%s: size %g and rate %g must be finite and above 0", who, size, rate);
+    if (!(c.nbp_fhigh - c.nbp_flow > 0.0))
+        return set_error(QH_ERR_INVALID, "%s: nbp0's band %g .. %g is not wider than 0", who, c.nbp_flow, c.nbp_fhigh);
+    *offset = 10.0 * std::log10((c.nbp_fhigh - c.nbp_flow) * size / rate);
+    return QH_OK;
+}
+// a getter's channel: one channel, not -1
+static const ChanCfg *agc_get_chan(qh_rxa *h, int ch, const void *out, const char *who)
+{
+    if (!h || !out || ch < 0 || ch >= h->e.nch) { set_error(QH_ERR_INVALID, "%s: bad arguments", who); return nullptr; }
+    return &h->e.cfg[(size_t)ch];
+}
+int qh_rxa_SetRXAAGCThresh(qh_rxa *h, int ch, double thresh, double size, double rate)
+{
+    if (!std::isfinite(thresh)) return set_error(QH_ERR_INVALID, "SetRXAAGCThresh: thresh %g is not finite", thresh);
+    if (!h) return set_error(QH_ERR_INVALID, "null engine");
+    QH_RXA_LOCK(h);
+    if (ch < -1 || ch >= h->e.nch) return set_error(QH_ERR_INVALID, "channel %d out of range", ch);
+    // every channel's value first: a refusal changes nothing
+    const int lo = ch < 0 ? 0 : ch, hi = ch < 0 ? h->e.nch : ch + 1;
+    std::vector<double> gain((size_t)(hi - lo));
+    for (int i = lo; i < hi; i++) {
+        const ChanCfg &c = h->e.cfg[(size_t)i];
+        double noise_offset = 0.0;
+        if (int rc = agc_noise_offset("SetRXAAGCThresh", c, size, rate, &noise_offset)) return rc;
+        const double g = agc_out_target() / (c.agc_var_gain * std::pow(10.0, (thresh + noise_offset) / 20.0));
+        if (!std::isfinite(g) || g <= 0.0) return set_error(QH_ERR_INVALID, "SetRXAAGCThresh: thresh %g gives no finite gain", thresh);
+        gain[(size_t)(i - lo)] = g;
+    }
+    FOR_CH(h, ch, { c.agc_max_gain = gain[(size_t)(_i - _lo)]; c.agc_dirty = true; });
+}
+int qh_rxa_GetRXAAGCThresh(qh_rxa *h, int ch, double *thresh, double size, double rate)
+{
+    if (!h) return set_error(QH_ERR_INVALID, "null engine");
+    QH_RXA_LOCK(h);
+    const ChanCfg *c = agc_get_chan(h, ch, thresh, "GetRXAAGCThresh");
+    if (!c) return QH_ERR_INVALID;
+    double noise_offset = 0.0;
+    if (int rc = agc_noise_offset("GetRXAAGCThresh", *c, size, rate, &noise_offset)) return rc;
+    *thresh = 20.0 * std::log10(agc_min_volts(*c)) - noise_offset;
+    return QH_OK;
+}
+int qh_rxa_SetRXAAGCHangLevel(qh_rxa *h, int ch, double hang_level)
+{
+    if (!std::isfinite(hang_level)) return set_error(QH_ERR_INVALID, "SetRXAAGCHangLevel: level %g is not finite", hang_level);
+    FOR_CH(h, ch, {
+        const double min_volts = agc_min_volts(c);
+        if (c.agc_max_input > min_volts) {
+            const double convert = std::pow(10.0, hang_level / 20.0);
+            const double tmp = std::max(1e-8, (convert - min_volts) / (c.agc_max_input - min_volts));
+            c.agc_hang_thresh = 1.0 + 0.125 * std::log10(tmp);
+        } else c.agc_hang_thresh = 1.0;
+        c.agc_dirty = true;
+    });
+}
+int qh_rxa_GetRXAAGCHangLevel(qh_rxa *h, int ch, double *hang_level)
+{
+    if (!h) return set_error(QH_ERR_INVALID, "null engine");
+    QH_RXA_LOCK(h);
+    const ChanCfg *c = agc_get_chan(h, ch, hang_level, "GetRXAAGCHangLevel");
+    if (!c) return QH_ERR_INVALID;
+    *hang_level = 20.0 * std::log10(agc_hang_level(*c) / 0.637);
+    return QH_OK;
+}
+int qh_rxa_GetRXAAGCHangThreshold(qh_rxa *h, int ch, int *hangthreshold)
+{
+    if (!h) return set_error(QH_ERR_INVALID, "null engine");
+    QH_RXA_LOCK(h);
+    const ChanCfg *c = agc_get_chan(h, ch, hangthreshold, "GetRXAAGCHangThreshold");
+    if (!c) return QH_ERR_INVALID;
+    *hangthreshold = (int)(100.0 * c->agc_hang_thresh);
+    return QH_OK;
+}
+int qh_rxa_GetRXAAGCTop(qh_rxa *h, int ch, double *max_agc)
+{
+    if (!h) return set_error(QH_ERR_INVALID, "null engine");
+    QH_RXA_LOCK(h);
+    const ChanCfg *c = agc_get_chan(h, ch, max_agc, "GetRXAAGCTop");
+    if (!c) return QH_ERR_INVALID;
+    *max_agc = 20.0 * std::log10(c->agc_max_gain);
+    return QH_OK;
+}
+int qh_rxa_SetRXAAGCMaxInputLevel(qh_rxa *h, int ch, double level)
+{
+    if (!std::isfinite(level) || level <= 0.0) return set_error(QH_ERR_INVALID, "SetRXAAGCMaxInputLevel: level %g must be finite and above 0", level);
+    FOR_CH(h, ch, { c.agc_max_input = level; c.agc_dirty = true; });
+}
+
 // xcbl / xspeak / xmpeak.  Run flags, npeaks and the enables do not flush (cblock.c:120-126, iir.c:322-330, :490-515); the design
 // setters recompute and zero their cascade -- speak's, or that one peak's (calc_speak ends in flush_speak, iir.c:216, :332-360, :517-548).
 // npeaks outside [0, 2] and fil outside [0, 2) would index past the reference's two-peak arrays: refused, nothing changes.
@@ -730,6 +882,16 @@ int qh_rxa_SetRXAPanelGain1(qh_rxa *h, int ch, double g) { FOR_CH(h, ch, { c.gai
 int qh_rxa_SetRXAPanelGain2(qh_rxa *h, int ch, double gI, double gQ) { FOR_CH(h, ch, { c.gain2I = gI; c.gain2Q = gQ; c.epi_dirty = true; }); }
 int qh_rxa_SetRXAPanelSelect(qh_rxa *h, int ch, int s) { FOR_CH(h, ch, { c.inselect = s; c.epi_dirty = true; }); }
 int qh_rxa_SetRXAPanelCopy(qh_rxa *h, int ch, int cp) { FOR_CH(h, ch, { c.copy = cp; c.epi_dirty = true; }); }
+// SetRXAPanelPan (patchpanel.c:158-176): the fields SetRXAPanelGain2 writes, by the reference's sine law (its PI, comm.h:146)
+int qh_rxa_SetRXAPanelPan(qh_rxa *h, int ch, double pan)
+{
+    if (!std::isfinite(pan)) return set_error(QH_ERR_INVALID, "SetRXAPanelPan: pan %g is not finite", pan);
+    const double PI = 3.1415926535897932;
+    const double gain1 = pan <= 0.5 ? 1.0 : std::sin(pan * PI), gain2 = pan <= 0.5 ? std::sin(pan * PI) : 1.0;
+    FOR_CH(h, ch, { c.gain2I = gain1; c.gain2Q = gain2; c.epi_dirty = true; });
+}
+// SetRXAPanelBinaural (patchpanel.c:186-192)
+int qh_rxa_SetRXAPanelBinaural(qh_rxa *h, int ch, int bin) { FOR_CH(h, ch, { c.copy = 1 - bin; c.epi_dirty = true; }); }
 
 int qh_rxa_process(qh_rxa *h, const double *d_in, long long in_stride, double *d_out, long long out_stride, int nblk)
 {

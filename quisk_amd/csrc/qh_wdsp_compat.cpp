@@ -772,6 +772,29 @@ void SetRXAPanelGain1(int channel, double gain) { WDSP_SETTER(qh_rxa_SetRXAPanel
 void SetRXAPanelGain2(int channel, double gainI, double gainQ) { WDSP_SETTER(qh_rxa_SetRXAPanelGain2(L.c->eng, 0, gainI, gainQ)); }
 void SetRXAPanelSelect(int channel, int select) { WDSP_SETTER(qh_rxa_SetRXAPanelSelect(L.c->eng, 0, select)); }
 void SetRXAPanelCopy(int channel, int copy) { WDSP_SETTER(qh_rxa_SetRXAPanelCopy(L.c->eng, 0, copy)); }
+void SetRXAPanelPan(int channel, double pan) { WDSP_SETTER(qh_rxa_SetRXAPanelPan(L.c->eng, 0, pan)); }                // patchpanel.c:158-176
+void SetRXAPanelBinaural(int channel, int bin) { WDSP_SETTER(qh_rxa_SetRXAPanelBinaural(L.c->eng, 0, bin)); }      // patchpanel.c:186-192
+// the AGC's display-side knobs, wcpAGC.c:440-557
+void SetRXAAGCThresh(int channel, double thresh, double size, double rate) { WDSP_SETTER(qh_rxa_SetRXAAGCThresh(L.c->eng, 0, thresh, size, rate)); }
+void GetRXAAGCThresh(int channel, double *thresh, double size, double rate) { WDSP_SETTER(qh_rxa_GetRXAAGCThresh(L.c->eng, 0, thresh, size, rate)); }
+void SetRXAAGCHangLevel(int channel, double hangLevel) { WDSP_SETTER(qh_rxa_SetRXAAGCHangLevel(L.c->eng, 0, hangLevel)); }
+void GetRXAAGCHangLevel(int channel, double *hangLevel) { WDSP_SETTER(qh_rxa_GetRXAAGCHangLevel(L.c->eng, 0, hangLevel)); }
+void GetRXAAGCHangThreshold(int channel, int *hangthreshold) { WDSP_SETTER(qh_rxa_GetRXAAGCHangThreshold(L.c->eng, 0, hangthreshold)); }
+void GetRXAAGCTop(int channel, double *max_agc) { WDSP_SETTER(qh_rxa_GetRXAAGCTop(L.c->eng, 0, max_agc)); }
+void SetRXAAGCMaxInputLevel(int channel, double level) { WDSP_SETTER(qh_rxa_SetRXAAGCMaxInputLevel(L.c->eng, 0, level)); }
+// nc, mp and window per stage: nbp.c:563-588, snb.c:829-855, bandpass.c:411-457
+void RXANBPSetNC(int channel, int nc) { WDSP_SETTER(qh_rxa_RXANBPSetNC(L.c->eng, 0, nc)); }
+void RXANBPSetMP(int channel, int mp) { WDSP_SETTER(qh_rxa_RXANBPSetMP(L.c->eng, 0, mp)); }
+void RXABPSNBASetNC(int channel, int nc) { WDSP_SETTER(qh_rxa_RXABPSNBASetNC(L.c->eng, 0, nc)); }
+void RXABPSNBASetMP(int channel, int mp) { WDSP_SETTER(qh_rxa_RXABPSNBASetMP(L.c->eng, 0, mp)); }
+void SetRXABandpassNC(int channel, int nc) { WDSP_SETTER(qh_rxa_SetRXABandpassNC(L.c->eng, 0, nc)); }
+void SetRXABandpassMP(int channel, int mp) { WDSP_SETTER(qh_rxa_SetRXABandpassMP(L.c->eng, 0, mp)); }
+void SetRXABandpassWindow(int channel, int wintype) { WDSP_SETTER(qh_rxa_SetRXABandpassWindow(L.c->eng, 0, wintype)); }
+// wisdom.c:32-121.  No FFTW plans are made here, so there is nothing to optimize or to store: the call returns as the reference's does
+// when the wisdom file was there, the directory is not looked at and the status stays the empty string.
+static char g_wisdom_status[128];
+char *wisdom_get_status(void) { return g_wisdom_status; }
+void WDSPwisdom(char *directory) { (void)directory; }
 void SetRXAAMDSBMode(int channel, int sbmode) { WDSP_SETTER(qh_rxa_SetRXAAMDSBMode(L.c->eng, 0, sbmode)); }
 void SetRXAAMDRun(int channel, int run) { WDSP_SETTER(qh_rxa_SetRXAAMDRun(L.c->eng, 0, run)); }
 void SetRXAFMLimRun(int channel, int run) { WDSP_SETTER(qh_rxa_SetRXAFMLimRun(L.c->eng, 0, run)); }

@@ -81,6 +81,24 @@ def load():
         f = getattr(L, "qh_rxa_" + n)
         f.argtypes = a
         f.restype = i
+    # the names other WDSP clients call (wdsp/wcpAGC.c:440-557, patchpanel.c:158-192, nbp.c:563-588, snb.c:829-855, bandpass.c:411-457,
+    # wisdom.c): the engine's forms and the WDSP names
+    pd, pi = C.POINTER(d), C.POINTER(i)
+    for n, a in (("SetRXAAGCThresh", [i, d, d, d]), ("GetRXAAGCThresh", [i, pd, d, d]), ("SetRXAAGCHangLevel", [i, d]),
+                 ("GetRXAAGCHangLevel", [i, pd]), ("GetRXAAGCHangThreshold", [i, pi]), ("GetRXAAGCTop", [i, pd]),
+                 ("SetRXAAGCMaxInputLevel", [i, d]), ("SetRXAPanelPan", [i, d]), ("SetRXAPanelBinaural", [i, i]),
+                 ("RXANBPSetNC", [i, i]), ("RXANBPSetMP", [i, i]), ("RXABPSNBASetNC", [i, i]), ("RXABPSNBASetMP", [i, i]),
+                 ("SetRXABandpassNC", [i, i]), ("SetRXABandpassMP", [i, i]), ("SetRXABandpassWindow", [i, i])):
+        f = getattr(L, "qh_rxa_" + n)
+        f.argtypes = [vp] + a
+        f.restype = i
+        f = getattr(L, n)
+        f.argtypes = a
+        f.restype = None
+    L.WDSPwisdom.argtypes = [C.c_char_p]
+    L.WDSPwisdom.restype = None
+    L.wisdom_get_status.argtypes = []
+    L.wisdom_get_status.restype = C.c_char_p
     # the FM squelch's WDSP names (wdsp/fmsq.c:235-279) and its diagnostic
     for n, a in (("SetRXAFMSQRun", [i, i]), ("SetRXAFMSQThreshold", [i, d]), ("SetRXAFMSQNC", [i, i]), ("SetRXAFMSQMP", [i, i])):
         f = getattr(L, n)

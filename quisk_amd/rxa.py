@@ -25,7 +25,9 @@ _SETTERS = ("SetRXAMode", "RXASetNC", "SetRXAShiftRun", "RXANBPSetRun", "SetRXAB
             "SetRXASSQLRun", "SetRXASSQLThreshold", "SetRXASSQLTauMute", "SetRXASSQLTauUnMute",
             "SetRXAFMSQRun", "SetRXAFMSQThreshold", "SetRXAFMSQNC", "SetRXAFMSQMP",
             "SetRXAFMAFFilter", "SetRXAFMNCde", "SetRXAFMMPde", "SetRXAFMNCaud", "SetRXAFMMPaud",
-            "SetRXAEQRun", "SetRXAEQNC", "SetRXAEQMP", "SetRXAEQProfile", "SetRXAEQCtfmode", "SetRXAEQWintype", "SetRXAGrphEQ", "SetRXAGrphEQ10")
+            "SetRXAEQRun", "SetRXAEQNC", "SetRXAEQMP", "SetRXAEQProfile", "SetRXAEQCtfmode", "SetRXAEQWintype", "SetRXAGrphEQ", "SetRXAGrphEQ10",
+            "SetRXAAGCThresh", "SetRXAAGCHangLevel", "SetRXAAGCMaxInputLevel", "SetRXAPanelPan", "SetRXAPanelBinaural",
+            "RXANBPSetNC", "RXANBPSetMP", "RXABPSNBASetNC", "RXABPSNBASetMP", "SetRXABandpassNC", "SetRXABandpassMP", "SetRXABandpassWindow")
 # the setters that take arrays: (element type, position among the arguments behind the channel)
 _ARRAYS = {"SetRXAEQProfile": ((C.c_double, 1), (C.c_double, 2)), "SetRXAGrphEQ": ((C.c_int, 0),), "SetRXAGrphEQ10": ((C.c_int, 0),)}
 
@@ -113,6 +115,27 @@ class RxaEngine:
         w = C.c_double(0)
         check(self._L.qh_rxa_RXANBPGetMinNotchWidth(self._h, ch, C.byref(w)))
         return w.value
+
+    # the AGC's display-side getters (wdsp/wcpAGC.c:440-520): host arithmetic on the channel's settings, nothing on the device is waited for
+    def GetRXAAGCThresh(self, ch, size, rate):
+        v = C.c_double(0)
+        check(self._L.qh_rxa_GetRXAAGCThresh(self._h, ch, C.byref(v), float(size), float(rate)))
+        return v.value
+
+    def GetRXAAGCHangLevel(self, ch):
+        v = C.c_double(0)
+        check(self._L.qh_rxa_GetRXAAGCHangLevel(self._h, ch, C.byref(v)))
+        return v.value
+
+    def GetRXAAGCHangThreshold(self, ch):
+        v = C.c_int(0)
+        check(self._L.qh_rxa_GetRXAAGCHangThreshold(self._h, ch, C.byref(v)))
+        return v.value
+
+    def GetRXAAGCTop(self, ch):
+        v = C.c_double(0)
+        check(self._L.qh_rxa_GetRXAAGCTop(self._h, ch, C.byref(v)))
+        return v.value
 
     def process_ptr(self, d_in, in_stride, d_out, out_stride, nblk):
         """Device pointers (ints), strides in complex samples.  Asynchronous on the engine's stream."""
