@@ -19,7 +19,7 @@ void Engine::pack_audio(const double2 *src, long long src_stride, long long n)
 
 void Engine::tick(int cat)
 {
-    if (!timing) return;
+    if (!wide.timing) return;
     if (ev_used >= (int)ev.size()) {
         hipEvent_t e;
         (void)hipEventCreate(&e);
@@ -470,7 +470,7 @@ int Engine::chain_needs(ChainCall &k)
         }
         if (c.ssql_on() && ((int)(0.070 * dsp_rate) < 64))
             return set_error(QH_ERR_UNSUPPORTED, "SSQL needs ramps of 64 samples or more: dsp_rate %d is too low", dsp_rate);
-        if (c.emnr_run && !emnr_tables) return set_error(QH_ERR_INVALID, "EMNR needs its gain tables first (qh_rxa_SetEMNRTables: WDSP's `calculus` and `zetaHat.bin` data)");
+        if (c.emnr_run && !wide.emnr_tables) return set_error(QH_ERR_INVALID, "EMNR needs its gain tables first (qh_rxa_SetEMNRTables: WDSP's `calculus` and `zetaHat.bin` data)");
         if (c.nbp_run) { k.any_nbp = true; if (c.nbp_nc > k.nc_max) k.nc_max = c.nbp_nc; } else k.every_nbp = false;
         if (c.bp1_run) { k.any_bp1 = true; if (c.bp1_nc > k.nc_max) k.nc_max = c.bp1_nc; }
         if (c.snba_run && c.snb_nc > k.nc_max) k.nc_max = c.snb_nc;       // bpsnba's own nc (RXABPSNBASetNC)
@@ -499,7 +499,7 @@ int Engine::chain_needs(ChainCall &k)
         k.any_eqp = true;
         if (c.eqp_nc > kLongPart) return set_error(QH_ERR_UNSUPPORTED, "channel %d: EQ nc = %d exceeds %d", ch, c.eqp_nc, kLongPart);
         // qsort leaves the order of equal keys undefined (eq.c:53-63), and with it the design
-        if (c.eqp_tie) return set_error(QH_ERR_UNSUPPORTED, "channel %d: two EQ frequencies coincide in [0, rate / 2] while their gains differ", ch);
+        if (c.w.eqp_tie) return set_error(QH_ERR_UNSUPPORTED, "channel %d: two EQ frequencies coincide in [0, rate / 2] while their gains differ", ch);
         if (c.eqp_nc > k.nc_max) k.nc_max = c.eqp_nc;
     }
     {   // one noise filter design for the engine's FMSQ channels
@@ -554,7 +554,7 @@ int Engine::plan_long(ChainCall &k)
         }
         f.parts = lp[s];
         // the stage's masks are laid out for another form now: all of them again
-        if (f.dirty) for (ChanCfg &c : cfg) c.*f.dirty = true;
+        if (f.dirty) for (ChanCfg &c : cfg) c.w.*f.dirty = true;
         else fm_dirty = fm_relayout = true;     // (the FM pair's design rows)
     }
     return QH_OK;
@@ -566,12 +566,12 @@ int Engine::plan_long(ChainCall &k)
 // spectra of the tile size, so a change rebuilds every one of them (the delay lines, kept 4095 samples deep, carry over).
 void Engine::pick_band_tile(int nc_max)
 {
-    const bool two_group = nc_max <= 2048 && band_tile_pref == 8192;
-    const bool six_k = nc_max <= 2048 && band_tile_pref == 6144;
+    const bool two_group = nc_max <= 2048 && wide.band_tile_pref == 8192;
+    const bool six_k = nc_max <= 2048 && wide.band_tile_pref == 6144;
     const int want = six_k ? kOsfir6kN : (nc_max > 2048 || two_group) ? kBandNfftMax : kNfft;
     if (want != bnfft || two_group != band2g || six_k != band6k) {
         bnfft = want; band2g = two_group; band6k = six_k;
-        for (ChanCfg &c : cfg) { c.nbp_dirty = c.bp1_dirty = true; c.snb_dirty = true; }
+        for (ChanCfg &c : cfg) { c.w.nbp_dirty = c.w.bp1_dirty = true; c.w.snb_dirty = true; }
     }
 }
 
@@ -589,9 +589,9 @@ int Engine::process_chain(const double *d_in, long long in_stride, double *d_out
     // bp1 does not, fixed AGC gain): the band tile then starts on a multiple of 256 samples, so that the 64 samples a wavefront
     // holds in one register lie in one DSP block and the taps' peak decay is scalar work (qh_osfir.hpp, "fused meters").  Any
     // other chain takes the per-mode path with the stand-alone meter kernel.
-    k.meters_fused = meters_on && !k.mixed && k.any_nbp && !k.any_bp1 && !k.any_eqp && dsp_size >= 64 && dsp_size <= 2048 && !k.long_mode;
-    if (meters_on && !k.meters_fused) k.mixed = true;
-    if (meters_on) if (int rc = meters_alloc()) return rc;
+    k.meters_fused = wide.meters_on && !k.mixed && k.any_nbp && !k.any_bp1 && !k.any_eqp && dsp_size >= 64 && dsp_size <= 2048 && !k.long_mode;
+    if (wide.meters_on && !k.meters_fused) k.mixed = true;
+    if (wide.meters_on) if (int rc = meters_alloc()) return rc;
     if (int rc = refresh_params()) return rc;
     if (k.mixed) if (int rc = refresh_demod()) return rc;
     if (k.gen) if (int rc = refresh_gen()) return rc;
@@ -616,7 +616,7 @@ int Engine::process_chain(const double *d_in, long long in_stride, double *d_out
     if (int rc = refresh_ssql(k)) return rc;
     // (snba_state: a linear call keeps the lists of the last per-mode one, and that one may have ended in snba_alloc's refusal, before any ratio was set)
     if (lists[L_SNBA].n && snba_state && snba_rows()) if (int rc = grow(snba_r12, snba_r12_cap, buf_cap / snba_prm.ratio, 2 * (long long)nch)) return rc;   // the blanker's 12 kHz rows
-    if (fq_list.n) if (int rc = grow(fq_noise, fq_noise_cap, buf_cap, nch)) return rc;     // the noise filter's output rows
+    if (fq_lists[0].n) if (int rc = grow(fq_noise, fq_noise_cap, buf_cap, nch)) return rc;     // the noise filter's output rows
     if (k.taps && tap_lists[0].n) if (int rc = grow(snd_rows, snd_cap, buf_cap, nch)) return rc;      // the sender's float rows
     snd_n = k.taps && tap_lists[0].n ? k.n_mid : 0;
     ev_used = 0;
@@ -693,16 +693,16 @@ int Engine::run_linear(ChainCall &k)
             // the equalizer's channels through their tiles, each with its own mask and delay line; a channel that does not run it is
             // passed on as it is (xeqp with run 0 copies, eq.c:206-207, and its fircore's delay line stays as it was)
             const bool last = stage == nstage - 1;
-            run_band(cur, cur_stride, dst, dst_stride, last ? epi : nullptr, n_mid, fc[FC_EQP], k.P, eq_list.dev, eq_list.n, false, k.eg_fused && last);
+            run_band(cur, cur_stride, dst, dst_stride, last ? epi : nullptr, n_mid, fc[FC_EQP], k.P, eq_lists[0].dev, eq_lists[0].n, false, k.eg_fused && last);
             fc[FC_EQP].flip();
-            if (eq_rest.n) {
+            if (eq_lists[1].n) {
                 const long long per = (n_mid + NT - 1) / NT;
-                const dim3 g((unsigned)(per < 1024 ? per : 1024), (unsigned)eq_rest.n);
-                if (!last) hipLaunchKernelGGL(copy_rows_kernel, g, dim3(NT), 0, stream, cur, dst, buf_cap, (int)n_mid, (const int *)eq_rest.dev);
+                const dim3 g((unsigned)(per < 1024 ? per : 1024), (unsigned)eq_lists[1].n);
+                if (!last) hipLaunchKernelGGL(copy_rows_kernel, g, dim3(NT), 0, stream, cur, dst, buf_cap, (int)n_mid, (const int *)eq_lists[1].dev);
                 else {
                     auto *pass = k.eg_fused ? &pointwise_kernel<double, false, true> : &pointwise_kernel<double, false>;
                     hipLaunchKernelGGL(pass, g, dim3(NT), 0, stream, cur, cur_stride, dst, dst_stride, (int)n_mid, (const unsigned long long *)nullptr,
-                                       (const unsigned long long *)nullptr, (const EpiParam *)epi, (const int *)eq_rest.dev, k.eg_fused ? eg : EgressFmt{});
+                                       (const unsigned long long *)nullptr, (const EpiParam *)epi, (const int *)eq_lists[1].dev, k.eg_fused ? eg : EgressFmt{});
                 }
             }
             cur = dst; cur_stride = dst_stride; stage++;
@@ -737,16 +737,16 @@ int Engine::plan_mixed(ChainCall &k)
     // 2 no envelope in nbp0's store, 3 no angles in nbp0's store, 4 no paired real filters, 5 no second stream at all, 6-7 where the second
     // stream forks (counted down from behind the FM channels' nbp0), 8 xfmd's dc removal as a pass of its own (fm_dc_tiled_kernel), 9 the AM
     // fade leveller as a pass of its own (am_level_tiled_kernel)
-    k.split = lists[L_FM].n > 0 && lists[L_REST].n > 0 && D > 1 && !meters_on && !k.taps && !k.gen && !lists[L_AMSQ].n && !lists[L_SNB].n && !timing && !(dbg_forms & 1);
+    k.split = lists[L_FM].n > 0 && lists[L_REST].n > 0 && D > 1 && !wide.meters_on && !k.taps && !k.gen && !lists[L_AMSQ].n && !lists[L_SNB].n && !wide.timing && !(dbg_forms & 1);
     // ... and when nothing sits between a channel's last filter and the output matrix (no AGC state machine, LMS, EMNR, SNBA,
     // limiter, squelch or position-1 stage anywhere), that last stage -- nbp0 for the plain channels, bp1 for AM / SAM, the CTCSS
     // notch for FM -- applies the matrix in its store and writes the caller's buffer: the output pass (32 B per output sample) goes.
     k.fm_theta_fused = k.split && k.any_nbp && !band6k && !band2g && bnfft == kNfft && !(dbg_forms & 8);
     bool no_lms = true;
     for (int f = 0; f < 2; f++) for (int p = 0; p < 3; p++) no_lms = no_lms && !lms_n(3 * f + p);
-    k.direct = k.split && !(dbg_forms & 2) && !eq_list.n && k.every_nbp && !eg.kind && !lists[L_LIM].n && !lists[L_AGC_CUR].n && !lists[L_AGC_OTHER].n && !lists[L_SNBA].n && !lists[L_SNB + 1].n && no_lms &&
+    k.direct = k.split && !(dbg_forms & 2) && !eq_lists[0].n && k.every_nbp && !eg.kind && !lists[L_LIM].n && !lists[L_AGC_CUR].n && !lists[L_AGC_OTHER].n && !lists[L_SNBA].n && !lists[L_SNB + 1].n && no_lms &&
                !lists[L_EMNR].n && !lists[L_EMNR + 1].n && !lists[L_EMNR + 2].n && !lists[L_FIX].n && !lists[L_FIX + 1].n && !lists[L_BP1P + 1].n && lists[L_BP1P].n == lists[L_BP1].n && lists[L_RB].n == lists[L_BP1].n &&
-               lists[L_USB].n + lists[L_FM].n == lists[L_PLAIN].n && !lists[L_AP].n && !lists[L_AP + 1].n && !ssql_listed() &&
+               lists[L_USB].n + lists[L_FM].n == lists[L_PLAIN].n && !lists[L_AP].n && !lists[L_AP + 1].n && !ssql_lists.any() &&
                // the first stores to `out` come while other channels' input is still being read: not for a caller that works in place
                extents_apart(k.out, k.out_stride, k.n_mid, k.in, k.in_stride, k.n_in, nch);
     // ... and the AM channels' nbp0 leaves the envelope and every tile's share of the fade leveller's averages: one pass does the rest
@@ -829,7 +829,7 @@ int Engine::run_mixed_front(ChainCall &k)
     } else {
         if (int rc = run_front(k.in, k.in_stride, cur, buf_cap, nullptr, n_in, n_mid)) return rc;
         run_gen(k);                  // xgen (RXA.c:565)
-        if (meters_on) hipLaunchKernelGGL(meter_kernel, dim3((unsigned)nch), dim3(64), 0, stream, cur, buf_cap, k.nblk, dsp_size, m_adc,
+        if (wide.meters_on) hipLaunchKernelGGL(meter_kernel, dim3((unsigned)nch), dim3(64), 0, stream, cur, buf_cap, k.nblk, dsp_size, m_adc,
                                           m_prm, (const int *)nullptr);
         if (k.any_nbp) {
             run_band(cur, buf_cap, other, buf_cap, nullptr, n_mid, fc[FC_NBP], P, nullptr, 0);
@@ -837,7 +837,7 @@ int Engine::run_mixed_front(ChainCall &k)
             std::swap(cur, other);
         }
     }
-    if (meters_on) hipLaunchKernelGGL(meter_kernel, dim3((unsigned)nch), dim3(64), 0, stream, cur, buf_cap, k.nblk, dsp_size, m_s,
+    if (wide.meters_on) hipLaunchKernelGGL(meter_kernel, dim3((unsigned)nch), dim3(64), 0, stream, cur, buf_cap, k.nblk, dsp_size, m_s,
                                       m_prm, (const int *)nullptr);
     run_sender(k);                   // xsender (RXA.c:570)
     if (lists[L_AMSQ].n) {           // xamsqcap (RXA.c:571): the magnitudes of the signal behind nbp0, for xamsq at the end of the chain
@@ -868,12 +868,12 @@ void Engine::snb_inplace(const ChainCall &k, const int *list, int n)
 // its detector, bpsnba and xsnba.  (The stores that write the caller's rows ahead of this point are off for such a call: plan_mixed.)
 void Engine::eqp_inplace(const ChainCall &k)
 {
-    if (!eq_list.n) return;
-    run_band(k.cur, buf_cap, k.other, buf_cap, nullptr, k.n_mid, fc[FC_EQP], k.P, eq_list.dev, eq_list.n);
+    if (!eq_lists[0].n) return;
+    run_band(k.cur, buf_cap, k.other, buf_cap, nullptr, k.n_mid, fc[FC_EQP], k.P, eq_lists[0].dev, eq_lists[0].n);
     fc[FC_EQP].flip();
     long long per = (k.n_mid + NT - 1) / NT;
-    hipLaunchKernelGGL(copy_rows_kernel, dim3((unsigned)(per < 1024 ? per : 1024), (unsigned)eq_list.n), dim3(NT), 0, stream, k.other, k.cur, buf_cap,
-                       (int)k.n_mid, (const int *)eq_list.dev);
+    hipLaunchKernelGGL(copy_rows_kernel, dim3((unsigned)(per < 1024 ? per : 1024), (unsigned)eq_lists[0].n), dim3(NT), 0, stream, k.other, k.cur, buf_cap,
+                       (int)k.n_mid, (const int *)eq_lists[0].dev);
 }
 
 // Segment scans: one 16-wavefront workgroup per channel fills one CU.  With fewer channels of a kind than the chip has CUs the
@@ -946,7 +946,7 @@ int Engine::run_am(ChainCall &k)
                                sam_pll_prm, kSamTile, kSamWarm);
             hipLaunchKernelGGL((pll_verify_kernel<true>), dim3((unsigned)nt), dim3(64), 0, am_stream, (const double *)theta, 2 * buf_cap, pts,
                                2 * buf_cap, (int)n_mid, lists[L_SAM].dev, pll_state, pll_ends, pll_ends_cap * kPllEndsW, sam_pll_prm, kSamTile, kSamWarm,
-                               pll_nfixed, pll_check_only);
+                               pll_nfixed, wide.pll_check_only);
             if (nt0)        // (the segment summaries behind the AM channels' rows)
                 am_detect<true>(k, am_stream, lists[L_SAM].dev, nt0, seg_groups(lists[L_AM].n + nt, n_mid), pts, 2 * buf_cap,
                                 seg_sum[0] + (size_t)lists[L_AM].n * kSegWaves * kSegMaxGroups * kSegSumW);
@@ -1022,7 +1022,7 @@ int Engine::run_fm(ChainCall &k)
                            fm_pll_prm, fm_tile, kFmWarm, fmdc_fused ? 1 : 0);
         hipLaunchKernelGGL((pll_verify_kernel<false>), dim3((unsigned)lists[L_FM].n), dim3(64), 0, stream, (const double *)theta, 2 * buf_cap, fil,
                            2 * buf_cap, (int)n_mid, lists[L_FM].dev, fm_pll_state, pll_ends, pll_ends_cap * kPllEndsW, fm_pll_prm, fm_tile, kFmWarm,
-                           pll_nfixed, pll_check_only, fmdc_fused ? 1 : 0);
+                           pll_nfixed, wide.pll_check_only, fmdc_fused ? 1 : 0);
         if (fmdc_fused) {
             hipLaunchKernelGGL(fm_dc_chain_kernel, dim3((unsigned)lists[L_FM].n), dim3(64), 0, stream, (int)n_mid, fm_tile, lists[L_FM].dev, fm_pll_state, fm_pll_prm,
                                (const double *)pll_ends, pll_ends_cap * kPllEndsW, fm_cin, fm_cin_cap);
@@ -1038,13 +1038,13 @@ int Engine::run_fm(ChainCall &k)
             hipLaunchKernelGGL(commit_fmdc_kernel, dim3((unsigned)((lists[L_FM].n + 255) / 256)), dim3(256), 0, stream, fm_pll_state, (const double *)fmdc_next, lists[L_FM].dev, lists[L_FM].n);
         }
     }
-    if (fq_list.n) {
+    if (fq_lists[0].n) {
         // xfmsq's noise filter (fmsq.c:147) over the trigger, xfmd's audio ahead of de-emphasis (RXA.c:220): the FMSQ channels' rows only,
         // with the stage's own mask and delay lines.  Where the audio is made in the load (fmdc_fused) it is loaded the same way here, two
         // channels a tile (the taps are real); otherwise it lies in the rows of cur.
         if (fmdc_src.a) band_fmdc = &fmdc_src;
-        run_band(cur, buf_cap, fq_noise, fq_noise_cap, nullptr, n_mid, fc[FC_FQ], k.P, fq_list.dev, fq_list.n, false, false, 0, nullptr, 0,
-                 fmdc_src.a ? fq_pairs.dev : nullptr, np_fq);
+        run_band(cur, buf_cap, fq_noise, fq_noise_cap, nullptr, n_mid, fc[FC_FQ], k.P, fq_lists[0].dev, fq_lists[0].n, false, false, 0, nullptr, 0,
+                 fmdc_src.a ? fq_lists[1].dev : nullptr, np_fq);
         fc[FC_FQ].flip();
         band_fmdc = nullptr;
     }
@@ -1072,7 +1072,7 @@ int Engine::run_fm(ChainCall &k)
                                sn_prm, sn_state, (double *)nullptr, k.direct ? k.out : (double2 *)nullptr, k.out_stride, (const EpiParam *)epi);
     }
     if (lists[L_LIM].n)      // detector limiter: lim_pre_gain 0.4, then its own wcpAGC (fmd.c:179-184)
-        hipLaunchKernelGGL(agc_form == 1 ? wcpagc_seq_kernel : wcpagc_kernel, dim3((unsigned)lists[L_LIM].n), dim3(64), 0, stream, cur, buf_cap,
+        hipLaunchKernelGGL(wide.agc_form == 1 ? wcpagc_seq_kernel : wcpagc_kernel, dim3((unsigned)lists[L_LIM].n), dim3(64), 0, stream, cur, buf_cap,
                            (int)n_mid, lists[L_LIM].dev, lim_prm, lim_state, 0.4);
     run_fmsq(k);            // xfmsq, RXA.c:575
     return QH_OK;
@@ -1083,9 +1083,9 @@ int Engine::run_fm(ChainCall &k)
 // commutes with the matrix, a muted sample is stored as 0 either way, and no other channel's path changes because one squelch runs.
 void Engine::run_fmsq(const ChainCall &k)
 {
-    if (!fq_list.n) return;
-    hipLaunchKernelGGL(fmsq_kernel, dim3((unsigned)fq_list.n), dim3(64), 0, stream, k.direct ? k.out : k.cur, k.direct ? k.out_stride : buf_cap, (int)k.n_mid,
-                       (const int *)fq_list.dev, (const double2 *)fq_noise, fq_noise_cap, (const FmsqParam *)fq_prm, fq_state, (const double *)fq_cup,
+    if (!fq_lists[0].n) return;
+    hipLaunchKernelGGL(fmsq_kernel, dim3((unsigned)fq_lists[0].n), dim3(64), 0, stream, k.direct ? k.out : k.cur, k.direct ? k.out_stride : buf_cap, (int)k.n_mid,
+                       (const int *)fq_lists[0].dev, (const double2 *)fq_noise, fq_noise_cap, (const FmsqParam *)fq_prm, fq_state, (const double *)fq_cup,
                        (const double *)fq_cdown);
 }
 
@@ -1094,7 +1094,7 @@ int Engine::run_snba(const ChainCall &k)
 {
     if (!lists[L_SNBA].n) return QH_OK;
     if (snba_tune_dirty) {
-        QH_HIP(hipMemcpyAsync(snba_tune, snba_tune_h.data(), snba_tune_h.size() * sizeof(SnbaTune), hipMemcpyHostToDevice, stream));
+        QH_HIP(hipMemcpyAsync(snba_tune, wide.snba_tune_h.data(), wide.snba_tune_h.size() * sizeof(SnbaTune), hipMemcpyHostToDevice, stream));
         QH_HIP(hipStreamSynchronize(stream));
         snba_tune_dirty = false;
     }
@@ -1158,18 +1158,18 @@ int Engine::run_agc(ChainCall &k)
 {
     const long long n_mid = k.n_mid;
     double2 *cur = k.cur, *other = k.other;
-    bool tiled = (agc_form == 0 || agc_form == 3) && n_mid >= kAgcTiledMin;      // (3: diagnostics, the tiles' check counts and repairs nothing)
+    bool tiled = (wide.agc_form == 0 || wide.agc_form == 3) && n_mid >= kAgcTiledMin;      // (3: diagnostics, the tiles' check counts and repairs nothing)
     int a_max = 0;
     for (int ch = 0; ch < nch && tiled; ch++) {
         ChanCfg &c = cfg[(size_t)ch];
-        if (!c.agc_on() || c.agc_stale) continue;
-        a_max = c.agc_abuf > a_max ? c.agc_abuf : a_max;
+        if (!c.agc_on() || c.w.agc_stale) continue;
+        a_max = c.w.agc_abuf > a_max ? c.w.agc_abuf : a_max;
     }
     // the tiles take the channels at the head of each list, the stepping kernel the ones behind them (all of them in a short call)
     const int nt_cur = tiled ? lists[L_AGC_CUR].n - n_agc_cur_stale : 0, nt_other = tiled ? lists[L_AGC_OTHER].n - n_agc_other_stale : 0;
     if (nt_cur + nt_other == 0) tiled = false;
     agc_last_tiled = nt_cur + nt_other;
-    for (ChanCfg &c : cfg) if (c.agc_on()) c.agc_ran = true;
+    for (ChanCfg &c : cfg) if (c.agc_on()) c.w.agc_ran = true;
     // the reference's full ring (RB_SIZE entries): this call's last inputs go in where xwcpagc writes them; a channel whose attack
     // window moved since its last call first takes its 2048-entry ring again from it (the entries the longer window jumped over)
     if (!agc_lring) {
@@ -1184,8 +1184,8 @@ int Engine::run_agc(ChainCall &k)
         std::vector<int> rw;
         for (int ch = 0; ch < nch; ch++) {
             ChanCfg &c = cfg[(size_t)ch];
-            if (c.agc_on() && c.agc_rewindow) rw.push_back(ch);
-            if (c.agc_on()) c.agc_rewindow = false;
+            if (c.agc_on() && c.w.agc_rewindow) rw.push_back(ch);
+            if (c.agc_on()) c.w.agc_rewindow = false;
         }
         if (!rw.empty()) {
             QH_HIP(hipMemcpyAsync(agc_rewin_list, rw.data(), rw.size() * sizeof(int), hipMemcpyHostToDevice, stream));
@@ -1208,8 +1208,8 @@ int Engine::run_agc(ChainCall &k)
     }
     // ... and when every channel has the AGC as its last stage (nothing at position 1, no meters, squelch or audio frames), the gain
     // multiply applies the output matrix and writes the caller's rows: the output pass goes
-    bool no_p1 = !lists[L_BP1P + 1].n && !lists[L_FIX].n && !lists[L_FIX + 1].n && !lists[L_EMNR + 1].n && !lists[L_EMNR + 2].n && !lists[L_AMSQ].n && !meters_on && !k.taps && !eg.kind && !lists[L_AP].n && !lists[L_AP + 1].n &&
-                 !ssql_listed();
+    bool no_p1 = !lists[L_BP1P + 1].n && !lists[L_FIX].n && !lists[L_FIX + 1].n && !lists[L_EMNR + 1].n && !lists[L_EMNR + 2].n && !lists[L_AMSQ].n && !wide.meters_on && !k.taps && !eg.kind && !lists[L_AP].n && !lists[L_AP + 1].n &&
+                 !ssql_lists.any();
     for (int f = 0; f < 2; f++) for (int p = 1; p < 3; p++) no_p1 = no_p1 && !lms_n(3 * f + p);
     k.agc_direct = tiled && no_p1 && nt_cur == lists[L_PLAIN].n && nt_other == lists[L_BP1].n;
     if (tiled) {
@@ -1283,7 +1283,7 @@ int Engine::run_agc(ChainCall &k)
             hipLaunchKernelGGL(agc_lanes_kernel, dim3((unsigned)ngroups, (unsigned)cnt), dim3(64), 0, stream, n, lst, (const AgcParam *)agc_prm,
                                agc_scr, agc_arr, (const double *)bnd, agc_ends_cap * kAgcEndsW, end, agc_ends_cap * kAgcEndsW, L);
             hipLaunchKernelGGL(agc_verify_kernel, dim3((unsigned)cnt), dim3(64), 0, stream, n, lst, (const AgcParam *)agc_prm, agc_scr, agc_arr,
-                               (const double *)bnd, agc_ends_cap * kAgcEndsW, end, agc_ends_cap * kAgcEndsW, L, agc_fin, agc_nfixed, agc_form == 3 ? 1 : 0);
+                               (const double *)bnd, agc_ends_cap * kAgcEndsW, end, agc_ends_cap * kAgcEndsW, L, agc_fin, agc_nfixed, wide.agc_form == 3 ? 1 : 0);
             hipLaunchKernelGGL(agc_tail_kernel, dim3((unsigned)cnt), dim3(256), 0, stream, (const double2 *)b, buf_cap, n, lst,
                                (const AgcParam *)agc_prm, agc_tail, 1.0);
             hipLaunchKernelGGL(agc_apply_kernel, dim3((unsigned)ntile, (unsigned)cnt), dim3(256), lds_apply, stream, b, buf_cap, n, lst,
@@ -1296,10 +1296,10 @@ int Engine::run_agc(ChainCall &k)
         run(other, lists[L_AGC_OTHER].dev, nt_other);
     }
     if (const int ns = lists[L_AGC_CUR].n - nt_cur)
-        hipLaunchKernelGGL(agc_form == 1 ? wcpagc_seq_kernel : wcpagc_kernel, dim3((unsigned)ns), dim3(64), 0, stream, cur, buf_cap, (int)n_mid,
+        hipLaunchKernelGGL(wide.agc_form == 1 ? wcpagc_seq_kernel : wcpagc_kernel, dim3((unsigned)ns), dim3(64), 0, stream, cur, buf_cap, (int)n_mid,
                            (const int *)(lists[L_AGC_CUR].dev + nt_cur), agc_prm, agc_state, 1.0);
     if (const int ns = lists[L_AGC_OTHER].n - nt_other)
-        hipLaunchKernelGGL(agc_form == 1 ? wcpagc_seq_kernel : wcpagc_kernel, dim3((unsigned)ns), dim3(64), 0, stream, other, buf_cap, (int)n_mid,
+        hipLaunchKernelGGL(wide.agc_form == 1 ? wcpagc_seq_kernel : wcpagc_kernel, dim3((unsigned)ns), dim3(64), 0, stream, other, buf_cap, (int)n_mid,
                            (const int *)(lists[L_AGC_OTHER].dev + nt_other), agc_prm, agc_state, 1.0);
     return QH_OK;
 }
@@ -1317,11 +1317,11 @@ void Engine::run_sender(const ChainCall &k)
 // adc meter, bpsnba's input, nbp0 and everything behind them read the generated signal.  Then the running modes' state moves on.
 void Engine::run_gen(const ChainCall &k)
 {
-    if (!k.gen || !gen_list.n) return;
+    if (!k.gen || !gen_lists[0].n) return;
     const long long per = (k.n_mid + NT - 1) / NT;
-    hipLaunchKernelGGL(gen_kernel, dim3((unsigned)(per < 1024 ? per : 1024), (unsigned)gen_list.n), dim3(NT), 0, stream, k.cur, buf_cap, (int)k.n_mid,
-                       (const int *)gen_list.dev, (const GenParam *)gen_prm, (const GenState *)gen_state, (const double2 *)gen_ck, (const double *)gen_ctrans);
-    hipLaunchKernelGGL(gen_advance_kernel, dim3((unsigned)((gen_list.n + 255) / 256)), dim3(256), 0, stream, (int)k.n_mid, (const int *)gen_list.dev, gen_list.n,
+    hipLaunchKernelGGL(gen_kernel, dim3((unsigned)(per < 1024 ? per : 1024), (unsigned)gen_lists[0].n), dim3(NT), 0, stream, k.cur, buf_cap, (int)k.n_mid,
+                       (const int *)gen_lists[0].dev, (const GenParam *)gen_prm, (const GenState *)gen_state, (const double2 *)gen_ck, (const double *)gen_ctrans);
+    hipLaunchKernelGGL(gen_advance_kernel, dim3((unsigned)((gen_lists[0].n + 255) / 256)), dim3(256), 0, stream, (int)k.n_mid, (const int *)gen_lists[0].dev, gen_lists[0].n,
                        (const GenParam *)gen_prm, gen_state);
 }
 
@@ -1370,8 +1370,8 @@ int Engine::process_fed(bool replay, const double *d_in, long long in_stride, do
         disp_fed_pending = false;
     }
     const int rc = replay ? process_replayed(d_in, in_stride, d_out, out_stride, nblk) : process(d_in, in_stride, d_out, out_stride, nblk);
-    if (rc || !disp || nblk <= 0) return rc;
-    return feed_display(disp, disp_ss);
+    if (rc || !wide.disp || nblk <= 0) return rc;
+    return feed_display(wide.disp, wide.disp_ss);
 }
 
 // the three stages of the listed channels, in place on the rows that hold them behind bp1 (cur / other)
@@ -1397,7 +1397,7 @@ void Engine::run_audio_peak(const ChainCall &k)
 // the squelch of the listed channels, in place on the rows that hold them behind bp1 (cur / other)
 void Engine::run_ssql(const ChainCall &k)
 {
-    if (!ssql_prm || !ssql_listed()) return;
+    if (!ssql_prm || !ssql_lists.any()) return;
     const int n = (int)k.n_mid, L = ssql_L;
     const long long ntile = (k.n_mid + L - 1) / L, estride = ssql_ends_cap * kSsE, ws = ssql_wcap;
     unsigned long long *xb = ssql_bits, *wdb = xb + (size_t)nch * ws, *trb = wdb + (size_t)nch * ws;
@@ -1448,7 +1448,7 @@ void Engine::run_output(const ChainCall &k)
     lms_at(k, 2, k.other);
     bp1_at(k, 1);
     if (lists[L_BP1].n) fc[FC_BP1].flip();       // the launches of both positions, and of run_am, read the one half
-    if (meters_on) {    // agcmeter sits after xwcpagc (RXA.c:589); mode 0's gain multiply is applied below, so its
+    if (wide.meters_on) {    // agcmeter sits after xwcpagc (RXA.c:589); mode 0's gain multiply is applied below, so its
                         // level reading is taken on the fixed-gain input times g^2 (m_g2)
         if (lists[L_PLAIN].n) hipLaunchKernelGGL(meter_kernel, dim3((unsigned)lists[L_PLAIN].n), dim3(64), 0, stream, k.cur, buf_cap, k.nblk, dsp_size,
                                         m_agc, m_prm, lists[L_PLAIN].dev, (const double *)m_g2);
@@ -1481,7 +1481,7 @@ int Engine::process_replayed(const double *d_in, long long in_stride, double *d_
     // own ping-pong of delay lines per call, event timing records per call: all of them stay on the plain path.  (The input resampler was
     // missing here until a seeded walk through the WDSP names at 144 ksps found it: a sequence captured after a setter replayed the
     // other parity of its delay lines, tests/test_gpu_wdsp_names_fuzz.py.)
-    if (rsmpin || rsmpout || timing || nblk <= 0) return process(d_in, in_stride, d_out, out_stride, nblk);
+    if (rsmpin || rsmpout || wide.timing || nblk <= 0) return process(d_in, in_stride, d_out, out_stride, nblk);
     const GraphKey key{d_in, d_out, in_stride, out_stride, nblk, epoch};
     if (!(key == graph_key)) { drop_graphs(); graph_key = key; graph_seen = false; }
     const unsigned before = flags();
@@ -1503,7 +1503,7 @@ int Engine::process_replayed(const double *d_in, long long in_stride, double *d_
     QH_HIP(hipSetDevice(device));
     if (hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal) != hipSuccess) {
         (void)hipGetLastError();
-        graph_on = false;
+        wide.graph_on = false;
         return process(d_in, in_stride, d_out, out_stride, nblk);
     }
     const int rc = process(d_in, in_stride, d_out, out_stride, nblk);
@@ -1521,7 +1521,7 @@ int Engine::process_replayed(const double *d_in, long long in_stride, double *d_
     (void)hipGetLastError();
     slot.exec = nullptr;
     set_flags(before);
-    graph_on = false;
+    wide.graph_on = false;
     return process(d_in, in_stride, d_out, out_stride, nblk);
 }
 

@@ -1,5 +1,6 @@
-// qh_engine.hpp -- the batched RXA receive engine for MI355X: its constants, the channels' settings (ChanCfg), the engine's state
-// (Engine) and the handle of the C ABI.  Declarations only: qh_engine.hip launches, qh_engine_params.hip designs, allocates and uploads,
+// qh_engine.hpp -- the batched RXA receive engine for MI355X: its constants, the channels' settings (ChanCfg; the notes of pending work
+// apart in ChanCfg::Work), the engine's state (Engine; the engine-wide settings apart in Engine::Wide) and the handle of the C ABI.
+// A new dsp_rate or dsp_size (Engine::rebuild) keeps ChanCfg's direct members and Wide and starts everything else again.  Declarations only: qh_engine.hip launches, qh_engine_params.hip designs, allocates and uploads,
 // qh_rxa_api.hip is the C ABI.  Besides alloc / grow / put_row and one-line accessors no function is defined here, and no ABI function.
 //
 // Mirrors create_rxa()/xrxa() of the reference (wdsp/RXA.c:31-598) for the blocks on the hot path.
@@ -72,7 +73,6 @@ static constexpr long long kAgcTiledMin = 16384;        // xwcpagc in time tiles
 struct ChanCfg {
     int mode = QH_LSB;                                          // RXA.c:33
     int shift_run = 1; double shift_freq = 0.0;                 // RXA.c:39-45
-    int shift_on_device = 1;                                    // whether the device phase is live or parked (nco_park_kernel)
     int nbp_run = 1, nbp_nc = 2048, nbp_wintype = 0;            // RXA.c:90-106
     // minimum-phase impulse responses, one flag per fircore as in the reference (RXANBPSetMP nbp.c:578, SetRXABandpassMP bandpass.c:447,
     // RXABPSNBASetMP snb.c:844); RXASetMP (RXA.c:948) writes all of them
@@ -87,11 +87,7 @@ struct ChanCfg {
     double agc_tau_attack = 0.001, agc_tau_decay = 0.250, agc_max_gain = 10000.0, agc_var_gain = 1.5;
     double agc_hangtime = 0.250, agc_hang_thresh = 0.250;
     double agc_max_input = 1.0;                                 // SetRXAAGCMaxInputLevel, wcpAGC.c:550-557
-    bool agc_dirty = true;
     bool agc_on() const { return agc_run && agc_mode != 0; }
-    int agc_abuf = -1;                  // attack_buffsize last uploaded
-    bool agc_rewindow = false;          // the attack window moved in mid-stream: the state's ring is taken again from the full one
-    bool agc_ran = false, agc_stale = false;    // the window moved while the ring held samples: ring_max may be stale (qh_agc_tiled.hpp)
     int bp1_run = 1, bp1_nc = 2048, bp1_wintype = 1;            // RXA.c:377-389
     double bp1_flow = -4150.0, bp1_fhigh = -150.0, bp1_gain = 1.0;
     double gain1 = 4.0, gain2I = 1.0, gain2Q = 1.0;             // RXA.c:464-474
@@ -100,18 +96,16 @@ struct ChanCfg {
     double fm_dev = 5000.0, ctcss_freq = 254.1;                 // RXA.c:198,208
     int ctcss_run = 1;                                          // RXA.c:207
     // xfmd's de-emphasis and audio filters (create_fmd's arguments, RXA.c:209-212: nc max(2048, dsp_size) -- Engine::init --, mp 0; the
-    // audio band, RXA.c:196-197).  fm_de_flush / fm_aud_flush: SetRXAFMNCde / NCaud took a new nc (setNc_fircore zeroes that filter's line)
+    // audio band, RXA.c:196-197)
     int fm_nc_de = 2048, fm_mp_de = 0, fm_nc_aud = 2048, fm_mp_aud = 0;
     double fm_f_low = 300.0, fm_f_high = 3000.0;
-    bool fm_de_flush = false, fm_aud_flush = false;
-    int lim_run = 0; double lim_gain = 2.5; bool lim_dirty = true;   // FM detector limiter, fmd.c:106-108
+    int lim_run = 0; double lim_gain = 2.5;                     // FM detector limiter, fmd.c:106-108
     // anf / anr (create_anf / create_anr of create_rxa, RXA.c:278-315): [0] = anf, [1] = anr
-    struct Lms { int run = 0, position = 0, taps = 64, delay = 16; double two_mu = 0.0001, gamma = 0.1; bool dirty = true, flush = false; } lms[2];
+    struct Lms { int run = 0, position = 0, taps = 64, delay = 16; double two_mu = 0.0001, gamma = 0.1; } lms[2];
     // emnr (create_emnr of create_rxa, RXA.c:319-332)
     // snba (wdsp/snb.c) and its bandpass bpsnba (snb.c:696-855; run / position follow the mode, RXA.c:883-917)
     int snba_run = 0;
     int snb_nc = 2048;                                          // bpsnba's own nc (RXABPSNBASetNC, snb.c:829-842; made with nbp0's, RXA.c:114)
-    bool snba_flush = false, snba_taps_dirty = true, snba_rout_flush = false, snb_dirty = true, snb_flush = false;
     double snba_f_low = 200.0, snba_f_high = 0.0;               // outresamp fc_low / fcin (snb.c:45-46, resample.c:195-204)
     int snb_pos() const {
         if (!snba_run) return -1;
@@ -121,39 +115,30 @@ struct ChanCfg {
         default: return -1;
         }
     }
-    int emnr_run = 0, emnr_pos = 0, emnr_gain_method = 2, emnr_npe = 0, emnr_ae = 1; bool emnr_dirty = true, emnr_flush = false;
+    int emnr_run = 0, emnr_pos = 0, emnr_gain_method = 2, emnr_npe = 0, emnr_ae = 1;
     double emnr_ae_zeta = 0.75, emnr_ae_psi = 20.0, emnr_train_zeta = -2.0, emnr_train_t2 = 0.20;       // emnr.c:332,491-493
     // amsq (create_amsq of create_rxa, RXA.c:158-172)
-    int amsq_run = 0; double amsq_tail_thresh = 0.009, amsq_unmute_thresh = 0.010, amsq_max_tail = 1.5; bool amsq_dirty = true;
+    int amsq_run = 0; double amsq_tail_thresh = 0.009, amsq_unmute_thresh = 0.010, amsq_max_tail = 1.5;
     int bp1_pos = 0;                                            // SetRXAANFPosition / SetRXAANRPosition set it too (anf.c:236)
-    // xwcpagc mode 0 with a position-1 stage behind it: the gain is applied in place at the AGC's spot, not in the epilogue
-    bool demod_dirty = true, ctcss_flush = false;
-    bool nbp_dirty = true, bp1_dirty = true, nco_dirty = true, epi_dirty = true;
-    bool nbp_flush = false, bp1_flush = false;
-    // xcbl, xspeak, xmpeak (create_rxa, RXA.c:403-445: all three made with run 0); the design setters zero their cascade (sp_flush,
-    // mp_flush) at the next block boundary
+    // xcbl, xspeak, xmpeak (create_rxa, RXA.c:403-445: all three made with run 0); the design setters zero their cascade (w.sp_flush,
+    // w.mp_flush) at the next block boundary
     int cbl_run = 0, sp_run = 0, mp_run = 0, mp_npeaks = 2;
     double sp_f = 600.0, sp_bw = 100.0, sp_gain = 2.0;
     int mp_enable[kApPeaks] = { 1, 1 };
     double mp_f[kApPeaks] = { 2125.0, 2295.0 }, mp_bw[kApPeaks] = { 75.0, 75.0 }, mp_gain[kApPeaks] = { 1.0, 1.0 };
-    bool ap_dirty = true, sp_flush = false, mp_flush[kApPeaks] = { false, false };
     bool ap_on() const { return cbl_run || sp_run || mp_run; }
     // xssql (create_ssql of create_rxa, RXA.c:447-461: run 0, wthresh 0.08, tau_mute = tau_unmute = 0.1); no setter flushes it
     int ssql_run = 0;
     double ssql_wthresh = 0.08, ssql_tau_mute = 0.1, ssql_tau_unmute = 0.1;
-    bool ssql_dirty = true;
     bool ssql_on() const { return ssql_run != 0; }
     // xfmsq (create_fmsq of create_rxa, RXA.c:214-234: run 0, tail 0.750, unmute 0.562 -- not 0.9 apart until SetRXAFMSQThreshold runs --,
     // nc max(2048, dsp_size), mp 0)
     int fmsq_run = 0, fmsq_nc = 2048, fmsq_mp = 0;
     double fmsq_tail_thresh = 0.750, fmsq_unmute_thresh = 0.562;
-    bool fmsq_dirty = true;
     // xeqp (create_eqp of create_rxa, RXA.c:257-275: run 0, nc max(2048, dsp_size) -- Engine::init --, mp 0, ten frequencies with 0 dB each,
-    // ctfmode 0, wintype 0).  eqp_F / eqp_G: nfreqs + 1 entries, G[0] the preamp, F[0] not read.  eqp_flush: SetRXAEQNC took a new nc
-    // (setNc_fircore zeroes the delay line); eqp_tie: two frequencies coincide after eq_impulse's clamp while their gains differ
+    // ctfmode 0, wintype 0).  eqp_F / eqp_G: nfreqs + 1 entries, G[0] the preamp, F[0] not read
     int eqp_run = 0, eqp_nc = 2048, eqp_mp = 0, eqp_ctfmode = 0, eqp_wintype = 0;
     std::vector<double> eqp_F = { 0.0, 32.0, 63.0, 125.0, 250.0, 500.0, 1000.0, 2000.0, 4000.0, 8000.0, 16000.0 }, eqp_G = std::vector<double>(11, 0.0);
-    bool eqp_dirty = true, eqp_flush = false, eqp_tie = false;
     // xsender / xsiphon (qh_taps.hpp): both off until enabled -- a tap costs a pass (the reference runs the siphon of every channel,
     // RXA.c:392-401, and the sender of channel 0, RXA.c:131)
     int sender_run = 0, sip_run = 0;
@@ -163,7 +148,31 @@ struct ChanCfg {
     double gen_tone_mag = 1.0, gen_tone_freq = 1000.0, gen_noise_mag = 1.0;
     double gen_sweep_mag = 1.0, gen_sweep_f1 = -20000.0, gen_sweep_f2 = 20000.0, gen_sweep_rate = 4000.0;
     unsigned long long gen_seed = 0;
-    bool gen_seed_set = false, gen_dirty = true, gen_sweep_dirty = true, gen_tone_reset = false, gen_sweep_reset = false;
+    bool gen_seed_set = false;
+    // The notes of work: what a setter has left for the next call to do (dirty: design and upload again; flush: zero that state) and what
+    // is on the device now.  The rule for a new member of ChanCfg: a note of work goes in Work; anything that a setter list replayed on
+    // a fresh engine would reproduce is a setting and goes outside.  Engine::rebuild keeps the settings and starts Work from its defaults.
+    struct Work {
+        int shift_on_device = 1;            // whether the device phase is live or parked (nco_park_kernel)
+        bool agc_dirty = true;
+        int agc_abuf = -1;                  // attack_buffsize last uploaded
+        bool agc_rewindow = false;          // the attack window moved in mid-stream: the state's ring is taken again from the full one
+        bool agc_ran = false, agc_stale = false;    // the window moved while the ring held samples: ring_max may be stale (qh_agc_tiled.hpp)
+        struct Lms { bool dirty = true, flush = false; } lms[2];
+        bool snba_flush = false, snba_taps_dirty = true, snba_rout_flush = false, snb_dirty = true, snb_flush = false;
+        bool emnr_dirty = true, emnr_flush = false, amsq_dirty = true;
+        bool demod_dirty = true, ctcss_flush = false;
+        bool nbp_dirty = true, bp1_dirty = true, nco_dirty = true, epi_dirty = true;
+        bool nbp_flush = false, bp1_flush = false;
+        bool ap_dirty = true, sp_flush = false, mp_flush[kApPeaks] = { false, false };
+        bool ssql_dirty = true, fmsq_dirty = true, lim_dirty = true;
+        bool fm_de_flush = false, fm_aud_flush = false;     // SetRXAFMNCde / NCaud took a new nc (setNc_fircore zeroes that filter's line)
+        // eqp_flush: SetRXAEQNC took a new nc (setNc_fircore zeroes the delay line); eqp_tie: two frequencies coincide after eq_impulse's
+        // clamp at this dsp_rate while their gains differ
+        bool eqp_dirty = true, eqp_flush = false, eqp_tie = false;
+        bool gen_dirty = true, gen_sweep_dirty = true, gen_tone_reset = false, gen_sweep_reset = false;
+    } w;
+    // xwcpagc mode 0 with a position-1 stage behind it: the gain is applied in place at the AGC's spot, not in the epilogue
     // (the new stages sit behind xwcpagc too, ahead of the panel: a fixed gain that changes while a peak still rings must not reach
     // the ringing tail, so it is applied at the AGC's spot for them as well; SSQL's detector reads amplitude, so it needs the gain too)
     bool fix_before() const
@@ -197,7 +206,7 @@ struct Fircore {
     long long mask_rows(int nch) const { return by_design ? rows : mask_stride ? nch : 1; }
     double2 *hist[2] = { nullptr, nullptr };
     int cur = 0;
-    bool ChanCfg::*dirty = nullptr;         // nbp0, bp1, bpsnba: the channel's flag that has its mask row designed and uploaded again (plan_long)
+    bool ChanCfg::Work::*dirty = nullptr;   // nbp0, bp1, bpsnba: the channel's flag that has its mask row designed and uploaded again (plan_long)
     bool can_long = true;
     int parts = 1;
     double2 *lmask = nullptr, *lhist[2] = { nullptr, nullptr };
@@ -226,7 +235,25 @@ struct Engine {
         { return in == o.in && out == o.out && in_stride == o.in_stride && out_stride == o.out_stride && nblk == o.nblk && epoch == o.epoch; }
     };
     struct GraphSlot { hipGraphExec_t exec = nullptr; unsigned after = 0; };
-    bool graph_on = false, graph_seen = false;
+    // The engine-wide settings.  The rule for a new member of Engine: a value that is set through the C ABI outside cfg and must outlive
+    // a rebuild (a new dsp_rate or dsp_size) lives here; Engine::rebuild moves `wide` out and back as a whole and carries nothing else
+    // of this kind.  (eg, pk and pk_src are set for one call and are not settings.)
+    struct Wide {
+        bool graph_on = false;                  // qh_rxa_set_graph_replay
+        bool timing = false, meters_on = false;
+        int band_tile_pref = 0;                 // qh_rxa_set_band_tile: 0 / 4096: 4096-point tiles, 8192: the two-group tiles
+        int snba_ovrlp = 4;                     // create_rxa's overlap (RXA.c:244): incr = xsize / 4
+        int snba_form = 0;                      // qh_rxa_set_snba_form (the blanker's two forms, below)
+        std::vector<SnbaTune> snba_tune_h;      // [nch]: the blanker's tuning, uploaded to snba_tune when a tuning setter has run
+        // a display bank fed from the sender rows at the end of every call (qh_rxa_attach_display)
+        qh_ana *disp = nullptr;
+        int disp_ss = 0;
+        int pll_check_only = 0;                 // diagnostics (qh_rxa_debug_pll): count unconverged tiles without re-running them
+        int agc_form = 0;                       // diagnostics (qh_rxa_debug_agc): 1 = the sample-by-sample form of the wcpAGC loop
+        bool emnr_tables = false;               // qh_rxa_SetEMNRTables has run: the tables below
+        std::vector<double> h_GG, h_GGS, h_zeta; std::vector<int> h_zeta_true; double h_zrange[4] = { 0, 0, 0, 0 };
+    } wide;
+    bool graph_seen = false;
     GraphKey graph_key;
     GraphSlot graph_slot[256];
     long long graph_launches = 0;
@@ -245,7 +272,6 @@ struct Engine {
     bool band2g = false;                    // 8192-point tiles shared by two lane groups (osfir8k_kernel): masks stored [even | odd]
     bool band6k = false;                    // 6144-point tiles on 384 lanes (osfir6k_kernel)
     int dbg_forms = [] { const char *e = std::getenv("QH_DBG_FORMS"); return e ? std::atoi(e) : 0; }();   // see process_chain
-    int band_tile_pref = 0;                 // qh_rxa_set_band_tile: 0 / 4096: 4096-point tiles, 8192: the two-group tiles
     std::vector<cd> band_mask(const std::vector<cd> &h) const;
     unsigned long long *nco_phase = nullptr, *nco_dphase = nullptr, *nco_parked = nullptr;
     double2 *nco_step = nullptr;
@@ -272,8 +298,7 @@ struct Engine {
     // adds them up (the qh_rat resamplers hold their own)
     std::map<void *, long long> owned;
     long long dev_bytes() const { long long b = 0; for (const auto &o : owned) b += o.second; return b; }
-    // timing
-    bool timing = false;
+    // timing (wide.timing)
     std::vector<hipEvent_t> ev;
     std::vector<int> ev_cat;
     int ev_used = 0;
@@ -295,6 +320,22 @@ struct Engine {
     };
     struct ChanList { int *dev = nullptr; int n = 0; };
     ChanList lists[L_COUNT];
+    // The channel lists of a stage that is made on first use: R rows of nch slots in one device block of their own (an engine that never
+    // runs the stage allocates nothing for it), row r's slots and count in row[r] (also lists[r]) and its channels on the host in h[r].
+    // list_make allocates the block (through alloc(), so `owned` holds it; the caller has quiesced) and points the rows into it;
+    // list_upload copies the host rows, each padded with zeros to nch, into it on `stream` -- `image` is that copy's source, kept here
+    // because the copy is not waited for -- and does nothing while the block has not been made.
+    template <int R> struct ListBlock {
+        int *block = nullptr;
+        ChanList row[R];
+        std::vector<int> h[R], image;
+        const ChanList &operator[](int r) const { return row[r]; }
+        bool any() const { for (const ChanList &l : row) if (l.n) return true; return false; }
+        void clear() { for (std::vector<int> &v : h) v.clear(); }
+        void count() { for (int r = 0; r < R; r++) row[r].n = (int)h[r].size(); }
+    };
+    template <int R> int list_make(ListBlock<R> &b);
+    template <int R> int list_upload(ListBlock<R> &b);
     int *list_block = nullptr;
     // channel pairs for the real filters behind the detectors (osfir_kernel PAIR): FM de-emphasis, bp1 of the AM and of the SAM channels
     // (partners have the same design; bp1: count 0 when a channel of the kind has complex taps; FM: de_real says that no running
@@ -315,12 +356,10 @@ struct Engine {
     std::vector<double> ap_M_h;
     std::vector<ApParam> ap_prm_h;
     int ap_alloc();
-    // xssql (qh_ssql.hpp), made when a channel first runs it: its two channel lists (by the buffer that holds the row, as L_AP; a
-    // block of their own, so that an engine without SSQL allocates what it did before), parameters, state, the ramps, the tiles' rows
+    // xssql (qh_ssql.hpp), made when a channel first runs it: its two channel lists (by the buffer that holds the row, as L_AP),
+    // parameters, state, the ramps, the tiles' rows
     // [nch][ssql_ends_cap][kSsE], the crossing / window / trigger bits [3][nch][ssql_wcap] and the words' machine records [nch][ssql_wcap]
-    ChanList ssql_lists[2];
-    std::vector<int> ssql_h[2];
-    int *ssql_list_block = nullptr;
+    ListBlock<2> ssql_lists;
     SsqlParam *ssql_prm = nullptr;
     SsqlState *ssql_state = nullptr;
     double *ssql_cup = nullptr, *ssql_cdown = nullptr, *ssql_ends = nullptr;
@@ -330,13 +369,11 @@ struct Engine {
     int ssql_L = 0, ssql_ntup = 0, ssql_ntdown = 0;
     std::vector<SsqlParam> ssql_prm_h;
     int ssql_alloc();
-    bool ssql_listed() const { return ssql_lists[0].n || ssql_lists[1].n; }
-    // xfmsq (qh_fmsq.hpp), made when a channel first runs it, in blocks of its own: the list of its channels and their pairs for the
-    // noise filter (neighbours in the list), parameters, state, the ramps, the noise filter (fc[FC_FQ]: one design for the engine's FMSQ
-    // channels) and its output rows [nch][fq_noise_cap]
-    ChanList fq_list, fq_pairs;
-    std::vector<int> fq_h, fq_pairs_h;
-    int *fq_list_block = nullptr;
+    // xfmsq (qh_fmsq.hpp), made when a channel first runs it, in blocks of its own: the list of its channels [0] and their pairs for the
+    // noise filter [1] (neighbours in the list, np_fq of them; an odd channel out is its own partner, so up to nch + 1 entries: they
+    // run on into the third row, which holds nothing else), parameters, state, the ramps, the noise filter (fc[FC_FQ]: one design for
+    // the engine's FMSQ channels) and its output rows [nch][fq_noise_cap]
+    ListBlock<3> fq_lists;
     int np_fq = 0;
     FmsqParam *fq_prm = nullptr;
     FmsqState *fq_state = nullptr;
@@ -348,13 +385,11 @@ struct Engine {
     int prm_fmsq(ChanCfg &c, int ch);
     int fmsq_filter();
     void launch_fmsq_flush();
-    // xeqp (wdsp/eq.c:166-208), made when a channel first runs it, in blocks of their own: the list of its channels and of the others
-    // (the linear path passes those on in a pointwise pass) and fc[FC_EQP], one mask row per channel (EQ profiles are per channel, as bp1's
-    // designs)
-    ChanList eq_list, eq_rest;
-    std::vector<int> eq_h, eq_rest_h;
+    // xeqp (wdsp/eq.c:166-208), made when a channel first runs it, in blocks of their own: the list of its channels [0] and of the others
+    // [1] (the linear path passes those on in a pointwise pass; counted as none until the stage exists) and fc[FC_EQP], one mask row per
+    // channel (EQ profiles are per channel, as bp1's designs)
+    ListBlock<2> eq_lists;
     std::vector<std::vector<cd>> eq_taps_h;     // per channel: the taps behind the mask row last uploaded (qh_rxa_debug_eqp); empty until then
-    int *eq_list_block = nullptr;
     int eq_key_built = 0;
     bool eq_lists_dirty = false;
     std::vector<cd> eqp_taps(const ChanCfg &c) const;
@@ -364,20 +399,16 @@ struct Engine {
     // ([0] the sender's; [1] / [2] the siphon's by the buffer that holds the row behind bp1, as L_AP), the sender's float rows of the last
     // call [nch][snd_cap] (snd_n samples each), the siphon's rings [nch][kSipSize] with their write indices [nch], and per channel the
     // fixed AGC gain that the output matrix applies behind the siphon's point (1.0 where it does not: refresh_params)
-    ChanList tap_lists[3];
-    std::vector<int> tap_h[3];
-    int *tap_list_block = nullptr;
+    ListBlock<3> tap_lists;
     float2 *snd_rows = nullptr;
     long long snd_cap = 0, snd_n = 0;
     double2 *sip_ring = nullptr;
     int *sip_idx = nullptr;
     double *tap_gain = nullptr;
-    bool taps_listed() const { return tap_lists[0].n || tap_lists[1].n || tap_lists[2].n; }
     int taps_alloc();
     // gen0 (qh_gen.hpp), made when a channel first runs it: the list of its channels, their parameters and state, the sweep tables
     // [nch][kGenCkMax] and the pulse's raised-cosine edge [pntrans + 1] (calc_pulse, gen.c:88-95)
-    ChanList gen_list;
-    std::vector<int> gen_h;
+    ListBlock<1> gen_lists;
     GenParam *gen_prm = nullptr;
     GenState *gen_state = nullptr;
     double2 *gen_ck = nullptr;
@@ -387,10 +418,8 @@ struct Engine {
     int gen_alloc();
     int prm_gen(ChanCfg &c, int ch);
     int refresh_gen();
-    // a display bank fed from the sender rows at the end of every call (qh_rxa_attach_display); disp_fed: recorded on the bank's stream
-    // behind its append of the rows, waited for by the engine's stream ahead of the next call's launches
-    qh_ana *disp = nullptr;
-    int disp_ss = 0;
+    // the attached display (wide.disp): disp_fed is recorded on the bank's stream behind its append of the rows and waited for by the
+    // engine's stream ahead of the next call's launches
     hipEvent_t disp_fed = nullptr;
     bool disp_fed_pending = false;
     int feed_display(qh_ana *a, int ss);
@@ -399,20 +428,17 @@ struct Engine {
     SnbaParam snba_prm{};
     double *snba_state = nullptr, *snba_hin = nullptr, *snba_hout = nullptr, *snba_scratch = nullptr;
     SnbaIdx *snba_idx = nullptr;
-    SnbaTune *snba_tune = nullptr;          // [nch]; host copy below, uploaded when a tuning setter has run
-    std::vector<SnbaTune> snba_tune_h;
+    SnbaTune *snba_tune = nullptr;          // [nch]; host copy wide.snba_tune_h, uploaded when a tuning setter has run
     bool snba_tune_dirty = true;
     int snba_alloc();
-    int snba_ovrlp = 4;                 // create_rxa's overlap (RXA.c:244): incr = xsize / 4
     void snba_plan(int ovrlp);
     int snba_set_ovrlp(int ovrlp);
     // The blanker's two forms (qh_snba.hpp).  qh_rxa_set_snba_form: 0 = the single kernel where it can run (dsp_rate up to 48 kHz and
     // dsp_size up to 1024) and the three passes elsewhere, 1 = the three passes everywhere.  The state is one layout for both, so the
-    // form may change between calls.  snba_r12: the passes' 12 kHz rows, [2][nch][snba_r12_cap] (into the frames | out of them).
-    int snba_form = 0;
+    // form (wide.snba_form) may change between calls.  snba_r12: the passes' 12 kHz rows, [2][nch][snba_r12_cap] (into the frames | out of them).
     double *snba_r12 = nullptr;
     long long snba_r12_cap = 0;
-    bool snba_rows() const { return snba_form == 1 || snba_prm.ratio > kSnbFusedMaxRatio || dsp_size > kSnbFusedMaxDsp; }
+    bool snba_rows() const { return wide.snba_form == 1 || snba_prm.ratio > kSnbFusedMaxRatio || dsp_size > kSnbFusedMaxDsp; }
     // the dsp_rate / dsp_size pairs the blanker takes: 12000 * 2^k (k = 0 .. 5), the size a multiple of the ratio and at most 4096
     static bool snba_accepts(int rate, int size);
     static const char *snba_accepted() { return "SNBA: dsp_rate 12000, 24000, 48000, 96000, 192000 or 384000 and dsp_size a multiple of dsp_rate / 12000, up to 4096"; }
@@ -421,8 +447,6 @@ struct Engine {
     EmnrScalars *emnr_scal = nullptr;
     double *emnr_state = nullptr, *emnr_window = nullptr, *emnr_GG = nullptr, *emnr_GGS = nullptr, *emnr_zeta = nullptr;
     int *emnr_zeta_true = nullptr;
-    bool emnr_tables = false;
-    std::vector<double> h_GG, h_GGS, h_zeta; std::vector<int> h_zeta_true; double h_zrange[4] = { 0, 0, 0, 0 };
     AmsqParam *amsq_prm = nullptr;
     AmsqState *amsq_state = nullptr;
     double *amsq_cup = nullptr, *amsq_cdown = nullptr, *amsq_mag = nullptr;
@@ -434,10 +458,8 @@ struct Engine {
     // short-form channels alone and lms_long_lists[3 f + k] the others, in a block of their own made with the first of them (an engine
     // without one allocates what it did before); lms_long_Ks: bit log2(K) set when a channel of the list runs at K taps per lane.
     // lms_long_rows[f]: weights and ring [nch][kLmsLongRow], made when filter f first has such a channel.
-    ChanList lms_long_lists[6];
-    std::vector<int> lms_long_h[6];
+    ListBlock<6> lms_long_lists;
     unsigned lms_long_Ks[6] = { 0, 0, 0, 0, 0, 0 };
-    int *lms_long_list_block = nullptr;
     double *lms_long_rows[2] = { nullptr, nullptr };
     static bool lms_long_form(const ChanCfg::Lms &m) { return m.taps > 64 || m.delay < 1 || m.delay > 64; }
     int lms_n(int k) const { return lists[L_LMS + k].n + lms_long_lists[k].n; }       // channels of either form on LMS list k
@@ -478,8 +500,6 @@ struct Engine {
     double *sb_phi = nullptr, *sb_sum = nullptr, *sb_start = nullptr;
     long long sb_phi_key = -1;
     int set_sb_phi(long long n, int S);
-    int pll_check_only = 0;                 // diagnostics (qh_rxa_debug_pll): count unconverged tiles without re-running them
-    int agc_form = 0;                       // diagnostics (qh_rxa_debug_agc): 1 = the sample-by-sample form of the wcpAGC loop
     SamChanParam *sam_prm = nullptr;
     PllParam sam_pll_prm{}, fm_pll_prm{};
     SnotchParam *sn_prm = nullptr;
@@ -521,7 +541,6 @@ struct Engine {
     int *agc_lout = nullptr, *agc_rewin_list = nullptr;
     AgcParam *lim_prm = nullptr;        // FM detector limiter: a wcpAGC of its own (fmd.c:48-72)
     AgcState *lim_state = nullptr;
-    bool meters_on = false;
     MeterState *m_adc = nullptr, *m_s = nullptr, *m_agc = nullptr;
     MeterParam m_prm{};
     // meters fused into the nbp0 launch of the linear fast path (qh_osfir.hpp METER): per tile and row of 16 lanes partials of the
@@ -672,6 +691,22 @@ template <typename T> int Engine::alloc(T *&p, long long n, bool zero)
     QH_HIP(dev_alloc(&p, (size_t)n));
     owned[p] = n * (long long)sizeof(T);
     if (zero) QH_HIP(hipMemsetAsync(p, 0, (size_t)n * sizeof(T), stream));
+    return QH_OK;
+}
+
+template <int R> int Engine::list_make(ListBlock<R> &b)
+{
+    if (int rc = alloc(b.block, (long long)R * nch)) return rc;
+    for (int r = 0; r < R; r++) b.row[r].dev = b.block + (size_t)nch * r;
+    return QH_OK;
+}
+
+template <int R> int Engine::list_upload(ListBlock<R> &b)
+{
+    if (!b.block) return QH_OK;
+    b.image.assign((size_t)R * nch, 0);
+    for (int r = 0; r < R; r++) std::copy(b.h[r].begin(), b.h[r].end(), b.image.begin() + (size_t)nch * r);
+    QH_HIP(hipMemcpyAsync(b.block, b.image.data(), b.image.size() * sizeof(int), hipMemcpyHostToDevice, stream));
     return QH_OK;
 }
 

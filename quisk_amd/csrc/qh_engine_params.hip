@@ -149,7 +149,7 @@ int Engine::init()
     if (!stream) { QH_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking)); own_stream = true; }
     cfg.assign((size_t)nch, ChanCfg());
     for (ChanCfg &c : cfg) c.eqp_nc = c.fm_nc_de = c.fm_nc_aud = std::max(2048, dsp_size);     // create_eqp's nc, RXA.c:265; create_fmd's, RXA.c:209,211
-    snba_tune_h.assign((size_t)nch, SnbaTune{ 64, 2, 10, 2, 2, 0, 8.0, 20.0, 0.5 });         // create_snba's arguments, RXA.c:183-202
+    wide.snba_tune_h.assign((size_t)nch, SnbaTune{ 64, 2, 10, 2, 2, 0, 8.0, 20.0, 0.5 });         // create_snba's arguments, RXA.c:183-202
     // the fircore stages: the FM pair holds a mask row per distinct design among its channels (one row to begin with), xfmsq's noise
     // filter one design for its channels, the others one per channel
     for (int s = 0; s < FC_COUNT; s++) {
@@ -157,7 +157,7 @@ int Engine::init()
         fc[s].by_design = s == FC_DE || s == FC_AUD;
         fc[s].chan.assign((size_t)nch, Fircore::Chan());
     }
-    fc[FC_NBP].dirty = &ChanCfg::nbp_dirty; fc[FC_BP1].dirty = &ChanCfg::bp1_dirty; fc[FC_SNB].dirty = &ChanCfg::snb_dirty;
+    fc[FC_NBP].dirty = &ChanCfg::Work::nbp_dirty; fc[FC_BP1].dirty = &ChanCfg::Work::bp1_dirty; fc[FC_SNB].dirty = &ChanCfg::Work::snb_dirty;
     fc[FC_FQ].can_long = fc[FC_EQP].can_long = false;
 
     std::vector<cd> tw = fft_twiddle_table(kNfft);
@@ -227,9 +227,9 @@ int Engine::refresh_params()
         std::vector<unsigned long long> law;
         for (int ch = 0; ch < nch; ch++) {
             const ChanCfg &c = cfg[(size_t)ch];
-            if (!c.nco_dirty) continue;
+            if (!c.w.nco_dirty) continue;
             nco_list.push_back(ch);
-            const bool flip = (c.shift_run != 0) != (c.shift_on_device != 0);
+            const bool flip = (c.shift_run != 0) != (c.w.shift_on_device != 0);
             law.push_back(flip ? (c.shift_run ? 2ull : 1ull) : 0ull);
             law.push_back(c.shift_run ? turns_fx(c.shift_freq, (double)in_rate) : 0ull);
         }
@@ -242,16 +242,16 @@ int Engine::refresh_params()
     }
     for (int ch = 0; ch < nch; ch++) {
         ChanCfg &c = cfg[(size_t)ch];
-        if (c.nco_dirty) {
-            if ((c.shift_run != 0) != (c.shift_on_device != 0)) {
+        if (c.w.nco_dirty) {
+            if ((c.shift_run != 0) != (c.w.shift_on_device != 0)) {
                 launch_nco_park(ch, c.shift_run ? 1 : 0);
-                c.shift_on_device = c.shift_run ? 1 : 0;
+                c.w.shift_on_device = c.shift_run ? 1 : 0;
             }
             // calc_shift, wdsp/shift.c:29-34: delta = 2*pi*shift/rate per input sample
             if (int rc = put_row(nco_dphase, ch, c.shift_run ? turns_fx(c.shift_freq, (double)in_rate) : 0ull)) return rc;
-            c.nco_dirty = false;
+            c.w.nco_dirty = false;
         }
-        if (c.epi_dirty) {
+        if (c.w.epi_dirty) {
             // xwcpagc mode 0 (wcpAGC.c:167-175) then xpanel (patchpanel.c:55-101) as one 2x2 real matrix
             // (with a position-1 anf / anr / bp1 behind it the gain is applied at the AGC's own spot instead: fix_before)
             const double g = (c.agc_run && c.agc_mode == 0 && !c.fix_before()) ? c.agc_fixed : 1.0;
@@ -270,28 +270,28 @@ int Engine::refresh_params()
             case 3: e.a = 0; e.b = gI * sQ * g; e.c = gQ * sI * g; e.d = 0; break;
             }
             if (int rc = put_row(epi, ch, e)) return rc;
-            c.epi_dirty = false;
+            c.w.epi_dirty = false;
         }
-        if (c.nbp_dirty) c.snb_dirty = true;        // bpsnba's nbp shares window, auto-increase and the notch database with nbp0 (nc and mp are its own)
-        if (c.snb_dirty && c.snba_run && fc[FC_SNB].mask) if (int rc = snb_mask(c, ch)) return rc;
-        if (c.snb_flush && fc[FC_SNB].hist[0]) if (int rc = zero_rows(fc[FC_SNB], ch)) return rc;         // setNc_fircore zeroes the delay line
-        c.snb_flush = false;
-        if (c.nbp_dirty) {
+        if (c.w.nbp_dirty) c.w.snb_dirty = true;        // bpsnba's nbp shares window, auto-increase and the notch database with nbp0 (nc and mp are its own)
+        if (c.w.snb_dirty && c.snba_run && fc[FC_SNB].mask) if (int rc = snb_mask(c, ch)) return rc;
+        if (c.w.snb_flush && fc[FC_SNB].hist[0]) if (int rc = zero_rows(fc[FC_SNB], ch)) return rc;         // setNc_fircore zeroes the delay line
+        c.w.snb_flush = false;
+        if (c.w.nbp_dirty) {
             if (int rc = design_band(fc[FC_NBP], c, ch, { c.nbp_run, c.nbp_nc, c.nbp_wintype, c.nbp_mp, c.fnfrun, c.nbp_flow, c.nbp_fhigh, c.nbp_gain }, last_nbp)) return rc;
-            c.nbp_dirty = false;
+            c.w.nbp_dirty = false;
         }
-        if (c.bp1_dirty) {
+        if (c.w.bp1_dirty) {
             if (int rc = design_band(fc[FC_BP1], c, ch, { c.bp1_run, c.bp1_nc, c.bp1_wintype, c.bp1_mp, 0, c.bp1_flow, c.bp1_fhigh, c.bp1_gain }, last_bp1)) return rc;
-            c.bp1_dirty = false;
+            c.w.bp1_dirty = false;
             lists_dirty = true;             // the channel pairs of the real bp1 filters follow the designs
         }
-        if (c.nbp_flush) {      // setNc_fircore re-plans and so zeroes the delay line
+        if (c.w.nbp_flush) {      // setNc_fircore re-plans and so zeroes the delay line
             if (int rc = zero_rows(fc[FC_NBP], ch)) return rc;
-            c.nbp_flush = false;
+            c.w.nbp_flush = false;
         }
-        if (c.bp1_flush) {      // flush_bandpass on off->on (RXA.c:825) and setNc_fircore
+        if (c.w.bp1_flush) {      // flush_bandpass on off->on (RXA.c:825) and setNc_fircore
             if (int rc = zero_rows(fc[FC_BP1], ch)) return rc;
-            c.bp1_flush = false;
+            c.w.bp1_flush = false;
         }
     }
     if (!nco_list.empty())      // retune_list still holds the channels; the new dphase values are in place
@@ -327,7 +327,7 @@ int Engine::snb_mask(ChanCfg &c, int ch)
     for (auto &v : h) v *= (double)(2 * dsp_size);
     std::vector<cd> m;
     if (int rc = put_taps(fc[FC_SNB], ch, h, m)) return rc;
-    c.snb_dirty = false;
+    c.w.snb_dirty = false;
     return QH_OK;
 }
 
@@ -454,7 +454,7 @@ int Engine::demod_init()
     }
     demod_alloc = true;
     lists_dirty = true;
-    for (ChanCfg &c : cfg) c.demod_dirty = true;
+    for (ChanCfg &c : cfg) c.w.demod_dirty = true;
     return QH_OK;
 }
 
@@ -463,16 +463,13 @@ void Engine::build_lists(std::vector<int> (&h)[L_COUNT])
 {
     std::vector<int> stale_cur, stale_other;
     int sam0 = 0;
-    ssql_h[0].clear(); ssql_h[1].clear();
-    fq_h.clear(); fq_pairs_h.clear();
-    for (std::vector<int> &t : tap_h) t.clear();
-    gen_h.clear();
-    for (int k = 0; k < 6; k++) { lms_long_h[k].clear(); lms_long_Ks[k] = 0; }
+    ssql_lists.clear(); fq_lists.clear(); tap_lists.clear(); gen_lists.clear(); lms_long_lists.clear();
+    for (unsigned &ks : lms_long_Ks) ks = 0;
     for (int ch = 0; ch < nch; ch++) {
         const ChanCfg &c = cfg[(size_t)ch];
-        if (c.sender_run) tap_h[0].push_back(ch);
-        if (c.gen_run) gen_h.push_back(ch);
-        if (c.sip_run) tap_h[c.bp1_run ? 2 : 1].push_back(ch);          // where the agc meter finds the channel (L_PLAIN / L_BP1)
+        if (c.sender_run) tap_lists.h[0].push_back(ch);
+        if (c.gen_run) gen_lists.h[0].push_back(ch);
+        if (c.sip_run) tap_lists.h[c.bp1_run ? 2 : 1].push_back(ch);          // where the agc meter finds the channel (L_PLAIN / L_BP1)
         if (c.amsq_run) h[L_AMSQ].push_back(ch);
         if (c.snba_run) h[L_SNBA].push_back(ch);
         if (c.snb_pos() >= 0) h[L_SNB + c.snb_pos()].push_back(ch);
@@ -482,15 +479,15 @@ void Engine::build_lists(std::vector<int> (&h)[L_COUNT])
             if (!c.lms[f].run) continue;
             const int k = 3 * f + (c.lms[f].position ? 1 + at_agc : 0);
             if (!lms_long_form(c.lms[f])) { h[L_LMS + k].push_back(ch); continue; }
-            lms_long_h[k].push_back(ch);
+            lms_long_lists.h[k].push_back(ch);
             lms_long_Ks[k] |= (unsigned)lms_long_K(c.lms[f].taps);          // K is a power of two: its own bit
         }
         if (c.bp1_run) h[L_BP1P + (c.bp1_pos ? 1 : 0)].push_back(ch);
         if (c.fix_before()) h[L_FIX + at_agc].push_back(ch);
         if (c.ap_on()) h[L_AP + (c.bp1_run ? 1 : 0)].push_back(ch);        // where the channel is behind bp1 at either position
-        if (c.ssql_on()) ssql_h[c.bp1_run ? 1 : 0].push_back(ch);
+        if (c.ssql_on()) ssql_lists.h[c.bp1_run ? 1 : 0].push_back(ch);
         if (c.fmd_run && c.lim_run) h[L_LIM].push_back(ch);
-        if (c.fmd_run && c.fmsq_run) fq_h.push_back(ch);
+        if (c.fmd_run && c.fmsq_run) fq_lists.h[0].push_back(ch);
         if (c.amd_run && c.amd_mode == 0) h[L_AM].push_back(ch);
         // SAM channels with sbmode 0 (no all-pass chains) first
         if (c.amd_run && c.amd_mode == 1) { if (c.sbmode == 0) h[L_SAM].insert(h[L_SAM].begin() + sam0++, ch); else h[L_SAM].push_back(ch); }
@@ -498,7 +495,7 @@ void Engine::build_lists(std::vector<int> (&h)[L_COUNT])
         h[c.bp1_run ? L_BP1 : L_PLAIN].push_back(ch);
         // xwcpagc sits between the two bp1 positions (RXA.c:581-586): a position-1 channel is still in `cur` there; channels whose
         // attack window moved in mid-stream go last
-        if (c.agc_run && c.agc_mode != 0) (at_agc ? (c.agc_stale ? stale_other : h[L_AGC_OTHER]) : (c.agc_stale ? stale_cur : h[L_AGC_CUR])).push_back(ch);
+        if (c.agc_run && c.agc_mode != 0) (at_agc ? (c.w.agc_stale ? stale_other : h[L_AGC_OTHER]) : (c.w.agc_stale ? stale_cur : h[L_AGC_CUR])).push_back(ch);
     }
     n_sam0 = sam0;
     n_agc_cur_stale = (int)stale_cur.size(); n_agc_other_stale = (int)stale_other.size();
@@ -541,22 +538,19 @@ void Engine::build_lists(std::vector<int> (&h)[L_COUNT])
     h[L_PAIRS_SAM] = bp1_pairs(h[L_SAM]);
     np_fm = (int)h[L_PAIRS_FM].size() / 2; np_am = (int)h[L_PAIRS_AM].size() / 2; np_sam = (int)h[L_PAIRS_SAM].size() / 2;
     for (int i = 0; i < L_COUNT; i++) lists[i].n = (int)h[i].size();
-    for (int b = 0; b < 2; b++) ssql_lists[b].n = (int)ssql_h[b].size();
-    for (int k = 0; k < 6; k++) lms_long_lists[k].n = (int)lms_long_h[k].size();
-    for (int t = 0; t < 3; t++) tap_lists[t].n = (int)tap_h[t].size();
-    gen_list.n = (int)gen_h.size();
-    for (size_t i = 0; i < fq_h.size(); i += 2) { fq_pairs_h.push_back(fq_h[i]); fq_pairs_h.push_back(i + 1 < fq_h.size() ? fq_h[i + 1] : fq_h[i]); }
-    fq_list.n = (int)fq_h.size(); np_fq = (int)fq_pairs_h.size() / 2;
+    const std::vector<int> &fq = fq_lists.h[0];
+    for (size_t i = 0; i < fq.size(); i += 2) { fq_lists.h[1].push_back(fq[i]); fq_lists.h[1].push_back(i + 1 < fq.size() ? fq[i + 1] : fq[i]); }
+    np_fq = (int)fq_lists.h[1].size() / 2;
+    ssql_lists.count(); fq_lists.count(); tap_lists.count(); gen_lists.count(); lms_long_lists.count();
 }
 
 // xsender / xsiphon (qh_taps.hpp): the lists at the first enable of either, the siphon's rings, indices and gains at its own (the sender's
 // rows follow the call's length: process_chain)
 int Engine::taps_alloc()
 {
-    if (!tap_list_block) {
+    if (!tap_lists.block) {
         if (int rc = quiesce()) return rc;
-        if (int rc = alloc(tap_list_block, 3LL * nch)) return rc;
-        for (int t = 0; t < 3; t++) tap_lists[t].dev = tap_list_block + (size_t)nch * t;
+        if (int rc = list_make(tap_lists)) return rc;
     }
     if ((tap_lists[1].n || tap_lists[2].n) && !sip_ring) {
         if (int rc = quiesce()) return rc;
@@ -580,7 +574,7 @@ int Engine::gen_alloc()
 {
     const double rate = (double)dsp_rate;
     if (int rc = quiesce()) return rc;
-    if (int rc = alloc(gen_list.dev, nch)) return rc;
+    if (int rc = list_make(gen_lists)) return rc;
     if (int rc = alloc(gen_prm, nch, true)) return rc;
     if (int rc = alloc(gen_state, nch, true)) return rc;
     if (int rc = alloc(gen_ck, (long long)nch * kGenCkMax, true)) return rc;
@@ -602,8 +596,8 @@ int Engine::gen_alloc()
     carry.gen.clear();
     gen_prm_h.assign((size_t)nch, GenParam{});
     for (ChanCfg &c : cfg) {
-        c.gen_dirty = c.gen_sweep_dirty = true;
-        c.gen_tone_reset = c.gen_sweep_reset = false;       // (the state is new)
+        c.w.gen_dirty = c.w.gen_sweep_dirty = true;
+        c.w.gen_tone_reset = c.w.gen_sweep_reset = false;       // (the state is new)
     }
     return QH_OK;
 }
@@ -621,7 +615,7 @@ int Engine::prm_gen(ChanCfg &c, int ch)
     q.noise_key = gen_mix64((c.gen_seed_set ? c.gen_seed : kGenGolden * (unsigned long long)(ch + 1)) + kGenGolden * (unsigned long long)(ch + 1));
     q.sweep_mag = c.gen_sweep_mag;
     q.pulse_mag = 1.0; q.pulse_tdelta = kTwoPiRef * 1000.0 / rate;                                                         // gen.c:145-149
-    if (c.gen_sweep_dirty) {
+    if (c.w.gen_sweep_dirty) {
         const SweepWalk w = sweep_walk(rate, c.gen_sweep_f1, c.gen_sweep_f2, c.gen_sweep_rate, kGenWalkMax, kGenCkStep);
         q.sweep_P = w.P; q.sweep_dphs0 = w.dphs0; q.sweep_d2phs = w.d2phs; q.sweep_full = w.full;
         q.sweep_nck = (int)w.ck.size();
@@ -632,13 +626,13 @@ int Engine::prm_gen(ChanCfg &c, int ch)
             QH_HIP(hipMemcpyAsync(gen_ck + (size_t)ch * kGenCkMax, t.data(), t.size() * sizeof(double2), hipMemcpyHostToDevice, stream));
             QH_HIP(hipStreamSynchronize(stream));
         }
-        c.gen_sweep_dirty = false;
+        c.w.gen_sweep_dirty = false;
     }
-    if (c.gen_tone_reset) QH_HIP(hipMemsetAsync(&gen_state[ch].tone_phs, 0, sizeof(double), stream));                       // calc_tone, gen.c:31
-    if (c.gen_sweep_reset) QH_HIP(hipMemsetAsync(&gen_state[ch].sweep_phs, 0, sizeof(double) + sizeof(long long), stream)); // calc_sweep, gen.c:51-52
-    c.gen_tone_reset = c.gen_sweep_reset = false;
+    if (c.w.gen_tone_reset) QH_HIP(hipMemsetAsync(&gen_state[ch].tone_phs, 0, sizeof(double), stream));                       // calc_tone, gen.c:31
+    if (c.w.gen_sweep_reset) QH_HIP(hipMemsetAsync(&gen_state[ch].sweep_phs, 0, sizeof(double) + sizeof(long long), stream)); // calc_sweep, gen.c:51-52
+    c.w.gen_tone_reset = c.w.gen_sweep_reset = false;
     QH_HIP(hipMemcpyAsync(gen_prm + ch, &q, sizeof(q), hipMemcpyHostToDevice, stream));
-    c.gen_dirty = false;
+    c.w.gen_dirty = false;
     return QH_OK;
 }
 
@@ -649,7 +643,7 @@ int Engine::refresh_gen()
     bool up = false;
     for (int ch = 0; ch < nch; ch++) {
         ChanCfg &c = cfg[(size_t)ch];
-        if (!c.gen_dirty) continue;
+        if (!c.w.gen_dirty) continue;
         if (int rc = prm_gen(c, ch)) return rc;
         up = true;
     }
@@ -662,10 +656,10 @@ int Engine::stages_alloc()
 {
     const double rate = (double)dsp_rate;
     if ((lists[L_AP].n || lists[L_AP + 1].n) && !ap_prm) if (int rc = ap_alloc()) return rc;
-    if (ssql_listed() && !ssql_prm) if (int rc = ssql_alloc()) return rc;
-    if (fq_list.n && !fq_prm) if (int rc = fmsq_alloc()) return rc;
-    if (taps_listed()) if (int rc = taps_alloc()) return rc;
-    if (gen_list.n && !gen_prm) if (int rc = gen_alloc()) return rc;
+    if (ssql_lists.any() && !ssql_prm) if (int rc = ssql_alloc()) return rc;
+    if (fq_lists[0].n && !fq_prm) if (int rc = fmsq_alloc()) return rc;
+    if (tap_lists.any()) if (int rc = taps_alloc()) return rc;
+    if (gen_lists[0].n && !gen_prm) if (int rc = gen_alloc()) return rc;
     if ((lists[L_EMNR].n || lists[L_EMNR + 1].n || lists[L_EMNR + 2].n) && !emnr_state) if (int rc = emnr_alloc()) return rc;
     if (lists[L_SNBA].n && !snba_state) if (int rc = snba_alloc()) return rc;
     if (lists[L_AMSQ].n && !amsq_prm) {
@@ -683,7 +677,7 @@ int Engine::stages_alloc()
         QH_HIP(hipMemcpyAsync(amsq_cup, up.data(), up.size() * 8, hipMemcpyHostToDevice, stream));
         QH_HIP(hipMemcpyAsync(amsq_cdown, down.data(), down.size() * 8, hipMemcpyHostToDevice, stream));
         QH_HIP(hipStreamSynchronize(stream));
-        for (ChanCfg &c : cfg) c.amsq_dirty = true;
+        for (ChanCfg &c : cfg) c.w.amsq_dirty = true;
     }
     bool any_lms = false;
     for (int k = 0; k < 6; k++) any_lms = any_lms || lms_n(k);
@@ -701,23 +695,20 @@ int Engine::stages_alloc()
             QH_HIP(hipMemcpyAsync(lms_state[f], init.data(), init.size() * sizeof(LmsState), hipMemcpyHostToDevice, stream));
             QH_HIP(hipStreamSynchronize(stream));
         }
-        for (ChanCfg &c : cfg) { c.lms[0].dirty = c.lms[1].dirty = true; c.lms[0].flush = c.lms[1].flush = false; }
+        for (ChanCfg &c : cfg) { c.w.lms[0].dirty = c.w.lms[1].dirty = true; c.w.lms[0].flush = c.w.lms[1].flush = false; }
     }
     // the long form's lists, and the rows of a filter that has a channel on them: zero, as create_anf / flush_anf leave w[] and d[]
     for (int f = 0; f < 2; f++) {
         if (!lms_long_lists[3 * f].n && !lms_long_lists[3 * f + 1].n && !lms_long_lists[3 * f + 2].n) continue;
-        if (lms_long_list_block && lms_long_rows[f]) continue;
+        if (lms_long_lists.block && lms_long_rows[f]) continue;
         if (int rc = quiesce()) return rc;
-        if (!lms_long_list_block) {
-            if (int rc = alloc(lms_long_list_block, 6LL * nch)) return rc;
-            for (int k = 0; k < 6; k++) lms_long_lists[k].dev = lms_long_list_block + (size_t)nch * k;
-        }
+        if (!lms_long_lists.block) if (int rc = list_make(lms_long_lists)) return rc;
         if (!lms_long_rows[f]) if (int rc = alloc(lms_long_rows[f], (long long)nch * kLmsLongRow, true)) return rc;
     }
     if (lists[L_LIM].n && !lim_prm) {
         if (int rc = alloc(lim_prm, nch)) return rc;
         if (int rc = alloc(lim_state, nch)) return rc;
-        for (ChanCfg &c : cfg) c.lim_dirty = true;
+        for (ChanCfg &c : cfg) c.w.lim_dirty = true;
     }
     return QH_OK;
 }
@@ -770,39 +761,18 @@ int Engine::refresh_lists()
     if (int rc = fc_follow(fc[FC_DE], h[L_FM])) return rc;
     if (int rc = fc_follow(fc[FC_AUD], h[L_FM])) return rc;
     // xfmsq's noise filter keeps its delay line while the stage is off (xfmsq with run 0 does not call its fircore, fmsq.c:143-147)
-    if (int rc = fc_follow(fc[FC_FQ], fq_h)) return rc;
+    if (int rc = fc_follow(fc[FC_FQ], fq_lists.h[0])) return rc;
     std::vector<int> all((size_t)nch * (L_COUNT + 3));
     for (int i = 0; i < L_COUNT; i++) std::copy(h[i].begin(), h[i].end(), all.begin() + (lists[i].dev - list_block));
     std::vector<double> fg((size_t)nch);
     for (int ch = 0; ch < nch; ch++) fg[(size_t)ch] = cfg[(size_t)ch].agc_fixed;
     QH_HIP(hipMemcpyAsync(list_block, all.data(), all.size() * sizeof(int), hipMemcpyHostToDevice, stream));
     QH_HIP(hipMemcpyAsync(fix_gain, fg.data(), fg.size() * sizeof(double), hipMemcpyHostToDevice, stream));
-    std::vector<int> ss;
-    if (ssql_list_block) {
-        ss.assign((size_t)nch * 2, 0);
-        for (int b = 0; b < 2; b++) std::copy(ssql_h[b].begin(), ssql_h[b].end(), ss.begin() + (size_t)nch * b);
-        QH_HIP(hipMemcpyAsync(ssql_list_block, ss.data(), ss.size() * sizeof(int), hipMemcpyHostToDevice, stream));
-    }
-    std::vector<int> ll;
-    if (lms_long_list_block) {
-        ll.assign((size_t)nch * 6, 0);
-        for (int k = 0; k < 6; k++) std::copy(lms_long_h[k].begin(), lms_long_h[k].end(), ll.begin() + (size_t)nch * k);
-        QH_HIP(hipMemcpyAsync(lms_long_list_block, ll.data(), ll.size() * sizeof(int), hipMemcpyHostToDevice, stream));
-    }
-    std::vector<int> tp;
-    if (tap_list_block) {
-        tp.assign((size_t)nch * 3, 0);
-        for (int t = 0; t < 3; t++) std::copy(tap_h[t].begin(), tap_h[t].end(), tp.begin() + (size_t)nch * t);
-        QH_HIP(hipMemcpyAsync(tap_list_block, tp.data(), tp.size() * sizeof(int), hipMemcpyHostToDevice, stream));
-    }
-    if (gen_list.dev && gen_list.n) QH_HIP(hipMemcpyAsync(gen_list.dev, gen_h.data(), gen_h.size() * sizeof(int), hipMemcpyHostToDevice, stream));
-    std::vector<int> fq;
-    if (fq_list_block) {
-        fq.assign((size_t)nch * 3, 0);
-        std::copy(fq_h.begin(), fq_h.end(), fq.begin());
-        std::copy(fq_pairs_h.begin(), fq_pairs_h.end(), fq.begin() + (size_t)nch);
-        QH_HIP(hipMemcpyAsync(fq_list_block, fq.data(), fq.size() * sizeof(int), hipMemcpyHostToDevice, stream));
-    }
+    if (int rc = list_upload(ssql_lists)) return rc;
+    if (int rc = list_upload(lms_long_lists)) return rc;
+    if (int rc = list_upload(tap_lists)) return rc;
+    if (int rc = list_upload(gen_lists)) return rc;
+    if (int rc = list_upload(fq_lists)) return rc;
     QH_HIP(hipStreamSynchronize(stream));
     lists_dirty = false;
     fm_dirty = true;                // the design rows follow the running FM channels
@@ -843,29 +813,29 @@ static AgcParam load_wcpagc(double rate, double tau_attack, double tau_decay, do
 // ---- per-channel parameters of the demodulator stages (refresh_demod: each only when its setter has run)
 int Engine::prm_agc(ChanCfg &c, int ch)
 {
-    if (!c.agc_dirty) return QH_OK;
+    if (!c.w.agc_dirty) return QH_OK;
     // create_rxa's constants (RXA.c:335-358)
     const AgcParam q = load_wcpagc((double)dsp_rate, c.agc_tau_attack, c.agc_tau_decay, 4.0, c.agc_max_gain, c.agc_var_gain, c.agc_max_input, 1.0, 0.250, 0.005,
                                    5.0, 1, 0.500, c.agc_hangtime, c.agc_hang_thresh, 0.100);
     if (q.attack_buffsize + 2 > kAgcRing)
         return set_error(QH_ERR_UNSUPPORTED, "AGC attack of %g s needs a look-ahead of %d samples (limit %d)", c.agc_tau_attack,
                          q.attack_buffsize, kAgcRing - 2);
-    c.agc_abuf = q.attack_buffsize;
+    c.w.agc_abuf = q.attack_buffsize;
     if (int rc = put_row(agc_prm, ch, q)) return rc;
-    c.agc_dirty = false;
+    c.w.agc_dirty = false;
     return QH_OK;
 }
 
 int Engine::prm_emnr(ChanCfg &c, int ch)
 {
-    if (emnr_chan && c.emnr_dirty) {
+    if (emnr_chan && c.w.emnr_dirty) {
         if (c.emnr_run && (c.emnr_npe < 0 || c.emnr_npe > 2 || c.emnr_gain_method < 0 || c.emnr_gain_method > 3))
             return set_error(QH_ERR_UNSUPPORTED, "EMNR: gain methods 0..3 and noise estimators 0..2");
         const EmnrChan ec{ c.emnr_gain_method, c.emnr_npe, c.emnr_ae, 0, c.emnr_ae_zeta, c.emnr_ae_psi, c.emnr_train_zeta, c.emnr_train_t2 };
         if (int rc = put_row(emnr_chan, ch, ec)) return rc;
-        c.emnr_dirty = false;
+        c.w.emnr_dirty = false;
     }
-    if (emnr_state && c.emnr_flush) {           // flush_emnr, emnr.c:583-596: the accumulators and their indices, not the estimators
+    if (emnr_state && c.w.emnr_flush) {           // flush_emnr, emnr.c:583-596: the accumulators and their indices, not the estimators
         EmnrScalars sc;
         QH_HIP(hipMemcpyAsync(&sc, emnr_scal + ch, sizeof(sc), hipMemcpyDeviceToHost, stream));
         QH_HIP(hipStreamSynchronize(stream));
@@ -873,7 +843,7 @@ int Engine::prm_emnr(ChanCfg &c, int ch)
         if (int rc = put_row(emnr_scal, ch, sc, false)) return rc;
         QH_HIP(hipMemsetAsync(emnr_state + (size_t)ch * kEmnrStateDoubles, 0, (size_t)EO_PREVG * sizeof(double), stream));
         QH_HIP(hipStreamSynchronize(stream));
-        c.emnr_flush = false;
+        c.w.emnr_flush = false;
     }
     return QH_OK;
 }
@@ -881,7 +851,7 @@ int Engine::prm_emnr(ChanCfg &c, int ch)
 int Engine::prm_snba(ChanCfg &c, int ch)
 {
     const SnbaParam &q = snba_prm;
-    if (snba_state && c.snba_taps_dirty) {
+    if (snba_state && c.w.snba_taps_dirty) {
         // calc_resample for outresamp (12 kHz -> dsp_rate, gain 2, resample.c:35-79) with the channel's output bandwidth
         if (q.ratio > 1) {
             const int L = q.ratio, ncoef = q.cpp_out * L;
@@ -894,24 +864,24 @@ int Engine::prm_snba(ChanCfg &c, int ch)
             QH_HIP(hipMemcpyAsync(snba_hout + (size_t)ch * ncoef, hp.data(), hp.size() * sizeof(double), hipMemcpyHostToDevice, stream));
             QH_HIP(hipStreamSynchronize(stream));
         }
-        c.snba_taps_dirty = false;
+        c.w.snba_taps_dirty = false;
     }
-    if (snba_state && (c.snba_flush || c.snba_rout_flush)) {
+    if (snba_state && (c.w.snba_flush || c.w.snba_rout_flush)) {
         double *st = snba_state + (size_t)ch * q.state_doubles;
         if (q.cpp_out > 1) QH_HIP(hipMemsetAsync(st + q.off_rout, 0, (size_t)(q.cpp_out - 1) * sizeof(double), stream));
-        if (c.snba_flush) {         // flush_snba, snb.c:161-185: the frame half of xbase, the accumulators, both resamplers
+        if (c.w.snba_flush) {         // flush_snba, snb.c:161-185: the frame half of xbase, the accumulators, both resamplers
             QH_HIP(hipMemsetAsync(st + kSnbX, 0, (size_t)kSnbX * sizeof(double), stream));
             QH_HIP(hipMemsetAsync(st + q.off_inacc, 0, (size_t)(q.state_doubles - q.off_inacc) * sizeof(double), stream));
             if (int rc = put_row(snba_idx, ch, SnbaIdx{ 0, 0, 0, 0, q.init_oaoutidx, { 0, 0, 0 } })) return rc;
         }
     }
-    c.snba_flush = c.snba_rout_flush = false;
+    c.w.snba_flush = c.w.snba_rout_flush = false;
     return QH_OK;
 }
 
 int Engine::prm_amsq(ChanCfg &c, int ch)
 {
-    if (!amsq_prm || !c.amsq_dirty) return QH_OK;
+    if (!amsq_prm || !c.w.amsq_dirty) return QH_OK;
     // calc_amsq, amsq.c:48-64: 10 ms average (RXA.c:165)
     const double rate = (double)dsp_rate;
     AmsqParam q{};
@@ -919,24 +889,25 @@ int Engine::prm_amsq(ChanCfg &c, int ch)
     q.tail_thresh = c.amsq_tail_thresh; q.unmute_thresh = c.amsq_unmute_thresh; q.min_tail = 0.0; q.max_tail = c.amsq_max_tail;
     q.muted_gain = 0.0; q.rate = rate; q.ntup = amsq_ntup; q.ntdown = amsq_ntdown;
     if (int rc = put_row(amsq_prm, ch, q)) return rc;
-    c.amsq_dirty = false;
+    c.w.amsq_dirty = false;
     return QH_OK;
 }
 
 int Engine::prm_lms(ChanCfg &c, int ch)
 {
     for (int f = 0; f < 2 && lms_prm[0]; f++) {
-        ChanCfg::Lms &m = c.lms[f];
-        if (m.dirty) {
+        const ChanCfg::Lms &m = c.lms[f];
+        ChanCfg::Work::Lms &wm = c.w.lms[f];
+        if (wm.dirty) {
             // lidx_min, lidx_max, den_mult, lincr, ldecr of create_rxa (RXA.c:290-295,310-315)
             if (int rc = put_row(lms_prm[f], ch, LmsParam{ m.taps, m.delay, f, 0, m.two_mu, m.gamma, f ? 120.0 : 0.0, 200.0, 6.25e-10, 1.0, 3.0 }))
                 return rc;
-            m.dirty = false;
+            wm.dirty = false;
         }
-        if (m.flush) {          // flush_anf (anf.c:135-140): delay line and weights; lidx / ngamma carry on
+        if (wm.flush) {          // flush_anf (anf.c:135-140): delay line and weights; lidx / ngamma carry on
             QH_HIP(hipMemsetAsync(lms_state[f] + ch, 0, offsetof(LmsState, lidx), stream));
             if (lms_long_rows[f]) QH_HIP(hipMemsetAsync(lms_long_rows[f] + (size_t)ch * kLmsLongRow, 0, (size_t)kLmsLongRow * sizeof(double), stream));
-            m.flush = false;
+            wm.flush = false;
         }
     }
     return QH_OK;
@@ -944,21 +915,21 @@ int Engine::prm_lms(ChanCfg &c, int ch)
 
 int Engine::prm_lim(ChanCfg &c, int ch)
 {
-    if (!c.lim_dirty || !lim_prm) return QH_OK;
+    if (!c.w.lim_dirty || !lim_prm) return QH_OK;
     // calc_fmd's create_wcpagc(1, 5, 1, ..., 0.001, 0.008, 4, lim_gain, 1.0, 1.0, 1.0, 0.9, 0.250, 0.004, 4.0, 0,
     // 0.500, 0.500, 2.000, 0.100) (fmd.c:48-72) through loadWcpAGC; a new limiter starts cleared
     const AgcParam q = load_wcpagc((double)dsp_rate, 0.001, 0.008, 4.0, c.lim_gain, 1.0, 1.0, 0.9, 0.250, 0.004, 4.0, 0, 0.500, 0.500, 2.000, 0.100);
     if (int rc = put_row(lim_prm, ch, q, false)) return rc;
     QH_HIP(hipMemsetAsync(lim_state + ch, 0, sizeof(AgcState), stream));
     if (int rc = put_row(&lim_state[ch].out_index, 0, kAgcRing - 1)) return rc;        // out_index = -1 (calc_wcpagc, wcpAGC.c:34)
-    c.lim_dirty = false;
+    c.w.lim_dirty = false;
     return QH_OK;
 }
 
 // the detectors' own parameters: AM's fade leveller, SAM's sideband mode, FM's gain and its CTCSS notch
 int Engine::prm_detect(ChanCfg &c, int ch)
 {
-    if (!c.demod_dirty) return QH_OK;
+    if (!c.w.demod_dirty) return QH_OK;
     const int lf = c.levelfade;
     const double again = (double)dsp_rate / (c.fm_dev * kTwoPiRef);     // wdsp/fmd.c:44
     const SamChanParam sp{ c.sbmode, c.levelfade };
@@ -972,12 +943,12 @@ int Engine::prm_detect(ChanCfg &c, int ch)
     if (int rc = put_row(fm_again, ch, again, false)) return rc;
     if (int rc = put_row(sam_prm, ch, sp, false)) return rc;
     if (int rc = put_row(sn_prm, ch, sn, false)) return rc;
-    if (c.ctcss_flush) {                    // calc_snotch ends with flush_snotch, wdsp/iir.c:48
+    if (c.w.ctcss_flush) {                    // calc_snotch ends with flush_snotch, wdsp/iir.c:48
         QH_HIP(hipMemsetAsync(sn_state + ch, 0, sizeof(SnotchState), stream));
-        c.ctcss_flush = false;
+        c.w.ctcss_flush = false;
     }
     QH_HIP(hipStreamSynchronize(stream));
-    c.demod_dirty = false;
+    c.w.demod_dirty = false;
     return QH_OK;
 }
 
@@ -1013,7 +984,7 @@ int Engine::fm_filters()
         std::vector<int> row_of((size_t)nch, 0);
         for (int ch = 0; ch < nch; ch++) {
             ChanCfg &c = cfg[(size_t)ch];
-            bool &flush = s ? c.fm_aud_flush : c.fm_de_flush;
+            bool &flush = s ? c.w.fm_aud_flush : c.w.fm_de_flush;
             if (flush) { if (int rc = zero_rows(f, ch)) return rc; flush = false; }      // setNc_fircore, firmin.c:455-467
             if (!c.fmd_run) continue;
             FmRow k;
@@ -1071,9 +1042,9 @@ int Engine::refresh_demod()
     // no longer holds (wcpAGC.c:197-210 only rescans when the sample that leaves equals it): the time tiles take the window's maximum,
     // so that channel stays on the kernel that steps the reference's bookkeeping -- it alone: the lists put such channels last
     for (ChanCfg &c : cfg) {
-        if (!c.agc_dirty || !c.agc_ran) continue;
+        if (!c.w.agc_dirty || !c.w.agc_ran) continue;
         const int abuf = (int)std::ceil((double)dsp_rate * 4.0 * c.agc_tau_attack);
-        if (c.agc_abuf != abuf) { c.agc_rewindow = true; if (!c.agc_stale) { c.agc_stale = true; lists_dirty = true; } }
+        if (c.w.agc_abuf != abuf) { c.w.agc_rewindow = true; if (!c.w.agc_stale) { c.w.agc_stale = true; lists_dirty = true; } }
     }
     if (lists_dirty) if (int rc = refresh_lists()) return rc;
     for (int ch = 0; ch < nch; ch++) {
@@ -1108,7 +1079,7 @@ void Engine::snba_plan(int ovrlp)
 int Engine::snba_set_ovrlp(int ovrlp)
 {
     if (ovrlp < 1 || ovrlp > kSnbX || kSnbX / ovrlp < 1) return set_error(QH_ERR_INVALID, "SetRXASNBAovrlp: 1 .. %d", kSnbX);
-    snba_ovrlp = ovrlp;
+    wide.snba_ovrlp = ovrlp;
     if (!snba_state) return QH_OK;                       // nothing built yet: snba_alloc plans with it
     QH_HIP(hipSetDevice(device));
     if (int rc = quiesce()) return rc;
@@ -1147,7 +1118,7 @@ int Engine::snba_alloc()
     q.cpp_in = q.ratio > 1 ? 140 * q.ratio + 1 : 1;
     q.cpp_out = q.ratio > 1 ? 141 : 1;
     q.asize = 64; q.npasses = 2; q.b = 10; q.pre = 2; q.post = 2; q.k1 = 8.0; q.k2 = 20.0; q.pmultmin = 0.5;
-    snba_plan(snba_ovrlp);
+    snba_plan(wide.snba_ovrlp);
     if (int rc = alloc(snba_state, (long long)nch * q.state_doubles, true)) return rc;
     if (int rc = alloc(snba_idx, nch)) return rc;
     std::vector<SnbaIdx> ix((size_t)nch, SnbaIdx{ 0, 0, 0, 0, q.init_oaoutidx, { 0, 0, 0 } });
@@ -1170,7 +1141,7 @@ int Engine::snba_alloc()
     if (int rc = fc_alloc(fc[FC_SNB])) return rc;
     QH_HIP(hipStreamSynchronize(stream));
     carry.snba_frames.clear();
-    for (ChanCfg &c : cfg) { c.snba_taps_dirty = true; c.snb_dirty = true; c.snba_flush = c.snba_rout_flush = false; c.snb_flush = false; }
+    for (ChanCfg &c : cfg) { c.w.snba_taps_dirty = true; c.w.snb_dirty = true; c.w.snba_flush = c.w.snba_rout_flush = false; c.w.snb_flush = false; }
     return QH_OK;
 }
 
@@ -1186,7 +1157,7 @@ int Engine::emnr_alloc()
     q.alpha = tc(0.985);
     q.eps_floor = 1.0e-300; q.gamma_max = 40.0; q.xi_min = std::pow(10.0, -40.0 / 10.0); q.q = 0.2; q.gmax = 10000.0;
     q.dim_zeta = 60;
-    q.z_gamma_min = h_zrange[0]; q.z_gamma_max = h_zrange[1]; q.z_xihat_min = h_zrange[2]; q.z_xihat_max = h_zrange[3];
+    q.z_gamma_min = wide.h_zrange[0]; q.z_gamma_max = wide.h_zrange[1]; q.z_xihat_min = wide.h_zrange[2]; q.z_xihat_max = wide.h_zrange[3];
     q.alphaCsmooth = tc(0.7); q.alphaMax = tc(0.96); q.alphaCmin = tc(0.7); q.alphaMin_max_value = tc(0.3);
     q.snrq = -incr / (0.064 * rate);
     q.betamax = tc(0.8);
@@ -1264,13 +1235,13 @@ int Engine::emnr_alloc()
         QH_HIP(hipMemcpyAsync(emnr_scal + ch, &sc0, sizeof(sc0), hipMemcpyHostToDevice, stream));
     }
     QH_HIP(hipMemcpyAsync(emnr_window, win.data(), win.size() * 8, hipMemcpyHostToDevice, stream));
-    QH_HIP(hipMemcpyAsync(emnr_GG, h_GG.data(), h_GG.size() * 8, hipMemcpyHostToDevice, stream));
-    QH_HIP(hipMemcpyAsync(emnr_GGS, h_GGS.data(), h_GGS.size() * 8, hipMemcpyHostToDevice, stream));
-    QH_HIP(hipMemcpyAsync(emnr_zeta, h_zeta.data(), h_zeta.size() * 8, hipMemcpyHostToDevice, stream));
-    QH_HIP(hipMemcpyAsync(emnr_zeta_true, h_zeta_true.data(), h_zeta_true.size() * 4, hipMemcpyHostToDevice, stream));
+    QH_HIP(hipMemcpyAsync(emnr_GG, wide.h_GG.data(), wide.h_GG.size() * 8, hipMemcpyHostToDevice, stream));
+    QH_HIP(hipMemcpyAsync(emnr_GGS, wide.h_GGS.data(), wide.h_GGS.size() * 8, hipMemcpyHostToDevice, stream));
+    QH_HIP(hipMemcpyAsync(emnr_zeta, wide.h_zeta.data(), wide.h_zeta.size() * 8, hipMemcpyHostToDevice, stream));
+    QH_HIP(hipMemcpyAsync(emnr_zeta_true, wide.h_zeta_true.data(), wide.h_zeta_true.size() * 4, hipMemcpyHostToDevice, stream));
     QH_HIP(hipStreamSynchronize(stream));
     if (int rc = emnr_lds_limit()) return rc;
-    for (ChanCfg &c : cfg) { c.emnr_dirty = true; c.emnr_flush = false; }
+    for (ChanCfg &c : cfg) { c.w.emnr_dirty = true; c.w.emnr_flush = false; }
     return QH_OK;
 }
 
@@ -1423,7 +1394,7 @@ int Engine::ap_alloc()
     ap_M_h.assign((size_t)nch * kApDim * kApDim, 0.0);
     ap_prm_h.assign((size_t)nch, ApParam{});
     ap_L = 0;
-    for (ChanCfg &c : cfg) { c.ap_dirty = true; c.sp_flush = false; for (bool &f : c.mp_flush) f = false; }    // the state starts at zero
+    for (ChanCfg &c : cfg) { c.w.ap_dirty = true; c.w.sp_flush = false; for (bool &f : c.w.mp_flush) f = false; }    // the state starts at zero
     return QH_OK;
 }
 
@@ -1459,7 +1430,7 @@ static void ap_transition(const ApParam &q, int L, double *T)
 int Engine::refresh_ap(const ChainCall &k)
 {
     if (!ap_prm) {
-        for (ChanCfg &c : cfg) { c.sp_flush = false; for (bool &f : c.mp_flush) f = false; }
+        for (ChanCfg &c : cfg) { c.w.sp_flush = false; for (bool &f : c.w.mp_flush) f = false; }
         return QH_OK;
     }
     const int nap = k.mixed ? lists[L_AP].n + lists[L_AP + 1].n : 0;
@@ -1479,17 +1450,17 @@ int Engine::refresh_ap(const ChainCall &k)
     const double *last_T = nullptr;
     for (int ch = 0; ch < nch; ch++) {
         ChanCfg &c = cfg[(size_t)ch];
-        if (c.sp_flush || c.mp_flush[0] || c.mp_flush[1]) {            // flush_speak: that cascade's x / y history, I and Q
+        if (c.w.sp_flush || c.w.mp_flush[0] || c.w.mp_flush[1]) {            // flush_speak: that cascade's x / y history, I and Q
             for (int comp = 0; comp < 2; comp++) {
                 double *st = ap_state + (size_t)ch * kApW + (size_t)comp * kApDim;
-                if (c.sp_flush) QH_HIP(hipMemsetAsync(st + kApSpeakAt, 0, kApCascade * sizeof(double), stream));
+                if (c.w.sp_flush) QH_HIP(hipMemsetAsync(st + kApSpeakAt, 0, kApCascade * sizeof(double), stream));
                 for (int p = 0; p < kApPeaks; p++)
-                    if (c.mp_flush[p]) QH_HIP(hipMemsetAsync(st + kApPeakAt + kApCascade * p, 0, kApCascade * sizeof(double), stream));
+                    if (c.w.mp_flush[p]) QH_HIP(hipMemsetAsync(st + kApPeakAt + kApCascade * p, 0, kApCascade * sizeof(double), stream));
             }
-            c.sp_flush = false;
-            for (bool &f : c.mp_flush) f = false;
+            c.w.sp_flush = false;
+            for (bool &f : c.w.mp_flush) f = false;
         }
-        if (!c.ap_dirty && !(nap && L != ap_L && c.ap_on())) continue;
+        if (!c.w.ap_dirty && !(nap && L != ap_L && c.ap_on())) continue;
         ApParam &q = ap_prm_h[(size_t)ch];
         q = ApParam{};
         q.sp = bq(c.sp_f, c.sp_bw, c.sp_gain);
@@ -1506,7 +1477,7 @@ int Engine::refresh_ap(const ChainCall &k)
             QH_HIP(hipMemcpyAsync(ap_M + (size_t)ch * kApDim * kApDim, T, (size_t)kApDim * kApDim * sizeof(double), hipMemcpyHostToDevice, stream));
         }
         QH_HIP(hipMemcpyAsync(ap_prm + ch, &q, sizeof(q), hipMemcpyHostToDevice, stream));
-        c.ap_dirty = false;
+        c.w.ap_dirty = false;
         up = true;
     }
     if (up) QH_HIP(hipStreamSynchronize(stream));
@@ -1518,8 +1489,7 @@ int Engine::refresh_ap(const ChainCall &k)
 int Engine::ssql_alloc()
 {
     const double rate = (double)dsp_rate;
-    if (int rc = alloc(ssql_list_block, 2LL * nch)) return rc;
-    for (int b = 0; b < 2; b++) ssql_lists[b].dev = ssql_list_block + (size_t)nch * b;
+    if (int rc = list_make(ssql_lists)) return rc;
     if (int rc = alloc(ssql_prm, nch)) return rc;
     if (int rc = alloc(ssql_state, nch)) return rc;
     SsqlState z{};                                  // calc_ssql (ssql.c:133-140): all zero but the trigger voltage, MUTED
@@ -1541,7 +1511,7 @@ int Engine::ssql_alloc()
     QH_HIP(hipStreamSynchronize(stream));
     ssql_prm_h.assign((size_t)nch, SsqlParam{});
     ssql_L = 0;
-    for (ChanCfg &c : cfg) c.ssql_dirty = true;
+    for (ChanCfg &c : cfg) c.w.ssql_dirty = true;
     return QH_OK;
 }
 
@@ -1600,14 +1570,14 @@ int Engine::refresh_ssql(const ChainCall &k)
     bool up = false;
     for (int ch = 0; ch < nch; ch++) {
         ChanCfg &c = cfg[(size_t)ch];
-        if (!c.ssql_dirty && !(nss && L != ssql_L && c.ssql_on())) continue;
+        if (!c.w.ssql_dirty && !(nss && L != ssql_L && c.ssql_on())) continue;
         SsqlParam &q = ssql_prm_h[(size_t)ch];
         q = base;
         q.wthresh = c.ssql_wthresh;
         q.mute_mult = 1.0 - std::exp(-1.0 / (rate * c.ssql_tau_mute));            // ssql.c:137-138, :339-370
         q.unmute_mult = 1.0 - std::exp(-1.0 / (rate * c.ssql_tau_unmute));
         QH_HIP(hipMemcpyAsync(ssql_prm + ch, &q, sizeof(q), hipMemcpyHostToDevice, stream));
-        c.ssql_dirty = false;
+        c.w.ssql_dirty = false;
         up = true;
     }
     if (up) QH_HIP(hipStreamSynchronize(stream));
@@ -1619,8 +1589,7 @@ int Engine::refresh_ssql(const ChainCall &k)
 int Engine::fmsq_alloc()
 {
     const double rate = (double)dsp_rate;
-    if (int rc = alloc(fq_list_block, 3LL * nch)) return rc;
-    fq_list.dev = fq_list_block; fq_pairs.dev = fq_list_block + (size_t)nch;
+    if (int rc = list_make(fq_lists)) return rc;
     if (int rc = alloc(fq_prm, nch)) return rc;
     if (int rc = alloc(fq_state, nch)) return rc;
     if (int rc = fc_alloc(fc[FC_FQ])) return rc;
@@ -1648,13 +1617,13 @@ int Engine::fmsq_alloc()
     QH_HIP(hipMemcpyAsync(fq_cdown, down.data(), down.size() * sizeof(double), hipMemcpyHostToDevice, stream));
     QH_HIP(hipStreamSynchronize(stream));
     fq_nc_built = 0;
-    for (ChanCfg &c : cfg) c.fmsq_dirty = true;
+    for (ChanCfg &c : cfg) c.w.fmsq_dirty = true;
     return QH_OK;
 }
 
 int Engine::prm_fmsq(ChanCfg &c, int ch)
 {
-    if (!fq_prm || !c.fmsq_dirty) return QH_OK;
+    if (!fq_prm || !c.w.fmsq_dirty) return QH_OK;
     // calc_fmsq, fmsq.c:48-53 with avtau 0.001, longtau 0.100, min_tail 0, max_tail 1.2 (RXA.c:225-226,231-232)
     const double rate = (double)dsp_rate;
     FmsqParam q{};
@@ -1663,7 +1632,7 @@ int Engine::prm_fmsq(ChanCfg &c, int ch)
     q.tail_thresh = c.fmsq_tail_thresh; q.unmute_thresh = c.fmsq_unmute_thresh; q.min_tail = 0.000; q.max_tail = 1.200;
     q.rate = rate; q.ntup = fq_ntup; q.ntdown = fq_ntdown;
     if (int rc = put_row(fq_prm, ch, q)) return rc;
-    c.fmsq_dirty = false;
+    c.w.fmsq_dirty = false;
     return QH_OK;
 }
 
@@ -1674,8 +1643,8 @@ int Engine::prm_fmsq(ChanCfg &c, int ch)
 // sqrt(2 (yr^2 + yi^2)): the residue enters in second order (tests/test_design_eq_host.py holds it under 1e-12 of the noise's RMS).
 int Engine::fmsq_filter()
 {
-    if (!fq_prm || !fq_list.n) return QH_OK;
-    const ChanCfg &c = cfg[(size_t)fq_h[0]];        // (chain_needs has refused FMSQ channels that differ)
+    if (!fq_prm || !fq_lists[0].n) return QH_OK;
+    const ChanCfg &c = cfg[(size_t)fq_lists.h[0][0]];        // (chain_needs has refused FMSQ channels that differ)
     if (c.fmsq_nc == fq_nc_built && c.fmsq_mp == fq_mp_built && fq_key_built == mask_key()) return QH_OK;
     std::vector<cd> h = fmsq_impulse(c.fmsq_nc, (double)dsp_rate, 1.0 / (2.0 * dsp_size));
     if (c.fmsq_mp) h = mp_imp(h, 16, 0);
@@ -1701,10 +1670,9 @@ std::vector<cd> Engine::eqp_taps(const ChanCfg &c) const
 int Engine::eqp_alloc()
 {
     if (int rc = quiesce()) return rc;
-    if (int rc = alloc(eq_list_block, 2LL * nch)) return rc;
-    eq_list.dev = eq_list_block; eq_rest.dev = eq_list_block + (size_t)nch;
+    if (int rc = list_make(eq_lists)) return rc;
     if (int rc = fc_alloc(fc[FC_EQP])) return rc;
-    for (ChanCfg &c : cfg) { c.eqp_dirty = true; c.eqp_flush = false; }
+    for (ChanCfg &c : cfg) { c.w.eqp_dirty = true; c.w.eqp_flush = false; }
     return QH_OK;
 }
 
@@ -1715,32 +1683,30 @@ int Engine::refresh_eqp()
 {
     Fircore &eq = fc[FC_EQP];
     if (eq_lists_dirty) {
-        eq_h.clear(); eq_rest_h.clear();
-        for (int ch = 0; ch < nch; ch++) (cfg[(size_t)ch].eqp_run ? eq_h : eq_rest_h).push_back(ch);
-        if (!eq_h.empty() && !eq.mask) if (int rc = eqp_alloc()) return rc;
-        eq_list.n = (int)eq_h.size(); eq_rest.n = eq.mask ? (int)eq_rest_h.size() : 0;
+        eq_lists.clear();
+        for (int ch = 0; ch < nch; ch++) eq_lists.h[cfg[(size_t)ch].eqp_run ? 0 : 1].push_back(ch);
+        if (!eq_lists.h[0].empty() && !eq.mask) if (int rc = eqp_alloc()) return rc;
+        eq_lists.count();
+        if (!eq.mask) eq_lists.row[1].n = 0;
         if (eq.mask) {
-            if (int rc = fc_follow(eq, eq_h)) return rc;
-            std::vector<int> all((size_t)nch * 2, 0);
-            std::copy(eq_h.begin(), eq_h.end(), all.begin());
-            std::copy(eq_rest_h.begin(), eq_rest_h.end(), all.begin() + (size_t)nch);
-            QH_HIP(hipMemcpyAsync(eq_list_block, all.data(), all.size() * sizeof(int), hipMemcpyHostToDevice, stream));
+            if (int rc = fc_follow(eq, eq_lists.h[0])) return rc;
+            if (int rc = list_upload(eq_lists)) return rc;
             QH_HIP(hipStreamSynchronize(stream));
         }
         eq_lists_dirty = false;
     }
     if (!eq.mask) return QH_OK;
-    if (eq_key_built != mask_key()) { for (ChanCfg &c : cfg) c.eqp_dirty = true; eq_key_built = mask_key(); }
+    if (eq_key_built != mask_key()) { for (ChanCfg &c : cfg) c.w.eqp_dirty = true; eq_key_built = mask_key(); }
     std::vector<cd> last_h, last, last_taps;
     const ChanCfg *last_cfg = nullptr;
     if (eq_taps_h.size() != (size_t)nch) eq_taps_h.assign((size_t)nch, std::vector<cd>());
     for (int ch = 0; ch < nch; ch++) {
         ChanCfg &c = cfg[(size_t)ch];
-        if (c.eqp_flush) {
+        if (c.w.eqp_flush) {
             if (int rc = zero_rows(eq, ch)) return rc;
-            c.eqp_flush = false;
+            c.w.eqp_flush = false;
         }
-        if (!c.eqp_run || !c.eqp_dirty) continue;       // (a channel that does not run keeps eqp_dirty until it does)
+        if (!c.eqp_run || !c.w.eqp_dirty) continue;       // (a channel that does not run keeps eqp_dirty until it does)
         const bool same = last_cfg && last_cfg->eqp_nc == c.eqp_nc && last_cfg->eqp_mp == c.eqp_mp && last_cfg->eqp_ctfmode == c.eqp_ctfmode &&
                           last_cfg->eqp_wintype == c.eqp_wintype && last_cfg->eqp_F == c.eqp_F && last_cfg->eqp_G == c.eqp_G;
         if (!same) {
@@ -1751,7 +1717,7 @@ int Engine::refresh_eqp()
         }
         if (int rc = put_taps(eq, ch, last_h, last)) return rc;
         eq_taps_h[(size_t)ch] = last_taps;
-        c.eqp_dirty = false;
+        c.w.eqp_dirty = false;
     }
     return QH_OK;
 }
@@ -1777,15 +1743,15 @@ int Engine::flush()
             QH_HIP(hipMemsetAsync(agc_state[c].ring, 0, sizeof(agc_state[c].ring), stream));
             QH_HIP(hipMemsetAsync(agc_state[c].abs_ring, 0, sizeof(agc_state[c].abs_ring), stream));
             QH_HIP(hipMemsetAsync(&agc_state[c].ring_max, 0, sizeof(double), stream));
-            if (cfg[(size_t)c].agc_stale) lists_dirty = true;
-            cfg[(size_t)c].agc_stale = false;     // an empty ring and ring_max = 0: nothing stale (qh_agc_tiled.hpp)
+            if (cfg[(size_t)c].w.agc_stale) lists_dirty = true;
+            cfg[(size_t)c].w.agc_stale = false;     // an empty ring and ring_max = 0: nothing stale (qh_agc_tiled.hpp)
         }
         if (agc_lring) {
             QH_HIP(hipMemsetAsync(agc_lring, 0, (size_t)nch * kAgcLongRing * sizeof(double2), stream));
             QH_HIP(hipMemsetAsync(agc_labs, 0, (size_t)nch * kAgcLongRing * sizeof(double), stream));
         }
     }
-    for (ChanCfg &c : cfg) { c.lms[0].flush = c.lms[1].flush = true; c.emnr_flush = true; c.snba_flush = true; }    // flush_anf / flush_anr / flush_emnr, RXA.c:541-543
+    for (ChanCfg &c : cfg) { c.w.lms[0].flush = c.w.lms[1].flush = true; c.w.emnr_flush = true; c.w.snba_flush = true; }    // flush_anf / flush_anr / flush_emnr, RXA.c:541-543
     if (amsq_state) QH_HIP(hipMemsetAsync(amsq_state, 0, (size_t)nch * sizeof(AmsqState), stream));     // flush_amsq
     if (ap_state) QH_HIP(hipMemsetAsync(ap_state, 0, (size_t)nch * kApW * sizeof(double), stream));    // flush_cbl / _speak / _mpeak, RXA.c:553-555
     if (ssql_state) launch_ssql_flush();        // flush_ssql, RXA.c:556
@@ -1832,8 +1798,8 @@ int Engine::set_rates(int new_in, int new_dsp, int new_out, int new_size)
         if (c.emnr_run && new_size > kEmnrIncr) return set_error(QH_ERR_UNSUPPORTED, "EMNR: dsp_size up to %d", kEmnrIncr);
         if (c.snba_run && !snba_accepts(new_dsp, new_size)) return set_error(QH_ERR_UNSUPPORTED, "%s", snba_accepted());
     }
-    if (disp && qh_ana_buff_size(disp) != new_size)
-        return set_error(QH_ERR_INVALID, "the attached display bank has buff_size %d: detach it before dsp_size becomes %d", qh_ana_buff_size(disp), new_size);
+    if (wide.disp && qh_ana_buff_size(wide.disp) != new_size)
+        return set_error(QH_ERR_INVALID, "the attached display bank has buff_size %d: detach it before dsp_size becomes %d", qh_ana_buff_size(wide.disp), new_size);
     QH_HIP(hipSetDevice(device));
     if (new_dsp != dsp_rate || new_size != dsp_size) return rebuild(new_in, new_dsp, new_out, new_size, new_D);
     if (int rc = quiesce()) return rc;
@@ -1843,7 +1809,7 @@ int Engine::set_rates(int new_in, int new_dsp, int new_out, int new_size)
         if (int rc = tile_lds_limits()) return rc;
         QH_HIP(hipMemsetAsync(nco_phase, 0, (size_t)nch * sizeof(unsigned long long), stream));         // setSamplerate_shift, shift.c:93-98
         QH_HIP(hipMemsetAsync(nco_parked, 0, (size_t)nch * sizeof(unsigned long long), stream));
-        for (ChanCfg &c : cfg) c.nco_dirty = true;          // calc_shift: delta is per sample of the new rate
+        for (ChanCfg &c : cfg) c.w.nco_dirty = true;          // calc_shift: delta is per sample of the new rate
     }
     if (new_out != out_rate) {      // setOutputSamplerate_rxa, RXA.c:616-625
         out_rate = new_out;
@@ -1854,35 +1820,20 @@ int Engine::set_rates(int new_in, int new_dsp, int new_out, int new_size)
 }
 
 // A channel's settings as a setter list replayed on a fresh engine would leave them: every value kept, every note of work pending or
-// done (dirty, flush, what is on the device) as ChanCfg() has it.
+// done (ChanCfg::Work) as ChanCfg() has it.
 static ChanCfg settings_of(const ChanCfg &o, int dsp_rate)
 {
-    // a member added to ChanCfg is a setting (kept by the copy below) or a note of work (to be put back to its default here): this
-    // reminder fails to compile until its author has looked
-    static_assert(sizeof(ChanCfg) == 920, "ChanCfg changed: see to settings_of, then update the size");
     ChanCfg c = o;
-    const ChanCfg d;
-    c.shift_on_device = d.shift_on_device;
-    c.agc_dirty = d.agc_dirty; c.agc_abuf = d.agc_abuf; c.agc_rewindow = d.agc_rewindow; c.agc_ran = d.agc_ran; c.agc_stale = d.agc_stale;
-    for (int f = 0; f < 2; f++) { c.lms[f].dirty = d.lms[f].dirty; c.lms[f].flush = d.lms[f].flush; }
-    c.snba_flush = d.snba_flush; c.snba_taps_dirty = d.snba_taps_dirty; c.snba_rout_flush = d.snba_rout_flush; c.snb_dirty = d.snb_dirty; c.snb_flush = d.snb_flush;
-    c.snba_f_low = d.snba_f_low; c.snba_f_high = d.snba_f_high;     // calc_snba makes outresamp with its creation arguments (snb.c:43-44)
-    c.emnr_dirty = d.emnr_dirty; c.emnr_flush = d.emnr_flush; c.amsq_dirty = d.amsq_dirty;
-    c.demod_dirty = d.demod_dirty; c.ctcss_flush = d.ctcss_flush;
-    c.nbp_dirty = d.nbp_dirty; c.bp1_dirty = d.bp1_dirty; c.nco_dirty = d.nco_dirty; c.epi_dirty = d.epi_dirty; c.nbp_flush = d.nbp_flush; c.bp1_flush = d.bp1_flush;
-    c.ap_dirty = d.ap_dirty; c.sp_flush = d.sp_flush;
-    for (int i = 0; i < kApPeaks; i++) c.mp_flush[i] = d.mp_flush[i];
-    c.ssql_dirty = d.ssql_dirty; c.fmsq_dirty = d.fmsq_dirty; c.lim_dirty = d.lim_dirty;
-    c.fm_de_flush = d.fm_de_flush; c.fm_aud_flush = d.fm_aud_flush;
-    c.eqp_dirty = d.eqp_dirty; c.eqp_flush = d.eqp_flush; c.eqp_tie = eqp_profile_tie(c.eqp_F, c.eqp_G, (double)dsp_rate);
-    c.gen_dirty = d.gen_dirty; c.gen_sweep_dirty = d.gen_sweep_dirty; c.gen_tone_reset = d.gen_tone_reset; c.gen_sweep_reset = d.gen_sweep_reset;
+    c.w = ChanCfg::Work();
+    c.snba_f_low = ChanCfg().snba_f_low; c.snba_f_high = ChanCfg().snba_f_high;     // calc_snba makes outresamp with its creation arguments (snb.c:43-44)
+    c.w.eqp_tie = eqp_profile_tie(c.eqp_F, c.eqp_G, (double)dsp_rate);
     return c;
 }
 
 // A new dsp_rate or dsp_size (setDSPSamplerate_rxa, setDSPBuffsize_rxa: RXA.c:627-740).  The engine is destroyed and constructed again
 // where it stands -- same handle, lock, stream, device and channel count -- so every buffer goes through alloc() and `owned` again and
-// every stage starts as create_rxa leaves it.  Carried over: the channels' settings (settings_of) and the engine-wide ones, and of the
-// state
+// every stage starts as create_rxa leaves it.  Carried over: the channels' settings (settings_of: all of ChanCfg but its Work) and the
+// engine-wide ones (Engine::Wide), and of the state
 //   dsp_rate alone   the delay lines of nbp0, bp1, eqp and xfmd's two filters, where the stage holds its one-tile form (nc <= 4096; a
 //                    partitioned stage's 65535-sample line is not carried and starts from zero: a stated deviation);
 //                    the SAM detector's sideband chains (init_amd leaves them)
@@ -1933,28 +1884,22 @@ int Engine::rebuild(int new_in, int new_dsp, int new_out, int new_size, int new_
     }
     std::vector<ChanCfg> keep_cfg;
     for (const ChanCfg &c : cfg) keep_cfg.push_back(settings_of(c, new_dsp));
-    // the engine-wide settings: one Engine member set through the C ABI outside cfg that is not listed here is lost by a rebuild
-    static_assert(sizeof(Engine) == 9360, "Engine changed: see to Engine::rebuild's Wide and carried state, then update the size");
-    struct Wide {
-        int device, nch; hipStream_t stream; bool own_stream; unsigned long long epoch;
-        bool graph_on; long long graph_launches; bool timing, meters_on; int band_tile_pref, snba_ovrlp, snba_form; std::vector<SnbaTune> snba_tune_h;
-        qh_ana *disp; int disp_ss, pll_check_only, agc_form;
-        bool emnr_tables; std::vector<double> h_GG, h_GGS, h_zeta; std::vector<int> h_zeta_true; double h_zrange[4];
-    } was{ device, nch, stream, own_stream, epoch, graph_on, graph_launches, timing, meters_on, band_tile_pref, snba_ovrlp, snba_form, snba_tune_h,
-           disp, disp_ss, pll_check_only, agc_form, emnr_tables, std::move(h_GG), std::move(h_GGS), std::move(h_zeta), std::move(h_zeta_true),
-           { h_zrange[0], h_zrange[1], h_zrange[2], h_zrange[3] } };
+    // the engine-wide settings (Engine::Wide) as a whole, and by hand the engine's identity and its count of replayed calls
+    Wide was = std::move(wide);
+    const int was_device = device, was_nch = nch;
+    const hipStream_t was_stream = stream;
+    const bool was_own_stream = own_stream;
+    const unsigned long long was_epoch = epoch;
+    const long long was_launches = graph_launches;
     own_stream = false;                     // the stream stays: callers hold it (qh_rxa_stream)
     this->~Engine();
     new (this) Engine();
-    device = was.device; nch = was.nch; stream = was.stream; own_stream = was.own_stream; epoch = was.epoch + 1;
+    device = was_device; nch = was_nch; stream = was_stream; own_stream = was_own_stream; epoch = was_epoch + 1;
     in_rate = new_in; dsp_rate = new_dsp; out_rate = new_out; dsp_size = new_size; D = new_D;
     int rc = init();
-    graph_on = was.graph_on; graph_launches = was.graph_launches; timing = was.timing; meters_on = was.meters_on;
-    band_tile_pref = was.band_tile_pref; snba_ovrlp = was.snba_ovrlp; snba_tune_h = was.snba_tune_h; snba_tune_dirty = true;
-    snba_form = was.snba_form;
-    disp = was.disp; disp_ss = was.disp_ss; pll_check_only = was.pll_check_only; agc_form = was.agc_form;
-    emnr_tables = was.emnr_tables; h_GG = std::move(was.h_GG); h_GGS = std::move(was.h_GGS); h_zeta = std::move(was.h_zeta); h_zeta_true = std::move(was.h_zeta_true);
-    std::copy(was.h_zrange, was.h_zrange + 4, h_zrange);
+    wide = std::move(was);
+    graph_launches = was_launches;
+    snba_tune_dirty = true;
     carry = std::move(keep);
     if (!rc) {
         cfg = keep_cfg;

@@ -86,14 +86,14 @@ static void bp1_check_set(ChanCfg &c, int amd_run, int anf_run, int anr_run, int
     if (emnr_run < 0) emnr_run = c.emnr_run;
     if (snba_run < 0) snba_run = c.snba_run;
     const double gain = (amd_run || anf_run || anr_run || emnr_run || snba_run) ? 2.0 : 1.0;
-    if (c.bp1_gain != gain) { c.bp1_gain = gain; c.bp1_dirty = true; }
+    if (c.bp1_gain != gain) { c.bp1_gain = gain; c.w.bp1_dirty = true; }
 }
 static void bp1_set(ChanCfg &c)
 {
     const int old = c.bp1_run;
     c.bp1_run = (c.amd_run || c.lms[0].run || c.lms[1].run || c.emnr_run || c.snba_run) ? 1 : 0;
-    if (old != c.bp1_run) c.bp1_dirty = true;
-    if (!old && c.bp1_run) c.bp1_flush = true;
+    if (old != c.bp1_run) c.w.bp1_dirty = true;
+    if (!old && c.bp1_run) c.w.bp1_flush = true;
 }
 
 int qh_rxa_SetRXAMode(qh_rxa *h, int ch, int mode)
@@ -108,8 +108,8 @@ int qh_rxa_SetRXAMode(qh_rxa *h, int ch, int mode)
             else if (mode == QH_SAM) { c.amd_run = 1; c.amd_mode = 1; }
             else if (mode == QH_FM) { c.fmd_run = 1; c.agc_run = 0; }
             bp1_set(c);
-            c.snb_dirty = true;
-            c.epi_dirty = true;
+            c.w.snb_dirty = true;
+            c.w.epi_dirty = true;
             h->e.lists_dirty = true;
         }
     });
@@ -124,7 +124,7 @@ int qh_rxa_SetRXAAMDRun(qh_rxa *h, int ch, int run)
             bp1_check_set(c, run, c.lms[0].run, c.lms[1].run);
             c.amd_run = run;
             bp1_set(c);
-            c.epi_dirty = true;
+            c.w.epi_dirty = true;
             h->e.lists_dirty = true;
         }
     });
@@ -133,14 +133,14 @@ int qh_rxa_SetRXAAMDRun(qh_rxa *h, int ch, int run)
 int qh_rxa_SetRXABandpassFreqs(qh_rxa *h, int ch, double f_low, double f_high)
 {
     FOR_CH(h, ch, {
-        if (f_low != c.bp1_flow || f_high != c.bp1_fhigh) { c.bp1_flow = f_low; c.bp1_fhigh = f_high; c.bp1_dirty = true; }
+        if (f_low != c.bp1_flow || f_high != c.bp1_fhigh) { c.bp1_flow = f_low; c.bp1_fhigh = f_high; c.w.bp1_dirty = true; }
     });
 }
 
 int qh_rxa_RXANBPSetFreqs(qh_rxa *h, int ch, double flow, double fhigh)
 {
     FOR_CH(h, ch, {
-        if (flow != c.nbp_flow || fhigh != c.nbp_fhigh) { c.nbp_flow = flow; c.nbp_fhigh = fhigh; c.nbp_dirty = true; }
+        if (flow != c.nbp_flow || fhigh != c.nbp_fhigh) { c.nbp_flow = flow; c.nbp_fhigh = fhigh; c.w.nbp_dirty = true; }
     });
 }
 
@@ -172,8 +172,8 @@ int qh_rxa_SetRXASNBAOutputBandwidth(qh_rxa *h, int ch, double flow, double fhig
         }
         if (f_low != c.snba_f_low || f_high != c.snba_f_high) {     // setBandwidth_resample rebuilds the filter and clears its ring
             c.snba_f_low = f_low; c.snba_f_high = f_high;
-            c.snba_taps_dirty = true; c.snba_rout_flush = true;
-            c.epi_dirty = true;
+            c.w.snba_taps_dirty = true; c.w.snba_rout_flush = true;
+            c.w.epi_dirty = true;
         }
     });
 }
@@ -185,7 +185,7 @@ static int snba_tune_set(qh_rxa *h, int ch, const char *who, bool ok, void (*app
     if (!ok) return set_error(QH_ERR_INVALID, "%s: value out of range", who);
     QH_RXA_LOCK(h);
     if (ch < -1 || ch >= h->e.nch) return set_error(QH_ERR_INVALID, "channel out of range");
-    for (int c = ch < 0 ? 0 : ch; c < (ch < 0 ? h->e.nch : ch + 1); c++) apply(h->e.snba_tune_h[(size_t)c], v);
+    for (int c = ch < 0 ? 0 : ch; c < (ch < 0 ? h->e.nch : ch + 1); c++) apply(h->e.wide.snba_tune_h[(size_t)c], v);
     h->e.snba_tune_dirty = true;
     h->e.drop_graphs(); h->e.epoch++;
     return QH_OK;
@@ -218,7 +218,7 @@ int qh_rxa_SetRXASNBAovrlp(qh_rxa *h, int ch, int ovrlp)
     if (int rc = h->e.snba_set_ovrlp(ovrlp)) return rc;
     // calc_snba makes the output resampler anew with its creation arguments: fc_low 200, the default cut-off (snb.c:45-46) -- what
     // SetRXASNBAOutputBandwidth had set is gone, as in WDSP
-    for (ChanCfg &c : h->e.cfg) { c.snba_f_low = 200.0; c.snba_f_high = 0.0; c.snba_taps_dirty = true; }
+    for (ChanCfg &c : h->e.cfg) { c.snba_f_low = 200.0; c.snba_f_high = 0.0; c.w.snba_taps_dirty = true; }
     return QH_OK;
 }
 
@@ -231,8 +231,8 @@ int qh_rxa_SetRXASNBARun(qh_rxa *h, int ch, int run)
             bp1_check_set(c, c.amd_run, c.lms[0].run, c.lms[1].run, -1, run);
             c.snba_run = run;
             bp1_set(c);
-            c.snb_dirty = true;
-            c.epi_dirty = true;
+            c.w.snb_dirty = true;
+            c.w.epi_dirty = true;
             h->e.lists_dirty = true;
         }
     });
@@ -246,6 +246,15 @@ int qh_rxa_RXASetPassband(qh_rxa *h, int ch, double f_low, double f_high)
     return qh_rxa_RXANBPSetFreqs(h, ch, f_low, f_high);
 }
 
+// What every fircore's nc setter takes: a power of two in [dsp_size, kLongNcMax].  who: the setter's name, heading the message of its
+// QH_ERR_INVALID; none: RXASetNC and SetRXAFMSQNC, which answer QH_ERR_UNSUPPORTED.
+static int nc_check(const qh_rxa *h, const char *who, int nc)
+{
+    if (nc >= 1 && !(nc & (nc - 1)) && nc <= kLongNcMax && !(h && nc < h->e.dsp_size)) return QH_OK;
+    if (!who) return set_error(QH_ERR_UNSUPPORTED, "nc must be a power of two in [dsp_size, %d]", kLongNcMax);
+    return set_error(QH_ERR_INVALID, "%s: nc must be a power of two in [dsp_size, %d]", who, kLongNcMax);
+}
+
 // xfmd's de-emphasis and audio filters, per channel (fmd.c:278-384).  Each acts only on a changed value, as there; the design rows follow
 // at the next process call (Engine::fm_filters).  which: 0 the de-emphasis filter, 1 the audio filter.
 static void fm_set_nc(Engine &e, ChanCfg &c, int which, int nc)
@@ -254,7 +263,7 @@ static void fm_set_nc(Engine &e, ChanCfg &c, int which, int nc)
     if (cur == nc) return;
     cur = nc;
     // setNc_fircore zeroes that filter's delay line (firmin.c:455-467): nothing long is held any more
-    (which ? c.fm_aud_flush : c.fm_de_flush) = true;
+    (which ? c.w.fm_aud_flush : c.w.fm_de_flush) = true;
     e.fc[which ? FC_AUD : FC_DE].chan[(size_t)(&c - e.cfg.data())].long_live = false;
     e.fm_dirty = true;
     if (!which) e.lists_dirty = true;       // the de-emphasis stage's channel pairs follow the designs
@@ -267,20 +276,14 @@ static void fm_set_mp(Engine &e, ChanCfg &c, int which, int mp)
     e.fm_dirty = true;
     if (!which) e.lists_dirty = true;
 }
-static int fm_nc_check(const qh_rxa *h, const char *who, int nc)
-{
-    if (nc < 1 || (nc & (nc - 1)) || nc > kLongNcMax || (h && nc < h->e.dsp_size))
-        return set_error(QH_ERR_INVALID, "%s: nc must be a power of two in [dsp_size, %d]", who, kLongNcMax);
-    return QH_OK;
-}
 int qh_rxa_SetRXAFMNCde(qh_rxa *h, int ch, int nc)
 {
-    if (int rc = fm_nc_check(h, "SetRXAFMNCde", nc)) return rc;
+    if (int rc = nc_check(h, "SetRXAFMNCde", nc)) return rc;
     FOR_CH(h, ch, { fm_set_nc(h->e, c, 0, nc); });
 }
 int qh_rxa_SetRXAFMNCaud(qh_rxa *h, int ch, int nc)
 {
-    if (int rc = fm_nc_check(h, "SetRXAFMNCaud", nc)) return rc;
+    if (int rc = nc_check(h, "SetRXAFMNCaud", nc)) return rc;
     FOR_CH(h, ch, { fm_set_nc(h->e, c, 1, nc); });
 }
 int qh_rxa_SetRXAFMMPde(qh_rxa *h, int ch, int mp) { FOR_CH(h, ch, { fm_set_mp(h->e, c, 0, mp ? 1 : 0); }); }
@@ -318,8 +321,8 @@ static void band_set_nc(Engine &e, ChanCfg &c, int which, int nc)
     int &cur = which == FC_NBP ? c.nbp_nc : which == FC_SNB ? c.snb_nc : c.bp1_nc;
     if (cur == nc) return;
     cur = nc;
-    (which == FC_NBP ? c.nbp_dirty : which == FC_SNB ? c.snb_dirty : c.bp1_dirty) = true;
-    (which == FC_NBP ? c.nbp_flush : which == FC_SNB ? c.snb_flush : c.bp1_flush) = true;
+    (which == FC_NBP ? c.w.nbp_dirty : which == FC_SNB ? c.w.snb_dirty : c.w.bp1_dirty) = true;
+    (which == FC_NBP ? c.w.nbp_flush : which == FC_SNB ? c.w.snb_flush : c.w.bp1_flush) = true;
     e.fc[which].chan[(size_t)(&c - e.cfg.data())].long_live = false;
 }
 static void band_set_mp(ChanCfg &c, int which, int mp)
@@ -327,27 +330,21 @@ static void band_set_mp(ChanCfg &c, int which, int mp)
     int &cur = which == FC_NBP ? c.nbp_mp : which == FC_SNB ? c.snb_mp : c.bp1_mp;
     if (cur == mp) return;
     cur = mp;
-    (which == FC_NBP ? c.nbp_dirty : which == FC_SNB ? c.snb_dirty : c.bp1_dirty) = true;
-}
-static int band_nc_check(const qh_rxa *h, const char *who, int nc)
-{
-    if (nc < 1 || (nc & (nc - 1)) || nc > kLongNcMax || (h && nc < h->e.dsp_size))
-        return set_error(QH_ERR_INVALID, "%s: nc must be a power of two in [dsp_size, %d]", who, kLongNcMax);
-    return QH_OK;
+    (which == FC_NBP ? c.w.nbp_dirty : which == FC_SNB ? c.w.snb_dirty : c.w.bp1_dirty) = true;
 }
 int qh_rxa_RXANBPSetNC(qh_rxa *h, int ch, int nc)
 {
-    if (int rc = band_nc_check(h, "RXANBPSetNC", nc)) return rc;
+    if (int rc = nc_check(h, "RXANBPSetNC", nc)) return rc;
     FOR_CH(h, ch, { band_set_nc(h->e, c, FC_NBP, nc); });
 }
 int qh_rxa_RXABPSNBASetNC(qh_rxa *h, int ch, int nc)
 {
-    if (int rc = band_nc_check(h, "RXABPSNBASetNC", nc)) return rc;
+    if (int rc = nc_check(h, "RXABPSNBASetNC", nc)) return rc;
     FOR_CH(h, ch, { band_set_nc(h->e, c, FC_SNB, nc); });
 }
 int qh_rxa_SetRXABandpassNC(qh_rxa *h, int ch, int nc)
 {
-    if (int rc = band_nc_check(h, "SetRXABandpassNC", nc)) return rc;
+    if (int rc = nc_check(h, "SetRXABandpassNC", nc)) return rc;
     FOR_CH(h, ch, { band_set_nc(h->e, c, FC_BP1, nc); });
 }
 int qh_rxa_RXANBPSetMP(qh_rxa *h, int ch, int mp) { FOR_CH(h, ch, { band_set_mp(c, FC_NBP, mp ? 1 : 0); }); }
@@ -357,19 +354,18 @@ int qh_rxa_SetRXABandpassMP(qh_rxa *h, int ch, int mp) { FOR_CH(h, ch, { band_se
 int qh_rxa_SetRXABandpassWindow(qh_rxa *h, int ch, int wintype)
 {
     if (wintype != 0 && wintype != 1) return set_error(QH_ERR_INVALID, "SetRXABandpassWindow: wintype %d (0 or 1)", wintype);
-    FOR_CH(h, ch, { if (c.bp1_wintype != wintype) { c.bp1_wintype = wintype; c.bp1_dirty = true; } });
+    FOR_CH(h, ch, { if (c.bp1_wintype != wintype) { c.bp1_wintype = wintype; c.w.bp1_dirty = true; } });
 }
 
 int qh_rxa_RXASetNC(qh_rxa *h, int ch, int nc)
 {
-    if (nc < 1 || (nc & (nc - 1)) || nc > kLongNcMax || (h && nc < h->e.dsp_size))
-        return set_error(QH_ERR_UNSUPPORTED, "nc must be a power of two in [dsp_size, %d]", kLongNcMax);
+    if (int rc = nc_check(h, nullptr, nc)) return rc;
     FOR_CH(h, ch, {
         // RXANBPSetNC, RXABPSNBASetNC, SetRXABandpassNC, wdsp/RXA.c:938-940
         band_set_nc(h->e, c, FC_NBP, nc); band_set_nc(h->e, c, FC_SNB, nc); band_set_nc(h->e, c, FC_BP1, nc);
         fm_set_nc(h->e, c, 0, nc); fm_set_nc(h->e, c, 1, nc);       // SetRXAFMNCde / SetRXAFMNCaud, wdsp/RXA.c:943-944
         c.fmsq_nc = nc;                         // SetRXAFMSQNC, wdsp/RXA.c:942
-        if (c.eqp_nc != nc) { c.eqp_nc = nc; c.eqp_dirty = true; c.eqp_flush = true; }      // SetRXAEQNC, wdsp/RXA.c:941
+        if (c.eqp_nc != nc) { c.eqp_nc = nc; c.w.eqp_dirty = true; c.w.eqp_flush = true; }      // SetRXAEQNC, wdsp/RXA.c:941
     });
 }
 
@@ -388,7 +384,7 @@ int qh_rxa_RXANBPAddNotch(qh_rxa *h, int ch, int notch, double fcenter, double f
     FOR_CH(h, ch, {
         if (notch >= 0 && notch <= (int)c.notches.size() && c.notches.size() < 1024) {
             c.notches.insert(c.notches.begin() + notch, mk_notch(fcenter, fwidth, active));
-            if (c.fnfrun) c.nbp_dirty = true;
+            if (c.fnfrun) c.w.nbp_dirty = true;
             if (rval) *rval = 0;
         } else if (rval) *rval = -1;
     });
@@ -400,7 +396,7 @@ int qh_rxa_RXANBPDeleteNotch(qh_rxa *h, int ch, int notch, int *rval)
     FOR_CH(h, ch, {
         if (notch >= 0 && notch < (int)c.notches.size()) {
             c.notches.erase(c.notches.begin() + notch);
-            if (c.fnfrun) c.nbp_dirty = true;
+            if (c.fnfrun) c.w.nbp_dirty = true;
             if (rval) *rval = 0;
         } else if (rval) *rval = -1;
     });
@@ -412,7 +408,7 @@ int qh_rxa_RXANBPEditNotch(qh_rxa *h, int ch, int notch, double fcenter, double 
     FOR_CH(h, ch, {
         if (notch >= 0 && notch < (int)c.notches.size()) {
             c.notches[(size_t)notch] = mk_notch(fcenter, fwidth, active);
-            if (c.fnfrun) c.nbp_dirty = true;
+            if (c.fnfrun) c.w.nbp_dirty = true;
             if (rval) *rval = 0;
         } else if (rval) *rval = -1;
     });
@@ -447,11 +443,11 @@ int qh_rxa_RXANBPGetMinNotchWidth(qh_rxa *h, int ch, double *minwidth)
     return QH_OK;
 }
 
-int qh_rxa_RXANBPSetTuneFrequency(qh_rxa *h, int ch, double f) { FOR_CH(h, ch, { if (f != c.ndb_tunefreq) { c.ndb_tunefreq = f; if (c.fnfrun) c.nbp_dirty = true; } }); }
-int qh_rxa_RXANBPSetShiftFrequency(qh_rxa *h, int ch, double f) { FOR_CH(h, ch, { if (f != c.ndb_shift) { c.ndb_shift = f; if (c.fnfrun) c.nbp_dirty = true; } }); }
-int qh_rxa_RXANBPSetNotchesRun(qh_rxa *h, int ch, int run) { FOR_CH(h, ch, { run = run ? 1 : 0; if (run != c.fnfrun) { c.fnfrun = run; c.nbp_dirty = true; } }); }
-int qh_rxa_RXANBPSetWindow(qh_rxa *h, int ch, int wintype) { FOR_CH(h, ch, { if (c.nbp_wintype != wintype) { c.nbp_wintype = wintype; c.nbp_dirty = true; } }); }
-int qh_rxa_RXANBPSetAutoIncrease(qh_rxa *h, int ch, int autoincr) { FOR_CH(h, ch, { if (c.autoincr != autoincr) { c.autoincr = autoincr; if (c.fnfrun) c.nbp_dirty = true; } }); }
+int qh_rxa_RXANBPSetTuneFrequency(qh_rxa *h, int ch, double f) { FOR_CH(h, ch, { if (f != c.ndb_tunefreq) { c.ndb_tunefreq = f; if (c.fnfrun) c.w.nbp_dirty = true; } }); }
+int qh_rxa_RXANBPSetShiftFrequency(qh_rxa *h, int ch, double f) { FOR_CH(h, ch, { if (f != c.ndb_shift) { c.ndb_shift = f; if (c.fnfrun) c.w.nbp_dirty = true; } }); }
+int qh_rxa_RXANBPSetNotchesRun(qh_rxa *h, int ch, int run) { FOR_CH(h, ch, { run = run ? 1 : 0; if (run != c.fnfrun) { c.fnfrun = run; c.w.nbp_dirty = true; } }); }
+int qh_rxa_RXANBPSetWindow(qh_rxa *h, int ch, int wintype) { FOR_CH(h, ch, { if (c.nbp_wintype != wintype) { c.nbp_wintype = wintype; c.w.nbp_dirty = true; } }); }
+int qh_rxa_RXANBPSetAutoIncrease(qh_rxa *h, int ch, int autoincr) { FOR_CH(h, ch, { if (c.autoincr != autoincr) { c.autoincr = autoincr; if (c.fnfrun) c.w.nbp_dirty = true; } }); }
 
 // RXASetMP (wdsp/RXA.c:948-958): minimum-phase impulse responses in every fircore of the channel's chain.
 int qh_rxa_RXASetMP(qh_rxa *h, int ch, int mp)
@@ -462,33 +458,33 @@ int qh_rxa_RXASetMP(qh_rxa *h, int ch, int mp)
         band_set_mp(c, FC_NBP, mp); band_set_mp(c, FC_SNB, mp); band_set_mp(c, FC_BP1, mp);
         fm_set_mp(h->e, c, 0, mp); fm_set_mp(h->e, c, 1, mp);       // SetRXAFMMPde / SetRXAFMMPaud, wdsp/RXA.c:956-957
         c.fmsq_mp = mp;                         // SetRXAFMSQMP, wdsp/RXA.c:955
-        if (c.eqp_mp != mp) { c.eqp_mp = mp; c.eqp_dirty = true; }      // SetRXAEQMP, wdsp/RXA.c:954
+        if (c.eqp_mp != mp) { c.eqp_mp = mp; c.w.eqp_dirty = true; }      // SetRXAEQMP, wdsp/RXA.c:954
     });
 }
 
-int qh_rxa_SetRXAShiftRun(qh_rxa *h, int ch, int run) { FOR_CH(h, ch, { c.shift_run = run; c.nco_dirty = true; }); }
-int qh_rxa_SetRXAShiftFreq(qh_rxa *h, int ch, double f) { FOR_CH(h, ch, { c.shift_freq = f; c.nco_dirty = true; }); }
-int qh_rxa_RXANBPSetRun(qh_rxa *h, int ch, int run) { FOR_CH(h, ch, { if (c.nbp_run != run) { c.nbp_run = run; c.nbp_dirty = true; } }); }
+int qh_rxa_SetRXAShiftRun(qh_rxa *h, int ch, int run) { FOR_CH(h, ch, { c.shift_run = run; c.w.nco_dirty = true; }); }
+int qh_rxa_SetRXAShiftFreq(qh_rxa *h, int ch, double f) { FOR_CH(h, ch, { c.shift_freq = f; c.w.nco_dirty = true; }); }
+int qh_rxa_RXANBPSetRun(qh_rxa *h, int ch, int run) { FOR_CH(h, ch, { if (c.nbp_run != run) { c.nbp_run = run; c.w.nbp_dirty = true; } }); }
 // (bandpass.c:385-390 writes the flag and nothing else; where a fixed AGC gain is applied -- at the AGC's own spot or in the output matrix --
 // depends on it: fix_before)
-int qh_rxa_SetRXABandpassRun(qh_rxa *h, int ch, int run) { FOR_CH(h, ch, { if (c.bp1_run != run) { c.bp1_run = run; c.bp1_dirty = true; c.epi_dirty = true; h->e.lists_dirty = true; } }); }
-int qh_rxa_SetRXAAMDSBMode(qh_rxa *h, int ch, int sbmode) { FOR_CH(h, ch, { c.sbmode = sbmode; c.demod_dirty = true; }); }
-int qh_rxa_SetRXAAMDFadeLevel(qh_rxa *h, int ch, int levelfade) { FOR_CH(h, ch, { c.levelfade = levelfade; c.demod_dirty = true; }); }
-int qh_rxa_SetRXAFMDeviation(qh_rxa *h, int ch, double deviation) { FOR_CH(h, ch, { c.fm_dev = deviation; c.demod_dirty = true; }); }
-int qh_rxa_SetRXACTCSSFreq(qh_rxa *h, int ch, double freq) { FOR_CH(h, ch, { c.ctcss_freq = freq; c.demod_dirty = true; c.ctcss_flush = true; }); }
-int qh_rxa_SetRXACTCSSRun(qh_rxa *h, int ch, int run) { FOR_CH(h, ch, { c.ctcss_run = run; c.demod_dirty = true; }); }
+int qh_rxa_SetRXABandpassRun(qh_rxa *h, int ch, int run) { FOR_CH(h, ch, { if (c.bp1_run != run) { c.bp1_run = run; c.w.bp1_dirty = true; c.w.epi_dirty = true; h->e.lists_dirty = true; } }); }
+int qh_rxa_SetRXAAMDSBMode(qh_rxa *h, int ch, int sbmode) { FOR_CH(h, ch, { c.sbmode = sbmode; c.w.demod_dirty = true; }); }
+int qh_rxa_SetRXAAMDFadeLevel(qh_rxa *h, int ch, int levelfade) { FOR_CH(h, ch, { c.levelfade = levelfade; c.w.demod_dirty = true; }); }
+int qh_rxa_SetRXAFMDeviation(qh_rxa *h, int ch, double deviation) { FOR_CH(h, ch, { c.fm_dev = deviation; c.w.demod_dirty = true; }); }
+int qh_rxa_SetRXACTCSSFreq(qh_rxa *h, int ch, double freq) { FOR_CH(h, ch, { c.ctcss_freq = freq; c.w.demod_dirty = true; c.w.ctcss_flush = true; }); }
+int qh_rxa_SetRXACTCSSRun(qh_rxa *h, int ch, int run) { FOR_CH(h, ch, { c.ctcss_run = run; c.w.demod_dirty = true; }); }
 // SetRXAFMLimRun / SetRXAFMLimGain (wdsp/fmd.c:336-362): the FM detector's limiter
 int qh_rxa_SetRXAFMLimRun(qh_rxa *h, int ch, int run) { FOR_CH(h, ch, { run = run ? 1 : 0; if (c.lim_run != run) { c.lim_run = run; h->e.lists_dirty = true; } }); }
 int qh_rxa_SetRXAFMLimGain(qh_rxa *h, int ch, double gaindB)
 {
     const double gain = std::pow(10.0, gaindB / 20.0);
-    FOR_CH(h, ch, { if (c.lim_gain != gain) { c.lim_gain = gain; c.lim_dirty = true; } });
+    FOR_CH(h, ch, { if (c.lim_gain != gain) { c.lim_gain = gain; c.w.lim_dirty = true; } });
 }
 
 // SetRXAEMNRRun ... SetRXAEMNRPosition, wdsp/emnr.c:1096-1143
 int qh_rxa_SetRXAEMNRRun(qh_rxa *h, int ch, int run)
 {
-    if (h && run && !h->e.emnr_tables)
+    if (h && run && !h->e.wide.emnr_tables)
         return set_error(QH_ERR_INVALID, "EMNR needs its gain tables first (qh_rxa_SetEMNRTables: WDSP's `calculus` and `zetaHat.bin` data)");
     if (h && run && h->e.dsp_size > kEmnrIncr) return set_error(QH_ERR_UNSUPPORTED, "EMNR: dsp_size up to %d", kEmnrIncr);
     FOR_CH(h, ch, {
@@ -497,21 +493,21 @@ int qh_rxa_SetRXAEMNRRun(qh_rxa *h, int ch, int run)
             bp1_check_set(c, c.amd_run, c.lms[0].run, c.lms[1].run, run);
             c.emnr_run = run;
             bp1_set(c);
-            c.epi_dirty = true;
+            c.w.epi_dirty = true;
             h->e.lists_dirty = true;
         }
     });
 }
-int qh_rxa_SetRXAEMNRgainMethod(qh_rxa *h, int ch, int method) { FOR_CH(h, ch, { c.emnr_gain_method = method; c.emnr_dirty = true; }); }
-int qh_rxa_SetRXAEMNRnpeMethod(qh_rxa *h, int ch, int method) { FOR_CH(h, ch, { c.emnr_npe = method; c.emnr_dirty = true; }); }
-int qh_rxa_SetRXAEMNRaeRun(qh_rxa *h, int ch, int run) { FOR_CH(h, ch, { c.emnr_ae = run ? 1 : 0; c.emnr_dirty = true; }); }
-int qh_rxa_SetRXAEMNRaeZetaThresh(qh_rxa *h, int ch, double v) { FOR_CH(h, ch, { c.emnr_ae_zeta = v; c.emnr_dirty = true; }); }       // emnr.c:1145
-int qh_rxa_SetRXAEMNRaePsi(qh_rxa *h, int ch, double v) { FOR_CH(h, ch, { c.emnr_ae_psi = v; c.emnr_dirty = true; }); }               // emnr.c:1153
-int qh_rxa_SetRXAEMNRtrainZetaThresh(qh_rxa *h, int ch, double v) { FOR_CH(h, ch, { c.emnr_train_zeta = v; c.emnr_dirty = true; }); }  // emnr.c:1161
-int qh_rxa_SetRXAEMNRtrainT2(qh_rxa *h, int ch, double v) { FOR_CH(h, ch, { c.emnr_train_t2 = v; c.emnr_dirty = true; }); }            // emnr.c:1169
+int qh_rxa_SetRXAEMNRgainMethod(qh_rxa *h, int ch, int method) { FOR_CH(h, ch, { c.emnr_gain_method = method; c.w.emnr_dirty = true; }); }
+int qh_rxa_SetRXAEMNRnpeMethod(qh_rxa *h, int ch, int method) { FOR_CH(h, ch, { c.emnr_npe = method; c.w.emnr_dirty = true; }); }
+int qh_rxa_SetRXAEMNRaeRun(qh_rxa *h, int ch, int run) { FOR_CH(h, ch, { c.emnr_ae = run ? 1 : 0; c.w.emnr_dirty = true; }); }
+int qh_rxa_SetRXAEMNRaeZetaThresh(qh_rxa *h, int ch, double v) { FOR_CH(h, ch, { c.emnr_ae_zeta = v; c.w.emnr_dirty = true; }); }       // emnr.c:1145
+int qh_rxa_SetRXAEMNRaePsi(qh_rxa *h, int ch, double v) { FOR_CH(h, ch, { c.emnr_ae_psi = v; c.w.emnr_dirty = true; }); }               // emnr.c:1153
+int qh_rxa_SetRXAEMNRtrainZetaThresh(qh_rxa *h, int ch, double v) { FOR_CH(h, ch, { c.emnr_train_zeta = v; c.w.emnr_dirty = true; }); }  // emnr.c:1161
+int qh_rxa_SetRXAEMNRtrainT2(qh_rxa *h, int ch, double v) { FOR_CH(h, ch, { c.emnr_train_t2 = v; c.w.emnr_dirty = true; }); }            // emnr.c:1169
 int qh_rxa_SetRXAEMNRPosition(qh_rxa *h, int ch, int position)
 {
-    FOR_CH(h, ch, { c.emnr_pos = position ? 1 : 0; c.bp1_pos = position ? 1 : 0; c.epi_dirty = true; h->e.lists_dirty = true; });
+    FOR_CH(h, ch, { c.emnr_pos = position ? 1 : 0; c.bp1_pos = position ? 1 : 0; c.w.epi_dirty = true; h->e.lists_dirty = true; });
 }
 // The data WDSP reads at create time from the files `calculus` (GG, GGS: 241 x 241 each) and `zetaHat.bin` (60 x 60 values, validity
 // flags and their gamma / xi ranges in dB), emnr.c:206-238,317-334
@@ -522,10 +518,10 @@ int qh_rxa_SetEMNRTables(qh_rxa *h, const double *GG, const double *GGS, const d
     QH_RXA_LOCK(h);
     Engine &e = h->e;
     e.epoch++;
-    e.h_GG.assign(GG, GG + 241 * 241); e.h_GGS.assign(GGS, GGS + 241 * 241);
-    e.h_zeta.assign(zeta_hat, zeta_hat + 3600); e.h_zeta_true.assign(zeta_true, zeta_true + 3600);
-    e.h_zrange[0] = gamma_min; e.h_zrange[1] = gamma_max; e.h_zrange[2] = xi_min; e.h_zrange[3] = xi_max;
-    e.emnr_tables = true;
+    e.wide.h_GG.assign(GG, GG + 241 * 241); e.wide.h_GGS.assign(GGS, GGS + 241 * 241);
+    e.wide.h_zeta.assign(zeta_hat, zeta_hat + 3600); e.wide.h_zeta_true.assign(zeta_true, zeta_true + 3600);
+    e.wide.h_zrange[0] = gamma_min; e.wide.h_zrange[1] = gamma_max; e.wide.h_zrange[2] = xi_min; e.wide.h_zrange[3] = xi_max;
+    e.wide.emnr_tables = true;
     if (e.emnr_GG) {            // already on the device: refresh
         QH_HIP(hipSetDevice(e.device));
         QH_HIP(hipMemcpyAsync(e.emnr_GG, GG, 241 * 241 * 8, hipMemcpyHostToDevice, e.stream));
@@ -548,8 +544,8 @@ static int lms_run(qh_rxa *h, int ch, int which, int run)
             bp1_check_set(c, c.amd_run, which == 0 ? run : c.lms[0].run, which == 1 ? run : c.lms[1].run);
             m.run = run;
             bp1_set(c);
-            m.flush = true;
-            c.lms[0].dirty = c.lms[1].dirty = true; c.epi_dirty = true;
+            c.w.lms[which].flush = true;
+            c.w.lms[0].dirty = c.w.lms[1].dirty = true; c.w.epi_dirty = true;
             h->e.lists_dirty = true;
         }
     });
@@ -571,7 +567,7 @@ static int lms_vals(qh_rxa *h, int ch, int which, const int *taps, const int *de
             h->e.lists_dirty = true;
         if (gain) m.two_mu = *gain;
         if (leakage) m.gamma = *leakage;
-        m.flush = true; m.dirty = true;
+        c.w.lms[which].flush = c.w.lms[which].dirty = true;
     });
 }
 static int lms_position(qh_rxa *h, int ch, int which, int position)
@@ -579,8 +575,8 @@ static int lms_position(qh_rxa *h, int ch, int which, int position)
     FOR_CH(h, ch, {
         c.lms[which].position = position ? 1 : 0;
         c.bp1_pos = position ? 1 : 0;                 // "rxa[channel].bp1.p->position = position", anf.c:236
-        c.lms[which].flush = true;
-        c.lms[0].dirty = c.lms[1].dirty = true; c.epi_dirty = true;
+        c.w.lms[which].flush = true;
+        c.w.lms[0].dirty = c.w.lms[1].dirty = true; c.w.epi_dirty = true;
         h->e.lists_dirty = true;
     });
 }
@@ -588,9 +584,9 @@ static int lms_position(qh_rxa *h, int ch, int which, int position)
 int qh_rxa_SetRXAAMSQRun(qh_rxa *h, int ch, int run) { FOR_CH(h, ch, { c.amsq_run = run ? 1 : 0; h->e.lists_dirty = true; }); }
 int qh_rxa_SetRXAAMSQThreshold(qh_rxa *h, int ch, double threshold)
 {
-    FOR_CH(h, ch, { const double t = std::pow(10.0, threshold / 20.0); c.amsq_tail_thresh = 0.9 * t; c.amsq_unmute_thresh = t; c.amsq_dirty = true; });
+    FOR_CH(h, ch, { const double t = std::pow(10.0, threshold / 20.0); c.amsq_tail_thresh = 0.9 * t; c.amsq_unmute_thresh = t; c.w.amsq_dirty = true; });
 }
-int qh_rxa_SetRXAAMSQMaxTail(qh_rxa *h, int ch, double tail) { FOR_CH(h, ch, { c.amsq_max_tail = tail < 0.0 ? 0.0 : tail; c.amsq_dirty = true; }); }
+int qh_rxa_SetRXAAMSQMaxTail(qh_rxa *h, int ch, double tail) { FOR_CH(h, ch, { c.amsq_max_tail = tail < 0.0 ? 0.0 : tail; c.w.amsq_dirty = true; }); }
 int qh_rxa_SetRXAANFRun(qh_rxa *h, int ch, int run) { return lms_run(h, ch, 0, run); }
 int qh_rxa_SetRXAANRRun(qh_rxa *h, int ch, int run) { return lms_run(h, ch, 1, run); }
 int qh_rxa_SetRXAANFVals(qh_rxa *h, int ch, int taps, int delay, double gain, double leakage) { return lms_vals(h, ch, 0, &taps, &delay, &gain, &leakage); }
@@ -617,19 +613,19 @@ int qh_rxa_SetRXAAGCMode(qh_rxa *h, int ch, int mode)
         case 4: c.agc_mode = 4; c.agc_hang_thresh = 1.0; c.agc_hangtime = 0.000; c.agc_tau_decay = 0.050; break;
         default: c.agc_mode = 5; break;
         }
-        c.epi_dirty = true; c.agc_dirty = true; c.lms[0].dirty = c.lms[1].dirty = true; h->e.lists_dirty = true;
+        c.w.epi_dirty = true; c.w.agc_dirty = true; c.w.lms[0].dirty = c.w.lms[1].dirty = true; h->e.lists_dirty = true;
     });
 }
-int qh_rxa_SetRXAAGCAttack(qh_rxa *h, int ch, int attack_ms) { FOR_CH(h, ch, { c.agc_tau_attack = (double)attack_ms / 1000.0; c.agc_dirty = true; }); }
-int qh_rxa_SetRXAAGCDecay(qh_rxa *h, int ch, int decay_ms) { FOR_CH(h, ch, { c.agc_tau_decay = (double)decay_ms / 1000.0; c.agc_dirty = true; }); }
-int qh_rxa_SetRXAAGCHang(qh_rxa *h, int ch, int hang_ms) { FOR_CH(h, ch, { c.agc_hangtime = (double)hang_ms / 1000.0; c.agc_dirty = true; }); }
-int qh_rxa_SetRXAAGCTop(qh_rxa *h, int ch, double max_agc_db) { FOR_CH(h, ch, { c.agc_max_gain = std::pow(10.0, max_agc_db / 20.0); c.agc_dirty = true; }); }
-int qh_rxa_SetRXAAGCSlope(qh_rxa *h, int ch, int slope) { FOR_CH(h, ch, { c.agc_var_gain = std::pow(10.0, (double)slope / 20.0 / 10.0); c.agc_dirty = true; }); }
-int qh_rxa_SetRXAAGCHangThreshold(qh_rxa *h, int ch, int t) { FOR_CH(h, ch, { c.agc_hang_thresh = (double)t / 100.0; c.agc_dirty = true; }); }
+int qh_rxa_SetRXAAGCAttack(qh_rxa *h, int ch, int attack_ms) { FOR_CH(h, ch, { c.agc_tau_attack = (double)attack_ms / 1000.0; c.w.agc_dirty = true; }); }
+int qh_rxa_SetRXAAGCDecay(qh_rxa *h, int ch, int decay_ms) { FOR_CH(h, ch, { c.agc_tau_decay = (double)decay_ms / 1000.0; c.w.agc_dirty = true; }); }
+int qh_rxa_SetRXAAGCHang(qh_rxa *h, int ch, int hang_ms) { FOR_CH(h, ch, { c.agc_hangtime = (double)hang_ms / 1000.0; c.w.agc_dirty = true; }); }
+int qh_rxa_SetRXAAGCTop(qh_rxa *h, int ch, double max_agc_db) { FOR_CH(h, ch, { c.agc_max_gain = std::pow(10.0, max_agc_db / 20.0); c.w.agc_dirty = true; }); }
+int qh_rxa_SetRXAAGCSlope(qh_rxa *h, int ch, int slope) { FOR_CH(h, ch, { c.agc_var_gain = std::pow(10.0, (double)slope / 20.0 / 10.0); c.w.agc_dirty = true; }); }
+int qh_rxa_SetRXAAGCHangThreshold(qh_rxa *h, int ch, int t) { FOR_CH(h, ch, { c.agc_hang_thresh = (double)t / 100.0; c.w.agc_dirty = true; }); }
 
 int qh_rxa_SetRXAAGCFixed(qh_rxa *h, int ch, double db)
 {
-    FOR_CH(h, ch, { c.agc_fixed = std::pow(10.0, db / 20.0); c.epi_dirty = true; c.lms[0].dirty = c.lms[1].dirty = true; });
+    FOR_CH(h, ch, { c.agc_fixed = std::pow(10.0, db / 20.0); c.w.epi_dirty = true; c.w.lms[0].dirty = c.w.lms[1].dirty = true; });
 }
 
 // ---- the AGC's display-side knobs (wcpAGC.c:440-557): host arithmetic on what loadWcpAGC derives (wcpAGC.c:115-146).  Every setter of
@@ -677,7 +673,7 @@ int qh_rxa_SetRXAAGCThresh(qh_rxa *h, int ch, double thresh, double size, double
         if (!std::isfinite(g) || g <= 0.0) return set_error(QH_ERR_INVALID, "SetRXAAGCThresh: thresh %g gives no finite gain", thresh);
         gain[(size_t)(i - lo)] = g;
     }
-    FOR_CH(h, ch, { c.agc_max_gain = gain[(size_t)(_i - _lo)]; c.agc_dirty = true; });
+    FOR_CH(h, ch, { c.agc_max_gain = gain[(size_t)(_i - _lo)]; c.w.agc_dirty = true; });
 }
 int qh_rxa_GetRXAAGCThresh(qh_rxa *h, int ch, double *thresh, double size, double rate)
 {
@@ -700,7 +696,7 @@ int qh_rxa_SetRXAAGCHangLevel(qh_rxa *h, int ch, double hang_level)
             const double tmp = std::max(1e-8, (convert - min_volts) / (c.agc_max_input - min_volts));
             c.agc_hang_thresh = 1.0 + 0.125 * std::log10(tmp);
         } else c.agc_hang_thresh = 1.0;
-        c.agc_dirty = true;
+        c.w.agc_dirty = true;
     });
 }
 int qh_rxa_GetRXAAGCHangLevel(qh_rxa *h, int ch, double *hang_level)
@@ -733,7 +729,7 @@ int qh_rxa_GetRXAAGCTop(qh_rxa *h, int ch, double *max_agc)
 int qh_rxa_SetRXAAGCMaxInputLevel(qh_rxa *h, int ch, double level)
 {
     if (!std::isfinite(level) || level <= 0.0) return set_error(QH_ERR_INVALID, "SetRXAAGCMaxInputLevel: level %g must be finite and above 0", level);
-    FOR_CH(h, ch, { c.agc_max_input = level; c.agc_dirty = true; });
+    FOR_CH(h, ch, { c.agc_max_input = level; c.w.agc_dirty = true; });
 }
 
 // xcbl / xspeak / xmpeak.  Run flags, npeaks and the enables do not flush (cblock.c:120-126, iir.c:322-330, :490-515); the design
@@ -744,24 +740,24 @@ static void ap_run_set(qh_rxa *h, ChanCfg &c, int &flag, int run)
     run = run ? 1 : 0;
     if (flag == run) return;
     flag = run;
-    c.ap_dirty = true; c.epi_dirty = true;          // fix_before() follows ap_on()
+    c.w.ap_dirty = true; c.w.epi_dirty = true;          // fix_before() follows ap_on()
     h->e.lists_dirty = true;
 }
 int qh_rxa_SetRXACBLRun(qh_rxa *h, int ch, int run) { FOR_CH(h, ch, { ap_run_set(h, c, c.cbl_run, run); }); }
 int qh_rxa_SetRXASPCWRun(qh_rxa *h, int ch, int run) { FOR_CH(h, ch, { ap_run_set(h, c, c.sp_run, run); }); }
-int qh_rxa_SetRXASPCWFreq(qh_rxa *h, int ch, double f) { FOR_CH(h, ch, { c.sp_f = f < 200.0 ? 200.0 : f; c.ap_dirty = true; c.sp_flush = true; }); }
-int qh_rxa_SetRXASPCWBandwidth(qh_rxa *h, int ch, double bw) { FOR_CH(h, ch, { c.sp_bw = bw; c.ap_dirty = true; c.sp_flush = true; }); }
-int qh_rxa_SetRXASPCWGain(qh_rxa *h, int ch, double g) { FOR_CH(h, ch, { c.sp_gain = g; c.ap_dirty = true; c.sp_flush = true; }); }
+int qh_rxa_SetRXASPCWFreq(qh_rxa *h, int ch, double f) { FOR_CH(h, ch, { c.sp_f = f < 200.0 ? 200.0 : f; c.w.ap_dirty = true; c.w.sp_flush = true; }); }
+int qh_rxa_SetRXASPCWBandwidth(qh_rxa *h, int ch, double bw) { FOR_CH(h, ch, { c.sp_bw = bw; c.w.ap_dirty = true; c.w.sp_flush = true; }); }
+int qh_rxa_SetRXASPCWGain(qh_rxa *h, int ch, double g) { FOR_CH(h, ch, { c.sp_gain = g; c.w.ap_dirty = true; c.w.sp_flush = true; }); }
 int qh_rxa_SetRXAmpeakRun(qh_rxa *h, int ch, int run) { FOR_CH(h, ch, { ap_run_set(h, c, c.mp_run, run); }); }
 int qh_rxa_SetRXAmpeakNpeaks(qh_rxa *h, int ch, int npeaks)
 {
     if (npeaks < 0 || npeaks > kApPeaks) return set_error(QH_ERR_INVALID, "SetRXAmpeakNpeaks: npeaks %d outside [0, %d]", npeaks, kApPeaks);
-    FOR_CH(h, ch, { if (c.mp_npeaks != npeaks) { c.mp_npeaks = npeaks; c.ap_dirty = true; } });
+    FOR_CH(h, ch, { if (c.mp_npeaks != npeaks) { c.mp_npeaks = npeaks; c.w.ap_dirty = true; } });
 }
 int qh_rxa_SetRXAmpeakFilEnable(qh_rxa *h, int ch, int fil, int enable)
 {
     if (fil < 0 || fil >= kApPeaks) return set_error(QH_ERR_INVALID, "SetRXAmpeakFilEnable: fil %d outside [0, %d)", fil, kApPeaks);
-    FOR_CH(h, ch, { enable = enable ? 1 : 0; if (c.mp_enable[fil] != enable) { c.mp_enable[fil] = enable; c.ap_dirty = true; } });
+    FOR_CH(h, ch, { enable = enable ? 1 : 0; if (c.mp_enable[fil] != enable) { c.mp_enable[fil] = enable; c.w.ap_dirty = true; } });
 }
 static int mpeak_design(qh_rxa *h, int ch, int fil, int what, double v)
 {
@@ -770,7 +766,7 @@ static int mpeak_design(qh_rxa *h, int ch, int fil, int what, double v)
         if (what == 0) c.mp_f[fil] = v < 200.0 ? 200.0 : v;
         else if (what == 1) c.mp_bw[fil] = v;
         else c.mp_gain[fil] = v;
-        c.ap_dirty = true; c.mp_flush[fil] = true;
+        c.w.ap_dirty = true; c.w.mp_flush[fil] = true;
     });
 }
 int qh_rxa_SetRXAmpeakFilFreq(qh_rxa *h, int ch, int fil, double f) { return mpeak_design(h, ch, fil, 0, f); }
@@ -784,23 +780,23 @@ int qh_rxa_SetRXASSQLRun(qh_rxa *h, int ch, int run)
 {
     FOR_CH(h, ch, {
         run = run ? 1 : 0;
-        if (c.ssql_run != run) { c.ssql_run = run; c.ssql_dirty = true; c.epi_dirty = true; h->e.lists_dirty = true; }   // fix_before() follows
+        if (c.ssql_run != run) { c.ssql_run = run; c.w.ssql_dirty = true; c.w.epi_dirty = true; h->e.lists_dirty = true; }   // fix_before() follows
     });
 }
 int qh_rxa_SetRXASSQLThreshold(qh_rxa *h, int ch, double threshold)
 {
     if (!std::isfinite(threshold)) return set_error(QH_ERR_INVALID, "SetRXASSQLThreshold: threshold %g is not finite", threshold);
-    FOR_CH(h, ch, { c.ssql_wthresh = threshold / 2.0; c.ssql_dirty = true; });
+    FOR_CH(h, ch, { c.ssql_wthresh = threshold / 2.0; c.w.ssql_dirty = true; });
 }
 int qh_rxa_SetRXASSQLTauMute(qh_rxa *h, int ch, double tau)
 {
     if (!std::isfinite(tau) || tau < 0.0) return set_error(QH_ERR_INVALID, "SetRXASSQLTauMute: tau %g is negative or not finite", tau);
-    FOR_CH(h, ch, { c.ssql_tau_mute = tau; c.ssql_dirty = true; });
+    FOR_CH(h, ch, { c.ssql_tau_mute = tau; c.w.ssql_dirty = true; });
 }
 int qh_rxa_SetRXASSQLTauUnMute(qh_rxa *h, int ch, double tau)
 {
     if (!std::isfinite(tau) || tau < 0.0) return set_error(QH_ERR_INVALID, "SetRXASSQLTauUnMute: tau %g is negative or not finite", tau);
-    FOR_CH(h, ch, { c.ssql_tau_unmute = tau; c.ssql_dirty = true; });
+    FOR_CH(h, ch, { c.ssql_tau_unmute = tau; c.w.ssql_dirty = true; });
 }
 
 // xfmsq (fmsq.c:235-279).  The noise filter's nc and mp are taken up at the next process call (one design for the engine's FMSQ
@@ -815,12 +811,11 @@ int qh_rxa_SetRXAFMSQRun(qh_rxa *h, int ch, int run)
 int qh_rxa_SetRXAFMSQThreshold(qh_rxa *h, int ch, double threshold)
 {
     if (!std::isfinite(threshold)) return set_error(QH_ERR_INVALID, "SetRXAFMSQThreshold: threshold %g is not finite", threshold);
-    FOR_CH(h, ch, { c.fmsq_tail_thresh = threshold; c.fmsq_unmute_thresh = 0.9 * threshold; c.fmsq_dirty = true; });
+    FOR_CH(h, ch, { c.fmsq_tail_thresh = threshold; c.fmsq_unmute_thresh = 0.9 * threshold; c.w.fmsq_dirty = true; });
 }
 int qh_rxa_SetRXAFMSQNC(qh_rxa *h, int ch, int nc)
 {
-    if (nc < 1 || (nc & (nc - 1)) || nc > kLongNcMax || (h && nc < h->e.dsp_size))
-        return set_error(QH_ERR_UNSUPPORTED, "nc must be a power of two in [dsp_size, %d]", kLongNcMax);
+    if (int rc = nc_check(h, nullptr, nc)) return rc;
     FOR_CH(h, ch, { c.fmsq_nc = nc; });
 }
 int qh_rxa_SetRXAFMSQMP(qh_rxa *h, int ch, int mp) { FOR_CH(h, ch, { c.fmsq_mp = mp ? 1 : 0; }); }
@@ -835,13 +830,12 @@ int qh_rxa_SetRXAEQRun(qh_rxa *h, int ch, int run)
 }
 int qh_rxa_SetRXAEQNC(qh_rxa *h, int ch, int nc)
 {
-    if (nc < 1 || (nc & (nc - 1)) || nc > kLongNcMax || (h && nc < h->e.dsp_size))
-        return set_error(QH_ERR_INVALID, "SetRXAEQNC: nc must be a power of two in [dsp_size, %d]", kLongNcMax);
-    FOR_CH(h, ch, { if (c.eqp_nc != nc) { c.eqp_nc = nc; c.eqp_dirty = true; c.eqp_flush = true; } });
+    if (int rc = nc_check(h, "SetRXAEQNC", nc)) return rc;
+    FOR_CH(h, ch, { if (c.eqp_nc != nc) { c.eqp_nc = nc; c.w.eqp_dirty = true; c.w.eqp_flush = true; } });
 }
 int qh_rxa_SetRXAEQMP(qh_rxa *h, int ch, int mp)
 {
-    FOR_CH(h, ch, { mp = mp ? 1 : 0; if (c.eqp_mp != mp) { c.eqp_mp = mp; c.eqp_dirty = true; } });
+    FOR_CH(h, ch, { mp = mp ? 1 : 0; if (c.eqp_mp != mp) { c.eqp_mp = mp; c.w.eqp_dirty = true; } });
 }
 static int eqp_set_profile(qh_rxa *h, int ch, int nfreqs, const double *F, const double *G, int ctfmode)
 {
@@ -855,13 +849,13 @@ static int eqp_set_profile(qh_rxa *h, int ch, int nfreqs, const double *F, const
     FOR_CH(h, ch, {
         c.eqp_F = f; c.eqp_G = g;
         if (ctfmode >= 0) c.eqp_ctfmode = ctfmode;
-        c.eqp_tie = eqp_profile_tie(f, g, (double)h->e.dsp_rate);
-        c.eqp_dirty = true;
+        c.w.eqp_tie = eqp_profile_tie(f, g, (double)h->e.dsp_rate);
+        c.w.eqp_dirty = true;
     });
 }
 int qh_rxa_SetRXAEQProfile(qh_rxa *h, int ch, int nfreqs, const double *F, const double *G) { return eqp_set_profile(h, ch, nfreqs, F, G, -1); }
-int qh_rxa_SetRXAEQCtfmode(qh_rxa *h, int ch, int mode) { FOR_CH(h, ch, { c.eqp_ctfmode = mode; c.eqp_dirty = true; }); }
-int qh_rxa_SetRXAEQWintype(qh_rxa *h, int ch, int wintype) { FOR_CH(h, ch, { c.eqp_wintype = wintype; c.eqp_dirty = true; }); }
+int qh_rxa_SetRXAEQCtfmode(qh_rxa *h, int ch, int mode) { FOR_CH(h, ch, { c.eqp_ctfmode = mode; c.w.eqp_dirty = true; }); }
+int qh_rxa_SetRXAEQWintype(qh_rxa *h, int ch, int wintype) { FOR_CH(h, ch, { c.eqp_wintype = wintype; c.w.eqp_dirty = true; }); }
 int qh_rxa_SetRXAGrphEQ(qh_rxa *h, int ch, const int *rxeq)
 {
     if (!rxeq) return set_error(QH_ERR_INVALID, "SetRXAGrphEQ: null pointer");
@@ -878,20 +872,20 @@ int qh_rxa_SetRXAGrphEQ10(qh_rxa *h, int ch, const int *rxeq)
     return eqp_set_profile(h, ch, 10, F, G, 0);
 }
 
-int qh_rxa_SetRXAPanelGain1(qh_rxa *h, int ch, double g) { FOR_CH(h, ch, { c.gain1 = g; c.epi_dirty = true; }); }
-int qh_rxa_SetRXAPanelGain2(qh_rxa *h, int ch, double gI, double gQ) { FOR_CH(h, ch, { c.gain2I = gI; c.gain2Q = gQ; c.epi_dirty = true; }); }
-int qh_rxa_SetRXAPanelSelect(qh_rxa *h, int ch, int s) { FOR_CH(h, ch, { c.inselect = s; c.epi_dirty = true; }); }
-int qh_rxa_SetRXAPanelCopy(qh_rxa *h, int ch, int cp) { FOR_CH(h, ch, { c.copy = cp; c.epi_dirty = true; }); }
+int qh_rxa_SetRXAPanelGain1(qh_rxa *h, int ch, double g) { FOR_CH(h, ch, { c.gain1 = g; c.w.epi_dirty = true; }); }
+int qh_rxa_SetRXAPanelGain2(qh_rxa *h, int ch, double gI, double gQ) { FOR_CH(h, ch, { c.gain2I = gI; c.gain2Q = gQ; c.w.epi_dirty = true; }); }
+int qh_rxa_SetRXAPanelSelect(qh_rxa *h, int ch, int s) { FOR_CH(h, ch, { c.inselect = s; c.w.epi_dirty = true; }); }
+int qh_rxa_SetRXAPanelCopy(qh_rxa *h, int ch, int cp) { FOR_CH(h, ch, { c.copy = cp; c.w.epi_dirty = true; }); }
 // SetRXAPanelPan (patchpanel.c:158-176): the fields SetRXAPanelGain2 writes, by the reference's sine law (its PI, comm.h:146)
 int qh_rxa_SetRXAPanelPan(qh_rxa *h, int ch, double pan)
 {
     if (!std::isfinite(pan)) return set_error(QH_ERR_INVALID, "SetRXAPanelPan: pan %g is not finite", pan);
     const double PI = 3.1415926535897932;
     const double gain1 = pan <= 0.5 ? 1.0 : std::sin(pan * PI), gain2 = pan <= 0.5 ? std::sin(pan * PI) : 1.0;
-    FOR_CH(h, ch, { c.gain2I = gain1; c.gain2Q = gain2; c.epi_dirty = true; });
+    FOR_CH(h, ch, { c.gain2I = gain1; c.gain2Q = gain2; c.w.epi_dirty = true; });
 }
 // SetRXAPanelBinaural (patchpanel.c:186-192)
-int qh_rxa_SetRXAPanelBinaural(qh_rxa *h, int ch, int bin) { FOR_CH(h, ch, { c.copy = 1 - bin; c.epi_dirty = true; }); }
+int qh_rxa_SetRXAPanelBinaural(qh_rxa *h, int ch, int bin) { FOR_CH(h, ch, { c.copy = 1 - bin; c.w.epi_dirty = true; }); }
 
 int qh_rxa_process(qh_rxa *h, const double *d_in, long long in_stride, double *d_out, long long out_stride, int nblk)
 {
@@ -900,7 +894,7 @@ int qh_rxa_process(qh_rxa *h, const double *d_in, long long in_stride, double *d
     if (!d_in || !d_out) return set_error(QH_ERR_INVALID, "null buffer");
     if (in_stride < (long long)nblk * h->e.dsp_insize || out_stride < (long long)nblk * h->e.dsp_outsize)
         return set_error(QH_ERR_INVALID, "stride shorter than nblk blocks");
-    return h->e.process_fed(h->e.graph_on, d_in, in_stride, d_out, out_stride, nblk);
+    return h->e.process_fed(h->e.wide.graph_on, d_in, in_stride, d_out, out_stride, nblk);
 }
 
 // ---- audio egress ---------------------------------------------------------------------------------------------------
@@ -963,7 +957,7 @@ int qh_rxa_set_graph_replay(qh_rxa *h, int on)
 {
     if (!h) return set_error(QH_ERR_INVALID, "null engine");
     QH_RXA_LOCK(h);
-    h->e.graph_on = on != 0;
+    h->e.wide.graph_on = on != 0;
     if (!on) { h->e.drop_graphs(); h->e.graph_key = Engine::GraphKey{}; }
     return QH_OK;
 }
@@ -973,7 +967,7 @@ int qh_rxa_set_band_tile(qh_rxa *h, int nfft)
 {
     if (!h || (nfft != 0 && nfft != 4096 && nfft != 6144 && nfft != 8192)) return set_error(QH_ERR_INVALID, "qh_rxa_set_band_tile: 0 (default), 4096, 6144 or 8192");
     QH_RXA_LOCK(h);
-    h->e.band_tile_pref = nfft;
+    h->e.wide.band_tile_pref = nfft;
     h->e.epoch++;                   // the next call picks the tile anew (pick_band_tile): a captured launch sequence runs the old one
     return QH_OK;
 }
@@ -983,11 +977,11 @@ int qh_rxa_set_snba_form(qh_rxa *h, int form)
 {
     if (!h || (form != 0 && form != 1)) return set_error(QH_ERR_INVALID, "qh_rxa_set_snba_form: 0 (default) or 1 (the three passes wherever they can run)");
     QH_RXA_LOCK(h);
-    h->e.snba_form = form;
+    h->e.wide.snba_form = form;
     h->e.epoch++;                   // a captured launch sequence runs the other form's kernels; the state is one layout for both
     return QH_OK;
 }
-int qh_rxa_snba_form(const qh_rxa *h) { return h ? h->e.snba_form : 0; }
+int qh_rxa_snba_form(const qh_rxa *h) { return h ? h->e.wide.snba_form : 0; }
 
 // The same chain fed with wire-format samples: the front kernel decodes them in its load.
 int qh_rxa_process_packed(qh_rxa *h, const void *d_src, long long src_bytes, const qh_iq_format *fmt, long long chan_stride,
@@ -1021,7 +1015,7 @@ int qh_rxa_flush(qh_rxa *h)
 // xsender's run && flag (sender.c:66-68) of channel ch, -1 = all: later calls leave the channel's signal behind nbp0 as float pairs
 int qh_rxa_set_sender(qh_rxa *h, int ch, int run)
 {
-    if (h && h->e.disp && !run) return set_error(QH_ERR_INVALID, "qh_rxa_set_sender: a display is attached (qh_rxa_attach_display), it reads every channel's rows");
+    if (h && h->e.wide.disp && !run) return set_error(QH_ERR_INVALID, "qh_rxa_set_sender: a display is attached (qh_rxa_attach_display), it reads every channel's rows");
     FOR_CH(h, ch, { run = run ? 1 : 0; if (c.sender_run != run) { c.sender_run = run; h->e.lists_dirty = true; } });
 }
 
@@ -1102,14 +1096,14 @@ int qh_rxa_attach_display(qh_rxa *h, qh_ana *a, int ss)
     if (!h) return set_error(QH_ERR_INVALID, "null engine");
     QH_RXA_LOCK(h);
     Engine &e = h->e;
-    if (!a) { e.disp = nullptr; return QH_OK; }
+    if (!a) { e.wide.disp = nullptr; return QH_OK; }
     if (qh_ana_ndisp(a) != e.nch || qh_ana_buff_size(a) != e.dsp_size || qh_ana_device(a) != e.device)
         return set_error(QH_ERR_INVALID, "qh_rxa_attach_display: the bank needs a display per channel (%d), buff_size = dsp_size (%d) and the engine's device",
                          e.nch, e.dsp_size);
     if (ss < 0 || ss >= qh_ana_num_stitch(a)) return set_error(QH_ERR_INVALID, "qh_rxa_attach_display: sub-span %d outside the bank's", ss);
     for (ChanCfg &c : e.cfg) if (!c.sender_run) { c.sender_run = 1; e.lists_dirty = true; }
     e.epoch++;
-    e.disp = a; e.disp_ss = ss;
+    e.wide.disp = a; e.wide.disp_ss = ss;
     return QH_OK;
 }
 
@@ -1118,30 +1112,30 @@ int qh_rxa_SetRXAPreGenRun(qh_rxa *h, int ch, int run)
 {
     FOR_CH(h, ch, { run = run ? 1 : 0; if (c.gen_run != run) { c.gen_run = run; h->e.lists_dirty = true; } });
 }
-int qh_rxa_SetRXAPreGenMode(qh_rxa *h, int ch, int mode) { FOR_CH(h, ch, { c.gen_mode = mode; c.gen_dirty = true; }); }
-int qh_rxa_SetRXAPreGenToneMag(qh_rxa *h, int ch, double mag) { FOR_CH(h, ch, { c.gen_tone_mag = mag; c.gen_dirty = true; }); }
+int qh_rxa_SetRXAPreGenMode(qh_rxa *h, int ch, int mode) { FOR_CH(h, ch, { c.gen_mode = mode; c.w.gen_dirty = true; }); }
+int qh_rxa_SetRXAPreGenToneMag(qh_rxa *h, int ch, double mag) { FOR_CH(h, ch, { c.gen_tone_mag = mag; c.w.gen_dirty = true; }); }
 // (calc_tone: the phase goes to 0, gen.c:31)
-int qh_rxa_SetRXAPreGenToneFreq(qh_rxa *h, int ch, double freq) { FOR_CH(h, ch, { c.gen_tone_freq = freq; c.gen_tone_reset = true; c.gen_dirty = true; }); }
-int qh_rxa_SetRXAPreGenNoiseMag(qh_rxa *h, int ch, double mag) { FOR_CH(h, ch, { c.gen_noise_mag = mag; c.gen_dirty = true; }); }
-int qh_rxa_SetRXAPreGenSweepMag(qh_rxa *h, int ch, double mag) { FOR_CH(h, ch, { c.gen_sweep_mag = mag; c.gen_dirty = true; }); }
+int qh_rxa_SetRXAPreGenToneFreq(qh_rxa *h, int ch, double freq) { FOR_CH(h, ch, { c.gen_tone_freq = freq; c.w.gen_tone_reset = true; c.w.gen_dirty = true; }); }
+int qh_rxa_SetRXAPreGenNoiseMag(qh_rxa *h, int ch, double mag) { FOR_CH(h, ch, { c.gen_noise_mag = mag; c.w.gen_dirty = true; }); }
+int qh_rxa_SetRXAPreGenSweepMag(qh_rxa *h, int ch, double mag) { FOR_CH(h, ch, { c.gen_sweep_mag = mag; c.w.gen_dirty = true; }); }
 // (calc_sweep: the phase goes to 0 and dphs back to its start, gen.c:51-52)
 int qh_rxa_SetRXAPreGenSweepFreq(qh_rxa *h, int ch, double freq1, double freq2)
 {
-    FOR_CH(h, ch, { c.gen_sweep_f1 = freq1; c.gen_sweep_f2 = freq2; c.gen_sweep_dirty = c.gen_sweep_reset = true; c.gen_dirty = true; });
+    FOR_CH(h, ch, { c.gen_sweep_f1 = freq1; c.gen_sweep_f2 = freq2; c.w.gen_sweep_dirty = c.w.gen_sweep_reset = true; c.w.gen_dirty = true; });
 }
 int qh_rxa_SetRXAPreGenSweepRate(qh_rxa *h, int ch, double rate)
 {
-    FOR_CH(h, ch, { c.gen_sweep_rate = rate; c.gen_sweep_dirty = c.gen_sweep_reset = true; c.gen_dirty = true; });
+    FOR_CH(h, ch, { c.gen_sweep_rate = rate; c.w.gen_sweep_dirty = c.w.gen_sweep_reset = true; c.w.gen_dirty = true; });
 }
 // The seed of the channel's noise stream (the default is a fixed function of the channel); the stream goes on from the sample it has reached
-int qh_rxa_set_gen_seed(qh_rxa *h, int ch, unsigned long long seed) { FOR_CH(h, ch, { c.gen_seed = seed; c.gen_seed_set = true; c.gen_dirty = true; }); }
+int qh_rxa_set_gen_seed(qh_rxa *h, int ch, unsigned long long seed) { FOR_CH(h, ch, { c.gen_seed = seed; c.gen_seed_set = true; c.w.gen_dirty = true; }); }
 
 // Meters (wdsp/meter.c): enable != 0 makes later process calls maintain the ADC, S and AGC meters.
 int qh_rxa_enable_meters(qh_rxa *h, int enable)
 {
     if (!h) return set_error(QH_ERR_INVALID, "null engine");
     QH_RXA_LOCK(h);
-    h->e.meters_on = enable != 0;
+    h->e.wide.meters_on = enable != 0;
     h->e.epoch++;                   // the meter launches join / leave the sequence
     return QH_OK;
 }
@@ -1153,7 +1147,7 @@ int qh_rxa_GetRXAMeter(qh_rxa *h, int ch, int mt, double *value)
     QH_RXA_LOCK(h);
     Engine &e = h->e;
     if (ch < 0 || ch >= e.nch || mt < 0 || mt > 6) return set_error(QH_ERR_INVALID, "channel or meter index out of range");
-    if (!e.meters_on || !e.m_adc) { *value = -400.0; return QH_OK; }             // flush_meter's initial reading
+    if (!e.wide.meters_on || !e.m_adc) { *value = -400.0; return QH_OK; }             // flush_meter's initial reading
     QH_HIP(hipSetDevice(e.device));
     QH_HIP(hipStreamSynchronize(e.stream));
     MeterState st;
@@ -1195,7 +1189,7 @@ int qh_rxa_debug_pll(qh_rxa *h, int check_only, int ch, double *out, int max)
     if (!h) return set_error(QH_ERR_INVALID, "null engine");
     QH_RXA_LOCK(h);
     Engine &e = h->e;
-    if (check_only >= 0) e.pll_check_only = check_only;
+    if (check_only >= 0) e.wide.pll_check_only = check_only;
     if (!out || max <= 0 || !e.pll_ends) return 0;
     QH_HIP(hipSetDevice(e.device));
     QH_HIP(hipStreamSynchronize(e.stream));
@@ -1280,7 +1274,7 @@ int qh_rxa_debug_agc(qh_rxa *h, int form)
 {
     if (!h) return set_error(QH_ERR_INVALID, "null engine");
     QH_RXA_LOCK(h);
-    if (h->e.agc_form != form) { h->e.agc_form = form; h->e.drop_graphs(); h->e.epoch++; }
+    if (h->e.wide.agc_form != form) { h->e.wide.agc_form = form; h->e.drop_graphs(); h->e.epoch++; }
     return QH_OK;
 }
 
@@ -1349,7 +1343,7 @@ int qh_rxa_enable_timing(qh_rxa *h, int enable)
 {
     if (!h) return set_error(QH_ERR_INVALID, "null engine");
     QH_RXA_LOCK(h);
-    h->e.timing = enable != 0;
+    h->e.wide.timing = enable != 0;
     return QH_OK;
 }
 

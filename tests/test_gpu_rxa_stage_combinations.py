@@ -48,17 +48,17 @@ CASES = [(s, n) for s in STAGES for n in NEIGHBOURS if not (s == "fmsq" and n.st
 ALL_ON = (("agc3",), ("agc1_hang", "amsq"), ("agc3", "emnr0", "anf1"))
 
 
-def _input(modes, n):
+def _input(modes, n, fs=FS):
     """what makes the squelches work: a hopping tone 0.15 s on, a steady one 0.2 s in between (syllabic); an FM carrier keyed 0.3 s high /
     0.22 s low over noise (keyed_fm_over_a_floor); each on its channel's carrier"""
-    t = np.arange(n) / FS
+    t = np.arange(n) / fs
     x = np.empty((len(modes), n), dtype=np.complex128)
     for c, m in enumerate(modes):
         car = np.exp(-2j * np.pi * ((synth.shift_freq(c) * t) % 1.0))
         if m == FM:
-            x[c] = keyed_fm_over_a_floor(n, FS, seed=3 + 4 * c) * car
+            x[c] = keyed_fm_over_a_floor(n, fs, seed=3 + 4 * c) * car
             continue
-        z = syllabic(n, FS, seed=40 + c, on=0.15, off=0.2, rest=1100.0)
+        z = syllabic(n, fs, seed=40 + c, on=0.15, off=0.2, rest=1100.0)
         x[c] = ((0.1 + 0.05 * z.real) if m == AM else 0.3 * (np.conj(z) if m == USB else z)) * car     # (USB: the input's negative side)
     return x
 
